@@ -15,9 +15,12 @@ The "e2e" object is BASELINE.json configs[3]: 128 synthetic pages through Detect
 (__call__ to __call__, PIL pages in, OCRResult out), STRONG scaling: with N > 1 every rank passes the same pages, detection
 shards pages and recognition shards lines over the ranks (surya_amd.dist: fingerprint check, one all_gather of the outputs).
 
-Prints ONE JSON line on rank 0 with the metric, plus
+Prints ONE JSON line on rank 0 with the metric. A plain run does only that: set-up, --warmup steps, --steps timed steps, the
+outputs of the last timed step (--dump-outputs DIR), the line. --full adds the rest to the line:
   roofline      event-timed GEMM launches of one extra (untimed) pass, dominant tile configuration
-  cpu_baseline  the CPU oracle (oracle/rec_oracle.py, a port of the reference's torch path) on a bounded sample
+  cpu_baseline  the CPU oracle (oracle/rec_oracle.py, a port of the reference's torch path) on a bounded sample, with parity
+  predictor_call, force_dist_check, detection, e2e, layout, table_rec, texify   the auxiliary legs (each has its --no-* switch)
+The --*-only profiling aids run their one leg with or without --full.
 """
 from __future__ import annotations
 
@@ -46,6 +49,10 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the roofline pass, the CPU baseline and parity checks and the auxiliary legs (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (tokens, scores, bboxes, lengths) to DIR/<name>.npy as float32")
     ap.add_argument("--config", default="REC-FULL")
     ap.add_argument("--lines", type=int, default=256, help="line crops per GPU per step")
     ap.add_argument("--batch", type=int, default=256, help="continuous-batching slots (RECOGNITION_BATCH_SIZE)")
@@ -1232,6 +1239,25 @@ def print_json(obj) -> None:
         data = data[os.write(_JSON_FD, data):]
 
 
+def dump_outputs(dirname, toks, boxes, scores, max_tokens) -> None:
+    """--dump-outputs: what a caller of the device loop receives from the last timed step, as dense float32 arrays in the workload's
+    line order: tokens [n, T] (-1 past a line's end), scores [n, T] and bboxes [n, T, 6] (0 past a line's end), lengths [n]."""
+    os.makedirs(dirname, exist_ok=True)
+    lens = np.array([len(t) for t in toks], np.int64)
+    T = max([max_tokens, *lens.tolist()])
+    tok = np.full((len(lens), T), -1, np.float32)
+    sc = np.zeros((len(lens), T), np.float32)
+    for i, (t, s) in enumerate(zip(toks, scores)):
+        tok[i, :len(t)] = t
+        sc[i, :len(s)] = s
+    bb = np.asarray(boxes, np.float32)
+    bbox = np.zeros((len(lens), T, 6), np.float32)
+    bbox[:, :bb.shape[1]] = bb[:, :T]
+    bbox[np.arange(T)[None, :] >= lens[:, None]] = 0
+    for name, a in (("tokens", tok), ("scores", sc), ("bboxes", bbox), ("lengths", lens.astype(np.float32))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -1338,19 +1364,23 @@ def main():
         score / bbox records over RCCL (north_star: "all-gather of token outputs over xGMI"), so each rank ends the step holding
         the results of all args.lines x world lines, as sharded_prediction_loop returns them."""
         toks, boxes, scores = pred.generate(prep, args.batch)
+        last[:] = [toks, boxes, scores]
         if dist_on:
             tg = time.perf_counter()
             b = boxes.numpy()
             if b.shape[1] < args.max_tokens:
                 b = np.pad(b, ((0, 0), (0, args.max_tokens - b.shape[1]), (0, 0)))
             ptoks, pscores = pred.last_packed            # generate()'s dense bookkeeping, as sharded_prediction_loop passes it
-            all_toks, _, _ = sdist.gather_line_outputs(ptoks, pscores, b, mine, n_global, args.max_tokens, device=coll_dev, stats=gather_stats)
+            all_toks, all_scores, all_boxes = sdist.gather_line_outputs(ptoks, pscores, b, mine, n_global, args.max_tokens, device=coll_dev,
+                                                                        stats=gather_stats)
+            last[:] = [all_toks, all_boxes, all_scores]  # every rank ends the step holding all lines: those are what it hands back
             assert len(all_toks) == n_global and int(all_toks.lens.min()) > 0
             gather_s[0] += time.perf_counter() - tg
             if world == 1:                              # forced one-rank group: the gathered records must be this rank's own (untimed check)
                 assert all_toks == toks, "all_gather_into_tensor returned different tokens"
         return toks
 
+    last = [None, None, None]                           # (tokens, bboxes, scores) of the latest step
     total_tokens = 0
     for _ in range(args.warmup):
         toks = step()
@@ -1383,6 +1413,8 @@ def main():
         devs = [None] * world
         dist.all_gather_object(devs, rank_devices[0])
         rank_devices = devs
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last, args.max_tokens)
 
     if args.host_profile and rank == 0:
         import cProfile, pstats
@@ -1396,7 +1428,7 @@ def main():
     # ---- roofline: one more pass with every GEMM launch bracketed by HIP events on its stream
     roof = None
     lib = L.lib()
-    if rank == 0:
+    if rank == 0 and args.full:
         lib.surya_prof_enable(1)
         pred.generate(prep, args.batch)
         cats = read_profile(lib, L)
@@ -1484,7 +1516,7 @@ def main():
             traceback.print_exc()
             return {"error": f"{name}: {type(e).__name__}: {str(e)[:300]}"}
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         r = leg("cpu_baseline", lambda: cpu_baseline(cfg, sd, prep, min(args.cpu_lines, args.lines), args.max_tokens, toks))
         out["cpu_baseline"], out["parity"] = r if isinstance(r, tuple) else (r, None)
         if args.lines == 256 and args.config == "REC-FULL" and args.max_tokens == 48:
@@ -1498,9 +1530,9 @@ def main():
                 out["parity"][key] = cp
             else:
                 out["parity"] = {key: cp}
-    if rank == 0 and world == 1 and not args.no_predictor_call:
+    if args.full and rank == 0 and world == 1 and not args.no_predictor_call:
         out["predictor_call"] = leg("predictor_call", lambda: bench_predictor_call(args, pred, cfg, sd, crops_u8))
-    if args.force_dist:
+    if args.full and args.force_dist:
         def sharded_call_check():
             """The product's sharded __call__ (fingerprint all_gather, shard deal, one all_gather_into_tensor of the records) on the forced
             one-rank group, against the plain call on the same 8 pages: identical OCRResults."""
@@ -1518,14 +1550,14 @@ def main():
             same = all(a.model_dump() == b.model_dump() for a, b in zip(plain, shard))
             return {"pages": len(imgs), "lines": sum(len(r.text_lines) for r in plain), "sharded_call_equals_plain_call": bool(same)}
         out["force_dist_check"] = leg("force_dist_check", sharded_call_check)
-    if not args.no_det:
+    if args.full and not args.no_det:
         out["detection"] = leg("detection", lambda: bench_det(args, local_rank, world, rank, barrier))
-    if not args.no_e2e:
+    if args.full and not args.no_e2e:
         out["e2e"] = leg("e2e", lambda: bench_e2e(args, pred, local_rank, world, rank, barrier))
-    if rank == 0 and world == 1 and not args.no_layout:
+    if args.full and rank == 0 and world == 1 and not args.no_layout:
         out["layout"] = leg("layout", lambda: bench_layout(args, local_rank))
         out["table_rec"] = leg("table_rec", lambda: bench_table(args, local_rank))
-    if rank == 0 and world == 1 and not args.no_texify:
+    if args.full and rank == 0 and world == 1 and not args.no_texify:
         del pred
         torch.cuda.empty_cache()
         out["texify"] = leg("texify", lambda: bench_texify(args, cfg, sd, local_rank))

@@ -175,9 +175,12 @@ def test_det_default_1024_oracle_matches_reference():
     sd = make_det_weights(cfg, 0)
     x = do.normalise_pages(make_pages(g["pages"], g["size"], seed=g["page_seed"])[g["page"]:g["page"] + 1])
     out = do.forward(sd, cfg, x)
-    assert torch.equal(out, g["logits"])
     up = do.heatmaps(sd, cfg, x)
-    assert torch.equal(up[:, :, ::4, ::4], g["upsampled_sample"])
+    # bit-identical where the CPU runs the fixture's convolution kernels; another CPU's oneDNN kernels sum the 1024^2
+    # convolutions in another order, a few float32 ulp on the [0, 1] maps (1.3e-6 with AVX2 kernels instead of AVX-512)
+    if not (torch.equal(out, g["logits"]) and torch.equal(up[:, :, ::4, ::4], g["upsampled_sample"])):
+        torch.testing.assert_close(out, g["logits"], rtol=0, atol=1e-5)
+        torch.testing.assert_close(up[:, :, ::4, ::4], g["upsampled_sample"], rtol=0, atol=1e-5)
 
 
 def test_host_assembly_and_tokenizer_match_reference_vectors():

@@ -406,6 +406,15 @@ def _page_polys(n_pages, seed):
     return out
 
 
+@pytest.fixture
+def host_only(monkeypatch):
+    """The fakes live on the host: the streamed call sees no GPU, on a GPU machine too (its detector thread would otherwise make
+    the fake model's "cpu" device the thread's current GPU)."""
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)
+
+
+@pytest.mark.usefixtures("host_only")
 @pytest.mark.parametrize("n_pages,det_batch,slots", [(9, 2, 4), (5, 5, 3), (12, 4, 32)])
 def test_streamed_call_orchestration_on_fakes(n_pages, det_batch, slots):
     """_call_streamed with a fake detector and the contract-checking fake model: producer thread, queue, chunk-local page indices,
@@ -433,6 +442,7 @@ def test_streamed_call_orchestration_on_fakes(n_pages, det_batch, slots):
         settings.RECOGNITION_STEPS_PER_SYNC, settings.RECOGNITION_ENCODE_AHEAD, settings.RECOGNITION_MAX_TOKENS = old
 
 
+@pytest.mark.usefixtures("host_only")
 def test_streamed_call_surfaces_a_producer_failure():
     old = (settings.RECOGNITION_ENCODE_AHEAD, settings.RECOGNITION_MAX_TOKENS)
     settings.RECOGNITION_ENCODE_AHEAD, settings.RECOGNITION_MAX_TOKENS = True, 12
