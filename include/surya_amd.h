@@ -242,6 +242,9 @@ int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, c
                              float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
                              int heads, int kv_heads, int max_kv_len, float scale, void* stream);
 
+/* bf16 split-K projection of the decode step (launch_gemm_splitk): raw fp32 partial sums to part[*splitk][M][N] (capacity 8 slabs), no
+ * epilogue; M <= 256 as the decoder runs it. */
+int surya_op_gemm_splitk_bf16(const void* X, long ldx, const void* W, long ldw, float* part, int M, int N, int K, int* splitk, void* stream);
 /* MXFP8 ops (csrc/gemm_mx.h). quantize: fp32 rows [rows][K], K % 128 == 0 -> e4m3 [rows][K] + e8m0 scales K-tile-major
  * [K / 128][rows][4], with the rule every producer kernel uses (block scale = smallest power of two that keeps absmax <=
  * 448, round to nearest even). gemm_mx: C[M,N] fp32 = X W^T from MXFP8 operands (scales K-tile-major with M resp. N rows),
@@ -448,6 +451,9 @@ int surya_prof_enable(int on);
  * sa::Tuning in csrc/common.h: "graph", "split_target", "bigtile", "persist", "lmhead", "dattn", ...). Process-wide; results never depend on it
  * beyond fp rounding order. Returns SA_ERR_ARG for an unknown key. */
 int surya_set_tuning(const char* key, int value);
+/* Synchronous check of the decode GEMM ring's give-up word (csrc/gemm_ring.h): SA_OK while every ring wait of this library's recognition
+ * launches was satisfied, SA_ERR_STATE once one gave up (its launch's numbers are then wrong); reset != 0 clears the word. */
+int surya_gemm_ring_status(int reset);
 int surya_prof_read(int max_cfg, int* launches, double* ms, double* flops, double* bytes);
 /* surya_prof_read + slab_bytes[]: the fp32 partial slabs split-K launches wrote (a by-product of the kernel's own decomposition,
  * NOT part of `bytes`: `bytes` counts the result once in the storage type, as an unsplit GEMM would write it). slab_bytes may be NULL. */

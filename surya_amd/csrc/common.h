@@ -206,6 +206,10 @@ struct Tuning {
     int big_m_gateup = -1;   // decode gate|up above 256 rows: -1 = by rows (8-phase 256x256 tile at 4-6 row blocks, else the generic choice), 0 = generic,
                              // 1 = persistent 8-phase loop, 2 = 8-phase tile per workgroup
     int gateup_ring = 2;     // decode gate|up (64x64 tiles, M in (128, 256]): LDS stages of its direct-to-LDS loop (2 = unrolled pair, 3 / 4 = ring with counted vmcnt)
+    int dring = 1;           // decode gate|up and long-slice split-K projections (bf16, 128 < M <= 256) on the loader / consumer LDS ring (gemm_ring.h):
+                             // 0 = the gemm_nt_kernel tiles, 1 = ring, 2 = ring with non-temporal weight loads; + 4 = also at M <= 128 (tests). Same bits in every arm
+    int dring_min_kt = 0;    // ... split-K projections too when a slice has at least this many K-tiles (down: 26-27; qkv / o: 6-10); 0 = never.
+                             // Off: in the bench's decode step the down projection took 12.8 us on the ring against 12.5 on the 64 x 64 tile (profiles/r07_*)
     int conv_persist = 3;    // 3 x 3 / 5 x 5 convolutions on 256x256 tiles on the persistent 8-phase loop with the gather in its request stream: bit 0 = Cin % 64 == 0 (a K-tile is one tap), bit 1 = Cin == 32 (two taps per K-tile); 0 = one-tile 2-stage kernel
     int dwconv_pipe = 2;     // depthwise convolutions: 2 = round-3 kernel with its index split by host-made reciprocals (64-bit % and / were ~700 instructions per thread; +1 % on the forward), 1 = all loads unconditional (hipcc hoists them all: 2 waves per SIMD, -4.5 %), 0 = round-3 kernel
     int conv_lean = 1;       // implicit-GEMM convolutions whose K-tiles align with filter taps: gather state precomputed per workgroup (0 = round-4 per-request arithmetic)

@@ -1542,6 +1542,10 @@ static inline int launch_gemm_persist(const GemmArgs<TI, TO>& a, hipStream_t s) 
     return (int)hipGetLastError();
 }
 
+}  // namespace sa
+#include "gemm_ring.h"
+namespace sa {
+
 // Tile choice. M <= 256 is the decode regime: one workgroup spans all rows (weights stream from HBM once), BN picked so
 // the grid has >= ~128 workgroups where N allows. Larger M uses 128x128 tiles, with 64x64 for problems too small to
 // fill the chip.
@@ -1574,6 +1578,10 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
             // else 64x64, direct-to-LDS. Larger gate|up tiles (128x64: +26 us/step, 128x128: +69), a 256x128 lm_head tile (+30) and
             // 3- / 4-stage rings for lm_head (+25) all lost in r02 (profiles/r02_decode_sweeps.md).
             if (a.N >= 64 * 512) return launch_gemm_cfg<TI, TO, 128, 128, 2, 2, EPI, false, 2>(a, s);
+            if constexpr (EPI == EPI_SWIGLU && sizeof(TI) == 2 && sizeof(TO) == 2) {
+                const int rc = launch_gateup_ring(a, s);      // loader / consumer ring (gemm_ring.h, Tuning::dring)
+                if (rc >= 0) return rc;
+            }
             if constexpr (EPI == EPI_SWIGLU && sizeof(TI) == 2) {
                 // decode gate|up (M = 256, N = 10240, K = 1280): 4 MFMAs per wave and K-tile against a ~700-cycle L2 round trip -- with two
                 // stages a workgroup's 20 K-tiles are 20 serial round trips. Round 5 A/B: a 3- / 4-stage ring (the split-K tiles' loop) keeps
@@ -1699,6 +1707,10 @@ static inline int launch_gemm_splitk(GemmArgs<TI, TI>& a, hipStream_t s) {
         const int pick = a.M <= 256 ? 0 : (mode >= 0 ? mode : (w128 >= 136 ? 2 : (w12864 <= 256 ? 3 : 0)));
         if (pick == 2) return launch_gemm_cfg<TI, TI, 128, 128, 2, 2, EPI_BIAS, true, 4>(a, s);
         if (pick == 3) return launch_gemm_cfg<TI, TI, 128, 64, 4, 1, EPI_BIAS, true, 4>(a, s);
+    }
+    if constexpr (sizeof(TI) == 2) {
+        const int rc = launch_splitk_ring(a, s);              // loader / consumer ring (gemm_ring.h, Tuning::dring)
+        if (rc >= 0) return rc;
     }
     return launch_gemm_cfg<TI, TI, 64, 64, 2, 2, EPI_BIAS, true, 4>(a, s);
 }

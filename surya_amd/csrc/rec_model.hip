@@ -1413,6 +1413,14 @@ int surya_op_mx_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* s
     return (int)hipGetLastError();
 }
 
+int surya_op_gemm_splitk_bf16(const void* X, long ldx, const void* W, long ldw, float* part, int M, int N, int K, int* splitk, void* stream) {
+    if (!X || !W || !part || !splitk) return SA_ERR_ARG;
+    GemmArgs<bf16_t, bf16_t> a{reinterpret_cast<const bf16_t*>(X), ldx, reinterpret_cast<const bf16_t*>(W), ldw, nullptr, 0, nullptr, nullptr, 0, M, N, K, 1, part};
+    const int rc = launch_gemm_splitk<bf16_t>(a, (hipStream_t)stream);
+    *splitk = a.splitk;
+    return rc;
+}
+
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream) {
     if (!X || !SX || !W || !SW) return SA_ERR_ARG;
@@ -1457,7 +1465,7 @@ int surya_set_tuning(const char* key, int value) {
     Tuning& t = tuning();
     struct { const char* k; int* v; } tab[] = {
         {"graph", &t.graph}, {"split_target", &t.split_target}, {"split_min_kt", &t.split_min_kt}, {"split_max", &t.split_max},
-        {"bigtile", &t.bigtile}, {"bigtile_any", &t.bigtile_any}, {"conv_lean", &t.conv_lean}, {"conv_persist", &t.conv_persist}, {"dwconv_pipe", &t.dwconv_pipe}, {"bigtile_ratio_pct", &t.bigtile_ratio_pct}, {"gateup_ring", &t.gateup_ring}, {"big_m_split", &t.big_m_split}, {"big_m_gateup", &t.big_m_gateup}, {"glds", &t.glds}, {"bigtile_min_k", &t.bigtile_min_k}, {"dattn", &t.dattn}, {"rnorm", &t.rnorm},
+        {"bigtile", &t.bigtile}, {"bigtile_any", &t.bigtile_any}, {"conv_lean", &t.conv_lean}, {"conv_persist", &t.conv_persist}, {"dwconv_pipe", &t.dwconv_pipe}, {"bigtile_ratio_pct", &t.bigtile_ratio_pct}, {"gateup_ring", &t.gateup_ring}, {"dring", &t.dring}, {"dring_min_kt", &t.dring_min_kt}, {"big_m_split", &t.big_m_split}, {"big_m_gateup", &t.big_m_gateup}, {"glds", &t.glds}, {"bigtile_min_k", &t.bigtile_min_k}, {"dattn", &t.dattn}, {"rnorm", &t.rnorm},
         {"ghead", &t.ghead}, {"fuse_embed", &t.fuse_embed}, {"persist", &t.persist}, {"lmhead", &t.lmhead}, {"kvprefetch", &t.kvprefetch},
         {"dattn_db", &t.dattn_db}, {"lay_ln", &t.lay_ln}, {"det_head_blk", &t.det_head_blk}, {"det_fuse", &t.det_fuse}, {"det_up4", &t.det_up4}, {"fmb_chunk", &t.fmb_chunk}};
     for (auto& e : tab)
@@ -1468,6 +1476,8 @@ int surya_set_tuning(const char* key, int value) {
         }
     return SA_ERR_ARG;
 }
+
+int surya_gemm_ring_status(int reset) { return sa::ring_error(reset != 0); }
 
 int surya_prof_enable(int on) {
     GemmProfiler& pf = gemm_profiler();
