@@ -440,6 +440,38 @@ int surya_layout_select(surya_layout* h, const int32_t* src_index, int n);
 int surya_layout_encoder_states(surya_layout* h, void* out, int batch, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * OCR-error classifier: DistilBERT encoder (post-LayerNorm) + sequence-classification head.
+ * Replaces DistilBertForSequenceClassification.forward (surya/ocr_error/model/encoder.py:720-764) as
+ * OCRErrorPredictor calls it (surya/ocr_error/__init__.py:19-63). The texts of one call are PACKED: ids holds the
+ * sum of text_len tokens back to back ([CLS] ... [SEP] each) and no padded row is computed; a text's logits do not
+ * depend on its batch mates (the reference masks padded keys with zero softmax weight and reads only the [CLS] row).
+ * ---------------------------------------------------------------------------------------------------------- */
+typedef struct surya_ocrerr_config {
+    int32_t vocab, max_pos, dim, heads, hidden, layers, num_labels;
+    float ln_eps;                        /* 1e-12 (encoder.py:54, :417, :420) */
+    int32_t max_texts, max_tokens;       /* per forward: texts and packed tokens */
+    int32_t dtype;
+} surya_ocrerr_config;
+/* Weight table: SA_OW_* globals, then SA_OL_COUNT entries per layer. Every entry is in the compute dtype. WORD [vocab][dim],
+ * POS [max_pos][dim] (learned, or the sin-cos table built by the caller), PRE [dim][dim], CLS [num_labels][dim]; per layer QKV_W =
+ * q_lin | k_lin | v_lin rows fused [3 dim][dim] (q rows and bias already multiplied by 1 / sqrt(head_dim) when that is a power of two,
+ * see SA_OCRERR_Q_PRESCALED), OUT [dim][dim], LIN1 [hidden][dim], LIN2 [dim][hidden], LN weights / biases [dim]. */
+enum { SA_OW_WORD = 0, SA_OW_POS, SA_OW_EMB_LN_W, SA_OW_EMB_LN_B, SA_OW_PRE_W, SA_OW_PRE_B, SA_OW_CLS_W, SA_OW_CLS_B, SA_OW_GLOBALS };
+enum { SA_OL_QKV_W = 0, SA_OL_QKV_B, SA_OL_OUT_W, SA_OL_OUT_B, SA_OL_SA_LN_W, SA_OL_SA_LN_B, SA_OL_LIN1_W, SA_OL_LIN1_B, SA_OL_LIN2_W,
+       SA_OL_LIN2_B, SA_OL_OUT_LN_W, SA_OL_OUT_LN_B, SA_OL_COUNT };
+/* head_dim 64: the caller folds the exact 1 / 8 into the q rows; other head dims pass the scale to attention (it is applied to q there) */
+#define SA_OCRERR_Q_PRESCALED(head_dim) ((head_dim) == 64)
+
+typedef struct surya_ocrerr surya_ocrerr;
+int surya_ocrerr_create(const surya_ocrerr_config* cfg, const void* const* weights, int n_weights, surya_ocrerr** out);
+int surya_ocrerr_destroy(surya_ocrerr* h);
+/* ids: device int32 [sum text_len] packed token ids; text_len: HOST int32 [n_texts], each in 1 .. max_pos; logits: device fp32
+ * [n_texts][num_labels] (rounded to the compute dtype, as the reference's logits are); labels: device int32 [n_texts] (first argmax).
+ * Enqueue only (the host arrays are staged before the call returns). */
+int surya_ocrerr_forward(surya_ocrerr* h, const int32_t* ids, const int32_t* text_len, int n_texts, float* logits, int32_t* labels,
+                         void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Measurement support (bench.py `roofline`): when enabled every GEMM launch is bracketed by hipEvents on its own
  * stream. surya_prof_read syncs the device and returns, per bucket (0: 128x128 GEMM, 1: tall 256-row GEMM tiles, 2: smaller GEMM tiles,
  * 3: implicit-GEMM convolutions),

@@ -241,6 +241,8 @@ struct Tuning {
     int persist = 1;         // 256x256 bf16 GEMMs (>= 4 even K-tiles) as the PERSISTENT 8-phase loop (gemm_nt_p8p_kernel: the half-tile ring runs on across
                              // tiles, wave-private epilogue): 1 = on (round 5: +3...10 % per encoder / prefill shape once the two wave groups were
                              // re-aligned around the epilogue, +0.9 % on the bench's recognition leg); 0 = one tile per workgroup
+    int ocrerr_cls_only = 1; // OCR-error classifier (ocr_error_model.hip): 1 = the last layer after its QKV projection runs for the [CLS] rows only (cls_attn_kernel,
+                             // out_lin / LayerNorms / FFN at M = texts), 0 = the full last layer and a gather of the [CLS] rows (the checker / A/B arm)
 };
 inline Tuning& tuning() { static Tuning t; return t; }
 inline int& tuning_epoch() { static int e = 0; return e; }   // bumped by surya_set_tuning whenever a knob changes value

@@ -1,0 +1,314 @@
+// OCR-error classifier on MI355X: the DistilBERT sequence classifier of surya/ocr_error (model/encoder.py) behind surya_ocrerr_* of
+// include/surya_amd.h. Replaces DistilBertForSequenceClassification.forward as OCRErrorPredictor calls it (ocr_error/__init__.py:19-63).
+//
+// Design notes (vs the PyTorch path):
+//   * texts are PACKED: one forward runs over T = sum of the text lengths; no padded row is computed anywhere. The reference's padding
+//     is invisible in its result (padded keys get exactly zero softmax weight, only the [CLS] row is read), so this is exact;
+//   * attention is segment attention with one segment per text (attn_mfma_kernel in bf16, attn_valu_kernel in fp32);
+//   * q_lin | k_lin | v_lin run as one GEMM; the 1 / sqrt(head_dim) of encoder.py:174 is folded into the q rows at load when it is a
+//     power of two (head_dim 64: bit for bit the reference's division of the rounded projection);
+//   * out_lin and lin2 add the residual in the GEMM epilogue (rounded projection + residual, rounded: the reference's two T ops),
+//     lin1 applies the erf GELU there; the LayerNorms are separate row kernels;
+//   * the LAST layer is computed for the [CLS] rows only (Tuning::ocrerr_cls_only): its QKV GEMM still covers every token (the [CLS]
+//     query attends to all keys), then attention for one query per text and out_lin, both LayerNorms and the FFN on n rows instead of T.
+//     fp32 mode runs attn_valu_kernel over each text's first 64-query tile for this (the [CLS] row comes out bit-identical to the full
+//     layer's), bf16 mode the one-query cls_attn_kernel;
+//   * GEMMs over the [CLS] rows are pinned to the 64 x 64 tile, and no GEMM here splits K: every GEMM tile walks K in the same order
+//     with the same MFMA, so a text's logits do not depend on how many rows its batch mates add.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../include/surya_amd.h"
+#include "gemm.h"
+#include "kernels.h"
+#include "attn_mfma.h"
+#include "ocr_error_kernels.h"
+
+namespace sa {
+
+struct OcrErrBase {
+    virtual ~OcrErrBase() {}
+    virtual int forward(const int32_t* ids, const int32_t* text_len, int n, float* logits, int32_t* labels, hipStream_t s) = 0;
+};
+
+static size_t oalign(size_t v) { return (v + 255) & ~(size_t)255; }
+
+template <typename T>
+struct OcrErrModel : OcrErrBase {
+    surya_ocrerr_config c;
+    std::vector<const T*> w;
+    int D = 64;
+    float attn_scale = 1.f;
+    char* arena = nullptr;
+    T *x, *tmp, *h1, *att, *qkv, *ffn;            // packed rows [max_tokens][...]
+    T *cx, *ctmp, *ch1, *cffn, *cpre;             // [CLS] rows [max_texts][...]
+    T* catt;                                      // fp32 [CLS] attention: [max_texts][64][dim] (a text's first query tile); bf16: [max_texts][dim]
+    // staging: two pinned host slots mirrored on the device, one H2D copy per forward; a slot is reused only after its copy completed
+    struct Slot { char* host = nullptr; char* dev = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
+    Slot slot[2];
+    int cur = 0;
+    size_t stage_cap = 0;
+    size_t cls_lds = 0;
+
+    const T* gw(int i) const { return w[i]; }
+    const T* lw(int l, int i) const { return w[SA_OW_GLOBALS + l * SA_OL_COUNT + i]; }
+
+    int init(const surya_ocrerr_config& cfg, const void* const* weights) {
+        c = cfg;
+        const int nw = SA_OW_GLOBALS + c.layers * SA_OL_COUNT;
+        for (int i = 0; i < nw; ++i) w.push_back(reinterpret_cast<const T*>(weights[i]));
+        D = c.dim / c.heads;
+        attn_scale = SA_OCRERR_Q_PRESCALED(D) ? 1.f : 1.f / std::sqrt((float)D);
+        const long Tm = c.max_tokens, Nm = c.max_texts, E = sizeof(T);
+        const size_t sizes[] = {(size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E),
+                                (size_t)(Tm * 3 * c.dim * E), (size_t)(Tm * c.hidden * E),
+                                (size_t)(Nm * c.dim * E), (size_t)(Nm * c.dim * E), (size_t)(Nm * c.dim * E), (size_t)(Nm * c.hidden * E),
+                                (size_t)(Nm * c.dim * E), (size_t)(Nm * (std::is_same<T, float>::value ? 64 : 1) * c.dim * E)};
+        size_t total = 0;
+        for (size_t b : sizes) total += oalign(b);
+        SA_HIP(hipMalloc((void**)&arena, total));
+        poison_arena(arena, total);
+        T** ptrs[] = {&x, &tmp, &h1, &att, &qkv, &ffn, &cx, &ctmp, &ch1, &cffn, &cpre, &catt};
+        size_t off = 0;
+        for (int i = 0; i < 12; ++i) { *ptrs[i] = reinterpret_cast<T*>(arena + off); off += oalign(sizes[i]); }
+        // per forward: tok_pos [T], cls rows [n], text lengths [n], tiles (seg, q0) [<= T / 64 + n] x 2, offsets 4 x 2 x [n] longs
+        const long tiles = Tm / 64 + Nm + 1;
+        stage_cap = oalign(Tm * 4) + 2 * oalign(Nm * 4) + 4 * oalign(tiles * 4) + 8 * oalign(Nm * 8) + 4096;
+        for (Slot& sl : slot) {
+            SA_HIP(hipHostMalloc((void**)&sl.host, stage_cap, hipHostMallocDefault));
+            SA_HIP(hipMalloc((void**)&sl.dev, stage_cap));
+            SA_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
+        }
+        const int ncmax = (c.max_pos + 63) / 64;
+        cls_lds = (size_t)(c.dim + (long)c.heads * ncmax * 64 + (long)c.heads * ncmax) * sizeof(float);
+        if (std::is_same<T, bf16_t>::value && cls_lds > 64 * 1024) return SA_ERR_UNSUPPORTED;
+        return SA_OK;
+    }
+    ~OcrErrModel() override {
+        for (Slot& sl : slot) {
+            if (sl.pending) (void)hipEventSynchronize(sl.ev);
+            if (sl.host) (void)hipHostFree(sl.host);
+            if (sl.dev) (void)hipFree(sl.dev);
+            if (sl.ev) (void)hipEventDestroy(sl.ev);
+        }
+        if (arena) (void)hipFree(arena);
+    }
+
+    template <int EPI>
+    int gemm(const T* X, long ldx, const T* Wt, const T* bias, T* C, const T* R, int M, int N, int K, bool pinned, hipStream_t s) {
+        GemmArgs<T, T> a{X, ldx, Wt, (long)K, C, (long)N, bias, R, (long)N, M, N, K};
+        if (M <= 0) return SA_OK;
+        if (pinned) return launch_gemm_cfg<T, T, 64, 64, 2, 2, EPI>(a, s);     // [CLS]-row GEMMs: one path whatever the text count
+        return launch_gemm<T, T, EPI>(a, s);
+    }
+    int layernorm(const T* in, const T* wt, const T* b, T* out, int rows, hipStream_t s) {
+        if (rows <= 0) return SA_OK;
+        hipLaunchKernelGGL(ocr::layernorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, in, wt, b, out, rows, c.dim, c.ln_eps);
+        return (int)hipGetLastError();
+    }
+    int attention(const T* q, T* o, const AttnSegs& sg, int n_tiles, long o_row, hipStream_t s) {
+        if (n_tiles <= 0) return SA_OK;
+        const long ld = 3L * c.dim;
+        dim3 grid(n_tiles, c.heads);
+        if constexpr (std::is_same<T, bf16_t>::value) {
+#define SA_OCR_ATTN_M(DD) hipLaunchKernelGGL((attn_mfma_kernel<DD>), grid, dim3(128), 0, s, q, q + c.dim, q + 2 * c.dim, o, sg, ld, (long)D, ld, \
+                                             (long)D, o_row, (long)D, 1, 0, attn_scale)
+            switch (D) {
+                case 32: SA_OCR_ATTN_M(32); break;
+                case 64: SA_OCR_ATTN_M(64); break;
+                case 80: SA_OCR_ATTN_M(80); break;
+                case 128: SA_OCR_ATTN_M(128); break;
+                default: return SA_ERR_UNSUPPORTED;
+            }
+#undef SA_OCR_ATTN_M
+        } else {
+#define SA_OCR_ATTN_V(DD) hipLaunchKernelGGL((attn_valu_kernel<T, DD>), grid, dim3(256), 0, s, q, q + c.dim, q + 2 * c.dim, o, sg, ld, (long)D, ld, \
+                                             (long)D, o_row, (long)D, 1, 0, attn_scale)
+            switch (D) {
+                case 32: SA_OCR_ATTN_V(32); break;
+                case 64: SA_OCR_ATTN_V(64); break;
+                case 80: SA_OCR_ATTN_V(80); break;
+                case 128: SA_OCR_ATTN_V(128); break;
+                default: return SA_ERR_UNSUPPORTED;
+            }
+#undef SA_OCR_ATTN_V
+        }
+        return (int)hipGetLastError();
+    }
+    int cls_attention(const int* starts, const int* lens, int n, hipStream_t s) {
+        if constexpr (std::is_same<T, bf16_t>::value) {
+#define SA_OCR_CLS(DD) hipLaunchKernelGGL((ocr::cls_attn_kernel<DD>), dim3(n), dim3(256), cls_lds, s, qkv, starts, lens, catt, c.dim, c.heads, attn_scale)
+            switch (D) {
+                case 32: SA_OCR_CLS(32); break;
+                case 64: SA_OCR_CLS(64); break;
+                case 80: SA_OCR_CLS(80); break;
+                case 128: SA_OCR_CLS(128); break;
+                default: return SA_ERR_UNSUPPORTED;
+            }
+#undef SA_OCR_CLS
+            return (int)hipGetLastError();
+        }
+        return SA_ERR_STATE;
+    }
+
+    int forward(const int32_t* ids, const int32_t* text_len, int n, float* logits, int32_t* labels, hipStream_t s) override {
+        if (n <= 0) return SA_OK;
+        if (n > c.max_texts) return SA_ERR_SHAPE;
+        long T_ = 0;
+        for (int i = 0; i < n; ++i) {
+            if (text_len[i] < 1 || text_len[i] > c.max_pos) return SA_ERR_SHAPE;
+            T_ += text_len[i];
+        }
+        if (T_ > c.max_tokens) return SA_ERR_SHAPE;
+        const int Tn = (int)T_;
+        // ---- host plan -> one staged copy
+        Slot& sl = slot[cur];
+        cur ^= 1;
+        if (sl.pending) { SA_HIP(hipEventSynchronize(sl.ev)); sl.pending = false; }
+        size_t off = 0;
+        auto take = [&](size_t bytes) { const size_t o = off; off = oalign(off + bytes); return o; };
+        const size_t o_pos = take((size_t)Tn * 4), o_start = take((size_t)n * 4), o_len = take((size_t)n * 4);
+        int n_tiles = 0;
+        for (int i = 0; i < n; ++i) n_tiles += cdiv(text_len[i], 64);
+        const size_t o_tseg = take((size_t)n_tiles * 4), o_tq0 = take((size_t)n_tiles * 4), o_cseg = take((size_t)n * 4), o_cq0 = take((size_t)n * 4);
+        const size_t o_qo = take((size_t)n * 8), o_ko = take((size_t)n * 8), o_vo = take((size_t)n * 8), o_oo = take((size_t)n * 8),
+                     o_co = take((size_t)n * 8);
+        if (off > stage_cap) return SA_ERR_SHAPE;
+        int* h_pos = reinterpret_cast<int*>(sl.host + o_pos);
+        int* h_start = reinterpret_cast<int*>(sl.host + o_start);
+        int* h_len = reinterpret_cast<int*>(sl.host + o_len);
+        int* h_tseg = reinterpret_cast<int*>(sl.host + o_tseg);
+        int* h_tq0 = reinterpret_cast<int*>(sl.host + o_tq0);
+        int* h_cseg = reinterpret_cast<int*>(sl.host + o_cseg);
+        int* h_cq0 = reinterpret_cast<int*>(sl.host + o_cq0);
+        long* h_qo = reinterpret_cast<long*>(sl.host + o_qo);
+        long* h_ko = reinterpret_cast<long*>(sl.host + o_ko);
+        long* h_vo = reinterpret_cast<long*>(sl.host + o_vo);
+        long* h_oo = reinterpret_cast<long*>(sl.host + o_oo);
+        long* h_co = reinterpret_cast<long*>(sl.host + o_co);
+        {
+            int t = 0, k = 0;
+            for (int i = 0; i < n; ++i) {
+                const int L = text_len[i];
+                h_start[i] = t; h_len[i] = L;
+                for (int p = 0; p < L; ++p) h_pos[t + p] = p;
+                for (int q0 = 0; q0 < L; q0 += 64) { h_tseg[k] = i; h_tq0[k] = q0; ++k; }
+                h_cseg[i] = i; h_cq0[i] = 0;
+                h_qo[i] = (long)t * 3 * c.dim; h_ko[i] = h_qo[i]; h_vo[i] = h_qo[i];      // (the k / v column offsets are in the base pointers)
+                h_oo[i] = (long)t * c.dim;
+                h_co[i] = (long)i * 64 * c.dim;
+                t += L;
+            }
+        }
+        SA_HIP(hipMemcpyAsync(sl.dev, sl.host, off, hipMemcpyHostToDevice, s));
+        SA_HIP(hipEventRecord(sl.ev, s));
+        sl.pending = true;
+        const int* d_pos = reinterpret_cast<const int*>(sl.dev + o_pos);
+        const int* d_start = reinterpret_cast<const int*>(sl.dev + o_start);
+        const int* d_len = reinterpret_cast<const int*>(sl.dev + o_len);
+        AttnSegs full{reinterpret_cast<const int*>(sl.dev + o_tseg), reinterpret_cast<const int*>(sl.dev + o_tq0), d_len,
+                      reinterpret_cast<const long*>(sl.dev + o_qo), reinterpret_cast<const long*>(sl.dev + o_ko),
+                      reinterpret_cast<const long*>(sl.dev + o_vo), reinterpret_cast<const long*>(sl.dev + o_oo)};
+        AttnSegs first = full;                       // each text's first 64-query tile, output rows [text][64][dim] in catt (fp32 [CLS] path)
+        first.tile_seg = reinterpret_cast<const int*>(sl.dev + o_cseg);
+        first.tile_q0 = reinterpret_cast<const int*>(sl.dev + o_cq0);
+        first.o_off = reinterpret_cast<const long*>(sl.dev + o_co);
+
+        // ---- embeddings
+        hipLaunchKernelGGL(ocr::embed_ln_kernel<T>, dim3(cdiv(Tn, 4)), dim3(256), 0, s, ids, d_pos, gw(SA_OW_WORD), gw(SA_OW_POS),
+                           gw(SA_OW_EMB_LN_W), gw(SA_OW_EMB_LN_B), x, Tn, c.dim, c.vocab, c.ln_eps);
+        int rc = (int)hipGetLastError();
+        if (rc) return rc;
+        const int dim = c.dim, hid = c.hidden;
+        const bool cls_only = tuning().ocrerr_cls_only != 0;
+        for (int l = 0; l < c.layers; ++l) {
+            const bool last_cls = cls_only && l == c.layers - 1;
+            if ((rc = gemm<EPI_BIAS>(x, dim, lw(l, SA_OL_QKV_W), lw(l, SA_OL_QKV_B), qkv, nullptr, Tn, 3 * dim, dim, false, s))) return rc;
+            if (!last_cls) {
+                if ((rc = attention(qkv, att, full, n_tiles, dim, s))) return rc;
+                if ((rc = gemm<EPI_RESIDUAL>(att, dim, lw(l, SA_OL_OUT_W), lw(l, SA_OL_OUT_B), tmp, x, Tn, dim, dim, false, s))) return rc;
+                if ((rc = layernorm(tmp, lw(l, SA_OL_SA_LN_W), lw(l, SA_OL_SA_LN_B), h1, Tn, s))) return rc;
+                if ((rc = gemm<EPI_GELU>(h1, dim, lw(l, SA_OL_LIN1_W), lw(l, SA_OL_LIN1_B), ffn, nullptr, Tn, hid, dim, false, s))) return rc;
+                if ((rc = gemm<EPI_RESIDUAL>(ffn, hid, lw(l, SA_OL_LIN2_W), lw(l, SA_OL_LIN2_B), tmp, h1, Tn, dim, hid, false, s))) return rc;
+                if ((rc = layernorm(tmp, lw(l, SA_OL_OUT_LN_W), lw(l, SA_OL_OUT_LN_B), x, Tn, s))) return rc;
+                continue;
+            }
+            // last layer, [CLS] rows only
+            long att_ld = dim;
+            if constexpr (std::is_same<T, float>::value) {
+                if ((rc = attention(qkv, catt, first, n, dim, s))) return rc;
+                att_ld = 64L * dim;                  // row 0 of each text's 64-row block
+            } else {
+                if ((rc = cls_attention(d_start, d_len, n, s))) return rc;
+            }
+            hipLaunchKernelGGL(ocr::gather_rows_kernel<T>, dim3(n), dim3(64), 0, s, x, d_start, cx, n, dim);
+            if ((rc = (int)hipGetLastError())) return rc;
+            if ((rc = gemm<EPI_RESIDUAL>(catt, att_ld, lw(l, SA_OL_OUT_W), lw(l, SA_OL_OUT_B), ctmp, cx, n, dim, dim, true, s))) return rc;
+            if ((rc = layernorm(ctmp, lw(l, SA_OL_SA_LN_W), lw(l, SA_OL_SA_LN_B), ch1, n, s))) return rc;
+            if ((rc = gemm<EPI_GELU>(ch1, dim, lw(l, SA_OL_LIN1_W), lw(l, SA_OL_LIN1_B), cffn, nullptr, n, hid, dim, true, s))) return rc;
+            if ((rc = gemm<EPI_RESIDUAL>(cffn, hid, lw(l, SA_OL_LIN2_W), lw(l, SA_OL_LIN2_B), ctmp, ch1, n, dim, hid, true, s))) return rc;
+            if ((rc = layernorm(ctmp, lw(l, SA_OL_OUT_LN_W), lw(l, SA_OL_OUT_LN_B), cx, n, s))) return rc;
+        }
+        if (!cls_only || c.layers == 0) {
+            hipLaunchKernelGGL(ocr::gather_rows_kernel<T>, dim3(n), dim3(64), 0, s, x, d_start, cx, n, dim);
+            if ((rc = (int)hipGetLastError())) return rc;
+        }
+        // ---- head: pre_classifier + ReLU (GEMM at M = n), classifier + argmax
+        if ((rc = gemm<EPI_RELU>(cx, dim, gw(SA_OW_PRE_W), gw(SA_OW_PRE_B), cpre, nullptr, n, dim, dim, true, s))) return rc;
+        hipLaunchKernelGGL(ocr::cls_head_kernel<T>, dim3(n), dim3(64), 0, s, cpre, gw(SA_OW_CLS_W), gw(SA_OW_CLS_B), logits, labels, dim,
+                           c.num_labels);
+        return (int)hipGetLastError();
+    }
+};
+
+}  // namespace sa
+
+using namespace sa;
+
+struct surya_ocrerr { std::unique_ptr<OcrErrBase> impl; };
+
+extern "C" {
+
+int surya_ocrerr_create(const surya_ocrerr_config* cfg, const void* const* weights, int n_weights, surya_ocrerr** out) {
+    if (!cfg || !weights || !out) return SA_ERR_ARG;
+    if (cfg->dtype != SA_DTYPE_F32 && cfg->dtype != SA_DTYPE_BF16) return SA_ERR_UNSUPPORTED;
+    if (cfg->layers < 1 || cfg->heads < 1 || cfg->dim % cfg->heads || cfg->num_labels < 1 || cfg->vocab < 1) return SA_ERR_ARG;
+    const int D = cfg->dim / cfg->heads;
+    if (D != 32 && D != 64 && D != 80 && D != 128) return SA_ERR_UNSUPPORTED;
+    if (cfg->dim % 64 || cfg->hidden % 64) return SA_ERR_SHAPE;          // GEMM K chunks (64 bf16 / 32 fp32 elements), 16-byte rows
+    if (cfg->max_pos < 1 || cfg->max_pos > 4096) return SA_ERR_UNSUPPORTED;
+    if (cfg->max_texts < 1 || cfg->max_tokens < 1) return SA_ERR_ARG;
+    if (n_weights != SA_OW_GLOBALS + cfg->layers * SA_OL_COUNT) return SA_ERR_ARG;
+    for (int i = 0; i < n_weights; ++i)
+        if (!weights[i]) return SA_ERR_ARG;
+    auto* h = new surya_ocrerr();
+    int rc;
+    if (cfg->dtype == SA_DTYPE_F32) {
+        auto* m = new OcrErrModel<float>();
+        h->impl.reset(m);
+        rc = m->init(*cfg, weights);
+    } else {
+        auto* m = new OcrErrModel<bf16_t>();
+        h->impl.reset(m);
+        rc = m->init(*cfg, weights);
+    }
+    if (rc) { delete h; return rc; }
+    *out = h;
+    return SA_OK;
+}
+
+int surya_ocrerr_destroy(surya_ocrerr* h) {
+    delete h;
+    return SA_OK;
+}
+
+int surya_ocrerr_forward(surya_ocrerr* h, const int32_t* ids, const int32_t* text_len, int n_texts, float* logits, int32_t* labels,
+                         void* stream) {
+    if (!h || !h->impl || (n_texts > 0 && (!ids || !text_len || !logits || !labels)) || n_texts < 0) return SA_ERR_ARG;
+    return h->impl->forward(ids, text_len, n_texts, logits, labels, (hipStream_t)stream);
+}
+
+}  // extern "C"

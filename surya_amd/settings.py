@@ -73,6 +73,10 @@ class Settings:
         self.SURYA_AMD_SHARD: bool = _env("SURYA_AMD_SHARD", bool, False)
         # rank 0 repacks the weights, the other ranks receive them through one bucketed RCCL broadcast at construction
         self.SURYA_AMD_BROADCAST_WEIGHTS: bool = _env("SURYA_AMD_BROADCAST_WEIGHTS", bool, False)
+        # OCR-error classifier (settings.py:124-126): a checkpoint directory, or a config name (OCRERR-TINY / OCRERR-DEFAULT) for
+        # synthetic weights; the reference's S3 default is not reachable here and selects OCRERR-DEFAULT
+        self.OCR_ERROR_MODEL_CHECKPOINT: str = _env("OCR_ERROR_MODEL_CHECKPOINT", str, "s3://ocr_error_detection/2025_02_18")
+        self.OCR_ERROR_BATCH_SIZE: Optional[int] = _env("OCR_ERROR_BATCH_SIZE", int, None)
         self.SURYA_AMD_REC_CONFIG: str = _env("SURYA_AMD_REC_CONFIG", str, "REC-FULL")
         self.SURYA_AMD_DET_CONFIG: str = _env("SURYA_AMD_DET_CONFIG", str, "DET-DEFAULT")
 

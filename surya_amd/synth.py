@@ -428,3 +428,106 @@ def make_table_weights(cfg, seed: int = 0) -> Dict[str, torch.Tensor]:
     """Table-recognition twin of make_layout_weights: `encoder.*` = table_rec's DonutSwinModel (the same Swin stack,
     surya/table_rec/model/encoder.py), `decoder.*` = SuryaTableRecDecoder (surya/table_rec/model/decoder.py)."""
     return make_layout_weights(cfg, seed)
+
+
+# ------------------------------------------------------------------------------------------------------------------ OCR-error classifier
+def make_ocr_error_weights(cfg, seed: int = 0, recipe: str = "conditioned") -> Dict[str, torch.Tensor]:
+    """fp32 CPU state dict of DistilBertForSequenceClassification (surya/ocr_error/model/encoder.py) with the reference's parameter names.
+
+    recipe "default": the reference's own initialisation (normal std 0.02, zero biases, unit LayerNorms; _init_weights) -- every logit
+    is then ~0.03 and every label a near-tie. "conditioned": unit-gain projections (std 1 / sqrt(fan_in)), q / k at 1.5x so attention is
+    peaked and the [CLS] state depends on the text, unit-scale embeddings, perturbed LayerNorms, and a classifier whose two rows are +u and
+    -u: the fp32 logits are O(1) and their margin varies from text to text, large against bf16 rounding on most texts."""
+    if recipe not in ("default", "conditioned"):
+        raise ValueError(f"unknown recipe {recipe!r}")
+    g = torch.Generator().manual_seed(seed)
+    D, H, V, P = cfg.dim, cfg.hidden_dim, cfg.vocab_size, cfg.max_position_embeddings
+    cond = recipe == "conditioned"
+    sd: Dict[str, torch.Tensor] = {}
+
+    def lin(name, n_out, n_in, gain=1.0):
+        sd[name + ".weight"] = _normal(g, (n_out, n_in), gain / math.sqrt(n_in) if cond else 0.02)
+        sd[name + ".bias"] = _normal(g, (n_out,), 0.02) if cond else torch.zeros(n_out)
+
+    def ln(name):
+        sd[name + ".weight"] = 1.0 + _normal(g, (D,), 0.1) if cond else torch.ones(D)
+        sd[name + ".bias"] = _normal(g, (D,), 0.1) if cond else torch.zeros(D)
+
+    sd["distilbert.embeddings.word_embeddings.weight"] = _normal(g, (V, D), 1.0 if cond else 0.02)
+    sd["distilbert.embeddings.word_embeddings.weight"][cfg.pad_token_id] = 0.0        # nn.Embedding(padding_idx=pad_token_id)
+    if cfg.sinusoidal_pos_embds:
+        from .ocr_error.config import sinusoidal_table
+        sd["distilbert.embeddings.position_embeddings.weight"] = sinusoidal_table(P, D)
+    else:
+        sd["distilbert.embeddings.position_embeddings.weight"] = _normal(g, (P, D), 0.5 if cond else 0.02)
+    ln("distilbert.embeddings.LayerNorm")
+    for i in range(cfg.n_layers):
+        p = f"distilbert.transformer.layer.{i}."
+        lin(p + "attention.q_lin", D, D, 1.5)
+        lin(p + "attention.k_lin", D, D, 1.5)
+        lin(p + "attention.v_lin", D, D)
+        lin(p + "attention.out_lin", D, D)
+        ln(p + "sa_layer_norm")
+        lin(p + "ffn.lin1", H, D)
+        lin(p + "ffn.lin2", D, H)
+        ln(p + "output_layer_norm")
+    lin("pre_classifier", D, D)
+    if cond:
+        u = _normal(g, (D,), 4.0 / math.sqrt(D))
+        w = torch.zeros(cfg.num_labels, D)
+        w[0], w[1 % cfg.num_labels] = u, -u
+        if cfg.num_labels > 2:
+            w[2:] = _normal(g, (cfg.num_labels - 2, D), 4.0 / math.sqrt(D))
+        sd["classifier.weight"], sd["classifier.bias"] = w, torch.zeros(cfg.num_labels)
+    else:
+        lin("classifier", cfg.num_labels, D)
+    return sd
+
+
+def make_wordpiece_vocab(seed: int = 0, size: int = 1024) -> List[str]:
+    """A deterministic BERT-style vocabulary (the line order of vocab.txt): [PAD] = 0, [unused1..99], [UNK] / [CLS] / [SEP] / [MASK] =
+    100..103, then ASCII punctuation, digits, letters, accented letters, some CJK ideographs, "##" continuations of every single
+    character, and multi-letter pieces (common English fragments plus seeded random ones), with and without "##"."""
+    import random
+    rng = random.Random(seed)
+    toks = ["[PAD]"] + [f"[unused{i}]" for i in range(1, 100)] + ["[UNK]", "[CLS]", "[SEP]", "[MASK]"]
+    singles = [chr(c) for c in range(33, 127) if not chr(c).isupper()] + list("àáâäçèéêëìíîïñòóôöùúûüß") + list("的一是不了人我在有他这中大来上国个到说们为子和你地出道也时年")
+    toks += singles
+    toks += ["##" + c for c in singles if c.isalnum()]
+    common = ["the", "and", "ing", "ion", "tion", "ent", "her", "for", "tha", "nth", "int", "ere", "tio", "ter", "est", "ers", "ati", "hat",
+              "ate", "all", "eth", "hes", "ver", "his", "oft", "ith", "fth", "sth", "oth", "res", "ont", "of", "to", "in", "is", "it", "on",
+              "be", "as", "at", "by", "or", "an", "we", "ocr", "text", "page", "error", "good", "bad", "model", "table", "line", "word"]
+    toks += common + ["##" + c for c in common if len(c) > 2] + ["##s", "##ed", "##ly", "##er", "##es", "##al"]
+    letters = "abcdefghijklmnopqrstuvwxyz"
+    seen = set(toks)
+    while len(toks) < size:
+        n = rng.choice((2, 2, 3, 3, 4, 5))
+        t = "".join(rng.choice(letters) for _ in range(n))
+        if rng.random() < 0.5:
+            t = "##" + t
+        if t not in seen:
+            seen.add(t)
+            toks.append(t)
+    return toks[:size]
+
+
+def write_ocr_error_checkpoint(path: str, cfg, sd: Dict[str, torch.Tensor], vocab: List[str], model_max_length: int = 512,
+                               do_lower_case: bool = True) -> str:
+    """A checkpoint directory in the reference's on-disk format (OCRErrorModelLoader: DistilBertConfig.from_pretrained /
+    from_pretrained / DistilBertTokenizer.from_pretrained of one directory): config.json, model.safetensors, vocab.txt and
+    tokenizer_config.json."""
+    import json
+    import os
+    from safetensors.torch import save_file
+    from .ocr_error.config import config_to_reference_json
+    os.makedirs(path, exist_ok=True)
+    with open(os.path.join(path, "config.json"), "w") as f:
+        json.dump(config_to_reference_json(cfg), f, indent=1)
+    save_file({k: v.contiguous() for k, v in sd.items()}, os.path.join(path, "model.safetensors"))
+    with open(os.path.join(path, "vocab.txt"), "w", encoding="utf-8") as f:
+        f.write("\n".join(vocab) + "\n")
+    with open(os.path.join(path, "tokenizer_config.json"), "w") as f:
+        json.dump({"tokenizer_class": "DistilBertTokenizer", "do_lower_case": do_lower_case, "model_max_length": model_max_length,
+                   "strip_accents": None, "tokenize_chinese_chars": True, "unk_token": "[UNK]", "sep_token": "[SEP]",
+                   "pad_token": "[PAD]", "cls_token": "[CLS]", "mask_token": "[MASK]"}, f, indent=1)
+    return path
