@@ -14,7 +14,8 @@
  *   - all work is enqueued on the hipStream_t passed in (as void*); functions do not synchronise unless
  *     documented ("sync"). A handle is re-entrant but not thread-safe: one host thread per handle, like the
  *     reference's single-threaded device path (surya/settings.py:179-183).
- *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16.
+ *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (text detector and
+ *     surya_op_gemm only; every other engine returns SA_ERR_UNSUPPORTED for it).
  */
 #ifndef SURYA_AMD_H
 #define SURYA_AMD_H
@@ -34,6 +35,7 @@ extern "C" {
 
 #define SA_DTYPE_F32 0
 #define SA_DTYPE_BF16 1
+#define SA_DTYPE_F16 2
 
 /* Library / build info: returns a static string "surya_amd <version> gfx950". */
 const char* surya_amd_version(void);
@@ -209,7 +211,8 @@ int surya_rec_set_kv_fp8(surya_rec* h, int on);
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
 /* C[M,N] = X[M,K] W[N,K]^T + bias, epilogue: 0 none/bias, 1 +residual R, 2 gelu, 3 swiglu (W rows interleaved,
- * C is [M,N/2]), 4 hardswish, 5 relu. out_f32 != 0: C (and R) are fp32 regardless of dtype. */
+ * C is [M,N/2]), 4 hardswish, 5 relu. out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the
+ * detector's epilogues (0, 1, 4, 5) with fp16 output only; anything else returns SA_ERR_UNSUPPORTED. */
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,
                   const void* bias, const void* R, long ldr, int M, int N, int K, void* stream);
 int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, int rows, int C, float eps,

@@ -29,11 +29,22 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         }                                                                                              \
     } while (0)
 
+// storage type for fp16: a distinct C++ type (bf16_t is an integer type, so dispatch on the storage type needs another one)
+typedef _Float16 fp16_t;
+typedef __attribute__((ext_vector_type(8))) _Float16 f16x8;
+typedef __attribute__((ext_vector_type(2))) _Float16 f16x2;
+typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+typedef __attribute__((ext_vector_type(2))) float f32x2v;
+
 __device__ __forceinline__ float bf2f(bf16_t v) { return __uint_as_float(((uint32_t)v) << 16); }
 __device__ __forceinline__ bf16_t f2bf(float f) {
     __bf16 b = (__bf16)f;   // v_cvt_pk_bf16_f32 on gfx950, round-to-nearest-even
     return __builtin_bit_cast(bf16_t, b);
 }
+// fp16 pair: v_cvt_pk_f16_f32 (round to nearest even, overflow -> +-inf, NaN stays NaN: torch's .half()); NOT v_cvt_pkrtz_f16_f32
+__device__ __forceinline__ uint32_t pack2h(float a, float b) { return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2v{a, b}, f16x2)); }
+__device__ __forceinline__ float h2f(fp16_t v) { return (float)v; }
+__device__ __forceinline__ fp16_t f2h(float f) { return __builtin_bit_cast(f16x2, pack2h(f, 0.f))[0]; }
 
 template <typename T> struct Ty;
 template <> struct Ty<float> {
@@ -51,6 +62,14 @@ template <> struct Ty<bf16_t> {
     __device__ static __forceinline__ float rnd(float v) { return bf2f(f2bf(v)); }
 };
 
+template <> struct Ty<fp16_t> {
+    static constexpr int KE = 64;
+    static constexpr int V16 = 8;
+    __device__ static __forceinline__ float ld(const fp16_t* p) { return h2f(*p); }
+    __device__ static __forceinline__ void st(fp16_t* p, float v) { *p = f2h(v); }
+    __device__ static __forceinline__ float rnd(float v) { return h2f(f2h(v)); }
+};
+
 // Unpack a 16-byte register chunk into floats (4 for f32, 8 for bf16).
 __device__ __forceinline__ void unpack16(const uint4& v, float (&o)[4], float*) {
     o[0] = __uint_as_float(v.x); o[1] = __uint_as_float(v.y); o[2] = __uint_as_float(v.z); o[3] = __uint_as_float(v.w);
@@ -61,7 +80,44 @@ __device__ __forceinline__ void unpack16(const uint4& v, float (&o)[8], bf16_t*)
     o[4] = __uint_as_float(v.z << 16); o[5] = __uint_as_float(v.z & 0xffff0000u);
     o[6] = __uint_as_float(v.w << 16); o[7] = __uint_as_float(v.w & 0xffff0000u);
 }
+__device__ __forceinline__ void unpack16(const uint4& v, float (&o)[8], fp16_t*) {
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { const f16x2 h = __builtin_bit_cast(f16x2, w[i]); o[2 * i] = (float)h[0]; o[2 * i + 1] = (float)h[1]; }
+}
 __device__ __forceinline__ uint32_t pack2(float a, float b) { return (uint32_t)f2bf(a) | ((uint32_t)f2bf(b) << 16); }
+
+// The 16-bit storage types (bf16, fp16) as ONE trait: every kernel written for "a 16-bit storage type" takes its packing, unpacking,
+// dot products and MFMA from here, so its bf16 and fp16 instances are the same code with the twin instructions (same cycles on gfx950).
+template <typename T> struct H16;
+template <> struct H16<bf16_t> {
+    typedef bf16x2 x2;
+    __device__ static __forceinline__ uint32_t pk(float a, float b) { return pack2(a, b); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return __uint_as_float(w << 16); }
+    __device__ static __forceinline__ float hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+    __device__ static __forceinline__ x2 cvt(f32x2v v) { return __builtin_convertvector(v, x2); }         // round to nearest even
+    __device__ static __forceinline__ float dot2(x2 a, uint32_t b, float c) {                              // v_dot2c_f32_bf16
+        return __builtin_amdgcn_fdot2_f32_bf16(a, __builtin_bit_cast(x2, b), c, false);
+    }
+    template <typename A, typename B>                                                                    // any 16-byte register chunks
+    __device__ static __forceinline__ f32x16 mfma(const A& w, const B& x, const f32x16& c) {           // v_mfma_f32_32x32x16_bf16
+        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
+    }
+};
+template <> struct H16<fp16_t> {
+    typedef f16x2 x2;
+    __device__ static __forceinline__ uint32_t pk(float a, float b) { return pack2h(a, b); }
+    __device__ static __forceinline__ float lo(uint32_t w) { return (float)__builtin_bit_cast(f16x2, w)[0]; }
+    __device__ static __forceinline__ float hi(uint32_t w) { return (float)__builtin_bit_cast(f16x2, w)[1]; }
+    __device__ static __forceinline__ x2 cvt(f32x2v v) { return __builtin_convertvector(v, x2); }         // v_cvt_pk_f16_f32
+    __device__ static __forceinline__ float dot2(x2 a, uint32_t b, float c) {                              // v_dot2c_f32_f16
+        return __builtin_amdgcn_fdot2(a, __builtin_bit_cast(x2, b), c, false);
+    }
+    template <typename A, typename B>                                                                    // any 16-byte register chunks
+    __device__ static __forceinline__ f32x16 mfma(const A& w, const B& x, const f32x16& c) {           // v_mfma_f32_32x32x16_f16
+        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
+    }
+};
 
 // Store 4 consecutive outputs.
 __device__ __forceinline__ void store4(float* p, float a, float b, float c, float d) {
@@ -70,8 +126,12 @@ __device__ __forceinline__ void store4(float* p, float a, float b, float c, floa
 __device__ __forceinline__ void store4(bf16_t* p, float a, float b, float c, float d) {
     *reinterpret_cast<uint2*>(p) = make_uint2(pack2(a, b), pack2(c, d));
 }
+__device__ __forceinline__ void store4(fp16_t* p, float a, float b, float c, float d) {
+    *reinterpret_cast<uint2*>(p) = make_uint2(pack2h(a, b), pack2h(c, d));
+}
 __device__ __forceinline__ void store2(float* p, float a, float b) { *reinterpret_cast<float2*>(p) = make_float2(a, b); }
 __device__ __forceinline__ void store2(bf16_t* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack2(a, b); }
+__device__ __forceinline__ void store2(fp16_t* p, float a, float b) { *reinterpret_cast<uint32_t*>(p) = pack2h(a, b); }
 __device__ __forceinline__ void load4(const float* p, float (&o)[4]) {
     float4 v = *reinterpret_cast<const float4*>(p); o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w;
 }
@@ -79,6 +139,10 @@ __device__ __forceinline__ void load4(const bf16_t* p, float (&o)[4]) {
     uint2 v = *reinterpret_cast<const uint2*>(p);
     o[0] = __uint_as_float(v.x << 16); o[1] = __uint_as_float(v.x & 0xffff0000u);
     o[2] = __uint_as_float(v.y << 16); o[3] = __uint_as_float(v.y & 0xffff0000u);
+}
+__device__ __forceinline__ void load4(const fp16_t* p, float (&o)[4]) {
+    uint2 v = *reinterpret_cast<const uint2*>(p);
+    o[0] = H16<fp16_t>::lo(v.x); o[1] = H16<fp16_t>::hi(v.x); o[2] = H16<fp16_t>::lo(v.y); o[3] = H16<fp16_t>::hi(v.y);
 }
 
 // Cross-lane sums on the VALU (DPP) instead of __shfl_xor, which hipcc lowers to ds_bpermute_b32 (an LDS round trip of
@@ -228,7 +292,7 @@ struct Tuning {
                              // compute): 0 = when some active slot's context exceeds one 128-key tile (host bound; eager launches only -- under graph replay, `graph` = 1, the single-buffer kernel runs and the bound is not advanced), 1 = always, -1 = never
     int lay_ln = 1;          // layout / table encoder LayerNorm (bf16): 1 = rows held in registers by C / 8 lanes (layernorm_rows_bf16_kernel), 0 = a wave per row
     int det_head_blk = 1;    // detector's folded decode head: 1 = register-blocked sum + classify (4 x 2 pixel blocks), 0 = per-pixel kernel
-    int det_fuse = 1023;     // detector's fused forms (det_model.hip find_fusions; bf16): bit 0 = LiteMLA depthwise 5x5 + grouped 1x1, bit 1 = LiteMLA kv + out in one
+    int det_fuse = 1023;     // detector's fused forms (det_model.hip find_fusions; bf16 and fp16): bit 0 = LiteMLA depthwise 5x5 + grouped 1x1, bit 1 = LiteMLA kv + out in one
                              // launch, bit 2 = z0 inside the head's sum + classify pass, bit 3 = MBConv depthwise 3x3 + projection, bit 4 = FusedMBConv
                              // 3x3 + Hardswish + projection, bit 5 = stem convolutions on the patch-in-LDS kernel, bit 6 = whole MBConv blocks (expand + depthwise +
                              // projection) in one launch at the stride-2 transitions (det_mbconv.h), bit 7 = (with bit 2) the folded head entirely on the matrix cores

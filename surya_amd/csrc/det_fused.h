@@ -158,8 +158,9 @@ __global__ __launch_bounds__(256) void litemla_fused_kernel(const T* __restrict_
 #ifndef SA_DW5_ORDER
 #define SA_DW5_ORDER 0      // 0 = a filter column per iteration (input rows shared by the output rows), 1 = the first version: a filter row per iteration, taps in dwconv_tx_kernel's order
 #endif
-__global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ wdw, const bf16_t* __restrict__ wg,
-                                                      bf16_t* __restrict__ out, const bf16_t* __restrict__ zero, int H, int W, int C, int tiles_x) {
+template <typename T>
+__global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const T* __restrict__ in, const T* __restrict__ wdw, const T* __restrict__ wg,
+                                                      T* __restrict__ out, const T* __restrict__ zero, int H, int W, int C, int tiles_x) {
     constexpr int TH = 8, TW = 32, PH = TH + 4, PW = TW + 4;
     __shared__ __attribute__((aligned(16))) unsigned char in_t[PH * PW * 64];
     __shared__ __attribute__((aligned(16))) float wd[25 * 32];
@@ -168,7 +169,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int g = blockIdx.y, b = blockIdx.z;
     const int y0 = ((int)blockIdx.x / tiles_x) * TH, x0 = ((int)blockIdx.x % tiles_x) * TW;
-    const bf16_t* img = in + (long)b * H * W * C + g * 32;
+    const T* img = in + (long)b * H * W * C + g * 32;
     {   // patch: direct-to-LDS requests, all in flight at once (16-byte slot = pixel * 4 + chunk, 27 instructions of 64 slots; outside the image
         // the lane reads the zero page). Staged through registers in a rolled loop it was one global round trip per 16 bytes and thread, 7 in a row.
         typedef const __attribute__((address_space(1))) void* gptr_t;
@@ -182,7 +183,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
                 const int idx = q * 64 + lane, px = idx >> 2, c = idx & 3, ty = px / PW, tx = px - ty * PW;
                 const int gy = y0 - 2 + ty, gx = x0 - 2 + tx;
                 const bool inb = (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
-                const bf16_t* gp = inb ? img + ((long)gy * W + gx) * C + c * 8 : zero;
+                const T* gp = inb ? img + ((long)gy * W + gx) * C + c * 8 : zero;
                 __builtin_amdgcn_global_load_lds((gptr_t)gp, (lptr_t)(in_t + q * 1024), 16, 0, 0);
             }
         }
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
     if (tid < 100) {
         const int tap = tid >> 2, c = tid & 3;
         float t[8];
-        unpack16(*reinterpret_cast<const uint4*>(wdw + (long)tap * C + g * 32 + c * 8), t, (bf16_t*)nullptr);
+        unpack16(*reinterpret_cast<const uint4*>(wdw + (long)tap * C + g * 32 + c * 8), t, (T*)nullptr);
 #pragma unroll
         for (int e = 0; e < 8; ++e) wd[tap * 32 + c * 8 + e] = t[e];
     }
@@ -226,7 +227,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
                 for (int r4 = 0; r4 < 4; ++r4) {
                     const int r = hr * 4 + r4;
                     float xv[8];
-                    unpack16(raw[r4], xv, (bf16_t*)nullptr);
+                    unpack16(raw[r4], xv, (T*)nullptr);
 #pragma unroll
                     for (int o = 0; o < 4; ++o) {
                         const int ky = r - o;
@@ -256,7 +257,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
 #pragma unroll
                 for (int kx = 0; kx < 5; ++kx) {
                     float xv[8];
-                    unpack16(*reinterpret_cast<const uint4*>(in_t + (row * PW + x + kx) * 64 + chunk * 16), xv, (bf16_t*)nullptr);
+                    unpack16(*reinterpret_cast<const uint4*>(in_t + (row * PW + x + kx) * 64 + chunk * 16), xv, (T*)nullptr);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) acc[o][e] += xv[e] * wr[kx][e];
                 }
@@ -269,7 +270,7 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
         for (int o = 0; o < 4; ++o) {
             const int px = (yg * 4 + o) * TW + x;
             *reinterpret_cast<uint4*>(a_t + px * 64 + ((chunk ^ ((px >> 2) & 3)) << 4)) =
-                make_uint4(pack2(acc[o][0], acc[o][1]), pack2(acc[o][2], acc[o][3]), pack2(acc[o][4], acc[o][5]), pack2(acc[o][6], acc[o][7]));
+                make_uint4(H16<T>::pk(acc[o][0], acc[o][1]), H16<T>::pk(acc[o][2], acc[o][3]), H16<T>::pk(acc[o][4], acc[o][5]), H16<T>::pk(acc[o][6], acc[o][7]));
         }
     }
     __syncthreads();
@@ -286,25 +287,24 @@ __global__ __launch_bounds__(256, SA_DW5_WG) void dw5_g1x1_kernel(const bf16_t* 
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             const u32x4 xf = *reinterpret_cast<const u32x4*>(a_t + px * 64 + (((ks * 2 + lh) ^ ((px >> 2) & 3)) << 4));
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[ks]), __builtin_bit_cast(bf16x8, xf), acc, 0, 0, 0);
+            acc = H16<T>::mfma(wf[ks], xf, acc);
         }
         const int gy = y0 + mt, gx = x0 + lr;
         if (gy < H && gx < W) {
-            bf16_t* dst = out + (((long)b * H + gy) * W + gx) * C + g * 32;
+            T* dst = out + (((long)b * H + gy) * W + gx) * C + g * 32;
 #pragma unroll
             for (int q = 0; q < 4; ++q) store4(dst + 8 * q + 4 * lh, acc[4 * q], acc[4 * q + 1], acc[4 * q + 2], acc[4 * q + 3]);
         }
     }
 }
 
-static inline int launch_dw5_g1x1(const bf16_t* in, const bf16_t* wdw, const bf16_t* wg, bf16_t* out, const bf16_t* zero, int B, int H, int W, int C,
+template <typename T>
+static inline int launch_dw5_g1x1(const T* in, const T* wdw, const T* wg, T* out, const T* zero, int B, int H, int W, int C,
                                   hipStream_t s) {
     const int tx = cdiv(W, 32), ty = cdiv(H, 8);
-    hipLaunchKernelGGL(dw5_g1x1_kernel, dim3(tx * ty, C / 32, B), dim3(256), 0, s, in, wdw, wg, out, zero, H, W, C, tx);
+    hipLaunchKernelGGL(dw5_g1x1_kernel<T>, dim3(tx * ty, C / 32, B), dim3(256), 0, s, in, wdw, wg, out, zero, H, W, C, tx);
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_dw5_g1x1(const T*, const T*, const T*, T*, const T*, int, int, int, int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 // ---------------------------------------------------------------------------------------------------
 // Decode head with z0 inside (SA_DET_UPSUM_CLASSIFY + the stage-0 1x1 convolution that feeds it). head_upsum_classify_blk_kernel read
@@ -315,12 +315,11 @@ static inline int launch_dw5_g1x1(const T*, const T*, const T*, T*, const T*, in
 // pass is head_upsum_classify_blk_kernel's: 16 lanes per block, lane `sub` takes channels [slab + 8 sub, + 8), same tap tiles, same sums.
 // A0 comes FRAGMENT-MAJOR ([C / 32][4 K steps][64 lanes][8], det_mbconv.h's mbconv_w2_fragments at engine init): a fragment load is one contiguous KiB
 // (from the row-major [C][64] weight it touched 32 cache lines, 16 such loads per slab at one wave per SIMD).
-template <int R1, int R2, int R3, int BH>
-__global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__ x0, const bf16_t* __restrict__ A0, const bf16_t* __restrict__ zb,
-                                                      const bf16_t* __restrict__ z1, const bf16_t* __restrict__ z2, const bf16_t* __restrict__ z3,
-                                                      const bf16_t* __restrict__ w, const bf16_t* __restrict__ bias, float* __restrict__ out,
+template <typename T, int R1, int R2, int R3, int BH>
+__global__ __launch_bounds__(256) void head_z0_kernel(const T* __restrict__ x0, const T* __restrict__ A0, const T* __restrict__ zb,
+                                                      const T* __restrict__ z1, const T* __restrict__ z2, const T* __restrict__ z3,
+                                                      const T* __restrict__ w, const T* __restrict__ bias, float* __restrict__ out,
                                                       int B, int H0, int W0, int C, int L) {
-    typedef bf16_t T;
     constexpr int K = 64, NP = 4, V = 8;
     static_assert(BH == 2, "4 x 2 pixel blocks: 8 GEMM rows per block");
     __shared__ __attribute__((aligned(16))) unsigned char slab[128 * 256];     // [128 px][256 B]
@@ -336,7 +335,7 @@ __global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__
         gm = gm < nblk ? gm : nblk - 1;
         const int bxm = (int)(gm % bw), bym = (int)((gm / bw) % bh);
         const long im = gm / ((long)bw * bh);
-        const bf16_t* xp = x0 + ((im * H0 + BH * bym + ((m >> 2) & 1)) * W0 + 4 * bxm + (m & 3)) * K;
+        const T* xp = x0 + ((im * H0 + BH * bym + ((m >> 2) & 1)) * W0 + 4 * bxm + (m & 3)) * K;
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) xf[ks] = *reinterpret_cast<const u32x4*>(xp + (ks * 2 + lh) * 8);
     }
@@ -387,7 +386,7 @@ __global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__
                 for (int r = 0; r < 16; ++r) za[j][r] = 0.f;
 #pragma unroll
                 for (int ks = 0; ks < 4; ++ks)
-                    za[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[j][ks]), __builtin_bit_cast(bf16x8, xf[ks]), za[j], 0, 0, 0);
+                    za[j] = H16<T>::mfma(wf[j][ks], xf[ks], za[j]);
             }
             const int row = wv * 32 + lr;
 #pragma unroll
@@ -395,10 +394,10 @@ __global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float bq[4];
-                    load4(reinterpret_cast<const bf16_t*>(&braw[j][q]), bq);
+                    load4(reinterpret_cast<const T*>(&braw[j][q]), bq);
                     const int chunk = j * 4 + q;
                     *reinterpret_cast<uint2*>(slab + row * 256 + ((chunk ^ (row & 15)) << 4) + lh * 8) =
-                        make_uint2(pack2(za[j][4 * q] + bq[0], za[j][4 * q + 1] + bq[1]), pack2(za[j][4 * q + 2] + bq[2], za[j][4 * q + 3] + bq[3]));
+                        make_uint2(H16<T>::pk(za[j][4 * q] + bq[0], za[j][4 * q + 1] + bq[1]), H16<T>::pk(za[j][4 * q + 2] + bq[2], za[j][4 * q + 3] + bq[3]));
                 }
         }
         __syncthreads();
@@ -430,9 +429,9 @@ __global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__
 #pragma unroll
                 for (int i = 0; i < NP; ++i) {
                     const f32x2 yv = f32x2{fmaxf(v[py][px][i].x, 0.f), fmaxf(v[py][px][i].y, 0.f)};
-                    const bf16x2_t yb = __builtin_convertvector(yv, bf16x2_t);
-                    acc[py][px][0] = __builtin_amdgcn_fdot2_f32_bf16(yb, __builtin_bit_cast(bf16x2_t, w0u[i]), acc[py][px][0], false);
-                    acc[py][px][1] = __builtin_amdgcn_fdot2_f32_bf16(yb, __builtin_bit_cast(bf16x2_t, w1u[i]), acc[py][px][1], false);
+                    const typename H16<T>::x2 yb = H16<T>::cvt(yv);
+                    acc[py][px][0] = H16<T>::dot2(yb, w0u[i], acc[py][px][0]);
+                    acc[py][px][1] = H16<T>::dot2(yb, w1u[i], acc[py][px][1]);
                 }
     }
 #undef HZ_LOADW
@@ -452,16 +451,14 @@ __global__ __launch_bounds__(256) void head_z0_kernel(const bf16_t* __restrict__
             }
 }
 
-static inline int launch_head_z0(const bf16_t* x0, const bf16_t* A0, const bf16_t* zb, const bf16_t* z1, const bf16_t* z2, const bf16_t* z3,
-                                 const bf16_t* w, const bf16_t* bias, float* planes, int B, int H0, int W0, int K, int C, int L, hipStream_t s) {
+template <typename T>
+static inline int launch_head_z0(const T* x0, const T* A0, const T* zb, const T* z1, const T* z2, const T* z3,
+                                 const T* w, const T* bias, float* planes, int B, int H0, int W0, int K, int C, int L, hipStream_t s) {
     if (K != 64 || C % 128 || L > 2 || H0 % 8 || W0 % 8 || !zb) return SA_ERR_SHAPE;
     const long nblk = (long)B * (H0 / 2) * (W0 / 4);
-    hipLaunchKernelGGL((head_z0_kernel<2, 4, 8, 2>), dim3((unsigned)cdivl(nblk, 16)), dim3(256), 0, s, x0, A0, zb, z1, z2, z3, w, bias, planes, B, H0, W0, C, L);
+    hipLaunchKernelGGL((head_z0_kernel<T, 2, 4, 8, 2>), dim3((unsigned)cdivl(nblk, 16)), dim3(256), 0, s, x0, A0, zb, z1, z2, z3, w, bias, planes, B, H0, W0, C, L);
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_head_z0(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, float*, int, int, int, int, int,
-                                 int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 // ---------------------------------------------------------------------------------------------------
 // MBConv tail (encoderdecoder.py:174-225): depthwise 3x3 (+ bias + Hardswish) -> projection 1x1 (+ folded BN bias, + residual).
@@ -483,10 +480,10 @@ static inline int launch_head_z0(const T*, const T*, const T*, const T*, const T
 #ifndef SA_DWP_ABL
 #define SA_DWP_ABL 0     // ablation builds (tools/microbench/dwproj_ablate.sh): 1 = producers never re-request inputs, 2 = consumers skip the MFMAs, 4 = producers skip the depthwise arithmetic, 8 = consumers never re-request W
 #endif
-template <int S>
-__global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ wd, const bf16_t* __restrict__ bd,
-                                                     const bf16_t* __restrict__ w2, const bf16_t* __restrict__ b2,
-                                                     const bf16_t* __restrict__ res, bf16_t* __restrict__ out, int H, int W, int Cm, int Ho, int Wo,
+template <typename T, int S>
+__global__ __launch_bounds__(512) void dwproj_kernel(const T* __restrict__ in, const T* __restrict__ wd, const T* __restrict__ bd,
+                                                     const T* __restrict__ w2, const T* __restrict__ b2,
+                                                     const T* __restrict__ res, T* __restrict__ out, int H, int W, int Cm, int Ho, int Wo,
                                                      int Cout, int tiles_x, int tiles_y) {
     constexpr int CW = 256, TX = 4, NIN = (TX - 1) * S + 3;
     constexpr int WRING = 65536, WSLOT = 1280;              // LDS: [0, 32 KiB) A tiles; [0, 64 KiB) the output tile (epilogue); then the tap ring
@@ -506,7 +503,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
         const int pt = tid - 256;
         const int dch = pt & 7, dxg = (pt >> 3) & 3, dy = pt >> 5;
         const int iy0 = (oy0 + dy) * S - 1, ix0 = (ox0 + dxg * TX) * S - 1;
-        const bf16_t* img = in + (long)b * H * W * Cm + dch * 8;
+        const T* img = in + (long)b * H * W * Cm + dch * 8;
         int roff[3], coff[NIN];                              // (sums and masks are formed per load: 3 x NIN of each kept live spill)
         unsigned rmask[3], cmask[NIN];
 #pragma unroll
@@ -515,7 +512,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
         for (int j = 0; j < NIN; ++j) { const int ix = ix0 + j; coff[j] = min(max(ix, 0), W - 1) * Cm; cmask[j] = (unsigned)ix < (unsigned)W ? 0xffffffffu : 0u; }
         // tap ring: thread pt < 80 carries 16 bytes of (tap pt >> 3 | bias = row 9), channels (pt & 7) * 8 of the chunk
         const bool wl = pt < 80;
-        const bf16_t* wsrc = (pt >> 3) < 9 ? wd + (long)(pt >> 3) * Cm + (pt & 7) * 8 : bd + (pt & 7) * 8;
+        const T* wsrc = (pt >> 3) < 9 ? wd + (long)(pt >> 3) * Cm + (pt & 7) * 8 : bd + (pt & 7) * 8;
         u32x4 wld;
         if (wl) {
             *reinterpret_cast<u32x4*>(smem + WRING + pt * 16) = *reinterpret_cast<const u32x4*>(wsrc);
@@ -538,7 +535,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
             f32x2 a2[TX][4];
             {
                 f32x2 bv[4];
-                UpsumPk<bf16_t>::unpack(*reinterpret_cast<const uint4*>(ws + 9 * 128), bv);
+                UpsumPk<T>::unpack(*reinterpret_cast<const uint4*>(ws + 9 * 128), bv);
 #pragma unroll
                 for (int o = 0; o < TX; ++o)
 #pragma unroll
@@ -549,12 +546,12 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
             for (int ky = 0; ky < 3; ++ky) {
                 f32x2 w3[3][4];
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx) UpsumPk<bf16_t>::unpack(*reinterpret_cast<const uint4*>(ws + (ky * 3 + kx) * 128), w3[kx]);
+                for (int kx = 0; kx < 3; ++kx) UpsumPk<T>::unpack(*reinterpret_cast<const uint4*>(ws + (ky * 3 + kx) * 128), w3[kx]);
 #pragma unroll
                 for (int j = 0; j < NIN; ++j) {
                     const unsigned m = rmask[ky] & cmask[j];
                     f32x2 x[4];
-                    UpsumPk<bf16_t>::unpack(make_uint4(raw[ky][j][0] & m, raw[ky][j][1] & m, raw[ky][j][2] & m, raw[ky][j][3] & m), x);
+                    UpsumPk<T>::unpack(make_uint4(raw[ky][j][0] & m, raw[ky][j][1] & m, raw[ky][j][2] & m, raw[ky][j][3] & m), x);
                     if constexpr (!(SA_DWP_ABL & 1)) raw[ky][j] = *reinterpret_cast<const u32x4*>(img + (roff[ky] + coff[j] + cn));       // its last use was the line above
 #pragma unroll
                     for (int o = 0; o < TX; ++o) {
@@ -580,7 +577,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
                 }
                 const int row = dy * 16 + dxg * TX + o;
                 *reinterpret_cast<uint4*>(smem + (c & 1) * 16384 + row * 128 + ((dch ^ ((row >> 1) & 7)) << 4)) =
-                    make_uint4(pack2(r[0], r[1]), pack2(r[2], r[3]), pack2(r[4], r[5]), pack2(r[6], r[7]));
+                    make_uint4(H16<T>::pk(r[0], r[1]), H16<T>::pk(r[2], r[3]), H16<T>::pk(r[4], r[5]), H16<T>::pk(r[6], r[7]));
             }
             __syncthreads();                                 // (B_c) chunk c is in buffer c & 1
         }
@@ -596,7 +593,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
                 for (int r = 0; r < 16; ++r) acc[j][i][r] = 0.f;
         // w2 comes FRAGMENT-MAJOR ([Cm / 64][Cout / 32][4 K steps][64 lanes][8]: det_mbconv.h's mbconv_w2_fragments at engine init): a fragment load is
         // one contiguous KiB instead of 32 cache lines of the row-major [Cout][Cm] weight
-        const bf16_t* w2p = w2 + ((long)((n0 + wv * 64) >> 5) * 4 * 64 + lane) * 8;
+        const T* w2p = w2 + ((long)((n0 + wv * 64) >> 5) * 4 * 64 + lane) * 8;
         const long w2cs = (long)(Cout >> 5) * 4 * 64 * 8;     // elements per 64-channel chunk
         // W fragments: two named sets; all eight 16-byte loads of the NEXT chunk are issued in one burst at the top of a chunk (the four
         // loads of a 128-byte weight row then meet in L1; spread over the chunk, one per kk, every one of them went to L2 again)
@@ -619,7 +616,7 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
             if constexpr (SA_DWP_ABL & 2) { asm volatile("" :: "v"(xf_[0]), "v"(xf_[1]), "v"(xf_[2]), "v"(xf_[3]), "v"(WF[0][kk_]), "v"(WF[1][kk_])); } else \
             _Pragma("unroll") for (int j_ = 0; j_ < 2; ++j_)                                                            \
                 _Pragma("unroll") for (int i_ = 0; i_ < 4; ++i_)                                                        \
-                    acc[j_][i_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WF[j_][kk_]), __builtin_bit_cast(bf16x8, xf_[i_]), acc[j_][i_], 0, 0, 0); \
+                    acc[j_][i_] = H16<T>::mfma(WF[j_][kk_], xf_[i_], acc[j_][i_]); \
         }                                                                                                               \
     }
         DP_LW(wa, 0);
@@ -655,8 +652,8 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
                 for (int q = 0; q < 4; ++q) {
                     const int chunk = (wv * 64 + j * 32 + q * 8) >> 3;
                     *reinterpret_cast<uint2*>(smem + row * ROWB + ((chunk ^ (row & 31)) << 4) + lh * 8) =
-                        make_uint2(pack2(acc[j][i][4 * q] + bq[j][q][0], acc[j][i][4 * q + 1] + bq[j][q][1]),
-                                   pack2(acc[j][i][4 * q + 2] + bq[j][q][2], acc[j][i][4 * q + 3] + bq[j][q][3]));
+                        make_uint2(H16<T>::pk(acc[j][i][4 * q] + bq[j][q][0], acc[j][i][4 * q + 1] + bq[j][q][1]),
+                                   H16<T>::pk(acc[j][i][4 * q + 2] + bq[j][q][2], acc[j][i][4 * q + 3] + bq[j][q][3]));
                 }
         }
     }
@@ -683,8 +680,8 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
             const uint4 rawo = *reinterpret_cast<const uint4*>(smem + row * ROWB + ((cc ^ (row & 31)) << 4));
             if (res) {
                 float a[8], r8[8];
-                unpack16(rawo, a, (bf16_t*)nullptr);
-                unpack16(rr[it], r8, (bf16_t*)nullptr);
+                unpack16(rawo, a, (T*)nullptr);
+                unpack16(rr[it], r8, (T*)nullptr);
                 if (ok[it]) {
                     store4(out + offs[it], a[0] + r8[0], a[1] + r8[1], a[2] + r8[2], a[3] + r8[3]);
                     store4(out + offs[it] + 4, a[4] + r8[4], a[5] + r8[5], a[6] + r8[6], a[7] + r8[7]);
@@ -696,15 +693,16 @@ __global__ __launch_bounds__(512) void dwproj_kernel(const bf16_t* __restrict__ 
     }
 }
 
-static inline int launch_dwproj(const bf16_t* in, const bf16_t* wd, const bf16_t* bd, int act, const bf16_t* w2, const bf16_t* b2, const bf16_t* res,
-                                bf16_t* out, int B, int H, int W, int Cm, int Ho, int Wo, int Cout, int stride, hipStream_t s) {
+template <typename T>
+static inline int launch_dwproj(const T* in, const T* wd, const T* bd, int act, const T* w2, const T* b2, const T* res,
+                                T* out, int B, int H, int W, int Cm, int Ho, int Wo, int Cout, int stride, hipStream_t s) {
     if (Cm % 128 || (Cout != 256 && Cout != 512) || (stride != 1 && stride != 2) || (long)B * H * W * Cm >= (1L << 31) || act != ACT_HSWISH) return SA_ERR_SHAPE;
     const int tx = cdiv(Wo, 16), ty = cdiv(Ho, 8);
     const unsigned grid = (unsigned)(B * tx * ty);
 #define SA_DWPROJ(SS)                                                                                                           \
     {                                                                                                                           \
         constexpr size_t lds = 65536 + 2 * 1280;                                                                                \
-        auto kern = dwproj_kernel<SS>;                                                                                          \
+        auto kern = dwproj_kernel<T, SS>;                                                                                          \
         static AttrOnce attr;                                                                                                   \
         attr.ensure(kern, lds);                                                                                                 \
         hipLaunchKernelGGL(kern, dim3(grid, Cout / 256), dim3(512), lds, s, in, wd, bd, w2, b2, res, out, H, W, Cm, Ho, Wo, Cout, tx, ty); \
@@ -713,9 +711,6 @@ static inline int launch_dwproj(const bf16_t* in, const bf16_t* wd, const bf16_t
 #undef SA_DWPROJ
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_dwproj(const T*, const T*, const T*, int, const T*, const T*, const T*, T*, int, int, int, int, int, int, int, int,
-                                hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 // ---------------------------------------------------------------------------------------------------
 // Stem convolutions: 3x3, 32 output channels, Cin = 8 (the padded RGB input, stride 2) or 32 (the residual ConvBlock), at 512^2 x 16 pages the
@@ -734,22 +729,22 @@ static inline int launch_dwproj(const T*, const T*, const T*, int, const T*, con
 // NHWC pages with SegformerImageProcessor's rescale + normalise -- the input-layout kernels' conversions (nchw_to_nhwc_kernel / u8_to_nhwc_kernel,
 // bit for bit) done in the patch loader, so the 8-channel copy of the page (16 bytes per pixel written and read back: 0.54 GB per 16 pages) never exists.
 struct StemSrc { const float* planes; const unsigned char* u8; float m0, m1, m2, s0, s1, s2; int pix; };
-template <int SRC>
+template <typename T, int SRC>
 __device__ __forceinline__ uint4 stem_pixel(const StemSrc& s, int b, long hw, long p) {
     if constexpr (SRC == 1) {
         const float* q = s.planes + (long)b * 3 * hw + p;
-        return make_uint4(pack2(q[0], q[hw]), pack2(q[2 * hw], 0.f), 0u, 0u);                 // nchw_to_nhwc_kernel's pixel
+        return make_uint4(H16<T>::pk(q[0], q[hw]), H16<T>::pk(q[2 * hw], 0.f), 0u, 0u);                 // nchw_to_nhwc_kernel's pixel
     } else {
 #pragma clang fp contract(off)
         const unsigned char* px = s.u8 + ((long)b * hw + p) * s.pix;                          // u8_to_nhwc_kernel's pixel (float64 rescale rounded once)
         const double k = 1.0 / 255.0;
         const float v0 = ((float)((double)px[0] * k) - s.m0) / s.s0, v1 = ((float)((double)px[1] * k) - s.m1) / s.s1, v2 = ((float)((double)px[2] * k) - s.m2) / s.s2;
-        return make_uint4(pack2(v0, v1), pack2(v2, 0.f), 0u, 0u);
+        return make_uint4(H16<T>::pk(v0, v1), H16<T>::pk(v2, 0.f), 0u, 0u);
     }
 }
-template <int CIN, int S, int EPI, int SRC = 0>      // EPI: 0 = bias + Hardswish, 1 = bias + residual
-__global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w, const bf16_t* __restrict__ bias,
-                                                       const bf16_t* __restrict__ res, bf16_t* __restrict__ out, int H, int W, int Ho, int Wo, int Kpad,
+template <typename T, int CIN, int S, int EPI, int SRC = 0>      // EPI: 0 = bias + Hardswish, 1 = bias + residual
+__global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_kernel(const T* __restrict__ in, const T* __restrict__ w, const T* __restrict__ bias,
+                                                       const T* __restrict__ res, T* __restrict__ out, int H, int W, int Ho, int Wo, int Kpad,
                                                        int tiles_x, int tiles_y, int ntiles, StemSrc src = StemSrc()) {
     static_assert(SRC == 0 || CIN == 8, "pixel sources feed the first convolution only");
     constexpr int TH = 8, TW = 32, PH = (TH - 1) * S + 3, PW = (TW - 1) * S + 3, PB = CIN * 2, CPP = PB / 16;
@@ -774,7 +769,7 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
         const int bid_ = t_begin + min((TL), t_cnt - 1);                                                                \
         const int b_ = bid_ / (tiles_x * tiles_y), tr_ = bid_ - b_ * tiles_x * tiles_y;                                 \
         const int iy0_ = (tr_ / tiles_x) * TH * S - 1, ix0_ = (tr_ % tiles_x) * TW * S - 1;                             \
-        const bf16_t* img_ = in + (long)b_ * H * W * CIN;                                                               \
+        const T* img_ = in + (long)b_ * H * W * CIN;                                                               \
         _Pragma("unroll") for (int i_ = 0; i_ < NPRE; ++i_) {                                                           \
             const int idx_ = min(tid + i_ * 256, PH * PW * CPP - 1), px_ = idx_ / CPP, c_ = idx_ % CPP, pr_ = px_ / PW, pc_ = px_ - pr_ * PW; \
             const int iy_ = iy0_ + pr_, ix_ = ix0_ + pc_;                                                               \
@@ -782,7 +777,7 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
             const long pp_ = (long)min(max(iy_, 0), H - 1) * W + min(max(ix_, 0), W - 1);                               \
             uint4 v_;                                                                                                   \
             if constexpr (SRC == 0) v_ = *reinterpret_cast<const uint4*>(img_ + pp_ * CIN + c_ * 8);                    \
-            else v_ = stem_pixel<SRC>(src, b_, (long)H * W, pp_);                                                       \
+            else v_ = stem_pixel<T, SRC>(src, b_, (long)H * W, pp_);                                                       \
             const unsigned m_ = ok_ ? 0xffffffffu : 0u;      /* unconditional load, masked: no branch between a load and its use */ \
             pre[i_] = make_uint4(v_.x & m_, v_.y & m_, v_.z & m_, v_.w & m_);                                           \
         }                                                                                                               \
@@ -834,7 +829,7 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
                 const int prow = (wv * 2 + i) * S + ky, pcol = lr * S + kx;
                 const int csw = CPP == 4 ? (chunk ^ ((pcol >> 2) & 3)) : chunk;
                 const u32x4 xf = *reinterpret_cast<const u32x4*>(patch + (prow * PW + pcol) * PB + csw * 16);
-                acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[s_]), __builtin_bit_cast(bf16x8, xf), acc[i], 0, 0, 0);
+                acc[i] = H16<T>::mfma(wf[s_], xf, acc[i]);
             }
         }
         __syncthreads();                                     // every wave is done with the patch: the next tile may overwrite it
@@ -853,7 +848,7 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
                 }
                 const int c0 = 8 * (2 * p_ + lh);
                 float bv[8];
-                unpack16(*reinterpret_cast<const uint4*>(bias + c0), bv, (bf16_t*)nullptr);
+                unpack16(*reinterpret_cast<const uint4*>(bias + c0), bv, (T*)nullptr);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) v[e] += bv[e];
                 if (EPI == 0) {
@@ -861,12 +856,12 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
                     for (int e = 0; e < 8; ++e) v[e] = hardswish_f(v[e]);
                 } else {
                     float r8[8];
-                    unpack16(rraw[i][p_], r8, (bf16_t*)nullptr);
+                    unpack16(rraw[i][p_], r8, (T*)nullptr);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] += r8[e];
                 }
                 if (live[i])
-                    *reinterpret_cast<uint4*>(out + obase[i] + c0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+                    *reinterpret_cast<uint4*>(out + obase[i] + c0) = make_uint4(H16<T>::pk(v[0], v[1]), H16<T>::pk(v[2], v[3]), H16<T>::pk(v[4], v[5]), H16<T>::pk(v[6], v[7]));
             }
         }
     }
@@ -874,25 +869,22 @@ __global__ __launch_bounds__(256, CIN == 32 ? 2 : (SRC ? 3 : 4)) void stem_conv_
 }
 
 // Returns SA_ERR_UNSUPPORTED for shapes the kernel does not take (the caller then runs the implicit-GEMM path).
-static inline int launch_stem_conv(const bf16_t* in, const bf16_t* w, const bf16_t* bias, const bf16_t* res, bf16_t* out, int B, int H, int W, int Cin,
+template <typename T>
+static inline int launch_stem_conv(const T* in, const T* w, const T* bias, const T* res, T* out, int B, int H, int W, int Cin,
                                    int Ho, int Wo, int Cout, int k, int stride, int pad, int Kpad, int act, hipStream_t s) {
     if (Cout != 32 || k != 3 || pad != 1 || !bias) return SA_ERR_UNSUPPORTED;
     const int tx = cdiv(Wo, 32), ty = cdiv(Ho, 8), ntiles = B * tx * ty;
     const int wg_per_cu = Cin == 32 ? 2 : 4;                 // by registers (the Cin = 32 kernel holds 72 registers of weight fragments)
     const unsigned grid = (unsigned)std::min(ntiles, 256 * wg_per_cu) / 8 * 8 ? (unsigned)std::min(ntiles, 256 * wg_per_cu) / 8 * 8 : 8u;      // persistent, whole XCD rounds
     if (Cin == 32 && stride == 1 && act == ACT_HSWISH && !res)
-        hipLaunchKernelGGL((stem_conv_kernel<32, 1, 0>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
+        hipLaunchKernelGGL((stem_conv_kernel<T, 32, 1, 0>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
     else if (Cin == 32 && stride == 1 && act == ACT_NONE && res)
-        hipLaunchKernelGGL((stem_conv_kernel<32, 1, 1>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
+        hipLaunchKernelGGL((stem_conv_kernel<T, 32, 1, 1>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
     else if (Cin == 8 && stride == 2 && act == ACT_HSWISH && !res)
-        hipLaunchKernelGGL((stem_conv_kernel<8, 2, 0>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
+        hipLaunchKernelGGL((stem_conv_kernel<T, 8, 2, 0>), dim3(grid), dim3(256), 0, s, in, w, bias, res, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles);
     else
         return SA_ERR_UNSUPPORTED;
     return (int)hipGetLastError();
-}
-template <typename T>
-static inline int launch_stem_conv(const T*, const T*, const T*, const T*, T*, int, int, int, int, int, int, int, int, int, int, int, int, hipStream_t) {
-    return SA_ERR_UNSUPPORTED;
 }
 // ---------------------------------------------------------------------------------------------------
 // The stem's residual block (encoderdecoder.py:367-390: x + conv2(hswish(conv1(x))), two 32 -> 32 3x3 convolutions at half resolution) in ONE kernel:
@@ -909,8 +901,9 @@ static inline int launch_stem_conv(const T*, const T*, const T*, const T*, T*, i
 #ifndef SA_SR_ABL
 #define SA_SR_ABL 0      // timing ablations (results wrong): 1 = no conv1 MFMAs, 2 = no conv2 MFMAs, 4 = no patch requests after the first, 8 = no conv1 epilogue, 16 = no conv2 epilogue
 #endif
-__global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w1, const bf16_t* __restrict__ b1,
-                                                          const bf16_t* __restrict__ w2, const bf16_t* __restrict__ b2, bf16_t* __restrict__ out,
+template <typename T>
+__global__ __launch_bounds__(512, 1) void stem_res_kernel(const T* __restrict__ in, const T* __restrict__ w1, const T* __restrict__ b1,
+                                                          const T* __restrict__ w2, const T* __restrict__ b2, T* __restrict__ out,
                                                           int H, int W, int Kpad, int tiles_x, int tiles_y, int ntiles) {
     constexpr int TH = 8, TW = 32, IH = TH + 2, IW = TW + 2, PH = TH + 4, PW = TW + 4, NI = IH * IW, NIT = (NI + 31) / 32, NSTEP = 18;
     constexpr int PATCHB = PH * PW * 64, INTERB = NIT * 32 * 64;
@@ -934,7 +927,7 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
     }
     u32x4 wf[NSTEP];
     {
-        const bf16_t* w = conv1 ? w1 : w2;
+        const T* w = conv1 ? w1 : w2;
 #pragma unroll
         for (int s_ = 0; s_ < NSTEP; ++s_) wf[s_] = *reinterpret_cast<const u32x4*>(w + (long)lr * Kpad + s_ * 16 + lh * 8);
         // pin the fragments' arrival HERE: left alone, hipcc sinks their s_waitcnt vmcnt(0) to the first MFMA inside the tile loop, where it also waits
@@ -1049,7 +1042,7 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
                     for (int k = 0; k < 2; ++k) {
                         const int csw = chunk ^ (((qx[k] + kx) >> 2) & 3);
                         const u32x4 xf = *reinterpret_cast<const u32x4*>(patch + qoff[k] + (ky * PW + kx) * 64 + csw * 16);
-                        acc[k] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[s_]), __builtin_bit_cast(bf16x8, xf), acc[k], 0, 0, 0);
+                        acc[k] = H16<T>::mfma(wf[s_], xf, acc[k]);
                     }
                 }
                 if (three) {
@@ -1058,7 +1051,7 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
                         const int tap = s_ >> 1, chunk = (s_ & 1) * 2 + lh, ky = tap / 3, kx = tap - ky * 3;
                         const int csw = chunk ^ (((qx[2] + kx) >> 2) & 3);
                         const u32x4 xf = *reinterpret_cast<const u32x4*>(patch + qoff[2] + (ky * PW + kx) * 64 + csw * 16);
-                        acc[2] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[s_]), __builtin_bit_cast(bf16x8, xf), acc[2], 0, 0, 0);
+                        acc[2] = H16<T>::mfma(wf[s_], xf, acc[2]);
                     }
                 }
                 // lane = intermediate pixel (qy, qx), quad g = channels 8 g + 4 lh + (0..3); outside the image the intermediate tensor is zero
@@ -1070,8 +1063,8 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
                     // (a lane past the grid's end repeats pixel NI - 1 -- same inputs, same value: its store is a harmless duplicate, no predicate)
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
-                        const uint32_t p01 = pack2(hardswish_f(acc[k][4 * g] + bq1[g][0]), hardswish_f(acc[k][4 * g + 1] + bq1[g][1])) & m;
-                        const uint32_t p23 = pack2(hardswish_f(acc[k][4 * g + 2] + bq1[g][2]), hardswish_f(acc[k][4 * g + 3] + bq1[g][3])) & m;
+                        const uint32_t p01 = H16<T>::pk(hardswish_f(acc[k][4 * g] + bq1[g][0]), hardswish_f(acc[k][4 * g + 1] + bq1[g][1])) & m;
+                        const uint32_t p23 = H16<T>::pk(hardswish_f(acc[k][4 * g + 2] + bq1[g][2]), hardswish_f(acc[k][4 * g + 3] + bq1[g][3])) & m;
                         *reinterpret_cast<uint2*>(inter + (qy[k] * IW + qx[k]) * 64 + ((g ^ ((qx[k] >> 2) & 3)) << 4) + lh * 8) = make_uint2(p01, p23);
                     }
                 }
@@ -1126,9 +1119,9 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
                         const int csw = chunk ^ ((pcol >> 2) & 3);
                         const u32x4 xf = *reinterpret_cast<const u32x4*>(inter + ((wv * 2 + r) * IW + pcol) * 64 + csw * 16);
                         if (r <= 2)
-                            acc2[0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[(r * 3 + kx) * 2 + hf]), __builtin_bit_cast(bf16x8, xf), acc2[0], 0, 0, 0);
+                            acc2[0] = H16<T>::mfma(wf[(r * 3 + kx) * 2 + hf], xf, acc2[0]);
                         if (r >= 1)
-                            acc2[1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[((r - 1) * 3 + kx) * 2 + hf]), __builtin_bit_cast(bf16x8, xf), acc2[1], 0, 0, 0);
+                            acc2[1] = H16<T>::mfma(wf[((r - 1) * 3 + kx) * 2 + hf], xf, acc2[1]);
                     }
                 }
             }
@@ -1151,12 +1144,12 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
                     }
                     const int c0 = 8 * (2 * p_ + lh);
                     float bv[8], r8[8];
-                    unpack16(b2raw[p_], bv, (bf16_t*)nullptr);
-                    unpack16(rraw[i][p_], r8, (bf16_t*)nullptr);
+                    unpack16(b2raw[p_], bv, (T*)nullptr);
+                    unpack16(rraw[i][p_], r8, (T*)nullptr);
 #pragma unroll
                     for (int e = 0; e < 8; ++e) v[e] = (v[e] + bv[e]) + r8[e];
                     if (live[i])
-                        *reinterpret_cast<uint4*>(out + obase[i] + c0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+                        *reinterpret_cast<uint4*>(out + obase[i] + c0) = make_uint4(H16<T>::pk(v[0], v[1]), H16<T>::pk(v[2], v[3]), H16<T>::pk(v[4], v[5]), H16<T>::pk(v[6], v[7]));
                 }
             }
         }
@@ -1168,31 +1161,31 @@ __global__ __launch_bounds__(512, 1) void stem_res_kernel(const bf16_t* __restri
     }
 }
 
-static inline int launch_stem_res(const bf16_t* in, const bf16_t* w1, const bf16_t* b1, const bf16_t* w2, const bf16_t* b2, bf16_t* out, int B, int H,
+template <typename T>
+static inline int launch_stem_res(const T* in, const T* w1, const T* b1, const T* w2, const T* b2, T* out, int B, int H,
                                   int W, int Kpad, hipStream_t s) {
     if (!b1 || !b2 || (long)H * W * 64 >= (1L << 31) || (long)B * cdiv(W, 32) * cdiv(H, 8) >= (1L << 31)) return SA_ERR_UNSUPPORTED;   // (per-image byte offsets are 32-bit; find_fusions checks the same)
     const int tx = cdiv(W, 32), ty = cdiv(H, 8), ntiles = B * tx * ty;
     const unsigned g0 = (unsigned)std::min(ntiles, 256) / 8 * 8, grid = g0 ? g0 : 8u;      // persistent: one workgroup per CU, whole XCD rounds
     const size_t lds = 3 * (12 * 36 * 64) + 2 * (11 * 32 * 64);
-    auto kern = stem_res_kernel;
+    auto kern = stem_res_kernel<T>;
     static AttrOnce attr;
     attr.ensure(kern, lds);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, in, w1, b1, w2, b2, out, H, W, Kpad, tx, ty, ntiles);
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_stem_res(const T*, const T*, const T*, const T*, const T*, T*, int, int, int, int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 // The first convolution straight from the caller's pixels (SRC 1 / 2 above)
-static inline int launch_stem_conv_pixels(const StemSrc& src, const bf16_t* w, const bf16_t* bias, bf16_t* out, int B, int H, int W, int Ho, int Wo,
+template <typename T>
+static inline int launch_stem_conv_pixels(const StemSrc& src, const T* w, const T* bias, T* out, int B, int H, int W, int Ho, int Wo,
                                           int Cout, int k, int stride, int pad, int Kpad, int act, hipStream_t s) {
     if (Cout != 32 || k != 3 || pad != 1 || !bias || stride != 2 || act != ACT_HSWISH || (!src.planes && !src.u8)) return SA_ERR_UNSUPPORTED;
     const int tx = cdiv(Wo, 32), ty = cdiv(Ho, 8), ntiles = B * tx * ty;
     const unsigned g0 = (unsigned)std::min(ntiles, 256 * 3) / 8 * 8, grid = g0 ? g0 : 8u;
     if (src.planes)
-        hipLaunchKernelGGL((stem_conv_kernel<8, 2, 0, 1>), dim3(grid), dim3(256), 0, s, (const bf16_t*)nullptr, w, bias, (const bf16_t*)nullptr, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles, src);
+        hipLaunchKernelGGL((stem_conv_kernel<T, 8, 2, 0, 1>), dim3(grid), dim3(256), 0, s, (const T*)nullptr, w, bias, (const T*)nullptr, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles, src);
     else
-        hipLaunchKernelGGL((stem_conv_kernel<8, 2, 0, 2>), dim3(grid), dim3(256), 0, s, (const bf16_t*)nullptr, w, bias, (const bf16_t*)nullptr, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles, src);
+        hipLaunchKernelGGL((stem_conv_kernel<T, 8, 2, 0, 2>), dim3(grid), dim3(256), 0, s, (const T*)nullptr, w, bias, (const T*)nullptr, out, H, W, Ho, Wo, Kpad, tx, ty, ntiles, src);
     return (int)hipGetLastError();
 }
 
@@ -1234,11 +1227,11 @@ static inline int launch_stem_conv_pixels(const StemSrc& src, const bf16_t* w, c
 #ifndef SA_FMB_ABL
 #define SA_FMB_ABL 0                     // timing ablations (tools/microbench/fmb_ablate.sh; results are wrong with any bit set): 1 chunk epilogue without
 #endif                                   // bias + Hardswish, 2 no W1 ring requests after a tile's first, 4 no patch requests, 8 one K stage per chunk
-template <int CIN, int S, int MCH>      // MCH = mid channels per chunk: 128 (one workgroup per CU) or 64 (half the accumulators: two workgroups per CU,
+template <typename T, int CIN, int S, int MCH>      // MCH = mid channels per chunk: 128 (one workgroup per CU) or 64 (half the accumulators: two workgroups per CU,
                                         // one multiplying while the other runs its chunk epilogue on the vector ALU)
-__global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w1, const bf16_t* __restrict__ b1,
-                                                 const bf16_t* __restrict__ w2, const bf16_t* __restrict__ b2, const bf16_t* __restrict__ res,
-                                                 bf16_t* __restrict__ out, const bf16_t* __restrict__ zero, int H, int W, int Ho, int Wo, int MID,
+__global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const T* __restrict__ in, const T* __restrict__ w1, const T* __restrict__ b1,
+                                                 const T* __restrict__ w2, const T* __restrict__ b2, const T* __restrict__ res,
+                                                 T* __restrict__ out, const T* __restrict__ zero, int H, int W, int Ho, int Wo, int MID,
                                                  int Kpad, int tiles_x, int tiles_y, int ntiles) {
     constexpr int COUT = 64, TH = 8, TW = 32, PH = (TH - 1) * S + 3, PW = (TW - 1) * S + 3, PB = CIN * 2, CPP = CIN / 8;
     constexpr int SH = CPP == 4 ? 2 : (CPP == 8 ? 1 : 0), KS_TAP = CIN / 16, NKT = (9 * CIN + 63) / 64;
@@ -1388,7 +1381,7 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
     {                                                                                                                   \
         _Pragma("unroll") for (int j_ = 0; j_ < NJ; ++j_)                                                               \
             _Pragma("unroll") for (int i_ = 0; i_ < 2; ++i_)                                                            \
-                sacc[j_][i_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WF[j_]), __builtin_bit_cast(bf16x8, XF[i_]), sacc[j_][i_], 0, 0, 0); \
+                sacc[j_][i_] = H16<T>::mfma(WF[j_], XF[i_], sacc[j_][i_]); \
     }
 #define FM_SGB()                                                                                                        \
     {                                                                                                                   \
@@ -1445,7 +1438,7 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
                         // form was ~8 vector instructions per value at one wave per SIMD (107 of op 4's 589 us, SA_FMB_ABL = 1). Same operations as
                         // hardswish_f(s + b), every step one fp32 rounding.
                         float bq[4];
-                        load4(reinterpret_cast<const bf16_t*>(&b1r[j][g]), bq);
+                        load4(reinterpret_cast<const T*>(&b1r[j][g]), bq);
 #if SA_FMB_PK
                       if (MCH == 128) {
 #pragma unroll
@@ -1454,7 +1447,7 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
                             if (!(SA_FMB_ABL & 1)) {
                                 x = hardswish_pk(x + f32x2{bq[2 * h], bq[2 * h + 1]});
                             }
-                            pk[g][h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2_t));
+                            pk[g][h] = __builtin_bit_cast(uint32_t, H16<T>::cvt(x));
                         }
                       } else
 #endif
@@ -1462,7 +1455,7 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
                         float v[4];
 #pragma unroll
                         for (int r = 0; r < 4; ++r) v[r] = (SA_FMB_ABL & 1) ? sacc[j][i][4 * g + r] : hardswish_f(sacc[j][i][4 * g + r] + bq[r]);
-                        pk[g][0] = pack2(v[0], v[1]); pk[g][1] = pack2(v[2], v[3]);
+                        pk[g][0] = H16<T>::pk(v[0], v[1]); pk[g][1] = H16<T>::pk(v[2], v[3]);
                       }
                     }
 #pragma unroll
@@ -1474,7 +1467,7 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
                         const int s2 = j * 2 + p_;
 #pragma unroll
                         for (int j2 = 0; j2 < 2; ++j2)
-                            oacc[j2][i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w2f[j2][s2]), __builtin_bit_cast(bf16x8, x2), oacc[j2][i], 0, 0, 0);
+                            oacc[j2][i] = H16<T>::mfma(w2f[j2][s2], x2, oacc[j2][i]);
                     }
                 }
         }
@@ -1497,17 +1490,17 @@ __global__ __launch_bounds__(256, MCH == 64 ? 2 : 1) void fmb_kernel(const bf16_
                     }
                     const int c0 = j2 * 32 + 8 * (2 * p_ + lh);
                     float bv[8];
-                    unpack16(*reinterpret_cast<const uint4*>(b2 + c0), bv, (bf16_t*)nullptr);
+                    unpack16(*reinterpret_cast<const uint4*>(b2 + c0), bv, (T*)nullptr);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) v[e] = Ty<bf16_t>::rnd(v[e] + bv[e]);
+                    for (int e = 0; e < 8; ++e) v[e] = Ty<T>::rnd(v[e] + bv[e]);
                     if (res) {
                         float r8[8];
-                        unpack16(*reinterpret_cast<const uint4*>(res + obase + c0), r8, (bf16_t*)nullptr);
+                        unpack16(*reinterpret_cast<const uint4*>(res + obase + c0), r8, (T*)nullptr);
 #pragma unroll
                         for (int e = 0; e < 8; ++e) v[e] += r8[e];
                     }
                     if (live)
-                        *reinterpret_cast<uint4*>(out + obase + c0) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+                        *reinterpret_cast<uint4*>(out + obase + c0) = make_uint4(H16<T>::pk(v[0], v[1]), H16<T>::pk(v[2], v[3]), H16<T>::pk(v[4], v[5]), H16<T>::pk(v[6], v[7]));
                 }
         }
     }
@@ -1521,8 +1514,9 @@ static inline bool fmb_shape_ok(int cin, int mid, int cout, int stride, int ho, 
     return cout == 64 && mid % 128 == 0 && ((cin == 64 && stride == 1) || (cin == 32 && stride == 2));
 }
 
-static inline int launch_fmb(const bf16_t* in, const bf16_t* w1, const bf16_t* b1, const bf16_t* w2, const bf16_t* b2, const bf16_t* res, bf16_t* out,
-                             const bf16_t* zero, int B, int H, int W, int Cin, int Ho, int Wo, int Mid, int Cout, int stride, int pad, int Kpad,
+template <typename T>
+static inline int launch_fmb(const T* in, const T* w1, const T* b1, const T* w2, const T* b2, const T* res, T* out,
+                             const T* zero, int B, int H, int W, int Cin, int Ho, int Wo, int Mid, int Cout, int stride, int pad, int Kpad,
                              hipStream_t s) {
     if (!fmb_shape_ok(Cin, Mid, Cout, stride, Ho, Wo) || pad != 1 || !b1 || !b2) return SA_ERR_SHAPE;
     const int tx = cdiv(Wo, 32), ty = cdiv(Ho, 8), ntiles = B * tx * ty;
@@ -1530,7 +1524,7 @@ static inline int launch_fmb(const bf16_t* in, const bf16_t* w1, const bf16_t* b
     {                                                                                                                           \
         constexpr int PH_ = 7 * (SS) + 3, PW_ = 31 * (SS) + 3;                                                                  \
         constexpr size_t lds = (size_t)((PH_ * PW_ * (CI) * 2 + 1023) & ~1023) + ((MC) == 64 ? 2 * 2 : (SA_FMB_NB3 ? 3 : 2)) * (MC) * 128; \
-        auto kern = fmb_kernel<CI, SS, MC>;                                                                                     \
+        auto kern = fmb_kernel<T, CI, SS, MC>;                                                                                     \
         static AttrOnce attr;                                                                                                   \
         attr.ensure(kern, lds);                                                                                                 \
         const unsigned g_ = (unsigned)std::max(8, std::min(ntiles, 256 * (WGS)) / 8 * 8);                                       \
@@ -1541,8 +1535,5 @@ static inline int launch_fmb(const bf16_t* in, const bf16_t* w1, const bf16_t* b
 #undef SA_FMB
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_fmb(const T*, const T*, const T*, const T*, const T*, const T*, T*, const T*, int, int, int, int, int, int, int, int, int, int,
-                             int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 }  // namespace sa

@@ -33,9 +33,10 @@ __device__ __forceinline__ void head_axis_weights(int p, int R, int& i0, float& 
     f = src - fl;
 }
 
-__global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restrict__ x0, const bf16_t* __restrict__ A0f, const bf16_t* __restrict__ zb,
-                                                           const bf16_t* __restrict__ z1, const bf16_t* __restrict__ z2, const bf16_t* __restrict__ z3,
-                                                           const bf16_t* __restrict__ w, const bf16_t* __restrict__ bias, float* __restrict__ out,
+template <typename T>
+__global__ __launch_bounds__(256, 3) void head_mfma_kernel(const T* __restrict__ x0, const T* __restrict__ A0f, const T* __restrict__ zb,
+                                                           const T* __restrict__ z1, const T* __restrict__ z2, const T* __restrict__ z3,
+                                                           const T* __restrict__ w, const T* __restrict__ bias, float* __restrict__ out,
                                                            int B, int H0, int W0, int C, int L, int ntiles) {
     // Second version (the first held a 128-channel slab's A0 fragments in registers: 16 KiB requested by EACH of the four waves per slab -- 22
     // vector-memory requests per wave and step, 88 KiB through the CU's 64 B/clk L1 path per workgroup-step against 2560 cycles of MFMA -- and ran two
@@ -78,7 +79,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
                 const float wy = dy == 0 ? 1.0f - fys : (dy == 1 ? fys : 0.0f), wx = dx == 0 ? 1.0f - fxs : (dx == 1 ? fxs : 0.0f);
                 v[e] = wy * wx;
             }
-            wt[s] = u32x4{pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7])};
+            wt[s] = u32x4{H16<T>::pk(v[0], v[1]), H16<T>::pk(v[2], v[3]), H16<T>::pk(v[4], v[5]), H16<T>::pk(v[6], v[7])};
         }
     }
     // ---- tap requests: request i of this wave (q = wv * 3 + i) fills LDS rows q * 8 + (lane >> 3) of the tap buffer (128-byte rows), physical chunk
@@ -86,7 +87,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
     // z1 / z2 (tap 60), request 10 z2 / z3 (tap 84): the source pointer is per lane.
     const int h1 = H0 / 2, w1 = W0 / 2, h2 = H0 / 4, w2 = W0 / 4, h3 = H0 / 8, w3 = W0 / 8;
     const int tiles_x = (W0 + TW - 1) / TW, tiles_y = H0 / TH;      // W0 is a multiple of 8: the last tile of a row may be half outside (clamped loads, no stores)
-    const bf16_t* zptr[3];
+    const T* zptr[3];
     const int zchunk = (((lane & 7) ^ ((((lane >> 3) >> 1) & 1) << 1)) << 3);     // element offset of this lane's 16 bytes inside a 64-channel slab row
     // tr-read addressing (attn_mfma.h): 16-lane group gi covers channels (gi & 1) * 16 .. + 15 of a 32-channel tile for tap half lh; lane i of the group
     // supplies the address of tap row (i >> 2), channels (i & 3) * 4 .. + 3. Row pitch 128 bytes; the chunk XOR flips bit 1 only (never the tile bit).
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
     const int per = ntiles >> 3, rem = ntiles & 7;
     const int t_begin = xcd * per + min(xcd, rem), t_cnt = per + (xcd < rem ? 1 : 0);
     const long HW = (long)H0 * W0;
-    const float blv[2] = {Ty<bf16_t>::ld(bias), Ty<bf16_t>::ld(bias + (L > 1 ? 1 : 0))};
+    const float blv[2] = {Ty<T>::ld(bias), Ty<T>::ld(bias + (L > 1 ? 1 : 0))};
 
 #define HM_TILE(TL, IMG, Y0, X0)                                                                                        \
     {                                                                                                                   \
@@ -139,7 +140,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
     }
 #define HM_LOADX(XF, IMG, Y0, X0)                                                                                       \
     {                                                                                                                   \
-        const bf16_t* xp_ = x0 + (((long)(IMG) * H0 + (Y0) + py) * W0 + min((X0) + px, W0 - 1)) * K0 + lh * 8;           \
+        const T* xp_ = x0 + (((long)(IMG) * H0 + (Y0) + py) * W0 + min((X0) + px, W0 - 1)) * K0 + lh * 8;           \
         _Pragma("unroll") for (int ks_ = 0; ks_ < 4; ++ks_) XF[ks_] = *reinterpret_cast<const u32x4*>(xp_ + ks_ * 16);  \
     }
 
@@ -185,7 +186,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
                 for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                     for (int j = 0; j < 2; ++j)
-                        acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, af[j][ks]), __builtin_bit_cast(bf16x8, xf[ks]), acc[j], 0, 0, 0);
+                        acc[j] = H16<T>::mfma(af[j][ks], xf[ks], acc[j]);
             }
             if (last) HM_LOADX(xf, nimg, ny0, nx0);          // (this tile's last use of xf was the z0 part above)
             // interpolation part: Z^T fragments of (step, tile) f + 1 are read while f multiplies
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
         const s16x4 hi_ = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp_ + troff[1])); \
         ZF = __builtin_shufflevector(lo_, hi_, 0, 1, 2, 3, 4, 5, 6, 7);                                                 \
     }
-#define HM_MZ(ZF, F) acc[(F) & 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, ZF), __builtin_bit_cast(bf16x8, wt[(F) >> 1]), acc[(F) & 1], 0, 0, 0);
+#define HM_MZ(ZF, F) acc[(F) & 1] = H16<T>::mfma(ZF, wt[(F) >> 1], acc[(F) & 1]);
             {
                 s16x8 za, zb2;
                 HM_RZ(za, 0);
@@ -225,14 +226,14 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     float bq[4];
-                    load4(reinterpret_cast<const bf16_t*>(&cb[q]), bq);
+                    load4(reinterpret_cast<const T*>(&cb[q]), bq);
                     const f32x2 v01 = f32x2{fmaxf(acc[j][4 * q] + bq[0], 0.f), fmaxf(acc[j][4 * q + 1] + bq[1], 0.f)};
                     const f32x2 v23 = f32x2{fmaxf(acc[j][4 * q + 2] + bq[2], 0.f), fmaxf(acc[j][4 * q + 3] + bq[3], 0.f)};
-                    const bf16x2_t y01 = __builtin_convertvector(v01, bf16x2_t), y23 = __builtin_convertvector(v23, bf16x2_t);
-                    p0 = __builtin_amdgcn_fdot2_f32_bf16(y01, __builtin_bit_cast(bf16x2_t, wa[q].x), p0, false);
-                    p0 = __builtin_amdgcn_fdot2_f32_bf16(y23, __builtin_bit_cast(bf16x2_t, wa[q].y), p0, false);
-                    p1 = __builtin_amdgcn_fdot2_f32_bf16(y01, __builtin_bit_cast(bf16x2_t, wb[q].x), p1, false);
-                    p1 = __builtin_amdgcn_fdot2_f32_bf16(y23, __builtin_bit_cast(bf16x2_t, wb[q].y), p1, false);
+                    const typename H16<T>::x2 y01 = H16<T>::cvt(v01), y23 = H16<T>::cvt(v23);
+                    p0 = H16<T>::dot2(y01, wa[q].x, p0);
+                    p0 = H16<T>::dot2(y23, wa[q].y, p0);
+                    p1 = H16<T>::dot2(y01, wb[q].x, p1);
+                    p1 = H16<T>::dot2(y23, wb[q].y, p1);
                 }
             }
         }
@@ -240,8 +241,8 @@ __global__ __launch_bounds__(256, 3) void head_mfma_kernel(const bf16_t* __restr
         p0 += __shfl_xor(p0, 32, 64);
         p1 += __shfl_xor(p1, 32, 64);
         if (lh < L && x0c + px < W0) {
-            const float z = Ty<bf16_t>::rnd((lh ? p1 : p0) + blv[lh]);
-            out[((long)img * L + lh) * HW + (long)(y0 + py) * W0 + x0c + px] = Ty<bf16_t>::rnd(1.0f / (1.0f + expf(-z)));
+            const float z = Ty<T>::rnd((lh ? p1 : p0) + blv[lh]);
+            out[((long)img * L + lh) * HW + (long)(y0 + py) * W0 + x0c + px] = Ty<T>::rnd(1.0f / (1.0f + expf(-z)));
         }
         img = nimg; y0 = ny0; x0c = nx0;
     }
@@ -257,12 +258,13 @@ static inline bool head_mfma_shape_ok(int H0, int W0, int K, int C, int L) {
     return K == 64 && C % 64 == 0 && C <= 1024 && L >= 1 && L <= 2 && H0 % 8 == 0 && W0 % 8 == 0 && H0 >= 16 && W0 >= 32;
 }
 
-static inline int launch_head_mfma(const bf16_t* x0, const bf16_t* A0f, const bf16_t* zb, const bf16_t* z1, const bf16_t* z2, const bf16_t* z3,
-                                   const bf16_t* w, const bf16_t* bias, float* planes, int B, int H0, int W0, int K, int C, int L, hipStream_t s) {
+template <typename T>
+static inline int launch_head_mfma(const T* x0, const T* A0f, const T* zb, const T* z1, const T* z2, const T* z3,
+                                   const T* w, const T* bias, float* planes, int B, int H0, int W0, int K, int C, int L, hipStream_t s) {
     if (!head_mfma_shape_ok(H0, W0, K, C, L) || !zb || (long)B * (H0 / 2) * (W0 / 2) * C >= (1L << 31)) return SA_ERR_SHAPE;
     const int ntiles = B * (H0 / 8) * ((W0 + 15) / 16);
     const size_t lds = 2 * 96 * 128 + 2 * 8192 + (size_t)C * 6;
-    auto kern = head_mfma_kernel;
+    auto kern = head_mfma_kernel<T>;
     static AttrOnce attr;
     attr.ensure(kern, lds);
     int dev = 0, n_cu = 0;
@@ -272,8 +274,5 @@ static inline int launch_head_mfma(const bf16_t* x0, const bf16_t* A0f, const bf
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, x0, A0f, zb, z1, z2, z3, w, bias, planes, B, H0, W0, C, L, ntiles);
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_head_mfma(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, float*, int, int, int, int, int,
-                                   int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 }  // namespace sa

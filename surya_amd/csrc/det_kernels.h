@@ -25,7 +25,7 @@ __global__ void nchw_to_nhwc_kernel(const float* __restrict__ in, T* __restrict_
             float v[8];
 #pragma unroll
             for (int c = 0; c < 8; ++c) v[c] = c < C ? in[(b * C + c) * hw + r] : 0.f;
-            *reinterpret_cast<uint4*>(o) = make_uint4(pack2(v[0], v[1]), pack2(v[2], v[3]), pack2(v[4], v[5]), pack2(v[6], v[7]));
+            *reinterpret_cast<uint4*>(o) = make_uint4(H16<T>::pk(v[0], v[1]), H16<T>::pk(v[2], v[3]), H16<T>::pk(v[4], v[5]), H16<T>::pk(v[6], v[7]));
             return;
         }
     }
@@ -49,7 +49,7 @@ __global__ void u8_to_nhwc_kernel(const unsigned char* __restrict__ in, T* __res
     const float v0 = ((float)((double)px[0] * k) - m0) / s0, v1 = ((float)((double)px[1] * k) - m1) / s1, v2 = ((float)((double)px[2] * k) - m2) / s2;
     if constexpr (sizeof(T) == 2) {
         if (CP == 8) {                                       // one 16-byte store per pixel (see nchw_to_nhwc_kernel)
-            *reinterpret_cast<uint4*>(o) = make_uint4(pack2(v0, v1), pack2(v2, 0.f), 0u, 0u);
+            *reinterpret_cast<uint4*>(o) = make_uint4(H16<T>::pk(v0, v1), H16<T>::pk(v2, 0.f), 0u, 0u);
             return;
         }
     }
@@ -364,7 +364,7 @@ static inline int launch_conv(const ConvArgs<T>& a_in, hipStream_t s) {
     a.fcin = make_fastdiv((unsigned)a.Cin); a.fkw = make_fastdiv((unsigned)a.KW);
     a.fhw = make_fastdiv((unsigned)(a.Ho * a.Wo)); a.fwo = make_fastdiv((unsigned)a.Wo);
     const long M = (long)a.B * a.Ho * a.Wo;
-    if constexpr (std::is_same<T, bf16_t>::value) {
+    if constexpr (sizeof(T) == 2) {
         // (the 32-channel stem convolutions stay on the register-staged kernel: 128x32 tiles measured 5-15 % slower on the gather)
         if (a.zero && a.Cout >= 64 && a.Cout % 8 == 0 && M < (1L << 31)) {
             if (a.res && a.act == ACT_NONE) return launch_conv_on_gemm<T, EPI_RESIDUAL>(a, s);
@@ -893,19 +893,18 @@ template <int R, int BH> struct UpsumGeo {              // BH = pixel rows of th
 
 // The arithmetic runs on fp32 PAIRS (v_pk_mul_f32 / v_pk_fma_f32: the first blocked version spent ~30 scalar VALU operations per value
 // -- 1.14 ms per 16 pages, gpurun r04k, VALU-bound at one wave per SIMD -- unpack, two interpolation passes, a software bf16 rounding
-// and two multiply-adds); the bf16 path rounds y with v_cvt_pk_bf16_f32 and feeds the classifier's bf16 weight pairs to
-// v_dot2c_f32_bf16 (exact products, fp32 accumulation).
+// and two multiply-adds); the 16-bit paths round y with v_cvt_pk_bf16_f32 / v_cvt_pk_f16_f32 and feed the classifier's weight pairs to
+// v_dot2c_f32_bf16 / v_dot2c_f32_f16 (exact products, fp32 accumulation).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 
-template <typename T> struct UpsumPk;
-template <> struct UpsumPk<bf16_t> {
+template <typename T> struct UpsumPk {                       // bf16 and fp16 (H16<T>)
     static constexpr int NP = 4;                             // pairs per 16-byte chunk
     __device__ __forceinline__ static void unpack(const uint4& r, f32x2 (&o)[4]) {
-        o[0] = f32x2{__uint_as_float(r.x << 16), __uint_as_float(r.x & 0xffff0000u)};
-        o[1] = f32x2{__uint_as_float(r.y << 16), __uint_as_float(r.y & 0xffff0000u)};
-        o[2] = f32x2{__uint_as_float(r.z << 16), __uint_as_float(r.z & 0xffff0000u)};
-        o[3] = f32x2{__uint_as_float(r.w << 16), __uint_as_float(r.w & 0xffff0000u)};
+        o[0] = f32x2{H16<T>::lo(r.x), H16<T>::hi(r.x)};
+        o[1] = f32x2{H16<T>::lo(r.y), H16<T>::hi(r.y)};
+        o[2] = f32x2{H16<T>::lo(r.z), H16<T>::hi(r.z)};
+        o[3] = f32x2{H16<T>::lo(r.w), H16<T>::hi(r.w)};
     }
 };
 template <> struct UpsumPk<float> {
@@ -979,7 +978,7 @@ __global__ __launch_bounds__(256) void head_upsum_classify_blk_kernel(const T* _
                                                                       const T* __restrict__ w, const T* __restrict__ bias,
                                                                       float* __restrict__ out, int B, int H0, int W0, int C, int L) {
     constexpr int V = Ty<T>::V16, NP = UpsumPk<T>::NP;
-    constexpr bool BF = std::is_same<T, bf16_t>::value;
+    constexpr bool BF = sizeof(T) == 2;                      // 16-bit storage: dot2 on the rounded y pairs
     const int sub = threadIdx.x & 15;
     const int bw = W0 / 4, bh = H0 / BH;
     const long nblk = (long)B * bh * bw;
@@ -1029,9 +1028,9 @@ __global__ __launch_bounds__(256) void head_upsum_classify_blk_kernel(const T* _
                 for (int i = 0; i < NP; ++i) {
                     const f32x2 yv = f32x2{fmaxf(v[py][px][i].x, 0.f), fmaxf(v[py][px][i].y, 0.f)};
                     if constexpr (BF) {
-                        const bf16x2_t yb = __builtin_convertvector(yv, bf16x2_t);       // y = T(relu(v)), round to nearest even
-                        acc[py][px][0] = __builtin_amdgcn_fdot2_f32_bf16(yb, __builtin_bit_cast(bf16x2_t, w0u[i]), acc[py][px][0], false);
-                        acc[py][px][1] = __builtin_amdgcn_fdot2_f32_bf16(yb, __builtin_bit_cast(bf16x2_t, w1u[i]), acc[py][px][1], false);
+                        const typename H16<T>::x2 yb = H16<T>::cvt(yv);                  // y = T(relu(v)), round to nearest even
+                        acc[py][px][0] = H16<T>::dot2(yb, w0u[i], acc[py][px][0]);
+                        acc[py][px][1] = H16<T>::dot2(yb, w1u[i], acc[py][px][1]);
                     } else {
                         accp[py][px][0] += yv * w0p[i];
                         accp[py][px][1] += yv * w1p[i];

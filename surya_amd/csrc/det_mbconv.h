@@ -39,10 +39,10 @@ namespace sa {
 #define MBC_STAMP(ROLE, IT, K) {}
 #endif
 
-template <int CIN, int S, int TH, int TW, int COUT>
-__global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ in, const bf16_t* __restrict__ w1, const bf16_t* __restrict__ b1,
-                                                     const bf16_t* __restrict__ wd, const bf16_t* __restrict__ bd, const bf16_t* __restrict__ w2,
-                                                     const bf16_t* __restrict__ b2, const bf16_t* __restrict__ res, bf16_t* __restrict__ out,
+template <typename T, int CIN, int S, int TH, int TW, int COUT>
+__global__ __launch_bounds__(512) void mbconv_kernel(const T* __restrict__ in, const T* __restrict__ w1, const T* __restrict__ b1,
+                                                     const T* __restrict__ wd, const T* __restrict__ bd, const T* __restrict__ w2,
+                                                     const T* __restrict__ b2, const T* __restrict__ res, T* __restrict__ out,
                                                      int H, int W, int Ho, int Wo, int Cm, int tiles_x, int tiles_y
 #if SA_MBC_TIMING
                                                      , long long* __restrict__ dbg
@@ -112,7 +112,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
             const bool valid = idx < NROW && (unsigned)iy < (unsigned)H && (unsigned)ix < (unsigned)W;
             emask[t] = valid ? 0xffffffffu : 0u;
             erow[t] = idx * 128 + lh * 8;
-            const bf16_t* src = in + (((long)b * H + min(max(iy, 0), H - 1)) * W + min(max(ix, 0), W - 1)) * CIN + lh * 8;
+            const T* src = in + (((long)b * H + min(max(iy, 0), H - 1)) * W + min(max(ix, 0), W - 1)) * CIN + lh * 8;
 #pragma unroll
             for (int kk = 0; kk < KK1; ++kk) pf[t][kk] = *reinterpret_cast<const u32x4*>(src + kk * 16);
         }
@@ -145,10 +145,10 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
 #define MB_M(WF, KK)                                                                                                    \
     {                                                                                                                   \
         _Pragma("unroll") for (int i_ = 0; i_ < NF; ++i_) {                                                             \
-            acc[2 * i_] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WF[0]), __builtin_bit_cast(bf16x8, pf[i_][KK]), acc[2 * i_], 0, 0, 0); \
-            acc[2 * i_ + 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WF[1]), __builtin_bit_cast(bf16x8, pf[i_][KK]), acc[2 * i_ + 1], 0, 0, 0); \
+            acc[2 * i_] = H16<T>::mfma(WF[0], pf[i_][KK], acc[2 * i_]); \
+            acc[2 * i_ + 1] = H16<T>::mfma(WF[1], pf[i_][KK], acc[2 * i_ + 1]); \
         }                                                                                                               \
-        acc[2 * NF] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, WF[2]), __builtin_bit_cast(bf16x8, pf[NF][KK]), acc[2 * NF], 0, 0, 0); \
+        acc[2 * NF] = H16<T>::mfma(WF[2], pf[NF][KK], acc[2 * NF]); \
     }
 #define MB_SGB()                                                                                                        \
     {                                                                                                                   \
@@ -199,7 +199,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                     for (int g = 0; g < 4; ++g) {
                         float bq[4];
                         const uint2 braw = u < 2 * NF ? b1r[u & 1][g] : (hct ? b1r[1][g] : b1r[0][g]);
-                        load4(reinterpret_cast<const bf16_t*>(&braw), bq);
+                        load4(reinterpret_cast<const T*>(&braw), bq);
                         uint32_t pk[2];
 #pragma unroll
                         for (int h = 0; h < 2; ++h) {
@@ -207,7 +207,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                             if constexpr (!(SA_MBC_ABL & 2)) {
                                 x = hardswish_pk(x + f32x2{bq[2 * h], bq[2 * h + 1]});      // common.h: the op list's Hardswish on an fp32 pair
                             }
-                            pk[h] = __builtin_bit_cast(uint32_t, __builtin_convertvector(x, bf16x2_t)) & emask[t];
+                            pk[h] = __builtin_bit_cast(uint32_t, H16<T>::cvt(x)) & emask[t];
                         }
                         *reinterpret_cast<uint2*>(eb + (erow[t] & ~127) + (((ct * 4 + g) ^ key) << 4) + lh * 8) = make_uint2(pk[0], pk[1]);
                     }
@@ -244,7 +244,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
         // vector -- and was measured: 13 us faster per launch, but it is NOT the fp32 fma: pages 7 and 15 of the 16-page bench input left the op list's bits
         // (9e-3 on the maps) while 2- and 4-page inputs stayed identical. Kept exact.)
         const bool wl = pt_ < 80;
-        const bf16_t* wsrc = (pt_ >> 3) < 9 ? wd + (long)(pt_ >> 3) * Cm + (pt_ & 7) * 8 : bd + (pt_ & 7) * 8;
+        const T* wsrc = (pt_ >> 3) < 9 ? wd + (long)(pt_ >> 3) * Cm + (pt_ & 7) * 8 : bd + (pt_ & 7) * 8;
         u32x4 wld = {0u, 0u, 0u, 0u};
         if constexpr (DREQ) MB_ISSUE(0, 0);
         if (wl) wld = *reinterpret_cast<const u32x4*>(wsrc);
@@ -258,7 +258,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
         // W2 comes FRAGMENT-MAJOR (mbconv_w2_fragments_kernel below, once per engine): [chunk][cout tile][K step][lane][8], so a fragment load is 1 KiB
         // contiguous = 8 cache lines. From the row-major [Cout][Cm] weight a load touched 32 lines (one per output channel, 32 bytes used of each): 1024 /
         // 2048 line requests per chunk and CU, and the D waves' iteration was bound by them (4449 / 5544 cycles against ~1700 of arithmetic).
-        const bf16_t* w2p = w2 + ((long)(d * NJ) * 4 * 64 + lane) * 8;
+        const T* w2p = w2 + ((long)(d * NJ) * 4 * 64 + lane) * 8;
         if constexpr (DREQ) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                                     // (P0)
         for (int it = 0; it < nch + 2; ++it) {
@@ -276,11 +276,11 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                 // waits vmcnt(0), i.e. for the W2 fragments: 5400 of a 6600-cycle iteration.)
                 constexpr int NS = 5;
                 u32x4 tw[NS][2], ex[NS][PT];
-#define MB_LE(SET, T)                                                                                                   \
+#define MB_LE(SET, TP)                                                                                                  \
     {                                                                                                                   \
-        tw[SET][0] = *reinterpret_cast<const u32x4*>(ws + (T) * 256);                                                   \
-        tw[SET][1] = *reinterpret_cast<const u32x4*>(ws + (T) * 256 + 16);                                              \
-        _Pragma("unroll") for (int p_ = 0; p_ < PT; ++p_) ex[SET][p_] = *reinterpret_cast<const u32x4*>(eb + eoff[p_][T]); \
+        tw[SET][0] = *reinterpret_cast<const u32x4*>(ws + (TP) * 256);                                                   \
+        tw[SET][1] = *reinterpret_cast<const u32x4*>(ws + (TP) * 256 + 16);                                              \
+        _Pragma("unroll") for (int p_ = 0; p_ < PT; ++p_) ex[SET][p_] = *reinterpret_cast<const u32x4*>(eb + eoff[p_][TP]); \
     }
                 const f32x4 bl = *reinterpret_cast<const f32x4*>(ws + 9 * 256), bh = *reinterpret_cast<const f32x4*>(ws + 9 * 256 + 16);
 #pragma unroll
@@ -290,8 +290,8 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                 // taps of chunk `it` into slot it & 1 (read by the depthwise of the NEXT iteration); chunk it + 1's requested
                 if (wl) {
                     unsigned char* dst = smem + OFF_TAP + (it & 1) * TAPB + pt_ * 32;
-                    *reinterpret_cast<u32x4*>(dst) = u32x4{wld[0] << 16, wld[0] & 0xffff0000u, wld[1] << 16, wld[1] & 0xffff0000u};
-                    *reinterpret_cast<u32x4*>(dst + 16) = u32x4{wld[2] << 16, wld[2] & 0xffff0000u, wld[3] << 16, wld[3] & 0xffff0000u};
+                    *reinterpret_cast<u32x4*>(dst) = u32x4{__float_as_uint(H16<T>::lo(wld[0])), __float_as_uint(H16<T>::hi(wld[0])), __float_as_uint(H16<T>::lo(wld[1])), __float_as_uint(H16<T>::hi(wld[1]))};
+                    *reinterpret_cast<u32x4*>(dst + 16) = u32x4{__float_as_uint(H16<T>::lo(wld[2])), __float_as_uint(H16<T>::hi(wld[2])), __float_as_uint(H16<T>::lo(wld[3])), __float_as_uint(H16<T>::hi(wld[3]))};
                     wld = *reinterpret_cast<const u32x4*>(wsrc + min(it + 1, nch - 1) * MCH);
                 }
                 // W2 fragments of chunk it - 2 (used behind the depthwise arithmetic below)
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                         for (int p = 0; p < PT; ++p) {
                             f32x2 x[4];
                             const u32x4 xr = ex[t % NS][p];
-                            UpsumPk<bf16_t>::unpack(make_uint4(xr[0], xr[1], xr[2], xr[3]), x);
+                            UpsumPk<T>::unpack(make_uint4(xr[0], xr[1], xr[2], xr[3]), x);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) a2[p][e] += x[e] * w4[e];       // dwproj_kernel's expression: the fp32 fma of the op list
                         }
@@ -340,7 +340,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
 #pragma unroll
                     for (int e = 0; e < 4; ++e) { r[2 * e] = hardswish_f(a2[p][e].x); r[2 * e + 1] = hardswish_f(a2[p][e].y); }
                     *reinterpret_cast<uint4*>(smem + OFF_D + (c1 & 1) * DB + doff[p]) =
-                        make_uint4(pack2(r[0], r[1]), pack2(r[2], r[3]), pack2(r[4], r[5]), pack2(r[6], r[7]));
+                        make_uint4(H16<T>::pk(r[0], r[1]), H16<T>::pk(r[2], r[3]), H16<T>::pk(r[4], r[5]), H16<T>::pk(r[6], r[7]));
                 }
             }
             if (wv == 4) MBC_STAMP(1, it, 1);
@@ -363,7 +363,7 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                         for (int j = 0; j < NJ; ++j)
 #pragma unroll
                             for (int p = 0; p < PT; ++p)
-                                acc[j][p] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w2f[j][kk]), __builtin_bit_cast(bf16x8, xf[kk][p]), acc[j][p], 0, 0, 0);
+                                acc[j][p] = H16<T>::mfma(w2f[j][kk], xf[kk][p], acc[j][p]);
                     }
                 }
             }
@@ -393,8 +393,8 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
                 for (int q = 0; q < 4; ++q) {
                     const int chunk = ((d * NJ + j) * 32 + q * 8) >> 3;
                     *reinterpret_cast<uint2*>(smem + row * ROWB + ((chunk ^ (row & 31)) << 4) + lh * 8) =
-                        make_uint2(pack2(acc[j][p][4 * q] + bq[q][0], acc[j][p][4 * q + 1] + bq[q][1]),
-                                   pack2(acc[j][p][4 * q + 2] + bq[q][2], acc[j][p][4 * q + 3] + bq[q][3]));
+                        make_uint2(H16<T>::pk(acc[j][p][4 * q] + bq[q][0], acc[j][p][4 * q + 1] + bq[q][1]),
+                                   H16<T>::pk(acc[j][p][4 * q + 2] + bq[q][2], acc[j][p][4 * q + 3] + bq[q][3]));
                 }
             }
         }
@@ -410,8 +410,8 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
             const long off = (((long)b * Ho + oy) * Wo + ox) * COUT + cc * 8;
             if (res) {
                 float a[8], r8[8];
-                unpack16(rawo, a, (bf16_t*)nullptr);
-                unpack16(*reinterpret_cast<const uint4*>(res + off), r8, (bf16_t*)nullptr);
+                unpack16(rawo, a, (T*)nullptr);
+                unpack16(*reinterpret_cast<const uint4*>(res + off), r8, (T*)nullptr);
                 store4(out + off, a[0] + r8[0], a[1] + r8[1], a[2] + r8[2], a[3] + r8[3]);
                 store4(out + off + 4, a[4] + r8[4], a[5] + r8[5], a[6] + r8[6], a[7] + r8[7]);
             } else {
@@ -423,7 +423,8 @@ __global__ __launch_bounds__(512) void mbconv_kernel(const bf16_t* __restrict__ 
 
 // W2 [Cout][Cm] row-major -> [Cm / 64][Cout / 32][4][64 lanes][8]: lane (lr, lh) of fragment (chunk c, cout tile jt, K step kk) holds
 // W2[jt * 32 + lr][c * 64 + kk * 16 + lh * 8 + (0..7)] -- the MFMA A operand of the projection as one contiguous KiB.
-__global__ __launch_bounds__(256) void mbconv_w2_fragments_kernel(const bf16_t* __restrict__ w2, bf16_t* __restrict__ w2f, int Cout, int Cm) {
+template <typename T>
+__global__ __launch_bounds__(256) void mbconv_w2_fragments_kernel(const T* __restrict__ w2, T* __restrict__ w2f, int Cout, int Cm) {
     const long n = (long)Cout * Cm / 8, i = (long)blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
     const int lane = (int)(i & 63), kk = (int)((i >> 6) & 3);
@@ -431,10 +432,11 @@ __global__ __launch_bounds__(256) void mbconv_w2_fragments_kernel(const bf16_t* 
     const int jt = (int)(r % (Cout / 32)), c = (int)(r / (Cout / 32));
     *reinterpret_cast<uint4*>(w2f + i * 8) = *reinterpret_cast<const uint4*>(w2 + (long)(jt * 32 + (lane & 31)) * Cm + c * 64 + kk * 16 + (lane >> 5) * 8);
 }
-static inline int mbconv_w2_fragments(const bf16_t* w2, bf16_t* w2f, int Cout, int Cm, hipStream_t s) {
+template <typename T>
+static inline int mbconv_w2_fragments(const T* w2, T* w2f, int Cout, int Cm, hipStream_t s) {
     if (Cout % 32 || Cm % 64) return SA_ERR_SHAPE;
     const long n = (long)Cout * Cm / 8;
-    hipLaunchKernelGGL(mbconv_w2_fragments_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w2, w2f, Cout, Cm);
+    hipLaunchKernelGGL(mbconv_w2_fragments_kernel<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, w2, w2f, Cout, Cm);
     return (int)hipGetLastError();
 }
 
@@ -449,8 +451,9 @@ static long long* g_mbc_dbg = nullptr;
 #define MBC_DBG_ARG
 #endif
 // w2f: the projection weight fragment-major (mbconv_w2_fragments)
-static inline int launch_mbconv(const bf16_t* in, const bf16_t* w1, const bf16_t* b1, const bf16_t* wd, const bf16_t* bd, const bf16_t* w2,
-                                const bf16_t* b2, const bf16_t* res, bf16_t* out, int B, int H, int W, int Cin, int Cm, int Ho, int Wo, int Cout,
+template <typename T>
+static inline int launch_mbconv(const T* in, const T* w1, const T* b1, const T* wd, const T* bd, const T* w2,
+                                const T* b2, const T* res, T* out, int B, int H, int W, int Cin, int Cm, int Ho, int Wo, int Cout,
                                 int stride, hipStream_t s) {
     if (!mbconv_shape_ok(Cin, Cm, Cout, stride) || !b1 || !bd || !b2 || (long)B * H * W * Cin >= (1L << 31) || Cm > 8192) return SA_ERR_SHAPE;
 #define SA_MBC(CI, SS, TH_, TW_, CO)                                                                                            \
@@ -458,7 +461,7 @@ static inline int launch_mbconv(const bf16_t* in, const bf16_t* w1, const bf16_t
         constexpr int PH_ = ((TH_) - 1) * (SS) + 3, PW_ = ((TW_) - 1) * (SS) + 3, RT_ = (PH_ * PW_ + 31) / 32;                  \
         const size_t lds = (size_t)2 * RT_ * 32 * 128 + 2 * 64 * (CI) * 2 + 2 * (TH_) * (TW_) * 128 + 2 * 2560 + (size_t)Cm * 2;             \
         const int tx = cdiv(Wo, TW_), ty = cdiv(Ho, TH_);                                                                       \
-        auto kern = mbconv_kernel<CI, SS, TH_, TW_, CO>;                                                                        \
+        auto kern = mbconv_kernel<T, CI, SS, TH_, TW_, CO>;                                                                        \
         static AttrOnce attr;                                                                                                   \
         attr.ensure(kern, lds);                                                                                                 \
         hipLaunchKernelGGL(kern, dim3((unsigned)(B * tx * ty)), dim3(512), lds, s, in, w1, b1, wd, bd, w2, b2, res, out, H, W, Ho, Wo, Cm, tx, ty MBC_DBG_ARG); \
@@ -467,8 +470,5 @@ static inline int launch_mbconv(const bf16_t* in, const bf16_t* w1, const bf16_t
 #undef SA_MBC
     return (int)hipGetLastError();
 }
-template <typename T>
-static inline int launch_mbconv(const T*, const T*, const T*, const T*, const T*, const T*, const T*, const T*, T*, int, int, int, int, int, int, int, int,
-                                int, hipStream_t) { return SA_ERR_UNSUPPORTED; }
 
 }  // namespace sa

@@ -116,7 +116,7 @@ struct DetModel : DetBase {
     void find_fusions() {
         const int n = (int)ops.size();
         fuse_kind.assign(n, 0); fuse_with.assign(n, -1); mb_start.assign(n, 0);
-        constexpr bool BF = std::is_same<T, bf16_t>::value;
+        constexpr bool BF = sizeof(T) == 2;        // the fused forms exist for the 16-bit storage types (bf16, fp16)
         for (int i = 0; i < n; ++i) {
             const surya_det_op& a = ops[i];
             if (a.type == SA_DET_LITEMLA && a.p0 == 32) fuse_kind[i] = FUSE_MLA_ATTN;
@@ -180,7 +180,7 @@ struct DetModel : DetBase {
     int prepare_fused_weights() {
         mb_w2f.assign(ops.size(), nullptr);
         head_a0f.assign(ops.size(), nullptr);
-        if constexpr (std::is_same<T, bf16_t>::value) {
+        if constexpr (sizeof(T) == 2) {
             for (size_t j = 0; j < ops.size(); ++j) {
                 if (fuse_kind[j] != FUSE_HEAD_Z0) continue;
                 const surya_det_op& zc = ops[fuse_with[j]];
@@ -231,7 +231,7 @@ struct DetModel : DetBase {
                 case SA_DET_UPSUM_CLASSIFY: {
                     const long HWl = (long)op.hin * op.win, P = (long)B * HWl;
                     if (op.cin % Ty<T>::V16 || op.cout > 4) return SA_ERR_SHAPE;
-                    if constexpr (std::is_same<T, bf16_t>::value) {
+                    if constexpr (sizeof(T) == 2) {
                         if (fk == FUSE_HEAD_Z0 && upsum.n == 3) {
                             const surya_det_op& zc = ops[fuse_with[oi]];
                             if ((fuse & FUSE_HEAD_MFMA) && head_mfma_shape_ok(op.hin, op.win, zc.cin, op.cin, op.cout)) {
@@ -291,7 +291,7 @@ struct DetModel : DetBase {
                     break;
                 }
                 case SA_DET_CONV: {
-                    if constexpr (std::is_same<T, bf16_t>::value) {
+                    if constexpr (sizeof(T) == 2) {
                         if (mb_start[oi] && (fuse & FUSE_MBCONV)) {
                             const surya_det_op& dw = ops[oi + 1];
                             const surya_det_op& pj = ops[oi + 2];
@@ -314,7 +314,7 @@ struct DetModel : DetBase {
                             break;
                         }
                     }
-                    if constexpr (std::is_same<T, bf16_t>::value) {
+                    if constexpr (sizeof(T) == 2) {
                         if (input_fold >= 0 && oi == input_fold + 1 && (fuse & FUSE_INPUT) && (fuse & FUSE_STEM)) {
                             StemSrc src{pixels_u8 ? nullptr : pixels, pixels_u8, 0.f, 0.f, 0.f, 1.f, 1.f, 1.f, pix};
                             if (pixels_u8) { src.m0 = ms[0]; src.m1 = ms[1]; src.m2 = ms[2]; src.s0 = ms[3]; src.s1 = ms[4]; src.s2 = ms[5]; }
@@ -348,7 +348,7 @@ struct DetModel : DetBase {
                     break;
                 }
                 case SA_DET_DWCONV: {
-                    if constexpr (std::is_same<T, bf16_t>::value) {
+                    if constexpr (sizeof(T) == 2) {
                         if (fk == FUSE_MLA_AGG) {
                             const surya_det_op& gp = ops[fuse_with[oi]];
                             if ((rc = launch_dw5_g1x1(bufs[op.in0], WT(op.w_idx), WT(gp.w_idx), bufs[gp.out], zero_page, B, op.hin, op.win, op.cin, s))) return rc;
@@ -463,6 +463,19 @@ struct DetModel : DetBase {
     }
 };
 
+// fp16 GEMMs for surya_op_gemm (rec_model.hip): the detector's epilogues only, instantiated in this translation unit beside DetModel<fp16_t>
+int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
+                int M, int N, int K, hipStream_t s) {
+    GemmArgs<fp16_t, fp16_t> a{(const fp16_t*)X, ldx, (const fp16_t*)W, ldw, (fp16_t*)C, ldc, (const fp16_t*)bias, (const fp16_t*)R, ldr, M, N, K};
+    switch (epi) {
+        case EPI_BIAS: return launch_gemm<fp16_t, fp16_t, EPI_BIAS>(a, s);
+        case EPI_RESIDUAL: return R ? launch_gemm<fp16_t, fp16_t, EPI_RESIDUAL>(a, s) : SA_ERR_ARG;
+        case EPI_HARDSWISH: return launch_gemm<fp16_t, fp16_t, EPI_HARDSWISH>(a, s);
+        case EPI_RELU: return launch_gemm<fp16_t, fp16_t, EPI_RELU>(a, s);
+    }
+    return SA_ERR_UNSUPPORTED;
+}
+
 }  // namespace sa
 
 using namespace sa;
@@ -487,6 +500,10 @@ int surya_det_create(const surya_det_config* cfg, const surya_det_op* ops, const
         h->impl = std::move(m);
     } else if (cfg->dtype == SA_DTYPE_BF16) {
         auto m = std::make_unique<DetModel<bf16_t>>();
+        rc = m->init(*cfg, ops, weights, n_weights, buf_elems, n_bufs);
+        h->impl = std::move(m);
+    } else if (cfg->dtype == SA_DTYPE_F16) {
+        auto m = std::make_unique<DetModel<fp16_t>>();
         rc = m->init(*cfg, ops, weights, n_weights, buf_elems, n_bufs);
         h->impl = std::move(m);
     } else {

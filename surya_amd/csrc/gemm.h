@@ -88,10 +88,12 @@ struct GemmArgs {
 // of row (l & 31); bf16: one v_mfma_f32_32x32x16_bf16; fp32: four v_mfma_f32_32x32x2_f32 on the chunk's 4 floats
 // (k-permuted identically on both operands, so the sum is unchanged and exact).
 template <typename TI> struct Mfma;
+// The 16-bit types take their MFMA from the H16 trait (common.h): bf16 and fp16 share the lane map (K-chunk of 8 elements per lane).
 template <> struct Mfma<bf16_t> {
-    __device__ static __forceinline__ void run(f32x16& acc, const u32x4& w, const u32x4& x) {
-        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), acc, 0, 0, 0);
-    }
+    __device__ static __forceinline__ void run(f32x16& acc, const u32x4& w, const u32x4& x) { acc = H16<bf16_t>::mfma(w, x, acc); }
+};
+template <> struct Mfma<fp16_t> {
+    __device__ static __forceinline__ void run(f32x16& acc, const u32x4& w, const u32x4& x) { acc = H16<fp16_t>::mfma(w, x, acc); }
 };
 template <> struct Mfma<float> {
     __device__ static __forceinline__ void run(f32x16& acc, const u32x4& w, const u32x4& x) {
@@ -1135,7 +1137,7 @@ __global__ __launch_bounds__(512) void gemm_nt_p8p_kernel(GemmArgs<TI, TO> p) {
                 if ((ZERO) && kk_ == 0) {                                                                         \
                     f32x16 z_;                                                                                    \
                     _Pragma("unroll") for (int r_ = 0; r_ < 16; ++r_) z_[r_] = 0.f;                               \
-                    acc[(JH) * 2 + j_][I] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, wf[j_][kk_]), __builtin_bit_cast(bf16x8, XR[kk_]), z_, 0, 0, 0); \
+                    acc[(JH) * 2 + j_][I] = H16<TI>::mfma(wf[j_][kk_], XR[kk_], z_);                           \
                 } else {                                                                                          \
                     Mfma<TI>::run(acc[(JH) * 2 + j_][I], wf[j_][kk_], XR[kk_]);                                   \
                 }                                                                                                 \
@@ -1320,8 +1322,8 @@ __global__ __launch_bounds__(512) void gemm_nt_p8p_kernel(GemmArgs<TI, TO> p) {
                         // (ds_bpermute directly: __shfl adds `lane & ~63`, a lane-id term hipcc hoists out of the tile loop and spills)
                         const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute((wcol >> 1) << 2, (int)bpack), hi = (unsigned)__builtin_amdgcn_ds_bpermute(((wcol >> 1) + 1) << 2, (int)bpack);
                         float v[4] = {acc[j][i][4 * g], acc[j][i][4 * g + 1], acc[j][i][4 * g + 2], acc[j][i][4 * g + 3]};
-                        v[0] += __uint_as_float(lo << 16); v[1] += __uint_as_float(lo & 0xffff0000u);
-                        v[2] += __uint_as_float(hi << 16); v[3] += __uint_as_float(hi & 0xffff0000u);
+                        v[0] += H16<TI>::lo(lo); v[1] += H16<TI>::hi(lo);
+                        v[2] += H16<TI>::lo(hi); v[3] += H16<TI>::hi(hi);
                         if constexpr (EPI == EPI_GELU) {
 #pragma unroll
                             for (int r = 0; r < 4; ++r) v[r] = gelu_epi<TI>(v[r]);
@@ -1345,12 +1347,12 @@ __global__ __launch_bounds__(512) void gemm_nt_p8p_kernel(GemmArgs<TI, TO> p) {
                         if constexpr (GLU) {
                             if constexpr (EPI == EPI_GEGLU) {
                                 const float g0 = Ty<TO>::rnd(gelu_tanh_f(Ty<TO>::rnd(v[0]))), g1 = Ty<TO>::rnd(gelu_tanh_f(Ty<TO>::rnd(v[2])));
-                                pk[j][i][g] = pack2(g0 * Ty<TO>::rnd(v[1]), g1 * Ty<TO>::rnd(v[3]));
+                                pk[j][i][g] = H16<TO>::pk(g0 * Ty<TO>::rnd(v[1]), g1 * Ty<TO>::rnd(v[3]));
                             } else {
-                                pk[j][i][g] = pack2(silu_epi<TI>(v[0]) * v[1], silu_epi<TI>(v[2]) * v[3]);
+                                pk[j][i][g] = H16<TO>::pk(silu_epi<TI>(v[0]) * v[1], silu_epi<TI>(v[2]) * v[3]);
                             }
                         } else {
-                            pk[j][i][g] = Pk{pack2(v[0], v[1]), pack2(v[2], v[3])};
+                            pk[j][i][g] = Pk{H16<TO>::pk(v[0], v[1]), H16<TO>::pk(v[2], v[3])};
                         }
                     }
             }

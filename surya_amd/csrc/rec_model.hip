@@ -1099,6 +1099,10 @@ using namespace sa;
 struct surya_rec { std::unique_ptr<RecBase> impl; surya_rec_config cfg; };
 
 // ------------------------------------------------------------------------------------------------ op level
+namespace sa {   // det_model.hip: the fp16 GEMMs of surya_op_gemm
+int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
+                int M, int N, int K, hipStream_t s);
+}
 template <typename TI, typename TO>
 static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R,
                      long ldr, int M, int N, int K, hipStream_t s) {
@@ -1227,6 +1231,8 @@ int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, cons
     if (dtype == SA_DTYPE_BF16)
         return out_f32 ? op_gemm_t<bf16_t, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s)
                        : op_gemm_t<bf16_t, bf16_t>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
+    if (dtype == SA_DTYPE_F16)            // the detector's epilogues (bias, residual, Hardswish, ReLU), 16-bit output only; built in det_model.hip
+        return out_f32 ? SA_ERR_UNSUPPORTED : sa::op_gemm_f16(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
     return SA_ERR_UNSUPPORTED;
 }
 

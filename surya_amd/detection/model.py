@@ -16,13 +16,17 @@ class DetOpC(C.Structure):
                                          "hout", "wout", "w_idx", "b_idx", "p0", "p1")]
 
 
+# compute dtypes of the engine: fp32 = reference mode; bf16 = the default; fp16 = the reference's GPU default (surya settings.MODEL_DTYPE)
+_DTYPES = {torch.float32: L.DTYPE_F32, torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}
+
+
 class HipDetModel:
     def __init__(self, cfg: DetConfig, state_dict, *, height: int, width: int, dtype: torch.dtype = torch.bfloat16,
                  device="cuda:0", max_batch: int = 16, broadcast_weights: bool = False, process_group=None):
         if not torch.cuda.is_available():
             raise L.SuryaAmdError("HipDetModel needs a GPU (MI355X); there is no CPU fallback")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be float32 (reference mode) or bfloat16")
+        if dtype not in _DTYPES:
+            raise ValueError("dtype must be float32 (reference mode), bfloat16 or float16")
         self.lib = L.lib()
         self.lib.surya_det_create.argtypes = None
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
@@ -48,7 +52,7 @@ class HipDetModel:
         table = (C.c_void_p * len(self.weights))(*[w.data_ptr() for w in self.weights])
         bufs = (C.c_size_t * len(plan.buf_elems))(*plan.buf_elems)
         c = L.DetConfigC(n_ops=len(plan.ops), max_batch=max_batch, height=height, width=width, num_labels=cfg.num_labels,
-                         dtype=L.DTYPE_F32 if dtype == torch.float32 else L.DTYPE_BF16)
+                         dtype=_DTYPES[dtype])
         self.handle = C.c_void_p()
         L.check(self.lib.surya_det_create(C.byref(c), ops, table, len(self.weights), bufs, len(plan.buf_elems),
                                           C.byref(self.handle)), "surya_det_create")

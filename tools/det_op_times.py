@@ -1,12 +1,14 @@
 """Per-op event times of the detection forward (surya_det_forward_timed) on the GPU box, op list vs fused forms.
 
-  python tools/det_op_times.py [--pages 16] [--size 1024] [--fuse 0,15] [--reps 5]
+  python tools/det_op_times.py [--pages 16] [--size 1024] [--fuse 0,15] [--reps 5] [--dtype bf16,fp16]
 
 For every value of sa::Tuning det_fuse given: warm up, take the per-op MINIMUM over `reps` timed forwards, print one row per op
 (type, shape, ms, TFLOP/s of the op's own FLOPs, GB/s of its own tensors) and bucket sums (conv3x3 / conv1x1 / depthwise / litemla /
 head / other); then the wall clock of `steps` plain forwards per arm, and the heat maps of every arm against arm 0 (max abs diff).
 Everything goes to stdout as text; --json adds one JSON line with the bucket sums (bench.py's detection roofline keys are built
-the same way, surya_amd/detection/buckets.py)."""
+the same way, surya_amd/detection/buckets.py). --dtype takes one or more compute dtypes (bf16, fp16): one engine per dtype in the same
+process, the arms run dtype after dtype for each det_fuse value, and a last block prints the wall-clock ratio of every dtype to the
+first one per det_fuse value."""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +32,7 @@ def main():
     ap.add_argument("--fuse", default="0,1023")
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--dtype", default="bf16", help="comma-separated compute dtypes (bf16, fp16), each its own engine in this process")
     ap.add_argument("--json", action="store_true")
     ap.add_argument("--tuning", action="append", default=[], help="sa::Tuning key=value applied before the runs (repeatable), e.g. bigtile_min_k=192")
     ap.add_argument("--rows", action="store_true", help="print the per-op rows (default: buckets only for arms after the first)")
@@ -43,7 +46,9 @@ def main():
 
     cfg = det_config(args.config)
     sd = make_det_weights(cfg, 0)
-    m = HipDetModel(cfg, sd, height=args.size, width=args.size, dtype=torch.bfloat16, max_batch=args.pages)
+    dtypes = args.dtype.split(",")
+    tdt = {"bf16": torch.bfloat16, "fp16": torch.float16}
+    models = {d: HipDetModel(cfg, sd, height=args.size, width=args.size, dtype=tdt[d], max_batch=args.pages) for d in dtypes}
     x = do.normalise_pages(make_pages(args.pages, args.size, seed=1234)).cuda().contiguous()
     lib = L.lib()
     for kv in args.tuning:
@@ -51,7 +56,8 @@ def main():
         L.check(lib.surya_set_tuning(k.encode(), C.c_int(int(v))), f"surya_set_tuning({kv})")
     arms = [int(v) for v in args.fuse.split(",")]
     heats, summary = {}, {}
-    for arm in arms:
+    for arm, dname in [(a, d) for a in arms for d in dtypes]:
+        m = models[dname]
         L.check(lib.surya_set_tuning(b"det_fuse", C.c_int(arm)), "surya_set_tuning")
         for _ in range(2):
             m.forward(x)
@@ -61,10 +67,10 @@ def main():
             heat, rows = m.forward_timed(x)
             ms = [r[1] for r in rows]
             best = ms if best is None else [min(a, b) for a, b in zip(best, ms)]
-        heats[arm] = heat.clone()
+        heats[(dname, arm)] = heat.clone()
         ops = [r[0] for r in rows]
         buckets = {}
-        print(f"\n=== det_fuse = {arm}: {args.pages} pages {args.size}^2, {args.config}, bf16; per-op min of {args.reps} event-timed forwards ===")
+        print(f"\n=== det_fuse = {arm}: {args.pages} pages {args.size}^2, {args.config}, {dname}; per-op min of {args.reps} event-timed forwards ===")
         ran = {r[0]: r for r in launch_rows(ops, best)}
         for i, (o, t) in enumerate(zip(ops, best)):
             _, bk, _, fl, by = ran.get(i, (i, bucket_of(o), 0.0, op_flops(o), op_bytes(o)))
@@ -88,13 +94,21 @@ def main():
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / args.steps
         print(f"--- wall: {dt*1e3:.3f} ms per forward = {args.pages / dt:.1f} pages/s")
-        summary[arm] = {"ms_per_forward": round(dt * 1e3, 3), "pages_per_s": round(args.pages / dt, 1),
+        summary[f"{dname}/{arm}" if len(dtypes) > 1 else arm] = {"ms_per_forward": round(dt * 1e3, 3), "pages_per_s": round(args.pages / dt, 1),
                         "buckets_ms": {k: round(v[0], 3) for k, v in buckets.items()}}
-    base = heats[arms[0]]
-    for arm in arms[1:]:
-        d = (heats[arm] - base).abs()
-        print(f"heat maps det_fuse={arm} vs {arms[0]}: max abs diff {d.max().item():.3e}, mean {d.mean().item():.3e}, "
-              f"bit-identical: {bool(torch.equal(heats[arm].view(torch.int32), base.view(torch.int32)))}")
+    for dname in dtypes:
+        base = heats[(dname, arms[0])]
+        for arm in arms[1:]:
+            h = heats[(dname, arm)]
+            d = (h - base).abs()
+            print(f"{dname} heat maps det_fuse={arm} vs {arms[0]}: max abs diff {d.max().item():.3e}, mean {d.mean().item():.3e}, "
+                  f"bit-identical: {bool(torch.equal(h.view(torch.int32), base.view(torch.int32)))}")
+    for dname in dtypes[1:]:
+        for arm in arms:
+            a, b = summary[f"{dname}/{arm}"], summary[f"{dtypes[0]}/{arm}"]
+            d = (heats[(dname, arm)] - heats[(dtypes[0], arm)]).abs()
+            print(f"det_fuse={arm}: {dname} {a['ms_per_forward']:.3f} ms / {dtypes[0]} {b['ms_per_forward']:.3f} ms per forward = "
+                  f"{a['ms_per_forward'] / b['ms_per_forward']:.3f}; heat maps differ by max {d.max().item():.3e}")
     L.check(lib.surya_set_tuning(b"det_fuse", C.c_int(1023)), "surya_set_tuning")
     if args.json:
         print(json.dumps(summary))
