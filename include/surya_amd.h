@@ -441,6 +441,20 @@ int surya_layout_wait_steps(surya_layout* h, int ring, int batch, int n_steps, f
 int surya_layout_select(surya_layout* h, const int32_t* src_index, int n);
 /* Test hook: encoder output [batch * tokens, hidden] of the last encode (device, compute dtype). */
 int surya_layout_encoder_states(surya_layout* h, void* out, int batch, void* stream);
+/* Page pre-processing of the layout family on the device (no handle): uint8 pages -> the pixel_values surya_layout_encode reads.
+ * Replaces, per image, the PIL crop of a slicer strip (surya/layout/slicer.py) and SuryaEncoderImageProcessor (surya/common/donut/
+ * processor.py:24-126: cv2.resize to the model size with flag 2 = INTER_CUBIC, uint8 result, x * 1/255 in fp64, (x - mean) / std in
+ * fp32), bit-identical to the host restatement (surya_amd/layout/predictor.py LayoutImageProcessor).
+ *   pages        device uint8, every page HWC at its descriptor's byte offset, pixel_stride bytes per pixel: 3 (RGB) or 4 (RGBX,
+ *                the fourth byte ignored); pages_bytes = the size of that buffer (every page must lie inside it)
+ *   descs        HOST array of n descriptors, one per output image
+ *                { int64 page_off; int32 page_w, page_h; int32 x0, y0, cw, ch (crop rectangle inside the page, >= 1 px) } -- 32 bytes
+ *   mean, std    host fp32 [3]
+ *   pixel_values device fp32 [n][3][out_h][out_w], written in place
+ * SA_ERR_ARG for a NULL pointer, n < 0 or another pixel_stride; SA_ERR_SHAPE for a crop outside its page, a page outside
+ * pages_bytes or an empty output size. Enqueue only (the descriptors are read before the call returns). */
+int surya_layout_preprocess(const uint8_t* pages, size_t pages_bytes, const void* descs, int n, int pixel_stride, const float* mean,
+                            const float* std, int out_h, int out_w, float* pixel_values, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * OCR-error classifier: DistilBERT encoder (post-LayerNorm) + sequence-classification head.

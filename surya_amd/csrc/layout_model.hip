@@ -25,6 +25,7 @@
 #include "kernels.h"
 #include "decode_attn.h"
 #include "layout_kernels.h"
+#include "layout_prep.h"
 
 namespace sa {
 
@@ -841,6 +842,12 @@ int surya_layout_select(surya_layout* h, const int32_t* src_index, int n) {
 int surya_layout_encoder_states(surya_layout* h, void* out, int batch, void* stream) {
     if (!h || !out) return SA_ERR_ARG;
     return h->impl->encoder_states(out, batch, (hipStream_t)stream);
+}
+
+int surya_layout_preprocess(const uint8_t* pages, size_t pages_bytes, const void* descs, int n, int pixel_stride, const float* mean,
+                            const float* std, int out_h, int out_w, float* pixel_values, void* stream) {
+    return sa::lprep::run(pages, pages_bytes, reinterpret_cast<const sa::lprep::PageDesc*>(descs), n, pixel_stride, mean, std, out_h,
+                          out_w, pixel_values, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -130,6 +130,11 @@ class LayoutPredictor(BasePredictor):
     shard_pages: bool = settings.SURYA_AMD_SHARD
     process_group = None
 
+    # Pages are cropped into their slices, resized and normalised on the device (surya_layout_preprocess, layout/preprocess_gpu.py) when
+    # the model is the HIP engine on a GPU and the processor is the family's own; LAYOUT_PREPROCESS_HOST=1 selects the host chain instead.
+    device_preprocess: bool = not settings.LAYOUT_PREPROCESS_HOST
+    device_prep = None
+
     def __call__(self, images: List[Image.Image], batch_size: Optional[int] = None, top_k: int = 5) -> List[LayoutResult]:
         if self.shard_pages:
             from ..common.predictor import sharded_over_ranks
@@ -155,29 +160,40 @@ class LayoutPredictor(BasePredictor):
         if start < len(counts):
             batches.append((start, len(counts)))
         dcfg = self.model.config.decoder
+        from .preprocess_gpu import device_preprocessor
+        prep = device_preprocessor(self, self.processor)
         results: List[LayoutResult] = []
         for start, end in batches:
             batch_images = [image.convert("RGB") for image in images[start:end]]
-            batch_images, tile_positions = slicer.slice(batch_images)
-            orig_sizes = [image.size for image in batch_images]
+            if prep is not None:                                         # slices by reference: (page, crop box), no PIL crop
+                rects, tile_positions = slicer.slice_rects(batch_images)
+                batch_images = [(batch_images[p], box) for p, box in rects]
+                orig_sizes = [(box[2] - box[0], box[3] - box[1]) for _, box in rects]
+            else:
+                batch_images, tile_positions = slicer.slice(batch_images)
+                orig_sizes = [image.size for image in batch_images]
             batch_results = []
             for s0 in range(0, len(batch_images), self.model.max_batch):     # a page's slices may exceed the model's batch
                 chunk = batch_images[s0:s0 + self.model.max_batch]
-                batch_results.extend(self._detect_chunk(chunk, orig_sizes[s0:s0 + self.model.max_batch], dcfg, top_k))
+                batch_results.extend(self._detect_chunk(chunk, orig_sizes[s0:s0 + self.model.max_batch], dcfg, top_k, prep=prep))
             assert len(batch_results) == len(tile_positions)
             results.extend(slicer.join(batch_results, tile_positions))
         assert len(results) == len(images)
         return results
 
-    def _detect_chunk(self, chunk, orig_sizes, dcfg, top_k) -> List[LayoutResult]:
+    def _detect_chunk(self, chunk, orig_sizes, dcfg, top_k, prep=None) -> List[LayoutResult]:
         """The greedy box loop of surya/layout/__init__.py:110-177 for one encoder batch. One model call per box as there, served from
         device-fed runs (model.FedRuns): the host derives every fed-back token itself and the run records are checked against it. The
-        per-step host work covers all unfinished pages at once (numpy / one batched softmax + top-k) instead of a Python loop per page."""
+        per-step host work covers all unfinished pages at once (numpy / one batched softmax + top-k) instead of a Python loop per page.
+        chunk: PIL slices, or with `prep` (the device pre-processing) (page, crop box) pairs."""
         from .model import FedRuns
         n = len(chunk)
-        px = torch.from_numpy(np.stack(self.processor(chunk)["pixel_values"]))
-        if torch.device(self.model.device).type == "cuda":          # (a host stand-in model of the CPU tests takes the tensor as it is)
-            px = px.pin_memory().to(self.model.device, non_blocking=True)
+        if prep is not None:
+            px = prep(chunk, self.processor)
+        else:
+            px = torch.from_numpy(np.stack(self.processor(chunk)["pixel_values"]))
+            if torch.device(self.model.device).type == "cuda":          # (a host stand-in model of the CPU tests takes the tensor as it is)
+                px = px.pin_memory().to(self.model.device, non_blocking=True)
         self.model.encode(px.contiguous())
         assert dcfg.pause_token_count == 0, "pause tokens in the decoder prompt are not built"
         sizes = np.asarray(orig_sizes, np.int64).reshape(n, 2)

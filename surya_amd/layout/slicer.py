@@ -55,6 +55,16 @@ class ImageSlicer:
                 positions.append((index, tx, ty))
         return pieces, positions
 
+    def slice_rects(self, images: List[Image.Image]):
+        """`slice` by reference: [(page index, crop box)] instead of the cropped strips (a strip is a rectangle of its page; the device
+        pre-processing reads it there, layout/preprocess_gpu.py), and the same tile positions."""
+        rects, positions = [], []
+        for index, image in enumerate(images):
+            for box, (tx, ty) in self._strips(image.size):
+                rects.append((index, box))
+                positions.append((index, tx, ty))
+        return rects, positions
+
     # -------------------------------------------------------------------------------------------------------------- stitching
     def join(self, results: List[LayoutResult], tile_positions: List[Tuple[int, int, int]]) -> List[LayoutResult]:
         pages: List[LayoutResult] = []

@@ -64,6 +64,9 @@ class Settings:
         # layout / table recognition: decode steps per device-fed run (the host reads the records of this many boxes at a time; the
         # boxes after a page's end token are discarded, so results do not depend on it). 1..16.
         self.LAYOUT_STEPS_PER_SYNC: int = _env("LAYOUT_STEPS_PER_SYNC", int, 8)
+        # crop / resize / normalise of layout and table pages on the GPU (surya_layout_preprocess); 1 keeps the host (numpy)
+        # LayoutImageProcessor -- the checker of tests/test_gpu_layout_prep.py, not a fallback
+        self.LAYOUT_PREPROCESS_HOST: bool = _env("LAYOUT_PREPROCESS_HOST", bool, False)
         self.RECOGNITION_ENCODE_AHEAD: bool = bool(_env("RECOGNITION_ENCODE_AHEAD", int, 1))
         # detect -> recognise calls admit the first pages' lines while the detector still works on the later pages (predictor._call_streamed)
         self.RECOGNITION_STREAM_DETECTION: bool = bool(_env("RECOGNITION_STREAM_DETECTION", int, 1))

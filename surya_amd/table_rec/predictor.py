@@ -87,6 +87,11 @@ class TableRecPredictor(BasePredictor):
     shard_pages: bool = settings.SURYA_AMD_SHARD
     process_group = None
 
+    # The first pass's pixel values are made on the device from the table images (surya_layout_preprocess, layout/preprocess_gpu.py)
+    # when the model is the HIP engine on a GPU and the processor is the family's own; LAYOUT_PREPROCESS_HOST=1 selects the host chain.
+    device_preprocess: bool = not settings.LAYOUT_PREPROCESS_HOST
+    device_prep = None
+
     def __call__(self, images: List[Image.Image], batch_size: Optional[int] = None) -> List[TableResult]:
         if self.shard_pages:
             from ..common.predictor import sharded_over_ranks
@@ -158,13 +163,19 @@ class TableRecPredictor(BasePredictor):
         query_items = [{"polygon": [[0, 0], [im.width, 0], [im.width, im.height], [0, im.height]], "category": CATEGORY_TO_ID["Table"],
                         "colspan": 0, "merges": 0, "is_header": 0} for im in images]
         shaper = LabelShaper()
+        from ..layout.preprocess_gpu import device_preprocessor
+        prep = device_preprocessor(self, self.processor.image_processor) if type(self.processor) is TableRecProcessor else None
         results: List[TableResult] = []
         for i in range(0, len(images), batch_size):
             batch_images = [image.convert("RGB") for image in images[i:i + batch_size]]
             n = len(batch_images)
             orig_sizes = [image.size for image in batch_images]
-            inputs = self.processor(images=batch_images, query_items=query_items[i:i + batch_size])
-            self.model.encode_host(torch.from_numpy(np.stack(inputs["pixel_values"])))
+            if prep is not None:
+                inputs = self.processor(images=batch_images, query_items=query_items[i:i + batch_size], pixels=False)
+                self.model.encode(prep([(im, (0, 0) + im.size) for im in batch_images], self.processor.image_processor))
+            else:
+                inputs = self.processor(images=batch_images, query_items=query_items[i:i + batch_size])
+                self.model.encode_host(torch.from_numpy(np.stack(inputs["pixel_values"])))
             rowcol = self.inference_loop(list(range(n)), inputs["input_ids"])
             # second pass: one prompt per detected row, all the batch's columns as context (:190-230)
             row_queries, idx_map, columns = [], [], []

@@ -35,7 +35,9 @@ class TableRecProcessor:
             corner[1] = 0 if y < 0 else (new_size[1] if y > new_size[1] else y)
         return polygon
 
-    def __call__(self, images: Optional[List], query_items: List[dict], columns: Optional[List[dict]] = None, convert_images: bool = True):
+    def __call__(self, images: Optional[List], query_items: List[dict], columns: Optional[List[dict]] = None, convert_images: bool = True,
+                 pixels: bool = True):
+        """pixels=False: everything convert_images does but the pixel values (the predictor's device pre-processing makes those)."""
         if convert_images:
             assert len(images) == len(query_items) and len(images) > 0
             for image, q in zip(images, query_items):
@@ -50,6 +52,6 @@ class TableRecProcessor:
         # torch.tensor(..., dtype=long) on mixed int / float lists truncates toward zero (:83)
         ids = np.array(prompts, dtype=np.float64).astype(np.int64)
         out = {"input_ids": ids, "attention_mask": np.ones_like(ids)}
-        if convert_images:
+        if convert_images and pixels:
             out["pixel_values"] = self.image_processor(images)["pixel_values"]
         return out
