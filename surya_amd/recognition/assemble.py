@@ -1,0 +1,240 @@
+"""Output assembly of the recognition predictor: finished token streams -> TextLine / TextChar objects (reference
+recognition/__init__.py:609-771 + :886-925). Plain functions of the processor (three stop ids and the tokenizer) and the call's
+`flat` dict; RecognitionPredictor keeps one-line delegations under its historical method names."""
+import re
+from array import array
+from typing import List, Optional
+
+import numpy as np
+
+from ..common.geometry import PolygonBox, coerce_polygon
+from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags, prediction_to_polygon_batch, unwrap_math,
+                          words_from_chars)
+from .processor import NOMATH_TOKEN
+from .schema import TaskNames, TextChar, TextLine
+
+_SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
+_CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
+assert _CHAR_FIELDS == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
+_new_char, _set = TextChar.__new__, object.__setattr__
+
+
+def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
+    """TextChar.model_construct(...) with all four fields given, without its per-call field loop (1.9 -> 0.55 us; a page of
+    text is ~10^4 of these). Same object state: __dict__, fields_set, no extras, no private attributes."""
+    m = _new_char(TextChar)
+    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid})
+    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))
+    _set(m, "__pydantic_extra__", None)
+    _set(m, "__pydantic_private__", None)
+    return m
+
+
+_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words")
+assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
+_new_line = TextLine.__new__
+_BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
+
+
+def _text_line(polygon, confidence, text, chars, words) -> TextLine:
+    """TextLine(...) for values that are already in validated form (polygon = coerce_polygon(...), confidence not NaN, chars a
+    list of TextChar): the object state validation would produce, without walking the character list again."""
+    m = _new_line(TextLine)
+    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
+                         "original_text_good": False, "words": words})
+    _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
+    _set(m, "__pydantic_extra__", None)
+    _set(m, "__pydantic_private__", None)
+    return m
+
+
+def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False) -> list:
+    """Token stream -> per line (texts, confidences, bbox_valid, polygons [n, 4, 2]) (reference :609-771): the stream is cut
+    into runs of math-BPE ids, single special tags and UTF-16 ids; only the last kind carries per-character boxes.
+    Array form of the reference's per-token loop: run boundaries, close-polygon filtering and the
+    char -> box index map are numpy expressions per line; Python only walks the (few) runs of a line. Lines come back as
+    None (<NOP>), or a tuple that `chars_of` turns into TextChars after the geometry has been applied in bulk."""
+    eos, pad, nop = proc.eos_token_id, proc.pad_token_id, proc.no_output_token
+    out = []
+    for tokens, polys, sc in zip(predicted_tokens, predicted_polygons, scores):
+        if nop in tokens:
+            out.append(None)
+            continue
+        if drop_repeated_text and detect_repeat_token(tokens):
+            out.append(([""], np.zeros(1), np.zeros(1, bool), _BLANK_POLY[None].copy()))
+            continue
+        tid = np.asarray(tokens, np.int64)
+        stop = np.nonzero((tid == eos) | (tid == pad))[0]
+        n = int(stop[0]) if len(stop) else len(tid)
+        n = min(n, len(polys), len(sc))              # zip() of the reference stops at the shortest of the three
+        if n == 0:
+            out.append(([], np.zeros(0), np.zeros(0, bool), np.zeros((0, 4, 2))))
+            continue
+        tid = tid[:n]
+        P = np.asarray(polys[:n], np.float64)
+        conf = np.asarray(sc[:n], np.float64)
+        # clean_close_polygons: a box is dropped when all 4 corners sit within 0.1 of the PREVIOUS box of its run (util.py:100-120)
+        far = (np.abs(P[1:] - P[:-1]).reshape(n - 1, 8).max(axis=1) > 0.1).tolist() if n > 1 else []
+        texts, src, csrc, valid = line_runs(proc, tid.tolist(), far)
+        if not texts:
+            out.append(([], np.zeros(0), np.zeros(0, bool), np.zeros((0, 4, 2))))
+        else:
+            v = np.asarray(valid, bool)
+            pp = P[src]
+            pp[~v] = _BLANK_POLY
+            out.append((texts, conf[csrc], v, pp))
+    return out
+
+
+def line_runs(proc, ids: list, far: list):
+    """The runs of one token stream (already cut at eos / pad): per output char its text, the token whose BOX it takes, the
+    token whose CONFIDENCE it takes, bbox_valid. `far[j]`: box j + 1 differs from box j by more than 0.1 in some corner. The
+    reference indexes a run's unfiltered confidences with the index into its FILTERED boxes (:700-712): kept as is."""
+    tk = proc.ocr_tokenizer
+    q_off, s_off = tk.qwen_offset, tk.special_token_offset
+    n = len(ids)
+    texts, src, csrc, valid = [], [], [], []
+    if n and min(ids) >= s_off:
+        kind = None                                  # one UTF-16 run (the usual line of text)
+    else:
+        kind = [0 if t < q_off else (1 if t < s_off else 2) for t in ids]
+    a_ = 0
+    while a_ < n:
+        if kind is None:
+            k, b_ = 2, n
+        else:
+            k = kind[a_]
+            b_ = a_ + 1
+            if k != 1:
+                while b_ < n and kind[b_] == k:
+                    b_ += 1
+        if k == 2:
+            # a run of UTF-16 code units decodes in one piece (tokenizer._decode_ocr's flush of a non-math buffer)
+            # (ids above the tokenizer's range -- a checkpoint with a padded lm_head -- wrap into 16 bits like the byte masking
+            # of tokenizer._decode_ocr instead of raising OverflowError)
+            text = array("H", [(t - s_off) & 0xFFFF for t in ids[a_:b_]]).tobytes().decode("utf-16le", errors="ignore")
+            if text:
+                boxes = [a_] + [j for j in range(a_ + 1, b_) if far[j - 1]]
+                L, nb = len(text), len(boxes)
+                texts.extend(text)
+                src.extend(boxes[:L] if L <= nb else boxes + [boxes[-1]] * (L - nb))      # char i -> box min(i, nb - 1)
+                csrc.extend(range(a_, a_ + L) if L <= nb else list(range(a_, a_ + nb)) + [a_ + nb - 1] * (L - nb))
+                valid.extend([True] * L)
+        else:
+            text = tk.decode(ids[a_:b_], task=TaskNames.ocr_without_boxes if k == 1 else TaskNames.block_without_boxes)
+            if not (k == 1 and (text == NOMATH_TOKEN or _SCRIPT_TAG.match(text))):
+                texts.append(text); src.append(a_); csrc.append(a_); valid.append(False)
+        a_ = b_
+    return texts, src, csrc, valid
+
+
+def chars_of(line, res_scale, line_bbox) -> List[TextChar]:
+    """TextChars of one line with the reference's per-char geometry (:905-909: rescale by the high-res factor with int()
+    truncation, shift to the line's corner, clamp into the line's bbox) applied to all of the line's polygons at once;
+    objects are built without re-validating fields that were just computed (pydantic model_construct)."""
+    texts, conf, valid, P = line
+    if not texts:
+        return []
+    P = P.copy()
+    P[..., 0] = np.trunc(P[..., 0] * (1.0 / res_scale[0])) + line_bbox[0]
+    P[..., 1] = np.trunc(P[..., 1] * (1.0 / res_scale[1])) + line_bbox[1]
+    np.clip(P[..., 0], line_bbox[0], line_bbox[2], out=P[..., 0])
+    np.clip(P[..., 1], line_bbox[1], line_bbox[3], out=P[..., 1])
+    polys = P.tolist()
+    conf = [0.0 if c != c else c for c in conf.tolist()]               # BaseChar: NaN -> 0, stored as a float
+    return [_text_char(pg, c, t, v) for pg, c, t, v in zip(polys, conf, texts, valid.tolist())]
+
+
+def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size) -> TextLine:
+    """One line's TextLine from its finished token stream (reference :609-771 + :886-925)."""
+    polygon, res_scale = flat["polygons"][orig], flat["res_scales"][orig]
+    polys = prediction_to_polygon_batch(bbox_rows[None], [flat["slices"][sorted_pos].shape], bbox_size, bbox_size // 2)
+    chars = get_bboxes_text(proc, flat, [tokens], [sc], polys, drop_repeated_text)[0]
+    if chars is None or not chars[0]:      # <NOP> (input text was good) or nothing decoded (reference :889-899)
+        return TextLine(text="", polygon=polygon, chars=[], confidence=1, original_text_good=True)
+    # mean of the characters' confidences as the TextChar objects hold them (NaN -> 0, schema.py), reference :899-903
+    confidence = float(np.mean(np.where(np.isnan(chars[1]), 0.0, chars[1])))
+    box = PolygonBox(polygon=polygon)
+    chars = chars_of(chars, res_scale, box.bbox)
+    chars = fix_unbalanced_tags(chars, proc.ocr_tokenizer.special_tokens)
+    text = clean_math_tags(unwrap_math("".join(c.text for c in chars)))
+    return TextLine(text=text, polygon=polygon, chars=chars, confidence=confidence,
+                    words=words_from_chars(chars, box) if return_words else [])
+
+
+def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
+    """TextLines of several finished lines at once; items = [(sorted_pos, orig, tokens, scores, bbox_rows[T, 6])]. The same
+    result as `assemble_line` per item (tests/test_assemble_cpu.py compares the two), but the numpy work -- box tokens ->
+    polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
+    array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
+    runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    eos, pad, nop = proc.eos_token_id, proc.pad_token_id, proc.no_output_token
+    out: List[Optional[TextLine]] = [None] * len(items)
+    work, t_max = [], 0
+    for i, (sp, orig, tokens, sc, rows) in enumerate(items):
+        if nop in tokens or (drop_repeated_text and detect_repeat_token(tokens)):
+            out[i] = assemble_line(proc, flat, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size)
+            continue
+        n = len(tokens)
+        for j, t in enumerate(tokens):
+            if t == eos or t == pad:
+                n = j
+                break
+        n = min(n, len(rows), len(sc))
+        if n == 0:
+            out[i] = TextLine(text="", polygon=flat["polygons"][orig], chars=[], confidence=1, original_text_good=True)
+            continue
+        work.append((i, n))
+        t_max = max(t_max, n)
+    if not work:
+        return out
+    W = len(work)
+    R = np.zeros((W, t_max, 6), np.float32)
+    for w, (i, n) in enumerate(work):
+        R[w, :n] = items[i][4][:n]
+    P = prediction_to_polygon_batch(R, [flat["slices"][items[i][0]].shape for i, _ in work], bbox_size,
+                                    bbox_size // 2).astype(np.float64)                       # [W, t_max, 4, 2]
+    far = (np.abs(P[:, 1:] - P[:, :-1]).reshape(W, t_max - 1, 8).max(axis=2) > 0.1).tolist() if t_max > 1 else [[]] * W
+    keep, all_w, all_src, all_conf, all_valid, counts, geo = [], [], [], [], [], [], []
+    for w, (i, n) in enumerate(work):
+        sp, orig, tokens, sc, rows = items[i]
+        texts, src, csrc, valid = line_runs(proc, tokens[:n], far[w])
+        if not texts:                      # nothing decoded (reference :889-899)
+            out[i] = TextLine(text="", polygon=flat["polygons"][orig], chars=[], confidence=1, original_text_good=True)
+            continue
+        polygon = coerce_polygon(flat["polygons"][orig])
+        xs, ys = [p[0] for p in polygon], [p[1] for p in polygon]
+        bbox = [min(xs), min(ys), max(xs), max(ys)]
+        rs = flat["res_scales"][orig]
+        keep.append((i, texts, valid, polygon, bbox))
+        all_w.extend([w] * len(src)); all_src.extend(src); all_valid.extend(valid)
+        all_conf.extend([0.0 if sc[j] != sc[j] else sc[j] for j in csrc])          # TextChar's NaN -> 0 rule
+        counts.append(len(src))
+        geo.append((1.0 / rs[0], 1.0 / rs[1], bbox[0], bbox[1], bbox[2], bbox[3]))
+    if not keep:
+        return out
+    PP = P[all_w, all_src]                                                                    # [C, 4, 2]
+    v_all = np.asarray(all_valid, bool)
+    PP[~v_all] = _BLANK_POLY
+    g = np.repeat(np.asarray(geo, np.float64), counts, axis=0)[:, :, None]                    # [C, 6, 1]
+    PP[..., 0] = np.minimum(np.maximum(np.trunc(PP[..., 0] * g[:, 0]) + g[:, 2], g[:, 2]), g[:, 4])
+    PP[..., 1] = np.minimum(np.maximum(np.trunc(PP[..., 1] * g[:, 1]) + g[:, 3], g[:, 3]), g[:, 5])
+    polys = PP.tolist()
+    conf_arr = np.asarray(all_conf, np.float64)
+    special = proc.ocr_tokenizer.special_tokens
+    a = 0
+    for (i, texts, valid, polygon, bbox), c in zip(keep, counts):
+        b = a + c
+        confidence = float(np.mean(conf_arr[a:b]))
+        chars = [_text_char(pg, cf, t, v) for pg, cf, t, v in zip(polys[a:b], all_conf[a:b], texts, valid)]
+        a = b
+        if not all(valid):                                   # tags only come from special / math runs (bbox_valid False)
+            chars = fix_unbalanced_tags(chars, special)
+            text = "".join(ch.text for ch in chars)
+        else:
+            text = "".join(texts)
+        if "<" in text:
+            text = clean_math_tags(unwrap_math(text))
+        words = words_from_chars(chars, PolygonBox(polygon=polygon)) if return_words else []
+        out[i] = _text_line(polygon, confidence, text, chars, words)
+    return out

@@ -1,0 +1,245 @@
+"""The recognition device loop: continuous batching over KV slots until every line stopped (reference recognition/__init__.py:501-607).
+One DeviceLoop per RecognitionPredictor.generate call owns ALL loop state -- queue, slot table, token / score / box matrices, admitted
+chunks, look-ahead queue, the decode call in flight -- so a loop that died leaves nothing behind but what the model handle keeps
+(unconsumed look-ahead images: `run` discards them first). It knows the model surface, not the predictor."""
+from collections import deque
+
+import numpy as np
+
+from ..settings import settings
+from .postprocess import detect_repeat_token
+
+FEED_END = object()          # what a `generate(feed=...)` callable returns once no further lines will come
+_REP = 40                    # detect_repeat_token's window
+_REP_COLS = np.arange(-_REP, 0)
+
+
+class DeviceLoop:
+    """on_done(line, tokens, scores, bbox_rows[T, 6]) is called once per line, as soon as its stream is final; on_flush() after
+    every host synchronisation point that finished at least one line (so a caller can hand the lines over in batches).
+
+    `feed` (optional) makes the line list open-ended: `feed(block)` returns the next `prepare_lines` dict whose prompts carry
+    the ids that continue the ones already admitted (queue order == id order), None when nothing is ready (only for block =
+    False) or FEED_END. The loop polls it between decode calls and blocks on it only when it has nothing left to run, so lines
+    can be admitted while their producer (the detector of a streamed detect -> recognise call) still works on later pages.
+    Scheduling decisions never change a line's stream (slot / batch-composition invariance), so the result per line is the
+    one the closed list gives."""
+
+    def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None):
+        self.model, self.eos, self.pad, self.nop, self.slots = model, eos, pad, nop, slots
+        self.overall_max_tokens, self.min_prefill_ratio = overall_max_tokens, min_prefill_ratio
+        self.on_done, self.on_flush, self.feed, self.feed_done = on_done, on_flush, feed, feed is None
+        self.steps_per_sync = max(1, min(settings.RECOGNITION_STEPS_PER_SYNC, 8))
+        self.max_prefill = model.c.max_prefill_tokens
+        self.queue = deque()                                   # ids of the admitted lines that wait for a slot, in id order
+        self.grids, self.prompt_ids, self.predicted_tokens, self.scores = [], [], [], []      # per line
+        self.chunk_tiles, self.chunk_offs, self.chunk_base = [], [], []      # per admitted dict: its tile tensor, local tile offsets, first id
+        self.line_chunk = np.zeros(0, np.int64)                # id -> index into the three lists above
+        self.batch_bboxes = np.zeros((0, overall_max_tokens, 6), np.float32)
+        # Token bookkeeping in array form: one row per line, written for all active slots of a step at once (the per-token Python
+        # loop cost 1.2-1.6 us per token, a third of the device's own time per decode call, and fought the assembly thread for
+        # the GIL). slot_line is THE slot table: the line id a slot decodes, -1 for an empty slot.
+        self.cap = max(1, overall_max_tokens) + 1
+        self.tok_mat = np.zeros((0, self.cap), np.int64)
+        self.sc_mat = np.zeros((0, self.cap), np.float32)
+        self.line_len, self.max_tok = np.zeros(0, np.int64), np.zeros(0, np.int64)      # tokens so far / token budget per line
+        self.slot_line = np.full(slots, -1, np.int64)
+        # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
+        # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
+        # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
+        self.look_ahead, self.ahead = settings.RECOGNITION_ENCODE_AHEAD, deque()      # ahead: the encoded ids, in id order
+        self.ahead_cap = max(model.c.max_prefill_tokens, model.c.max_slots)
+        self.merge2 = model.cfg.encoder.spatial_merge_size ** 2
+        self.inflight, self.ring = None, 0                     # the decode call whose outputs were not read yet: (steps, ring half)
+
+    @property
+    def num_active(self) -> int:
+        return int(np.count_nonzero(self.slot_line >= 0))
+
+    @property
+    def num_empty(self) -> int:
+        return self.slots - self.num_active
+
+    def admit(self, d):
+        """Append the lines of one prepare_lines dict (ids continue the admitted ones)."""
+        new = d["prompts"]
+        base, m = len(self.grids), len(new)
+        if m == 0:
+            return
+        assert [p.id for p in new] == list(range(base, base + m)), "fed prompts must continue the admitted ids"
+        mt = np.asarray([d["max_tokens"][p.id] for p in new], np.int64)
+        assert int(mt.max()) <= self.overall_max_tokens, "a fed line's token budget exceeds the call's overall_max_tokens"
+        self.grids.extend(d["grids"])
+        self.prompt_ids.extend(d["prompt_ids"])
+        self.predicted_tokens.extend([] for _ in range(m))
+        self.scores.extend([] for _ in range(m))
+        self.chunk_tiles.append(d["tiles"]); self.chunk_offs.append(d["tile_offs"]); self.chunk_base.append(base)
+        self.line_chunk = np.concatenate([self.line_chunk, np.full(m, len(self.chunk_base) - 1, np.int64)])
+        self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((m, self.overall_max_tokens, 6), np.float32)])
+        self.tok_mat = np.concatenate([self.tok_mat, np.zeros((m, self.cap), np.int64)])
+        self.sc_mat = np.concatenate([self.sc_mat, np.zeros((m, self.cap), np.float32)])
+        self.line_len = np.concatenate([self.line_len, np.zeros(m, np.int64)])
+        self.max_tok = np.concatenate([self.max_tok, mt])
+        self.queue.extend(range(base, base + m))
+
+    def tiles_of(self, first_id, last_id):
+        """Tile rows of the consecutive lines first_id..last_id (all of one admitted dict)."""
+        c = int(self.line_chunk[first_id])
+        assert c == int(self.line_chunk[last_id])
+        o, b0 = self.chunk_offs[c], self.chunk_base[c]
+        return self.chunk_tiles[c][int(o[first_id - b0]): int(o[last_id - b0 + 1])]
+
+    def poll(self, block):
+        """Admit what the feed has ready; with `block`, wait for the next dict (or the end)."""
+        got = False
+        while not self.feed_done:
+            nxt = self.feed(block and not got)
+            self.feed_done = nxt is FEED_END
+            if nxt is None or self.feed_done:
+                break
+            self.admit(nxt)
+            got = got or bool(nxt["prompts"])
+
+    def _finish(self, p_idx):
+        L_ = int(self.line_len[p_idx])
+        self.predicted_tokens[p_idx] = self.tok_mat[p_idx, :L_].tolist()
+        self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
+        if self.on_done is not None:
+            self.on_done(p_idx, self.predicted_tokens[p_idx], self.scores[p_idx],
+                         self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)])
+
+    def _put(self, p, pos, t, s_, b_):
+        """Token t / score s_ / box b_ of lines p at positions pos (arrays over the lines of one step)."""
+        self.tok_mat[p, pos] = t
+        self.sc_mat[p, pos] = s_
+        m = pos < self.overall_max_tokens
+        if m.all():
+            self.batch_bboxes[p, pos] = b_
+        elif m.any():
+            self.batch_bboxes[p[m], pos[m]] = b_[m]
+        self.line_len[p] = pos + 1
+
+    def _flush_active(self):
+        """Tell the model which slots still decode (ascending) and let the caller collect the lines that just finished."""
+        self.model.set_active(np.flatnonzero(self.slot_line >= 0).tolist())
+        if self.on_flush is not None:
+            self.on_flush()
+
+    def absorb(self, call):
+        """Host half of one decode call: append its tokens, apply the stop rules (reference :583-595)."""
+        k, ring = call
+        tok, sc, bb = self.model.wait_outputs(k, ring)
+        slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
+        changed = False
+        for step in range(k):
+            s_idx = np.flatnonzero(slot_line >= 0)
+            if s_idx.size == 0:
+                break
+            p = slot_line[s_idx]
+            pos = line_len[p]
+            t = tok[step, s_idx]
+            self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
+            new_len = pos + 1
+            stop = (t == eos) | (t == pad) | (new_len >= max_tok[p])
+            # repeat rule: <= 5 distinct ids in the last 40 and the last u ids equal to the u before; the distinct count is
+            # screened in array form, only the few candidate lines run the exact rule
+            c = np.flatnonzero(~stop & (new_len >= _REP))
+            if c.size:
+                win = np.sort(tok_mat[p[c, None], new_len[c, None] + _REP_COLS], axis=1)
+                few = c[(np.diff(win, axis=1) != 0).sum(axis=1) + 1 <= 5]
+                for ci in few.tolist():
+                    if detect_repeat_token(tok_mat[p[ci], :new_len[ci]].tolist()):
+                        stop[ci] = True
+            if stop.any():
+                changed = True
+                for ci in np.flatnonzero(stop).tolist():
+                    slot_line[int(s_idx[ci])] = -1
+                    self._finish(int(p[ci]))
+        if changed:
+            self._flush_active()
+
+    def encode_ahead(self):
+        """Start the encoder pass of the next queued lines: up to a batch, within the look-ahead capacity, of ONE admitted dict."""
+        grids, line_chunk = self.grids, self.line_chunk
+        cand, ntok_img = [], 0
+        for i in self.queue:
+            t = int(grids[i][0]) * int(grids[i][1]) // self.merge2
+            if len(cand) >= self.slots or (cand and ntok_img + t > self.ahead_cap):
+                break
+            if cand and line_chunk[i] != line_chunk[cand[0]]:
+                break                                  # one tile tensor per encoder pass: the next admitted dict waits its turn
+            cand.append(i)
+            ntok_img += t
+        self.model.encode_ahead(self.tiles_of(cand[0], cand[-1]), [grids[i] for i in cand])
+        self.ahead.extend(cand)
+
+    def prefill_batch(self):
+        """Fill the empty slots (ascending) from the head of the queue; a line whose first token already stops never takes its slot."""
+        queue, ahead, look_ahead, line_chunk = self.queue, self.ahead, self.look_ahead, self.line_chunk
+        empty = np.flatnonzero(self.slot_line < 0).tolist()
+        if look_ahead and not ahead:
+            self.encode_ahead()                        # nothing encoded yet (first batch): the prefill below waits for it
+        take, ntok = [], 0
+        while queue and len(take) < len(empty) and (not look_ahead or len(take) < len(ahead)):
+            L_ = len(self.prompt_ids[queue[0]])
+            if take and (ntok + L_ > self.max_prefill or line_chunk[queue[0]] != line_chunk[take[0]]):
+                break
+            take.append(queue.popleft())
+            ntok += L_
+        slots = empty[: len(take)]
+        grids, prompt_ids = [self.grids[i] for i in take], [self.prompt_ids[i] for i in take]
+        if look_ahead:
+            for i in take:
+                assert ahead.popleft() == i
+            self.model.prefill(None, grids, prompt_ids, slots)
+            if not ahead and queue:
+                self.encode_ahead()                    # the next lines' encoder pass runs beside the decode steps below
+        else:
+            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, slots)      # queue order == id order
+        tok, sc, bb = self.model.read_outputs(1)
+        ids_, sl_ = np.asarray(take, np.int64), np.asarray(slots, np.int64)
+        first = tok[0, sl_]
+        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_])
+        for p_id, s, go in zip(take, slots, ((first != self.eos) & (first != self.nop)).tolist()):
+            if go:                                                  # prefill stop rule (reference :559-563)
+                self.slot_line[s] = p_id
+            else:
+                self._finish(p_id)
+        self._flush_active()
+
+    def run(self, prep=None):
+        """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
+        if callable(getattr(self.model, "discard_ahead", None)):
+            self.model.discard_ahead()                 # a previous loop that ended early (exception) must not poison this one
+        if prep is not None:
+            self.admit(prep)
+        # The device runs one decode call ahead of the host: call n + 1 is enqueued before call n's tokens are looked at,
+        # so the bookkeeping above overlaps with GPU work. A line that stops inside call n rides along in call n + 1
+        # (its outputs are dropped: the slot is unmapped by then); new lines are admitted only with nothing in flight.
+        while True:
+            if not self.feed_done:
+                self.poll(block=not (self.queue or self.inflight or self.num_active > 0))
+            if not (self.queue or self.inflight or self.num_active > 0):
+                if self.feed_done:
+                    break
+                continue
+            if self.queue and (self.num_empty / self.slots) > self.min_prefill_ratio:
+                if self.inflight:
+                    self.absorb(self.inflight)
+                    self.inflight = None
+                else:
+                    self.prefill_batch()
+                continue
+            # steps some active line can still need once the call in flight is done (token budgets are known up front)
+            act = self.slot_line[self.slot_line >= 0]
+            budget = (int((self.max_tok[act] - self.line_len[act]).max()) if act.size else 0) - (self.inflight[0] if self.inflight else 0)
+            if budget <= 0 and not self.inflight and act.size:
+                budget = 1                             # a line admitted with a one-token budget still gets its stop-rule step
+            nxt = None
+            if budget > 0:
+                nxt = (min(self.steps_per_sync, budget), self.ring)
+                self.model.decode_async(*nxt)
+                self.ring ^= 1
+            if self.inflight:
+                self.absorb(self.inflight)
+            self.inflight = nxt

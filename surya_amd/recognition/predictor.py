@@ -15,12 +15,9 @@ There is no CPU fallback: without the HIP library and a GPU, construction raises
 """
 from __future__ import annotations
 
-import json
 import os
-import re
 import time
-from array import array
-from collections import deque
+import zlib
 from concurrent.futures import ThreadPoolExecutor
 from dataclasses import dataclass
 from typing import List, Optional
@@ -29,53 +26,15 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ..common.geometry import PolygonBox, coerce_polygon
 from ..common.imageops import fill_poly_mask
-from ..common.predictor import BasePredictor, ModelLoader, gc_paused
-from ..config import RecConfig, rec_config
+from ..common.predictor import BasePredictor, gc_paused
 from ..settings import settings
-from .model import HipRecModel
+from . import assemble
+from .loader import RecognitionModelLoader, rec_config_from_reference_json  # noqa: F401  (re-exported)
+from .loop import FEED_END, DeviceLoop
 from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref
-from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags,
-                          prediction_to_polygon_batch, sort_text_lines, unwrap_math, words_from_chars)
-from .processor import NOMATH_TOKEN, SuryaOCRProcessor
-from .schema import OCRResult, TaskNames, TextChar, TextLine
-from .tokenizer import ByteMathTokenizer, OCRTokenizer
-
-
-_SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
-_CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
-assert _CHAR_FIELDS == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
-_new_char, _set = TextChar.__new__, object.__setattr__
-
-
-def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
-    """TextChar.model_construct(...) with all four fields given, without its per-call field loop (1.9 -> 0.55 us; a page of
-    text is ~10^4 of these). Same object state: __dict__, fields_set, no extras, no private attributes."""
-    m = _new_char(TextChar)
-    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid})
-    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))
-    _set(m, "__pydantic_extra__", None)
-    _set(m, "__pydantic_private__", None)
-    return m
-
-
-_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words")
-assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
-_new_line = TextLine.__new__
-_BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
-
-
-def _text_line(polygon, confidence, text, chars, words) -> TextLine:
-    """TextLine(...) for values that are already in validated form (polygon = coerce_polygon(...), confidence not NaN, chars a
-    list of TextChar): the object state validation would produce, without walking the character list again."""
-    m = _new_line(TextLine)
-    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
-                         "original_text_good": False, "words": words})
-    _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
-    _set(m, "__pydantic_extra__", None)
-    _set(m, "__pydantic_private__", None)
-    return m
+from .postprocess import sort_text_lines
+from .schema import OCRResult, TaskNames, TextLine
 
 
 # ------------------------------------------------------------------------------------------------ input slicing
@@ -117,116 +76,70 @@ def slice_polys_from_image(image: np.ndarray, polys) -> List[np.ndarray]:
     return [slice_and_pad_poly(image, p) for p in polys]
 
 
-# ------------------------------------------------------------------------------------------------------ loader
-class RecognitionModelLoader(ModelLoader):
-    """`checkpoint` may be None (synthetic config named by SURYA_AMD_REC_CONFIG), a dict
-    {"config": RecConfig, "state_dict": {...}}, or a directory holding the reference's HF-format files
-    (config.json + *.safetensors; recognition/loader.py:25-82)."""
-
-    def __init__(self, checkpoint=None):
-        super().__init__(checkpoint)
-        self._cfg: Optional[RecConfig] = None
-        self._sd = None
-        self._special_tokens = None
-
-    def _resolve(self):
-        if self._cfg is not None:
-            return
-        ck = self.checkpoint
-        if isinstance(ck, dict):
-            self._cfg, self._sd = ck["config"], ck["state_dict"]
-            self._special_tokens = ck.get("special_tokens")
-        elif isinstance(ck, str) and os.path.isdir(ck):
-            from safetensors.torch import load_file
-            with open(os.path.join(ck, "config.json")) as f:
-                raw = json.load(f)
-            self._cfg = rec_config_from_reference_json(raw)
-            self._special_tokens = raw.get("special_ocr_tokens")
-            self._sd = None if self._receives_weights() else {}
-            for fn in sorted(os.listdir(ck)):
-                if fn.endswith(".safetensors") and self._sd is not None:
-                    self._sd.update(load_file(os.path.join(ck, fn)))
-        else:
-            from ..synth import make_rec_weights
-            self._cfg = rec_config(ck if isinstance(ck, str) else settings.SURYA_AMD_REC_CONFIG)
-            self._sd = None if self._receives_weights() else make_rec_weights(self._cfg, 0)
-
-    @staticmethod
-    def _receives_weights() -> bool:
-        """SURYA_AMD_BROADCAST_WEIGHTS with an initialised process group: only rank 0 reads / builds the state dict."""
-        if not settings.SURYA_AMD_BROADCAST_WEIGHTS:
-            return False
-        from .. import dist as sdist
-        rank, world = sdist.world_info()
-        return world > 1 and rank != 0
-
-    def tokenizer(self) -> OCRTokenizer:
-        self._resolve()
-        if isinstance(self.checkpoint, str) and os.path.isdir(self.checkpoint):
-            # Real checkpoint: the id layout is DEFINED by the files (processor/tokenizer.py:224-260) -- the Qwen2 BPE that
-            # ships with it sets qwen_offset, special_ocr_tokens["all"] sets the tag range, exactly len(unique tags) wide.
-            # No placeholder tags, no byte-tokenizer stand-in: either would shift every UTF-16 id silently.
-            from transformers import Qwen2Tokenizer
-            math_tok = Qwen2Tokenizer.from_pretrained(self.checkpoint)      # raises if the vocabulary files are missing
-            if not self._special_tokens or not self._special_tokens.get("all"):
-                raise ValueError(f"{self.checkpoint}/config.json has no special_ocr_tokens; cannot lay out token ids")
-            tok = OCRTokenizer(self._special_tokens, math_tok, reserve_special=0)
-            # the lm_head may be PADDED beyond the tokenizer (the reference never ties the two sizes); ids the tokenizer does not
-            # know can then be emitted and decode to nothing. A tokenizer LARGER than the head cannot be right.
-            if tok.vocab_size > self._cfg.decoder.vocab_size:
-                raise ValueError(f"token-id layout mismatch: qwen_offset {tok.qwen_offset} + {tok.num_special} tags + 65536 "
-                                 f"UTF-16 units = {tok.vocab_size} > decoder.vocab_size = {self._cfg.decoder.vocab_size}")
-            if tok.vocab_size < self._cfg.decoder.vocab_size:
-                import warnings
-                warnings.warn(f"decoder.vocab_size {self._cfg.decoder.vocab_size} exceeds the tokenizer's {tok.vocab_size} ids "
-                              "(padded lm_head); ids beyond the tokenizer decode to nothing")
-            return tok
-        # synthetic configs only: one id per UTF-8 byte stands in for the BPE, and the tag range is padded to the
-        # config's fixed width (a randomly initialised model can emit any id)
-        return OCRTokenizer(self._special_tokens, ByteMathTokenizer(self._cfg.qwen_offset),
-                            reserve_special=self._cfg.num_special_tokens)
-
-    def model(self, device=None, dtype=None, **caps) -> HipRecModel:
-        self._resolve()
-        if device is None:
-            device = settings.TORCH_DEVICE_MODEL
-        if device == "cuda":
-            device = "cuda:0"
-        if dtype is None:
-            dtype = torch.bfloat16          # recognition/loader.py:35-38 picks bf16 on GPUs with native bf16
-        tok = self.tokenizer()
-        sysm = tok.system_tokens
-        caps.setdefault("max_slots", settings.RECOGNITION_BATCH_SIZE or RecognitionPredictor.default_batch_sizes["cuda"])
-        caps.setdefault("max_kv_len", 1536 + 32)
-        if settings.SURYA_AMD_BROADCAST_WEIGHTS:
-            from .. import dist as sdist
-            caps.setdefault("broadcast_weights", sdist.collectives_on())
-        return HipRecModel(self._cfg, self._sd, image_token_id=sysm["<IMAGE>"], pad_token_id=sysm["<PAD>"],
-                           eos_token_id=sysm["</S>"], dtype=dtype, device=device, **caps)
-
-    def processor(self, device=None, dtype=None) -> SuryaOCRProcessor:
-        self._resolve()
-        e = self._cfg.encoder
-        return SuryaOCRProcessor(self.tokenizer(), self._cfg.num_register_tokens, e.patch_size, e.spatial_merge_size)
+def new_flat() -> dict:
+    """The lines of one call, flattened over its pages. By line id (sorted / admission order): slices, task_names, input_text;
+    by ORIGINAL position (page order): polygons, res_scales; slice_map holds the line count per page. The device path adds "pages"."""
+    return {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
 
 
-def rec_config_from_reference_json(raw: dict) -> RecConfig:
-    """Map a SuryaModelConfig config.json (surya/common/surya/config.py) onto RecConfig."""
-    from ..config import DecoderConfig, EncoderConfig
-    ve, de = raw.get("vision_encoder", {}), raw.get("decoder", {})
-    enc = EncoderConfig(**{k: (tuple(v) if isinstance(v, list) else v) for k, v in ve.items()
-                           if k in EncoderConfig.__dataclass_fields__})
-    dkw = {k: v for k, v in de.items() if k in DecoderConfig.__dataclass_fields__}
-    if "head_dim" not in dkw and "hidden_size" in dkw and "num_attention_heads" in dkw:
-        dkw["head_dim"] = dkw["hidden_size"] // dkw["num_attention_heads"]
-    dec = DecoderConfig(**dkw)
-    return RecConfig(name="checkpoint", encoder=enc, decoder=dec, bbox_size=raw.get("bbox_size", 1025),
-                     image_embed_encoding_size=raw.get("image_embed_encoding_size", 1024),
-                     image_embed_encoding_multiplier=raw.get("image_embed_encoding_multiplier", 256),
-                     num_register_tokens=raw.get("num_register_tokens", 4))
+def page_lines(det_pred, image, highres):
+    """One page's detected polygons -> (the polygons, the image its crops are cut from, the polygons in that image's pixels, its
+    scale against the detected page). With a high-resolution copy of the page the crops come from the copy."""
+    polygons = [p.polygon for p in det_pred.bboxes]
+    if not highres:
+        return polygons, image, polygons, (1, 1)
+    ws, hs = highres.size[0] / image.size[0], highres.size[1] / image.size[1]
+    return polygons, highres, [[[int(p[0] * ws), int(p[1] * hs)] for p in poly] for poly in polygons], (ws, hs)
 
 
-FEED_END = object()          # what a `generate(feed=...)` callable returns once no further lines will come
+def inputs_fingerprint(shapes, chunks) -> list:
+    """What every rank of a sharded call must agree on (dist.assert_same_inputs): the item count, a CRC of the items' (h, w) or
+    (w, h) pairs and a CRC of sample bytes."""
+    shapes = np.asarray(shapes, np.int64).reshape(-1, 2)
+    return [len(shapes), zlib.crc32(shapes.tobytes()), zlib.crc32(b"".join(chunks))]
+
+
+class AssemblyHandover(ThreadPoolExecutor):
+    """One call's assembly worker. Output assembly is host work of the same order as the device loop itself; it runs on one worker
+    thread WHILE the device decodes the next lines: the lines that stopped at a synchronisation point (`on_done` each, then `on_flush`)
+    are handed over together (batched numpy work, `_assemble_batch`). The scheduler thread spends most of its time blocked in
+    hipEventSynchronize (GIL released), which is when the worker runs. `orig_of[k]`: the original position of line id k."""
+
+    def __init__(self, pred, flat, orig_of, drop_repeated_text, return_words):
+        self.pred, self.flat, self.orig_of = pred, flat, orig_of
+        self.options = (drop_repeated_text, return_words, pred.model.cfg.bbox_size)
+        super().__init__(1)                                    # (as a context manager: the worker is joined on the way out)
+        self.futures, self.pending = [], []
+
+    def assemble(self, batch):
+        # batch = [(line id, tokens, scores, bbox_rows)]: the lines that stopped at one synchronisation point
+        return self.pred._assemble_batch(self.flat, [(k, self.orig_of[k], t, sc, bb) for k, t, sc, bb in batch], *self.options)
+
+    def on_done(self, k, tokens, sc, bbox_rows):
+        self.pending.append((k, list(tokens), list(sc), bbox_rows.copy()))
+
+    def on_flush(self):
+        if self.pending:
+            batch = self.pending[:]
+            self.pending.clear()
+            self.futures.append(([b[0] for b in batch], self.submit(self.assemble, batch)))
+
+    def finish(self, stamps, t_loop) -> list:
+        """After the loop: hand over what is pending, wait for the worker; the TextLines by ORIGINAL position."""
+        self.on_flush()
+        t2 = time.perf_counter()
+        text_lines = self.place((ks, f.result()) for ks, f in self.futures)
+        stamps.update(device_loop_ms=(t2 - t_loop) * 1e3, assemble_tail_ms=(time.perf_counter() - t2) * 1e3)
+        return text_lines
+
+    def place(self, groups) -> list:
+        """groups = [(line ids, their TextLines)] -> the TextLines by ORIGINAL position, every position filled."""
+        text_lines = [None] * len(self.orig_of)
+        for ks, lines in groups:
+            for k, line in zip(ks, lines):
+                text_lines[self.orig_of[k]] = line
+        assert all(t is not None for t in text_lines)
+        return text_lines
 
 
 @dataclass
@@ -261,24 +174,11 @@ class RecognitionPredictor(BasePredictor):
     # pixels as uint8 and describes lines by reference. RECOGNITION_PREPROCESS_HOST=1 selects the host (numpy) chain instead.
     device_preprocess: bool = not settings.RECOGNITION_PREPROCESS_HOST
 
-    def __init__(self, checkpoint=None, device=None, dtype=None):
-        super().__init__(checkpoint, device, dtype)
-        self.prompt_queue = deque()
-        self.batch_prompt_mapping = None
-        self.preprocess_workers = min(8, os.cpu_count() or 1)
+    preprocess_workers: int = min(8, os.cpu_count() or 1)   # threads of the host pre-processing chain
 
-    # ------------------------------------------------------------------------------------------ bookkeeping
-    def setup_cache(self, batch_size: int):
-        self.prompt_queue.clear()
-        self.batch_prompt_mapping = {i: None for i in range(batch_size)}
-
-    @property
-    def num_empty_slots(self):
-        return sum(v is None for v in self.batch_prompt_mapping.values())
-
-    @property
-    def num_active_slots(self):
-        return len(self.batch_prompt_mapping) - self.num_empty_slots
+    def line_budget(self, task) -> int:
+        """Token budget of one line of `task`."""
+        return settings.RECOGNITION_MAX_TOKENS or self.tasks[task]["max_tokens"]
 
     # --------------------------------------------------------------------------------------------- slicing
     def _page(self, flat: dict, image) -> int:
@@ -288,17 +188,9 @@ class RecognitionPredictor(BasePredictor):
 
     def detect_and_slice_bboxes(self, images, task_names, det_predictor, detection_batch_size=None, highres_images=None):
         det_predictions = det_predictor(images, batch_size=detection_batch_size)
-        flat = {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
+        flat = new_flat()
         for det_pred, image, highres, task in zip(det_predictions, images, highres_images, task_names):
-            polygons = [p.polygon for p in det_pred.bboxes]
-            if highres:
-                ws, hs = highres.size[0] / image.size[0], highres.size[1] / image.size[1]
-                scaled = [[[int(p[0] * ws), int(p[1] * hs)] for p in poly] for poly in polygons]
-                src, polys_px = highres, scaled
-                scales = [(ws, hs)] * len(polygons)
-            else:
-                src, polys_px = image, polygons
-                scales = [(1, 1)] * len(polygons)
+            polygons, src, polys_px, scale = page_lines(det_pred, image, highres)
             if self.device_preprocess:
                 pg = self._page(flat, src)
                 slices = [poly_ref(pg, src.size[0], src.size[1], poly) for poly in polys_px]
@@ -308,13 +200,13 @@ class RecognitionPredictor(BasePredictor):
             flat["slices"].extend(slices)
             flat["polygons"].extend(polygons)
             flat["task_names"].extend([task] * len(slices))
-            flat["res_scales"].extend(scales)
+            flat["res_scales"].extend([scale] * len(polygons))
         flat["input_text"] = [None] * len(flat["slices"])
         return flat
 
     def slice_bboxes(self, images, task_names, bboxes=None, polygons=None, input_text=None) -> dict:
         assert bboxes is not None or polygons is not None
-        flat = {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
+        flat = new_flat()
         # ONE decision for the whole call (prepare_lines dispatches on the type of the first slice): the device path takes 4-point
         # polygons only, so a single polygon with another vertex count anywhere sends every image of the call down the host path
         dev = self.device_preprocess and (polygons is None or all(len(pl) == 4 for page in polygons for pl in page))
@@ -405,7 +297,7 @@ class RecognitionPredictor(BasePredictor):
         prompts, max_tokens = [], {}
         for idx, (img, txt, task) in enumerate(zip(flat["slices"], flat["input_text"], flat["task_names"])):
             prompts.append(RecognitionPrompt(id=idx, task_name=task, text=txt, image=img, math_mode=math_mode))
-            max_tokens[idx] = settings.RECOGNITION_MAX_TOKENS or self.tasks[task]["max_tokens"]
+            max_tokens[idx] = self.line_budget(task)
         if prompts and isinstance(prompts[0].image, LineRef):
             tiles, tile_offs, grids, prompt_ids = self.preprocess_prompts_device(prompts, flat.get("pages", []))
         else:
@@ -414,239 +306,22 @@ class RecognitionPredictor(BasePredictor):
                 "prompt_ids": prompt_ids}
 
     def generate(self, prep: dict | None, recognition_batch_size: int | None = None, on_done=None, on_flush=None, feed=None) -> tuple:
-        """Device half: continuous batching over KV slots until every line stopped (reference :501-607).
-        on_done(line, tokens, scores, bbox_rows[T, 6]) is called once per line, as soon as its stream is final; on_flush() after
-        every host synchronisation point that finished at least one line (so a caller can hand the lines over in batches).
-
-        `feed` (optional) makes the line list open-ended: `feed(block)` returns the next `prepare_lines` dict whose prompts carry
-        the ids that continue the ones already admitted (queue order == id order), None when nothing is ready (only for block =
-        False) or FEED_END. The loop polls it between decode calls and blocks on it only when it has nothing left to run, so lines
-        can be admitted while their producer (the detector of a streamed detect -> recognise call) still works on later pages.
-        Scheduling decisions never change a line's stream (slot / batch-composition invariance), so the result per line is the
-        one the closed list gives. A streamed call states its token budget up front in the first dict (`overall_max_tokens`)."""
-        prompts, grids, prompt_ids = [], [], []
-        batch_max_tokens: dict = {}
-        predicted_tokens, scores = [], []
-        chunk_tiles, chunk_offs, chunk_base = [], [], []      # per admitted dict: its tile tensor, local tile offsets, first id
-        line_chunk = np.zeros(0, np.int64)                    # id -> index into the three lists above
+        """Device half: one DeviceLoop (loop.py, which documents on_done / on_flush / feed) run until every line stopped (reference
+        :501-607). A streamed call states its token budget up front in the first dict (`overall_max_tokens`)."""
         if recognition_batch_size is None:
             recognition_batch_size = self.get_batch_size()
-        recognition_batch_size = min(recognition_batch_size, self.model.max_slots)
-        self.setup_cache(recognition_batch_size)
-        if callable(getattr(self.model, "discard_ahead", None)):
-            self.model.discard_ahead()                         # a previous loop that ended early (exception) must not poison this one
         first = prep if prep is not None else {}
         overall_max_tokens = int(first.get("overall_max_tokens") or max(first["max_tokens"].values()))
-        batch_bboxes = np.zeros((0, overall_max_tokens, 6), np.float32)
-        eos, pad, nop = self.processor.eos_token_id, self.processor.pad_token_id, self.processor.no_output_token
-        steps_per_sync = max(1, min(settings.RECOGNITION_STEPS_PER_SYNC, 8))
-        max_prefill = self.model.c.max_prefill_tokens
-        # Token bookkeeping in array form: one row per line, written for all active slots of a step at once (the per-token Python
-        # loop cost 1.2-1.6 us per token, a third of the device's own time per decode call, and fought the assembly thread for
-        # the GIL). batch_prompt_mapping stays the slot table the scheduling decisions read; slot_line mirrors it as an array.
-        cap = max(1, overall_max_tokens) + 1
-        tok_mat = np.zeros((0, cap), np.int64)
-        sc_mat = np.zeros((0, cap), np.float32)
-        line_len = np.zeros(0, np.int64)
-        max_tok = np.zeros(0, np.int64)
-        slot_line = np.full(recognition_batch_size, -1, np.int64)
-        REP = 40                                               # detect_repeat_token's window
-        rep_cols = np.arange(-REP, 0)
-
-        def admit(d):
-            """Append the lines of one prepare_lines dict (ids continue the admitted ones)."""
-            nonlocal batch_bboxes, tok_mat, sc_mat, line_len, max_tok, line_chunk
-            new = d["prompts"]
-            base, m = len(prompts), len(new)
-            if m == 0:
-                return
-            assert [p.id for p in new] == list(range(base, base + m)), "fed prompts must continue the admitted ids"
-            mt = np.asarray([d["max_tokens"][p.id] for p in new], np.int64)
-            assert int(mt.max()) <= overall_max_tokens, "a fed line's token budget exceeds the call's overall_max_tokens"
-            prompts.extend(new)
-            grids.extend(d["grids"])
-            prompt_ids.extend(d["prompt_ids"])
-            batch_max_tokens.update(d["max_tokens"])
-            predicted_tokens.extend([] for _ in range(m))
-            scores.extend([] for _ in range(m))
-            chunk_tiles.append(d["tiles"]); chunk_offs.append(d["tile_offs"]); chunk_base.append(base)
-            line_chunk = np.concatenate([line_chunk, np.full(m, len(chunk_base) - 1, np.int64)])
-            batch_bboxes = np.concatenate([batch_bboxes, np.zeros((m, overall_max_tokens, 6), np.float32)])
-            tok_mat = np.concatenate([tok_mat, np.zeros((m, cap), np.int64)])
-            sc_mat = np.concatenate([sc_mat, np.zeros((m, cap), np.float32)])
-            line_len = np.concatenate([line_len, np.zeros(m, np.int64)])
-            max_tok = np.concatenate([max_tok, mt])
-            self.prompt_queue.extend(new)
-
-        def tiles_of(first_id, last_id):
-            """Tile rows of the consecutive lines first_id..last_id (all of one admitted dict)."""
-            c = int(line_chunk[first_id])
-            assert c == int(line_chunk[last_id])
-            o, b0 = chunk_offs[c], chunk_base[c]
-            return chunk_tiles[c][int(o[first_id - b0]): int(o[last_id - b0 + 1])]
-
-        feed_done = feed is None
-
-        def poll(block):
-            """Admit what the feed has ready; with `block`, wait for the next dict (or the end)."""
-            nonlocal feed_done
-            got = False
-            while not feed_done:
-                nxt = feed(block and not got)
-                if nxt is None:
-                    break
-                if nxt is FEED_END:
-                    feed_done = True
-                    break
-                admit(nxt)
-                got = got or bool(nxt["prompts"])
-
-        if prep is not None:
-            admit(prep)
-
-        def finished(p_idx):
-            L_ = int(line_len[p_idx])
-            predicted_tokens[p_idx] = tok_mat[p_idx, :L_].tolist()
-            scores[p_idx] = sc_mat[p_idx, :L_].tolist()
-            if on_done is not None:
-                on_done(p_idx, predicted_tokens[p_idx], scores[p_idx], batch_bboxes[p_idx, :max(min(L_, overall_max_tokens), 1)])
-
-        def put(p, pos, t, s_, b_):
-            """Token t / score s_ / box b_ of lines p at positions pos (arrays over the lines of one step)."""
-            tok_mat[p, pos] = t
-            sc_mat[p, pos] = s_
-            m = pos < overall_max_tokens
-            if m.all():
-                batch_bboxes[p, pos] = b_
-            elif m.any():
-                batch_bboxes[p[m], pos[m]] = b_[m]
-            line_len[p] = pos + 1
-
-        def absorb(call):
-            """Host half of one decode call: append its tokens, apply the stop rules (reference :583-595)."""
-            k, ring = call
-            tok, sc, bb = self.model.wait_outputs(k, ring)
-            changed = False
-            for step in range(k):
-                s_idx = np.flatnonzero(slot_line >= 0)
-                if s_idx.size == 0:
-                    break
-                p = slot_line[s_idx]
-                pos = line_len[p]
-                t = tok[step, s_idx]
-                put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
-                new_len = pos + 1
-                stop = (t == eos) | (t == pad) | (new_len >= max_tok[p])
-                # repeat rule: <= 5 distinct ids in the last 40 and the last u ids equal to the u before; the distinct count is
-                # screened in array form, only the few candidate lines run the exact rule
-                c = np.flatnonzero(~stop & (new_len >= REP))
-                if c.size:
-                    win = np.sort(tok_mat[p[c, None], new_len[c, None] + rep_cols], axis=1)
-                    few = c[(np.diff(win, axis=1) != 0).sum(axis=1) + 1 <= 5]
-                    for ci in few.tolist():
-                        if detect_repeat_token(tok_mat[p[ci], :new_len[ci]].tolist()):
-                            stop[ci] = True
-                if stop.any():
-                    changed = True
-                    for ci in np.flatnonzero(stop).tolist():
-                        s_ = int(s_idx[ci])
-                        slot_line[s_] = -1
-                        self.batch_prompt_mapping[s_] = None
-                        finished(int(p[ci]))
-            if changed:
-                self.model.set_active([k_ for k_, v in self.batch_prompt_mapping.items() if v is not None])
-                if on_flush is not None:
-                    on_flush()
-
-        # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
-        # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
-        # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
-        look_ahead = settings.RECOGNITION_ENCODE_AHEAD
-        ahead = deque()
-        ahead_cap = max(self.model.c.max_prefill_tokens, self.model.c.max_slots)
-        merge2 = self.model.cfg.encoder.spatial_merge_size ** 2
-
-        def encode_ahead():
-            cand, ntok_img = [], 0
-            for p in self.prompt_queue:
-                t = int(grids[p.id][0]) * int(grids[p.id][1]) // merge2
-                if len(cand) >= recognition_batch_size or (cand and ntok_img + t > ahead_cap):
-                    break
-                if cand and line_chunk[p.id] != line_chunk[cand[0]]:
-                    break                              # one tile tensor per encoder pass: the next admitted dict waits its turn
-                cand.append(p.id)
-                ntok_img += t
-            self.model.encode_ahead(tiles_of(cand[0], cand[-1]), [grids[i] for i in cand])
-            ahead.extend(cand)
-
-        # The device runs one decode call ahead of the host: call n + 1 is enqueued before call n's tokens are looked at,
-        # so the bookkeeping above overlaps with GPU work. A line that stops inside call n rides along in call n + 1
-        # (its outputs are dropped: the slot is unmapped by then); new lines are admitted only with nothing in flight.
-        inflight, ring = None, 0
-        while True:
-            if not feed_done:
-                poll(block=not (self.prompt_queue or self.num_active_slots > 0 or inflight))
-            if not (self.prompt_queue or self.num_active_slots > 0 or inflight):
-                if feed_done:
-                    break
-                continue
-            if (self.num_empty_slots / recognition_batch_size) > self.min_prefill_ratio and self.prompt_queue:
-                if inflight:
-                    absorb(inflight)
-                    inflight = None
-                    continue
-                empty = [k for k, v in self.batch_prompt_mapping.items() if v is None]
-                if look_ahead and not ahead:
-                    encode_ahead()                     # nothing encoded yet (first batch): the prefill below waits for it
-                take, ntok = [], 0
-                while self.prompt_queue and len(take) < len(empty) and (not look_ahead or len(take) < len(ahead)):
-                    L_ = len(prompt_ids[self.prompt_queue[0].id])
-                    if take and (ntok + L_ > max_prefill or line_chunk[self.prompt_queue[0].id] != line_chunk[take[0].id]):
-                        break
-                    take.append(self.prompt_queue.popleft())
-                    ntok += L_
-                slots = empty[: len(take)]
-                if look_ahead:
-                    for p in take:
-                        assert ahead.popleft() == p.id
-                    self.model.prefill(None, [grids[p.id] for p in take], [prompt_ids[p.id] for p in take], slots)
-                    if not ahead and self.prompt_queue:
-                        encode_ahead()                 # the next lines' encoder pass runs beside the decode steps below
-                else:
-                    self.model.prefill(tiles_of(take[0].id, take[-1].id), [grids[p.id] for p in take],   # queue order == id order
-                                       [prompt_ids[p.id] for p in take], slots)
-                tok, sc, bb = self.model.read_outputs(1)
-                ids_, sl_ = np.asarray([p.id for p in take], np.int64), np.asarray(slots, np.int64)
-                first = tok[0, sl_]
-                put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_])
-                for p_id, s, go in zip(ids_.tolist(), slots, ((first != eos) & (first != nop)).tolist()):
-                    if go:                                                  # prefill stop rule (reference :559-563)
-                        self.batch_prompt_mapping[s] = p_id
-                        slot_line[s] = p_id
-                    else:
-                        finished(p_id)
-                self.model.set_active([k for k, v in self.batch_prompt_mapping.items() if v is not None])
-                if on_flush is not None:
-                    on_flush()
-            else:
-                # steps some active line can still need once the call in flight is done (token budgets are known up front)
-                act = slot_line[slot_line >= 0]
-                budget = (int((max_tok[act] - line_len[act]).max()) if act.size else 0) - (inflight[0] if inflight else 0)
-                if budget <= 0 and not inflight and self.num_active_slots > 0:
-                    budget = 1                         # a line admitted with a one-token budget still gets its stop-rule step
-                nxt = None
-                if budget > 0:
-                    nxt = (min(steps_per_sync, budget), ring)
-                    self.model.decode_async(*nxt)
-                    ring ^= 1
-                if inflight:
-                    absorb(inflight)
-                inflight = nxt
+        proc = self.processor
+        loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
+                          min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
+                          on_done=on_done, on_flush=on_flush, feed=feed)
+        loop.run(prep)
         # the loop's own dense bookkeeping (ids [n, cap], scores [n, cap], lengths): what the sharded loop packs for its all_gather
         # without walking the per-line lists again
         from ..dist import PackedLines
-        self.last_packed = (PackedLines(tok_mat, line_len), PackedLines(sc_mat, line_len))
-        return predicted_tokens, torch.from_numpy(batch_bboxes), scores
+        self.last_packed = (PackedLines(loop.tok_mat, loop.line_len), PackedLines(loop.sc_mat, loop.line_len))
+        return loop.predicted_tokens, torch.from_numpy(loop.batch_bboxes), loop.scores
 
     def prediction_loop(self, flat: dict, recognition_batch_size: int | None = None, math_mode: bool = True) -> tuple:
         return self.generate(self.prepare_lines(flat, math_mode), recognition_batch_size)
@@ -657,27 +332,26 @@ class RecognitionPredictor(BasePredictor):
         recognises only the lines dealt to it round-robin, and all ranks get all results back through ONE all_gather
         (surya_amd/dist.py). No collective touches the per-step data path. Single process: plain loop."""
         from .. import dist as sdist
-        import zlib
         group = self.process_group
         rank, world = sdist.world_info(group)
-        n = len(flat["slices"])
+        slices = flat["slices"]
+        n = len(slices)
         if not sdist.collectives_on(group):                  # one rank (unless a forced 1-rank group, dist.force_collectives)
             return self.prediction_loop(flat, recognition_batch_size, math_mode)
         dev = sdist.collective_device(self.model.device, group)
-        shapes = np.asarray([s.shape[:2] for s in flat["slices"]], np.int64).reshape(-1, 2)
-        if n and isinstance(flat["slices"][0], LineRef):      # device path: lines are references into the uploaded pages
-            probe = b"".join(np.asarray([(l.page, l.x0, l.y0, l.x1, l.y1) for l in flat["slices"]], np.int64).tobytes()
-                             for _ in (0,)) + b"".join(pg.reshape(-1)[:4096].tobytes() for pg in flat.get("pages", [])[:16])
+        if n and isinstance(slices[0], LineRef):              # device path: lines are references into the uploaded pages
+            probe = [np.asarray([(l.page, l.x0, l.y0, l.x1, l.y1) for l in slices], np.int64).tobytes()]
+            probe += [pg.reshape(-1)[:4096].tobytes() for pg in flat.get("pages", [])[:16]]
         else:
-            probe = b"".join(np.ascontiguousarray(flat["slices"][i]).tobytes()[:4096] for i in range(0, n, max(1, n // 16)))
-        sdist.assert_same_inputs([n, zlib.crc32(shapes.tobytes()), zlib.crc32(probe)], group, dev)
+            probe = [np.ascontiguousarray(slices[i]).tobytes()[:4096] for i in range(0, n, max(1, n // 16))]
+        sdist.assert_same_inputs(inputs_fingerprint([s.shape[:2] for s in slices], probe), group, dev)
         if n == 0:
             return self.prediction_loop(flat, recognition_batch_size, math_mode)
         mine = sdist.shard_indices(n, world, rank)
         local = {k: [flat[k][i] for i in mine] for k in ("slices", "input_text", "task_names")}
         if "pages" in flat:
             local["pages"] = flat["pages"]
-        max_tokens = max(settings.RECOGNITION_MAX_TOKENS or self.tasks[t]["max_tokens"] for t in flat["task_names"])
+        max_tokens = max(self.line_budget(t) for t in flat["task_names"])
         if mine:
             self.last_packed = None                          # only what generate() sets DURING this call counts (a stand-in prediction_loop
             toks, boxes, scores = self.prediction_loop(local, recognition_batch_size, math_mode)      # must not gather an earlier call's arrays)
@@ -694,194 +368,29 @@ class RecognitionPredictor(BasePredictor):
         return toks, torch.from_numpy(boxes), scores
 
     # ------------------------------------------------------------------------------------- output assembly
+    # (assemble.py; the call paths reach it through these names, so a stand-in set on the instance takes effect)
     def get_bboxes_text(self, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False) -> list:
-        """Token stream -> per line (texts, confidences, bbox_valid, polygons [n, 4, 2]) (reference :609-771): the stream is cut
-        into runs of math-BPE ids, single special tags and UTF-16 ids; only the last kind carries per-character boxes.
-        Array form of the reference's per-token loop: run boundaries, close-polygon filtering and the
-        char -> box index map are numpy expressions per line; Python only walks the (few) runs of a line. Lines come back as
-        None (<NOP>), or a tuple that `_chars_of` turns into TextChars after the geometry has been applied in bulk."""
-        eos, pad, nop = self.processor.eos_token_id, self.processor.pad_token_id, self.processor.no_output_token
-        blank = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
-        out = []
-        for tokens, polys, sc in zip(predicted_tokens, predicted_polygons, scores):
-            if nop in tokens:
-                out.append(None)
-                continue
-            if drop_repeated_text and detect_repeat_token(tokens):
-                out.append(([""], np.zeros(1), np.zeros(1, bool), blank[None].copy()))
-                continue
-            tid = np.asarray(tokens, np.int64)
-            stop = np.nonzero((tid == eos) | (tid == pad))[0]
-            n = int(stop[0]) if len(stop) else len(tid)
-            n = min(n, len(polys), len(sc))              # zip() of the reference stops at the shortest of the three
-            if n == 0:
-                out.append(([], np.zeros(0), np.zeros(0, bool), np.zeros((0, 4, 2))))
-                continue
-            tid = tid[:n]
-            P = np.asarray(polys[:n], np.float64)
-            conf = np.asarray(sc[:n], np.float64)
-            # clean_close_polygons: a box is dropped when all 4 corners sit within 0.1 of the PREVIOUS box of its run (util.py:100-120)
-            far = (np.abs(P[1:] - P[:-1]).reshape(n - 1, 8).max(axis=1) > 0.1).tolist() if n > 1 else []
-            texts, src, csrc, valid = self._line_runs(tid.tolist(), far)
-            if not texts:
-                out.append(([], np.zeros(0), np.zeros(0, bool), np.zeros((0, 4, 2))))
-            else:
-                v = np.asarray(valid, bool)
-                pp = P[src]
-                pp[~v] = blank
-                out.append((texts, conf[csrc], v, pp))
-        return out
+        return assemble.get_bboxes_text(self.processor, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text)
 
-    def _line_runs(self, ids: list, far: list):
-        """The runs of one token stream (already cut at eos / pad): per output char its text, the token whose BOX it takes, the
-        token whose CONFIDENCE it takes, bbox_valid. `far[j]`: box j + 1 differs from box j by more than 0.1 in some corner. The
-        reference indexes a run's unfiltered confidences with the index into its FILTERED boxes (:700-712): kept as is."""
-        tk = self.processor.ocr_tokenizer
-        q_off, s_off = tk.qwen_offset, tk.special_token_offset
-        n = len(ids)
-        texts, src, csrc, valid = [], [], [], []
-        if n and min(ids) >= s_off:
-            kind = None                                  # one UTF-16 run (the usual line of text)
-        else:
-            kind = [0 if t < q_off else (1 if t < s_off else 2) for t in ids]
-        a_ = 0
-        while a_ < n:
-            if kind is None:
-                k, b_ = 2, n
-            else:
-                k = kind[a_]
-                b_ = a_ + 1
-                if k != 1:
-                    while b_ < n and kind[b_] == k:
-                        b_ += 1
-            if k == 2:
-                # a run of UTF-16 code units decodes in one piece (tokenizer._decode_ocr's flush of a non-math buffer)
-                # (ids above the tokenizer's range -- a checkpoint with a padded lm_head -- wrap into 16 bits like the byte masking
-                # of tokenizer._decode_ocr instead of raising OverflowError)
-                text = array("H", [(t - s_off) & 0xFFFF for t in ids[a_:b_]]).tobytes().decode("utf-16le", errors="ignore")
-                if text:
-                    boxes = [a_] + [j for j in range(a_ + 1, b_) if far[j - 1]]
-                    L, nb = len(text), len(boxes)
-                    texts.extend(text)
-                    src.extend(boxes[:L] if L <= nb else boxes + [boxes[-1]] * (L - nb))      # char i -> box min(i, nb - 1)
-                    csrc.extend(range(a_, a_ + L) if L <= nb else list(range(a_, a_ + nb)) + [a_ + nb - 1] * (L - nb))
-                    valid.extend([True] * L)
-            else:
-                text = tk.decode(ids[a_:b_], task=TaskNames.ocr_without_boxes if k == 1 else TaskNames.block_without_boxes)
-                if not (k == 1 and (text == NOMATH_TOKEN or _SCRIPT_TAG.match(text))):
-                    texts.append(text); src.append(a_); csrc.append(a_); valid.append(False)
-            a_ = b_
-        return texts, src, csrc, valid
-
-    @staticmethod
-    def _chars_of(line, res_scale, line_bbox) -> List[TextChar]:
-        """TextChars of one line with the reference's per-char geometry (:905-909: rescale by the high-res factor with int()
-        truncation, shift to the line's corner, clamp into the line's bbox) applied to all of the line's polygons at once;
-        objects are built without re-validating fields that were just computed (pydantic model_construct)."""
-        texts, conf, valid, P = line
-        if not texts:
-            return []
-        P = P.copy()
-        P[..., 0] = np.trunc(P[..., 0] * (1.0 / res_scale[0])) + line_bbox[0]
-        P[..., 1] = np.trunc(P[..., 1] * (1.0 / res_scale[1])) + line_bbox[1]
-        np.clip(P[..., 0], line_bbox[0], line_bbox[2], out=P[..., 0])
-        np.clip(P[..., 1], line_bbox[1], line_bbox[3], out=P[..., 1])
-        polys = P.tolist()
-        conf = [0.0 if c != c else c for c in conf.tolist()]               # BaseChar: NaN -> 0, stored as a float
-        return [_text_char(pg, c, t, v) for pg, c, t, v in zip(polys, conf, texts, valid.tolist())]
+    _chars_of = staticmethod(assemble.chars_of)
 
     def _assemble_line(self, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size) -> TextLine:
-        """One line's TextLine from its finished token stream (reference :609-771 + :886-925)."""
-        polygon, res_scale = flat["polygons"][orig], flat["res_scales"][orig]
-        polys = prediction_to_polygon_batch(bbox_rows[None], [flat["slices"][sorted_pos].shape], bbox_size, bbox_size // 2)
-        chars = self.get_bboxes_text(flat, [tokens], [sc], polys, drop_repeated_text)[0]
-        if chars is None or not chars[0]:      # <NOP> (input text was good) or nothing decoded (reference :889-899)
-            return TextLine(text="", polygon=polygon, chars=[], confidence=1, original_text_good=True)
-        # mean of the characters' confidences as the TextChar objects hold them (NaN -> 0, schema.py), reference :899-903
-        confidence = float(np.mean(np.where(np.isnan(chars[1]), 0.0, chars[1])))
-        box = PolygonBox(polygon=polygon)
-        chars = self._chars_of(chars, res_scale, box.bbox)
-        chars = fix_unbalanced_tags(chars, self.processor.ocr_tokenizer.special_tokens)
-        text = clean_math_tags(unwrap_math("".join(c.text for c in chars)))
-        return TextLine(text=text, polygon=polygon, chars=chars, confidence=confidence,
-                        words=words_from_chars(chars, box) if return_words else [])
+        return assemble.assemble_line(self.processor, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size)
 
     def _assemble_batch(self, flat, items, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
-        """TextLines of several finished lines at once; items = [(sorted_pos, orig, tokens, scores, bbox_rows[T, 6])]. The same
-        result as `_assemble_line` per item (tests/test_assemble_cpu.py compares the two), but the numpy work -- box tokens ->
-        polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
-        array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
-        runs (`_line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
-        eos, pad, nop = self.processor.eos_token_id, self.processor.pad_token_id, self.processor.no_output_token
-        out: List[Optional[TextLine]] = [None] * len(items)
-        work, t_max = [], 0
-        for i, (sp, orig, tokens, sc, rows) in enumerate(items):
-            if nop in tokens or (drop_repeated_text and detect_repeat_token(tokens)):
-                out[i] = self._assemble_line(flat, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size)
-                continue
-            n = len(tokens)
-            for j, t in enumerate(tokens):
-                if t == eos or t == pad:
-                    n = j
-                    break
-            n = min(n, len(rows), len(sc))
-            if n == 0:
-                out[i] = TextLine(text="", polygon=flat["polygons"][orig], chars=[], confidence=1, original_text_good=True)
-                continue
-            work.append((i, n))
-            t_max = max(t_max, n)
-        if not work:
-            return out
-        W = len(work)
-        R = np.zeros((W, t_max, 6), np.float32)
-        for w, (i, n) in enumerate(work):
-            R[w, :n] = items[i][4][:n]
-        P = prediction_to_polygon_batch(R, [flat["slices"][items[i][0]].shape for i, _ in work], bbox_size,
-                                        bbox_size // 2).astype(np.float64)                       # [W, t_max, 4, 2]
-        far = (np.abs(P[:, 1:] - P[:, :-1]).reshape(W, t_max - 1, 8).max(axis=2) > 0.1).tolist() if t_max > 1 else [[]] * W
-        keep, all_w, all_src, all_conf, all_valid, counts, geo = [], [], [], [], [], [], []
-        for w, (i, n) in enumerate(work):
-            sp, orig, tokens, sc, rows = items[i]
-            texts, src, csrc, valid = self._line_runs(tokens[:n], far[w])
-            if not texts:                      # nothing decoded (reference :889-899)
-                out[i] = TextLine(text="", polygon=flat["polygons"][orig], chars=[], confidence=1, original_text_good=True)
-                continue
-            polygon = coerce_polygon(flat["polygons"][orig])
-            xs, ys = [p[0] for p in polygon], [p[1] for p in polygon]
-            bbox = [min(xs), min(ys), max(xs), max(ys)]
-            rs = flat["res_scales"][orig]
-            keep.append((i, texts, valid, polygon, bbox))
-            all_w.extend([w] * len(src)); all_src.extend(src); all_valid.extend(valid)
-            all_conf.extend([0.0 if sc[j] != sc[j] else sc[j] for j in csrc])          # TextChar's NaN -> 0 rule
-            counts.append(len(src))
-            geo.append((1.0 / rs[0], 1.0 / rs[1], bbox[0], bbox[1], bbox[2], bbox[3]))
-        if not keep:
-            return out
-        PP = P[all_w, all_src]                                                                    # [C, 4, 2]
-        v_all = np.asarray(all_valid, bool)
-        PP[~v_all] = _BLANK_POLY
-        g = np.repeat(np.asarray(geo, np.float64), counts, axis=0)[:, :, None]                    # [C, 6, 1]
-        PP[..., 0] = np.minimum(np.maximum(np.trunc(PP[..., 0] * g[:, 0]) + g[:, 2], g[:, 2]), g[:, 4])
-        PP[..., 1] = np.minimum(np.maximum(np.trunc(PP[..., 1] * g[:, 1]) + g[:, 3], g[:, 3]), g[:, 5])
-        polys = PP.tolist()
-        conf_arr = np.asarray(all_conf, np.float64)
-        special = self.processor.ocr_tokenizer.special_tokens
-        a = 0
-        for (i, texts, valid, polygon, bbox), c in zip(keep, counts):
-            b = a + c
-            confidence = float(np.mean(conf_arr[a:b]))
-            chars = [_text_char(pg, cf, t, v) for pg, cf, t, v in zip(polys[a:b], all_conf[a:b], texts, valid)]
-            a = b
-            if not all(valid):                                   # tags only come from special / math runs (bbox_valid False)
-                chars = fix_unbalanced_tags(chars, special)
-                text = "".join(ch.text for ch in chars)
-            else:
-                text = "".join(texts)
-            if "<" in text:
-                text = clean_math_tags(unwrap_math(text))
-            words = words_from_chars(chars, PolygonBox(polygon=polygon)) if return_words else []
-            out[i] = _text_line(polygon, confidence, text, chars, words)
-        return out
+        return assemble.assemble_batch(self.processor, flat, items, drop_repeated_text, return_words, bbox_size)
+
+    @staticmethod
+    def _page_results(images, slice_map, text_lines, sort_lines) -> List[OCRResult]:
+        """The lines (by original position) regrouped per page."""
+        results, start = [], 0
+        for image, count in zip(images, slice_map):
+            lines = text_lines[start:start + count]
+            start += count
+            if sort_lines:
+                lines = sort_text_lines(lines)
+            results.append(OCRResult(text_lines=lines, image_bbox=[0, 0, image.size[0], image.size[1]]))
+        return results
 
     def __call__(self, images: List[Image.Image], task_names: List[str] | None = None, det_predictor=None,
                  detection_batch_size: int | None = None, recognition_batch_size: int | None = None,
@@ -933,64 +442,26 @@ class RecognitionPredictor(BasePredictor):
             return []
         stamps["slice_ms"] = (time.perf_counter() - t_call) * 1e3
 
-        # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854)
+        # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
+        # position of sorted line k, so a finished line can be assembled against its own polygon / scale
         order = sorted(range(len(flat["slices"])), key=lambda i: -flat["slices"][i].shape[1])
         for key in ("slices", "input_text", "task_names"):
             flat[key] = [flat[key][i] for i in order]
 
-        # original position of every sorted line, so a finished line can be assembled against its own polygon / scale
-        orig_of = order
-        bbox_size = self.model.cfg.bbox_size
-
-        def assemble(batch):
-            # batch = [(sorted_pos, tokens, scores, bbox_rows)]: the lines that stopped at one synchronisation point
-            return self._assemble_batch(flat, [(k, orig_of[k], t, sc, bb) for k, t, sc, bb in batch], drop_repeated_text,
-                                        return_words, bbox_size)
-
-        text_lines = [None] * len(order)                      # by ORIGINAL position
-        if self.shard_lines:
-            predicted_tokens, batch_bboxes, scores = self.sharded_prediction_loop(flat, recognition_batch_size, math_mode)
-            bb = batch_bboxes.numpy()
-            for a in range(0, len(order), 256):
-                ks = range(a, min(a + 256, len(order)))
-                for k, line in zip(ks, assemble([(k, predicted_tokens[k], scores[k], bb[k]) for k in ks])):
-                    text_lines[orig_of[k]] = line
-        else:
-            # Output assembly is host work of the same order as the device loop itself; it runs on one worker thread WHILE the
-            # device decodes the next lines: the lines that stopped at a synchronisation point are handed over together as soon
-            # as it is over (batched numpy work, `_assemble_batch`). The scheduler thread spends most of its time blocked in
-            # hipEventSynchronize (GIL released), which is when the worker runs.
-            futures, pending = [], []
-            with ThreadPoolExecutor(1) as pool:
-                def on_done(k, tokens, sc, bbox_rows):
-                    pending.append((k, list(tokens), list(sc), bbox_rows.copy()))
-
-                def on_flush():
-                    if pending:
-                        batch = pending[:]
-                        pending.clear()
-                        futures.append(([b[0] for b in batch], pool.submit(assemble, batch)))
+        with AssemblyHandover(self, flat, order, drop_repeated_text, return_words) as hand:
+            if self.shard_lines:
+                predicted_tokens, batch_bboxes, scores = self.sharded_prediction_loop(flat, recognition_batch_size, math_mode)
+                bb = batch_bboxes.numpy()
+                chunks = [range(a, min(a + 256, len(order))) for a in range(0, len(order), 256)]
+                text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) for k in ks])) for ks in chunks)
+            else:
                 t0 = time.perf_counter()
                 prep = self.prepare_lines(flat, math_mode)
                 t1 = time.perf_counter()
-                self.generate(prep, recognition_batch_size, on_done=on_done, on_flush=on_flush)
-                on_flush()
-                t2 = time.perf_counter()
-                for ks, f in futures:
-                    for k, line in zip(ks, f.result()):
-                        text_lines[orig_of[k]] = line
-                stamps.update(prepare_ms=(t1 - t0) * 1e3, device_loop_ms=(t2 - t1) * 1e3,
-                              assemble_tail_ms=(time.perf_counter() - t2) * 1e3)
-            assert all(t is not None for t in text_lines)
-
-        results, start = [], 0
-        for idx, image in enumerate(images):
-            end = start + flat["slice_map"][idx]
-            lines = text_lines[start:end]
-            start = end
-            if sort_lines:
-                lines = sort_text_lines(lines)
-            results.append(OCRResult(text_lines=lines, image_bbox=[0, 0, image.size[0], image.size[1]]))
+                self.generate(prep, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush)
+                stamps["prepare_ms"] = (t1 - t0) * 1e3
+                text_lines = hand.finish(stamps, t1)
+        results = self._page_results(images, flat["slice_map"], text_lines, sort_lines)
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results
 
@@ -1012,16 +483,13 @@ class RecognitionPredictor(BasePredictor):
     def _call_page_sharded(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                            sort_lines, math_mode, return_words, drop_repeated_text) -> list:
         from .. import dist as sdist
-        import zlib
         group = self.process_group
         rank, world = sdist.world_info(group)
         n = len(images)
         dev = sdist.collective_device(self.model.device, group)
-        sizes = np.asarray([im.size for im in images], np.int64).reshape(-1, 2)
         # (a 64 x 16 pixel corner of up to 16 pages: `tobytes()` of whole pages copied several MB per page on every rank, inside the call)
-        probe = b"".join(images[i].crop((0, 0, min(images[i].size[0], 64), min(images[i].size[1], 16))).tobytes()
-                         for i in range(0, n, max(1, n // 16))) if n else b""
-        sdist.assert_same_inputs([n, zlib.crc32(sizes.tobytes()), zlib.crc32(probe)], group, dev)
+        probe = [images[i].crop((0, 0, min(images[i].size[0], 64), min(images[i].size[1], 16))).tobytes() for i in range(0, n, max(1, n // 16))]
+        sdist.assert_same_inputs(inputs_fingerprint([im.size for im in images], probe), group, dev)
         mine = sdist.shard_indices(n, world, rank)
         saved = (self.shard_pages, self.shard_lines, getattr(det_predictor, "shard_pages", False))
         self.shard_pages = self.shard_lines = False
@@ -1080,45 +548,34 @@ class RecognitionPredictor(BasePredictor):
                 and type(det_predictor)._detect_device is DetectionPredictor._detect_device
                 and type(det_predictor)._iter_detect_device is DetectionPredictor._iter_detect_device
                 and det_predictor.device_postprocess and not det_predictor.shard_pages)
-
     def _call_streamed(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                        sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call) -> List[OCRResult]:
         import queue
         import sys
         import threading
-        # by line id (admission order): slices / task_names / input_text; by ORIGINAL position (page order): the rest
-        flat = {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
+        flat = new_flat()
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
-        overall_max_tokens = max([settings.RECOGNITION_MAX_TOKENS or self.tasks[t]["max_tokens"] for t in task_names] or [1])
-        device = self.model.device
+        overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
         det_wall = [0.0]
         stop = threading.Event()
 
         def produce():
             try:
                 if torch.cuda.is_available():
-                    torch.cuda.set_device(device)             # the current device is per thread
+                    torch.cuda.set_device(self.model.device)             # the current device is per thread
                 page, t_p = 0, time.perf_counter()
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
                     pages, refs, polys_all, scales_all, tasks_all = [], [], [], [], []
                     for det_pred in dets:
-                        image, highres, task = images[page], highres_images[page], task_names[page]
-                        polygons = [b.polygon for b in det_pred.bboxes]
-                        if highres:
-                            ws, hs = highres.size[0] / image.size[0], highres.size[1] / image.size[1]
-                            src = highres
-                            polys_px = [[[int(pt[0] * ws), int(pt[1] * hs)] for pt in poly] for poly in polygons]
-                            scale = (ws, hs)
-                        else:
-                            src, polys_px, scale = image, polygons, (1, 1)
+                        polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
                         refs.extend(poly_ref(len(pages) - 1, src.size[0], src.size[1], poly) for poly in polys_px)
                         polys_all.extend(polygons)
                         scales_all.extend([scale] * len(polygons))
-                        tasks_all.extend([task] * len(polygons))
+                        tasks_all.extend([task_names[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -1137,8 +594,7 @@ class RecognitionPredictor(BasePredictor):
                     flat["input_text"].extend([None] * len(order))
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
-                           "max_tokens": {p.id: settings.RECOGNITION_MAX_TOKENS or self.tasks[p.task_name]["max_tokens"]
-                                          for p in prompts}})
+                           "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts}})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -1153,45 +609,18 @@ class RecognitionPredictor(BasePredictor):
                 raise item
             return item
 
-        bbox_size = self.model.cfg.bbox_size
-
-        def assemble(batch):
-            return self._assemble_batch(flat, [(k, orig_of[k], t, sc, bb) for k, t, sc, bb in batch], drop_repeated_text,
-                                        return_words, bbox_size)
-
-        futures, pending = [], []
         # the producer's Python work (box lists, line descriptors) must not keep the scheduler from its next launch for a
         # whole default switch interval (5 ms = a decode call of 4 steps)
         old_switch = sys.getswitchinterval()
         sys.setswitchinterval(min(old_switch, 5e-4))
-        if os.environ.get("SURYA_AMD_PROFILE_PRODUCER"):     # debugging aid: cProfile of the detector thread's Python work, to stderr
-            import cProfile, pstats
-            _inner = produce
-
-            def produce():                                   # noqa: F811
-                pr = cProfile.Profile()
-                pr.enable()
-                try:
-                    _inner()
-                finally:
-                    pr.disable()
-                    pstats.Stats(pr, stream=sys.stderr).sort_stats("tottime").print_stats(22)
         producer = threading.Thread(target=produce, name="surya-amd-detect", daemon=True)
         try:
-            with ThreadPoolExecutor(1) as pool:
-                def on_done(k, tokens, sc, bbox_rows):
-                    pending.append((k, list(tokens), list(sc), bbox_rows.copy()))
-
-                def on_flush():
-                    if pending:
-                        batch = pending[:]
-                        pending.clear()
-                        futures.append(([b[0] for b in batch], pool.submit(assemble, batch)))
+            with AssemblyHandover(self, flat, orig_of, drop_repeated_text, return_words) as hand:
                 t0 = time.perf_counter()
                 producer.start()
                 try:
                     self.generate({"prompts": [], "max_tokens": {}, "overall_max_tokens": overall_max_tokens}, recognition_batch_size,
-                                  on_done=on_done, on_flush=on_flush, feed=feed)
+                                  on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...
                     producer.join(timeout=30.0)        # ... and is waited for: it launches detector and pre-processing work on this predictor's
@@ -1199,27 +628,13 @@ class RecognitionPredictor(BasePredictor):
                         self._poisoned = "a streamed call failed and its detector thread did not stop within 30 s: create a new predictor"
                     raise
                 producer.join()                        # it has put FEED_END: nothing left to run
-                on_flush()
-                t2 = time.perf_counter()
-                n = len(orig_of)
-                text_lines = [None] * n
-                for ks, f in futures:
-                    for k, line in zip(ks, f.result()):
-                        text_lines[orig_of[k]] = line
-                stamps.update(streamed=1.0, detect_thread_ms=det_wall[0], device_loop_ms=(t2 - t0) * 1e3,
-                              assemble_tail_ms=(time.perf_counter() - t2) * 1e3)
+                stamps.update(streamed=1.0, detect_thread_ms=det_wall[0])
+                text_lines = hand.finish(stamps, t0)
         finally:
             sys.setswitchinterval(old_switch)
-        if n == 0:
+        if not text_lines:
             return []
-        assert all(t is not None for t in text_lines) and len(flat["slice_map"]) == len(images)
-        results, start = [], 0
-        for idx, image in enumerate(images):
-            end = start + flat["slice_map"][idx]
-            lines = text_lines[start:end]
-            start = end
-            if sort_lines:
-                lines = sort_text_lines(lines)
-            results.append(OCRResult(text_lines=lines, image_bbox=[0, 0, image.size[0], image.size[1]]))
+        assert len(flat["slice_map"]) == len(images)
+        results = self._page_results(images, flat["slice_map"], text_lines, sort_lines)
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results

@@ -1,4 +1,5 @@
-"""CPU: the predictor's device loop (continuous batching + pipelined decode calls + look-ahead encoding) against a fake
+"""CPU: the recognition device loop (recognition/loop.py: DeviceLoop, driven through RecognitionPredictor.generate or directly;
+continuous batching + pipelined decode calls + look-ahead encoding) against a fake
 model that implements the HipRecModel surface and ENFORCES the C-ABI contracts of include/surya_amd.h:
 
   * outputs of decode_async(n, ring) are only readable through wait_outputs(n, ring), each call exactly once, and a ring
@@ -121,7 +122,6 @@ def expected(line, max_tokens):
 def make(n_lines, max_tokens, slots):
     from surya_amd.recognition.predictor import RecognitionPredictor, RecognitionPrompt
     pred = object.__new__(RecognitionPredictor)
-    pred.prompt_queue, pred.batch_prompt_mapping = deque(), None
     pred.model = FakeModel(slots)
     pred.processor = SimpleNamespace(eos_token_id=EOS, pad_token_id=PAD, no_output_token=NOP)
     grids = [(2, 2 + 2 * (i % 3)) for i in range(n_lines)]
@@ -325,13 +325,77 @@ def test_a_loop_that_ended_early_does_not_poison_the_next_one():
         assert m.ahead, "the scenario needs outstanding look-ahead images"
         m.inflight.clear(); m.ring_busy = [False, False]; m.active = []; m.prefill_out = None      # what surya_rec_* keep per call, not per loop
         pred2, prep2 = make(9, 10, 4)
-        pred.prompt_queue.extend(prep2["prompts"])                           # stale queue content must not survive either
+        # the loop's own state died with its DeviceLoop; the model handle's look-ahead is all that survives: add stale entries to it
+        m.ahead.extend(p.id for p in prep2["prompts"])
         toks, _, _ = pred.generate(prep2, 4)
         assert m.stats["discards"] >= 2 and not m.ahead
         for i in range(9):
             assert toks[i] == expected(i, prep2["max_tokens"][i])
     finally:
         settings.RECOGNITION_STEPS_PER_SYNC, settings.RECOGNITION_ENCODE_AHEAD = old
+
+
+# ---------------------------------------------------------------------------------------------- the loop's methods, one at a time
+def _loop(slots, overall, **kw):
+    from surya_amd.recognition.loop import DeviceLoop
+    return DeviceLoop(FakeModel(slots), EOS, PAD, NOP, slots, overall, 0.0, **kw)
+
+
+def test_admit_two_chunks_and_tile_lookup_across_their_border():
+    """Two admitted dicts keep their own tile tensors: ranges on either side of the border resolve into the right tensor with the
+    chunk's LOCAL offsets; a range that spans the border is refused (one tile tensor per encoder pass / prefill)."""
+    _, prep = make(7, 9, 4)
+    a, b = _chunks(prep, (3,))
+    loop = _loop(4, 9)
+    loop.admit(a)
+    loop.admit(b)
+    assert list(loop.queue) == list(range(7)) and loop.line_chunk.tolist() == [0, 0, 0, 1, 1, 1, 1]
+    assert loop.tok_mat.shape == (7, 10) and loop.batch_bboxes.shape == (7, 9, 6) and loop.num_empty == 4 and loop.num_active == 0
+    assert loop.max_tok.tolist() == [prep["max_tokens"][i] for i in range(7)]
+    offs = prep["tile_offs"]
+    for first, last in [(0, 0), (1, 2), (0, 2), (3, 3), (3, 6), (5, 6)]:
+        got = loop.tiles_of(first, last)
+        assert got.base is (a if last < 3 else b)["tiles"] or got is (a if last < 3 else b)["tiles"]
+        assert np.array_equal(got, prep["tiles"][offs[first]:offs[last + 1]])
+        assert got.shape[0] == sum(h * w for h, w in prep["grids"][first:last + 1])
+    for first, last in [(2, 3), (0, 6)]:
+        with pytest.raises(AssertionError):
+            loop.tiles_of(first, last)
+    with pytest.raises(AssertionError, match="continue the admitted ids"):
+        loop.admit(b)
+
+
+def test_absorb_ignores_the_steps_after_a_lines_eos():
+    """absorb on a hand-made three-step output: line 0 (slot 2) emits EOS in step 1, so its step-2 token must be ignored, its slot
+    freed and on_done called exactly once; line 1 (slot 0) takes all three steps and stays active."""
+    done, flushes = [], []
+
+    class Model(FakeModel):
+        def wait_outputs(self, n, ring):
+            assert (n, ring) == (3, 1)
+            tok = np.full((3, 4), -7, np.int32); sc = np.zeros((3, 4), np.float32); bb = np.zeros((3, 4, 6), np.int32)
+            tok[:, 2], sc[:, 2] = [500, EOS, 777], [0.1, 0.2, 0.3]
+            tok[:, 0], sc[:, 0] = [600, 601, 602], [0.4, 0.5, 0.6]
+            bb[:, 2], bb[:, 0] = 20, 10
+            return tok, sc, bb
+
+        def set_active(self, slots):
+            self.active = list(slots)
+
+    _, prep = make(2, 9, 4)
+    loop = _loop(4, 9, on_done=lambda k, t, s, b: done.append((k, list(t), list(s), b.copy())), on_flush=lambda: flushes.append(len(done)))
+    loop.model = Model(4)
+    loop.admit(prep)
+    loop.queue.clear()
+    loop.slot_line[2], loop.slot_line[0] = 0, 1                            # as prefill_batch leaves them: first token already written
+    loop.tok_mat[:, 0], loop.line_len[:] = [400, 401], 1
+    loop.absorb((3, 1))
+    assert loop.slot_line.tolist() == [1, -1, -1, -1] and loop.num_active == 1 and loop.num_empty == 3
+    assert loop.model.active == [0] and flushes == [1]
+    assert len(done) == 1 and done[0][0] == 0 and done[0][1] == [400, 500, EOS] == loop.predicted_tokens[0]
+    assert done[0][2] == pytest.approx([0.0, 0.1, 0.2]) and (done[0][3][1:, 0] == 20).all() and done[0][3].shape == (3, 6)
+    assert loop.line_len.tolist() == [3, 4] and 777 not in loop.tok_mat
+    assert loop.tok_mat[1, :4].tolist() == [401, 600, 601, 602] and loop.predicted_tokens[1] == []      # still running: not final yet
 
 
 # ---------------------------------------------------------------------------------------------- the streamed call, without a GPU
@@ -353,7 +417,6 @@ def _streamed_predictor(slots, fail_after=None):
     from surya_amd.recognition.predictor import RecognitionPredictor, TaskNames
     from surya_amd.recognition.schema import TextLine
     pred = object.__new__(RecognitionPredictor)
-    pred.prompt_queue, pred.batch_prompt_mapping = deque(), None
     pred.model = StreamFakeModel(slots)
     pred.processor = SimpleNamespace(eos_token_id=EOS, pad_token_id=PAD, no_output_token=NOP)
     pred.last_timing = {}

@@ -1,4 +1,4 @@
-"""Host cost of RecognitionPredictor.generate's device loop (stop rules, token bookkeeping, scheduling) per emitted token, measured on
+"""Host cost of the recognition device loop (recognition/loop.py, run through RecognitionPredictor.generate: stop rules, token bookkeeping, scheduling) per emitted token, measured on
 the CPU against a fake model whose calls return immediately (vectorised scripted tokens): what the Python side adds per decode call
 when the device is infinitely fast. If this exceeds the device's time per call (4 steps x ~1.2 ms), the GPU idles.
 
@@ -63,7 +63,6 @@ def main():
     rng = np.random.default_rng(0)
     stop_at = rng.integers(20, 70, size=a.lines) if a.ragged else np.full(a.lines, 10 ** 9)
     pred = object.__new__(RecognitionPredictor)
-    pred.prompt_queue, pred.batch_prompt_mapping = deque(), None
     pred.model = FastFake(a.slots, stop_at)
     pred.processor = SimpleNamespace(eos_token_id=EOS, pad_token_id=PAD, no_output_token=NOP)
     grids = [(2, 4)] * a.lines
