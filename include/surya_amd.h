@@ -264,6 +264,22 @@ int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_
  * The network is described as a list of ops over NHWC activation buffers (built by surya_amd/detection/plan.py from
  * the reference's state-dict; BatchNorm folded, 3x3 weights as [Cout][ky][kx][Cin] with K padded to x64).
  * ---------------------------------------------------------------------------------------------------------- */
+/* What surya_det_create accepts. An op list is either computed correctly or refused on the host before anything is allocated or
+ * launched (SA_ERR_ARG: an index; SA_ERR_SHAPE: sizes; SA_ERR_UNSUPPORTED: a parameter no kernel takes). V = elements per 16 bytes of
+ * the compute dtype (4 in fp32, 8 in bf16 / fp16), KE = the K-tile (32 / 64 elements). Every op: sizes in [1, 65535], its buffers hold
+ * hin * win * cin (in0, in1) and hout * wout * cout (out, res) elements per image, and every buffer it reads was written by an op before it.
+ *   INPUT          cin <= cout, cout % V == 0 (one pixel = whole 16-byte stores), hout x wout == hin x win
+ *   CONV           cin % V == 0 (a 16-byte gather chunk stays inside one filter tap), cout % 4 == 0 (4-wide epilogue), p1 % KE == 0,
+ *                  p1 >= k * k * cin, hout x wout == floor((hin + 2 p0 - k) / stride) + 1, max_batch * hout * wout < 2^31;
+ *                  `act` together with `res` is refused: the 1x1 (GEMM) path has a residual epilogue and an activation epilogue, not both
+ *   DWCONV         (k, stride) in {3, 5} x {1, 2}, cin == cout, cin % V == 0, hout x wout as for CONV
+ *   GROUPED1X1     p0 <= 32 (a group's input row lives in 32 registers), p0 % V == 0, cin % p0 == 0, cin == cout, cin / p0 <= 65535
+ *   LITEMLA        p0 in {16, 32}, cout % p0 == 0, cout / p0 heads: even (half from in0, half from in1), cin == 3 * cout / 2
+ *   UPCAT          cin % V == 0, p0 % 4 == 0 and cout % 4 == 0 (4-wide stores), p0 + cin <= cout
+ *   CLASSIFY       cin % V == 0, 1 <= cout <= 4, bias required, hin * win * cout <= num_labels * (height / 4) * (width / 4) (the planes)
+ *   UPSUM_SRC      at most 3 in front of an UPSUM_CLASSIFY, each [hin, win, cin] with the UPSUM_CLASSIFY's cin
+ *   UPSUM_CLASSIFY as CLASSIFY
+ *   UPSAMPLE_OUT   (hin, win, cout) those of the CLASSIFY / UPSUM_CLASSIFY before it, cout * hout * wout <= num_labels * height * width */
 enum { SA_DET_INPUT = 0,       /* fp32 NCHW pixels -> NHWC, channels padded to `cout`                      */
        SA_DET_CONV,            /* dense KxK conv as implicit GEMM: bias, act, optional residual `res`        */
        SA_DET_DWCONV,          /* depthwise KxK: weights [K*K][C], bias, act                                 */
@@ -310,6 +326,10 @@ int surya_det_forward(surya_det* h, const float* pixel_values, int batch, float*
 int surya_det_op_count(surya_det* h);
 int surya_det_forward_timed(surya_det* h, const float* pixel_values, int batch, float* heatmaps, float* lowres, void* stream, float* op_ms,
                             int n_op_ms);
+/* Test and measurement support (tests/test_gpu_det_microplan.py): a device-to-device copy of the first `batch` images of activation
+ * buffer `buf` -- batch * buf_elems[buf] elements of the engine's compute dtype, NHWC as the op that wrote it left them -- into dst
+ * (device, dst_bytes >= that). SA_ERR_ARG for a bad index, a batch outside [1, max_batch] or a dst_bytes too small. Enqueue only. */
+int surya_det_read_buffer(surya_det* h, int buf, int batch, void* dst, size_t dst_bytes, void* stream);
 /* Same forward from the resized pages themselves: device uint8 [batch, H, W, pixel_stride], pixel_stride 3 (RGB) or 4 (RGBX =
  * PIL's in-memory layout, uploaded without repacking; the fourth byte is ignored). The rescale
  * (x * 1/255 in fp32) and normalisation ((x - mean) / std) of SegformerImageProcessor._preprocess

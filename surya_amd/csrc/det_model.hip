@@ -22,6 +22,7 @@ struct DetBase {
     virtual int forward(const float* pixels, const unsigned char* pixels_u8, const float* mean_std, int B, float* heat, float* lowres,
                         hipStream_t s, int pix = 3, float* op_ms = nullptr) = 0;
     virtual int n_ops() const = 0;
+    virtual int read_buffer(int buf, int B, void* dst, size_t dst_bytes, hipStream_t s) const = 0;
 };
 
 template <typename T>
@@ -78,6 +79,15 @@ struct DetModel : DetBase {
 
     int n_ops() const override { return (int)ops.size(); }
 
+    // test and measurement support (surya_det_read_buffer): the first B images of an activation buffer, as the op that wrote it left them
+    int read_buffer(int buf, int B, void* dst, size_t dst_bytes, hipStream_t s) const override {
+        if (buf < 0 || buf >= (int)bufs.size() || B <= 0 || B > max_batch || !dst) return SA_ERR_ARG;
+        const size_t bytes = (size_t)B * buf_elems[buf] * sizeof(T);
+        if (dst_bytes < bytes) return SA_ERR_ARG;
+        SA_HIP(hipMemcpyAsync(dst, bufs[buf], bytes, hipMemcpyDeviceToDevice, s));
+        return SA_OK;
+    }
+
     // ---- fused forms (round 6), found once by a peephole pass over the op list. The list itself is unchanged (every op still owns its
     // output buffer), so sa::Tuning::det_fuse can switch each form on and off at run time: the op-by-op path stays the checker of
     // tests/test_gpu_det_fused.py and the A/B arm of tools/det_op_times.py.
@@ -113,6 +123,11 @@ struct DetModel : DetBase {
         return false;
     }
 
+    // the consumer reads the producer's output as the producer wrote it (a fused form takes the producer's sizes for both: an op list that
+    // re-interprets the buffer in between, or pads the depthwise / 3x3 differently from the kernels' fixed halo, keeps the op-by-op path)
+    static bool same_tensor(const surya_det_op& prod, const surya_det_op& cons) {
+        return cons.cin == prod.cout && cons.hin == prod.hout && cons.win == prod.wout;
+    }
     void find_fusions() {
         const int n = (int)ops.size();
         fuse_kind.assign(n, 0); fuse_with.assign(n, -1); mb_start.assign(n, 0);
@@ -123,12 +138,12 @@ struct DetModel : DetBase {
             if (!BF || i + 1 >= n) continue;
             const surya_det_op& b = ops[i + 1];
             if (a.type == SA_DET_DWCONV && a.k == 5 && a.stride == 1 && a.b_idx < 0 && a.act == SA_ACT_NONE && b.type == SA_DET_GROUPED1X1 &&
-                b.in0 == a.out && b.p0 == 32 && a.cin % 32 == 0) { fuse_kind[i] = FUSE_MLA_AGG; fuse_with[i] = i + 1; }
+                b.in0 == a.out && b.p0 == 32 && a.cin % 32 == 0 && a.p0 == 2 && same_tensor(a, b)) { fuse_kind[i] = FUSE_MLA_AGG; fuse_with[i] = i + 1; }
             if (a.type == SA_DET_DWCONV && a.k == 3 && (a.stride == 1 || a.stride == 2) && b.type == SA_DET_CONV && b.k == 1 && b.stride == 1 &&
                 b.in0 == a.out && b.act == SA_ACT_NONE && b.p1 == b.cin && a.cin % 128 == 0 && (b.cout == 256 || b.cout == 512) && b.b_idx >= 0 &&
-                a.b_idx >= 0 && a.act == SA_ACT_HSWISH) { fuse_kind[i] = FUSE_DWPROJ; fuse_with[i] = i + 1; }
+                a.b_idx >= 0 && a.act == SA_ACT_HSWISH && a.p0 == 1 && same_tensor(a, b)) { fuse_kind[i] = FUSE_DWPROJ; fuse_with[i] = i + 1; }
             if (a.type == SA_DET_CONV && a.k == 3 && a.act == SA_ACT_HSWISH && a.res < 0 && b.type == SA_DET_CONV && b.k == 1 && b.stride == 1 &&
-                b.in0 == a.out && b.act == SA_ACT_NONE && b.p1 == b.cin && fmb_supported(a, b)) { fuse_kind[i] = FUSE_FMB; fuse_with[i] = i + 1; }
+                b.in0 == a.out && b.act == SA_ACT_NONE && b.p1 == b.cin && a.p0 == 1 && same_tensor(a, b) && fmb_supported(a, b)) { fuse_kind[i] = FUSE_FMB; fuse_with[i] = i + 1; }
             if (a.type == SA_DET_CONV && a.k == 3 && a.stride == 1 && a.p0 == 1 && a.cin == 32 && a.cout == 32 && a.act == SA_ACT_HSWISH && a.res < 0 &&
                 a.b_idx >= 0 && b.type == SA_DET_CONV && b.k == 3 && b.stride == 1 && b.p0 == 1 && b.cin == 32 && b.cout == 32 && b.act == SA_ACT_NONE &&
                 b.b_idx >= 0 && b.in0 == a.out && b.res == a.in0 && b.p1 == a.p1 && (long)a.hin * a.win * 64 < (1L << 31) &&
@@ -154,7 +169,7 @@ struct DetModel : DetBase {
             const surya_det_op& dw = ops[i + 1];
             const surya_det_op& pj = ops[i + 2];
             if (fuse_kind[i + 1] != FUSE_DWPROJ || a.type != SA_DET_CONV || a.k != 1 || a.stride != 1 || a.act != SA_ACT_HSWISH || a.res >= 0 ||
-                a.p1 != a.cin || a.b_idx < 0 || dw.in0 != a.out || !mbconv_shape_ok(a.cin, a.cout, pj.cout, dw.stride)) continue;
+                a.p1 != a.cin || a.b_idx < 0 || dw.in0 != a.out || !same_tensor(a, dw) || !mbconv_shape_ok(a.cin, a.cout, pj.cout, dw.stride)) continue;
             bool only_reader = true;
             for (int k = 0; k < n; ++k) if (k != i + 1 && (ops[k].in0 == a.out || ops[k].in1 == a.out || ops[k].res == a.out)) only_reader = false;
             if (only_reader) mb_start[i] = 1;
@@ -174,7 +189,7 @@ struct DetModel : DetBase {
             bool only_reader = true;
             for (int i = 0; i < n; ++i) if (i != j && (ops[i].in0 == c.out || ops[i].in1 == c.out || ops[i].res == c.out)) only_reader = false;
             if (c.k == 1 && c.stride == 1 && c.act == SA_ACT_NONE && c.res < 0 && c.p1 == c.cin && c.cin == 64 && c.cout % 128 == 0 && c.cout <= 1024 &&
-                ops[j].cout <= 2 && ops[j].hin % 8 == 0 && ops[j].win % 8 == 0 && only_reader) { fuse_kind[j] = FUSE_HEAD_Z0; fuse_with[j] = prod; }
+                ops[j].cout <= 2 && ops[j].hin % 8 == 0 && ops[j].win % 8 == 0 && only_reader && same_tensor(c, ops[j])) { fuse_kind[j] = FUSE_HEAD_Z0; fuse_with[j] = prod; }
         }
     }
     int prepare_fused_weights() {
@@ -476,6 +491,89 @@ int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void*
     return SA_ERR_UNSUPPORTED;
 }
 
+// surya_det_create's contract (include/surya_amd.h, above the op enum): an op list is computed correctly or refused here, on the host,
+// before anything is allocated or launched. Every limit below is one a kernel's indexing has: 16-byte vector loads (V elements), 4-wide
+// stores, the 32 weight registers of grouped1x1_kernel, the two template widths of the LiteMLA kernels, the planes' and the caller's sizes.
+static int det_validate(const surya_det_config& c, const surya_det_op* ops, int n_weights, const size_t* be, int n_bufs) {
+    const bool f32 = c.dtype == SA_DTYPE_F32;
+    const long V = f32 ? 4 : 8, KE = f32 ? 32 : 64;
+    const long planes_elems = (long)c.num_labels * (c.height / 4) * (c.width / 4), heat_elems = (long)c.num_labels * c.height * c.width;
+    std::vector<char> written(n_bufs, 0);
+    int upsum_n = 0, upsum_c = 0;
+    long cls_h = -1, cls_w = -1, cls_l = -1;              // what the last CLASSIFY / UPSUM_CLASSIFY left in the planes
+    auto idx_ok = [](int i, int n, bool need) { return i >= (need ? 0 : -1) && i < n; };
+    auto conv_out = [](long in, long pad, long k, long stride) { return in + 2 * pad - k < 0 ? -1 : (in + 2 * pad - k) / stride + 1; };
+    for (int i = 0; i < c.n_ops; ++i) {
+        const surya_det_op& o = ops[i];
+        const int t = o.type;
+        if (t < SA_DET_INPUT || t > SA_DET_UPSUM_CLASSIFY) return SA_ERR_UNSUPPORTED;
+        const bool has_in = t != SA_DET_INPUT && t != SA_DET_UPSAMPLE_OUT;
+        const bool has_out = t != SA_DET_CLASSIFY && t != SA_DET_UPSAMPLE_OUT && t != SA_DET_UPSUM_SRC && t != SA_DET_UPSUM_CLASSIFY;
+        const bool has_w = t == SA_DET_CONV || t == SA_DET_DWCONV || t == SA_DET_GROUPED1X1 || t == SA_DET_CLASSIFY || t == SA_DET_UPSUM_CLASSIFY;
+        if (!idx_ok(o.in0, n_bufs, has_in) || !idx_ok(o.in1, n_bufs, t == SA_DET_LITEMLA) || !idx_ok(o.out, n_bufs, has_out) ||
+            !idx_ok(o.res, n_bufs, false) || !idx_ok(o.w_idx, n_weights, has_w) ||
+            !idx_ok(o.b_idx, n_weights, t == SA_DET_CLASSIFY || t == SA_DET_UPSUM_CLASSIFY)) return SA_ERR_ARG;
+        if (o.hin <= 0 || o.win <= 0 || o.hout <= 0 || o.wout <= 0 || o.cout <= 0 || (t != SA_DET_UPSAMPLE_OUT && o.cin <= 0)) return SA_ERR_SHAPE;
+        if (o.hin > 65535 || o.win > 65535 || o.hout > 65535 || o.wout > 65535 || o.cin > 65535 || o.cout > 65535) return SA_ERR_SHAPE;
+        if (o.act < SA_ACT_NONE || o.act > SA_ACT_RELU) return SA_ERR_UNSUPPORTED;
+        const long in_e = (long)o.hin * o.win * o.cin, out_e = (long)o.hout * o.wout * o.cout;
+        if (has_in && ((size_t)in_e > be[o.in0] || !written[o.in0])) return SA_ERR_SHAPE;
+        if (t == SA_DET_LITEMLA && ((size_t)in_e > be[o.in1] || !written[o.in1])) return SA_ERR_SHAPE;
+        if (has_out && (size_t)out_e > be[o.out]) return SA_ERR_SHAPE;
+        if (o.res >= 0 && (t != SA_DET_CONV || (size_t)out_e > be[o.res] || !written[o.res])) return SA_ERR_SHAPE;
+        const bool same_hw = o.hout == o.hin && o.wout == o.win;
+        switch (t) {
+            case SA_DET_INPUT:
+                if (o.cin > o.cout || o.cout % V || !same_hw) return SA_ERR_SHAPE;
+                break;
+            case SA_DET_CONV:
+                if (o.k < 1 || o.stride < 1 || o.p0 < 0) return SA_ERR_UNSUPPORTED;
+                if (o.act != SA_ACT_NONE && o.res >= 0) return SA_ERR_UNSUPPORTED;
+                if (o.cin % V || o.cout % 4 || o.p1 % KE || o.p1 < (long)o.k * o.k * o.cin) return SA_ERR_SHAPE;
+                if (o.hout != conv_out(o.hin, o.p0, o.k, o.stride) || o.wout != conv_out(o.win, o.p0, o.k, o.stride)) return SA_ERR_SHAPE;
+                if ((long)c.max_batch * o.hout * o.wout >= (1L << 31)) return SA_ERR_SHAPE;
+                break;
+            case SA_DET_DWCONV:
+                if ((o.k != 3 && o.k != 5) || (o.stride != 1 && o.stride != 2) || o.p0 < 0) return SA_ERR_UNSUPPORTED;
+                if (o.cin != o.cout || o.cin % V) return SA_ERR_SHAPE;
+                if (o.hout != conv_out(o.hin, o.p0, o.k, o.stride) || o.wout != conv_out(o.win, o.p0, o.k, o.stride)) return SA_ERR_SHAPE;
+                break;
+            case SA_DET_GROUPED1X1:
+                if (o.p0 <= 0 || o.p0 > 32) return SA_ERR_UNSUPPORTED;
+                if (o.p0 % V || o.cin % o.p0 || o.cin != o.cout || !same_hw) return SA_ERR_SHAPE;
+                break;
+            case SA_DET_LITEMLA: {
+                if (o.p0 != 16 && o.p0 != 32) return SA_ERR_UNSUPPORTED;
+                const int heads = o.cout / o.p0;
+                if (o.cout % o.p0 || heads < 2 || heads % 2 || o.cin != heads / 2 * 3 * o.p0 || !same_hw) return SA_ERR_SHAPE;
+                break;
+            }
+            case SA_DET_UPCAT:
+                if (o.cin % V || o.p0 < 0 || o.p0 % 4 || o.cout % 4 || (long)o.p0 + o.cin > o.cout) return SA_ERR_SHAPE;
+                break;
+            case SA_DET_UPSUM_SRC:
+                if (upsum_n >= 3) return SA_ERR_UNSUPPORTED;
+                if (o.cin % V || (upsum_n && o.cin != upsum_c)) return SA_ERR_SHAPE;
+                upsum_c = o.cin; ++upsum_n;
+                break;
+            case SA_DET_CLASSIFY:
+            case SA_DET_UPSUM_CLASSIFY:
+                if (o.cin % V || o.cout > 4 || (long)o.hin * o.win * o.cout > planes_elems) return SA_ERR_SHAPE;
+                if (t == SA_DET_UPSUM_CLASSIFY && upsum_n && upsum_c != o.cin) return SA_ERR_SHAPE;
+                if (t == SA_DET_CLASSIFY && upsum_n) return SA_ERR_SHAPE;       // declared addends nothing would consume
+                upsum_n = 0;
+                cls_h = o.hin; cls_w = o.win; cls_l = o.cout;
+                break;
+            case SA_DET_UPSAMPLE_OUT:
+                if (o.hin != cls_h || o.win != cls_w || o.cout != cls_l || (long)o.cout * o.hout * o.wout > heat_elems) return SA_ERR_SHAPE;
+                break;
+        }
+        if (has_out) written[o.out] = 1;
+    }
+    if (upsum_n) return SA_ERR_SHAPE;
+    return SA_OK;
+}
+
 }  // namespace sa
 
 using namespace sa;
@@ -487,11 +585,8 @@ int surya_det_create(const surya_det_config* cfg, const surya_det_op* ops, const
                      const size_t* buf_elems, int n_bufs, surya_det** out) {
     if (!cfg || !ops || !weights || !buf_elems || !out || cfg->n_ops <= 0 || n_bufs <= 0 || cfg->max_batch <= 0) return SA_ERR_ARG;
     if (cfg->height % 32 || cfg->width % 32 || cfg->num_labels < 1 || cfg->num_labels > 4) return SA_ERR_SHAPE;
-    for (int i = 0; i < cfg->n_ops; ++i) {
-        const surya_det_op& o = ops[i];
-        if (o.out >= n_bufs || o.in0 >= n_bufs || o.in1 >= n_bufs || o.res >= n_bufs || o.w_idx >= n_weights || o.b_idx >= n_weights)
-            return SA_ERR_ARG;
-    }
+    if (cfg->dtype != SA_DTYPE_F32 && cfg->dtype != SA_DTYPE_BF16 && cfg->dtype != SA_DTYPE_F16) return SA_ERR_UNSUPPORTED;
+    if (int rc = det_validate(*cfg, ops, n_weights, buf_elems, n_bufs)) return rc;
     auto* h = new surya_det();
     int rc;
     if (cfg->dtype == SA_DTYPE_F32) {
@@ -538,6 +633,11 @@ int surya_det_forward(surya_det* h, const float* pixel_values, int batch, float*
 }
 
 int surya_det_op_count(surya_det* h) { return h ? h->impl->n_ops() : SA_ERR_ARG; }
+
+int surya_det_read_buffer(surya_det* h, int buf, int batch, void* dst, size_t dst_bytes, void* stream) {
+    if (!h || !dst) return SA_ERR_ARG;
+    return h->impl->read_buffer(buf, batch, dst, dst_bytes, (hipStream_t)stream);
+}
 
 int surya_det_forward_timed(surya_det* h, const float* pixel_values, int batch, float* heatmaps, float* lowres, void* stream, float* op_ms,
                             int n_op_ms) {

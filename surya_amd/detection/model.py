@@ -36,9 +36,38 @@ class HipDetModel:
         # algorithmic FLOPs per page = the reference's own op order; the folded decode head executes fewer
         self.flops_per_image = plan.reference_flops_per_image
         self.executed_flops_per_image = plan.flops_per_image
+        self.in_shape = (cfg.num_channels, height, width)
+        self.num_labels = cfg.num_labels
+        self._create(plan, broadcast_weights, process_group)
+
+    @classmethod
+    def from_plan(cls, plan, *, height: int, width: int, num_labels: int, dtype: torch.dtype = torch.bfloat16, max_batch: int = 16,
+                  device="cuda:0"):
+        """Test and measurement support: an engine over `plan` (a DetPlan) as it stands -- no config, no state dict. height / width /
+        num_labels size the fp32 planes and the heat maps (surya_det_config); the pixels `forward` takes are those of the plan's INPUT op."""
+        if not torch.cuda.is_available():
+            raise L.SuryaAmdError("HipDetModel needs a GPU (MI355X); there is no CPU fallback")
+        if dtype not in _DTYPES:
+            raise ValueError("dtype must be float32 (reference mode), bfloat16 or float16")
+        from .plan import OP_INPUT
+        self = cls.__new__(cls)
+        self.lib = L.lib()
+        self.lib.surya_det_create.argtypes = None
+        self.cfg, self.dtype, self.device = None, dtype, torch.device(device)
+        self.height, self.width, self.max_batch, self.num_labels = height, width, max_batch, num_labels
+        torch.cuda.set_device(self.device)
+        self.flops_per_image = self.executed_flops_per_image = plan.flops_per_image
+        inp = [o for o in plan.ops if o["type"] == OP_INPUT]
+        self.in_shape = (inp[0]["cin"], inp[0]["hin"], inp[0]["win"]) if inp else (0, 0, 0)
+        self._create(plan, False, None)
+        return self
+
+    def _create(self, plan, broadcast_weights, process_group):
         from .plan import OP_LITEMLA, OP_UPSUM_SRC
+        dtype, height, width, max_batch = self.dtype, self.height, self.width, self.max_batch
         self.launches_per_forward = sum(2 if o["type"] == OP_LITEMLA else (0 if o["type"] == OP_UPSUM_SRC else 1) for o in plan.ops)
         self.plan_ops = [dict(o) for o in plan.ops]
+        self.buf_elems = list(plan.buf_elems)
         self.weights = [w.to(device=self.device, dtype=dtype).contiguous() for w in plan.weights]
         if broadcast_weights:             # every rank planned the op list (shapes); the folded weights used are rank 0's
             from .. import dist as sdist
@@ -49,9 +78,9 @@ class HipDetModel:
                 for w, t in zip(self.weights, tmp):
                     w.copy_(t)
         ops = (DetOpC * len(plan.ops))(*[DetOpC(**{k: v for k, v in o.items() if k != "tag"}) for o in plan.ops])
-        table = (C.c_void_p * len(self.weights))(*[w.data_ptr() for w in self.weights])
+        table = (C.c_void_p * max(1, len(self.weights)))(*[w.data_ptr() for w in self.weights])
         bufs = (C.c_size_t * len(plan.buf_elems))(*plan.buf_elems)
-        c = L.DetConfigC(n_ops=len(plan.ops), max_batch=max_batch, height=height, width=width, num_labels=cfg.num_labels,
+        c = L.DetConfigC(n_ops=len(plan.ops), max_batch=max_batch, height=height, width=width, num_labels=self.num_labels,
                          dtype=_DTYPES[dtype])
         self.handle = C.c_void_p()
         L.check(self.lib.surya_det_create(C.byref(c), ops, table, len(self.weights), bufs, len(plan.buf_elems),
@@ -82,15 +111,30 @@ class HipDetModel:
         """pixel_values cuda fp32 [B,3,H,W] -> heatmaps fp32 [B, labels, H, W] (and [B, labels, H/4, W/4])."""
         assert pixel_values.is_cuda and pixel_values.dtype == torch.float32 and pixel_values.is_contiguous()
         B = pixel_values.shape[0]
-        assert tuple(pixel_values.shape[1:]) == (self.cfg.num_channels, self.height, self.width) and B <= self.max_batch
+        assert tuple(pixel_values.shape[1:]) == self.in_shape and B <= self.max_batch
         torch.cuda.set_device(self.device)
-        heat = torch.empty((B, self.cfg.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
-        low = torch.empty((B, self.cfg.num_labels, self.height // 4, self.width // 4), dtype=torch.float32,
+        # (a plan without UPSAMPLE_OUT / CLASSIFY leaves these untouched: the ABI wants a non-null heat pointer all the same)
+        heat = torch.empty((B, self.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
+        low = torch.empty((B, self.num_labels, self.height // 4, self.width // 4), dtype=torch.float32,
                           device=self.device) if want_lowres else None
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib.surya_det_forward(self.handle, L.ptr(pixel_values), C.c_int(B), L.ptr(heat), L.ptr(low), stream),
                 "surya_det_forward")
         return (heat, low) if want_lowres else heat
+
+    def read_buffer(self, buf: int, batch: int, shape):
+        """Test and measurement support (surya_det_read_buffer): the first `batch` images of activation buffer `buf` after a forward,
+        as a tensor of the compute dtype shaped [batch, *shape] (NHWC: shape = (h, w, c) of the op that wrote it)."""
+        n = 1
+        for d in shape:
+            n *= int(d)
+        assert 0 <= buf < len(self.buf_elems) and n == self.buf_elems[buf], "shape must cover the whole buffer"
+        torch.cuda.set_device(self.device)
+        out = torch.empty((batch, *shape), dtype=self.dtype, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.surya_det_read_buffer(self.handle, C.c_int(buf), C.c_int(batch), L.ptr(out), C.c_size_t(out.numel() * out.element_size()),
+                                               stream), "surya_det_read_buffer")
+        return out
 
     def forward_timed(self, pixel_values: torch.Tensor):
         """Measurement support (surya_det_forward_timed): the same forward with a hipEvent in front of every op of the plan.
@@ -98,7 +142,7 @@ class HipDetModel:
         assert pixel_values.is_cuda and pixel_values.dtype == torch.float32 and pixel_values.is_contiguous()
         B = pixel_values.shape[0]
         torch.cuda.set_device(self.device)
-        heat = torch.empty((B, self.cfg.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
+        heat = torch.empty((B, self.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
         n = int(self.lib.surya_det_op_count(self.handle))
         ms = (C.c_float * n)()
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
@@ -113,8 +157,8 @@ class HipDetModel:
         B, pix = pages_u8.shape[0], pages_u8.shape[3]
         assert tuple(pages_u8.shape[1:3]) == (self.height, self.width) and pix in (3, 4) and B <= self.max_batch
         torch.cuda.set_device(self.device)
-        heat = torch.empty((B, self.cfg.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
-        low = torch.empty((B, self.cfg.num_labels, self.height // 4, self.width // 4), dtype=torch.float32,
+        heat = torch.empty((B, self.num_labels, self.height, self.width), dtype=torch.float32, device=self.device)
+        low = torch.empty((B, self.num_labels, self.height // 4, self.width // 4), dtype=torch.float32,
                           device=self.device) if want_lowres else None
         m = (C.c_float * 3)(*[float(np.float32(v)) for v in mean])
         sd = (C.c_float * 3)(*[float(np.float32(v)) for v in std])
