@@ -350,6 +350,16 @@ int surya_det_forward_u8(surya_det* h, const uint8_t* pixels_nhwc, int pixel_str
 int surya_resample_lanczos_u8(const uint8_t* src, int src_w, int src_h, int src_pix, uint8_t* dst, int dst_w, int dst_h, int dst_pix,
                               const int32_t* bounds_x, const int32_t* taps_x, int ksize_x, const int32_t* bounds_y,
                               const int32_t* taps_y, int ksize_y, uint8_t* tmp, void* stream);
+/* One Pillow `Image.reduce((fx, fy))` of an 8-bit RGB page on the device: the integer box reduction `img.thumbnail(size, LANCZOS)`
+ * (reducing_gap = 2.0) runs in front of its LANCZOS passes when an axis shrinks by 4x or more (600-dpi scans, camera photos). The
+ * LANCZOS call that follows takes tables built for the source box (0, 0, src_w / fx, src_h / fy) (pil_resample.plan_chain).
+ * Bit-identical to Pillow: a pixel = ((sum + n / 2) * (2^24 / n)) >> 24 in uint32 over the n source pixels present in its fx x fy
+ * block (the last column / row / corner of a size that is no multiple of the factor average what exists).
+ *   src   device uint8 [src_h][src_w][src_pix], dst device uint8 [ceil(src_h / fy)][ceil(src_w / fx)][dst_pix]; pix = 3 (RGB) or
+ *         4 (RGBX, fourth byte ignored / written 0; a 4-byte dst must be 4-byte aligned). 1 <= fx, fy <= 255, not both 1; any
+ *         height. SA_ERR_ARG otherwise. fx in 2..4 streams through vector loads where the rows are aligned for them (RGBX: 16
+ *         or 8 bytes, RGB: 4); every other case runs the generic kernel. Enqueue only. */
+int surya_reduce_u8(const uint8_t* src, int src_w, int src_h, int src_pix, uint8_t* dst, int dst_pix, int fx, int fy, void* stream);
 
 /* Heat map -> text boxes on the device. Replaces detect_boxes (surya/detection/heatmap.py:27-107:
  * get_dynamic_thresholds :14-24, cv2.connectedComponentsWithStats, per-component cv2.dilate + cv2.minAreaRect + cv2.boxPoints,

@@ -8,8 +8,19 @@ Pillow is an installed dependency, not part of the reference tree) is integer ar
     rounded to 22-bit fixed point; each pass accumulates int32 from 2^21 and stores clip8(acc >> 22); horizontal pass first,
     its uint8 result feeds the vertical pass.
 This module computes the sizes and the fixed-point tables exactly as Pillow does (math.sin = the same libm); the kernels apply
-them. Only what the GPU path covers is restated: RGB pages, no `reduce()` pre-pass (thumbnail's reducing_gap = 2.0 triggers
-one when a side shrinks by 4x or more) -- `plan()` returns None for anything else and the caller keeps Pillow.
+them. Only what the GPU path covers is restated: RGB pages. `plan()` covers the pages whose thumbnail is plain LANCZOS and returns
+None for anything else.
+
+Pages whose thumbnail shrinks an axis by 4x or more: `plan_chain()`. `thumbnail(..., reducing_gap=2.0)` = Image.resize with
+    fx = int(w / tw / 2.0) or 1, fy = int(h / th / 2.0) or 1; when either exceeds 1 an `Image.reduce((fx, fy))` box reduction
+    (src/libImaging/Reduce.c) runs first, then the LANCZOS passes over the reduced image with box = (0, 0, w / fx, h / fy):
+    scale = (in1 - in0) / out, center = in0 + (xx + 0.5) * scale, the tap window clipped to the reduced SIZE (not to in1).
+    The box reaches the C code as float32, the tables are float64 from there on.
+reduce(): output ceil(w / fx) x ceil(h / fy); a pixel = ((sum + n // 2) * (2^24 // n)) >> 24 in uint32 over the n source pixels that
+    exist in its fx x fy block (ragged last column / row / corner: their own n). 2^24 // n is the FLOOR: for n not a power of two one
+    block sum per output level comes out one below (sum + n // 2) // n.
+`reduce_reference` states that in numpy (the checker of csrc/resample.h's reduce kernels; Pillow is its checker). Still left to Pillow
+in both planners: images more than 100 times as tall as wide.
 """
 from __future__ import annotations
 
@@ -32,10 +43,14 @@ def _lanczos(x: float) -> float:
 
 
 @lru_cache(maxsize=256)
-def lanczos_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray, int]:
-    """precompute_coeffs + normalize_coeffs_8bpc for the whole axis (box = (0, in_size)):
-    bounds int32 [out, 2] = (first source index, tap count), taps int32 [out, ksize] in 22-bit fixed point."""
-    scale = filterscale = in_size / out_size
+def lanczos_coeffs(in_size: int, out_size: int, in0: float = 0.0, in1: Optional[float] = None) -> Tuple[np.ndarray, np.ndarray, int]:
+    """precompute_coeffs + normalize_coeffs_8bpc for the source span [in0, in1) of an axis of in_size pixels (default: the whole
+    axis, box = (0, in_size)): bounds int32 [out, 2] = (first source index, tap count), taps int32 [out, ksize] in 22-bit fixed
+    point. The span is float32 in Pillow's C signature (a fractional in1 follows a ragged reduce())."""
+    f0 = np.float32(in0)
+    f1 = np.float32(in_size if in1 is None else in1)
+    in0 = float(f0)
+    scale = filterscale = float(f1 - f0) / out_size
     if filterscale < 1.0:
         filterscale = 1.0
     support = 3.0 * filterscale
@@ -45,7 +60,7 @@ def lanczos_coeffs(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray,
     ss = 1.0 / filterscale
     one = float(1 << PRECISION_BITS)
     for xx in range(out_size):
-        center = (xx + 0.5) * scale
+        center = in0 + (xx + 0.5) * scale
         xmin = int(center - support + 0.5)
         if xmin < 0:
             xmin = 0
@@ -82,42 +97,75 @@ def thumbnail_size(w: int, h: int, size: Tuple[int, int]) -> Optional[Tuple[int,
     return x, y
 
 
-def plan(w: int, h: int, size: Tuple[int, int]) -> Optional[List[Tuple[int, int]]]:
-    """The chain of sizes `thumbnail(size, LANCZOS)` + `resize(size, LANCZOS)` passes through, as a list of (w, h) targets
-    (empty = already at `size`), or None when Pillow would take a path the kernels do not restate."""
-    steps: List[Tuple[int, int]] = []
+Box = Tuple[float, float, float, float]
+
+
+def plan_chain(w: int, h: int, size: Tuple[int, int]) -> Optional[list]:
+    """The steps of `thumbnail(size, LANCZOS)` + `resize(size, LANCZOS)`, thumbnail's reduce() pre-pass included, as a list of
+    ("reduce", fx, fy) and ("resize", (w, h), box) -- box None = the whole image, else (0, 0, w / fx, h / fy) on the reduced image --
+    (empty = already at `size`), or None for the tall images Pillow resizes in two calls."""
+    steps: list = []
     cw, ch = w, h
     t = thumbnail_size(w, h, size)
     if t is not None and t != (w, h):
-        # resize(t, reducing_gap=2.0): a reduce() pre-pass when a side shrinks >= 4x; the tall-image special case
-        if int(w / t[0] / 2.0) > 1 or int(h / t[1] / 2.0) > 1:
-            return None
         if h > w * 100 and t[1] < h:
             return None
-        steps.append(t)
+        fx, fy = int(w / t[0] / 2.0) or 1, int(h / t[1] / 2.0) or 1          # Image.resize(t, reducing_gap=2.0)
+        box = None
+        if fx > 1 or fy > 1:
+            steps.append(("reduce", fx, fy))
+            box = (0.0, 0.0, w / fx, h / fy)
+        steps.append(("resize", t, box))
         cw, ch = t
     if (cw, ch) != tuple(size):
         if ch > cw * 100 and size[1] < ch:
             return None
-        steps.append((int(size[0]), int(size[1])))
+        steps.append(("resize", (int(size[0]), int(size[1])), None))
     return steps
 
 
-def resample_reference(img: np.ndarray, out_w: int, out_h: int) -> np.ndarray:
-    """numpy statement of ImagingResample for uint8 [H, W, C] (the checker of the kernels in tests; Pillow itself is the
-    checker of this function)."""
+def plan(w: int, h: int, size: Tuple[int, int]) -> Optional[List[Tuple[int, int]]]:
+    """`plan_chain` for the pages whose thumbnail is plain LANCZOS: the list of (w, h) targets the two resizes go to (empty =
+    already at `size`), or None when Pillow would reduce first or resize a tall image in two calls."""
+    steps = plan_chain(w, h, size)
+    if steps is None or any(s[0] == "reduce" for s in steps):
+        return None
+    return [s[1] for s in steps]
+
+
+def reduce_reference(img: np.ndarray, fx: int, fy: int) -> np.ndarray:
+    """numpy statement of ImagingReduce for uint8 [H, W, C] -> [ceil(H / fy), ceil(W / fx), C] (the checker of the reduce kernels;
+    Pillow itself is the checker of this function)."""
     h, w, c = img.shape
+    oh, ow = -(-h // fy), -(-w // fx)
+    pad = np.zeros((oh * fy, ow * fx, c), np.uint32)
+    pad[:h, :w] = img
+    s = pad.reshape(oh, fy, ow, fx, c).sum((1, 3), dtype=np.uint32)
+    nx, ny = np.full(ow, fx, np.uint32), np.full(oh, fy, np.uint32)
+    if w % fx:
+        nx[-1] = w % fx
+    if h % fy:
+        ny[-1] = h % fy
+    n = (ny[:, None] * nx[None, :])[..., None]
+    return (((s + n // 2) * ((1 << 24) // n)) >> 24).astype(np.uint8)          # uint32: (255.5 n) * (2^24 / n) < 2^32
+
+
+def resample_reference(img: np.ndarray, out_w: int, out_h: int, box: Optional[Box] = None) -> np.ndarray:
+    """numpy statement of ImagingResample for uint8 [H, W, C] (the checker of the kernels in tests; Pillow itself is the
+    checker of this function). box: the source rectangle (x0, y0, x1, y1), default the whole image."""
+    h, w, c = img.shape
+    x0_, y0_, x1_, y1_ = (0.0, 0.0, float(w), float(h)) if box is None else box
     cur = img
-    if out_w != w:
-        b, kk, _ = lanczos_coeffs(w, out_w)
+    if out_w != w or x0_ != 0 or x1_ != w:
+        b, kk, _ = lanczos_coeffs(w, out_w, x0_, x1_)
         out = np.empty((h, out_w, c), np.uint8)
         for xx in range(out_w):
             x0, n = int(b[xx, 0]), int(b[xx, 1])
             acc = (cur[:, x0:x0 + n].astype(np.int64) * kk[xx, :n].astype(np.int64)[None, :, None]).sum(1) + (1 << (PRECISION_BITS - 1))
             out[:, xx] = np.clip(acc >> PRECISION_BITS, 0, 255).astype(np.uint8)
         cur = out
-    if out_h != h:
-        b, kk, _ = lanczos_coeffs(h, out_h)
+    if out_h != h or y0_ != 0 or y1_ != h:
+        b, kk, _ = lanczos_coeffs(h, out_h, y0_, y1_)
         out = np.empty((out_h, cur.shape[1], c), np.uint8)
         for yy in range(out_h):
             y0, n = int(b[yy, 0]), int(b[yy, 1])

@@ -661,4 +661,10 @@ int surya_resample_lanczos_u8(const uint8_t* src, int src_w, int src_h, int src_
                                 ksize_y, tmp, (hipStream_t)stream);
 }
 
+int surya_reduce_u8(const uint8_t* src, int src_w, int src_h, int src_pix, uint8_t* dst, int dst_pix, int fx, int fy, void* stream) {
+    if (!src || !dst || src_w <= 0 || src_h <= 0 || fx < 1 || fy < 1 || fx > 255 || fy > 255 || (fx == 1 && fy == 1)) return SA_ERR_ARG;
+    if ((src_pix != 3 && src_pix != 4) || (dst_pix != 3 && dst_pix != 4) || (dst_pix == 4 && (uintptr_t)dst % 4 != 0)) return SA_ERR_ARG;
+    return sa::rs::reduce_run(src, src_w, src_h, src_pix, dst, dst_pix, fx, fy, (hipStream_t)stream);
+}
+
 }  // extern "C"

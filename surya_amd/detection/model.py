@@ -244,8 +244,9 @@ class HipDetPost:
 
 
 class DeviceResampler:
-    """Pillow LANCZOS resizes of uint8 pages on the device (surya_resample_lanczos_u8, csrc/resample.h). Coefficient tables are
-    built once per (source length, target length) pair by common/pil_resample.py and cached on the device."""
+    """Pillow LANCZOS resizes (surya_resample_lanczos_u8) and integer box reductions (surya_reduce_u8) of uint8 pages on the
+    device (csrc/resample.h). Coefficient tables are built once per (source length, target length, source span) by
+    common/pil_resample.py and cached on the device."""
 
     def __init__(self, device="cuda:0"):
         if not torch.cuda.is_available():
@@ -254,29 +255,49 @@ class DeviceResampler:
         self.device = torch.device(device)
         self._tables = {}
 
-    def _axis(self, n_in: int, n_out: int):
-        key = (n_in, n_out)
+    def _axis(self, n_in: int, n_out: int, in0: float = 0.0, in1: float = None):
+        in1 = float(n_in) if in1 is None else float(in1)
+        key = (n_in, n_out, float(in0), in1)
         t = self._tables.get(key)
         if t is None:
             from ..common.pil_resample import lanczos_coeffs
-            b, kk, ks = lanczos_coeffs(n_in, n_out)
+            b, kk, ks = lanczos_coeffs(n_in, n_out, float(in0), in1)
             t = self._tables[key] = (torch.from_numpy(b).to(self.device), torch.from_numpy(kk).to(self.device), ks)
         return t
 
-    def resize(self, src: torch.Tensor, size, out: torch.Tensor = None) -> torch.Tensor:
-        """src cuda uint8 [h, w, 3|4] -> Image.resize((W, H), LANCZOS) of it as uint8 [H, W, out.shape[2] or 4]."""
+    def reduce(self, src: torch.Tensor, fx: int, fy: int, out: torch.Tensor = None) -> torch.Tensor:
+        """src cuda uint8 [h, w, 3|4] -> Image.reduce((fx, fy)) of it as uint8 [ceil(h / fy), ceil(w / fx), out.shape[2] or 4]."""
+        assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 3
+        h, w, sp = src.shape
+        H, W = -(-h // int(fy)), -(-w // int(fx))
+        if out is None:
+            out = torch.empty((H, W, 4), dtype=torch.uint8, device=self.device)
+        assert out.is_cuda and out.is_contiguous() and tuple(out.shape[:2]) == (H, W) and out.shape[2] in (3, 4)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.surya_reduce_u8(L.ptr(src), C.c_int(w), C.c_int(h), C.c_int(sp), L.ptr(out), C.c_int(out.shape[2]),
+                                         C.c_int(int(fx)), C.c_int(int(fy)), stream), "surya_reduce_u8")
+        return out
+
+    def resize(self, src: torch.Tensor, size, out: torch.Tensor = None, box=None) -> torch.Tensor:
+        """src cuda uint8 [h, w, 3|4] -> Image.resize((W, H), LANCZOS, box) of it as uint8 [H, W, out.shape[2] or 4]. box: the
+        source rectangle (x0, y0, x1, y1) of the resize that follows a reduce() (pil_resample.plan_chain), default the image."""
         assert src.is_cuda and src.dtype == torch.uint8 and src.is_contiguous() and src.dim() == 3
         h, w, sp = src.shape
         W, H = int(size[0]), int(size[1])
+        x0, y0, x1, y1 = (0.0, 0.0, float(w), float(h)) if box is None else map(float, box)
+        # the kernels run a pass iff the length changes; Pillow also runs one for a box that is not the whole axis, which after a
+        # reduce() only comes with a length at least twice the target's
+        if (W == w and (x0 != 0 or x1 != w)) or (H == h and (y0 != 0 or y1 != h)):
+            raise L.SuryaAmdError(f"DeviceResampler.resize: box {box} on an axis that keeps its length ({w}x{h} -> {W}x{H})")
         if out is None:
             out = torch.empty((H, W, 4), dtype=torch.uint8, device=self.device)
         assert out.is_cuda and out.is_contiguous() and tuple(out.shape[:2]) == (H, W) and out.shape[2] in (3, 4)
         bx = kx = by = ky = None
         ksx = ksy = 0
         if W != w:
-            bx, kx, ksx = self._axis(w, W)
+            bx, kx, ksx = self._axis(w, W, x0, x1)
         if H != h:
-            by, ky, ksy = self._axis(h, H)
+            by, ky, ksy = self._axis(h, H, y0, y1)
         tmp = torch.empty((h, W, 4), dtype=torch.uint8, device=self.device) if (W != w and H != h) else None
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         L.check(self.lib.surya_resample_lanczos_u8(L.ptr(src), C.c_int(w), C.c_int(h), C.c_int(sp), L.ptr(out), C.c_int(W), C.c_int(H),

@@ -20,7 +20,7 @@ from ..common.predictor import BasePredictor, ModelLoader, gc_paused
 from ..config import DetConfig, det_config
 from ..settings import settings
 from .heatmap import TextDetectionResult, parallel_get_boxes, result_from_device_boxes
-from ..common.pil_resample import plan as plan_resize
+from ..common.pil_resample import plan_chain as plan_resize
 from .model import DeviceResampler, HipDetModel, HipDetPost
 
 
@@ -157,9 +157,12 @@ class DetectionPredictor(BasePredictor):
     # of two fp32 maps (8 MB at 1024^2). DETECTOR_POSTPROCESS_HOST=1 keeps the host post-processing of the reference layout
     # (heat maps D2H + surya_amd/detection/heatmap.py on a thread pool): the checker of tests/test_gpu_det.py, not a fallback.
     device_postprocess: bool = not settings.DETECTOR_POSTPROCESS_HOST
-    # the double LANCZOS resize of every page on the device; DETECTOR_RESIZE_HOST=1 keeps Pillow on a thread pool (the checker of
-    # tests/test_gpu_resample.py; also what pages take whose resize needs Pillow's reduce() pre-pass)
+    # the double LANCZOS resize of every page on the device, with the box reduction Pillow's thumbnail() puts in front of it for
+    # >= 4x shrinks; DETECTOR_RESIZE_HOST=1 keeps Pillow on a thread pool (the checker of tests/test_gpu_resample*.py)
     device_resize: bool = not settings.DETECTOR_RESIZE_HOST
+    # how the parts (pages / strips of tall pages) of the last call got to the processor size: resized on the device, by Pillow on
+    # the host, or already there. With device_resize, "host" counts only images more than 100 times as tall as wide.
+    last_resize_paths = {"device": 0, "host": 0, "ready": 0}
 
     def _detect(self, images: List[Image.Image], batch_size=None, include_maps=False) -> List[TextDetectionResult]:
         if self.device_postprocess:
@@ -292,6 +295,7 @@ class DetectionPredictor(BasePredictor):
             cur_n += splits[i]
         if cur:
             batches.append(cur)
+        paths = self.last_resize_paths = {"device": 0, "host": 0, "ready": 0}
         for idxs in batches:
             # the device path only READS the pages (zero-copy pixel views, resize on the device): no defensive copies of pages that
             # already are RGB (convert() and split_image() each copied 4 MB per 1024^2 page under the GIL; the Pillow resize of
@@ -306,9 +310,9 @@ class DetectionPredictor(BasePredictor):
                 split_index.extend([k] * len(ps))
                 split_heights.extend(hs)
             # pages go to the device as uint8; the reference's double LANCZOS resize to the processor size runs there too
-            # (surya_resample_lanczos_u8, bit-identical to Pillow) unless Pillow would take a path the kernels do not restate
-            # (a reduce() pre-pass for >= 4x shrinks: common/pil_resample.plan) or DETECTOR_RESIZE_HOST=1 asks for the host path;
-            # rescale + normalise happen in the model's first kernel
+            # (surya_reduce_u8 for the box reduction of >= 4x shrinks, surya_resample_lanczos_u8; bit-identical to Pillow) unless
+            # Pillow would take a path the kernels do not restate (images > 100 x as tall as wide: common/pil_resample.plan_chain)
+            # or DETECTOR_RESIZE_HOST=1 asks for the host path; rescale + normalise happen in the model's first kernel
             pw = self.processor.size["width"]
             plans = [None if not self.device_resize else plan_resize(p_.size[0], p_.size[1], (pw, ph)) for p_ in parts]
             pool = copy_pool()
@@ -320,6 +324,8 @@ class DetectionPredictor(BasePredictor):
                 px = [self.resize_image(parts[k]) if plans[k] is None else page_pixels(parts[k]) for k in range(len(parts))]
             # RGBX views of PIL's own memory where it can export them (page_pixels), else repacked RGB; one stride per batch
             ready = [k for k, pl in enumerate(plans) if pl is None or not pl]          # already at the processor size
+            for k, pl in enumerate(plans):
+                paths["device" if pl else "ready" if (pl is not None or parts[k].size == (pw, ph)) else "host"] += 1
             pix = 4 if all(px[k].shape[2] == 4 for k in ready) else 3
             host = torch.empty((len(parts), ph, pw, pix), dtype=torch.uint8, pin_memory=True)   # caching host allocator
             hv = host.numpy()
@@ -342,8 +348,11 @@ class DetectionPredictor(BasePredictor):
                 for k, o, b in zip(todo, offs_b[:-1], sizes_b):
                     cur = dev_stage[int(o): int(o) + b].view(px[k].shape)
                     pl = plans[k]
-                    for i, tgt in enumerate(pl):                            # thumbnail's size, then the processor size
-                        cur = self._resampler.resize(cur, tgt, out=dev_batch[k] if i == len(pl) - 1 else None)
+                    for i, st in enumerate(pl):                # [thumbnail's box reduction,] thumbnail's size, then the processor size
+                        if st[0] == "reduce":
+                            cur = self._resampler.reduce(cur, st[1], st[2])
+                        else:
+                            cur = self._resampler.resize(cur, st[1], out=dev_batch[k] if i == len(pl) - 1 else None, box=st[2])
             heat_parts = []
             for s in range(0, len(parts), self.model.max_batch):            # a single page may exceed max_batch tiles
                 heat_parts.append(self.model.forward_u8(dev_batch[s: s + self.model.max_batch], self.processor.image_mean,
