@@ -211,8 +211,11 @@ int surya_rec_set_kv_fp8(surya_rec* h, int on);
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
 /* C[M,N] = X[M,K] W[N,K]^T + bias, epilogue: 0 none/bias, 1 +residual R, 2 gelu, 3 swiglu (W rows interleaved,
- * C is [M,N/2]), 4 hardswish, 5 relu. out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the
- * detector's epilogues (0, 1, 4, 5) with fp16 output only; anything else returns SA_ERR_UNSUPPORTED. */
+ * C is [M,N/2]), 4 hardswish, 5 relu, 8 geglu = gelu_tanh(gate) * up with gate, up and the gelu each rounded to the compute dtype
+ * (the ADETR decoder's MLP, W rows interleaved like swiglu, C is [M,N/2]; fp32 and bf16 only, no bias, no R, out_f32 == 0).
+ * Codes 6 and 7 are epilogues of the recogniser that take further operands and are not reachable here: SA_ERR_ARG.
+ * out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the detector's epilogues (0, 1, 4, 5) with fp16
+ * output only; anything else returns SA_ERR_UNSUPPORTED. */
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,
                   const void* bias, const void* R, long ldr, int M, int N, int K, void* stream);
 int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, int rows, int C, float eps,
@@ -256,6 +259,66 @@ int surya_op_gemm_splitk_bf16(const void* X, long ldx, const void* W, long ldw, 
 int surya_op_mx_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* scales, void* stream);
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream);
+
+/* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
+ * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).
+ * dtype SA_DTYPE_F32 or SA_DTYPE_BF16 as the engine, anything else SA_ERR_UNSUPPORTED. All pointers are caller-owned device memory
+ * unless marked host; enqueue only; nothing is allocated.
+ * surya_lay_window_tables (host only, no GPU): what LayoutModel::init builds per (stage, shift) for an h x w token grid.
+ *   perm[h * w] (host, may be NULL) = window-order row of every token after padding to whole windows and the cyclic shift by -shift;
+ *   pad_rows (host, may be NULL; *n_pad entries, at most padded area - h * w) = the window-order rows of the zero padding, ascending;
+ *   padded_hw[2] = the grid in whole windows; *shift_used = 0 when min(h, w) == window (such a stage is never shifted), else shift.
+ *   min(h, w) < window: SA_ERR_UNSUPPORTED.
+ * surya_lay_cross_plan (host only): for Lk cached keys, the fp32 cross attention's keys per range and ranges (scratch = rows * heads *
+ *   ranges * (head_dim + 2) floats) and the bf16 kernel's padded key count Lkp (vT = images * kv_heads * head_dim * Lkp elements).
+ * surya_op_lay_layernorm: y[dst(r)] = LayerNorm(x[r]) over C channels, dst(r) = (r / rows_per_image) * (rows_per_image_out ?
+ *   rows_per_image_out : rows_per_image) + perm[r % rows_per_image], or r when perm == NULL. bf16 with C in {128, 256, 512, 1024} runs
+ *   layernorm_rows_bf16_kernel unless surya_set_tuning("lay_ln", 0), everything else layernorm_kernel. C % 4 == 0.
+ * surya_op_lay_window_attn: qkv [windows * 64][(nh + 2 nkv) * 32] in window order -> out [windows * 64][nh * 32]; bias fp32 [nh][64][64];
+ *   window index % (nwx * nwy) is its place in the image, shift > 0 masks across the cyclic-shift regions of the last window row / column.
+ *   bf16 runs swin_window_attn_mfma_kernel, fp32 swin_window_attn_kernel. ws must be 8.
+ * surya_op_lay_merge_ln: x [B][H][W][C] -> y [B * H/2 * W/2][4C] = LayerNorm of the 2x2 neighbours (0,0), (1,0), (0,1), (1,1). H, W even.
+ * surya_op_lay_rows: the encoder's row movers; dims is a HOST array:
+ *   SA_LAY_PATCHIFY   dims {B, C, H, W, P, Kpad}: src fp32 pixels [B][C][H][W] -> dst patch rows [B * H/P * W/P][Kpad]
+ *   SA_LAY_ADD_ROWS   dims {rows, rows_per_image, C}: dst[r] += src[r % rows_per_image]
+ *   SA_LAY_ZERO_ROWS  dims {B, n_pad, rows_per_image, C}: dst[b * rows_per_image + index[i]] = 0
+ *   SA_LAY_GATHER_ADD dims {rows, rows_per_image, C, rows_per_image_src}: dst[r] += src[(r / rows_per_image) * (rows_per_image_src ?
+ *                     rows_per_image_src : rows_per_image) + index[r % rows_per_image]]
+ * surya_op_lay_cross_attn: M query rows, one per decoder row, over the Lk keys of image item_map[row]; kv [n_images][Lk][2 * nkv * head_dim]
+ *   (k heads | v heads). S in 1..8: qpart fp32 [S][M][nq * head_dim] split-K slabs, summed and rounded to the compute dtype; S == 0: qpart
+ *   is a plain [M][nq * head_dim] matrix of the compute dtype (the prefill path). bf16: transpose_cross_v_kernel fills vT, then
+ *   cross_attn_mfma_kernel; fp32: cross_attn_split_kernel + cross_attn_merge_kernel through scratch (sizes: surya_lay_cross_plan; the
+ *   buffer the dtype does not use may be NULL). head_dim in {32, 64}, nq / nkv <= 8.
+ * surya_op_lay_rmsnorm: SuryaADETRDecoderRMSNorm (variance clamped at eps, scale 1 + w, clamp to the dtype's range, NaN -> 0).
+ * surya_op_lay_reduce_norm: x_out = T(res + T(bias + sum of S slabs part[S][M][H])), y = that RMSNorm of x_out. res may alias x_out;
+ *   bias may be NULL; w == NULL skips y. H % 4 == 0, H <= 4096, S in 1..8.
+ * surya_op_lay_prefill_attn: causal self-attention of B prompts of Tn tokens, qkv [B * Tn][(nq + 2 nkv) * head_dim], RoPE at positions
+ *   0 .. Tn - 1 from rope_cs [Tmax][head_dim / 2][2] (cos, sin); writes out [B * Tn][nq * head_dim] and rows 0 .. Tn - 1 of the caches
+ *   [B][nkv][Tmax][head_dim]. head_dim in {32, 64}, Tn * head_dim * 8 bytes of LDS.
+ * surya_op_lay_embed: family SA_FAMILY_LAYOUT: box_embed_kernel over tokens [rows][7]; SA_FAMILY_TABLE: table_embed_kernel over tokens
+ *   [rows][10]; tabs = DEVICE array of 17 device pointers in the order of SA_LW_EMB_TABLES. vocab > bbox_size.
+ * surya_op_lay_heads: layout_heads_kernel<T, false>: row b of x starts at element b * ldx; class_logits fp32 [B][label_count], bbox fp32 [B][6]. */
+enum { SA_LAY_PATCHIFY = 0, SA_LAY_ADD_ROWS, SA_LAY_ZERO_ROWS, SA_LAY_GATHER_ADD };
+int surya_lay_window_tables(int h, int w, int window, int shift, int32_t* perm, int32_t* pad_rows, int32_t* n_pad, int32_t* padded_hw,
+                            int32_t* shift_used);
+int surya_lay_cross_plan(int Lk, int32_t* chunk, int32_t* ranges, int32_t* Lkp);
+int surya_op_lay_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image,
+                           int C, float eps, int rows_per_image_out, void* stream);
+int surya_op_lay_window_attn(int dtype, const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift,
+                             int ws, void* stream);
+int surya_op_lay_merge_ln(int dtype, const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream);
+int surya_op_lay_rows(int dtype, int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream);
+int surya_op_lay_cross_attn(int dtype, int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map,
+                            void* out, float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream);
+int surya_op_lay_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int C, float eps, void* stream);
+int surya_op_lay_reduce_norm(int dtype, const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y,
+                             int H, float eps, void* stream);
+int surya_op_lay_prefill_attn(int dtype, int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn,
+                              int nq, int nkv, int Tmax, float scale, void* stream);
+int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed,
+                       int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream);
+int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w,
+                       const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Detection model: EfficientViT-L backbone + SegFormer-style decode head + sigmoid + x4 bilinear upsample.

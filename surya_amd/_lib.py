@@ -19,6 +19,9 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: the detector
 (RD_LN1, RD_QKV_W, RD_QKV_B, RD_O_W, RD_LN2, RD_GU_W, RD_DOWN_W, RD_COUNT) = range(8)
 
 EPI_BIAS, EPI_RESIDUAL, EPI_GELU, EPI_SWIGLU, EPI_HARDSWISH, EPI_RELU = range(6)
+EPI_GEGLU = 8                                   # gelu_tanh(gate) * up (ADETR decoder MLP); surya_op_gemm, fp32 / bf16
+FAMILY_LAYOUT, FAMILY_TABLE = 0, 1              # SA_FAMILY_*
+LAY_PATCHIFY, LAY_ADD_ROWS, LAY_ZERO_ROWS, LAY_GATHER_ADD = range(4)      # SA_LAY_*: `kind` of surya_op_lay_rows
 
 
 class RecConfigC(C.Structure):
@@ -63,7 +66,31 @@ def lib() -> C.CDLL:
         _lib.surya_amd_version.restype = C.c_char_p
         _lib.surya_rec_workspace_bytes.restype = C.c_size_t
         _lib.surya_det_boxes_workspace_bytes.restype = C.c_size_t
+        _bind_lay_ops(_lib)
     return _lib
+
+
+def _bind_lay_ops(lib):
+    """Argument types of the layout family's op-level entry points (include/surya_amd.h): Python ints and floats convert themselves."""
+    i, l, f, p = C.c_int, C.c_long, C.c_float, C.c_void_p
+    ip = C.POINTER(C.c_int32)
+    sig = {
+        "surya_lay_window_tables": [i, i, i, i, ip, ip, ip, ip, ip],
+        "surya_lay_cross_plan": [i, ip, ip, ip],
+        "surya_op_lay_layernorm": [i, p, p, p, p, p, l, i, i, f, i, p],
+        "surya_op_lay_window_attn": [i, p, p, p, l, i, i, i, i, i, i, p],
+        "surya_op_lay_merge_ln": [i, p, p, p, p, i, i, i, i, f, p],
+        "surya_op_lay_rows": [i, i, p, p, p, ip, p],
+        "surya_op_lay_cross_attn": [i, i, p, i, i, p, i, p, p, p, p, i, i, i, f, p],
+        "surya_op_lay_rmsnorm": [i, p, p, p, i, i, f, p],
+        "surya_op_lay_reduce_norm": [i, p, i, i, p, p, p, p, p, i, f, p],
+        "surya_op_lay_prefill_attn": [i, i, p, p, p, p, p, i, i, i, i, i, f, p],
+        "surya_op_lay_embed": [i, i, p, p, p, i, i, i, i, i, i, i, i, p],
+        "surya_op_lay_heads": [i, p, l, p, p, p, p, p, p, p, p, i, i, i, f, f, p],
+    }
+    for name, args in sig.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, C.c_int
 
 
 def check(rc: int, what: str):

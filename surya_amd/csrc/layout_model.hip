@@ -48,6 +48,196 @@ __global__ void fill_int_kernel(int* p, int v, int n) {
     if (i < n) p[i] = v;
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Launch code of the family's own kernels: grid, block and LDS arithmetic and the choice between the fp32 and the bf16 kernel live HERE
+// only. LayoutModel and the op-level entry points (surya_op_lay_*, the end of this file) both call these, so a kernel tested alone is
+// launched exactly as the engine launches it.
+namespace lay {
+
+// Window-order row of every token of an h x w grid (window_partition after F.pad to whole windows and torch.roll(-shift),
+// donut/encoder.py:588-636) and the window-order rows nothing maps to (the zero padding). A grid whose smaller side does not exceed the
+// window is not shifted (:551-559). Host only.
+inline int window_tables(int h, int w, int ws, int shift_req, std::vector<int>& perm, std::vector<int>& pads, int& hp, int& wp, int& shift) {
+    if (h <= 0 || w <= 0 || ws <= 0 || shift_req < 0 || shift_req >= ws) return SA_ERR_ARG;
+    if (std::min(h, w) < ws) return SA_ERR_UNSUPPORTED;       // a map below the window: the reference's [64][64] bias would not fit either
+    shift = std::min(h, w) > ws ? shift_req : 0;
+    hp = (h + ws - 1) / ws * ws; wp = (w + ws - 1) / ws * ws;
+    perm.assign((size_t)h * w, 0);
+    std::vector<char> hit((size_t)hp * wp, 0);
+    for (int y = 0; y < h; ++y)
+        for (int xx = 0; xx < w; ++xx) {
+            const int ys = ((y - shift) % hp + hp) % hp, xs = ((xx - shift) % wp + wp) % wp;
+            const int r = ((ys / ws) * (wp / ws) + xs / ws) * ws * ws + (ys % ws) * ws + xs % ws;
+            perm[(size_t)y * w + xx] = r;
+            hit[r] = 1;
+        }
+    pads.clear();
+    for (int r = 0; r < hp * wp; ++r)
+        if (!hit[r]) pads.push_back(r);
+    return SA_OK;
+}
+
+template <typename T>
+int launch_patchify(const float* px, T* rows, int B, int C, int H, int W, int P, int Kpad, hipStream_t s) {
+    const long total = (long)B * (H / P) * (W / P) * Kpad;
+    hipLaunchKernelGGL(patchify_kernel<T>, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, px, rows, B, C, H, W, P, Kpad);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_add_rows(T* x, const T* tab, long rows, int rpi, int C, hipStream_t s) {
+    const long n4 = rows * (C / 4);
+    hipLaunchKernelGGL(add_rows_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, x, tab, rows, rpi, C);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_zero_rows(T* y, const int* pad_rows, int n_pad, int B, int rpi, int C, hipStream_t s) {
+    const long n4 = (long)B * n_pad * (C / 4);
+    hipLaunchKernelGGL(zero_rows_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, y, pad_rows, n_pad, B, rpi, C);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_gather_add(T* x, const T* a, const int* pm, long rows, int rpi, int C, int rpi_src, hipStream_t s) {
+    const long n4 = rows * (C / 4);
+    hipLaunchKernelGGL(gather_add_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, x, a, pm, rows, rpi, C, rpi_src);
+    return (int)hipGetLastError();
+}
+
+// bf16 rows of 128 / 256 / 512 / 1024 channels are held in registers by C / 8 lanes (layernorm_rows_bf16_kernel; 16-byte aligned rows)
+// unless sa::Tuning lay_ln is 0; everything else takes the one-wave-per-row kernel.
+template <typename T>
+int launch_layernorm(const T* in, const T* w, const T* b, T* out, const int* pm, long rows, int rpi, int C, float eps, int rpi_out, hipStream_t s) {
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        if (rows > 0 && tuning().lay_ln) {
+#define SA_LN_ROWS(LPR, NV)                                                                                                              \
+    {                                                                                                                                    \
+        hipLaunchKernelGGL((layernorm_rows_bf16_kernel<LPR, NV>), dim3((unsigned)cdivl(rows, 256 / LPR)), dim3(256), 0, s, in, w, b, out, \
+                           pm, rows, rpi, eps, rpi_out);                                                                                 \
+        return (int)hipGetLastError();                                                                                                   \
+    }
+            if (C == 128) SA_LN_ROWS(16, 1)
+            if (C == 256) SA_LN_ROWS(32, 1)
+            if (C == 512) SA_LN_ROWS(64, 1)
+            if (C == 1024) SA_LN_ROWS(64, 2)
+#undef SA_LN_ROWS
+        }
+    }
+    hipLaunchKernelGGL(layernorm_kernel<T>, dim3((unsigned)cdivl(rows, 4)), dim3(256), 0, s, in, w, b, out, pm, rows, rpi, C, eps, rpi_out);
+    return (int)hipGetLastError();
+}
+
+// one workgroup per (window of 64 tokens, head); bf16 on the matrix cores, fp32 on the VALU
+template <typename T>
+int launch_window_attn(const T* qkv, const float* bias, T* out, long windows, int nh, int nkv, int nwx, int nwy, int shift, int ws, hipStream_t s) {
+    if constexpr (std::is_same<T, bf16_t>::value)
+        hipLaunchKernelGGL(swin_window_attn_mfma_kernel, dim3((unsigned)windows, nh), dim3(128), 0, s, qkv, bias, out, nh, nkv, nwx, nwy, shift, ws);
+    else
+        hipLaunchKernelGGL(swin_window_attn_kernel<T>, dim3((unsigned)windows, nh), dim3(256), 0, s, qkv, bias, out, nh, nkv, nwx, nwy, shift, ws);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+int launch_merge_ln(const T* x, const T* w, const T* b, T* y, int B, int H, int W, int C, float eps, hipStream_t s) {
+    const long orows = (long)B * (H / 2) * (W / 2);
+    hipLaunchKernelGGL(merge_ln_kernel<T>, dim3((unsigned)cdivl(orows, 4)), dim3(256), 0, s, x, w, b, y, B, H, W, C, eps);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+int launch_rmsnorm(const T* x, const T* w, T* y, int rows, int C, float eps, hipStream_t s) {
+    hipLaunchKernelGGL(adetr_rmsnorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, y, rows, C, eps);
+    return (int)hipGetLastError();
+}
+
+// Cross attention over Lk cached keys. fp32: `ranges` key ranges of `chunk` keys (>= 128 keys per range, at most 8 ranges), one record of
+// head_dim + 2 floats per (row, head, range) in `scratch`. bf16: the values transposed once per encode into rows of Lkp keys (whole 32-key steps).
+struct CrossPlan { int chunk, ranges, Lkp; };
+inline CrossPlan cross_plan(int Lk) {
+    const int n = std::max(1, std::min(8, Lk / 128));
+    CrossPlan p;
+    p.chunk = (Lk + n - 1) / n;
+    p.ranges = (Lk + p.chunk - 1) / p.chunk;
+    p.Lkp = (Lk + 31) & ~31;
+    return p;
+}
+template <typename T>
+int launch_transpose_cross_v(const T* kv, T* vT, int images, int Lk, int nkv, int d, hipStream_t s) {
+    hipLaunchKernelGGL(transpose_cross_v_kernel<T>, dim3(64, images), dim3(256), 0, s, kv, vT, Lk, cross_plan(Lk).Lkp, nkv, d);
+    return (int)hipGetLastError();
+}
+// rows query rows (S == 0: qpart is a plain [M][nq * d] matrix of T; else the sum of S <= 8 fp32 slabs [S][M][nq * d]); bf16 reads kv and vT and
+// needs no scratch, fp32 reads kv and goes through scratch.
+template <typename T>
+int launch_cross_attn(const float* qpart, int S, int M, const T* kv, const T* vT, float* scratch, T* out, const int* item_map, int rows, int nq,
+                      int nkv, int d, int Lk, float scale, hipStream_t s) {
+    const int G = nq / nkv;
+    if (G < 1 || G > 8 || nq % nkv || (d != 64 && d != 32) || S < 0 || S > 8 || Lk < 1) return SA_ERR_UNSUPPORTED;
+    const CrossPlan cp = cross_plan(Lk);
+    if constexpr (std::is_same<T, bf16_t>::value) {                  // matrix-core kernel on the transposed values (layout_kernels.h)
+        if (d == 64) hipLaunchKernelGGL((cross_attn_mfma_kernel<64>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk,
+                                        cp.Lkp, scale);
+        else hipLaunchKernelGGL((cross_attn_mfma_kernel<32>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk, cp.Lkp,
+                                scale);
+    } else {
+        const size_t lds = ((size_t)G * cp.chunk + (size_t)G * d + 1024) * sizeof(float);
+        if (lds > 64 * 1024 - 512) return SA_ERR_UNSUPPORTED;
+        dim3 grid(rows, nkv, cp.ranges);
+        const int mblocks = cdiv(rows * nq * (d / 4), 256);
+        if (d == 64) {
+            hipLaunchKernelGGL((cross_attn_split_kernel<T, 64>), grid, dim3(256), lds, s, qpart, S, M, kv, scratch, item_map, nq, nkv, Lk, cp.chunk, scale);
+            hipLaunchKernelGGL((cross_attn_merge_kernel<T, 64>), dim3(mblocks), dim3(256), 0, s, scratch, out, rows * nq, cp.ranges);
+        } else {
+            hipLaunchKernelGGL((cross_attn_split_kernel<T, 32>), grid, dim3(256), lds, s, qpart, S, M, kv, scratch, item_map, nq, nkv, Lk, cp.chunk, scale);
+            hipLaunchKernelGGL((cross_attn_merge_kernel<T, 32>), dim3(mblocks), dim3(256), 0, s, scratch, out, rows * nq, cp.ranges);
+        }
+    }
+    return (int)hipGetLastError();
+}
+
+// one workgroup per row, one 4-channel chunk per thread, whole waves
+template <typename T>
+int launch_reduce_norm(const float* part, int S, int M, const T* res, const T* bias, T* xo, const T* nw, T* y, int H, float eps, hipStream_t s) {
+    if (H % 4 || H < 4 || H > 4096 || S < 1 || S > 8) return SA_ERR_UNSUPPORTED;
+    const int threads = std::min(1024, ((H / 4 + 63) / 64) * 64);
+    hipLaunchKernelGGL(splitk_residual_adetr_norm_kernel<T>, dim3(M), dim3(threads), 0, s, part, S, M, res, bias, xo, nw, y, H, eps);
+    return (int)hipGetLastError();
+}
+
+// one workgroup per (row, kv head); the prompt's rotated keys and its values sit in LDS as fp32
+template <typename T>
+int launch_prefill_attn(const T* qkv, T* out, T* kc, T* vc, const float2* rope_cs, int B, int Tn, int nq, int nkv, int d, int Tmax, float scale,
+                        hipStream_t s) {
+    if ((d != 64 && d != 32) || nq % nkv || Tn < 1 || Tn > Tmax) return SA_ERR_UNSUPPORTED;
+    const size_t lds = (size_t)2 * Tn * d * sizeof(float);
+    if (lds > 64 * 1024 - 512) return SA_ERR_UNSUPPORTED;
+    if (d == 64) hipLaunchKernelGGL((adetr_prefill_attn_kernel<T, 64>), dim3(B, nkv), dim3(256), lds, s, qkv, out, kc, vc, rope_cs, Tn, nq, nkv, Tmax, scale);
+    else hipLaunchKernelGGL((adetr_prefill_attn_kernel<T, 32>), dim3(B, nkv), dim3(256), lds, s, qkv, out, kc, vc, rope_cs, Tn, nq, nkv, Tmax, scale);
+    return (int)hipGetLastError();
+}
+
+// one workgroup per token row; tabs = 17 device pointers (layout: 14 box tables + label; table recognition: + category, merge, colspan)
+template <typename T>
+int launch_embed(int family, const int* tokens, const T* const* tabs, T* x, int rows, int Hd, int box_embed, int bbox_size, int vocab, int label_count,
+                 int category_count, int merge_count, hipStream_t s) {
+    if (family == SA_FAMILY_TABLE)
+        hipLaunchKernelGGL(table_embed_kernel<T>, dim3(rows), dim3(256), 0, s, tokens, tabs, x, Hd, box_embed, bbox_size, vocab, category_count, merge_count);
+    else
+        hipLaunchKernelGGL(box_embed_kernel<T>, dim3(rows), dim3(256), 0, s, tokens, tabs, x, Hd, bbox_size, vocab, label_count);
+    return (int)hipGetLastError();
+}
+
+// the heads without the fed-back token (layout_heads_kernel<T, false>): one workgroup per row, the row in LDS as fp32
+template <typename T>
+int launch_heads(const T* x, long ldx, const T* fnorm_w, const T* ln_w, const T* ln_b, const T* lm_w, const T* bb_w, const T* bb_b, float* cls,
+                 float* box, int B, int Hd, int label_count, float rms_eps, float ln_eps, hipStream_t s) {
+    if (Hd % 4 || (size_t)Hd * 4 > 64 * 1024 - 512) return SA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL((layout_heads_kernel<T, false>), dim3(B), dim3(256), (size_t)Hd * 4, s, x, fnorm_w, ln_w, ln_b, lm_w, bb_w, bb_b, cls, box, Hd,
+                       label_count, rms_eps, ln_eps, ldx);
+    return (int)hipGetLastError();
+}
+
+}  // namespace lay
+
 template <typename T>
 struct LayoutModel : LayoutBase {
     surya_layout_config c;
@@ -71,7 +261,7 @@ struct LayoutModel : LayoutBase {
     float* cross_scratch;                        // [B][nq][ranges][hd + 2] partial cross-attention records
     static constexpr int MAX_PROMPT = 64;        // tokens of a decoder prompt that prefill() takes in one pass
     size_t enc_mlp_bytes = 0, enc_qkv_bytes = 0; // sizes of the encoder workspaces prefill() borrows between two encodes
-    int cross_ranges = 1, cross_chunk = 0;
+    int cross_ranges = 1;                        // key ranges of the fp32 cross attention (lay::cross_plan): sizes its scratch
     int* cross_map_dev = nullptr;                // [max_batch] decoder row -> encoded image whose K / V it cross-attends
     int batch_active = 0;                        // decoder rows of the current decode (encode: = batch; select: any re-batching)
     float2* rope_cs;
@@ -119,7 +309,7 @@ struct LayoutModel : LayoutBase {
         const size_t o_qkv = take(win_elems * 3 * sizeof(T)), o_att = take(win_elems * sizeof(T)), o_mlp = take(rows0 * 4 * E * sizeof(T));
         enc_qkv_bytes = win_elems * 3 * sizeof(T); enc_mlp_bytes = rows0 * 4 * E * sizeof(T);
         const size_t o_ckv = take((size_t)c.dec_layers * B * Lk * 2 * kv * sizeof(T));
-        Lkp = (Lk + 31) & ~31;
+        Lkp = lay::cross_plan(Lk).Lkp;
         const size_t o_cvt = take((size_t)c.dec_layers * B * kv * Lkp * sizeof(T));
         const size_t kv_elems = (size_t)c.dec_layers * B * c.dec_kv_heads * c.max_boxes * hd();
         const size_t o_k = take(kv_elems * sizeof(T)), o_v = take(kv_elems * sizeof(T));
@@ -127,8 +317,7 @@ struct LayoutModel : LayoutBase {
         const size_t o_da = take(B * qd * sizeof(T)), o_dr = take(B * Hd * sizeof(T)), o_dm = take(B * I * sizeof(T));
         const size_t o_part = take((size_t)8 * B * std::max(qkv_d, Hd) * sizeof(float));
         const size_t o_rope = take((size_t)c.max_boxes * (hd() / 2) * sizeof(float2));
-        cross_chunk = (Lk + std::max(1, std::min(8, Lk / 128)) - 1) / std::max(1, std::min(8, Lk / 128));     // >= 128 keys per range
-        cross_ranges = (Lk + cross_chunk - 1) / cross_chunk;
+        cross_ranges = lay::cross_plan(Lk).ranges;                   // >= 128 keys per range
         const size_t o_cscr = take(B * c.dec_heads * cross_ranges * (hd() + 2) * sizeof(float)), o_cmap = take(B * sizeof(int));
         const size_t o_boxes = take(B * 10 * sizeof(int)), o_slots = take(B * sizeof(int)), o_len = take(B * sizeof(int));
         const size_t o_cls = take(B * c.label_count * sizeof(float)), o_box = take(B * 6 * sizeof(float));
@@ -159,33 +348,20 @@ struct LayoutModel : LayoutBase {
         cross_scratch = (float*)(b + o_cscr); cross_map_dev = (int*)(b + o_cmap);
         boxes_dev = (int*)(b + o_boxes); slots_dev = (int*)(b + o_slots); len_dev = (int*)(b + o_len);
         cls_dev = (float*)(b + o_cls); box_dev = (float*)(b + o_box); tabs_dev = (const T**)(b + o_tabs);
-        {   // window-order row of every token, per stage and shift (window_partition after F.pad to whole windows and torch.roll(-shift),
-            // donut/encoder.py:588-636), and the window-order rows nothing maps to (the padding)
+        {   // window-order row of every token, per stage and shift, and the window-order rows nothing maps to (lay::window_tables)
             int h = gh(), wd = gw();
             for (int s = 0; s < c.n_stages; ++s) {
                 const int ws = c.window;
                 if ((h % 2 || wd % 2) && s + 1 < c.n_stages) return SA_ERR_SHAPE;      // (the reference's sin-cos table is sized for grid >> stage)
-                if (std::min(h, wd) < ws) return SA_ERR_UNSUPPORTED;       // a map below the window: the reference's [64][64] bias would not fit either
-                const bool part_ok = std::min(h, wd) > ws;                 // else no shift (:551-559)
-                const int hp = (h + ws - 1) / ws * ws, wp = (wd + ws - 1) / ws * ws;
-                grid_hp.push_back(hp); grid_wp.push_back(wp);
                 for (int sh = 0; sh < 2; ++sh) {
-                    const int shift = (sh && part_ok) ? ws / 2 : 0;
-                    std::vector<int> p((size_t)h * wd);
-                    std::vector<char> hit((size_t)hp * wp, 0);
-                    for (int y = 0; y < h; ++y)
-                        for (int xx = 0; xx < wd; ++xx) {
-                            const int ys = ((y - shift) % hp + hp) % hp, xs = ((xx - shift) % wp + wp) % wp;
-                            const int r = ((ys / ws) * (wp / ws) + xs / ws) * ws * ws + (ys % ws) * ws + xs % ws;
-                            p[(size_t)y * wd + xx] = r;
-                            hit[r] = 1;
-                        }
+                    std::vector<int> p, pads;
+                    int hp = 0, wp = 0, shift = 0;
+                    const int trc = lay::window_tables(h, wd, ws, sh ? ws / 2 : 0, p, pads, hp, wp, shift);
+                    if (trc) return trc;
+                    if (!sh) { grid_hp.push_back(hp); grid_wp.push_back(wp); }
                     int* d = (int*)(b + o_perm[2 * s + sh]);
                     SA_HIP(hipMemcpy(d, p.data(), p.size() * sizeof(int), hipMemcpyHostToDevice));
                     perm.push_back(d);
-                    std::vector<int> pads;
-                    for (int r = 0; r < hp * wp; ++r)
-                        if (!hit[r]) pads.push_back(r);
                     int* pd = nullptr;
                     if (!pads.empty()) {
                         SA_HIP(hipMalloc((void**)&pd, pads.size() * sizeof(int)));
@@ -229,23 +405,7 @@ struct LayoutModel : LayoutBase {
         return launch_gemm<T, T, EPI>(a, s);
     }
     int layernorm(const T* in, int wi, int bi, T* out, const int* pm, long rows, int rpi, int C, float eps, hipStream_t s, int rpi_out = 0) {
-        if constexpr (std::is_same<T, bf16_t>::value) {      // rows held in registers by C / 8 lanes (layout_kernels.h); 16-byte aligned rows
-            if (rows > 0 && tuning().lay_ln) {
-#define SA_LN_ROWS(LPR, NV)                                                                                                              \
-    {                                                                                                                                    \
-        hipLaunchKernelGGL((lay::layernorm_rows_bf16_kernel<LPR, NV>), dim3((unsigned)cdivl(rows, 256 / LPR)), dim3(256), 0, s, in, W(wi), W(bi), \
-                           out, pm, rows, rpi, eps, rpi_out);                                                                            \
-        return (int)hipGetLastError();                                                                                                   \
-    }
-                if (C == 128) SA_LN_ROWS(16, 1)
-                if (C == 256) SA_LN_ROWS(32, 1)
-                if (C == 512) SA_LN_ROWS(64, 1)
-                if (C == 1024) SA_LN_ROWS(64, 2)
-#undef SA_LN_ROWS
-            }
-        }
-        hipLaunchKernelGGL(lay::layernorm_kernel<T>, dim3((unsigned)cdivl(rows, 4)), dim3(256), 0, s, in, W(wi), W(bi), out, pm, rows, rpi, C, eps, rpi_out);
-        return (int)hipGetLastError();
+        return lay::launch_layernorm<T>(in, W(wi), W(bi), out, pm, rows, rpi, C, eps, rpi_out, s);
     }
 
     int encode(const float* pixels, int B, hipStream_t s) override {
@@ -254,9 +414,7 @@ struct LayoutModel : LayoutBase {
         int h = gh(), wd = gw(), dim = c.embed_dim;
         long rows = (long)B * h * wd;
         {
-            const long total = rows * 64;
-            hipLaunchKernelGGL(lay::patchify_kernel<T>, dim3((unsigned)cdivl(total, 256)), dim3(256), 0, s, pixels, patch_rows, B, 3, c.img_h,
-                               c.img_w, c.patch, 64);
+            if ((rc = lay::launch_patchify<T>(pixels, patch_rows, B, 3, c.img_h, c.img_w, c.patch, 64, s))) return rc;
             if ((rc = gemm<EPI_BIAS>(patch_rows, 64, W(SA_LW_PATCH_W), 64, hbuf, dim, W(SA_LW_PATCH_B), nullptr, 0, (int)rows, dim, 64, s))) return rc;
             if ((rc = layernorm(hbuf, SA_LW_EMB_LN_W, SA_LW_EMB_LN_B, x, nullptr, rows, h * wd, dim, 1e-5f, s))) return rc;
         }
@@ -264,10 +422,7 @@ struct LayoutModel : LayoutBase {
             const int sb = stage_base[st], nh = c.heads[st], nkv = c.kv_heads[st], ws = c.window;
             if (dim / nh != 32) return SA_ERR_UNSUPPORTED;
             const int rpi = h * wd;
-            {
-                const long n4 = rows * (dim / 4);
-                hipLaunchKernelGGL(lay::add_rows_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, x, W(sb + SA_LS_SINCOS), rows, rpi, dim);
-            }
+            if ((rc = lay::launch_add_rows<T>(x, W(sb + SA_LS_SINCOS), rows, rpi, dim, s))) return rc;
             const int qkv_n = (nh + 2 * nkv) * 32;
             for (int bi = 0; bi < c.depths[st]; ++bi) {
                 const int wb = sb + SA_LS_COUNT + bi * SA_LB_COUNT;
@@ -276,26 +431,16 @@ struct LayoutModel : LayoutBase {
                 const int hp = grid_hp[st], wp = grid_wp[st], rpw = hp * wp;                  // the grid in whole windows
                 const long rows_w = (long)B * rpw;
                 const int pi = 2 * st + (shifted ? 1 : 0);
-                if (pad_count[pi]) {
-                    const long n4 = (long)B * pad_count[pi] * (dim / 4);
-                    hipLaunchKernelGGL(lay::zero_rows_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, hbuf, pad_rows[pi], pad_count[pi], B, rpw, dim);
-                }
+                if (pad_count[pi] && (rc = lay::launch_zero_rows<T>(hbuf, pad_rows[pi], pad_count[pi], B, rpw, dim, s))) return rc;
                 if ((rc = layernorm(x, wb + SA_LB_LN1_W, wb + SA_LB_LN1_B, hbuf, pm, rows, rpi, dim, c.enc_eps, s, rpw))) return rc;
                 if ((rc = gemm<EPI_BIAS>(hbuf, dim, W(wb + SA_LB_QKV_W), dim, qkv, qkv_n, W(wb + SA_LB_QKV_B), nullptr, 0, (int)rows_w, qkv_n, dim, s)))
                     return rc;
                 const int nwx = wp / ws, nwy = hp / ws;
-                if constexpr (std::is_same<T, bf16_t>::value)
-                    hipLaunchKernelGGL(lay::swin_window_attn_mfma_kernel, dim3((unsigned)(rows_w / 64), nh), dim3(128), 0, s, qkv,
-                                       reinterpret_cast<const float*>(w[wb + SA_LB_RELBIAS]), att, nh, nkv, nwx, nwy, shifted ? ws / 2 : 0, ws);
-                else
-                    hipLaunchKernelGGL(lay::swin_window_attn_kernel<T>, dim3((unsigned)(rows_w / 64), nh), dim3(256), 0, s, qkv,
-                                       reinterpret_cast<const float*>(w[wb + SA_LB_RELBIAS]), att, nh, nkv, nwx, nwy, shifted ? ws / 2 : 0, ws);
+                if ((rc = lay::launch_window_attn<T>(qkv, reinterpret_cast<const float*>(w[wb + SA_LB_RELBIAS]), att, rows_w / 64, nh, nkv, nwx, nwy,
+                                                     shifted ? ws / 2 : 0, ws, s))) return rc;
                 if ((rc = gemm<EPI_BIAS>(att, dim, W(wb + SA_LB_PROJ_W), dim, hbuf, dim, W(wb + SA_LB_PROJ_B), nullptr, 0, (int)rows_w, dim, dim, s)))
                     return rc;
-                {
-                    const long n4 = rows * (dim / 4);
-                    hipLaunchKernelGGL(lay::gather_add_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, x, hbuf, pm, rows, rpi, dim, rpw);
-                }
+                if ((rc = lay::launch_gather_add<T>(x, hbuf, pm, rows, rpi, dim, rpw, s))) return rc;
                 if ((rc = layernorm(x, wb + SA_LB_LN2_W, wb + SA_LB_LN2_B, hbuf, nullptr, rows, rpi, dim, c.enc_eps, s))) return rc;
                 if ((rc = gemm<EPI_GELU>(hbuf, dim, W(wb + SA_LB_FC1_W), dim, mlp, 4 * dim, W(wb + SA_LB_FC1_B), nullptr, 0, (int)rows, 4 * dim, dim, s)))
                     return rc;
@@ -304,17 +449,13 @@ struct LayoutModel : LayoutBase {
             }
             if (st + 1 < c.n_stages) {
                 const long orows = rows / 4;
-                hipLaunchKernelGGL(lay::merge_ln_kernel<T>, dim3((unsigned)cdivl(orows, 4)), dim3(256), 0, s, x, W(sb + SA_LS_MERGE_NORM_W),
-                                   W(sb + SA_LS_MERGE_NORM_B), mlp, B, h, wd, dim, 1e-5f);
+                if ((rc = lay::launch_merge_ln<T>(x, W(sb + SA_LS_MERGE_NORM_W), W(sb + SA_LS_MERGE_NORM_B), mlp, B, h, wd, dim, 1e-5f, s))) return rc;
                 if ((rc = gemm<EPI_BIAS>(mlp, 4 * dim, W(sb + SA_LS_MERGE_RED_W), 4 * dim, x, 2 * dim, nullptr, nullptr, 0, (int)orows, 2 * dim,
                                          4 * dim, s))) return rc;
                 rows = orows; h /= 2; wd /= 2; dim *= 2;
             }
         }
-        {
-            const long n4 = rows * (dim / 4);
-            hipLaunchKernelGGL(lay::add_rows_kernel<T>, dim3((unsigned)cdivl(n4, 256)), dim3(256), 0, s, x, W(SA_LW_POS_EMB), rows, h * wd, dim);
-        }
+        if ((rc = lay::launch_add_rows<T>(x, W(SA_LW_POS_EMB), rows, h * wd, dim, s))) return rc;
         enc_rows_final = (int)rows;
         batch_encoded = batch_active = B;
         fed_ready = false;
@@ -326,8 +467,7 @@ struct LayoutModel : LayoutBase {
             T* dst = ckv + (size_t)l * c.max_batch * Lk * kv2;
             if ((rc = gemm<EPI_BIAS>(x, dim, W(lb + SA_LD_CKV_W), dim, dst, kv2, nullptr, nullptr, 0, (int)rows, kv2, dim, s))) return rc;
             if constexpr (std::is_same<T, bf16_t>::value)
-                hipLaunchKernelGGL(lay::transpose_cross_v_kernel<T>, dim3(64, B), dim3(256), 0, s, dst, cvT + (size_t)l * c.max_batch * kvd() * Lkp, Lk, Lkp,
-                                   c.dec_kv_heads, hd());
+                if ((rc = lay::launch_transpose_cross_v<T>(dst, cvT + (size_t)l * c.max_batch * kvd() * Lkp, B, Lk, c.dec_kv_heads, hd(), s))) return rc;
         }
         return (int)hipGetLastError();
     }
@@ -383,53 +523,22 @@ struct LayoutModel : LayoutBase {
         memcpy(hb, boxes, (size_t)rows * tokw() * sizeof(int));
         SA_HIP(hipMemcpyAsync(pbox, hb, (size_t)rows * tokw() * sizeof(int), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(lay::expand_map_kernel, dim3(cdiv(rows, 256)), dim3(256), 0, s, cross_map_dev, pmap, B, Tn);
-        if (c.family == SA_FAMILY_TABLE)
-            hipLaunchKernelGGL(lay::table_embed_kernel<T>, dim3(rows), dim3(256), 0, s, pbox, tabs_dev, px, Hd, c.box_embed, c.bbox_size, c.vocab,
-                               c.category_count, c.merge_count);
-        else
-            hipLaunchKernelGGL(lay::box_embed_kernel<T>, dim3(rows), dim3(256), 0, s, pbox, tabs_dev, px, Hd, c.bbox_size, c.vocab, c.label_count);
+        if ((rc = lay::launch_embed<T>(c.family, pbox, tabs_dev, px, rows, Hd, c.box_embed, c.bbox_size, c.vocab, c.label_count, c.category_count,
+                                       c.merge_count, s))) return rc;
         const float scale = 1.0f / sqrtf((float)d);
         const size_t layer_kv = (size_t)c.max_batch * nkv * c.max_boxes * d;
-        auto norm = [&](const T* in, int wi, T* outp) {
-            hipLaunchKernelGGL(lay::adetr_rmsnorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, in, W(wi), outp, rows, Hd, c.rms_eps);
-        };
+        auto norm = [&](const T* in, int wi, T* outp) { (void)lay::launch_rmsnorm<T>(in, W(wi), outp, rows, Hd, c.rms_eps, s); };
         for (int l = 0; l < c.dec_layers; ++l) {
             const int lb = dec_base + l * SA_LD_COUNT;
             norm(px, lb + SA_LD_CNORM, ph);
             if ((rc = gemm<EPI_BIAS>(ph, Hd, W(lb + SA_LD_CQ_W), Hd, pq, Hd, nullptr, nullptr, 0, rows, Hd, Hd, s))) return rc;
-            {
-                const T* kvp = ckv + (size_t)l * c.max_batch * Lk * 2 * kv;
-                const size_t lds = ((size_t)G * cross_chunk + (size_t)G * d + 1024) * sizeof(float);
-                dim3 grid(rows, nkv, cross_ranges);
-                const int mblocks = cdiv(rows * nq * (d / 4), 256);
-                if constexpr (std::is_same<T, bf16_t>::value) {
-                    const T* vtp = cvT + (size_t)l * c.max_batch * kv * Lkp;
-                    if (d == 64) hipLaunchKernelGGL((lay::cross_attn_mfma_kernel<64>), dim3(rows, nkv), dim3(512), 0, s, reinterpret_cast<const float*>(pq), 0, rows,
-                                                    kvp, vtp, pat, pmap, nq, nkv, Lk, Lkp, scale);
-                    else hipLaunchKernelGGL((lay::cross_attn_mfma_kernel<32>), dim3(rows, nkv), dim3(512), 0, s, reinterpret_cast<const float*>(pq), 0, rows,
-                                            kvp, vtp, pat, pmap, nq, nkv, Lk, Lkp, scale);
-                } else if (d == 64) {
-                    hipLaunchKernelGGL((lay::cross_attn_split_kernel<T, 64>), grid, dim3(256), lds, s, reinterpret_cast<const float*>(pq), 0, rows, kvp, pscr,
-                                       pmap, nq, nkv, Lk, cross_chunk, scale);
-                    hipLaunchKernelGGL((lay::cross_attn_merge_kernel<T, 64>), dim3(mblocks), dim3(256), 0, s, pscr, pat, rows * nq, cross_ranges);
-                } else {
-                    hipLaunchKernelGGL((lay::cross_attn_split_kernel<T, 32>), grid, dim3(256), lds, s, reinterpret_cast<const float*>(pq), 0, rows, kvp, pscr,
-                                       pmap, nq, nkv, Lk, cross_chunk, scale);
-                    hipLaunchKernelGGL((lay::cross_attn_merge_kernel<T, 32>), dim3(mblocks), dim3(256), 0, s, pscr, pat, rows * nq, cross_ranges);
-                }
-            }
+            if ((rc = lay::launch_cross_attn<T>(reinterpret_cast<const float*>(pq), 0, rows, ckv + (size_t)l * c.max_batch * Lk * 2 * kv,
+                                                cvT + (size_t)l * c.max_batch * kv * Lkp, pscr, pat, pmap, rows, nq, nkv, d, Lk, scale, s))) return rc;
             if ((rc = gemm<EPI_RESIDUAL>(pat, Hd, W(lb + SA_LD_CO_W), Hd, prs, Hd, W(lb + SA_LD_CO_B), px, Hd, rows, Hd, Hd, s))) return rc;
             norm(prs, lb + SA_LD_TNORM, ph);
             if ((rc = gemm<EPI_BIAS>(ph, Hd, W(lb + SA_LD_QKV_W), Hd, pqkv, qkv_d, nullptr, nullptr, 0, rows, qkv_d, Hd, s))) return rc;
-            {
-                T* kc = kcache + (size_t)l * layer_kv;
-                T* vc = vcache + (size_t)l * layer_kv;
-                const size_t lds = (size_t)2 * Tn * d * sizeof(float);
-                if (d == 64) hipLaunchKernelGGL((lay::adetr_prefill_attn_kernel<T, 64>), dim3(B, nkv), dim3(256), lds, s, pqkv, pat, kc, vc, rope_cs, Tn, nq, nkv,
-                                                c.max_boxes, scale);
-                else hipLaunchKernelGGL((lay::adetr_prefill_attn_kernel<T, 32>), dim3(B, nkv), dim3(256), lds, s, pqkv, pat, kc, vc, rope_cs, Tn, nq, nkv,
-                                        c.max_boxes, scale);
-            }
+            if ((rc = lay::launch_prefill_attn<T>(pqkv, pat, kcache + (size_t)l * layer_kv, vcache + (size_t)l * layer_kv, rope_cs, B, Tn, nq, nkv, d,
+                                                  c.max_boxes, scale, s))) return rc;
             // layout: + RAW layer input (double residual flow); table_rec: + the cross-attention output
             if ((rc = gemm<EPI_RESIDUAL>(pat, Hd, W(lb + SA_LD_TO_W), Hd, prs, Hd, W(lb + SA_LD_TO_B), c.family == SA_FAMILY_TABLE ? prs : px, Hd, rows, Hd,
                                          Hd, s))) return rc;
@@ -437,10 +546,8 @@ struct LayoutModel : LayoutBase {
             if ((rc = gemm<EPI_GEGLU>(ph, Hd, W(lb + SA_LD_GU_W), Hd, pml, I, nullptr, nullptr, 0, rows, 2 * I, Hd, s))) return rc;
             if ((rc = gemm<EPI_RESIDUAL>(pml, I, W(lb + SA_LD_DOWN_W), I, px, Hd, nullptr, prs, Hd, rows, Hd, I, s))) return rc;
         }
-        hipLaunchKernelGGL((lay::layout_heads_kernel<T, false>), dim3(B), dim3(256), (size_t)Hd * 4, s, px + (size_t)(Tn - 1) * Hd, W(SA_LW_DEC_FNORM),
-                           W(SA_LW_DEC_LN_W), W(SA_LW_DEC_LN_B), W(SA_LW_DEC_LM_W), W(SA_LW_DEC_BB_W), W(SA_LW_DEC_BB_B), cls_dev, box_dev, Hd,
-                           c.label_count, c.rms_eps, c.ln_eps, (long)Tn * Hd);
-        if ((rc = (int)hipGetLastError())) return rc;
+        if ((rc = lay::launch_heads<T>(px + (size_t)(Tn - 1) * Hd, (long)Tn * Hd, W(SA_LW_DEC_FNORM), W(SA_LW_DEC_LN_W), W(SA_LW_DEC_LN_B), W(SA_LW_DEC_LM_W),
+                                       W(SA_LW_DEC_BB_W), W(SA_LW_DEC_BB_B), cls_dev, box_dev, B, Hd, c.label_count, c.rms_eps, c.ln_eps, s))) return rc;
         float* hc = reinterpret_cast<float*>(pinned + 256 + (size_t)c.max_batch * MAX_PROMPT * 10 * sizeof(int));
         float* hbx = hc + (size_t)c.max_batch * c.label_count;
         SA_HIP(hipMemcpyAsync(hc, cls_dev, (size_t)B * c.label_count * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -460,13 +567,10 @@ struct LayoutModel : LayoutBase {
         memcpy(hb, boxes, (size_t)B * tokw() * sizeof(int));
         SA_HIP(hipMemcpyAsync(boxes_dev, hb, (size_t)B * tokw() * sizeof(int), hipMemcpyHostToDevice, s));
         hipLaunchKernelGGL(fill_int_kernel, dim3(cdiv(B, 64)), dim3(64), 0, s, len_dev, pos, B);
-        if (c.family == SA_FAMILY_TABLE)
-            hipLaunchKernelGGL(lay::table_embed_kernel<T>, dim3(B), dim3(256), 0, s, boxes_dev, tabs_dev, dx, Hd, c.box_embed, c.bbox_size, c.vocab,
-                               c.category_count, c.merge_count);
-        else
-            hipLaunchKernelGGL(lay::box_embed_kernel<T>, dim3(B), dim3(256), 0, s, boxes_dev, tabs_dev, dx, Hd, c.bbox_size, c.vocab, c.label_count);
-        hipLaunchKernelGGL(lay::adetr_rmsnorm_kernel<T>, dim3(cdiv(B, 4)), dim3(256), 0, s, dx, W(dec_base + SA_LD_CNORM), dh, B, Hd, c.rms_eps);
-        return (int)hipGetLastError();
+        int rc;
+        if ((rc = lay::launch_embed<T>(c.family, boxes_dev, tabs_dev, dx, B, Hd, c.box_embed, c.bbox_size, c.vocab, c.label_count, c.category_count,
+                                       c.merge_count, s))) return rc;
+        return lay::launch_rmsnorm<T>(dx, W(dec_base + SA_LD_CNORM), dh, B, Hd, c.rms_eps, s);
     }
 
     // The decoder layers of one step for B rows: dx = the token embeddings, dh = cross_pre_norm(dx) of layer 0, len_dev = the cache
@@ -488,46 +592,17 @@ struct LayoutModel : LayoutBase {
             return r;
         };
         auto reduce_norm = [&](int S, const T* res, const T* bias, T* xo, const T* nw) {
-            const int threads = std::min(1024, ((Hd / 4 + 63) / 64) * 64);
-            hipLaunchKernelGGL(lay::splitk_residual_adetr_norm_kernel<T>, dim3(B), dim3(threads), 0, s, part, S, B, res, bias, xo, nw, dh, Hd,
-                               c.rms_eps);
+            return lay::launch_reduce_norm<T>(part, S, B, res, bias, xo, nw, dh, Hd, c.rms_eps, s);
         };
-        if (Hd % 4 || Hd > 4096) return SA_ERR_UNSUPPORTED;
         for (int l = 0; l < c.dec_layers; ++l) {
             const int lb = dec_base + l * SA_LD_COUNT;
             int S = 1;
             // cross attention (double residual flow, adetr/decoder.py:430-457): cross = o(attn(norm(x))) + x; dh = norm(x) on entry
             if ((rc = splitk(dh, Hd, W(lb + SA_LD_CQ_W), Hd, Hd, S))) return rc;
-            {
-                const T* kvp = ckv + (size_t)l * c.max_batch * Lk * 2 * kv;
-                const int G = nq / nkv;
-                const size_t lds = ((size_t)G * cross_chunk + (size_t)G * d + 1024) * sizeof(float);
-                dim3 grid(B, nkv, cross_ranges);
-                if (G > 8 || G * (d / 4) > 256) return SA_ERR_UNSUPPORTED;
-                const int mblocks = cdiv(B * nq * (d / 4), 256);
-                bool done = false;
-                if constexpr (std::is_same<T, bf16_t>::value) {          // matrix-core kernel on the transposed values (layout_kernels.h)
-                    const T* vtp = cvT + (size_t)l * c.max_batch * kv * Lkp;
-                    done = true;
-                    if (d == 64) hipLaunchKernelGGL((lay::cross_attn_mfma_kernel<64>), dim3(B, nkv), dim3(512), 0, s, part, S, B, kvp, vtp, dattn, cross_map_dev,
-                                                    nq, nkv, Lk, Lkp, scale);
-                    else if (d == 32) hipLaunchKernelGGL((lay::cross_attn_mfma_kernel<32>), dim3(B, nkv), dim3(512), 0, s, part, S, B, kvp, vtp, dattn,
-                                                         cross_map_dev, nq, nkv, Lk, Lkp, scale);
-                    else done = false;
-                }
-                if (done) {
-                } else if (d == 64) {
-                    hipLaunchKernelGGL((lay::cross_attn_split_kernel<T, 64>), grid, dim3(256), lds, s, part, S, B, kvp, cross_scratch, cross_map_dev, nq, nkv, Lk,
-                                       cross_chunk, scale);
-                    hipLaunchKernelGGL((lay::cross_attn_merge_kernel<T, 64>), dim3(mblocks), dim3(256), 0, s, cross_scratch, dattn, B * nq, cross_ranges);
-                } else if (d == 32) {
-                    hipLaunchKernelGGL((lay::cross_attn_split_kernel<T, 32>), grid, dim3(256), lds, s, part, S, B, kvp, cross_scratch, cross_map_dev, nq, nkv, Lk,
-                                       cross_chunk, scale);
-                    hipLaunchKernelGGL((lay::cross_attn_merge_kernel<T, 32>), dim3(mblocks), dim3(256), 0, s, cross_scratch, dattn, B * nq, cross_ranges);
-                } else return SA_ERR_UNSUPPORTED;
-            }
+            if ((rc = lay::launch_cross_attn<T>(part, S, B, ckv + (size_t)l * c.max_batch * Lk * 2 * kv, cvT + (size_t)l * c.max_batch * kv * Lkp,
+                                                cross_scratch, dattn, cross_map_dev, B, nq, nkv, d, Lk, scale, s))) return rc;
             if ((rc = splitk(dattn, Hd, W(lb + SA_LD_CO_W), Hd, Hd, S))) return rc;
-            reduce_norm(S, dx, W(lb + SA_LD_CO_B), dres, W(lb + SA_LD_TNORM));              // dres = cross, dh = temporal_pre_norm(cross)
+            if ((rc = reduce_norm(S, dx, W(lb + SA_LD_CO_B), dres, W(lb + SA_LD_TNORM)))) return rc;            // dres = cross, dh = temporal_pre_norm(cross)
             // self attention on norm(cross); residual = o(attn) + RAW layer input
             {
                 GemmArgs<T, T> a{dh, Hd, W(lb + SA_LD_QKV_W), Hd, nullptr, 0, nullptr, nullptr, 0, B, qkv_d, Hd, 1, part};
@@ -565,11 +640,11 @@ struct LayoutModel : LayoutBase {
             }
             if ((rc = splitk(dattn, Hd, W(lb + SA_LD_TO_W), Hd, Hd, S))) return rc;
             // layout: + RAW layer input (double residual flow); table_rec: + the cross-attention output (adetr/decoder.py:395-417)
-            reduce_norm(S, c.family == SA_FAMILY_TABLE ? dres : dx, W(lb + SA_LD_TO_B), dres, W(lb + SA_LD_MNORM));   // dh = channel_pre_norm(residual)
+            if ((rc = reduce_norm(S, c.family == SA_FAMILY_TABLE ? dres : dx, W(lb + SA_LD_TO_B), dres, W(lb + SA_LD_MNORM)))) return rc; // dh = channel_pre_norm(residual)
             // MLP: x = down(gelu_tanh(gate(n)) * up(n)) + residual; dh <- the next layer's cross_pre_norm(x)
             if ((rc = gemm<EPI_GEGLU>(dh, Hd, W(lb + SA_LD_GU_W), Hd, dmlp, I, nullptr, nullptr, 0, B, 2 * I, Hd, s))) return rc;
             if ((rc = splitk(dmlp, I, W(lb + SA_LD_DOWN_W), Hd, I, S))) return rc;
-            reduce_norm(S, dres, nullptr, dx, l + 1 < c.dec_layers ? W(lb + SA_LD_COUNT + SA_LD_CNORM) : nullptr);
+            if ((rc = reduce_norm(S, dres, nullptr, dx, l + 1 < c.dec_layers ? W(lb + SA_LD_COUNT + SA_LD_CNORM) : nullptr))) return rc;
         }
         return (int)hipGetLastError();
     }
@@ -582,10 +657,8 @@ struct LayoutModel : LayoutBase {
         fed_ready = false;
         if ((rc = start_step(boxes, B, pos, s))) return rc;
         if ((rc = decode_layers(B, s))) return rc;
-        hipLaunchKernelGGL((lay::layout_heads_kernel<T, false>), dim3(B), dim3(256), (size_t)Hd * 4, s, dx, W(SA_LW_DEC_FNORM), W(SA_LW_DEC_LN_W),
-                           W(SA_LW_DEC_LN_B), W(SA_LW_DEC_LM_W), W(SA_LW_DEC_BB_W), W(SA_LW_DEC_BB_B), cls_dev, box_dev, Hd, c.label_count,
-                           c.rms_eps, c.ln_eps, (long)Hd);
-        if ((rc = (int)hipGetLastError())) return rc;
+        if ((rc = lay::launch_heads<T>(dx, (long)Hd, W(SA_LW_DEC_FNORM), W(SA_LW_DEC_LN_W), W(SA_LW_DEC_LN_B), W(SA_LW_DEC_LM_W), W(SA_LW_DEC_BB_W),
+                                       W(SA_LW_DEC_BB_B), cls_dev, box_dev, B, Hd, c.label_count, c.rms_eps, c.ln_eps, s))) return rc;
         float* hc = reinterpret_cast<float*>(pinned + 256 + (size_t)c.max_batch * MAX_PROMPT * 10 * sizeof(int));
         float* hbx = hc + (size_t)c.max_batch * c.label_count;
         SA_HIP(hipMemcpyAsync(hc, cls_dev, (size_t)B * c.label_count * sizeof(float), hipMemcpyDeviceToHost, s));
@@ -762,6 +835,21 @@ struct LayoutModel : LayoutBase {
 
 }  // namespace sa
 
+namespace sa {
+// EPI_GEGLU for surya_op_gemm (rec_model.hip): the ADETR MLP's gate|up GEMM exactly as LayoutModel::gemm<EPI_GEGLU> launches it
+int op_gemm_geglu(int dtype, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int K, hipStream_t s) {
+    if (dtype == SA_DTYPE_F32) {
+        GemmArgs<float, float> a{(const float*)X, ldx, (const float*)W, ldw, (float*)C, ldc, nullptr, nullptr, 0, M, N, K};
+        return launch_gemm<float, float, EPI_GEGLU>(a, s);
+    }
+    if (dtype == SA_DTYPE_BF16) {
+        GemmArgs<bf16_t, bf16_t> a{(const bf16_t*)X, ldx, (const bf16_t*)W, ldw, (bf16_t*)C, ldc, nullptr, nullptr, 0, M, N, K};
+        return launch_gemm<bf16_t, bf16_t, EPI_GEGLU>(a, s);
+    }
+    return SA_ERR_UNSUPPORTED;
+}
+}  // namespace sa
+
 using namespace sa;
 struct surya_layout { std::unique_ptr<LayoutBase> impl; };
 
@@ -849,5 +937,141 @@ int surya_layout_preprocess(const uint8_t* pages, size_t pages_bytes, const void
     return sa::lprep::run(pages, pages_bytes, reinterpret_cast<const sa::lprep::PageDesc*>(descs), n, pixel_stride, mean, std, out_h,
                           out_w, pixel_values, (hipStream_t)stream);
 }
+
+// ------------------------------------------------------------------------------------------------ op level
+// Every kernel of the family alone, through the launch functions LayoutModel calls (sa::lay::launch_*). Caller-owned device memory, enqueue only.
+#define SA_LAY_DT(CALL_F32, CALL_BF16)                 \
+    if (dtype == SA_DTYPE_F32) { typedef float T; return CALL_F32; }     \
+    if (dtype == SA_DTYPE_BF16) { typedef bf16_t T; return CALL_BF16; } \
+    return SA_ERR_UNSUPPORTED;
+#define SA_LAY_BOTH(CALL) SA_LAY_DT(CALL, CALL)
+
+int surya_lay_window_tables(int h, int w, int window, int shift, int32_t* perm, int32_t* pad_rows, int32_t* n_pad, int32_t* padded_hw,
+                            int32_t* shift_used) {
+    std::vector<int> p, pads;
+    int hp = 0, wp = 0, sh = 0;
+    const int rc = lay::window_tables(h, w, window, shift, p, pads, hp, wp, sh);
+    if (rc) return rc;
+    if (perm) memcpy(perm, p.data(), p.size() * sizeof(int));
+    if (pad_rows && !pads.empty()) memcpy(pad_rows, pads.data(), pads.size() * sizeof(int));
+    if (n_pad) *n_pad = (int)pads.size();
+    if (padded_hw) { padded_hw[0] = hp; padded_hw[1] = wp; }
+    if (shift_used) *shift_used = sh;
+    return SA_OK;
+}
+
+int surya_lay_cross_plan(int Lk, int32_t* chunk, int32_t* ranges, int32_t* Lkp) {
+    if (Lk < 1) return SA_ERR_ARG;
+    const lay::CrossPlan cp = lay::cross_plan(Lk);
+    if (chunk) *chunk = cp.chunk;
+    if (ranges) *ranges = cp.ranges;
+    if (Lkp) *Lkp = cp.Lkp;
+    return SA_OK;
+}
+
+int surya_op_lay_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image,
+                           int C, float eps, int rows_per_image_out, void* stream) {
+    if (!x || !w || !b || !y || rows <= 0 || rows_per_image <= 0 || C <= 0 || C % 4) return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_layernorm<T>((const T*)x, (const T*)w, (const T*)b, (T*)y, perm, rows, rows_per_image, C, eps, rows_per_image_out,
+                                         (hipStream_t)stream))
+}
+
+int surya_op_lay_window_attn(int dtype, const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift,
+                             int ws, void* stream) {
+    if (!qkv || !bias || !out || windows <= 0 || nh <= 0 || nkv <= 0 || nwx <= 0 || nwy <= 0 || shift < 0) return SA_ERR_ARG;
+    if (ws != 8 || shift >= ws) return SA_ERR_UNSUPPORTED;           // 64 tokens per window, head dim 32
+    SA_LAY_BOTH(lay::launch_window_attn<T>((const T*)qkv, bias, (T*)out, windows, nh, nkv, nwx, nwy, shift, ws, (hipStream_t)stream))
+}
+
+int surya_op_lay_merge_ln(int dtype, const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream) {
+    if (!x || !w || !b || !y || B <= 0 || H < 2 || W < 2 || C <= 0) return SA_ERR_ARG;
+    if (H % 2 || W % 2 || C % 4) return SA_ERR_SHAPE;
+    SA_LAY_BOTH(lay::launch_merge_ln<T>((const T*)x, (const T*)w, (const T*)b, (T*)y, B, H, W, C, eps, (hipStream_t)stream))
+}
+
+int surya_op_lay_rows(int dtype, int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream) {
+    if (!dst || !dims) return SA_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kind) {
+        case SA_LAY_PATCHIFY: {
+            const int B = dims[0], Cc = dims[1], H = dims[2], Wd = dims[3], P = dims[4], Kpad = dims[5];
+            if (!src || B <= 0 || Cc <= 0 || P <= 0 || H <= 0 || Wd <= 0 || Kpad < Cc * P * P) return SA_ERR_ARG;
+            if (H % P || Wd % P) return SA_ERR_SHAPE;
+            SA_LAY_BOTH(lay::launch_patchify<T>((const float*)src, (T*)dst, B, Cc, H, Wd, P, Kpad, s))
+        }
+        case SA_LAY_ADD_ROWS: {
+            if (!src || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0 || dims[2] % 4) return SA_ERR_ARG;
+            SA_LAY_BOTH(lay::launch_add_rows<T>((T*)dst, (const T*)src, dims[0], dims[1], dims[2], s))
+        }
+        case SA_LAY_ZERO_ROWS: {
+            if (!index || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0 || dims[3] <= 0 || dims[3] % 4) return SA_ERR_ARG;
+            SA_LAY_BOTH(lay::launch_zero_rows<T>((T*)dst, index, dims[1], dims[0], dims[2], dims[3], s))
+        }
+        case SA_LAY_GATHER_ADD: {
+            if (!src || !index || dims[0] <= 0 || dims[1] <= 0 || dims[2] <= 0 || dims[2] % 4 || dims[3] < 0) return SA_ERR_ARG;
+            SA_LAY_BOTH(lay::launch_gather_add<T>((T*)dst, (const T*)src, index, dims[0], dims[1], dims[2], dims[3], s))
+        }
+    }
+    return SA_ERR_ARG;
+}
+
+int surya_op_lay_cross_attn(int dtype, int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map,
+                            void* out, float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream) {
+    if (!qpart || !kv || !item_map || !out || M <= 0 || n_images <= 0 || nq <= 0 || nkv <= 0 || Lk <= 0) return SA_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SA_DTYPE_BF16) {
+        if (!vT) return SA_ERR_ARG;
+        if (head_dim != 64 && head_dim != 32) return SA_ERR_UNSUPPORTED;
+        const int rc = lay::launch_transpose_cross_v<bf16_t>((const bf16_t*)kv, (bf16_t*)vT, n_images, Lk, nkv, head_dim, s);
+        if (rc) return rc;
+        return lay::launch_cross_attn<bf16_t>((const float*)qpart, S, M, (const bf16_t*)kv, (const bf16_t*)vT, nullptr, (bf16_t*)out, item_map, M, nq, nkv,
+                                              head_dim, Lk, scale, s);
+    }
+    if (dtype == SA_DTYPE_F32) {
+        if (!scratch) return SA_ERR_ARG;
+        return lay::launch_cross_attn<float>((const float*)qpart, S, M, (const float*)kv, nullptr, scratch, (float*)out, item_map, M, nq, nkv, head_dim, Lk,
+                                             scale, s);
+    }
+    return SA_ERR_UNSUPPORTED;
+}
+
+int surya_op_lay_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int C, float eps, void* stream) {
+    if (!x || !w || !y || rows <= 0 || C <= 0 || C % 4) return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_rmsnorm<T>((const T*)x, (const T*)w, (T*)y, rows, C, eps, (hipStream_t)stream))
+}
+
+int surya_op_lay_reduce_norm(int dtype, const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y,
+                             int H, float eps, void* stream) {
+    if (!part || !res || !x_out || M <= 0 || (w && !y)) return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_reduce_norm<T>(part, S, M, (const T*)res, (const T*)bias, (T*)x_out, (const T*)w, (T*)y, H, eps, (hipStream_t)stream))
+}
+
+int surya_op_lay_prefill_attn(int dtype, int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn,
+                              int nq, int nkv, int Tmax, float scale, void* stream) {
+    if (!qkv || !out || !kcache || !vcache || !rope_cs || B <= 0 || nq <= 0 || nkv <= 0) return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_prefill_attn<T>((const T*)qkv, (T*)out, (T*)kcache, (T*)vcache, (const float2*)rope_cs, B, Tn, nq, nkv, head_dim, Tmax, scale,
+                                            (hipStream_t)stream))
+}
+
+int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed,
+                       int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream) {
+    if (!tokens || !tabs || !x || rows <= 0 || Hd <= 0 || bbox_size <= 0) return SA_ERR_ARG;
+    if (vocab <= bbox_size) return SA_ERR_SHAPE;                   // corners clamp to [0, bbox_size] and index [vocab]-row tables (surya_layout_create)
+    if (family == SA_FAMILY_TABLE) {
+        if (box_embed <= 0 || box_embed >= Hd || category_count <= 0 || merge_count <= 0) return SA_ERR_ARG;
+    } else if (family != SA_FAMILY_LAYOUT || label_count <= 0) return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_embed<T>(family, tokens, (const T* const*)tabs, (T*)x, rows, Hd, box_embed, bbox_size, vocab, label_count, category_count,
+                                     merge_count, (hipStream_t)stream))
+}
+
+int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w,
+                       const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream) {
+    if (!x || !fnorm_w || !ln_w || !ln_b || !lm_w || !bb_w || !bb_b || !class_logits || !bbox || B <= 0 || Hd <= 0 || label_count <= 0 || ldx < Hd)
+        return SA_ERR_ARG;
+    SA_LAY_BOTH(lay::launch_heads<T>((const T*)x, ldx, (const T*)fnorm_w, (const T*)ln_w, (const T*)ln_b, (const T*)lm_w, (const T*)bb_w, (const T*)bb_b,
+                                     class_logits, bbox, B, Hd, label_count, rms_eps, ln_eps, (hipStream_t)stream))
+}
+#undef SA_LAY_BOTH
+#undef SA_LAY_DT
 
 }  // extern "C"

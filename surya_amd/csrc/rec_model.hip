@@ -1102,6 +1102,8 @@ struct surya_rec { std::unique_ptr<RecBase> impl; surya_rec_config cfg; };
 namespace sa {   // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
+// layout_model.hip: the ADETR MLP's gated epilogue (gelu_tanh(gate) * up), fp32 and bf16
+int op_gemm_geglu(int dtype, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int K, hipStream_t s);
 }
 template <typename TI, typename TO>
 static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R,
@@ -1227,6 +1229,8 @@ int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, cons
                   const void* bias, const void* R, long ldr, int M, int N, int K, void* stream) {
     if (!X || !W || !C) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
+    if (epi == EPI_GEGLU)                 // no bias, no residual, output in the compute dtype (LayoutModel's only use of it)
+        return (bias || R || out_f32 || N % 2) ? SA_ERR_UNSUPPORTED : sa::op_gemm_geglu(dtype, X, ldx, W, ldw, C, ldc, M, N, K, s);
     if (dtype == SA_DTYPE_F32) return op_gemm_t<float, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
     if (dtype == SA_DTYPE_BF16)
         return out_f32 ? op_gemm_t<bf16_t, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s)
