@@ -227,12 +227,14 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
  * and keys; its first query / key / value / output row starts at element offset q_off / k_off / v_off / o_off[s] (host
  * arrays) of q / k / v / out (device), rows `*_row` elements apart, heads `*_head` elements apart; query head h reads kv
  * head h / group. head_dim in {32, 64, 80, 128}.
- * surya_op_decode_attn: one decode step's attention launch exactly as RecModel::decode_layer issues it: row r = active slot
+ * surya_op_decode_attn: one decode step's attention, through the launcher the engines use (launch_decode_attn, csrc/decode_attn.h): row r = active slot
  * active_slots[r] with row_len[r] cached tokens; q|k|v of the new token = sum of n_slabs fp32 split-K slabs
  * qkv_part[slab][rows][(heads + 2 kv_heads) * head_dim] + qkv_bias, rounded to the storage dtype; RoPE from the (cos, sin) table
  * rope_cs[max_kv_len][head_dim / 2][2]; k, v appended to the caches [slot][kv_head][max_kv_len][head_dim] at row_len[r];
  * out[r][heads * head_dim] = attention over row_len[r] + 1 keys (decoder/__init__.py:193-234). bf16 runs
- * decode_attn_flash_kernel, fp32 decode_attn_mfma_kernel. All pointers device. Enqueue only. */
+ * decode_attn_flash2_kernel (tuning dattn = 4, the default) or decode_attn_flash_kernel (dattn = 3), fp32 decode_attn_mfma_kernel. The hook
+ * has no host bound on the contexts, so of decode_attn_flash2_kernel's two forms the two-buffer one runs at dattn_db = 1 only; the engine also
+ * picks it at dattn_db = 0 once a context exceeds 128 keys. All pointers device. Enqueue only. */
 int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const void* v, void* out, const int32_t* seg_len,
                   const int64_t* q_off, const int64_t* k_off, const int64_t* v_off, const int64_t* o_off, int n_seg, int heads, int group,
                   int causal, float scale, long q_row, long q_head, long k_row, long k_head, long o_row, long o_head, void* stream);

@@ -178,4 +178,29 @@ __global__ __launch_bounds__(128) void attn_mfma_kernel(const bf16_t* __restrict
     }
 }
 
+// The launch of segment attention, for the engines (RecModel, OcrErrModel) and surya_op_attn alike: bf16 on the matrix cores, fp32 on
+// attn_valu_kernel (kernels.h). One workgroup per (64-query tile of sg, head); the strides are in elements.
+template <typename T>
+int launch_attn(int D, const T* q, const T* k, const T* v, T* o, const AttnSegs& sg, int n_tiles, int heads, long q_row, long q_head,
+                long k_row, long k_head, long o_row, long o_head, int group, int causal, float scale, hipStream_t s) {
+    if (n_tiles <= 0) return SA_OK;
+    auto go = [&](auto kern, int threads) {
+        hipLaunchKernelGGL(kern, dim3(n_tiles, heads), dim3(threads), 0, s, q, k, v, o, sg, q_row, q_head, k_row, k_head, o_row, o_head, group,
+                           causal, scale);
+        return (int)hipGetLastError();
+    };
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        if (D == 32) return go(attn_mfma_kernel<32>, 128);
+        if (D == 64) return go(attn_mfma_kernel<64>, 128);
+        if (D == 80) return go(attn_mfma_kernel<80>, 128);
+        if (D == 128) return go(attn_mfma_kernel<128>, 128);
+    } else {
+        if (D == 32) return go(attn_valu_kernel<T, 32>, 256);
+        if (D == 64) return go(attn_valu_kernel<T, 64>, 256);
+        if (D == 80) return go(attn_valu_kernel<T, 80>, 256);
+        if (D == 128) return go(attn_valu_kernel<T, 128>, 256);
+    }
+    return SA_ERR_UNSUPPORTED;
+}
+
 }  // namespace sa

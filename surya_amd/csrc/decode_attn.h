@@ -842,4 +842,26 @@ static inline size_t decode_attn_mfma_lds() {
     return (size_t)2 * KT * ROWB + 32 * ROWB + (size_t)MAXG * KT * 4 + (size_t)(MAXG + 2) * D * 4 + 3 * MAXG * 4 + 64;
 }
 
+// One decode step's attention for `rows` active rows: what RecModel::decode_layer, LayoutModel::decode_layers and surya_op_decode_attn
+// hand to the one launcher of the three kernels above.
+template <typename T>
+struct DecodeAttnArgs {
+    const float* qkv_part; int S;        // the qkv projection's split-K slabs [S][rows][(nq + 2 nkv) d], 1 <= S <= 8
+    const T* qkv_bias;
+    T* out;                              // [rows][nq d]
+    T *kcache, *vcache;                  // one layer's [slot][kv head][max_kv_len][d]
+    const int *active_slots, *row_len;   // [rows]: slot and cached length of every row
+    const float2* rope_cs;               // [max_kv_len][d / 2] (cos, sin)
+    int rows, nq, nkv, d, max_kv_len;
+    float scale;
+    int ctx_bound = 0;                   // host's upper bound on any row's context (cached keys + the new one); 0 = unknown
+    uint8_t *out8 = nullptr, *sout = nullptr; int srows = 0;   // optional MXFP8 copy of the output (gemm_mx.h): the bf16 flash kernels only
+};
+// The ladder over (d, heads per kv head), the kernel version (Tuning::dattn, Tuning::dattn_db with ctx_bound), the LDS opt-in and the launch.
+// bf16: decode_attn_flash2_kernel, or decode_attn_flash_kernel at dattn = 3; fp32, and head shapes those two lack: decode_attn_mfma_kernel.
+// Defined for float and bf16_t in rec_model.hip, whose code object alone holds the kernels (a header template would compile the whole ladder
+// into every object that decodes).
+template <typename T>
+int launch_decode_attn(const DecodeAttnArgs<T>& a, hipStream_t s);
+
 }  // namespace sa

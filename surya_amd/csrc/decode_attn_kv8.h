@@ -411,4 +411,54 @@ static inline size_t decode_attn_kv8_lds() {
     return (size_t)2 * 2 * 256 * D + (size_t)2 * 2 * 256 * 4 + (size_t)16 * D * 2 + (size_t)(MAXG + 2) * D * 4 + 2 * D + 16;
 }
 
+// Keys per slot of the V^T and scale arrays: max_kv_len rounded up to whole 256-key tiles.
+static inline int kv8_tmax(int max_kv_len) { return (max_kv_len + 255) & ~255; }
+
+// The launches of this file. The arrays are one layer's: k8 [slot][kv head][max_kv_len][d],
+// v8t [slot][kv head][d][kv8_tmax], ksc / vsc [slot][kv head][kv8_tmax].
+// Prefill's quantisation of n_tokens appended rows, for RecModel::decoder_layers_prefill and surya_op_kv8_quant_rows alike.
+inline int launch_kv8_quant_rows(int d, const bf16_t* kc, const bf16_t* vc, const int* tok_slot, const int* tok_pos, int n_tokens, uint8_t* k8,
+                                 uint8_t* v8t, float* ksc, float* vsc, int nkv, int max_kv_len, hipStream_t s) {
+    auto go = [&](auto kern) {
+        hipLaunchKernelGGL(kern, dim3(cdiv(n_tokens * nkv, 4)), dim3(256), 0, s, kc, vc, tok_slot, tok_pos, n_tokens, k8, v8t, ksc, vsc, nkv,
+                           max_kv_len, kv8_tmax(max_kv_len));
+        return (int)hipGetLastError();
+    };
+    if (d == 128) return go(kv8_quant_rows_kernel<128>);
+    if (d == 64) return go(kv8_quant_rows_kernel<64>);
+    if (d == 32) return go(kv8_quant_rows_kernel<32>);
+    return SA_ERR_UNSUPPORTED;
+}
+
+// One decode step's attention over the FP8 cache, for RecModel::decode_layer and surya_op_decode_attn_kv8 alike.
+struct DecodeAttnKv8Args {
+    const float* qkv_part; int S;        // the qkv projection's split-K slabs [S][rows][(nq + 2 nkv) d]
+    const bf16_t* qkv_bias;
+    bf16_t* out;                         // [rows][nq d]
+    uint8_t *k8, *v8t; float *ksc, *vsc; // one layer's arrays (layout above)
+    const int *active_slots, *row_len;   // [rows]
+    const float2* rope_cs;
+    int rows, nq, nkv, d, max_kv_len;
+    float scale;
+    uint8_t *out8 = nullptr, *sout = nullptr; int srows = 0;   // optional MXFP8 copy of the output (gemm_mx.h)
+};
+template <int D, int MAXG>
+int launch_decode_attn_kv8_as(const DecodeAttnKv8Args& a, hipStream_t s) {
+    static AttrOnce attr;
+    const size_t lds = decode_attn_kv8_lds<D, MAXG>();
+    attr.ensure(decode_attn_kv8_kernel<D, MAXG>, lds);
+    hipLaunchKernelGGL((decode_attn_kv8_kernel<D, MAXG>), dim3(a.rows, a.nkv), dim3(KV8_THREADS), lds, s, a.qkv_part, a.S, a.qkv_bias, a.out, a.k8,
+                       a.v8t, a.ksc, a.vsc, a.active_slots, a.row_len, a.rope_cs, a.nq, a.nkv, a.max_kv_len, kv8_tmax(a.max_kv_len), a.scale, a.out8,
+                       a.sout, a.srows);
+    return (int)hipGetLastError();
+}
+inline int launch_decode_attn_kv8(const DecodeAttnKv8Args& a, hipStream_t s) {
+    const int G = a.nq / a.nkv;
+    if (a.d == 128 && G <= 5) return launch_decode_attn_kv8_as<128, 5>(a, s);
+    if (a.d == 128 && G <= 8) return launch_decode_attn_kv8_as<128, 8>(a, s);
+    if (a.d == 64 && G <= 8) return launch_decode_attn_kv8_as<64, 8>(a, s);
+    if (a.d == 32 && G <= 8) return launch_decode_attn_kv8_as<32, 8>(a, s);
+    return SA_ERR_UNSUPPORTED;
+}
+
 }  // namespace sa

@@ -676,5 +676,13 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
     if (table) embed_norm_row<T, NT>(table + (long)tok_next * H, x + (long)r * H, wnorm, y + (long)r * H, H, eps, red, y8, sy, srows, r);
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The launch of rmsnorm_kernel: RecModel and surya_op_rmsnorm both go through it. src_row = nullptr: row r reads row r.
+template <typename T>
+int launch_rmsnorm(const T* x, long ldx, const T* w, T* y, long ldy, const int* src_row, int rows, int C, float eps, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    hipLaunchKernelGGL(rmsnorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, y, ldy, src_row, rows, C, eps);
+    return (int)hipGetLastError();
+}
 
 }  // namespace sa

@@ -607,36 +607,10 @@ struct LayoutModel : LayoutBase {
             {
                 GemmArgs<T, T> a{dh, Hd, W(lb + SA_LD_QKV_W), Hd, nullptr, 0, nullptr, nullptr, 0, B, qkv_d, Hd, 1, part};
                 if ((rc = launch_gemm_splitk<T>(a, s))) return rc;
-                const int S = a.splitk, G = nq / nkv;
-                dim3 grid(B, nkv), block(256);
-                T* kc = kcache + (size_t)l * layer_kv;
-                T* vc = vcache + (size_t)l * layer_kv;
-#define SA_LAY_DEC(KERN, LDS, ...)                                                                                                  \
-    {                                                                                                                               \
-        auto kern = KERN;                                                                                                           \
-        static AttrOnce attr;                                                                                                       \
-        attr.ensure(kern, LDS);                                                                                                     \
-        hipLaunchKernelGGL(kern, grid, block, LDS, s, part, S, W(SA_LW_DEC_ZERO_BIAS), dattn, kc, vc, slots_dev, len_dev, rope_cs, nq, \
-                           nkv, c.max_boxes, scale, ##__VA_ARGS__);                                                                \
-    }
-                bool done = false;
-                if constexpr (std::is_same<T, bf16_t>::value) {
-                    done = true;
-                    // round 4: the thread-local-prologue kernel of the recogniser's decode step (decode_attn.h, fourth version; dattn = 3 keeps the third)
-                    if (tuning().dattn == 3) {
-                        if (d == 64 && G <= 8) SA_LAY_DEC((decode_attn_flash_kernel<64, 8>), (decode_attn_flash_lds<64, 8>()), (uint8_t*)nullptr, (uint8_t*)nullptr, 0)
-                        else if (d == 32 && G <= 8) SA_LAY_DEC((decode_attn_flash_kernel<32, 8>), (decode_attn_flash_lds<32, 8>()), (uint8_t*)nullptr, (uint8_t*)nullptr, 0)
-                        else done = false;
-                    } else if (d == 64 && G <= 8) SA_LAY_DEC((decode_attn_flash2_kernel<64, 8, false>), (decode_attn_flash2_lds<64, 8, false>()), (uint8_t*)nullptr, (uint8_t*)nullptr, 0)
-                    else if (d == 32 && G <= 8) SA_LAY_DEC((decode_attn_flash2_kernel<32, 8, false>), (decode_attn_flash2_lds<32, 8, false>()), (uint8_t*)nullptr, (uint8_t*)nullptr, 0)
-                    else done = false;
-                }
-                if (!done) {
-                    if (d == 64 && G <= 8) SA_LAY_DEC((decode_attn_mfma_kernel<T, 64, 8>), (decode_attn_mfma_lds<T, 64, 8>()))
-                    else if (d == 32 && G <= 8) SA_LAY_DEC((decode_attn_mfma_kernel<T, 32, 8>), (decode_attn_mfma_lds<T, 32, 8>()))
-                    else return SA_ERR_UNSUPPORTED;
-                }
-#undef SA_LAY_DEC
+                // the recogniser's decode-attention launcher (decode_attn.h); no host bound on the contexts here
+                DecodeAttnArgs<T> da{part, a.splitk, W(SA_LW_DEC_ZERO_BIAS), dattn, kcache + (size_t)l * layer_kv, vcache + (size_t)l * layer_kv, slots_dev,
+                                     len_dev, rope_cs, B, nq, nkv, d, c.max_boxes, scale};
+                if ((rc = launch_decode_attn<T>(da, s))) return rc;
             }
             if ((rc = splitk(dattn, Hd, W(lb + SA_LD_TO_W), Hd, Hd, S))) return rc;
             // layout: + RAW layer input (double residual flow); table_rec: + the cross-attention output (adetr/decoder.py:395-417)

@@ -110,33 +110,8 @@ struct OcrErrModel : OcrErrBase {
         return (int)hipGetLastError();
     }
     int attention(const T* q, T* o, const AttnSegs& sg, int n_tiles, long o_row, hipStream_t s) {
-        if (n_tiles <= 0) return SA_OK;
         const long ld = 3L * c.dim;
-        dim3 grid(n_tiles, c.heads);
-        if constexpr (std::is_same<T, bf16_t>::value) {
-#define SA_OCR_ATTN_M(DD) hipLaunchKernelGGL((attn_mfma_kernel<DD>), grid, dim3(128), 0, s, q, q + c.dim, q + 2 * c.dim, o, sg, ld, (long)D, ld, \
-                                             (long)D, o_row, (long)D, 1, 0, attn_scale)
-            switch (D) {
-                case 32: SA_OCR_ATTN_M(32); break;
-                case 64: SA_OCR_ATTN_M(64); break;
-                case 80: SA_OCR_ATTN_M(80); break;
-                case 128: SA_OCR_ATTN_M(128); break;
-                default: return SA_ERR_UNSUPPORTED;
-            }
-#undef SA_OCR_ATTN_M
-        } else {
-#define SA_OCR_ATTN_V(DD) hipLaunchKernelGGL((attn_valu_kernel<T, DD>), grid, dim3(256), 0, s, q, q + c.dim, q + 2 * c.dim, o, sg, ld, (long)D, ld, \
-                                             (long)D, o_row, (long)D, 1, 0, attn_scale)
-            switch (D) {
-                case 32: SA_OCR_ATTN_V(32); break;
-                case 64: SA_OCR_ATTN_V(64); break;
-                case 80: SA_OCR_ATTN_V(80); break;
-                case 128: SA_OCR_ATTN_V(128); break;
-                default: return SA_ERR_UNSUPPORTED;
-            }
-#undef SA_OCR_ATTN_V
-        }
-        return (int)hipGetLastError();
+        return launch_attn<T>(D, q, q + c.dim, q + 2 * c.dim, o, sg, n_tiles, c.heads, ld, D, ld, D, o_row, D, 1, 0, attn_scale, s);
     }
     int cls_attention(const int* starts, const int* lens, int n, hipStream_t s) {
         if constexpr (std::is_same<T, bf16_t>::value) {

@@ -28,6 +28,46 @@
 
 namespace sa {
 
+// --------------------------------------------------------------------------------- decode attention launch
+// launch_decode_attn (decode_attn.h): every decode-attention launch of the library -- RecModel::decode_layer, LayoutModel::decode_layers
+// and surya_op_decode_attn -- is this one, so a kernel tested through the hook is launched exactly as the engines launch it.
+template <auto KERN, typename T, typename... X>
+static int decode_attn_as(const DecodeAttnArgs<T>& a, size_t lds, hipStream_t s, X... extra) {
+    static AttrOnce attr;                                    // one per kernel: KERN is a template argument
+    attr.ensure(KERN, lds);
+    hipLaunchKernelGGL(KERN, dim3(a.rows, a.nkv), dim3(256), lds, s, a.qkv_part, a.S, a.qkv_bias, a.out, a.kcache, a.vcache, a.active_slots,
+                       a.row_len, a.rope_cs, a.nq, a.nkv, a.max_kv_len, a.scale, extra...);
+    return (int)hipGetLastError();
+}
+template <int D, int MAXG>
+static int decode_attn_flash(const DecodeAttnArgs<bf16_t>& a, hipStream_t s) {
+    const Tuning& t = tuning();
+    if (t.dattn == 3) return decode_attn_as<decode_attn_flash_kernel<D, MAXG>>(a, decode_attn_flash_lds<D, MAXG>(), s, a.out8, a.sout, a.srows);
+    // two tile buffers once some row's context exceeds one 128-key tile (Tuning::dattn_db); one workgroup per CU either way
+    if (t.dattn_db == 1 || (t.dattn_db == 0 && !t.graph && a.ctx_bound > 128 && a.rows * a.nkv <= 256))
+        return decode_attn_as<decode_attn_flash2_kernel<D, MAXG, true>>(a, decode_attn_flash2_lds<D, MAXG, true>(), s, a.out8, a.sout, a.srows);
+    return decode_attn_as<decode_attn_flash2_kernel<D, MAXG, false>>(a, decode_attn_flash2_lds<D, MAXG, false>(), s, a.out8, a.sout, a.srows);
+}
+template <typename T>
+int launch_decode_attn(const DecodeAttnArgs<T>& a, hipStream_t s) {
+    const int G = a.nq / a.nkv, d = a.d;                     // G <= MAXG on every rung: MAXG sizes the kernels' LDS arrays
+    if constexpr (std::is_same<T, bf16_t>::value) {          // bf16: per-wave flash kernels
+        if (d == 128 && G <= 5) return decode_attn_flash<128, 5>(a, s);
+        if (d == 128 && G <= 8) return decode_attn_flash<128, 8>(a, s);
+        if (d == 64 && G <= 8) return decode_attn_flash<64, 8>(a, s);
+        if (d == 32 && G <= 8) return decode_attn_flash<32, 8>(a, s);
+    }
+    if (a.out8) return SA_ERR_UNSUPPORTED;                   // only the flash kernels write the MXFP8 copy of their output
+    // fp32 reference mode, and bf16 head shapes the flash ladder lacks (today the two ladders cover the same shapes)
+    if (d == 128 && G <= 5) return decode_attn_as<decode_attn_mfma_kernel<T, 128, 5>>(a, decode_attn_mfma_lds<T, 128, 5>(), s);
+    if (d == 128 && G <= 8) return decode_attn_as<decode_attn_mfma_kernel<T, 128, 8>>(a, decode_attn_mfma_lds<T, 128, 8>(), s);
+    if (d == 64 && G <= 8) return decode_attn_as<decode_attn_mfma_kernel<T, 64, 8>>(a, decode_attn_mfma_lds<T, 64, 8>(), s);
+    if (d == 32 && G <= 8) return decode_attn_as<decode_attn_mfma_kernel<T, 32, 8>>(a, decode_attn_mfma_lds<T, 32, 8>(), s);
+    return SA_ERR_UNSUPPORTED;
+}
+template int launch_decode_attn<float>(const DecodeAttnArgs<float>&, hipStream_t);
+template int launch_decode_attn<bf16_t>(const DecodeAttnArgs<bf16_t>&, hipStream_t);
+
 // ------------------------------------------------------------------------------------------------- staging
 struct Stager {   // pinned host arena mirrored by a device arena; one H2D copy per plan
     char* host = nullptr;
@@ -216,7 +256,7 @@ struct RecModel : RecBase {
     uint8_t *k8c = nullptr, *v8tc = nullptr;     // [layer][slot][kvh][Tmax][D], [layer][slot][kvh][D][Tmax8]
     float *ksc8 = nullptr, *vsc8 = nullptr;      // [layer][slot][kvh][Tmax8]
     bool kv8 = false;
-    int tmax8() const { return (c.max_kv_len + 255) & ~255; }   // whole 256-key tiles (decode_attn_kv8.h)
+    int tmax8() const { return kv8_tmax(c.max_kv_len); }
     uint8_t *dh8 = nullptr, *sdh = nullptr, *dattn8 = nullptr, *sattn = nullptr, *dmlp8 = nullptr, *smlp = nullptr, *dlast8 = nullptr,
             *slast = nullptr;
     bool mx() const { return !mxw.empty(); }
@@ -345,44 +385,7 @@ struct RecModel : RecBase {
         return launch_gemm<T, T, EPI>(a, s);
     }
     int rmsnorm(const T* x, long ldx, const T* wt, T* y, long ldy, const int* src_row, int rows, int C, float eps, hipStream_t s) {
-        if (rows <= 0) return SA_OK;
-        hipLaunchKernelGGL(rmsnorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, wt, y, ldy, src_row, rows, C, eps);
-        return (int)hipGetLastError();
-    }
-    int attention(int D, const T* q, const T* k, const T* v, T* o, const AttnSegs& sg, int n_tiles, int heads, long q_row,
-                  long q_head, long k_row, long k_head, long o_row, long o_head, int group, int causal, float scale,
-                  hipStream_t s) {
-        if (n_tiles <= 0) return SA_OK;
-        dim3 grid(n_tiles, heads), block(256);
-        if constexpr (std::is_same<T, bf16_t>::value) {
-            // bf16: matrix-core kernel (attn_mfma.h); the vector-ALU kernel below is the fp32 reference-mode path
-            {
-#define SA_ATTN_M(DD)                                                                                                    \
-    hipLaunchKernelGGL((attn_mfma_kernel<DD>), grid, dim3(128), 0, s, q, k, v, o, sg, q_row, q_head, k_row, k_head, o_row, \
-                       o_head, group, causal, scale)
-                switch (D) {
-                    case 32: SA_ATTN_M(32); break;
-                    case 64: SA_ATTN_M(64); break;
-                    case 80: SA_ATTN_M(80); break;
-                    case 128: SA_ATTN_M(128); break;
-                    default: return SA_ERR_UNSUPPORTED;
-                }
-#undef SA_ATTN_M
-                return (int)hipGetLastError();
-            }
-        }
-#define SA_ATTN(DD)                                                                                                    \
-    hipLaunchKernelGGL((attn_valu_kernel<T, DD>), grid, block, 0, s, q, k, v, o, sg, q_row, q_head, k_row, k_head, o_row, \
-                       o_head, group, causal, scale)
-        switch (D) {
-            case 32: SA_ATTN(32); break;
-            case 64: SA_ATTN(64); break;
-            case 80: SA_ATTN(80); break;
-            case 128: SA_ATTN(128); break;
-            default: return SA_ERR_UNSUPPORTED;
-        }
-#undef SA_ATTN
-        return (int)hipGetLastError();
+        return launch_rmsnorm<T>(x, ldx, wt, y, ldy, src_row, rows, C, eps, s);
     }
 
     // Vision encoder for images [0, n) whose tiles start at `tiles`; merged tokens (original order index g)
@@ -453,7 +456,7 @@ struct RecModel : RecBase {
                 const bool fullatt = (c.fullatt_mask >> l) & 1u;
                 const AttnSegs& sg = fullatt ? d_full : d_win;
                 const int nt = (int)(fullatt ? full.tile_seg.size() : win.tile_seg.size());
-                if ((rc = attention(D, eqkv, eqkv, eqkv, eh, sg, nt, c.enc_heads, 3 * He, D, 3 * He, D, He, D, 1, 0, scale, s)))
+                if ((rc = launch_attn<T>(D, eqkv, eqkv, eqkv, eh, sg, nt, c.enc_heads, 3 * He, D, 3 * He, D, He, D, 1, 0, scale, s)))
                     return rc;
                 if ((rc = gemm<EPI_RESIDUAL>(eh, He, WE(l, SA_RE_PROJ_W), He, ex, He, WE(l, SA_RE_PROJ_B), ex, He, Pi, He, He, s)))
                     return rc;
@@ -536,19 +539,12 @@ struct RecModel : RecBase {
             if constexpr (std::is_same<T, bf16_t>::value) {
                 if (kv8) {
                     const size_t l8 = (size_t)c.max_slots * nkv, T8 = tmax8();
-                    uint8_t* k8l = k8c + l * l8 * c.max_kv_len * d;
-                    uint8_t* v8l = v8tc + l * l8 * d * T8;
-                    float* ksl = ksc8 + l * l8 * T8;
-                    float* vsl = vsc8 + l * l8 * T8;
-                    dim3 qg(cdiv(M * nkv, 4));
-                    if (d == 128) hipLaunchKernelGGL(kv8_quant_rows_kernel<128>, qg, dim3(256), 0, s, kc, vc, d_tok_slot, d_tok_pos, M, k8l, v8l, ksl, vsl, nkv, c.max_kv_len, (int)T8);
-                    else if (d == 64) hipLaunchKernelGGL(kv8_quant_rows_kernel<64>, qg, dim3(256), 0, s, kc, vc, d_tok_slot, d_tok_pos, M, k8l, v8l, ksl, vsl, nkv, c.max_kv_len, (int)T8);
-                    else if (d == 32) hipLaunchKernelGGL(kv8_quant_rows_kernel<32>, qg, dim3(256), 0, s, kc, vc, d_tok_slot, d_tok_pos, M, k8l, v8l, ksl, vsl, nkv, c.max_kv_len, (int)T8);
-                    else return SA_ERR_UNSUPPORTED;
+                    if ((rc = launch_kv8_quant_rows(d, kc, vc, d_tok_slot, d_tok_pos, M, k8c + l * l8 * c.max_kv_len * d, v8tc + l * l8 * d * T8,
+                                                    ksc8 + l * l8 * T8, vsc8 + l * l8 * T8, nkv, c.max_kv_len, s))) return rc;
                 }
             }
-            if ((rc = attention(d, dqkv, kc, vc, dattn, *sg, n_tiles, nq, qkv_d, d, d, (long)c.max_kv_len * d, (long)nq * d, d,
-                                nq / nkv, 1, scale, s))) return rc;
+            if ((rc = launch_attn<T>(d, dqkv, kc, vc, dattn, *sg, n_tiles, nq, qkv_d, d, d, (long)c.max_kv_len * d, (long)nq * d, d,
+                                     nq / nkv, 1, scale, s))) return rc;
             if ((rc = gemm<EPI_RESIDUAL>(dattn, (long)nq * d, WD(l, SA_RD_O_W), (long)nq * d, dx, Hd, nullptr, dx, Hd, M, Hd, nq * d,
                                          s))) return rc;
             if ((rc = rmsnorm(dx, Hd, WD(l, SA_RD_LN2), dh, Hd, nullptr, M, Hd, c.dec_eps, s))) return rc;
@@ -709,75 +705,21 @@ struct RecModel : RecBase {
         if (q8) rc = splitk_gemm_mx(hh8, shh, Hd, MXW(l, SA_MX_QKV_W), MXW(l, SA_MX_QKV_S), M, qkv_d, Hd, h.part, &S, s);
         else rc = splitk_gemm(hh, Hd, WD(l, SA_RD_QKV_W), Hd, M, qkv_d, Hd, h.part, &S, s);
         if (rc) return rc;
-        dim3 grid(M, nkv), block(256);
-        const int G = nq / nkv;
-#define SA_DEC_LAUNCH(KERN, LDS, ...)                                                                                       \
-    {                                                                                                                       \
-        auto kern = KERN;                                                                                                   \
-        static AttrOnce attr;                                                                                               \
-        attr.ensure(kern, LDS);                                                                                             \
-        hipLaunchKernelGGL(kern, grid, block, LDS, s, h.part, S, WD(l, SA_RD_QKV_B), at, kc, vc, act, rl, rope_cs, nq, nkv,  \
-                           c.max_kv_len, scale, ##__VA_ARGS__);                                                             \
-    }
-#define SA_DEC_MFMA(DD, GG) SA_DEC_LAUNCH((decode_attn_mfma_kernel<T, DD, GG>), (decode_attn_mfma_lds<T, DD, GG>()))
-#define SA_DEC_FLASH3(DD, GG) SA_DEC_LAUNCH((decode_attn_flash_kernel<DD, GG>), (decode_attn_flash_lds<DD, GG>()), at8, sat, c.max_slots)
-#define SA_DEC_FLASH4(DD, GG)                                                                                                         \
-    {                                                                                                                                 \
-        const int dbk = tuning().dattn_db;                                                                                            \
-        if (dbk == 1 || (dbk == 0 && !tuning().graph && ctx_bound > 128 && M * nkv <= 256))   /* one workgroup per CU either way */          \
-            SA_DEC_LAUNCH((decode_attn_flash2_kernel<DD, GG, true>), (decode_attn_flash2_lds<DD, GG, true>()), at8, sat, c.max_slots) \
-        else SA_DEC_LAUNCH((decode_attn_flash2_kernel<DD, GG, false>), (decode_attn_flash2_lds<DD, GG, false>()), at8, sat, c.max_slots) \
-    }
-#define SA_DEC_FLASH(DD, GG) { if (tuning().dattn == 3) SA_DEC_FLASH3(DD, GG) else SA_DEC_FLASH4(DD, GG) }
         bool launched = false;
         if constexpr (std::is_same<T, bf16_t>::value) {
             if (kv8) {                                       // FP8 KV cache (decode_attn_kv8.h)
                 const size_t l8 = (size_t)c.max_slots * nkv, T8 = tmax8();
-                uint8_t* k8l = k8c + l * l8 * c.max_kv_len * d;
-                uint8_t* v8l = v8tc + l * l8 * d * T8;
-                float* ksl = ksc8 + l * l8 * T8;
-                float* vsl = vsc8 + l * l8 * T8;
-#define SA_DEC_KV8(DD, GG)                                                                                                       \
-    {                                                                                                                           \
-        auto kern = decode_attn_kv8_kernel<DD, GG>;                                                                             \
-        static AttrOnce attr;                                                                                                   \
-        attr.ensure(kern, decode_attn_kv8_lds<DD, GG>());                                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(KV8_THREADS), (decode_attn_kv8_lds<DD, GG>()), s, h.part, S, WD(l, SA_RD_QKV_B), at, k8l, v8l, ksl, \
-                           vsl, act, rl, rope_cs, nq, nkv, c.max_kv_len, (int)T8, scale, at8, sat, c.max_slots);                \
-    }
+                DecodeAttnKv8Args a{h.part, S, WD(l, SA_RD_QKV_B), at, k8c + l * l8 * c.max_kv_len * d, v8tc + l * l8 * d * T8, ksc8 + l * l8 * T8,
+                                    vsc8 + l * l8 * T8, act, rl, rope_cs, M, nq, nkv, d, c.max_kv_len, scale, at8, sat, c.max_slots};
+                if ((rc = launch_decode_attn_kv8(a, s))) return rc;
                 launched = true;
-                if (d == 128 && G <= 5) SA_DEC_KV8(128, 5)
-                else if (d == 128 && G <= 8) SA_DEC_KV8(128, 8)
-                else if (d == 64 && G <= 8) SA_DEC_KV8(64, 8)
-                else if (d == 32 && G <= 8) SA_DEC_KV8(32, 8)
-                else return SA_ERR_UNSUPPORTED;
-#undef SA_DEC_KV8
             }
         }
-        if constexpr (std::is_same<T, bf16_t>::value) {      // bf16: per-wave flash kernel (decode_attn.h, third version)
-          if (!launched) {
-            launched = true;
-            if (d == 128 && G <= 5) SA_DEC_FLASH(128, 5)
-            else if (d == 128 && G <= 8) SA_DEC_FLASH(128, 8)
-            else if (d == 64 && G <= 8) SA_DEC_FLASH(64, 8)
-            else if (d == 32 && G <= 8) SA_DEC_FLASH(32, 8)
-            else launched = false;
-          }
+        if (!launched) {
+            DecodeAttnArgs<T> a{h.part, S, WD(l, SA_RD_QKV_B), at, kc, vc, act, rl, rope_cs, M, nq, nkv, d, c.max_kv_len, scale, ctx_bound, at8, sat,
+                                c.max_slots};
+            if ((rc = launch_decode_attn<T>(a, s))) return rc;
         }
-        if (!launched) {                                     // fp32 reference mode (and head shapes the flash kernel lacks)
-            if (d == 128 && G <= 5) SA_DEC_MFMA(128, 5)
-            else if (d == 128) SA_DEC_MFMA(128, 8)
-            else if (d == 64) SA_DEC_MFMA(64, 8)
-            else if (d == 32) SA_DEC_MFMA(32, 8)
-            else return SA_ERR_UNSUPPORTED;
-        }
-#undef SA_DEC_FLASH
-#undef SA_DEC_FLASH3
-#undef SA_DEC_FLASH4
-#undef SA_DEC_MFMA
-#undef SA_DEC_LAUNCH
-        if ((rc = (int)hipGetLastError())) return rc;
-        if (q8 && !launched) return SA_ERR_UNSUPPORTED;      // only the flash kernel writes the MXFP8 copy of its output
         const bool last = (l + 1 == c.dec_layers);
         const T* wnext = last ? W(SA_RW_DEC_NORM) : WD(l + 1, SA_RD_LN1);
         T* ynext = last ? dlast + (size_t)h.r0 * Hd : hh;
@@ -1280,33 +1222,15 @@ int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const v
     DevSegs sg;
     int rc = sg.init(seg_len, q_off, k_off, v_off, o_off, n_seg);
     if (rc) return rc;
-    dim3 grid(sg.n_tiles, heads);
-#define SA_OPA_M(DD) hipLaunchKernelGGL((attn_mfma_kernel<DD>), grid, dim3(128), 0, s, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, \
-                                        (bf16_t*)out, sg.a, q_row, q_head, k_row, k_head, o_row, o_head, group, causal, scale)
-#define SA_OPA_V(DD) hipLaunchKernelGGL((attn_valu_kernel<float, DD>), grid, dim3(256), 0, s, (const float*)q, (const float*)k, (const float*)v, \
-                                        (float*)out, sg.a, q_row, q_head, k_row, k_head, o_row, o_head, group, causal, scale)
-    if (dtype == SA_DTYPE_BF16) {
-        switch (head_dim) {
-            case 32: SA_OPA_M(32); break;
-            case 64: SA_OPA_M(64); break;
-            case 80: SA_OPA_M(80); break;
-            case 128: SA_OPA_M(128); break;
-            default: return SA_ERR_UNSUPPORTED;
-        }
-    } else if (dtype == SA_DTYPE_F32) {
-        switch (head_dim) {
-            case 32: SA_OPA_V(32); break;
-            case 64: SA_OPA_V(64); break;
-            case 80: SA_OPA_V(80); break;
-            case 128: SA_OPA_V(128); break;
-            default: return SA_ERR_UNSUPPORTED;
-        }
-    } else {
-        return SA_ERR_UNSUPPORTED;
-    }
-#undef SA_OPA_M
-#undef SA_OPA_V
-    SA_HIP(hipGetLastError());
+    if (dtype == SA_DTYPE_BF16)
+        rc = sa::launch_attn<bf16_t>(head_dim, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, sg.a, sg.n_tiles, heads, q_row, q_head,
+                                     k_row, k_head, o_row, o_head, group, causal, scale, s);
+    else if (dtype == SA_DTYPE_F32)
+        rc = sa::launch_attn<float>(head_dim, (const float*)q, (const float*)k, (const float*)v, (float*)out, sg.a, sg.n_tiles, heads, q_row, q_head, k_row,
+                                    k_head, o_row, o_head, group, causal, scale, s);
+    else
+        rc = SA_ERR_UNSUPPORTED;
+    if (rc) return rc;
     SA_HIP(hipStreamSynchronize(s));          // the segment tables above are freed on return
     return SA_OK;
 }
@@ -1317,64 +1241,27 @@ int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_s
     if (!qkv_part || !qkv_bias || !out || !kcache || !vcache || !active_slots || !row_len || !rope_cs) return SA_ERR_ARG;
     if (rows <= 0 || n_slabs < 1 || n_slabs > 8 || kv_heads <= 0 || heads % kv_heads) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int G = heads / kv_heads, d = head_dim;
-    dim3 grid(rows, kv_heads), block(256);
     const float2* cs = reinterpret_cast<const float2*>(rope_cs);
-#define SA_OPD(KERN, LDS, TT, ...)                                                                                              \
-    {                                                                                                                           \
-        auto kern = KERN;                                                                                                       \
-        static AttrOnce attr;                                                                                                   \
-        attr.ensure(kern, LDS);                                                                                                 \
-        hipLaunchKernelGGL(kern, grid, block, LDS, s, qkv_part, n_slabs, (const TT*)qkv_bias, (TT*)out, (TT*)kcache, (TT*)vcache, \
-                           active_slots, row_len, cs, heads, kv_heads, max_kv_len, scale, ##__VA_ARGS__);                       \
+    // no host bound on the contexts at the op level (ctx_bound = 0): the two-buffer kernel runs at dattn_db = 1 only (tests run both)
+    if (dtype == SA_DTYPE_BF16) {
+        sa::DecodeAttnArgs<bf16_t> a{qkv_part, n_slabs, (const bf16_t*)qkv_bias, (bf16_t*)out, (bf16_t*)kcache, (bf16_t*)vcache, active_slots, row_len,
+                                     cs, rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        return sa::launch_decode_attn<bf16_t>(a, s);
     }
-#define SA_OPD_FLASH3(DD, GG) SA_OPD((decode_attn_flash_kernel<DD, GG>), (decode_attn_flash_lds<DD, GG>()), bf16_t, (uint8_t*)nullptr, (uint8_t*)nullptr, 0)
-#define SA_OPD_FLASH4(DD, GG)                                                                                                                 \
-    {   /* no host length bound at the op level: the two-buffer variant is picked by the knob alone (tests run both) */                       \
-        if (tuning().dattn_db == 1)                                                                                                           \
-            SA_OPD((decode_attn_flash2_kernel<DD, GG, true>), (decode_attn_flash2_lds<DD, GG, true>()), bf16_t, (uint8_t*)nullptr, (uint8_t*)nullptr, 0) \
-        else SA_OPD((decode_attn_flash2_kernel<DD, GG, false>), (decode_attn_flash2_lds<DD, GG, false>()), bf16_t, (uint8_t*)nullptr, (uint8_t*)nullptr, 0) \
+    if (dtype == SA_DTYPE_F32) {
+        sa::DecodeAttnArgs<float> a{qkv_part, n_slabs, (const float*)qkv_bias, (float*)out, (float*)kcache, (float*)vcache, active_slots, row_len, cs,
+                                    rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        return sa::launch_decode_attn<float>(a, s);
     }
-#define SA_OPD_FLASH(DD, GG) { if (tuning().dattn == 3) SA_OPD_FLASH3(DD, GG) else SA_OPD_FLASH4(DD, GG) }
-#define SA_OPD_MFMA(DD, GG) SA_OPD((decode_attn_mfma_kernel<float, DD, GG>), (decode_attn_mfma_lds<float, DD, GG>()), float)
-    if (dtype == SA_DTYPE_BF16) {          // the dispatch of RecModel::decode_layer
-        if (d == 128 && G <= 5) SA_OPD_FLASH(128, 5)
-        else if (d == 128 && G <= 8) SA_OPD_FLASH(128, 8)
-        else if (d == 64 && G <= 8) SA_OPD_FLASH(64, 8)
-        else if (d == 32 && G <= 8) SA_OPD_FLASH(32, 8)
-        else return SA_ERR_UNSUPPORTED;
-    } else if (dtype == SA_DTYPE_F32) {
-        if (d == 128 && G <= 5) SA_OPD_MFMA(128, 5)
-        else if (d == 128 && G <= 8) SA_OPD_MFMA(128, 8)
-        else if (d == 64 && G <= 8) SA_OPD_MFMA(64, 8)
-        else if (d == 32 && G <= 8) SA_OPD_MFMA(32, 8)
-        else return SA_ERR_UNSUPPORTED;
-    } else {
-        return SA_ERR_UNSUPPORTED;
-    }
-#undef SA_OPD_FLASH
-#undef SA_OPD_FLASH3
-#undef SA_OPD_FLASH4
-#undef SA_OPD_MFMA
-#undef SA_OPD
-    return (int)hipGetLastError();
+    return SA_ERR_UNSUPPORTED;
 }
 
 int surya_op_kv8_quant_rows(int head_dim, const void* kcache, const void* vcache, const int32_t* tok_slot, const int32_t* tok_pos, int n_tokens,
                             void* k8, void* v8t, float* kscale, float* vscale, int kv_heads, int max_kv_len, void* stream) {
     if (!kcache || !vcache || !tok_slot || !tok_pos || !k8 || !v8t || !kscale || !vscale || n_tokens <= 0 || kv_heads <= 0) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int T8 = (max_kv_len + 255) & ~255;
-    dim3 qg(cdiv(n_tokens * kv_heads, 4));
-#define SA_Q8(DD)                                                                                                                  \
-    hipLaunchKernelGGL(kv8_quant_rows_kernel<DD>, qg, dim3(256), 0, s, (const bf16_t*)kcache, (const bf16_t*)vcache, tok_slot, tok_pos, \
-                       n_tokens, (uint8_t*)k8, (uint8_t*)v8t, kscale, vscale, kv_heads, max_kv_len, T8)
-    if (head_dim == 128) SA_Q8(128);
-    else if (head_dim == 64) SA_Q8(64);
-    else if (head_dim == 32) SA_Q8(32);
-    else return SA_ERR_UNSUPPORTED;
-#undef SA_Q8
-    return (int)hipGetLastError();
+    return sa::launch_kv8_quant_rows(head_dim, (const bf16_t*)kcache, (const bf16_t*)vcache, tok_slot, tok_pos, n_tokens, (uint8_t*)k8, (uint8_t*)v8t, kscale,
+                                     vscale, kv_heads, max_kv_len, s);
 }
 
 int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
@@ -1383,25 +1270,9 @@ int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, c
     if (!qkv_part || !qkv_bias || !out || !k8 || !v8t || !kscale || !vscale || !active_slots || !row_len || !rope_cs) return SA_ERR_ARG;
     if (rows <= 0 || n_slabs < 1 || n_slabs > 8 || kv_heads <= 0 || heads % kv_heads) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    const int G = heads / kv_heads, d = head_dim, T8 = (max_kv_len + 255) & ~255;
-    dim3 grid(rows, kv_heads), block(256);
-    const float2* cs = reinterpret_cast<const float2*>(rope_cs);
-#define SA_OPD8(DD, GG)                                                                                                          \
-    {                                                                                                                           \
-        auto kern = decode_attn_kv8_kernel<DD, GG>;                                                                             \
-        static AttrOnce attr;                                                                                                   \
-        attr.ensure(kern, decode_attn_kv8_lds<DD, GG>());                                                                       \
-        hipLaunchKernelGGL(kern, grid, dim3(KV8_THREADS), (decode_attn_kv8_lds<DD, GG>()), s, qkv_part, n_slabs, (const bf16_t*)qkv_bias, \
-                           (bf16_t*)out, (uint8_t*)k8, (uint8_t*)v8t, kscale, vscale, active_slots, row_len, cs, heads, kv_heads, \
-                           max_kv_len, T8, scale, (uint8_t*)nullptr, (uint8_t*)nullptr, 0);                                     \
-    }
-    if (d == 128 && G <= 5) SA_OPD8(128, 5)
-    else if (d == 128 && G <= 8) SA_OPD8(128, 8)
-    else if (d == 64 && G <= 8) SA_OPD8(64, 8)
-    else if (d == 32 && G <= 8) SA_OPD8(32, 8)
-    else return SA_ERR_UNSUPPORTED;
-#undef SA_OPD8
-    return (int)hipGetLastError();
+    sa::DecodeAttnKv8Args a{qkv_part, n_slabs, (const bf16_t*)qkv_bias, (bf16_t*)out, (uint8_t*)k8, (uint8_t*)v8t, kscale, vscale, active_slots, row_len,
+                            reinterpret_cast<const float2*>(rope_cs), rows, heads, kv_heads, head_dim, max_kv_len, scale};
+    return sa::launch_decode_attn_kv8(a, s);
 }
 
 __global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const float* __restrict__ x, int K, uint8_t* __restrict__ q,
@@ -1545,15 +1416,9 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
                      void* stream) {
     if (!x || !w || !y || rows <= 0) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SA_DTYPE_F32)
-        hipLaunchKernelGGL(rmsnorm_kernel<float>, dim3(cdiv(rows, 4)), dim3(256), 0, s, (const float*)x, ldx, (const float*)w,
-                           (float*)y, ldy, (const int*)nullptr, rows, C, eps);
-    else if (dtype == SA_DTYPE_BF16)
-        hipLaunchKernelGGL(rmsnorm_kernel<bf16_t>, dim3(cdiv(rows, 4)), dim3(256), 0, s, (const bf16_t*)x, ldx, (const bf16_t*)w,
-                           (bf16_t*)y, ldy, (const int*)nullptr, rows, C, eps);
-    else
-        return SA_ERR_UNSUPPORTED;
-    return (int)hipGetLastError();
+    if (dtype == SA_DTYPE_F32) return sa::launch_rmsnorm<float>((const float*)x, ldx, (const float*)w, (float*)y, ldy, nullptr, rows, C, eps, s);
+    if (dtype == SA_DTYPE_BF16) return sa::launch_rmsnorm<bf16_t>((const bf16_t*)x, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, nullptr, rows, C, eps, s);
+    return SA_ERR_UNSUPPORTED;
 }
 
 }  // extern "C"

@@ -267,6 +267,11 @@ def test_decode_attn_two_tile_buffers_bit_identical_and_vs_fp32(hip_lib, d, nq, 
     assert worst_kv <= 4e-2
 
 
-def test_decode_attn_fp32_mode_vs_fp32(hip_lib):
-    worst, ref_max, worst_kv = _decode_case(hip_lib, torch.float32, 128, 10, 2, DECODE_LENS, 3, 1024, seed=11)
+@pytest.mark.parametrize("d,nq,nkv", [(128, 10, 2), (64, 8, 2), (32, 4, 2)])
+def test_decode_attn_fp32_mode_vs_fp32(hip_lib, d, nq, nkv):
+    """decode_attn_mfma_kernel<float>: the recogniser's rung, and the two rungs the layout / table decoder runs in fp32 mode on the shapes of
+    test_decode_attn_flash_other_shapes_vs_fp32."""
+    lens, S, Tmax = (DECODE_LENS, 3, 1024) if d == 128 else ([0, 7, 64, 127, 128, 130, 257], 2, 512)
+    worst, ref_max, worst_kv = _decode_case(hip_lib, torch.float32, d, nq, nkv, lens, S, Tmax, seed=11)
+    print(f"fp32 decode attention d={d}: worst {worst:.3e} (bound {2e-5 * ref_max:.3e}), appended rows {worst_kv:.3e} (bound 1e-5)")
     assert worst <= 2e-5 * ref_max and worst_kv <= 1e-5, (worst, worst_kv)
