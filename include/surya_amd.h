@@ -191,7 +191,9 @@ int surya_rec_set_next_tokens(surya_rec* h, const int32_t* slots, const int32_t*
  * consecutive rows are contiguous -- what the GEMM's scale fetch reads in one piece). After this call
  * surya_rec_decode / _decode_async multiply MXFP8 activations (quantised inside the producing kernels) by these weights with
  * v_mfma_scale_f32_32x32x64_f8f6f4; prefill keeps the bf16 weights. table == NULL returns to the bf16 decode path.
- * The caller keeps the tensors alive. Needs dec_hidden, heads * head_dim and intermediate sizes that are multiples of 128. */
+ * The caller keeps the tensors alive. Needs dec_hidden, heads * head_dim and intermediate sizes that are multiples of 128.
+ * Holds at every slot count: above 256 active rows only the GEMM tiles grow (csrc/gemm_mx.h; tuning mx_big_m_split / mx_big_m_gateup),
+ * the split-K slice counts and the K order stay, so a line's tokens, scores and boxes do not depend on the number of active slots. */
 enum { SA_MX_QKV_W = 0, SA_MX_QKV_S, SA_MX_O_W, SA_MX_O_S, SA_MX_GU_W, SA_MX_GU_S, SA_MX_DOWN_W, SA_MX_DOWN_S, SA_MX_COUNT };
 enum { SA_MX_LM_W = 0, SA_MX_LM_S, SA_MX_GLOBALS };      /* after the per-layer entries */
 #define SA_MX_TOTAL(dec_layers) ((dec_layers) * SA_MX_COUNT + SA_MX_GLOBALS)
@@ -256,7 +258,7 @@ int surya_op_gemm_splitk_bf16(const void* X, long ldx, const void* W, long ldw, 
 /* MXFP8 ops (csrc/gemm_mx.h). quantize: fp32 rows [rows][K], K % 128 == 0 -> e4m3 [rows][K] + e8m0 scales K-tile-major
  * [K / 128][rows][4], with the rule every producer kernel uses (block scale = smallest power of two that keeps absmax <=
  * 448, round to nearest even). gemm_mx: C[M,N] fp32 = X W^T from MXFP8 operands (scales K-tile-major with M resp. N rows),
- * M <= 256. mode 0: one pass; mode 1: split-K, `C` receives the slabs [*splitk][M][N] (capacity 8 slabs) and the caller sums
+ * any M (above 256 rows the launchers pick larger tiles, same bits per element). mode 0: one pass; mode 1: split-K, `C` receives the slabs [*splitk][M][N] (capacity 8 slabs) and the caller sums
  * them; mode 2: SwiGLU epilogue -> MXFP8 [M][N/2] in q_out, scales [N / 256][M][4] in sq_out (N % 256 == 0). */
 int surya_op_mx_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* scales, void* stream);
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,

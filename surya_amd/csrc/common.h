@@ -269,6 +269,9 @@ struct Tuning {
                              // 0 = the 64x64 tile of the <= 256-row regime, 2 = 128x128, 3 = 128x64 (slice count unchanged: same bits in every arm)
     int big_m_gateup = -1;   // decode gate|up above 256 rows: -1 = by rows (8-phase 256x256 tile at 4-6 row blocks, else the generic choice), 0 = generic,
                              // 1 = persistent 8-phase loop, 2 = 8-phase tile per workgroup
+    int mx_big_m_split = -1; // MXFP8 decode projections above 256 rows (round 10, gemm_mx.h): -1 = by workgroup count (as big_m_split), 0 = 64x64 always, 2 = 128x128, 3 = 128x64
+                             // (4-stage ring; slice count unchanged: same bits in every arm)
+    int mx_big_m_gateup = -1; // MXFP8 decode gate|up above 256 rows: -1 = measured best (128x128 at every row count), 0 = 64x64, 1 = 128x128, 2 = 256x256 on four waves (loses; same bits in every arm)
     int gateup_ring = 2;     // decode gate|up (64x64 tiles, M in (128, 256]): LDS stages of its direct-to-LDS loop (2 = unrolled pair, 3 / 4 = ring with counted vmcnt)
     int dring = 1;           // decode gate|up and long-slice split-K projections (bf16, 128 < M <= 256) on the loader / consumer LDS ring (gemm_ring.h):
                              // 0 = the gemm_nt_kernel tiles, 1 = ring, 2 = ring with non-temporal weight loads; + 4 = also at M <= 128 (tests). Same bits in every arm

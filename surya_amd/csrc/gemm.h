@@ -1463,7 +1463,10 @@ static inline int launch_gemm_cfg(const GemmArgs<TI, TO>& a, hipStream_t s) {
     int tiles = SPLIT ? cdiv(cdiv(a.N, BN) * a.splitk, 8) * 8 * cdiv(a.M, BM) : cdiv(a.M, BM) * cdiv(a.N, BN);
     a.bn_used = BN;
     GemmArgs<TI, TO> aa = a;
-    if (!SPLIT && BM >= 128 && BN >= 128) {          // XCD-aware super-tiles for the large-tile configurations
+    // (not under mgroup: the kernel applies the super-tile mapping AFTER the mgroup one, over a grid of another size -- with both set, a
+    // launch whose column-tile count is no multiple of 8 left tiles uncomputed: REC-SMALL's lm_head at 320 rows, 218 tiles of 320 columns,
+    // returned stale greedy partials. REC-FULL's 256 column tiles happened to be covered either way.)
+    if (!SPLIT && !a.mgroup && BM >= 128 && BN >= 128) {          // XCD-aware super-tiles for the large-tile configurations
         const int tm = cdiv(a.M, BM), tn = cdiv(a.N, BN);
         constexpr int GRP = ((BM + BN) * 128 * (GLDS > 2 && GLDS != 8 ? GLDS : 2) > 80 * 1024) ? 32 : 64;
         if (tm * tn >= 8 * GRP) {

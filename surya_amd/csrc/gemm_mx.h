@@ -24,8 +24,12 @@
 // As in gemm.h the WEIGHT fragment is the first MFMA operand (result D[n][m]: a lane owns 4 consecutive columns of one row).
 //
 // Epilogues: split-K fp32 slabs (consumers: decode attention, reduce + norm), SwiGLU -> MXFP8 (the next GEMM's operand,
-// quantised from the fp32 accumulators: a 64-column tile yields exactly one 32-wide block per row), greedy-argmax partials
-// (lm_head), plain fp32 (tests).
+// quantised from the fp32 accumulators: every 64-column group of a tile yields exactly one 32-wide block per row), greedy-argmax
+// partials (lm_head), plain fp32 (last_logits, tests).
+//
+// Rows: any M. Up to 256 rows the tiles are 64 x 64 (128 x 128 for the lm_head); above, the launchers at the end of this file pick
+// 128 x 128 / 128 x 64 split-K tiles and a 128 x 128 or 256 x 256 gate|up tile (round 10). Slice counts depend on
+// (N, K) only and every tile walks K in the same order, so an output element has the same bits whatever tile computed it.
 #pragma once
 #include "gemm.h"
 
@@ -253,22 +257,29 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs p) {
         if (part == 0 && m0 + row < p.M) p.amax[(long)(m0 + row) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
         return;
     } else if constexpr (SWIGLU) {
-        // MXFP8 output: one 32-wide block per (row, tile) at BN = 64. TPR = 4 adjacent lanes share a row, 8 values each.
-        static_assert(BN == 64 && BM == 64, "SwiGLU -> MX epilogue is written for the 64x64 tile");
-        const int row = tid >> 2, part = tid & 3;
-        const unsigned char* rowp = smem + row * ROWB;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(rowp + (((2 * part) ^ (row & XM)) << 4));
-        const f32x4 b = *reinterpret_cast<const f32x4*>(rowp + (((2 * part + 1) ^ (row & XM)) << 4));
-        float m = fmaxf(fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))),
-                        fmaxf(fmaxf(fabsf(b[0]), fabsf(b[1])), fmaxf(fabsf(b[2]), fabsf(b[3]))));
-        m = quad_max(m);
-        const int e = mx_block_exp(m);
-        const uint32_t q0 = mx_pack4(ldexpf(a[0], -e), ldexpf(a[1], -e), ldexpf(a[2], -e), ldexpf(a[3], -e));
-        const uint32_t q1 = mx_pack4(ldexpf(b[0], -e), ldexpf(b[1], -e), ldexpf(b[2], -e), ldexpf(b[3], -e));
-        const int mrow = m0 + row, nout = n0 / 2;                  // N / 2 % 32 == 0 is checked by the launcher
-        if (mrow < p.M && nout < p.N / 2) {
-            *reinterpret_cast<uint2*>(p.Q + (long)mrow * p.ldq + nout + part * 8) = make_uint2(q0, q1);
-            if (part == 0) p.SQ[((long)(nout >> 7) * p.sq_rows + mrow) * 4 + ((nout >> 5) & 3)] = (uint8_t)(e + 127);
+        // MXFP8 output: every 64-column group of the tile yields one 32-wide block per row (its scale byte at
+        // [(n_out >> 7)][row][(n_out >> 5) & 3]). 4 adjacent lanes share a (row, block), 8 values each; BM * BN / 64 blocks per
+        // tile, 64 of them per pass, so every lane of a quad takes part in every pass (BM % 64 == 0). At 64 x 64 this is the one
+        // pass of the first version: row = tid >> 2, block 0.
+        constexpr int NBLK = BN / 64;
+        const int part = tid & 3;
+#pragma unroll 2
+        for (int it = 0; it < BM * NBLK / 64; ++it) {
+            const int rb = it * 64 + (tid >> 2), row = rb / NBLK, blk = rb % NBLK;
+            const unsigned char* rowp = smem + row * ROWB;
+            const f32x4 a = *reinterpret_cast<const f32x4*>(rowp + (((blk * 8 + 2 * part) ^ (row & XM)) << 4));
+            const f32x4 b = *reinterpret_cast<const f32x4*>(rowp + (((blk * 8 + 2 * part + 1) ^ (row & XM)) << 4));
+            float m = fmaxf(fmaxf(fmaxf(fabsf(a[0]), fabsf(a[1])), fmaxf(fabsf(a[2]), fabsf(a[3]))),
+                            fmaxf(fmaxf(fabsf(b[0]), fabsf(b[1])), fmaxf(fabsf(b[2]), fabsf(b[3]))));
+            m = quad_max(m);
+            const int e = mx_block_exp(m);
+            const uint32_t q0 = mx_pack4(ldexpf(a[0], -e), ldexpf(a[1], -e), ldexpf(a[2], -e), ldexpf(a[3], -e));
+            const uint32_t q1 = mx_pack4(ldexpf(b[0], -e), ldexpf(b[1], -e), ldexpf(b[2], -e), ldexpf(b[3], -e));
+            const int mrow = m0 + row, nout = n0 / 2 + blk * 32;        // N / 2 % 32 == 0 is checked by the launcher
+            if (mrow < p.M && nout < p.N / 2) {
+                *reinterpret_cast<uint2*>(p.Q + (long)mrow * p.ldq + nout + part * 8) = make_uint2(q0, q1);
+                if (part == 0) p.SQ[((long)(nout >> 7) * p.sq_rows + mrow) * 4 + ((nout >> 5) & 3)] = (uint8_t)(e + 127);
+            }
         }
         return;
     } else {
@@ -288,7 +299,7 @@ static inline int launch_gemm_mx_cfg(const MxArgs& a, hipStream_t s) {
     const int tiles = cdiv(cdiv(a.N, BN) * a.splitk, 8) * 8 * cdiv(a.M, BM);
     a.bn_used = BN;
     constexpr size_t stage_bytes = (size_t)((BM + BN) * 132) * STAGES;
-    constexpr size_t out_bytes = (size_t)BM * BN * 4;
+    constexpr size_t out_bytes = (size_t)BM * BN * ((EPI == MX_EPI_SWIGLU && !SPLIT) ? 2 : 4);     // SwiGLU stages BN / 2 columns
     constexpr size_t lds = stage_bytes > out_bytes ? stage_bytes : out_bytes;
     static_assert(lds <= 160 * 1024, "LDS");
     auto kern = gemm_mx_kernel<BM, BN, EPI, SPLIT, STAGES>;
@@ -312,6 +323,12 @@ static inline int launch_gemm_mx_cfg(const MxArgs& a, hipStream_t s) {
     return (int)hipGetLastError();
 }
 
+// gate|up tile above 256 rows when Tuning::mx_big_m_gateup is -1 (0 = 64 x 64, 1 = 128 x 128, 2 = 256 x 256): 128 x 128 at every row count.
+// Measured on the REC-FULL decode step (tools/microbench/decode_sweep.py --fp8 --configs mxbigm, profiles/r10_a_*): against 64 x 64 the
+// 128 x 128 tile takes 12 us off the step at 512 rows and 43 us at 1024; the 256 x 256 tile on four waves (one wave per SIMD, 2 x 40 /
+// 4 x 40 workgroups) LOSES 220 us at 512 rows and 22 us at 1024 -- unlike bf16, whose 8-phase 256 x 256 tile wins at 1024 rows.
+static inline int mx_gateup_pick(int /*M*/, int /*N*/) { return 1; }
+
 static inline int mx_check(const MxArgs& a) {
     if (a.K % 128 != 0 || a.N % 4 != 0 || a.ldx % 16 != 0 || a.ldw % 16 != 0 || !a.X || !a.W || !a.SX || !a.SW || a.sx_rows < a.M ||
         a.sw_rows < a.N)
@@ -319,30 +336,50 @@ static inline int mx_check(const MxArgs& a) {
     return SA_OK;
 }
 
-// Non-split launches of the decode regime (M <= 256): 64x64 tiles, 128x128 for lm_head-sized N (the bf16 path's choice).
-// LDS ring depths (4 split-K / 3 gate|up / 2 lm_head) were swept on the decode step (profiles/r02_fp8_decode.md): deeper rings
-// (6, 8 stages) LOSE 20-100 us per step -- a bigger LDS footprint keeps the next kernel's workgroups from moving in beside
-// the tail of this one -- and shallower ones are flat (gate|up 2 stages) or lose (split-K 2 stages: +115 us).
+// Non-split launches. M <= 256 (the decode regime the path was built for): 64x64 tiles, 128x128 for lm_head-sized N (the bf16
+// path's choice). LDS ring depths (4 split-K / 3 gate|up / 2 lm_head) were swept on the decode step (profiles/r02_fp8_decode.md):
+// deeper rings (6, 8 stages) LOSE 20-100 us per step -- a bigger LDS footprint keeps the next kernel's workgroups from moving in
+// beside the tail of this one -- and shallower ones are flat (gate|up 2 stages) or lose (split-K 2 stages: +115 us).
+// Above 256 rows (round 10) only the tile grows: every tile walks K in 128-element K-tiles of two 64-deep MFMA steps, in order, so an
+// output element has the same bits whatever tile computed it, and the lm_head column-block width stays a function of N alone
+// (a line's (max, sum-exp) partials do not depend on M). Tuning::mx_big_m_gateup picks the gate|up tile.
 template <int EPI>
 static inline int launch_gemm_mx(const MxArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return SA_OK;
     if (int rc = mx_check(a)) return rc;
-    if (a.M > 256) return SA_ERR_UNSUPPORTED;
     if constexpr (EPI == MX_EPI_SWIGLU) {
         if (a.N % 256 != 0 || !a.Q || !a.SQ || a.ldq % 8 != 0 || a.sq_rows < a.M) return SA_ERR_SHAPE;   // N / 2 = whole 128-wide K-tiles of the next GEMM
+        if (a.M > 256) {
+            const int mode = tuning().mx_big_m_gateup;      // -1 = by rows, 0 = 64 x 64, 1 = 128 x 128, 2 = 256 x 256
+            const int pick = mode >= 0 ? mode : mx_gateup_pick(a.M, a.N);
+            if (pick == 2) return launch_gemm_mx_cfg<256, 256, EPI, false, 2>(a, s);
+            if (pick == 1) return launch_gemm_mx_cfg<128, 128, EPI, false, 2>(a, s);
+        }
         return launch_gemm_mx_cfg<64, 64, EPI, false, 3>(a, s);
     } else {
         if (a.N >= 64 * 512) return launch_gemm_mx_cfg<128, 128, EPI, false, 2>(a, s);
+        if constexpr (EPI == MX_EPI_F32) {
+            if (a.M > 256) return launch_gemm_mx_cfg<128, 128, EPI, false, 2>(a, s);
+        }
         return launch_gemm_mx_cfg<64, 64, EPI, false, 3>(a, s);
     }
 }
 
 // Split-K launch: slice count from (N, K) only, K-tiles are 128 elements here (pick_splitk counts 128-BYTE tiles: same number).
+// Above 256 rows the 64 x 64 tile re-reads every W slice once per 64 rows; the slice count stays what it is and only the tile
+// grows, picked by workgroup count as launch_gemm_splitk does for bf16 (Tuning::mx_big_m_split forces an arm).
 static inline int launch_gemm_mx_splitk(MxArgs& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return SA_OK;
     if (int rc = mx_check(a)) return rc;
-    if (!a.part || a.M > 256) return SA_ERR_SHAPE;
+    if (!a.part) return SA_ERR_SHAPE;
     a.splitk = pick_splitk(cdiv(a.N, 64), a.K / 128);
+    if (a.M > 256) {
+        const int mode = tuning().mx_big_m_split;           // -1 = by workgroup count, 0 = 64 x 64 always, 2 = 128 x 128, 3 = 128 x 64
+        const int w128 = cdiv(a.M, 128) * cdiv(a.N, 128) * a.splitk, w12864 = cdiv(a.M, 128) * cdiv(a.N, 64) * a.splitk;
+        const int pick = mode >= 0 ? mode : (w128 >= 136 ? 2 : (w12864 <= 256 ? 3 : 0));
+        if (pick == 2) return launch_gemm_mx_cfg<128, 128, MX_EPI_F32, true, 4>(a, s);
+        if (pick == 3) return launch_gemm_mx_cfg<128, 64, MX_EPI_F32, true, 4>(a, s);
+    }
     return launch_gemm_mx_cfg<64, 64, MX_EPI_F32, true, 4>(a, s);
 }
 

@@ -1346,7 +1346,7 @@ int surya_set_tuning(const char* key, int value) {
     Tuning& t = tuning();
     struct { const char* k; int* v; } tab[] = {
         {"graph", &t.graph}, {"split_target", &t.split_target}, {"split_min_kt", &t.split_min_kt}, {"split_max", &t.split_max},
-        {"bigtile", &t.bigtile}, {"bigtile_any", &t.bigtile_any}, {"conv_lean", &t.conv_lean}, {"conv_persist", &t.conv_persist}, {"dwconv_pipe", &t.dwconv_pipe}, {"bigtile_ratio_pct", &t.bigtile_ratio_pct}, {"gateup_ring", &t.gateup_ring}, {"dring", &t.dring}, {"dring_min_kt", &t.dring_min_kt}, {"big_m_split", &t.big_m_split}, {"big_m_gateup", &t.big_m_gateup}, {"glds", &t.glds}, {"bigtile_min_k", &t.bigtile_min_k}, {"dattn", &t.dattn}, {"rnorm", &t.rnorm},
+        {"bigtile", &t.bigtile}, {"bigtile_any", &t.bigtile_any}, {"conv_lean", &t.conv_lean}, {"conv_persist", &t.conv_persist}, {"dwconv_pipe", &t.dwconv_pipe}, {"bigtile_ratio_pct", &t.bigtile_ratio_pct}, {"gateup_ring", &t.gateup_ring}, {"dring", &t.dring}, {"dring_min_kt", &t.dring_min_kt}, {"big_m_split", &t.big_m_split}, {"big_m_gateup", &t.big_m_gateup}, {"mx_big_m_split", &t.mx_big_m_split}, {"mx_big_m_gateup", &t.mx_big_m_gateup}, {"glds", &t.glds}, {"bigtile_min_k", &t.bigtile_min_k}, {"dattn", &t.dattn}, {"rnorm", &t.rnorm},
         {"ghead", &t.ghead}, {"fuse_embed", &t.fuse_embed}, {"persist", &t.persist}, {"lmhead", &t.lmhead}, {"kvprefetch", &t.kvprefetch},
         {"dattn_db", &t.dattn_db}, {"lay_ln", &t.lay_ln}, {"det_head_blk", &t.det_head_blk}, {"det_fuse", &t.det_fuse}, {"det_up4", &t.det_up4}, {"fmb_chunk", &t.fmb_chunk}, {"ocrerr_cls_only", &t.ocrerr_cls_only}};
     for (auto& e : tab)

@@ -80,7 +80,8 @@ class HipRecModel:
     def set_decode_fp8(self, on: bool):
         """Decode steps on MXFP8 weights and activations (surya_rec_set_mx_weights; bf16 models only). The e4m3 / e8m0 twins
         of the decoder projections and lm_head are quantised once from the kernel-layout bf16 table and stay resident next to
-        it (prefill keeps using the bf16 weights)."""
+        it (prefill keeps using the bf16 weights). Holds at every slot count: above 256 active slots the MXFP8 GEMMs take larger tiles
+        (csrc/gemm_mx.h) with the same split-K slices and K order, so a line's results do not depend on recognition_batch_size."""
         if on and self.dtype != torch.bfloat16:
             raise ValueError("the fp8 decode path exists for bfloat16 models only")
         if on:
@@ -97,7 +98,8 @@ class HipRecModel:
     def set_kv_fp8(self, on: bool):
         """Decode steps on an FP8 (e4m3 + one power-of-two scale per token and kv head) KV cache (surya_rec_set_kv_fp8,
         csrc/decode_attn_kv8.h; bf16 models only). Prefill still attends over the bf16 cache; lines prefilled after the call decode
-        from the fp8 arrays. Switch while no line is in flight."""
+        from the fp8 arrays. Switch while no line is in flight. One workgroup per (row, kv head): no slot limit, alone or together with
+        set_decode_fp8 (tests/test_gpu_fp8_slots.py runs both at 512 slots)."""
         if on and self.dtype != torch.bfloat16:
             raise ValueError("the fp8 KV cache exists for bfloat16 models only")
         L.check(self.lib.surya_rec_set_kv_fp8(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_kv_fp8")

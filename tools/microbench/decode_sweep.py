@@ -5,9 +5,13 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
+`--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
+`mxbigm` (with --fp8 --slots 512 / 1024): the MXFP8 tiles above 256 rows (mx_big_m_split x mx_big_m_gateup), arm 0 = everything
+64 x 64 run twice, the default twice, and the bf16 default of the same build as the last arm. Tokens are compared with the first
+arm of the same arithmetic (fp8 with fp8, bf16 with bf16).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -34,6 +38,7 @@ def main():
     ap.add_argument("--steps", type=int, default=32)
     ap.add_argument("--slots", type=int, default=256)
     ap.add_argument("--configs", default="all")
+    ap.add_argument("--fp8", action="store_true", help="run every arm on the MXFP8 decode path (set_decode_fp8(True))")
     args = ap.parse_args()
     from surya_amd import _lib as L
     from surya_amd.config import rec_config
@@ -57,7 +62,8 @@ def main():
         for k, v in kw.items():
             L.check(lib.surya_set_tuning(k.encode(), C.c_int(v)), f"surya_set_tuning({k})")
 
-    base = dict(graph=0, split_target=256, split_min_kt=4, split_max=8, dattn=4, rnorm=2, ghead=2, fuse_embed=1, lmhead=1, kvprefetch=0, gateup_ring=2, big_m_split=-1, big_m_gateup=-1)
+    base = dict(graph=0, split_target=256, split_min_kt=4, split_max=8, dattn=4, rnorm=2, ghead=2, fuse_embed=1, lmhead=1, kvprefetch=0, gateup_ring=2, big_m_split=-1, big_m_gateup=-1,
+                mx_big_m_split=-1, mx_big_m_gateup=-1)
     if args.configs == "base":
         variants = [dict()]
     elif args.configs == "fewer":        # fewer, longer split-K slices for the bf16 path
@@ -72,6 +78,10 @@ def main():
         variants = [dict(big_m_split=0, big_m_gateup=0), dict(), dict(big_m_split=2, big_m_gateup=0), dict(big_m_split=3, big_m_gateup=0),
                     dict(big_m_split=0, big_m_gateup=2), dict(big_m_split=2, big_m_gateup=2), dict(big_m_split=2, big_m_gateup=1),
                     dict(big_m_split=0, big_m_gateup=0), dict()]
+    elif args.configs == "mxbigm":       # round 10: MXFP8 tiles above 256 rows (run with --fp8 --slots 512 / 1024), arm 0 and the default twice, bf16 last
+        variants = [dict(mx_big_m_split=0, mx_big_m_gateup=0), dict()]
+        variants += [dict(mx_big_m_split=sp, mx_big_m_gateup=gu) for gu in (0, 1, 2) for sp in (0, 2, 3) if (sp, gu) != (0, 0)]
+        variants += [dict(mx_big_m_split=0, mx_big_m_gateup=0), dict(), dict(fp8=0)]
     elif args.configs == "pf":           # K/V prefetch workgroups in the reduce kernels, on / off, interleaved
         variants = [dict(kvprefetch=1), dict(), dict(kvprefetch=1), dict(), dict(lmhead=2, kvprefetch=1), dict(lmhead=2)]
     elif args.configs == "fp8only":
@@ -102,19 +112,17 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / n_steps, (time.perf_counter() - t0) * 1e6 / n_steps, np.concatenate(toks)
 
-    ref = None
-    print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == config 0")
+    ref = {}
+    print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == first arm of the same arithmetic")
     for v in variants:
         v = dict(v)
-        m.set_decode_fp8(bool(v.pop("fp8", 0)))
+        m.set_decode_fp8(bool(v.pop("fp8", int(args.fp8))))
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        if ref is None:
-            ref = best[2]
-        same = float((best[2] == ref).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault(v["fp8"], best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
