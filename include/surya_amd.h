@@ -14,8 +14,8 @@
  *   - all work is enqueued on the hipStream_t passed in (as void*); functions do not synchronise unless
  *     documented ("sync"). A handle is re-entrant but not thread-safe: one host thread per handle, like the
  *     reference's single-threaded device path (surya/settings.py:179-183).
- *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (text detector and
- *     surya_op_gemm only; every other engine returns SA_ERR_UNSUPPORTED for it).
+ *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (the text detector, the
+ *     OCR-error classifier, surya_op_gemm and surya_op_attn; every other engine returns SA_ERR_UNSUPPORTED for it).
  */
 #ifndef SURYA_AMD_H
 #define SURYA_AMD_H
@@ -216,8 +216,9 @@ int surya_rec_set_kv_fp8(surya_rec* h, int on);
  * C is [M,N/2]), 4 hardswish, 5 relu, 8 geglu = gelu_tanh(gate) * up with gate, up and the gelu each rounded to the compute dtype
  * (the ADETR decoder's MLP, W rows interleaved like swiglu, C is [M,N/2]; fp32 and bf16 only, no bias, no R, out_f32 == 0).
  * Codes 6 and 7 are epilogues of the recogniser that take further operands and are not reachable here: SA_ERR_ARG.
- * out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the detector's epilogues (0, 1, 4, 5) with fp16
- * output only; anything else returns SA_ERR_UNSUPPORTED. */
+ * out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the detector's epilogues (0, 1, 4, 5) and the
+ * OCR-error classifier's gelu (2: the projection rounded to fp16, erf GELU, rounded; no R) with fp16 output only; anything else returns
+ * SA_ERR_UNSUPPORTED. */
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,
                   const void* bias, const void* R, long ldr, int M, int N, int K, void* stream);
 int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, int rows, int C, float eps,
@@ -225,7 +226,7 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
 /* Attention kernels by themselves (tests against fp32 PyTorch SDPA; synchronous -- the call returns after the kernel ran).
  * surya_op_attn: segment attention = the vision encoder's window / whole-image attention (non-causal varlen,
  * surya/common/surya/encoder/__init__.py:238-261) and the decoder prefill's causal GQA (decoder/__init__.py:101-128).
- * dtype bf16 runs attn_mfma_kernel<head_dim>, fp32 runs attn_valu_kernel (reference mode). Segment s has seg_len[s] queries
+ * dtype bf16 and fp16 run attn_mfma_kernel<T, head_dim> (both forms, causal or not), fp32 runs attn_valu_kernel (reference mode). Segment s has seg_len[s] queries
  * and keys; its first query / key / value / output row starts at element offset q_off / k_off / v_off / o_off[s] (host
  * arrays) of q / k / v / out (device), rows `*_row` elements apart, heads `*_head` elements apart; query head h reads kv
  * head h / group. head_dim in {32, 64, 80, 128}.
@@ -568,13 +569,15 @@ typedef struct surya_ocrerr_config {
 } surya_ocrerr_config;
 /* Weight table: SA_OW_* globals, then SA_OL_COUNT entries per layer. Every entry is in the compute dtype. WORD [vocab][dim],
  * POS [max_pos][dim] (learned, or the sin-cos table built by the caller), PRE [dim][dim], CLS [num_labels][dim]; per layer QKV_W =
- * q_lin | k_lin | v_lin rows fused [3 dim][dim] (q rows and bias already multiplied by 1 / sqrt(head_dim) when that is a power of two,
- * see SA_OCRERR_Q_PRESCALED), OUT [dim][dim], LIN1 [hidden][dim], LIN2 [dim][hidden], LN weights / biases [dim]. */
+ * q_lin | k_lin | v_lin rows fused [3 dim][dim] (q rows and bias already multiplied by 1 / sqrt(head_dim) when that is a power of two and
+ * the dtype is fp32 or bf16, see SA_OCRERR_Q_PRESCALED; an fp16 table carries the reference's q rows as they are), OUT [dim][dim], LIN1 [hidden][dim], LIN2 [dim][hidden], LN weights / biases [dim]. */
 enum { SA_OW_WORD = 0, SA_OW_POS, SA_OW_EMB_LN_W, SA_OW_EMB_LN_B, SA_OW_PRE_W, SA_OW_PRE_B, SA_OW_CLS_W, SA_OW_CLS_B, SA_OW_GLOBALS };
 enum { SA_OL_QKV_W = 0, SA_OL_QKV_B, SA_OL_OUT_W, SA_OL_OUT_B, SA_OL_SA_LN_W, SA_OL_SA_LN_B, SA_OL_LIN1_W, SA_OL_LIN1_B, SA_OL_LIN2_W,
        SA_OL_LIN2_B, SA_OL_OUT_LN_W, SA_OL_OUT_LN_B, SA_OL_COUNT };
-/* head_dim 64: the caller folds the exact 1 / 8 into the q rows; other head dims pass the scale to attention (it is applied to q there) */
-#define SA_OCRERR_Q_PRESCALED(head_dim) ((head_dim) == 64)
+/* head_dim 64 in fp32 / bf16: the caller folds the 1 / 8 into the q rows (exact: a power of two, and neither format has a subnormal
+ * range a weight reaches). fp16 never folds: a q weight below 8 x 2^-14 = 4.9e-4 would become subnormal and lose significand bits.
+ * Unfolded tables (fp16, other head dims) have the engine pass 1 / sqrt(head_dim) to attention, which applies it to the fp32 scores. */
+#define SA_OCRERR_Q_PRESCALED(head_dim, dtype) ((head_dim) == 64 && (dtype) != SA_DTYPE_F16)
 
 typedef struct surya_ocrerr surya_ocrerr;
 int surya_ocrerr_create(const surya_ocrerr_config* cfg, const void* const* weights, int n_weights, surya_ocrerr** out);

@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.so")   # env: A/B builds of the kernels
 
 SA_MAX_STEPS = 16
-DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: the detector and surya_op_gemm only
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: the detector, the OCR-error classifier, surya_op_gemm / surya_op_attn
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
  RW_LM_B, RW_BBOX_W, RW_BBOX_B, RW_ENC_INVFREQ, RW_DEC_INVFREQ, RW_GLOBALS) = range(17)
 (RE_NORM1, RE_QKV_W, RE_QKV_B, RE_PROJ_W, RE_PROJ_B, RE_NORM2, RE_GU_W, RE_GU_B, RE_DOWN_W, RE_DOWN_B, RE_COUNT) = range(11)

@@ -5,6 +5,7 @@
 #include <cstdlib>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
 
 #include "../../include/surya_amd.h"
 
@@ -221,9 +222,32 @@ __device__ __forceinline__ float gelu_erf_f(float x) { return 0.5f * x * (1.0f +
 // has matrix time. Abramowitz-Stegun 7.1.26 instead: erfc(z) = t (a1 + t (a2 + t (a3 + t (a4 + t a5)))) exp(-z^2), t = 1 / (1 + p z), |error| <
 // 1.5e-7 absolute on erf -- three orders below a bf16 rounding step of the result; x < 0 takes 1 + erf(x) = erfc(|x|) directly (no
 // cancellation). Every bf16 tile shape uses this one function; fp32 reference mode keeps erff.
+// fp16 (the OCR-error classifier's lin1): the reference's order in full -- the projection rounded to fp16 (a Linear output; overflow
+// to +-inf as .half()), the erf GELU of that value, the store's rounding. The bf16 form below skips the first rounding and its erfc is
+// good to 1.5e-7 ABSOLUTE: far below a bf16 step, but fp16 has three more significand bits and normal numbers down to 6e-5, and in the
+// tail x < -3.4 (results of -6e-4 and smaller, erfc below 7.5e-4) that form misses by whole steps. Here erfc(z) = t exp(-z^2 + P9(t)),
+// t = 1 / (1 + z / 2): the Chebyshev fit of Numerical Recipes' erfcc, RELATIVE error < 1.2e-7 for every z >= 0 -- the same rcp + exp as
+// the bf16 form and five more fused multiply-adds. Every finite fp16 input gives the correctly rounded result or its neighbour (all
+// 63488 checked on the host). x < 0 takes erfc(|x| / sqrt 2) directly, x >= 0 takes 2 - erfc: no cancellation on either side. The
+// multiply-adds are written out: a value must not depend on how the compiler contracts them in one tile shape or another.
 template <typename TI>
 __device__ __forceinline__ float gelu_epi(float x) {
-    if constexpr (sizeof(TI) == 2) {
+    if constexpr (std::is_same<TI, fp16_t>::value) {
+        const float xr = Ty<fp16_t>::rnd(x);
+        const float z = fabsf(xr) * 0.70710678118654752440f;
+        const float t = __builtin_amdgcn_rcpf(fmaf(0.5f, z, 1.0f));
+        float p = fmaf(t, 0.17087277f, -0.82215223f);
+        p = fmaf(t, p, 1.48851587f);
+        p = fmaf(t, p, -1.13520398f);
+        p = fmaf(t, p, 0.27886807f);
+        p = fmaf(t, p, -0.18628806f);
+        p = fmaf(t, p, 0.09678418f);
+        p = fmaf(t, p, 0.37409196f);
+        p = fmaf(t, p, 1.00002368f);
+        p = fmaf(t, p, -1.26551223f);
+        const float e = t * __expf(fmaf(-z, z, p));                         // erfc(|x| / sqrt 2) in [0, 1]; 0 at x = +-inf
+        return 0.5f * xr * (xr < 0.f ? e : 2.0f - e);
+    } else if constexpr (sizeof(TI) == 2) {
         const float z = fabsf(x) * 0.70710678118654752440f;
         const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f, z, 1.0f));
         const float poly = t * fmaf(t, fmaf(t, fmaf(t, fmaf(t, 1.061405429f, -1.453152027f), 1.421413741f), -0.284496736f), 0.254829592f);
@@ -310,8 +334,10 @@ struct Tuning {
     int persist = 1;         // 256x256 bf16 GEMMs (>= 4 even K-tiles) as the PERSISTENT 8-phase loop (gemm_nt_p8p_kernel: the half-tile ring runs on across
                              // tiles, wave-private epilogue): 1 = on (round 5: +3...10 % per encoder / prefill shape once the two wave groups were
                              // re-aligned around the epilogue, +0.9 % on the bench's recognition leg); 0 = one tile per workgroup
-    int ocrerr_cls_only = 1; // OCR-error classifier (ocr_error_model.hip): 1 = the last layer after its QKV projection runs for the [CLS] rows only (cls_attn_kernel,
-                             // out_lin / LayerNorms / FFN at M = texts), 0 = the full last layer and a gather of the [CLS] rows (the checker / A/B arm)
+    int ocrerr_cls_only = 1; // OCR-error classifier (ocr_error_model.hip): 1 = the last layer after its QKV projection runs for the [CLS] rows only (cls_attn_kernel
+                             // in bf16, the first query tile on the full layer's attention kernel in fp32 and fp16: the same bits as 0; out_lin / LayerNorms / FFN at
+                             // M = texts), 2 = as 1 with cls_attn_kernel in fp16 too (A/B arm: equal to rounding only), 0 = the full last layer and a gather of the
+                             // [CLS] rows (the checker / A/B arm)
 };
 inline Tuning& tuning() { static Tuning t; return t; }
 inline int& tuning_epoch() { static int e = 0; return e; }   // bumped by surya_set_tuning whenever a knob changes value

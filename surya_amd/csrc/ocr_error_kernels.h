@@ -94,38 +94,42 @@ __global__ void gather_rows_kernel(const T* __restrict__ x, const int* __restric
 }
 
 // Attention of ONE query per text -- its [CLS] row, the only row the classification head reads (encoder.py:760-761) -- over the text's
-// L <= max_pos keys, every head; bf16 mode. One workgroup per text, shaped like a decode step: the packed qkv rows [T][3 dim]
-// (q | k | v, head h at columns h * D) of the text are read once.
-//   scores   item (key j, head h) per thread, fp32 dot products of the bf16 q and k rows, kept in LDS;
+// L <= max_pos keys, every head; the 16-bit modes (T = bf16_t or fp16_t through Ty<T> / H16<T>: bf16's last layer, fp16's at
+// ocrerr_cls_only = 2). One workgroup per text, shaped like a decode step: the packed qkv rows [T][3 dim] (q | k | v, head h at columns
+// h * D) of the text are read once.
+//   scores   item (key j, head h) per thread, fp32 dot products of the 16-bit q and k rows, kept in LDS;
 //   softmax  a wave per head walks the keys in 64-key chunks with the running max of attn_mfma_kernel (the same chunk boundaries, so
-//            the same max at every chunk) and rounds the un-normalised exp() values to bf16 as that kernel rounds its P fragment;
+//            the same max at every chunk) and rounds the un-normalised exp() values to T as that kernel rounds its P fragment (fp16:
+//            entries below 2^-14 become subnormals, as there);
 //            the row sum takes the unrounded values, as there; chunk c's P is later scaled by exp(m_c - m_final) / l;
 //   P V      a thread per pair of output columns, keys in order, fp32 sums.
-// The score and P V sums associate differently from the MFMA kernel: agreement to fp32 rounding of the bf16 inputs, not to the bit.
+// The score and P V sums associate differently from the MFMA kernel: agreement to fp32 rounding of the 16-bit inputs, not to the bit
+// (which is why fp16, whose finer steps such a difference crosses 8x as often as bf16's, takes the MFMA kernel by default).
 // LDS: q [dim] + P [heads][NC * 64] + chunk factors [heads][NC] floats (dynamic; the host sizes it for max_pos).
-template <int D>
-__global__ __launch_bounds__(256) void cls_attn_kernel(const bf16_t* __restrict__ qkv, const int* __restrict__ starts, const int* __restrict__ lens,
-                                                       bf16_t* __restrict__ out, int dim, int heads, float scale) {
+template <typename T, int D>
+__global__ __launch_bounds__(256) void cls_attn_kernel(const T* __restrict__ qkv, const int* __restrict__ starts, const int* __restrict__ lens,
+                                                       T* __restrict__ out, int dim, int heads, float scale) {
+    static_assert(sizeof(T) == 2, "16-bit storage types");
     extern __shared__ __attribute__((aligned(16))) float cls_sm[];
     const int t = blockIdx.x, L = lens[t], tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int NC = (L + 63) / 64, Lp = NC * 64;
     const long ld = 3L * dim;
-    const bf16_t* base = qkv + (long)starts[t] * ld;
+    const T* base = qkv + (long)starts[t] * ld;
     float* qs = cls_sm;
     float* ps = qs + dim;
     float* fac = ps + (long)heads * Lp;
-    for (int c = tid; c < dim; c += 256) qs[c] = bf2f(base[c]);
+    for (int c = tid; c < dim; c += 256) qs[c] = Ty<T>::ld(base + c);
     __syncthreads();
     for (int it = tid; it < heads * L; it += 256) {
         const int j = it / heads, h = it - j * heads;
-        const bf16_t* kr = base + (long)j * ld + dim + h * D;
+        const T* kr = base + (long)j * ld + dim + h * D;
         const float* qh = qs + h * D;
         float s = 0.f;
 #pragma unroll
         for (int d = 0; d < D; d += 8) {
             const uint4 raw = *reinterpret_cast<const uint4*>(kr + d);
             float kv[8];
-            unpack16(raw, kv, (bf16_t*)nullptr);
+            unpack16(raw, kv, (T*)nullptr);
 #pragma unroll
             for (int e = 0; e < 8; ++e) s += qh[d + e] * kv[e];
         }
@@ -143,7 +147,7 @@ __global__ __launch_bounds__(256) void cls_attn_kernel(const bf16_t* __restrict_
             const float alpha = exp2f((m - mnew) * sl2);
             const float p = j < L ? exp2f((sv - mnew) * sl2) : 0.f;
             l = l * alpha + wave_sum(p);
-            ph[j] = bf2f(f2bf(p));
+            ph[j] = Ty<T>::rnd(p);
             if (lane == c) my_m = mnew;
             m = mnew;
         }
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(256) void cls_attn_kernel(const bf16_t* __restrict_
         }
     }
     __syncthreads();
-    const bf16_t* vb = base + 2L * dim;
+    const T* vb = base + 2L * dim;
     for (int o = tid * 2; o < dim; o += 512) {
         const int h = o / D;
         const float* ph = ps + h * Lp;
@@ -164,8 +168,8 @@ __global__ __launch_bounds__(256) void cls_attn_kernel(const bf16_t* __restrict_
             for (int j = c * 64; j < j1; ++j) {
                 const uint32_t raw = *reinterpret_cast<const uint32_t*>(vb + (long)j * ld + o);
                 const float p = ph[j];
-                c0 += p * __uint_as_float(raw << 16);
-                c1 += p * __uint_as_float(raw & 0xFFFF0000u);
+                c0 += p * H16<T>::lo(raw);
+                c1 += p * H16<T>::hi(raw);
             }
             const float f = fac[h * NC + c];
             a0 += c0 * f;

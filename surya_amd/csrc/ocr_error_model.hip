@@ -4,15 +4,19 @@
 // Design notes (vs the PyTorch path):
 //   * texts are PACKED: one forward runs over T = sum of the text lengths; no padded row is computed anywhere. The reference's padding
 //     is invisible in its result (padded keys get exactly zero softmax weight, only the [CLS] row is read), so this is exact;
-//   * attention is segment attention with one segment per text (attn_mfma_kernel in bf16, attn_valu_kernel in fp32);
+//   * attention is segment attention with one segment per text (attn_mfma_kernel in bf16 and fp16, attn_valu_kernel in fp32);
 //   * q_lin | k_lin | v_lin run as one GEMM; the 1 / sqrt(head_dim) of encoder.py:174 is folded into the q rows at load when it is a
-//     power of two (head_dim 64: bit for bit the reference's division of the rounded projection);
+//     power of two (head_dim 64: bit for bit the reference's division of the rounded projection) -- in fp32 and bf16. NOT in fp16: a
+//     weight below 8 x 2^-14 would turn subnormal and lose bits, so the fp16 table carries the reference's q rows and attention scales;
 //   * out_lin and lin2 add the residual in the GEMM epilogue (rounded projection + residual, rounded: the reference's two T ops),
 //     lin1 applies the erf GELU there; the LayerNorms are separate row kernels;
 //   * the LAST layer is computed for the [CLS] rows only (Tuning::ocrerr_cls_only): its QKV GEMM still covers every token (the [CLS]
 //     query attends to all keys), then attention for one query per text and out_lin, both LayerNorms and the FFN on n rows instead of T.
 //     fp32 mode runs attn_valu_kernel over each text's first 64-query tile for this (the [CLS] row comes out bit-identical to the full
-//     layer's), bf16 mode the one-query cls_attn_kernel;
+//     layer's), bf16 mode the one-query cls_attn_kernel. fp16 mode runs attn_mfma_kernel over the first tile, bit-identical as in fp32:
+//     cls_attn_kernel<fp16_t> (ocrerr_cls_only = 2) agrees with the matrix-core kernel to fp32 rounding only, which flips the fp16
+//     rounding of ~0.4 of a text's 768 attention outputs by one step, and one such flip moves a logit by up to 1.2e-3 of the largest
+//      -- bf16's steps are 8x coarser and flip 8x more rarely;
 //   * GEMMs over the [CLS] rows are pinned to the 64 x 64 tile, and no GEMM here splits K: every GEMM tile walks K in the same order
 //     with the same MFMA, so a text's logits do not depend on how many rows its batch mates add.
 #include <algorithm>
@@ -45,7 +49,7 @@ struct OcrErrModel : OcrErrBase {
     char* arena = nullptr;
     T *x, *tmp, *h1, *att, *qkv, *ffn;            // packed rows [max_tokens][...]
     T *cx, *ctmp, *ch1, *cffn, *cpre;             // [CLS] rows [max_texts][...]
-    T* catt;                                      // fp32 [CLS] attention: [max_texts][64][dim] (a text's first query tile); bf16: [max_texts][dim]
+    T* catt;                                      // fp32 / fp16 [CLS] attention: [max_texts][64][dim] (a text's first query tile); one-query kernel: [max_texts][dim]
     // staging: two pinned host slots mirrored on the device, one H2D copy per forward; a slot is reused only after its copy completed
     struct Slot { char* host = nullptr; char* dev = nullptr; hipEvent_t ev = nullptr; bool pending = false; };
     Slot slot[2];
@@ -61,12 +65,12 @@ struct OcrErrModel : OcrErrBase {
         const int nw = SA_OW_GLOBALS + c.layers * SA_OL_COUNT;
         for (int i = 0; i < nw; ++i) w.push_back(reinterpret_cast<const T*>(weights[i]));
         D = c.dim / c.heads;
-        attn_scale = SA_OCRERR_Q_PRESCALED(D) ? 1.f : 1.f / std::sqrt((float)D);
+        attn_scale = SA_OCRERR_Q_PRESCALED(D, c.dtype) ? 1.f : 1.f / std::sqrt((float)D);
         const long Tm = c.max_tokens, Nm = c.max_texts, E = sizeof(T);
         const size_t sizes[] = {(size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E), (size_t)(Tm * c.dim * E),
                                 (size_t)(Tm * 3 * c.dim * E), (size_t)(Tm * c.hidden * E),
                                 (size_t)(Nm * c.dim * E), (size_t)(Nm * c.dim * E), (size_t)(Nm * c.dim * E), (size_t)(Nm * c.hidden * E),
-                                (size_t)(Nm * c.dim * E), (size_t)(Nm * (std::is_same<T, float>::value ? 64 : 1) * c.dim * E)};
+                                (size_t)(Nm * c.dim * E), (size_t)(Nm * (std::is_same<T, bf16_t>::value ? 1 : 64) * c.dim * E)};
         size_t total = 0;
         for (size_t b : sizes) total += oalign(b);
         SA_HIP(hipMalloc((void**)&arena, total));
@@ -84,7 +88,7 @@ struct OcrErrModel : OcrErrBase {
         }
         const int ncmax = (c.max_pos + 63) / 64;
         cls_lds = (size_t)(c.dim + (long)c.heads * ncmax * 64 + (long)c.heads * ncmax) * sizeof(float);
-        if (std::is_same<T, bf16_t>::value && cls_lds > 64 * 1024) return SA_ERR_UNSUPPORTED;
+        if (sizeof(T) == 2 && cls_lds > 64 * 1024) return SA_ERR_UNSUPPORTED;
         return SA_OK;
     }
     ~OcrErrModel() override {
@@ -114,8 +118,8 @@ struct OcrErrModel : OcrErrBase {
         return launch_attn<T>(D, q, q + c.dim, q + 2 * c.dim, o, sg, n_tiles, c.heads, ld, D, ld, D, o_row, D, 1, 0, attn_scale, s);
     }
     int cls_attention(const int* starts, const int* lens, int n, hipStream_t s) {
-        if constexpr (std::is_same<T, bf16_t>::value) {
-#define SA_OCR_CLS(DD) hipLaunchKernelGGL((ocr::cls_attn_kernel<DD>), dim3(n), dim3(256), cls_lds, s, qkv, starts, lens, catt, c.dim, c.heads, attn_scale)
+        if constexpr (sizeof(T) == 2) {
+#define SA_OCR_CLS(DD) hipLaunchKernelGGL((ocr::cls_attn_kernel<T, DD>), dim3(n), dim3(256), cls_lds, s, qkv, starts, lens, catt, c.dim, c.heads, attn_scale)
             switch (D) {
                 case 32: SA_OCR_CLS(32); break;
                 case 64: SA_OCR_CLS(64); break;
@@ -213,7 +217,9 @@ struct OcrErrModel : OcrErrBase {
             }
             // last layer, [CLS] rows only
             long att_ld = dim;
-            if constexpr (std::is_same<T, float>::value) {
+            // the one-query kernel: bf16 always, fp16 at ocrerr_cls_only = 2 (the A/B arm); else the text's first query tile on the full layer's kernel
+            const bool one_query = std::is_same<T, bf16_t>::value || (std::is_same<T, fp16_t>::value && tuning().ocrerr_cls_only == 2);
+            if (!one_query) {
                 if ((rc = attention(qkv, catt, first, n, dim, s))) return rc;
                 att_ld = 64L * dim;                  // row 0 of each text's 64-row block
             } else {
@@ -239,6 +245,18 @@ struct OcrErrModel : OcrErrBase {
     }
 };
 
+// surya_op_gemm / surya_op_attn in fp16 (rec_model.hip): the GELU epilogue and segment attention exactly as OcrErrModel<fp16_t> launches
+// them, instantiated in this translation unit beside it
+int op_gemm_f16_gelu(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, int M, int N, int K, hipStream_t s) {
+    GemmArgs<fp16_t, fp16_t> a{(const fp16_t*)X, ldx, (const fp16_t*)W, ldw, (fp16_t*)C, ldc, (const fp16_t*)bias, nullptr, 0, M, N, K};
+    return launch_gemm<fp16_t, fp16_t, EPI_GELU>(a, s);
+}
+int op_attn_f16(int D, const void* q, const void* k, const void* v, void* o, const AttnSegs& sg, int n_tiles, int heads, long q_row, long q_head,
+                long k_row, long k_head, long o_row, long o_head, int group, int causal, float scale, hipStream_t s) {
+    return launch_attn<fp16_t>(D, (const fp16_t*)q, (const fp16_t*)k, (const fp16_t*)v, (fp16_t*)o, sg, n_tiles, heads, q_row, q_head, k_row, k_head,
+                               o_row, o_head, group, causal, scale, s);
+}
+
 }  // namespace sa
 
 using namespace sa;
@@ -249,11 +267,11 @@ extern "C" {
 
 int surya_ocrerr_create(const surya_ocrerr_config* cfg, const void* const* weights, int n_weights, surya_ocrerr** out) {
     if (!cfg || !weights || !out) return SA_ERR_ARG;
-    if (cfg->dtype != SA_DTYPE_F32 && cfg->dtype != SA_DTYPE_BF16) return SA_ERR_UNSUPPORTED;
+    if (cfg->dtype != SA_DTYPE_F32 && cfg->dtype != SA_DTYPE_BF16 && cfg->dtype != SA_DTYPE_F16) return SA_ERR_UNSUPPORTED;
     if (cfg->layers < 1 || cfg->heads < 1 || cfg->dim % cfg->heads || cfg->num_labels < 1 || cfg->vocab < 1) return SA_ERR_ARG;
     const int D = cfg->dim / cfg->heads;
     if (D != 32 && D != 64 && D != 80 && D != 128) return SA_ERR_UNSUPPORTED;
-    if (cfg->dim % 64 || cfg->hidden % 64) return SA_ERR_SHAPE;          // GEMM K chunks (64 bf16 / 32 fp32 elements), 16-byte rows
+    if (cfg->dim % 64 || cfg->hidden % 64) return SA_ERR_SHAPE;          // GEMM K chunks (64 bf16 / fp16 or 32 fp32 elements), 16-byte rows
     if (cfg->max_pos < 1 || cfg->max_pos > 4096) return SA_ERR_UNSUPPORTED;
     if (cfg->max_texts < 1 || cfg->max_tokens < 1) return SA_ERR_ARG;
     if (n_weights != SA_OW_GLOBALS + cfg->layers * SA_OL_COUNT) return SA_ERR_ARG;
@@ -263,6 +281,10 @@ int surya_ocrerr_create(const surya_ocrerr_config* cfg, const void* const* weigh
     int rc;
     if (cfg->dtype == SA_DTYPE_F32) {
         auto* m = new OcrErrModel<float>();
+        h->impl.reset(m);
+        rc = m->init(*cfg, weights);
+    } else if (cfg->dtype == SA_DTYPE_F16) {
+        auto* m = new OcrErrModel<fp16_t>();
         h->impl.reset(m);
         rc = m->init(*cfg, weights);
     } else {

@@ -1044,6 +1044,10 @@ struct surya_rec { std::unique_ptr<RecBase> impl; surya_rec_config cfg; };
 namespace sa {   // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
+// ocr_error_model.hip: the fp16 GELU epilogue and fp16 segment attention of the OCR-error classifier
+int op_gemm_f16_gelu(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, int M, int N, int K, hipStream_t s);
+int op_attn_f16(int D, const void* q, const void* k, const void* v, void* o, const AttnSegs& sg, int n_tiles, int heads, long q_row, long q_head,
+                long k_row, long k_head, long o_row, long o_head, int group, int causal, float scale, hipStream_t s);
 // layout_model.hip: the ADETR MLP's gated epilogue (gelu_tanh(gate) * up), fp32 and bf16
 int op_gemm_geglu(int dtype, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int K, hipStream_t s);
 }
@@ -1177,8 +1181,11 @@ int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, cons
     if (dtype == SA_DTYPE_BF16)
         return out_f32 ? op_gemm_t<bf16_t, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s)
                        : op_gemm_t<bf16_t, bf16_t>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
-    if (dtype == SA_DTYPE_F16)            // the detector's epilogues (bias, residual, Hardswish, ReLU), 16-bit output only; built in det_model.hip
-        return out_f32 ? SA_ERR_UNSUPPORTED : sa::op_gemm_f16(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
+    if (dtype == SA_DTYPE_F16) {          // 16-bit output only: the detector's epilogues (bias, residual, Hardswish, ReLU; built in det_model.hip)
+        if (out_f32) return SA_ERR_UNSUPPORTED;                       // and the OCR-error classifier's GELU (ocr_error_model.hip)
+        if (epi == EPI_GELU) return R ? SA_ERR_UNSUPPORTED : sa::op_gemm_f16_gelu(X, ldx, W, ldw, C, ldc, bias, M, N, K, s);
+        return sa::op_gemm_f16(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
+    }
     return SA_ERR_UNSUPPORTED;
 }
 
@@ -1225,6 +1232,8 @@ int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const v
     if (dtype == SA_DTYPE_BF16)
         rc = sa::launch_attn<bf16_t>(head_dim, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)out, sg.a, sg.n_tiles, heads, q_row, q_head,
                                      k_row, k_head, o_row, o_head, group, causal, scale, s);
+    else if (dtype == SA_DTYPE_F16)
+        rc = sa::op_attn_f16(head_dim, q, k, v, out, sg.a, sg.n_tiles, heads, q_row, q_head, k_row, k_head, o_row, o_head, group, causal, scale, s);
     else if (dtype == SA_DTYPE_F32)
         rc = sa::launch_attn<float>(head_dim, (const float*)q, (const float*)k, (const float*)v, (float*)out, sg.a, sg.n_tiles, heads, q_row, q_head, k_row,
                                     k_head, o_row, o_head, group, causal, scale, s);

@@ -23,8 +23,10 @@ class OcrErrConfigC(C.Structure):
 
 def repack_ocr_error_weights(cfg: OCRErrorConfig, sd, dtype: torch.dtype, device) -> List[torch.Tensor]:
     """Reference state dict (DistilBertForSequenceClassification names) -> the table of include/surya_amd.h (SA_OW_* then SA_OL_* per
-    layer). q_lin | k_lin | v_lin are fused into one [3 dim, dim] weight; for head_dim 64 the q rows and bias are multiplied by 1 / 8
-    (exact in any binary format: the engine's q is then the reference's q_lin(x) / sqrt(d), encoder.py:174, bit for bit)."""
+    layer). q_lin | k_lin | v_lin are fused into one [3 dim, dim] weight. For head_dim 64 in float32 / bfloat16 the q rows and bias are
+    multiplied by 1 / 8 (a power of two, exact in formats whose exponent range the weights never leave: the engine's q is then the
+    reference's q_lin(x) / sqrt(d), encoder.py:174, bit for bit). A float16 table is NOT folded (SA_OCRERR_Q_PRESCALED): a weight below
+    8 x 2^-14 = 4.9e-4 would become subnormal and lose bits, so it carries the reference's q rows and the engine scales in attention."""
     out: List[torch.Tensor] = []
     f = lambda k: sd[k].float()
 
@@ -42,7 +44,7 @@ def repack_ocr_error_weights(cfg: OCRErrorConfig, sd, dtype: torch.dtype, device
     put(f("distilbert.embeddings.LayerNorm.weight")); put(f("distilbert.embeddings.LayerNorm.bias"))
     put(f("pre_classifier.weight")); put(f("pre_classifier.bias"))
     put(f("classifier.weight")); put(f("classifier.bias"))
-    qscale = 1.0 / 8.0 if cfg.head_dim == 64 else 1.0
+    qscale = 1.0 / 8.0 if cfg.head_dim == 64 and dtype != torch.float16 else 1.0
     for i in range(cfg.n_layers):
         p = f"distilbert.transformer.layer.{i}."
         a = p + "attention."
@@ -57,6 +59,9 @@ def repack_ocr_error_weights(cfg: OCRErrorConfig, sd, dtype: torch.dtype, device
     return out
 
 
+_DTYPES = {torch.float32: L.DTYPE_F32, torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}
+
+
 def pack_ids(seqs: Sequence[Sequence[int]]) -> Tuple[torch.Tensor, List[int]]:
     """Token id lists -> (packed int32 CPU tensor, lengths)."""
     lens = [len(s) for s in seqs]
@@ -69,8 +74,8 @@ class HipOCRErrorModel:
                  max_tokens: int = 64 * 512):
         if not torch.cuda.is_available():
             raise L.SuryaAmdError("HipOCRErrorModel needs a GPU (MI355X); there is no CPU fallback")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be float32 (reference mode) or bfloat16")
+        if dtype not in _DTYPES:
+            raise ValueError("dtype must be float32 (reference mode), bfloat16 or float16")
         cfg.validate()
         self.lib = L.lib()
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
@@ -80,7 +85,7 @@ class HipOCRErrorModel:
         self.c = OcrErrConfigC(vocab=cfg.vocab_size, max_pos=cfg.max_position_embeddings, dim=cfg.dim, heads=cfg.n_heads,
                                hidden=cfg.hidden_dim, layers=cfg.n_layers, num_labels=cfg.num_labels, ln_eps=cfg.layer_norm_eps,
                                max_texts=self.max_texts, max_tokens=self.max_tokens,
-                               dtype=L.DTYPE_F32 if dtype == torch.float32 else L.DTYPE_BF16)
+                               dtype=_DTYPES[dtype])
         table = (C.c_void_p * len(self.weights))(*[t.data_ptr() for t in self.weights])
         self.handle = C.c_void_p()
         L.check(self.lib.surya_ocrerr_create(C.byref(self.c), table, len(self.weights), C.byref(self.handle)), "surya_ocrerr_create")
