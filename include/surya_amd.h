@@ -15,7 +15,8 @@
  *     documented ("sync"). A handle is re-entrant but not thread-safe: one host thread per handle, like the
  *     reference's single-threaded device path (surya/settings.py:179-183).
  *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (the text detector, the
- *     OCR-error classifier, surya_op_gemm and surya_op_attn; every other engine returns SA_ERR_UNSUPPORTED for it).
+ *     OCR-error classifier, the layout / table-recognition engine and the op-level entries; the recogniser returns
+ *     SA_ERR_UNSUPPORTED for it).
  */
 #ifndef SURYA_AMD_H
 #define SURYA_AMD_H
@@ -214,7 +215,7 @@ int surya_rec_set_kv_fp8(surya_rec* h, int on);
  * ---------------------------------------------------------------------------------------------------------- */
 /* C[M,N] = X[M,K] W[N,K]^T + bias, epilogue: 0 none/bias, 1 +residual R, 2 gelu, 3 swiglu (W rows interleaved,
  * C is [M,N/2]), 4 hardswish, 5 relu, 8 geglu = gelu_tanh(gate) * up with gate, up and the gelu each rounded to the compute dtype
- * (the ADETR decoder's MLP, W rows interleaved like swiglu, C is [M,N/2]; fp32 and bf16 only, no bias, no R, out_f32 == 0).
+ * (the ADETR decoder's MLP, W rows interleaved like swiglu, C is [M,N/2]; fp32 and bf16 only, no bias, no R, out_f32 == 0; fp16: surya_op_gemm_geglu_f16 below).
  * Codes 6 and 7 are epilogues of the recogniser that take further operands and are not reachable here: SA_ERR_ARG.
  * out_f32 != 0: C (and R) are fp32 regardless of dtype. dtype SA_DTYPE_F16 takes the detector's epilogues (0, 1, 4, 5) and the
  * OCR-error classifier's gelu (2: the projection rounded to fp16, erf GELU, rounded; no R) with fp16 output only; anything else returns
@@ -235,7 +236,8 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
  * qkv_part[slab][rows][(heads + 2 kv_heads) * head_dim] + qkv_bias, rounded to the storage dtype; RoPE from the (cos, sin) table
  * rope_cs[max_kv_len][head_dim / 2][2]; k, v appended to the caches [slot][kv_head][max_kv_len][head_dim] at row_len[r];
  * out[r][heads * head_dim] = attention over row_len[r] + 1 keys (decoder/__init__.py:193-234). bf16 runs
- * decode_attn_flash2_kernel (tuning dattn = 4, the default) or decode_attn_flash_kernel (dattn = 3), fp32 decode_attn_mfma_kernel. The hook
+ * decode_attn_flash2_kernel (tuning dattn = 4, the default) or decode_attn_flash_kernel (dattn = 3), fp32 decode_attn_mfma_kernel, fp16
+ * decode_attn_flash2_kernel<.., fp16_t> at head_dim 64 / 32 with heads / kv_heads <= 8 (the layout / table decoders' shapes). The hook
  * has no host bound on the contexts, so of decode_attn_flash2_kernel's two forms the two-buffer one runs at dattn_db = 1 only; the engine also
  * picks it at dattn_db = 0 once a context exceeds 128 keys. All pointers device. Enqueue only. */
 int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const void* v, void* out, const int32_t* seg_len,
@@ -267,7 +269,8 @@ int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_
 
 /* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
  * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).
- * dtype SA_DTYPE_F32 or SA_DTYPE_BF16 as the engine, anything else SA_ERR_UNSUPPORTED. All pointers are caller-owned device memory
+ * dtype SA_DTYPE_F32 or SA_DTYPE_BF16, anything else SA_ERR_UNSUPPORTED: these entries keep their two dtypes. The engine's third dtype has
+ * entries of its own, surya_op_lay_<op>_f16 (the same arguments without `dtype`, the same launch code on the fp16 instance; declared below). All pointers are caller-owned device memory
  * unless marked host; enqueue only; nothing is allocated.
  * surya_lay_window_tables (host only, no GPU): what LayoutModel::init builds per (stage, shift) for an h x w token grid.
  *   perm[h * w] (host, may be NULL) = window-order row of every token after padding to whole windows and the cyclic shift by -shift;
@@ -275,13 +278,13 @@ int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_
  *   padded_hw[2] = the grid in whole windows; *shift_used = 0 when min(h, w) == window (such a stage is never shifted), else shift.
  *   min(h, w) < window: SA_ERR_UNSUPPORTED.
  * surya_lay_cross_plan (host only): for Lk cached keys, the fp32 cross attention's keys per range and ranges (scratch = rows * heads *
- *   ranges * (head_dim + 2) floats) and the bf16 kernel's padded key count Lkp (vT = images * kv_heads * head_dim * Lkp elements).
+ *   ranges * (head_dim + 2) floats) and the bf16 / fp16 kernel's padded key count Lkp (vT = images * kv_heads * head_dim * Lkp elements).
  * surya_op_lay_layernorm: y[dst(r)] = LayerNorm(x[r]) over C channels, dst(r) = (r / rows_per_image) * (rows_per_image_out ?
- *   rows_per_image_out : rows_per_image) + perm[r % rows_per_image], or r when perm == NULL. bf16 with C in {128, 256, 512, 1024} runs
+ *   rows_per_image_out : rows_per_image) + perm[r % rows_per_image], or r when perm == NULL. bf16 / fp16 with C in {128, 256, 512, 1024} run
  *   layernorm_rows_bf16_kernel unless surya_set_tuning("lay_ln", 0), everything else layernorm_kernel. C % 4 == 0.
  * surya_op_lay_window_attn: qkv [windows * 64][(nh + 2 nkv) * 32] in window order -> out [windows * 64][nh * 32]; bias fp32 [nh][64][64];
  *   window index % (nwx * nwy) is its place in the image, shift > 0 masks across the cyclic-shift regions of the last window row / column.
- *   bf16 runs swin_window_attn_mfma_kernel, fp32 swin_window_attn_kernel. ws must be 8.
+ *   bf16 / fp16 run swin_window_attn_mfma_kernel<T>, fp32 swin_window_attn_kernel. ws must be 8.
  * surya_op_lay_merge_ln: x [B][H][W][C] -> y [B * H/2 * W/2][4C] = LayerNorm of the 2x2 neighbours (0,0), (1,0), (0,1), (1,1). H, W even.
  * surya_op_lay_rows: the encoder's row movers; dims is a HOST array:
  *   SA_LAY_PATCHIFY   dims {B, C, H, W, P, Kpad}: src fp32 pixels [B][C][H][W] -> dst patch rows [B * H/P * W/P][Kpad]
@@ -291,10 +294,11 @@ int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_
  *                     rows_per_image_src : rows_per_image) + index[r % rows_per_image]]
  * surya_op_lay_cross_attn: M query rows, one per decoder row, over the Lk keys of image item_map[row]; kv [n_images][Lk][2 * nkv * head_dim]
  *   (k heads | v heads). S in 1..8: qpart fp32 [S][M][nq * head_dim] split-K slabs, summed and rounded to the compute dtype; S == 0: qpart
- *   is a plain [M][nq * head_dim] matrix of the compute dtype (the prefill path). bf16: transpose_cross_v_kernel fills vT, then
- *   cross_attn_mfma_kernel; fp32: cross_attn_split_kernel + cross_attn_merge_kernel through scratch (sizes: surya_lay_cross_plan; the
+ *   is a plain [M][nq * head_dim] matrix of the compute dtype (the prefill path). bf16 / fp16: transpose_cross_v_kernel fills vT, then
+ *   cross_attn_mfma_kernel<T>; fp32: cross_attn_split_kernel + cross_attn_merge_kernel through scratch (sizes: surya_lay_cross_plan; the
  *   buffer the dtype does not use may be NULL). head_dim in {32, 64}, nq / nkv <= 8.
- * surya_op_lay_rmsnorm: SuryaADETRDecoderRMSNorm (variance clamped at eps, scale 1 + w, clamp to the dtype's range, NaN -> 0).
+ * surya_op_lay_rmsnorm: SuryaADETRDecoderRMSNorm (variance clamped at eps, scale 1 + w, clamp to the dtype's finite range -- +-65504 in
+ *   fp16 --, NaN -> 0: a row holding +inf comes out as zeros, as from the reference).
  * surya_op_lay_reduce_norm: x_out = T(res + T(bias + sum of S slabs part[S][M][H])), y = that RMSNorm of x_out. res may alias x_out;
  *   bias may be NULL; w == NULL skips y. H % 4 == 0, H <= 4096, S in 1..8.
  * surya_op_lay_prefill_attn: causal self-attention of B prompts of Tn tokens, qkv [B * Tn][(nq + 2 nkv) * head_dim], RoPE at positions
@@ -324,6 +328,30 @@ int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void*
                        int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream);
 int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w,
                        const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream);
+
+/* The same kernels alone in fp16 (SA_DTYPE_F16, the engine's third compute dtype): the arguments of surya_op_lay_<op> without `dtype`, every
+ * pointer of the compute dtype fp16. fp16 takes the kernels bf16 takes (the matrix-core window and cross attention, the rows-in-registers
+ * LayerNorm); surya_op_lay_cross_attn_f16 needs vT like bf16 and ignores scratch. surya_op_gemm_geglu_f16 = surya_op_gemm's code 8 (geglu)
+ * with fp16 operands and output: X [M][K], W [N][K] rows interleaved (gate_j, up_j), C [M][N / 2]. */
+int surya_op_lay_layernorm_f16(const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image, int C, float
+        eps, int rows_per_image_out, void* stream);
+int surya_op_lay_window_attn_f16(const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift, int ws,
+        void* stream);
+int surya_op_lay_merge_ln_f16(const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream);
+int surya_op_lay_rows_f16(int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream);
+int surya_op_lay_cross_attn_f16(int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map, void* out,
+        float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream);
+int surya_op_lay_rmsnorm_f16(const void* x, const void* w, void* y, int rows, int C, float eps, void* stream);
+int surya_op_lay_reduce_norm_f16(const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y, int H, float
+        eps, void* stream);
+int surya_op_lay_prefill_attn_f16(int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn, int nq,
+        int nkv, int Tmax, float scale, void* stream);
+int surya_op_lay_embed_f16(int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed, int bbox_size, int
+        vocab, int label_count, int category_count, int merge_count, void* stream);
+int surya_op_lay_heads_f16(const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w, const
+        void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream);
+int surya_op_gemm_geglu_f16(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int K, void* stream);
+
 
 /* ------------------------------------------------------------------------------------------------------------
  * Detection model: EfficientViT-L backbone + SegFormer-style decode head + sigmoid + x4 bilinear upsample.

@@ -12,14 +12,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.so")   # env: A/B builds of the kernels
 
 SA_MAX_STEPS = 16
-DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: the detector, the OCR-error classifier, surya_op_gemm / surya_op_attn
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: every engine but the recogniser, and their op-level entries
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
  RW_LM_B, RW_BBOX_W, RW_BBOX_B, RW_ENC_INVFREQ, RW_DEC_INVFREQ, RW_GLOBALS) = range(17)
 (RE_NORM1, RE_QKV_W, RE_QKV_B, RE_PROJ_W, RE_PROJ_B, RE_NORM2, RE_GU_W, RE_GU_B, RE_DOWN_W, RE_DOWN_B, RE_COUNT) = range(11)
 (RD_LN1, RD_QKV_W, RD_QKV_B, RD_O_W, RD_LN2, RD_GU_W, RD_DOWN_W, RD_COUNT) = range(8)
 
 EPI_BIAS, EPI_RESIDUAL, EPI_GELU, EPI_SWIGLU, EPI_HARDSWISH, EPI_RELU = range(6)
-EPI_GEGLU = 8                                   # gelu_tanh(gate) * up (ADETR decoder MLP); surya_op_gemm, fp32 / bf16
+EPI_GEGLU = 8                                   # gelu_tanh(gate) * up (ADETR decoder MLP); surya_op_gemm, fp32 / bf16 (fp16: surya_op_gemm_geglu_f16)
 FAMILY_LAYOUT, FAMILY_TABLE = 0, 1              # SA_FAMILY_*
 LAY_PATCHIFY, LAY_ADD_ROWS, LAY_ZERO_ROWS, LAY_GATHER_ADD = range(4)      # SA_LAY_*: `kind` of surya_op_lay_rows
 
@@ -91,6 +91,10 @@ def _bind_lay_ops(lib):
     for name, args in sig.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, C.c_int
+        if name.startswith("surya_op_lay_"):                     # the fp16 entry of the same op: the same arguments without `dtype`
+            f16 = getattr(lib, name + "_f16")
+            f16.argtypes, f16.restype = args[1:], C.c_int
+    lib.surya_op_gemm_geglu_f16.argtypes, lib.surya_op_gemm_geglu_f16.restype = [p, l, p, l, p, l, i, i, i, p], C.c_int
 
 
 def check(rc: int, what: str):

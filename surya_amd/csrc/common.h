@@ -54,6 +54,7 @@ template <> struct Ty<float> {
     __device__ static __forceinline__ float ld(const float* p) { return *p; }
     __device__ static __forceinline__ void st(float* p, float v) { *p = v; }
     __device__ static __forceinline__ float rnd(float v) { return v; }   // round through storage type
+    static constexpr float FMAX = 3.4028234663852886e38f;                  // torch.finfo(dtype).max
 };
 template <> struct Ty<bf16_t> {
     static constexpr int KE = 64;
@@ -61,6 +62,7 @@ template <> struct Ty<bf16_t> {
     __device__ static __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); }
     __device__ static __forceinline__ void st(bf16_t* p, float v) { *p = f2bf(v); }
     __device__ static __forceinline__ float rnd(float v) { return bf2f(f2bf(v)); }
+    static constexpr float FMAX = 3.3895313892515355e38f;
 };
 
 template <> struct Ty<fp16_t> {
@@ -69,6 +71,7 @@ template <> struct Ty<fp16_t> {
     __device__ static __forceinline__ float ld(const fp16_t* p) { return h2f(*p); }
     __device__ static __forceinline__ void st(fp16_t* p, float v) { *p = f2h(v); }
     __device__ static __forceinline__ float rnd(float v) { return h2f(f2h(v)); }
+    static constexpr float FMAX = 65504.0f;
 };
 
 // Unpack a 16-byte register chunk into floats (4 for f32, 8 for bf16).
@@ -104,6 +107,10 @@ template <> struct H16<bf16_t> {
     __device__ static __forceinline__ f32x16 mfma(const A& w, const B& x, const f32x16& c) {           // v_mfma_f32_32x32x16_bf16
         return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
     }
+    template <typename A, typename B>                                                                    // the 16 x 16 x 32 shape: same lane maps in both types
+    __device__ static __forceinline__ f32x4 mfma16(const A& w, const B& x, const f32x4& c) {           // v_mfma_f32_16x16x32_bf16
+        return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, w), __builtin_bit_cast(bf16x8, x), c, 0, 0, 0);
+    }
 };
 template <> struct H16<fp16_t> {
     typedef f16x2 x2;
@@ -118,7 +125,20 @@ template <> struct H16<fp16_t> {
     __device__ static __forceinline__ f32x16 mfma(const A& w, const B& x, const f32x16& c) {           // v_mfma_f32_32x32x16_f16
         return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
     }
+    template <typename A, typename B>
+    __device__ static __forceinline__ f32x4 mfma16(const A& w, const B& x, const f32x4& c) {           // v_mfma_f32_16x16x32_f16
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w), __builtin_bit_cast(f16x8, x), c, 0, 0, 0);
+    }
 };
+
+// The tail of SuryaADETRDecoderRMSNorm (adetr/decoder.py:42-47): clamp to the storage type's finite range, then NaN -> 0. torch.clamp keeps a
+// NaN, so the NaN test comes FIRST here: fmaxf(NaN, -lim) is -lim under IEEE maxNum and the test after it would never fire. Finite and
+// infinite inputs give the same bits in either order. In fp16 a NaN is within reach: one residual element above 65504 is +inf, the row's
+// variance is inf, rstd = 0 and inf * 0 = NaN at that element (the reference returns a row of zeros).
+template <typename T>
+__device__ __forceinline__ float adetr_clamp(float t) {
+    return (t != t) ? 0.f : fminf(fmaxf(t, -Ty<T>::FMAX), Ty<T>::FMAX);
+}
 
 // Store 4 consecutive outputs.
 __device__ __forceinline__ void store4(float* p, float a, float b, float c, float d) {
@@ -308,7 +328,7 @@ struct Tuning {
     int bigtile_min_k = 0;   // ... only when K >= this (short-K GEMMs are prologue / epilogue bound: two 128x128 workgroups per CU overlap those)
     int glds = 2;            // LDS stages of the 128x128 direct-to-LDS GEMM (2 or 3)
     // round 4 (A/B knobs of the decode step's non-GEMM kernels and of the persistent big-tile GEMM; defaults = measured best)
-    int dattn = 4;           // bf16 decode attention: 4 = thread-local prologue (decode_attn_flash2_kernel), 3 = third version
+    int dattn = 4;           // bf16 decode attention (fp16: always the fourth version): 4 = thread-local prologue (decode_attn_flash2_kernel), 3 = third version
     int rnorm = 2;           // split-K reduce + residual + RMSNorm: 2 = slab loads sized by the slice count, 1 = round-3 kernel, 3 = one wave per row
     int ghead = 2;           // greedy head: 2 = registers-only partial reduce + vector bbox head (+ next step's embedding when fused), 1 = round-3 kernel
     int fuse_embed = 1;      // inner decode steps: the greedy head also writes the next step's embedding + first RMSNorm (no embed launch)
@@ -319,7 +339,7 @@ struct Tuning {
                              // compute): 0 = when some active slot's context exceeds one 128-key tile (host bound; eager launches only -- under graph replay, `graph` = 1, the single-buffer kernel runs and the bound is not advanced), 1 = always, -1 = never.
                              // The rule lives in launch_decode_attn, which the layout / table decoder and surya_op_decode_attn call without a bound: 0 = single buffer there,
                              // and 1 reaches them too (deliberate: the two forms are bit-identical)
-    int lay_ln = 1;          // layout / table encoder LayerNorm (bf16): 1 = rows held in registers by C / 8 lanes (layernorm_rows_bf16_kernel), 0 = a wave per row
+    int lay_ln = 1;          // layout / table encoder LayerNorm (bf16, fp16): 1 = rows held in registers by C / 8 lanes (layernorm_rows_bf16_kernel), 0 = a wave per row
     int det_head_blk = 1;    // detector's folded decode head: 1 = register-blocked sum + classify (4 x 2 pixel blocks), 0 = per-pixel kernel
     int det_fuse = 1023;     // detector's fused forms (det_model.hip find_fusions; bf16 and fp16): bit 0 = LiteMLA depthwise 5x5 + grouped 1x1, bit 1 = LiteMLA kv + out in one
                              // launch, bit 2 = z0 inside the head's sum + classify pass, bit 3 = MBConv depthwise 3x3 + projection, bit 4 = FusedMBConv

@@ -528,14 +528,15 @@ __global__ __launch_bounds__(256) void decode_attn_flash_kernel(const float* __r
 // the host picks DB only when some active slot's context exceeds one tile (rec_model.hip, ctx bound kept on the host), where the
 // launch has at most one workgroup per CU anyway at the task's batch (128 slots x 2 kv heads). Same arithmetic, same order: outputs
 // are bit-identical to the single-buffered kernel.
-template <int D, int MAXG, bool DB = false>
-__global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __restrict__ qkv_part, int S, const bf16_t* __restrict__ qkv_bias,
-                                                                 bf16_t* __restrict__ out, bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+// T (last, so that the bf16 users keep their spelling): bf16_t or fp16_t -- the layout / table engine's fp16 mode; packing and MFMA from H16<T>.
+template <int D, int MAXG, bool DB = false, typename T = bf16_t>
+__global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __restrict__ qkv_part, int S, const T* __restrict__ qkv_bias,
+                                                                 T* __restrict__ out, T* __restrict__ kc, T* __restrict__ vc,
                                                                  const int* __restrict__ active_slots, const int* __restrict__ row_len,
                                                                  const float2* __restrict__ rope_cs, int nq, int nkv, int Tmax,
                                                                  float scale, uint8_t* __restrict__ out8 = nullptr,
                                                                  uint8_t* __restrict__ sout = nullptr, int srows = 0) {
-    typedef bf16_t T;
+    static_assert(sizeof(T) == 2, "a 16-bit storage type");
     constexpr int CPR = D / 8;                               // 16-byte chunks per K/V row
     constexpr int ROWB = D * 2;                              // bytes per K/V row
     constexpr int KT = 128;                                  // keys per LDS tile: 32 per wave
@@ -728,7 +729,7 @@ __global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __
 #pragma unroll
             for (int kk = 0; kk < NKK; ++kk) {
                 const u32x4 kf = *reinterpret_cast<const u32x4*>(Kt + krow * ROWB + (((kk * 2 + h) ^ (krow & XM)) << 4));
-                sacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[kk]), sacc, 0, 0, 0);
+                sacc = H16<T>::mfma(kf, qf[kk], sacc);
             }
             float bm = -INFINITY;                            // register 4g + r = key k0 + 8g + 4h + r
 #pragma unroll
@@ -759,20 +760,19 @@ __global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __
             for (int st = 0; st < 2; ++st) {
                 if (k0 + st * 16 < nk) {                     // wave-uniform; rows of a started 16-key step hold finite data
                     u32x4 pf;
-                    pf[0] = pack2(sacc[8 * st + 0], sacc[8 * st + 1]);
-                    pf[1] = pack2(sacc[8 * st + 2], sacc[8 * st + 3]);
-                    pf[2] = pack2(sacc[8 * st + 4], sacc[8 * st + 5]);
-                    pf[3] = pack2(sacc[8 * st + 6], sacc[8 * st + 7]);
+                    pf[0] = H16<T>::pk(sacc[8 * st + 0], sacc[8 * st + 1]);
+                    pf[1] = H16<T>::pk(sacc[8 * st + 2], sacc[8 * st + 3]);
+                    pf[2] = H16<T>::pk(sacc[8 * st + 4], sacc[8 * st + 5]);
+                    pf[3] = H16<T>::pk(sacc[8 * st + 6], sacc[8 * st + 7]);
 #pragma unroll
                     for (int db = 0; db < NDB; ++db) {
-                        const bf16_t* vp = reinterpret_cast<const bf16_t*>(Vt) + (k0 + st * 16) * D + db * 32 + tr_off;
+                        const T* vp = reinterpret_cast<const T*>(Vt) + (k0 + st * 16) * D + db * 32 + tr_off;
                         typedef short s16x4_t __attribute__((ext_vector_type(4)));
                         typedef short s16x8_t __attribute__((ext_vector_type(8)));
                         const s16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vp));
                         const s16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(vp + 8 * D));
                         const s16x8_t vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-                        oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf),
-                                                                           oacc[db], 0, 0, 0);
+                        oacc[db] = H16<T>::mfma(vf, pf, oacc[db]);
                     }
                 }
             }
@@ -860,8 +860,19 @@ struct DecodeAttnArgs {
 // The ladder over (d, heads per kv head), the kernel version (Tuning::dattn, Tuning::dattn_db with ctx_bound), the LDS opt-in and the launch.
 // bf16: decode_attn_flash2_kernel, or decode_attn_flash_kernel at dattn = 3; fp32, and head shapes those two lack: decode_attn_mfma_kernel.
 // Defined for float and bf16_t in rec_model.hip, whose code object alone holds the kernels (a header template would compile the whole ladder
-// into every object that decodes).
+// into every object that decodes); for fp16_t in layout_model.hip, beside its only user (decode_attn_flash2_kernel<.., fp16_t> at d = 64 / 32).
 template <typename T>
 int launch_decode_attn(const DecodeAttnArgs<T>& a, hipStream_t s);
+template <> int launch_decode_attn<fp16_t>(const DecodeAttnArgs<fp16_t>& a, hipStream_t s);
+
+// The launch itself, shared by the definitions of launch_decode_attn: LDS opt-in once per kernel, grid (rows, kv heads), 256 threads.
+template <auto KERN, typename T, typename... X>
+static int decode_attn_as(const DecodeAttnArgs<T>& a, size_t lds, hipStream_t s, X... extra) {
+    static AttrOnce attr;                                    // one per kernel: KERN is a template argument
+    attr.ensure(KERN, lds);
+    hipLaunchKernelGGL(KERN, dim3(a.rows, a.nkv), dim3(256), lds, s, a.qkv_part, a.S, a.qkv_bias, a.out, a.kcache, a.vcache, a.active_slots,
+                       a.row_len, a.rope_cs, a.nq, a.nkv, a.max_kv_len, a.scale, extra...);
+    return (int)hipGetLastError();
+}
 
 }  // namespace sa

@@ -71,21 +71,23 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const T* __restrict__ x,
     }
 }
 
-// bf16 rows of 128 ... 1024 channels (the Swin stages): the kernel above gives a whole wave to a row -- at C = 128 half its lanes idle, the
+// bf16 / fp16 rows of 128 ... 1024 channels (the Swin stages): the kernel above gives a whole wave to a row -- at C = 128 half its lanes idle, the
 // other half move 8 bytes each and read the row three times (stage 1 of 32 pages = 1.18 M rows: 489 us for 600 MB, 1.2 TB/s). Here a row
 // belongs to LPR = min(64, C / 8) lanes that hold it in registers (one 16-byte load per 8 channels), several rows share a wave, the two
 // reductions run inside the LPR-lane group, and a workgroup walks 256 / LPR rows. Same two-pass statistics in fp32; the sums associate
-// differently (lane-local 8, then a butterfly), i.e. agreement with the kernel above to fp32 rounding, not to the bit -- bf16 mode only.
-template <int LPR, int NV>
-__global__ __launch_bounds__(256) void layernorm_rows_bf16_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ w,
-                                                                  const bf16_t* __restrict__ b, bf16_t* __restrict__ y,
+// differently (lane-local 8, then a butterfly), i.e. agreement with the kernel above to fp32 rounding, not to the bit -- the 16-bit storage
+// types only (T = bf16_t or fp16_t; the name is from the time it had one).
+template <typename T, int LPR, int NV>
+__global__ __launch_bounds__(256) void layernorm_rows_bf16_kernel(const T* __restrict__ x, const T* __restrict__ w,
+                                                                  const T* __restrict__ b, T* __restrict__ y,
                                                                   const int* __restrict__ perm, long rows, int rows_per_image, float eps,
                                                                   int rows_per_image_out) {
+    static_assert(sizeof(T) == 2, "a 16-bit storage type");
     constexpr int C = LPR * 8 * NV, RPB = 256 / LPR;
     const int sub = threadIdx.x % LPR;
     const long row = (long)blockIdx.x * RPB + threadIdx.x / LPR;
     const bool live = row < rows;                          // dead rows shadow the last one (the shuffles below need every lane)
-    const bf16_t* xr = x + (live ? row : rows - 1) * C;
+    const T* xr = x + (live ? row : rows - 1) * C;
     u32x4 raw[NV];
 #pragma unroll
     for (int v = 0; v < NV; ++v) raw[v] = *reinterpret_cast<const u32x4*>(xr + (v * LPR + sub) * 8);
@@ -95,8 +97,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_bf16_kernel(const bf16_t* 
     for (int v = 0; v < NV; ++v)
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            f[v][2 * i] = __uint_as_float(raw[v][i] << 16);
-            f[v][2 * i + 1] = __uint_as_float(raw[v][i] & 0xFFFF0000u);
+            f[v][2 * i] = H16<T>::lo(raw[v][i]);
+            f[v][2 * i + 1] = H16<T>::hi(raw[v][i]);
             s += f[v][2 * i] + f[v][2 * i + 1];
         }
 #pragma unroll
@@ -113,7 +115,7 @@ __global__ __launch_bounds__(256) void layernorm_rows_bf16_kernel(const bf16_t* 
     if (!live) return;
     long drow = row;
     if (perm) drow = (row / rows_per_image) * (rows_per_image_out ? rows_per_image_out : rows_per_image) + perm[row % rows_per_image];
-    bf16_t* yr = y + drow * C;
+    T* yr = y + drow * C;
 #pragma unroll
     for (int v = 0; v < NV; ++v) {
         const int c0 = (v * LPR + sub) * 8;
@@ -239,26 +241,28 @@ __global__ __launch_bounds__(256) void swin_window_attn_kernel(const T* __restri
     store4(op + 4, o[4], o[5], o[6], o[7]);
 }
 
-// bf16 windows on the matrix cores. One workgroup (2 waves x 32 queries) per (window, head); the tile plan of attn_mfma.h with the
+// bf16 / fp16 windows on the matrix cores (H16<T>: the twin instructions, the same lane maps). One workgroup (2 waves x 32 queries) per (window, head); the tile plan of attn_mfma.h with the
 // whole window as its single 64-key chunk:
 //   S^T = K Q^T   v_mfma_f32_32x32x16_bf16(K fragment, Q fragment): a lane owns ONE query (lane & 31) and 16 of each 32 keys, so
 //                 bias / mask / softmax are per-lane work plus one exchange with lane ^ 32;
 //   O^T = V^T P^T the lane's exp() values are its P fragment, the V^T fragment comes from two ds_read_b64_tr_b16 per 16-key step.
 // The scalar kernel above spent 23.8 ms per stage-1 layer of 32 pages in LDS reads (profiles/r03_f_layout_kernel_stats_before.md); it
 // stays as the fp32 reference-mode path.
-__global__ __launch_bounds__(128) void swin_window_attn_mfma_kernel(const bf16_t* __restrict__ qkv, const float* __restrict__ bias,
-                                                                    bf16_t* __restrict__ out, int nh, int nkv, int nwx, int nwy, int shift,
+template <typename T>
+__global__ __launch_bounds__(128) void swin_window_attn_mfma_kernel(const T* __restrict__ qkv, const float* __restrict__ bias,
+                                                                    T* __restrict__ out, int nh, int nkv, int nwx, int nwy, int shift,
                                                                     int ws) {
+    static_assert(sizeof(T) == 2, "a 16-bit storage type");
     constexpr int N = 64, D = 32, PK = D + 8;
     typedef short s16x4 __attribute__((ext_vector_type(4)));
     typedef short s16x8 __attribute__((ext_vector_type(8)));
-    __shared__ __attribute__((aligned(16))) bf16_t ks[N * PK];
-    __shared__ __attribute__((aligned(16))) bf16_t vs[N * PK];
+    __shared__ __attribute__((aligned(16))) T ks[N * PK];
+    __shared__ __attribute__((aligned(16))) T vs[N * PK];
     const long win = blockIdx.x;
     const int head = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int ql = lane & 31, h = lane >> 5, qi = wave * 32 + ql;
     const int row_w = (nh + 2 * nkv) * D, kvh = head % nkv;
-    const bf16_t* base = qkv + win * N * row_w;
+    const T* base = qkv + win * N * row_w;
     u32x4 kreg[2], vreg[2], qf[2];
 #pragma unroll
     for (int it = 0; it < 2; ++it) {
@@ -287,11 +291,11 @@ __global__ __launch_bounds__(128) void swin_window_attn_mfma_kernel(const bf16_t
     for (int kb = 0; kb < 2; ++kb) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) sacc[kb][r] = 0.f;
-        const bf16_t* kp = ks + (kb * 32 + ql) * PK + h * 8;
+        const T* kp = ks + (kb * 32 + ql) * PK + h * 8;
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk) {
             const u32x4 kf = *reinterpret_cast<const u32x4*>(kp + kk * 16);
-            sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, kf), __builtin_bit_cast(bf16x8, qf[kk]), sacc[kb], 0, 0, 0);
+            sacc[kb] = H16<T>::mfma(kf, qf[kk], sacc[kb]);
         }
     }
     const int wimg = (int)(win % ((long)nwx * nwy));
@@ -330,18 +334,18 @@ __global__ __launch_bounds__(128) void swin_window_attn_mfma_kernel(const bf16_t
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int kb = t >> 1, o8 = (t & 1) * 8;
-        u32x4 pf;                                                    // probabilities rounded to bf16 as softmax(...).to(bf16) does
-        pf[0] = pack2(sacc[kb][o8 + 0] * inv, sacc[kb][o8 + 1] * inv);
-        pf[1] = pack2(sacc[kb][o8 + 2] * inv, sacc[kb][o8 + 3] * inv);
-        pf[2] = pack2(sacc[kb][o8 + 4] * inv, sacc[kb][o8 + 5] * inv);
-        pf[3] = pack2(sacc[kb][o8 + 6] * inv, sacc[kb][o8 + 7] * inv);
-        const bf16_t* vp = vs + t * 16 * PK + tr_off;
+        u32x4 pf;                                                    // probabilities rounded to storage as softmax(...).to(dtype) does
+        pf[0] = H16<T>::pk(sacc[kb][o8 + 0] * inv, sacc[kb][o8 + 1] * inv);
+        pf[1] = H16<T>::pk(sacc[kb][o8 + 2] * inv, sacc[kb][o8 + 3] * inv);
+        pf[2] = H16<T>::pk(sacc[kb][o8 + 4] * inv, sacc[kb][o8 + 5] * inv);
+        pf[3] = H16<T>::pk(sacc[kb][o8 + 6] * inv, sacc[kb][o8 + 7] * inv);
+        const T* vp = vs + t * 16 * PK + tr_off;
         const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp));
         const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(vp + 8 * PK));
         const s16x8 vf = __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-        oacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, vf), __builtin_bit_cast(bf16x8, pf), oacc, 0, 0, 0);
+        oacc = H16<T>::mfma(vf, pf, oacc);
     }
-    bf16_t* op = out + (win * N + qi) * (long)(nh * D) + head * D;
+    T* op = out + (win * N + qi) * (long)(nh * D) + head * D;
 #pragma unroll
     for (int g = 0; g < 4; ++g) store4(op + g * 8 + h * 4, oacc[4 * g], oacc[4 * g + 1], oacc[4 * g + 2], oacc[4 * g + 3]);
 }
@@ -479,16 +483,11 @@ __global__ __launch_bounds__(256) void adetr_rmsnorm_kernel(const T* __restrict_
         q += v[0] * v[0] + v[1] * v[1] + v[2] * v[2] + v[3] * v[3];
     }
     const float rstd = rsqrtf(fmaxf(wave_sum(q) / (float)C, eps));
-    const float lim = sizeof(T) == 2 ? 3.3895313892515355e38f : 3.4028234663852886e38f;      // finfo(bf16 / fp32).max
     for (int c = lane * 4; c < C; c += 256) {
         float v[4], wv[4], o[4];
         load4(xr + c, v); load4(w + c, wv);
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            float t = v[i] * rstd * (1.0f + wv[i]);
-            t = fminf(fmaxf(t, -lim), lim);
-            o[i] = (t != t) ? 0.f : t;
-        }
+        for (int i = 0; i < 4; ++i) o[i] = adetr_clamp<T>(v[i] * rstd * (1.0f + wv[i]));
         store4(y + (long)row * C + c, o[0], o[1], o[2], o[3]);
     }
 }
@@ -642,12 +641,14 @@ __global__ __launch_bounds__(256) void cross_attn_merge_kernel(const float* __re
 //                                                      permuted accordingly (block b, row m = key 8 (m >> 2) + (m & 3) + 4 b ... see kperm).
 // All loads of a 3-step chunk (96 keys per wave) are issued before the first MFMA: one memory round trip per chunk. Replaces
 // cross_attn_split_kernel + cross_attn_merge_kernel (15 + 4.9 us per layer, profiles/r03_t_layout_table_kernel_stats.md) for bf16.
-template <int D>
-__global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __restrict__ qpart, int S, int M, const bf16_t* __restrict__ kv,
-                                                              const bf16_t* __restrict__ vT, bf16_t* __restrict__ out,
+// fp16 is the same kernel on v_mfma_f32_16x16x32_f16 (H16<T>::mfma16: the two types share the lane maps).
+template <typename T, int D>
+__global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __restrict__ qpart, int S, int M, const T* __restrict__ kv,
+                                                              const T* __restrict__ vT, T* __restrict__ out,
                                                               const int* __restrict__ item_map, int nq, int nkv, int Lk, int Lkp, float scale) {
+    static_assert(sizeof(T) == 2, "a 16-bit storage type");
     constexpr int NW = 8, NKS = D / 32, NDB = D / 16, CW = D + 4, STEPS = 3;
-    __shared__ __attribute__((aligned(16))) bf16_t qsh[16 * D];      // q heads of this kv head, rows >= G zero
+    __shared__ __attribute__((aligned(16))) T qsh[16 * D];      // q heads of this kv head, rows >= G zero
     __shared__ __attribute__((aligned(16))) float comb[NW * 8 * CW]; // per-wave (O[D], max, sum) of up to 8 heads
     const int b = blockIdx.x, kvh = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int G = nq / nkv, Hq = nq * D, row_w = 2 * nkv * D, img = item_map[b];
@@ -658,7 +659,7 @@ __global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __res
         const int hc = min(h, G - 1);                                 // rows >= G: load a valid address, store zero
         const long col = (long)(kvh * G + hc) * D + c;
         if (S == 0) {
-            a = bf2f(reinterpret_cast<const bf16_t*>(qpart)[(long)b * Hq + col]);
+            a = Ty<T>::ld(reinterpret_cast<const T*>(qpart) + (long)b * Hq + col);
         } else {                                                      // all slab loads in flight together (a `for s < S` loop is one round trip per slab)
             float p[8];
 #pragma unroll
@@ -666,7 +667,7 @@ __global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __res
 #pragma unroll
             for (int s = 0; s < 8; ++s) a += (s < S) ? p[s] : 0.f;
         }
-        qsh[i] = f2bf(h < G ? a : 0.f);
+        Ty<T>::st(qsh + i, h < G ? a : 0.f);
     }
     __syncthreads();
     u32x4 qf[NKS];
@@ -675,8 +676,8 @@ __global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __res
     // keys of this wave: [k_lo, k_hi), a multiple of 32 long except at the end of the sequence
     const int kpw = ((Lk + NW - 1) / NW + 31) & ~31;
     const int k_lo = wave * kpw, k_hi = min(Lk, k_lo + kpw);
-    const bf16_t* kbase = kv + (long)img * Lk * row_w + kvh * D;
-    const bf16_t* vbase = vT + ((long)img * nkv + kvh) * D * Lkp;
+    const T* kbase = kv + (long)img * Lk * row_w + kvh * D;
+    const T* vbase = vT + ((long)img * nkv + kvh) * D * Lkp;
     f32x4 oacc[NDB];
 #pragma unroll
     for (int db = 0; db < NDB; ++db) oacc[db] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -710,8 +711,7 @@ __global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __res
             for (int ks = 0; ks < NKS; ++ks)
 #pragma unroll
                 for (int kb = 0; kb < 2; ++kb)
-                    sacc[kb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, kf[st][kb][ks]), __builtin_bit_cast(bf16x8, qf[ks]),
-                                                                       sacc[kb], 0, 0, 0);
+                    sacc[kb] = H16<T>::mfma16(kf[st][kb][ks], qf[ks], sacc[kb]);
             float bm = -INFINITY;
 #pragma unroll
             for (int kb = 0; kb < 2; ++kb)
@@ -741,11 +741,11 @@ __global__ __launch_bounds__(512) void cross_attn_mfma_kernel(const float* __res
 #pragma unroll
                 for (int i = 0; i < 4; ++i) oacc[db][i] *= alpha;
             u32x4 pf;
-            pf[0] = pack2(sacc[0][0], sacc[0][1]); pf[1] = pack2(sacc[0][2], sacc[0][3]);
-            pf[2] = pack2(sacc[1][0], sacc[1][1]); pf[3] = pack2(sacc[1][2], sacc[1][3]);
+            pf[0] = H16<T>::pk(sacc[0][0], sacc[0][1]); pf[1] = H16<T>::pk(sacc[0][2], sacc[0][3]);
+            pf[2] = H16<T>::pk(sacc[1][0], sacc[1][1]); pf[3] = H16<T>::pk(sacc[1][2], sacc[1][3]);
 #pragma unroll
             for (int db = 0; db < NDB; ++db)
-                oacc[db] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, vf[st][db]), __builtin_bit_cast(bf16x8, pf), oacc[db], 0, 0, 0);
+                oacc[db] = H16<T>::mfma16(vf[st][db], pf, oacc[db]);
         }
     }
     float ltot = lrun + __shfl_xor(lrun, 16, 64);
@@ -834,14 +834,9 @@ __global__ __launch_bounds__(1024) void splitk_residual_adetr_norm_kernel(const 
     float tot = 0.f;
     for (int i = 0; i < (int)(blockDim.x >> 6); ++i) tot += red[i];
     const float rstd = rsqrtf(fmaxf(tot / (float)H, eps));
-    const float lim = sizeof(T) == 2 ? 3.3895313892515355e38f : 3.4028234663852886e38f;
     float o[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        float t = v[i] * rstd * (1.0f + g[i]);
-        t = fminf(fmaxf(t, -lim), lim);
-        o[i] = (t != t) ? 0.f : t;
-    }
+    for (int i = 0; i < 4; ++i) o[i] = adetr_clamp<T>(v[i] * rstd * (1.0f + g[i]));
     if (on_row) store4(y + (long)row * H + c, o[0], o[1], o[2], o[3]);
 }
 
@@ -992,12 +987,9 @@ __global__ __launch_bounds__(256) void layout_heads_kernel(const T* __restrict__
     float q = 0.f;
     for (int c = tid; c < Hd; c += 256) { const float v = Ty<T>::ld(xr + c); q += v * v; }
     const float rstd = rsqrtf(fmaxf(block_sum(q) / (float)Hd, rms_eps));
-    const float lim = sizeof(T) == 2 ? 3.3895313892515355e38f : 3.4028234663852886e38f;
     float s = 0.f;
     for (int c = tid; c < Hd; c += 256) {
-        float t = Ty<T>::ld(xr + c) * rstd * (1.0f + Ty<T>::ld(fnorm_w + c));
-        t = fminf(fmaxf(t, -lim), lim);
-        t = Ty<T>::rnd((t != t) ? 0.f : t);
+        const float t = Ty<T>::rnd(adetr_clamp<T>(Ty<T>::ld(xr + c) * rstd * (1.0f + Ty<T>::ld(fnorm_w + c))));
         h[c] = t;
         s += t;
     }
@@ -1070,11 +1062,7 @@ __global__ __launch_bounds__(256) void layout_heads_kernel(const T* __restrict__
                 float wv[4], o[4];
                 load4(cnorm_w + c, wv);
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    float t = h[c + i] * r2 * (1.0f + wv[i]);
-                    t = fminf(fmaxf(t, -lim), lim);
-                    o[i] = (t != t) ? 0.f : t;
-                }
+                for (int i = 0; i < 4; ++i) o[i] = adetr_clamp<T>(h[c + i] * r2 * (1.0f + wv[i]));
                 store4(yn + (long)b * Hd + c, o[0], o[1], o[2], o[3]);
             }
         }

@@ -103,15 +103,15 @@ int launch_gather_add(T* x, const T* a, const int* pm, long rows, int rpi, int C
     return (int)hipGetLastError();
 }
 
-// bf16 rows of 128 / 256 / 512 / 1024 channels are held in registers by C / 8 lanes (layernorm_rows_bf16_kernel; 16-byte aligned rows)
+// bf16 / fp16 rows of 128 / 256 / 512 / 1024 channels are held in registers by C / 8 lanes (layernorm_rows_bf16_kernel; 16-byte aligned rows)
 // unless sa::Tuning lay_ln is 0; everything else takes the one-wave-per-row kernel.
 template <typename T>
 int launch_layernorm(const T* in, const T* w, const T* b, T* out, const int* pm, long rows, int rpi, int C, float eps, int rpi_out, hipStream_t s) {
-    if constexpr (std::is_same<T, bf16_t>::value) {
+    if constexpr (sizeof(T) == 2) {                                  // a 16-bit storage type
         if (rows > 0 && tuning().lay_ln) {
 #define SA_LN_ROWS(LPR, NV)                                                                                                              \
     {                                                                                                                                    \
-        hipLaunchKernelGGL((layernorm_rows_bf16_kernel<LPR, NV>), dim3((unsigned)cdivl(rows, 256 / LPR)), dim3(256), 0, s, in, w, b, out, \
+        hipLaunchKernelGGL((layernorm_rows_bf16_kernel<T, LPR, NV>), dim3((unsigned)cdivl(rows, 256 / LPR)), dim3(256), 0, s, in, w, b, out, \
                            pm, rows, rpi, eps, rpi_out);                                                                                 \
         return (int)hipGetLastError();                                                                                                   \
     }
@@ -126,11 +126,11 @@ int launch_layernorm(const T* in, const T* w, const T* b, T* out, const int* pm,
     return (int)hipGetLastError();
 }
 
-// one workgroup per (window of 64 tokens, head); bf16 on the matrix cores, fp32 on the VALU
+// one workgroup per (window of 64 tokens, head); bf16 and fp16 on the matrix cores, fp32 on the VALU
 template <typename T>
 int launch_window_attn(const T* qkv, const float* bias, T* out, long windows, int nh, int nkv, int nwx, int nwy, int shift, int ws, hipStream_t s) {
-    if constexpr (std::is_same<T, bf16_t>::value)
-        hipLaunchKernelGGL(swin_window_attn_mfma_kernel, dim3((unsigned)windows, nh), dim3(128), 0, s, qkv, bias, out, nh, nkv, nwx, nwy, shift, ws);
+    if constexpr (sizeof(T) == 2)
+        hipLaunchKernelGGL(swin_window_attn_mfma_kernel<T>, dim3((unsigned)windows, nh), dim3(128), 0, s, qkv, bias, out, nh, nkv, nwx, nwy, shift, ws);
     else
         hipLaunchKernelGGL(swin_window_attn_kernel<T>, dim3((unsigned)windows, nh), dim3(256), 0, s, qkv, bias, out, nh, nkv, nwx, nwy, shift, ws);
     return (int)hipGetLastError();
@@ -150,7 +150,7 @@ int launch_rmsnorm(const T* x, const T* w, T* y, int rows, int C, float eps, hip
 }
 
 // Cross attention over Lk cached keys. fp32: `ranges` key ranges of `chunk` keys (>= 128 keys per range, at most 8 ranges), one record of
-// head_dim + 2 floats per (row, head, range) in `scratch`. bf16: the values transposed once per encode into rows of Lkp keys (whole 32-key steps).
+// head_dim + 2 floats per (row, head, range) in `scratch`. bf16 / fp16: the values transposed once per encode into rows of Lkp keys (whole 32-key steps).
 struct CrossPlan { int chunk, ranges, Lkp; };
 inline CrossPlan cross_plan(int Lk) {
     const int n = std::max(1, std::min(8, Lk / 128));
@@ -165,7 +165,7 @@ int launch_transpose_cross_v(const T* kv, T* vT, int images, int Lk, int nkv, in
     hipLaunchKernelGGL(transpose_cross_v_kernel<T>, dim3(64, images), dim3(256), 0, s, kv, vT, Lk, cross_plan(Lk).Lkp, nkv, d);
     return (int)hipGetLastError();
 }
-// rows query rows (S == 0: qpart is a plain [M][nq * d] matrix of T; else the sum of S <= 8 fp32 slabs [S][M][nq * d]); bf16 reads kv and vT and
+// rows query rows (S == 0: qpart is a plain [M][nq * d] matrix of T; else the sum of S <= 8 fp32 slabs [S][M][nq * d]); bf16 / fp16 read kv and vT and
 // needs no scratch, fp32 reads kv and goes through scratch.
 template <typename T>
 int launch_cross_attn(const float* qpart, int S, int M, const T* kv, const T* vT, float* scratch, T* out, const int* item_map, int rows, int nq,
@@ -173,10 +173,10 @@ int launch_cross_attn(const float* qpart, int S, int M, const T* kv, const T* vT
     const int G = nq / nkv;
     if (G < 1 || G > 8 || nq % nkv || (d != 64 && d != 32) || S < 0 || S > 8 || Lk < 1) return SA_ERR_UNSUPPORTED;
     const CrossPlan cp = cross_plan(Lk);
-    if constexpr (std::is_same<T, bf16_t>::value) {                  // matrix-core kernel on the transposed values (layout_kernels.h)
-        if (d == 64) hipLaunchKernelGGL((cross_attn_mfma_kernel<64>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk,
+    if constexpr (sizeof(T) == 2) {                                  // bf16 / fp16: matrix-core kernel on the transposed values (layout_kernels.h)
+        if (d == 64) hipLaunchKernelGGL((cross_attn_mfma_kernel<T, 64>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk,
                                         cp.Lkp, scale);
-        else hipLaunchKernelGGL((cross_attn_mfma_kernel<32>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk, cp.Lkp,
+        else hipLaunchKernelGGL((cross_attn_mfma_kernel<T, 32>), dim3(rows, nkv), dim3(512), 0, s, qpart, S, M, kv, vT, out, item_map, nq, nkv, Lk, cp.Lkp,
                                 scale);
     } else {
         const size_t lds = ((size_t)G * cp.chunk + (size_t)G * d + 1024) * sizeof(float);
@@ -253,7 +253,7 @@ struct LayoutModel : LayoutBase {
     std::vector<int> grid_hp, grid_wp;           // per stage: the grid rounded up to whole windows
     // decoder
     T *ckv;                                      // [layer][B][Lk][2 * kvd]
-    T *cvT = nullptr;                            // bf16: [layer][B][nkv][hd][Lkp] transposed cross-attention values (cross_attn_mfma_kernel)
+    T *cvT = nullptr;                            // bf16 / fp16: [layer][B][nkv][hd][Lkp] transposed cross-attention values (cross_attn_mfma_kernel)
     int Lkp = 0;
     T *kcache, *vcache;                          // [layer][B][nkv][Tmax][hd]
     T *dx, *dh, *dq, *dattn, *dres, *dmlp;
@@ -466,7 +466,7 @@ struct LayoutModel : LayoutBase {
             const int lb = dec_base + l * SA_LD_COUNT;
             T* dst = ckv + (size_t)l * c.max_batch * Lk * kv2;
             if ((rc = gemm<EPI_BIAS>(x, dim, W(lb + SA_LD_CKV_W), dim, dst, kv2, nullptr, nullptr, 0, (int)rows, kv2, dim, s))) return rc;
-            if constexpr (std::is_same<T, bf16_t>::value)
+            if constexpr (sizeof(T) == 2)
                 if ((rc = lay::launch_transpose_cross_v<T>(dst, cvT + (size_t)l * c.max_batch * kvd() * Lkp, B, Lk, c.dec_kv_heads, hd(), s))) return rc;
         }
         return (int)hipGetLastError();
@@ -820,6 +820,28 @@ int op_gemm_geglu(int dtype, const void* X, long ldx, const void* W, long ldw, v
         GemmArgs<bf16_t, bf16_t> a{(const bf16_t*)X, ldx, (const bf16_t*)W, ldw, (bf16_t*)C, ldc, nullptr, nullptr, 0, M, N, K};
         return launch_gemm<bf16_t, bf16_t, EPI_GEGLU>(a, s);
     }
+    if (dtype == SA_DTYPE_F16) {
+        GemmArgs<fp16_t, fp16_t> a{(const fp16_t*)X, ldx, (const fp16_t*)W, ldw, (fp16_t*)C, ldc, nullptr, nullptr, 0, M, N, K};
+        return launch_gemm<fp16_t, fp16_t, EPI_GEGLU>(a, s);
+    }
+    return SA_ERR_UNSUPPORTED;
+}
+
+// launch_decode_attn (decode_attn.h) in fp16: the fourth-version kernel on v_mfma_f32_32x32x16_f16 at the head shapes of this family's decoders,
+// in this code object beside LayoutModel<fp16_t>, its only user (the recogniser runs bf16). Tuning::dattn_db as in bf16; no third version.
+template <int D>
+static int decode_attn_flash_f16(const DecodeAttnArgs<fp16_t>& a, hipStream_t s) {
+    const Tuning& t = tuning();
+    if (t.dattn_db == 1 || (t.dattn_db == 0 && !t.graph && a.ctx_bound > 128 && a.rows * a.nkv <= 256))
+        return decode_attn_as<decode_attn_flash2_kernel<D, 8, true, fp16_t>>(a, decode_attn_flash2_lds<D, 8, true>(), s, a.out8, a.sout, a.srows);
+    return decode_attn_as<decode_attn_flash2_kernel<D, 8, false, fp16_t>>(a, decode_attn_flash2_lds<D, 8, false>(), s, a.out8, a.sout, a.srows);
+}
+template <>
+int launch_decode_attn<fp16_t>(const DecodeAttnArgs<fp16_t>& a, hipStream_t s) {
+    const int G = a.nq / a.nkv;
+    if (a.out8 || G < 1 || G > 8 || a.nq % a.nkv) return SA_ERR_UNSUPPORTED;
+    if (a.d == 64) return decode_attn_flash_f16<64>(a, s);
+    if (a.d == 32) return decode_attn_flash_f16<32>(a, s);
     return SA_ERR_UNSUPPORTED;
 }
 }  // namespace sa
@@ -849,6 +871,10 @@ int surya_layout_create(const surya_layout_config* cfg, const void* const* weigh
         h->impl = std::move(m);
     } else if (cfg->dtype == SA_DTYPE_BF16) {
         auto m = std::make_unique<LayoutModel<bf16_t>>();
+        rc = m->init(*cfg, weights, n_weights);
+        h->impl = std::move(m);
+    } else if (cfg->dtype == SA_DTYPE_F16) {
+        auto m = std::make_unique<LayoutModel<fp16_t>>();
         rc = m->init(*cfg, weights, n_weights);
         h->impl = std::move(m);
     } else {
@@ -914,9 +940,11 @@ int surya_layout_preprocess(const uint8_t* pages, size_t pages_bytes, const void
 
 // ------------------------------------------------------------------------------------------------ op level
 // Every kernel of the family alone, through the launch functions LayoutModel calls (sa::lay::launch_*). Caller-owned device memory, enqueue only.
-#define SA_LAY_DT(CALL_F32, CALL_BF16)                 \
+// The bodies (lay_op_*) take all three dtypes; the exported entries over them are at the end of the file.
+#define SA_LAY_DT(CALL_F32, CALL_16)                   \
     if (dtype == SA_DTYPE_F32) { typedef float T; return CALL_F32; }     \
-    if (dtype == SA_DTYPE_BF16) { typedef bf16_t T; return CALL_BF16; } \
+    if (dtype == SA_DTYPE_BF16) { typedef bf16_t T; return CALL_16; }   \
+    if (dtype == SA_DTYPE_F16) { typedef fp16_t T; return CALL_16; }    \
     return SA_ERR_UNSUPPORTED;
 #define SA_LAY_BOTH(CALL) SA_LAY_DT(CALL, CALL)
 
@@ -943,27 +971,27 @@ int surya_lay_cross_plan(int Lk, int32_t* chunk, int32_t* ranges, int32_t* Lkp) 
     return SA_OK;
 }
 
-int surya_op_lay_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image,
+static int lay_op_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image,
                            int C, float eps, int rows_per_image_out, void* stream) {
     if (!x || !w || !b || !y || rows <= 0 || rows_per_image <= 0 || C <= 0 || C % 4) return SA_ERR_ARG;
     SA_LAY_BOTH(lay::launch_layernorm<T>((const T*)x, (const T*)w, (const T*)b, (T*)y, perm, rows, rows_per_image, C, eps, rows_per_image_out,
                                          (hipStream_t)stream))
 }
 
-int surya_op_lay_window_attn(int dtype, const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift,
+static int lay_op_window_attn(int dtype, const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift,
                              int ws, void* stream) {
     if (!qkv || !bias || !out || windows <= 0 || nh <= 0 || nkv <= 0 || nwx <= 0 || nwy <= 0 || shift < 0) return SA_ERR_ARG;
     if (ws != 8 || shift >= ws) return SA_ERR_UNSUPPORTED;           // 64 tokens per window, head dim 32
     SA_LAY_BOTH(lay::launch_window_attn<T>((const T*)qkv, bias, (T*)out, windows, nh, nkv, nwx, nwy, shift, ws, (hipStream_t)stream))
 }
 
-int surya_op_lay_merge_ln(int dtype, const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream) {
+static int lay_op_merge_ln(int dtype, const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream) {
     if (!x || !w || !b || !y || B <= 0 || H < 2 || W < 2 || C <= 0) return SA_ERR_ARG;
     if (H % 2 || W % 2 || C % 4) return SA_ERR_SHAPE;
     SA_LAY_BOTH(lay::launch_merge_ln<T>((const T*)x, (const T*)w, (const T*)b, (T*)y, B, H, W, C, eps, (hipStream_t)stream))
 }
 
-int surya_op_lay_rows(int dtype, int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream) {
+static int lay_op_rows(int dtype, int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream) {
     if (!dst || !dims) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     switch (kind) {
@@ -989,45 +1017,49 @@ int surya_op_lay_rows(int dtype, int kind, void* dst, const void* src, const int
     return SA_ERR_ARG;
 }
 
-int surya_op_lay_cross_attn(int dtype, int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map,
+static int lay_op_cross_attn(int dtype, int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map,
                             void* out, float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream) {
     if (!qpart || !kv || !item_map || !out || M <= 0 || n_images <= 0 || nq <= 0 || nkv <= 0 || Lk <= 0) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
-    if (dtype == SA_DTYPE_BF16) {
-        if (!vT) return SA_ERR_ARG;
-        if (head_dim != 64 && head_dim != 32) return SA_ERR_UNSUPPORTED;
-        const int rc = lay::launch_transpose_cross_v<bf16_t>((const bf16_t*)kv, (bf16_t*)vT, n_images, Lk, nkv, head_dim, s);
-        if (rc) return rc;
-        return lay::launch_cross_attn<bf16_t>((const float*)qpart, S, M, (const bf16_t*)kv, (const bf16_t*)vT, nullptr, (bf16_t*)out, item_map, M, nq, nkv,
-                                              head_dim, Lk, scale, s);
-    }
     if (dtype == SA_DTYPE_F32) {
         if (!scratch) return SA_ERR_ARG;
         return lay::launch_cross_attn<float>((const float*)qpart, S, M, (const float*)kv, nullptr, scratch, (float*)out, item_map, M, nq, nkv, head_dim, Lk,
                                              scale, s);
     }
-    return SA_ERR_UNSUPPORTED;
+    if (dtype != SA_DTYPE_BF16 && dtype != SA_DTYPE_F16) return SA_ERR_UNSUPPORTED;
+    if (!vT) return SA_ERR_ARG;
+    if (head_dim != 64 && head_dim != 32) return SA_ERR_UNSUPPORTED;
+#define SA_LAY_CROSS16(T)                                                                                                                  \
+    {                                                                                                                                      \
+        const int rc = lay::launch_transpose_cross_v<T>((const T*)kv, (T*)vT, n_images, Lk, nkv, head_dim, s);                             \
+        if (rc) return rc;                                                                                                                 \
+        return lay::launch_cross_attn<T>((const float*)qpart, S, M, (const T*)kv, (const T*)vT, nullptr, (T*)out, item_map, M, nq, nkv, head_dim, \
+                                         Lk, scale, s);                                                                                    \
+    }
+    if (dtype == SA_DTYPE_BF16) SA_LAY_CROSS16(bf16_t)
+    SA_LAY_CROSS16(fp16_t)
+#undef SA_LAY_CROSS16
 }
 
-int surya_op_lay_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int C, float eps, void* stream) {
+static int lay_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int C, float eps, void* stream) {
     if (!x || !w || !y || rows <= 0 || C <= 0 || C % 4) return SA_ERR_ARG;
     SA_LAY_BOTH(lay::launch_rmsnorm<T>((const T*)x, (const T*)w, (T*)y, rows, C, eps, (hipStream_t)stream))
 }
 
-int surya_op_lay_reduce_norm(int dtype, const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y,
+static int lay_op_reduce_norm(int dtype, const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y,
                              int H, float eps, void* stream) {
     if (!part || !res || !x_out || M <= 0 || (w && !y)) return SA_ERR_ARG;
     SA_LAY_BOTH(lay::launch_reduce_norm<T>(part, S, M, (const T*)res, (const T*)bias, (T*)x_out, (const T*)w, (T*)y, H, eps, (hipStream_t)stream))
 }
 
-int surya_op_lay_prefill_attn(int dtype, int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn,
+static int lay_op_prefill_attn(int dtype, int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn,
                               int nq, int nkv, int Tmax, float scale, void* stream) {
     if (!qkv || !out || !kcache || !vcache || !rope_cs || B <= 0 || nq <= 0 || nkv <= 0) return SA_ERR_ARG;
     SA_LAY_BOTH(lay::launch_prefill_attn<T>((const T*)qkv, (T*)out, (T*)kcache, (T*)vcache, (const float2*)rope_cs, B, Tn, nq, nkv, head_dim, Tmax, scale,
                                             (hipStream_t)stream))
 }
 
-int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed,
+static int lay_op_embed(int dtype, int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed,
                        int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream) {
     if (!tokens || !tabs || !x || rows <= 0 || Hd <= 0 || bbox_size <= 0) return SA_ERR_ARG;
     if (vocab <= bbox_size) return SA_ERR_SHAPE;                   // corners clamp to [0, bbox_size] and index [vocab]-row tables (surya_layout_create)
@@ -1038,7 +1070,7 @@ int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void*
                                      merge_count, (hipStream_t)stream))
 }
 
-int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w,
+static int lay_op_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w,
                        const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream) {
     if (!x || !fnorm_w || !ln_w || !ln_b || !lm_w || !bb_w || !bb_b || !class_logits || !bbox || B <= 0 || Hd <= 0 || label_count <= 0 || ldx < Hd)
         return SA_ERR_ARG;
@@ -1047,5 +1079,62 @@ int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, 
 }
 #undef SA_LAY_BOTH
 #undef SA_LAY_DT
+
+// The entries of include/surya_amd.h over the bodies above. surya_op_lay_<op>(dtype, ...) keeps its contract of two dtypes (fp32 and bf16;
+// anything else SA_ERR_UNSUPPORTED, which callers rely on); surya_op_lay_<op>_f16(...) is the same call on the fp16 instance.
+int surya_op_lay_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image, int C, float eps, int rows_per_image_out, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_layernorm(dtype, x, w, b, y, perm, rows, rows_per_image, C, eps, rows_per_image_out, stream);
+}
+int surya_op_lay_layernorm_f16(const void* x, const void* w, const void* b, void* y, const int32_t* perm, long rows, int rows_per_image, int C, float eps, int rows_per_image_out, void* stream) { return lay_op_layernorm(SA_DTYPE_F16, x, w, b, y, perm, rows, rows_per_image, C, eps, rows_per_image_out, stream); }
+
+int surya_op_lay_window_attn(int dtype, const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift, int ws, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_window_attn(dtype, qkv, bias, out, windows, nh, nkv, nwx, nwy, shift, ws, stream);
+}
+int surya_op_lay_window_attn_f16(const void* qkv, const float* bias, void* out, long windows, int nh, int nkv, int nwx, int nwy, int shift, int ws, void* stream) { return lay_op_window_attn(SA_DTYPE_F16, qkv, bias, out, windows, nh, nkv, nwx, nwy, shift, ws, stream); }
+
+int surya_op_lay_merge_ln(int dtype, const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_merge_ln(dtype, x, w, b, y, B, H, W, C, eps, stream);
+}
+int surya_op_lay_merge_ln_f16(const void* x, const void* w, const void* b, void* y, int B, int H, int W, int C, float eps, void* stream) { return lay_op_merge_ln(SA_DTYPE_F16, x, w, b, y, B, H, W, C, eps, stream); }
+
+int surya_op_lay_rows(int dtype, int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_rows(dtype, kind, dst, src, index, dims, stream);
+}
+int surya_op_lay_rows_f16(int kind, void* dst, const void* src, const int32_t* index, const int32_t* dims, void* stream) { return lay_op_rows(SA_DTYPE_F16, kind, dst, src, index, dims, stream); }
+
+int surya_op_lay_cross_attn(int dtype, int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map, void* out, float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_cross_attn(dtype, head_dim, qpart, S, M, kv, n_images, item_map, out, scratch, vT, nq, nkv, Lk, scale, stream);
+}
+int surya_op_lay_cross_attn_f16(int head_dim, const void* qpart, int S, int M, const void* kv, int n_images, const int32_t* item_map, void* out, float* scratch, void* vT, int nq, int nkv, int Lk, float scale, void* stream) { return lay_op_cross_attn(SA_DTYPE_F16, head_dim, qpart, S, M, kv, n_images, item_map, out, scratch, vT, nq, nkv, Lk, scale, stream); }
+
+int surya_op_lay_rmsnorm(int dtype, const void* x, const void* w, void* y, int rows, int C, float eps, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_rmsnorm(dtype, x, w, y, rows, C, eps, stream);
+}
+int surya_op_lay_rmsnorm_f16(const void* x, const void* w, void* y, int rows, int C, float eps, void* stream) { return lay_op_rmsnorm(SA_DTYPE_F16, x, w, y, rows, C, eps, stream); }
+
+int surya_op_lay_reduce_norm(int dtype, const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y, int H, float eps, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_reduce_norm(dtype, part, S, M, res, bias, x_out, w, y, H, eps, stream);
+}
+int surya_op_lay_reduce_norm_f16(const float* part, int S, int M, const void* res, const void* bias, void* x_out, const void* w, void* y, int H, float eps, void* stream) { return lay_op_reduce_norm(SA_DTYPE_F16, part, S, M, res, bias, x_out, w, y, H, eps, stream); }
+
+int surya_op_lay_prefill_attn(int dtype, int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn, int nq, int nkv, int Tmax, float scale, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_prefill_attn(dtype, head_dim, qkv, out, kcache, vcache, rope_cs, B, Tn, nq, nkv, Tmax, scale, stream);
+}
+int surya_op_lay_prefill_attn_f16(int head_dim, const void* qkv, void* out, void* kcache, void* vcache, const float* rope_cs, int B, int Tn, int nq, int nkv, int Tmax, float scale, void* stream) { return lay_op_prefill_attn(SA_DTYPE_F16, head_dim, qkv, out, kcache, vcache, rope_cs, B, Tn, nq, nkv, Tmax, scale, stream); }
+
+int surya_op_lay_embed(int dtype, int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed, int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_embed(dtype, family, tokens, tabs, x, rows, Hd, box_embed, bbox_size, vocab, label_count, category_count, merge_count, stream);
+}
+int surya_op_lay_embed_f16(int family, const int32_t* tokens, const void* const* tabs, void* x, int rows, int Hd, int box_embed, int bbox_size, int vocab, int label_count, int category_count, int merge_count, void* stream) { return lay_op_embed(SA_DTYPE_F16, family, tokens, tabs, x, rows, Hd, box_embed, bbox_size, vocab, label_count, category_count, merge_count, stream); }
+
+int surya_op_lay_heads(int dtype, const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w, const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream) {
+    return dtype == SA_DTYPE_F16 ? SA_ERR_UNSUPPORTED : lay_op_heads(dtype, x, ldx, fnorm_w, ln_w, ln_b, lm_w, bb_w, bb_b, class_logits, bbox, B, Hd, label_count, rms_eps, ln_eps, stream);
+}
+int surya_op_lay_heads_f16(const void* x, long ldx, const void* fnorm_w, const void* ln_w, const void* ln_b, const void* lm_w, const void* bb_w, const void* bb_b, float* class_logits, float* bbox, int B, int Hd, int label_count, float rms_eps, float ln_eps, void* stream) { return lay_op_heads(SA_DTYPE_F16, x, ldx, fnorm_w, ln_w, ln_b, lm_w, bb_w, bb_b, class_logits, bbox, B, Hd, label_count, rms_eps, ln_eps, stream); }
+
+int surya_op_gemm_geglu_f16(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, int M, int N, int K, void* stream) {
+    if (!X || !W || !C || N % 2) return SA_ERR_ARG;
+    return sa::op_gemm_geglu(SA_DTYPE_F16, X, ldx, W, ldw, C, ldc, M, N, K, (hipStream_t)stream);
+}
 
 }  // extern "C"

@@ -31,14 +31,6 @@ namespace sa {
 // --------------------------------------------------------------------------------- decode attention launch
 // launch_decode_attn (decode_attn.h): every decode-attention launch of the library -- RecModel::decode_layer, LayoutModel::decode_layers
 // and surya_op_decode_attn -- is this one, so a kernel tested through the hook is launched exactly as the engines launch it.
-template <auto KERN, typename T, typename... X>
-static int decode_attn_as(const DecodeAttnArgs<T>& a, size_t lds, hipStream_t s, X... extra) {
-    static AttrOnce attr;                                    // one per kernel: KERN is a template argument
-    attr.ensure(KERN, lds);
-    hipLaunchKernelGGL(KERN, dim3(a.rows, a.nkv), dim3(256), lds, s, a.qkv_part, a.S, a.qkv_bias, a.out, a.kcache, a.vcache, a.active_slots,
-                       a.row_len, a.rope_cs, a.nq, a.nkv, a.max_kv_len, a.scale, extra...);
-    return (int)hipGetLastError();
-}
 template <int D, int MAXG>
 static int decode_attn_flash(const DecodeAttnArgs<bf16_t>& a, hipStream_t s) {
     const Tuning& t = tuning();
@@ -1176,7 +1168,8 @@ int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, cons
     if (!X || !W || !C) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     if (epi == EPI_GEGLU)                 // no bias, no residual, output in the compute dtype (LayoutModel's only use of it)
-        return (bias || R || out_f32 || N % 2) ? SA_ERR_UNSUPPORTED : sa::op_gemm_geglu(dtype, X, ldx, W, ldw, C, ldc, M, N, K, s);
+        return (bias || R || out_f32 || N % 2 || dtype == SA_DTYPE_F16) ? SA_ERR_UNSUPPORTED       // (fp16: surya_op_gemm_geglu_f16, layout_model.hip)
+                                                                         : sa::op_gemm_geglu(dtype, X, ldx, W, ldw, C, ldc, M, N, K, s);
     if (dtype == SA_DTYPE_F32) return op_gemm_t<float, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
     if (dtype == SA_DTYPE_BF16)
         return out_f32 ? op_gemm_t<bf16_t, float>(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s)
@@ -1261,6 +1254,11 @@ int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_s
         sa::DecodeAttnArgs<float> a{qkv_part, n_slabs, (const float*)qkv_bias, (float*)out, (float*)kcache, (float*)vcache, active_slots, row_len, cs,
                                     rows, heads, kv_heads, head_dim, max_kv_len, scale};
         return sa::launch_decode_attn<float>(a, s);
+    }
+    if (dtype == SA_DTYPE_F16) {              // the layout / table decoder's head shapes (d = 64 / 32), built in layout_model.hip
+        sa::DecodeAttnArgs<sa::fp16_t> a{qkv_part, n_slabs, (const sa::fp16_t*)qkv_bias, (sa::fp16_t*)out, (sa::fp16_t*)kcache, (sa::fp16_t*)vcache,
+                                         active_slots, row_len, cs, rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        return sa::launch_decode_attn<sa::fp16_t>(a, s);
     }
     return SA_ERR_UNSUPPORTED;
 }

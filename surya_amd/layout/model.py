@@ -158,14 +158,17 @@ def repack_layout_weights(cfg, sd, dtype: torch.dtype, device) -> List[torch.Ten
     return out
 
 
+_DTYPE_CODES = {torch.float32: L.DTYPE_F32, torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}
+
+
 class HipLayoutModel:
     def __init__(self, cfg, state_dict, *, dtype: torch.dtype = torch.bfloat16, device="cuda:0", max_batch: int = 32,
                  max_boxes: int = 100):
         """cfg: layout.config.LayoutConfig or table_rec.config.TableRecConfig (the two callers of the model family)."""
         if not torch.cuda.is_available():
             raise L.SuryaAmdError("HipLayoutModel needs a GPU (MI355X); there is no CPU fallback")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be float32 (reference mode) or bfloat16")
+        if dtype not in _DTYPE_CODES:
+            raise ValueError("dtype must be float32 (reference mode), bfloat16 (the default) or float16 (the reference's GPU dtype)")
         self.lib = L.lib()
         self.cfg, self.dtype, self.device = cfg, dtype, torch.device(device)
         self.max_batch, self.max_boxes = max_batch, max_boxes
@@ -181,7 +184,7 @@ class HipLayoutModel:
                           dec_hidden=d.hidden_size, dec_inter=d.intermediate_size, dec_heads=d.num_attention_heads,
                           dec_kv_heads=d.num_key_value_heads, vocab=d.vocab_size, label_count=self.label_count, bbox_size=d.bbox_size,
                           rms_eps=d.rms_norm_eps, ln_eps=d.layer_norm_eps, max_batch=max_batch, max_boxes=max_boxes,
-                          dtype=L.DTYPE_F32 if dtype == torch.float32 else L.DTYPE_BF16,
+                          dtype=_DTYPE_CODES[dtype],
                           family=FAMILY_TABLE if self.is_table else FAMILY_LAYOUT, box_embed=d.box_embed_size if self.is_table else d.hidden_size,
                           category_count=d.category_count if self.is_table else 0, merge_count=d.merge_count if self.is_table else 0)
         for i, (dep, nh, nkv) in enumerate(zip(e.depths, e.num_heads, e.num_kv_heads)):

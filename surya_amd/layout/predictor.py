@@ -32,11 +32,25 @@ def _round_bf16(a: np.ndarray) -> np.ndarray:
     return ((u + (((u >> 16) & 1) + 0x7FFF)) & 0xFFFF0000).view(np.float32)
 
 
+def _round_f16(a: np.ndarray) -> np.ndarray:
+    """fp32 values rounded to the nearest float16 (ties to even, numpy's conversion), kept as fp32 -- what an fp16 tensor op leaves behind.
+    Above 1024 the fp16 spacing is 1 (above 2048: 2), so the corner sums of a box near the far edge round visibly."""
+    return np.ascontiguousarray(a, np.float32).astype(np.float16).astype(np.float32)
+
+
+_ROUNDERS = {"bfloat16": _round_bf16, "bf16": _round_bf16, "float16": _round_f16, "fp16": _round_f16, "half": _round_f16}
+
+
+def model_dtype_name(model) -> str:
+    """The name polygons_of_predictions takes for the dtype a model computes in (a host stand-in without `dtype` counts as float32)."""
+    return {torch.bfloat16: "bfloat16", torch.float16: "float16"}.get(getattr(model, "dtype", torch.float32), "float32")
+
+
 def polygons_of_predictions(preds: np.ndarray, sizes: np.ndarray, bbox_scaler, skew_scaler, skew_min=0.001, dtype="float32") -> np.ndarray:
     """surya/layout/util.py:4-40 for a batch: preds [n, >= 6] (the fed-back token as floats), sizes [n, 2] = (width, height) ->
     float64 [n, 4, 2]. The reference does the corner arithmetic with TENSOR ops, i.e. in the model dtype (every intermediate rounded to
-    fp32, or to bf16 for a bf16 model), and only the final `.item() * scale` in Python floats; `dtype` names that dtype."""
-    R = _round_bf16 if dtype in ("bfloat16", "bf16") else (lambda a: a)
+    fp32, to bf16 for a bf16 model, to fp16 for an fp16 model), and only the final `.item() * scale` in Python floats; `dtype` names that dtype."""
+    R = _ROUNDERS.get(dtype, lambda a: a)
     p = R(np.asarray(preds, np.float32))
     sz = np.asarray(sizes, np.float64).reshape(-1, 2)
     w_scale, h_scale = sz[:, 0] / bbox_scaler, sz[:, 1] / bbox_scaler
@@ -199,7 +213,7 @@ class LayoutPredictor(BasePredictor):
         sizes = np.asarray(orig_sizes, np.int64).reshape(n, 2)
         self.model.set_feedback(sizes)
         runs = FedRuns(self.model, 0, LAYOUT_MAX_BOXES, settings.LAYOUT_STEPS_PER_SYNC)
-        mdtype = "bfloat16" if getattr(self.model, "dtype", torch.float32) == torch.bfloat16 else "float32"
+        mdtype = model_dtype_name(self.model)
         boxes = np.full((n, 7), dcfg.bos_token_id, np.int32)
         preds = [[] for _ in range(n)]
         all_done = np.zeros(n, bool)
@@ -209,8 +223,8 @@ class LayoutPredictor(BasePredictor):
             cls, box = runs.step(boxes, ~all_done)           # finished pages: the device's rule keeps running, the host's does not
             class_preds = cls.argmax(-1)
             box_preds = box * dcfg.bbox_size
-            if mdtype == "bfloat16":
-                box_preds = _round_bf16(box_preds)                   # a tensor op in the model dtype (exact for bbox_size = 1024)
+            if mdtype in _ROUNDERS:
+                box_preds = _ROUNDERS[mdtype](box_preds)             # a tensor op in the model dtype (exact for bbox_size = 1024)
             all_done |= (class_preds == dcfg.eos_token_id) | (class_preds == dcfg.pad_token_id)
             if all_done.all():
                 break
