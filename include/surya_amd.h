@@ -14,9 +14,11 @@
  *   - all work is enqueued on the hipStream_t passed in (as void*); functions do not synchronise unless
  *     documented ("sync"). A handle is re-entrant but not thread-safe: one host thread per handle, like the
  *     reference's single-threaded device path (surya/settings.py:179-183).
- *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (the text detector, the
- *     OCR-error classifier, the layout / table-recognition engine and the op-level entries; the recogniser returns
- *     SA_ERR_UNSUPPORTED for it).
+ *   - dtype: 0 = fp32 ("reference mode": exact-f32 MFMA, used for bit-exact token tests), 1 = bf16, 2 = fp16 (every engine and the op-level
+ *     entries). surya_rec_config takes all three: SA_DTYPE_F16 runs the recogniser -- vision encoder, prompt prefill, KV append, the decode steps
+ *     with the device-resident greedy loop, the heads, surya_rec_copy_last_logits, surya_rec_encode_only -- in fp16 with torch's .half()
+ *     rounding (nearest even, overflow to +-inf; no loss scaling, no clamping) and fp32 accumulation; surya_rec_set_mx_weights and
+ *     surya_rec_set_kv_fp8 return SA_ERR_UNSUPPORTED on an fp16 handle as on an fp32 one.
  */
 #ifndef SURYA_AMD_H
 #define SURYA_AMD_H
@@ -237,7 +239,8 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
  * rope_cs[max_kv_len][head_dim / 2][2]; k, v appended to the caches [slot][kv_head][max_kv_len][head_dim] at row_len[r];
  * out[r][heads * head_dim] = attention over row_len[r] + 1 keys (decoder/__init__.py:193-234). bf16 runs
  * decode_attn_flash2_kernel (tuning dattn = 4, the default) or decode_attn_flash_kernel (dattn = 3), fp32 decode_attn_mfma_kernel, fp16
- * decode_attn_flash2_kernel<.., fp16_t> at head_dim 64 / 32 with heads / kv_heads <= 8 (the layout / table decoders' shapes). The hook
+ * decode_attn_flash2_kernel<.., fp16_t> at head_dim 64 / 32 with heads / kv_heads <= 8 (the layout / table decoders' shapes) and at head_dim
+ * 128 with heads / kv_heads <= 5 or <= 8 (the recogniser's; fp16 has no decode_attn_flash_kernel: dattn = 3 runs the flash2 kernel too). The hook
  * has no host bound on the contexts, so of decode_attn_flash2_kernel's two forms the two-buffer one runs at dattn_db = 1 only; the engine also
  * picks it at dattn_db = 0 once a context exceeds 128 keys. All pointers device. Enqueue only. */
 int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const void* v, void* out, const int32_t* seg_len,
@@ -258,6 +261,16 @@ int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, c
 /* bf16 split-K projection of the decode step (launch_gemm_splitk): raw fp32 partial sums to part[*splitk][M][N] (capacity 8 slabs), no
  * epilogue; M <= 256 as the decoder runs it. */
 int surya_op_gemm_splitk_bf16(const void* X, long ldx, const void* W, long ldw, float* part, int M, int N, int K, int* splitk, void* stream);
+/* The same in fp16 (launch_gemm_splitk<fp16_t>, as RecModel<fp16_t> launches it; the 128 x 128 / 128 x 64 tiles above 256 rows included). */
+int surya_op_gemm_splitk_f16(const void* X, long ldx, const void* W, long ldw, float* part, int M, int N, int K, int* splitk, void* stream);
+/* The fp16 recogniser's GEMMs through launch_gemm, the launcher RecModel<fp16_t> uses (surya_op_gemm(SA_DTYPE_F16, ..) keeps refusing what it
+ * refused). X [M][K], W [N][K], bias [N] or NULL: fp16. mode 0: 16-bit output, epi 0 bias, 1 residual (R fp16, required), 2 gelu, 3 swiglu
+ * (W rows interleaved, C is [M][N/2]). mode 1: fp32 output C [M][N], epi 0 only (surya_rec_copy_last_logits). mode 2: the lm_head with greedy
+ * partials, epi 6 only: C, R unused; amax receives one float4 {max, bits of the first argmax column, sum exp(v - max), 0} per (row, column tile)
+ * at amax[(m * cdiv(N, *bn_used) + tile) * 4], *bn_used = the tile width chosen (>= 64: size amax for M * cdiv(N, 64) float4). Anything else
+ * SA_ERR_UNSUPPORTED. Enqueue only. */
+int surya_op_rec_gemm_f16(int mode, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R,
+                          long ldr, int M, int N, int K, float* amax, int* bn_used, void* stream);
 /* MXFP8 ops (csrc/gemm_mx.h). quantize: fp32 rows [rows][K], K % 128 == 0 -> e4m3 [rows][K] + e8m0 scales K-tile-major
  * [K / 128][rows][4], with the rule every producer kernel uses (block scale = smallest power of two that keeps absmax <=
  * 448, round to nearest even). gemm_mx: C[M,N] fp32 = X W^T from MXFP8 operands (scales K-tile-major with M resp. N rows),

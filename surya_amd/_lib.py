@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.so")   # env: A/B builds of the kernels
 
 SA_MAX_STEPS = 16
-DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; fp16: every engine but the recogniser, and their op-level entries
+DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
  RW_LM_B, RW_BBOX_W, RW_BBOX_B, RW_ENC_INVFREQ, RW_DEC_INVFREQ, RW_GLOBALS) = range(17)
 (RE_NORM1, RE_QKV_W, RE_QKV_B, RE_PROJ_W, RE_PROJ_B, RE_NORM2, RE_GU_W, RE_GU_B, RE_DOWN_W, RE_DOWN_B, RE_COUNT) = range(11)
@@ -95,6 +95,9 @@ def _bind_lay_ops(lib):
             f16 = getattr(lib, name + "_f16")
             f16.argtypes, f16.restype = args[1:], C.c_int
     lib.surya_op_gemm_geglu_f16.argtypes, lib.surya_op_gemm_geglu_f16.restype = [p, l, p, l, p, l, i, i, i, p], C.c_int
+    # the fp16 recogniser's GEMMs (csrc/rec_model_f16.hip)
+    lib.surya_op_rec_gemm_f16.argtypes, lib.surya_op_rec_gemm_f16.restype = [i, i, p, l, p, l, p, l, p, p, l, i, i, i, p, ip, p], C.c_int
+    lib.surya_op_gemm_splitk_f16.argtypes, lib.surya_op_gemm_splitk_f16.restype = [p, l, p, l, p, i, i, i, ip, p], C.c_int
 
 
 def check(rc: int, what: str):

@@ -864,6 +864,9 @@ struct DecodeAttnArgs {
 template <typename T>
 int launch_decode_attn(const DecodeAttnArgs<T>& a, hipStream_t s);
 template <> int launch_decode_attn<fp16_t>(const DecodeAttnArgs<fp16_t>& a, hipStream_t s);
+// ... whose d = 128 rungs (G <= 5, G <= 8: the recogniser's heads) are built in rec_model_f16.hip beside RecModel<fp16_t>. fp16 has no
+// decode_attn_flash_kernel: at Tuning::dattn = 3 it runs decode_attn_flash2_kernel like every other setting.
+int decode_attn_f16_d128(const DecodeAttnArgs<fp16_t>& a, hipStream_t s);
 
 // The launch itself, shared by the definitions of launch_decode_attn: LDS opt-in once per kernel, grid (rows, kv heads), 256 threads.
 template <auto KERN, typename T, typename... X>

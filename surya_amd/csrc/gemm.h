@@ -1713,7 +1713,7 @@ static inline int launch_gemm_splitk(GemmArgs<TI, TI>& a, hipStream_t s) {
         if (pick == 2) return launch_gemm_cfg<TI, TI, 128, 128, 2, 2, EPI_BIAS, true, 4>(a, s);
         if (pick == 3) return launch_gemm_cfg<TI, TI, 128, 64, 4, 1, EPI_BIAS, true, 4>(a, s);
     }
-    if constexpr (std::is_same<TI, bf16_t>::value) {          // (the ring kernel is written for bf16; off by default for split-K: dring_min_kt)
+    if constexpr (sizeof(TI) == 2) {                          // (the ring kernel moves 16-bit elements; off by default for split-K: dring_min_kt)
         const int rc = launch_splitk_ring(a, s);              // loader / consumer ring (gemm_ring.h, Tuning::dring)
         if (rc >= 0) return rc;
     }

@@ -1,4 +1,4 @@
-// Loader / consumer LDS ring for the decode-regime bf16 GEMMs (128 < M <= 256): gate|up (EPI_SWIGLU) and the split-K projections.
+// Loader / consumer LDS ring for the decode-regime 16-bit (bf16 / fp16) GEMMs (128 < M <= 256): gate|up (EPI_SWIGLU) and the split-K projections.
 //
 // The tiles of gemm_nt_kernel make every wave both load and multiply, and all waves meet at a workgroup barrier per K-tile. At one
 // workgroup per CU that loop takes in ~28-35 GB/s per CU; here the roles are split:
@@ -12,21 +12,23 @@
 // gives up sets ring_error_word and stops waiting for the rest of the launch (wrong numbers, no hang); the host reads the word through
 // ring_error().
 //
-// Arithmetic is gemm_nt_kernel's: the same LDS image (128-byte K-rows, XOR swizzle on the source address), the same v_mfma_f32_32x32x16_bf16
+// Arithmetic is gemm_nt_kernel's: the same LDS image (128-byte K-rows, XOR swizzle on the source address), the same v_mfma_f32_32x32x16_bf16 (_f16)
 // with the weight fragment first, K walked K-tile by K-tile and kk = 0..3 inside one, split-K slices from the same kt_begin / kt_end
 // formula. Each output element therefore sees the same MFMA sequence as on any other tile shape: results are bit-identical.
 #pragma once
 
 namespace sa {
 
-static __device__ unsigned ring_error_word;     // != 0: some ring wave gave up waiting (one copy per translation unit)
+static __device__ unsigned ring_error_word;     // != 0: some ring wave gave up waiting (one copy per translation unit: surya_gemm_ring_status asks each)
 
 // (consumer waves, loader waves, slots): gate|up on 64 x 160 tiles -- 4 row blocks x 64 column blocks = 256 workgroups, one per CU, the four
 // row blocks of a weight slab on one XCD -- and the split-K projections on the 64 x 64 tile of launch_gemm_splitk (same units and slices).
-template <int EPI, int BM, int BN, int CWM, int CWN, int NL, int SLOTS, bool SPLIT, int WAUX>
-__global__ __launch_bounds__(64 * (CWM * CWN + NL)) void gemm_ring_kernel(GemmArgs<bf16_t, bf16_t> p) {
-    using TI = bf16_t;
-    using TO = bf16_t;
+// T: bf16_t or fp16_t -- both are 2-byte elements on the same MFMA lane map (Mfma<T> / H16<T>), so the ring, its flags and the staging are one code.
+template <typename T, int EPI, int BM, int BN, int CWM, int CWN, int NL, int SLOTS, bool SPLIT, int WAUX>
+__global__ __launch_bounds__(64 * (CWM * CWN + NL)) void gemm_ring_kernel(GemmArgs<T, T> p) {
+    using TI = T;
+    using TO = T;
+    static_assert(sizeof(T) == 2, "the ring moves 128-byte K-rows of 16-bit elements");
     constexpr int NC = CWM * CWN;                               // consumer waves: 0 .. NC-1; loader waves: NC .. NC+NL-1
     constexpr int WTM = BM / CWM, WTN = BN / CWN, FM = WTM / 32, FN = WTN / 32;
     constexpr int XG = BM / 8, G = (BM + BN) / 8, GPW = G / NL;     // 8-row groups of a slot (X first), groups per loader wave
@@ -176,7 +178,7 @@ __global__ __launch_bounds__(64 * (CWM * CWN + NL)) void gemm_ring_kernel(GemmAr
     // ---- epilogue: the tile through LDS (row pitch padded by 16 bytes), then whole 16-byte chunks of contiguous rows
     constexpr bool GLU = (EPI == EPI_SWIGLU);
     constexpr int OW = GLU ? BN / 2 : BN;
-    constexpr int ES = SPLIT ? 4 : 2;                           // staged element bytes: fp32 slabs or bf16
+    constexpr int ES = SPLIT ? 4 : 2;                           // staged element bytes: fp32 slabs or T
     constexpr int ROWB = OW * ES, PITCH = ROWB + 16, CPR = ROWB / 16, EPC = 16 / ES;
     static_assert(ROWB % 16 == 0 && BM * PITCH <= SLOTS * SLOT, "output staging");
     if (wave < NC) {
@@ -214,15 +216,15 @@ __global__ __launch_bounds__(64 * (CWM * CWN + NL)) void gemm_ring_kernel(GemmAr
     }
 }
 
-template <int EPI, int BM, int BN, int CWM, int CWN, int NL, int SLOTS, bool SPLIT, int WAUX>
-static inline int launch_gemm_ring(const GemmArgs<bf16_t, bf16_t>& a, hipStream_t s) {
+template <typename T, int EPI, int BM, int BN, int CWM, int CWN, int NL, int SLOTS, bool SPLIT, int WAUX>
+static inline int launch_gemm_ring(const GemmArgs<T, T>& a, hipStream_t s) {
     const int S = SPLIT ? a.splitk : 1;
     const int grid = cdiv(cdiv(a.N, BN) * S, 8) * 8 * cdiv(a.M, BM);
     constexpr int NT = 64 * (CWM * CWN + NL);
     constexpr size_t lds = (size_t)SLOTS * (BM + BN) * 128 + (size_t)SLOTS * (NL + CWM * CWN) * 4;
     static_assert(lds <= 160 * 1024 && SLOTS * (NL + CWM * CWN) <= NT, "ring LDS / flag clear");
     a.bn_used = BN;
-    auto kern = gemm_ring_kernel<EPI, BM, BN, CWM, CWN, NL, SLOTS, SPLIT, WAUX>;
+    auto kern = gemm_ring_kernel<T, EPI, BM, BN, CWM, CWN, NL, SLOTS, SPLIT, WAUX>;
     static AttrOnce attr;
     attr.ensure(kern, lds);
     GemmProfiler& pf = gemm_profiler();
@@ -249,19 +251,21 @@ static inline int ring_mode(int M) {
     if (M <= 128 && !(d & 4)) return 0;
     return d & 3;
 }
-static inline int launch_gateup_ring(const GemmArgs<bf16_t, bf16_t>& a, hipStream_t s) {
+template <typename T>
+static inline int launch_gateup_ring(const GemmArgs<T, T>& a, hipStream_t s) {
     const int mode = ring_mode(a.M);
     if (!mode || a.bias || a.N % 8 != 0) return -1;
-    if (mode == 2) return launch_gemm_ring<EPI_SWIGLU, 64, 160, 1, 5, 4, 5, false, 2>(a, s);
-    return launch_gemm_ring<EPI_SWIGLU, 64, 160, 1, 5, 4, 5, false, 0>(a, s);
+    if (mode == 2) return launch_gemm_ring<T, EPI_SWIGLU, 64, 160, 1, 5, 4, 5, false, 2>(a, s);
+    return launch_gemm_ring<T, EPI_SWIGLU, 64, 160, 1, 5, 4, 5, false, 0>(a, s);
 }
 // split-K: the 64 x 64 units and slice count of launch_gemm_splitk, for slices of at least dring_min_kt K-tiles (default 0: never)
-static inline int launch_splitk_ring(const GemmArgs<bf16_t, bf16_t>& a, hipStream_t s) {
+template <typename T>
+static inline int launch_splitk_ring(const GemmArgs<T, T>& a, hipStream_t s) {
     const int mode = ring_mode(a.M);
     const int min_kt = tuning().dring_min_kt;
-    if (!mode || min_kt <= 0 || (a.K / Ty<bf16_t>::KE) / a.splitk < min_kt) return -1;
-    if (mode == 2) return launch_gemm_ring<EPI_BIAS, 64, 64, 2, 2, 4, 8, true, 2>(a, s);
-    return launch_gemm_ring<EPI_BIAS, 64, 64, 2, 2, 4, 8, true, 0>(a, s);
+    if (!mode || min_kt <= 0 || (a.K / Ty<T>::KE) / a.splitk < min_kt) return -1;
+    if (mode == 2) return launch_gemm_ring<T, EPI_BIAS, 64, 64, 2, 2, 4, 8, true, 2>(a, s);
+    return launch_gemm_ring<T, EPI_BIAS, 64, 64, 2, 2, 4, 8, true, 0>(a, s);
 }
 
 // Host check of the ring's give-up word (synchronous): 0 = every wait was satisfied since the last reset.

@@ -828,7 +828,7 @@ int op_gemm_geglu(int dtype, const void* X, long ldx, const void* W, long ldw, v
 }
 
 // launch_decode_attn (decode_attn.h) in fp16: the fourth-version kernel on v_mfma_f32_32x32x16_f16 at the head shapes of this family's decoders,
-// in this code object beside LayoutModel<fp16_t>, its only user (the recogniser runs bf16). Tuning::dattn_db as in bf16; no third version.
+// in this code object beside LayoutModel<fp16_t> (d = 128, the recogniser's, is built in rec_model_f16.hip). Tuning::dattn_db as in bf16; no third version.
 template <int D>
 static int decode_attn_flash_f16(const DecodeAttnArgs<fp16_t>& a, hipStream_t s) {
     const Tuning& t = tuning();
@@ -842,6 +842,7 @@ int launch_decode_attn<fp16_t>(const DecodeAttnArgs<fp16_t>& a, hipStream_t s) {
     if (a.out8 || G < 1 || G > 8 || a.nq % a.nkv) return SA_ERR_UNSUPPORTED;
     if (a.d == 64) return decode_attn_flash_f16<64>(a, s);
     if (a.d == 32) return decode_attn_flash_f16<32>(a, s);
+    if (a.d == 128) return decode_attn_f16_d128(a, s);       // the recogniser's head shape: built beside RecModel<fp16_t> (rec_model_f16.hip)
     return SA_ERR_UNSUPPORTED;
 }
 }  // namespace sa

@@ -9,21 +9,8 @@
 //     ContinuousBatchingCache.merge / pad_left / trim_left (recognition/cache.py:8-105) have no equivalent data
 //     movement -- admitting a prompt writes its K/V rows straight into a free slot;
 //   * the greedy head keeps next-token / length state on the device, so n decode steps need no host round trip.
-#include <algorithm>
-#include <cstdlib>
-#include <cstring>
-#include <map>
-#include <memory>
-#include <set>
-#include <vector>
-
-#include "../../include/surya_amd.h"
-#include "gemm.h"
-#include "gemm_mx.h"
-#include "kernels.h"
-#include "decode_attn.h"
-#include "decode_attn_kv8.h"
-#include "attn_mfma.h"
+// The engine itself, RecModel<T>, is rec_engine.h: this file instantiates it for float and bf16_t, rec_model_f16.hip for fp16_t.
+#include "rec_engine.h"
 #include "rec_prep.h"
 
 namespace sa {
@@ -60,964 +47,9 @@ int launch_decode_attn(const DecodeAttnArgs<T>& a, hipStream_t s) {
 template int launch_decode_attn<float>(const DecodeAttnArgs<float>&, hipStream_t);
 template int launch_decode_attn<bf16_t>(const DecodeAttnArgs<bf16_t>&, hipStream_t);
 
-// ------------------------------------------------------------------------------------------------- staging
-struct Stager {   // pinned host arena mirrored by a device arena; one H2D copy per plan
-    char* host = nullptr;
-    char* dev = nullptr;
-    size_t cap = 0, off = 0;
-    hipEvent_t ev = nullptr;
-    bool pending = false;
-    int init(size_t bytes) {
-        cap = bytes;
-        SA_HIP(hipHostMalloc((void**)&host, cap, hipHostMallocDefault));
-        SA_HIP(hipMalloc((void**)&dev, cap));
-        SA_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        return SA_OK;
-    }
-    void destroy() {
-        if (host) (void)hipHostFree(host);
-        if (dev) (void)hipFree(dev);
-        if (ev) (void)hipEventDestroy(ev);
-        host = dev = nullptr; ev = nullptr;
-    }
-    void begin() {
-        if (pending) { (void)hipEventSynchronize(ev); pending = false; }
-        off = 0;
-    }
-    template <typename U> U* put(const U* src, size_t n) {   // returns the DEVICE address
-        size_t bytes = n * sizeof(U);
-        size_t o = (off + 255) & ~(size_t)255;
-        if (o + bytes > cap) return nullptr;
-        if (bytes) memcpy(host + o, src, bytes);
-        off = o + bytes;
-        return reinterpret_cast<U*>(dev + o);
-    }
-    template <typename U> U* put(const std::vector<U>& v) { return put(v.data(), v.size()); }
-    int flush(hipStream_t s) {
-        if (off) {
-            SA_HIP(hipMemcpyAsync(dev, host, off, hipMemcpyHostToDevice, s));
-            SA_HIP(hipEventRecord(ev, s));
-            pending = true;
-        }
-        return SA_OK;
-    }
-};
-
-// ------------------------------------------------------------------------------------------- encoder plan
-struct EncPlan {
-    int P = 0;
-    std::vector<int> src_row, pos_hw, merged_src, hidx, widx;
-    std::vector<int> win_cu, img_cu;            // segment boundaries in patches
-};
-
-// Index math of get_window_index / rot_pos_emb / get_2d_learned_embeddings for images [0, n) of grid_hw.
-static int plan_encoder(const surya_rec_config& c, const int32_t* grid_hw, int n, EncPlan& pl) {
-    const int mg = c.merge, unit = mg * mg, vw = c.window_tokens;
-    pl = EncPlan();
-    pl.win_cu.push_back(0);
-    pl.img_cu.push_back(0);
-    int tok_base = 0;
-    for (int im = 0; im < n; ++im) {
-        const int h = grid_hw[2 * im], w = grid_hw[2 * im + 1];
-        if (h <= 0 || w <= 0 || h % mg || w % mg) return SA_ERR_SHAPE;
-        const int lh = h / mg, lw = w / mg;
-        const int pad_h = vw - lh % vw, pad_w = vw - lw % vw;      // == vw when divisible: one empty window row
-        const int nh = (lh + pad_h) / vw, nw = (lw + pad_w) / vw;
-        for (int wy = 0; wy < nh; ++wy)
-            for (int wx = 0; wx < nw; ++wx) {
-                int cnt = 0;
-                for (int dy = 0; dy < vw; ++dy)
-                    for (int dx = 0; dx < vw; ++dx) {
-                        const int y = wy * vw + dy, x = wx * vw + dx;
-                        if (y >= lh || x >= lw) continue;
-                        const int tok = y * lw + x;
-                        pl.merged_src.push_back(tok_base + tok);
-                        // get_2d_learned_embeddings: (arange(n) / max(1, n-1) * mult).long() in fp32
-                        pl.hidx.push_back((int)(((float)y / (float)std::max(1, lh - 1)) * (float)c.embed_multiplier));
-                        pl.widx.push_back((int)(((float)x / (float)std::max(1, lw - 1)) * (float)c.embed_multiplier));
-                        for (int u = 0; u < unit; ++u) {
-                            pl.src_row.push_back((tok_base + tok) * unit + u);
-                            pl.pos_hw.push_back(y * mg + u / mg);
-                            pl.pos_hw.push_back(x * mg + u % mg);
-                        }
-                        ++cnt;
-                    }
-                if (cnt) pl.win_cu.push_back(pl.win_cu.back() + cnt * unit);   // unique_consecutive drops empties
-            }
-        tok_base += lh * lw;
-        pl.img_cu.push_back(pl.img_cu.back() + h * w);
-    }
-    pl.P = pl.img_cu.back();
-    return SA_OK;
-}
-
-struct SegLists {   // host side of AttnSegs
-    std::vector<int> tile_seg, tile_q0, seg_len;
-    std::vector<long> q_off, k_off, v_off, o_off;
-    void add_tiles(int seg, int L) {
-        for (int q0 = 0; q0 < L; q0 += 64) { tile_seg.push_back(seg); tile_q0.push_back(q0); }
-    }
-};
-
-static AttnSegs stage_segs(Stager& st, const SegLists& s) {
-    AttnSegs a;
-    a.tile_seg = st.put(s.tile_seg); a.tile_q0 = st.put(s.tile_q0); a.seg_len = st.put(s.seg_len);
-    a.q_off = st.put(s.q_off); a.k_off = st.put(s.k_off); a.v_off = st.put(s.v_off); a.o_off = st.put(s.o_off);
-    return a;
-}
-
-__global__ void set_slot_state_kernel(const int* slots, const int* lens, int* kv_len, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) kv_len[slots[i]] = lens[i];
-}
-__global__ void set_next_tokens_kernel(const int* slots, const int* toks, int* next_token, int n) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) next_token[slots[i]] = toks[i];
-}
-
-// --------------------------------------------------------------------------------------------------- model
-struct RecBase {
-    virtual ~RecBase() {}
-    virtual int prefill(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
-    virtual int set_active(const int32_t*, int, hipStream_t) = 0;
-    virtual int encode_ahead(const float*, const int32_t*, int, hipStream_t) = 0;
-    virtual int decode(int, hipStream_t) = 0;
-    virtual int read_outputs(int, int32_t*, float*, int32_t*, hipStream_t) = 0;
-    virtual int decode_async(int, int, hipStream_t) = 0;
-    virtual int wait_outputs(int, int, int32_t*, float*, int32_t*) = 0;
-    virtual int encode_only(const float*, const int32_t*, int, void*, hipStream_t) = 0;
-    virtual int copy_last_logits(float*, int, int*, hipStream_t) = 0;
-    virtual int set_next_tokens(const int32_t*, const int32_t*, int, hipStream_t) = 0;
-    virtual int set_mx_weights(const void* const*, int) = 0;
-    virtual int set_kv_fp8(int) = 0;
-};
-
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
-
-template <typename T>
-struct RecModel : RecBase {
-    surya_rec_config c;
-    std::vector<const void*> w;
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
-    Stager st, st_small, st_enc;                         // st_enc: plans of the look-ahead encoder (its own stream)
-    hipStream_t estream = nullptr;                       // low-priority stream of the look-ahead encoder
-    hipEvent_t ev_ahead_in = nullptr, ev_ahead_done = nullptr, ev_ahead_free = nullptr;
-    T* emb_ahead = nullptr;                              // [max_prefill_tokens][dec_hidden] image embeddings encoded ahead
-    long ahead_tokens = 0, ahead_consumed = 0;
-    bool ahead_free_recorded = false;
-    // encoder workspaces
-    T *tiles_t, *ex, *eh, *eqkv, *emlp, *emh, *emerged;
-    // decoder workspaces
-    T *dx, *dh, *dqkv, *dattn, *dmlp, *dlast;
-    float* logits;
-    float2* erope;           // [max_patches][enc head_dim / 2] (cos, sin) of the vision rotary embedding
-    float4* amax;            // greedy-head partials of the lm_head GEMM: [slot row][column tile]
-    float2* rope_cs;                                     // decoder RoPE table [max_kv_len][head_dim/2] (cos, sin)
-    float* part;                                         // split-K partial sums [8][max_slots][max(qkv_dim, hidden)]
-    T *kcache, *vcache;
-    int *kv_len, *next_token, *active_dev, *row_len;
-    int* out_token; float* out_score; int* out_bbox;     // [SA_MAX_STEPS][max_slots] (bbox x6)
-    char* out_host = nullptr;                            // pinned mirror of the three output arrays
-    size_t out_bytes = 0;
-    int n_active = 0;
-    int last_rows = 0;
-    bool last_heads_mx = false;                          // the last heads() call ran the MXFP8 lm_head (test hook below)
-    // hipGraph replay of decode steps: a step is ~113 short launches; captured once per (active rows, steps) and replayed
-    // from an internal stream (capture is not allowed on the legacy default stream torch hands us).
-    hipStream_t gstream = nullptr;
-    hipEvent_t gev_in = nullptr, gev_out = nullptr;
-    hipEvent_t ev_ring[2] = {nullptr, nullptr};          // outputs of ring half r are in the pinned mirror
-    std::map<long, hipGraphExec_t> graphs;
-    std::set<long> seen_keys;
-    bool use_graph = true;
-    int graph_epoch = 0;                                 // tuning_epoch() the cached graphs were captured under
-    // Host-side upper bounds of kv_len (set at prefill, +1 per decode step of an active slot): they only pick the decode-attention
-    // variant -- two K/V tile buffers once some active context exceeds one 128-key tile -- and never enter a result.
-    std::vector<int> h_len, h_active;
-    int ctx_bound = 0;                                   // cached keys + the new one, max over the active slots, of the step being enqueued
-                                                         // (not consulted with hipGraph replay on: a captured step must not depend on host state)
-    // MXFP8 decode weights (surya_rec_set_mx_weights; gemm_mx.h): e4m3 copies + e8m0 block scales of the decoder projections
-    // and lm_head, used by the decode steps only (prefill keeps the bf16 weights), and MXFP8 twins of the four decode-step
-    // activation buffers, written by the kernels that produce the bf16 ones.
-    std::vector<const uint8_t*> mxw;
-    char* mx_arena = nullptr;
-    // FP8 KV cache of the decode steps (surya_rec_set_kv_fp8; decode_attn_kv8.h). Prefill keeps writing (and attending over) the
-    // bf16 cache and quantises the prompt rows into these arrays; the decode steps read and append only here.
-    char* kv8_arena = nullptr;
-    uint8_t *k8c = nullptr, *v8tc = nullptr;     // [layer][slot][kvh][Tmax][D], [layer][slot][kvh][D][Tmax8]
-    float *ksc8 = nullptr, *vsc8 = nullptr;      // [layer][slot][kvh][Tmax8]
-    bool kv8 = false;
-    int tmax8() const { return kv8_tmax(c.max_kv_len); }
-    uint8_t *dh8 = nullptr, *sdh = nullptr, *dattn8 = nullptr, *sattn = nullptr, *dmlp8 = nullptr, *smlp = nullptr, *dlast8 = nullptr,
-            *slast = nullptr;
-    bool mx() const { return !mxw.empty(); }
-    const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
-    const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
-
-    const T* W(int idx) const { return reinterpret_cast<const T*>(w[idx]); }
-    const T* WE(int l, int k) const { return W(SA_RW_ENC(l, k)); }
-    const T* WD(int l, int k) const { return W(SA_RW_DEC(c.enc_depth, l, k)); }
-
-    static size_t layout(const surya_rec_config& c, RecModel* m) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-        const size_t Pm = c.max_patches, Tm = std::max(c.max_prefill_tokens, c.max_slots), S = c.max_slots;
-        const int unit = c.merge * c.merge;
-        const size_t qkv_d = (size_t)(c.dec_heads + 2 * c.dec_kv_heads) * c.dec_head_dim;
-        size_t o_tiles = take(Pm * c.patch_dim_pad * sizeof(T));
-        size_t o_ex = take(Pm * c.enc_hidden * sizeof(T));
-        size_t o_eh = take(Pm * c.enc_hidden * sizeof(T));
-        size_t o_eqkv = take(Pm * 3 * c.enc_hidden * sizeof(T));
-        size_t o_emlp = take(Pm * c.enc_inter_pad * sizeof(T));
-        size_t o_emh = take(Pm * c.enc_hidden * sizeof(T));                 // [P/unit, unit*He]
-        size_t o_erope = take(Pm * (size_t)(c.enc_hidden / c.enc_heads / 2) * sizeof(float2));
-        size_t o_emerged = take(Pm / unit * c.enc_out_hidden * sizeof(T));
-        size_t o_dx = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_dh = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_dqkv = take(Tm * qkv_d * sizeof(T));
-        size_t o_dattn = take(Tm * c.dec_heads * c.dec_head_dim * sizeof(T));
-        size_t o_dmlp = take(Tm * c.dec_inter * sizeof(T));
-        size_t o_dlast = take(S * c.dec_hidden * sizeof(T));
-        size_t o_ahead = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_logits = take(S * (size_t)c.vocab * sizeof(float));
-        size_t o_amax = take(S * (size_t)cdiv(c.vocab, 32) * sizeof(float4));
-        size_t o_rope = take((size_t)c.max_kv_len * (c.dec_head_dim / 2) * sizeof(float2));
-        size_t o_part = take((size_t)8 * S * std::max(qkv_d, (size_t)c.dec_hidden) * sizeof(float));
-        const size_t kv_elems = (size_t)c.dec_layers * S * c.dec_kv_heads * c.max_kv_len * c.dec_head_dim;
-        size_t o_k = take(kv_elems * sizeof(T));
-        size_t o_v = take(kv_elems * sizeof(T));
-        size_t o_kvlen = take(S * sizeof(int));
-        size_t o_next = take(S * sizeof(int));
-        size_t o_active = take(S * sizeof(int));
-        size_t o_rowlen = take(S * sizeof(int));
-        size_t o_out = take((size_t)SA_MAX_STEPS * S * 8 * sizeof(int));
-        if (m) {
-            char* b = m->arena;
-            m->tiles_t = (T*)(b + o_tiles); m->ex = (T*)(b + o_ex); m->eh = (T*)(b + o_eh); m->eqkv = (T*)(b + o_eqkv);
-            m->emlp = (T*)(b + o_emlp); m->emh = (T*)(b + o_emh); m->emerged = (T*)(b + o_emerged); m->erope = (float2*)(b + o_erope);
-            m->dx = (T*)(b + o_dx); m->dh = (T*)(b + o_dh); m->dqkv = (T*)(b + o_dqkv); m->dattn = (T*)(b + o_dattn);
-            m->dmlp = (T*)(b + o_dmlp); m->dlast = (T*)(b + o_dlast); m->emb_ahead = (T*)(b + o_ahead); m->logits = (float*)(b + o_logits); m->amax = (float4*)(b + o_amax);
-            m->part = (float*)(b + o_part); m->rope_cs = (float2*)(b + o_rope);
-            m->kcache = (T*)(b + o_k); m->vcache = (T*)(b + o_v);
-            m->kv_len = (int*)(b + o_kvlen); m->next_token = (int*)(b + o_next); m->active_dev = (int*)(b + o_active); m->row_len = (int*)(b + o_rowlen);
-            m->out_token = (int*)(b + o_out);
-            m->out_score = (float*)(m->out_token + (size_t)SA_MAX_STEPS * S);
-            m->out_bbox = (int*)(m->out_score + (size_t)SA_MAX_STEPS * S);
-            m->out_bytes = (size_t)SA_MAX_STEPS * S * 8 * sizeof(int);
-        }
-        return off;
-    }
-
-    int init(const surya_rec_config& cfg, const void* const* weights, int n) {
-        c = cfg;
-        w.assign(weights, weights + n);
-        arena_bytes = layout(c, nullptr);
-        SA_HIP(hipMalloc((void**)&arena, arena_bytes));
-        poison_arena(arena, arena_bytes);
-        layout(c, this);
-        {
-            const int half = c.dec_head_dim / 2, n = c.max_kv_len * half;
-            hipLaunchKernelGGL(rope_table_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const float*>(w[SA_RW_DEC_INVFREQ]), rope_cs, c.max_kv_len, half);
-            SA_HIP(hipGetLastError());
-        }
-        SA_HIP(hipMemset(kv_len, 0, c.max_slots * sizeof(int)));
-        SA_HIP(hipMemset(next_token, 0, c.max_slots * sizeof(int)));
-        SA_HIP(hipMemset(out_token, 0, out_bytes));
-        SA_HIP(hipHostMalloc((void**)&out_host, out_bytes, hipHostMallocDefault));
-        const size_t Pm = c.max_patches, Tm = std::max(c.max_prefill_tokens, c.max_slots);
-        int rc = st.init((Pm * 8 + Tm * 8 + (size_t)c.max_slots * 64) * sizeof(int) + (1 << 20));
-        if (rc) return rc;
-        rc = st_small.init((size_t)c.max_slots * 4 * sizeof(int) + 4096);
-        if (rc) return rc;
-        rc = st_enc.init((Pm * 8 + (size_t)c.max_slots * 64) * sizeof(int) + (1 << 20));
-        if (rc) return rc;
-        {   // the look-ahead encoder runs beside the decode steps: lowest priority, so decode kernels get CUs first
-            int least = 0, greatest = 0;
-            SA_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            // (confining the encoder to a CU mask instead -- 128 / 192 / 224 CUs, prefix or strided -- was measured and is
-            // slower than priority alone: 2599-2719 vs 2799 lines/s on 1024 lines, r01)
-            SA_HIP(hipStreamCreateWithPriority(&estream, hipStreamNonBlocking, least));
-            SA_HIP(hipEventCreateWithFlags(&ev_ahead_in, hipEventDisableTiming));
-            SA_HIP(hipEventCreateWithFlags(&ev_ahead_done, hipEventDisableTiming));
-            SA_HIP(hipEventCreateWithFlags(&ev_ahead_free, hipEventDisableTiming));
-        }
-        SA_HIP(hipStreamCreateWithFlags(&gstream, hipStreamNonBlocking));
-        SA_HIP(hipEventCreateWithFlags(&gev_in, hipEventDisableTiming));
-        SA_HIP(hipEventCreateWithFlags(&gev_out, hipEventDisableTiming));
-        for (auto& e : ev_ring) SA_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        // hipGraph replay of the decode steps is opt-in (surya_set_tuning("graph", 1)): with the pipelined decode_async loop the host
-        // enqueues call n + 1 while call n runs, so plain launches never starve the GPU, and a graph launch of ~450 kernel
-        // nodes starts later than the first eager launch does (r01: 101.1 ms/step with graphs, 96.2 ms without).
-        use_graph = true;                                  // cleared for good if a capture fails
-        SA_HIP(hipDeviceSynchronize());
-        return SA_OK;
-    }
-    ~RecModel() override {
-        if (mx_arena) (void)hipFree(mx_arena);
-        if (kv8_arena) (void)hipFree(kv8_arena);
-        for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
-        if (gstream) (void)hipStreamDestroy(gstream);
-        if (gev_in) (void)hipEventDestroy(gev_in);
-        if (gev_out) (void)hipEventDestroy(gev_out);
-        for (auto e : ev_ring) if (e) (void)hipEventDestroy(e);
-        st.destroy(); st_small.destroy(); st_enc.destroy();
-        if (estream) (void)hipStreamDestroy(estream);
-        for (hipEvent_t e : {ev_ahead_in, ev_ahead_done, ev_ahead_free}) if (e) (void)hipEventDestroy(e);
-        if (arena) (void)hipFree(arena);
-        if (out_host) (void)hipHostFree(out_host);
-    }
-
-    // ------------------------------------------------------------------------------------------ helpers
-    template <int EPI>
-    int gemm(const T* X, long ldx, const T* Wt, long ldw, T* C, long ldc, const T* bias, const T* R, long ldr, int M, int N,
-             int K, hipStream_t s) {
-        GemmArgs<T, T> a{X, ldx, Wt, ldw, C, ldc, bias, R, ldr, M, N, K};
-        return launch_gemm<T, T, EPI>(a, s);
-    }
-    int rmsnorm(const T* x, long ldx, const T* wt, T* y, long ldy, const int* src_row, int rows, int C, float eps, hipStream_t s) {
-        return launch_rmsnorm<T>(x, ldx, wt, y, ldy, src_row, rows, C, eps, s);
-    }
-
-    // Vision encoder for images [0, n) whose tiles start at `tiles`; merged tokens (original order index g)
-    // are written to dst + dst_rows[g] * dec_hidden. Chunks on image boundaries when P exceeds max_patches.
-    int encode(const float* tiles, const int32_t* grid_hw, int n, const std::vector<int>& dst_rows, T* dst, hipStream_t s) {
-        return encode(tiles, grid_hw, n, dst_rows, dst, s, st);
-    }
-    int encode(const float* tiles, const int32_t* grid_hw, int n, const std::vector<int>& dst_rows, T* dst, hipStream_t s,
-               Stager& st) {
-        const int unit = c.merge * c.merge, He = c.enc_hidden, D = He / c.enc_heads;
-        int i0 = 0;
-        long patch_base = 0, tok_base = 0;
-        while (i0 < n) {
-            int i1 = i0;
-            long P = 0;
-            while (i1 < n) {
-                const long p = (long)grid_hw[2 * i1] * grid_hw[2 * i1 + 1];
-                if (p > c.max_patches) return SA_ERR_SHAPE;
-                if (P + p > c.max_patches) break;
-                P += p; ++i1;
-            }
-            EncPlan pl;
-            int rc = plan_encoder(c, grid_hw + 2 * i0, i1 - i0, pl);
-            if (rc) return rc;
-            SegLists win, full;
-            for (size_t sgi = 0; sgi + 1 < pl.win_cu.size(); ++sgi) {
-                const int a = pl.win_cu[sgi], L = pl.win_cu[sgi + 1] - a;
-                win.seg_len.push_back(L);
-                win.q_off.push_back((long)a * 3 * He); win.k_off.push_back((long)a * 3 * He + He);
-                win.v_off.push_back((long)a * 3 * He + 2 * He); win.o_off.push_back((long)a * He);
-                win.add_tiles((int)sgi, L);
-            }
-            for (size_t sgi = 0; sgi + 1 < pl.img_cu.size(); ++sgi) {
-                const int a = pl.img_cu[sgi], L = pl.img_cu[sgi + 1] - a;
-                full.seg_len.push_back(L);
-                full.q_off.push_back((long)a * 3 * He); full.k_off.push_back((long)a * 3 * He + He);
-                full.v_off.push_back((long)a * 3 * He + 2 * He); full.o_off.push_back((long)a * He);
-                full.add_tiles((int)sgi, L);
-            }
-            std::vector<int> dst_row(pl.merged_src.size());
-            for (size_t g = 0; g < dst_row.size(); ++g) dst_row[g] = dst_rows[tok_base + pl.merged_src[g]];
-            st.begin();
-            const int* d_src_row = st.put(pl.src_row);
-            const int* d_pos = st.put(pl.pos_hw);
-            const int* d_dst = st.put(dst_row);
-            const int* d_hidx = st.put(pl.hidx);
-            const int* d_widx = st.put(pl.widx);
-            AttnSegs d_win = stage_segs(st, win), d_full = stage_segs(st, full);
-            if (!d_full.o_off) return SA_ERR_NOMEM;
-            rc = st.flush(s);
-            if (rc) return rc;
-
-            const int Pi = (int)P;
-            hipLaunchKernelGGL(convert_tiles_kernel<T>, dim3(Pi), dim3(64), 0, s, tiles + patch_base * c.patch_dim, tiles_t,
-                               d_src_row, Pi, c.patch_dim, c.patch_dim_pad);
-            if ((rc = gemm<EPI_BIAS>(tiles_t, c.patch_dim_pad, W(SA_RW_PATCH), c.patch_dim_pad, ex, He, nullptr, nullptr, 0, Pi,
-                                     He, c.patch_dim_pad, s))) return rc;
-            const float scale = 1.0f / sqrtf((float)D);
-            hipLaunchKernelGGL(rope_vision_table_kernel, dim3((unsigned)cdivl((long)Pi * (D / 2), 256)), dim3(256), 0, s, d_pos,
-                               reinterpret_cast<const float*>(w[SA_RW_ENC_INVFREQ]), erope, Pi, D);
-            for (int l = 0; l < c.enc_depth; ++l) {
-                if ((rc = rmsnorm(ex, He, WE(l, SA_RE_NORM1), eh, He, nullptr, Pi, He, c.enc_eps, s))) return rc;
-                {   // qkv projection with the 2-D rotary embedding of q and k in its epilogue (pair-interleaved weight rows)
-                    GemmArgs<T, T> a{eh, He, WE(l, SA_RE_QKV_W), He, eqkv, 3 * He, WE(l, SA_RE_QKV_B), nullptr, 0, Pi, 3 * He, He};
-                    a.rope = erope; a.rope_cols = 2 * He; a.rope_D = D;
-                    if ((rc = launch_gemm<T, T, EPI_ROPE>(a, s))) return rc;
-                }
-                const bool fullatt = (c.fullatt_mask >> l) & 1u;
-                const AttnSegs& sg = fullatt ? d_full : d_win;
-                const int nt = (int)(fullatt ? full.tile_seg.size() : win.tile_seg.size());
-                if ((rc = launch_attn<T>(D, eqkv, eqkv, eqkv, eh, sg, nt, c.enc_heads, 3 * He, D, 3 * He, D, He, D, 1, 0, scale, s)))
-                    return rc;
-                if ((rc = gemm<EPI_RESIDUAL>(eh, He, WE(l, SA_RE_PROJ_W), He, ex, He, WE(l, SA_RE_PROJ_B), ex, He, Pi, He, He, s)))
-                    return rc;
-                if ((rc = rmsnorm(ex, He, WE(l, SA_RE_NORM2), eh, He, nullptr, Pi, He, c.enc_eps, s))) return rc;
-                if ((rc = gemm<EPI_SWIGLU>(eh, He, WE(l, SA_RE_GU_W), He, emlp, c.enc_inter_pad, WE(l, SA_RE_GU_B), nullptr, 0,
-                                           Pi, 2 * c.enc_inter_pad, He, s))) return rc;
-                if ((rc = gemm<EPI_RESIDUAL>(emlp, c.enc_inter_pad, WE(l, SA_RE_DOWN_W), c.enc_inter_pad, ex, He,
-                                             WE(l, SA_RE_DOWN_B), ex, He, Pi, He, c.enc_inter_pad, s))) return rc;
-            }
-            // merger: ln_q eps is fixed 1e-6 in the reference (encoder/__init__.py:114)
-            if ((rc = rmsnorm(ex, He, W(SA_RW_MERGER_LN), eh, He, nullptr, Pi, He, 1e-6f, s))) return rc;
-            const int Mg = Pi / unit, Hm = He * unit;
-            if ((rc = gemm<EPI_GELU>(eh, Hm, W(SA_RW_FC1_W), Hm, emh, Hm, W(SA_RW_FC1_B), nullptr, 0, Mg, Hm, Hm, s))) return rc;
-            if ((rc = gemm<EPI_BIAS>(emh, Hm, W(SA_RW_FC2_W), Hm, emerged, c.enc_out_hidden, W(SA_RW_FC2_B), nullptr, 0, Mg,
-                                     c.enc_out_hidden, Hm, s))) return rc;
-            hipLaunchKernelGGL(scatter_image_kernel<T>, dim3(Mg), dim3(128), 0, s, emerged, W(SA_RW_IMG_H), W(SA_RW_IMG_W), d_dst,
-                               d_hidx, d_widx, dst, c.dec_hidden);
-            if ((rc = (int)hipGetLastError())) return rc;
-            patch_base += P;
-            tok_base += P / unit;
-            i0 = i1;
-        }
-        return SA_OK;
-    }
-
-    int encode_only(const float* tiles, const int32_t* grid_hw, int n, void* out, hipStream_t s) override {
-        if (c.enc_out_hidden != c.dec_hidden) return SA_ERR_SHAPE;
-        long ntok = 0;
-        for (int i = 0; i < n; ++i) ntok += (long)grid_hw[2 * i] * grid_hw[2 * i + 1] / (c.merge * c.merge);
-        std::vector<int> ident(ntok);
-        for (long i = 0; i < ntok; ++i) ident[i] = (int)i;
-        return encode(tiles, grid_hw, n, ident, reinterpret_cast<T*>(out), s);
-    }
-
-    // Look-ahead encoding: the vision encoder needs no KV slots, so the images of the NEXT lines in the queue are encoded on
-    // a second (low-priority) stream while the current lines decode -- the decode phase is a chain of short latency-bound
-    // kernels that leaves most of the chip idle (two bench processes on one GPU: 3149 vs 2727 lines/s, r01). The embeddings
-    // land in emb_ahead in image order; prefill(tiles = NULL, ...) consumes them front to back.
-    int encode_ahead(const float* tiles, const int32_t* grid_hw, int n, hipStream_t s) override {
-        if (c.enc_out_hidden != c.dec_hidden) return SA_ERR_SHAPE;
-        if (n == 0) {                                                    // discard: a caller whose loop ended early (an exception between
-            ahead_consumed = ahead_tokens = 0;                           // encode_ahead and the prefill that would have consumed it) starts clean;
-            return SA_OK;                                                // emb_ahead is re-used only behind ev_ahead_free / stream order as always
-        }
-        if (n < 0 || !tiles || !grid_hw) return SA_ERR_ARG;
-        if (ahead_consumed != ahead_tokens) return SA_ERR_STATE;         // previous look-ahead not fully consumed
-        long ntok = 0;
-        for (int i = 0; i < n; ++i) ntok += (long)grid_hw[2 * i] * grid_hw[2 * i + 1] / (c.merge * c.merge);
-        if (ntok > std::max(c.max_prefill_tokens, c.max_slots)) return SA_ERR_SHAPE;
-        std::vector<int> ident(ntok);
-        for (long i = 0; i < ntok; ++i) ident[i] = (int)i;
-        SA_HIP(hipEventRecord(ev_ahead_in, s));                          // tiles were produced on the caller's stream
-        SA_HIP(hipStreamWaitEvent(estream, ev_ahead_in, 0));
-        if (ahead_free_recorded) SA_HIP(hipStreamWaitEvent(estream, ev_ahead_free, 0));   // last consumer of emb_ahead is done
-        int rc = encode(tiles, grid_hw, n, ident, emb_ahead, estream, st_enc);
-        if (rc) return rc;
-        SA_HIP(hipEventRecord(ev_ahead_done, estream));
-        ahead_tokens = ntok;
-        ahead_consumed = 0;
-        return SA_OK;
-    }
-
-    // ------------------------------------------------------------------------------------------ decoder
-    // Prefill: packed prompt tokens, causal attention over the freshly written cache rows.
-    int decoder_layers_prefill(int M, const int* d_tok_slot, const int* d_tok_pos, const AttnSegs* sg, int n_tiles, hipStream_t s) {
-        const int Hd = c.dec_hidden, nq = c.dec_heads, nkv = c.dec_kv_heads, d = c.dec_head_dim, I = c.dec_inter;
-        const int qkv_d = (nq + 2 * nkv) * d;
-        const float scale = 1.0f / sqrtf((float)d);
-        const size_t layer_kv = (size_t)c.max_slots * nkv * c.max_kv_len * d;
-        const float* inv_freq = reinterpret_cast<const float*>(w[SA_RW_DEC_INVFREQ]);
-        int rc;
-        for (int l = 0; l < c.dec_layers; ++l) {
-            T* kc = kcache + l * layer_kv;
-            T* vc = vcache + l * layer_kv;
-            if ((rc = rmsnorm(dx, Hd, WD(l, SA_RD_LN1), dh, Hd, nullptr, M, Hd, c.dec_eps, s))) return rc;
-            if ((rc = gemm<EPI_BIAS>(dh, Hd, WD(l, SA_RD_QKV_W), Hd, dqkv, qkv_d, WD(l, SA_RD_QKV_B), nullptr, 0, M, qkv_d, Hd, s)))
-                return rc;
-            hipLaunchKernelGGL(rope_kv_append_kernel<T>, dim3(M), dim3(256), 0, s, dqkv, d_tok_slot, d_tok_pos, rope_cs, kc, vc,
-                               nq, nkv, d, c.max_kv_len);
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                if (kv8) {
-                    const size_t l8 = (size_t)c.max_slots * nkv, T8 = tmax8();
-                    if ((rc = launch_kv8_quant_rows(d, kc, vc, d_tok_slot, d_tok_pos, M, k8c + l * l8 * c.max_kv_len * d, v8tc + l * l8 * d * T8,
-                                                    ksc8 + l * l8 * T8, vsc8 + l * l8 * T8, nkv, c.max_kv_len, s))) return rc;
-                }
-            }
-            if ((rc = launch_attn<T>(d, dqkv, kc, vc, dattn, *sg, n_tiles, nq, qkv_d, d, d, (long)c.max_kv_len * d, (long)nq * d, d,
-                                     nq / nkv, 1, scale, s))) return rc;
-            if ((rc = gemm<EPI_RESIDUAL>(dattn, (long)nq * d, WD(l, SA_RD_O_W), (long)nq * d, dx, Hd, nullptr, dx, Hd, M, Hd, nq * d,
-                                         s))) return rc;
-            if ((rc = rmsnorm(dx, Hd, WD(l, SA_RD_LN2), dh, Hd, nullptr, M, Hd, c.dec_eps, s))) return rc;
-            if ((rc = gemm<EPI_SWIGLU>(dh, Hd, WD(l, SA_RD_GU_W), Hd, dmlp, I, nullptr, nullptr, 0, M, 2 * I, Hd, s))) return rc;
-            if ((rc = gemm<EPI_RESIDUAL>(dmlp, I, WD(l, SA_RD_DOWN_W), I, dx, Hd, nullptr, dx, Hd, M, Hd, I, s))) return rc;
-        }
-        return SA_OK;
-    }
-
-    // The rows of a decode step and their workspaces: every per-row buffer is row-major, so a row range is a pointer offset.
-    // (r02 ran two halves of the batch on two streams: no gain -- a 128-row launch takes as long as a 256-row one -- removed.)
-    struct Half { int r0, M; float* part; hipStream_t s; };
-
-    int splitk_gemm(const T* X, long ldx, const T* Wt, long ldw, int M, int N, int K, float* part_, int* S, hipStream_t s) {
-        GemmArgs<T, T> a{X, ldx, Wt, ldw, nullptr, 0, nullptr, nullptr, 0, M, N, K, 1, part_};
-        int rc = launch_gemm_splitk<T>(a, s);
-        *S = a.splitk;
-        return rc;
-    }
-    // pf_cache: the K or V cache of the layer whose decode attention comes next -- M extra workgroups request this step's rows of it
-    // while the reduce runs (KvPrefetch, kernels.h). bf16 cache only; nullptr = plain reduce.
-    int reduce_residual_norm(int S, int M, const float* part_, T* x, const T* wnorm, T* y, hipStream_t s, uint8_t* y8 = nullptr,
-                             uint8_t* sy = nullptr, const T* pf_cache = nullptr, const Half* h = nullptr) {
-        const int threads = cdiv(c.dec_hidden / 4, 64) * 64;         // one 4-element chunk per thread
-        if (threads > 1024 || c.dec_hidden % 4) return SA_ERR_UNSUPPORTED;
-        KvPrefetch pf;
-        if (pf_cache && h && tuning().kvprefetch && (c.dec_head_dim * sizeof(T)) % 16 == 0) {
-            pf.base = reinterpret_cast<const unsigned char*>(pf_cache);
-            pf.slots = active_dev + h->r0; pf.lens = row_len + h->r0;
-            pf.head_stride = (long)c.max_kv_len * c.dec_head_dim * sizeof(T);
-            pf.slot_stride = pf.head_stride * c.dec_kv_heads;
-            pf.heads = c.dec_kv_heads; pf.row_bytes = c.dec_head_dim * (int)sizeof(T); pf.max_rows = c.max_kv_len;
-        }
-        const int grid = pf.base ? 2 * M : M;
-#define SA_RNORM(SL) hipLaunchKernelGGL((splitk_residual_norm_kernel<T, SL>), dim3(grid), dim3(threads), 0, s, part_, S, M, x, (const T*)nullptr, \
-                                        wnorm, y, c.dec_hidden, c.dec_eps, y8, sy, c.max_slots, pf)
-        // only as many slab loads per thread as the slice count needs (the sums are the same: the extra slabs were masked duplicates)
-        if (tuning().rnorm == 1 || S > 4) SA_RNORM(8);
-        else if (S > 2) SA_RNORM(4);
-        else SA_RNORM(2);
-#undef SA_RNORM
-        return (int)hipGetLastError();
-    }
-    // Activation scale tensors are K-tile-major with max_slots rows per K-tile ([K / 128][max_slots][4]); a row range of the
-    // batch is a pointer offset of 4 bytes per row.
-    int splitk_gemm_mx(const uint8_t* X, const uint8_t* SX, long ldx, const uint8_t* Wq, const uint8_t* SW, int M, int N, int K,
-                       float* part_, int* S, hipStream_t s) {
-        MxArgs a{X, ldx, SX, Wq, (long)K, SW, M, N, K, (long)c.max_slots, (long)N};
-        a.part = part_;
-        int rc = launch_gemm_mx_splitk(a, s);
-        *S = a.splitk;
-        return rc;
-    }
-
-    // FP8 KV cache for the decode steps (bf16 model only). Takes effect for lines prefilled AFTER the call: switch while no line
-    // is in flight.
-    // Captured decode steps hold launch arguments AND kernel choices: any mode change (fp8 KV cache, MXFP8 weights, a tuning knob)
-    // must drop them, or a replay would run the other attention kernel on a cache the new shapes no longer append to.
-    void drop_graphs() {
-        for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
-        graphs.clear(); seen_keys.clear();
-    }
-    int set_kv_fp8(int on) override {
-        if constexpr (!std::is_same<T, bf16_t>::value) return on ? SA_ERR_UNSUPPORTED : SA_OK;
-        if ((on != 0) != kv8) drop_graphs();
-        if (!on) { kv8 = false; return SA_OK; }
-        const int d = c.dec_head_dim;
-        if (d != 128 && d != 64 && d != 32) return SA_ERR_UNSUPPORTED;
-        if (c.dec_heads / c.dec_kv_heads > 8) return SA_ERR_UNSUPPORTED;
-        if (!kv8_arena) {
-            const size_t rows = (size_t)c.dec_layers * c.max_slots * c.dec_kv_heads, T8 = tmax8();
-            size_t off = 0;
-            auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-            const size_t o_k = take(rows * c.max_kv_len * d), o_v = take(rows * d * T8), o_ks = take(rows * T8 * 4), o_vs = take(rows * T8 * 4);
-            SA_HIP(hipMalloc((void**)&kv8_arena, off));
-            SA_HIP(hipMemset(kv8_arena, 0, off));           // finite bytes and scales everywhere: masked key columns multiply P = 0
-            SA_HIP(hipDeviceSynchronize());
-            k8c = (uint8_t*)(kv8_arena + o_k); v8tc = (uint8_t*)(kv8_arena + o_v);
-            ksc8 = (float*)(kv8_arena + o_ks); vsc8 = (float*)(kv8_arena + o_vs);
-        }
-        kv8 = true;
-        return SA_OK;
-    }
-
-    // MXFP8 weight table of the decode steps: per layer SA_MX_COUNT pointers, then SA_MX_LM_W, SA_MX_LM_S. bf16 model only.
-    int set_mx_weights(const void* const* tbl, int n) override {
-        if constexpr (!std::is_same<T, bf16_t>::value) return SA_ERR_UNSUPPORTED;
-        if (!tbl) { if (!mxw.empty()) drop_graphs(); mxw.clear(); return SA_OK; }     // back to the bf16 decode weights
-        if (n != SA_MX_TOTAL(c.dec_layers)) return SA_ERR_ARG;
-        for (int i = 0; i < n; ++i)
-            if (!tbl[i]) return SA_ERR_ARG;
-        const int Hd = c.dec_hidden, A = c.dec_heads * c.dec_head_dim, I = c.dec_inter;
-        if (Hd % 128 || A % 128 || I % 128 || c.dec_head_dim % 32) return SA_ERR_SHAPE;     // whole 128-element K-tiles, 32-wide blocks
-        if (!mx_arena) {
-            const size_t S = c.max_slots;
-            size_t off = 0;
-            auto take = [&](size_t b) { size_t o = off; off = align_up(off + b); return o; };
-            const size_t o1 = take(S * Hd), o2 = take(S * Hd / 32), o3 = take(S * A), o4 = take(S * A / 32), o5 = take(S * I),
-                         o6 = take(S * I / 32), o7 = take(S * Hd), o8 = take(S * Hd / 32);
-            SA_HIP(hipMalloc((void**)&mx_arena, off));
-            SA_HIP(hipMemset(mx_arena, 0, off));
-            uint8_t* b = reinterpret_cast<uint8_t*>(mx_arena);
-            dh8 = b + o1; sdh = b + o2; dattn8 = b + o3; sattn = b + o4; dmlp8 = b + o5; smlp = b + o6; dlast8 = b + o7; slast = b + o8;
-        }
-        mxw.resize(n);
-        for (int i = 0; i < n; ++i) mxw[i] = reinterpret_cast<const uint8_t*>(tbl[i]);
-        drop_graphs();                                                  // captured steps hold the old launch arguments
-        return SA_OK;
-    }
-
-
-    // The round-4 head / embedding kernels (kernels.h) hold a row's operands in registers: partial tiles, hidden size and the fused
-    // embedding are bounded by their thread geometry; anything larger keeps the round-3 kernels.
-    bool head2_ok() const {
-        return tuning().ghead == 2 && c.dec_hidden <= 2048 && c.dec_hidden % 8 == 0 && (!mx() || c.dec_hidden % 32 == 0);
-    }
-    int decode_embed(const Half& h) {
-        const int Hd = c.dec_hidden;
-        if (head2_ok()) {
-            hipLaunchKernelGGL(embed_slots_norm2_kernel<T>, dim3(h.M), dim3(SA_HEAD_THREADS), 0, h.s, W(SA_RW_TOK_EMBED), next_token,
-                               active_dev + h.r0, kv_len, c.max_kv_len, row_len + h.r0, dx + (size_t)h.r0 * Hd, WD(0, SA_RD_LN1),
-                               dh + (size_t)h.r0 * Hd, Hd, c.dec_eps, mx() ? dh8 + (size_t)h.r0 * Hd : nullptr,
-                               mx() ? sdh + (size_t)h.r0 * 4 : nullptr, c.max_slots);
-            return (int)hipGetLastError();
-        }
-        hipLaunchKernelGGL(embed_slots_norm_kernel<T>, dim3(h.M), dim3(64), 0, h.s, W(SA_RW_TOK_EMBED), next_token, active_dev + h.r0,
-                           kv_len, c.max_kv_len, row_len + h.r0, dx + (size_t)h.r0 * Hd, WD(0, SA_RD_LN1), dh + (size_t)h.r0 * Hd, Hd,
-                           c.dec_eps, mx() ? dh8 + (size_t)h.r0 * Hd : nullptr, mx() ? sdh + (size_t)h.r0 * 4 : nullptr, c.max_slots);
-        return (int)hipGetLastError();
-    }
-
-    // One decoder layer of one decode step for the rows of `h`. The three skinny projections (qkv, o, down) run split-K so
-    // they cover the chip; their partial sums are combined by the kernel that needs the result anyway: decode attention
-    // (qkv) and a fused residual-add + next-RMSNorm pass (o, down). The last layer leaves the final-norm rows in `dlast`.
-    int decode_layer(int l, const Half& h) {
-        const int Hd = c.dec_hidden, nq = c.dec_heads, nkv = c.dec_kv_heads, d = c.dec_head_dim, I = c.dec_inter;
-        const int qkv_d = (nq + 2 * nkv) * d, M = h.M;
-        const float scale = 1.0f / sqrtf((float)d);
-        const size_t layer_kv = (size_t)c.max_slots * nkv * c.max_kv_len * d;
-        hipStream_t s = h.s;
-        T* kc = kcache + l * layer_kv;
-        T* vc = vcache + l * layer_kv;
-        T* x = dx + (size_t)h.r0 * Hd;
-        T* hh = dh + (size_t)h.r0 * Hd;
-        T* at = dattn + (size_t)h.r0 * nq * d;
-        T* ml = dmlp + (size_t)h.r0 * I;
-        const int* act = active_dev + h.r0;
-        const int* rl = row_len + h.r0;
-        int rc, S = 1;
-        const bool q8 = mx();
-        const int A = nq * d;
-        uint8_t *hh8 = nullptr, *shh = nullptr, *at8 = nullptr, *sat = nullptr, *ml8 = nullptr, *sml = nullptr;
-        if (q8) {
-            hh8 = dh8 + (size_t)h.r0 * Hd; shh = sdh + (size_t)h.r0 * 4;
-            at8 = dattn8 + (size_t)h.r0 * A; sat = sattn + (size_t)h.r0 * 4;
-            ml8 = dmlp8 + (size_t)h.r0 * I; sml = smlp + (size_t)h.r0 * 4;
-        }
-        if (q8) rc = splitk_gemm_mx(hh8, shh, Hd, MXW(l, SA_MX_QKV_W), MXW(l, SA_MX_QKV_S), M, qkv_d, Hd, h.part, &S, s);
-        else rc = splitk_gemm(hh, Hd, WD(l, SA_RD_QKV_W), Hd, M, qkv_d, Hd, h.part, &S, s);
-        if (rc) return rc;
-        bool launched = false;
-        if constexpr (std::is_same<T, bf16_t>::value) {
-            if (kv8) {                                       // FP8 KV cache (decode_attn_kv8.h)
-                const size_t l8 = (size_t)c.max_slots * nkv, T8 = tmax8();
-                DecodeAttnKv8Args a{h.part, S, WD(l, SA_RD_QKV_B), at, k8c + l * l8 * c.max_kv_len * d, v8tc + l * l8 * d * T8, ksc8 + l * l8 * T8,
-                                    vsc8 + l * l8 * T8, act, rl, rope_cs, M, nq, nkv, d, c.max_kv_len, scale, at8, sat, c.max_slots};
-                if ((rc = launch_decode_attn_kv8(a, s))) return rc;
-                launched = true;
-            }
-        }
-        if (!launched) {
-            DecodeAttnArgs<T> a{h.part, S, WD(l, SA_RD_QKV_B), at, kc, vc, act, rl, rope_cs, M, nq, nkv, d, c.max_kv_len, scale, ctx_bound, at8, sat,
-                                c.max_slots};
-            if ((rc = launch_decode_attn<T>(a, s))) return rc;
-        }
-        const bool last = (l + 1 == c.dec_layers);
-        const T* wnext = last ? W(SA_RW_DEC_NORM) : WD(l + 1, SA_RD_LN1);
-        T* ynext = last ? dlast + (size_t)h.r0 * Hd : hh;
-        if (q8) {
-            if ((rc = splitk_gemm_mx(at8, sat, A, MXW(l, SA_MX_O_W), MXW(l, SA_MX_O_S), M, Hd, A, h.part, &S, s))) return rc;
-            if ((rc = reduce_residual_norm(S, M, h.part, x, WD(l, SA_RD_LN2), hh, s, hh8, shh))) return rc;
-            MxArgs g{hh8, Hd, shh, MXW(l, SA_MX_GU_W), Hd, MXW(l, SA_MX_GU_S), M, 2 * I, Hd, (long)c.max_slots, (long)2 * I};
-            g.Q = ml8; g.ldq = I; g.SQ = sml; g.sq_rows = c.max_slots;
-            if ((rc = launch_gemm_mx<MX_EPI_SWIGLU>(g, s))) return rc;
-            if ((rc = splitk_gemm_mx(ml8, sml, I, MXW(l, SA_MX_DOWN_W), MXW(l, SA_MX_DOWN_S), M, Hd, I, h.part, &S, s))) return rc;
-            return reduce_residual_norm(S, M, h.part, x, wnext, ynext, s, last ? dlast8 + (size_t)h.r0 * Hd : hh8,
-                                        last ? slast + (size_t)h.r0 * 4 : shh);
-        }
-        // the next layer's cache rows of this step's slots are requested while the two reduce kernels run: V first (it is needed
-        // second and may fall back to the infinity cache behind gate|up's 26 MB), K right before the attention launch
-        const bool warm = !last && !kv8;
-        const T* v_next = warm ? vcache + (size_t)(l + 1) * layer_kv : nullptr;
-        const T* k_next = warm ? kcache + (size_t)(l + 1) * layer_kv : nullptr;
-        if ((rc = splitk_gemm(at, (long)nq * d, WD(l, SA_RD_O_W), (long)nq * d, M, Hd, nq * d, h.part, &S, s))) return rc;
-        if ((rc = reduce_residual_norm(S, M, h.part, x, WD(l, SA_RD_LN2), hh, s, nullptr, nullptr, v_next, &h))) return rc;
-        if ((rc = gemm<EPI_SWIGLU>(hh, Hd, WD(l, SA_RD_GU_W), Hd, ml, I, nullptr, nullptr, 0, M, 2 * I, Hd, s))) return rc;
-        if ((rc = splitk_gemm(ml, I, WD(l, SA_RD_DOWN_W), I, M, Hd, I, h.part, &S, s))) return rc;
-        return reduce_residual_norm(S, M, h.part, x, wnext, ynext, s, nullptr, nullptr, k_next, &h);
-    }
-
-    // fuse_next: the rows are the active list of a decode call and another step follows -- the head also writes that step's
-    // embedding, first RMSNorm and row_len (decode_eager skips the embed launch).
-    int heads(int rows, const int* d_last_row, const int* d_row_slot, int step, int len_inc, bool normed, hipStream_t s, bool fuse_next = false) {
-        const int Hd = c.dec_hidden;
-        int rc;
-        T* last = dlast;
-        float4* am = amax;
-        if (!normed && (rc = rmsnorm(dx, Hd, W(SA_RW_DEC_NORM), last, Hd, d_last_row, rows, Hd, c.dec_eps, s))) return rc;
-        // lm_head with the greedy reduction in its epilogue: logits stay in LDS, the head combines per-tile partials.
-        int bn_used = 0;
-        if (mx() && normed) {       // decode steps: MXFP8 lm_head on the MXFP8 copy of the final-norm rows
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
-                a.amax = am;
-                a.bias = W(SA_RW_LM_B);
-                if ((rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s))) return rc;
-                bn_used = a.bn_used;
-            }
-        } else {
-            GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
-            a.amax = am;
-            if ((rc = launch_gemm<T, float, EPI_ARGMAX>(a, s))) return rc;
-            bn_used = a.bn_used;
-        }
-        const int tiles_n = cdiv(c.vocab, bn_used);
-        const size_t so = (size_t)step * c.max_slots;
-        last_rows = rows;
-        last_heads_mx = mx() && normed;
-        if (head2_ok() && tiles_n <= 4 * SA_HEAD_THREADS) {
-            const bool fz = fuse_next;
-            hipLaunchKernelGGL((greedy_head2_kernel<T>), dim3(rows), dim3(SA_HEAD_THREADS), 0, s, reinterpret_cast<const float4*>(am), tiles_n,
-                               last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id, c.pad_token_id, (float)c.bbox_size,
-                               out_token + so, out_score + so, out_bbox + so * 6, next_token, kv_len, len_inc,
-                               fz ? W(SA_RW_TOK_EMBED) : (const T*)nullptr, WD(0, SA_RD_LN1), dx, dh, row_len, c.max_kv_len, c.dec_eps,
-                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots);
-            return (int)hipGetLastError();
-        }
-        if (fuse_next) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
-        hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(rows), dim3(256), 0, s, reinterpret_cast<const float*>(am),
-                           (long)tiles_n, tiles_n, last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id,
-                           c.pad_token_id, (float)c.bbox_size, out_token + so, out_score + so, out_bbox + so * 6, next_token,
-                           kv_len, len_inc);
-        last_rows = rows;
-        last_heads_mx = mx() && normed;
-        return (int)hipGetLastError();
-    }
-
-    int prefill(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
-                const int32_t* slot_ids, int n_seqs, hipStream_t s) override {
-        if (n_seqs <= 0) return SA_OK;
-        if (n_seqs > c.max_slots) return SA_ERR_ARG;
-        const int Ttot = seq_offsets[n_seqs];
-        if (Ttot > c.max_prefill_tokens) return SA_ERR_SHAPE;
-        const int nq = c.dec_heads, nkv = c.dec_kv_heads, d = c.dec_head_dim;
-        std::vector<int> ids(Ttot), tok_slot(Ttot), tok_pos(Ttot), lens(n_seqs), last_row(n_seqs), img_pos;
-        SegLists sg;
-        for (int i = 0; i < n_seqs; ++i) {
-            const int a = seq_offsets[i], L = seq_offsets[i + 1] - a;
-            if (L <= 0 || L >= c.max_kv_len || slot_ids[i] < 0 || slot_ids[i] >= c.max_slots) return SA_ERR_ARG;
-            lens[i] = L; last_row[i] = a + L - 1;
-            if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
-            h_len[slot_ids[i]] = L;
-            for (int t = 0; t < L; ++t) {
-                const int id = input_ids[a + t];
-                if (id < 0 || id >= c.vocab) return SA_ERR_ARG;
-                const bool img = (id == c.image_token_id);
-                ids[a + t] = img ? -1 : id;
-                if (img) img_pos.push_back(a + t);
-                tok_slot[a + t] = slot_ids[i]; tok_pos[a + t] = t;
-            }
-            sg.seg_len.push_back(L);
-            sg.q_off.push_back((long)a * (nq + 2 * nkv) * d);
-            sg.k_off.push_back((long)slot_ids[i] * nkv * c.max_kv_len * d);
-            sg.v_off.push_back((long)slot_ids[i] * nkv * c.max_kv_len * d);
-            sg.o_off.push_back((long)a * nq * d);
-            sg.add_tiles(i, L);
-        }
-        long ntok = 0;
-        for (int i = 0; i < n_images; ++i) ntok += (long)grid_hw[2 * i] * grid_hw[2 * i + 1] / (c.merge * c.merge);
-        if ((long)img_pos.size() != ntok) return SA_ERR_SHAPE;   // reference only warns (common/surya/__init__.py:216-221)
-        int rc;
-        // small plan first (its own stager: the encoder re-stages per chunk)
-        st_small.begin();
-        const int* d_slots = st_small.put(slot_ids, n_seqs);
-        const int* d_lens = st_small.put(lens);
-        const int* d_last = st_small.put(last_row);
-        if (!d_last) return SA_ERR_NOMEM;
-        if ((rc = st_small.flush(s))) return rc;
-        // token embeddings for non-image positions
-        {
-            st.begin();
-            const int* d_ids = st.put(ids);
-            if (!d_ids) return SA_ERR_NOMEM;
-            if ((rc = st.flush(s))) return rc;
-            hipLaunchKernelGGL(embed_tokens_kernel<T>, dim3(Ttot), dim3(128), 0, s, W(SA_RW_TOK_EMBED), d_ids, dx, c.dec_hidden);
-        }
-        if (n_images > 0 && tiles) {
-            if ((rc = encode(tiles, grid_hw, n_images, img_pos, dx, s))) return rc;
-        } else if (n_images > 0) {
-            // embeddings were encoded ahead (encode_ahead): take the next ntok rows of emb_ahead
-            if (ahead_consumed + ntok > ahead_tokens) return SA_ERR_STATE;
-            st.begin();
-            const int* d_img = st.put(img_pos);
-            if (!d_img) return SA_ERR_NOMEM;
-            if ((rc = st.flush(s))) return rc;
-            SA_HIP(hipStreamWaitEvent(s, ev_ahead_done, 0));
-            hipLaunchKernelGGL(scatter_rows_kernel<T>, dim3((unsigned)ntok), dim3(128), 0, s, emb_ahead + ahead_consumed * c.dec_hidden,
-                               d_img, dx, c.dec_hidden);
-            ahead_consumed += ntok;
-            SA_HIP(hipEventRecord(ev_ahead_free, s));
-            ahead_free_recorded = true;
-        }
-        st.begin();
-        const int* d_tok_slot = st.put(tok_slot);
-        const int* d_tok_pos = st.put(tok_pos);
-        AttnSegs d_sg = stage_segs(st, sg);
-        if (!d_sg.o_off) return SA_ERR_NOMEM;
-        if ((rc = st.flush(s))) return rc;
-        hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, s, d_slots, d_lens, kv_len, n_seqs);
-        if ((rc = decoder_layers_prefill(Ttot, d_tok_slot, d_tok_pos, &d_sg, (int)sg.tile_seg.size(), s))) return rc;
-        return heads(n_seqs, d_last, d_slots, 0, 0, false, s);
-    }
-
-    int set_active(const int32_t* slots, int n, hipStream_t s) override {
-        if (n < 0 || n > c.max_slots) return SA_ERR_ARG;
-        n_active = n;
-        for (int i = 0; i < n; ++i)
-            if (slots[i] < 0 || slots[i] >= c.max_slots) return SA_ERR_ARG;
-        h_active.assign(slots, slots + n);
-        if (n == 0) return SA_OK;
-        st_small.begin();
-        const int* d = st_small.put(slots, n);
-        if (!d) return SA_ERR_NOMEM;
-        int rc = st_small.flush(s);
-        if (rc) return rc;
-        SA_HIP(hipMemcpyAsync(active_dev, d, n * sizeof(int), hipMemcpyDeviceToDevice, s));
-        return SA_OK;
-    }
-
-    bool can_fuse_embed() const {       // greedy_head2_kernel's fused tail: two 4-element chunks per thread, lm_head partials in registers
-        return tuning().fuse_embed && head2_ok() && c.dec_hidden <= 2 * 4 * SA_HEAD_THREADS && cdiv(c.vocab, 320) <= 4 * SA_HEAD_THREADS &&
-               cdiv(c.vocab, 64) <= 4 * SA_HEAD_THREADS;
-    }
-    int decode_eager(int M, int n_steps, int step0, hipStream_t s) {
-        int rc;
-        const Half h{0, M, part, s};
-        const bool fuse = can_fuse_embed();
-        if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
-        for (int step = 0; step < n_steps; ++step) {
-            ctx_bound = 0;
-            for (int a : h_active) {
-                ctx_bound = std::max(ctx_bound, h_len[a] + 1);
-                h_len[a] = std::min(h_len[a] + 1, c.max_kv_len);
-            }
-            if ((step == 0 || !fuse) && (rc = decode_embed(h))) return rc;
-            for (int l = 0; l < c.dec_layers; ++l)
-                if ((rc = decode_layer(l, h))) return rc;
-            if ((rc = heads(M, nullptr, active_dev, step0 + step, 1, true, s, fuse && step + 1 < n_steps))) return rc;
-        }
-        return SA_OK;
-    }
-
-    int decode(int n_steps, hipStream_t s) override { return decode_steps(n_steps, 0, s); }
-
-    // Pipelined form: the outputs of this call go to ring half `ring` (steps [8 * ring, 8 * ring + n_steps)) and are
-    // mirrored to pinned host memory behind an event, so the caller can enqueue the NEXT call before it looks at this
-    // one: the host-side bookkeeping and launch latency then overlap with the GPU instead of leaving it idle between
-    // calls (r01 trace: ~0.7 ms idle per round trip, 8 % of the recognition step).
-    int decode_async(int n_steps, int ring, hipStream_t s) override {
-        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        int rc = decode_steps(n_steps, ring * (SA_MAX_STEPS / 2), s);
-        if (rc) return rc;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
-        const size_t nt = (size_t)n_steps * S;
-        if (nt) {
-            SA_HIP(hipMemcpyAsync(out_host + off * 4, out_token + off, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(out_host + full * 4 + off * 4, out_score + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(out_host + full * 8 + off * 24, out_bbox + off * 6, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-        }
-        SA_HIP(hipEventRecord(ev_ring[ring], s));
-        return SA_OK;
-    }
-
-    int wait_outputs(int n_steps, int ring, int32_t* tokens, float* scores, int32_t* bboxes) override {
-        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        SA_HIP(hipEventSynchronize(ev_ring[ring]));
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
-        const size_t nt = (size_t)n_steps * S;
-        memcpy(tokens, out_host + off * 4, nt * sizeof(int));
-        memcpy(scores, out_host + full * 4 + off * 4, nt * sizeof(float));
-        memcpy(bboxes, out_host + full * 8 + off * 24, nt * 6 * sizeof(int));
-        return SA_OK;
-    }
-
-    int decode_steps(int n_steps, int step0, hipStream_t s) {
-        if (n_steps < 0 || step0 < 0 || step0 + n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        const int M = n_active;
-        if (M == 0 || n_steps == 0) return SA_OK;
-        if (!use_graph || !tuning().graph || gemm_profiler().enabled) return decode_eager(M, n_steps, step0, s);
-        if (graph_epoch != tuning_epoch()) { drop_graphs(); graph_epoch = tuning_epoch(); }   // a knob changed since the captures
-        const long key = ((long)M * 64 + n_steps) * 64 + step0;
-        auto it = graphs.find(key);
-        if (it == graphs.end()) {
-            // first sight of this shape runs eagerly (one-time hipFuncSetAttribute calls must not happen inside a capture)
-            if (!seen_keys.count(key)) { seen_keys.insert(key); return decode_eager(M, n_steps, step0, s); }
-            hipGraph_t g = nullptr;
-            SA_HIP(hipStreamBeginCapture(gstream, hipStreamCaptureModeThreadLocal));
-            int rc = decode_eager(M, n_steps, step0, gstream);
-            hipError_t e = hipStreamEndCapture(gstream, &g);
-            if (rc || e != hipSuccess || !g) {                 // capture failed: fall back to eager launches for good
-                if (g) (void)hipGraphDestroy(g);
-                (void)hipGetLastError();
-                use_graph = false;
-                return decode_eager(M, n_steps, step0, s);
-            }
-            hipGraphExec_t ex = nullptr;
-            e = hipGraphInstantiate(&ex, g, nullptr, nullptr, 0);
-            (void)hipGraphDestroy(g);
-            if (e != hipSuccess) { use_graph = false; (void)hipGetLastError(); return decode_eager(M, n_steps, step0, s); }
-            it = graphs.emplace(key, ex).first;
-        }
-        SA_HIP(hipEventRecord(gev_in, s));
-        SA_HIP(hipStreamWaitEvent(gstream, gev_in, 0));
-        SA_HIP(hipGraphLaunch(it->second, gstream));
-        SA_HIP(hipEventRecord(gev_out, gstream));
-        SA_HIP(hipStreamWaitEvent(s, gev_out, 0));
-        return SA_OK;
-    }
-
-    int read_outputs(int n_steps, int32_t* tokens, float* scores, int32_t* bboxes, hipStream_t s) override {
-        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S;
-        const size_t nt = (size_t)n_steps * S;
-        SA_HIP(hipMemcpyAsync(out_host, out_token, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(out_host + full * 4, out_score, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(out_host + full * 8, out_bbox, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipStreamSynchronize(s));
-        memcpy(tokens, out_host, nt * sizeof(int));
-        memcpy(scores, out_host + full * 4, nt * sizeof(float));
-        memcpy(bboxes, out_host + full * 8, nt * 6 * sizeof(int));
-        return SA_OK;
-    }
-
-    // Test hook: the product path never materialises logits (EPI_ARGMAX above), so they are recomputed here from the
-    // final-norm rows of the last prefill / decode step, which are still in `dlast`, with the same GEMM main loop.
-    int copy_last_logits(float* dst, int max_rows, int* rows, hipStream_t s) override {
-        const int r = std::min(max_rows, last_rows);
-        *rows = r;
-        if (r <= 0) return SA_OK;
-        const int Hd = c.dec_hidden;
-        int rc;
-        if (last_heads_mx) {
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), last_rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
-                a.C = logits; a.ldc = c.vocab; a.bias = W(SA_RW_LM_B);
-                if ((rc = launch_gemm_mx<MX_EPI_F32>(a, s))) return rc;
-            }
-        } else {
-            GemmArgs<T, float> a{dlast, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, last_rows, c.vocab, Hd};
-            if ((rc = launch_gemm<T, float, EPI_BIAS>(a, s))) return rc;
-        }
-        SA_HIP(hipMemcpyAsync(dst, logits, (size_t)r * c.vocab * sizeof(float), hipMemcpyDeviceToDevice, s));
-        return SA_OK;
-    }
-
-    int set_next_tokens(const int32_t* slots, const int32_t* toks, int n, hipStream_t s) override {
-        if (n <= 0) return SA_OK;
-        st_small.begin();
-        const int* ds = st_small.put(slots, n);
-        const int* dt = st_small.put(toks, n);
-        if (!dt) return SA_ERR_NOMEM;
-        int rc = st_small.flush(s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(set_next_tokens_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, dt, next_token, n);
-        return (int)hipGetLastError();
-    }
-};
-
 static int check_cfg(const surya_rec_config* c) {
     if (!c) return SA_ERR_ARG;
-    if (c->dtype != SA_DTYPE_F32 && c->dtype != SA_DTYPE_BF16) return SA_ERR_UNSUPPORTED;
+    if (c->dtype != SA_DTYPE_F32 && c->dtype != SA_DTYPE_BF16 && c->dtype != SA_DTYPE_F16) return SA_ERR_UNSUPPORTED;
     if (c->enc_hidden % 64 || c->enc_inter_pad % 64 || c->patch_dim_pad % 64 || c->dec_hidden % 64 || c->dec_inter % 64 ||
         (c->dec_heads * c->dec_head_dim) % 64 || c->vocab % 4)
         return SA_ERR_SHAPE;
@@ -1033,7 +65,12 @@ using namespace sa;
 struct surya_rec { std::unique_ptr<RecBase> impl; surya_rec_config cfg; };
 
 // ------------------------------------------------------------------------------------------------ op level
-namespace sa {   // det_model.hip: the fp16 GEMMs of surya_op_gemm
+namespace sa {
+// rec_model_f16.hip: RecModel<fp16_t>
+size_t rec_f16_workspace_bytes(const surya_rec_config& cfg);
+int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int n, std::unique_ptr<RecBase>& out);
+int rec_f16_ring_error(bool reset);
+// det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
 // ocr_error_model.hip: the fp16 GELU epilogue and fp16 segment attention of the OCR-error classifier
@@ -1065,6 +102,7 @@ const char* surya_amd_version(void) { return "surya_amd 0.1.0 gfx950"; }
 
 size_t surya_rec_workspace_bytes(const surya_rec_config* cfg) {
     if (check_cfg(cfg)) return 0;
+    if (cfg->dtype == SA_DTYPE_F16) return sa::rec_f16_workspace_bytes(*cfg);
     return cfg->dtype == SA_DTYPE_F32 ? RecModel<float>::layout(*cfg, nullptr) : RecModel<bf16_t>::layout(*cfg, nullptr);
 }
 
@@ -1080,6 +118,8 @@ int surya_rec_create(const surya_rec_config* cfg, const void* const* weights, in
         auto m = std::make_unique<RecModel<float>>();
         rc = m->init(*cfg, weights, n_weights);
         h->impl = std::move(m);
+    } else if (cfg->dtype == SA_DTYPE_F16) {
+        rc = sa::rec_f16_create(*cfg, weights, n_weights, h->impl);
     } else {
         auto m = std::make_unique<RecModel<bf16_t>>();
         rc = m->init(*cfg, weights, n_weights);
@@ -1255,7 +295,7 @@ int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_s
                                     rows, heads, kv_heads, head_dim, max_kv_len, scale};
         return sa::launch_decode_attn<float>(a, s);
     }
-    if (dtype == SA_DTYPE_F16) {              // the layout / table decoder's head shapes (d = 64 / 32), built in layout_model.hip
+    if (dtype == SA_DTYPE_F16) {              // d = 64 / 32 built in layout_model.hip, d = 128 (the recogniser's) in rec_model_f16.hip
         sa::DecodeAttnArgs<sa::fp16_t> a{qkv_part, n_slabs, (const sa::fp16_t*)qkv_bias, (sa::fp16_t*)out, (sa::fp16_t*)kcache, (sa::fp16_t*)vcache,
                                          active_slots, row_len, cs, rows, heads, kv_heads, head_dim, max_kv_len, scale};
         return sa::launch_decode_attn<sa::fp16_t>(a, s);
@@ -1365,7 +405,10 @@ int surya_set_tuning(const char* key, int value) {
     return SA_ERR_ARG;
 }
 
-int surya_gemm_ring_status(int reset) { return sa::ring_error(reset != 0); }
+int surya_gemm_ring_status(int reset) {       // every translation unit that runs the ring has a give-up word of its own
+    const int a = sa::ring_error(reset != 0), b = sa::rec_f16_ring_error(reset != 0);
+    return a ? a : b;
+}
 
 int surya_prof_enable(int on) {
     GemmProfiler& pf = gemm_profiler();

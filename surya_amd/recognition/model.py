@@ -28,8 +28,8 @@ class HipRecModel:
         self.device = torch.device(device)
         self.dtype = dtype
         torch.cuda.set_device(self.device)
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be float32 (reference mode) or bfloat16")
+        if dtype not in (torch.float32, torch.bfloat16, torch.float16):
+            raise ValueError("dtype must be float32 (reference mode), bfloat16 or float16")
         e, d = cfg.encoder, cfg.decoder
         self.max_slots = max_slots
         self.vocab = d.vocab_size
@@ -57,7 +57,7 @@ class HipRecModel:
             bbox_size=cfg.bbox_size, embed_multiplier=cfg.image_embed_encoding_multiplier,
             image_token_id=image_token_id, pad_token_id=pad_token_id, eos_token_id=eos_token_id, max_slots=max_slots,
             max_kv_len=max_kv_len, max_patches=max_patches, max_prefill_tokens=max_prefill_tokens,
-            dtype=L.DTYPE_F32 if dtype == torch.float32 else L.DTYPE_BF16)
+            dtype={torch.float32: L.DTYPE_F32, torch.bfloat16: L.DTYPE_BF16, torch.float16: L.DTYPE_F16}[dtype])
         self.c = c
         table = (C.c_void_p * len(self.weights))(*[t.data_ptr() for t in self.weights])
         self.handle = C.c_void_p()
