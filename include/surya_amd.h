@@ -212,6 +212,27 @@ int surya_rec_set_mx_weights(surya_rec* h, const void* const* table, int n);
  * oracle/mx_oracle.py::kv8_quantize and tests/test_gpu_kv8.py. Call while no line is in flight. */
 int surya_rec_set_kv_fp8(surya_rec* h, int on);
 
+/* Constrained output: restrict the tokens of a line to an allowed set (a character whitelist / blacklist; surya_amd/recognition/
+ * tokenizer.py::token_mask builds the sets). The reference has no such switch -- a caller patches process_outputs and masks
+ * next_token_logits -- and here logits never exist outside a tile (the lm_head epilogues reduce each tile to one partial), so the
+ * mask is applied inside those epilogues, before the max and the sum-exp pass: token = first argmax over the allowed ids, score =
+ * softmax over the allowed ids, i.e. what process_outputs gives on next_token_logits.masked_fill(~allowed, -inf). The first token of a
+ * line (the prefill's head pass) is constrained like every later one. The fused next-step embedding and the bbox head are untouched.
+ *   set_token_masks: `masks` = host array [n_masks][ceil(vocab / 32)] of uint32, bit (c & 31) of word (c >> 5) set = id c allowed; it is
+ *                copied into handle-owned device memory whose address never changes (captured decode steps stay valid while only the
+ *                contents change), in stream order. Every mask needs an allowed id below vocab and n_masks <= SA_MAX_TOKEN_MASKS, else
+ *                SA_ERR_ARG (nothing changes). n_masks == 0 switches back to the unmasked kernels: a handle that never saw a mask, or
+ *                saw 0 last, launches exactly what it launched before this entry existed. Switching between the two drops captured
+ *                decode steps, as surya_rec_set_kv_fp8 does. A new table sets every slot back to -1.
+ *   set_slot_masks: mask id (row of the table, or -1 = unconstrained) of `n` slots; call it for the slots about to be prefilled. A slot
+ *                keeps its id until it is set again or the table is replaced. SA_ERR_STATE without a table; a slot named twice, a slot
+ *                or an id out of range: SA_ERR_ARG.
+ * surya_rec_copy_last_logits keeps returning the UNMASKED logits (the mask lives in the greedy epilogues only): a test recomputes the
+ * masked token and score from them. Call both while no line that they concern is in flight. */
+#define SA_MAX_TOKEN_MASKS 64
+int surya_rec_set_token_masks(surya_rec* h, const uint32_t* masks, int n_masks, void* stream);
+int surya_rec_set_slot_masks(surya_rec* h, const int32_t* slots, const int32_t* mask_ids, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -277,6 +298,16 @@ int surya_op_rec_gemm_f16(int mode, int epi, const void* X, long ldx, const void
  * any M (above 256 rows the launchers pick larger tiles, same bits per element). mode 0: one pass; mode 1: split-K, `C` receives the slabs [*splitk][M][N] (capacity 8 slabs) and the caller sums
  * them; mode 2: SwiGLU epilogue -> MXFP8 [M][N/2] in q_out, scales [N / 256][M][4] in sq_out (N % 256 == 0). */
 int surya_op_mx_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* scales, void* stream);
+/* The lm_head launch by itself, through the launcher the recognition engine uses (launch_gemm / launch_gemm_mx with the greedy-partial
+ * epilogue; above 256 rows the grouped 256 x 320 launch), so the epilogues can be tested at small K. dtype SA_DTYPE_F32 / BF16 / F16: X
+ * [M][K], W [N][K], bias [N] or NULL in that dtype, SX = SW = NULL. dtype SA_OP_MXFP8: X, W e4m3 with e8m0 scales SX, SW laid out as
+ * surya_op_gemm_mx takes them, bias bf16 [N] or NULL. masks = NULL: the unmasked epilogue. Otherwise the masked one: masks [n][ceil(N / 32)]
+ * uint32, slot_mask [slots] int32 (row of masks or -1) and row_slot [M] int32 (NULL: row m is slot m), all DEVICE arrays as the engine
+ * holds them; the caller keeps ids inside the table. amax receives one float4 {max, bits of the first argmax column, sum exp(v - max), 0}
+ * per (row, column tile) at amax[(m * cdiv(N, *bn_used) + tile) * 4]; *bn_used = the tile width chosen (>= 64). Enqueue only. */
+#define SA_OP_MXFP8 3
+int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                              const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream);
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream);
 

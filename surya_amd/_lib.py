@@ -12,6 +12,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.so")   # env: A/B builds of the kernels
 
 SA_MAX_STEPS = 16
+SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
+OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
  RW_LM_B, RW_BBOX_W, RW_BBOX_B, RW_ENC_INVFREQ, RW_DEC_INVFREQ, RW_GLOBALS) = range(17)
@@ -98,6 +100,10 @@ def _bind_lay_ops(lib):
     # the fp16 recogniser's GEMMs (csrc/rec_model_f16.hip)
     lib.surya_op_rec_gemm_f16.argtypes, lib.surya_op_rec_gemm_f16.restype = [i, i, p, l, p, l, p, l, p, p, l, i, i, i, p, ip, p], C.c_int
     lib.surya_op_gemm_splitk_f16.argtypes, lib.surya_op_gemm_splitk_f16.restype = [p, l, p, l, p, i, i, i, ip, p], C.c_int
+    # constrained output (token masks of the lm_head's greedy epilogues) and the lm_head launch by itself
+    lib.surya_rec_set_token_masks.argtypes, lib.surya_rec_set_token_masks.restype = [p, C.POINTER(C.c_uint32), i, p], C.c_int
+    lib.surya_rec_set_slot_masks.argtypes, lib.surya_rec_set_slot_masks.restype = [p, ip, ip, i, p], C.c_int
+    lib.surya_op_lm_head_partials.argtypes, lib.surya_op_lm_head_partials.restype = [i, p, p, p, p, p, i, i, i, p, p, p, p, ip, p], C.c_int
 
 
 def check(rc: int, what: str):

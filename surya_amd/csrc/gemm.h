@@ -35,7 +35,31 @@
 namespace sa {
 
 enum GemmEpi { EPI_BIAS = 0, EPI_RESIDUAL = 1, EPI_GELU = 2, EPI_SWIGLU = 3, EPI_HARDSWISH = 4, EPI_RELU = 5, EPI_ARGMAX = 6, EPI_ROPE = 7,
-               EPI_GEGLU = 8 /* gelu_tanh(gate) * up, rows interleaved like SWIGLU (ADETR decoder MLP, adetr/decoder.py:331-344) */ };
+               EPI_GEGLU = 8 /* gelu_tanh(gate) * up, rows interleaved like SWIGLU (ADETR decoder MLP, adetr/decoder.py:331-344) */,
+               EPI_ARGMAX_MASK = 9 /* EPI_ARGMAX over the columns a per-row token mask allows (TokenMask below) */ };
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_MASK; }
+
+// Allowed-column sets of the greedy-partial epilogues (EPI_ARGMAX_MASK here, MX_EPI_ARGMAX_MASK in gemm_mx.h). Row m of the GEMM belongs
+// to slot row_slot[m] (the map the greedy head receives: the prefilled sequences' slots, or the active list of a decode step), a slot names
+// one row of `table` or -1 = unconstrained. A disallowed column is treated exactly like a column past N: -inf before the max pass and the
+// sum-exp pass, so a tile without an allowed column yields the record (-inf, 0x7fffffff, 0) a tile wholly past N yields. Tile widths do
+// not depend on the mask: a partial covers the same columns with the mask on or off, and an all-ones mask gives the unmasked bits.
+struct TokenMask {
+    const uint32_t* table = nullptr;   // [n_masks][words]: bit (c & 31) of word (c >> 5) set = column c allowed
+    const int* slot_mask = nullptr;    // [slots]: row of `table`, -1 = every column allowed
+    const int* row_slot = nullptr;     // [M]; nullptr: row m is slot m
+    int words = 0;                     // cdiv(N, 32)
+    // mask id of GEMM row m (rows past M read row M - 1)
+    __device__ __forceinline__ int id_of(int m, int M) const {
+        const int gm = min(m, M - 1);
+        return slot_mask[row_slot ? row_slot[gm] : gm];
+    }
+    // word `w` of mask `mid` (words past the table read its last word: their columns are past N)
+    __device__ __forceinline__ uint32_t word_of(int mid, int w) const {
+        const uint32_t v = table[(long)max(mid, 0) * words + min(w, words - 1)];
+        return mid < 0 ? 0xffffffffu : v;
+    }
+};
 
 template <typename TI, typename TO>
 struct GemmArgs {
@@ -53,6 +77,7 @@ struct GemmArgs {
     // per (row, tile column) goes to amax[m * cdiv(N, bn_used) + tile_n]; the launcher reports the tile width it chose.
     float4* amax = nullptr;
     mutable int bn_used = 0;
+    TokenMask tmask;             // EPI_ARGMAX_MASK
     // EPI_ROPE (vision qkv projection): rotary embedding of the q and k columns (n < rope_cols) in the epilogue. The weight
     // rows of every head are stored PAIR-INTERLEAVED (new column 2j = old j, 2j + 1 = old j + D/2), so the lane that owns
     // four consecutive columns holds two complete rotate_half pairs; rope[m * (D/2) + j] = (cos, sin) of token m, pair j.
@@ -103,6 +128,54 @@ template <> struct Mfma<float> {
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(__uint_as_float(w[3]), __uint_as_float(x[3]), acc, 0, 0, 0);
     }
 };
+
+// Greedy-head partials of one staged fp32 tile (rows of CPR 16-byte chunks, XOR-swizzled) over the columns the row's mask allows: the
+// reduction of the EPI_ARGMAX epilogue below with one more condition on a column. A thread's SEG * 4 columns lie in whole mask words (or
+// inside one), fetched before the first pass; both passes are unrolled so that the word a chunk consults is a register.
+template <int BM, int NT, int CPR, int XM>
+__device__ __forceinline__ void argmax_partial_masked(const unsigned char* smem, const TokenMask& tm, int m0, int n0, int M, int N,
+                                                      float4* amax, int tiles_n, int tile_n) {
+    constexpr int TPR = NT / BM, SEG = CPR / TPR, ROWB = CPR * 16, NWD = (SEG * 4 + 31) / 32;
+    static_assert(NT % BM == 0 && (TPR & (TPR - 1)) == 0 && TPR <= 8 && CPR % TPR == 0, "argmax epilogue split");
+    static_assert(SEG * 4 >= 32 ? (SEG * 4) % 32 == 0 : 32 % (SEG * 4) == 0, "a thread's columns: whole mask words, or a part of one");
+    const int tid = threadIdx.x, row = tid / TPR, part = tid % TPR;
+    const int nbeg = n0 + part * SEG * 4;                     // n0 is a multiple of the tile width, itself a multiple of 32
+    uint32_t mw[NWD];
+    const int mid = tm.id_of(m0 + row, M);                    // resolved once; the words are independent loads behind it
+#pragma unroll
+    for (int k = 0; k < NWD; ++k) mw[k] = tm.word_of(mid, (nbeg >> 5) + k);
+    const unsigned char* rowp = smem + row * ROWB;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+        const uint32_t bits = mw[(cc * 4) >> 5] >> (n & 31);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N && ((bits >> i) & 1u) && v[i] > best) { best = v[i]; bi = n + i; }     // strict >: first allowed maximum wins
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+        const uint32_t bits = mw[(cc * 4) >> 5] >> (n & 31);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N && ((bits >> i) & 1u)) se += expf(v[i] - best);       // an allowed column exists here, so best is finite
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) se += __shfl_xor(se, o, 64);
+    if (part == 0 && m0 + row < M) amax[(long)(m0 + row) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
+}
 
 // BM x BN output tile per workgroup of WM x WN waves.
 template <typename TI, typename TO, int BM, int BN, int WM, int WN, int EPI, bool SPLIT = false, int GLDS = 0, bool CONV = false, int WAUX = 0>
@@ -675,7 +748,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
     // a lane holds, for each of its FM rows, FN x 16 of the wave's columns in ascending order (the other FN x 16 sit in lane ^ 32),
     // so the row's (max, first argmax, sum exp) over the wave's columns is a serial pass + one exchange; the WN waves of a row meet
     // in 16 bytes of LDS each.
-    constexpr bool ARGMAX_DIRECT = (EPI == EPI_ARGMAX) && ((size_t)BM * BN * 4 > 160 * 1024);
+    constexpr bool ARGMAX_DIRECT = epi_is_argmax(EPI) && ((size_t)BM * BN * 4 > 160 * 1024);
     if constexpr (ARGMAX_DIRECT) {
         static_assert(!SPLIT && std::is_same<TO, float>::value && NT >= BM, "direct argmax epilogue");
         const bool with_bias = p.bias != nullptr;                             // wave-uniform
@@ -686,9 +759,51 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
             if (with_bias) load4(p.bias + min(n0 + tid * 4, p.N - 4), b);
             *reinterpret_cast<float4*>(bias_s + tid * 4) = make_float4(b[0], b[1], b[2], b[3]);
         }
+        // EPI_ARGMAX_MASK: the tile's mask words, [BM][BN / 32] at an odd row stride (a lane reads its own row's word: no bank conflict), in
+        // LDS beside the bias (ten words per row in registers next to the accumulators would not fit; a lane reads the word of (row block
+        // i, column block j) where it masks that block). One thread per row: the row's mask id is resolved once (row -> slot -> id, two
+        // dependent loads) and its ten table words are independent loads behind it.
+        constexpr int MWS = (BN / 32) | 1;
+        [[maybe_unused]] uint32_t* mask_s = reinterpret_cast<uint32_t*>(smem + (size_t)BM * WN * 16 + (size_t)BN * 4);
+        if constexpr (EPI == EPI_ARGMAX_MASK) {
+            static_assert(BN % 32 == 0 && WTN == FN * 32 && NT >= BM && (size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * MWS * 4 <= (size_t)(BM + BN) * 256,
+                          "mask words fit the staging LDS");
+            if (tid < BM) {
+                const int mid = p.tmask.id_of(m0 + tid, p.M);
+#pragma unroll
+                for (int k = 0; k < BN / 32; ++k) {
+                    // ... with the bits of columns past N cleared: where the accumulators are masked one bit says both "inside N" and "allowed"
+                    const int wd = (n0 >> 5) + k, left = p.N - wd * 32;
+                    const uint32_t inside = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << left) - 1u);
+                    mask_s[tid * MWS + k] = p.tmask.word_of(mid, wd) & inside;
+                }
+            }
+        }
         __syncthreads();
         // columns of this lane: base + off with off = j * 32 + g * 8 + r a compile-time constant; off < lim are inside N
-        const int base = n0 + wn * WTN + (lane >> 5) * 4, lim = p.N - base;
+        const int base = n0 + wn * WTN + (lane >> 5) * 4;
+        [[maybe_unused]] const int lim = p.N - base;
+        if constexpr (EPI == EPI_ARGMAX_MASK) {
+            // a disallowed column is a column past N: -inf here, once, before the max pass and the sum-exp pass
+            const uint32_t* mrow = mask_s + (wm * WTM + (lane & 31)) * MWS + wn * FN;
+            const int sh = (lane >> 5) * 4;
+#pragma unroll
+            for (int j = 0; j < FN; ++j) {
+                uint32_t bits[FM];
+#pragma unroll
+                for (int i = 0; i < FM; ++i) bits[i] = mrow[i * 32 * MWS + j] >> sh;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) {
+                    const float4 b4 = *reinterpret_cast<const float4*>(bias_s + wn * WTN + j * 32 + g * 8 + (lane >> 5) * 4);
+                    const float b[4] = {b4.x, b4.y, b4.z, b4.w};
+#pragma unroll
+                    for (int i = 0; i < FM; ++i)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            acc[j][i][4 * g + r] = ((bits[i] >> (g * 8 + r)) & 1u) ? acc[j][i][4 * g + r] + b[r] : -INFINITY;
+                }
+            }
+        } else {
 #pragma unroll
         for (int j = 0; j < FN; ++j)
 #pragma unroll
@@ -701,6 +816,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
                     for (int r = 0; r < 4; ++r)          // masked once, here: every later pass sees -inf past N
                         acc[j][i][4 * g + r] = (j * 32 + g * 8 + r < lim) ? acc[j][i][4 * g + r] + b[r] : -INFINITY;
             }
+        }
 #pragma unroll
         for (int i = 0; i < FM; ++i) {
             __builtin_amdgcn_sched_barrier(0);                                    // one row block at a time (register pressure)
@@ -746,10 +862,12 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
                 if (r4.x > best || (r4.x == best && ri < bi)) { best = r4.x; bi = ri; }
             }
             float se = 0.f;
+            // (EPI_ARGMAX_MASK: a row may have no allowed column in the whole tile -- every wave -inf -- and exp(-inf - (-inf)) must not appear)
+            const float fsafe = (EPI == EPI_ARGMAX_MASK && best == -INFINITY) ? 0.f : best;
 #pragma unroll
             for (int w = 0; w < WN; ++w) {
                 const float4 r4 = rec[tid * WN + w];
-                se += r4.z * expf(r4.x - best);                                      // a wave past N holds (-inf, -, 0): contributes 0
+                se += r4.z * expf(r4.x - fsafe);                                     // a wave past N holds (-inf, -, 0): contributes 0
             }
             p.amax[(long)(m0 + tid) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
         }
@@ -850,6 +968,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
         }
     }
     __syncthreads();
+    if constexpr (EPI == EPI_ARGMAX_MASK) {
+        static_assert(!SPLIT && std::is_same<TO, float>::value, "argmax epilogue works on fp32 tiles");
+        argmax_partial_masked<BM, NT, CPR, XM>(smem, p.tmask, m0, n0, p.M, p.N, p.amax, tiles_n, tile_n);
+        return;
+    }
     if constexpr (EPI == EPI_ARGMAX) {
         // Greedy-head partials straight from the staged tile: the [M, N] fp32 logits never travel to HBM (84 MB written and
         // read twice per decode step at V = 81920, M = 256 -- more than the lm_head weights themselves).
@@ -954,7 +1077,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
 template <typename TI, typename TO, int EPI, int CONV = 0>
 __global__ __launch_bounds__(512) void gemm_nt_p8p_kernel(GemmArgs<TI, TO> p) {
     constexpr int BM = 256, BN = 256, GRP = 32, KE = Ty<TI>::KE, HT = 16384;
-    static_assert(sizeof(TI) == 2 && sizeof(TO) == 2 && EPI != EPI_ARGMAX, "persistent 8-phase loop: bf16 operands, 2-byte outputs");
+    static_assert(sizeof(TI) == 2 && sizeof(TO) == 2 && !epi_is_argmax(EPI), "persistent 8-phase loop: bf16 operands, 2-byte outputs");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
@@ -1479,7 +1602,7 @@ static inline int launch_gemm_cfg(const GemmArgs<TI, TO>& a, hipStream_t s) {
     constexpr size_t out_w = ((EPI == EPI_SWIGLU || EPI == EPI_GEGLU) && !SPLIT) ? BN / 2 : BN;
     constexpr size_t out_bytes = (size_t)BM * out_w * (SPLIT ? sizeof(float) : sizeof(TO));
     constexpr size_t stage_bytes = (size_t)(BM + BN) * 128 * (GLDS > 2 && GLDS != 8 ? GLDS : 2);
-    constexpr bool argmax_direct = (EPI == EPI_ARGMAX) && ((size_t)BM * BN * 4 > 160 * 1024);     // partials straight from the accumulators
+    constexpr bool argmax_direct = epi_is_argmax(EPI) && ((size_t)BM * BN * 4 > 160 * 1024);     // partials straight from the accumulators
     constexpr size_t lds = (argmax_direct || stage_bytes > out_bytes) ? stage_bytes : out_bytes;   // staging buffers are reused for the output tile
     auto kern = gemm_nt_kernel<TI, TO, BM, BN, WM, WN, EPI, SPLIT, GLDS, CONV, WAUX>;
     static AttrOnce attr;           // >64 KiB dynamic LDS needs the opt-in attribute; harmless below
@@ -1492,7 +1615,7 @@ static inline int launch_gemm_cfg(const GemmArgs<TI, TO>& a, hipStream_t s) {
         (void)hipEventRecord(pf.ev[2 * pf.n + 1], s);
         pf.cfg_of[pf.n] = CONV ? 3 : gemm_cfg_id(BM, BN);       // bucket 3 = implicit-GEMM convolutions
         pf.flops_of[pf.n] = CONV ? 2.0 * a.M * a.N * a.cTaps * a.cCin : 2.0 * a.M * a.N * a.K;
-        const double outn = (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) ? a.N / 2 : (EPI == EPI_ARGMAX ? 4.0 * cdiv(a.N, BN) : a.N);
+        const double outn = (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) ? a.N / 2 : (epi_is_argmax(EPI) ? 4.0 * cdiv(a.N, BN) : a.N);
         const double xelems = CONV ? (double)a.M / std::max(1, a.cHo * a.cWo) * a.cH * a.cW * a.cCin : (double)a.M * a.K;   // the input tensor once
         // algorithmic bytes: X + W + the result ONCE in the storage type (what an unsplit GEMM of this shape would move). The fp32
         // partial slabs a split-K launch actually writes are the kernel's own decomposition, not the problem's: counted apart
@@ -1562,8 +1685,11 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
         if (a.K % Ty<TI>::KE != 0 || a.N % 4 != 0 || n_out % (16 / (int)sizeof(TO)) != 0 || a.ldc % (16 / (int)sizeof(TO)) != 0)
             return SA_ERR_SHAPE;
     }
+    if constexpr (EPI == EPI_ARGMAX_MASK) {
+        if (!a.tmask.table || !a.tmask.slot_mask || a.tmask.words != cdiv(a.N, 32)) return SA_ERR_ARG;
+    }
     if (a.M <= 256) {
-        if constexpr (EPI == EPI_ARGMAX) {
+        if constexpr (epi_is_argmax(EPI)) {
             // the fused lm_head hands per-column-block (max, sum-exp) partials to greedy_head: keep the block width a function
             // of N alone so a line's score is summed in the same groups whatever the number of active rows
             // Round 4: lm_head-sized N runs as ONE round of 256-row x 320-column tiles (81920 = 256 x 320: a tile per CU). The 128x128
@@ -1603,7 +1729,7 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
         if (a.N >= 64 * 128) return launch_gemm_cfg<TI, TO, 64, 64, 2, 2, EPI>(a, s);
         return launch_gemm_cfg<TI, TO, 64, 32, 2, 1, EPI>(a, s);
     }
-    if constexpr (EPI == EPI_ARGMAX) {
+    if constexpr (epi_is_argmax(EPI)) {
         // 257 ... 1024 (and more) rows (round 6; the reference's recognition_batch_size is open-ended, its README runs 864): the SAME 256 x 320
         // tile per 256-row block, so the per-column-block (max, sum-exp) partials -- and with them every line's score bits -- are the ones the
         // <= 256-row launch produces, whatever the slot count; the row blocks of a W tile share it through one XCD's L2 (mgroup)
@@ -1650,7 +1776,7 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
         // encoder / prefill shape and on 8k^3 (1212 -> 1026 TF/s, profiles/r03_sweeps.txt): the big-tile loop is bound by L2 -> LDS bytes
         // per flop, not by prefetch depth.)
         if (bigtile && a.K >= tuning().bigtile_min_k && ((t256 >= 256 && cost256 <= cost128) || tuning().bigtile_any)) {
-            if constexpr (EPI != EPI_ARGMAX) {
+            if constexpr (!epi_is_argmax(EPI)) {
                 const int nk = a.K / Ty<TI>::KE;
                 if constexpr (sizeof(TI) == 2)
                     if (tuning().persist && nk >= 4 && nk % 2 == 0 && a.N % 8 == 0) return launch_gemm_persist<TI, TO, EPI>(a, s);
@@ -1659,7 +1785,7 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
             // two thirds of the LDS fragment bytes per MFMA of the 8-wave layout (32 KB per 64 MFMAs instead of 24 KB per 32). A third
             // stage does not fit (3 x 64 KB > 160 KB of LDS). Same K order and MFMA: bit-identical outputs.
             // A/B: tools/microbench/bigtile_ab.py 1 2.
-            if constexpr (sizeof(TI) == 2 && EPI != EPI_ARGMAX) {
+            if constexpr (sizeof(TI) == 2 && !epi_is_argmax(EPI)) {
                 if (bigtile == 2) return launch_gemm_cfg<TI, TO, 256, 256, 2, 2, EPI, false, 2>(a, s);
                 // bigtile = 3: the 8-phase schedule (half-tile ring, counted vmcnt, two wave groups one barrier apart); even K-tile counts
                 if (bigtile == 3 && (a.K / Ty<TI>::KE) % 2 == 0) return launch_gemm_cfg<TI, TO, 256, 256, 4, 2, EPI, false, 8>(a, s);

@@ -150,7 +150,14 @@ struct RecBase {
     virtual int set_next_tokens(const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_mx_weights(const void* const*, int) = 0;
     virtual int set_kv_fp8(int) = 0;
+    virtual int set_token_masks(const uint32_t*, int, hipStream_t) = 0;
+    virtual int set_slot_masks(const int32_t*, const int32_t*, int, hipStream_t) = 0;
 };
+
+static __global__ void set_slot_masks_kernel(const int* slots, const int* ids, int* slot_mask, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) slot_mask[slots[i]] = ids[i];
+}
 
 static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
 
@@ -213,6 +220,16 @@ struct RecModel : RecBase {
             *slast = nullptr;
     static constexpr bool MX_OK = std::is_same<T, bf16_t>::value;     // MXFP8 weights / activations exist beside the bf16 engine only
     bool mx() const { return MX_OK && !mxw.empty(); }
+    // Allowed-character sets (surya_rec_set_token_masks / surya_rec_set_slot_masks; TokenMask in gemm.h): a table of SA_MAX_TOKEN_MASKS
+    // bit rows over the vocabulary and one row id per slot, at addresses that never change once allocated -- captured decode steps hold
+    // the pointers, the contents follow the calls in stream order. n_token_masks == 0: the unmasked lm_head kernels, as ever.
+    char* mask_arena = nullptr;
+    uint32_t* mask_table = nullptr;                      // [SA_MAX_TOKEN_MASKS][mask_words()]
+    int* slot_mask = nullptr;                            // [max_slots], -1 = unconstrained
+    Stager st_mask;
+    int n_token_masks = 0;
+    int mask_words() const { return cdiv(c.vocab, 32); }
+    TokenMask token_mask(const int* d_row_slot) const { return TokenMask{mask_table, slot_mask, d_row_slot, mask_words()}; }
     const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
     const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
 
@@ -318,6 +335,7 @@ struct RecModel : RecBase {
     ~RecModel() override {
         if (mx_arena) (void)hipFree(mx_arena);
         if (kv8_arena) (void)hipFree(kv8_arena);
+        if (mask_arena) { (void)hipFree(mask_arena); st_mask.destroy(); }
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -582,6 +600,69 @@ struct RecModel : RecBase {
         return SA_OK;
     }
 
+    // The mask table of the lm_head's greedy epilogues. Every row needs an allowed id inside the vocabulary: a row without one would
+    // make the head emit the "no column" index 0x7fffffff and the next step embed it. Replacing the table sets every slot back to -1 (the
+    // ids named rows of the old table). Switching between the masked and the unmasked kernels drops captured steps, as set_kv_fp8 does.
+    int set_token_masks(const uint32_t* masks, int n, hipStream_t s) override {
+        if (n < 0 || n > SA_MAX_TOKEN_MASKS || (n > 0 && !masks)) return SA_ERR_ARG;
+        const int words = mask_words();
+        for (int i = 0; i < n; ++i) {
+            bool any = false;
+            for (int wd = 0; wd < words && !any; ++wd) {
+                const int left = c.vocab - wd * 32;                     // bits of the last word past the vocabulary do not count
+                any = (masks[(size_t)i * words + wd] & (left >= 32 ? 0xffffffffu : ((1u << left) - 1u))) != 0;
+            }
+            if (!any) return SA_ERR_ARG;
+        }
+        if (n == 0) {
+            if (n_token_masks > 0) drop_graphs();
+            n_token_masks = 0;
+            return SA_OK;
+        }
+        const size_t table_bytes = (size_t)SA_MAX_TOKEN_MASKS * words * sizeof(uint32_t);
+        if (!mask_arena) {                                  // first table: memory and staging, or nothing (a failure leaves the handle as it was)
+            const size_t slot_bytes = align_up((size_t)c.max_slots * sizeof(int));
+            char* mem = nullptr;
+            SA_HIP(hipMalloc((void**)&mem, slot_bytes + table_bytes));
+            int rc = st_mask.init(table_bytes + (size_t)c.max_slots * 2 * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipMemsetAsync(mem, 0xff, slot_bytes + table_bytes, s);      // every slot -1, every column allowed
+            if (rc) { st_mask.destroy(); st_mask = Stager(); (void)hipFree(mem); return rc; }
+            mask_arena = mem;
+            slot_mask = reinterpret_cast<int*>(mask_arena);
+            mask_table = reinterpret_cast<uint32_t*>(mask_arena + slot_bytes);
+        }
+        st_mask.begin();
+        const uint32_t* d = st_mask.put(masks, (size_t)n * words);
+        if (!d) return SA_ERR_NOMEM;
+        int rc = st_mask.flush(s);
+        if (rc) return rc;
+        SA_HIP(hipMemsetAsync(slot_mask, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        SA_HIP(hipMemcpyAsync(mask_table, d, (size_t)n * words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+        if (n_token_masks == 0) drop_graphs();              // only once the new table is on its way: a refused call changes nothing
+        n_token_masks = n;
+        return SA_OK;
+    }
+    // Mask ids of the slots about to be prefilled (-1 = unconstrained); a slot keeps its id until it is set again.
+    int set_slot_masks(const int32_t* slots, const int32_t* ids, int n, hipStream_t s) override {
+        if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
+        if (n > c.max_slots) return SA_ERR_ARG;
+        if (n_token_masks == 0) return SA_ERR_STATE;
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] < 0 || slots[i] >= c.max_slots || ids[i] < -1 || ids[i] >= n_token_masks) return SA_ERR_ARG;
+            if (seen[slots[i]]) return SA_ERR_ARG;          // a slot named twice: which id would win is a race in the scatter
+            seen[slots[i]] = 1;
+        }
+        st_mask.begin();
+        const int* ds = st_mask.put(slots, n);
+        const int* di = st_mask.put(ids, n);
+        if (!di) return SA_ERR_NOMEM;
+        int rc = st_mask.flush(s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(set_slot_masks_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, di, slot_mask, n);
+        return (int)hipGetLastError();
+    }
+
     // MXFP8 weight table of the decode steps: per layer SA_MX_COUNT pointers, then SA_MX_LM_W, SA_MX_LM_S. bf16 model only.
     int set_mx_weights(const void* const* tbl, int n) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return SA_ERR_UNSUPPORTED;
@@ -716,13 +797,19 @@ struct RecModel : RecBase {
                 MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
                 a.amax = am;
                 a.bias = W(SA_RW_LM_B);
-                if ((rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s))) return rc;
+                if (n_token_masks > 0) {
+                    a.tmask = token_mask(d_row_slot);
+                    if ((rc = launch_gemm_mx<MX_EPI_ARGMAX_MASK>(a, s))) return rc;
+                } else if ((rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s))) return rc;
                 bn_used = a.bn_used;
             }
         } else {
             GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
             a.amax = am;
-            if ((rc = launch_gemm<T, float, EPI_ARGMAX>(a, s))) return rc;
+            if (n_token_masks > 0) {
+                a.tmask = token_mask(d_row_slot);
+                if ((rc = launch_gemm<T, float, EPI_ARGMAX_MASK>(a, s))) return rc;
+            } else if ((rc = launch_gemm<T, float, EPI_ARGMAX>(a, s))) return rc;
             bn_used = a.bn_used;
         }
         const int tiles_n = cdiv(c.vocab, bn_used);
@@ -946,6 +1033,7 @@ struct RecModel : RecBase {
 
     // Test hook: the product path never materialises logits (EPI_ARGMAX above), so they are recomputed here from the
     // final-norm rows of the last prefill / decode step, which are still in `dlast`, with the same GEMM main loop.
+    // With token masks set these are still the UNMASKED logits: the mask lives in the greedy epilogues only.
     int copy_last_logits(float* dst, int max_rows, int* rows, hipStream_t s) override {
         const int r = std::min(max_rows, last_rows);
         *rows = r;

@@ -70,6 +70,7 @@ namespace sa {
 size_t rec_f16_workspace_bytes(const surya_rec_config& cfg);
 int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int n, std::unique_ptr<RecBase>& out);
 int rec_f16_ring_error(bool reset);
+int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, int* bn_used, hipStream_t s);
 // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
@@ -93,6 +94,24 @@ static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, 
         case EPI_RELU: return launch_gemm<TI, TO, EPI_RELU>(a, s);
     }
     return SA_ERR_ARG;
+}
+
+
+// surya_op_lm_head_partials: the lm_head launch of RecModel<T>::heads for the 16-bit / fp32 operand types built here
+template <typename T>
+static int op_lm_head_t(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, int* bn_used,
+                        hipStream_t s) {
+    GemmArgs<T, float> a{(const T*)X, (long)K, (const T*)W, (long)K, nullptr, (long)N, (const T*)bias, nullptr, 0, M, N, K};
+    a.amax = amax;
+    int rc;
+    if (tm) {
+        a.tmask = *tm;
+        rc = launch_gemm<T, float, EPI_ARGMAX_MASK>(a, s);
+    } else {
+        rc = launch_gemm<T, float, EPI_ARGMAX>(a, s);
+    }
+    *bn_used = a.bn_used;
+    return rc;
 }
 
 
@@ -201,6 +220,43 @@ int surya_rec_set_mx_weights(surya_rec* h, const void* const* table, int n) {
 int surya_rec_set_kv_fp8(surya_rec* h, int on) {
     if (!h) return SA_ERR_ARG;
     return h->impl->set_kv_fp8(on);
+}
+
+int surya_rec_set_token_masks(surya_rec* h, const uint32_t* masks, int n_masks, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_token_masks(masks, n_masks, (hipStream_t)stream);
+}
+int surya_rec_set_slot_masks(surya_rec* h, const int32_t* slots, const int32_t* mask_ids, int n, void* stream) {
+    if (!h || (n > 0 && (!slots || !mask_ids))) return SA_ERR_ARG;
+    return h->impl->set_slot_masks(slots, mask_ids, n, (hipStream_t)stream);
+}
+
+int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                              const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream) {
+    if (!X || !W || !amax || !bn_used || M <= 0 || N <= 0 || K <= 0 || (masks && !slot_mask)) return SA_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    const TokenMask tm{masks, slot_mask, row_slot, cdiv(N, 32)};
+    const TokenMask* tp = masks ? &tm : nullptr;
+    float4* am = reinterpret_cast<float4*>(amax);
+    if (dtype == SA_DTYPE_F32) return op_lm_head_t<float>(X, W, bias, M, N, K, tp, am, bn_used, s);
+    if (dtype == SA_DTYPE_BF16) return op_lm_head_t<bf16_t>(X, W, bias, M, N, K, tp, am, bn_used, s);
+    if (dtype == SA_DTYPE_F16) return sa::op_lm_head_f16(X, W, bias, M, N, K, tp, am, bn_used, s);
+    if (dtype == SA_OP_MXFP8) {
+        if (!SX || !SW) return SA_ERR_ARG;
+        MxArgs a{(const uint8_t*)X, (long)K, (const uint8_t*)SX, (const uint8_t*)W, (long)K, (const uint8_t*)SW, M, N, K, (long)M, (long)N};
+        a.amax = am;
+        a.bias = (const bf16_t*)bias;
+        int rc;
+        if (tp) {
+            a.tmask = tm;
+            rc = launch_gemm_mx<MX_EPI_ARGMAX_MASK>(a, s);
+        } else {
+            rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s);
+        }
+        *bn_used = a.bn_used;
+        return rc;
+    }
+    return SA_ERR_UNSUPPORTED;
 }
 
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,

@@ -35,6 +35,21 @@ int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int 
 }
 int rec_f16_ring_error(bool reset) { return ring_error(reset); }     // this unit's ring_error_word (gemm_ring.h)
 
+// the fp16 arm of surya_op_lm_head_partials (rec_model.hip): the lm_head launch of RecModel<fp16_t>::heads, masked (tm) or not
+int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, int* bn_used, hipStream_t s) {
+    GemmArgs<fp16_t, float> a{(const fp16_t*)X, (long)K, (const fp16_t*)W, (long)K, nullptr, (long)N, (const fp16_t*)bias, nullptr, 0, M, N, K};
+    a.amax = amax;
+    int rc;
+    if (tm) {
+        a.tmask = *tm;
+        rc = launch_gemm<fp16_t, float, EPI_ARGMAX_MASK>(a, s);
+    } else {
+        rc = launch_gemm<fp16_t, float, EPI_ARGMAX>(a, s);
+    }
+    *bn_used = a.bn_used;
+    return rc;
+}
+
 }  // namespace sa
 
 using namespace sa;

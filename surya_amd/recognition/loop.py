@@ -23,7 +23,12 @@ class DeviceLoop:
     False) or FEED_END. The loop polls it between decode calls and blocks on it only when it has nothing left to run, so lines
     can be admitted while their producer (the detector of a streamed detect -> recognise call) still works on later pages.
     Scheduling decisions never change a line's stream (slot / batch-composition invariance), so the result per line is the
-    one the closed list gives."""
+    one the closed list gives.
+
+    Constrained output: the dict handed to `run` may carry "token_masks" (uint32 [n, words], the call's distinct allowed-id sets,
+    uploaded once before the first prefill) and every admitted dict "mask_ids" (one row id per prompt, -1 = unconstrained). A line's
+    id stays with the line: it is set on whatever slot the line is prefilled into, so a slot that is reused takes its new line's id.
+    Without "token_masks" the model's mask entry points are never called."""
 
     def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None):
         self.model, self.eos, self.pad, self.nop, self.slots = model, eos, pad, nop, slots
@@ -44,6 +49,8 @@ class DeviceLoop:
         self.sc_mat = np.zeros((0, self.cap), np.float32)
         self.line_len, self.max_tok = np.zeros(0, np.int64), np.zeros(0, np.int64)      # tokens so far / token budget per line
         self.slot_line = np.full(slots, -1, np.int64)
+        self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
+        self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
@@ -80,6 +87,11 @@ class DeviceLoop:
         self.sc_mat = np.concatenate([self.sc_mat, np.zeros((m, self.cap), np.float32)])
         self.line_len = np.concatenate([self.line_len, np.zeros(m, np.int64)])
         self.max_tok = np.concatenate([self.max_tok, mt])
+        mk = d.get("mask_ids")
+        mk = np.full(m, -1, np.int64) if mk is None else np.asarray(mk, np.int64)
+        assert mk.shape == (m,) and int(mk.min()) >= -1 and int(mk.max()) < self.n_masks, \
+            "mask ids must name rows of the call's token-mask table"
+        self.line_mask = np.concatenate([self.line_mask, mk])
         self.queue.extend(range(base, base + m))
 
     def tiles_of(self, first_id, last_id):
@@ -188,6 +200,8 @@ class DeviceLoop:
             ntok += L_
         slots = empty[: len(take)]
         grids, prompt_ids = [self.grids[i] for i in take], [self.prompt_ids[i] for i in take]
+        if self.n_masks:
+            self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
         if look_ahead:
             for i in take:
                 assert ahead.popleft() == i
@@ -209,6 +223,17 @@ class DeviceLoop:
 
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
+        table = None if prep is None else prep.get("token_masks")
+        if table is None or len(table) == 0:
+            return self._run(prep)
+        self.model.set_token_masks(table)              # once per call: identical masks were merged by the caller
+        self.n_masks = len(table)
+        try:
+            return self._run(prep)
+        finally:
+            self.model.set_token_masks(None)           # the next call starts on the unmasked kernels
+
+    def _run(self, prep):
         if callable(getattr(self.model, "discard_ahead", None)):
             self.model.discard_ahead()                 # a previous loop that ended early (exception) must not poison this one
         if prep is not None:

@@ -66,6 +66,7 @@ class HipRecModel:
         self._score = np.zeros((L.SA_MAX_STEPS, max_slots), np.float32)
         self._bbox = np.zeros((L.SA_MAX_STEPS, max_slots, 6), np.int32)
         self.mx_weights = None
+        self.n_token_masks = 0
         self.decode_fp8 = False
         if decode_fp8 is None:
             from ..settings import settings
@@ -104,6 +105,30 @@ class HipRecModel:
             raise ValueError("the fp8 KV cache exists for bfloat16 models only")
         L.check(self.lib.surya_rec_set_kv_fp8(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_kv_fp8")
         self.kv_fp8 = bool(on)
+
+    def set_token_masks(self, masks):
+        """The call's allowed-id sets (surya_rec_set_token_masks): uint32 [n_masks, ceil(vocab / 32)], bit (c & 31) of word (c >> 5) set =
+        id c allowed (OCRTokenizer.token_mask builds a row). None or an empty table switches back to the unmasked lm_head kernels. A new
+        table sets every slot back to unconstrained; set_slot_masks names the rows of the slots about to be prefilled."""
+        words = (self.vocab + 31) // 32
+        if masks is None or len(masks) == 0:
+            L.check(self.lib.surya_rec_set_token_masks(self.handle, None, C.c_int(0), self._stream), "surya_rec_set_token_masks")
+            self.n_token_masks = 0
+            return
+        m = np.ascontiguousarray(np.asarray(masks, np.uint32))
+        if m.ndim != 2 or m.shape[1] != words:
+            raise ValueError(f"token masks must be [n, {words}] uint32 for a vocabulary of {self.vocab}, got {m.shape}")
+        L.check(self.lib.surya_rec_set_token_masks(self.handle, L.np_ptr(m, C.c_uint32), C.c_int(m.shape[0]), self._stream),
+                "surya_rec_set_token_masks")
+        self.n_token_masks = int(m.shape[0])
+
+    def set_slot_masks(self, slots, mask_ids):
+        """Mask id (row of the table, -1 = unconstrained) of the slots about to be prefilled; a slot keeps it until it is set again."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int32))
+        m = np.ascontiguousarray(np.asarray(mask_ids, np.int32))
+        assert s.shape == m.shape and s.ndim == 1
+        L.check(self.lib.surya_rec_set_slot_masks(self.handle, L.np_ptr(s), L.np_ptr(m), C.c_int(len(s)), self._stream),
+                "surya_rec_set_slot_masks")
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -211,6 +236,7 @@ class HipRecModel:
         return out
 
     def last_logits(self) -> torch.Tensor:
+        """fp32 logits of the last prefill / decode step, recomputed; with token masks set these are still the UNMASKED logits."""
         buf = torch.empty((self.max_slots, self.vocab), dtype=torch.float32, device=self.device)
         rows = C.c_int(0)
         L.check(self.lib.surya_rec_copy_last_logits(self.handle, L.ptr(buf), C.c_int(self.max_slots), C.byref(rows),

@@ -99,6 +99,56 @@ def inputs_fingerprint(shapes, chunks) -> list:
     return [len(shapes), zlib.crc32(shapes.tobytes()), zlib.crc32(b"".join(chunks))]
 
 
+def per_image_lists(arg, name, n_images) -> list:
+    """An `allowlist` / `blocklist` argument as one entry per image: None, a str, or a list with one None / str per line."""
+    if arg is None or isinstance(arg, str):
+        return [arg] * n_images
+    if not isinstance(arg, (list, tuple)):
+        raise TypeError(f"{name} must be a str or a list with one entry per image, got {type(arg).__name__}")
+    if len(arg) != n_images:
+        raise ValueError(f"{name} has {len(arg)} entries for {n_images} images")
+    for e in arg:
+        if e is None or isinstance(e, str):
+            continue
+        if not isinstance(e, (list, tuple)) or not all(x is None or isinstance(x, str) for x in e):
+            raise TypeError(f"an entry of {name} is None, a str, or a list of None / str per line")
+    return list(arg)
+
+
+class LineConstraints:
+    """The allowlist / blocklist arguments of one call, resolved: `table` holds the call's distinct token masks (MaskTable: identical
+    sets are merged), `per_image[i]` the mask id of every line of image i (an int) or one id per line (a list). `lines_known` is False
+    on the detector paths, where the per-line form cannot be matched to lines that do not exist yet."""
+
+    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None):
+        from .tokenizer import MaskTable
+        self.table = MaskTable(tokenizer, vocab_size, limit)
+        allow, block = per_image_lists(allowlist, "allowlist", n_images), per_image_lists(blocklist, "blocklist", n_images)
+        self.per_image = []
+        for i, (a, b) in enumerate(zip(allow, block)):
+            if not isinstance(a, (list, tuple)) and not isinstance(b, (list, tuple)):
+                self.per_image.append(self.table.id_for(a, b))
+                continue
+            if line_counts is None:
+                raise ValueError("a per-line allowlist / blocklist needs bboxes or polygons: with det_predictor the lines are not known yet")
+            n = line_counts[i]
+            a = list(a) if isinstance(a, (list, tuple)) else [a] * n
+            b = list(b) if isinstance(b, (list, tuple)) else [b] * n
+            if len(a) != n or len(b) != n:
+                raise ValueError(f"image {i} has {n} lines but its allowlist / blocklist entry has {len(a)} / {len(b)}")
+            self.per_image.append([self.table.id_for(x, y) for x, y in zip(a, b)])
+
+    def __bool__(self):
+        return len(self.table) > 0
+
+    def line_ids(self, slice_map) -> list:
+        """One id per line, in page order, for pages of slice_map[i] lines."""
+        out = []
+        for ids, n in zip(self.per_image, slice_map):
+            out.extend(ids if isinstance(ids, list) else [ids] * n)
+        return out
+
+
 class AssemblyHandover(ThreadPoolExecutor):
     """One call's assembly worker. Output assembly is host work of the same order as the device loop itself; it runs on one worker
     thread WHILE the device decodes the next lines: the lines that stopped at a synchronisation point (`on_done` each, then `on_flush`)
@@ -302,8 +352,11 @@ class RecognitionPredictor(BasePredictor):
             tiles, tile_offs, grids, prompt_ids = self.preprocess_prompts_device(prompts, flat.get("pages", []))
         else:
             tiles, tile_offs, grids, prompt_ids = self.preprocess_prompts(prompts)
-        return {"prompts": prompts, "max_tokens": max_tokens, "tiles": tiles, "tile_offs": tile_offs, "grids": grids,
+        prep = {"prompts": prompts, "max_tokens": max_tokens, "tiles": tiles, "tile_offs": tile_offs, "grids": grids,
                 "prompt_ids": prompt_ids}
+        if flat.get("token_masks") is not None:               # constrained output: the call's mask table and one row id per line
+            prep.update(token_masks=flat["token_masks"], mask_ids=flat["mask_ids"])
+        return prep
 
     def generate(self, prep: dict | None, recognition_batch_size: int | None = None, on_done=None, on_flush=None, feed=None) -> tuple:
         """Device half: one DeviceLoop (loop.py, which documents on_done / on_flush / feed) run until every line stopped (reference
@@ -351,6 +404,8 @@ class RecognitionPredictor(BasePredictor):
         local = {k: [flat[k][i] for i in mine] for k in ("slices", "input_text", "task_names")}
         if "pages" in flat:
             local["pages"] = flat["pages"]
+        if flat.get("token_masks") is not None:               # every rank holds the whole table; the ids travel with the lines
+            local.update(token_masks=flat["token_masks"], mask_ids=[flat["mask_ids"][i] for i in mine])
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
         if mine:
             self.last_packed = None                          # only what generate() sets DURING this call counts (a stand-in prediction_loop
@@ -397,14 +452,35 @@ class RecognitionPredictor(BasePredictor):
                  highres_images: List[Image.Image] | None = None, bboxes: List[List[List[int]]] | None = None,
                  polygons: List[List[List[List[int]]]] | None = None, input_text: List[List[str | None]] | None = None,
                  sort_lines: bool = False, math_mode: bool = True, return_words: bool = False,
-                 drop_repeated_text: bool = False) -> List[OCRResult]:
+                 drop_repeated_text: bool = False, allowlist=None, blocklist=None) -> List[OCRResult]:
+        """`allowlist` / `blocklist` (not in the reference; keywords after its own arguments) restrict the characters a line may
+        contain -- "0123456789.,-" for a numeric column. Each is a str for every line of the call, or a list with one entry per image:
+        None, a str, or a list with one None / str per bbox / polygon of that image (not with det_predictor: the lines are not known
+        yet). A line takes one of the two, not both. Tokens and confidences are the reference's process_outputs on logits whose
+        disallowed ids are -inf, so a confidence is the softmax over the allowed set; EOS, pad and no-output stay allowed, formatting and
+        math tags do not under an allowlist (OCRTokenizer.token_mask). Stop rules, sorting and assembly are unchanged."""
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
+            # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
+            lists = {} if allowlist is None and blocklist is None else {"allowlist": allowlist, "blocklist": blocklist}
             return self._call(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                              bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text)
+                              bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
+
+    def _constraints(self, allowlist, blocklist, images, bboxes, polygons):
+        """The call's LineConstraints, or None for a call without lists (or whose lists are all None)."""
+        if allowlist is None and blocklist is None:
+            return None
+        given = polygons if polygons is not None else bboxes
+        if given is not None and len(given) != len(images):
+            raise ValueError("You need to pass in one list of bboxes / polygons for each image")
+        counts = None if given is None else [len(g) for g in given]
+        from .. import _lib as L
+        cons = LineConstraints(self.processor.ocr_tokenizer, allowlist, blocklist, len(images), counts,
+                               vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS)
+        return cons if cons else None
 
     def _call(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images, bboxes,
-              polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text) -> List[OCRResult]:
+              polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None) -> List[OCRResult]:
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         allowed = self.tasks.keys()
@@ -419,6 +495,7 @@ class RecognitionPredictor(BasePredictor):
         if highres_images is not None:
             assert len(images) == len(highres_images), "You need to pass in one highres image for each image"
         highres_images = convert_if_not_rgb(highres_images) if highres_images is not None else [None] * len(images)
+        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons)
 
         if bboxes is None and polygons is None:
             assert det_predictor is not None, (
@@ -426,11 +503,12 @@ class RecognitionPredictor(BasePredictor):
             if self.shard_pages:
                 from .. import dist as sdist
                 if sdist.collectives_on(self.process_group):
+                    lists = {} if cons is None else {"allowlist": allowlist, "blocklist": blocklist}
                     return self._call_page_sharded(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
-                                                   highres_images, sort_lines, math_mode, return_words, drop_repeated_text)
+                                                   highres_images, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
             if self._can_stream(det_predictor):
                 return self._call_streamed(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
-                                           highres_images, sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call)
+                                           highres_images, sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call, cons=cons)
             flat = self.detect_and_slice_bboxes(images, task_names, det_predictor, detection_batch_size, highres_images)
         else:
             if bboxes is not None:
@@ -441,11 +519,15 @@ class RecognitionPredictor(BasePredictor):
         if len(flat["slices"]) == 0:
             return []
         stamps["slice_ms"] = (time.perf_counter() - t_call) * 1e3
+        sorted_keys = ("slices", "input_text", "task_names")
+        if cons is not None:                                  # by line id like the slices: sorted with them below
+            flat["token_masks"], flat["mask_ids"] = cons.table.array(), cons.line_ids(flat["slice_map"])
+            sorted_keys += ("mask_ids",)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
         order = sorted(range(len(flat["slices"])), key=lambda i: -flat["slices"][i].shape[1])
-        for key in ("slices", "input_text", "task_names"):
+        for key in sorted_keys:
             flat[key] = [flat[key][i] for i in order]
 
         with AssemblyHandover(self, flat, order, drop_repeated_text, return_words) as hand:
@@ -481,7 +563,7 @@ class RecognitionPredictor(BasePredictor):
     gather_page_results: bool = True
 
     def _call_page_sharded(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                           sort_lines, math_mode, return_words, drop_repeated_text) -> list:
+                           sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None) -> list:
         from .. import dist as sdist
         group = self.process_group
         rank, world = sdist.world_info(group)
@@ -495,11 +577,15 @@ class RecognitionPredictor(BasePredictor):
         self.shard_pages = self.shard_lines = False
         if hasattr(det_predictor, "shard_pages"):
             det_predictor.shard_pages = False
+        lists = {}                                            # a call without lists reaches the rank's own call exactly as it always did
+        if allowlist is not None or blocklist is not None:
+            lists = {"allowlist": [per_image_lists(allowlist, "allowlist", n)[i] for i in mine],
+                     "blocklist": [per_image_lists(blocklist, "blocklist", n)[i] for i in mine]}
         try:
             hr = [highres_images[i] for i in mine]
             local = self._call([images[i] for i in mine], [task_names[i] for i in mine], det_predictor, detection_batch_size,
                                recognition_batch_size, hr if any(h is not None for h in hr) else None,
-                               None, None, None, sort_lines, math_mode, return_words, drop_repeated_text) if mine else []
+                               None, None, None, sort_lines, math_mode, return_words, drop_repeated_text, **lists) if mine else []
         finally:
             self.shard_pages, self.shard_lines = saved[0], saved[1]
             if hasattr(det_predictor, "shard_pages"):
@@ -549,7 +635,7 @@ class RecognitionPredictor(BasePredictor):
                 and type(det_predictor)._iter_detect_device is DetectionPredictor._iter_detect_device
                 and det_predictor.device_postprocess and not det_predictor.shard_pages)
     def _call_streamed(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                       sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call) -> List[OCRResult]:
+                       sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call, cons=None) -> List[OCRResult]:
         import queue
         import sys
         import threading
@@ -568,7 +654,7 @@ class RecognitionPredictor(BasePredictor):
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
-                    pages, refs, polys_all, scales_all, tasks_all = [], [], [], [], []
+                    pages, refs, polys_all, scales_all, tasks_all, masks_all = [], [], [], [], [], []
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
@@ -576,6 +662,8 @@ class RecognitionPredictor(BasePredictor):
                         polys_all.extend(polygons)
                         scales_all.extend([scale] * len(polygons))
                         tasks_all.extend([task_names[page]] * len(polygons))
+                        if cons is not None:                  # (per-call and per-image lists only: one id per page)
+                            masks_all.extend([cons.per_image[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -594,7 +682,8 @@ class RecognitionPredictor(BasePredictor):
                     flat["input_text"].extend([None] * len(order))
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
-                           "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts}})
+                           "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts},
+                           "mask_ids": [masks_all[i] for i in order] if cons is not None else None})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -619,8 +708,10 @@ class RecognitionPredictor(BasePredictor):
                 t0 = time.perf_counter()
                 producer.start()
                 try:
-                    self.generate({"prompts": [], "max_tokens": {}, "overall_max_tokens": overall_max_tokens}, recognition_batch_size,
-                                  on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
+                    first = {"prompts": [], "max_tokens": {}, "overall_max_tokens": overall_max_tokens}
+                    if cons is not None:
+                        first["token_masks"] = cons.table.array()      # the whole call's table up front: chunks carry row ids only
+                    self.generate(first, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...
                     producer.join(timeout=30.0)        # ... and is waited for: it launches detector and pre-processing work on this predictor's

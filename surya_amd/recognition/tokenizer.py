@@ -11,6 +11,8 @@ import html
 import re
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
+
 from .schema import TaskNames, TASK_NAMES
 
 DEFAULT_SPECIAL_TOKENS: Dict[str, List[str]] = {
@@ -73,6 +75,43 @@ class OCRTokenizer:
     @property
     def vocab_size(self) -> int:
         return self.special_token_offset + 65536
+
+    # ---------------------------------------------------------------------------------- constrained output
+    ALWAYS_ALLOWED = ("</S>", "<PAD>", "<NOP>")      # a constrained line must still be able to stop, pad or say "no output"
+
+    @staticmethod
+    def _units(chars: str) -> List[int]:
+        """UTF-16 code units of the characters of `chars` (a non-BMP character has two: its surrogates)."""
+        raw = chars.encode("utf-16le", errors="surrogatepass")
+        return [raw[i] + (raw[i + 1] << 8) for i in range(0, len(raw), 2)]
+
+    def token_mask(self, allow: Optional[str] = None, block: Optional[str] = None, vocab_size: Optional[int] = None) -> np.ndarray:
+        """Allowed-id set as uint32 words over `vocab_size` ids (default: this tokenizer's; a model may pad its vocabulary): bit (c & 31) of
+        word (c >> 5) set = id c may be emitted. The format of HipRecModel.set_token_masks / surya_rec_set_token_masks.
+
+        allow: an id is allowed iff it is the UTF-16 code unit of one of the characters (special_token_offset + unit), or EOS, pad or the
+        no-output token, which are always allowed. Nothing else: no formatting or math tags, no math-BPE ids. A character outside the BMP
+        allows BOTH of its surrogates, each by itself: this OVER-permits (any allowed high surrogate may pair with any allowed low one).
+        block: every id is allowed except the code units of the characters (the three ids above cannot be blocked). A character outside the
+        BMP raises ValueError: blocking its surrogates would block every character that shares one.
+        Exactly one of the two is given."""
+        if (allow is None) == (block is None):
+            raise ValueError("token_mask takes exactly one of allow / block")
+        if not isinstance(allow if allow is not None else block, str):
+            raise TypeError("an allowlist / blocklist is a str of characters")
+        V = self.vocab_size if vocab_size is None else int(vocab_size)
+        bits = np.zeros(((V + 31) // 32) * 32, bool)
+        if allow is not None:
+            ids = [self.special_token_offset + u for u in self._units(allow)]
+        else:
+            if any(ord(ch) > 0xFFFF for ch in block):
+                raise ValueError("a blocklist takes characters of the Basic Multilingual Plane only (a surrogate is shared by 1024 characters)")
+            bits[:V] = True
+            ids = [self.special_token_offset + u for u in self._units(block)]
+        ids = [i for i in ids if i < V]
+        bits[ids] = allow is not None
+        bits[[self.SPECIAL_TOKEN_MAPPING[t] for t in self.ALWAYS_ALLOWED if t in self.SPECIAL_TOKEN_MAPPING]] = True
+        return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
 
     # --------------------------------------------------------------------------------------------- encode
     def _tokenize_ocr(self, text: str) -> List[int]:
@@ -169,3 +208,38 @@ class OCRTokenizer:
         if task in (TaskNames.ocr_with_boxes, TaskNames.ocr_without_boxes):
             return self._decode_ocr(token_ids)
         return self.math_tokenizer.decode(token_ids)
+
+
+class MaskTable:
+    """The distinct token masks of one call and the id of each: identical masks (the same allowed set, however it was written) are
+    stored -- and uploaded -- once. `id_for(None, None)` is -1, the unconstrained line."""
+
+    def __init__(self, tokenizer: OCRTokenizer, vocab_size: Optional[int] = None, limit: Optional[int] = None):
+        self.tokenizer, self.vocab_size, self.limit = tokenizer, vocab_size, limit
+        self.rows: List[np.ndarray] = []
+        self._by_bytes: Dict[bytes, int] = {}
+        self._by_spec: Dict[tuple, int] = {}
+
+    def id_for(self, allow: Optional[str] = None, block: Optional[str] = None) -> int:
+        if allow is None and block is None:
+            return -1
+        if allow is not None and block is not None:
+            raise ValueError("a line takes an allowlist or a blocklist, not both")
+        spec = (allow, block)
+        if spec not in self._by_spec:
+            m = self.tokenizer.token_mask(allow, block, self.vocab_size)
+            key = m.tobytes()
+            if key not in self._by_bytes:
+                if self.limit is not None and len(self.rows) >= self.limit:
+                    raise ValueError(f"more than {self.limit} distinct allowlists / blocklists in one call")
+                self._by_bytes[key] = len(self.rows)
+                self.rows.append(m)
+            self._by_spec[spec] = self._by_bytes[key]
+        return self._by_spec[spec]
+
+    def __len__(self):
+        return len(self.rows)
+
+    def array(self) -> np.ndarray:
+        """uint32 [n_masks, words]."""
+        return np.stack(self.rows) if self.rows else np.zeros((0, 0), np.uint32)

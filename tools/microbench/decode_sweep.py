@@ -5,13 +5,17 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
 `mxbigm` (with --fp8 --slots 512 / 1024): the MXFP8 tiles above 256 rows (mx_big_m_split x mx_big_m_gateup), arm 0 = everything
 64 x 64 run twice, the default twice, and the bf16 default of the same build as the last arm. Tokens are compared with the first
 arm of the same arithmetic (fp8 with fp8, bf16 with bf16).
+
+`masks`: the unmasked step against the step with a token mask on EVERY slot (HipRecModel.set_token_masks: the masked lm_head
+epilogues), arms alternating none / digits allowlist / none / random 50 % mask / none. Tokens are compared with the first arm of the
+same mask. `maskonly`: the digits arm alone.
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -82,6 +86,10 @@ def main():
         variants = [dict(mx_big_m_split=0, mx_big_m_gateup=0), dict()]
         variants += [dict(mx_big_m_split=sp, mx_big_m_gateup=gu) for gu in (0, 1, 2) for sp in (0, 2, 3) if (sp, gu) != (0, 0)]
         variants += [dict(mx_big_m_split=0, mx_big_m_gateup=0), dict(), dict(fp8=0)]
+    elif args.configs == "masks":        # constrained output: a mask on every slot against none, alternating
+        variants = [dict(), dict(masks=1), dict(), dict(masks=2), dict()]
+    elif args.configs == "maskonly":     # one arm, a digits allowlist on every slot (for a kernel trace beside `base`)
+        variants = [dict(masks=1)]
     elif args.configs == "pf":           # K/V prefetch workgroups in the reduce kernels, on / off, interleaved
         variants = [dict(kvprefetch=1), dict(), dict(kvprefetch=1), dict(), dict(lmhead=2, kvprefetch=1), dict(lmhead=2)]
     elif args.configs == "fp8only":
@@ -112,20 +120,40 @@ def main():
         torch.cuda.synchronize()
         return e0.elapsed_time(e1) * 1e3 / n_steps, (time.perf_counter() - t0) * 1e6 / n_steps, np.concatenate(toks)
 
+    def set_masks(kind):                         # 0 = off, 1 = digits allowlist, 2 = a random half of the vocabulary (+ the control ids)
+        if not kind:
+            return m.set_token_masks(None)
+        from surya_amd.recognition.loader import RecognitionModelLoader
+        tk = RecognitionModelLoader({"config": cfg, "state_dict": {}}).processor().ocr_tokenizer
+        V = cfg.decoder.vocab_size
+        mask = tk.token_mask(allow="0123456789.,-", vocab_size=V)
+        if kind == 2:
+            mask = mask | np.random.default_rng(7).integers(0, 2 ** 32, size=mask.shape, dtype=np.uint32)
+            mask[-1] &= np.uint32((1 << (V - 32 * (len(mask) - 1))) - 1) if V % 32 else np.uint32(0xFFFFFFFF)
+        m.set_token_masks(mask[None])
+        m.set_slot_masks(slots, [0] * n)
+
     ref = {}
     print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == first arm of the same arithmetic")
     for v in variants:
         v = dict(v)
         m.set_decode_fp8(bool(v.pop("fp8", int(args.fp8))))
+        masks = v.pop("masks", 0)
+        if masks or args.configs in ("masks", "maskonly"):
+            set_masks(masks)
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
+        if args.configs in ("masks", "maskonly"):
+            v["masks"] = masks
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        same = float((best[2] == ref.setdefault(v["fp8"], best[2])).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0)), best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
+    if args.configs in ("masks", "maskonly"):
+        m.set_token_masks(None)
 
 
 if __name__ == "__main__":
