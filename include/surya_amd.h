@@ -233,6 +233,26 @@ int surya_rec_set_kv_fp8(surya_rec* h, int on);
 int surya_rec_set_token_masks(surya_rec* h, const uint32_t* masks, int n_masks, void* stream);
 int surya_rec_set_slot_masks(surya_rec* h, const int32_t* slots, const int32_t* mask_ids, int n, void* stream);
 
+/* Alternatives: the SA_MAX_ALTERNATIVES most likely tokens of every step with their probabilities, i.e. what a caller of the reference gets
+ * from a stable descending sort of softmax(next_token_logits) inside process_outputs (ties: lower id first). Logits never exist outside a
+ * tile here, and a greedy partial keeps only its tile's winner, so the candidates are collected where the partials are: the lm_head's *_TOPK
+ * epilogues write each tile's four best allowed columns beside its partial, and a small kernel behind the greedy head picks the row's four
+ * best and divides by the head's own max and total (entry 0 is the emitted token, and its probability has the bits of the emitted score on
+ * rows that go on; a row that chose eos / pad keeps score 0 and still reports its alternatives). With token masks set the alternatives
+ * are the best ALLOWED tokens and the probabilities are over the allowed set. Tokens, scores, boxes and the next step's input do not change.
+ *   set_alternatives: on = 0 / 1, anything else SA_ERR_ARG. The first switch-on allocates the candidate and output arrays (and their pinned
+ *                mirror); a handle that never switches it on allocates nothing and launches exactly what it launched before this entry
+ *                existed. Addresses never change afterwards. Switching drops captured decode steps, as surya_rec_set_token_masks does.
+ *                Call while no line is in flight.
+ *   read_alternatives / wait_alternatives: tokens [n_steps][max_slots][SA_MAX_ALTERNATIVES] int32 (-1 where fewer ids are allowed) and probs
+ *                (0 there) of the steps surya_rec_read_outputs / surya_rec_wait_outputs return, same indexing, best first;
+ *                surya_rec_decode_async mirrors the ring half behind the same event. SA_ERR_STATE while the feature is off, and from
+ *                wait_alternatives for a ring half whose decode_async ran while it was off. */
+#define SA_MAX_ALTERNATIVES 4
+int surya_rec_set_alternatives(surya_rec* h, int on);
+int surya_rec_read_alternatives(surya_rec* h, int n_steps, int32_t* tokens, float* probs, void* stream);
+int surya_rec_wait_alternatives(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* probs);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -308,6 +328,16 @@ int surya_op_mx_quantize(const float* x, int rows, int K, uint8_t* q, uint8_t* s
 #define SA_OP_MXFP8 3
 int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
                               const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream);
+/* surya_op_lm_head_partials with the *_TOPK epilogue (same launchers, same arguments; masks = NULL: unconstrained, through the same kernel):
+ * alt receives beside amax the tile's four best allowed columns inside N, alt[((m * tiles + tile) * 4 + j) * 2] = {float value, int32 column
+ * bits}, value descending, column ascending among equal values, (-inf, 0x7fffffff) for missing entries; entry 0 is (max, argmax) of the
+ * partial. With top_tokens / top_probs [M][4] (both or neither; DEVICE) it also runs the greedy head's reduction over the partials and the
+ * combine kernel of the engine: head_token [M] int32 and head_score [M] float (DEVICE, required then) receive the head's token and
+ * 1 / total (indexed by slot, like top_tokens / top_probs; row_slot = NULL: row m), scratch [16 * M + 16] float is working memory.
+ * Enqueue only. */
+int surya_op_lm_head_topk(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                          const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, float* alt, int* bn_used,
+                          int32_t* top_tokens, float* top_probs, int32_t* head_token, float* head_score, float* scratch, void* stream);
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream);
 

@@ -12,6 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.so")   # env: A/B builds of the kernels
 
 SA_MAX_STEPS = 16
+SA_MAX_ALTERNATIVES = 4                         # alternatives per token (surya_rec_set_alternatives); top_k < 4 is a slice on the host
 SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
 OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
@@ -104,6 +105,12 @@ def _bind_lay_ops(lib):
     lib.surya_rec_set_token_masks.argtypes, lib.surya_rec_set_token_masks.restype = [p, C.POINTER(C.c_uint32), i, p], C.c_int
     lib.surya_rec_set_slot_masks.argtypes, lib.surya_rec_set_slot_masks.restype = [p, ip, ip, i, p], C.c_int
     lib.surya_op_lm_head_partials.argtypes, lib.surya_op_lm_head_partials.restype = [i, p, p, p, p, p, i, i, i, p, p, p, p, ip, p], C.c_int
+    # alternatives (the k most likely tokens of every step) and the *_TOPK lm_head launch by itself
+    lib.surya_rec_set_alternatives.argtypes, lib.surya_rec_set_alternatives.restype = [p, i], C.c_int
+    lib.surya_rec_read_alternatives.argtypes, lib.surya_rec_read_alternatives.restype = [p, i, ip, C.POINTER(C.c_float), p], C.c_int
+    lib.surya_rec_wait_alternatives.argtypes, lib.surya_rec_wait_alternatives.restype = [p, i, i, ip, C.POINTER(C.c_float)], C.c_int
+    lib.surya_op_lm_head_topk.argtypes = [i, p, p, p, p, p, i, i, i, p, p, p, p, p, ip, p, p, p, p, p, p]
+    lib.surya_op_lm_head_topk.restype = C.c_int
 
 
 def check(rc: int, what: str):

@@ -387,6 +387,29 @@ struct AttrOnce {
     }
 };
 
+// Alternatives (SA_MAX_ALTERNATIVES of surya_amd.h; EPI_TOPK in gemm.h, MX_EPI_TOPK in gemm_mx.h, topk_combine_kernel in kernels.h). A candidate is {logit, bits of its column}; the
+// order everywhere is value descending, column ascending among equal values -- the order whose first element the greedy partials pick
+// (strict > over ascending columns). A missing candidate is (-inf, 0x7fffffff): it sorts last and nothing comes after it. -inf is never a
+// candidate's value: that is how a disallowed column and a column past N look after masking.
+constexpr int SA_ALT_NONE = 0x7fffffff;
+// (v, c) comes strictly after (pv, pc)
+__device__ __forceinline__ bool alt_after(float v, int c, float pv, int pc) { return (v < pv) | ((v == pv) & (c > pc)); }     // (| and &: selects, not branches)
+// (v, c) comes before (bv, bc)
+__device__ __forceinline__ bool alt_before(float v, int c, float bv, int bc) { return (v > bv) | ((v == bv) & (c < bc)); }
+// the best of `n` candidates that comes strictly after (pv, pc)
+__device__ __forceinline__ float2 alt_next(const float2* cand, int n, float pv, int pc) {
+    float cb = -INFINITY;
+    int ci = SA_ALT_NONE;
+    for (int k = 0; k < n; ++k) {
+        const float v = cand[k].x;
+        const int cc = __float_as_int(cand[k].y);
+        const bool take = (v > -INFINITY) & alt_after(v, cc, pv, pc) & alt_before(v, cc, cb, ci);
+        cb = take ? v : cb;
+        ci = take ? cc : ci;
+    }
+    return make_float2(cb, __int_as_float(ci));
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline long cdivl(long a, long b) { return (a + b - 1) / b; }
 

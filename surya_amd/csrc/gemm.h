@@ -36,8 +36,10 @@ namespace sa {
 
 enum GemmEpi { EPI_BIAS = 0, EPI_RESIDUAL = 1, EPI_GELU = 2, EPI_SWIGLU = 3, EPI_HARDSWISH = 4, EPI_RELU = 5, EPI_ARGMAX = 6, EPI_ROPE = 7,
                EPI_GEGLU = 8 /* gelu_tanh(gate) * up, rows interleaved like SWIGLU (ADETR decoder MLP, adetr/decoder.py:331-344) */,
-               EPI_ARGMAX_MASK = 9 /* EPI_ARGMAX over the columns a per-row token mask allows (TokenMask below) */ };
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_MASK; }
+               EPI_ARGMAX_MASK = 9 /* EPI_ARGMAX over the columns a per-row token mask allows (TokenMask below) */,
+               EPI_TOPK = 10 /* EPI_ARGMAX_MASK (an absent table = unconstrained) + the tile's SA_MAX_ALTERNATIVES best allowed columns */ };
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_MASK || epi == EPI_TOPK; }
+constexpr bool epi_is_masked(int epi) { return epi == EPI_ARGMAX_MASK || epi == EPI_TOPK; }
 
 // Allowed-column sets of the greedy-partial epilogues (EPI_ARGMAX_MASK here, MX_EPI_ARGMAX_MASK in gemm_mx.h). Row m of the GEMM belongs
 // to slot row_slot[m] (the map the greedy head receives: the prefilled sequences' slots, or the active list of a decode step), a slot names
@@ -59,6 +61,11 @@ struct TokenMask {
         const uint32_t v = table[(long)max(mid, 0) * words + min(w, words - 1)];
         return mid < 0 ? 0xffffffffu : v;
     }
+    // The *_TOPK epilogues always carry a TokenMask; there an absent table means what slot id -1 means, and nothing is dereferenced
+    __device__ __forceinline__ int id_or_none(int m, int M) const { return table ? id_of(m, M) : -1; }
+    __device__ __forceinline__ uint32_t word_or_all(int mid, int w) const {
+        return mid < 0 ? 0xffffffffu : table[(long)mid * words + min(w, words - 1)];
+    }
 };
 
 template <typename TI, typename TO>
@@ -77,7 +84,10 @@ struct GemmArgs {
     // per (row, tile column) goes to amax[m * cdiv(N, bn_used) + tile_n]; the launcher reports the tile width it chose.
     float4* amax = nullptr;
     mutable int bn_used = 0;
-    TokenMask tmask;             // EPI_ARGMAX_MASK
+    TokenMask tmask;             // EPI_ARGMAX_MASK, EPI_TOPK
+    // EPI_TOPK: beside amax, the tile's SA_MAX_ALTERNATIVES best allowed columns inside N as {value, column bits}, best first, at
+    // alt[(m * cdiv(N, bn_used) + tile_n) * 4 + j]; entry 0 is (max, argmax) of the amax partial, missing entries are (-inf, 0x7fffffff)
+    float2* alt = nullptr;
     // EPI_ROPE (vision qkv projection): rotary embedding of the q and k columns (n < rope_cols) in the epilogue. The weight
     // rows of every head are stored PAIR-INTERLEAVED (new column 2j = old j, 2j + 1 = old j + D/2), so the lane that owns
     // four consecutive columns holds two complete rotate_half pairs; rope[m * (D/2) + j] = (cos, sin) of token m, pair j.
@@ -175,6 +185,91 @@ __device__ __forceinline__ void argmax_partial_masked(const unsigned char* smem,
 #pragma unroll
     for (int o = 1; o < TPR; o <<= 1) se += __shfl_xor(se, o, 64);
     if (part == 0 && m0 + row < M) amax[(long)(m0 + row) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
+}
+
+// argmax_partial_masked plus the tile's four best allowed columns (EPI_TOPK / MX_EPI_TOPK). The amax record is computed by the same
+// statements in the same order, so it has the masked epilogue's bits (the unmasked one's with no table or slot id -1). Alternatives: pass t
+// takes the best (value, column) strictly after pass t - 1's winner; a thread scans its own columns (ascending, strict >: the first of equal
+// values), the TPR threads of a row meet in a butterfly after which all of them hold the winner. No state beyond the previous winner.
+template <int BM, int NT, int CPR, int XM>
+__device__ __forceinline__ void topk_partial_masked(const unsigned char* smem, const TokenMask& tm, int m0, int n0, int M, int N,
+                                                    float4* amax, float2* alt, int tiles_n, int tile_n) {
+    constexpr int TPR = NT / BM, SEG = CPR / TPR, ROWB = CPR * 16, NWD = (SEG * 4 + 31) / 32;
+    static_assert(NT % BM == 0 && (TPR & (TPR - 1)) == 0 && TPR <= 8 && CPR % TPR == 0, "argmax epilogue split");
+    static_assert(SEG * 4 >= 32 ? (SEG * 4) % 32 == 0 : 32 % (SEG * 4) == 0, "a thread's columns: whole mask words, or a part of one");
+    const int tid = threadIdx.x, row = tid / TPR, part = tid % TPR;
+    const int nbeg = n0 + part * SEG * 4;
+    uint32_t mw[NWD];
+    const int mid = tm.id_or_none(m0 + row, M);
+#pragma unroll
+    for (int k = 0; k < NWD; ++k) mw[k] = tm.word_or_all(mid, (nbeg >> 5) + k);
+    const unsigned char* rowp = smem + row * ROWB;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+        const uint32_t bits = mw[(cc * 4) >> 5] >> (n & 31);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N && ((bits >> i) & 1u) && v[i] > best) { best = v[i]; bi = n + i; }
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    float se = 0.f;
+#pragma unroll
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+        const uint32_t bits = mw[(cc * 4) >> 5] >> (n & 31);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N && ((bits >> i) & 1u)) se += expf(v[i] - best);
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) se += __shfl_xor(se, o, 64);
+    const bool writer = part == 0 && m0 + row < M;
+    if (writer) amax[(long)(m0 + row) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
+    float2* arow = alt + ((long)(m0 + row) * tiles_n + tile_n) * SA_MAX_ALTERNATIVES;
+    if (writer) arow[0] = make_float2(best, __int_as_float(bi));
+    float pv = best;
+    int pc = bi;
+#pragma unroll 1
+    for (int t = 1; t < SA_MAX_ALTERNATIVES; ++t) {
+        float cb = -INFINITY;
+        int ci = SA_ALT_NONE;
+        // (a rolled loop over the chunks: unrolled, the compiler keeps the thread's SEG * 4 staged values in registers across the passes --
+        // 64 more VGPRs on the 128 x 128 tile, which then runs one wave per SIMD instead of three. The tile is re-read from LDS instead.)
+#pragma unroll 2
+        for (int cc = 0; cc < SEG; ++cc) {
+            const int c = part * SEG + cc, n = n0 + c * 4;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+            uint32_t word = mw[0];
+#pragma unroll
+            for (int k = 1; k < NWD; ++k) word = ((cc * 4) >> 5) == k ? mw[k] : word;      // static indices: mw stays in registers
+            const uint32_t bits = word >> (n & 31);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const bool take = (n + i < N) & (((bits >> i) & 1u) != 0) & alt_after(v[i], n + i, pv, pc) & (v[i] > cb);
+                cb = take ? v[i] : cb;
+                ci = take ? n + i : ci;
+            }
+        }
+#pragma unroll
+        for (int o = 1; o < TPR; o <<= 1) {
+            const float ob = __shfl_xor(cb, o, 64);
+            const int oi = __shfl_xor(ci, o, 64);
+            if (alt_before(ob, oi, cb, ci)) { cb = ob; ci = oi; }
+        }
+        if (writer) arow[t] = make_float2(cb, __int_as_float(ci));
+        pv = cb;
+        pc = ci;
+    }
 }
 
 // BM x BN output tile per workgroup of WM x WN waves.
@@ -765,17 +860,25 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
         // dependent loads) and its ten table words are independent loads behind it.
         constexpr int MWS = (BN / 32) | 1;
         [[maybe_unused]] uint32_t* mask_s = reinterpret_cast<uint32_t*>(smem + (size_t)BM * WN * 16 + (size_t)BN * 4);
-        if constexpr (EPI == EPI_ARGMAX_MASK) {
+        // EPI_TOPK: per-wave candidate lists [BM][WN][4] {value, column bits} behind the mask words (16 KB beside the 8 KB of `rec`)
+        [[maybe_unused]] float2* alt_s = reinterpret_cast<float2*>(smem + (size_t)BM * WN * 16 + (size_t)BN * 4 + (((size_t)BM * MWS * 4 + 15) & ~(size_t)15));
+        if constexpr (EPI == EPI_TOPK)
+            static_assert((size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * MWS * 4 + 16 + (size_t)BM * WN * SA_MAX_ALTERNATIVES * 8 <= (size_t)(BM + BN) * 256,
+                          "candidate lists fit the staging LDS");
+        if constexpr (epi_is_masked(EPI)) {
             static_assert(BN % 32 == 0 && WTN == FN * 32 && NT >= BM && (size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * MWS * 4 <= (size_t)(BM + BN) * 256,
                           "mask words fit the staging LDS");
             if (tid < BM) {
-                const int mid = p.tmask.id_of(m0 + tid, p.M);
+                int mid;
+                if constexpr (EPI == EPI_TOPK) mid = p.tmask.id_or_none(m0 + tid, p.M);
+                else mid = p.tmask.id_of(m0 + tid, p.M);
 #pragma unroll
                 for (int k = 0; k < BN / 32; ++k) {
                     // ... with the bits of columns past N cleared: where the accumulators are masked one bit says both "inside N" and "allowed"
                     const int wd = (n0 >> 5) + k, left = p.N - wd * 32;
                     const uint32_t inside = left >= 32 ? 0xffffffffu : (left <= 0 ? 0u : (1u << left) - 1u);
-                    mask_s[tid * MWS + k] = p.tmask.word_of(mid, wd) & inside;
+                    if constexpr (EPI == EPI_TOPK) mask_s[tid * MWS + k] = p.tmask.word_or_all(mid, wd) & inside;
+                    else mask_s[tid * MWS + k] = p.tmask.word_of(mid, wd) & inside;
                 }
             }
         }
@@ -783,7 +886,7 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
         // columns of this lane: base + off with off = j * 32 + g * 8 + r a compile-time constant; off < lim are inside N
         const int base = n0 + wn * WTN + (lane >> 5) * 4;
         [[maybe_unused]] const int lim = p.N - base;
-        if constexpr (EPI == EPI_ARGMAX_MASK) {
+        if constexpr (epi_is_masked(EPI)) {
             // a disallowed column is a column past N: -inf here, once, before the max pass and the sum-exp pass
             const uint32_t* mrow = mask_s + (wm * WTM + (lane & 31)) * MWS + wn * FN;
             const int sh = (lane >> 5) * 4;
@@ -850,6 +953,40 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
                     }
             se += __shfl_xor(se, 32, 64);
             if (lane < 32) rec[(wm * WTM + i * 32 + lane) * WN + wn] = make_float4(best, __int_as_float(bi), se, 0.f);
+            if constexpr (EPI == EPI_TOPK) {
+                // the wave's four best columns of this row: pass t takes the best (value, column) strictly after pass t - 1's winner. The
+                // accumulators are only read; a lane's offsets ascend, so strict > keeps the first of equal values, and an offset comes
+                // after the previous winner's column when it exceeds that column minus the lane's base.
+                float2* arow = alt_s + ((wm * WTM + i * 32 + (lane & 31)) * WN + wn) * SA_MAX_ALTERNATIVES;
+                if (lane < 32) arow[0] = make_float2(best, __int_as_float(bi));
+                float pv = best;
+                int pc = bi;
+#pragma unroll 1
+                for (int t = 1; t < SA_MAX_ALTERNATIVES; ++t) {
+                    const int d = pc - base;
+                    float cb = -INFINITY;
+                    int co = 0;
+#pragma unroll
+                    for (int j = 0; j < FN; ++j)
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) {
+                                const float v = acc[j][i][4 * g + r];
+                                const int o = j * 32 + g * 8 + r;
+                                const bool take = ((v < pv) | ((v == pv) & (o > d))) & (v > cb);     // selects, not branches
+                                cb = take ? v : cb;
+                                co = take ? o : co;
+                            }
+                    int ci = (cb == -INFINITY) ? SA_ALT_NONE : base + co;
+                    const float ob = __shfl_xor(cb, 32, 64);
+                    const int oi = __shfl_xor(ci, 32, 64);
+                    if (alt_before(ob, oi, cb, ci)) { cb = ob; ci = oi; }
+                    if (lane < 32) arow[t] = make_float2(cb, __int_as_float(ci));
+                    pv = cb;
+                    pc = ci;
+                }
+            }
         }
         __syncthreads();
         if (tid < BM && m0 + tid < p.M) {
@@ -863,13 +1000,25 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
             }
             float se = 0.f;
             // (EPI_ARGMAX_MASK: a row may have no allowed column in the whole tile -- every wave -inf -- and exp(-inf - (-inf)) must not appear)
-            const float fsafe = (EPI == EPI_ARGMAX_MASK && best == -INFINITY) ? 0.f : best;
+            const float fsafe = (epi_is_masked(EPI) && best == -INFINITY) ? 0.f : best;
 #pragma unroll
             for (int w = 0; w < WN; ++w) {
                 const float4 r4 = rec[tid * WN + w];
                 se += r4.z * expf(r4.x - fsafe);                                     // a wave past N holds (-inf, -, 0): contributes 0
             }
             p.amax[(long)(m0 + tid) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
+            if constexpr (EPI == EPI_TOPK) {
+                // the row's WN sorted lists -> the tile's four best, by the same "next after the previous winner" rule
+                float2* arow = p.alt + ((long)(m0 + tid) * tiles_n + tile_n) * SA_MAX_ALTERNATIVES;
+                const float2* cand = alt_s + tid * WN * SA_MAX_ALTERNATIVES;
+                float2 cur = make_float2(best, __int_as_float(bi));
+                arow[0] = cur;
+#pragma unroll 1
+                for (int t = 1; t < SA_MAX_ALTERNATIVES; ++t) {
+                    cur = alt_next(cand, WN * SA_MAX_ALTERNATIVES, cur.x, __float_as_int(cur.y));
+                    arow[t] = cur;
+                }
+            }
         }
         return;
     }
@@ -971,6 +1120,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
     if constexpr (EPI == EPI_ARGMAX_MASK) {
         static_assert(!SPLIT && std::is_same<TO, float>::value, "argmax epilogue works on fp32 tiles");
         argmax_partial_masked<BM, NT, CPR, XM>(smem, p.tmask, m0, n0, p.M, p.N, p.amax, tiles_n, tile_n);
+        return;
+    }
+    if constexpr (EPI == EPI_TOPK) {
+        static_assert(!SPLIT && std::is_same<TO, float>::value, "argmax epilogue works on fp32 tiles");
+        topk_partial_masked<BM, NT, CPR, XM>(smem, p.tmask, m0, n0, p.M, p.N, p.amax, p.alt, tiles_n, tile_n);
         return;
     }
     if constexpr (EPI == EPI_ARGMAX) {
@@ -1687,6 +1841,9 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
     }
     if constexpr (EPI == EPI_ARGMAX_MASK) {
         if (!a.tmask.table || !a.tmask.slot_mask || a.tmask.words != cdiv(a.N, 32)) return SA_ERR_ARG;
+    }
+    if constexpr (EPI == EPI_TOPK) {        // the table is optional here; with one, the rest of the mask must be there
+        if (!a.alt || (a.tmask.table && (!a.tmask.slot_mask || a.tmask.words != cdiv(a.N, 32)))) return SA_ERR_ARG;
     }
     if (a.M <= 256) {
         if constexpr (epi_is_argmax(EPI)) {

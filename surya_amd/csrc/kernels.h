@@ -436,7 +436,8 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
                                                           const T* __restrict__ bb, const int* __restrict__ row_slot,
                                                           int eos_id, int pad_id, float bbox_size, int* __restrict__ out_token,
                                                           float* __restrict__ out_score, int* __restrict__ out_bbox,
-                                                          int* __restrict__ next_token, int* __restrict__ kv_len, int len_inc) {
+                                                          int* __restrict__ next_token, int* __restrict__ kv_len, int len_inc,
+                                                          float2* __restrict__ best_tot = nullptr) {
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lr = logits + (long)r * ldl * (PART ? 4 : 1);
     __shared__ float smax[4], ssum[4];
@@ -496,6 +497,7 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
         out_score[slot] = done ? 0.f : 1.0f / tot;
         next_token[slot] = done ? pad_id : bi;
         kv_len[slot] += len_inc;
+        if (best_tot) best_tot[slot] = make_float2(best, tot);      // alternatives on: the row's max and total for topk_combine_kernel
     }
     // bbox head: 6 dot products of length H, one wave each (waves 0..3 take outputs 0..3, then 4..5)
     const T* hr = hidden + (long)r * H;
@@ -594,7 +596,8 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
                                                                        int* __restrict__ kv_len, int len_inc,
                                                                        const T* __restrict__ table, const T* __restrict__ wnorm, T* __restrict__ x,
                                                                        T* __restrict__ y, int* __restrict__ row_len, int Tmax, float eps,
-                                                                       uint8_t* __restrict__ y8, uint8_t* __restrict__ sy, int srows) {
+                                                                       uint8_t* __restrict__ y8, uint8_t* __restrict__ sy, int srows,
+                                                                       float2* __restrict__ best_tot = nullptr) {
     constexpr int NT = SA_HEAD_THREADS, NW = NT / 64, NP = 4, V = Ty<T>::V16, NB = 32 / V;   // NB x 64 x V = 2048 >= H
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float smax[NW], ssum[NW], red[NW];
@@ -667,6 +670,7 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
         next_token[slot] = tok_next;
         kv_len[slot] = klen + len_inc;
         if (table) row_len[r] = min(klen + len_inc, Tmax - 1);
+        if (best_tot) best_tot[slot] = make_float2(best, tot);      // alternatives on: the row's max and total for topk_combine_kernel
     }
     if (lane == 0 && wave < 6) {
         const float lin = Ty<T>::rnd(d + bias_o);
@@ -674,6 +678,60 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
         out_bbox[slot * 6 + wave] = (int)(sg * bbox_size);
     }
     if (table) embed_norm_row<T, NT>(table + (long)tok_next * H, x + (long)r * H, wnorm, y + (long)r * H, H, eps, red, y8, sy, srows, r);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Alternatives: the row's SA_MAX_ALTERNATIVES best allowed tokens from the per-tile candidates of the lm_head's *_TOPK epilogue
+// (alt[(row * tiles_n + tile) * 4 + j] = {logit, column bits}, gemm.h). One workgroup per row, behind the greedy head: pass t takes the
+// best candidate strictly after pass t - 1's winner in the order value descending, column ascending, so entry 0 is the head's token
+// (the head picks the first maximum over the tiles' winners, and every tile's winner is its entry 0). prob_j = exp(v_j - best) / tot with
+// the row's max and total exactly as the head computed them (best_tot[slot]): nothing is summed again in another order, and entry 0,
+// exp(0) / tot, has the bits of the head's score 1 / tot. Done rows (eos / pad chosen, score 0) report their alternatives all the same.
+// Fewer than four allowed ids: token -1, probability 0. row_slot = nullptr: row r is slot r.
+constexpr int SA_ALT_THREADS = 256;
+static __global__ __launch_bounds__(SA_ALT_THREADS) void topk_combine_kernel(const float2* __restrict__ alt, int tiles_n, const int* __restrict__ row_slot,
+                                                                      const float2* __restrict__ best_tot, int* __restrict__ alt_token,
+                                                                      float* __restrict__ alt_prob) {
+    constexpr int NW = SA_ALT_THREADS / 64;
+    const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int n = tiles_n * SA_MAX_ALTERNATIVES;
+    const float2* cand = alt + (long)r * n;
+    __shared__ float sv[SA_MAX_ALTERNATIVES][NW];
+    __shared__ int sc[SA_MAX_ALTERNATIVES][NW];
+    const int slot = row_slot ? row_slot[r] : r;
+    const float2 bt = best_tot[slot];
+    float pv = INFINITY;
+    int pc = -1;
+    for (int t = 0; t < SA_MAX_ALTERNATIVES; ++t) {
+        float cb = -INFINITY;
+        int ci = SA_ALT_NONE;
+        for (int k = tid; k < n; k += SA_ALT_THREADS) {
+            const float2 q = cand[k];
+            const int qc = __float_as_int(q.y);
+            const bool take = (q.x > -INFINITY) & alt_after(q.x, qc, pv, pc) & alt_before(q.x, qc, cb, ci);
+            cb = take ? q.x : cb;
+            ci = take ? qc : ci;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float ob = __shfl_xor(cb, o, 64);
+            const int oi = __shfl_xor(ci, o, 64);
+            if (alt_before(ob, oi, cb, ci)) { cb = ob; ci = oi; }
+        }
+        if (lane == 0) { sv[t][wave] = cb; sc[t][wave] = ci; }
+        __syncthreads();
+        cb = sv[t][0]; ci = sc[t][0];
+#pragma unroll
+        for (int w = 1; w < NW; ++w)
+            if (alt_before(sv[t][w], sc[t][w], cb, ci)) { cb = sv[t][w]; ci = sc[t][w]; }
+        if (tid == 0) {
+            const bool none = ci == SA_ALT_NONE;
+            alt_token[slot * SA_MAX_ALTERNATIVES + t] = none ? -1 : ci;
+            alt_prob[slot * SA_MAX_ALTERNATIVES + t] = none ? 0.f : expf(cb - bt.x) / bt.y;
+        }
+        pv = cb;
+        pc = ci;
+    }
 }
 
 // ---------------------------------------------------------------------------------------------------

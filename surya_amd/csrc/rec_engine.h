@@ -152,6 +152,9 @@ struct RecBase {
     virtual int set_kv_fp8(int) = 0;
     virtual int set_token_masks(const uint32_t*, int, hipStream_t) = 0;
     virtual int set_slot_masks(const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int set_alternatives(int) = 0;
+    virtual int read_alternatives(int, int32_t*, float*, hipStream_t) = 0;
+    virtual int wait_alternatives(int, int, int32_t*, float*) = 0;
 };
 
 static __global__ void set_slot_masks_kernel(const int* slots, const int* ids, int* slot_mask, int n) {
@@ -230,6 +233,16 @@ struct RecModel : RecBase {
     int n_token_masks = 0;
     int mask_words() const { return cdiv(c.vocab, 32); }
     TokenMask token_mask(const int* d_row_slot) const { return TokenMask{mask_table, slot_mask, d_row_slot, mask_words()}; }
+    // Alternatives (surya_rec_set_alternatives): per-tile candidates of the lm_head's *_TOPK epilogue, the head's (max, total) per slot and
+    // the [SA_MAX_STEPS][max_slots][SA_MAX_ALTERNATIVES] outputs with their pinned mirror, allocated on the first switch-on at addresses
+    // that never change afterwards. alts == false: the lm_head and head launches are the ones of a handle without this entry.
+    char* alt_arena = nullptr;
+    float2* alt_part = nullptr;                          // [max_slots][cdiv(vocab, 64)][4]: 64 columns is the narrowest lm_head tile
+    float2* best_tot = nullptr;                          // [max_slots]
+    int* alt_token = nullptr; float* alt_prob = nullptr; // [SA_MAX_STEPS][max_slots][4]
+    char* alt_host = nullptr;
+    bool alts = false;
+    bool ring_alts[2] = {false, false};                  // the last decode_async on this ring half mirrored its alternatives
     const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
     const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
 
@@ -336,6 +349,8 @@ struct RecModel : RecBase {
         if (mx_arena) (void)hipFree(mx_arena);
         if (kv8_arena) (void)hipFree(kv8_arena);
         if (mask_arena) { (void)hipFree(mask_arena); st_mask.destroy(); }
+        if (alt_arena) (void)hipFree(alt_arena);
+        if (alt_host) (void)hipHostFree(alt_host);
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -663,6 +678,32 @@ struct RecModel : RecBase {
         return (int)hipGetLastError();
     }
 
+    // Alternatives on / off. Memory on the first switch-on, or nothing (a failure leaves the handle as it was); switching drops captured
+    // steps, which hold the other lm_head kernel and the head's null / non-null (max, total) pointer.
+    int set_alternatives(int on) override {
+        if (on != 0 && on != 1) return SA_ERR_ARG;
+        if (on && !alt_arena) {
+            const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S * SA_MAX_ALTERNATIVES;
+            const size_t part_bytes = align_up(S * (size_t)cdiv(c.vocab, 64) * SA_MAX_ALTERNATIVES * sizeof(float2));
+            const size_t bt_bytes = align_up(S * sizeof(float2)), out_b = align_up(outs * sizeof(int));
+            char* mem = nullptr;
+            char* host = nullptr;
+            SA_HIP(hipMalloc((void**)&mem, part_bytes + bt_bytes + 2 * out_b));
+            int rc = (int)hipHostMalloc((void**)&host, outs * 8, hipHostMallocDefault);
+            if (!rc) rc = (int)hipMemset(mem, 0, part_bytes + bt_bytes + 2 * out_b);
+            if (rc) { if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
+            alt_arena = mem;
+            alt_host = host;
+            alt_part = reinterpret_cast<float2*>(mem);
+            best_tot = reinterpret_cast<float2*>(mem + part_bytes);
+            alt_token = reinterpret_cast<int*>(mem + part_bytes + bt_bytes);
+            alt_prob = reinterpret_cast<float*>(mem + part_bytes + bt_bytes + out_b);
+        }
+        if ((on != 0) != alts) drop_graphs();
+        alts = on != 0;
+        return SA_OK;
+    }
+
     // MXFP8 weight table of the decode steps: per layer SA_MX_COUNT pointers, then SA_MX_LM_W, SA_MX_LM_S. bf16 model only.
     int set_mx_weights(const void* const* tbl, int n) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return SA_ERR_UNSUPPORTED;
@@ -797,7 +838,11 @@ struct RecModel : RecBase {
                 MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
                 a.amax = am;
                 a.bias = W(SA_RW_LM_B);
-                if (n_token_masks > 0) {
+                if (alts) {
+                    if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
+                    a.alt = alt_part;
+                    if ((rc = launch_gemm_mx<MX_EPI_TOPK>(a, s))) return rc;
+                } else if (n_token_masks > 0) {
                     a.tmask = token_mask(d_row_slot);
                     if ((rc = launch_gemm_mx<MX_EPI_ARGMAX_MASK>(a, s))) return rc;
                 } else if ((rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s))) return rc;
@@ -806,7 +851,11 @@ struct RecModel : RecBase {
         } else {
             GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
             a.amax = am;
-            if (n_token_masks > 0) {
+            if (alts) {
+                if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
+                a.alt = alt_part;
+                if ((rc = launch_gemm<T, float, EPI_TOPK>(a, s))) return rc;
+            } else if (n_token_masks > 0) {
                 a.tmask = token_mask(d_row_slot);
                 if ((rc = launch_gemm<T, float, EPI_ARGMAX_MASK>(a, s))) return rc;
             } else if ((rc = launch_gemm<T, float, EPI_ARGMAX>(a, s))) return rc;
@@ -816,23 +865,31 @@ struct RecModel : RecBase {
         const size_t so = (size_t)step * c.max_slots;
         last_rows = rows;
         last_heads_mx = mx() && normed;
+        float2* bt = alts ? best_tot : nullptr;
+        // alternatives: the row's four best candidates and their probabilities, behind whichever head ran
+        auto combine = [&]() -> int {
+            if ((rc = (int)hipGetLastError()) || !alts) return rc;
+            hipLaunchKernelGGL(topk_combine_kernel, dim3(rows), dim3(SA_ALT_THREADS), 0, s, alt_part, tiles_n, d_row_slot, bt,
+                               alt_token + so * SA_MAX_ALTERNATIVES, alt_prob + so * SA_MAX_ALTERNATIVES);
+            return (int)hipGetLastError();
+        };
         if (head2_ok() && tiles_n <= 4 * SA_HEAD_THREADS) {
             const bool fz = fuse_next;
             hipLaunchKernelGGL((greedy_head2_kernel<T>), dim3(rows), dim3(SA_HEAD_THREADS), 0, s, reinterpret_cast<const float4*>(am), tiles_n,
                                last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id, c.pad_token_id, (float)c.bbox_size,
                                out_token + so, out_score + so, out_bbox + so * 6, next_token, kv_len, len_inc,
                                fz ? W(SA_RW_TOK_EMBED) : (const T*)nullptr, WD(0, SA_RD_LN1), dx, dh, row_len, c.max_kv_len, c.dec_eps,
-                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots);
-            return (int)hipGetLastError();
+                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots, bt);
+            return combine();
         }
         if (fuse_next) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
         hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(rows), dim3(256), 0, s, reinterpret_cast<const float*>(am),
                            (long)tiles_n, tiles_n, last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id,
                            c.pad_token_id, (float)c.bbox_size, out_token + so, out_score + so, out_bbox + so * 6, next_token,
-                           kv_len, len_inc);
+                           kv_len, len_inc, bt);
         last_rows = rows;
         last_heads_mx = mx() && normed;
-        return (int)hipGetLastError();
+        return combine();
     }
 
     int prefill(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
@@ -967,7 +1024,36 @@ struct RecModel : RecBase {
             SA_HIP(hipMemcpyAsync(out_host + full * 4 + off * 4, out_score + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
             SA_HIP(hipMemcpyAsync(out_host + full * 8 + off * 24, out_bbox + off * 6, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
         }
+        ring_alts[ring] = alts;
+        if (nt && alts) {
+            const size_t A = SA_MAX_ALTERNATIVES;
+            SA_HIP(hipMemcpyAsync(alt_host + off * A * 4, alt_token + off * A, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
+            SA_HIP(hipMemcpyAsync(alt_host + (full + off) * A * 4, alt_prob + off * A, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
         SA_HIP(hipEventRecord(ev_ring[ring], s));
+        return SA_OK;
+    }
+
+    // Alternatives of the steps wait_outputs / read_outputs return: [step][slot][SA_MAX_ALTERNATIVES], same indexing
+    int wait_alternatives(int n_steps, int ring, int32_t* tokens, float* probs) override {
+        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
+        if (!alts || !ring_alts[ring]) return SA_ERR_STATE;       // (a call enqueued while the feature was off mirrored nothing)
+        SA_HIP(hipEventSynchronize(ev_ring[ring]));
+        const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
+        const size_t nt = (size_t)n_steps * S;
+        memcpy(tokens, alt_host + off * A * 4, nt * A * sizeof(int));
+        memcpy(probs, alt_host + (full + off) * A * 4, nt * A * sizeof(float));
+        return SA_OK;
+    }
+    int read_alternatives(int n_steps, int32_t* tokens, float* probs, hipStream_t s) override {
+        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
+        if (!alts) return SA_ERR_STATE;
+        const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
+        SA_HIP(hipMemcpyAsync(alt_host, alt_token, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(alt_host + full * A * 4, alt_prob, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
+        SA_HIP(hipStreamSynchronize(s));
+        memcpy(tokens, alt_host, nt * A * sizeof(int));
+        memcpy(probs, alt_host + full * A * 4, nt * A * sizeof(float));
         return SA_OK;
     }
 

@@ -70,7 +70,8 @@ namespace sa {
 size_t rec_f16_workspace_bytes(const surya_rec_config& cfg);
 int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int n, std::unique_ptr<RecBase>& out);
 int rec_f16_ring_error(bool reset);
-int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, int* bn_used, hipStream_t s);
+int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt, int* bn_used,
+                   hipStream_t s);
 // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
@@ -99,12 +100,16 @@ static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, 
 
 // surya_op_lm_head_partials: the lm_head launch of RecModel<T>::heads for the 16-bit / fp32 operand types built here
 template <typename T>
-static int op_lm_head_t(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, int* bn_used,
-                        hipStream_t s) {
+static int op_lm_head_t(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt,
+                        int* bn_used, hipStream_t s) {
     GemmArgs<T, float> a{(const T*)X, (long)K, (const T*)W, (long)K, nullptr, (long)N, (const T*)bias, nullptr, 0, M, N, K};
     a.amax = amax;
     int rc;
-    if (tm) {
+    if (alt) {                      // surya_op_lm_head_topk: one kernel with or without a table
+        if (tm) a.tmask = *tm;
+        a.alt = alt;
+        rc = launch_gemm<T, float, EPI_TOPK>(a, s);
+    } else if (tm) {
         a.tmask = *tm;
         rc = launch_gemm<T, float, EPI_ARGMAX_MASK>(a, s);
     } else {
@@ -231,23 +236,47 @@ int surya_rec_set_slot_masks(surya_rec* h, const int32_t* slots, const int32_t* 
     return h->impl->set_slot_masks(slots, mask_ids, n, (hipStream_t)stream);
 }
 
-int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
-                              const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream) {
+int surya_rec_set_alternatives(surya_rec* h, int on) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_alternatives(on);
+}
+int surya_rec_read_alternatives(surya_rec* h, int n_steps, int32_t* tokens, float* probs, void* stream) {
+    if (!h || !tokens || !probs) return SA_ERR_ARG;
+    return h->impl->read_alternatives(n_steps, tokens, probs, (hipStream_t)stream);
+}
+int surya_rec_wait_alternatives(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* probs) {
+    if (!h || !tokens || !probs) return SA_ERR_ARG;
+    return h->impl->wait_alternatives(n_steps, ring, tokens, probs);
+}
+
+// surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
+static __global__ void iota_kernel(int* dst, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) dst[i] = i;
+}
+
+// surya_op_lm_head_partials (alt == nullptr) and the lm_head launch of surya_op_lm_head_topk
+static int op_lm_head(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                      const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, float2* alt, int* bn_used,
+                      hipStream_t s) {
     if (!X || !W || !amax || !bn_used || M <= 0 || N <= 0 || K <= 0 || (masks && !slot_mask)) return SA_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
     const TokenMask tm{masks, slot_mask, row_slot, cdiv(N, 32)};
     const TokenMask* tp = masks ? &tm : nullptr;
     float4* am = reinterpret_cast<float4*>(amax);
-    if (dtype == SA_DTYPE_F32) return op_lm_head_t<float>(X, W, bias, M, N, K, tp, am, bn_used, s);
-    if (dtype == SA_DTYPE_BF16) return op_lm_head_t<bf16_t>(X, W, bias, M, N, K, tp, am, bn_used, s);
-    if (dtype == SA_DTYPE_F16) return sa::op_lm_head_f16(X, W, bias, M, N, K, tp, am, bn_used, s);
+    if (dtype == SA_DTYPE_F32) return op_lm_head_t<float>(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
+    if (dtype == SA_DTYPE_BF16) return op_lm_head_t<bf16_t>(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
+    if (dtype == SA_DTYPE_F16) return sa::op_lm_head_f16(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
     if (dtype == SA_OP_MXFP8) {
         if (!SX || !SW) return SA_ERR_ARG;
         MxArgs a{(const uint8_t*)X, (long)K, (const uint8_t*)SX, (const uint8_t*)W, (long)K, (const uint8_t*)SW, M, N, K, (long)M, (long)N};
         a.amax = am;
         a.bias = (const bf16_t*)bias;
         int rc;
-        if (tp) {
+        if (alt) {
+            if (tp) a.tmask = tm;
+            a.alt = alt;
+            rc = launch_gemm_mx<MX_EPI_TOPK>(a, s);
+        } else if (tp) {
             a.tmask = tm;
             rc = launch_gemm_mx<MX_EPI_ARGMAX_MASK>(a, s);
         } else {
@@ -257,6 +286,40 @@ int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const vo
         return rc;
     }
     return SA_ERR_UNSUPPORTED;
+}
+
+int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                              const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream) {
+    return op_lm_head(dtype, X, SX, W, SW, bias, M, N, K, masks, slot_mask, row_slot, amax, nullptr, bn_used, (hipStream_t)stream);
+}
+
+int surya_op_lm_head_topk(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                          const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, float* alt, int* bn_used,
+                          int32_t* top_tokens, float* top_probs, int32_t* head_token, float* head_score, float* scratch, void* stream) {
+    if (!alt || (top_tokens != nullptr) != (top_probs != nullptr) || (top_tokens && (!head_token || !head_score || !scratch))) return SA_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    float2* al = reinterpret_cast<float2*>(alt);
+    int rc = op_lm_head(dtype, X, SX, W, SW, bias, M, N, K, masks, slot_mask, row_slot, amax, al, bn_used, s);
+    if (rc || !top_tokens) return rc;
+    // the engine's fallback head (greedy_head_kernel<T, true>: the reduction greedy_head2_kernel states) with an empty bbox head, then
+    // the combine kernel. scratch: (max, total) [M][2] | bbox [M][6] | next token [M] | kv_len [M] | six zero bbox biases (10 M .. 10 M + 6)
+    // | identity row -> slot map [M] from 11 M + 16 on, where the caller gave none
+    const int tiles_n = cdiv(N, *bn_used);
+    SA_HIP(hipMemsetAsync(scratch, 0, ((size_t)16 * M + 16) * sizeof(float), s));
+    float2* bt = reinterpret_cast<float2*>(scratch);
+    int* ib = reinterpret_cast<int*>(scratch);
+    if (!row_slot) {
+        int* ident = ib + (size_t)11 * M + 16;
+        hipLaunchKernelGGL(iota_kernel, dim3(cdiv(M, 256)), dim3(256), 0, s, ident, M);
+        SA_HIP(hipGetLastError());
+        row_slot = ident;
+    }
+    hipLaunchKernelGGL((greedy_head_kernel<float, true>), dim3(M), dim3(256), 0, s, amax, (long)tiles_n, tiles_n, scratch, 0, scratch,
+                       scratch + (size_t)10 * M, row_slot, -1, -1, 1.0f, head_token, head_score, ib + (size_t)2 * M, ib + (size_t)8 * M,
+                       ib + (size_t)9 * M, 0, bt);
+    SA_HIP(hipGetLastError());
+    hipLaunchKernelGGL(topk_combine_kernel, dim3(M), dim3(SA_ALT_THREADS), 0, s, al, tiles_n, row_slot, bt, top_tokens, top_probs);
+    return (int)hipGetLastError();
 }
 
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,

@@ -76,7 +76,8 @@ def shard_indices(n: int, world: int, rank: int) -> List[int]:
 
 
 class PackedLines(Sequence):
-    """Ragged per-line values (token ids or scores) as ONE dense array [n, T] + lengths [n]; behaves like the list of lists the
+    """Ragged per-line values (token ids or scores; with trailing dimensions, [n, T, 4], the alternatives of a top_k call) as ONE
+    dense array [n, T] + lengths [n]; behaves like the list of lists the
     reference's prediction_loop returns (`lines[i]` is a Python list of line i's values) but converts a line only when somebody
     asks for it. The gather below hands every rank ALL lines of the call: unpacking them eagerly into Python lists on every rank
     was 10 us per line inside the timed step (22 ms at 8 x 256 lines) for a consumer that reads each line once."""
@@ -124,7 +125,7 @@ class PackedLines(Sequence):
 
 
 def gather_line_outputs(tokens, scores, bboxes: np.ndarray, local_idx: Sequence[int], n_total: int, max_tokens: int,
-                        device="cpu", group=None, stats: dict | None = None):
+                        device="cpu", group=None, stats: dict | None = None, alts=None):
     """All ranks contribute the outputs of their shard; every rank gets all n_total lines back in global order.
     tokens / scores: lists of per-line lists, or PackedLines (the continuous-batching loop's own dense bookkeeping,
     RecognitionPredictor.last_packed -- no per-token Python on the way in). bboxes: [n_local, max_tokens, 6].
@@ -132,7 +133,10 @@ def gather_line_outputs(tokens, scores, bboxes: np.ndarray, local_idx: Sequence[
     ONE collective: a rank's record is a flat int32 buffer of four planes -- meta [per_rank, 2] (global index + 1, length; 0 =
     padding line), token ids [per_rank, T], score bits [per_rank, T], bbox ints [per_rank, T, 6]; entries past a line's length are
     zero. Planes, not an array of per-token structs: packing and unpacking are then contiguous whole-array copies (the [.., 8]
-    struct layout of round 4 spent 5 ms of strided numpy writes at 2048 lines); nothing here is per line."""
+    struct layout of round 4 spent 5 ms of strided numpy writes at 2048 lines); nothing here is per line.
+    alts = (PackedLines ids [n_local, >= T, A] int32, PackedLines probabilities [n_local, >= T, A] float32) of a top_k call (every rank
+    passes them or none does): two more planes [per_rank, T, A] in the same record, and the result grows to (tokens, scores, bboxes,
+    alternative ids PackedLines [n_total, T, A], probabilities PackedLines); entries past a line's length are (-1, 0)."""
     import time
     import torch.distributed as dist
     t_start = time.perf_counter()
@@ -140,6 +144,9 @@ def gather_line_outputs(tokens, scores, bboxes: np.ndarray, local_idx: Sequence[
     per_rank = (n_total + world - 1) // world
     T = max_tokens
     o_tok, o_sc, o_bb, rec_len = 2 * per_rank, (2 + T) * per_rank, (2 + 2 * T) * per_rank, (2 + 8 * T) * per_rank
+    A = 0 if alts is None else int(alts[0].data.shape[2])
+    o_at, o_ap = rec_len, rec_len + per_rank * T * A          # the alternatives' planes behind the four others
+    rec_len += 2 * per_rank * T * A
     rec = np.zeros(rec_len, np.int32)
     n_local = len(local_idx)
     if n_local:
@@ -154,12 +161,22 @@ def gather_line_outputs(tokens, scores, bboxes: np.ndarray, local_idx: Sequence[
         mask = np.arange(T)[None, :] < lens[:, None]                       # [n_local, T]
         tok_p = rec[o_tok:o_sc].reshape(per_rank, T)
         sc_p = rec[o_sc:o_bb].reshape(per_rank, T).view(np.float32)         # bit-cast, lossless
-        bb_p = rec[o_bb:].reshape(per_rank, T, 6)
+        bb_p = rec[o_bb:o_at].reshape(per_rank, T, 6)
         np.multiply(pt.data[:, :w], mask[:, :w], out=tok_p[:n_local, :w], casting="unsafe")
         np.copyto(sc_p[:n_local, :w], ps.data[:, :w], casting="unsafe")
         sc_p[:n_local][~mask] = 0
         np.copyto(bb_p[:n_local], bboxes[:, :T], casting="unsafe")         # float box coordinates are whole numbers (bbox bins)
         bb_p[:n_local][~mask] = 0
+        if A:
+            assert len(alts[0]) == n_local and len(alts[1]) == n_local
+            wa = min(T, alts[0].data.shape[1], alts[1].data.shape[1])
+            at_p = rec[o_at:o_ap].reshape(per_rank, T, A)
+            ap_p = rec[o_ap:].reshape(per_rank, T, A).view(np.float32)
+            at_p[:n_local] = -1
+            np.copyto(at_p[:n_local, :wa], alts[0].data[:, :wa], casting="unsafe")
+            np.copyto(ap_p[:n_local, :wa], alts[1].data[:, :wa], casting="unsafe")
+            at_p[:n_local][~mask] = -1
+            ap_p[:n_local][~mask] = 0
     t_packed = time.perf_counter()
     if not collectives_on(group):
         allr = rec[None]
@@ -183,12 +200,19 @@ def gather_line_outputs(tokens, scores, bboxes: np.ndarray, local_idx: Sequence[
     out_len = np.zeros(n_total, np.int64)
     out_tok[g] = plane(o_tok, o_sc, (T,))
     out_sc[g] = plane(o_sc, o_bb, (T,)).view(np.float32)
-    out_bb[g] = plane(o_bb, rec_len, (T, 6))
+    out_bb[g] = plane(o_bb, o_at, (T, 6))
     out_len[g] = meta[rows, 1]
+    out_alts = ()
+    if A:
+        out_at = np.full((n_total, T, A), -1, np.int32)
+        out_ap = np.zeros((n_total, T, A), np.float32)
+        out_at[g] = plane(o_at, o_ap, (T, A))
+        out_ap[g] = plane(o_ap, rec_len, (T, A)).view(np.float32)
+        out_alts = (PackedLines(out_at, out_len), PackedLines(out_ap, out_len))
     if stats is not None:                  # host seconds: pack + unpack (whole-array numpy) apart from the collective (H2D, all_gather, D2H)
         stats["pack_unpack_s"] = stats.get("pack_unpack_s", 0.0) + (t_packed - t_start) + (time.perf_counter() - t_gathered)
         stats["collective_s"] = stats.get("collective_s", 0.0) + (t_gathered - t_packed)
-    return PackedLines(out_tok, out_len), PackedLines(out_sc, out_len), out_bb
+    return (PackedLines(out_tok, out_len), PackedLines(out_sc, out_len), out_bb) + out_alts
 
 
 def gather_objects(local: list, local_idx: Sequence[int], n_total: int, group=None) -> list:

@@ -11,11 +11,11 @@ from ..common.geometry import PolygonBox, coerce_polygon
 from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags, prediction_to_polygon_batch, unwrap_math,
                           words_from_chars)
 from .processor import NOMATH_TOKEN
-from .schema import TaskNames, TextChar, TextLine
+from .schema import CharAlternative, TaskNames, TextChar, TextLine
 
 _SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
 _CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
-assert _CHAR_FIELDS == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
+assert _CHAR_FIELDS | {"alternatives"} == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
 _new_char, _set = TextChar.__new__, object.__setattr__
 
 
@@ -23,8 +23,8 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     """TextChar.model_construct(...) with all four fields given, without its per-call field loop (1.9 -> 0.55 us; a page of
     text is ~10^4 of these). Same object state: __dict__, fields_set, no extras, no private attributes."""
     m = _new_char(TextChar)
-    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid})
-    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))
+    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid, "alternatives": None})
+    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))        # (alternatives: the default, as in TextChar(...) without it)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
     return m
@@ -48,7 +48,38 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     return m
 
 
-def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False) -> list:
+class AltDecoder:
+    """Token id -> text of ONE alternative, cached for a call: a UTF-16 unit decodes alone (a lone surrogate gives ""), special and
+    math ids decode through the tokenizer as `line_runs` decodes their runs. The three stop ids (eos, pad, no-output: "the line ends
+    here") never become characters of a line and read "" as alternatives; their token_id says which one it was."""
+
+    def __init__(self, proc):
+        self.tk = proc.ocr_tokenizer
+        self.cache = {proc.eos_token_id: "", proc.pad_token_id: "", proc.no_output_token: ""}
+
+    def __call__(self, t: int) -> str:
+        s = self.cache.get(t)
+        if s is None:
+            tk = self.tk
+            if t >= tk.special_token_offset:
+                s = array("H", [(t - tk.special_token_offset) & 0xFFFF]).tobytes().decode("utf-16le", errors="ignore")
+            else:
+                s = tk.decode([t], task=TaskNames.ocr_without_boxes if t >= tk.qwen_offset else TaskNames.block_without_boxes)
+            self.cache[t] = s
+        return s
+
+
+def attach_alternatives(chars, csrc, alts, top_k, decode) -> None:
+    """chars[i].alternatives = the first `top_k` alternatives of token csrc[i] -- the token the character takes its confidence
+    from -- without the missing entries (id -1: fewer ids were allowed). alts = (ids [T, 4], probabilities [T, 4])."""
+    ids, pr = alts[0].tolist(), alts[1].tolist()
+    for ch, j in zip(chars, csrc):
+        ch.alternatives = [CharAlternative.model_construct(text=decode(t), confidence=p, token_id=t)
+                           for t, p in zip(ids[j][:top_k], pr[j][:top_k]) if t >= 0]
+        ch.__pydantic_fields_set__.add("alternatives")
+
+
+def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False, csrc_out=None) -> list:
     """Token stream -> per line (texts, confidences, bbox_valid, polygons [n, 4, 2]) (reference :609-771): the stream is cut
     into runs of math-BPE ids, single special tags and UTF-16 ids; only the last kind carries per-character boxes.
     Array form of the reference's per-token loop: run boundaries, close-polygon filtering and the
@@ -57,6 +88,8 @@ def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, dr
     eos, pad, nop = proc.eos_token_id, proc.pad_token_id, proc.no_output_token
     out = []
     for tokens, polys, sc in zip(predicted_tokens, predicted_polygons, scores):
+        if csrc_out is not None:
+            csrc_out.append(None)                    # replaced below for a line that has characters of its own
         if nop in tokens:
             out.append(None)
             continue
@@ -83,6 +116,8 @@ def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, dr
             pp = P[src]
             pp[~v] = _BLANK_POLY
             out.append((texts, conf[csrc], v, pp))
+            if csrc_out is not None:
+                csrc_out[-1] = csrc
     return out
 
 
@@ -145,17 +180,22 @@ def chars_of(line, res_scale, line_bbox) -> List[TextChar]:
     return [_text_char(pg, c, t, v) for pg, c, t, v in zip(polys, conf, texts, valid.tolist())]
 
 
-def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size) -> TextLine:
-    """One line's TextLine from its finished token stream (reference :609-771 + :886-925)."""
+def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size, alts=None) -> TextLine:
+    """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
+    of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
+    fix_unbalanced_tags inserts keep None)."""
     polygon, res_scale = flat["polygons"][orig], flat["res_scales"][orig]
     polys = prediction_to_polygon_batch(bbox_rows[None], [flat["slices"][sorted_pos].shape], bbox_size, bbox_size // 2)
-    chars = get_bboxes_text(proc, flat, [tokens], [sc], polys, drop_repeated_text)[0]
+    csrc = [] if alts is not None else None
+    chars = get_bboxes_text(proc, flat, [tokens], [sc], polys, drop_repeated_text, csrc_out=csrc)[0]
     if chars is None or not chars[0]:      # <NOP> (input text was good) or nothing decoded (reference :889-899)
         return TextLine(text="", polygon=polygon, chars=[], confidence=1, original_text_good=True)
     # mean of the characters' confidences as the TextChar objects hold them (NaN -> 0, schema.py), reference :899-903
     confidence = float(np.mean(np.where(np.isnan(chars[1]), 0.0, chars[1])))
     box = PolygonBox(polygon=polygon)
     chars = chars_of(chars, res_scale, box.bbox)
+    if alts is not None and csrc[0] is not None:
+        attach_alternatives(chars, csrc[0], alts, flat["top_k"], AltDecoder(proc))
     chars = fix_unbalanced_tags(chars, proc.ocr_tokenizer.special_tokens)
     text = clean_math_tags(unwrap_math("".join(c.text for c in chars)))
     return TextLine(text=text, polygon=polygon, chars=chars, confidence=confidence,
@@ -163,7 +203,8 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
 
 
 def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
-    """TextLines of several finished lines at once; items = [(sorted_pos, orig, tokens, scores, bbox_rows[T, 6])]. The same
+    """TextLines of several finished lines at once; items = [(sorted_pos, orig, tokens, scores, bbox_rows[T, 6])], with a sixth
+    element (alternative ids [T, 4], probabilities [T, 4]) when the call asked for alternatives (flat["top_k"]). The same
     result as `assemble_line` per item (tests/test_assemble_cpu.py compares the two), but the numpy work -- box tokens ->
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
@@ -171,9 +212,12 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     eos, pad, nop = proc.eos_token_id, proc.pad_token_id, proc.no_output_token
     out: List[Optional[TextLine]] = [None] * len(items)
     work, t_max = [], 0
-    for i, (sp, orig, tokens, sc, rows) in enumerate(items):
+    decode = None
+    for i, it in enumerate(items):
+        sp, orig, tokens, sc, rows = it[:5]
         if nop in tokens or (drop_repeated_text and detect_repeat_token(tokens)):
-            out[i] = assemble_line(proc, flat, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size)
+            out[i] = assemble_line(proc, flat, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size,
+                                   alts=it[5] if len(it) > 5 else None)
             continue
         n = len(tokens)
         for j, t in enumerate(tokens):
@@ -197,7 +241,7 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     far = (np.abs(P[:, 1:] - P[:, :-1]).reshape(W, t_max - 1, 8).max(axis=2) > 0.1).tolist() if t_max > 1 else [[]] * W
     keep, all_w, all_src, all_conf, all_valid, counts, geo = [], [], [], [], [], [], []
     for w, (i, n) in enumerate(work):
-        sp, orig, tokens, sc, rows = items[i]
+        sp, orig, tokens, sc, rows = items[i][:5]
         texts, src, csrc, valid = line_runs(proc, tokens[:n], far[w])
         if not texts:                      # nothing decoded (reference :889-899)
             out[i] = TextLine(text="", polygon=flat["polygons"][orig], chars=[], confidence=1, original_text_good=True)
@@ -206,7 +250,7 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
         xs, ys = [p[0] for p in polygon], [p[1] for p in polygon]
         bbox = [min(xs), min(ys), max(xs), max(ys)]
         rs = flat["res_scales"][orig]
-        keep.append((i, texts, valid, polygon, bbox))
+        keep.append((i, texts, valid, polygon, bbox, csrc))
         all_w.extend([w] * len(src)); all_src.extend(src); all_valid.extend(valid)
         all_conf.extend([0.0 if sc[j] != sc[j] else sc[j] for j in csrc])          # TextChar's NaN -> 0 rule
         counts.append(len(src))
@@ -223,11 +267,14 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     conf_arr = np.asarray(all_conf, np.float64)
     special = proc.ocr_tokenizer.special_tokens
     a = 0
-    for (i, texts, valid, polygon, bbox), c in zip(keep, counts):
+    for (i, texts, valid, polygon, bbox, csrc), c in zip(keep, counts):
         b = a + c
         confidence = float(np.mean(conf_arr[a:b]))
         chars = [_text_char(pg, cf, t, v) for pg, cf, t, v in zip(polys[a:b], all_conf[a:b], texts, valid)]
         a = b
+        if len(items[i]) > 5 and items[i][5] is not None:
+            decode = decode or AltDecoder(proc)
+            attach_alternatives(chars, csrc, items[i][5], flat["top_k"], decode)
         if not all(valid):                                   # tags only come from special / math runs (bbox_valid False)
             chars = fix_unbalanced_tags(chars, special)
             text = "".join(ch.text for ch in chars)

@@ -12,6 +12,7 @@ from .postprocess import detect_repeat_token
 FEED_END = object()          # what a `generate(feed=...)` callable returns once no further lines will come
 _REP = 40                    # detect_repeat_token's window
 _REP_COLS = np.arange(-_REP, 0)
+SA_MAX_ALTERNATIVES = 4      # alternatives the model reports per token (include/surya_amd.h)
 
 
 class DeviceLoop:
@@ -28,9 +29,16 @@ class DeviceLoop:
     Constrained output: the dict handed to `run` may carry "token_masks" (uint32 [n, words], the call's distinct allowed-id sets,
     uploaded once before the first prefill) and every admitted dict "mask_ids" (one row id per prompt, -1 = unconstrained). A line's
     id stays with the line: it is set on whatever slot the line is prefilled into, so a slot that is reused takes its new line's id.
-    Without "token_masks" the model's mask entry points are never called."""
+    Without "token_masks" the model's mask entry points are never called.
 
-    def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None):
+    Alternatives (`alternatives=True`): the model reports the SA_MAX_ALTERNATIVES most likely tokens of every step; the loop keeps
+    them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
+    line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
+    exception. Not requested: the arrays do not exist, on_done keeps its four arguments and the model's three entry points
+    (set_alternatives / read_alternatives / wait_alternatives) are never called -- a model without them works."""
+
+    def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None,
+                 alternatives=False):
         self.model, self.eos, self.pad, self.nop, self.slots = model, eos, pad, nop, slots
         self.overall_max_tokens, self.min_prefill_ratio = overall_max_tokens, min_prefill_ratio
         self.on_done, self.on_flush, self.feed, self.feed_done = on_done, on_flush, feed, feed is None
@@ -49,6 +57,9 @@ class DeviceLoop:
         self.sc_mat = np.zeros((0, self.cap), np.float32)
         self.line_len, self.max_tok = np.zeros(0, np.int64), np.zeros(0, np.int64)      # tokens so far / token budget per line
         self.slot_line = np.full(slots, -1, np.int64)
+        self.alternatives = bool(alternatives)
+        self.alt_tok_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.int32) if self.alternatives else None
+        self.alt_p_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.float32) if self.alternatives else None
         self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
         self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
@@ -85,6 +96,9 @@ class DeviceLoop:
         self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((m, self.overall_max_tokens, 6), np.float32)])
         self.tok_mat = np.concatenate([self.tok_mat, np.zeros((m, self.cap), np.int64)])
         self.sc_mat = np.concatenate([self.sc_mat, np.zeros((m, self.cap), np.float32)])
+        if self.alternatives:
+            self.alt_tok_mat = np.concatenate([self.alt_tok_mat, np.full((m, self.cap, SA_MAX_ALTERNATIVES), -1, np.int32)])
+            self.alt_p_mat = np.concatenate([self.alt_p_mat, np.zeros((m, self.cap, SA_MAX_ALTERNATIVES), np.float32)])
         self.line_len = np.concatenate([self.line_len, np.zeros(m, np.int64)])
         self.max_tok = np.concatenate([self.max_tok, mt])
         mk = d.get("mask_ids")
@@ -117,13 +131,17 @@ class DeviceLoop:
         self.predicted_tokens[p_idx] = self.tok_mat[p_idx, :L_].tolist()
         self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
         if self.on_done is not None:
+            more = (self.alt_tok_mat[p_idx, :L_].copy(), self.alt_p_mat[p_idx, :L_].copy()) if self.alternatives else ()
             self.on_done(p_idx, self.predicted_tokens[p_idx], self.scores[p_idx],
-                         self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)])
+                         self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)], *more)
 
-    def _put(self, p, pos, t, s_, b_):
-        """Token t / score s_ / box b_ of lines p at positions pos (arrays over the lines of one step)."""
+    def _put(self, p, pos, t, s_, b_, at=None, ap=None):
+        """Token t / score s_ / box b_ (/ alternatives at, ap) of lines p at positions pos (arrays over the lines of one step)."""
         self.tok_mat[p, pos] = t
         self.sc_mat[p, pos] = s_
+        if at is not None:
+            self.alt_tok_mat[p, pos] = at
+            self.alt_p_mat[p, pos] = ap
         m = pos < self.overall_max_tokens
         if m.all():
             self.batch_bboxes[p, pos] = b_
@@ -141,6 +159,7 @@ class DeviceLoop:
         """Host half of one decode call: append its tokens, apply the stop rules (reference :583-595)."""
         k, ring = call
         tok, sc, bb = self.model.wait_outputs(k, ring)
+        at, ap = self.model.wait_alternatives(k, ring) if self.alternatives else (None, None)
         slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
         changed = False
         for step in range(k):
@@ -150,7 +169,10 @@ class DeviceLoop:
             p = slot_line[s_idx]
             pos = line_len[p]
             t = tok[step, s_idx]
-            self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
+            if at is None:
+                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
+            else:
+                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], at[step, s_idx], ap[step, s_idx])
             new_len = pos + 1
             stop = (t == eos) | (t == pad) | (new_len >= max_tok[p])
             # repeat rule: <= 5 distinct ids in the last 40 and the last u ids equal to the u before; the distinct count is
@@ -213,7 +235,11 @@ class DeviceLoop:
         tok, sc, bb = self.model.read_outputs(1)
         ids_, sl_ = np.asarray(take, np.int64), np.asarray(slots, np.int64)
         first = tok[0, sl_]
-        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_])
+        more = ()
+        if self.alternatives:                                       # the first token has alternatives too
+            at, ap = self.model.read_alternatives(1)
+            more = (at[0, sl_], ap[0, sl_])
+        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more)
         for p_id, s, go in zip(take, slots, ((first != self.eos) & (first != self.nop)).tolist()):
             if go:                                                  # prefill stop rule (reference :559-563)
                 self.slot_line[s] = p_id
@@ -223,6 +249,15 @@ class DeviceLoop:
 
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
+        if not self.alternatives:
+            return self._run_masked(prep)
+        self.model.set_alternatives(True)
+        try:
+            return self._run_masked(prep)
+        finally:
+            self.model.set_alternatives(False)         # the next call starts on the kernels without candidates
+
+    def _run_masked(self, prep):
         table = None if prep is None else prep.get("token_masks")
         if table is None or len(table) == 0:
             return self._run(prep)

@@ -67,6 +67,8 @@ class HipRecModel:
         self._bbox = np.zeros((L.SA_MAX_STEPS, max_slots, 6), np.int32)
         self.mx_weights = None
         self.n_token_masks = 0
+        self.alternatives = False
+        self._alt_tok = self._alt_p = None              # host arrays of read_alternatives / wait_alternatives, made on first use
         self.decode_fp8 = False
         if decode_fp8 is None:
             from ..settings import settings
@@ -129,6 +131,35 @@ class HipRecModel:
         assert s.shape == m.shape and s.ndim == 1
         L.check(self.lib.surya_rec_set_slot_masks(self.handle, L.np_ptr(s), L.np_ptr(m), C.c_int(len(s)), self._stream),
                 "surya_rec_set_slot_masks")
+
+    def set_alternatives(self, on: bool):
+        """Report the SA_MAX_ALTERNATIVES most likely (allowed) tokens of every step beside the token itself (surya_rec_set_alternatives).
+        Off (the default) the handle launches the kernels it always launched; tokens, scores and boxes are the same either way."""
+        L.check(self.lib.surya_rec_set_alternatives(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_alternatives")
+        self.alternatives = bool(on)
+        if on and self._alt_tok is None:
+            self._alt_tok = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.int32)
+            self._alt_p = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.float32)
+
+    def _alt_bufs(self, first):
+        if self._alt_tok is None:       # never switched on: the library refuses below, with buffers it may not write to anyway
+            return np.zeros((1, 1, L.SA_MAX_ALTERNATIVES), np.int32), np.zeros((1, 1, L.SA_MAX_ALTERNATIVES), np.float32)
+        return self._alt_tok[first:], self._alt_p[first:]
+
+    def read_alternatives(self, n_steps: int = 1):
+        """Sync; (tokens [n_steps, slots, 4] int32, -1 = fewer ids allowed; probs [n_steps, slots, 4]) of the steps read_outputs returns,
+        best first: entry 0 is the emitted token."""
+        tok, pr = self._alt_bufs(0)
+        L.check(self.lib.surya_rec_read_alternatives(self.handle, C.c_int(n_steps), L.np_ptr(tok), L.np_ptr(pr, C.c_float), self._stream),
+                "surya_rec_read_alternatives")
+        return tok[:n_steps], pr[:n_steps]
+
+    def wait_alternatives(self, n_steps: int, ring: int):
+        """The alternatives of the decode_async call on `ring`, parallel to wait_outputs."""
+        tok, pr = self._alt_bufs(ring * (L.SA_MAX_STEPS // 2))
+        L.check(self.lib.surya_rec_wait_alternatives(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(tok), L.np_ptr(pr, C.c_float)),
+                "surya_rec_wait_alternatives")
+        return tok[:n_steps], pr[:n_steps]
 
     def __del__(self):
         h = getattr(self, "handle", None)

@@ -163,10 +163,11 @@ class AssemblyHandover(ThreadPoolExecutor):
 
     def assemble(self, batch):
         # batch = [(line id, tokens, scores, bbox_rows)]: the lines that stopped at one synchronisation point
-        return self.pred._assemble_batch(self.flat, [(k, self.orig_of[k], t, sc, bb) for k, t, sc, bb in batch], *self.options)
+        return self.pred._assemble_batch(self.flat, [(b[0], self.orig_of[b[0]]) + tuple(b[1:]) for b in batch], *self.options)
 
-    def on_done(self, k, tokens, sc, bbox_rows):
-        self.pending.append((k, list(tokens), list(sc), bbox_rows.copy()))
+    def on_done(self, k, tokens, sc, bbox_rows, *alts):
+        # alts: (alternative ids [T, 4], probabilities [T, 4]) of a call with top_k, else nothing
+        self.pending.append((k, list(tokens), list(sc), bbox_rows.copy()) + ((alts,) if alts else ()))
 
     def on_flush(self):
         if self.pending:
@@ -366,14 +367,17 @@ class RecognitionPredictor(BasePredictor):
         first = prep if prep is not None else {}
         overall_max_tokens = int(first.get("overall_max_tokens") or max(first["max_tokens"].values()))
         proc = self.processor
+        more = {"alternatives": True} if self._top_k is not None else {}      # (only then: a stand-in loop keeps its signature)
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
                           min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
-                          on_done=on_done, on_flush=on_flush, feed=feed)
+                          on_done=on_done, on_flush=on_flush, feed=feed, **more)
         loop.run(prep)
         # the loop's own dense bookkeeping (ids [n, cap], scores [n, cap], lengths): what the sharded loop packs for its all_gather
         # without walking the per-line lists again
         from ..dist import PackedLines
         self.last_packed = (PackedLines(loop.tok_mat, loop.line_len), PackedLines(loop.sc_mat, loop.line_len))
+        if more:                                              # ... and the alternatives [n, cap, 4] likewise
+            self.last_alternatives = (PackedLines(loop.alt_tok_mat, loop.line_len), PackedLines(loop.alt_p_mat, loop.line_len))
         return loop.predicted_tokens, torch.from_numpy(loop.batch_bboxes), loop.scores
 
     def prediction_loop(self, flat: dict, recognition_batch_size: int | None = None, math_mode: bool = True) -> tuple:
@@ -407,6 +411,7 @@ class RecognitionPredictor(BasePredictor):
         if flat.get("token_masks") is not None:               # every rank holds the whole table; the ids travel with the lines
             local.update(token_masks=flat["token_masks"], mask_ids=[flat["mask_ids"][i] for i in mine])
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
+        alts = None
         if mine:
             self.last_packed = None                          # only what generate() sets DURING this call counts (a stand-in prediction_loop
             toks, boxes, scores = self.prediction_loop(local, recognition_batch_size, math_mode)      # must not gather an earlier call's arrays)
@@ -414,11 +419,20 @@ class RecognitionPredictor(BasePredictor):
             if packed is not None and len(packed[0]) == len(toks):      # generate()'s dense arrays: no per-token Python in the pack
                 toks, scores = packed
             self.last_packed = None                          # (and the [n, cap] matrices are not pinned on the predictor between calls)
+            alts, self.last_alternatives = getattr(self, "last_alternatives", None), None
             boxes = boxes.numpy()
             if boxes.shape[1] < max_tokens:
                 boxes = np.pad(boxes, ((0, 0), (0, max_tokens - boxes.shape[1]), (0, 0)))
         else:
             toks, scores, boxes = [], [], np.zeros((0, max_tokens, 6), np.float32)
+        if self._top_k is not None:                          # the two alternative arrays ride in the same collective
+            if alts is None:
+                alts = (sdist.PackedLines(np.zeros((0, max_tokens, 4), np.int32), np.zeros(0, np.int64)),
+                        sdist.PackedLines(np.zeros((0, max_tokens, 4), np.float32), np.zeros(0, np.int64)))
+            toks, scores, boxes, a_tok, a_p = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group,
+                                                                        alts=alts)
+            self.last_alternatives = (a_tok, a_p)
+            return toks, torch.from_numpy(boxes), scores
         toks, scores, boxes = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group)
         return toks, torch.from_numpy(boxes), scores
 
@@ -453,12 +467,37 @@ class RecognitionPredictor(BasePredictor):
                  polygons: List[List[List[List[int]]]] | None = None, input_text: List[List[str | None]] | None = None,
                  sort_lines: bool = False, math_mode: bool = True, return_words: bool = False,
                  drop_repeated_text: bool = False, allowlist=None, blocklist=None) -> List[OCRResult]:
-        """`allowlist` / `blocklist` (not in the reference; keywords after its own arguments) restrict the characters a line may
+        """`self.top_k` (an attribute like `shard_lines`: the call's signature ends with the two lists; None = off, else 2..4): every
+        TextChar also carries `alternatives`, the top_k most likely readings of the token it takes its confidence from, best first
+        (entry 0 is the character's own), with `allowlist` / `blocklist` the most likely ALLOWED readings. Texts, confidences and boxes
+        do not change. Anything else raises ValueError before any device work.
+
+        `allowlist` / `blocklist` (not in the reference; keywords after its own arguments) restrict the characters a line may
         contain -- "0123456789.,-" for a numeric column. Each is a str for every line of the call, or a list with one entry per image:
         None, a str, or a list with one None / str per bbox / polygon of that image (not with det_predictor: the lines are not known
         yet). A line takes one of the two, not both. Tokens and confidences are the reference's process_outputs on logits whose
         disallowed ids are -inf, so a confidence is the softmax over the allowed set; EOS, pad and no-output stay allowed, formatting and
         math tags do not under an allowlist (OCRTokenizer.token_mask). Stop rules, sorting and assembly are unchanged."""
+        top_k = self.top_k
+        if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= 4):
+            raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
+        # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
+        # page-sharded path and by stand-ins and read it from here)
+        saved_k, self._top_k = self._top_k, top_k
+        try:
+            return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
+                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist)
+        finally:
+            self._top_k = saved_k
+            if top_k is not None:
+                self.last_alternatives = None
+
+    top_k: int | None = None          # alternatives per character (2..4), None = off: RecognitionPredictor.top_k = 3, or on an instance
+    _top_k = None                     # the running call's validated top_k (see __call__)
+    last_alternatives = None
+
+    def _call_gc_paused(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
+                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist):
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
             # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
@@ -519,6 +558,8 @@ class RecognitionPredictor(BasePredictor):
         if len(flat["slices"]) == 0:
             return []
         stamps["slice_ms"] = (time.perf_counter() - t_call) * 1e3
+        if self._top_k is not None:
+            flat["top_k"] = self._top_k
         sorted_keys = ("slices", "input_text", "task_names")
         if cons is not None:                                  # by line id like the slices: sorted with them below
             flat["token_masks"], flat["mask_ids"] = cons.table.array(), cons.line_ids(flat["slice_map"])
@@ -535,7 +576,9 @@ class RecognitionPredictor(BasePredictor):
                 predicted_tokens, batch_bboxes, scores = self.sharded_prediction_loop(flat, recognition_batch_size, math_mode)
                 bb = batch_bboxes.numpy()
                 chunks = [range(a, min(a + 256, len(order))) for a in range(0, len(order), 256)]
-                text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) for k in ks])) for ks in chunks)
+                la = self.last_alternatives if self._top_k is not None else None
+                alt_of = (lambda k: ()) if la is None else (lambda k: ((la[0].row(k), la[1].row(k)),))
+                text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) + alt_of(k) for k in ks])) for ks in chunks)
             else:
                 t0 = time.perf_counter()
                 prep = self.prepare_lines(flat, math_mode)
@@ -640,6 +683,8 @@ class RecognitionPredictor(BasePredictor):
         import sys
         import threading
         flat = new_flat()
+        if self._top_k is not None:
+            flat["top_k"] = self._top_k
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])

@@ -4,7 +4,9 @@ from __future__ import annotations
 import math
 from typing import List, Optional
 
-from pydantic import BaseModel, field_validator
+import inspect
+
+from pydantic import BaseModel, Field, field_validator, model_serializer
 
 from ..common.geometry import PolygonBox
 
@@ -33,8 +35,34 @@ class BaseChar(PolygonBox):
             return v
 
 
+class CharAlternative(BaseModel):
+    """One reading of a character (RecognitionPredictor.top_k): the decoded token, its probability among the allowed tokens,
+    and the token id (a lone UTF-16 surrogate has no text of its own: "" with its id kept)."""
+    text: str
+    confidence: float
+    token_id: int
+
+
+_EXCLUDE_IF = "exclude_if" in inspect.signature(Field).parameters          # pydantic >= 2.12: the exclusion runs inside pydantic-core
+
+
 class TextChar(BaseChar):
     bbox_valid: bool = True
+    # the `top_k` most likely readings, best first (entry 0 is the character's own); None unless the call asked for them, and
+    # then left out of the serialised form, which stays the reference's (model_json_schema lists the field all the same). The
+    # exclusion costs model_dump one predicate call per character (tools/hostbench/dump_cost.py: no difference to a TextChar
+    # without the field at 3.6-5 us per character; the wrap serialiser that older pydantic needs takes 3.6 to 9.7 us).
+    if _EXCLUDE_IF:
+        alternatives: Optional[List[CharAlternative]] = Field(default=None, exclude_if=lambda v: v is None)
+    else:
+        alternatives: Optional[List[CharAlternative]] = None
+
+        @model_serializer(mode="wrap")
+        def _without_absent_alternatives(self, handler):
+            d = handler(self)
+            if self.alternatives is None:
+                d.pop("alternatives", None)
+            return d
 
 
 class TextWord(BaseChar):

@@ -5,7 +5,7 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
@@ -16,6 +16,9 @@ arm of the same arithmetic (fp8 with fp8, bf16 with bf16).
 `masks`: the unmasked step against the step with a token mask on EVERY slot (HipRecModel.set_token_masks: the masked lm_head
 epilogues), arms alternating none / digits allowlist / none / random 50 % mask / none. Tokens are compared with the first arm of the
 same mask. `maskonly`: the digits arm alone.
+
+`alts`: alternatives (HipRecModel.set_alternatives: the *_TOPK lm_head epilogue and the combine kernel behind the head) off / on / off /
+on / off, alternating; tokens must be identical to the first arm. `altsonly`: the "on" arm alone (for a kernel trace beside `base`).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -90,6 +93,10 @@ def main():
         variants = [dict(), dict(masks=1), dict(), dict(masks=2), dict()]
     elif args.configs == "maskonly":     # one arm, a digits allowlist on every slot (for a kernel trace beside `base`)
         variants = [dict(masks=1)]
+    elif args.configs == "alts":         # alternatives: off against on, alternating
+        variants = [dict(), dict(alts=1), dict(), dict(alts=1), dict()]
+    elif args.configs == "altsonly":
+        variants = [dict(alts=1)]
     elif args.configs == "pf":           # K/V prefetch workgroups in the reduce kernels, on / off, interleaved
         variants = [dict(kvprefetch=1), dict(), dict(kvprefetch=1), dict(), dict(lmhead=2, kvprefetch=1), dict(lmhead=2)]
     elif args.configs == "fp8only":
@@ -115,6 +122,8 @@ def main():
             if i + 1 < len(calls):
                 m.decode_async(*calls[i + 1])
             t, _, _ = m.wait_outputs(*call)
+            if m.alternatives:
+                m.wait_alternatives(*call)               # what the device loop reads beside the tokens
             toks.append(t[: call[0], :n].copy())
         e1.record()
         torch.cuda.synchronize()
@@ -139,12 +148,17 @@ def main():
         v = dict(v)
         m.set_decode_fp8(bool(v.pop("fp8", int(args.fp8))))
         masks = v.pop("masks", 0)
+        alts = v.pop("alts", 0)
+        if alts or args.configs in ("alts", "altsonly"):
+            m.set_alternatives(bool(alts))
         if masks or args.configs in ("masks", "maskonly"):
             set_masks(masks)
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
         if args.configs in ("masks", "maskonly"):
             v["masks"] = masks
+        if args.configs in ("alts", "altsonly"):
+            v["alts"] = alts
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
@@ -154,6 +168,8 @@ def main():
     m.set_decode_fp8(False)
     if args.configs in ("masks", "maskonly"):
         m.set_token_masks(None)
+    if args.configs in ("alts", "altsonly"):
+        m.set_alternatives(False)
 
 
 if __name__ == "__main__":
