@@ -253,6 +253,32 @@ int surya_rec_set_alternatives(surya_rec* h, int on);
 int surya_rec_read_alternatives(surya_rec* h, int n_steps, int32_t* tokens, float* probs, void* stream);
 int surya_rec_wait_alternatives(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* probs);
 
+/* Forced decoding: align a known transcription. Given a line and its token ids, every step emits the forced id instead of the greedy one and
+ * reports how likely the model found it -- what a caller of the reference gets from teacher-forcing input_ids and reading
+ * log_softmax(next_token_logits)[forced]. Logits never exist outside a tile here and the next step's input is chosen on the device, so the
+ * lm_head's *_FORCED epilogues pick the forced column's logit up where the partials are, and the greedy head feeds the forced id on.
+ * A slot's ids are consumed one per head pass (the prefill's included: the first token of a line is forced too); a slot past the end of its
+ * ids, or with none, free-runs with the bits of a handle that never switched the feature on. Under forcing token = the forced id,
+ * score = p(id | image, preceding ids) (0 for eos / pad, as ever), and the box is the one predicted from the forced prefix.
+ *   set_forced:  on = 0 / 1, anything else SA_ERR_ARG. The first switch-on allocates the id table [max_slots][SA_MAX_FORCED_TOKENS] (-1), the
+ *                cursors and the outputs with their pinned mirror; a handle that never switches it on allocates nothing and launches exactly
+ *                what it launched before this entry existed. Addresses never change afterwards. Switching drops captured decode steps;
+ *                switch-off sets the table back to -1. SA_ERR_STATE while token masks or alternatives are on, and surya_rec_set_token_masks
+ *                (n_masks > 0) / surya_rec_set_alternatives(1) return SA_ERR_STATE while forcing is on. Call while no line is in flight.
+ *   set_forced_tokens: slot slots[i] gets tokens[offsets[i] .. offsets[i + 1]) (HOST arrays, offsets [n + 1]), -1 behind them, cursor 0; call
+ *                it for the slots about to be prefilled, like surya_rec_set_slot_masks. Length 0: the slot free-runs. SA_ERR_STATE while
+ *                off; SA_ERR_ARG, with nothing changed, for a slot named twice or out of range, an id outside [0, vocab) or a length above
+ *                SA_MAX_FORCED_TOKENS.
+ *   read_forced / wait_forced: [n_steps][max_slots] greedy_tokens (the model's own argmax), greedy_probs (its probability, 1 / total) and
+ *                forced_logprobs (log p of the emitted token: the forced id, or the greedy one on a free-running slot) of the steps
+ *                surya_rec_read_outputs / surya_rec_wait_outputs return, same indexing; surya_rec_decode_async mirrors the ring half
+ *                behind the same event. SA_ERR_STATE while off, and from wait_forced for a ring half whose decode_async ran while off. */
+#define SA_MAX_FORCED_TOKENS 1024
+int surya_rec_set_forced(surya_rec* h, int on);
+int surya_rec_set_forced_tokens(surya_rec* h, const int32_t* slots, const int32_t* tokens, const int32_t* offsets, int n, void* stream);
+int surya_rec_read_forced(surya_rec* h, int n_steps, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs, void* stream);
+int surya_rec_wait_forced(surya_rec* h, int n_steps, int ring, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -338,6 +364,11 @@ int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const vo
 int surya_op_lm_head_topk(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
                           const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, float* alt, int* bn_used,
                           int32_t* top_tokens, float* top_probs, int32_t* head_token, float* head_score, float* scratch, void* stream);
+/* surya_op_lm_head_partials with the *_FORCED epilogue (same launchers; no masks): beside amax, which has the bits of the unmasked launch,
+ * flogit[m] receives the accumulator-plus-bias value of column forced_col[m] (DEVICE int32 [M]) from the one tile that holds it; rows with
+ * forced_col -1 (or outside [0, N)) are left untouched. Enqueue only. */
+int surya_op_lm_head_forced(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                            const int32_t* forced_col, float* amax, float* flogit, int* bn_used, void* stream);
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream);
 

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.s
 
 SA_MAX_STEPS = 16
 SA_MAX_ALTERNATIVES = 4                         # alternatives per token (surya_rec_set_alternatives); top_k < 4 is a slice on the host
+SA_MAX_FORCED_TOKENS = 1024                     # forced ids per slot (surya_rec_set_forced_tokens)
 SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
 OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
@@ -111,6 +112,13 @@ def _bind_lay_ops(lib):
     lib.surya_rec_wait_alternatives.argtypes, lib.surya_rec_wait_alternatives.restype = [p, i, i, ip, C.POINTER(C.c_float)], C.c_int
     lib.surya_op_lm_head_topk.argtypes = [i, p, p, p, p, p, i, i, i, p, p, p, p, p, ip, p, p, p, p, p, p]
     lib.surya_op_lm_head_topk.restype = C.c_int
+    # forced decoding (align a known transcription) and the *_FORCED lm_head launch by itself
+    fp = C.POINTER(C.c_float)
+    lib.surya_rec_set_forced.argtypes, lib.surya_rec_set_forced.restype = [p, i], C.c_int
+    lib.surya_rec_set_forced_tokens.argtypes, lib.surya_rec_set_forced_tokens.restype = [p, ip, ip, ip, i, p], C.c_int
+    lib.surya_rec_read_forced.argtypes, lib.surya_rec_read_forced.restype = [p, i, ip, fp, fp, p], C.c_int
+    lib.surya_rec_wait_forced.argtypes, lib.surya_rec_wait_forced.restype = [p, i, i, ip, fp, fp], C.c_int
+    lib.surya_op_lm_head_forced.argtypes, lib.surya_op_lm_head_forced.restype = [i, p, p, p, p, p, i, i, i, p, p, p, ip, p], C.c_int
 
 
 def check(rc: int, what: str):

@@ -37,8 +37,9 @@ namespace sa {
 enum GemmEpi { EPI_BIAS = 0, EPI_RESIDUAL = 1, EPI_GELU = 2, EPI_SWIGLU = 3, EPI_HARDSWISH = 4, EPI_RELU = 5, EPI_ARGMAX = 6, EPI_ROPE = 7,
                EPI_GEGLU = 8 /* gelu_tanh(gate) * up, rows interleaved like SWIGLU (ADETR decoder MLP, adetr/decoder.py:331-344) */,
                EPI_ARGMAX_MASK = 9 /* EPI_ARGMAX over the columns a per-row token mask allows (TokenMask below) */,
-               EPI_TOPK = 10 /* EPI_ARGMAX_MASK (an absent table = unconstrained) + the tile's SA_MAX_ALTERNATIVES best allowed columns */ };
-constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_MASK || epi == EPI_TOPK; }
+               EPI_TOPK = 10 /* EPI_ARGMAX_MASK (an absent table = unconstrained) + the tile's SA_MAX_ALTERNATIVES best allowed columns */,
+               EPI_FORCED = 11 /* EPI_ARGMAX + the logit of each row's forced column (ForcedCols below) */ };
+constexpr bool epi_is_argmax(int epi) { return epi == EPI_ARGMAX || epi == EPI_ARGMAX_MASK || epi == EPI_TOPK || epi == EPI_FORCED; }
 constexpr bool epi_is_masked(int epi) { return epi == EPI_ARGMAX_MASK || epi == EPI_TOPK; }
 
 // Allowed-column sets of the greedy-partial epilogues (EPI_ARGMAX_MASK here, MX_EPI_ARGMAX_MASK in gemm_mx.h). Row m of the GEMM belongs
@@ -68,6 +69,25 @@ struct TokenMask {
     }
 };
 
+// Forced decoding (EPI_FORCED here, MX_EPI_FORCED in gemm_mx.h): beside the unmasked greedy partial, the one tile that holds a row's forced
+// column stores that column's accumulator-plus-bias value -- the tile's own fp32 number, the one the max pass compared -- to flogit[m].
+// Row m belongs to slot row_slot[m]; its forced column is table[slot][cursor[slot]], -1 (or a cursor outside [0, stride), or a column
+// outside [0, N)) = free-running: nothing is written for that row. cursor = nullptr: position 0 (the op hook: table = one column per row).
+struct ForcedCols {
+    const int* table = nullptr;        // [slots][stride]
+    const int* cursor = nullptr;       // [slots]
+    const int* row_slot = nullptr;     // [M]; nullptr: row m is slot m
+    int stride = 0;
+    float* flogit = nullptr;           // [M]
+    __device__ __forceinline__ int col_of(int m, int M, int N) const {
+        if (m >= M) return -1;
+        const int slot = row_slot ? row_slot[m] : m;
+        const int cur = cursor ? cursor[slot] : 0;
+        const int c = table[(long)slot * stride + min(max(cur, 0), stride - 1)];
+        return (cur >= 0 && cur < stride && c < N) ? c : -1;
+    }
+};
+
 template <typename TI, typename TO>
 struct GemmArgs {
     const TI* X; long ldx;       // [M, K]
@@ -88,6 +108,7 @@ struct GemmArgs {
     // EPI_TOPK: beside amax, the tile's SA_MAX_ALTERNATIVES best allowed columns inside N as {value, column bits}, best first, at
     // alt[(m * cdiv(N, bn_used) + tile_n) * 4 + j]; entry 0 is (max, argmax) of the amax partial, missing entries are (-inf, 0x7fffffff)
     float2* alt = nullptr;
+    ForcedCols forced;           // EPI_FORCED
     // EPI_ROPE (vision qkv projection): rotary embedding of the q and k columns (n < rope_cols) in the epilogue. The weight
     // rows of every head are stored PAIR-INTERLEAVED (new column 2j = old j, 2j + 1 = old j + D/2), so the lane that owns
     // four consecutive columns holds two complete rotate_half pairs; rope[m * (D/2) + j] = (cos, sin) of token m, pair j.
@@ -269,6 +290,50 @@ __device__ __forceinline__ void topk_partial_masked(const unsigned char* smem, c
         if (writer) arow[t] = make_float2(cb, __int_as_float(ci));
         pv = cb;
         pc = ci;
+    }
+}
+
+// The unmasked greedy partial of one staged fp32 tile -- the statements of the EPI_ARGMAX / MX_EPI_ARGMAX epilogues, so the record has their
+// bits -- plus the staged value of the row's forced column where this tile holds it (EPI_FORCED / MX_EPI_FORCED; ForcedCols above).
+template <int BM, int NT, int CPR, int XM>
+__device__ __forceinline__ void argmax_partial_forced(const unsigned char* smem, const ForcedCols& fc, int m0, int n0, int M, int N,
+                                                      float4* amax, int tiles_n, int tile_n) {
+    constexpr int TPR = NT / BM, SEG = CPR / TPR, ROWB = CPR * 16;
+    static_assert(NT % BM == 0 && (TPR & (TPR - 1)) == 0 && TPR <= 8 && CPR % TPR == 0, "argmax epilogue split");
+    const int tid = threadIdx.x, row = tid / TPR, part = tid % TPR;
+    const unsigned char* rowp = smem + row * ROWB;
+    float best = -INFINITY;
+    int bi = 0x7fffffff;
+#pragma unroll 4
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N && v[i] > best) { best = v[i]; bi = n + i; }     // strict >: first maximum wins
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    float se = 0.f;
+#pragma unroll 4
+    for (int cc = 0; cc < SEG; ++cc) {
+        const int c = part * SEG + cc, n = n0 + c * 4;
+        const f32x4 v = *reinterpret_cast<const f32x4*>(rowp + ((c ^ (row & XM)) << 4));
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            if (n + i < N) se += expf(v[i] - best);
+    }
+#pragma unroll
+    for (int o = 1; o < TPR; o <<= 1) se += __shfl_xor(se, o, 64);
+    if (part == 0 && m0 + row < M) {
+        amax[(long)(m0 + row) * tiles_n + tile_n] = make_float4(best, __int_as_float(bi), se, 0.f);
+        const int rel = fc.col_of(m0 + row, M, N) - n0;           // free-running: negative
+        if (rel >= 0 && rel < CPR * 4)
+            fc.flogit[m0 + row] = *reinterpret_cast<const float*>(rowp + (((rel >> 2) ^ (row & XM)) << 4) + (rel & 3) * 4);
     }
 }
 
@@ -865,6 +930,17 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
         if constexpr (EPI == EPI_TOPK)
             static_assert((size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * MWS * 4 + 16 + (size_t)BM * WN * SA_MAX_ALTERNATIVES * 8 <= (size_t)(BM + BN) * 256,
                           "candidate lists fit the staging LDS");
+        // EPI_FORCED: the row's forced column as a tile-relative offset, [BM] ints where the masked epilogues keep their mask words; -1 where
+        // the column is not in this tile (or the row is free-running). One thread per row resolves row -> slot -> cursor -> column once.
+        [[maybe_unused]] int* fcol_s = reinterpret_cast<int*>(smem + (size_t)BM * WN * 16 + (size_t)BN * 4);
+        if constexpr (EPI == EPI_FORCED) {
+            static_assert(WTN == FN * 32 && NT >= BM && (size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * 4 <= (size_t)(BM + BN) * 256,
+                          "forced offsets fit the staging LDS");
+            if (tid < BM) {
+                const int rel = p.forced.col_of(m0 + tid, p.M, p.N) - n0;
+                fcol_s[tid] = ((rel >= 0) & (rel < BN)) ? rel : -1;
+            }
+        }
         if constexpr (epi_is_masked(EPI)) {
             static_assert(BN % 32 == 0 && WTN == FN * 32 && NT >= BM && (size_t)BM * WN * 16 + (size_t)BN * 4 + (size_t)BM * MWS * 4 <= (size_t)(BM + BN) * 256,
                           "mask words fit the staging LDS");
@@ -953,6 +1029,22 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
                     }
             se += __shfl_xor(se, 32, 64);
             if (lane < 32) rec[(wm * WTM + i * 32 + lane) * WN + wn] = make_float4(best, __int_as_float(bi), se, 0.f);
+            if constexpr (EPI == EPI_FORCED) {
+                // the lane that holds the row's forced column keeps its value: one compare-and-select pass over the row block's accumulators
+                // against the column's offset from the lane's base (compile-time offsets, selects, the accumulators only read). A lane's
+                // offsets are j * 32 + g * 8 + r with r < 4: bit 2 clear, below WTN.
+                const int frow = wm * WTM + i * 32 + (lane & 31);
+                const int d = fcol_s[frow] - (wn * WTN + (lane >> 5) * 4);
+                float fv = 0.f;
+#pragma unroll
+                for (int j = 0; j < FN; ++j)
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) fv = (d == j * 32 + g * 8 + r) ? acc[j][i][4 * g + r] : fv;
+                const bool owner = (d >= 0) & (d < WTN) & ((d & 4) == 0) & (m0 + frow < p.M);
+                if (owner) p.forced.flogit[m0 + frow] = fv;
+            }
             if constexpr (EPI == EPI_TOPK) {
                 // the wave's four best columns of this row: pass t takes the best (value, column) strictly after pass t - 1's winner. The
                 // accumulators are only read; a lane's offsets ascend, so strict > keeps the first of equal values, and an offset comes
@@ -1125,6 +1217,11 @@ __global__ __launch_bounds__(64 * WM * WN) void gemm_nt_kernel(GemmArgs<TI, TO> 
     if constexpr (EPI == EPI_TOPK) {
         static_assert(!SPLIT && std::is_same<TO, float>::value, "argmax epilogue works on fp32 tiles");
         topk_partial_masked<BM, NT, CPR, XM>(smem, p.tmask, m0, n0, p.M, p.N, p.amax, p.alt, tiles_n, tile_n);
+        return;
+    }
+    if constexpr (EPI == EPI_FORCED) {
+        static_assert(!SPLIT && std::is_same<TO, float>::value, "argmax epilogue works on fp32 tiles");
+        argmax_partial_forced<BM, NT, CPR, XM>(smem, p.forced, m0, n0, p.M, p.N, p.amax, tiles_n, tile_n);
         return;
     }
     if constexpr (EPI == EPI_ARGMAX) {
@@ -1844,6 +1941,9 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
     }
     if constexpr (EPI == EPI_TOPK) {        // the table is optional here; with one, the rest of the mask must be there
         if (!a.alt || (a.tmask.table && (!a.tmask.slot_mask || a.tmask.words != cdiv(a.N, 32)))) return SA_ERR_ARG;
+    }
+    if constexpr (EPI == EPI_FORCED) {
+        if (!a.forced.table || !a.forced.flogit || a.forced.stride <= 0) return SA_ERR_ARG;
     }
     if (a.M <= 256) {
         if constexpr (epi_is_argmax(EPI)) {

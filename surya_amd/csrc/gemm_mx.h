@@ -38,7 +38,8 @@ namespace sa {
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
 enum MxEpi { MX_EPI_F32 = 0, MX_EPI_SWIGLU = 1, MX_EPI_ARGMAX = 2, MX_EPI_ARGMAX_MASK = 3 /* over the columns a TokenMask allows (gemm.h) */,
-             MX_EPI_TOPK = 4 /* MX_EPI_ARGMAX_MASK (an absent table = unconstrained) + the tile's four best allowed columns (gemm.h) */ };
+             MX_EPI_TOPK = 4 /* MX_EPI_ARGMAX_MASK (an absent table = unconstrained) + the tile's four best allowed columns (gemm.h) */,
+             MX_EPI_FORCED = 5 /* MX_EPI_ARGMAX + the logit of each row's forced column (ForcedCols, gemm.h) */ };
 
 struct MxArgs {
     const uint8_t* X; long ldx; const uint8_t* SX;   // e4m3 [M][ldx >= K], e8m0 K-tile-major [K / 128][sx_rows][4]
@@ -55,6 +56,7 @@ struct MxArgs {
     mutable int bn_used = 0;
     TokenMask tmask;                                 // MX_EPI_ARGMAX_MASK, MX_EPI_TOPK
     float2* alt = nullptr;                           // MX_EPI_TOPK: the candidates of GemmArgs::alt
+    ForcedCols forced;                               // MX_EPI_FORCED
 };
 
 template <int BM, int BN, int EPI, bool SPLIT, int STAGES>
@@ -230,6 +232,9 @@ __global__ __launch_bounds__(256) void gemm_mx_kernel(MxArgs p) {
     } else if constexpr (EPI == MX_EPI_TOPK && !SPLIT) {
         topk_partial_masked<BM, NT, CPR, XM>(smem, p.tmask, m0, n0, p.M, p.N, p.amax, p.alt, tiles_n, tile_n);
         return;
+    } else if constexpr (EPI == MX_EPI_FORCED && !SPLIT) {
+        argmax_partial_forced<BM, NT, CPR, XM>(smem, p.forced, m0, n0, p.M, p.N, p.amax, tiles_n, tile_n);
+        return;
     } else if constexpr (EPI == MX_EPI_ARGMAX && !SPLIT) {
         // greedy-head partials from the staged tile (same reduction as gemm.h's EPI_ARGMAX)
         constexpr int TPR = NT / BM, SEG = CPR / TPR;
@@ -325,7 +330,7 @@ static inline int launch_gemm_mx_cfg(const MxArgs& a, hipStream_t s) {
         const double in = ((double)a.M + a.N) * a.K * (1.0 + 1.0 / 32);
         pf.bytes_of[pf.n] = in + (SPLIT ? (double)a.M * a.N * 2.0          // the result once (bf16); the fp32 slabs are counted apart
                                         : EPI == MX_EPI_SWIGLU ? a.M * (a.N / 2) * (1.0 + 1.0 / 32)
-                                        : (EPI == MX_EPI_ARGMAX || EPI == MX_EPI_ARGMAX_MASK || EPI == MX_EPI_TOPK) ? 16.0 * a.M * cdiv(a.N, BN) : 4.0 * a.M * a.N);
+                                        : (EPI == MX_EPI_ARGMAX || EPI == MX_EPI_ARGMAX_MASK || EPI == MX_EPI_TOPK || EPI == MX_EPI_FORCED) ? 16.0 * a.M * cdiv(a.N, BN) : 4.0 * a.M * a.N);
         pf.slab_of[pf.n] = SPLIT ? (double)a.splitk * a.M * a.N * 4.0 : 0.0;
         ++pf.n;
     }
@@ -371,6 +376,9 @@ static inline int launch_gemm_mx(const MxArgs& a, hipStream_t s) {
         }
         if constexpr (EPI == MX_EPI_TOPK) {
             if (!a.alt || (a.tmask.table && (!a.tmask.slot_mask || a.tmask.words != cdiv(a.N, 32)))) return SA_ERR_ARG;
+        }
+        if constexpr (EPI == MX_EPI_FORCED) {
+            if (!a.forced.table || !a.forced.flogit || a.forced.stride <= 0) return SA_ERR_ARG;
         }
         if (a.N >= 64 * 512) return launch_gemm_mx_cfg<128, 128, EPI, false, 2>(a, s);
         if constexpr (EPI == MX_EPI_F32) {

@@ -423,6 +423,45 @@ __global__ __launch_bounds__(64) void embed_slots_norm_kernel(const T* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------
+// Forced decoding in the greedy heads (surya_rec_set_forced). table == nullptr: the feature is off and the head does what it always did.
+// Otherwise f = table[slot][cursor[slot]] (-1, or a cursor at or past `stride`: the slot free-runs). best, bi and tot are computed as ever;
+//   f >= 0: the emitted token is f, done = f in {eos, pad}, score = done ? 0 : expf(flogit - best) / tot, the next input is done ? pad : f
+//           (flogit[r]: the lm_head's *_FORCED epilogue; when f is the row's argmax it has the bits of best, so the score is 1 / tot exactly);
+//   f <  0: today's statements, today's bits.
+// Both: greedy_token = bi, greedy_prob = 1 / tot, logprob = (flogit - best) - logf(tot) (f < 0: -logf(tot), the greedy token's), and the
+// cursor advances by one.
+struct ForcedHead {
+    const int* table = nullptr;        // [slots][stride]
+    int* cursor = nullptr;             // [slots]
+    const float* flogit = nullptr;     // [rows] of this launch
+    int stride = 0;
+    int* greedy_token = nullptr;       // [slots] of this step
+    float* greedy_prob = nullptr;
+    float* logprob = nullptr;
+    // the slot's forced id at its cursor (every thread of the head reads it before thread 0 advances the cursor behind a barrier)
+    __device__ __forceinline__ int id_of(int slot, int& cur) const {
+        if (!table) { cur = 0; return -1; }
+        cur = cursor[slot];
+        const int f = table[(long)slot * stride + min(max(cur, 0), stride - 1)];
+        return (cur >= 0 && cur < stride) ? f : -1;
+    }
+    // thread 0 of the head, with the row's max, first argmax and total; -> the emitted token, `score` and `done` replaced where forced
+    __device__ __forceinline__ void emit(int r, int slot, int f, int cur, float best, int bi, float tot, int eos_id, int pad_id, int& token,
+                                         float& score, bool& done) const {
+        const float dl = f >= 0 ? flogit[r] - best : 0.f;
+        if (f >= 0) {
+            token = f;
+            done = (f == eos_id) || (f == pad_id);
+            score = done ? 0.f : expf(dl) / tot;
+        }
+        greedy_token[slot] = bi;
+        greedy_prob[slot] = 1.0f / tot;
+        logprob[slot] = dl - logf(tot);
+        cursor[slot] = cur + 1;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Greedy head (process_outputs, recognition/__init__.py:294-324) on fp32 logits [rows, V]:
 // pred = argmax (first max), score = max softmax prob = 1 / sum(exp(x - max)), done = pred in {eos, pad};
 // bbox = trunc(sigmoid(W_b h + b) * bbox_size) (common/surya/__init__.py:329); updates the slot state for
@@ -437,7 +476,7 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
                                                           int eos_id, int pad_id, float bbox_size, int* __restrict__ out_token,
                                                           float* __restrict__ out_score, int* __restrict__ out_bbox,
                                                           int* __restrict__ next_token, int* __restrict__ kv_len, int len_inc,
-                                                          float2* __restrict__ best_tot = nullptr) {
+                                                          float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{}) {
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lr = logits + (long)r * ldl * (PART ? 4 : 1);
     __shared__ float smax[4], ssum[4];
@@ -492,12 +531,25 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
     const int slot = row_slot[r];
     if (tid == 0) {
         const float tot = ssum[0] + ssum[1] + ssum[2] + ssum[3];
-        const bool done = (bi == eos_id) || (bi == pad_id);
-        out_token[slot] = bi;
-        out_score[slot] = done ? 0.f : 1.0f / tot;
-        next_token[slot] = done ? pad_id : bi;
-        kv_len[slot] += len_inc;
-        if (best_tot) best_tot[slot] = make_float2(best, tot);      // alternatives on: the row's max and total for topk_combine_kernel
+        if (fh.table) {             // forced decoding (ForcedHead above); one thread reads and advances the cursor
+            int cur;
+            const int f = fh.id_of(slot, cur);
+            int token = bi;
+            bool done = (bi == eos_id) || (bi == pad_id);
+            float score = done ? 0.f : 1.0f / tot;
+            fh.emit(r, slot, f, cur, best, bi, tot, eos_id, pad_id, token, score, done);
+            out_token[slot] = token;
+            out_score[slot] = score;
+            next_token[slot] = done ? pad_id : token;
+            kv_len[slot] += len_inc;
+        } else {
+            const bool done = (bi == eos_id) || (bi == pad_id);
+            out_token[slot] = bi;
+            out_score[slot] = done ? 0.f : 1.0f / tot;
+            next_token[slot] = done ? pad_id : bi;
+            kv_len[slot] += len_inc;
+            if (best_tot) best_tot[slot] = make_float2(best, tot);      // alternatives on: the row's max and total for topk_combine_kernel
+        }
     }
     // bbox head: 6 dot products of length H, one wave each (waves 0..3 take outputs 0..3, then 4..5)
     const T* hr = hidden + (long)r * H;
@@ -597,7 +649,7 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
                                                                        const T* __restrict__ table, const T* __restrict__ wnorm, T* __restrict__ x,
                                                                        T* __restrict__ y, int* __restrict__ row_len, int Tmax, float eps,
                                                                        uint8_t* __restrict__ y8, uint8_t* __restrict__ sy, int srows,
-                                                                       float2* __restrict__ best_tot = nullptr) {
+                                                                       float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{}) {
     constexpr int NT = SA_HEAD_THREADS, NW = NT / 64, NP = 4, V = Ty<T>::V16, NB = 32 / V;   // NB x 64 x V = 2048 >= H
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float smax[NW], ssum[NW], red[NW];
@@ -619,6 +671,8 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
     const int slot = row_slot[r];
     const int klen = kv_len[slot];
     const float bias_o = Ty<T>::ld(bb + wave);
+    int fcur;
+    const int fid = fh.id_of(slot, fcur);          // forced decoding: -1 while off (workgroup-uniform; read before the barriers below)
 
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -659,14 +713,18 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
     }
     d = wave_sum(d);
     __syncthreads();
-    const bool done = (bi == eos_id) || (bi == pad_id);
-    const int tok_next = done ? pad_id : bi;
+    const int tok = fid >= 0 ? fid : bi;            // the emitted token: the forced id where there is one
+    bool done = (tok == eos_id) || (tok == pad_id);
+    const int tok_next = done ? pad_id : tok;
     if (tid == 0) {
         float tot = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) tot += ssum[w];
-        out_token[slot] = bi;
-        out_score[slot] = done ? 0.f : 1.0f / tot;
+        float score = done ? 0.f : 1.0f / tot;
+        int token = tok;
+        if (fh.table) fh.emit(r, slot, fid, fcur, best, bi, tot, eos_id, pad_id, token, score, done);
+        out_token[slot] = token;
+        out_score[slot] = score;
         next_token[slot] = tok_next;
         kv_len[slot] = klen + len_inc;
         if (table) row_len[r] = min(klen + len_inc, Tmax - 1);

@@ -155,7 +155,19 @@ struct RecBase {
     virtual int set_alternatives(int) = 0;
     virtual int read_alternatives(int, int32_t*, float*, hipStream_t) = 0;
     virtual int wait_alternatives(int, int, int32_t*, float*) = 0;
+    virtual int set_forced(int) = 0;
+    virtual int set_forced_tokens(const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int read_forced(int, int32_t*, float*, float*, hipStream_t) = 0;
+    virtual int wait_forced(int, int, int32_t*, float*, float*) = 0;
 };
+
+// surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
+static __global__ __launch_bounds__(256) void set_forced_tokens_kernel(const int* slots, const int* tokens, const int* offsets, int* table,
+                                                                       int* cursor, int stride) {
+    const int i = blockIdx.x, slot = slots[i], a = offsets[i], len = offsets[i + 1] - a;
+    for (int j = threadIdx.x; j < stride; j += 256) table[(long)slot * stride + j] = j < len ? tokens[a + j] : -1;
+    if (threadIdx.x == 0) cursor[slot] = 0;
+}
 
 static __global__ void set_slot_masks_kernel(const int* slots, const int* ids, int* slot_mask, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -243,6 +255,17 @@ struct RecModel : RecBase {
     char* alt_host = nullptr;
     bool alts = false;
     bool ring_alts[2] = {false, false};                  // the last decode_async on this ring half mirrored its alternatives
+    // Forced decoding (surya_rec_set_forced): the id table [max_slots][SA_MAX_FORCED_TOKENS] (-1 = free-running), a cursor per slot, the
+    // forced logit per lm_head row, the [SA_MAX_STEPS][max_slots] outputs and their pinned mirror, allocated on the first switch-on at
+    // addresses that never change afterwards. forcing == false: the lm_head and head launches are the ones of a handle without this entry.
+    char* forced_arena = nullptr;
+    int* forced_table = nullptr; int* forced_cursor = nullptr; float* flogit = nullptr;
+    int* greedy_token = nullptr; float* greedy_prob = nullptr; float* forced_logprob = nullptr;   // [SA_MAX_STEPS][max_slots]
+    char* forced_host = nullptr;
+    Stager st_forced;
+    bool forcing = false;
+    bool ring_forced[2] = {false, false};                // the last decode_async on this ring half mirrored the forced outputs
+    ForcedCols forced_cols(const int* d_row_slot) const { return ForcedCols{forced_table, forced_cursor, d_row_slot, SA_MAX_FORCED_TOKENS, flogit}; }
     const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
     const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
 
@@ -351,6 +374,8 @@ struct RecModel : RecBase {
         if (mask_arena) { (void)hipFree(mask_arena); st_mask.destroy(); }
         if (alt_arena) (void)hipFree(alt_arena);
         if (alt_host) (void)hipHostFree(alt_host);
+        if (forced_arena) { (void)hipFree(forced_arena); st_forced.destroy(); }
+        if (forced_host) (void)hipHostFree(forced_host);
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -620,6 +645,7 @@ struct RecModel : RecBase {
     // ids named rows of the old table). Switching between the masked and the unmasked kernels drops captured steps, as set_kv_fp8 does.
     int set_token_masks(const uint32_t* masks, int n, hipStream_t s) override {
         if (n < 0 || n > SA_MAX_TOKEN_MASKS || (n > 0 && !masks)) return SA_ERR_ARG;
+        if (n > 0 && forcing) return SA_ERR_STATE;          // forced decoding runs the unmasked partial
         const int words = mask_words();
         for (int i = 0; i < n; ++i) {
             bool any = false;
@@ -682,6 +708,7 @@ struct RecModel : RecBase {
     // steps, which hold the other lm_head kernel and the head's null / non-null (max, total) pointer.
     int set_alternatives(int on) override {
         if (on != 0 && on != 1) return SA_ERR_ARG;
+        if (on && forcing) return SA_ERR_STATE;
         if (on && !alt_arena) {
             const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S * SA_MAX_ALTERNATIVES;
             const size_t part_bytes = align_up(S * (size_t)cdiv(c.vocab, 64) * SA_MAX_ALTERNATIVES * sizeof(float2));
@@ -702,6 +729,68 @@ struct RecModel : RecBase {
         if ((on != 0) != alts) drop_graphs();
         alts = on != 0;
         return SA_OK;
+    }
+
+    // Forced decoding on / off. Memory on the first switch-on, or nothing (a failure leaves the handle as it was); switching drops captured
+    // steps, which hold the other lm_head kernel and the head's empty / filled ForcedHead. Switch-off sets the table back to -1.
+    int set_forced(int on) override {
+        if (on != 0 && on != 1) return SA_ERR_ARG;
+        if (on && (n_token_masks > 0 || alts)) return SA_ERR_STATE;
+        const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S;
+        const size_t table_bytes = align_up(S * SA_MAX_FORCED_TOKENS * sizeof(int)), slot_bytes = align_up(S * sizeof(int)), out_b = align_up(outs * 4);
+        if (on && !forced_arena) {
+            char* mem = nullptr;
+            char* host = nullptr;
+            SA_HIP(hipMalloc((void**)&mem, table_bytes + 2 * slot_bytes + 3 * out_b));
+            int rc = (int)hipHostMalloc((void**)&host, outs * 12, hipHostMallocDefault);
+            Stager st;
+            if (!rc) rc = st.init(S * SA_MAX_FORCED_TOKENS * sizeof(int) + (2 * S + 1) * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipMemset(mem, 0, table_bytes + 2 * slot_bytes + 3 * out_b);
+            if (!rc) rc = (int)hipMemset(mem, 0xff, table_bytes);           // every slot free-running
+            if (rc) { st.destroy(); if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
+            st_forced = st;
+            forced_arena = mem;
+            forced_host = host;
+            forced_table = reinterpret_cast<int*>(mem);
+            forced_cursor = reinterpret_cast<int*>(mem + table_bytes);
+            flogit = reinterpret_cast<float*>(mem + table_bytes + slot_bytes);
+            greedy_token = reinterpret_cast<int*>(mem + table_bytes + 2 * slot_bytes);
+            greedy_prob = reinterpret_cast<float*>(mem + table_bytes + 2 * slot_bytes + out_b);
+            forced_logprob = reinterpret_cast<float*>(mem + table_bytes + 2 * slot_bytes + 2 * out_b);
+        }
+        if (!on && forcing) {
+            SA_HIP(hipDeviceSynchronize());                                 // (a switch, not a step: no line is in flight)
+            SA_HIP(hipMemset(forced_table, 0xff, table_bytes));
+            SA_HIP(hipDeviceSynchronize());
+        }
+        if ((on != 0) != forcing) drop_graphs();
+        forcing = on != 0;
+        return SA_OK;
+    }
+    // The forced ids of the slots about to be prefilled: slot slots[i] gets tokens[offsets[i] .. offsets[i + 1]), -1 behind them, cursor 0.
+    int set_forced_tokens(const int32_t* slots, const int32_t* tokens, const int32_t* offsets, int n, hipStream_t s) override {
+        if (n < 0 || n > c.max_slots) return SA_ERR_ARG;
+        if (!forcing) return SA_ERR_STATE;
+        if (n == 0) return SA_OK;
+        if (offsets[0] < 0) return SA_ERR_ARG;
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            const int len = offsets[i + 1] - offsets[i];
+            if (slots[i] < 0 || slots[i] >= c.max_slots || seen[slots[i]] || len < 0 || len > SA_MAX_FORCED_TOKENS) return SA_ERR_ARG;
+            seen[slots[i]] = 1;
+            for (int j = offsets[i]; j < offsets[i + 1]; ++j)
+                if (tokens[j] < 0 || tokens[j] >= c.vocab) return SA_ERR_ARG;
+        }
+        st_forced.begin();
+        const int* ds = st_forced.put(slots, n);
+        const int* dof = st_forced.put(offsets, (size_t)n + 1);
+        const int* dt = st_forced.put(tokens + offsets[0], (size_t)(offsets[n] - offsets[0]));
+        if (!ds || !dof || !dt) return SA_ERR_NOMEM;
+        int rc = st_forced.flush(s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(set_forced_tokens_kernel, dim3(n), dim3(256), 0, s, ds, dt - offsets[0], dof, forced_table, forced_cursor,
+                           SA_MAX_FORCED_TOKENS);
+        return (int)hipGetLastError();
     }
 
     // MXFP8 weight table of the decode steps: per layer SA_MX_COUNT pointers, then SA_MX_LM_W, SA_MX_LM_S. bf16 model only.
@@ -838,7 +927,10 @@ struct RecModel : RecBase {
                 MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
                 a.amax = am;
                 a.bias = W(SA_RW_LM_B);
-                if (alts) {
+                if (forcing) {
+                    a.forced = forced_cols(d_row_slot);
+                    if ((rc = launch_gemm_mx<MX_EPI_FORCED>(a, s))) return rc;
+                } else if (alts) {
                     if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
                     a.alt = alt_part;
                     if ((rc = launch_gemm_mx<MX_EPI_TOPK>(a, s))) return rc;
@@ -851,7 +943,10 @@ struct RecModel : RecBase {
         } else {
             GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
             a.amax = am;
-            if (alts) {
+            if (forcing) {
+                a.forced = forced_cols(d_row_slot);
+                if ((rc = launch_gemm<T, float, EPI_FORCED>(a, s))) return rc;
+            } else if (alts) {
                 if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
                 a.alt = alt_part;
                 if ((rc = launch_gemm<T, float, EPI_TOPK>(a, s))) return rc;
@@ -866,6 +961,8 @@ struct RecModel : RecBase {
         last_rows = rows;
         last_heads_mx = mx() && normed;
         float2* bt = alts ? best_tot : nullptr;
+        ForcedHead fh;                                        // empty while forcing is off: the heads do what they always did
+        if (forcing) fh = ForcedHead{forced_table, forced_cursor, flogit, SA_MAX_FORCED_TOKENS, greedy_token + so, greedy_prob + so, forced_logprob + so};
         // alternatives: the row's four best candidates and their probabilities, behind whichever head ran
         auto combine = [&]() -> int {
             if ((rc = (int)hipGetLastError()) || !alts) return rc;
@@ -879,14 +976,14 @@ struct RecModel : RecBase {
                                last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id, c.pad_token_id, (float)c.bbox_size,
                                out_token + so, out_score + so, out_bbox + so * 6, next_token, kv_len, len_inc,
                                fz ? W(SA_RW_TOK_EMBED) : (const T*)nullptr, WD(0, SA_RD_LN1), dx, dh, row_len, c.max_kv_len, c.dec_eps,
-                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots, bt);
+                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots, bt, fh);
             return combine();
         }
         if (fuse_next) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
         hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(rows), dim3(256), 0, s, reinterpret_cast<const float*>(am),
                            (long)tiles_n, tiles_n, last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id,
                            c.pad_token_id, (float)c.bbox_size, out_token + so, out_score + so, out_bbox + so * 6, next_token,
-                           kv_len, len_inc, bt);
+                           kv_len, len_inc, bt, fh);
         last_rows = rows;
         last_heads_mx = mx() && normed;
         return combine();
@@ -1030,7 +1127,38 @@ struct RecModel : RecBase {
             SA_HIP(hipMemcpyAsync(alt_host + off * A * 4, alt_token + off * A, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
             SA_HIP(hipMemcpyAsync(alt_host + (full + off) * A * 4, alt_prob + off * A, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
         }
+        ring_forced[ring] = forcing;
+        if (nt && forcing) {
+            SA_HIP(hipMemcpyAsync(forced_host + off * 4, greedy_token + off, nt * sizeof(int), hipMemcpyDeviceToHost, s));
+            SA_HIP(hipMemcpyAsync(forced_host + (full + off) * 4, greedy_prob + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+            SA_HIP(hipMemcpyAsync(forced_host + (2 * full + off) * 4, forced_logprob + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
         SA_HIP(hipEventRecord(ev_ring[ring], s));
+        return SA_OK;
+    }
+
+    // Forced-decoding outputs of the steps wait_outputs / read_outputs return: [step][slot], same indexing
+    int wait_forced(int n_steps, int ring, int32_t* gtok, float* gprob, float* logp) override {
+        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
+        if (!forcing || !ring_forced[ring]) return SA_ERR_STATE;  // (a call enqueued while the feature was off mirrored nothing)
+        SA_HIP(hipEventSynchronize(ev_ring[ring]));
+        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S, nt = (size_t)n_steps * S;
+        memcpy(gtok, forced_host + off * 4, nt * sizeof(int));
+        memcpy(gprob, forced_host + (full + off) * 4, nt * sizeof(float));
+        memcpy(logp, forced_host + (2 * full + off) * 4, nt * sizeof(float));
+        return SA_OK;
+    }
+    int read_forced(int n_steps, int32_t* gtok, float* gprob, float* logp, hipStream_t s) override {
+        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
+        if (!forcing) return SA_ERR_STATE;
+        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
+        SA_HIP(hipMemcpyAsync(forced_host, greedy_token, nt * sizeof(int), hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(forced_host + full * 4, greedy_prob, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+        SA_HIP(hipMemcpyAsync(forced_host + 2 * full * 4, forced_logprob, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+        SA_HIP(hipStreamSynchronize(s));
+        memcpy(gtok, forced_host, nt * sizeof(int));
+        memcpy(gprob, forced_host + full * 4, nt * sizeof(float));
+        memcpy(logp, forced_host + 2 * full * 4, nt * sizeof(float));
         return SA_OK;
     }
 

@@ -71,7 +71,7 @@ size_t rec_f16_workspace_bytes(const surya_rec_config& cfg);
 int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int n, std::unique_ptr<RecBase>& out);
 int rec_f16_ring_error(bool reset);
 int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt, int* bn_used,
-                   hipStream_t s);
+                   hipStream_t s, const ForcedCols* fc = nullptr);
 // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
@@ -101,11 +101,14 @@ static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, 
 // surya_op_lm_head_partials: the lm_head launch of RecModel<T>::heads for the 16-bit / fp32 operand types built here
 template <typename T>
 static int op_lm_head_t(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt,
-                        int* bn_used, hipStream_t s) {
+                        int* bn_used, hipStream_t s, const ForcedCols* fc = nullptr) {
     GemmArgs<T, float> a{(const T*)X, (long)K, (const T*)W, (long)K, nullptr, (long)N, (const T*)bias, nullptr, 0, M, N, K};
     a.amax = amax;
     int rc;
-    if (alt) {                      // surya_op_lm_head_topk: one kernel with or without a table
+    if (fc) {                       // surya_op_lm_head_forced
+        a.forced = *fc;
+        rc = launch_gemm<T, float, EPI_FORCED>(a, s);
+    } else if (alt) {                      // surya_op_lm_head_topk: one kernel with or without a table
         if (tm) a.tmask = *tm;
         a.alt = alt;
         rc = launch_gemm<T, float, EPI_TOPK>(a, s);
@@ -249,6 +252,23 @@ int surya_rec_wait_alternatives(surya_rec* h, int n_steps, int ring, int32_t* to
     return h->impl->wait_alternatives(n_steps, ring, tokens, probs);
 }
 
+int surya_rec_set_forced(surya_rec* h, int on) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_forced(on);
+}
+int surya_rec_set_forced_tokens(surya_rec* h, const int32_t* slots, const int32_t* tokens, const int32_t* offsets, int n, void* stream) {
+    if (!h || (n > 0 && (!slots || !offsets)) || (n > 0 && !tokens && offsets[n] != offsets[0])) return SA_ERR_ARG;
+    return h->impl->set_forced_tokens(slots, tokens, offsets, n, (hipStream_t)stream);
+}
+int surya_rec_read_forced(surya_rec* h, int n_steps, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs, void* stream) {
+    if (!h || !greedy_tokens || !greedy_probs || !forced_logprobs) return SA_ERR_ARG;
+    return h->impl->read_forced(n_steps, greedy_tokens, greedy_probs, forced_logprobs, (hipStream_t)stream);
+}
+int surya_rec_wait_forced(surya_rec* h, int n_steps, int ring, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs) {
+    if (!h || !greedy_tokens || !greedy_probs || !forced_logprobs) return SA_ERR_ARG;
+    return h->impl->wait_forced(n_steps, ring, greedy_tokens, greedy_probs, forced_logprobs);
+}
+
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
 static __global__ void iota_kernel(int* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -258,21 +278,24 @@ static __global__ void iota_kernel(int* dst, int n) {
 // surya_op_lm_head_partials (alt == nullptr) and the lm_head launch of surya_op_lm_head_topk
 static int op_lm_head(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
                       const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, float2* alt, int* bn_used,
-                      hipStream_t s) {
+                      hipStream_t s, const ForcedCols* fc = nullptr) {
     if (!X || !W || !amax || !bn_used || M <= 0 || N <= 0 || K <= 0 || (masks && !slot_mask)) return SA_ERR_ARG;
     const TokenMask tm{masks, slot_mask, row_slot, cdiv(N, 32)};
     const TokenMask* tp = masks ? &tm : nullptr;
     float4* am = reinterpret_cast<float4*>(amax);
-    if (dtype == SA_DTYPE_F32) return op_lm_head_t<float>(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
-    if (dtype == SA_DTYPE_BF16) return op_lm_head_t<bf16_t>(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
-    if (dtype == SA_DTYPE_F16) return sa::op_lm_head_f16(X, W, bias, M, N, K, tp, am, alt, bn_used, s);
+    if (dtype == SA_DTYPE_F32) return op_lm_head_t<float>(X, W, bias, M, N, K, tp, am, alt, bn_used, s, fc);
+    if (dtype == SA_DTYPE_BF16) return op_lm_head_t<bf16_t>(X, W, bias, M, N, K, tp, am, alt, bn_used, s, fc);
+    if (dtype == SA_DTYPE_F16) return sa::op_lm_head_f16(X, W, bias, M, N, K, tp, am, alt, bn_used, s, fc);
     if (dtype == SA_OP_MXFP8) {
         if (!SX || !SW) return SA_ERR_ARG;
         MxArgs a{(const uint8_t*)X, (long)K, (const uint8_t*)SX, (const uint8_t*)W, (long)K, (const uint8_t*)SW, M, N, K, (long)M, (long)N};
         a.amax = am;
         a.bias = (const bf16_t*)bias;
         int rc;
-        if (alt) {
+        if (fc) {
+            a.forced = *fc;
+            rc = launch_gemm_mx<MX_EPI_FORCED>(a, s);
+        } else if (alt) {
             if (tp) a.tmask = tm;
             a.alt = alt;
             rc = launch_gemm_mx<MX_EPI_TOPK>(a, s);
@@ -291,6 +314,13 @@ static int op_lm_head(int dtype, const void* X, const void* SX, const void* W, c
 int surya_op_lm_head_partials(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
                               const uint32_t* masks, const int32_t* slot_mask, const int32_t* row_slot, float* amax, int* bn_used, void* stream) {
     return op_lm_head(dtype, X, SX, W, SW, bias, M, N, K, masks, slot_mask, row_slot, amax, nullptr, bn_used, (hipStream_t)stream);
+}
+
+int surya_op_lm_head_forced(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,
+                            const int32_t* forced_col, float* amax, float* flogit, int* bn_used, void* stream) {
+    if (!forced_col || !flogit) return SA_ERR_ARG;
+    const ForcedCols fc{forced_col, nullptr, nullptr, 1, flogit};       // one id per row, read at position 0
+    return op_lm_head(dtype, X, SX, W, SW, bias, M, N, K, nullptr, nullptr, nullptr, amax, nullptr, bn_used, (hipStream_t)stream, &fc);
 }
 
 int surya_op_lm_head_topk(int dtype, const void* X, const void* SX, const void* W, const void* SW, const void* bias, int M, int N, int K,

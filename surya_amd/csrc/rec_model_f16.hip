@@ -37,11 +37,14 @@ int rec_f16_ring_error(bool reset) { return ring_error(reset); }     // this uni
 
 // the fp16 arm of surya_op_lm_head_partials / surya_op_lm_head_topk (rec_model.hip): the lm_head launch of RecModel<fp16_t>::heads, masked (tm) or not
 int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt, int* bn_used,
-                   hipStream_t s) {
+                   hipStream_t s, const ForcedCols* fc) {
     GemmArgs<fp16_t, float> a{(const fp16_t*)X, (long)K, (const fp16_t*)W, (long)K, nullptr, (long)N, (const fp16_t*)bias, nullptr, 0, M, N, K};
     a.amax = amax;
     int rc;
-    if (alt) {                      // surya_op_lm_head_topk
+    if (fc) {                       // surya_op_lm_head_forced
+        a.forced = *fc;
+        rc = launch_gemm<fp16_t, float, EPI_FORCED>(a, s);
+    } else if (alt) {                      // surya_op_lm_head_topk
         if (tm) a.tmask = *tm;
         a.alt = alt;
         rc = launch_gemm<fp16_t, float, EPI_TOPK>(a, s);

@@ -15,7 +15,7 @@ from .schema import CharAlternative, TaskNames, TextChar, TextLine
 
 _SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
 _CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
-assert _CHAR_FIELDS | {"alternatives"} == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
+assert _CHAR_FIELDS | {"alternatives", "greedy"} == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
 _new_char, _set = TextChar.__new__, object.__setattr__
 
 
@@ -23,14 +23,15 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     """TextChar.model_construct(...) with all four fields given, without its per-call field loop (1.9 -> 0.55 us; a page of
     text is ~10^4 of these). Same object state: __dict__, fields_set, no extras, no private attributes."""
     m = _new_char(TextChar)
-    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid, "alternatives": None})
-    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))        # (alternatives: the default, as in TextChar(...) without it)
+    _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid, "alternatives": None,
+                         "greedy": None})
+    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))        # (alternatives, greedy: the defaults, as in TextChar(...) without them)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
     return m
 
 
-_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words")
+_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -41,7 +42,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     list of TextChar): the object state validation would produce, without walking the character list again."""
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
-                         "original_text_good": False, "words": words})
+                         "original_text_good": False, "words": words, "log_prob": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -77,6 +78,22 @@ def attach_alternatives(chars, csrc, alts, top_k, decode) -> None:
         ch.alternatives = [CharAlternative.model_construct(text=decode(t), confidence=p, token_id=t)
                            for t, p in zip(ids[j][:top_k], pr[j][:top_k]) if t >= 0]
         ch.__pydantic_fields_set__.add("alternatives")
+
+
+def attach_greedy(chars, csrc, forced, decode) -> None:
+    """chars[i].greedy = the model's own reading at token csrc[i] -- the token the character takes its confidence from -- of an
+    aligned line. forced = (greedy ids [T], their probabilities [T], log-probabilities of the forced ids [T])."""
+    ids, pr = forced[0].tolist(), forced[1].tolist()
+    for ch, j in zip(chars, csrc):
+        ch.greedy = CharAlternative.model_construct(text=decode(ids[j]), confidence=pr[j], token_id=ids[j])
+        ch.__pydantic_fields_set__.add("greedy")
+
+
+def set_log_prob(line: TextLine, forced) -> TextLine:
+    """line.log_prob = the sum of an aligned line's forced log-probabilities, eos included (float64 sum of the fp32 values)."""
+    line.log_prob = float(np.sum(np.asarray(forced[2], np.float64)))
+    line.__pydantic_fields_set__.add("log_prob")
+    return line
 
 
 def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False, csrc_out=None) -> list:
@@ -184,6 +201,16 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
+    if alts is not None and flat.get("forced"):       # an aligned line: alts = (greedy ids, probabilities, forced log-probabilities)
+        forced, flat = alts, {**flat, "forced": False}
+        line = assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size,
+                             alts=(forced[0][:, None], forced[1][:, None]))
+        for ch in line.chars:                         # the same char -> token map as alternatives: entry 0 of a one-entry list
+            if ch.alternatives is not None:
+                ch.greedy, ch.alternatives = ch.alternatives[0], None
+                ch.__pydantic_fields_set__.discard("alternatives")
+                ch.__pydantic_fields_set__.add("greedy")
+        return set_log_prob(line, forced)
     polygon, res_scale = flat["polygons"][orig], flat["res_scales"][orig]
     polys = prediction_to_polygon_batch(bbox_rows[None], [flat["slices"][sorted_pos].shape], bbox_size, bbox_size // 2)
     csrc = [] if alts is not None else None
@@ -195,7 +222,7 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     box = PolygonBox(polygon=polygon)
     chars = chars_of(chars, res_scale, box.bbox)
     if alts is not None and csrc[0] is not None:
-        attach_alternatives(chars, csrc[0], alts, flat["top_k"], AltDecoder(proc))
+        attach_alternatives(chars, csrc[0], alts, flat.get("top_k") or 1, AltDecoder(proc))
     chars = fix_unbalanced_tags(chars, proc.ocr_tokenizer.special_tokens)
     text = clean_math_tags(unwrap_math("".join(c.text for c in chars)))
     return TextLine(text=text, polygon=polygon, chars=chars, confidence=confidence,
@@ -209,6 +236,16 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    if flat.get("forced"):          # aligned lines: the sixth element is (greedy ids, probabilities, forced log-probabilities) [T] each
+        plain = {**flat, "forced": False}
+        forced_of = [it[5] for it in items]
+        out = _assemble_batch_forced(proc, plain, [tuple(it[:5]) for it in items], forced_of, drop_repeated_text, return_words, bbox_size)
+        return [set_log_prob(line, f) for line, f in zip(out, forced_of)]
+    return _assemble_batch_forced(proc, flat, items, None, drop_repeated_text, return_words, bbox_size)
+
+
+def _assemble_batch_forced(proc, flat, items, forced_of, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
+    """assemble_batch; forced_of (or None): per item the forced-decoding outputs its characters take `greedy` from."""
     eos, pad, nop = proc.eos_token_id, proc.pad_token_id, proc.no_output_token
     out: List[Optional[TextLine]] = [None] * len(items)
     work, t_max = [], 0
@@ -216,6 +253,10 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     for i, it in enumerate(items):
         sp, orig, tokens, sc, rows = it[:5]
         if nop in tokens or (drop_repeated_text and detect_repeat_token(tokens)):
+            if forced_of is not None:
+                out[i] = assemble_line(proc, {**flat, "forced": True}, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size,
+                                       alts=forced_of[i])
+                continue
             out[i] = assemble_line(proc, flat, sp, orig, tokens, sc, rows, drop_repeated_text, return_words, bbox_size,
                                    alts=it[5] if len(it) > 5 else None)
             continue
@@ -275,6 +316,9 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
         if len(items[i]) > 5 and items[i][5] is not None:
             decode = decode or AltDecoder(proc)
             attach_alternatives(chars, csrc, items[i][5], flat["top_k"], decode)
+        if forced_of is not None:
+            decode = decode or AltDecoder(proc)
+            attach_greedy(chars, csrc, forced_of[i], decode)
         if not all(valid):                                   # tags only come from special / math runs (bbox_valid False)
             chars = fix_unbalanced_tags(chars, special)
             text = "".join(ch.text for ch in chars)

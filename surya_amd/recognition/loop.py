@@ -35,10 +35,19 @@ class DeviceLoop:
     them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
     line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
     exception. Not requested: the arrays do not exist, on_done keeps its four arguments and the model's three entry points
-    (set_alternatives / read_alternatives / wait_alternatives) are never called -- a model without them works."""
+    (set_alternatives / read_alternatives / wait_alternatives) are never called -- a model without them works.
+
+    Forced decoding (`forced=True`, not together with alternatives or token masks): every admitted dict carries "forced_ids", one id
+    list per prompt; the loop sets a line's list on whatever slot the line is prefilled into (beside set_slot_masks), the line's token
+    budget is the length of its list (an empty list: the line free-runs on the budget it came with), and the repeat rule is skipped --
+    a ground-truth line of forty dashes must not stop early. The model emits the forced ids and reports beside them its own argmax,
+    that argmax's probability and the emitted token's log-probability; the loop keeps them per line (greedy_tok_mat / greedy_p_mat /
+    logp_mat [lines, cap]) and hands a finished line's rows to `on_done` as three more arguments. The feature is switched on for the
+    run and off on the way out, also after an exception. Not requested: the arrays do not exist and the model's four entry points
+    (set_forced / set_forced_tokens / read_forced / wait_forced) are never called -- a model without them works."""
 
     def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None,
-                 alternatives=False):
+                 alternatives=False, forced=False):
         self.model, self.eos, self.pad, self.nop, self.slots = model, eos, pad, nop, slots
         self.overall_max_tokens, self.min_prefill_ratio = overall_max_tokens, min_prefill_ratio
         self.on_done, self.on_flush, self.feed, self.feed_done = on_done, on_flush, feed, feed is None
@@ -60,6 +69,12 @@ class DeviceLoop:
         self.alternatives = bool(alternatives)
         self.alt_tok_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.int32) if self.alternatives else None
         self.alt_p_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.float32) if self.alternatives else None
+        self.forced = bool(forced)
+        assert not (self.forced and self.alternatives), "forced decoding and alternatives exclude each other"
+        self.forced_ids = []                                   # per line: its forced id list (forced only)
+        self.greedy_tok_mat = np.zeros((0, self.cap), np.int32) if self.forced else None
+        self.greedy_p_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
+        self.logp_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
         self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
         self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
@@ -86,6 +101,10 @@ class DeviceLoop:
             return
         assert [p.id for p in new] == list(range(base, base + m)), "fed prompts must continue the admitted ids"
         mt = np.asarray([d["max_tokens"][p.id] for p in new], np.int64)
+        if self.forced:
+            fi = [[int(t) for t in ids] for ids in d["forced_ids"]]
+            assert len(fi) == m, "forced_ids: one id list per prompt"
+            mt = np.asarray([len(ids) or b for ids, b in zip(fi, mt.tolist())], np.int64)      # the budget is the list's length
         assert int(mt.max()) <= self.overall_max_tokens, "a fed line's token budget exceeds the call's overall_max_tokens"
         self.grids.extend(d["grids"])
         self.prompt_ids.extend(d["prompt_ids"])
@@ -99,6 +118,11 @@ class DeviceLoop:
         if self.alternatives:
             self.alt_tok_mat = np.concatenate([self.alt_tok_mat, np.full((m, self.cap, SA_MAX_ALTERNATIVES), -1, np.int32)])
             self.alt_p_mat = np.concatenate([self.alt_p_mat, np.zeros((m, self.cap, SA_MAX_ALTERNATIVES), np.float32)])
+        if self.forced:
+            self.forced_ids.extend(fi)
+            self.greedy_tok_mat = np.concatenate([self.greedy_tok_mat, np.zeros((m, self.cap), np.int32)])
+            self.greedy_p_mat = np.concatenate([self.greedy_p_mat, np.zeros((m, self.cap), np.float32)])
+            self.logp_mat = np.concatenate([self.logp_mat, np.zeros((m, self.cap), np.float32)])
         self.line_len = np.concatenate([self.line_len, np.zeros(m, np.int64)])
         self.max_tok = np.concatenate([self.max_tok, mt])
         mk = d.get("mask_ids")
@@ -132,16 +156,21 @@ class DeviceLoop:
         self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
         if self.on_done is not None:
             more = (self.alt_tok_mat[p_idx, :L_].copy(), self.alt_p_mat[p_idx, :L_].copy()) if self.alternatives else ()
+            if self.forced:
+                more = (self.greedy_tok_mat[p_idx, :L_].copy(), self.greedy_p_mat[p_idx, :L_].copy(), self.logp_mat[p_idx, :L_].copy())
             self.on_done(p_idx, self.predicted_tokens[p_idx], self.scores[p_idx],
                          self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)], *more)
 
-    def _put(self, p, pos, t, s_, b_, at=None, ap=None):
-        """Token t / score s_ / box b_ (/ alternatives at, ap) of lines p at positions pos (arrays over the lines of one step)."""
+    def _put(self, p, pos, t, s_, b_, at=None, ap=None, fo=None):
+        """Token t / score s_ / box b_ (/ alternatives at, ap / forced outputs fo = (greedy token, its probability, log-probability))
+        of lines p at positions pos (arrays over the lines of one step)."""
         self.tok_mat[p, pos] = t
         self.sc_mat[p, pos] = s_
         if at is not None:
             self.alt_tok_mat[p, pos] = at
             self.alt_p_mat[p, pos] = ap
+        if fo is not None:
+            self.greedy_tok_mat[p, pos], self.greedy_p_mat[p, pos], self.logp_mat[p, pos] = fo
         m = pos < self.overall_max_tokens
         if m.all():
             self.batch_bboxes[p, pos] = b_
@@ -160,6 +189,7 @@ class DeviceLoop:
         k, ring = call
         tok, sc, bb = self.model.wait_outputs(k, ring)
         at, ap = self.model.wait_alternatives(k, ring) if self.alternatives else (None, None)
+        fo = self.model.wait_forced(k, ring) if self.forced else None
         slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
         changed = False
         for step in range(k):
@@ -169,7 +199,9 @@ class DeviceLoop:
             p = slot_line[s_idx]
             pos = line_len[p]
             t = tok[step, s_idx]
-            if at is None:
+            if fo is not None:
+                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], fo=tuple(a[step, s_idx] for a in fo))
+            elif at is None:
                 self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
             else:
                 self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], at[step, s_idx], ap[step, s_idx])
@@ -178,7 +210,7 @@ class DeviceLoop:
             # repeat rule: <= 5 distinct ids in the last 40 and the last u ids equal to the u before; the distinct count is
             # screened in array form, only the few candidate lines run the exact rule
             c = np.flatnonzero(~stop & (new_len >= _REP))
-            if c.size:
+            if c.size and not self.forced:                          # (a forced text may repeat as it likes)
                 win = np.sort(tok_mat[p[c, None], new_len[c, None] + _REP_COLS], axis=1)
                 few = c[(np.diff(win, axis=1) != 0).sum(axis=1) + 1 <= 5]
                 for ci in few.tolist():
@@ -224,6 +256,8 @@ class DeviceLoop:
         grids, prompt_ids = [self.grids[i] for i in take], [self.prompt_ids[i] for i in take]
         if self.n_masks:
             self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
+        if self.forced:
+            self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
         if look_ahead:
             for i in take:
                 assert ahead.popleft() == i
@@ -239,8 +273,12 @@ class DeviceLoop:
         if self.alternatives:                                       # the first token has alternatives too
             at, ap = self.model.read_alternatives(1)
             more = (at[0, sl_], ap[0, sl_])
-        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more)
-        for p_id, s, go in zip(take, slots, ((first != self.eos) & (first != self.nop)).tolist()):
+        fo = tuple(a[0, sl_] for a in self.model.read_forced(1)) if self.forced else None
+        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more, fo=fo)
+        go_on = (first != self.eos) & (first != self.nop)
+        if self.forced:
+            go_on &= self.max_tok[ids_] > 1                         # a one-id list is complete with the prefill's token
+        for p_id, s, go in zip(take, slots, go_on.tolist()):
             if go:                                                  # prefill stop rule (reference :559-563)
                 self.slot_line[s] = p_id
             else:
@@ -249,6 +287,12 @@ class DeviceLoop:
 
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
+        if self.forced:
+            self.model.set_forced(True)
+            try:
+                return self._run_masked(prep)
+            finally:
+                self.model.set_forced(False)           # the next call starts on the greedy kernels
         if not self.alternatives:
             return self._run_masked(prep)
         self.model.set_alternatives(True)

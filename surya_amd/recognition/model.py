@@ -69,6 +69,8 @@ class HipRecModel:
         self.n_token_masks = 0
         self.alternatives = False
         self._alt_tok = self._alt_p = None              # host arrays of read_alternatives / wait_alternatives, made on first use
+        self.forced = False
+        self._forced_bufs = None                        # host arrays of read_forced / wait_forced, made on first use
         self.decode_fp8 = False
         if decode_fp8 is None:
             from ..settings import settings
@@ -160,6 +162,48 @@ class HipRecModel:
         L.check(self.lib.surya_rec_wait_alternatives(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(tok), L.np_ptr(pr, C.c_float)),
                 "surya_rec_wait_alternatives")
         return tok[:n_steps], pr[:n_steps]
+
+    def set_forced(self, on: bool):
+        """Forced decoding (surya_rec_set_forced): slots with forced ids (set_forced_tokens) emit them instead of the greedy token and
+        report the ids' probabilities. Off (the default) the handle launches the kernels it always launched. Not together with token
+        masks or alternatives."""
+        L.check(self.lib.surya_rec_set_forced(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_forced")
+        self.forced = bool(on)
+        if on and self._forced_bufs is None:
+            shape = (L.SA_MAX_STEPS, self.max_slots)
+            self._forced_bufs = (np.zeros(shape, np.int32), np.zeros(shape, np.float32), np.zeros(shape, np.float32))
+
+    def set_forced_tokens(self, slots, ids):
+        """ids[i]: the token ids slot slots[i] is forced to from its next prefill on, one per head pass, the prefill's included (an
+        empty list: the slot free-runs). Call for the slots about to be prefilled."""
+        s = np.ascontiguousarray(slots, np.int32)
+        offs = np.zeros(len(ids) + 1, np.int32)
+        np.cumsum([len(x) for x in ids], out=offs[1:])
+        flat = np.ascontiguousarray([t for x in ids for t in x], np.int32) if offs[-1] else np.zeros(1, np.int32)
+        if len(s) != len(ids):
+            raise ValueError("set_forced_tokens: one id list per slot")
+        L.check(self.lib.surya_rec_set_forced_tokens(self.handle, L.np_ptr(s), L.np_ptr(flat), L.np_ptr(offs), C.c_int(len(s)), self._stream),
+                "surya_rec_set_forced_tokens")
+
+    def _forced_views(self, first):
+        if self._forced_bufs is None:   # never switched on: the library refuses below, with buffers it may not write to anyway
+            return np.zeros((1, 1), np.int32), np.zeros((1, 1), np.float32), np.zeros((1, 1), np.float32)
+        return tuple(b[first:] for b in self._forced_bufs)
+
+    def read_forced(self, n_steps: int = 1):
+        """Sync; (greedy_tokens [n_steps, slots] int32, greedy_probs, forced_logprobs [n_steps, slots] float32) of the steps read_outputs
+        returns: the model's own argmax and its probability, and the log-probability of the token that was emitted."""
+        gt, gp, lp = self._forced_views(0)
+        L.check(self.lib.surya_rec_read_forced(self.handle, C.c_int(n_steps), L.np_ptr(gt), L.np_ptr(gp, C.c_float), L.np_ptr(lp, C.c_float),
+                                               self._stream), "surya_rec_read_forced")
+        return gt[:n_steps], gp[:n_steps], lp[:n_steps]
+
+    def wait_forced(self, n_steps: int, ring: int):
+        """The forced-decoding outputs of the decode_async call on `ring`, parallel to wait_outputs."""
+        gt, gp, lp = self._forced_views(ring * (L.SA_MAX_STEPS // 2))
+        L.check(self.lib.surya_rec_wait_forced(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(gt), L.np_ptr(gp, C.c_float),
+                                               L.np_ptr(lp, C.c_float)), "surya_rec_wait_forced")
+        return gt[:n_steps], gp[:n_steps], lp[:n_steps]
 
     def __del__(self):
         h = getattr(self, "handle", None)

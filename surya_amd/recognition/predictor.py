@@ -357,6 +357,8 @@ class RecognitionPredictor(BasePredictor):
                 "prompt_ids": prompt_ids}
         if flat.get("token_masks") is not None:               # constrained output: the call's mask table and one row id per line
             prep.update(token_masks=flat["token_masks"], mask_ids=flat["mask_ids"])
+        if flat.get("forced_ids") is not None:                # align(): one forced id list per line
+            prep["forced_ids"] = flat["forced_ids"]
         return prep
 
     def generate(self, prep: dict | None, recognition_batch_size: int | None = None, on_done=None, on_flush=None, feed=None) -> tuple:
@@ -368,6 +370,8 @@ class RecognitionPredictor(BasePredictor):
         overall_max_tokens = int(first.get("overall_max_tokens") or max(first["max_tokens"].values()))
         proc = self.processor
         more = {"alternatives": True} if self._top_k is not None else {}      # (only then: a stand-in loop keeps its signature)
+        if first.get("forced_ids") is not None:
+            more = {"forced": True}
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
                           min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
                           on_done=on_done, on_flush=on_flush, feed=feed, **more)
@@ -376,7 +380,9 @@ class RecognitionPredictor(BasePredictor):
         # without walking the per-line lists again
         from ..dist import PackedLines
         self.last_packed = (PackedLines(loop.tok_mat, loop.line_len), PackedLines(loop.sc_mat, loop.line_len))
-        if more:                                              # ... and the alternatives [n, cap, 4] likewise
+        if "forced" in more:                                  # ... an aligned call's greedy ids, their probabilities, the log-probabilities
+            self.last_forced = tuple(PackedLines(a, loop.line_len) for a in (loop.greedy_tok_mat, loop.greedy_p_mat, loop.logp_mat))
+        if "alternatives" in more:                            # ... and the alternatives [n, cap, 4] likewise
             self.last_alternatives = (PackedLines(loop.alt_tok_mat, loop.line_len), PackedLines(loop.alt_p_mat, loop.line_len))
         return loop.predicted_tokens, torch.from_numpy(loop.batch_bboxes), loop.scores
 
@@ -492,9 +498,87 @@ class RecognitionPredictor(BasePredictor):
             if top_k is not None:
                 self.last_alternatives = None
 
+    def forced_ids(self, text: str, task: str) -> List[int]:
+        """The ids `align` forces for one line: the tokenizer's ids of the text for the line's task, then eos."""
+        return [int(t) for t in self.processor.ocr_tokenizer(text, task)["input_ids"][0]] + [int(self.processor.eos_token_id)]
+
+    def align(self, images: List[Image.Image], texts: List[List[str]], task_names: List[str] | None = None,
+              bboxes: List[List[List[int]]] | None = None, polygons: List[List[List[List[int]]]] | None = None,
+              recognition_batch_size: int | None = None, math_mode: bool = True, return_words: bool = False) -> List[OCRResult]:
+        """Align known transcriptions: texts[i][j] is the text of image i's j-th bbox / polygon (one of the two is required). Every
+        line is decoded with its own tokens forced (`forced_ids`) instead of the model's choices, so the result holds the GIVEN text,
+        read back through the tokenizer, with per-character polygons predicted from the forced prefix and per-character `confidence`
+        = p(character | image, preceding text); a line's `confidence` is computed as in `__call__`. Two more fields:
+        `TextLine.log_prob`, the sum of the log-probabilities of the line's tokens, eos included (p(eos | text) says whether the model
+        thinks the line is complete), and `TextChar.greedy`, the model's own reading (text, probability, token id) at the token the
+        character takes its confidence from -- the character itself where the model agrees. ValueError, naming image and line, for
+        a count mismatch, a line longer than its task's token budget or than SA_MAX_FORCED_TOKENS, or an id outside the model's
+        vocabulary. Not with `shard_lines` or a process group: multi-rank alignment is not supported. Allow-lists and `top_k`
+        do not apply to an aligned call."""
+        if getattr(self, "_poisoned", None):
+            raise RuntimeError(self._poisoned)
+        if self.shard_lines or self.shard_pages or self.process_group is not None:
+            raise NotImplementedError("align() runs on one rank: unset shard_lines / shard_pages / process_group")
+        from .. import _lib as L
+        given = polygons if polygons is not None else bboxes
+        if given is None:
+            raise ValueError("align() needs bboxes or polygons: the lines the texts belong to")
+        if task_names is None:
+            task_names = [TaskNames.ocr_with_boxes] * len(images)
+        if not (len(images) == len(texts) == len(given) == len(task_names)):
+            raise ValueError(f"align(): {len(images)} images, {len(texts)} text lists, {len(given)} bbox / polygon lists, {len(task_names)} task names")
+        for t in task_names:
+            if t not in self.tasks:
+                raise ValueError(f"task {t!r} is not supported. Supported tasks are {list(self.tasks)}")
+        vocab = getattr(self.model, "vocab", None)
+        forced = []
+        for i, (tx, gv, task) in enumerate(zip(texts, given, task_names)):
+            if len(tx) != len(gv):
+                raise ValueError(f"image {i} has {len(gv)} lines but {len(tx)} texts")
+            budget = self.line_budget(task)
+            for j, text in enumerate(tx):
+                if not isinstance(text, str):
+                    raise ValueError(f"image {i}, line {j}: the text must be a str, got {type(text).__name__}")
+                ids = self.forced_ids(text, task)
+                if len(ids) > budget:
+                    raise ValueError(f"image {i}, line {j}: {len(ids)} tokens (eos included) exceed the token budget {budget} of task {task}")
+                if len(ids) > L.SA_MAX_FORCED_TOKENS:
+                    raise ValueError(f"image {i}, line {j}: {len(ids)} tokens exceed SA_MAX_FORCED_TOKENS = {L.SA_MAX_FORCED_TOKENS}")
+                if vocab is not None and max(ids) >= vocab:
+                    raise ValueError(f"image {i}, line {j}: token id {max(ids)} is outside the model's vocabulary of {vocab}")
+                forced.append(ids)
+        saved_k, self._top_k = self._top_k, None              # (an aligned call reports `greedy`, not alternatives)
+        try:
+            with gc_paused():
+                return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
+        finally:
+            self._top_k = saved_k
+
+    def _align(self, images, forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words) -> List[OCRResult]:
+        t_call = time.perf_counter()
+        stamps = self.last_timing = {}
+        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
+        if len(flat["slices"]) == 0:
+            return []
+        flat["forced"], flat["forced_ids"] = True, forced     # by line id like the slices: sorted with them below
+        order = sorted(range(len(flat["slices"])), key=lambda i: -flat["slices"][i].shape[1])
+        for key in ("slices", "input_text", "task_names", "forced_ids"):
+            flat[key] = [flat[key][i] for i in order]
+        with AssemblyHandover(self, flat, order, False, return_words) as hand:
+            t0 = time.perf_counter()
+            prep = self.prepare_lines(flat, math_mode)
+            t1 = time.perf_counter()
+            self.generate(prep, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush)
+            stamps["prepare_ms"] = (t1 - t0) * 1e3
+            text_lines = hand.finish(stamps, t1)
+        results = self._page_results(images, flat["slice_map"], text_lines, False)
+        stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
+        return results
+
     top_k: int | None = None          # alternatives per character (2..4), None = off: RecognitionPredictor.top_k = 3, or on an instance
     _top_k = None                     # the running call's validated top_k (see __call__)
     last_alternatives = None
+    last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
 
     def _call_gc_paused(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist):

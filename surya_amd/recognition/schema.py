@@ -52,16 +52,23 @@ class TextChar(BaseChar):
     # then left out of the serialised form, which stays the reference's (model_json_schema lists the field all the same). The
     # exclusion costs model_dump one predicate call per character (tools/hostbench/dump_cost.py: no difference to a TextChar
     # without the field at 3.6-5 us per character; the wrap serialiser that older pydantic needs takes 3.6 to 9.7 us).
+    # `greedy` (RecognitionPredictor.align): the model's own reading at the token the character takes its confidence from -- text,
+    # probability, token id; it equals the character where the model agrees with the aligned text. None, and left out like
+    # `alternatives`, everywhere else.
     if _EXCLUDE_IF:
         alternatives: Optional[List[CharAlternative]] = Field(default=None, exclude_if=lambda v: v is None)
+        greedy: Optional[CharAlternative] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         alternatives: Optional[List[CharAlternative]] = None
+        greedy: Optional[CharAlternative] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_alternatives(self, handler):
             d = handler(self)
             if self.alternatives is None:
                 d.pop("alternatives", None)
+            if self.greedy is None:
+                d.pop("greedy", None)
             return d
 
 
@@ -73,6 +80,19 @@ class TextLine(BaseChar):
     chars: List[TextChar]
     original_text_good: bool = False
     words: List[TextWord] | None = None
+    # RecognitionPredictor.align: log p(text, eos | image), the sum of the forced tokens' log-probabilities; None, and left out of the
+    # serialised form, in every other result
+    if _EXCLUDE_IF:
+        log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
+    else:
+        log_prob: Optional[float] = None
+
+        @model_serializer(mode="wrap")
+        def _without_absent_log_prob(self, handler):
+            d = handler(self)
+            if self.log_prob is None:
+                d.pop("log_prob", None)
+            return d
 
 
 class OCRResult(BaseModel):

@@ -5,7 +5,7 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
@@ -19,6 +19,10 @@ same mask. `maskonly`: the digits arm alone.
 
 `alts`: alternatives (HipRecModel.set_alternatives: the *_TOPK lm_head epilogue and the combine kernel behind the head) off / on / off /
 on / off, alternating; tokens must be identical to the first arm. `altsonly`: the "on" arm alone (for a kernel trace beside `base`).
+
+`forced`: forced decoding (HipRecModel.set_forced: the *_FORCED lm_head epilogue and the forced greedy head) off / on / off / on / off,
+alternating, every slot forced to random ids for the whole run; the off arms' tokens must be identical to the first arm, the on arms emit
+their ids. `forcedonly`: the "on" arm alone (for a kernel trace beside `base`).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -97,6 +101,10 @@ def main():
         variants = [dict(), dict(alts=1), dict(), dict(alts=1), dict()]
     elif args.configs == "altsonly":
         variants = [dict(alts=1)]
+    elif args.configs == "forced":       # forced decoding: off against on, alternating
+        variants = [dict(), dict(forced=1), dict(), dict(forced=1), dict()]
+    elif args.configs == "forcedonly":
+        variants = [dict(forced=1)]
     elif args.configs == "pf":           # K/V prefetch workgroups in the reduce kernels, on / off, interleaved
         variants = [dict(kvprefetch=1), dict(), dict(kvprefetch=1), dict(), dict(lmhead=2, kvprefetch=1), dict(lmhead=2)]
     elif args.configs == "fp8only":
@@ -107,7 +115,13 @@ def main():
         variants = [dict(), dict(graph=1), dict(split_target=512), dict(split_target=384), dict(split_target=192), dict(split_min_kt=2),
                     dict(split_max=4)]
 
+    stop_ids = (cfg.eos_token_id, cfg.pad_token_id)
+    forced_ids = [[int(t) if t not in stop_ids else 17 for t in row]
+                  for row in np.random.default_rng(99).integers(0, cfg.decoder.vocab_size, size=(n, args.steps + 1))]
+
     def run(n_steps):
+        if m.forced:
+            m.set_forced_tokens(slots, [row[: n_steps + 1] for row in forced_ids])
         m.prefill(tiles, grids, seqs, slots)
         m.read_outputs(1)
         m.set_active(slots)
@@ -124,6 +138,8 @@ def main():
             t, _, _ = m.wait_outputs(*call)
             if m.alternatives:
                 m.wait_alternatives(*call)               # what the device loop reads beside the tokens
+            if m.forced:
+                m.wait_forced(*call)
             toks.append(t[: call[0], :n].copy())
         e1.record()
         torch.cuda.synchronize()
@@ -151,6 +167,9 @@ def main():
         alts = v.pop("alts", 0)
         if alts or args.configs in ("alts", "altsonly"):
             m.set_alternatives(bool(alts))
+        forced = v.pop("forced", 0)
+        if forced or args.configs in ("forced", "forcedonly"):
+            m.set_forced(bool(forced))
         if masks or args.configs in ("masks", "maskonly"):
             set_masks(masks)
         setk(**{**base, **v})
@@ -159,10 +178,12 @@ def main():
             v["masks"] = masks
         if args.configs in ("alts", "altsonly"):
             v["alts"] = alts
+        if args.configs in ("forced", "forcedonly"):
+            v["forced"] = forced
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0)), best[2])).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0)), best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
@@ -170,6 +191,8 @@ def main():
         m.set_token_masks(None)
     if args.configs in ("alts", "altsonly"):
         m.set_alternatives(False)
+    if args.configs in ("forced", "forcedonly"):
+        m.set_forced(False)
 
 
 if __name__ == "__main__":
