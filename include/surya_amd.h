@@ -372,6 +372,61 @@ int surya_op_lm_head_forced(int dtype, const void* X, const void* SX, const void
 int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_t* W, const uint8_t* SW, int M, int N, int K,
                      float* C, int* splitk, uint8_t* q_out, uint8_t* sq_out, void* stream);
 
+/* The recogniser's non-GEMM kernels by themselves (csrc/kernels.h), each through the launch code RecModel<T> uses (sa::launch_* of
+ * csrc/kernels.h: the same grid and block arithmetic, the same choice of kernel instance, the same refusals). dtype SA_DTYPE_F32, SA_DTYPE_BF16
+ * or SA_DTYPE_F16 (one entry per op; anything else SA_ERR_UNSUPPORTED): every `void*` operand is of that dtype. All pointers are caller-owned
+ * device memory unless marked host; enqueue only; nothing is allocated. The MXFP8 copies (y8, sy) exist beside bf16 only, as in the engine
+ * (SA_ERR_UNSUPPORTED otherwise); they want H % 128 == 0 and the scales K-tile-major, sy[(c / 128) * srows * 4 + row * 4 + (c / 32) % 4].
+ * surya_op_rec_rmsnorm_rows: surya_op_rmsnorm with the engine's row gather: y[r] = Qwen2RMSNorm(x[src_row ? src_row[r] : r]), rows ldx / ldy
+ *   elements apart. C and ldx multiples of 16 bytes, ldy of 4 elements.
+ * surya_op_rec_rows: the prefill's row movers; dims is a HOST array:
+ *   SA_REC_CONVERT_TILES dims {P, kin, kout}: src fp32 [.][kin] -> dst[r][0 .. kout) = T(src[index[r]]), zero from column kin on
+ *   SA_REC_SCATTER_IMAGE dims {rows, H}: dst[index[r]] = T(src[r] + T(src2[index2[r]] + src3[index3[r]])) (merged tokens, row and column
+ *                        position embeddings)
+ *   SA_REC_SCATTER_ROWS  dims {rows, H}: dst[index[r]] = src[r]
+ *   SA_REC_EMBED_TOKENS  dims {rows, H}: dst[r] = src[index[r]]; rows with index[r] < 0 are left as they are
+ *   (operands a kind does not name: NULL)
+ * surya_op_rec_rope_table: (cos, sin) pairs in fp32. SA_REC_ROPE_VISION: n = patches, d = head_dim; table[p][i] for i < d / 2 is the pair of
+ *   pos_hw[2 p] * inv_freq[i] (i < d / 4) or pos_hw[2 p + 1] * inv_freq[i - d / 4]; dtype is not used. SA_REC_ROPE_DECODER: n = max_kv_len, d =
+ *   head_dim / 2; table[t][i] = the pair of t * inv_freq[i], rounded to dtype; pos_hw = NULL.
+ * surya_op_rec_rope_kv_append: the prefill's RoPE + cache append. qkv [n_tokens][(heads + 2 kv_heads) * head_dim]: q rotated in place; k
+ *   rotated and v copied to row tok_pos[t] of slot tok_slot[t] in the caches [slot][kv_head][max_kv_len][head_dim]; rope_cs as above.
+ * surya_op_rec_reduce_norm: x[M][H] = T(x + sum of S slabs part[S][M][H]) in place, then y = Qwen2RMSNorm(x) * w; w == NULL skips y. S in
+ *   1..8, H % 4 == 0, H <= 4096. Tuning rnorm picks the kernel instance as in the engine.
+ * surya_op_rec_decode_embed: row r is slot active_slots[r]: row_len[r] = min(kv_len[slot], max_kv_len - 1), x[r] = table[next_token[slot]],
+ *   y[r] = Qwen2RMSNorm(x[r]) * w. Tuning ghead = 2 and H <= 2048, H % 8 == 0: embed_slots_norm2_kernel, else embed_slots_norm_kernel.
+ * surya_op_rec_head: the greedy head over the lm_head's partials (surya_op_lm_head_partials) of `rows` rows, row r of slot row_slot[r]:
+ *   out_token, out_score, out_bbox [.][6], next_token and kv_len are indexed by slot. table != NULL: the fused next-step embedding (x, y,
+ *   row_len and the MXFP8 copy of row r, as surya_op_rec_decode_embed writes them). best_tot [slots][2] or NULL. forced_table != NULL: forced
+ *   decoding ([slots][forced_stride] ids, forced_cursor [slots], flogit [rows]; greedy_token, greedy_prob, logprob by slot). Tuning ghead = 2,
+ *   H <= 2048 and tiles_n <= 1536: greedy_head2_kernel, else greedy_head_kernel<T, true>, which has no fused embedding (SA_ERR_STATE). */
+enum { SA_REC_CONVERT_TILES = 0, SA_REC_SCATTER_IMAGE, SA_REC_SCATTER_ROWS, SA_REC_EMBED_TOKENS };
+enum { SA_REC_ROPE_VISION = 0, SA_REC_ROPE_DECODER };
+typedef struct surya_rec_head_args {
+    const float* part;                   /* [rows][tiles_n][4] */
+    const void *hidden, *wb, *bb;        /* [rows][H], [6][H], [6] */
+    const int32_t* row_slot;
+    int32_t *out_token; float* out_score; int32_t *out_bbox, *next_token, *kv_len;
+    const void *table, *wnorm; void *x, *y; int32_t* row_len; uint8_t *y8, *sy;
+    float* best_tot;
+    const int32_t* forced_table; int32_t* forced_cursor; const float* flogit; int32_t* greedy_token; float *greedy_prob, *logprob;
+    int32_t tiles_n, rows, H, eos_id, pad_id, len_inc, max_kv_len, srows, forced_stride;
+    float bbox_size, eps;
+} surya_rec_head_args;
+int surya_op_rec_rmsnorm_rows(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, const int32_t* src_row, int rows, int C,
+                              float eps, void* stream);
+int surya_op_rec_rows(int dtype, int kind, void* dst, const void* src, const void* src2, const void* src3, const int32_t* index,
+                      const int32_t* index2, const int32_t* index3, const int32_t* dims, void* stream);
+int surya_op_rec_rope_table(int dtype, int kind, const int32_t* pos_hw, const float* inv_freq, float* table, int n, int d, void* stream);
+int surya_op_rec_rope_kv_append(int dtype, void* qkv, const int32_t* tok_slot, const int32_t* tok_pos, const float* rope_cs, void* kcache,
+                                void* vcache, int n_tokens, int heads, int kv_heads, int head_dim, int max_kv_len, void* stream);
+int surya_op_rec_reduce_norm(int dtype, const float* part, int S, int M, void* x, const void* w, void* y, int H, float eps, uint8_t* y8,
+                             uint8_t* sy, int srows, void* stream);
+int surya_op_rec_decode_embed(int dtype, const void* table, const int32_t* next_token, const int32_t* active_slots, const int32_t* kv_len,
+                              int max_kv_len, int32_t* row_len, void* x, const void* w, void* y, int rows, int H, float eps, uint8_t* y8,
+                              uint8_t* sy, int srows, void* stream);
+int surya_op_rec_head(int dtype, const surya_rec_head_args* args, void* stream);
+
 /* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
  * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).
  * dtype SA_DTYPE_F32 or SA_DTYPE_BF16, anything else SA_ERR_UNSUPPORTED: these entries keep their two dtypes. The engine's third dtype has

@@ -25,6 +25,8 @@ DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes
 EPI_BIAS, EPI_RESIDUAL, EPI_GELU, EPI_SWIGLU, EPI_HARDSWISH, EPI_RELU = range(6)
 EPI_GEGLU = 8                                   # gelu_tanh(gate) * up (ADETR decoder MLP); surya_op_gemm, fp32 / bf16 (fp16: surya_op_gemm_geglu_f16)
 FAMILY_LAYOUT, FAMILY_TABLE = 0, 1              # SA_FAMILY_*
+REC_CONVERT_TILES, REC_SCATTER_IMAGE, REC_SCATTER_ROWS, REC_EMBED_TOKENS = range(4)    # SA_REC_*: `kind` of surya_op_rec_rows
+REC_ROPE_VISION, REC_ROPE_DECODER = 0, 1        # SA_REC_ROPE_*: `kind` of surya_op_rec_rope_table
 LAY_PATCHIFY, LAY_ADD_ROWS, LAY_ZERO_ROWS, LAY_GATHER_ADD = range(4)      # SA_LAY_*: `kind` of surya_op_lay_rows
 
 
@@ -44,6 +46,15 @@ class RecConfigC(C.Structure):
 class DetConfigC(C.Structure):
     _fields_ = [("n_ops", C.c_int32), ("max_batch", C.c_int32), ("height", C.c_int32), ("width", C.c_int32),
                 ("num_labels", C.c_int32), ("dtype", C.c_int32)]
+
+
+class RecHeadArgsC(C.Structure):
+    """surya_rec_head_args (include/surya_amd.h): the operands of surya_op_rec_head."""
+    _fields_ = ([(n, C.c_void_p) for n in (
+        "part", "hidden", "wb", "bb", "row_slot", "out_token", "out_score", "out_bbox", "next_token", "kv_len", "table", "wnorm", "x", "y",
+        "row_len", "y8", "sy", "best_tot", "forced_table", "forced_cursor", "flogit", "greedy_token", "greedy_prob", "logprob")] +
+                [(n, C.c_int32) for n in ("tiles_n", "rows", "H", "eos_id", "pad_id", "len_inc", "max_kv_len", "srows", "forced_stride")] +
+                [("bbox_size", C.c_float), ("eps", C.c_float)])
 
 
 class SuryaAmdError(RuntimeError):
@@ -119,6 +130,19 @@ def _bind_lay_ops(lib):
     lib.surya_rec_read_forced.argtypes, lib.surya_rec_read_forced.restype = [p, i, ip, fp, fp, p], C.c_int
     lib.surya_rec_wait_forced.argtypes, lib.surya_rec_wait_forced.restype = [p, i, i, ip, fp, fp], C.c_int
     lib.surya_op_lm_head_forced.argtypes, lib.surya_op_lm_head_forced.restype = [i, p, p, p, p, p, i, i, i, p, p, p, ip, p], C.c_int
+    # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
+    rec = {
+        "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],
+        "surya_op_rec_rows": [i, i, p, p, p, p, p, p, p, ip, p],
+        "surya_op_rec_rope_table": [i, i, p, p, p, i, i, p],
+        "surya_op_rec_rope_kv_append": [i, p, p, p, p, p, p, i, i, i, i, i, p],
+        "surya_op_rec_reduce_norm": [i, p, i, i, p, p, p, i, f, p, p, i, p],
+        "surya_op_rec_decode_embed": [i, p, p, p, p, i, p, p, p, p, i, i, f, p, p, i, p],
+        "surya_op_rec_head": [i, C.POINTER(RecHeadArgsC), p],
+    }
+    for name, args in rec.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, C.c_int
 
 
 def check(rc: int, what: str):

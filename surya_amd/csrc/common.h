@@ -329,7 +329,7 @@ struct Tuning {
     int glds = 2;            // LDS stages of the 128x128 direct-to-LDS GEMM (2 or 3)
     // round 4 (A/B knobs of the decode step's non-GEMM kernels and of the persistent big-tile GEMM; defaults = measured best)
     int dattn = 4;           // bf16 decode attention (fp16: always the fourth version): 4 = thread-local prologue (decode_attn_flash2_kernel), 3 = third version
-    int rnorm = 2;           // split-K reduce + residual + RMSNorm: 2 = slab loads sized by the slice count, 1 = round-3 kernel, 3 = one wave per row
+    int rnorm = 2;           // split-K reduce + residual + RMSNorm: 2 = slab loads sized by the slice count (2, 4 or 8 per thread), anything else as 2; 1 = round-3 kernel (8 loads whatever the count)
     int ghead = 2;           // greedy head: 2 = registers-only partial reduce + vector bbox head (+ next step's embedding when fused), 1 = round-3 kernel
     int fuse_embed = 1;      // inner decode steps: the greedy head also writes the next step's embedding + first RMSNorm (no embed launch)
     int kvprefetch = 0;      // 1: the two reduce kernels of a decode layer request the next layer's V / K cache rows (extra workgroups, kernels.h KvPrefetch).

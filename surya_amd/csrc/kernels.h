@@ -412,7 +412,7 @@ __global__ __launch_bounds__(64) void embed_slots_norm_kernel(const T* __restric
         const float o[4] = {g[0] * Ty<T>::rnd(v[0] * rstd), g[1] * Ty<T>::rnd(v[1] * rstd), g[2] * Ty<T>::rnd(v[2] * rstd),
                             g[3] * Ty<T>::rnd(v[3] * rstd)};
         store4(yr + c, o[0], o[1], o[2], o[3]);
-        if (y8) {   // MXFP8 copy (H % 256 == 0 on this path: whole 8-lane groups stay inside the row)
+        if (y8) {   // MXFP8 copy (H % 128 == 0 on this path, launch_decode_embed: an aligned group of 8 lanes is inside the row or outside it, on the last trip too)
             const float q[4] = {Ty<T>::rnd(o[0]), Ty<T>::rnd(o[1]), Ty<T>::rnd(o[2]), Ty<T>::rnd(o[3])};
             int e8;
             const uint32_t pk = mx_quant4_oct(q, e8);
@@ -798,6 +798,131 @@ template <typename T>
 int launch_rmsnorm(const T* x, long ldx, const T* w, T* y, long ldy, const int* src_row, int rows, int C, float eps, hipStream_t s) {
     if (rows <= 0) return SA_OK;
     hipLaunchKernelGGL(rmsnorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, ldx, w, y, ldy, src_row, rows, C, eps);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The launches of the other kernels above: RecModel<T> and the surya_op_rec_* hooks (rec_ops.h) both go through them, so a kernel tested
+// through its hook has the grid, the block, the kernel instance and the refusals the engine gives it. Plain arguments only.
+template <typename T>
+int launch_convert_tiles(const float* in, T* out, const int* src_row, int P, int kin, int kout, hipStream_t s) {
+    if (P <= 0) return SA_OK;
+    if (kout % 4 || kin > kout) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(convert_tiles_kernel<T>, dim3(P), dim3(64), 0, s, in, out, src_row, P, kin, kout);
+    return (int)hipGetLastError();
+}
+// tab [P][D / 2] (cos, sin); no storage type: the qkv GEMM's epilogue multiplies in fp32
+inline int launch_rope_vision_table(const int* pos_hw, const float* inv_freq, float2* tab, int P, int D, hipStream_t s) {
+    if (P <= 0) return SA_OK;
+    if (D <= 0 || D % 4) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(rope_vision_table_kernel, dim3((unsigned)cdivl((long)P * (D / 2), 256)), dim3(256), 0, s, pos_hw, inv_freq, tab, P, D);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_scatter_image(const T* merged, const T* hemb, const T* wemb, const int* dst_row, const int* hidx, const int* widx, T* embeds, int rows,
+                         int H, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    if (H % 4) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(scatter_image_kernel<T>, dim3(rows), dim3(128), 0, s, merged, hemb, wemb, dst_row, hidx, widx, embeds, H);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_scatter_rows(const T* src, const int* dst_row, T* dst, int rows, int H, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    if (H % Ty<T>::V16) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(scatter_rows_kernel<T>, dim3((unsigned)rows), dim3(128), 0, s, src, dst_row, dst, H);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_embed_tokens(const T* table, const int* ids, T* x, int rows, int H, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    if (H % Ty<T>::V16) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(embed_tokens_kernel<T>, dim3(rows), dim3(128), 0, s, table, ids, x, H);
+    return (int)hipGetLastError();
+}
+// table [Tmax][half] (cos, sin), rounded to T; also the layout / table decoder's table
+template <typename T>
+int launch_rope_table(const float* inv_freq, float2* table, int Tmax, int half, hipStream_t s) {
+    if (Tmax <= 0 || half <= 0 || (long)Tmax * half > 0x7fffffffL) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(rope_table_kernel<T>, dim3(cdiv(Tmax * half, 256)), dim3(256), 0, s, inv_freq, table, Tmax, half);
+    return (int)hipGetLastError();
+}
+template <typename T>
+int launch_rope_kv_append(T* qkv, const int* tok_slot, const int* tok_pos, const float2* rope_cs, T* kc, T* vc, int M, int nq, int nkv, int D,
+                          int Tmax, hipStream_t s) {
+    if (M <= 0) return SA_OK;
+    if (D <= 0 || D % 2 || nq <= 0 || nkv <= 0) return SA_ERR_SHAPE;
+    hipLaunchKernelGGL(rope_kv_append_kernel<T>, dim3(M), dim3(256), 0, s, qkv, tok_slot, tok_pos, rope_cs, kc, vc, nq, nkv, D, Tmax);
+    return (int)hipGetLastError();
+}
+
+// splitk_residual_norm_kernel: one 4-element chunk per thread in whole waves, and only as many slab loads per thread as the slice count
+// needs (the sums are the same: the extra slabs were masked duplicates); Tuning::rnorm = 1 keeps the round-3 instance, eight loads
+// whatever S. pf: the engine's prefetch workgroups (KvPrefetch above), M more workgroups; nobody else fills it. No bias: this engine's
+// projections have none.
+template <typename T>
+int launch_reduce_norm(const float* part, int S, int M, T* x, const T* w, T* y, int H, float eps, uint8_t* y8, uint8_t* sy, int srows,
+                       const KvPrefetch& pf, hipStream_t s) {
+    const int threads = cdiv(H / 4, 64) * 64;
+    if (threads > 1024 || H % 4) return SA_ERR_UNSUPPORTED;
+    const int grid = pf.base ? 2 * M : M;
+#define SA_RNORM(SL) hipLaunchKernelGGL((splitk_residual_norm_kernel<T, SL>), dim3(grid), dim3(threads), 0, s, part, S, M, x, (const T*)nullptr, \
+                                        w, y, H, eps, y8, sy, srows, pf)
+    if (tuning().rnorm == 1 || S > 4) SA_RNORM(8);
+    else if (S > 2) SA_RNORM(4);
+    else SA_RNORM(2);
+#undef SA_RNORM
+    return (int)hipGetLastError();
+}
+
+// The round-4 head / embedding kernels hold a row's operands in registers: partial tiles, hidden size and the fused embedding are bounded
+// by their thread geometry; anything larger keeps the round-3 kernels. mx: the model runs MXFP8 decode weights.
+inline bool head2_ok(int H, bool mx) { return tuning().ghead == 2 && H <= 2048 && H % 8 == 0 && (!mx || H % 32 == 0); }
+
+// First step of a decode call: embed_slots_norm2_kernel where head2_ok, else the one-wave embed_slots_norm_kernel.
+template <typename T>
+int launch_decode_embed(const T* table, const int* next_token, const int* active_slots, const int* kv_len, int Tmax, int* row_len, T* x,
+                        const T* w, T* y, int rows, int H, float eps, uint8_t* y8, uint8_t* sy, int srows, bool mx, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    if (H % 4 || (y8 && H % 128)) return SA_ERR_SHAPE;       // 4-element chunks; the MXFP8 copy: whole 128-element K-tiles (set_mx_weights)
+    if (head2_ok(H, mx)) {
+        hipLaunchKernelGGL(embed_slots_norm2_kernel<T>, dim3(rows), dim3(SA_HEAD_THREADS), 0, s, table, next_token, active_slots, kv_len, Tmax,
+                           row_len, x, w, y, H, eps, y8, sy, srows);
+        return (int)hipGetLastError();
+    }
+    hipLaunchKernelGGL(embed_slots_norm_kernel<T>, dim3(rows), dim3(64), 0, s, table, next_token, active_slots, kv_len, Tmax, row_len, x, w, y, H,
+                       eps, y8, sy, srows);
+    return (int)hipGetLastError();
+}
+
+// The greedy head on the lm_head's per-tile partials [rows][tiles_n]. table != nullptr: the fused next-step embedding (x, y, row_len of
+// row r; row_slot is the active list), which only greedy_head2_kernel has -- where the fallback head has to run, SA_ERR_STATE.
+template <typename T>
+struct HeadArgs {
+    const float4* part; int tiles_n; int rows;
+    const T* hidden; int H; const T* wb; const T* bb; const int* row_slot;
+    int eos_id, pad_id; float bbox_size;
+    int* out_token; float* out_score; int* out_bbox; int* next_token; int* kv_len; int len_inc;
+    const T* table = nullptr; const T* wnorm = nullptr; T* x = nullptr; T* y = nullptr; int* row_len = nullptr; int Tmax = 0; float eps = 0.f;
+    uint8_t* y8 = nullptr; uint8_t* sy = nullptr; int srows = 0;
+    float2* best_tot = nullptr;
+    ForcedHead fh;
+};
+template <typename T>
+int launch_head(const HeadArgs<T>& a, bool mx, hipStream_t s) {
+    if (a.rows <= 0) return SA_OK;
+    if (a.tiles_n <= 0) return SA_ERR_ARG;
+    if (head2_ok(a.H, mx) && a.tiles_n <= 4 * SA_HEAD_THREADS) {
+        hipLaunchKernelGGL((greedy_head2_kernel<T>), dim3(a.rows), dim3(SA_HEAD_THREADS), 0, s, a.part, a.tiles_n, a.hidden, a.H, a.wb, a.bb,
+                           a.row_slot, a.eos_id, a.pad_id, a.bbox_size, a.out_token, a.out_score, a.out_bbox, a.next_token, a.kv_len, a.len_inc,
+                           a.table, a.wnorm, a.x, a.y, a.row_len, a.Tmax, a.eps, a.table ? a.y8 : (uint8_t*)nullptr,
+                           a.table ? a.sy : (uint8_t*)nullptr, a.srows, a.best_tot, a.fh);
+        return (int)hipGetLastError();
+    }
+    if (a.table) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
+    hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(a.rows), dim3(256), 0, s, reinterpret_cast<const float*>(a.part), (long)a.tiles_n,
+                       a.tiles_n, a.hidden, a.H, a.wb, a.bb, a.row_slot, a.eos_id, a.pad_id, a.bbox_size, a.out_token, a.out_score, a.out_bbox,
+                       a.next_token, a.kv_len, a.len_inc, a.best_tot, a.fh);
     return (int)hipGetLastError();
 }
 

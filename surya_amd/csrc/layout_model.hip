@@ -380,10 +380,8 @@ struct LayoutModel : LayoutBase {
             const void* tabs[17];
             for (int i = 0; i < 17; ++i) tabs[i] = w[SA_LW_EMB_TABLES + i];
             SA_HIP(hipMemcpy((void*)tabs_dev, tabs, sizeof(tabs), hipMemcpyHostToDevice));
-            const int half = hd() / 2, nn = c.max_boxes * half;
-            hipLaunchKernelGGL(rope_table_kernel<T>, dim3(cdiv(nn, 256)), dim3(256), 0, 0, reinterpret_cast<const float*>(w[SA_LW_DEC_INVFREQ]),
-                               rope_cs, c.max_boxes, half);
-            SA_HIP(hipGetLastError());
+            const int trc = launch_rope_table<T>(reinterpret_cast<const float*>(w[SA_LW_DEC_INVFREQ]), rope_cs, c.max_boxes, hd() / 2, 0);
+            if (trc) return trc;
         }
         SA_HIP(hipHostMalloc((void**)&pinned, B * (MAX_PROMPT * 10 * sizeof(int) + (c.label_count + 6) * sizeof(float)) + 256, hipHostMallocDefault));
         int rrc = init_rings();

@@ -331,10 +331,8 @@ struct RecModel : RecBase {
         poison_arena(arena, arena_bytes);
         layout(c, this);
         {
-            const int half = c.dec_head_dim / 2, n = c.max_kv_len * half;
-            hipLaunchKernelGGL(rope_table_kernel<T>, dim3(cdiv(n, 256)), dim3(256), 0, 0,
-                               reinterpret_cast<const float*>(w[SA_RW_DEC_INVFREQ]), rope_cs, c.max_kv_len, half);
-            SA_HIP(hipGetLastError());
+            const int rc = launch_rope_table<T>(reinterpret_cast<const float*>(w[SA_RW_DEC_INVFREQ]), rope_cs, c.max_kv_len, c.dec_head_dim / 2, 0);
+            if (rc) return rc;
         }
         SA_HIP(hipMemset(kv_len, 0, c.max_slots * sizeof(int)));
         SA_HIP(hipMemset(next_token, 0, c.max_slots * sizeof(int)));
@@ -450,13 +448,11 @@ struct RecModel : RecBase {
             if (rc) return rc;
 
             const int Pi = (int)P;
-            hipLaunchKernelGGL(convert_tiles_kernel<T>, dim3(Pi), dim3(64), 0, s, tiles + patch_base * c.patch_dim, tiles_t,
-                               d_src_row, Pi, c.patch_dim, c.patch_dim_pad);
+            if ((rc = launch_convert_tiles<T>(tiles + patch_base * c.patch_dim, tiles_t, d_src_row, Pi, c.patch_dim, c.patch_dim_pad, s))) return rc;
             if ((rc = gemm<EPI_BIAS>(tiles_t, c.patch_dim_pad, W(SA_RW_PATCH), c.patch_dim_pad, ex, He, nullptr, nullptr, 0, Pi,
                                      He, c.patch_dim_pad, s))) return rc;
             const float scale = 1.0f / sqrtf((float)D);
-            hipLaunchKernelGGL(rope_vision_table_kernel, dim3((unsigned)cdivl((long)Pi * (D / 2), 256)), dim3(256), 0, s, d_pos,
-                               reinterpret_cast<const float*>(w[SA_RW_ENC_INVFREQ]), erope, Pi, D);
+            if ((rc = launch_rope_vision_table(d_pos, reinterpret_cast<const float*>(w[SA_RW_ENC_INVFREQ]), erope, Pi, D, s))) return rc;
             for (int l = 0; l < c.enc_depth; ++l) {
                 if ((rc = rmsnorm(ex, He, WE(l, SA_RE_NORM1), eh, He, nullptr, Pi, He, c.enc_eps, s))) return rc;
                 {   // qkv projection with the 2-D rotary embedding of q and k in its epilogue (pair-interleaved weight rows)
@@ -483,9 +479,7 @@ struct RecModel : RecBase {
             if ((rc = gemm<EPI_GELU>(eh, Hm, W(SA_RW_FC1_W), Hm, emh, Hm, W(SA_RW_FC1_B), nullptr, 0, Mg, Hm, Hm, s))) return rc;
             if ((rc = gemm<EPI_BIAS>(emh, Hm, W(SA_RW_FC2_W), Hm, emerged, c.enc_out_hidden, W(SA_RW_FC2_B), nullptr, 0, Mg,
                                      c.enc_out_hidden, Hm, s))) return rc;
-            hipLaunchKernelGGL(scatter_image_kernel<T>, dim3(Mg), dim3(128), 0, s, emerged, W(SA_RW_IMG_H), W(SA_RW_IMG_W), d_dst,
-                               d_hidx, d_widx, dst, c.dec_hidden);
-            if ((rc = (int)hipGetLastError())) return rc;
+            if ((rc = launch_scatter_image<T>(emerged, W(SA_RW_IMG_H), W(SA_RW_IMG_W), d_dst, d_hidx, d_widx, dst, Mg, c.dec_hidden, s))) return rc;
             patch_base += P;
             tok_base += P / unit;
             i0 = i1;
@@ -545,8 +539,7 @@ struct RecModel : RecBase {
             if ((rc = rmsnorm(dx, Hd, WD(l, SA_RD_LN1), dh, Hd, nullptr, M, Hd, c.dec_eps, s))) return rc;
             if ((rc = gemm<EPI_BIAS>(dh, Hd, WD(l, SA_RD_QKV_W), Hd, dqkv, qkv_d, WD(l, SA_RD_QKV_B), nullptr, 0, M, qkv_d, Hd, s)))
                 return rc;
-            hipLaunchKernelGGL(rope_kv_append_kernel<T>, dim3(M), dim3(256), 0, s, dqkv, d_tok_slot, d_tok_pos, rope_cs, kc, vc,
-                               nq, nkv, d, c.max_kv_len);
+            if ((rc = launch_rope_kv_append<T>(dqkv, d_tok_slot, d_tok_pos, rope_cs, kc, vc, M, nq, nkv, d, c.max_kv_len, s))) return rc;
             if constexpr (std::is_same<T, bf16_t>::value) {
                 if (kv8) {
                     const size_t l8 = (size_t)c.max_slots * nkv, T8 = tmax8();
@@ -579,8 +572,6 @@ struct RecModel : RecBase {
     // while the reduce runs (KvPrefetch, kernels.h). bf16 cache only; nullptr = plain reduce.
     int reduce_residual_norm(int S, int M, const float* part_, T* x, const T* wnorm, T* y, hipStream_t s, uint8_t* y8 = nullptr,
                              uint8_t* sy = nullptr, const T* pf_cache = nullptr, const Half* h = nullptr) {
-        const int threads = cdiv(c.dec_hidden / 4, 64) * 64;         // one 4-element chunk per thread
-        if (threads > 1024 || c.dec_hidden % 4) return SA_ERR_UNSUPPORTED;
         KvPrefetch pf;
         if (pf_cache && h && tuning().kvprefetch && (c.dec_head_dim * sizeof(T)) % 16 == 0) {
             pf.base = reinterpret_cast<const unsigned char*>(pf_cache);
@@ -589,15 +580,7 @@ struct RecModel : RecBase {
             pf.slot_stride = pf.head_stride * c.dec_kv_heads;
             pf.heads = c.dec_kv_heads; pf.row_bytes = c.dec_head_dim * (int)sizeof(T); pf.max_rows = c.max_kv_len;
         }
-        const int grid = pf.base ? 2 * M : M;
-#define SA_RNORM(SL) hipLaunchKernelGGL((splitk_residual_norm_kernel<T, SL>), dim3(grid), dim3(threads), 0, s, part_, S, M, x, (const T*)nullptr, \
-                                        wnorm, y, c.dec_hidden, c.dec_eps, y8, sy, c.max_slots, pf)
-        // only as many slab loads per thread as the slice count needs (the sums are the same: the extra slabs were masked duplicates)
-        if (tuning().rnorm == 1 || S > 4) SA_RNORM(8);
-        else if (S > 2) SA_RNORM(4);
-        else SA_RNORM(2);
-#undef SA_RNORM
-        return (int)hipGetLastError();
+        return launch_reduce_norm<T>(part_, S, M, x, wnorm, y, c.dec_hidden, c.dec_eps, y8, sy, c.max_slots, pf, s);
     }
     // Activation scale tensors are K-tile-major with max_slots rows per K-tile ([K / 128][max_slots][4]); a row range of the
     // batch is a pointer offset of 4 bytes per row.
@@ -820,24 +803,12 @@ struct RecModel : RecBase {
     }
 
 
-    // The round-4 head / embedding kernels (kernels.h) hold a row's operands in registers: partial tiles, hidden size and the fused
-    // embedding are bounded by their thread geometry; anything larger keeps the round-3 kernels.
-    bool head2_ok() const {
-        return tuning().ghead == 2 && c.dec_hidden <= 2048 && c.dec_hidden % 8 == 0 && (!mx() || c.dec_hidden % 32 == 0);
-    }
+    bool head2_ok() const { return sa::head2_ok(c.dec_hidden, mx()); }       // the rule of launch_decode_embed / launch_head (kernels.h)
     int decode_embed(const Half& h) {
         const int Hd = c.dec_hidden;
-        if (head2_ok()) {
-            hipLaunchKernelGGL(embed_slots_norm2_kernel<T>, dim3(h.M), dim3(SA_HEAD_THREADS), 0, h.s, W(SA_RW_TOK_EMBED), next_token,
-                               active_dev + h.r0, kv_len, c.max_kv_len, row_len + h.r0, dx + (size_t)h.r0 * Hd, WD(0, SA_RD_LN1),
-                               dh + (size_t)h.r0 * Hd, Hd, c.dec_eps, mx() ? dh8 + (size_t)h.r0 * Hd : nullptr,
-                               mx() ? sdh + (size_t)h.r0 * 4 : nullptr, c.max_slots);
-            return (int)hipGetLastError();
-        }
-        hipLaunchKernelGGL(embed_slots_norm_kernel<T>, dim3(h.M), dim3(64), 0, h.s, W(SA_RW_TOK_EMBED), next_token, active_dev + h.r0,
-                           kv_len, c.max_kv_len, row_len + h.r0, dx + (size_t)h.r0 * Hd, WD(0, SA_RD_LN1), dh + (size_t)h.r0 * Hd, Hd,
-                           c.dec_eps, mx() ? dh8 + (size_t)h.r0 * Hd : nullptr, mx() ? sdh + (size_t)h.r0 * 4 : nullptr, c.max_slots);
-        return (int)hipGetLastError();
+        return launch_decode_embed<T>(W(SA_RW_TOK_EMBED), next_token, active_dev + h.r0, kv_len, c.max_kv_len, row_len + h.r0, dx + (size_t)h.r0 * Hd,
+                                      WD(0, SA_RD_LN1), dh + (size_t)h.r0 * Hd, h.M, Hd, c.dec_eps, mx() ? dh8 + (size_t)h.r0 * Hd : nullptr,
+                                      mx() ? sdh + (size_t)h.r0 * 4 : nullptr, c.max_slots, mx(), h.s);
     }
 
     // One decoder layer of one decode step for the rows of `h`. The three skinny projections (qkv, o, down) run split-K so
@@ -970,22 +941,14 @@ struct RecModel : RecBase {
                                alt_token + so * SA_MAX_ALTERNATIVES, alt_prob + so * SA_MAX_ALTERNATIVES);
             return (int)hipGetLastError();
         };
-        if (head2_ok() && tiles_n <= 4 * SA_HEAD_THREADS) {
-            const bool fz = fuse_next;
-            hipLaunchKernelGGL((greedy_head2_kernel<T>), dim3(rows), dim3(SA_HEAD_THREADS), 0, s, reinterpret_cast<const float4*>(am), tiles_n,
-                               last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id, c.pad_token_id, (float)c.bbox_size,
-                               out_token + so, out_score + so, out_bbox + so * 6, next_token, kv_len, len_inc,
-                               fz ? W(SA_RW_TOK_EMBED) : (const T*)nullptr, WD(0, SA_RD_LN1), dx, dh, row_len, c.max_kv_len, c.dec_eps,
-                               (fz && mx()) ? dh8 : (uint8_t*)nullptr, (fz && mx()) ? sdh : (uint8_t*)nullptr, c.max_slots, bt, fh);
-            return combine();
-        }
-        if (fuse_next) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
-        hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(rows), dim3(256), 0, s, reinterpret_cast<const float*>(am),
-                           (long)tiles_n, tiles_n, last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id,
-                           c.pad_token_id, (float)c.bbox_size, out_token + so, out_score + so, out_bbox + so * 6, next_token,
-                           kv_len, len_inc, bt, fh);
-        last_rows = rows;
-        last_heads_mx = mx() && normed;
+        const bool fz = fuse_next;
+        HeadArgs<T> ha{reinterpret_cast<const float4*>(am), tiles_n, rows, last, Hd, W(SA_RW_BBOX_W), W(SA_RW_BBOX_B), d_row_slot, c.eos_token_id,
+                       c.pad_token_id, (float)c.bbox_size, out_token + so, out_score + so, out_bbox + so * 6, next_token, kv_len, len_inc};
+        ha.table = fz ? W(SA_RW_TOK_EMBED) : (const T*)nullptr;
+        ha.wnorm = WD(0, SA_RD_LN1); ha.x = dx; ha.y = dh; ha.row_len = row_len; ha.Tmax = c.max_kv_len; ha.eps = c.dec_eps;
+        ha.y8 = (fz && mx()) ? dh8 : (uint8_t*)nullptr; ha.sy = (fz && mx()) ? sdh : (uint8_t*)nullptr; ha.srows = c.max_slots;
+        ha.best_tot = bt; ha.fh = fh;
+        if ((rc = launch_head<T>(ha, mx(), s))) return rc;
         return combine();
     }
 
@@ -1036,7 +999,7 @@ struct RecModel : RecBase {
             const int* d_ids = st.put(ids);
             if (!d_ids) return SA_ERR_NOMEM;
             if ((rc = st.flush(s))) return rc;
-            hipLaunchKernelGGL(embed_tokens_kernel<T>, dim3(Ttot), dim3(128), 0, s, W(SA_RW_TOK_EMBED), d_ids, dx, c.dec_hidden);
+            if ((rc = launch_embed_tokens<T>(W(SA_RW_TOK_EMBED), d_ids, dx, Ttot, c.dec_hidden, s))) return rc;
         }
         if (n_images > 0 && tiles) {
             if ((rc = encode(tiles, grid_hw, n_images, img_pos, dx, s))) return rc;
@@ -1048,8 +1011,7 @@ struct RecModel : RecBase {
             if (!d_img) return SA_ERR_NOMEM;
             if ((rc = st.flush(s))) return rc;
             SA_HIP(hipStreamWaitEvent(s, ev_ahead_done, 0));
-            hipLaunchKernelGGL(scatter_rows_kernel<T>, dim3((unsigned)ntok), dim3(128), 0, s, emb_ahead + ahead_consumed * c.dec_hidden,
-                               d_img, dx, c.dec_hidden);
+            if ((rc = launch_scatter_rows<T>(emb_ahead + ahead_consumed * c.dec_hidden, d_img, dx, (int)ntok, c.dec_hidden, s))) return rc;
             ahead_consumed += ntok;
             SA_HIP(hipEventRecord(ev_ahead_free, s));
             ahead_free_recorded = true;

@@ -11,6 +11,7 @@
 //   * the greedy head keeps next-token / length state on the device, so n decode steps need no host round trip.
 // The engine itself, RecModel<T>, is rec_engine.h: this file instantiates it for float and bf16_t, rec_model_f16.hip for fp16_t.
 #include "rec_engine.h"
+#include "rec_ops.h"
 #include "rec_prep.h"
 
 namespace sa {
@@ -618,6 +619,50 @@ int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y,
     if (dtype == SA_DTYPE_F32) return sa::launch_rmsnorm<float>((const float*)x, ldx, (const float*)w, (float*)y, ldy, nullptr, rows, C, eps, s);
     if (dtype == SA_DTYPE_BF16) return sa::launch_rmsnorm<bf16_t>((const bf16_t*)x, ldx, (const bf16_t*)w, (bf16_t*)y, ldy, nullptr, rows, C, eps, s);
     return SA_ERR_UNSUPPORTED;
+}
+
+// ---- the recogniser's non-GEMM kernels alone (rec_ops.h): one entry per op, the dtype picks the instance
+static int rec_dispatch(int dtype, int op, const void* a, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SA_DTYPE_F32) return sa::rec_op_any<float>(op, a, s);
+    if (dtype == SA_DTYPE_BF16) return sa::rec_op_any<bf16_t>(op, a, s);
+    if (dtype == SA_DTYPE_F16) return sa::op_rec_f16(op, a, s);
+    return SA_ERR_UNSUPPORTED;
+}
+
+int surya_op_rec_rmsnorm_rows(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, const int32_t* src_row, int rows, int C,
+                              float eps, void* stream) {
+    const sa::RecRmsRowsOp a{x, ldx, w, y, ldy, src_row, rows, C, eps};
+    return rec_dispatch(dtype, sa::REC_OP_RMS_ROWS, &a, stream);
+}
+int surya_op_rec_rows(int dtype, int kind, void* dst, const void* src, const void* src2, const void* src3, const int32_t* index,
+                      const int32_t* index2, const int32_t* index3, const int32_t* dims, void* stream) {
+    const sa::RecRowsOp a{kind, dst, src, src2, src3, index, index2, index3, dims};
+    return rec_dispatch(dtype, sa::REC_OP_ROWS, &a, stream);
+}
+int surya_op_rec_rope_table(int dtype, int kind, const int32_t* pos_hw, const float* inv_freq, float* table, int n, int d, void* stream) {
+    const sa::RecRopeTableOp a{kind, pos_hw, inv_freq, table, n, d};
+    return rec_dispatch(dtype, sa::REC_OP_ROPE_TABLE, &a, stream);
+}
+int surya_op_rec_rope_kv_append(int dtype, void* qkv, const int32_t* tok_slot, const int32_t* tok_pos, const float* rope_cs, void* kcache,
+                                void* vcache, int n_tokens, int heads, int kv_heads, int head_dim, int max_kv_len, void* stream) {
+    const sa::RecRopeKvOp a{qkv, tok_slot, tok_pos, rope_cs, kcache, vcache, n_tokens, heads, kv_heads, head_dim, max_kv_len};
+    return rec_dispatch(dtype, sa::REC_OP_ROPE_KV, &a, stream);
+}
+int surya_op_rec_reduce_norm(int dtype, const float* part, int S, int M, void* x, const void* w, void* y, int H, float eps, uint8_t* y8,
+                             uint8_t* sy, int srows, void* stream) {
+    const sa::RecReduceOp a{part, S, M, x, w, y, H, eps, y8, sy, srows};
+    return rec_dispatch(dtype, sa::REC_OP_REDUCE, &a, stream);
+}
+int surya_op_rec_decode_embed(int dtype, const void* table, const int32_t* next_token, const int32_t* active_slots, const int32_t* kv_len,
+                              int max_kv_len, int32_t* row_len, void* x, const void* w, void* y, int rows, int H, float eps, uint8_t* y8,
+                              uint8_t* sy, int srows, void* stream) {
+    const sa::RecEmbedOp a{table, next_token, active_slots, kv_len, max_kv_len, row_len, x, w, y, rows, H, eps, y8, sy, srows};
+    return rec_dispatch(dtype, sa::REC_OP_EMBED, &a, stream);
+}
+int surya_op_rec_head(int dtype, const surya_rec_head_args* args, void* stream) {
+    if (!args) return SA_ERR_ARG;
+    return rec_dispatch(dtype, sa::REC_OP_HEAD, args, stream);
 }
 
 }  // extern "C"

@@ -6,6 +6,7 @@
 // (surya_rec_set_mx_weights / surya_rec_set_kv_fp8 return SA_ERR_UNSUPPORTED, as on an fp32 engine), and decode_attn_flash_kernel -- at
 // Tuning::dattn = 3 an fp16 engine runs decode_attn_flash2_kernel.
 #include "rec_engine.h"
+#include "rec_ops.h"
 
 namespace sa {
 
@@ -57,6 +58,9 @@ int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N,
     *bn_used = a.bn_used;
     return rc;
 }
+
+// the fp16 arm of the surya_op_rec_* entries (rec_model.hip): the launchers of kernels.h on the fp16 instances
+int op_rec_f16(int op, const void* args, hipStream_t s) { return rec_op_any<fp16_t>(op, args, s); }
 
 }  // namespace sa
 
