@@ -279,6 +279,40 @@ int surya_rec_set_forced_tokens(surya_rec* h, const int32_t* slots, const int32_
 int surya_rec_read_forced(surya_rec* h, int n_steps, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs, void* stream);
 int surya_rec_wait_forced(surya_rec* h, int n_steps, int ring, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs);
 
+/* Beam search: the `width` best readings of a line instead of the greedy one -- what a caller of a seq2seq OCR engine gets from num_beams.
+ * The reference cannot do it without replacing its cache; here a line owns `width` consecutive slots (a group, lead slot g * width), the
+ * candidates of a beam are the SA_MAX_ALTERNATIVES tokens the *_TOPK epilogues already report (the best `width` of width x 4 candidates is
+ * exact beam search for width <= 4), a small kernel behind topk_combine_kernel selects and places the survivors, and a copy kernel forks the
+ * KV rows of a beam that continues twice. The rules are stated once, in csrc/beam_core.h: score = sum of log p(token | image, prefix), eos
+ * included, no length normalisation, log p = float(log(double(p))), fp32 sums; a finished beam (eos, pad; at the first token also the
+ * no-output id) stays in the set as one frozen candidate and keeps stepping on pad; order = score descending, parent slot ascending, rank
+ * ascending; a parent's best child stays in the parent's slot, further children go to the slots of beams that did not survive, so a step
+ * in which every beam continues once copies nothing; fewer candidates than slots leave empty beams (parent -1, score -inf). The line is
+ * prefilled once, into the lead slot; the first selection takes the best `width` first tokens of that slot and forks the prompt's rows.
+ * Per step the engine launches head -> combine -> select -> fork -> embed (the head does not fuse the next embedding: it depends on the
+ * selection), three launches more than greedy; nothing in it needs the host, so surya_rec_decode(n) and surya_rec_decode_async keep working.
+ *   set_beam:    width 0 = off, 2..SA_MAX_BEAMS = on, anything else SA_ERR_ARG; no_output_token_id: the tokenizer's id that ends a line at its
+ *                first token (-1: none). The first switch-on allocates the beam arrays, their pinned mirror and the alternatives arena if
+ *                it is absent; a handle that never switches it on allocates nothing and launches exactly what it launched before this entry
+ *                existed. Switching drops captured decode steps. SA_ERR_STATE while forcing, the FP8 KV cache or MXFP8 weights are on, and
+ *                surya_rec_set_forced(1) / surya_rec_set_kv_fp8(1) / surya_rec_set_mx_weights(non-NULL) return SA_ERR_STATE while beam
+ *                search is on (the fork copies the bf16 / fp16 / fp32 caches only). Token masks are allowed: the candidates are then the
+ *                allowed tokens; set a line's mask id on every slot of its group. surya_rec_set_alternatives stays independent, and
+ *                surya_rec_read_alternatives / wait_alternatives also work while beam search is on (the alternatives of the beam that sat in
+ *                the slot BEFORE the step's selection). Call while no line is in flight.
+ *   while on:    surya_rec_prefill takes lead slots only (slot % width == 0 and slot + width <= max_slots, else SA_ERR_ARG), and
+ *                surya_rec_set_active whole groups only, ascending (else SA_ERR_ARG). tokens / scores of surya_rec_read_outputs are each
+ *                slot's own greedy choice and mean nothing; the box of a beam at a step is bboxes[step][its parent's slot].
+ *   read_beam / wait_beam: [n_steps][max_slots] tokens (pad for a frozen or empty beam), parents (slot index inside the group the beam came
+ *                from: its own index when it stayed in place, -1 = empty), ranks (which alternative of the parent), probs (the token's
+ *                probability, 0 for a frozen or empty beam) and logps (cumulative score, -inf = empty) of the steps
+ *                surya_rec_read_outputs / surya_rec_wait_outputs return, same indexing; surya_rec_decode_async mirrors the ring half behind
+ *                the same event. SA_ERR_STATE while off, and from wait_beam for a ring half whose decode_async ran while off. */
+#define SA_MAX_BEAMS 4
+int surya_rec_set_beam(surya_rec* h, int width, int no_output_token_id);
+int surya_rec_read_beam(surya_rec* h, int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, void* stream);
+int surya_rec_wait_beam(surya_rec* h, int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -426,6 +460,22 @@ int surya_op_rec_decode_embed(int dtype, const void* table, const int32_t* next_
                               int max_kv_len, int32_t* row_len, void* x, const void* w, void* y, int rows, int H, float eps, uint8_t* y8,
                               uint8_t* sy, int srows, void* stream);
 int surya_op_rec_head(int dtype, const surya_rec_head_args* args, void* stream);
+/* Beam search's two kernels alone (csrc/beam.h), through the launchers the engine uses; device pointers.
+ *   beam_select: `n_groups` groups of `width` consecutive slots out of `n_slots`; group g starts at slot lead_slots[g * stride] (NULL:
+ *                g * width). In / out per slot: score, finished. In: alt_token / alt_prob [n_slots][SA_MAX_ALTERNATIVES]. Out per slot:
+ *                token, parent, rank, prob, logp, next_token (pad for a finished beam), fork_src (absolute source slot or -1). With kv_len
+ *                (else all four NULL): a first selection copies the lead's kv_len to the group and into prompt_len; fork_base = prompt_len,
+ *                or 0 on a first selection and for a slot whose beam was empty; fork_len = min(the lead's kv_len, max_kv_len).
+ *   kv_fork:     caches [layers][slots][kv_heads][max_kv_len][head_dim] of `dtype`; for every slot r < rows with fork_src[r] >= 0, rows
+ *                [base[r], len[r]) of every layer, kv head, K and V are copied from slot fork_src[r] to slot r. A source must not be a
+ *                destination of the same call. head_dim * sizeof(dtype) must be a multiple of 16 and the caches 16-byte aligned
+ *                (SA_ERR_SHAPE). Unknown dtype: SA_ERR_UNSUPPORTED. */
+int surya_op_rec_beam_select(const int32_t* lead_slots, int stride, int n_groups, int width, int n_slots, const int32_t* alt_token,
+                             const float* alt_prob, float* score, int32_t* finished, int eos_id, int pad_id, int no_output_id, int first,
+                             int32_t* token, int32_t* parent, int32_t* rank, float* prob, float* logp, int32_t* next_token, int32_t* fork_src,
+                             int32_t* kv_len, int32_t* prompt_len, int32_t* fork_base, int32_t* fork_len, int max_kv_len, void* stream);
+int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* fork_src, const int32_t* base, const int32_t* len, int rows,
+                         int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream);
 
 /* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
  * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).
@@ -781,7 +831,8 @@ int surya_ocrerr_forward(surya_ocrerr* h, const int32_t* ids, const int32_t* tex
  * stream. surya_prof_read syncs the device and returns, per bucket (0: 128x128 GEMM, 1: tall 256-row GEMM tiles, 2: smaller GEMM tiles,
  * 3: implicit-GEMM convolutions),
  * the number of launches, the summed event time (ms) and the summed ALGORITHMIC flops / bytes
- * (2MNK; X + W + C (+R) once each). Arrays need >= 4 entries. Not for use inside timed regions.
+ * (2MNK; X + W + C (+R) once each). Arrays need >= 4 entries; a reader that passes 6 also gets beam search's two launches (4: the selection,
+ * 5: the KV fork; launches and time only). Not for use inside timed regions.
  * ---------------------------------------------------------------------------------------------------------- */
 int surya_prof_enable(int on);
 /* Launch-policy knob for A/B measurements inside one process (tools/microbench/decode_sweep.py; keys = the fields of

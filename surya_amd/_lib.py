@@ -13,7 +13,8 @@ LIB_PATH = os.environ.get("SURYA_AMD_LIB") or os.path.join(HERE, "libsurya_amd.s
 
 SA_MAX_STEPS = 16
 SA_MAX_ALTERNATIVES = 4                         # alternatives per token (surya_rec_set_alternatives); top_k < 4 is a slice on the host
-SA_MAX_FORCED_TOKENS = 1024                     # forced ids per slot (surya_rec_set_forced_tokens)
+SA_MAX_BEAMS = 4                                # widest beam (surya_rec_set_beam): a row reports four candidates
+SA_MAX_FORCED_TOKENS = 1024                    # forced ids per slot (surya_rec_set_forced_tokens)
 SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
 OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
@@ -130,6 +131,13 @@ def _bind_lay_ops(lib):
     lib.surya_rec_read_forced.argtypes, lib.surya_rec_read_forced.restype = [p, i, ip, fp, fp, p], C.c_int
     lib.surya_rec_wait_forced.argtypes, lib.surya_rec_wait_forced.restype = [p, i, i, ip, fp, fp], C.c_int
     lib.surya_op_lm_head_forced.argtypes, lib.surya_op_lm_head_forced.restype = [i, p, p, p, p, p, i, i, i, p, p, p, ip, p], C.c_int
+    # beam search (the n best readings of a line) and its two kernels by themselves
+    lib.surya_rec_set_beam.argtypes, lib.surya_rec_set_beam.restype = [p, i, i], C.c_int
+    lib.surya_rec_read_beam.argtypes, lib.surya_rec_read_beam.restype = [p, i, ip, ip, ip, fp, fp, p], C.c_int
+    lib.surya_rec_wait_beam.argtypes, lib.surya_rec_wait_beam.restype = [p, i, i, ip, ip, ip, fp, fp], C.c_int
+    lib.surya_op_rec_beam_select.argtypes = [p, i, i, i, i, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, i, p]
+    lib.surya_op_rec_beam_select.restype = C.c_int
+    lib.surya_op_rec_kv_fork.argtypes, lib.surya_op_rec_kv_fork.restype = [i, p, p, p, p, p, i, i, i, i, i, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

@@ -1813,7 +1813,8 @@ __global__ __launch_bounds__(512) void gemm_nt_p8p_kernel(GemmArgs<TI, TO> p) {
 // Optional per-launch timing with HIP events on the launch stream (bench.py's `roofline` object): one record per
 // tile configuration, accumulating launches, algorithmic FLOPs / bytes and event-measured milliseconds.
 struct GemmProfiler {
-    static constexpr int NCFG = 4, POOL = 8192;
+    static constexpr int NCFG = 4, POOL = 8192;               // NCFG: the GEMM buckets every reader gets
+    static constexpr int NCFG_ALL = 6;                        // + 4: beam_select_kernel, 5: kv_fork_kernel (time only; a reader that asks for them)
     bool enabled = false;
     hipEvent_t ev[2 * POOL];
     bool have_events = false;

@@ -17,6 +17,7 @@
 #include "decode_attn.h"
 #include "decode_attn_kv8.h"
 #include "attn_mfma.h"
+#include "beam.h"
 
 namespace sa {
 
@@ -159,6 +160,9 @@ struct RecBase {
     virtual int set_forced_tokens(const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int read_forced(int, int32_t*, float*, float*, hipStream_t) = 0;
     virtual int wait_forced(int, int, int32_t*, float*, float*) = 0;
+    virtual int set_beam(int, int) = 0;
+    virtual int read_beam(int, int32_t*, int32_t*, int32_t*, float*, float*, hipStream_t) = 0;
+    virtual int wait_beam(int, int, int32_t*, int32_t*, int32_t*, float*, float*) = 0;
 };
 
 // surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
@@ -266,6 +270,17 @@ struct RecModel : RecBase {
     bool forcing = false;
     bool ring_forced[2] = {false, false};                // the last decode_async on this ring half mirrored the forced outputs
     ForcedCols forced_cols(const int* d_row_slot) const { return ForcedCols{forced_table, forced_cursor, d_row_slot, SA_MAX_FORCED_TOKENS, flogit}; }
+    // Beam search (surya_rec_set_beam; beam.h, beam_core.h): per slot the beam's cumulative score, finished flag, its group's prompt length
+    // and the fork plan of the step (source slot, first row, row count); the five [SA_MAX_STEPS][max_slots] outputs and their pinned mirror,
+    // allocated on the first switch-on at addresses that never change afterwards. beam == 0: every launch is the one of a handle without
+    // this entry. beam > 0: the lm_head runs its *_TOPK epilogue whatever `alts` says, and the head never fuses the next step's embedding.
+    char* beam_arena = nullptr;
+    float* beam_score = nullptr; int *beam_fin = nullptr, *beam_prompt = nullptr, *fork_src = nullptr, *fork_base = nullptr, *fork_len = nullptr;   // [max_slots]
+    int *beam_token = nullptr, *beam_parent = nullptr, *beam_rank = nullptr; float *beam_prob = nullptr, *beam_logp = nullptr;
+    char* beam_host = nullptr;
+    int beam = 0, beam_nop = -1;
+    bool ring_beam[2] = {false, false};                  // the last decode_async on this ring half mirrored the beam outputs
+    bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
     const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
     const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
 
@@ -372,6 +387,8 @@ struct RecModel : RecBase {
         if (mask_arena) { (void)hipFree(mask_arena); st_mask.destroy(); }
         if (alt_arena) (void)hipFree(alt_arena);
         if (alt_host) (void)hipHostFree(alt_host);
+        if (beam_arena) (void)hipFree(beam_arena);
+        if (beam_host) (void)hipHostFree(beam_host);
         if (forced_arena) { (void)hipFree(forced_arena); st_forced.destroy(); }
         if (forced_host) (void)hipHostFree(forced_host);
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
@@ -603,6 +620,7 @@ struct RecModel : RecBase {
     }
     int set_kv_fp8(int on) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return on ? SA_ERR_UNSUPPORTED : SA_OK;
+        if (on && beam > 0) return SA_ERR_STATE;            // the KV fork copies the bf16 / fp16 / fp32 caches only
         if ((on != 0) != kv8) drop_graphs();
         if (!on) { kv8 = false; return SA_OK; }
         const int d = c.dec_head_dim;
@@ -692,7 +710,16 @@ struct RecModel : RecBase {
     int set_alternatives(int on) override {
         if (on != 0 && on != 1) return SA_ERR_ARG;
         if (on && forcing) return SA_ERR_STATE;
-        if (on && !alt_arena) {
+        if (on) {
+            const int rc = ensure_alt_arena();
+            if (rc) return rc;
+        }
+        if ((on != 0) != alts) drop_graphs();
+        alts = on != 0;
+        return SA_OK;
+    }
+    int ensure_alt_arena() {
+        if (!alt_arena) {
             const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S * SA_MAX_ALTERNATIVES;
             const size_t part_bytes = align_up(S * (size_t)cdiv(c.vocab, 64) * SA_MAX_ALTERNATIVES * sizeof(float2));
             const size_t bt_bytes = align_up(S * sizeof(float2)), out_b = align_up(outs * sizeof(int));
@@ -709,16 +736,72 @@ struct RecModel : RecBase {
             alt_token = reinterpret_cast<int*>(mem + part_bytes + bt_bytes);
             alt_prob = reinterpret_cast<float*>(mem + part_bytes + bt_bytes + out_b);
         }
-        if ((on != 0) != alts) drop_graphs();
-        alts = on != 0;
         return SA_OK;
+    }
+
+    // Beam search on (width 2..SA_MAX_BEAMS) / off (0). Memory on the first switch-on, or nothing (a failure leaves the handle as it was);
+    // switching drops captured steps, which hold the other lm_head kernel, the fused or unfused head and no selection / fork launches.
+    int set_beam(int width, int nop_id) override {
+        if (width != 0 && (width < 2 || width > SA_MAX_BEAMS || width > c.max_slots)) return SA_ERR_ARG;
+        if (width && (forcing || kv8 || mx())) return SA_ERR_STATE;
+        if (width) {
+            int rc = ensure_alt_arena();
+            if (rc) return rc;
+            if (!beam_arena) {
+                const size_t S = c.max_slots, slot_b = align_up(S * 4), out_b = align_up((size_t)SA_MAX_STEPS * S * 4);
+                char* mem = nullptr;
+                char* host = nullptr;
+                SA_HIP(hipMalloc((void**)&mem, 6 * slot_b + 5 * out_b));
+                rc = (int)hipHostMalloc((void**)&host, (size_t)SA_MAX_STEPS * S * 20, hipHostMallocDefault);
+                if (!rc) rc = (int)hipMemset(mem, 0, 6 * slot_b + 5 * out_b);
+                if (!rc) rc = (int)hipMemset(mem + 3 * slot_b, 0xff, slot_b);       // fork_src -1: nothing to copy
+                if (rc) { if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
+                beam_arena = mem;
+                beam_host = host;
+                beam_score = reinterpret_cast<float*>(mem); beam_fin = reinterpret_cast<int*>(mem + slot_b);
+                beam_prompt = reinterpret_cast<int*>(mem + 2 * slot_b); fork_src = reinterpret_cast<int*>(mem + 3 * slot_b);
+                fork_base = reinterpret_cast<int*>(mem + 4 * slot_b); fork_len = reinterpret_cast<int*>(mem + 5 * slot_b);
+                char* o = mem + 6 * slot_b;
+                beam_token = reinterpret_cast<int*>(o); beam_parent = reinterpret_cast<int*>(o + out_b); beam_rank = reinterpret_cast<int*>(o + 2 * out_b);
+                beam_prob = reinterpret_cast<float*>(o + 3 * out_b); beam_logp = reinterpret_cast<float*>(o + 4 * out_b);
+            }
+        }
+        if (width != beam) drop_graphs();
+        beam = width;
+        beam_nop = nop_id;
+        return SA_OK;
+    }
+    // Selection and fork of one step for `n_groups` groups: lead slots at list[g * stride] (beam.h). first: the prefill's selection.
+    int beam_step(const int* list, int stride, int n_groups, int step, int first, hipStream_t s) {
+        const size_t so = (size_t)step * c.max_slots;
+        BeamSelectArgs a{list, stride, n_groups, beam, c.max_slots, alt_token + so * SA_MAX_ALTERNATIVES, alt_prob + so * SA_MAX_ALTERNATIVES,
+                         beam_score, beam_fin, c.eos_token_id, c.pad_token_id, beam_nop, first, beam_token + so, beam_parent + so, beam_rank + so,
+                         beam_prob + so, beam_logp + so, next_token, fork_src, kv_len, beam_prompt, fork_base, fork_len, c.max_kv_len};
+        GemmProfiler& pf = gemm_profiler();                   // surya_prof_enable: the two launches as buckets 4 and 5 (time only)
+        auto timed = [&](int bucket, auto&& launch) -> int {
+            const bool prof = pf.enabled && pf.n < GemmProfiler::POOL;
+            if (prof) (void)hipEventRecord(pf.ev[2 * pf.n], s);
+            const int rc = launch();
+            if (prof) {
+                (void)hipEventRecord(pf.ev[2 * pf.n + 1], s);
+                pf.cfg_of[pf.n] = bucket; pf.flops_of[pf.n] = pf.bytes_of[pf.n] = pf.slab_of[pf.n] = 0.0;
+                ++pf.n;
+            }
+            return rc;
+        };
+        int rc = timed(4, [&] { return launch_beam_select(a, s); });
+        if (rc) return rc;
+        return timed(5, [&] {
+            return launch_kv_fork<T>(kcache, vcache, list, stride == 1 ? beam : 1, fork_src, fork_base, fork_len, n_groups * beam, c.dec_layers,
+                                     c.max_slots, c.dec_kv_heads, c.max_kv_len, c.dec_head_dim, s);
+        });
     }
 
     // Forced decoding on / off. Memory on the first switch-on, or nothing (a failure leaves the handle as it was); switching drops captured
     // steps, which hold the other lm_head kernel and the head's empty / filled ForcedHead. Switch-off sets the table back to -1.
     int set_forced(int on) override {
         if (on != 0 && on != 1) return SA_ERR_ARG;
-        if (on && (n_token_masks > 0 || alts)) return SA_ERR_STATE;
+        if (on && (n_token_masks > 0 || alts || beam > 0)) return SA_ERR_STATE;
         const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S;
         const size_t table_bytes = align_up(S * SA_MAX_FORCED_TOKENS * sizeof(int)), slot_bytes = align_up(S * sizeof(int)), out_b = align_up(outs * 4);
         if (on && !forced_arena) {
@@ -780,6 +863,7 @@ struct RecModel : RecBase {
     int set_mx_weights(const void* const* tbl, int n) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return SA_ERR_UNSUPPORTED;
         if (!tbl) { if (!mxw.empty()) drop_graphs(); mxw.clear(); return SA_OK; }     // back to the bf16 decode weights
+        if (beam > 0) return SA_ERR_STATE;
         if (n != SA_MX_TOTAL(c.dec_layers)) return SA_ERR_ARG;
         for (int i = 0; i < n; ++i)
             if (!tbl[i]) return SA_ERR_ARG;
@@ -901,7 +985,7 @@ struct RecModel : RecBase {
                 if (forcing) {
                     a.forced = forced_cols(d_row_slot);
                     if ((rc = launch_gemm_mx<MX_EPI_FORCED>(a, s))) return rc;
-                } else if (alts) {
+                } else if (topk()) {
                     if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
                     a.alt = alt_part;
                     if ((rc = launch_gemm_mx<MX_EPI_TOPK>(a, s))) return rc;
@@ -917,7 +1001,7 @@ struct RecModel : RecBase {
             if (forcing) {
                 a.forced = forced_cols(d_row_slot);
                 if ((rc = launch_gemm<T, float, EPI_FORCED>(a, s))) return rc;
-            } else if (alts) {
+            } else if (topk()) {
                 if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
                 a.alt = alt_part;
                 if ((rc = launch_gemm<T, float, EPI_TOPK>(a, s))) return rc;
@@ -931,12 +1015,12 @@ struct RecModel : RecBase {
         const size_t so = (size_t)step * c.max_slots;
         last_rows = rows;
         last_heads_mx = mx() && normed;
-        float2* bt = alts ? best_tot : nullptr;
+        float2* bt = topk() ? best_tot : nullptr;
         ForcedHead fh;                                        // empty while forcing is off: the heads do what they always did
         if (forcing) fh = ForcedHead{forced_table, forced_cursor, flogit, SA_MAX_FORCED_TOKENS, greedy_token + so, greedy_prob + so, forced_logprob + so};
         // alternatives: the row's four best candidates and their probabilities, behind whichever head ran
         auto combine = [&]() -> int {
-            if ((rc = (int)hipGetLastError()) || !alts) return rc;
+            if ((rc = (int)hipGetLastError()) || !topk()) return rc;
             hipLaunchKernelGGL(topk_combine_kernel, dim3(rows), dim3(SA_ALT_THREADS), 0, s, alt_part, tiles_n, d_row_slot, bt,
                                alt_token + so * SA_MAX_ALTERNATIVES, alt_prob + so * SA_MAX_ALTERNATIVES);
             return (int)hipGetLastError();
@@ -964,9 +1048,10 @@ struct RecModel : RecBase {
         for (int i = 0; i < n_seqs; ++i) {
             const int a = seq_offsets[i], L = seq_offsets[i + 1] - a;
             if (L <= 0 || L >= c.max_kv_len || slot_ids[i] < 0 || slot_ids[i] >= c.max_slots) return SA_ERR_ARG;
+            if (beam > 0 && (slot_ids[i] % beam || slot_ids[i] + beam > c.max_slots)) return SA_ERR_ARG;      // lead slots of whole groups only
             lens[i] = L; last_row[i] = a + L - 1;
             if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
-            h_len[slot_ids[i]] = L;
+            for (int b = 0; b < std::max(beam, 1); ++b) h_len[slot_ids[i] + b] = L;
             for (int t = 0; t < L; ++t) {
                 const int id = input_ids[a + t];
                 if (id < 0 || id >= c.vocab) return SA_ERR_ARG;
@@ -1024,7 +1109,8 @@ struct RecModel : RecBase {
         if ((rc = st.flush(s))) return rc;
         hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, s, d_slots, d_lens, kv_len, n_seqs);
         if ((rc = decoder_layers_prefill(Ttot, d_tok_slot, d_tok_pos, &d_sg, (int)sg.tile_seg.size(), s))) return rc;
-        return heads(n_seqs, d_last, d_slots, 0, 0, false, s);
+        if ((rc = heads(n_seqs, d_last, d_slots, 0, 0, false, s)) || beam == 0) return rc;
+        return beam_step(d_slots, 1, n_seqs, 0, 1, s);       // the B best first tokens, and the prompt's rows to the group's other slots
     }
 
     int set_active(const int32_t* slots, int n, hipStream_t s) override {
@@ -1032,6 +1118,13 @@ struct RecModel : RecBase {
         n_active = n;
         for (int i = 0; i < n; ++i)
             if (slots[i] < 0 || slots[i] >= c.max_slots) return SA_ERR_ARG;
+        if (beam > 0) {                                     // whole groups, ascending
+            if (n % beam) return SA_ERR_ARG;
+            for (int i = 0; i < n; ++i) {
+                const int lead = slots[i - i % beam];
+                if (lead % beam || slots[i] != lead + i % beam || (i >= beam && i % beam == 0 && lead <= slots[i - beam])) return SA_ERR_ARG;
+            }
+        }
         h_active.assign(slots, slots + n);
         if (n == 0) return SA_OK;
         st_small.begin();
@@ -1050,7 +1143,7 @@ struct RecModel : RecBase {
     int decode_eager(int M, int n_steps, int step0, hipStream_t s) {
         int rc;
         const Half h{0, M, part, s};
-        const bool fuse = can_fuse_embed();
+        const bool fuse = can_fuse_embed() && beam == 0;      // beam search: the next step's input is the selection's, not the head's
         if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
         for (int step = 0; step < n_steps; ++step) {
             ctx_bound = 0;
@@ -1062,6 +1155,7 @@ struct RecModel : RecBase {
             for (int l = 0; l < c.dec_layers; ++l)
                 if ((rc = decode_layer(l, h))) return rc;
             if ((rc = heads(M, nullptr, active_dev, step0 + step, 1, true, s, fuse && step + 1 < n_steps))) return rc;
+            if (beam > 0 && (rc = beam_step(active_dev, beam, M / beam, step0 + step, 0, s))) return rc;
         }
         return SA_OK;
     }
@@ -1083,11 +1177,17 @@ struct RecModel : RecBase {
             SA_HIP(hipMemcpyAsync(out_host + full * 4 + off * 4, out_score + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
             SA_HIP(hipMemcpyAsync(out_host + full * 8 + off * 24, out_bbox + off * 6, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
         }
-        ring_alts[ring] = alts;
-        if (nt && alts) {
+        ring_alts[ring] = topk();
+        if (nt && topk()) {
             const size_t A = SA_MAX_ALTERNATIVES;
             SA_HIP(hipMemcpyAsync(alt_host + off * A * 4, alt_token + off * A, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
             SA_HIP(hipMemcpyAsync(alt_host + (full + off) * A * 4, alt_prob + off * A, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
+        }
+        ring_beam[ring] = beam > 0;
+        if (nt && beam > 0) {
+            const int* src[5] = {beam_token, beam_parent, beam_rank, (const int*)beam_prob, (const int*)beam_logp};
+            for (int k = 0; k < 5; ++k)
+                SA_HIP(hipMemcpyAsync(beam_host + ((size_t)k * full + off) * 4, src[k] + off, nt * 4, hipMemcpyDeviceToHost, s));
         }
         ring_forced[ring] = forcing;
         if (nt && forcing) {
@@ -1127,7 +1227,7 @@ struct RecModel : RecBase {
     // Alternatives of the steps wait_outputs / read_outputs return: [step][slot][SA_MAX_ALTERNATIVES], same indexing
     int wait_alternatives(int n_steps, int ring, int32_t* tokens, float* probs) override {
         if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        if (!alts || !ring_alts[ring]) return SA_ERR_STATE;       // (a call enqueued while the feature was off mirrored nothing)
+        if (!topk() || !ring_alts[ring]) return SA_ERR_STATE;       // (a call enqueued while the feature was off mirrored nothing)
         SA_HIP(hipEventSynchronize(ev_ring[ring]));
         const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
         const size_t nt = (size_t)n_steps * S;
@@ -1137,13 +1237,35 @@ struct RecModel : RecBase {
     }
     int read_alternatives(int n_steps, int32_t* tokens, float* probs, hipStream_t s) override {
         if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        if (!alts) return SA_ERR_STATE;
+        if (!topk()) return SA_ERR_STATE;
         const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
         SA_HIP(hipMemcpyAsync(alt_host, alt_token, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
         SA_HIP(hipMemcpyAsync(alt_host + full * A * 4, alt_prob, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
         SA_HIP(hipStreamSynchronize(s));
         memcpy(tokens, alt_host, nt * A * sizeof(int));
         memcpy(probs, alt_host + full * A * 4, nt * A * sizeof(float));
+        return SA_OK;
+    }
+
+    // Beam outputs of the steps wait_outputs / read_outputs return: five [step][slot] arrays, same indexing
+    int wait_beam(int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps) override {
+        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
+        if (beam == 0 || !ring_beam[ring]) return SA_ERR_STATE;   // (a call enqueued while the feature was off mirrored nothing)
+        SA_HIP(hipEventSynchronize(ev_ring[ring]));
+        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S, nt = (size_t)n_steps * S;
+        void* dst[5] = {tokens, parents, ranks, probs, logps};
+        for (int k = 0; k < 5; ++k) memcpy(dst[k], beam_host + ((size_t)k * full + off) * 4, nt * 4);
+        return SA_OK;
+    }
+    int read_beam(int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, hipStream_t s) override {
+        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
+        if (beam == 0) return SA_ERR_STATE;
+        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
+        const int* src[5] = {beam_token, beam_parent, beam_rank, (const int*)beam_prob, (const int*)beam_logp};
+        for (int k = 0; k < 5; ++k) SA_HIP(hipMemcpyAsync(beam_host + (size_t)k * full * 4, src[k], nt * 4, hipMemcpyDeviceToHost, s));
+        SA_HIP(hipStreamSynchronize(s));
+        void* dst[5] = {tokens, parents, ranks, probs, logps};
+        for (int k = 0; k < 5; ++k) memcpy(dst[k], beam_host + (size_t)k * full * 4, nt * 4);
         return SA_OK;
     }
 

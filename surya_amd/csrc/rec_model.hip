@@ -270,6 +270,19 @@ int surya_rec_wait_forced(surya_rec* h, int n_steps, int ring, int32_t* greedy_t
     return h->impl->wait_forced(n_steps, ring, greedy_tokens, greedy_probs, forced_logprobs);
 }
 
+int surya_rec_set_beam(surya_rec* h, int width, int no_output_token_id) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_beam(width, no_output_token_id);
+}
+int surya_rec_read_beam(surya_rec* h, int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, void* stream) {
+    if (!h || !tokens || !parents || !ranks || !probs || !logps) return SA_ERR_ARG;
+    return h->impl->read_beam(n_steps, tokens, parents, ranks, probs, logps, (hipStream_t)stream);
+}
+int surya_rec_wait_beam(surya_rec* h, int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps) {
+    if (!h || !tokens || !parents || !ranks || !probs || !logps) return SA_ERR_ARG;
+    return h->impl->wait_beam(n_steps, ring, tokens, parents, ranks, probs, logps);
+}
+
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
 static __global__ void iota_kernel(int* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -596,11 +609,13 @@ int surya_prof_read2(int max_cfg, int* launches, double* ms, double* flops, doub
     GemmProfiler& pf = gemm_profiler();
     if (!launches || !ms || !flops || !bytes || max_cfg < GemmProfiler::NCFG) return SA_ERR_ARG;
     SA_HIP(hipDeviceSynchronize());
-    for (int c = 0; c < GemmProfiler::NCFG; ++c) { launches[c] = 0; ms[c] = flops[c] = bytes[c] = 0.0; if (slab_bytes) slab_bytes[c] = 0.0; }
+    const int ncfg = std::min(max_cfg, (int)GemmProfiler::NCFG_ALL);      // buckets 4 and 5 (beam search) only for a reader with room for them
+    for (int c = 0; c < ncfg; ++c) { launches[c] = 0; ms[c] = flops[c] = bytes[c] = 0.0; if (slab_bytes) slab_bytes[c] = 0.0; }
     for (int i = 0; i < pf.n; ++i) {
+        const int c = pf.cfg_of[i];
+        if (c >= ncfg) continue;
         float t = 0.f;
         SA_HIP(hipEventElapsedTime(&t, pf.ev[2 * i], pf.ev[2 * i + 1]));
-        const int c = pf.cfg_of[i];
         launches[c]++; ms[c] += t; flops[c] += pf.flops_of[i]; bytes[c] += pf.bytes_of[i];
         if (slab_bytes) slab_bytes[c] += pf.slab_of[i];
     }
@@ -663,6 +678,20 @@ int surya_op_rec_decode_embed(int dtype, const void* table, const int32_t* next_
 int surya_op_rec_head(int dtype, const surya_rec_head_args* args, void* stream) {
     if (!args) return SA_ERR_ARG;
     return rec_dispatch(dtype, sa::REC_OP_HEAD, args, stream);
+}
+int surya_op_rec_beam_select(const int32_t* lead_slots, int stride, int n_groups, int width, int n_slots, const int32_t* alt_token,
+                             const float* alt_prob, float* score, int32_t* finished, int eos_id, int pad_id, int no_output_id, int first,
+                             int32_t* token, int32_t* parent, int32_t* rank, float* prob, float* logp, int32_t* next_token, int32_t* fork_src,
+                             int32_t* kv_len, int32_t* prompt_len, int32_t* fork_base, int32_t* fork_len, int max_kv_len, void* stream) {
+    if (n_groups < 0 || (!lead_slots && (long)n_groups * width > n_slots)) return SA_ERR_ARG;
+    const sa::BeamSelectArgs a{lead_slots, stride, n_groups, width, n_slots, alt_token, alt_prob, score, finished, eos_id, pad_id, no_output_id,
+                               first ? 1 : 0, token, parent, rank, prob, logp, next_token, fork_src, kv_len, prompt_len, fork_base, fork_len, max_kv_len};
+    return sa::launch_beam_select(a, (hipStream_t)stream);
+}
+int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* fork_src, const int32_t* base, const int32_t* len, int rows,
+                         int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream) {
+    const sa::RecKvForkOp a{kcache, vcache, fork_src, base, len, rows, layers, slots, kv_heads, max_kv_len, head_dim};
+    return rec_dispatch(dtype, sa::REC_OP_KV_FORK, &a, stream);
 }
 
 }  // extern "C"

@@ -3,6 +3,7 @@
 // instantiated in rec_model.hip, fp16_t in rec_model_f16.hip (op_rec_f16), as the engine is.
 #pragma once
 #include "kernels.h"
+#include "beam.h"
 
 namespace sa {
 
@@ -15,7 +16,8 @@ struct RecEmbedOp {
     const void* table; const int *next_token, *active_slots, *kv_len; int Tmax; int* row_len; void* x; const void* w; void* y;
     int rows, H; float eps; uint8_t *y8, *sy; int srows;
 };
-enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD };
+struct RecKvForkOp { void *kc, *vc; const int *fork_src, *base, *len; int rows, layers, slots, nkv, Tmax, D; };
+enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK };
 
 template <typename T> constexpr bool rec_mx_ok() { return std::is_same<T, bf16_t>::value; }     // the MXFP8 copies exist beside bf16 only
 
@@ -103,6 +105,12 @@ int rec_op(const surya_rec_head_args& a, hipStream_t s) {
 }
 
 template <typename T>
+int rec_op(const RecKvForkOp& a, hipStream_t s) {
+    if (a.rows < 0 || a.rows > a.slots) return SA_ERR_ARG;       // row r is slot r here (the engine passes its active list instead)
+    return launch_kv_fork<T>((T*)a.kc, (T*)a.vc, nullptr, 1, a.fork_src, a.base, a.len, a.rows, a.layers, a.slots, a.nkv, a.Tmax, a.D, s);
+}
+
+template <typename T>
 int rec_op_any(int op, const void* a, hipStream_t s) {
     switch (op) {
         case REC_OP_RMS_ROWS: return rec_op<T>(*static_cast<const RecRmsRowsOp*>(a), s);
@@ -112,6 +120,7 @@ int rec_op_any(int op, const void* a, hipStream_t s) {
         case REC_OP_REDUCE: return rec_op<T>(*static_cast<const RecReduceOp*>(a), s);
         case REC_OP_EMBED: return rec_op<T>(*static_cast<const RecEmbedOp*>(a), s);
         case REC_OP_HEAD: return rec_op<T>(*static_cast<const surya_rec_head_args*>(a), s);
+        case REC_OP_KV_FORK: return rec_op<T>(*static_cast<const RecKvForkOp*>(a), s);
     }
     return SA_ERR_ARG;
 }

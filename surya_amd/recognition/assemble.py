@@ -11,7 +11,7 @@ from ..common.geometry import PolygonBox, coerce_polygon
 from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags, prediction_to_polygon_batch, unwrap_math,
                           words_from_chars)
 from .processor import NOMATH_TOKEN
-from .schema import CharAlternative, TaskNames, TextChar, TextLine
+from .schema import CharAlternative, LineHypothesis, TaskNames, TextChar, TextLine
 
 _SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
 _CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
@@ -31,7 +31,7 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     return m
 
 
-_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob")
+_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -42,7 +42,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     list of TextChar): the object state validation would produce, without walking the character list again."""
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
-                         "original_text_good": False, "words": words, "log_prob": None})
+                         "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -94,6 +94,33 @@ def set_log_prob(line: TextLine, forced) -> TextLine:
     line.log_prob = float(np.sum(np.asarray(forced[2], np.float64)))
     line.__pydantic_fields_set__.add("log_prob")
     return line
+
+
+def assemble_beam_batch(proc, flat, items, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
+    """A beam-search call's lines: items = [(sorted position, original position, hypotheses)], hypotheses the loop's BeamHypothesis list
+    of the line, best first. Every hypothesis goes through assemble_batch like a greedy line (tokens, per-token probabilities as scores,
+    box rows; drop_repeated_text and return_words apply to each); the TextLine is hypothesis 0 with log_prob and `hypotheses` set. A line
+    without a hypothesis (no candidate at all) is the empty line."""
+    flat_items, owner = [], []
+    for i, (sp, orig, hyps) in enumerate(items):
+        for h in hyps or [None]:
+            flat_items.append((sp, orig, [], [], np.zeros((1, 6), np.float32)) if h is None else (sp, orig, h.tokens, h.scores, h.bboxes))
+            owner.append(i)
+    lines = assemble_batch(proc, flat, flat_items, drop_repeated_text, return_words, bbox_size)
+    out, at = [], 0
+    for i, (_, _, hyps) in enumerate(items):
+        n = max(len(hyps), 1)
+        mine = lines[at:at + n]
+        at += n
+        line = mine[0]
+        line.hypotheses = [LineHypothesis(text=ln.text, confidence=ln.confidence, log_prob=h.log_prob, finished=h.finished, chars=ln.chars,
+                                          words=ln.words) for ln, h in zip(mine, hyps)]
+        line.__pydantic_fields_set__.add("hypotheses")
+        if hyps:
+            line.log_prob = float(hyps[0].log_prob)
+            line.__pydantic_fields_set__.add("log_prob")
+        out.append(line)
+    return out
 
 
 def get_bboxes_text(proc, flat, predicted_tokens, scores, predicted_polygons, drop_repeated_text=False, csrc_out=None) -> list:

@@ -2,7 +2,7 @@
 One DeviceLoop per RecognitionPredictor.generate call owns ALL loop state -- queue, slot table, token / score / box matrices, admitted
 chunks, look-ahead queue, the decode call in flight -- so a loop that died leaves nothing behind but what the model handle keeps
 (unconsumed look-ahead images: `run` discards them first). It knows the model surface, not the predictor."""
-from collections import deque
+from collections import deque, namedtuple
 
 import numpy as np
 
@@ -13,6 +13,11 @@ FEED_END = object()          # what a `generate(feed=...)` callable returns once
 _REP = 40                    # detect_repeat_token's window
 _REP_COLS = np.arange(-_REP, 0)
 SA_MAX_ALTERNATIVES = 4      # alternatives the model reports per token (include/surya_amd.h)
+SA_MAX_BEAMS = 4             # widest beam: the best B of B x 4 candidates is exact beam search for B <= 4
+
+# One reading of a line out of a beam run: token ids (eos included when finished), each token's probability, box rows [T, 6], the sum
+# of the tokens' log-probabilities as the device accumulated it, and whether the reading reached eos / pad.
+BeamHypothesis = namedtuple("BeamHypothesis", "tokens scores bboxes log_prob finished")
 
 
 class DeviceLoop:
@@ -44,10 +49,28 @@ class DeviceLoop:
     that argmax's probability and the emitted token's log-probability; the loop keeps them per line (greedy_tok_mat / greedy_p_mat /
     logp_mat [lines, cap]) and hands a finished line's rows to `on_done` as three more arguments. The feature is switched on for the
     run and off on the way out, also after an exception. Not requested: the arrays do not exist and the model's four entry points
-    (set_forced / set_forced_tokens / read_forced / wait_forced) are never called -- a model without them works."""
+    (set_forced / set_forced_tokens / read_forced / wait_forced) are never called -- a model without them works.
+
+    Beam search (`beam=B`, 2..4; not together with alternatives or forced decoding): the model keeps the B best readings of a line in
+    a group of B consecutive slots, so `slots // B` lines are in flight and everything above that says "slot" means a group. A line is
+    prefilled once, into its group's lead slot g * B (its mask id goes to all B slots); the model selects, places and forks on the
+    device (csrc/beam_core.h states the rules) and reports per step and slot the token, the parent slot inside the group, the rank,
+    the token's probability and the cumulative log-probability. The loop keeps per group [B, cap] token / probability / box histories,
+    re-indexed by the parents each step in array form; a child's box is the step's box of its parent's slot. A line ends when all its
+    beams are finished, when its token budget is reached (also right after the prefill), or when the repeat rule fires on the
+    best-scored live beam. `on_done(line, hypotheses)` gets a list of BeamHypothesis, finished ones by log_prob descending, then the
+    unfinished ones; empty beams (fewer candidates than slots) are dropped. The mode is switched on for the run and off on the way
+    out, also after an exception. beam=None: set_beam / read_beam / wait_beam are never called -- a model without them works."""
 
     def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None,
-                 alternatives=False, forced=False):
+                 alternatives=False, forced=False, beam=None):
+        self.beam = int(beam) if beam else 0
+        if self.beam:
+            assert 2 <= self.beam <= SA_MAX_BEAMS and slots >= self.beam, "beam width must be 2..4 and fit the slots"
+            assert not (alternatives or forced), "beam search excludes per-token alternatives and forced decoding"
+            self.model_slots = slots
+            slots //= self.beam                                # from here on a "slot" of this loop is a GROUP of `beam` model slots
+            self.lane = np.arange(self.beam)
         self.model, self.eos, self.pad, self.nop, self.slots = model, eos, pad, nop, slots
         self.overall_max_tokens, self.min_prefill_ratio = overall_max_tokens, min_prefill_ratio
         self.on_done, self.on_flush, self.feed, self.feed_done = on_done, on_flush, feed, feed is None
@@ -75,6 +98,14 @@ class DeviceLoop:
         self.greedy_tok_mat = np.zeros((0, self.cap), np.int32) if self.forced else None
         self.greedy_p_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
         self.logp_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
+        if self.beam:
+            # per group: the beams' token / probability / box histories [groups, beam, cap(, 6)], re-indexed by `parents` every step; their
+            # lengths, cumulative scores, finished flags and whether the slot holds a beam at all
+            B, cap = self.beam, self.cap
+            self.b_tok, self.b_p = np.zeros((slots, B, cap), np.int64), np.zeros((slots, B, cap), np.float32)
+            self.b_box = np.zeros((slots, B, cap, 6), np.float32)
+            self.b_len, self.b_score = np.zeros((slots, B), np.int64), np.full((slots, B), -np.inf, np.float32)
+            self.b_fin, self.b_alive = np.ones((slots, B), bool), np.zeros((slots, B), bool)
         self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
         self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
@@ -150,6 +181,63 @@ class DeviceLoop:
             self.admit(nxt)
             got = got or bool(nxt["prompts"])
 
+    def _finish_beam(self, p_idx, g):
+        """The line of group g is final: its beams as hypotheses, finished ones by score descending, then the unfinished ones."""
+        order = sorted(np.flatnonzero(self.b_alive[g]).tolist(), key=lambda b: (not self.b_fin[g, b], -float(self.b_score[g, b]), b))
+        hyps = []
+        for b in order:
+            n = int(self.b_len[g, b])
+            hyps.append(BeamHypothesis(self.b_tok[g, b, :n].tolist(), self.b_p[g, b, :n].tolist(),
+                                       self.b_box[g, b, :max(min(n, self.overall_max_tokens), 1)].copy(), float(self.b_score[g, b]),
+                                       bool(self.b_fin[g, b])))
+        if hyps:
+            self.predicted_tokens[p_idx], self.scores[p_idx] = hyps[0].tokens, hyps[0].scores
+        if self.on_done is not None:
+            self.on_done(p_idx, hyps)
+
+    def _beam_step(self, g, p, pos, first, tok, par, prob, logp, boxes):
+        """One selection for groups g (lines p, `pos` tokens so far): tok / par / prob / logp [n, beam] as the model reports them per slot,
+        boxes [n, beam, 6] the step's box of every slot BEFORE the selection. Histories move with `par`; a live child appends its token,
+        its probability and its parent's box; a frozen beam keeps what it has; parent -1 empties the slot. -> the lines that end."""
+        B, lane = self.beam, self.lane
+        src = np.where(par >= 0, par, lane[None, :])
+        if first:
+            was_fin = np.zeros(par.shape, bool)
+            self.b_len[g] = 0
+        else:
+            ix = src[:, :, None]
+            self.b_tok[g] = np.take_along_axis(self.b_tok[g], ix, 1)
+            self.b_p[g] = np.take_along_axis(self.b_p[g], ix, 1)
+            self.b_box[g] = np.take_along_axis(self.b_box[g], ix[:, :, :, None], 1)
+            self.b_len[g] = np.take_along_axis(self.b_len[g], src, 1)
+            was_fin = np.take_along_axis(self.b_fin[g], src, 1)
+        alive = par >= 0
+        live = alive & ~was_fin
+        gi, bi = np.nonzero(live)
+        col = pos[gi]
+        self.b_tok[g[gi], bi, col] = tok[gi, bi]
+        self.b_p[g[gi], bi, col] = prob[gi, bi]
+        self.b_box[g[gi], bi, col] = boxes[gi, src[gi, bi]]
+        blen = self.b_len[g]
+        blen[live] = (pos[:, None] + 1 + np.zeros_like(par))[live]
+        self.b_len[g] = blen
+        ends = (tok == self.eos) | (tok == self.pad)
+        if first:
+            ends |= tok == self.nop
+        fin = ~alive | was_fin | ends
+        self.b_fin[g], self.b_alive[g], self.b_score[g] = fin, alive, logp
+        new_len = pos + 1
+        self.line_len[p] = new_len
+        stop = fin.all(axis=1) | (new_len >= self.max_tok[p])
+        # repeat rule (DeviceLoop.absorb's) on the best-ranked live beam: highest score, lower slot on a tie
+        for ci in np.flatnonzero(~stop & (new_len >= _REP)).tolist():
+            sc = np.where(fin[ci], -np.inf, logp[ci])
+            b = int(np.argmax(sc))
+            t_ = self.b_tok[g[ci], b, :new_len[ci]]
+            if np.unique(t_[-_REP:]).size <= 5 and detect_repeat_token(t_.tolist()):
+                stop[ci] = True
+        return stop
+
     def _finish(self, p_idx):
         L_ = int(self.line_len[p_idx])
         self.predicted_tokens[p_idx] = self.tok_mat[p_idx, :L_].tolist()
@@ -180,7 +268,10 @@ class DeviceLoop:
 
     def _flush_active(self):
         """Tell the model which slots still decode (ascending) and let the caller collect the lines that just finished."""
-        self.model.set_active(np.flatnonzero(self.slot_line >= 0).tolist())
+        act = np.flatnonzero(self.slot_line >= 0)
+        if self.beam:
+            act = (act[:, None] * self.beam + self.lane[None, :]).reshape(-1)       # whole groups, ascending
+        self.model.set_active(act.tolist())
         if self.on_flush is not None:
             self.on_flush()
 
@@ -188,6 +279,8 @@ class DeviceLoop:
         """Host half of one decode call: append its tokens, apply the stop rules (reference :583-595)."""
         k, ring = call
         tok, sc, bb = self.model.wait_outputs(k, ring)
+        if self.beam:
+            return self._absorb_beam(k, bb, self.model.wait_beam(k, ring))
         at, ap = self.model.wait_alternatives(k, ring) if self.alternatives else (None, None)
         fo = self.model.wait_forced(k, ring) if self.forced else None
         slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
@@ -224,6 +317,23 @@ class DeviceLoop:
         if changed:
             self._flush_active()
 
+    def _absorb_beam(self, k, bb, out):
+        bt, bpar, _, bprob, blogp = out
+        changed = False
+        for step in range(k):
+            g = np.flatnonzero(self.slot_line >= 0)
+            if g.size == 0:
+                break
+            p = self.slot_line[g]
+            sl = g[:, None] * self.beam + self.lane[None, :]
+            stop = self._beam_step(g, p, self.line_len[p], False, bt[step][sl], bpar[step][sl], bprob[step][sl], blogp[step][sl], bb[step][sl])
+            for ci in np.flatnonzero(stop).tolist():
+                changed = True
+                self.slot_line[int(g[ci])] = -1
+                self._finish_beam(int(p[ci]), int(g[ci]))
+        if changed:
+            self._flush_active()
+
     def encode_ahead(self):
         """Start the encoder pass of the next queued lines: up to a batch, within the look-ahead capacity, of ONE admitted dict."""
         grids, line_chunk = self.grids, self.line_chunk
@@ -254,6 +364,8 @@ class DeviceLoop:
             ntok += L_
         slots = empty[: len(take)]
         grids, prompt_ids = [self.grids[i] for i in take], [self.prompt_ids[i] for i in take]
+        if self.beam:
+            return self._prefill_beam(take, slots, grids, prompt_ids)
         if self.n_masks:
             self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
         if self.forced:
@@ -285,8 +397,42 @@ class DeviceLoop:
                 self._finish(p_id)
         self._flush_active()
 
+    def _prefill_beam(self, take, groups, grids, prompt_ids):
+        """prefill_batch in beam mode: a line is prefilled once, into the lead slot of its group; the model's first selection spreads the
+        best first tokens over the group. A line's mask id goes to every slot of its group."""
+        queue, ahead, B = self.queue, self.ahead, self.beam
+        g = np.asarray(groups, np.int64)
+        sl = g[:, None] * B + self.lane[None, :]
+        if self.n_masks:
+            self.model.set_slot_masks(sl.reshape(-1).tolist(), np.repeat(self.line_mask[take], B).tolist())
+        lead = (g * B).tolist()
+        if self.look_ahead:
+            for i in take:
+                assert ahead.popleft() == i
+            self.model.prefill(None, grids, prompt_ids, lead)
+            if not ahead and queue:
+                self.encode_ahead()
+        else:
+            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, lead)
+        _, _, bb = self.model.read_outputs(1)
+        bt, bpar, _, bprob, blogp = self.model.read_beam(1)
+        p = np.asarray(take, np.int64)
+        stop = self._beam_step(g, p, np.zeros(len(take), np.int64), True, bt[0][sl], bpar[0][sl], bprob[0][sl], blogp[0][sl], bb[0][sl])
+        for p_id, gg, st in zip(take, groups, stop.tolist()):
+            if st:
+                self._finish_beam(p_id, gg)
+            else:
+                self.slot_line[gg] = p_id
+        self._flush_active()
+
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
+        if self.beam:
+            self.model.set_beam(self.beam, self.nop)
+            try:
+                return self._run_masked(prep)
+            finally:
+                self.model.set_beam(None)              # the next call starts on the greedy kernels
         if self.forced:
             self.model.set_forced(True)
             try:

@@ -71,6 +71,8 @@ class HipRecModel:
         self._alt_tok = self._alt_p = None              # host arrays of read_alternatives / wait_alternatives, made on first use
         self.forced = False
         self._forced_bufs = None                        # host arrays of read_forced / wait_forced, made on first use
+        self.beam = 0
+        self._beam_bufs = None                          # host arrays of read_beam / wait_beam, made on first use
         self.decode_fp8 = False
         if decode_fp8 is None:
             from ..settings import settings
@@ -204,6 +206,42 @@ class HipRecModel:
         L.check(self.lib.surya_rec_wait_forced(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(gt), L.np_ptr(gp, C.c_float),
                                                L.np_ptr(lp, C.c_float)), "surya_rec_wait_forced")
         return gt[:n_steps], gp[:n_steps], lp[:n_steps]
+
+    def set_beam(self, width: Optional[int], no_output_token_id: int = -1):
+        """Beam search (surya_rec_set_beam): `width` in 2..SA_MAX_BEAMS keeps the `width` best readings of every line in a group of `width`
+        consecutive slots (prefill names lead slots, set_active whole groups); None or 0 switches it off, and the handle launches the
+        kernels it always launched. Not together with forced decoding, the fp8 KV cache or MXFP8 decode weights."""
+        w = int(width or 0)
+        L.check(self.lib.surya_rec_set_beam(self.handle, C.c_int(w), C.c_int(no_output_token_id)), "surya_rec_set_beam")
+        self.beam = w
+        if w and self._beam_bufs is None:
+            shape = (L.SA_MAX_STEPS, self.max_slots)
+            self._beam_bufs = tuple(np.zeros(shape, t) for t in (np.int32, np.int32, np.int32, np.float32, np.float32))
+        if w and self._alt_tok is None:                     # read_alternatives works in beam mode
+            self._alt_tok = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.int32)
+            self._alt_p = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.float32)
+
+    def _beam_views(self, first):
+        if self._beam_bufs is None:     # never switched on: the library refuses below, with buffers it may not write to anyway
+            return tuple(np.zeros((1, 1), t) for t in (np.int32, np.int32, np.int32, np.float32, np.float32))
+        return tuple(b[first:] for b in self._beam_bufs)
+
+    def read_beam(self, n_steps: int = 1):
+        """Sync; (tokens, parents, ranks [n_steps, slots] int32, probs, logps [n_steps, slots] float32) of the steps read_outputs returns:
+        per slot the beam placed there by the step's selection -- its token (pad: frozen or empty), the slot index inside the group it came
+        from (own index: stayed in place, -1: empty), which alternative of the parent it took, that token's probability and the cumulative
+        log-probability. The box of a beam is read_outputs' box of its parent's slot."""
+        v = self._beam_views(0)
+        L.check(self.lib.surya_rec_read_beam(self.handle, C.c_int(n_steps), L.np_ptr(v[0]), L.np_ptr(v[1]), L.np_ptr(v[2]),
+                                             L.np_ptr(v[3], C.c_float), L.np_ptr(v[4], C.c_float), self._stream), "surya_rec_read_beam")
+        return tuple(a[:n_steps] for a in v)
+
+    def wait_beam(self, n_steps: int, ring: int):
+        """The beam outputs of the decode_async call on `ring`, parallel to wait_outputs."""
+        v = self._beam_views(ring * (L.SA_MAX_STEPS // 2))
+        L.check(self.lib.surya_rec_wait_beam(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(v[0]), L.np_ptr(v[1]), L.np_ptr(v[2]),
+                                             L.np_ptr(v[3], C.c_float), L.np_ptr(v[4], C.c_float)), "surya_rec_wait_beam")
+        return tuple(a[:n_steps] for a in v)
 
     def __del__(self):
         h = getattr(self, "handle", None)

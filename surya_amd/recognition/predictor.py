@@ -163,10 +163,15 @@ class AssemblyHandover(ThreadPoolExecutor):
 
     def assemble(self, batch):
         # batch = [(line id, tokens, scores, bbox_rows)]: the lines that stopped at one synchronisation point
+        if self.pred._beam is not None:                        # a beam-search call: [(line id, hypotheses)]
+            return assemble.assemble_beam_batch(self.pred.processor, self.flat, [(b[0], self.orig_of[b[0]], b[1]) for b in batch], *self.options)
         return self.pred._assemble_batch(self.flat, [(b[0], self.orig_of[b[0]]) + tuple(b[1:]) for b in batch], *self.options)
 
-    def on_done(self, k, tokens, sc, bbox_rows, *alts):
+    def on_done(self, k, tokens, sc=None, bbox_rows=None, *alts):
         # alts: (alternative ids [T, 4], probabilities [T, 4]) of a call with top_k, else nothing
+        if sc is None:                                         # a beam-search call: `tokens` is the line's hypothesis list
+            self.pending.append((k, list(tokens)))
+            return
         self.pending.append((k, list(tokens), list(sc), bbox_rows.copy()) + ((alts,) if alts else ()))
 
     def on_flush(self):
@@ -372,6 +377,8 @@ class RecognitionPredictor(BasePredictor):
         more = {"alternatives": True} if self._top_k is not None else {}      # (only then: a stand-in loop keeps its signature)
         if first.get("forced_ids") is not None:
             more = {"forced": True}
+        elif self._beam is not None:
+            more = {"beam": self._beam}
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
                           min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
                           on_done=on_done, on_flush=on_flush, feed=feed, **more)
@@ -483,20 +490,51 @@ class RecognitionPredictor(BasePredictor):
         None, a str, or a list with one None / str per bbox / polygon of that image (not with det_predictor: the lines are not known
         yet). A line takes one of the two, not both. Tokens and confidences are the reference's process_outputs on logits whose
         disallowed ids are -inf, so a confidence is the softmax over the allowed set; EOS, pad and no-output stay allowed, formatting and
-        math tags do not under an allowlist (OCRTokenizer.token_mask). Stop rules, sorting and assembly are unchanged."""
+        math tags do not under an allowlist (OCRTokenizer.token_mask). Stop rules, sorting and assembly are unchanged.
+
+        `self.beam_width` (an attribute like `top_k`; None = greedy, else 2..4): beam search on the device. Every TextLine carries
+        `hypotheses`, its up to beam_width best readings as LineHypothesis(text, confidence, log_prob, finished, chars) -- finished
+        readings by log_prob descending, then the ones the token budget or the repeat rule cut -- each assembled like a line
+        (`drop_repeated_text` and `return_words` apply to each). The TextLine itself is hypothesis 0 and its `log_prob` is set; it is
+        the most likely whole reading, which may differ from the greedy one. log_prob is the sum of the tokens' log-probabilities,
+        eos included, without length normalisation: comparable with `align`'s. `recognition_batch_size` keeps meaning KV slots, and a
+        line takes beam_width of them, so a beam call decodes recognition_batch_size // beam_width lines at a time. `allowlist` /
+        `blocklist` work with it (the readings are made of allowed characters). ValueError before any device work for another value,
+        together with `top_k` (the alternatives arrays serve the beams), or on a model running MXFP8 decode weights or the fp8 KV cache;
+        NotImplementedError with `shard_lines`, `shard_pages` or a process group. With `det_predictor` a beam call detects all pages
+        before it recognises (no streamed detection). `align` is unaffected."""
         top_k = self.top_k
         if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= 4):
             raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
+        beam = self._check_beam_width(top_k)
         # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
         # page-sharded path and by stand-ins and read it from here)
         saved_k, self._top_k = self._top_k, top_k
+        saved_b, self._beam = self._beam, beam
         try:
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist)
         finally:
-            self._top_k = saved_k
+            self._top_k, self._beam = saved_k, saved_b
             if top_k is not None:
                 self.last_alternatives = None
+
+    def _check_beam_width(self, top_k):
+        """`self.beam_width` validated for a call (None: off), before any device work."""
+        beam = self.beam_width
+        if beam is None:
+            return None
+        if isinstance(beam, bool) or not isinstance(beam, int) or not 2 <= beam <= 4:
+            raise ValueError(f"beam_width must be None or an integer in 2..4, got {beam!r}")
+        if top_k is not None:
+            raise ValueError("beam_width and top_k exclude each other: the alternatives arrays serve the beams")
+        if self.shard_lines or self.shard_pages or self.process_group is not None:
+            raise NotImplementedError("a beam-search call runs on one rank: unset shard_lines / shard_pages / process_group")
+        if getattr(self.model, "decode_fp8", False):
+            raise ValueError("beam_width is not available with MXFP8 decode weights (RECOGNITION_DECODE_FP8 / set_decode_fp8)")
+        if getattr(self.model, "kv_fp8", False):
+            raise ValueError("beam_width is not available with the fp8 KV cache (RECOGNITION_KV_FP8 / set_kv_fp8)")
+        return beam
 
     def forced_ids(self, text: str, task: str) -> List[int]:
         """The ids `align` forces for one line: the tokenizer's ids of the text for the line's task, then eos."""
@@ -548,11 +586,12 @@ class RecognitionPredictor(BasePredictor):
                     raise ValueError(f"image {i}, line {j}: token id {max(ids)} is outside the model's vocabulary of {vocab}")
                 forced.append(ids)
         saved_k, self._top_k = self._top_k, None              # (an aligned call reports `greedy`, not alternatives)
+        saved_b, self._beam = self._beam, None                # (and one reading, the given one, whatever beam_width says)
         try:
             with gc_paused():
                 return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
         finally:
-            self._top_k = saved_k
+            self._top_k, self._beam = saved_k, saved_b
 
     def _align(self, images, forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words) -> List[OCRResult]:
         t_call = time.perf_counter()
@@ -577,6 +616,8 @@ class RecognitionPredictor(BasePredictor):
 
     top_k: int | None = None          # alternatives per character (2..4), None = off: RecognitionPredictor.top_k = 3, or on an instance
     _top_k = None                     # the running call's validated top_k (see __call__)
+    beam_width: int | None = None     # readings per line (2..4), None = greedy: RecognitionPredictor.beam_width = 3, or on an instance
+    _beam = None                      # the running call's validated beam_width (see __call__)
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
 
@@ -752,7 +793,7 @@ class RecognitionPredictor(BasePredictor):
         """This package's detector on its device post-processing path, one process, and a `__call__` nobody overrode (a subclass that
         filters or edits the results in `__call__` must keep seeing every page before the first crop is cut: serial path)."""
         from ..detection.predictor import DetectionPredictor
-        return (self.stream_detection and self.device_preprocess and not self.shard_lines
+        return (self.stream_detection and self.device_preprocess and not self.shard_lines and self._beam is None      # (a beam call: serial)
                 and isinstance(det_predictor, DetectionPredictor)
                 and type(det_predictor).__call__ is DetectionPredictor.__call__ and type(det_predictor)._call is DetectionPredictor._call
                 and type(det_predictor).iter_detect is DetectionPredictor.iter_detect

@@ -76,22 +76,41 @@ class TextWord(BaseChar):
     bbox_valid: bool = True
 
 
+class LineHypothesis(BaseModel):
+    """One reading of a line out of a beam-search call (RecognitionPredictor.beam_width): its text and characters, assembled like a
+    TextLine's, `confidence` computed like a TextLine's, `log_prob` = the sum of log p(token | image, preceding tokens) over its tokens,
+    eos included, without length normalisation (comparable with `align`'s log_prob), and whether the reading reached its end
+    (`finished`) or was cut by the token budget or the repeat rule."""
+    text: str
+    confidence: Optional[float] = 0
+    log_prob: float
+    finished: bool
+    chars: List[TextChar]
+    words: List[TextWord] | None = None
+
+
 class TextLine(BaseChar):
     chars: List[TextChar]
     original_text_good: bool = False
     words: List[TextWord] | None = None
-    # RecognitionPredictor.align: log p(text, eos | image), the sum of the forced tokens' log-probabilities; None, and left out of the
-    # serialised form, in every other result
+    # RecognitionPredictor.align: log p(text, eos | image), the sum of the forced tokens' log-probabilities; in a beam-search call the
+    # score of the line's best reading. None, and left out of the serialised form, in every other result.
+    # `hypotheses` (RecognitionPredictor.beam_width): the line's n best readings, finished ones by log_prob descending, then unfinished
+    # ones; entry 0 is the line itself. None, and left out like log_prob, everywhere else.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
+        hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
+        hypotheses: Optional[List[LineHypothesis]] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
             d = handler(self)
             if self.log_prob is None:
                 d.pop("log_prob", None)
+            if self.hypotheses is None:
+                d.pop("hypotheses", None)
             return d
 
 
