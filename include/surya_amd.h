@@ -151,7 +151,8 @@ int surya_rec_read_outputs(surya_rec* h, int n_steps, int32_t* tokens, float* sc
  * n_steps <= SA_MAX_STEPS / 2) plus an async copy of that half to pinned host memory and an event; wait_outputs blocks on
  * that event only (NOT on the stream, so a later decode_async may already be queued) and returns the arrays laid out
  * like read_outputs. A slot whose line finished inside call n still steps through call n + 1; its KV length is clamped
- * to max_kv_len - 1 on the device and the caller ignores its outputs. */
+ * to max_kv_len - 1 on the device and the caller ignores its outputs. (How every read_* / wait_* pair below shares one mirror
+ * layout: DESIGN.md 4m.) */
 int surya_rec_decode_async(surya_rec* h, int n_steps, int ring, void* stream);
 int surya_rec_wait_outputs(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* scores, int32_t* bboxes);
 

@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <set>
@@ -60,6 +61,86 @@ struct Stager {   // pinned host arena mirrored by a device arena; one H2D copy 
             SA_HIP(hipEventRecord(ev, s));
             pending = true;
         }
+        return SA_OK;
+    }
+};
+
+// -------------------------------------------------------------------------------------------------- arenas
+static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+
+struct Carve {   // offsets of consecutive 256-byte-aligned blocks of one arena; `off` ends up as the arena's size
+    size_t off = 0;
+    size_t take(size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; }
+};
+
+struct DevBlock {   // a zeroed device block and (host_bytes > 0) a pinned host block: both, or nothing
+    char* dev = nullptr;
+    char* host = nullptr;
+    int alloc(size_t dev_bytes, size_t host_bytes) {
+        char *d = nullptr, *h = nullptr;
+        SA_HIP(hipMalloc((void**)&d, dev_bytes));
+        int rc = host_bytes ? (int)hipHostMalloc((void**)&h, host_bytes, hipHostMallocDefault) : SA_OK;
+        if (!rc) rc = (int)hipMemset(d, 0, dev_bytes);
+        if (rc) { if (h) (void)hipHostFree(h); (void)hipFree(d); return rc; }
+        dev = d; host = h;
+        return SA_OK;
+    }
+    void release() {
+        if (host) (void)hipHostFree(host);
+        if (dev) (void)hipFree(dev);
+        dev = host = nullptr;
+    }
+};
+
+// ------------------------------------------------------------------------------------------- step outputs
+// One set of per-step outputs: per field a device array [SA_MAX_STEPS][max_slots][cell bytes] that the head kernels write at
+// step * max_slots, and one pinned mirror that holds the fields one behind the other, each in the device array's order. Ring half r
+// of a pipelined decode call starts at step r * SA_MAX_STEPS / 2. span() is the only place that turns (field, step) into addresses
+// ("Step-output sets").
+struct StepOutputs {
+    static constexpr int MAX_FIELDS = 5;
+    struct Field { const char* dev; size_t cell; };      // device array, bytes per (step, slot) cell
+    struct Span { size_t host, dev, bytes; };            // byte offsets into the mirror and the device array, and the length
+    Field f[MAX_FIELDS] = {};
+    int n = 0;
+    size_t slots = 0;                                    // max_slots
+    char* host = nullptr;                                // the pinned mirror, host_bytes() long
+    bool mirrored[2] = {false, false};                   // the last mirror-or-not decision on this ring half was "mirror"
+    void add(const void* dev, size_t cell) { f[n++] = Field{static_cast<const char*>(dev), cell}; }
+    size_t host_bytes() const { return span(n - 1, SA_MAX_STEPS, 0).host; }      // where the last field ends
+    static int ring_step(int ring) { return ring * (SA_MAX_STEPS / 2); }
+    // Field k starts at (the widths of the fields before it) * SA_MAX_STEPS * max_slots; inside a field a step is `slots` cells.
+    Span span(int k, int step, int n_steps) const {
+        const size_t full = (size_t)SA_MAX_STEPS * slots, off = (size_t)step * slots;
+        size_t before = 0;
+        for (int j = 0; j < k; ++j) before += f[j].cell;
+        return Span{full * before + off * f[k].cell, off * f[k].cell, (size_t)n_steps * slots * f[k].cell};
+    }
+    // Async copies of steps [step, step + n_steps) to the mirror, one per field in field order (none for n_steps == 0).
+    int copy(int step, int n_steps, hipStream_t s) const {
+        for (int k = 0; k < n && n_steps; ++k) {
+            const Span p = span(k, step, n_steps);
+            SA_HIP(hipMemcpyAsync(host + p.host, f[k].dev + p.dev, p.bytes, hipMemcpyDeviceToHost, s));
+        }
+        return SA_OK;
+    }
+    int mirror(int ring, int n_steps, hipStream_t s) {   // the ring half's first n_steps steps
+        mirrored[ring] = true;
+        return copy(ring_step(ring), n_steps, s);
+    }
+    // The ring half's first n_steps steps out of the mirror (the caller has waited for the copies).
+    void wait(int ring, int n_steps, void* const* dst) const {
+        for (int k = 0; k < n; ++k) {
+            const Span p = span(k, ring_step(ring), n_steps);
+            memcpy(dst[k], host + p.host, p.bytes);
+        }
+    }
+    // Steps [0, n_steps), synchronously.
+    int read(int n_steps, void* const* dst, hipStream_t s) const {
+        const int rc = copy(0, n_steps, s);
+        if (rc) return rc;
+        SA_HIP(hipStreamSynchronize(s));
+        wait(0, n_steps, dst);
         return SA_OK;
     }
 };
@@ -137,15 +218,19 @@ static __global__ void set_next_tokens_kernel(const int* slots, const int* toks,
 }
 
 // --------------------------------------------------------------------------------------------------- model
+// The step-output sets of an engine, in the order decode_async mirrors them; the fields of each in the order of its surya_rec_read_* /
+// surya_rec_wait_* arguments (RecModel::init names them).
+enum StepSet { STEPS_BASE = 0, STEPS_ALTS, STEPS_BEAM, STEPS_FORCED, STEPS_SETS };
+
 struct RecBase {
     virtual ~RecBase() {}
     virtual int prefill(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_active(const int32_t*, int, hipStream_t) = 0;
     virtual int encode_ahead(const float*, const int32_t*, int, hipStream_t) = 0;
     virtual int decode(int, hipStream_t) = 0;
-    virtual int read_outputs(int, int32_t*, float*, int32_t*, hipStream_t) = 0;
     virtual int decode_async(int, int, hipStream_t) = 0;
-    virtual int wait_outputs(int, int, int32_t*, float*, int32_t*) = 0;
+    virtual int read_steps(StepSet, int n_steps, std::initializer_list<void*> dst, hipStream_t) = 0;     // dst: one pointer per field of the set
+    virtual int wait_steps(StepSet, int n_steps, int ring, std::initializer_list<void*> dst) = 0;
     virtual int encode_only(const float*, const int32_t*, int, void*, hipStream_t) = 0;
     virtual int copy_last_logits(float*, int, int*, hipStream_t) = 0;
     virtual int set_next_tokens(const int32_t*, const int32_t*, int, hipStream_t) = 0;
@@ -154,15 +239,9 @@ struct RecBase {
     virtual int set_token_masks(const uint32_t*, int, hipStream_t) = 0;
     virtual int set_slot_masks(const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_alternatives(int) = 0;
-    virtual int read_alternatives(int, int32_t*, float*, hipStream_t) = 0;
-    virtual int wait_alternatives(int, int, int32_t*, float*) = 0;
     virtual int set_forced(int) = 0;
     virtual int set_forced_tokens(const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
-    virtual int read_forced(int, int32_t*, float*, float*, hipStream_t) = 0;
-    virtual int wait_forced(int, int, int32_t*, float*, float*) = 0;
     virtual int set_beam(int, int) = 0;
-    virtual int read_beam(int, int32_t*, int32_t*, int32_t*, float*, float*, hipStream_t) = 0;
-    virtual int wait_beam(int, int, int32_t*, int32_t*, int32_t*, float*, float*) = 0;
 };
 
 // surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
@@ -178,7 +257,7 @@ static __global__ void set_slot_masks_kernel(const int* slots, const int* ids, i
     if (i < n) slot_mask[slots[i]] = ids[i];
 }
 
-static size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
+template <int I> using HeadEpi = std::integral_constant<int, I>;      // compile-time index into a weight format's lm_head epilogues (heads())
 
 template <typename T>
 struct RecModel : RecBase {
@@ -204,8 +283,8 @@ struct RecModel : RecBase {
     T *kcache, *vcache;
     int *kv_len, *next_token, *active_dev, *row_len;
     int* out_token; float* out_score; int* out_bbox;     // [SA_MAX_STEPS][max_slots] (bbox x6)
-    char* out_host = nullptr;                            // pinned mirror of the three output arrays
     size_t out_bytes = 0;
+    StepOutputs outs[STEPS_SETS];                        // what decode_async mirrors and read_steps / wait_steps return (StepOutputs above)
     int n_active = 0;
     int last_rows = 0;
     bool last_heads_mx = false;                          // the last heads() call ran the MXFP8 lm_head (test hook below)
@@ -227,10 +306,10 @@ struct RecModel : RecBase {
     // and lm_head, used by the decode steps only (prefill keeps the bf16 weights), and MXFP8 twins of the four decode-step
     // activation buffers, written by the kernels that produce the bf16 ones.
     std::vector<const uint8_t*> mxw;
-    char* mx_arena = nullptr;
+    DevBlock mx_arena;
     // FP8 KV cache of the decode steps (surya_rec_set_kv_fp8; decode_attn_kv8.h). Prefill keeps writing (and attending over) the
     // bf16 cache and quantises the prompt rows into these arrays; the decode steps read and append only here.
-    char* kv8_arena = nullptr;
+    DevBlock kv8_arena;
     uint8_t *k8c = nullptr, *v8tc = nullptr;     // [layer][slot][kvh][Tmax][D], [layer][slot][kvh][D][Tmax8]
     float *ksc8 = nullptr, *vsc8 = nullptr;      // [layer][slot][kvh][Tmax8]
     bool kv8 = false;
@@ -252,35 +331,44 @@ struct RecModel : RecBase {
     // Alternatives (surya_rec_set_alternatives): per-tile candidates of the lm_head's *_TOPK epilogue, the head's (max, total) per slot and
     // the [SA_MAX_STEPS][max_slots][SA_MAX_ALTERNATIVES] outputs with their pinned mirror, allocated on the first switch-on at addresses
     // that never change afterwards. alts == false: the lm_head and head launches are the ones of a handle without this entry.
-    char* alt_arena = nullptr;
+    DevBlock alt_arena;
     float2* alt_part = nullptr;                          // [max_slots][cdiv(vocab, 64)][4]: 64 columns is the narrowest lm_head tile
     float2* best_tot = nullptr;                          // [max_slots]
     int* alt_token = nullptr; float* alt_prob = nullptr; // [SA_MAX_STEPS][max_slots][4]
-    char* alt_host = nullptr;
     bool alts = false;
-    bool ring_alts[2] = {false, false};                  // the last decode_async on this ring half mirrored its alternatives
     // Forced decoding (surya_rec_set_forced): the id table [max_slots][SA_MAX_FORCED_TOKENS] (-1 = free-running), a cursor per slot, the
     // forced logit per lm_head row, the [SA_MAX_STEPS][max_slots] outputs and their pinned mirror, allocated on the first switch-on at
     // addresses that never change afterwards. forcing == false: the lm_head and head launches are the ones of a handle without this entry.
-    char* forced_arena = nullptr;
+    DevBlock forced_arena;
     int* forced_table = nullptr; int* forced_cursor = nullptr; float* flogit = nullptr;
     int* greedy_token = nullptr; float* greedy_prob = nullptr; float* forced_logprob = nullptr;   // [SA_MAX_STEPS][max_slots]
-    char* forced_host = nullptr;
     Stager st_forced;
     bool forcing = false;
-    bool ring_forced[2] = {false, false};                // the last decode_async on this ring half mirrored the forced outputs
     ForcedCols forced_cols(const int* d_row_slot) const { return ForcedCols{forced_table, forced_cursor, d_row_slot, SA_MAX_FORCED_TOKENS, flogit}; }
     // Beam search (surya_rec_set_beam; beam.h, beam_core.h): per slot the beam's cumulative score, finished flag, its group's prompt length
     // and the fork plan of the step (source slot, first row, row count); the five [SA_MAX_STEPS][max_slots] outputs and their pinned mirror,
     // allocated on the first switch-on at addresses that never change afterwards. beam == 0: every launch is the one of a handle without
     // this entry. beam > 0: the lm_head runs its *_TOPK epilogue whatever `alts` says, and the head never fuses the next step's embedding.
-    char* beam_arena = nullptr;
+    DevBlock beam_arena;
     float* beam_score = nullptr; int *beam_fin = nullptr, *beam_prompt = nullptr, *fork_src = nullptr, *fork_base = nullptr, *fork_len = nullptr;   // [max_slots]
     int *beam_token = nullptr, *beam_parent = nullptr, *beam_rank = nullptr; float *beam_prob = nullptr, *beam_logp = nullptr;
-    char* beam_host = nullptr;
     int beam = 0, beam_nop = -1;
-    bool ring_beam[2] = {false, false};                  // the last decode_async on this ring half mirrored the beam outputs
     bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
+    // Which step-output sets the kernels write right now: decode_async mirrors these, read_steps / wait_steps refuse the others.
+    bool steps_on(StepSet k) const { return k == STEPS_BASE || (k == STEPS_ALTS && topk()) || (k == STEPS_BEAM && beam > 0) || (k == STEPS_FORCED && forcing); }
+    // The modes that cannot be on together, and why; every setter asks excluded() before it switches its own mode on.
+    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, MODES };
+    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx()}; return on[m]; }
+    bool excluded(int m) const {
+        static constexpr int pairs[5][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
+                                            {M_FORCED, M_ALTS},       // ... which collects no candidates
+                                            {M_FORCED, M_BEAM},
+                                            {M_BEAM, M_KV8},          // the KV fork copies the bf16 / fp16 / fp32 caches only
+                                            {M_BEAM, M_MX}};         // (beam search on the fp8 decode paths is out of scope: DESIGN.md 4l)
+        for (auto& p : pairs)
+            if ((p[0] == m && mode_on(p[1])) || (p[1] == m && mode_on(p[0]))) return true;
+        return false;
+    }
     const uint8_t* MXW(int l, int k) const { return mxw[(size_t)l * SA_MX_COUNT + k]; }
     const uint8_t* MXG(int k) const { return mxw[(size_t)c.dec_layers * SA_MX_COUNT + k]; }
 
@@ -289,38 +377,37 @@ struct RecModel : RecBase {
     const T* WD(int l, int k) const { return W(SA_RW_DEC(c.enc_depth, l, k)); }
 
     static size_t layout(const surya_rec_config& c, RecModel* m) {
-        size_t off = 0;
-        auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
+        Carve cv;
         const size_t Pm = c.max_patches, Tm = std::max(c.max_prefill_tokens, c.max_slots), S = c.max_slots;
         const int unit = c.merge * c.merge;
         const size_t qkv_d = (size_t)(c.dec_heads + 2 * c.dec_kv_heads) * c.dec_head_dim;
-        size_t o_tiles = take(Pm * c.patch_dim_pad * sizeof(T));
-        size_t o_ex = take(Pm * c.enc_hidden * sizeof(T));
-        size_t o_eh = take(Pm * c.enc_hidden * sizeof(T));
-        size_t o_eqkv = take(Pm * 3 * c.enc_hidden * sizeof(T));
-        size_t o_emlp = take(Pm * c.enc_inter_pad * sizeof(T));
-        size_t o_emh = take(Pm * c.enc_hidden * sizeof(T));                 // [P/unit, unit*He]
-        size_t o_erope = take(Pm * (size_t)(c.enc_hidden / c.enc_heads / 2) * sizeof(float2));
-        size_t o_emerged = take(Pm / unit * c.enc_out_hidden * sizeof(T));
-        size_t o_dx = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_dh = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_dqkv = take(Tm * qkv_d * sizeof(T));
-        size_t o_dattn = take(Tm * c.dec_heads * c.dec_head_dim * sizeof(T));
-        size_t o_dmlp = take(Tm * c.dec_inter * sizeof(T));
-        size_t o_dlast = take(S * c.dec_hidden * sizeof(T));
-        size_t o_ahead = take(Tm * c.dec_hidden * sizeof(T));
-        size_t o_logits = take(S * (size_t)c.vocab * sizeof(float));
-        size_t o_amax = take(S * (size_t)cdiv(c.vocab, 32) * sizeof(float4));
-        size_t o_rope = take((size_t)c.max_kv_len * (c.dec_head_dim / 2) * sizeof(float2));
-        size_t o_part = take((size_t)8 * S * std::max(qkv_d, (size_t)c.dec_hidden) * sizeof(float));
+        size_t o_tiles = cv.take(Pm * c.patch_dim_pad * sizeof(T));
+        size_t o_ex = cv.take(Pm * c.enc_hidden * sizeof(T));
+        size_t o_eh = cv.take(Pm * c.enc_hidden * sizeof(T));
+        size_t o_eqkv = cv.take(Pm * 3 * c.enc_hidden * sizeof(T));
+        size_t o_emlp = cv.take(Pm * c.enc_inter_pad * sizeof(T));
+        size_t o_emh = cv.take(Pm * c.enc_hidden * sizeof(T));                 // [P/unit, unit*He]
+        size_t o_erope = cv.take(Pm * (size_t)(c.enc_hidden / c.enc_heads / 2) * sizeof(float2));
+        size_t o_emerged = cv.take(Pm / unit * c.enc_out_hidden * sizeof(T));
+        size_t o_dx = cv.take(Tm * c.dec_hidden * sizeof(T));
+        size_t o_dh = cv.take(Tm * c.dec_hidden * sizeof(T));
+        size_t o_dqkv = cv.take(Tm * qkv_d * sizeof(T));
+        size_t o_dattn = cv.take(Tm * c.dec_heads * c.dec_head_dim * sizeof(T));
+        size_t o_dmlp = cv.take(Tm * c.dec_inter * sizeof(T));
+        size_t o_dlast = cv.take(S * c.dec_hidden * sizeof(T));
+        size_t o_ahead = cv.take(Tm * c.dec_hidden * sizeof(T));
+        size_t o_logits = cv.take(S * (size_t)c.vocab * sizeof(float));
+        size_t o_amax = cv.take(S * (size_t)cdiv(c.vocab, 32) * sizeof(float4));
+        size_t o_rope = cv.take((size_t)c.max_kv_len * (c.dec_head_dim / 2) * sizeof(float2));
+        size_t o_part = cv.take((size_t)8 * S * std::max(qkv_d, (size_t)c.dec_hidden) * sizeof(float));
         const size_t kv_elems = (size_t)c.dec_layers * S * c.dec_kv_heads * c.max_kv_len * c.dec_head_dim;
-        size_t o_k = take(kv_elems * sizeof(T));
-        size_t o_v = take(kv_elems * sizeof(T));
-        size_t o_kvlen = take(S * sizeof(int));
-        size_t o_next = take(S * sizeof(int));
-        size_t o_active = take(S * sizeof(int));
-        size_t o_rowlen = take(S * sizeof(int));
-        size_t o_out = take((size_t)SA_MAX_STEPS * S * 8 * sizeof(int));
+        size_t o_k = cv.take(kv_elems * sizeof(T));
+        size_t o_v = cv.take(kv_elems * sizeof(T));
+        size_t o_kvlen = cv.take(S * sizeof(int));
+        size_t o_next = cv.take(S * sizeof(int));
+        size_t o_active = cv.take(S * sizeof(int));
+        size_t o_rowlen = cv.take(S * sizeof(int));
+        size_t o_out = cv.take((size_t)SA_MAX_STEPS * S * 8 * sizeof(int));
         if (m) {
             char* b = m->arena;
             m->tiles_t = (T*)(b + o_tiles); m->ex = (T*)(b + o_ex); m->eh = (T*)(b + o_eh); m->eqkv = (T*)(b + o_eqkv);
@@ -335,7 +422,7 @@ struct RecModel : RecBase {
             m->out_bbox = (int*)(m->out_score + (size_t)SA_MAX_STEPS * S);
             m->out_bytes = (size_t)SA_MAX_STEPS * S * 8 * sizeof(int);
         }
-        return off;
+        return cv.off;
     }
 
     int init(const surya_rec_config& cfg, const void* const* weights, int n) {
@@ -352,7 +439,11 @@ struct RecModel : RecBase {
         SA_HIP(hipMemset(kv_len, 0, c.max_slots * sizeof(int)));
         SA_HIP(hipMemset(next_token, 0, c.max_slots * sizeof(int)));
         SA_HIP(hipMemset(out_token, 0, out_bytes));
-        SA_HIP(hipHostMalloc((void**)&out_host, out_bytes, hipHostMallocDefault));
+        for (auto& o : outs) o.slots = c.max_slots;
+        StepOutputs& base = outs[STEPS_BASE];              // always on: a ring half counts as mirrored from the start
+        base.add(out_token, 4); base.add(out_score, 4); base.add(out_bbox, 24);
+        base.mirrored[0] = base.mirrored[1] = true;
+        SA_HIP(hipHostMalloc((void**)&base.host, base.host_bytes(), hipHostMallocDefault));     // (the other sets' mirrors come with their arenas)
         const size_t Pm = c.max_patches, Tm = std::max(c.max_prefill_tokens, c.max_slots);
         int rc = st.init((Pm * 8 + Tm * 8 + (size_t)c.max_slots * 64) * sizeof(int) + (1 << 20));
         if (rc) return rc;
@@ -382,15 +473,9 @@ struct RecModel : RecBase {
         return SA_OK;
     }
     ~RecModel() override {
-        if (mx_arena) (void)hipFree(mx_arena);
-        if (kv8_arena) (void)hipFree(kv8_arena);
-        if (mask_arena) { (void)hipFree(mask_arena); st_mask.destroy(); }
-        if (alt_arena) (void)hipFree(alt_arena);
-        if (alt_host) (void)hipHostFree(alt_host);
-        if (beam_arena) (void)hipFree(beam_arena);
-        if (beam_host) (void)hipHostFree(beam_host);
-        if (forced_arena) { (void)hipFree(forced_arena); st_forced.destroy(); }
-        if (forced_host) (void)hipHostFree(forced_host);
+        for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena}) b->release();
+        if (mask_arena) (void)hipFree(mask_arena);
+        st_mask.destroy(); st_forced.destroy();
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -400,7 +485,7 @@ struct RecModel : RecBase {
         if (estream) (void)hipStreamDestroy(estream);
         for (hipEvent_t e : {ev_ahead_in, ev_ahead_done, ev_ahead_free}) if (e) (void)hipEventDestroy(e);
         if (arena) (void)hipFree(arena);
-        if (out_host) (void)hipHostFree(out_host);
+        if (outs[STEPS_BASE].host) (void)hipHostFree(outs[STEPS_BASE].host);
     }
 
     // ------------------------------------------------------------------------------------------ helpers
@@ -620,22 +705,22 @@ struct RecModel : RecBase {
     }
     int set_kv_fp8(int on) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return on ? SA_ERR_UNSUPPORTED : SA_OK;
-        if (on && beam > 0) return SA_ERR_STATE;            // the KV fork copies the bf16 / fp16 / fp32 caches only
+        if (on && excluded(M_KV8)) return SA_ERR_STATE;
         if ((on != 0) != kv8) drop_graphs();
         if (!on) { kv8 = false; return SA_OK; }
         const int d = c.dec_head_dim;
         if (d != 128 && d != 64 && d != 32) return SA_ERR_UNSUPPORTED;
         if (c.dec_heads / c.dec_kv_heads > 8) return SA_ERR_UNSUPPORTED;
-        if (!kv8_arena) {
+        if (!kv8_arena.dev) {
             const size_t rows = (size_t)c.dec_layers * c.max_slots * c.dec_kv_heads, T8 = tmax8();
-            size_t off = 0;
-            auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes); return o; };
-            const size_t o_k = take(rows * c.max_kv_len * d), o_v = take(rows * d * T8), o_ks = take(rows * T8 * 4), o_vs = take(rows * T8 * 4);
-            SA_HIP(hipMalloc((void**)&kv8_arena, off));
-            SA_HIP(hipMemset(kv8_arena, 0, off));           // finite bytes and scales everywhere: masked key columns multiply P = 0
+            Carve cv;
+            const size_t o_k = cv.take(rows * c.max_kv_len * d), o_v = cv.take(rows * d * T8), o_ks = cv.take(rows * T8 * 4), o_vs = cv.take(rows * T8 * 4);
+            const int rc = kv8_arena.alloc(cv.off, 0);      // zeroed: finite bytes and scales everywhere, masked key columns multiply P = 0
+            if (rc) return rc;
+            char* b = kv8_arena.dev;
+            k8c = (uint8_t*)(b + o_k); v8tc = (uint8_t*)(b + o_v);
+            ksc8 = (float*)(b + o_ks); vsc8 = (float*)(b + o_vs);
             SA_HIP(hipDeviceSynchronize());
-            k8c = (uint8_t*)(kv8_arena + o_k); v8tc = (uint8_t*)(kv8_arena + o_v);
-            ksc8 = (float*)(kv8_arena + o_ks); vsc8 = (float*)(kv8_arena + o_vs);
         }
         kv8 = true;
         return SA_OK;
@@ -646,7 +731,7 @@ struct RecModel : RecBase {
     // ids named rows of the old table). Switching between the masked and the unmasked kernels drops captured steps, as set_kv_fp8 does.
     int set_token_masks(const uint32_t* masks, int n, hipStream_t s) override {
         if (n < 0 || n > SA_MAX_TOKEN_MASKS || (n > 0 && !masks)) return SA_ERR_ARG;
-        if (n > 0 && forcing) return SA_ERR_STATE;          // forced decoding runs the unmasked partial
+        if (n > 0 && excluded(M_MASKS)) return SA_ERR_STATE;
         const int words = mask_words();
         for (int i = 0; i < n; ++i) {
             bool any = false;
@@ -663,15 +748,16 @@ struct RecModel : RecBase {
         }
         const size_t table_bytes = (size_t)SA_MAX_TOKEN_MASKS * words * sizeof(uint32_t);
         if (!mask_arena) {                                  // first table: memory and staging, or nothing (a failure leaves the handle as it was)
-            const size_t slot_bytes = align_up((size_t)c.max_slots * sizeof(int));
+            Carve cv;
+            const size_t o_slot = cv.take((size_t)c.max_slots * sizeof(int)), o_table = cv.take(table_bytes);
             char* mem = nullptr;
-            SA_HIP(hipMalloc((void**)&mem, slot_bytes + table_bytes));
+            SA_HIP(hipMalloc((void**)&mem, cv.off));
             int rc = st_mask.init(table_bytes + (size_t)c.max_slots * 2 * sizeof(int) + 4096);
-            if (!rc) rc = (int)hipMemsetAsync(mem, 0xff, slot_bytes + table_bytes, s);      // every slot -1, every column allowed
+            if (!rc) rc = (int)hipMemsetAsync(mem, 0xff, cv.off, s);      // every slot -1, every column allowed
             if (rc) { st_mask.destroy(); st_mask = Stager(); (void)hipFree(mem); return rc; }
             mask_arena = mem;
-            slot_mask = reinterpret_cast<int*>(mask_arena);
-            mask_table = reinterpret_cast<uint32_t*>(mask_arena + slot_bytes);
+            slot_mask = reinterpret_cast<int*>(mask_arena + o_slot);
+            mask_table = reinterpret_cast<uint32_t*>(mask_arena + o_table);
         }
         st_mask.begin();
         const uint32_t* d = st_mask.put(masks, (size_t)n * words);
@@ -709,7 +795,7 @@ struct RecModel : RecBase {
     // steps, which hold the other lm_head kernel and the head's null / non-null (max, total) pointer.
     int set_alternatives(int on) override {
         if (on != 0 && on != 1) return SA_ERR_ARG;
-        if (on && forcing) return SA_ERR_STATE;
+        if (on && excluded(M_ALTS)) return SA_ERR_STATE;
         if (on) {
             const int rc = ensure_alt_arena();
             if (rc) return rc;
@@ -719,23 +805,21 @@ struct RecModel : RecBase {
         return SA_OK;
     }
     int ensure_alt_arena() {
-        if (!alt_arena) {
-            const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S * SA_MAX_ALTERNATIVES;
-            const size_t part_bytes = align_up(S * (size_t)cdiv(c.vocab, 64) * SA_MAX_ALTERNATIVES * sizeof(float2));
-            const size_t bt_bytes = align_up(S * sizeof(float2)), out_b = align_up(outs * sizeof(int));
-            char* mem = nullptr;
-            char* host = nullptr;
-            SA_HIP(hipMalloc((void**)&mem, part_bytes + bt_bytes + 2 * out_b));
-            int rc = (int)hipHostMalloc((void**)&host, outs * 8, hipHostMallocDefault);
-            if (!rc) rc = (int)hipMemset(mem, 0, part_bytes + bt_bytes + 2 * out_b);
-            if (rc) { if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
-            alt_arena = mem;
-            alt_host = host;
-            alt_part = reinterpret_cast<float2*>(mem);
-            best_tot = reinterpret_cast<float2*>(mem + part_bytes);
-            alt_token = reinterpret_cast<int*>(mem + part_bytes + bt_bytes);
-            alt_prob = reinterpret_cast<float*>(mem + part_bytes + bt_bytes + out_b);
-        }
+        if (alt_arena.dev) return SA_OK;
+        const size_t S = c.max_slots, cell = SA_MAX_ALTERNATIVES * 4, out_b = (size_t)SA_MAX_STEPS * S * cell;
+        Carve cv;
+        const size_t o_part = cv.take(S * (size_t)cdiv(c.vocab, 64) * SA_MAX_ALTERNATIVES * sizeof(float2)), o_bt = cv.take(S * sizeof(float2)),
+                     o_tok = cv.take(out_b), o_prob = cv.take(out_b);
+        const int rc = alt_arena.alloc(cv.off, 2 * out_b);
+        if (rc) return rc;
+        char* mem = alt_arena.dev;
+        alt_part = reinterpret_cast<float2*>(mem + o_part);
+        best_tot = reinterpret_cast<float2*>(mem + o_bt);
+        alt_token = reinterpret_cast<int*>(mem + o_tok);
+        alt_prob = reinterpret_cast<float*>(mem + o_prob);
+        StepOutputs& o = outs[STEPS_ALTS];
+        o.add(alt_token, cell); o.add(alt_prob, cell);
+        o.host = alt_arena.host;
         return SA_OK;
     }
 
@@ -743,27 +827,29 @@ struct RecModel : RecBase {
     // switching drops captured steps, which hold the other lm_head kernel, the fused or unfused head and no selection / fork launches.
     int set_beam(int width, int nop_id) override {
         if (width != 0 && (width < 2 || width > SA_MAX_BEAMS || width > c.max_slots)) return SA_ERR_ARG;
-        if (width && (forcing || kv8 || mx())) return SA_ERR_STATE;
+        if (width && excluded(M_BEAM)) return SA_ERR_STATE;
         if (width) {
             int rc = ensure_alt_arena();
             if (rc) return rc;
-            if (!beam_arena) {
-                const size_t S = c.max_slots, slot_b = align_up(S * 4), out_b = align_up((size_t)SA_MAX_STEPS * S * 4);
-                char* mem = nullptr;
-                char* host = nullptr;
-                SA_HIP(hipMalloc((void**)&mem, 6 * slot_b + 5 * out_b));
-                rc = (int)hipHostMalloc((void**)&host, (size_t)SA_MAX_STEPS * S * 20, hipHostMallocDefault);
-                if (!rc) rc = (int)hipMemset(mem, 0, 6 * slot_b + 5 * out_b);
-                if (!rc) rc = (int)hipMemset(mem + 3 * slot_b, 0xff, slot_b);       // fork_src -1: nothing to copy
-                if (rc) { if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
-                beam_arena = mem;
-                beam_host = host;
-                beam_score = reinterpret_cast<float*>(mem); beam_fin = reinterpret_cast<int*>(mem + slot_b);
-                beam_prompt = reinterpret_cast<int*>(mem + 2 * slot_b); fork_src = reinterpret_cast<int*>(mem + 3 * slot_b);
-                fork_base = reinterpret_cast<int*>(mem + 4 * slot_b); fork_len = reinterpret_cast<int*>(mem + 5 * slot_b);
-                char* o = mem + 6 * slot_b;
-                beam_token = reinterpret_cast<int*>(o); beam_parent = reinterpret_cast<int*>(o + out_b); beam_rank = reinterpret_cast<int*>(o + 2 * out_b);
-                beam_prob = reinterpret_cast<float*>(o + 3 * out_b); beam_logp = reinterpret_cast<float*>(o + 4 * out_b);
+            if (!beam_arena.dev) {
+                const size_t S = c.max_slots, out_b = (size_t)SA_MAX_STEPS * S * 4;
+                Carve cv;
+                size_t o_slot[6], o_out[5];
+                for (size_t& v : o_slot) v = cv.take(S * 4);
+                for (size_t& v : o_out) v = cv.take(out_b);
+                DevBlock b;
+                if ((rc = b.alloc(cv.off, 5 * out_b))) return rc;
+                if ((rc = (int)hipMemset(b.dev + o_slot[3], 0xff, S * 4))) { b.release(); return rc; }      // fork_src -1: nothing to copy
+                beam_arena = b;
+                auto ints = [&](size_t o) { return reinterpret_cast<int*>(b.dev + o); };
+                auto floats = [&](size_t o) { return reinterpret_cast<float*>(b.dev + o); };
+                beam_score = floats(o_slot[0]); beam_fin = ints(o_slot[1]); beam_prompt = ints(o_slot[2]);
+                fork_src = ints(o_slot[3]); fork_base = ints(o_slot[4]); fork_len = ints(o_slot[5]);
+                beam_token = ints(o_out[0]); beam_parent = ints(o_out[1]); beam_rank = ints(o_out[2]);
+                beam_prob = floats(o_out[3]); beam_logp = floats(o_out[4]);
+                StepOutputs& o = outs[STEPS_BEAM];
+                for (size_t v : o_out) o.add(b.dev + v, 4);       // token, parent, rank, probability, log-probability
+                o.host = b.host;
             }
         }
         if (width != beam) drop_graphs();
@@ -801,28 +887,29 @@ struct RecModel : RecBase {
     // steps, which hold the other lm_head kernel and the head's empty / filled ForcedHead. Switch-off sets the table back to -1.
     int set_forced(int on) override {
         if (on != 0 && on != 1) return SA_ERR_ARG;
-        if (on && (n_token_masks > 0 || alts || beam > 0)) return SA_ERR_STATE;
-        const size_t S = c.max_slots, outs = (size_t)SA_MAX_STEPS * S;
-        const size_t table_bytes = align_up(S * SA_MAX_FORCED_TOKENS * sizeof(int)), slot_bytes = align_up(S * sizeof(int)), out_b = align_up(outs * 4);
-        if (on && !forced_arena) {
-            char* mem = nullptr;
-            char* host = nullptr;
-            SA_HIP(hipMalloc((void**)&mem, table_bytes + 2 * slot_bytes + 3 * out_b));
-            int rc = (int)hipHostMalloc((void**)&host, outs * 12, hipHostMallocDefault);
+        if (on && excluded(M_FORCED)) return SA_ERR_STATE;
+        const size_t S = c.max_slots, table_bytes = S * SA_MAX_FORCED_TOKENS * sizeof(int), out_b = (size_t)SA_MAX_STEPS * S * 4;
+        if (on && !forced_arena.dev) {
+            Carve cv;
+            const size_t o_table = cv.take(table_bytes), o_cursor = cv.take(S * sizeof(int)), o_flogit = cv.take(S * sizeof(float)),
+                         o_gtok = cv.take(out_b), o_gprob = cv.take(out_b), o_logp = cv.take(out_b);
+            DevBlock b;
             Stager st;
-            if (!rc) rc = st.init(S * SA_MAX_FORCED_TOKENS * sizeof(int) + (2 * S + 1) * sizeof(int) + 4096);
-            if (!rc) rc = (int)hipMemset(mem, 0, table_bytes + 2 * slot_bytes + 3 * out_b);
-            if (!rc) rc = (int)hipMemset(mem, 0xff, table_bytes);           // every slot free-running
-            if (rc) { st.destroy(); if (host) (void)hipHostFree(host); (void)hipFree(mem); return rc; }
+            int rc = b.alloc(cv.off, 3 * out_b);
+            if (!rc) rc = st.init(table_bytes + (2 * S + 1) * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipMemset(b.dev + o_table, 0xff, table_bytes);           // every slot free-running
+            if (rc) { st.destroy(); b.release(); return rc; }
             st_forced = st;
-            forced_arena = mem;
-            forced_host = host;
-            forced_table = reinterpret_cast<int*>(mem);
-            forced_cursor = reinterpret_cast<int*>(mem + table_bytes);
-            flogit = reinterpret_cast<float*>(mem + table_bytes + slot_bytes);
-            greedy_token = reinterpret_cast<int*>(mem + table_bytes + 2 * slot_bytes);
-            greedy_prob = reinterpret_cast<float*>(mem + table_bytes + 2 * slot_bytes + out_b);
-            forced_logprob = reinterpret_cast<float*>(mem + table_bytes + 2 * slot_bytes + 2 * out_b);
+            forced_arena = b;
+            forced_table = reinterpret_cast<int*>(b.dev + o_table);
+            forced_cursor = reinterpret_cast<int*>(b.dev + o_cursor);
+            flogit = reinterpret_cast<float*>(b.dev + o_flogit);
+            greedy_token = reinterpret_cast<int*>(b.dev + o_gtok);
+            greedy_prob = reinterpret_cast<float*>(b.dev + o_gprob);
+            forced_logprob = reinterpret_cast<float*>(b.dev + o_logp);
+            StepOutputs& o = outs[STEPS_FORCED];
+            o.add(greedy_token, 4); o.add(greedy_prob, 4); o.add(forced_logprob, 4);
+            o.host = b.host;
         }
         if (!on && forcing) {
             SA_HIP(hipDeviceSynchronize());                                 // (a switch, not a step: no line is in flight)
@@ -863,21 +950,20 @@ struct RecModel : RecBase {
     int set_mx_weights(const void* const* tbl, int n) override {
         if constexpr (!std::is_same<T, bf16_t>::value) return SA_ERR_UNSUPPORTED;
         if (!tbl) { if (!mxw.empty()) drop_graphs(); mxw.clear(); return SA_OK; }     // back to the bf16 decode weights
-        if (beam > 0) return SA_ERR_STATE;
+        if (excluded(M_MX)) return SA_ERR_STATE;
         if (n != SA_MX_TOTAL(c.dec_layers)) return SA_ERR_ARG;
         for (int i = 0; i < n; ++i)
             if (!tbl[i]) return SA_ERR_ARG;
         const int Hd = c.dec_hidden, A = c.dec_heads * c.dec_head_dim, I = c.dec_inter;
         if (Hd % 128 || A % 128 || I % 128 || c.dec_head_dim % 32) return SA_ERR_SHAPE;     // whole 128-element K-tiles, 32-wide blocks
-        if (!mx_arena) {
+        if (!mx_arena.dev) {
             const size_t S = c.max_slots;
-            size_t off = 0;
-            auto take = [&](size_t b) { size_t o = off; off = align_up(off + b); return o; };
-            const size_t o1 = take(S * Hd), o2 = take(S * Hd / 32), o3 = take(S * A), o4 = take(S * A / 32), o5 = take(S * I),
-                         o6 = take(S * I / 32), o7 = take(S * Hd), o8 = take(S * Hd / 32);
-            SA_HIP(hipMalloc((void**)&mx_arena, off));
-            SA_HIP(hipMemset(mx_arena, 0, off));
-            uint8_t* b = reinterpret_cast<uint8_t*>(mx_arena);
+            Carve cv;
+            const size_t o1 = cv.take(S * Hd), o2 = cv.take(S * Hd / 32), o3 = cv.take(S * A), o4 = cv.take(S * A / 32), o5 = cv.take(S * I),
+                         o6 = cv.take(S * I / 32), o7 = cv.take(S * Hd), o8 = cv.take(S * Hd / 32);
+            const int rc = mx_arena.alloc(cv.off, 0);
+            if (rc) return rc;
+            uint8_t* b = reinterpret_cast<uint8_t*>(mx_arena.dev);
             dh8 = b + o1; sdh = b + o2; dattn8 = b + o3; sattn = b + o4; dmlp8 = b + o5; smlp = b + o6; dlast8 = b + o7; slast = b + o8;
         }
         mxw.resize(n);
@@ -976,40 +1062,32 @@ struct RecModel : RecBase {
         float4* am = amax;
         if (!normed && (rc = rmsnorm(dx, Hd, W(SA_RW_DEC_NORM), last, Hd, d_last_row, rows, Hd, c.dec_eps, s))) return rc;
         // lm_head with the greedy reduction in its epilogue: logits stay in LDS, the head combines per-tile partials.
+        // Which greedy epilogue the mode asks for -- forced | candidates (masked or not) | masked | plain -- and what it reads, once for
+        // both weight formats: `launch(a, tag)` runs `a` with epilogue EPIS[tag] of its format.
         int bn_used = 0;
-        if (mx() && normed) {       // decode steps: MXFP8 lm_head on the MXFP8 copy of the final-norm rows
-            if constexpr (std::is_same<T, bf16_t>::value) {
-                MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
-                a.amax = am;
-                a.bias = W(SA_RW_LM_B);
-                if (forcing) {
-                    a.forced = forced_cols(d_row_slot);
-                    if ((rc = launch_gemm_mx<MX_EPI_FORCED>(a, s))) return rc;
-                } else if (topk()) {
-                    if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
-                    a.alt = alt_part;
-                    if ((rc = launch_gemm_mx<MX_EPI_TOPK>(a, s))) return rc;
-                } else if (n_token_masks > 0) {
-                    a.tmask = token_mask(d_row_slot);
-                    if ((rc = launch_gemm_mx<MX_EPI_ARGMAX_MASK>(a, s))) return rc;
-                } else if ((rc = launch_gemm_mx<MX_EPI_ARGMAX>(a, s))) return rc;
-                bn_used = a.bn_used;
-            }
-        } else {
-            GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
+        auto lm_head = [&](auto& a, auto&& launch) -> int {
             a.amax = am;
             if (forcing) {
                 a.forced = forced_cols(d_row_slot);
-                if ((rc = launch_gemm<T, float, EPI_FORCED>(a, s))) return rc;
-            } else if (topk()) {
+            } else {
                 if (n_token_masks > 0) a.tmask = token_mask(d_row_slot);
-                a.alt = alt_part;
-                if ((rc = launch_gemm<T, float, EPI_TOPK>(a, s))) return rc;
-            } else if (n_token_masks > 0) {
-                a.tmask = token_mask(d_row_slot);
-                if ((rc = launch_gemm<T, float, EPI_ARGMAX_MASK>(a, s))) return rc;
-            } else if ((rc = launch_gemm<T, float, EPI_ARGMAX>(a, s))) return rc;
+                if (topk()) a.alt = alt_part;
+            }
+            const int rc_ =forcing ? launch(a, HeadEpi<0>{}) : topk() ? launch(a, HeadEpi<1>{}) : n_token_masks > 0 ? launch(a, HeadEpi<2>{}) : launch(a, HeadEpi<3>{});
             bn_used = a.bn_used;
+            return rc_;
+        };
+        if (mx() && normed) {       // decode steps: MXFP8 lm_head on the MXFP8 copy of the final-norm rows
+            if constexpr (std::is_same<T, bf16_t>::value) {
+                static constexpr int EPIS[4] = {MX_EPI_FORCED, MX_EPI_TOPK, MX_EPI_ARGMAX_MASK, MX_EPI_ARGMAX};
+                MxArgs a{dlast8, Hd, slast, MXG(SA_MX_LM_W), Hd, MXG(SA_MX_LM_S), rows, c.vocab, Hd, (long)c.max_slots, (long)c.vocab};
+                a.bias = W(SA_RW_LM_B);
+                if ((rc = lm_head(a, [&](MxArgs& a_, auto e) { return launch_gemm_mx<EPIS[decltype(e)::value]>(a_, s); }))) return rc;
+            }
+        } else {
+            static constexpr int EPIS[4] = {EPI_FORCED, EPI_TOPK, EPI_ARGMAX_MASK, EPI_ARGMAX};
+            GemmArgs<T, float> a{last, Hd, W(SA_RW_LM_W), Hd, logits, c.vocab, W(SA_RW_LM_B), nullptr, 0, rows, c.vocab, Hd};
+            if ((rc = lm_head(a, [&](GemmArgs<T, float>& a_, auto e) { return launch_gemm<T, float, EPIS[decltype(e)::value]>(a_, s); }))) return rc;
         }
         const int tiles_n = cdiv(c.vocab, bn_used);
         const size_t so = (size_t)step * c.max_slots;
@@ -1168,116 +1246,29 @@ struct RecModel : RecBase {
     // calls (r01 trace: ~0.7 ms idle per round trip, 8 % of the recognition step).
     int decode_async(int n_steps, int ring, hipStream_t s) override {
         if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        int rc = decode_steps(n_steps, ring * (SA_MAX_STEPS / 2), s);
+        int rc = decode_steps(n_steps, StepOutputs::ring_step(ring), s);
         if (rc) return rc;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
-        const size_t nt = (size_t)n_steps * S;
-        if (nt) {
-            SA_HIP(hipMemcpyAsync(out_host + off * 4, out_token + off, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(out_host + full * 4 + off * 4, out_score + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(out_host + full * 8 + off * 24, out_bbox + off * 6, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-        }
-        ring_alts[ring] = topk();
-        if (nt && topk()) {
-            const size_t A = SA_MAX_ALTERNATIVES;
-            SA_HIP(hipMemcpyAsync(alt_host + off * A * 4, alt_token + off * A, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(alt_host + (full + off) * A * 4, alt_prob + off * A, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
-        }
-        ring_beam[ring] = beam > 0;
-        if (nt && beam > 0) {
-            const int* src[5] = {beam_token, beam_parent, beam_rank, (const int*)beam_prob, (const int*)beam_logp};
-            for (int k = 0; k < 5; ++k)
-                SA_HIP(hipMemcpyAsync(beam_host + ((size_t)k * full + off) * 4, src[k] + off, nt * 4, hipMemcpyDeviceToHost, s));
-        }
-        ring_forced[ring] = forcing;
-        if (nt && forcing) {
-            SA_HIP(hipMemcpyAsync(forced_host + off * 4, greedy_token + off, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(forced_host + (full + off) * 4, greedy_prob + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-            SA_HIP(hipMemcpyAsync(forced_host + (2 * full + off) * 4, forced_logprob + off, nt * sizeof(float), hipMemcpyDeviceToHost, s));
+        for (int k = 0; k < STEPS_SETS; ++k) {
+            outs[k].mirrored[ring] = false;                 // a set that is off mirrors nothing: wait_steps refuses this ring half
+            if (steps_on((StepSet)k) && (rc = outs[k].mirror(ring, n_steps, s))) return rc;
         }
         SA_HIP(hipEventRecord(ev_ring[ring], s));
         return SA_OK;
     }
 
-    // Forced-decoding outputs of the steps wait_outputs / read_outputs return: [step][slot], same indexing
-    int wait_forced(int n_steps, int ring, int32_t* gtok, float* gprob, float* logp) override {
+    // The fields of one set for the steps read_outputs / wait_outputs return, same [step][slot] indexing. A set that is off is refused,
+    // and so is a ring half whose decode_async was enqueued while the set was off.
+    int wait_steps(StepSet set, int n_steps, int ring, std::initializer_list<void*> dst) override {
         if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        if (!forcing || !ring_forced[ring]) return SA_ERR_STATE;  // (a call enqueued while the feature was off mirrored nothing)
+        if (!steps_on(set) || !outs[set].mirrored[ring]) return SA_ERR_STATE;
         SA_HIP(hipEventSynchronize(ev_ring[ring]));
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S, nt = (size_t)n_steps * S;
-        memcpy(gtok, forced_host + off * 4, nt * sizeof(int));
-        memcpy(gprob, forced_host + (full + off) * 4, nt * sizeof(float));
-        memcpy(logp, forced_host + (2 * full + off) * 4, nt * sizeof(float));
+        outs[set].wait(ring, n_steps, dst.begin());
         return SA_OK;
     }
-    int read_forced(int n_steps, int32_t* gtok, float* gprob, float* logp, hipStream_t s) override {
+    int read_steps(StepSet set, int n_steps, std::initializer_list<void*> dst, hipStream_t s) override {
         if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        if (!forcing) return SA_ERR_STATE;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
-        SA_HIP(hipMemcpyAsync(forced_host, greedy_token, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(forced_host + full * 4, greedy_prob, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(forced_host + 2 * full * 4, forced_logprob, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipStreamSynchronize(s));
-        memcpy(gtok, forced_host, nt * sizeof(int));
-        memcpy(gprob, forced_host + full * 4, nt * sizeof(float));
-        memcpy(logp, forced_host + 2 * full * 4, nt * sizeof(float));
-        return SA_OK;
-    }
-
-    // Alternatives of the steps wait_outputs / read_outputs return: [step][slot][SA_MAX_ALTERNATIVES], same indexing
-    int wait_alternatives(int n_steps, int ring, int32_t* tokens, float* probs) override {
-        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        if (!topk() || !ring_alts[ring]) return SA_ERR_STATE;       // (a call enqueued while the feature was off mirrored nothing)
-        SA_HIP(hipEventSynchronize(ev_ring[ring]));
-        const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
-        const size_t nt = (size_t)n_steps * S;
-        memcpy(tokens, alt_host + off * A * 4, nt * A * sizeof(int));
-        memcpy(probs, alt_host + (full + off) * A * 4, nt * A * sizeof(float));
-        return SA_OK;
-    }
-    int read_alternatives(int n_steps, int32_t* tokens, float* probs, hipStream_t s) override {
-        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        if (!topk()) return SA_ERR_STATE;
-        const size_t S = c.max_slots, A = SA_MAX_ALTERNATIVES, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
-        SA_HIP(hipMemcpyAsync(alt_host, alt_token, nt * A * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(alt_host + full * A * 4, alt_prob, nt * A * sizeof(float), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipStreamSynchronize(s));
-        memcpy(tokens, alt_host, nt * A * sizeof(int));
-        memcpy(probs, alt_host + full * A * 4, nt * A * sizeof(float));
-        return SA_OK;
-    }
-
-    // Beam outputs of the steps wait_outputs / read_outputs return: five [step][slot] arrays, same indexing
-    int wait_beam(int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps) override {
-        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        if (beam == 0 || !ring_beam[ring]) return SA_ERR_STATE;   // (a call enqueued while the feature was off mirrored nothing)
-        SA_HIP(hipEventSynchronize(ev_ring[ring]));
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S, nt = (size_t)n_steps * S;
-        void* dst[5] = {tokens, parents, ranks, probs, logps};
-        for (int k = 0; k < 5; ++k) memcpy(dst[k], beam_host + ((size_t)k * full + off) * 4, nt * 4);
-        return SA_OK;
-    }
-    int read_beam(int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, hipStream_t s) override {
-        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        if (beam == 0) return SA_ERR_STATE;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, nt = (size_t)n_steps * S;
-        const int* src[5] = {beam_token, beam_parent, beam_rank, (const int*)beam_prob, (const int*)beam_logp};
-        for (int k = 0; k < 5; ++k) SA_HIP(hipMemcpyAsync(beam_host + (size_t)k * full * 4, src[k], nt * 4, hipMemcpyDeviceToHost, s));
-        SA_HIP(hipStreamSynchronize(s));
-        void* dst[5] = {tokens, parents, ranks, probs, logps};
-        for (int k = 0; k < 5; ++k) memcpy(dst[k], beam_host + (size_t)k * full * 4, nt * 4);
-        return SA_OK;
-    }
-
-    int wait_outputs(int n_steps, int ring, int32_t* tokens, float* scores, int32_t* bboxes) override {
-        if (n_steps < 0 || n_steps > SA_MAX_STEPS / 2 || ring < 0 || ring > 1) return SA_ERR_ARG;
-        SA_HIP(hipEventSynchronize(ev_ring[ring]));
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S, off = (size_t)ring * (SA_MAX_STEPS / 2) * S;
-        const size_t nt = (size_t)n_steps * S;
-        memcpy(tokens, out_host + off * 4, nt * sizeof(int));
-        memcpy(scores, out_host + full * 4 + off * 4, nt * sizeof(float));
-        memcpy(bboxes, out_host + full * 8 + off * 24, nt * 6 * sizeof(int));
-        return SA_OK;
+        if (!steps_on(set)) return SA_ERR_STATE;
+        return outs[set].read(n_steps, dst.begin(), s);
     }
 
     int decode_steps(int n_steps, int step0, hipStream_t s) {
@@ -1312,20 +1303,6 @@ struct RecModel : RecBase {
         SA_HIP(hipGraphLaunch(it->second, gstream));
         SA_HIP(hipEventRecord(gev_out, gstream));
         SA_HIP(hipStreamWaitEvent(s, gev_out, 0));
-        return SA_OK;
-    }
-
-    int read_outputs(int n_steps, int32_t* tokens, float* scores, int32_t* bboxes, hipStream_t s) override {
-        if (n_steps <= 0 || n_steps > SA_MAX_STEPS) return SA_ERR_ARG;
-        const size_t S = c.max_slots, full = (size_t)SA_MAX_STEPS * S;
-        const size_t nt = (size_t)n_steps * S;
-        SA_HIP(hipMemcpyAsync(out_host, out_token, nt * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(out_host + full * 4, out_score, nt * sizeof(float), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipMemcpyAsync(out_host + full * 8, out_bbox, nt * 6 * sizeof(int), hipMemcpyDeviceToHost, s));
-        SA_HIP(hipStreamSynchronize(s));
-        memcpy(tokens, out_host, nt * sizeof(int));
-        memcpy(scores, out_host + full * 4, nt * sizeof(float));
-        memcpy(bboxes, out_host + full * 8, nt * 6 * sizeof(int));
         return SA_OK;
     }
 

@@ -198,7 +198,7 @@ int surya_rec_decode(surya_rec* h, int n_steps, void* stream) {
 }
 int surya_rec_read_outputs(surya_rec* h, int n_steps, int32_t* tokens, float* scores, int32_t* bboxes, void* stream) {
     if (!h || !tokens || !scores || !bboxes) return SA_ERR_ARG;
-    return h->impl->read_outputs(n_steps, tokens, scores, bboxes, (hipStream_t)stream);
+    return h->impl->read_steps(STEPS_BASE, n_steps, {tokens, scores, bboxes}, (hipStream_t)stream);
 }
 int surya_rec_decode_async(surya_rec* h, int n_steps, int ring, void* stream) {
     if (!h) return SA_ERR_ARG;
@@ -206,7 +206,7 @@ int surya_rec_decode_async(surya_rec* h, int n_steps, int ring, void* stream) {
 }
 int surya_rec_wait_outputs(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* scores, int32_t* bboxes) {
     if (!h || !tokens || !scores || !bboxes) return SA_ERR_ARG;
-    return h->impl->wait_outputs(n_steps, ring, tokens, scores, bboxes);
+    return h->impl->wait_steps(STEPS_BASE, n_steps, ring, {tokens, scores, bboxes});
 }
 int surya_rec_encode_only(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, void* out, void* stream) {
     if (!h || !tiles || !grid_hw || !out || n_images <= 0) return SA_ERR_ARG;
@@ -246,11 +246,11 @@ int surya_rec_set_alternatives(surya_rec* h, int on) {
 }
 int surya_rec_read_alternatives(surya_rec* h, int n_steps, int32_t* tokens, float* probs, void* stream) {
     if (!h || !tokens || !probs) return SA_ERR_ARG;
-    return h->impl->read_alternatives(n_steps, tokens, probs, (hipStream_t)stream);
+    return h->impl->read_steps(STEPS_ALTS, n_steps, {tokens, probs}, (hipStream_t)stream);
 }
 int surya_rec_wait_alternatives(surya_rec* h, int n_steps, int ring, int32_t* tokens, float* probs) {
     if (!h || !tokens || !probs) return SA_ERR_ARG;
-    return h->impl->wait_alternatives(n_steps, ring, tokens, probs);
+    return h->impl->wait_steps(STEPS_ALTS, n_steps, ring, {tokens, probs});
 }
 
 int surya_rec_set_forced(surya_rec* h, int on) {
@@ -263,11 +263,11 @@ int surya_rec_set_forced_tokens(surya_rec* h, const int32_t* slots, const int32_
 }
 int surya_rec_read_forced(surya_rec* h, int n_steps, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs, void* stream) {
     if (!h || !greedy_tokens || !greedy_probs || !forced_logprobs) return SA_ERR_ARG;
-    return h->impl->read_forced(n_steps, greedy_tokens, greedy_probs, forced_logprobs, (hipStream_t)stream);
+    return h->impl->read_steps(STEPS_FORCED, n_steps, {greedy_tokens, greedy_probs, forced_logprobs}, (hipStream_t)stream);
 }
 int surya_rec_wait_forced(surya_rec* h, int n_steps, int ring, int32_t* greedy_tokens, float* greedy_probs, float* forced_logprobs) {
     if (!h || !greedy_tokens || !greedy_probs || !forced_logprobs) return SA_ERR_ARG;
-    return h->impl->wait_forced(n_steps, ring, greedy_tokens, greedy_probs, forced_logprobs);
+    return h->impl->wait_steps(STEPS_FORCED, n_steps, ring, {greedy_tokens, greedy_probs, forced_logprobs});
 }
 
 int surya_rec_set_beam(surya_rec* h, int width, int no_output_token_id) {
@@ -276,11 +276,11 @@ int surya_rec_set_beam(surya_rec* h, int width, int no_output_token_id) {
 }
 int surya_rec_read_beam(surya_rec* h, int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, void* stream) {
     if (!h || !tokens || !parents || !ranks || !probs || !logps) return SA_ERR_ARG;
-    return h->impl->read_beam(n_steps, tokens, parents, ranks, probs, logps, (hipStream_t)stream);
+    return h->impl->read_steps(STEPS_BEAM, n_steps, {tokens, parents, ranks, probs, logps}, (hipStream_t)stream);
 }
 int surya_rec_wait_beam(surya_rec* h, int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps) {
     if (!h || !tokens || !parents || !ranks || !probs || !logps) return SA_ERR_ARG;
-    return h->impl->wait_beam(n_steps, ring, tokens, parents, ranks, probs, logps);
+    return h->impl->wait_steps(STEPS_BEAM, n_steps, ring, {tokens, parents, ranks, probs, logps});
 }
 
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)

@@ -3,6 +3,7 @@ One DeviceLoop per RecognitionPredictor.generate call owns ALL loop state -- que
 chunks, look-ahead queue, the decode call in flight -- so a loop that died leaves nothing behind but what the model handle keeps
 (unconsumed look-ahead images: `run` discards them first). It knows the model surface, not the predictor."""
 from collections import deque, namedtuple
+from contextlib import ExitStack
 
 import numpy as np
 
@@ -349,6 +350,17 @@ class DeviceLoop:
         self.model.encode_ahead(self.tiles_of(cand[0], cand[-1]), [grids[i] for i in cand])
         self.ahead.extend(cand)
 
+    def _prefill(self, take, grids, prompt_ids, slots):
+        """The model's prefill of lines `take` into `slots`: from the look-ahead queue, whose head they are, or with their own tiles."""
+        if self.look_ahead:
+            for i in take:
+                assert self.ahead.popleft() == i
+            self.model.prefill(None, grids, prompt_ids, slots)
+            if not self.ahead and self.queue:
+                self.encode_ahead()                    # the next lines' encoder pass runs beside the decode steps that follow
+        else:
+            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, slots)      # queue order == id order
+
     def prefill_batch(self):
         """Fill the empty slots (ascending) from the head of the queue; a line whose first token already stops never takes its slot."""
         queue, ahead, look_ahead, line_chunk = self.queue, self.ahead, self.look_ahead, self.line_chunk
@@ -370,14 +382,7 @@ class DeviceLoop:
             self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
         if self.forced:
             self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
-        if look_ahead:
-            for i in take:
-                assert ahead.popleft() == i
-            self.model.prefill(None, grids, prompt_ids, slots)
-            if not ahead and queue:
-                self.encode_ahead()                    # the next lines' encoder pass runs beside the decode steps below
-        else:
-            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, slots)      # queue order == id order
+        self._prefill(take, grids, prompt_ids, slots)
         tok, sc, bb = self.model.read_outputs(1)
         ids_, sl_ = np.asarray(take, np.int64), np.asarray(slots, np.int64)
         first = tok[0, sl_]
@@ -400,20 +405,12 @@ class DeviceLoop:
     def _prefill_beam(self, take, groups, grids, prompt_ids):
         """prefill_batch in beam mode: a line is prefilled once, into the lead slot of its group; the model's first selection spreads the
         best first tokens over the group. A line's mask id goes to every slot of its group."""
-        queue, ahead, B = self.queue, self.ahead, self.beam
+        B = self.beam
         g = np.asarray(groups, np.int64)
         sl = g[:, None] * B + self.lane[None, :]
         if self.n_masks:
             self.model.set_slot_masks(sl.reshape(-1).tolist(), np.repeat(self.line_mask[take], B).tolist())
-        lead = (g * B).tolist()
-        if self.look_ahead:
-            for i in take:
-                assert ahead.popleft() == i
-            self.model.prefill(None, grids, prompt_ids, lead)
-            if not ahead and queue:
-                self.encode_ahead()
-        else:
-            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, lead)
+        self._prefill(take, grids, prompt_ids, (g * B).tolist())
         _, _, bb = self.model.read_outputs(1)
         bt, bpar, _, bprob, blogp = self.model.read_beam(1)
         p = np.asarray(take, np.int64)
@@ -427,36 +424,24 @@ class DeviceLoop:
 
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
-        if self.beam:
-            self.model.set_beam(self.beam, self.nop)
-            try:
-                return self._run_masked(prep)
-            finally:
-                self.model.set_beam(None)              # the next call starts on the greedy kernels
-        if self.forced:
-            self.model.set_forced(True)
-            try:
-                return self._run_masked(prep)
-            finally:
-                self.model.set_forced(False)           # the next call starts on the greedy kernels
-        if not self.alternatives:
-            return self._run_masked(prep)
-        self.model.set_alternatives(True)
-        try:
-            return self._run_masked(prep)
-        finally:
-            self.model.set_alternatives(False)         # the next call starts on the kernels without candidates
-
-    def _run_masked(self, prep):
+        m = self.model
         table = None if prep is None else prep.get("token_masks")
-        if table is None or len(table) == 0:
+
+        def masks_on():
+            m.set_token_masks(table)                   # once per call: identical masks were merged by the caller
+            self.n_masks = len(table)
+        # (requested, switch on, switch off): switched on in this order, off in reverse on the way out, also after an exception, so the
+        # next call starts on the greedy, unmasked kernels without candidates. What was not requested never touches its entry points.
+        modes = [(self.beam, lambda: m.set_beam(self.beam, self.nop), lambda: m.set_beam(None)),
+                 (self.forced, lambda: m.set_forced(True), lambda: m.set_forced(False)),      # (at most one of the first three: __init__)
+                 (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False)),
+                 (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None))]
+        with ExitStack() as undo:
+            for wanted, on, off in modes:
+                if wanted:
+                    on()
+                    undo.callback(off)
             return self._run(prep)
-        self.model.set_token_masks(table)              # once per call: identical masks were merged by the caller
-        self.n_masks = len(table)
-        try:
-            return self._run(prep)
-        finally:
-            self.model.set_token_masks(None)           # the next call starts on the unmasked kernels
 
     def _run(self, prep):
         if callable(getattr(self.model, "discard_ahead", None)):

@@ -16,6 +16,35 @@ from ..config import RecConfig
 from .weights import repack_rec_weights, pad64
 
 
+class _StepBufs:
+    """Host arrays of one step-output set (outputs / alternatives / forced / beam: csrc/rec_engine.h, StepOutputs) and its two calls,
+    surya_rec_read_<name> and surya_rec_wait_<name>. One array [SA_MAX_STEPS, slots, *tail] per field, made by `ensure` when the set is
+    first switched on; ring half r is rows r * SA_MAX_STEPS / 2 onwards, so a wait never overwrites what the other half returned."""
+
+    def __init__(self, name, fields, slots):
+        self.name, self.fields, self.slots, self.bufs = name, fields, slots, None       # fields: (dtype, tail shape) per argument
+
+    def ensure(self):
+        if self.bufs is None:
+            self.bufs = tuple(np.zeros((L.SA_MAX_STEPS, self.slots) + tail, dt) for dt, tail in self.fields)
+
+    def _call(self, model, what, first, n_steps, before, after):
+        """what(handle, n_steps, *before, one pointer per field, *after), into rows first.. of the arrays; -> the first n_steps of them."""
+        bufs = self.bufs
+        if bufs is None:                # never switched on: the library refuses below, with buffers it may not write to anyway
+            bufs = tuple(np.zeros((1, 1) + tail, dt) for dt, tail in self.fields)
+        views = tuple(b[first:] for b in bufs)
+        ptrs = [L.np_ptr(v, C.c_float if v.dtype == np.float32 else C.c_int32) for v in views]
+        L.check(getattr(model.lib, what)(model.handle, C.c_int(n_steps), *before, *ptrs, *after), what)
+        return tuple(v[:n_steps] for v in views)
+
+    def read(self, model, n_steps):
+        return self._call(model, "surya_rec_read_" + self.name, 0, n_steps, (), (model._stream,))
+
+    def wait(self, model, n_steps, ring):
+        return self._call(model, "surya_rec_wait_" + self.name, ring * (L.SA_MAX_STEPS // 2), n_steps, (C.c_int(ring),), ())
+
+
 class HipRecModel:
     def __init__(self, cfg: RecConfig, state_dict, *, image_token_id: int, pad_token_id: int, eos_token_id: int,
                  dtype: torch.dtype = torch.bfloat16, device="cuda:0", max_slots: int = 256, max_kv_len: int = 512,
@@ -62,17 +91,17 @@ class HipRecModel:
         table = (C.c_void_p * len(self.weights))(*[t.data_ptr() for t in self.weights])
         self.handle = C.c_void_p()
         L.check(self.lib.surya_rec_create(C.byref(c), table, len(self.weights), C.byref(self.handle)), "surya_rec_create")
-        self._tok = np.zeros((L.SA_MAX_STEPS, max_slots), np.int32)
-        self._score = np.zeros((L.SA_MAX_STEPS, max_slots), np.float32)
-        self._bbox = np.zeros((L.SA_MAX_STEPS, max_slots, 6), np.int32)
+        i32, f32, A = np.int32, np.float32, (L.SA_MAX_ALTERNATIVES,)
+        self._out = _StepBufs("outputs", [(i32, ()), (f32, ()), (i32, (6,))], max_slots)
+        self._out.ensure()
+        self._alt = _StepBufs("alternatives", [(i32, A), (f32, A)], max_slots)               # the other sets: made on first switch-on
+        self._forced = _StepBufs("forced", [(i32, ()), (f32, ()), (f32, ())], max_slots)
+        self._beam = _StepBufs("beam", [(i32, ()), (i32, ()), (i32, ()), (f32, ()), (f32, ())], max_slots)
         self.mx_weights = None
         self.n_token_masks = 0
         self.alternatives = False
-        self._alt_tok = self._alt_p = None              # host arrays of read_alternatives / wait_alternatives, made on first use
         self.forced = False
-        self._forced_bufs = None                        # host arrays of read_forced / wait_forced, made on first use
         self.beam = 0
-        self._beam_bufs = None                          # host arrays of read_beam / wait_beam, made on first use
         self.decode_fp8 = False
         if decode_fp8 is None:
             from ..settings import settings
@@ -141,29 +170,17 @@ class HipRecModel:
         Off (the default) the handle launches the kernels it always launched; tokens, scores and boxes are the same either way."""
         L.check(self.lib.surya_rec_set_alternatives(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_alternatives")
         self.alternatives = bool(on)
-        if on and self._alt_tok is None:
-            self._alt_tok = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.int32)
-            self._alt_p = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.float32)
-
-    def _alt_bufs(self, first):
-        if self._alt_tok is None:       # never switched on: the library refuses below, with buffers it may not write to anyway
-            return np.zeros((1, 1, L.SA_MAX_ALTERNATIVES), np.int32), np.zeros((1, 1, L.SA_MAX_ALTERNATIVES), np.float32)
-        return self._alt_tok[first:], self._alt_p[first:]
+        if on:
+            self._alt.ensure()
 
     def read_alternatives(self, n_steps: int = 1):
         """Sync; (tokens [n_steps, slots, 4] int32, -1 = fewer ids allowed; probs [n_steps, slots, 4]) of the steps read_outputs returns,
         best first: entry 0 is the emitted token."""
-        tok, pr = self._alt_bufs(0)
-        L.check(self.lib.surya_rec_read_alternatives(self.handle, C.c_int(n_steps), L.np_ptr(tok), L.np_ptr(pr, C.c_float), self._stream),
-                "surya_rec_read_alternatives")
-        return tok[:n_steps], pr[:n_steps]
+        return self._alt.read(self, n_steps)
 
     def wait_alternatives(self, n_steps: int, ring: int):
         """The alternatives of the decode_async call on `ring`, parallel to wait_outputs."""
-        tok, pr = self._alt_bufs(ring * (L.SA_MAX_STEPS // 2))
-        L.check(self.lib.surya_rec_wait_alternatives(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(tok), L.np_ptr(pr, C.c_float)),
-                "surya_rec_wait_alternatives")
-        return tok[:n_steps], pr[:n_steps]
+        return self._alt.wait(self, n_steps, ring)
 
     def set_forced(self, on: bool):
         """Forced decoding (surya_rec_set_forced): slots with forced ids (set_forced_tokens) emit them instead of the greedy token and
@@ -171,9 +188,8 @@ class HipRecModel:
         masks or alternatives."""
         L.check(self.lib.surya_rec_set_forced(self.handle, C.c_int(1 if on else 0)), "surya_rec_set_forced")
         self.forced = bool(on)
-        if on and self._forced_bufs is None:
-            shape = (L.SA_MAX_STEPS, self.max_slots)
-            self._forced_bufs = (np.zeros(shape, np.int32), np.zeros(shape, np.float32), np.zeros(shape, np.float32))
+        if on:
+            self._forced.ensure()
 
     def set_forced_tokens(self, slots, ids):
         """ids[i]: the token ids slot slots[i] is forced to from its next prefill on, one per head pass, the prefill's included (an
@@ -187,25 +203,14 @@ class HipRecModel:
         L.check(self.lib.surya_rec_set_forced_tokens(self.handle, L.np_ptr(s), L.np_ptr(flat), L.np_ptr(offs), C.c_int(len(s)), self._stream),
                 "surya_rec_set_forced_tokens")
 
-    def _forced_views(self, first):
-        if self._forced_bufs is None:   # never switched on: the library refuses below, with buffers it may not write to anyway
-            return np.zeros((1, 1), np.int32), np.zeros((1, 1), np.float32), np.zeros((1, 1), np.float32)
-        return tuple(b[first:] for b in self._forced_bufs)
-
     def read_forced(self, n_steps: int = 1):
         """Sync; (greedy_tokens [n_steps, slots] int32, greedy_probs, forced_logprobs [n_steps, slots] float32) of the steps read_outputs
         returns: the model's own argmax and its probability, and the log-probability of the token that was emitted."""
-        gt, gp, lp = self._forced_views(0)
-        L.check(self.lib.surya_rec_read_forced(self.handle, C.c_int(n_steps), L.np_ptr(gt), L.np_ptr(gp, C.c_float), L.np_ptr(lp, C.c_float),
-                                               self._stream), "surya_rec_read_forced")
-        return gt[:n_steps], gp[:n_steps], lp[:n_steps]
+        return self._forced.read(self, n_steps)
 
     def wait_forced(self, n_steps: int, ring: int):
         """The forced-decoding outputs of the decode_async call on `ring`, parallel to wait_outputs."""
-        gt, gp, lp = self._forced_views(ring * (L.SA_MAX_STEPS // 2))
-        L.check(self.lib.surya_rec_wait_forced(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(gt), L.np_ptr(gp, C.c_float),
-                                               L.np_ptr(lp, C.c_float)), "surya_rec_wait_forced")
-        return gt[:n_steps], gp[:n_steps], lp[:n_steps]
+        return self._forced.wait(self, n_steps, ring)
 
     def set_beam(self, width: Optional[int], no_output_token_id: int = -1):
         """Beam search (surya_rec_set_beam): `width` in 2..SA_MAX_BEAMS keeps the `width` best readings of every line in a group of `width`
@@ -214,34 +219,20 @@ class HipRecModel:
         w = int(width or 0)
         L.check(self.lib.surya_rec_set_beam(self.handle, C.c_int(w), C.c_int(no_output_token_id)), "surya_rec_set_beam")
         self.beam = w
-        if w and self._beam_bufs is None:
-            shape = (L.SA_MAX_STEPS, self.max_slots)
-            self._beam_bufs = tuple(np.zeros(shape, t) for t in (np.int32, np.int32, np.int32, np.float32, np.float32))
-        if w and self._alt_tok is None:                     # read_alternatives works in beam mode
-            self._alt_tok = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.int32)
-            self._alt_p = np.zeros((L.SA_MAX_STEPS, self.max_slots, L.SA_MAX_ALTERNATIVES), np.float32)
-
-    def _beam_views(self, first):
-        if self._beam_bufs is None:     # never switched on: the library refuses below, with buffers it may not write to anyway
-            return tuple(np.zeros((1, 1), t) for t in (np.int32, np.int32, np.int32, np.float32, np.float32))
-        return tuple(b[first:] for b in self._beam_bufs)
+        if w:
+            self._beam.ensure()
+            self._alt.ensure()                              # read_alternatives works in beam mode
 
     def read_beam(self, n_steps: int = 1):
         """Sync; (tokens, parents, ranks [n_steps, slots] int32, probs, logps [n_steps, slots] float32) of the steps read_outputs returns:
         per slot the beam placed there by the step's selection -- its token (pad: frozen or empty), the slot index inside the group it came
         from (own index: stayed in place, -1: empty), which alternative of the parent it took, that token's probability and the cumulative
         log-probability. The box of a beam is read_outputs' box of its parent's slot."""
-        v = self._beam_views(0)
-        L.check(self.lib.surya_rec_read_beam(self.handle, C.c_int(n_steps), L.np_ptr(v[0]), L.np_ptr(v[1]), L.np_ptr(v[2]),
-                                             L.np_ptr(v[3], C.c_float), L.np_ptr(v[4], C.c_float), self._stream), "surya_rec_read_beam")
-        return tuple(a[:n_steps] for a in v)
+        return self._beam.read(self, n_steps)
 
     def wait_beam(self, n_steps: int, ring: int):
         """The beam outputs of the decode_async call on `ring`, parallel to wait_outputs."""
-        v = self._beam_views(ring * (L.SA_MAX_STEPS // 2))
-        L.check(self.lib.surya_rec_wait_beam(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(v[0]), L.np_ptr(v[1]), L.np_ptr(v[2]),
-                                             L.np_ptr(v[3], C.c_float), L.np_ptr(v[4], C.c_float)), "surya_rec_wait_beam")
-        return tuple(a[:n_steps] for a in v)
+        return self._beam.wait(self, n_steps, ring)
 
     def __del__(self):
         h = getattr(self, "handle", None)
@@ -317,10 +308,7 @@ class HipRecModel:
 
     def read_outputs(self, n_steps: int = 1):
         """Sync; returns (tokens [n_steps, slots], scores, bboxes [n_steps, slots, 6]) numpy views."""
-        L.check(self.lib.surya_rec_read_outputs(self.handle, C.c_int(n_steps), L.np_ptr(self._tok),
-                                                L.np_ptr(self._score, C.c_float), L.np_ptr(self._bbox), self._stream),
-                "surya_rec_read_outputs")
-        return self._tok[:n_steps], self._score[:n_steps], self._bbox[:n_steps]
+        return self._out.read(self, n_steps)
 
     def decode_async(self, n_steps: int, ring: int):
         """Enqueue n_steps (<= SA_MAX_STEPS / 2) decode steps whose outputs land in ring half `ring`; no sync."""
@@ -328,11 +316,7 @@ class HipRecModel:
 
     def wait_outputs(self, n_steps: int, ring: int):
         """Block until the decode_async call on `ring` finished (later calls may still be queued); copies of the outputs."""
-        h = L.SA_MAX_STEPS // 2
-        tok, sc, bb = self._tok[ring * h:], self._score[ring * h:], self._bbox[ring * h:]
-        L.check(self.lib.surya_rec_wait_outputs(self.handle, C.c_int(n_steps), C.c_int(ring), L.np_ptr(tok), L.np_ptr(sc, C.c_float),
-                                                L.np_ptr(bb)), "surya_rec_wait_outputs")
-        return tok[:n_steps], sc[:n_steps], bb[:n_steps]
+        return self._out.wait(self, n_steps, ring)
 
     def set_next_tokens(self, slots, tokens):
         s = np.ascontiguousarray(np.asarray(slots, np.int32))

@@ -293,6 +293,57 @@ def test_refusals(hip_lib):
     torch.cuda.synchronize()
 
 
+def test_decode_async_ring_equals_read(hip_lib):
+    """Two pipelined calls of four steps: what wait_outputs / wait_beam / wait_alternatives return per ring half is the synchronous run's,
+    and read_outputs / read_beam / read_alternatives of all 16 steps show the same bytes in rows 0-3 and 8-11 -- the mirror, the wait
+    and the read agree on where a step of each of the three sets lives."""
+    B, G = 2, len(LINES)
+    m = _model(torch.bfloat16, max_slots=24)
+    m.set_beam(B, _ids()[2])
+    ref = _beam_run(m, B, LINES, 8)
+    sl = (np.arange(G)[:, None] * B + np.arange(B)[None, :])
+    _prefill(m, LINES, (np.arange(G) * B).tolist())
+    m.set_active(sl.reshape(-1).tolist())
+    m.decode_async(4, 0)
+    m.decode_async(4, 1)
+    waited = []                                                              # per ring: the nine arrays over all slots, as returned
+    for ring in (0, 1):
+        waited.append([a.copy() for a in m.wait_outputs(4, ring) + m.wait_beam(4, ring) + m.wait_alternatives(4, ring)])
+    for i, k in enumerate(ARRAYS):
+        got = np.concatenate([w[3 + i][:, sl] for w in waited])
+        assert got.tobytes() == ref[k][1:].tobytes(), k
+    boxes = np.concatenate([w[2][:, sl] for w in waited])
+    parents = np.concatenate([w[4][:, sl] for w in waited])
+    boxes = np.take_along_axis(boxes, np.maximum(parents, 0)[..., None], axis=2)
+    assert boxes.tobytes() == ref["boxes"][1:].tobytes()
+    read = [a.copy() for a in m.read_outputs(16) + m.read_beam(16) + m.read_alternatives(16)]
+    for ring in (0, 1):
+        for i, (r, w) in enumerate(zip(read, waited[ring])):
+            assert r[8 * ring: 8 * ring + 4].tobytes() == w.tobytes(), (ring, i)
+    m.set_beam(None)
+
+
+def test_a_ring_half_filled_while_off_is_refused(hip_lib):
+    """decode_async ran with beam mode off, then it is switched on: that ring half mirrored neither beam outputs nor candidates."""
+    B, G = 2, len(LINES)
+    m = _model(torch.bfloat16, max_slots=24)
+    _run(m, list(range(G)), 0)
+    m.decode_async(2, 0)
+    m.wait_outputs(2, 0)
+    m.set_beam(B, _ids()[2])
+    for wait in (m.wait_beam, m.wait_alternatives):
+        with pytest.raises(L.SuryaAmdError, match="SA_ERR_STATE"):
+            wait(2, 0)
+    sl = (np.arange(G)[:, None] * B + np.arange(B)[None, :])
+    _prefill(m, LINES, (np.arange(G) * B).tolist())
+    m.set_active(sl.reshape(-1).tolist())
+    m.decode_async(2, 1)
+    m.wait_outputs(2, 1)
+    parents = m.wait_beam(2, 1)[1][:, sl]
+    assert (parents >= -1).all() and (parents >= 0).any(axis=2).all()
+    m.set_beam(None)
+
+
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_with_a_token_mask_every_token_is_allowed(hip_lib, dtype):
     cfg = _cfg_sd()[0]

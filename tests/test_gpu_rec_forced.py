@@ -240,13 +240,21 @@ def test_decode_async_ring_equals_read(hip_lib):
     m.decode_async(4, 0)
     m.decode_async(4, 1)
     got = [[], [], [], []]
+    waited = []
     for ring in (0, 1):
         t, _, _ = m.wait_outputs(4, ring)
         f = m.wait_forced(4, ring)
         for dst, a in zip(got, (t,) + tuple(f)):
             dst.append(a[:, SLOTS].copy())
+        waited.append([a.copy() for a in f])
     for a, b in zip(got, (ref[0], ref[3], ref[4], ref[5])):
         assert np.array_equal(_bits(np.concatenate(a)), _bits(b[1:]))
+    # the synchronous read of all 16 steps shows the bytes the waits returned in rows 0-3 and 8-11: mirror, wait and read agree on where
+    # a step lives
+    read = [a.copy() for a in m.read_forced(16)]
+    for ring in (0, 1):
+        for r, w in zip(read, waited[ring]):
+            assert r[8 * ring: 8 * ring + 4].tobytes() == w.tobytes()
 
 
 def test_a_ring_half_filled_while_off_is_refused(hip_lib):
