@@ -314,6 +314,34 @@ int surya_rec_set_beam(surya_rec* h, int width, int no_output_token_id);
 int surya_rec_read_beam(surya_rec* h, int n_steps, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps, void* stream);
 int surya_rec_wait_beam(surya_rec* h, int n_steps, int ring, int32_t* tokens, int32_t* parents, int32_t* ranks, float* probs, float* logps);
 
+/* Pattern-guided decoding: constrain a line to a regular expression (a date, an amount, an IBAN ...), i.e. an allowed set that depends on
+ * what the line has emitted so far. A token mask is one set per line; here the slot's mask id MOVES: it follows a deterministic finite
+ * automaton over the emitted tokens (surya_amd/recognition/pattern.py compiles the tables), and the greedy head, which picks each token,
+ * takes the transition on the device -- behind the token, slot_state[slot] = next_state[state][tok_class[token]] and the slot's mask id =
+ * state_mask[new state]. The next step's masked lm_head then reads the new state's row with no host round trip; a row that emitted eos /
+ * pad keeps its state. The lm_head epilogues do not change, and captured decode steps stay valid (the addresses never change).
+ *   set_patterns: HOST arrays tok_class [vocab] uint8 (class of each token id, < n_classes), next_state [n_states][n_classes] uint16
+ *                (< n_states) and state_mask [n_states] uint8 (row of the CURRENT token-mask table), copied in stream order into
+ *                handle-owned memory allocated on the first call at addresses that never change afterwards; every slot's state is set to
+ *                -1 (no pattern). n_states == 0 switches the feature off: a handle that never saw a pattern, or saw 0 last, launches
+ *                exactly what it launched before this entry existed. SA_ERR_ARG, with nothing changed, for n_states >
+ *                SA_MAX_PATTERN_STATES, n_classes outside 1..SA_MAX_PATTERN_CLASSES or an entry out of range; SA_ERR_STATE without a
+ *                token-mask table, and while forced decoding or beam search is on (surya_rec_set_forced(1) / surya_rec_set_beam(width)
+ *                return SA_ERR_STATE while patterns are on). Switching on or off drops captured decode steps; new contents keep them.
+ *                surya_rec_set_token_masks switches patterns off (the state -> row map names rows of the old table).
+ *   set_slot_patterns: start state (or -1 = no pattern: the slot's mask id is left alone) of `n` slots; call it for the slots about to be
+ *                prefilled, after surya_rec_set_slot_masks, which sets the states of the slots it names back to -1. A state >= 0 also
+ *                sets the slot's mask id to state_mask[state]. SA_ERR_STATE while off; a slot named twice, a slot or a state out of range:
+ *                SA_ERR_ARG.
+ *   copy_slot_states: the states of all max_slots slots into `dst` (device, int32 [max_slots]), for tests. SA_ERR_STATE before the first
+ *                set_patterns. */
+#define SA_MAX_PATTERN_STATES 4096
+#define SA_MAX_PATTERN_CLASSES 256
+int surya_rec_set_patterns(surya_rec* h, const uint8_t* tok_class, const uint16_t* next_state, const uint8_t* state_mask, int n_states,
+                           int n_classes, void* stream);
+int surya_rec_set_slot_patterns(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream);
+int surya_rec_copy_slot_states(surya_rec* h, int32_t* dst, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -433,7 +461,10 @@ int surya_op_gemm_mx(int mode, const uint8_t* X, const uint8_t* SX, const uint8_
  * surya_op_rec_head: the greedy head over the lm_head's partials (surya_op_lm_head_partials) of `rows` rows, row r of slot row_slot[r]:
  *   out_token, out_score, out_bbox [.][6], next_token and kv_len are indexed by slot. table != NULL: the fused next-step embedding (x, y,
  *   row_len and the MXFP8 copy of row r, as surya_op_rec_decode_embed writes them). best_tot [slots][2] or NULL. forced_table != NULL: forced
- *   decoding ([slots][forced_stride] ids, forced_cursor [slots], flogit [rows]; greedy_token, greedy_prob, logprob by slot). Tuning ghead = 2,
+ *   decoding ([slots][forced_stride] ids, forced_cursor [slots], flogit [rows]; greedy_token, greedy_prob, logprob by slot). pat_tok_class !=
+ *   NULL: pattern-guided decoding (pat_tok_class [pat_vocab], pat_next_state [.][pat_n_classes] (the row stride), pat_state_mask [.], pat_slot_state and
+ *   pat_slot_mask by slot; not beside forced_table: SA_ERR_ARG): a slot with state >= 0 whose row did not end moves to the next state and
+ *   gets that state's mask id; no other output changes. Tuning ghead = 2,
  *   H <= 2048 and tiles_n <= 1536: greedy_head2_kernel, else greedy_head_kernel<T, true>, which has no fused embedding (SA_ERR_STATE). */
 enum { SA_REC_CONVERT_TILES = 0, SA_REC_SCATTER_IMAGE, SA_REC_SCATTER_ROWS, SA_REC_EMBED_TOKENS };
 enum { SA_REC_ROPE_VISION = 0, SA_REC_ROPE_DECODER };
@@ -447,6 +478,9 @@ typedef struct surya_rec_head_args {
     const int32_t* forced_table; int32_t* forced_cursor; const float* flogit; int32_t* greedy_token; float *greedy_prob, *logprob;
     int32_t tiles_n, rows, H, eos_id, pad_id, len_inc, max_kv_len, srows, forced_stride;
     float bbox_size, eps;
+    /* pattern-guided decoding (surya_rec_set_patterns); pat_tok_class == NULL: off */
+    const uint8_t* pat_tok_class; const uint16_t* pat_next_state; const uint8_t* pat_state_mask; int32_t *pat_slot_state, *pat_slot_mask;
+    int32_t pat_n_classes, pat_vocab;
 } surya_rec_head_args;
 int surya_op_rec_rmsnorm_rows(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, const int32_t* src_row, int rows, int C,
                               float eps, void* stream);

@@ -16,6 +16,8 @@ SA_MAX_ALTERNATIVES = 4                         # alternatives per token (surya_
 SA_MAX_BEAMS = 4                                # widest beam (surya_rec_set_beam): a row reports four candidates
 SA_MAX_FORCED_TOKENS = 1024                    # forced ids per slot (surya_rec_set_forced_tokens)
 SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
+SA_MAX_PATTERN_STATES = 4096                    # states of a call's joint automaton (surya_rec_set_patterns)
+SA_MAX_PATTERN_CLASSES = 256                    # symbol classes of its alphabet (tok_class is uint8)
 OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
@@ -55,7 +57,9 @@ class RecHeadArgsC(C.Structure):
         "part", "hidden", "wb", "bb", "row_slot", "out_token", "out_score", "out_bbox", "next_token", "kv_len", "table", "wnorm", "x", "y",
         "row_len", "y8", "sy", "best_tot", "forced_table", "forced_cursor", "flogit", "greedy_token", "greedy_prob", "logprob")] +
                 [(n, C.c_int32) for n in ("tiles_n", "rows", "H", "eos_id", "pad_id", "len_inc", "max_kv_len", "srows", "forced_stride")] +
-                [("bbox_size", C.c_float), ("eps", C.c_float)])
+                [("bbox_size", C.c_float), ("eps", C.c_float)] +
+                [(n, C.c_void_p) for n in ("pat_tok_class", "pat_next_state", "pat_state_mask", "pat_slot_state", "pat_slot_mask")] +
+                [("pat_n_classes", C.c_int32), ("pat_vocab", C.c_int32)])
 
 
 class SuryaAmdError(RuntimeError):
@@ -138,6 +142,11 @@ def _bind_lay_ops(lib):
     lib.surya_op_rec_beam_select.argtypes = [p, i, i, i, i, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, i, p]
     lib.surya_op_rec_beam_select.restype = C.c_int
     lib.surya_op_rec_kv_fork.argtypes, lib.surya_op_rec_kv_fork.restype = [i, p, p, p, p, p, i, i, i, i, i, i, p], C.c_int
+    # pattern-guided decoding (a slot's mask id follows an automaton over its tokens; recognition/pattern.py compiles the tables)
+    lib.surya_rec_set_patterns.argtypes = [p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), i, i, p]
+    lib.surya_rec_set_patterns.restype = C.c_int
+    lib.surya_rec_set_slot_patterns.argtypes, lib.surya_rec_set_slot_patterns.restype = [p, ip, ip, i, p], C.c_int
+    lib.surya_rec_copy_slot_states.argtypes, lib.surya_rec_copy_slot_states.restype = [p, p, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

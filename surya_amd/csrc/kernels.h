@@ -462,6 +462,35 @@ struct ForcedHead {
 };
 
 // ---------------------------------------------------------------------------------------------------
+// Pattern-guided decoding in the greedy heads (surya_rec_set_patterns). tok_class == nullptr: the feature is off and the head does what
+// it always did. Otherwise a slot with state st = slot_state[slot] >= 0 follows a finite automaton over the tokens it emits: behind the
+// token, ns = next_state[st][tok_class[token]], slot_state[slot] = ns and slot_mask[slot] = state_mask[ns], the mask-table row the NEXT
+// step's masked lm_head reads for this slot (TokenMask, gemm.h) -- the stream orders the two launches, nobody else writes the slot's
+// entries while it decodes. A row that ended (eos / pad) keeps its state; st < 0 writes nothing. The token, the score, the box and the next
+// step's input do not depend on any of it: the lm_head that produced the partials already saw the state's row.
+struct PatternHead {
+    const uint8_t* tok_class = nullptr;     // [vocab]: the symbol class of a token id
+    const uint16_t* next_state = nullptr;   // [n_states] rows, n_classes entries apart (the engine: always SA_MAX_PATTERN_CLASSES)
+    const uint8_t* state_mask = nullptr;    // [n_states]: row of the token-mask table
+    int n_classes = 0, vocab = 0;
+    int* slot_state = nullptr;              // [slots], -1 = no pattern
+    int* slot_mask = nullptr;               // [slots]
+    // the slot's state: every thread may read it with the head's first loads, long before thread 0 needs it
+    __device__ __forceinline__ int state_of(int slot) const { return tok_class ? slot_state[slot] : -1; }
+    // thread 0: the class of the emitted token (the first of the three dependent loads; an id outside the vocabulary reads nothing)
+    __device__ __forceinline__ int class_of(int st, int tok, bool done) const {
+        return (st >= 0 && !done && (unsigned)tok < (unsigned)vocab) ? (int)tok_class[tok] : -1;
+    }
+    // thread 0, with class_of's value: the transition and the two stores
+    __device__ __forceinline__ void advance(int slot, int st, int cls) const {
+        if (cls < 0) return;
+        const int ns = next_state[(long)st * n_classes + cls];
+        slot_state[slot] = ns;
+        slot_mask[slot] = state_mask[ns];
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------
 // Greedy head (process_outputs, recognition/__init__.py:294-324) on fp32 logits [rows, V]:
 // pred = argmax (first max), score = max softmax prob = 1 / sum(exp(x - max)), done = pred in {eos, pad};
 // bbox = trunc(sigmoid(W_b h + b) * bbox_size) (common/surya/__init__.py:329); updates the slot state for
@@ -476,9 +505,11 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
                                                           int eos_id, int pad_id, float bbox_size, int* __restrict__ out_token,
                                                           float* __restrict__ out_score, int* __restrict__ out_bbox,
                                                           int* __restrict__ next_token, int* __restrict__ kv_len, int len_inc,
-                                                          float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{}) {
+                                                          float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{},
+                                                          PatternHead ph = PatternHead{}) {
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float* lr = logits + (long)r * ldl * (PART ? 4 : 1);
+    const int pst = ph.tok_class ? ph.state_of(row_slot[r]) : -1;      // pattern state: -1 while off (requested with the first loads)
     __shared__ float smax[4], ssum[4];
     __shared__ int sidx[4];
     float best = -INFINITY;
@@ -549,6 +580,7 @@ __global__ __launch_bounds__(256) void greedy_head_kernel(const float* __restric
             next_token[slot] = done ? pad_id : bi;
             kv_len[slot] += len_inc;
             if (best_tot) best_tot[slot] = make_float2(best, tot);      // alternatives on: the row's max and total for topk_combine_kernel
+            ph.advance(slot, pst, ph.class_of(pst, bi, done));          // pattern-guided decoding (PatternHead above)
         }
     }
     // bbox head: 6 dot products of length H, one wave each (waves 0..3 take outputs 0..3, then 4..5)
@@ -649,7 +681,8 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
                                                                        const T* __restrict__ table, const T* __restrict__ wnorm, T* __restrict__ x,
                                                                        T* __restrict__ y, int* __restrict__ row_len, int Tmax, float eps,
                                                                        uint8_t* __restrict__ y8, uint8_t* __restrict__ sy, int srows,
-                                                                       float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{}) {
+                                                                       float2* __restrict__ best_tot = nullptr, ForcedHead fh = ForcedHead{},
+                                                                       PatternHead ph = PatternHead{}) {
     constexpr int NT = SA_HEAD_THREADS, NW = NT / 64, NP = 4, V = Ty<T>::V16, NB = 32 / V;   // NB x 64 x V = 2048 >= H
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     __shared__ float smax[NW], ssum[NW], red[NW];
@@ -673,6 +706,7 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
     const float bias_o = Ty<T>::ld(bb + wave);
     int fcur;
     const int fid = fh.id_of(slot, fcur);          // forced decoding: -1 while off (workgroup-uniform; read before the barriers below)
+    const int pst = ph.state_of(slot);             // pattern state: -1 while off (the same request group)
 
     float best = -INFINITY;
     int bi = 0x7fffffff;
@@ -716,6 +750,9 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
     const int tok = fid >= 0 ? fid : bi;            // the emitted token: the forced id where there is one
     bool done = (tok == eos_id) || (tok == pad_id);
     const int tok_next = done ? pad_id : tok;
+    // pattern-guided decoding: thread 0 asks for the token's class now and takes the transition behind the fused embedding, whose loads
+    // depend on tok_next alone
+    const int pcls = tid == 0 ? ph.class_of(pst, tok, done) : -1;
     if (tid == 0) {
         float tot = 0.f;
 #pragma unroll
@@ -736,6 +773,7 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void greedy_head2_kernel(const flo
         out_bbox[slot * 6 + wave] = (int)(sg * bbox_size);
     }
     if (table) embed_norm_row<T, NT>(table + (long)tok_next * H, x + (long)r * H, wnorm, y + (long)r * H, H, eps, red, y8, sy, srows, r);
+    if (tid == 0) ph.advance(slot, pst, pcls);
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -907,6 +945,7 @@ struct HeadArgs {
     uint8_t* y8 = nullptr; uint8_t* sy = nullptr; int srows = 0;
     float2* best_tot = nullptr;
     ForcedHead fh;
+    PatternHead ph;
 };
 template <typename T>
 int launch_head(const HeadArgs<T>& a, bool mx, hipStream_t s) {
@@ -916,13 +955,13 @@ int launch_head(const HeadArgs<T>& a, bool mx, hipStream_t s) {
         hipLaunchKernelGGL((greedy_head2_kernel<T>), dim3(a.rows), dim3(SA_HEAD_THREADS), 0, s, a.part, a.tiles_n, a.hidden, a.H, a.wb, a.bb,
                            a.row_slot, a.eos_id, a.pad_id, a.bbox_size, a.out_token, a.out_score, a.out_bbox, a.next_token, a.kv_len, a.len_inc,
                            a.table, a.wnorm, a.x, a.y, a.row_len, a.Tmax, a.eps, a.table ? a.y8 : (uint8_t*)nullptr,
-                           a.table ? a.sy : (uint8_t*)nullptr, a.srows, a.best_tot, a.fh);
+                           a.table ? a.sy : (uint8_t*)nullptr, a.srows, a.best_tot, a.fh, a.ph);
         return (int)hipGetLastError();
     }
     if (a.table) return SA_ERR_STATE;                  // the caller checks can_fuse_embed() first
     hipLaunchKernelGGL((greedy_head_kernel<T, true>), dim3(a.rows), dim3(256), 0, s, reinterpret_cast<const float*>(a.part), (long)a.tiles_n,
                        a.tiles_n, a.hidden, a.H, a.wb, a.bb, a.row_slot, a.eos_id, a.pad_id, a.bbox_size, a.out_token, a.out_score, a.out_bbox,
-                       a.next_token, a.kv_len, a.len_inc, a.best_tot, a.fh);
+                       a.next_token, a.kv_len, a.len_inc, a.best_tot, a.fh, a.ph);
     return (int)hipGetLastError();
 }
 

@@ -242,6 +242,9 @@ struct RecBase {
     virtual int set_forced(int) = 0;
     virtual int set_forced_tokens(const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_beam(int, int) = 0;
+    virtual int set_patterns(const uint8_t*, const uint16_t*, const uint8_t*, int, int, hipStream_t) = 0;
+    virtual int set_slot_patterns(const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int copy_slot_states(int32_t*, hipStream_t) = 0;
 };
 
 // surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
@@ -255,6 +258,17 @@ static __global__ __launch_bounds__(256) void set_forced_tokens_kernel(const int
 static __global__ void set_slot_masks_kernel(const int* slots, const int* ids, int* slot_mask, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) slot_mask[slots[i]] = ids[i];
+}
+
+// surya_rec_set_slot_patterns (states != nullptr): slot_state = the start state, and where it is >= 0 the slot's mask id = that state's row.
+// surya_rec_set_slot_masks on a handle with pattern memory (states == nullptr): the named slots follow no automaton any more.
+static __global__ void set_slot_patterns_kernel(const int* slots, const int* states, const uint8_t* state_mask, int* slot_state, int* slot_mask,
+                                                int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int slot = slots[i], st = states ? states[i] : -1;
+    slot_state[slot] = st;
+    if (st >= 0) slot_mask[slot] = state_mask[st];
 }
 
 template <int I> using HeadEpi = std::integral_constant<int, I>;      // compile-time index into a weight format's lm_head epilogues (heads())
@@ -353,18 +367,32 @@ struct RecModel : RecBase {
     float* beam_score = nullptr; int *beam_fin = nullptr, *beam_prompt = nullptr, *fork_src = nullptr, *fork_base = nullptr, *fork_len = nullptr;   // [max_slots]
     int *beam_token = nullptr, *beam_parent = nullptr, *beam_rank = nullptr; float *beam_prob = nullptr, *beam_logp = nullptr;
     int beam = 0, beam_nop = -1;
+    // Pattern-guided decoding (surya_rec_set_patterns; PatternHead in kernels.h): the automaton's three tables at their largest size and a
+    // state per slot, allocated on the first call at addresses that never change afterwards -- captured decode steps hold the pointers,
+    // the contents follow the calls in stream order. pat_states == 0: the head launches are the ones of a handle without this entry.
+    char* pat_arena = nullptr;
+    uint8_t* pat_tok_class = nullptr;                    // [vocab]
+    uint16_t* pat_next_state = nullptr;                  // [SA_MAX_PATTERN_STATES][SA_MAX_PATTERN_CLASSES]: rows always SA_MAX_PATTERN_CLASSES
+                                                         // apart, so a captured head launch holds for tables of any class count
+    uint8_t* pat_state_mask = nullptr;                   // [SA_MAX_PATTERN_STATES]
+    int* slot_state = nullptr;                           // [max_slots], -1 = no pattern
+    Stager st_pat;
+    int pat_states = 0, pat_classes = 0;
     bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
     // Which step-output sets the kernels write right now: decode_async mirrors these, read_steps / wait_steps refuse the others.
     bool steps_on(StepSet k) const { return k == STEPS_BASE || (k == STEPS_ALTS && topk()) || (k == STEPS_BEAM && beam > 0) || (k == STEPS_FORCED && forcing); }
     // The modes that cannot be on together, and why; every setter asks excluded() before it switches its own mode on.
-    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, MODES };
-    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx()}; return on[m]; }
+    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, M_PATTERNS, MODES };
+    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx(), pat_states > 0}; return on[m]; }
     bool excluded(int m) const {
-        static constexpr int pairs[5][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
+        static constexpr int pairs[7][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
                                             {M_FORCED, M_ALTS},       // ... which collects no candidates
                                             {M_FORCED, M_BEAM},
                                             {M_BEAM, M_KV8},          // the KV fork copies the bf16 / fp16 / fp32 caches only
-                                            {M_BEAM, M_MX}};         // (beam search on the fp8 decode paths is out of scope: DESIGN.md 4l)
+                                            {M_BEAM, M_MX},          // (beam search on the fp8 decode paths is out of scope: DESIGN.md 4l)
+                                            {M_FORCED, M_PATTERNS},   // patterns move mask ids, and forced decoding reads no mask
+                                            {M_BEAM, M_PATTERNS}};    // a surviving beam would have to inherit its PARENT's state through
+                                                                      // beam_select_kernel's choice: left out for now
         for (auto& p : pairs)
             if ((p[0] == m && mode_on(p[1])) || (p[1] == m && mode_on(p[0]))) return true;
         return false;
@@ -475,7 +503,8 @@ struct RecModel : RecBase {
     ~RecModel() override {
         for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena}) b->release();
         if (mask_arena) (void)hipFree(mask_arena);
-        st_mask.destroy(); st_forced.destroy();
+        if (pat_arena) (void)hipFree(pat_arena);
+        st_mask.destroy(); st_forced.destroy(); st_pat.destroy();
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -744,7 +773,7 @@ struct RecModel : RecBase {
         if (n == 0) {
             if (n_token_masks > 0) drop_graphs();
             n_token_masks = 0;
-            return SA_OK;
+            return patterns_off(s);
         }
         const size_t table_bytes = (size_t)SA_MAX_TOKEN_MASKS * words * sizeof(uint32_t);
         if (!mask_arena) {                                  // first table: memory and staging, or nothing (a failure leaves the handle as it was)
@@ -768,7 +797,7 @@ struct RecModel : RecBase {
         SA_HIP(hipMemcpyAsync(mask_table, d, (size_t)n * words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         if (n_token_masks == 0) drop_graphs();              // only once the new table is on its way: a refused call changes nothing
         n_token_masks = n;
-        return SA_OK;
+        return patterns_off(s);                             // the state -> row map named rows of the old table
     }
     // Mask ids of the slots about to be prefilled (-1 = unconstrained); a slot keeps its id until it is set again.
     int set_slot_masks(const int32_t* slots, const int32_t* ids, int n, hipStream_t s) override {
@@ -788,7 +817,94 @@ struct RecModel : RecBase {
         int rc = st_mask.flush(s);
         if (rc) return rc;
         hipLaunchKernelGGL(set_slot_masks_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, di, slot_mask, n);
+        if (slot_state)                                     // a slot given a plain id follows no automaton any more (a reused slot would go on advancing)
+            hipLaunchKernelGGL(set_slot_patterns_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, (const int*)nullptr, pat_state_mask, slot_state,
+                               slot_mask, n);
         return (int)hipGetLastError();
+    }
+
+    // The automaton of pattern-guided decoding. Every entry is checked against the counts and the current mask table before anything is
+    // enqueued: the head reads next_state[state][class] and state_mask[state] unchecked. New tables set every slot's state back to -1.
+    // Switching between on and off drops captured steps, which hold the head's empty / filled PatternHead; new contents keep them.
+    int set_patterns(const uint8_t* tok_class, const uint16_t* next_state, const uint8_t* state_mask, int n_states, int n_classes,
+                     hipStream_t s) override {
+        if (n_states < 0 || n_states > SA_MAX_PATTERN_STATES) return SA_ERR_ARG;
+        if (n_states == 0) return patterns_off(s);
+        if (n_classes < 1 || n_classes > SA_MAX_PATTERN_CLASSES || !tok_class || !next_state || !state_mask) return SA_ERR_ARG;
+        if (n_token_masks == 0 || excluded(M_PATTERNS)) return SA_ERR_STATE;
+        const size_t n_next = (size_t)n_states * n_classes;
+        for (int v = 0; v < c.vocab; ++v)
+            if (tok_class[v] >= n_classes) return SA_ERR_ARG;
+        for (size_t i = 0; i < n_next; ++i)
+            if (next_state[i] >= n_states) return SA_ERR_ARG;
+        for (int i = 0; i < n_states; ++i)
+            if (state_mask[i] >= n_token_masks) return SA_ERR_ARG;
+        const size_t next_bytes = (size_t)SA_MAX_PATTERN_STATES * SA_MAX_PATTERN_CLASSES * sizeof(uint16_t), S = c.max_slots;
+        if (!pat_arena) {                                   // first tables: memory and staging, or nothing (a failure leaves the handle as it was)
+            Carve cv;
+            const size_t o_slot = cv.take(S * sizeof(int)), o_cls = cv.take(c.vocab), o_mask = cv.take(SA_MAX_PATTERN_STATES),
+                         o_next = cv.take(next_bytes);
+            char* mem = nullptr;
+            Stager st;
+            SA_HIP(hipMalloc((void**)&mem, cv.off));
+            int rc = st.init(next_bytes + (size_t)c.vocab + SA_MAX_PATTERN_STATES + S * 2 * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipMemsetAsync(mem, 0, cv.off, s);
+            if (rc) { st.destroy(); (void)hipFree(mem); return rc; }
+            st_pat = st;
+            pat_arena = mem;
+            slot_state = reinterpret_cast<int*>(mem + o_slot);
+            pat_tok_class = reinterpret_cast<uint8_t*>(mem + o_cls);
+            pat_state_mask = reinterpret_cast<uint8_t*>(mem + o_mask);
+            pat_next_state = reinterpret_cast<uint16_t*>(mem + o_next);
+        }
+        st_pat.begin();
+        const uint8_t* dc = st_pat.put(tok_class, (size_t)c.vocab);
+        const uint8_t* dm = st_pat.put(state_mask, (size_t)n_states);
+        const uint16_t* dn = st_pat.put(next_state, n_next);
+        if (!dc || !dm || !dn) return SA_ERR_NOMEM;
+        int rc = st_pat.flush(s);
+        if (rc) return rc;
+        SA_HIP(hipMemsetAsync(slot_state, 0xff, S * sizeof(int), s));
+        SA_HIP(hipMemcpyAsync(pat_tok_class, dc, (size_t)c.vocab, hipMemcpyDeviceToDevice, s));
+        SA_HIP(hipMemcpyAsync(pat_state_mask, dm, (size_t)n_states, hipMemcpyDeviceToDevice, s));
+        SA_HIP(hipMemcpy2DAsync(pat_next_state, SA_MAX_PATTERN_CLASSES * sizeof(uint16_t), dn, n_classes * sizeof(uint16_t),
+                                n_classes * sizeof(uint16_t), n_states, hipMemcpyDeviceToDevice, s));
+        if (pat_states == 0) drop_graphs();                 // only once the new tables are on their way: a refused call changes nothing
+        pat_states = n_states;
+        pat_classes = n_classes;
+        return SA_OK;
+    }
+    int patterns_off(hipStream_t s) {
+        if (pat_states == 0) return SA_OK;
+        drop_graphs();
+        pat_states = pat_classes = 0;
+        SA_HIP(hipMemsetAsync(slot_state, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        return SA_OK;
+    }
+    // Start states of the slots about to be prefilled (-1 = no pattern; the slot's mask id is then left alone).
+    int set_slot_patterns(const int32_t* slots, const int32_t* states, int n, hipStream_t s) override {
+        if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
+        if (n > c.max_slots) return SA_ERR_ARG;
+        if (pat_states == 0) return SA_ERR_STATE;
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] < 0 || slots[i] >= c.max_slots || states[i] < -1 || states[i] >= pat_states) return SA_ERR_ARG;
+            if (seen[slots[i]]) return SA_ERR_ARG;
+            seen[slots[i]] = 1;
+        }
+        st_pat.begin();
+        const int* ds = st_pat.put(slots, n);
+        const int* dt = st_pat.put(states, n);
+        if (!ds || !dt) return SA_ERR_NOMEM;
+        int rc = st_pat.flush(s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(set_slot_patterns_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, dt, pat_state_mask, slot_state, slot_mask, n);
+        return (int)hipGetLastError();
+    }
+    int copy_slot_states(int32_t* dst, hipStream_t s) override {
+        if (!slot_state) return SA_ERR_STATE;
+        SA_HIP(hipMemcpyAsync(dst, slot_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SA_OK;
     }
 
     // Alternatives on / off. Memory on the first switch-on, or nothing (a failure leaves the handle as it was); switching drops captured
@@ -1110,6 +1226,8 @@ struct RecModel : RecBase {
         ha.wnorm = WD(0, SA_RD_LN1); ha.x = dx; ha.y = dh; ha.row_len = row_len; ha.Tmax = c.max_kv_len; ha.eps = c.dec_eps;
         ha.y8 = (fz && mx()) ? dh8 : (uint8_t*)nullptr; ha.sy = (fz && mx()) ? sdh : (uint8_t*)nullptr; ha.srows = c.max_slots;
         ha.best_tot = bt; ha.fh = fh;
+        if (pat_states > 0)                                   // empty while patterns are off: the heads do what they always did
+            ha.ph = PatternHead{pat_tok_class, pat_next_state, pat_state_mask, SA_MAX_PATTERN_CLASSES, c.vocab, slot_state, slot_mask};
         if ((rc = launch_head<T>(ha, mx(), s))) return rc;
         return combine();
     }

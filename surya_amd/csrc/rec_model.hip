@@ -283,6 +283,20 @@ int surya_rec_wait_beam(surya_rec* h, int n_steps, int ring, int32_t* tokens, in
     return h->impl->wait_steps(STEPS_BEAM, n_steps, ring, {tokens, parents, ranks, probs, logps});
 }
 
+int surya_rec_set_patterns(surya_rec* h, const uint8_t* tok_class, const uint16_t* next_state, const uint8_t* state_mask, int n_states,
+                           int n_classes, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_patterns(tok_class, next_state, state_mask, n_states, n_classes, (hipStream_t)stream);
+}
+int surya_rec_set_slot_patterns(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream) {
+    if (!h || (n > 0 && (!slots || !start_states))) return SA_ERR_ARG;
+    return h->impl->set_slot_patterns(slots, start_states, n, (hipStream_t)stream);
+}
+int surya_rec_copy_slot_states(surya_rec* h, int32_t* dst, void* stream) {
+    if (!h || !dst) return SA_ERR_ARG;
+    return h->impl->copy_slot_states(dst, (hipStream_t)stream);
+}
+
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
 static __global__ void iota_kernel(int* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -92,6 +92,9 @@ int rec_op(const surya_rec_head_args& a, hipStream_t s) {
     if (!a.table && a.y8) return SA_ERR_ARG;
     if (a.forced_table && (!a.forced_cursor || !a.flogit || a.forced_stride <= 0 || !a.greedy_token || !a.greedy_prob || !a.logprob || a.best_tot))
         return SA_ERR_ARG;                                       // (the engine refuses alternatives beside forced decoding)
+    if (a.pat_tok_class && (!a.pat_next_state || !a.pat_state_mask || !a.pat_slot_state || !a.pat_slot_mask || a.pat_n_classes < 1 ||
+                            a.pat_n_classes > SA_MAX_PATTERN_CLASSES || a.pat_vocab <= 0 || a.forced_table))
+        return SA_ERR_ARG;                                       // (the engine refuses patterns beside forced decoding)
     if (a.y8 && !rec_mx_ok<T>()) return SA_ERR_UNSUPPORTED;
     if (a.H % 8 || (a.y8 && a.H % 128)) return SA_ERR_SHAPE;
     HeadArgs<T> h{reinterpret_cast<const float4*>(a.part), a.tiles_n, a.rows, (const T*)a.hidden, a.H, (const T*)a.wb, (const T*)a.bb, a.row_slot,
@@ -101,6 +104,8 @@ int rec_op(const surya_rec_head_args& a, hipStream_t s) {
     h.best_tot = reinterpret_cast<float2*>(a.best_tot);
     if (a.forced_table)
         h.fh = ForcedHead{a.forced_table, a.forced_cursor, a.flogit, a.forced_stride, a.greedy_token, a.greedy_prob, a.logprob};
+    if (a.pat_tok_class)
+        h.ph = PatternHead{a.pat_tok_class, a.pat_next_state, a.pat_state_mask, a.pat_n_classes, a.pat_vocab, a.pat_slot_state, a.pat_slot_mask};
     return launch_head<T>(h, a.y8 != nullptr, s);
 }
 

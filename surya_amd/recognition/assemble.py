@@ -31,7 +31,7 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     return m
 
 
-_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses")
+_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -42,7 +42,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     list of TextChar): the object state validation would produce, without walking the character list again."""
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
-                         "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None})
+                         "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -93,6 +93,19 @@ def set_log_prob(line: TextLine, forced) -> TextLine:
     """line.log_prob = the sum of an aligned line's forced log-probabilities, eos included (float64 sum of the fp32 values)."""
     line.log_prob = float(np.sum(np.asarray(forced[2], np.float64)))
     line.__pydantic_fields_set__.add("log_prob")
+    return line
+
+
+def set_pattern_matched(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
+    """line.pattern_matched for a line read under a pattern (flat["pattern_tables"], flat["start_states"] by sorted position): the host
+    replay of the automaton over the line's tokens -- true iff the line ended with EOS in an accepting state. A line without a
+    pattern keeps None."""
+    tables = flat.get("pattern_tables")
+    if tables is not None:
+        st = int(flat["start_states"][sorted_pos])
+        if st >= 0:
+            line.pattern_matched = bool(tables.matched(st, tokens))
+            line.__pydantic_fields_set__.add("pattern_matched")
     return line
 
 
@@ -228,6 +241,10 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
+    if flat.get("pattern_tables") is not None:        # a call with patterns: the plain line, then the host replay of its automaton
+        line = assemble_line(proc, {**flat, "pattern_tables": None}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
+                             bbox_size, alts=alts)
+        return set_pattern_matched(flat, sorted_pos, tokens, line)
     if alts is not None and flat.get("forced"):       # an aligned line: alts = (greedy ids, probabilities, forced log-probabilities)
         forced, flat = alts, {**flat, "forced": False}
         line = assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size,
@@ -263,6 +280,9 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    if flat.get("pattern_tables") is not None:
+        out = assemble_batch(proc, {**flat, "pattern_tables": None}, items, drop_repeated_text, return_words, bbox_size)
+        return [set_pattern_matched(flat, it[0], it[2], line) for it, line in zip(items, out)]
     if flat.get("forced"):          # aligned lines: the sixth element is (greedy ids, probabilities, forced log-probabilities) [T] each
         plain = {**flat, "forced": False}
         forced_of = [it[5] for it in items]

@@ -37,6 +37,13 @@ class DeviceLoop:
     id stays with the line: it is set on whatever slot the line is prefilled into, so a slot that is reused takes its new line's id.
     Without "token_masks" the model's mask entry points are never called.
 
+    Patterns: the dict handed to `run` may also carry "pattern_tables" (recognition/pattern.py::PatternTables, whose states' allowed
+    sets are rows of "token_masks"; uploaded once, behind the mask table) and every admitted dict "start_states" (one automaton state
+    per prompt, -1 = no pattern). A line's start state is set, beside its mask id, on whatever slot the line is prefilled into; from
+    then on the model moves the slot's state and mask id itself, token by token, on the device. Patterns are switched off on the way
+    out, before the mask table, also after an exception. Without "pattern_tables" set_patterns / set_slot_patterns are never called
+    -- a model without them works. Not with beam search or forced decoding.
+
     Alternatives (`alternatives=True`): the model reports the SA_MAX_ALTERNATIVES most likely tokens of every step; the loop keeps
     them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
     line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
@@ -109,6 +116,8 @@ class DeviceLoop:
             self.b_fin, self.b_alive = np.ones((slots, B), bool), np.zeros((slots, B), bool)
         self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
         self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
+        self.line_state = np.zeros(0, np.int64)                # id -> start state of the line's pattern, -1 = none
+        self.n_states = 0                                      # states of the automaton uploaded for this loop (0: patterns are off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
@@ -162,6 +171,11 @@ class DeviceLoop:
         assert mk.shape == (m,) and int(mk.min()) >= -1 and int(mk.max()) < self.n_masks, \
             "mask ids must name rows of the call's token-mask table"
         self.line_mask = np.concatenate([self.line_mask, mk])
+        st = d.get("start_states")
+        st = np.full(m, -1, np.int64) if st is None else np.asarray(st, np.int64)
+        assert st.shape == (m,) and int(st.min()) >= -1 and int(st.max()) < self.n_states, \
+            "start states must name states of the call's pattern tables"
+        self.line_state = np.concatenate([self.line_state, st])
         self.queue.extend(range(base, base + m))
 
     def tiles_of(self, first_id, last_id):
@@ -380,6 +394,8 @@ class DeviceLoop:
             return self._prefill_beam(take, slots, grids, prompt_ids)
         if self.n_masks:
             self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
+        if self.n_states:
+            self.model.set_slot_patterns(slots, self.line_state[take].tolist())   # behind the mask ids: a start state names its own row
         if self.forced:
             self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
         self._prefill(take, grids, prompt_ids, slots)
@@ -426,16 +442,23 @@ class DeviceLoop:
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
         m = self.model
         table = None if prep is None else prep.get("token_masks")
+        pattern_tables = None if prep is None else prep.get("pattern_tables")
+        assert pattern_tables is None or not (self.beam or self.forced), "patterns exclude beam search and forced decoding"
 
         def masks_on():
             m.set_token_masks(table)                   # once per call: identical masks were merged by the caller
             self.n_masks = len(table)
+
+        def patterns_on():
+            m.set_patterns(pattern_tables)             # behind the mask table: the states name its rows
+            self.n_states = int(pattern_tables.n_states)
         # (requested, switch on, switch off): switched on in this order, off in reverse on the way out, also after an exception, so the
         # next call starts on the greedy, unmasked kernels without candidates. What was not requested never touches its entry points.
         modes = [(self.beam, lambda: m.set_beam(self.beam, self.nop), lambda: m.set_beam(None)),
                  (self.forced, lambda: m.set_forced(True), lambda: m.set_forced(False)),      # (at most one of the first three: __init__)
                  (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False)),
-                 (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None))]
+                 (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None)),
+                 (pattern_tables is not None, patterns_on, lambda: m.set_patterns(None))]
         with ExitStack() as undo:
             for wanted, on, off in modes:
                 if wanted:

@@ -99,6 +99,7 @@ class HipRecModel:
         self._beam = _StepBufs("beam", [(i32, ()), (i32, ()), (i32, ()), (f32, ()), (f32, ())], max_slots)
         self.mx_weights = None
         self.n_token_masks = 0
+        self.n_pattern_states = 0
         self.alternatives = False
         self.forced = False
         self.beam = 0
@@ -148,14 +149,14 @@ class HipRecModel:
         words = (self.vocab + 31) // 32
         if masks is None or len(masks) == 0:
             L.check(self.lib.surya_rec_set_token_masks(self.handle, None, C.c_int(0), self._stream), "surya_rec_set_token_masks")
-            self.n_token_masks = 0
+            self.n_token_masks = self.n_pattern_states = 0          # (a new or dropped table switches patterns off)
             return
         m = np.ascontiguousarray(np.asarray(masks, np.uint32))
         if m.ndim != 2 or m.shape[1] != words:
             raise ValueError(f"token masks must be [n, {words}] uint32 for a vocabulary of {self.vocab}, got {m.shape}")
         L.check(self.lib.surya_rec_set_token_masks(self.handle, L.np_ptr(m, C.c_uint32), C.c_int(m.shape[0]), self._stream),
                 "surya_rec_set_token_masks")
-        self.n_token_masks = int(m.shape[0])
+        self.n_token_masks, self.n_pattern_states = int(m.shape[0]), 0
 
     def set_slot_masks(self, slots, mask_ids):
         """Mask id (row of the table, -1 = unconstrained) of the slots about to be prefilled; a slot keeps it until it is set again."""
@@ -164,6 +165,39 @@ class HipRecModel:
         assert s.shape == m.shape and s.ndim == 1
         L.check(self.lib.surya_rec_set_slot_masks(self.handle, L.np_ptr(s), L.np_ptr(m), C.c_int(len(s)), self._stream),
                 "surya_rec_set_slot_masks")
+
+    def set_patterns(self, tables):
+        """The call's pattern automaton (surya_rec_set_patterns; recognition/pattern.py::PatternTables, or anything with its tok_class /
+        next_state / state_mask arrays), uploaded behind the token-mask table its state_mask names rows of. None switches the feature
+        off. New tables set every slot back to "no pattern"; set_slot_patterns names the start states of the slots about to be prefilled."""
+        if tables is None:
+            L.check(self.lib.surya_rec_set_patterns(self.handle, None, None, None, C.c_int(0), C.c_int(0), self._stream), "surya_rec_set_patterns")
+            self.n_pattern_states = 0
+            return
+        tc = np.ascontiguousarray(np.asarray(tables.tok_class, np.uint8))
+        ns = np.ascontiguousarray(np.asarray(tables.next_state, np.uint16))
+        sm = np.ascontiguousarray(np.asarray(tables.state_mask, np.uint8))
+        if tc.shape != (self.vocab,) or ns.ndim != 2 or sm.shape != (ns.shape[0],):
+            raise ValueError(f"pattern tables must be tok_class [{self.vocab}], next_state [n_states, n_classes], state_mask [n_states], got "
+                             f"{tc.shape}, {ns.shape}, {sm.shape}")
+        L.check(self.lib.surya_rec_set_patterns(self.handle, L.np_ptr(tc, C.c_uint8), L.np_ptr(ns, C.c_uint16), L.np_ptr(sm, C.c_uint8),
+                                                C.c_int(ns.shape[0]), C.c_int(ns.shape[1]), self._stream), "surya_rec_set_patterns")
+        self.n_pattern_states = int(ns.shape[0])
+
+    def set_slot_patterns(self, slots, start_states):
+        """Start state (-1 = no pattern: the slot keeps its mask id) of the slots about to be prefilled, after set_slot_masks; a state
+        >= 0 also sets the slot's mask id to the state's row. A slot's state then follows its tokens on the device."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int32))
+        t = np.ascontiguousarray(np.asarray(start_states, np.int32))
+        assert s.shape == t.shape and s.ndim == 1
+        L.check(self.lib.surya_rec_set_slot_patterns(self.handle, L.np_ptr(s), L.np_ptr(t), C.c_int(len(s)), self._stream),
+                "surya_rec_set_slot_patterns")
+
+    def slot_states(self) -> np.ndarray:
+        """Sync; the automaton state of every slot, int32 [max_slots] (-1 = no pattern). A test hook, like last_logits."""
+        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
+        L.check(self.lib.surya_rec_copy_slot_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_slot_states")
+        return buf.cpu().numpy()
 
     def set_alternatives(self, on: bool):
         """Report the SA_MAX_ALTERNATIVES most likely (allowed) tokens of every step beside the token itself (surya_rec_set_alternatives).

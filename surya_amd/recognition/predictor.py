@@ -100,7 +100,7 @@ def inputs_fingerprint(shapes, chunks) -> list:
 
 
 def per_image_lists(arg, name, n_images) -> list:
-    """An `allowlist` / `blocklist` argument as one entry per image: None, a str, or a list with one None / str per line."""
+    """An `allowlist` / `blocklist` / `pattern` argument as one entry per image: None, a str, or a list with one None / str per line."""
     if arg is None or isinstance(arg, str):
         return [arg] * n_images
     if not isinstance(arg, (list, tuple)):
@@ -116,37 +116,61 @@ def per_image_lists(arg, name, n_images) -> list:
 
 
 class LineConstraints:
-    """The allowlist / blocklist arguments of one call, resolved: `table` holds the call's distinct token masks (MaskTable: identical
-    sets are merged), `per_image[i]` the mask id of every line of image i (an int) or one id per line (a list). `lines_known` is False
-    on the detector paths, where the per-line form cannot be matched to lines that do not exist yet."""
+    """The allowlist / blocklist / pattern arguments of one call, resolved: `table` holds the call's distinct token masks (MaskTable:
+    identical sets are merged), `per_image[i]` the mask id of every line of image i (an int) or one id per line (a list). `lines_known`
+    is False on the detector paths, where the per-line form cannot be matched to lines that do not exist yet. With patterns:
+    `patterns` is the call's PatternTables (recognition/pattern.py), compiled once, whose states' allowed sets are further rows of
+    `table`, and `per_image_state[i]` the start state of image i's lines in the same two forms (-1 = no pattern). A line with a
+    pattern has mask id -1: its start state names its row."""
 
-    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None):
+    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None, pattern=None):
         from .tokenizer import MaskTable
         self.table = MaskTable(tokenizer, vocab_size, limit)
         allow, block = per_image_lists(allowlist, "allowlist", n_images), per_image_lists(blocklist, "blocklist", n_images)
-        self.per_image = []
-        for i, (a, b) in enumerate(zip(allow, block)):
-            if not isinstance(a, (list, tuple)) and not isinstance(b, (list, tuple)):
+        pats = per_image_lists(pattern, "pattern", n_images)
+        self.per_image, per_image_pat = [], []
+        for i, (a, b, p) in enumerate(zip(allow, block, pats)):
+            if not any(isinstance(x, (list, tuple)) for x in (a, b, p)):
+                if p is not None and (a is not None or b is not None):
+                    raise ValueError(f"image {i}: a line takes a pattern or an allowlist / blocklist, not both")
                 self.per_image.append(self.table.id_for(a, b))
+                per_image_pat.append(p)
                 continue
             if line_counts is None:
-                raise ValueError("a per-line allowlist / blocklist needs bboxes or polygons: with det_predictor the lines are not known yet")
+                raise ValueError("a per-line allowlist / blocklist / pattern needs bboxes or polygons: with det_predictor the lines are not known yet")
             n = line_counts[i]
             a = list(a) if isinstance(a, (list, tuple)) else [a] * n
             b = list(b) if isinstance(b, (list, tuple)) else [b] * n
-            if len(a) != n or len(b) != n:
-                raise ValueError(f"image {i} has {n} lines but its allowlist / blocklist entry has {len(a)} / {len(b)}")
+            p = list(p) if isinstance(p, (list, tuple)) else [p] * n
+            if len(a) != n or len(b) != n or len(p) != n:
+                raise ValueError(f"image {i} has {n} lines but its allowlist / blocklist / pattern entry has {len(a)} / {len(b)} / {len(p)}")
+            for j, (x, y, z) in enumerate(zip(a, b, p)):
+                if z is not None and (x is not None or y is not None):
+                    raise ValueError(f"image {i}, line {j}: a line takes a pattern or an allowlist / blocklist, not both")
             self.per_image.append([self.table.id_for(x, y) for x, y in zip(a, b)])
+            per_image_pat.append(p)
+        distinct = list(dict.fromkeys(z for p in per_image_pat for z in (p if isinstance(p, list) else [p]) if z is not None))
+        self.patterns, self.per_image_state = None, None
+        if distinct:
+            from .pattern import compile_patterns
+            self.patterns = compile_patterns(tokenizer, distinct, vocab_size, extra_mask_rows=self.table)
+            start = {z: s for z, s in zip(self.patterns.patterns, self.patterns.starts)}
+            start[None] = -1
+            self.per_image_state = [[start[z] for z in p] if isinstance(p, list) else start[p] for p in per_image_pat]
 
     def __bool__(self):
         return len(self.table) > 0
 
-    def line_ids(self, slice_map) -> list:
+    def line_ids(self, slice_map, per_image=None) -> list:
         """One id per line, in page order, for pages of slice_map[i] lines."""
         out = []
-        for ids, n in zip(self.per_image, slice_map):
+        for ids, n in zip(self.per_image if per_image is None else per_image, slice_map):
             out.extend(ids if isinstance(ids, list) else [ids] * n)
         return out
+
+    def line_states(self, slice_map) -> list:
+        """One start state per line (-1 = no pattern), like line_ids; a call with patterns only."""
+        return self.line_ids(slice_map, self.per_image_state)
 
 
 class AssemblyHandover(ThreadPoolExecutor):
@@ -362,6 +386,8 @@ class RecognitionPredictor(BasePredictor):
                 "prompt_ids": prompt_ids}
         if flat.get("token_masks") is not None:               # constrained output: the call's mask table and one row id per line
             prep.update(token_masks=flat["token_masks"], mask_ids=flat["mask_ids"])
+        if flat.get("pattern_tables") is not None:            # ... and with patterns the call's automaton and one start state per line
+            prep.update(pattern_tables=flat["pattern_tables"], start_states=flat["start_states"])
         if flat.get("forced_ids") is not None:                # align(): one forced id list per line
             prep["forced_ids"] = flat["forced_ids"]
         return prep
@@ -423,6 +449,8 @@ class RecognitionPredictor(BasePredictor):
             local["pages"] = flat["pages"]
         if flat.get("token_masks") is not None:               # every rank holds the whole table; the ids travel with the lines
             local.update(token_masks=flat["token_masks"], mask_ids=[flat["mask_ids"][i] for i in mine])
+        if flat.get("pattern_tables") is not None:            # ... and so do the start states
+            local.update(pattern_tables=flat["pattern_tables"], start_states=[flat["start_states"][i] for i in mine])
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
         alts = None
         if mine:
@@ -492,6 +520,16 @@ class RecognitionPredictor(BasePredictor):
         disallowed ids are -inf, so a confidence is the softmax over the allowed set; EOS, pad and no-output stay allowed, formatting and
         math tags do not under an allowlist (OCRTokenizer.token_mask). Stop rules, sorting and assembly are unchanged.
 
+        `self.pattern` (an attribute like `top_k`, for the same reason; None = off; the forms of `allowlist`: a str for every line of the
+        calls that follow, or one entry per image of the call: None, a str, or a list with one None / str per bbox / polygon) constrains a
+        line to a regular expression -- r"\\d{2}/\\d{2}/\\d{4}" for a date column -- with the semantics of re.fullmatch on the line's text
+        (recognition/pattern.py documents the supported subset; anything else raises ValueError before any device work). The allowed
+        characters then depend on the position in the line: the line follows the pattern's automaton on the device, one step per token,
+        with no host round trip. A line takes `pattern` or `allowlist` / `blocklist`, not both; a call may mix lines of either kind and
+        unconstrained ones. `TextLine.pattern_matched` is True iff the line ended where the pattern accepts; a line cut by the token
+        budget, the repeat rule or the no-output token reports False and keeps its partial text; None without a pattern. Confidences
+        are softmax values over the set allowed at that position. `top_k` works with it. ValueError with `beam_width`, and in `align`.
+
         `self.beam_width` (an attribute like `top_k`; None = greedy, else 2..4): beam search on the device. Every TextLine carries
         `hypotheses`, its up to beam_width best readings as LineHypothesis(text, confidence, log_prob, finished, chars) -- finished
         readings by log_prob descending, then the ones the token budget or the repeat rule cut -- each assembled like a line
@@ -507,13 +545,17 @@ class RecognitionPredictor(BasePredictor):
         if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= 4):
             raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
         beam = self._check_beam_width(top_k)
+        pattern = self.pattern
+        if pattern is not None and beam is not None:
+            raise ValueError("pattern is not available with beam_width: a beam would have to inherit its parent's automaton state")
         # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
         # page-sharded path and by stand-ins and read it from here)
         saved_k, self._top_k = self._top_k, top_k
         saved_b, self._beam = self._beam, beam
         try:
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist)
+                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
+                                        pattern)
         finally:
             self._top_k, self._beam = saved_k, saved_b
             if top_k is not None:
@@ -552,7 +594,9 @@ class RecognitionPredictor(BasePredictor):
         character takes its confidence from -- the character itself where the model agrees. ValueError, naming image and line, for
         a count mismatch, a line longer than its task's token budget or than SA_MAX_FORCED_TOKENS, or an id outside the model's
         vocabulary. Not with `shard_lines` or a process group: multi-rank alignment is not supported. Allow-lists and `top_k`
-        do not apply to an aligned call."""
+        do not apply to an aligned call, and a set `pattern` raises ValueError: the text is given, there is nothing to constrain."""
+        if self.pattern is not None:
+            raise ValueError("pattern does not apply to align(): forced decoding reads no allowed set (set pattern = None)")
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         if self.shard_lines or self.shard_pages or self.process_group is not None:
@@ -618,21 +662,25 @@ class RecognitionPredictor(BasePredictor):
     _top_k = None                     # the running call's validated top_k (see __call__)
     beam_width: int | None = None     # readings per line (2..4), None = greedy: RecognitionPredictor.beam_width = 3, or on an instance
     _beam = None                      # the running call's validated beam_width (see __call__)
+    pattern = None                    # regex per call / image / line (see __call__), None = off: set on an instance, e.g. pred.pattern = r"\d+"
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
 
     def _call_gc_paused(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist):
+                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
+                        pattern=None):
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
             # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
             lists = {} if allowlist is None and blocklist is None else {"allowlist": allowlist, "blocklist": blocklist}
+            if pattern is not None:
+                lists["pattern"] = pattern
             return self._call(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                               bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
 
-    def _constraints(self, allowlist, blocklist, images, bboxes, polygons):
-        """The call's LineConstraints, or None for a call without lists (or whose lists are all None)."""
-        if allowlist is None and blocklist is None:
+    def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None):
+        """The call's LineConstraints, or None for a call without lists or patterns (or whose entries are all None)."""
+        if allowlist is None and blocklist is None and pattern is None:
             return None
         given = polygons if polygons is not None else bboxes
         if given is not None and len(given) != len(images):
@@ -640,11 +688,12 @@ class RecognitionPredictor(BasePredictor):
         counts = None if given is None else [len(g) for g in given]
         from .. import _lib as L
         cons = LineConstraints(self.processor.ocr_tokenizer, allowlist, blocklist, len(images), counts,
-                               vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS)
+                               vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS, pattern=pattern)
         return cons if cons else None
 
     def _call(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images, bboxes,
-              polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None) -> List[OCRResult]:
+              polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None,
+              pattern=None) -> List[OCRResult]:
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         allowed = self.tasks.keys()
@@ -659,7 +708,7 @@ class RecognitionPredictor(BasePredictor):
         if highres_images is not None:
             assert len(images) == len(highres_images), "You need to pass in one highres image for each image"
         highres_images = convert_if_not_rgb(highres_images) if highres_images is not None else [None] * len(images)
-        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons)
+        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons, pattern)
 
         if bboxes is None and polygons is None:
             assert det_predictor is not None, (
@@ -668,6 +717,8 @@ class RecognitionPredictor(BasePredictor):
                 from .. import dist as sdist
                 if sdist.collectives_on(self.process_group):
                     lists = {} if cons is None else {"allowlist": allowlist, "blocklist": blocklist}
+                    if cons is not None and cons.patterns is not None:
+                        lists["pattern"] = pattern
                     return self._call_page_sharded(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
                                                    highres_images, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
             if self._can_stream(det_predictor):
@@ -689,6 +740,9 @@ class RecognitionPredictor(BasePredictor):
         if cons is not None:                                  # by line id like the slices: sorted with them below
             flat["token_masks"], flat["mask_ids"] = cons.table.array(), cons.line_ids(flat["slice_map"])
             sorted_keys += ("mask_ids",)
+            if cons.patterns is not None:
+                flat["pattern_tables"], flat["start_states"] = cons.patterns, cons.line_states(flat["slice_map"])
+                sorted_keys += ("start_states",)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
@@ -731,7 +785,7 @@ class RecognitionPredictor(BasePredictor):
     gather_page_results: bool = True
 
     def _call_page_sharded(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                           sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None) -> list:
+                           sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None, pattern=None) -> list:
         from .. import dist as sdist
         group = self.process_group
         rank, world = sdist.world_info(group)
@@ -749,6 +803,8 @@ class RecognitionPredictor(BasePredictor):
         if allowlist is not None or blocklist is not None:
             lists = {"allowlist": [per_image_lists(allowlist, "allowlist", n)[i] for i in mine],
                      "blocklist": [per_image_lists(blocklist, "blocklist", n)[i] for i in mine]}
+        if pattern is not None:                               # a rank compiles the patterns of its own pages
+            lists["pattern"] = [per_image_lists(pattern, "pattern", n)[i] for i in mine]
         try:
             hr = [highres_images[i] for i in mine]
             local = self._call([images[i] for i in mine], [task_names[i] for i in mine], det_predictor, detection_batch_size,
@@ -810,6 +866,9 @@ class RecognitionPredictor(BasePredictor):
         flat = new_flat()
         if self._top_k is not None:
             flat["top_k"] = self._top_k
+        with_patterns = cons is not None and cons.patterns is not None
+        if with_patterns:                                     # assembly replays a line's automaton from its start state
+            flat["pattern_tables"], flat["start_states"] = cons.patterns, []
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
@@ -824,7 +883,7 @@ class RecognitionPredictor(BasePredictor):
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
-                    pages, refs, polys_all, scales_all, tasks_all, masks_all = [], [], [], [], [], []
+                    pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all = [], [], [], [], [], [], []
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
@@ -834,6 +893,8 @@ class RecognitionPredictor(BasePredictor):
                         tasks_all.extend([task_names[page]] * len(polygons))
                         if cons is not None:                  # (per-call and per-image lists only: one id per page)
                             masks_all.extend([cons.per_image[page]] * len(polygons))
+                            if with_patterns:
+                                states_all.extend([cons.per_image_state[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -850,10 +911,13 @@ class RecognitionPredictor(BasePredictor):
                     flat["slices"].extend(refs[i] for i in order)
                     flat["task_names"].extend(tasks_all[i] for i in order)
                     flat["input_text"].extend([None] * len(order))
+                    if with_patterns:
+                        flat["start_states"].extend(states_all[i] for i in order)
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
                            "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts},
-                           "mask_ids": [masks_all[i] for i in order] if cons is not None else None})
+                           "mask_ids": [masks_all[i] for i in order] if cons is not None else None,
+                           "start_states": [states_all[i] for i in order] if with_patterns else None})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -881,6 +945,8 @@ class RecognitionPredictor(BasePredictor):
                     first = {"prompts": [], "max_tokens": {}, "overall_max_tokens": overall_max_tokens}
                     if cons is not None:
                         first["token_masks"] = cons.table.array()      # the whole call's table up front: chunks carry row ids only
+                        if with_patterns:
+                            first["pattern_tables"] = cons.patterns
                     self.generate(first, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...

@@ -97,12 +97,17 @@ class TextLine(BaseChar):
     # score of the line's best reading. None, and left out of the serialised form, in every other result.
     # `hypotheses` (RecognitionPredictor.beam_width): the line's n best readings, finished ones by log_prob descending, then unfinished
     # ones; entry 0 is the line itself. None, and left out like log_prob, everywhere else.
+    # `pattern_matched` (RecognitionPredictor.__call__(pattern=)): whether the line, read under a pattern, ended with EOS where the
+    # pattern accepts -- False for a line cut by the token budget, the repeat rule or the no-output token (its text is then a proper
+    # prefix of a match, or empty). None, and left out likewise, for a line without a pattern.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
         hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
+        pattern_matched: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
         hypotheses: Optional[List[LineHypothesis]] = None
+        pattern_matched: Optional[bool] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
@@ -111,6 +116,8 @@ class TextLine(BaseChar):
                 d.pop("log_prob", None)
             if self.hypotheses is None:
                 d.pop("hypotheses", None)
+            if self.pattern_matched is None:
+                d.pop("pattern_matched", None)
             return d
 
 

@@ -237,6 +237,16 @@ class MaskTable:
             self._by_spec[spec] = self._by_bytes[key]
         return self._by_spec[spec]
 
+    def add_row(self, mask: np.ndarray, what: str = "allowlists / blocklists") -> int:
+        """The id of a ready-made row (the allowed set of a pattern state, recognition/pattern.py), merged with identical rows."""
+        key = mask.tobytes()
+        if key not in self._by_bytes:
+            if self.limit is not None and len(self.rows) >= self.limit:
+                raise ValueError(f"more than {self.limit} distinct {what} in one call")
+            self._by_bytes[key] = len(self.rows)
+            self.rows.append(mask)
+        return self._by_bytes[key]
+
     def __len__(self):
         return len(self.rows)
 

@@ -5,7 +5,7 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced|patterns] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
@@ -23,6 +23,12 @@ on / off, alternating; tokens must be identical to the first arm. `altsonly`: th
 `forced`: forced decoding (HipRecModel.set_forced: the *_FORCED lm_head epilogue and the forced greedy head) off / on / off / on / off,
 alternating, every slot forced to random ids for the whole run; the off arms' tokens must be identical to the first arm, the on arms emit
 their ids. `forcedonly`: the "on" arm alone (for a kernel trace beside `base`).
+
+`patterns`: pattern-guided decoding (HipRecModel.set_patterns: the greedy head advances every slot's automaton and mask id), three arms
+alternating in one process: unmasked / masks only (digits allowlist) / a pattern on every slot, twice, then unmasked once more. pat=1 is
+the date \d{2}/\d{2}/\d{4} (a line is complete after 10 tokens and keeps its state from then on), pat=2 is \d{64}, which takes a
+transition at every step of the run. Tokens are compared with the first arm of the same constraint. `patternonly`: the date arm alone
+(for a kernel trace beside `base` and `maskonly`).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -97,6 +103,10 @@ def main():
         variants = [dict(), dict(masks=1), dict(), dict(masks=2), dict()]
     elif args.configs == "maskonly":     # one arm, a digits allowlist on every slot (for a kernel trace beside `base`)
         variants = [dict(masks=1)]
+    elif args.configs == "patterns":     # pattern-guided decoding: unmasked / masks only / a pattern on every slot, alternating
+        variants = [dict(), dict(masks=1), dict(pat=1), dict(pat=2), dict(), dict(masks=1), dict(pat=1), dict(pat=2), dict()]
+    elif args.configs == "patternonly":  # one arm, the date pattern on every slot (for a kernel trace beside `base` / `maskonly`)
+        variants = [dict(pat=1)]
     elif args.configs == "alts":         # alternatives: off against on, alternating
         variants = [dict(), dict(alts=1), dict(), dict(alts=1), dict()]
     elif args.configs == "altsonly":
@@ -119,7 +129,12 @@ def main():
     forced_ids = [[int(t) if t not in stop_ids else 17 for t in row]
                   for row in np.random.default_rng(99).integers(0, cfg.decoder.vocab_size, size=(n, args.steps + 1))]
 
+    pat_start = [None]
+
     def run(n_steps):
+        if pat_start[0] is not None:                 # every run starts every slot's automaton again
+            m.set_slot_masks(slots, [-1] * n)
+            m.set_slot_patterns(slots, [pat_start[0]] * n)
         if m.forced:
             m.set_forced_tokens(slots, [row[: n_steps + 1] for row in forced_ids])
         m.prefill(tiles, grids, seqs, slots)
@@ -158,6 +173,18 @@ def main():
         m.set_token_masks(mask[None])
         m.set_slot_masks(slots, [0] * n)
 
+    def set_patterns(kind):                      # 0 = off (the mask table goes too), 1 = the date, 2 = 64 digits: a transition at every step
+        pat_start[0] = None
+        if not kind:
+            return m.set_token_masks(None)
+        from surya_amd.recognition.loader import RecognitionModelLoader
+        from surya_amd.recognition.pattern import compile_patterns
+        tk = RecognitionModelLoader({"config": cfg, "state_dict": {}}).processor().ocr_tokenizer
+        pt = compile_patterns(tk, [r"\d{2}/\d{2}/\d{4}" if kind == 1 else r"\d{64}"], cfg.decoder.vocab_size)
+        m.set_token_masks(pt.table.array())
+        m.set_patterns(pt)
+        pat_start[0] = pt.starts[0]
+
     ref = {}
     print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == first arm of the same arithmetic")
     for v in variants:
@@ -170,12 +197,21 @@ def main():
         forced = v.pop("forced", 0)
         if forced or args.configs in ("forced", "forcedonly"):
             m.set_forced(bool(forced))
+        pat = v.pop("pat", 0)
+        if pat:
+            set_patterns(pat)
+        elif args.configs in ("patterns", "patternonly"):
+            set_patterns(0)
+            if masks:
+                set_masks(masks)
         if masks or args.configs in ("masks", "maskonly"):
             set_masks(masks)
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
-        if args.configs in ("masks", "maskonly"):
+        if args.configs in ("masks", "maskonly", "patterns", "patternonly"):
             v["masks"] = masks
+            if args.configs in ("patterns", "patternonly"):
+                v["pat"] = pat
         if args.configs in ("alts", "altsonly"):
             v["alts"] = alts
         if args.configs in ("forced", "forcedonly"):
@@ -183,12 +219,12 @@ def main():
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0)), best[2])).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0), v.get("pat", 0)), best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
-    if args.configs in ("masks", "maskonly"):
-        m.set_token_masks(None)
+    if args.configs in ("masks", "maskonly", "patterns", "patternonly"):
+        m.set_token_masks(None)                      # (which switches patterns off as well)
     if args.configs in ("alts", "altsonly"):
         m.set_alternatives(False)
     if args.configs in ("forced", "forcedonly"):
