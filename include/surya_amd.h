@@ -342,6 +342,38 @@ int surya_rec_set_patterns(surya_rec* h, const uint8_t* tok_class, const uint16_
 int surya_rec_set_slot_patterns(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream);
 int surya_rec_copy_slot_states(surya_rec* h, int32_t* dst, void* stream);
 
+/* Lexicon-guided decoding: read a line as exactly one entry of a word list (a city, a surname, a product code). A word list has about as
+ * many distinct allowed sets as it has inner trie nodes, far beyond the SA_MAX_TOKEN_MASKS rows that patterns share with the allowlists,
+ * so the automaton is sparse (CSR; surya_amd/recognition/lexicon.py compiles a minimised acyclic one for all lexicons of a call) and
+ * every slot owns a mask-table row of its own, id SA_MAX_TOKEN_MASKS + slot, which a small kernel rewrites on the device behind each
+ * token (csrc/lexicon.h): clear the old state's bits, set the new state's. The masked lm_head epilogues read that row like a static
+ * one and do not change; logits are the same bits. A row that emitted eos / pad keeps its state and row.
+ *   set_lexicon: HOST arrays edge_off [n_states + 1] (edges of state s: edge_off[s] .. edge_off[s + 1]), edge_tok [n_edges] (token ids,
+ *                strictly ascending inside a state), edge_next [n_edges] (target states) and state_flags [n_states] (bit 0: terminal,
+ *                eos and pad allowed; bit 1: no_output_token_id allowed), copied in stream order into handle-owned memory sized by need;
+ *                every slot's lexicon state is set to -1. Everything is validated first -- offsets from 0 to n_edges and monotone,
+ *                tokens inside [0, vocab) and ascending, targets < n_states, flags < 4, an allowed id in every state, no_output_token_id
+ *                inside the vocabulary where a state names it, counts within SA_MAX_LEXICON_STATES / SA_MAX_LEXICON_EDGES: SA_ERR_ARG
+ *                with nothing changed otherwise. SA_ERR_STATE without a token-mask table, and while forced decoding or beam search is
+ *                on (their setters return SA_ERR_STATE while a lexicon is on). n_states == 0 switches the feature off: a handle that
+ *                never saw a lexicon, or saw 0 last, launches exactly what it launched before this entry existed. Switching on or off,
+ *                or growing the tables' memory, drops captured decode steps; new contents of the same capacity keep them. The first
+ *                call also gives the mask table its max_slots dynamic rows (max_slots * cdiv(vocab, 32) * 4 bytes). It may be on
+ *                together with patterns; a slot follows at most one of the two. surya_rec_set_token_masks switches it off.
+ *                At the limits the tables take 21 MB on the device and as much pinned host memory (4 + 1 bytes per state, 8 per edge).
+ *   set_slot_lexicon: start state (or -1 = no lexicon: the slot's mask id and row are left alone) of `n` slots; call it for the slots
+ *                about to be prefilled, after surya_rec_set_slot_masks, which sets the lexicon state of the slots it names back to -1.
+ *                A state >= 0 zeroes the slot's row, sets the state's bits and makes the row the slot's mask id. SA_ERR_STATE while
+ *                off; a slot named twice, a slot or a state out of range: SA_ERR_ARG.
+ *   copy_lexicon_states: the states of all max_slots slots into `dst` (device, int32 [max_slots]), for tests. SA_ERR_STATE before the
+ *                first set_lexicon. */
+#define SA_MAX_LEXICON_STATES (1 << 20)
+#define SA_MAX_LEXICON_EDGES (1 << 21)
+int surya_rec_set_lexicon(surya_rec* h, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* state_flags,
+                          int n_states, int n_edges, int no_output_token_id, void* stream);
+int surya_rec_set_slot_lexicon(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream);
+int surya_rec_copy_lexicon_states(surya_rec* h, int32_t* dst, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -511,6 +543,21 @@ int surya_op_rec_beam_select(const int32_t* lead_slots, int stride, int n_groups
                              int32_t* kv_len, int32_t* prompt_len, int32_t* fork_base, int32_t* fork_len, int max_kv_len, void* stream);
 int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* fork_src, const int32_t* base, const int32_t* len, int rows,
                          int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream);
+/* The two kernels of lexicon-guided decoding (csrc/lexicon.h) on caller-owned DEVICE buffers, through the launch code the engine uses. The
+ * tables are read unchecked, as the engine's are after its validation. `table` is a whole mask table of rows of `words` uint32; slot s
+ * owns row row_base + s. eos / pad / nop ids outside [0, vocab) have no bit.
+ *   lexicon_start: workgroup i gives slot slots[i] the state states[i]: slot_state = it; for a state >= 0 the slot's whole row is zeroed,
+ *                the state's bits are set and slot_mask = row_base + slot; -1 leaves mask id and row alone. A slot at most once.
+ *   lexicon_step: workgroup r moves slot row_slot[r] behind its token out_token[slot]: no lexicon (-1), eos / pad, an id outside the
+ *                vocabulary and an id the state has no edge for touch nothing; else the old state's words are cleared, the new state's
+ *                bits set and slot_state updated. A slot at most once per call. */
+typedef struct surya_rec_lexicon_args {
+    const int32_t *edge_off, *edge_tok, *edge_next; const uint8_t* state_flags;
+    uint32_t* table; int32_t *slot_state, *slot_mask;
+    int32_t words, row_base, vocab, eos_id, pad_id, nop_id;
+} surya_rec_lexicon_args;
+int surya_op_rec_lexicon_start(const surya_rec_lexicon_args* args, const int32_t* slots, const int32_t* states, int n, void* stream);
+int surya_op_rec_lexicon_step(const surya_rec_lexicon_args* args, const int32_t* row_slot, const int32_t* out_token, int rows, void* stream);
 
 /* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
  * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).

@@ -18,6 +18,8 @@ SA_MAX_FORCED_TOKENS = 1024                    # forced ids per slot (surya_rec_
 SA_MAX_TOKEN_MASKS = 64                         # rows of a handle's token-mask table (surya_rec_set_token_masks)
 SA_MAX_PATTERN_STATES = 4096                    # states of a call's joint automaton (surya_rec_set_patterns)
 SA_MAX_PATTERN_CLASSES = 256                    # symbol classes of its alphabet (tok_class is uint8)
+SA_MAX_LEXICON_STATES = 1 << 20                 # states of a call's joint lexicon automaton (surya_rec_set_lexicon)
+SA_MAX_LEXICON_EDGES = 1 << 21                  # ... and its edges
 OP_MXFP8 = 3                                    # SA_OP_MXFP8: the MXFP8 arm of surya_op_lm_head_partials
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2      # SA_DTYPE_*; every engine takes all three
 (RW_PATCH, RW_MERGER_LN, RW_FC1_W, RW_FC1_B, RW_FC2_W, RW_FC2_B, RW_IMG_H, RW_IMG_W, RW_DEC_NORM, RW_TOK_EMBED, RW_LM_W,
@@ -60,6 +62,12 @@ class RecHeadArgsC(C.Structure):
                 [("bbox_size", C.c_float), ("eps", C.c_float)] +
                 [(n, C.c_void_p) for n in ("pat_tok_class", "pat_next_state", "pat_state_mask", "pat_slot_state", "pat_slot_mask")] +
                 [("pat_n_classes", C.c_int32), ("pat_vocab", C.c_int32)])
+
+
+class RecLexiconArgsC(C.Structure):
+    """surya_rec_lexicon_args (include/surya_amd.h): the operands of surya_op_rec_lexicon_start / _step."""
+    _fields_ = ([(n, C.c_void_p) for n in ("edge_off", "edge_tok", "edge_next", "state_flags", "table", "slot_state", "slot_mask")] +
+                [(n, C.c_int32) for n in ("words", "row_base", "vocab", "eos_id", "pad_id", "nop_id")])
 
 
 class SuryaAmdError(RuntimeError):
@@ -147,6 +155,12 @@ def _bind_lay_ops(lib):
     lib.surya_rec_set_patterns.restype = C.c_int
     lib.surya_rec_set_slot_patterns.argtypes, lib.surya_rec_set_slot_patterns.restype = [p, ip, ip, i, p], C.c_int
     lib.surya_rec_copy_slot_states.argtypes, lib.surya_rec_copy_slot_states.restype = [p, p, p], C.c_int
+    # lexicon-guided decoding (every slot's own mask row follows a sparse automaton; recognition/lexicon.py compiles the tables)
+    lib.surya_rec_set_lexicon.argtypes, lib.surya_rec_set_lexicon.restype = [p, ip, ip, ip, C.POINTER(C.c_uint8), i, i, i, p], C.c_int
+    lib.surya_rec_set_slot_lexicon.argtypes, lib.surya_rec_set_slot_lexicon.restype = [p, ip, ip, i, p], C.c_int
+    lib.surya_rec_copy_lexicon_states.argtypes, lib.surya_rec_copy_lexicon_states.restype = [p, p, p], C.c_int
+    for name in ("surya_op_rec_lexicon_start", "surya_op_rec_lexicon_step"):
+        getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(RecLexiconArgsC), p, p, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

@@ -19,6 +19,7 @@
 #include "decode_attn_kv8.h"
 #include "attn_mfma.h"
 #include "beam.h"
+#include "lexicon.h"
 
 namespace sa {
 
@@ -245,6 +246,9 @@ struct RecBase {
     virtual int set_patterns(const uint8_t*, const uint16_t*, const uint8_t*, int, int, hipStream_t) = 0;
     virtual int set_slot_patterns(const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int copy_slot_states(int32_t*, hipStream_t) = 0;
+    virtual int set_lexicon(const int32_t*, const int32_t*, const int32_t*, const uint8_t*, int, int, int, hipStream_t) = 0;
+    virtual int set_slot_lexicon(const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int copy_lexicon_states(int32_t*, hipStream_t) = 0;
 };
 
 // surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
@@ -378,21 +382,44 @@ struct RecModel : RecBase {
     int* slot_state = nullptr;                           // [max_slots], -1 = no pattern
     Stager st_pat;
     int pat_states = 0, pat_classes = 0;
+    // Lexicon-guided decoding (surya_rec_set_lexicon; lexicon.h): a sparse automaton in handle-owned memory sized by need -- growing it,
+    // like switching the feature on or off, drops captured steps; new contents of the same capacity keep them -- and a state per slot,
+    // allocated on the first call at an address that never changes. Slot s owns row SA_MAX_TOKEN_MASKS + s of the mask table; those
+    // max_slots rows exist only on a handle that has seen a lexicon (mask_dyn_rows: the first set_lexicon moves the mask arena into a
+    // larger block, at the one moment at which every captured step is dropped anyway; from then on its addresses never move again).
+    // lex_states == 0: the handle launches exactly what a handle without this entry launches.
+    DevBlock lex_arena;                                  // device tables + their pinned staging copy, [lex_cap_states] / [lex_cap_edges]
+    int *lex_edge_off = nullptr, *lex_edge_tok = nullptr, *lex_edge_next = nullptr;
+    uint8_t* lex_flags = nullptr;
+    size_t lex_o_tok = 0, lex_o_next = 0, lex_o_flags = 0;   // offsets in both blocks (edge_off is at 0)
+    int lex_cap_states = 0, lex_cap_edges = 0;
+    hipEvent_t lex_ev = nullptr;                         // the staging copy is on the device
+    bool lex_pending = false;
+    int* slot_lex_state = nullptr;                       // [max_slots], -1 = no lexicon
+    Stager st_lex;                                       // slots and start states of set_slot_lexicon
+    bool mask_dyn_rows = false;
+    int lex_states = 0, lex_nop = -1;
+    LexiconArgs lex_args() const {
+        return LexiconArgs{lex_edge_off, lex_edge_tok, lex_edge_next, lex_flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS, slot_lex_state,
+                           slot_mask, c.vocab, c.eos_token_id, c.pad_token_id, lex_nop};
+    }
     bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
     // Which step-output sets the kernels write right now: decode_async mirrors these, read_steps / wait_steps refuse the others.
     bool steps_on(StepSet k) const { return k == STEPS_BASE || (k == STEPS_ALTS && topk()) || (k == STEPS_BEAM && beam > 0) || (k == STEPS_FORCED && forcing); }
     // The modes that cannot be on together, and why; every setter asks excluded() before it switches its own mode on.
-    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, M_PATTERNS, MODES };
-    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx(), pat_states > 0}; return on[m]; }
+    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, M_PATTERNS, M_LEXICON, MODES };
+    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx(), pat_states > 0, lex_states > 0}; return on[m]; }
     bool excluded(int m) const {
-        static constexpr int pairs[7][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
+        static constexpr int pairs[9][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
                                             {M_FORCED, M_ALTS},       // ... which collects no candidates
                                             {M_FORCED, M_BEAM},
                                             {M_BEAM, M_KV8},          // the KV fork copies the bf16 / fp16 / fp32 caches only
                                             {M_BEAM, M_MX},          // (beam search on the fp8 decode paths is out of scope: DESIGN.md 4l)
                                             {M_FORCED, M_PATTERNS},   // patterns move mask ids, and forced decoding reads no mask
-                                            {M_BEAM, M_PATTERNS}};    // a surviving beam would have to inherit its PARENT's state through
+                                            {M_BEAM, M_PATTERNS},     // a surviving beam would have to inherit its PARENT's state through
                                                                       // beam_select_kernel's choice: left out for now
+                                            {M_FORCED, M_LEXICON},    // as patterns: forced decoding reads no mask,
+                                            {M_BEAM, M_LEXICON}};     // and a surviving beam would inherit its parent's state AND row (4o)
         for (auto& p : pairs)
             if ((p[0] == m && mode_on(p[1])) || (p[1] == m && mode_on(p[0]))) return true;
         return false;
@@ -504,7 +531,10 @@ struct RecModel : RecBase {
         for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena}) b->release();
         if (mask_arena) (void)hipFree(mask_arena);
         if (pat_arena) (void)hipFree(pat_arena);
-        st_mask.destroy(); st_forced.destroy(); st_pat.destroy();
+        lex_arena.release();
+        if (slot_lex_state) (void)hipFree(slot_lex_state);
+        if (lex_ev) (void)hipEventDestroy(lex_ev);
+        st_mask.destroy(); st_forced.destroy(); st_pat.destroy(); st_lex.destroy();
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -773,12 +803,12 @@ struct RecModel : RecBase {
         if (n == 0) {
             if (n_token_masks > 0) drop_graphs();
             n_token_masks = 0;
-            return patterns_off(s);
+            return automata_off(s);
         }
         const size_t table_bytes = (size_t)SA_MAX_TOKEN_MASKS * words * sizeof(uint32_t);
         if (!mask_arena) {                                  // first table: memory and staging, or nothing (a failure leaves the handle as it was)
             Carve cv;
-            const size_t o_slot = cv.take((size_t)c.max_slots * sizeof(int)), o_table = cv.take(table_bytes);
+            const size_t o_slot = cv.take((size_t)c.max_slots * sizeof(int)), o_table = cv.take(table_bytes);   // (grow_mask_arena: same layout)
             char* mem = nullptr;
             SA_HIP(hipMalloc((void**)&mem, cv.off));
             int rc = st_mask.init(table_bytes + (size_t)c.max_slots * 2 * sizeof(int) + 4096);
@@ -797,7 +827,7 @@ struct RecModel : RecBase {
         SA_HIP(hipMemcpyAsync(mask_table, d, (size_t)n * words * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
         if (n_token_masks == 0) drop_graphs();              // only once the new table is on its way: a refused call changes nothing
         n_token_masks = n;
-        return patterns_off(s);                             // the state -> row map named rows of the old table
+        return automata_off(s);                             // the state -> row map named rows of the old table; every slot's id is -1 again
     }
     // Mask ids of the slots about to be prefilled (-1 = unconstrained); a slot keeps its id until it is set again.
     int set_slot_masks(const int32_t* slots, const int32_t* ids, int n, hipStream_t s) override {
@@ -820,7 +850,15 @@ struct RecModel : RecBase {
         if (slot_state)                                     // a slot given a plain id follows no automaton any more (a reused slot would go on advancing)
             hipLaunchKernelGGL(set_slot_patterns_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, (const int*)nullptr, pat_state_mask, slot_state,
                                slot_mask, n);
+        if (slot_lex_state) {                               // ... and rewrites no row any more
+            if ((rc = (int)hipGetLastError())) return rc;
+            return launch_lexicon_start(lex_args(), ds, nullptr, n, s);
+        }
         return (int)hipGetLastError();
+    }
+    int automata_off(hipStream_t s) {
+        const int rc = patterns_off(s);
+        return rc ? rc : lexicon_off(s);
     }
 
     // The automaton of pattern-guided decoding. Every entry is checked against the counts and the current mask table before anything is
@@ -904,6 +942,138 @@ struct RecModel : RecBase {
     int copy_slot_states(int32_t* dst, hipStream_t s) override {
         if (!slot_state) return SA_ERR_STATE;
         SA_HIP(hipMemcpyAsync(dst, slot_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SA_OK;
+    }
+
+    // The automaton of lexicon-guided decoding (lexicon.h), from host arrays. Everything is checked before anything is enqueued or
+    // allocated: the kernels read the tables unchecked. New tables set every slot's state back to -1.
+    int set_lexicon(const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* flags, int n_states, int n_edges,
+                    int nop, hipStream_t s) override {
+        if (n_states < 0 || n_states > SA_MAX_LEXICON_STATES || n_edges < 0 || n_edges > SA_MAX_LEXICON_EDGES) return SA_ERR_ARG;
+        if (n_states == 0) return lexicon_off(s);
+        if (!edge_off || !flags || (n_edges > 0 && (!edge_tok || !edge_next))) return SA_ERR_ARG;
+        if (n_token_masks == 0 || excluded(M_LEXICON)) return SA_ERR_STATE;
+        if (edge_off[0] != 0 || edge_off[n_states] != n_edges) return SA_ERR_ARG;
+        const bool ends = (c.eos_token_id >= 0 && c.eos_token_id < c.vocab) || (c.pad_token_id >= 0 && c.pad_token_id < c.vocab);
+        for (int st = 0; st < n_states; ++st) {
+            const int a = edge_off[st], b = edge_off[st + 1];
+            if (a < 0 || b < a || b > n_edges || (flags[st] & ~3)) return SA_ERR_ARG;
+            if ((flags[st] & 2) && (nop < 0 || nop >= c.vocab)) return SA_ERR_ARG;
+            if (b == a && !((flags[st] & 1) && ends) && !(flags[st] & 2)) return SA_ERR_ARG;      // a state without an allowed id
+            for (int e = a; e < b; ++e) {
+                if (edge_tok[e] < 0 || edge_tok[e] >= c.vocab || edge_next[e] < 0 || edge_next[e] >= n_states) return SA_ERR_ARG;
+                if (e > a && edge_tok[e] <= edge_tok[e - 1]) return SA_ERR_ARG;
+            }
+        }
+        int rc;
+        if (!slot_lex_state) {                              // first tables: the per-slot state and its staging, or nothing
+            int* mem = nullptr;
+            Stager st;
+            hipEvent_t ev = nullptr;
+            SA_HIP(hipMalloc((void**)&mem, (size_t)c.max_slots * sizeof(int)));
+            rc = st.init((size_t)c.max_slots * 2 * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (!rc) rc = (int)hipMemset(mem, 0xff, (size_t)c.max_slots * sizeof(int));      // every slot -1, whatever fails below
+            if (rc) { if (ev) (void)hipEventDestroy(ev); st.destroy(); (void)hipFree(mem); return rc; }
+            st_lex = st; lex_ev = ev; slot_lex_state = mem;
+        }
+        if (!mask_dyn_rows && (rc = grow_mask_arena(s))) return rc;
+        if (n_states > lex_cap_states || n_edges > lex_cap_edges) {      // grow: powers of two, so a call's tables mostly fit the last call's
+            int cs = std::max(lex_cap_states, 1024), ce = std::max(lex_cap_edges, 1024);
+            while (cs < n_states) cs *= 2;
+            while (ce < n_edges) ce *= 2;
+            Carve cv;
+            (void)cv.take(((size_t)cs + 1) * sizeof(int));
+            const size_t o_tok = cv.take((size_t)ce * sizeof(int)), o_next = cv.take((size_t)ce * sizeof(int)), o_flags = cv.take((size_t)cs);
+            DevBlock nb;
+            if ((rc = nb.alloc(cv.off, cv.off))) return rc;
+            SA_HIP(hipDeviceSynchronize());                 // nothing in flight reads the old tables or their staging copy
+            drop_graphs();                                  // captured steps hold the old addresses
+            lex_arena.release();
+            lex_arena = nb;
+            lex_pending = false;
+            lex_o_tok = o_tok; lex_o_next = o_next; lex_o_flags = o_flags;
+            lex_edge_off = reinterpret_cast<int*>(nb.dev);
+            lex_edge_tok = reinterpret_cast<int*>(nb.dev + o_tok);
+            lex_edge_next = reinterpret_cast<int*>(nb.dev + o_next);
+            lex_flags = reinterpret_cast<uint8_t*>(nb.dev + o_flags);
+            lex_cap_states = cs; lex_cap_edges = ce;
+            if (lex_states > 0) lex_states = 0;             // (the old tables are gone: off until the new ones are on their way)
+        }
+        if (lex_pending) { (void)hipEventSynchronize(lex_ev); lex_pending = false; }
+        char* hb = lex_arena.host;
+        memcpy(hb, edge_off, ((size_t)n_states + 1) * sizeof(int));
+        if (n_edges) {
+            memcpy(hb + lex_o_tok, edge_tok, (size_t)n_edges * sizeof(int));
+            memcpy(hb + lex_o_next, edge_next, (size_t)n_edges * sizeof(int));
+        }
+        memcpy(hb + lex_o_flags, flags, (size_t)n_states);
+        SA_HIP(hipMemcpyAsync(lex_edge_off, hb, ((size_t)n_states + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (n_edges) {
+            SA_HIP(hipMemcpyAsync(lex_edge_tok, hb + lex_o_tok, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
+            SA_HIP(hipMemcpyAsync(lex_edge_next, hb + lex_o_next, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
+        }
+        SA_HIP(hipMemcpyAsync(lex_flags, hb + lex_o_flags, (size_t)n_states, hipMemcpyHostToDevice, s));
+        SA_HIP(hipEventRecord(lex_ev, s));
+        lex_pending = true;
+        SA_HIP(hipMemsetAsync(slot_lex_state, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        if (lex_states == 0 || nop != lex_nop) drop_graphs();      // on <-> off, and the by-value no-output id of the step launch
+        lex_states = n_states;
+        lex_nop = nop;
+        return SA_OK;
+    }
+    // The mask arena with max_slots dynamic rows behind the static ones: a new block of the same layout, the old contents copied in
+    // stream order. Called once per handle, from the set_lexicon that switches the feature on for the first time, which drops every
+    // captured step anyway; no address moves after it.
+    int grow_mask_arena(hipStream_t s) {
+        const size_t words = mask_words(), table_bytes = (size_t)SA_MAX_TOKEN_MASKS * words * sizeof(uint32_t),
+                     dyn_bytes = (size_t)c.max_slots * words * sizeof(uint32_t);
+        Carve cv;
+        const size_t o_slot = cv.take((size_t)c.max_slots * sizeof(int)), o_table = cv.take(table_bytes + dyn_bytes);
+        char* mem = nullptr;
+        SA_HIP(hipMalloc((void**)&mem, cv.off));
+        int rc = (int)hipMemcpyAsync(mem + o_slot, slot_mask, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s);
+        if (!rc) rc = (int)hipMemcpyAsync(mem + o_table, mask_table, table_bytes, hipMemcpyDeviceToDevice, s);
+        if (!rc) rc = (int)hipMemsetAsync(mem + o_table + table_bytes, 0, dyn_bytes, s);
+        if (!rc) rc = (int)hipDeviceSynchronize();          // the copies are done and nothing in flight reads the old block
+        if (rc) { (void)hipFree(mem); return rc; }
+        drop_graphs();
+        (void)hipFree(mask_arena);
+        mask_arena = mem;
+        slot_mask = reinterpret_cast<int*>(mem + o_slot);
+        mask_table = reinterpret_cast<uint32_t*>(mem + o_table);
+        mask_dyn_rows = true;
+        return SA_OK;
+    }
+    int lexicon_off(hipStream_t s) {
+        if (lex_states == 0) return SA_OK;
+        drop_graphs();
+        lex_states = 0;
+        SA_HIP(hipMemsetAsync(slot_lex_state, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        return SA_OK;
+    }
+    // Start states of the slots about to be prefilled (-1 = no lexicon; the slot's mask id and row are then left alone).
+    int set_slot_lexicon(const int32_t* slots, const int32_t* states, int n, hipStream_t s) override {
+        if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
+        if (n > c.max_slots) return SA_ERR_ARG;
+        if (lex_states == 0) return SA_ERR_STATE;
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] < 0 || slots[i] >= c.max_slots || states[i] < -1 || states[i] >= lex_states) return SA_ERR_ARG;
+            if (seen[slots[i]]) return SA_ERR_ARG;
+            seen[slots[i]] = 1;
+        }
+        st_lex.begin();
+        const int* ds = st_lex.put(slots, n);
+        const int* dt = st_lex.put(states, n);
+        if (!ds || !dt) return SA_ERR_NOMEM;
+        int rc = st_lex.flush(s);
+        if (rc) return rc;
+        return launch_lexicon_start(lex_args(), ds, dt, n, s);
+    }
+    int copy_lexicon_states(int32_t* dst, hipStream_t s) override {
+        if (!slot_lex_state) return SA_ERR_STATE;
+        SA_HIP(hipMemcpyAsync(dst, slot_lex_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
         return SA_OK;
     }
 
@@ -1229,6 +1399,8 @@ struct RecModel : RecBase {
         if (pat_states > 0)                                   // empty while patterns are off: the heads do what they always did
             ha.ph = PatternHead{pat_tok_class, pat_next_state, pat_state_mask, SA_MAX_PATTERN_CLASSES, c.vocab, slot_state, slot_mask};
         if ((rc = launch_head<T>(ha, mx(), s))) return rc;
+        // lexicon-guided decoding: behind the token, every lexicon slot's own mask row becomes its next state's allowed set (lexicon.h)
+        if (lex_states > 0 && (rc = launch_lexicon_step(lex_args(), d_row_slot, out_token + so, rows, s))) return rc;
         return combine();
     }
 

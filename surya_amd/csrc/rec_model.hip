@@ -297,6 +297,20 @@ int surya_rec_copy_slot_states(surya_rec* h, int32_t* dst, void* stream) {
     return h->impl->copy_slot_states(dst, (hipStream_t)stream);
 }
 
+int surya_rec_set_lexicon(surya_rec* h, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, const uint8_t* state_flags,
+                          int n_states, int n_edges, int no_output_token_id, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_lexicon(edge_off, edge_tok, edge_next, state_flags, n_states, n_edges, no_output_token_id, (hipStream_t)stream);
+}
+int surya_rec_set_slot_lexicon(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream) {
+    if (!h || (n > 0 && (!slots || !start_states))) return SA_ERR_ARG;
+    return h->impl->set_slot_lexicon(slots, start_states, n, (hipStream_t)stream);
+}
+int surya_rec_copy_lexicon_states(surya_rec* h, int32_t* dst, void* stream) {
+    if (!h || !dst) return SA_ERR_ARG;
+    return h->impl->copy_lexicon_states(dst, (hipStream_t)stream);
+}
+
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
 static __global__ void iota_kernel(int* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -706,6 +720,24 @@ int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* f
                          int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream) {
     const sa::RecKvForkOp a{kcache, vcache, fork_src, base, len, rows, layers, slots, kv_heads, max_kv_len, head_dim};
     return rec_dispatch(dtype, sa::REC_OP_KV_FORK, &a, stream);
+}
+static int lexicon_op_args(const surya_rec_lexicon_args* g, sa::LexiconArgs& a) {
+    if (!g || !g->edge_off || !g->edge_tok || !g->edge_next || !g->state_flags || !g->table || !g->slot_state || !g->slot_mask || g->words <= 0 ||
+        g->row_base < 0 || g->vocab <= 0 || g->vocab > g->words * 32)
+        return SA_ERR_ARG;
+    a = sa::LexiconArgs{g->edge_off, g->edge_tok, g->edge_next, g->state_flags, g->table, g->words, g->row_base, g->slot_state, g->slot_mask,
+                        g->vocab, g->eos_id, g->pad_id, g->nop_id};
+    return SA_OK;
+}
+int surya_op_rec_lexicon_start(const surya_rec_lexicon_args* args, const int32_t* slots, const int32_t* states, int n, void* stream) {
+    sa::LexiconArgs a;
+    if (lexicon_op_args(args, a) || n < 0 || (n > 0 && (!slots || !states))) return SA_ERR_ARG;
+    return sa::launch_lexicon_start(a, slots, states, n, (hipStream_t)stream);
+}
+int surya_op_rec_lexicon_step(const surya_rec_lexicon_args* args, const int32_t* row_slot, const int32_t* out_token, int rows, void* stream) {
+    sa::LexiconArgs a;
+    if (lexicon_op_args(args, a) || rows < 0 || (rows > 0 && (!row_slot || !out_token))) return SA_ERR_ARG;
+    return sa::launch_lexicon_step(a, row_slot, out_token, rows, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -31,7 +31,8 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     return m
 
 
-_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched")
+_LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched",
+                "lexicon_index")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -42,7 +43,8 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     list of TextChar): the object state validation would produce, without walking the character list again."""
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
-                         "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None})
+                         "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None,
+                         "lexicon_index": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -106,6 +108,19 @@ def set_pattern_matched(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
         if st >= 0:
             line.pattern_matched = bool(tables.matched(st, tokens))
             line.__pydantic_fields_set__.add("pattern_matched")
+    return line
+
+
+def set_lexicon_index(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
+    """line.lexicon_index for a line read under a lexicon (flat["lexicon_tables"], flat["lexicon_starts"] by sorted position): the host
+    replay of the automaton over the line's tokens (not a comparison of the cleaned text) -- the entry's index in the line's own list
+    iff the line ended in a terminal state, else -1. A line without a lexicon keeps None."""
+    tables = flat.get("lexicon_tables")
+    if tables is not None:
+        st = int(flat["lexicon_starts"][sorted_pos])
+        if st >= 0:
+            line.lexicon_index = int(tables.entry_of(tables.lexicon_of_start(st), tokens))
+            line.__pydantic_fields_set__.add("lexicon_index")
     return line
 
 
@@ -241,6 +256,10 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
+    if flat.get("lexicon_tables") is not None:        # a call with lexicons: likewise (it may hold pattern lines too)
+        line = assemble_line(proc, {**flat, "lexicon_tables": None}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
+                             bbox_size, alts=alts)
+        return set_lexicon_index(flat, sorted_pos, tokens, line)
     if flat.get("pattern_tables") is not None:        # a call with patterns: the plain line, then the host replay of its automaton
         line = assemble_line(proc, {**flat, "pattern_tables": None}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
                              bbox_size, alts=alts)
@@ -280,6 +299,9 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    if flat.get("lexicon_tables") is not None:
+        out = assemble_batch(proc, {**flat, "lexicon_tables": None}, items, drop_repeated_text, return_words, bbox_size)
+        return [set_lexicon_index(flat, it[0], it[2], line) for it, line in zip(items, out)]
     if flat.get("pattern_tables") is not None:
         out = assemble_batch(proc, {**flat, "pattern_tables": None}, items, drop_repeated_text, return_words, bbox_size)
         return [set_pattern_matched(flat, it[0], it[2], line) for it, line in zip(items, out)]

@@ -44,6 +44,14 @@ class DeviceLoop:
     out, before the mask table, also after an exception. Without "pattern_tables" set_patterns / set_slot_patterns are never called
     -- a model without them works. Not with beam search or forced decoding.
 
+    Lexicons: the dict handed to `run` may also carry "lexicon_tables" (recognition/lexicon.py::LexiconTables; uploaded once, behind the
+    mask table, which must have at least one row) and every admitted dict "lexicon_starts" (one automaton state per prompt, -1 = no
+    lexicon). A line's start state is set on whatever slot the line is prefilled into, behind its mask id (and its pattern state: a
+    line follows at most one of the two); from then on the model rewrites the slot's own mask row itself, token by token, on the
+    device. The lexicon is switched off on the way out, before patterns and the mask table, also after an exception. Without
+    "lexicon_tables" set_lexicon / set_slot_lexicon are never called -- a model without them works. Not with beam search or forced
+    decoding.
+
     Alternatives (`alternatives=True`): the model reports the SA_MAX_ALTERNATIVES most likely tokens of every step; the loop keeps
     them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
     line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
@@ -118,6 +126,8 @@ class DeviceLoop:
         self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
         self.line_state = np.zeros(0, np.int64)                # id -> start state of the line's pattern, -1 = none
         self.n_states = 0                                      # states of the automaton uploaded for this loop (0: patterns are off)
+        self.line_lex = np.zeros(0, np.int64)                  # id -> start state of the line's lexicon, -1 = none
+        self.n_lex_states = 0                                  # states of the lexicon automaton uploaded for this loop (0: off)
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
@@ -176,6 +186,11 @@ class DeviceLoop:
         assert st.shape == (m,) and int(st.min()) >= -1 and int(st.max()) < self.n_states, \
             "start states must name states of the call's pattern tables"
         self.line_state = np.concatenate([self.line_state, st])
+        lx = d.get("lexicon_starts")
+        lx = np.full(m, -1, np.int64) if lx is None else np.asarray(lx, np.int64)
+        assert lx.shape == (m,) and int(lx.min()) >= -1 and int(lx.max()) < self.n_lex_states, \
+            "lexicon start states must name states of the call's lexicon tables"
+        self.line_lex = np.concatenate([self.line_lex, lx])
         self.queue.extend(range(base, base + m))
 
     def tiles_of(self, first_id, last_id):
@@ -396,6 +411,8 @@ class DeviceLoop:
             self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
         if self.n_states:
             self.model.set_slot_patterns(slots, self.line_state[take].tolist())   # behind the mask ids: a start state names its own row
+        if self.n_lex_states:
+            self.model.set_slot_lexicon(slots, self.line_lex[take].tolist())      # likewise: the slot's own row becomes its mask id
         if self.forced:
             self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
         self._prefill(take, grids, prompt_ids, slots)
@@ -444,6 +461,8 @@ class DeviceLoop:
         table = None if prep is None else prep.get("token_masks")
         pattern_tables = None if prep is None else prep.get("pattern_tables")
         assert pattern_tables is None or not (self.beam or self.forced), "patterns exclude beam search and forced decoding"
+        lexicon_tables = None if prep is None else prep.get("lexicon_tables")
+        assert lexicon_tables is None or not (self.beam or self.forced), "lexicons exclude beam search and forced decoding"
 
         def masks_on():
             m.set_token_masks(table)                   # once per call: identical masks were merged by the caller
@@ -452,13 +471,18 @@ class DeviceLoop:
         def patterns_on():
             m.set_patterns(pattern_tables)             # behind the mask table: the states name its rows
             self.n_states = int(pattern_tables.n_states)
+
+        def lexicon_on():
+            m.set_lexicon(lexicon_tables)              # behind the mask table too: every slot gets a row of its own behind its rows
+            self.n_lex_states = int(lexicon_tables.n_states)
         # (requested, switch on, switch off): switched on in this order, off in reverse on the way out, also after an exception, so the
         # next call starts on the greedy, unmasked kernels without candidates. What was not requested never touches its entry points.
         modes = [(self.beam, lambda: m.set_beam(self.beam, self.nop), lambda: m.set_beam(None)),
                  (self.forced, lambda: m.set_forced(True), lambda: m.set_forced(False)),      # (at most one of the first three: __init__)
                  (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False)),
                  (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None)),
-                 (pattern_tables is not None, patterns_on, lambda: m.set_patterns(None))]
+                 (pattern_tables is not None, patterns_on, lambda: m.set_patterns(None)),
+                 (lexicon_tables is not None, lexicon_on, lambda: m.set_lexicon(None))]
         with ExitStack() as undo:
             for wanted, on, off in modes:
                 if wanted:

@@ -100,6 +100,7 @@ class HipRecModel:
         self.mx_weights = None
         self.n_token_masks = 0
         self.n_pattern_states = 0
+        self.n_lexicon_states = 0
         self.alternatives = False
         self.forced = False
         self.beam = 0
@@ -149,14 +150,14 @@ class HipRecModel:
         words = (self.vocab + 31) // 32
         if masks is None or len(masks) == 0:
             L.check(self.lib.surya_rec_set_token_masks(self.handle, None, C.c_int(0), self._stream), "surya_rec_set_token_masks")
-            self.n_token_masks = self.n_pattern_states = 0          # (a new or dropped table switches patterns off)
+            self.n_token_masks = self.n_pattern_states = self.n_lexicon_states = 0      # (a new or dropped table switches patterns and the lexicon off)
             return
         m = np.ascontiguousarray(np.asarray(masks, np.uint32))
         if m.ndim != 2 or m.shape[1] != words:
             raise ValueError(f"token masks must be [n, {words}] uint32 for a vocabulary of {self.vocab}, got {m.shape}")
         L.check(self.lib.surya_rec_set_token_masks(self.handle, L.np_ptr(m, C.c_uint32), C.c_int(m.shape[0]), self._stream),
                 "surya_rec_set_token_masks")
-        self.n_token_masks, self.n_pattern_states = int(m.shape[0]), 0
+        self.n_token_masks, self.n_pattern_states, self.n_lexicon_states = int(m.shape[0]), 0, 0
 
     def set_slot_masks(self, slots, mask_ids):
         """Mask id (row of the table, -1 = unconstrained) of the slots about to be prefilled; a slot keeps it until it is set again."""
@@ -197,6 +198,42 @@ class HipRecModel:
         """Sync; the automaton state of every slot, int32 [max_slots] (-1 = no pattern). A test hook, like last_logits."""
         buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
         L.check(self.lib.surya_rec_copy_slot_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_slot_states")
+        return buf.cpu().numpy()
+
+    def set_lexicon(self, tables):
+        """The call's lexicon automaton (surya_rec_set_lexicon; recognition/lexicon.py::LexiconTables, or anything with its edge_off /
+        edge_tok / edge_next / state_flags arrays and `nop`), uploaded behind the token-mask table: every slot then owns a row of that
+        table, which the device rewrites behind each token. None switches the feature off. New tables set every slot back to "no
+        lexicon"; set_slot_lexicon names the start states of the slots about to be prefilled."""
+        if tables is None:
+            L.check(self.lib.surya_rec_set_lexicon(self.handle, None, None, None, None, C.c_int(0), C.c_int(0), C.c_int(-1), self._stream),
+                    "surya_rec_set_lexicon")
+            self.n_lexicon_states = 0
+            return
+        eo = np.ascontiguousarray(np.asarray(tables.edge_off, np.int32))
+        et = np.ascontiguousarray(np.asarray(tables.edge_tok, np.int32))
+        en = np.ascontiguousarray(np.asarray(tables.edge_next, np.int32))
+        fl = np.ascontiguousarray(np.asarray(tables.state_flags, np.uint8))
+        if eo.ndim != 1 or fl.shape != (len(eo) - 1,) or et.ndim != 1 or en.shape != et.shape:
+            raise ValueError(f"lexicon tables must be edge_off [n_states + 1], edge_tok / edge_next [n_edges], state_flags [n_states], got "
+                             f"{eo.shape}, {et.shape}, {en.shape}, {fl.shape}")
+        L.check(self.lib.surya_rec_set_lexicon(self.handle, L.np_ptr(eo), L.np_ptr(et), L.np_ptr(en), L.np_ptr(fl, C.c_uint8), C.c_int(len(fl)),
+                                               C.c_int(len(et)), C.c_int(int(tables.nop)), self._stream), "surya_rec_set_lexicon")
+        self.n_lexicon_states = int(len(fl))
+
+    def set_slot_lexicon(self, slots, start_states):
+        """Start state (-1 = no lexicon: the slot keeps its mask id) of the slots about to be prefilled, after set_slot_masks; a state
+        >= 0 makes the slot's own row its mask id. The slot's state and row then follow its tokens on the device."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int32))
+        t = np.ascontiguousarray(np.asarray(start_states, np.int32))
+        assert s.shape == t.shape and s.ndim == 1
+        L.check(self.lib.surya_rec_set_slot_lexicon(self.handle, L.np_ptr(s), L.np_ptr(t), C.c_int(len(s)), self._stream),
+                "surya_rec_set_slot_lexicon")
+
+    def copy_lexicon_states(self) -> np.ndarray:
+        """Sync; the lexicon state of every slot, int32 [max_slots] (-1 = no lexicon). A test hook, like slot_states."""
+        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
+        L.check(self.lib.surya_rec_copy_lexicon_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_lexicon_states")
         return buf.cpu().numpy()
 
     def set_alternatives(self, on: bool):

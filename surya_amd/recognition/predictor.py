@@ -115,15 +115,67 @@ def per_image_lists(arg, name, n_images) -> list:
     return list(arg)
 
 
+class LexiconKey(tuple):
+    """One lexicon of a call, hashable: its entries in order. (A type of its own, so that a list per line is told from a lexicon.)"""
+
+
+def _as_lexicon(x):
+    """x as a LexiconKey if it is a lexicon -- a non-empty list / tuple of str -- else None."""
+    if isinstance(x, (list, tuple)) and len(x) > 0 and all(isinstance(e, str) for e in x):
+        return LexiconKey(x)
+    return None
+
+
+def per_image_lexicons(arg, n_images) -> list:
+    """A `lexicon` argument as one entry per image: None, a LexiconKey, or a list with one None / LexiconKey per line. The argument is a
+    list of str (one lexicon for every line), or a list with one entry per image: None, a list of str, or a list per line of None /
+    list of str."""
+    if arg is None:
+        return [None] * n_images
+    if isinstance(arg, str) or not isinstance(arg, (list, tuple)):
+        raise TypeError(f"lexicon must be a list of str or a list with one entry per image, got {type(arg).__name__}")
+    if len(arg) == 0:
+        raise ValueError("lexicon is an empty list: a lexicon needs at least one entry")
+    whole = _as_lexicon(arg)
+    if whole is not None:
+        return [whole] * n_images
+    if len(arg) != n_images:
+        raise ValueError(f"lexicon has {len(arg)} entries for {n_images} images")
+    out = []
+    for i, e in enumerate(arg):
+        if e is None:
+            out.append(None)
+            continue
+        if isinstance(e, str) or not isinstance(e, (list, tuple)):
+            raise TypeError("an entry of lexicon is None, a list of str, or a list of None / list of str per line")
+        key = _as_lexicon(e)
+        if key is not None:
+            out.append(key)
+            continue
+        lines = []
+        for x in e:
+            k = None if x is None else _as_lexicon(x)
+            if x is not None and k is None:
+                if isinstance(x, (list, tuple)) and len(x) == 0:
+                    raise ValueError(f"image {i}: a lexicon is an empty list: it needs at least one entry")
+                raise TypeError("an entry of lexicon is None, a list of str, or a list of None / list of str per line")
+            lines.append(k)
+        out.append(lines)
+    return out
+
+
 class LineConstraints:
     """The allowlist / blocklist / pattern arguments of one call, resolved: `table` holds the call's distinct token masks (MaskTable:
     identical sets are merged), `per_image[i]` the mask id of every line of image i (an int) or one id per line (a list). `lines_known`
     is False on the detector paths, where the per-line form cannot be matched to lines that do not exist yet. With patterns:
     `patterns` is the call's PatternTables (recognition/pattern.py), compiled once, whose states' allowed sets are further rows of
     `table`, and `per_image_state[i]` the start state of image i's lines in the same two forms (-1 = no pattern). A line with a
-    pattern has mask id -1: its start state names its row."""
+    pattern has mask id -1: its start state names its row. With lexicons: `lexicons` is the call's LexiconTables
+    (recognition/lexicon.py), compiled once, and `per_image_lex[i]` the lexicon start state of image i's lines in the same two forms
+    (-1 = no lexicon). A line takes a lexicon, a pattern, or an allowlist / blocklist, never two. A lexicon needs a mask table on the
+    device, so a call whose only constraints are lexicons gets one row that allows everything and that no line names."""
 
-    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None, pattern=None):
+    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None, pattern=None, lexicon=None):
         from .tokenizer import MaskTable
         self.table = MaskTable(tokenizer, vocab_size, limit)
         allow, block = per_image_lists(allowlist, "allowlist", n_images), per_image_lists(blocklist, "blocklist", n_images)
@@ -157,6 +209,39 @@ class LineConstraints:
             start = {z: s for z, s in zip(self.patterns.patterns, self.patterns.starts)}
             start[None] = -1
             self.per_image_state = [[start[z] for z in p] if isinstance(p, list) else start[p] for p in per_image_pat]
+        self.lexicons, self.per_image_lex = None, None
+        lex = per_image_lexicons(lexicon, n_images)
+        if any(x is not None for x in lex):
+            self._add_lexicons(tokenizer, lex, per_image_pat, line_counts, vocab_size)
+
+    def _add_lexicons(self, tokenizer, lex, per_image_pat, line_counts, vocab_size):
+        for i, (lx, ids, p) in enumerate(zip(lex, self.per_image, per_image_pat)):
+            if lx is None:
+                continue
+            if not any(isinstance(x, list) for x in (lx, ids, p)):
+                if ids != -1 or p is not None:
+                    raise ValueError(f"image {i}: a line takes a lexicon, a pattern or an allowlist / blocklist, never two")
+                continue
+            if line_counts is None:
+                raise ValueError("a per-line lexicon needs bboxes or polygons: with det_predictor the lines are not known yet")
+            n = line_counts[i]
+            lx, ids, p = (x if isinstance(x, list) else [x] * n for x in (lx, ids, p))
+            if len(lx) != n:
+                raise ValueError(f"image {i} has {n} lines but its lexicon entry has {len(lx)}")
+            for j, (x, y, z) in enumerate(zip(lx, ids, p)):
+                if x is not None and (y != -1 or z is not None):
+                    raise ValueError(f"image {i}, line {j}: a line takes a lexicon, a pattern or an allowlist / blocklist, never two")
+        distinct = list(dict.fromkeys(k for x in lex for k in (x if isinstance(x, list) else [x]) if k is not None))
+        from .lexicon import compile_lexicons
+        self.lexicons = compile_lexicons(tokenizer, distinct, vocab_size)
+        start = {k: s for k, s in zip(distinct, self.lexicons.starts)}
+        start[None] = -1
+        self.per_image_lex = [[start[k] for k in x] if isinstance(x, list) else start[x] for x in lex]
+        if len(self.table) == 0:                              # the engine keeps lexicon rows behind a mask table: one row nobody names
+            V = tokenizer.vocab_size if vocab_size is None else int(vocab_size)
+            bits = np.zeros((V + 31) // 32 * 32, bool)
+            bits[:V] = True
+            self.table.add_row(np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32))
 
     def __bool__(self):
         return len(self.table) > 0
@@ -171,6 +256,10 @@ class LineConstraints:
     def line_states(self, slice_map) -> list:
         """One start state per line (-1 = no pattern), like line_ids; a call with patterns only."""
         return self.line_ids(slice_map, self.per_image_state)
+
+    def line_lexicon_starts(self, slice_map) -> list:
+        """One lexicon start state per line (-1 = no lexicon), like line_ids; a call with lexicons only."""
+        return self.line_ids(slice_map, self.per_image_lex)
 
 
 class AssemblyHandover(ThreadPoolExecutor):
@@ -388,6 +477,8 @@ class RecognitionPredictor(BasePredictor):
             prep.update(token_masks=flat["token_masks"], mask_ids=flat["mask_ids"])
         if flat.get("pattern_tables") is not None:            # ... and with patterns the call's automaton and one start state per line
             prep.update(pattern_tables=flat["pattern_tables"], start_states=flat["start_states"])
+        if flat.get("lexicon_tables") is not None:            # ... and with lexicons theirs
+            prep.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=flat["lexicon_starts"])
         if flat.get("forced_ids") is not None:                # align(): one forced id list per line
             prep["forced_ids"] = flat["forced_ids"]
         return prep
@@ -451,6 +542,8 @@ class RecognitionPredictor(BasePredictor):
             local.update(token_masks=flat["token_masks"], mask_ids=[flat["mask_ids"][i] for i in mine])
         if flat.get("pattern_tables") is not None:            # ... and so do the start states
             local.update(pattern_tables=flat["pattern_tables"], start_states=[flat["start_states"][i] for i in mine])
+        if flat.get("lexicon_tables") is not None:
+            local.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=[flat["lexicon_starts"][i] for i in mine])
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
         alts = None
         if mine:
@@ -530,6 +623,17 @@ class RecognitionPredictor(BasePredictor):
         budget, the repeat rule or the no-output token reports False and keeps its partial text; None without a pattern. Confidences
         are softmax values over the set allowed at that position. `top_k` works with it. ValueError with `beam_width`, and in `align`.
 
+        `self.lexicon` (an attribute like `pattern`; None = off; a list of str for every line of the calls that follow, or one entry per
+        image of the call: None, a list of str, or a list with one None / list of str per bbox / polygon) reads a line as exactly one
+        entry of a word list -- a city, a surname, a product code, one of the 40 000 postal codes -- with re.fullmatch semantics. Entries
+        are taken verbatim: no case folding, no Unicode normalisation, no stripping; duplicates are allowed. The call's lexicons are
+        compiled once into a minimised automaton (recognition/lexicon.py; 10^5 entries are fine) that every line follows on the device,
+        with no host round trip. A line takes a lexicon, a pattern, or an allowlist / blocklist, never two; a call may mix all of them
+        with unconstrained lines. `TextLine.lexicon_index` is the index, in the line's own list, of the entry read (the first for a
+        duplicate); -1 for a line cut by the token budget, the repeat rule or the no-output token, which keeps its partial text, a
+        proper prefix of an entry; None without a lexicon. `top_k` works with it. ValueError, before any device work, with `beam_width`,
+        in `align`, for an empty list, an empty entry and an entry the model's vocabulary cannot write.
+
         `self.beam_width` (an attribute like `top_k`; None = greedy, else 2..4): beam search on the device. Every TextLine carries
         `hypotheses`, its up to beam_width best readings as LineHypothesis(text, confidence, log_prob, finished, chars) -- finished
         readings by log_prob descending, then the ones the token budget or the repeat rule cut -- each assembled like a line
@@ -548,6 +652,9 @@ class RecognitionPredictor(BasePredictor):
         pattern = self.pattern
         if pattern is not None and beam is not None:
             raise ValueError("pattern is not available with beam_width: a beam would have to inherit its parent's automaton state")
+        lexicon = self.lexicon
+        if lexicon is not None and beam is not None:
+            raise ValueError("lexicon is not available with beam_width: a beam would have to inherit its parent's automaton state and row")
         # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
         # page-sharded path and by stand-ins and read it from here)
         saved_k, self._top_k = self._top_k, top_k
@@ -555,7 +662,7 @@ class RecognitionPredictor(BasePredictor):
         try:
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                                        pattern)
+                                        pattern, lexicon)
         finally:
             self._top_k, self._beam = saved_k, saved_b
             if top_k is not None:
@@ -597,6 +704,8 @@ class RecognitionPredictor(BasePredictor):
         do not apply to an aligned call, and a set `pattern` raises ValueError: the text is given, there is nothing to constrain."""
         if self.pattern is not None:
             raise ValueError("pattern does not apply to align(): forced decoding reads no allowed set (set pattern = None)")
+        if self.lexicon is not None:
+            raise ValueError("lexicon does not apply to align(): forced decoding reads no allowed set (set lexicon = None)")
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         if self.shard_lines or self.shard_pages or self.process_group is not None:
@@ -663,24 +772,27 @@ class RecognitionPredictor(BasePredictor):
     beam_width: int | None = None     # readings per line (2..4), None = greedy: RecognitionPredictor.beam_width = 3, or on an instance
     _beam = None                      # the running call's validated beam_width (see __call__)
     pattern = None                    # regex per call / image / line (see __call__), None = off: set on an instance, e.g. pred.pattern = r"\d+"
+    lexicon = None                    # word list per call / image / line (see __call__), None = off: pred.lexicon = ["Alabama", "Alaska", ...]
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
 
     def _call_gc_paused(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                        pattern=None):
+                        pattern=None, lexicon=None):
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
             # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
             lists = {} if allowlist is None and blocklist is None else {"allowlist": allowlist, "blocklist": blocklist}
             if pattern is not None:
                 lists["pattern"] = pattern
+            if lexicon is not None:
+                lists["lexicon"] = lexicon
             return self._call(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                               bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
 
-    def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None):
-        """The call's LineConstraints, or None for a call without lists or patterns (or whose entries are all None)."""
-        if allowlist is None and blocklist is None and pattern is None:
+    def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None, lexicon=None):
+        """The call's LineConstraints, or None for a call without lists, patterns or lexicons (or whose entries are all None)."""
+        if allowlist is None and blocklist is None and pattern is None and lexicon is None:
             return None
         given = polygons if polygons is not None else bboxes
         if given is not None and len(given) != len(images):
@@ -688,12 +800,13 @@ class RecognitionPredictor(BasePredictor):
         counts = None if given is None else [len(g) for g in given]
         from .. import _lib as L
         cons = LineConstraints(self.processor.ocr_tokenizer, allowlist, blocklist, len(images), counts,
-                               vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS, pattern=pattern)
+                               vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS, pattern=pattern,
+                               lexicon=lexicon)
         return cons if cons else None
 
     def _call(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images, bboxes,
               polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None,
-              pattern=None) -> List[OCRResult]:
+              pattern=None, lexicon=None) -> List[OCRResult]:
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         allowed = self.tasks.keys()
@@ -708,7 +821,7 @@ class RecognitionPredictor(BasePredictor):
         if highres_images is not None:
             assert len(images) == len(highres_images), "You need to pass in one highres image for each image"
         highres_images = convert_if_not_rgb(highres_images) if highres_images is not None else [None] * len(images)
-        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons, pattern)
+        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons, pattern, lexicon)
 
         if bboxes is None and polygons is None:
             assert det_predictor is not None, (
@@ -719,6 +832,8 @@ class RecognitionPredictor(BasePredictor):
                     lists = {} if cons is None else {"allowlist": allowlist, "blocklist": blocklist}
                     if cons is not None and cons.patterns is not None:
                         lists["pattern"] = pattern
+                    if cons is not None and cons.lexicons is not None:
+                        lists["lexicon"] = lexicon
                     return self._call_page_sharded(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
                                                    highres_images, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
             if self._can_stream(det_predictor):
@@ -743,6 +858,9 @@ class RecognitionPredictor(BasePredictor):
             if cons.patterns is not None:
                 flat["pattern_tables"], flat["start_states"] = cons.patterns, cons.line_states(flat["slice_map"])
                 sorted_keys += ("start_states",)
+            if cons.lexicons is not None:
+                flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, cons.line_lexicon_starts(flat["slice_map"])
+                sorted_keys += ("lexicon_starts",)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
@@ -785,7 +903,8 @@ class RecognitionPredictor(BasePredictor):
     gather_page_results: bool = True
 
     def _call_page_sharded(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                           sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None, pattern=None) -> list:
+                           sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None, pattern=None,
+                           lexicon=None) -> list:
         from .. import dist as sdist
         group = self.process_group
         rank, world = sdist.world_info(group)
@@ -805,6 +924,10 @@ class RecognitionPredictor(BasePredictor):
                      "blocklist": [per_image_lists(blocklist, "blocklist", n)[i] for i in mine]}
         if pattern is not None:                               # a rank compiles the patterns of its own pages
             lists["pattern"] = [per_image_lists(pattern, "pattern", n)[i] for i in mine]
+        if lexicon is not None:                               # ... and the lexicons (back in argument form: lists, not keys)
+            per = per_image_lexicons(lexicon, n)
+            lists["lexicon"] = [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list)
+                                else list(per[i]) for i in mine]
         try:
             hr = [highres_images[i] for i in mine]
             local = self._call([images[i] for i in mine], [task_names[i] for i in mine], det_predictor, detection_batch_size,
@@ -869,6 +992,9 @@ class RecognitionPredictor(BasePredictor):
         with_patterns = cons is not None and cons.patterns is not None
         if with_patterns:                                     # assembly replays a line's automaton from its start state
             flat["pattern_tables"], flat["start_states"] = cons.patterns, []
+        with_lexicons = cons is not None and cons.lexicons is not None
+        if with_lexicons:
+            flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, []
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
@@ -883,7 +1009,7 @@ class RecognitionPredictor(BasePredictor):
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
-                    pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all = [], [], [], [], [], [], []
+                    pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all, lex_all = [], [], [], [], [], [], [], []
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
@@ -895,6 +1021,8 @@ class RecognitionPredictor(BasePredictor):
                             masks_all.extend([cons.per_image[page]] * len(polygons))
                             if with_patterns:
                                 states_all.extend([cons.per_image_state[page]] * len(polygons))
+                            if with_lexicons:
+                                lex_all.extend([cons.per_image_lex[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -913,11 +1041,14 @@ class RecognitionPredictor(BasePredictor):
                     flat["input_text"].extend([None] * len(order))
                     if with_patterns:
                         flat["start_states"].extend(states_all[i] for i in order)
+                    if with_lexicons:
+                        flat["lexicon_starts"].extend(lex_all[i] for i in order)
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
                            "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts},
                            "mask_ids": [masks_all[i] for i in order] if cons is not None else None,
-                           "start_states": [states_all[i] for i in order] if with_patterns else None})
+                           "start_states": [states_all[i] for i in order] if with_patterns else None,
+                           "lexicon_starts": [lex_all[i] for i in order] if with_lexicons else None})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -947,6 +1078,8 @@ class RecognitionPredictor(BasePredictor):
                         first["token_masks"] = cons.table.array()      # the whole call's table up front: chunks carry row ids only
                         if with_patterns:
                             first["pattern_tables"] = cons.patterns
+                        if with_lexicons:
+                            first["lexicon_tables"] = cons.lexicons
                     self.generate(first, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...

@@ -100,14 +100,19 @@ class TextLine(BaseChar):
     # `pattern_matched` (RecognitionPredictor.__call__(pattern=)): whether the line, read under a pattern, ended with EOS where the
     # pattern accepts -- False for a line cut by the token budget, the repeat rule or the no-output token (its text is then a proper
     # prefix of a match, or empty). None, and left out likewise, for a line without a pattern.
+    # `lexicon_index` (RecognitionPredictor.lexicon): the index, in the line's own word list, of the entry the line read -- >= 0 iff the
+    # line ended (EOS or pad) on a whole entry; -1 for a line cut by the token budget, the repeat rule or the no-output token (its text is
+    # then a proper prefix of an entry, or empty). None, and left out likewise, for a line without a lexicon.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
         hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
         pattern_matched: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
+        lexicon_index: Optional[int] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
         hypotheses: Optional[List[LineHypothesis]] = None
         pattern_matched: Optional[bool] = None
+        lexicon_index: Optional[int] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
@@ -118,6 +123,8 @@ class TextLine(BaseChar):
                 d.pop("hypotheses", None)
             if self.pattern_matched is None:
                 d.pop("pattern_matched", None)
+            if self.lexicon_index is None:
+                d.pop("lexicon_index", None)
             return d
 
 

@@ -5,7 +5,7 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced|patterns] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced|patterns|lexicon] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
@@ -29,6 +29,12 @@ alternating in one process: unmasked / masks only (digits allowlist) / a pattern
 the date \d{2}/\d{2}/\d{4} (a line is complete after 10 tokens and keeps its state from then on), pat=2 is \d{64}, which takes a
 transition at every step of the run. Tokens are compared with the first arm of the same constraint. `patternonly`: the date arm alone
 (for a kernel trace beside `base` and `maskonly`).
+
+`lexicon`: lexicon-guided decoding (HipRecModel.set_lexicon: lexicon_step_kernel behind every head rewrites each slot's own mask row),
+arms alternating in one process: unmasked / masks only / the date pattern / a lexicon on every slot, twice, then unmasked once more --
+three identical unmasked arms, whose spread is the noise band. lex=1 is 2000 random five-digit codes (a line is complete after 6 tokens
+and keeps its state and row from then on), lex=2 is 300 entries with 300 different first characters and 40 digits each: a root with 300
+children, and a transition at every step of the run. `lexicononly` / `lexiconwide`: the lex=1 / lex=2 arm alone (for a kernel trace).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -107,6 +113,11 @@ def main():
         variants = [dict(), dict(masks=1), dict(pat=1), dict(pat=2), dict(), dict(masks=1), dict(pat=1), dict(pat=2), dict()]
     elif args.configs == "patternonly":  # one arm, the date pattern on every slot (for a kernel trace beside `base` / `maskonly`)
         variants = [dict(pat=1)]
+    elif args.configs == "lexicon":      # lexicon-guided decoding against unmasked / masks only / the date pattern, alternating
+        arms = [dict(), dict(masks=1), dict(pat=1), dict(lex=1), dict(lex=2)]
+        variants = arms + arms + [dict()]
+    elif args.configs in ("lexicononly", "lexiconwide"):     # one arm, a lexicon on every slot (for a kernel trace)
+        variants = [dict(lex=1 if args.configs == "lexicononly" else 2)]
     elif args.configs == "alts":         # alternatives: off against on, alternating
         variants = [dict(), dict(alts=1), dict(), dict(alts=1), dict()]
     elif args.configs == "altsonly":
@@ -130,8 +141,12 @@ def main():
                   for row in np.random.default_rng(99).integers(0, cfg.decoder.vocab_size, size=(n, args.steps + 1))]
 
     pat_start = [None]
+    lex_start = [None]
 
     def run(n_steps):
+        if lex_start[0] is not None:                 # every run starts every slot's lexicon again
+            m.set_slot_masks(slots, [-1] * n)
+            m.set_slot_lexicon(slots, [lex_start[0]] * n)
         if pat_start[0] is not None:                 # every run starts every slot's automaton again
             m.set_slot_masks(slots, [-1] * n)
             m.set_slot_patterns(slots, [pat_start[0]] * n)
@@ -185,6 +200,23 @@ def main():
         m.set_patterns(pt)
         pat_start[0] = pt.starts[0]
 
+    def set_lexicon(kind):                       # 0 = off (the mask table goes too), 1 = 2000 five-digit codes, 2 = a root with 300 children
+        lex_start[0] = pat_start[0] = None
+        if not kind:
+            return m.set_token_masks(None)
+        import random
+        from surya_amd.recognition.lexicon import compile_lexicons
+        from surya_amd.recognition.loader import RecognitionModelLoader
+        tk = RecognitionModelLoader({"config": cfg, "state_dict": {}}).processor().ocr_tokenizer
+        r = random.Random(2)
+        entries = (["%05d" % r.randrange(100000) for _ in range(2000)] if kind == 1 else
+                   [chr(0x100 + k) + "".join(r.choice("0123456789") for _ in range(40)) for k in range(300)])
+        lt = compile_lexicons(tk, [entries], cfg.decoder.vocab_size)
+        m.set_token_masks(tk.token_mask(allow="0123456789.,-", vocab_size=cfg.decoder.vocab_size)[None])     # (a lexicon needs a mask table)
+        m.set_lexicon(lt)
+        lex_start[0] = lt.starts[0]
+
+    lex_cfg = args.configs in ("lexicon", "lexicononly", "lexiconwide")
     ref = {}
     print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == first arm of the same arithmetic")
     for v in variants:
@@ -198,6 +230,9 @@ def main():
         if forced or args.configs in ("forced", "forcedonly"):
             m.set_forced(bool(forced))
         pat = v.pop("pat", 0)
+        lex = v.pop("lex", 0)
+        if lex_cfg:
+            set_lexicon(lex)                         # (off: the mask table and patterns go too; the arm's own constraint follows)
         if pat:
             set_patterns(pat)
         elif args.configs in ("patterns", "patternonly"):
@@ -208,10 +243,12 @@ def main():
             set_masks(masks)
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
-        if args.configs in ("masks", "maskonly", "patterns", "patternonly"):
+        if args.configs in ("masks", "maskonly", "patterns", "patternonly") or lex_cfg:
             v["masks"] = masks
-            if args.configs in ("patterns", "patternonly"):
+            if args.configs in ("patterns", "patternonly") or lex_cfg:
                 v["pat"] = pat
+            if lex_cfg:
+                v["lex"] = lex
         if args.configs in ("alts", "altsonly"):
             v["alts"] = alts
         if args.configs in ("forced", "forcedonly"):
@@ -219,12 +256,12 @@ def main():
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0), v.get("pat", 0)), best[2])).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0), v.get("pat", 0), v.get("lex", 0)), best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
-    if args.configs in ("masks", "maskonly", "patterns", "patternonly"):
-        m.set_token_masks(None)                      # (which switches patterns off as well)
+    if args.configs in ("masks", "maskonly", "patterns", "patternonly") or lex_cfg:
+        m.set_token_masks(None)                      # (which switches patterns and the lexicon off as well)
     if args.configs in ("alts", "altsonly"):
         m.set_alternatives(False)
     if args.configs in ("forced", "forcedonly"):
