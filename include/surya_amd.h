@@ -374,6 +374,39 @@ int surya_rec_set_lexicon(surya_rec* h, const int32_t* edge_off, const int32_t* 
 int surya_rec_set_slot_lexicon(surya_rec* h, const int32_t* slots, const int32_t* start_states, int n, void* stream);
 int surya_rec_copy_lexicon_states(surya_rec* h, int32_t* dst, void* stream);
 
+/* Boosted decoding: prefer the words of a user list without forbidding anything else ("hot words"). A boosted slot follows a sparse
+ * automaton of the lexicon's CSR form (surya_amd/recognition/boost.py compiles it) and owns the mask-table row a lexicon slot would, but
+ * the row is the PREFERRED set S of the position: per step the lm_head runs its masked greedy epilogue (record A, over S) and its plain
+ * one (record B, over every column, into a second partial buffer), and boost_head_kernel decodes from v' = v + beta * [in S] by the exact
+ * rules of csrc/boost_core.h: token = first maximum of v', score = its softmax probability under v'. No GEMM kernel changes. The
+ * automaton is total: a token without an edge goes to out_state (a state without edges) if it is a word unit -- bit set in row
+ * word_row of the mask table -- and to the slot's root otherwise (csrc/boost.h). eos / pad keep state and row.
+ *   set_boost:   HOST arrays as surya_rec_set_lexicon's (edge_off [n_states + 1], edge_tok [n_edges] strictly ascending inside a state,
+ *                edge_next [n_edges]), all validated first -- offsets from 0 to n_edges and monotone, tokens inside [0, vocab), not eos
+ *                or pad, ascending, targets < n_states, out_state a state without edges, word_row a row of the mask table, counts
+ *                within SA_MAX_LEXICON_STATES / SA_MAX_LEXICON_EDGES: SA_ERR_ARG with nothing changed otherwise. SA_ERR_STATE without a
+ *                token-mask table, while alternatives, beam search, forced decoding, patterns or a lexicon are on (their setters
+ *                return SA_ERR_STATE while boosting is on), and where the greedy head on partials cannot run (tuning ghead != 2, hidden
+ *                size > 2048). n_states == 0 switches the feature off: a handle that never saw a boost table, or saw 0 last, launches
+ *                exactly what it launched before this entry existed. Switching on or off, or growing the tables' memory, drops captured
+ *                decode steps; new contents of the same capacity keep them. Every slot is set to "not boosted". The first call
+ *                allocates the dynamic mask rows (as set_lexicon's first call), the second partial buffer and the outputs below.
+ *                surya_rec_set_token_masks switches it off. Static masks on other slots, MXFP8 weights and the fp8 KV cache are fine.
+ *   set_slot_boost: root state (-1 = not boosted: beta +inf, state -1, mask id and row left alone) and beta (finite, >= 0, logit
+ *                units) of `n` slots; call it for the slots about to be prefilled, after surya_rec_set_slot_masks, which sets the
+ *                slots it names back to "not boosted". SA_ERR_STATE while off; a slot named twice, a slot, root or beta out of range:
+ *                SA_ERR_ARG.
+ *   copy_boost_states: the states of all max_slots slots into `dst` (device, int32 [max_slots]), for tests.
+ *   read_boost / wait_boost: per step and slot, like surya_rec_read_outputs / surya_rec_wait_outputs: plain_tokens = the token the
+ *                model would have emitted here without the boost (record B's index), plain_probs = the emitted token's probability
+ *                without the boost. SA_ERR_STATE while off. */
+int surya_rec_set_boost(surya_rec* h, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, int n_states, int n_edges,
+                        int out_state, int word_row, void* stream);
+int surya_rec_set_slot_boost(surya_rec* h, const int32_t* slots, const int32_t* roots, const float* betas, int n, void* stream);
+int surya_rec_copy_boost_states(surya_rec* h, int32_t* dst, void* stream);
+int surya_rec_read_boost(surya_rec* h, int n_steps, int32_t* plain_tokens, float* plain_probs, void* stream);
+int surya_rec_wait_boost(surya_rec* h, int n_steps, int ring, int32_t* plain_tokens, float* plain_probs);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
@@ -558,6 +591,21 @@ typedef struct surya_rec_lexicon_args {
 } surya_rec_lexicon_args;
 int surya_op_rec_lexicon_start(const surya_rec_lexicon_args* args, const int32_t* slots, const int32_t* states, int n, void* stream);
 int surya_op_rec_lexicon_step(const surya_rec_lexicon_args* args, const int32_t* row_slot, const int32_t* out_token, int rows, void* stream);
+/* The kernels of boosted decoding (csrc/boost.h) on caller-owned DEVICE buffers, through the launch code the engine uses.
+ *   boost_step: `lex` as above (state_flags: one zero byte per state; slot_state = the boost states; nop_id unused), slot_root by slot,
+ *                out_state and word_row as surya_rec_set_boost. Workgroup r moves slot row_slot[r] behind out_token[slot]: state -1,
+ *                eos / pad and an id outside the vocabulary touch nothing; else the edge's target, or out_state for a word unit, or the
+ *                slot's root; the slot's row becomes the new state's set. A slot at most once per call.
+ *   boost_head: surya_op_rec_head's operands (`head`: part = record A's partials; best_tot, forced_table and pat_tok_class NULL) plus
+ *                part_b [rows][tiles_n][4] (record B), slot_beta by slot (+inf = record A alone: the bits of surya_op_rec_head on
+ *                `part`), plain_token / plain_prob by slot. Where surya_op_rec_head would run the fallback head: SA_ERR_STATE. */
+typedef struct surya_rec_boost_head_args {
+    surya_rec_head_args head;
+    const float* part_b; const float* slot_beta; int32_t* plain_token; float* plain_prob;
+} surya_rec_boost_head_args;
+int surya_op_rec_boost_step(const surya_rec_lexicon_args* lex, const int32_t* slot_root, int out_state, int word_row, const int32_t* row_slot,
+                            const int32_t* out_token, int rows, void* stream);
+int surya_op_rec_boost_head(int dtype, const surya_rec_boost_head_args* args, void* stream);
 
 /* The layout / table-recognition engine's own kernels by themselves (csrc/layout_kernels.h), each through the launch code LayoutModel
  * uses (sa::lay::launch_* of csrc/layout_model.hip: the same grid, block and LDS arithmetic and the same choice of kernel per dtype).

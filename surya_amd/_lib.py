@@ -70,6 +70,11 @@ class RecLexiconArgsC(C.Structure):
                 [(n, C.c_int32) for n in ("words", "row_base", "vocab", "eos_id", "pad_id", "nop_id")])
 
 
+class RecBoostHeadArgsC(C.Structure):
+    """surya_rec_boost_head_args (include/surya_amd.h): the operands of surya_op_rec_boost_head."""
+    _fields_ = [("head", RecHeadArgsC)] + [(n, C.c_void_p) for n in ("part_b", "slot_beta", "plain_token", "plain_prob")]
+
+
 class SuryaAmdError(RuntimeError):
     pass
 
@@ -161,6 +166,14 @@ def _bind_lay_ops(lib):
     lib.surya_rec_copy_lexicon_states.argtypes, lib.surya_rec_copy_lexicon_states.restype = [p, p, p], C.c_int
     for name in ("surya_op_rec_lexicon_start", "surya_op_rec_lexicon_step"):
         getattr(lib, name).argtypes, getattr(lib, name).restype = [C.POINTER(RecLexiconArgsC), p, p, i, p], C.c_int
+    # boosted decoding (a slot's own mask row is its preferred set; recognition/boost.py compiles the tables) and its kernels by themselves
+    lib.surya_rec_set_boost.argtypes, lib.surya_rec_set_boost.restype = [p, ip, ip, ip, i, i, i, i, p], C.c_int
+    lib.surya_rec_set_slot_boost.argtypes, lib.surya_rec_set_slot_boost.restype = [p, ip, ip, fp, i, p], C.c_int
+    lib.surya_rec_copy_boost_states.argtypes, lib.surya_rec_copy_boost_states.restype = [p, p, p], C.c_int
+    lib.surya_rec_read_boost.argtypes, lib.surya_rec_read_boost.restype = [p, i, ip, fp, p], C.c_int
+    lib.surya_rec_wait_boost.argtypes, lib.surya_rec_wait_boost.restype = [p, i, i, ip, fp], C.c_int
+    lib.surya_op_rec_boost_step.argtypes, lib.surya_op_rec_boost_step.restype = [C.POINTER(RecLexiconArgsC), p, i, i, p, p, i, p], C.c_int
+    lib.surya_op_rec_boost_head.argtypes, lib.surya_op_rec_boost_head.restype = [i, C.POINTER(RecBoostHeadArgsC), p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

@@ -20,6 +20,7 @@
 #include "attn_mfma.h"
 #include "beam.h"
 #include "lexicon.h"
+#include "boost.h"
 
 namespace sa {
 
@@ -221,7 +222,7 @@ static __global__ void set_next_tokens_kernel(const int* slots, const int* toks,
 // --------------------------------------------------------------------------------------------------- model
 // The step-output sets of an engine, in the order decode_async mirrors them; the fields of each in the order of its surya_rec_read_* /
 // surya_rec_wait_* arguments (RecModel::init names them).
-enum StepSet { STEPS_BASE = 0, STEPS_ALTS, STEPS_BEAM, STEPS_FORCED, STEPS_SETS };
+enum StepSet { STEPS_BASE = 0, STEPS_ALTS, STEPS_BEAM, STEPS_FORCED, STEPS_BOOST, STEPS_SETS };
 
 struct RecBase {
     virtual ~RecBase() {}
@@ -249,6 +250,9 @@ struct RecBase {
     virtual int set_lexicon(const int32_t*, const int32_t*, const int32_t*, const uint8_t*, int, int, int, hipStream_t) = 0;
     virtual int set_slot_lexicon(const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int copy_lexicon_states(int32_t*, hipStream_t) = 0;
+    virtual int set_boost(const int32_t*, const int32_t*, const int32_t*, int, int, int, int, hipStream_t) = 0;
+    virtual int set_slot_boost(const int32_t*, const int32_t*, const float*, int, hipStream_t) = 0;
+    virtual int copy_boost_states(int32_t*, hipStream_t) = 0;
 };
 
 // surya_rec_set_forced_tokens: workgroup i writes the whole table row of slots[i] -- its ids, then -1 -- and sets the slot's cursor to 0
@@ -403,14 +407,37 @@ struct RecModel : RecBase {
         return LexiconArgs{lex_edge_off, lex_edge_tok, lex_edge_next, lex_flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS, slot_lex_state,
                            slot_mask, c.vocab, c.eos_token_id, c.pad_token_id, lex_nop};
     }
+    // Boosted decoding (surya_rec_set_boost; boost.h): a sparse automaton like the lexicon's, in handle-owned memory sized by need -- growing
+    // it, like switching the feature on or off, drops captured steps; new contents of the same capacity keep them. State, root and beta
+    // per slot, the second lm_head partial buffer (record B) and the STEPS_BOOST outputs with their pinned mirror are allocated on the
+    // first call at addresses that never change. A boosted slot owns the mask-table row a lexicon slot would (mask_dyn_rows above).
+    // bst_states == 0: the handle launches exactly what a handle without this entry launches.
+    DevBlock bst_arena;                                  // device tables (+ an all-zero state_flags array) and their pinned staging copy
+    int *bst_edge_off = nullptr, *bst_edge_tok = nullptr, *bst_edge_next = nullptr;
+    uint8_t* bst_flags = nullptr;
+    size_t bst_o_tok = 0, bst_o_next = 0;
+    int bst_cap_states = 0, bst_cap_edges = 0;
+    hipEvent_t bst_ev = nullptr;
+    bool bst_pending = false;
+    DevBlock bst_slots;                                  // per-slot state / root / beta, record B's partials, the outputs and their mirror
+    int *slot_bst_state = nullptr, *slot_bst_root = nullptr; float* slot_bst_beta = nullptr;     // [max_slots]: -1, -1, +inf = not boosted
+    float4* amax_b = nullptr;                            // as amax
+    int* plain_token = nullptr; float* plain_prob = nullptr;     // [SA_MAX_STEPS][max_slots]
+    Stager st_bst;                                       // slots, roots and betas of set_slot_boost
+    int bst_states = 0, bst_out = 0, bst_word_row = 0;
+    BoostArgs bst_args() const {
+        return BoostArgs{LexiconArgs{bst_edge_off, bst_edge_tok, bst_edge_next, bst_flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS,
+                                     slot_bst_state, slot_mask, c.vocab, c.eos_token_id, c.pad_token_id, -1},
+                         slot_bst_root, slot_bst_beta, bst_out, bst_word_row};
+    }
     bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
     // Which step-output sets the kernels write right now: decode_async mirrors these, read_steps / wait_steps refuse the others.
-    bool steps_on(StepSet k) const { return k == STEPS_BASE || (k == STEPS_ALTS && topk()) || (k == STEPS_BEAM && beam > 0) || (k == STEPS_FORCED && forcing); }
+    bool steps_on(StepSet k) const { return k == STEPS_BASE || (k == STEPS_ALTS && topk()) || (k == STEPS_BEAM && beam > 0) || (k == STEPS_FORCED && forcing) || (k == STEPS_BOOST && bst_states > 0); }
     // The modes that cannot be on together, and why; every setter asks excluded() before it switches its own mode on.
-    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, M_PATTERNS, M_LEXICON, MODES };
-    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx(), pat_states > 0, lex_states > 0}; return on[m]; }
+    enum Mode { M_MASKS, M_ALTS, M_FORCED, M_BEAM, M_KV8, M_MX, M_PATTERNS, M_LEXICON, M_BOOST, MODES };
+    bool mode_on(int m) const { const bool on[MODES] = {n_token_masks > 0, alts, forcing, beam > 0, kv8, mx(), pat_states > 0, lex_states > 0, bst_states > 0}; return on[m]; }
     bool excluded(int m) const {
-        static constexpr int pairs[9][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
+        static constexpr int pairs[14][2] = {{M_FORCED, M_MASKS},      // forced decoding runs the unmasked partial
                                             {M_FORCED, M_ALTS},       // ... which collects no candidates
                                             {M_FORCED, M_BEAM},
                                             {M_BEAM, M_KV8},          // the KV fork copies the bf16 / fp16 / fp32 caches only
@@ -419,7 +446,12 @@ struct RecModel : RecBase {
                                             {M_BEAM, M_PATTERNS},     // a surviving beam would have to inherit its PARENT's state through
                                                                       // beam_select_kernel's choice: left out for now
                                             {M_FORCED, M_LEXICON},    // as patterns: forced decoding reads no mask,
-                                            {M_BEAM, M_LEXICON}};     // and a surviving beam would inherit its parent's state AND row (4o)
+                                            {M_BEAM, M_LEXICON},      // and a surviving beam would inherit its parent's state AND row (4o)
+                                            {M_BOOST, M_ALTS},        // boosting runs the masked and the plain greedy epilogue, alternatives,
+                                            {M_BOOST, M_BEAM},        // beam search and forced decoding run others (4p)
+                                            {M_BOOST, M_FORCED},
+                                            {M_BOOST, M_PATTERNS},    // their heads and rows would have to be combined with the boost's:
+                                            {M_BOOST, M_LEXICON}};    // the follow-up (4p)
         for (auto& p : pairs)
             if ((p[0] == m && mode_on(p[1])) || (p[1] == m && mode_on(p[0]))) return true;
         return false;
@@ -532,9 +564,11 @@ struct RecModel : RecBase {
         if (mask_arena) (void)hipFree(mask_arena);
         if (pat_arena) (void)hipFree(pat_arena);
         lex_arena.release();
+        bst_arena.release(); bst_slots.release();
+        if (bst_ev) (void)hipEventDestroy(bst_ev);
         if (slot_lex_state) (void)hipFree(slot_lex_state);
         if (lex_ev) (void)hipEventDestroy(lex_ev);
-        st_mask.destroy(); st_forced.destroy(); st_pat.destroy(); st_lex.destroy();
+        st_mask.destroy(); st_forced.destroy(); st_pat.destroy(); st_lex.destroy(); st_bst.destroy();
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
         if (gev_in) (void)hipEventDestroy(gev_in);
@@ -850,15 +884,15 @@ struct RecModel : RecBase {
         if (slot_state)                                     // a slot given a plain id follows no automaton any more (a reused slot would go on advancing)
             hipLaunchKernelGGL(set_slot_patterns_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, (const int*)nullptr, pat_state_mask, slot_state,
                                slot_mask, n);
-        if (slot_lex_state) {                               // ... and rewrites no row any more
-            if ((rc = (int)hipGetLastError())) return rc;
-            return launch_lexicon_start(lex_args(), ds, nullptr, n, s);
-        }
-        return (int)hipGetLastError();
+        if ((rc = (int)hipGetLastError())) return rc;
+        if (slot_lex_state && (rc = launch_lexicon_start(lex_args(), ds, nullptr, n, s))) return rc;      // ... and rewrites no row any more
+        if (slot_bst_state) return launch_boost_start(bst_args(), ds, nullptr, nullptr, n, s);            // ... and is not boosted any more
+        return SA_OK;
     }
     int automata_off(hipStream_t s) {
-        const int rc = patterns_off(s);
-        return rc ? rc : lexicon_off(s);
+        int rc = patterns_off(s);
+        if (!rc) rc = lexicon_off(s);
+        return rc ? rc : boost_off(s);
     }
 
     // The automaton of pattern-guided decoding. Every entry is checked against the counts and the current mask table before anything is
@@ -1074,6 +1108,134 @@ struct RecModel : RecBase {
     int copy_lexicon_states(int32_t* dst, hipStream_t s) override {
         if (!slot_lex_state) return SA_ERR_STATE;
         SA_HIP(hipMemcpyAsync(dst, slot_lex_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SA_OK;
+    }
+
+    // The automaton of boosted decoding (boost.h), from host arrays. Everything is checked before anything is enqueued or allocated: the
+    // kernels read the tables unchecked. New tables set every slot back to "not boosted".
+    int set_boost(const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, int n_states, int n_edges, int out_state,
+                  int word_row, hipStream_t s) override {
+        if (n_states < 0 || n_states > SA_MAX_LEXICON_STATES || n_edges < 0 || n_edges > SA_MAX_LEXICON_EDGES) return SA_ERR_ARG;
+        if (n_states == 0) return boost_off(s);
+        if (!edge_off || (n_edges > 0 && (!edge_tok || !edge_next))) return SA_ERR_ARG;
+        if (n_token_masks == 0 || excluded(M_BOOST)) return SA_ERR_STATE;
+        if (!head2_ok() || cdiv(c.vocab, 64) > 4 * SA_HEAD_THREADS) return SA_ERR_STATE;      // the fallback head would have to run
+        if (out_state < 0 || out_state >= n_states || word_row < 0 || word_row >= n_token_masks) return SA_ERR_ARG;
+        if (edge_off[0] != 0 || edge_off[n_states] != n_edges || edge_off[out_state + 1] != edge_off[out_state]) return SA_ERR_ARG;
+        for (int st = 0; st < n_states; ++st) {
+            const int a = edge_off[st], b = edge_off[st + 1];
+            if (a < 0 || b < a || b > n_edges) return SA_ERR_ARG;
+            for (int e = a; e < b; ++e) {
+                const int t = edge_tok[e];
+                if (t < 0 || t >= c.vocab || t == c.eos_token_id || t == c.pad_token_id || edge_next[e] < 0 || edge_next[e] >= n_states) return SA_ERR_ARG;
+                if (e > a && t <= edge_tok[e - 1]) return SA_ERR_ARG;
+            }
+        }
+        int rc;
+        if (!bst_slots.dev) {                               // first tables: the per-slot arrays, record B's partials, the outputs -- or nothing
+            const size_t S = c.max_slots, out_b = (size_t)SA_MAX_STEPS * S * 4;
+            Carve cv;
+            const size_t o_state = cv.take(S * 4), o_root = cv.take(S * 4), o_beta = cv.take(S * 4),
+                         o_amax = cv.take(S * (size_t)cdiv(c.vocab, 32) * sizeof(float4)), o_ptok = cv.take(out_b), o_pprob = cv.take(out_b);
+            DevBlock b;
+            Stager st;
+            hipEvent_t ev = nullptr;
+            std::vector<float> inf(S, INFINITY);
+            rc = b.alloc(cv.off, 2 * out_b);
+            if (!rc) rc = st.init(S * 3 * sizeof(int) + 4096);
+            if (!rc) rc = (int)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+            if (!rc) rc = (int)hipMemset(b.dev + o_state, 0xff, o_beta - o_state);                    // state and root -1
+            if (!rc) rc = (int)hipMemcpy(b.dev + o_beta, inf.data(), S * 4, hipMemcpyHostToDevice);      // beta +inf
+            if (rc) { if (ev) (void)hipEventDestroy(ev); st.destroy(); b.release(); return rc; }
+            bst_slots = b; st_bst = st; bst_ev = ev;
+            slot_bst_state = reinterpret_cast<int*>(b.dev + o_state);
+            slot_bst_root = reinterpret_cast<int*>(b.dev + o_root);
+            slot_bst_beta = reinterpret_cast<float*>(b.dev + o_beta);
+            amax_b = reinterpret_cast<float4*>(b.dev + o_amax);
+            plain_token = reinterpret_cast<int*>(b.dev + o_ptok);
+            plain_prob = reinterpret_cast<float*>(b.dev + o_pprob);
+            StepOutputs& o = outs[STEPS_BOOST];
+            o.add(plain_token, 4); o.add(plain_prob, 4);
+            o.host = b.host;
+        }
+        if (!mask_dyn_rows && (rc = grow_mask_arena(s))) return rc;
+        if (n_states > bst_cap_states || n_edges > bst_cap_edges) {      // grow: powers of two, so a call's tables mostly fit the last call's
+            int cs = std::max(bst_cap_states, 1024), ce = std::max(bst_cap_edges, 1024);
+            while (cs < n_states) cs *= 2;
+            while (ce < n_edges) ce *= 2;
+            Carve cv;
+            (void)cv.take(((size_t)cs + 1) * sizeof(int));
+            const size_t o_tok = cv.take((size_t)ce * sizeof(int)), o_next = cv.take((size_t)ce * sizeof(int)), o_flags = cv.take((size_t)cs);
+            DevBlock nb;
+            if ((rc = nb.alloc(cv.off, o_flags))) return rc;      // (the flags stay the zeros of the allocation: no staging copy)
+            SA_HIP(hipDeviceSynchronize());                 // nothing in flight reads the old tables or their staging copy
+            drop_graphs();                                  // captured steps hold the old addresses
+            bst_arena.release();
+            bst_arena = nb;
+            bst_pending = false;
+            bst_o_tok = o_tok; bst_o_next = o_next;
+            bst_edge_off = reinterpret_cast<int*>(nb.dev);
+            bst_edge_tok = reinterpret_cast<int*>(nb.dev + o_tok);
+            bst_edge_next = reinterpret_cast<int*>(nb.dev + o_next);
+            bst_flags = reinterpret_cast<uint8_t*>(nb.dev + o_flags);
+            bst_cap_states = cs; bst_cap_edges = ce;
+            bst_states = 0;                                 // (the old tables are gone: off until the new ones are on their way)
+        }
+        if (bst_pending) { (void)hipEventSynchronize(bst_ev); bst_pending = false; }
+        char* hb = bst_arena.host;
+        memcpy(hb, edge_off, ((size_t)n_states + 1) * sizeof(int));
+        SA_HIP(hipMemcpyAsync(bst_edge_off, hb, ((size_t)n_states + 1) * sizeof(int), hipMemcpyHostToDevice, s));
+        if (n_edges) {
+            memcpy(hb + bst_o_tok, edge_tok, (size_t)n_edges * sizeof(int));
+            memcpy(hb + bst_o_next, edge_next, (size_t)n_edges * sizeof(int));
+            SA_HIP(hipMemcpyAsync(bst_edge_tok, hb + bst_o_tok, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
+            SA_HIP(hipMemcpyAsync(bst_edge_next, hb + bst_o_next, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
+        }
+        SA_HIP(hipEventRecord(bst_ev, s));
+        bst_pending = true;
+        if ((rc = reset_boost_slots(s))) return rc;
+        if (bst_states == 0 || out_state != bst_out || word_row != bst_word_row) drop_graphs();      // on <-> off, and the by-value ids of the step launch
+        bst_states = n_states;
+        bst_out = out_state;
+        bst_word_row = word_row;
+        return SA_OK;
+    }
+    int reset_boost_slots(hipStream_t s) {                  // every slot: state and root -1, beta +inf (0x7f800000)
+        SA_HIP(hipMemsetAsync(slot_bst_state, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        SA_HIP(hipMemsetAsync(slot_bst_root, 0xff, (size_t)c.max_slots * sizeof(int), s));
+        SA_HIP(hipMemsetD32Async((hipDeviceptr_t)slot_bst_beta, 0x7f800000, (size_t)c.max_slots, s));
+        return SA_OK;
+    }
+    int boost_off(hipStream_t s) {
+        if (bst_states == 0) return SA_OK;
+        drop_graphs();
+        bst_states = 0;
+        return reset_boost_slots(s);
+    }
+    // Roots and boosts of the slots about to be prefilled (root -1 = not boosted: beta +inf, the slot's mask id and row are left alone).
+    int set_slot_boost(const int32_t* slots, const int32_t* roots, const float* betas, int n, hipStream_t s) override {
+        if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
+        if (n > c.max_slots) return SA_ERR_ARG;
+        if (bst_states == 0) return SA_ERR_STATE;
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] < 0 || slots[i] >= c.max_slots || roots[i] < -1 || roots[i] >= bst_states) return SA_ERR_ARG;
+            if (roots[i] >= 0 && !(betas[i] >= 0.f && betas[i] < INFINITY)) return SA_ERR_ARG;      // finite, >= 0 (NaN fails both)
+            if (seen[slots[i]]) return SA_ERR_ARG;
+            seen[slots[i]] = 1;
+        }
+        st_bst.begin();
+        const int* ds = st_bst.put(slots, n);
+        const int* dr = st_bst.put(roots, n);
+        const float* db = st_bst.put(betas, n);
+        if (!ds || !dr || !db) return SA_ERR_NOMEM;
+        int rc = st_bst.flush(s);
+        if (rc) return rc;
+        return launch_boost_start(bst_args(), ds, dr, db, n, s);
+    }
+    int copy_boost_states(int32_t* dst, hipStream_t s) override {
+        if (!slot_bst_state) return SA_ERR_STATE;
+        SA_HIP(hipMemcpyAsync(dst, slot_bst_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
         return SA_OK;
     }
 
@@ -1361,7 +1523,13 @@ struct RecModel : RecBase {
             }
             const int rc_ =forcing ? launch(a, HeadEpi<0>{}) : topk() ? launch(a, HeadEpi<1>{}) : n_token_masks > 0 ? launch(a, HeadEpi<2>{}) : launch(a, HeadEpi<3>{});
             bn_used = a.bn_used;
-            return rc_;
+            if (rc_ || bst_states == 0) return rc_;
+            // boosted decoding: that was record A (the masked epilogue; a boosted slot's row is its preferred set). Record B, the plain
+            // greedy epilogue of the same tiling, goes into the second partial buffer.
+            a.amax = amax_b;
+            a.tmask = TokenMask{};
+            const int rc_b = launch(a, HeadEpi<3>{});
+            return rc_b ? rc_b : a.bn_used != bn_used ? (int)SA_ERR_STATE : (int)SA_OK;
         };
         if (mx() && normed) {       // decode steps: MXFP8 lm_head on the MXFP8 copy of the final-norm rows
             if constexpr (std::is_same<T, bf16_t>::value) {
@@ -1398,6 +1566,11 @@ struct RecModel : RecBase {
         ha.best_tot = bt; ha.fh = fh;
         if (pat_states > 0)                                   // empty while patterns are off: the heads do what they always did
             ha.ph = PatternHead{pat_tok_class, pat_next_state, pat_state_mask, SA_MAX_PATTERN_CLASSES, c.vocab, slot_state, slot_mask};
+        if (bst_states > 0) {                                 // boosted decoding: the head on both records, then every boosted slot's next state and row
+            BoostHeadArgs<T> bh{ha, reinterpret_cast<const float4*>(amax_b), slot_bst_beta, plain_token + so, plain_prob + so};
+            if ((rc = launch_boost_head<T>(bh, mx(), s))) return rc;
+            return launch_boost_step(bst_args(), d_row_slot, out_token + so, rows, s);
+        }
         if ((rc = launch_head<T>(ha, mx(), s))) return rc;
         // lexicon-guided decoding: behind the token, every lexicon slot's own mask row becomes its next state's allowed set (lexicon.h)
         if (lex_states > 0 && (rc = launch_lexicon_step(lex_args(), d_row_slot, out_token + so, rows, s))) return rc;

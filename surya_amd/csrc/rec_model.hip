@@ -311,6 +311,28 @@ int surya_rec_copy_lexicon_states(surya_rec* h, int32_t* dst, void* stream) {
     return h->impl->copy_lexicon_states(dst, (hipStream_t)stream);
 }
 
+int surya_rec_set_boost(surya_rec* h, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next, int n_states, int n_edges,
+                        int out_state, int word_row, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->set_boost(edge_off, edge_tok, edge_next, n_states, n_edges, out_state, word_row, (hipStream_t)stream);
+}
+int surya_rec_set_slot_boost(surya_rec* h, const int32_t* slots, const int32_t* roots, const float* betas, int n, void* stream) {
+    if (!h || (n > 0 && (!slots || !roots || !betas))) return SA_ERR_ARG;
+    return h->impl->set_slot_boost(slots, roots, betas, n, (hipStream_t)stream);
+}
+int surya_rec_copy_boost_states(surya_rec* h, int32_t* dst, void* stream) {
+    if (!h || !dst) return SA_ERR_ARG;
+    return h->impl->copy_boost_states(dst, (hipStream_t)stream);
+}
+int surya_rec_read_boost(surya_rec* h, int n_steps, int32_t* plain_tokens, float* plain_probs, void* stream) {
+    if (!h || !plain_tokens || !plain_probs) return SA_ERR_ARG;
+    return h->impl->read_steps(STEPS_BOOST, n_steps, {plain_tokens, plain_probs}, (hipStream_t)stream);
+}
+int surya_rec_wait_boost(surya_rec* h, int n_steps, int ring, int32_t* plain_tokens, float* plain_probs) {
+    if (!h || !plain_tokens || !plain_probs) return SA_ERR_ARG;
+    return h->impl->wait_steps(STEPS_BOOST, n_steps, ring, {plain_tokens, plain_probs});
+}
+
 // surya_op_lm_head_topk without a row -> slot map: the identity, for the head kernel (which always reads one)
 static __global__ void iota_kernel(int* dst, int n) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -738,6 +760,17 @@ int surya_op_rec_lexicon_step(const surya_rec_lexicon_args* args, const int32_t*
     sa::LexiconArgs a;
     if (lexicon_op_args(args, a) || rows < 0 || (rows > 0 && (!row_slot || !out_token))) return SA_ERR_ARG;
     return sa::launch_lexicon_step(a, row_slot, out_token, rows, (hipStream_t)stream);
+}
+int surya_op_rec_boost_step(const surya_rec_lexicon_args* lex, const int32_t* slot_root, int out_state, int word_row, const int32_t* row_slot,
+                            const int32_t* out_token, int rows, void* stream) {
+    sa::BoostArgs b;
+    if (lexicon_op_args(lex, b.lx) || !slot_root || out_state < 0 || word_row < 0 || rows < 0 || (rows > 0 && (!row_slot || !out_token))) return SA_ERR_ARG;
+    b.slot_root = const_cast<int32_t*>(slot_root); b.out_state = out_state; b.word_row = word_row;
+    return sa::launch_boost_step(b, row_slot, out_token, rows, (hipStream_t)stream);
+}
+int surya_op_rec_boost_head(int dtype, const surya_rec_boost_head_args* args, void* stream) {
+    if (!args) return SA_ERR_ARG;
+    return rec_dispatch(dtype, sa::REC_OP_BOOST_HEAD, args, stream);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #pragma once
 #include "kernels.h"
 #include "beam.h"
+#include "boost.h"
 
 namespace sa {
 
@@ -17,7 +18,7 @@ struct RecEmbedOp {
     int rows, H; float eps; uint8_t *y8, *sy; int srows;
 };
 struct RecKvForkOp { void *kc, *vc; const int *fork_src, *base, *len; int rows, layers, slots, nkv, Tmax, D; };
-enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK };
+enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK, REC_OP_BOOST_HEAD };
 
 template <typename T> constexpr bool rec_mx_ok() { return std::is_same<T, bf16_t>::value; }     // the MXFP8 copies exist beside bf16 only
 
@@ -84,7 +85,7 @@ int rec_op(const RecEmbedOp& a, hipStream_t s) {
 }
 
 template <typename T>
-int rec_op(const surya_rec_head_args& a, hipStream_t s) {
+int rec_head_args(const surya_rec_head_args& a, HeadArgs<T>& h) {       // checked and cast: surya_op_rec_head and surya_op_rec_boost_head
     if (!a.part || !a.hidden || !a.wb || !a.bb || !a.row_slot || !a.out_token || !a.out_score || !a.out_bbox || !a.next_token || !a.kv_len ||
         a.rows <= 0 || a.tiles_n <= 0 || a.H <= 0)
         return SA_ERR_ARG;
@@ -97,7 +98,7 @@ int rec_op(const surya_rec_head_args& a, hipStream_t s) {
         return SA_ERR_ARG;                                       // (the engine refuses patterns beside forced decoding)
     if (a.y8 && !rec_mx_ok<T>()) return SA_ERR_UNSUPPORTED;
     if (a.H % 8 || (a.y8 && a.H % 128)) return SA_ERR_SHAPE;
-    HeadArgs<T> h{reinterpret_cast<const float4*>(a.part), a.tiles_n, a.rows, (const T*)a.hidden, a.H, (const T*)a.wb, (const T*)a.bb, a.row_slot,
+    h = HeadArgs<T>{reinterpret_cast<const float4*>(a.part), a.tiles_n, a.rows, (const T*)a.hidden, a.H, (const T*)a.wb, (const T*)a.bb, a.row_slot,
                   a.eos_id, a.pad_id, a.bbox_size, a.out_token, a.out_score, a.out_bbox, a.next_token, a.kv_len, a.len_inc};
     h.table = (const T*)a.table; h.wnorm = (const T*)a.wnorm; h.x = (T*)a.x; h.y = (T*)a.y; h.row_len = a.row_len; h.Tmax = a.max_kv_len;
     h.eps = a.eps; h.y8 = a.y8; h.sy = a.sy; h.srows = a.srows;
@@ -106,7 +107,24 @@ int rec_op(const surya_rec_head_args& a, hipStream_t s) {
         h.fh = ForcedHead{a.forced_table, a.forced_cursor, a.flogit, a.forced_stride, a.greedy_token, a.greedy_prob, a.logprob};
     if (a.pat_tok_class)
         h.ph = PatternHead{a.pat_tok_class, a.pat_next_state, a.pat_state_mask, a.pat_n_classes, a.pat_vocab, a.pat_slot_state, a.pat_slot_mask};
-    return launch_head<T>(h, a.y8 != nullptr, s);
+    return SA_OK;
+}
+
+template <typename T>
+int rec_op(const surya_rec_head_args& a, hipStream_t s) {
+    HeadArgs<T> h;
+    const int rc = rec_head_args<T>(a, h);
+    return rc ? rc : launch_head<T>(h, a.y8 != nullptr, s);
+}
+
+template <typename T>
+int rec_op(const surya_rec_boost_head_args& a, hipStream_t s) {
+    if (!a.part_b || !a.slot_beta || !a.plain_token || !a.plain_prob || a.head.best_tot || a.head.forced_table || a.head.pat_tok_class) return SA_ERR_ARG;
+    BoostHeadArgs<T> g;
+    const int rc = rec_head_args<T>(a.head, g.h);
+    if (rc) return rc;
+    g.part_b = reinterpret_cast<const float4*>(a.part_b); g.slot_beta = a.slot_beta; g.plain_token = a.plain_token; g.plain_prob = a.plain_prob;
+    return launch_boost_head<T>(g, a.head.y8 != nullptr, s);
 }
 
 template <typename T>
@@ -126,6 +144,7 @@ int rec_op_any(int op, const void* a, hipStream_t s) {
         case REC_OP_EMBED: return rec_op<T>(*static_cast<const RecEmbedOp*>(a), s);
         case REC_OP_HEAD: return rec_op<T>(*static_cast<const surya_rec_head_args*>(a), s);
         case REC_OP_KV_FORK: return rec_op<T>(*static_cast<const RecKvForkOp*>(a), s);
+        case REC_OP_BOOST_HEAD: return rec_op<T>(*static_cast<const surya_rec_boost_head_args*>(a), s);
     }
     return SA_ERR_ARG;
 }

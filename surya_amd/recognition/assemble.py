@@ -15,7 +15,7 @@ from .schema import CharAlternative, LineHypothesis, TaskNames, TextChar, TextLi
 
 _SCRIPT_TAG = re.compile(r"<SCRIPT-\w+>")
 _CHAR_FIELDS = frozenset(("polygon", "confidence", "text", "bbox_valid"))
-assert _CHAR_FIELDS | {"alternatives", "greedy"} == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
+assert _CHAR_FIELDS | {"alternatives", "greedy", "plain", "plain_confidence"} == frozenset(TextChar.model_fields), "TextChar fields changed: update _text_char"
 _new_char, _set = TextChar.__new__, object.__setattr__
 
 
@@ -24,15 +24,15 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
     text is ~10^4 of these). Same object state: __dict__, fields_set, no extras, no private attributes."""
     m = _new_char(TextChar)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "bbox_valid": bbox_valid, "alternatives": None,
-                         "greedy": None})
-    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))        # (alternatives, greedy: the defaults, as in TextChar(...) without them)
+                         "greedy": None, "plain": None, "plain_confidence": None})
+    _set(m, "__pydantic_fields_set__", set(_CHAR_FIELDS))        # (alternatives, greedy, plain*: the defaults, as in TextChar(...) without them)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
     return m
 
 
 _LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched",
-                "lexicon_index")
+                "lexicon_index", "boost_matches")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -44,7 +44,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
                          "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None,
-                         "lexicon_index": None})
+                         "lexicon_index": None, "boost_matches": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -121,6 +121,32 @@ def set_lexicon_index(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
         if st >= 0:
             line.lexicon_index = int(tables.entry_of(tables.lexicon_of_start(st), tokens))
             line.__pydantic_fields_set__.add("lexicon_index")
+    return line
+
+
+def boost_items(flat, items):
+    """The items of a boosted call with their sixth element -- (plain ids [T], the emitted tokens' plain probabilities [T]) -- in the
+    form of one alternative per token, and the flat dict that assembles them so: the characters then take `plain` from the token
+    `alternatives` and `greedy` take theirs from."""
+    inner = {**flat, "boost_tables": None, "top_k": 1}
+    return inner, [tuple(it[:5]) + ((np.asarray(it[5][0])[:, None], np.asarray(it[5][1])[:, None]),) if len(it) > 5 and it[5] is not None
+                   else tuple(it[:5]) for it in items]
+
+
+def set_boost_fields(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
+    """A line of a boosted call (flat["boost_tables"], flat["boost_roots"] by sorted position), assembled with its plain readings as
+    one-entry alternatives: a boosted line gets boost_matches -- the host replay of the automaton over its tokens -- and its characters
+    plain / plain_confidence; a line that was not boosted keeps None everywhere."""
+    root = int(flat["boost_roots"][sorted_pos])
+    for ch in line.chars:
+        alt, ch.alternatives = ch.alternatives, None
+        ch.__pydantic_fields_set__.discard("alternatives")
+        if root >= 0 and alt:
+            ch.plain, ch.plain_confidence = alt[0].text, alt[0].confidence
+            ch.__pydantic_fields_set__.update(("plain", "plain_confidence"))
+    if root >= 0:
+        line.boost_matches = [int(i) for i in flat["boost_tables"].matches(root, tokens)]
+        line.__pydantic_fields_set__.add("boost_matches")
     return line
 
 
@@ -256,6 +282,11 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
+    if flat.get("boost_tables") is not None:          # a boosted call: alts = (plain ids [T], the emitted tokens' plain probabilities [T])
+        inner, its = boost_items(flat, [(sorted_pos, orig, tokens, sc, bbox_rows, alts)])
+        line = assemble_line(proc, inner, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size,
+                             alts=its[0][5] if len(its[0]) > 5 else None)
+        return set_boost_fields(flat, sorted_pos, tokens, line)
     if flat.get("lexicon_tables") is not None:        # a call with lexicons: likewise (it may hold pattern lines too)
         line = assemble_line(proc, {**flat, "lexicon_tables": None}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
                              bbox_size, alts=alts)
@@ -299,6 +330,10 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    if flat.get("boost_tables") is not None:
+        inner, its = boost_items(flat, items)
+        out = assemble_batch(proc, inner, its, drop_repeated_text, return_words, bbox_size)
+        return [set_boost_fields(flat, it[0], it[2], line) for it, line in zip(items, out)]
     if flat.get("lexicon_tables") is not None:
         out = assemble_batch(proc, {**flat, "lexicon_tables": None}, items, drop_repeated_text, return_words, bbox_size)
         return [set_lexicon_index(flat, it[0], it[2], line) for it, line in zip(items, out)]

@@ -52,6 +52,16 @@ class DeviceLoop:
     "lexicon_tables" set_lexicon / set_slot_lexicon are never called -- a model without them works. Not with beam search or forced
     decoding.
 
+    Boosted decoding: the dict handed to `run` may also carry "boost_tables" (recognition/boost.py::BoostTables, whose word_row names
+    the row of "token_masks" that holds the word-unit set; uploaded once, behind the mask table) with "boost_weight" (beta, one per call)
+    and every admitted dict "boost_roots" (one root state per prompt, -1 = not boosted). A line's root and beta are set on whatever slot
+    the line is prefilled into, behind its mask id; from then on the model moves the slot's state and preferred set itself. The model
+    reports per step the token it would have emitted without the boost and the emitted token's probability without it; the loop keeps
+    them per line (plain_tok_mat / plain_p_mat [lines, cap]) and hands a finished line's rows to `on_done` as two more arguments.
+    Boosting is switched off on the way out, before the mask table, also after an exception. Without "boost_tables" set_boost /
+    set_slot_boost / read_boost / wait_boost are never called -- a model without them works. Not with alternatives, beam search,
+    forced decoding, patterns or lexicons.
+
     Alternatives (`alternatives=True`): the model reports the SA_MAX_ALTERNATIVES most likely tokens of every step; the loop keeps
     them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
     line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
@@ -128,6 +138,9 @@ class DeviceLoop:
         self.n_states = 0                                      # states of the automaton uploaded for this loop (0: patterns are off)
         self.line_lex = np.zeros(0, np.int64)                  # id -> start state of the line's lexicon, -1 = none
         self.n_lex_states = 0                                  # states of the lexicon automaton uploaded for this loop (0: off)
+        self.line_root = np.zeros(0, np.int64)                 # id -> root state of the line's boost list, -1 = not boosted
+        self.n_boost_states, self.boost_beta = 0, 0.0          # states of the boost automaton uploaded for this loop (0: off), the call's beta
+        self.plain_tok_mat = self.plain_p_mat = None           # [lines, cap] while boosting is on
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
@@ -191,6 +204,14 @@ class DeviceLoop:
         assert lx.shape == (m,) and int(lx.min()) >= -1 and int(lx.max()) < self.n_lex_states, \
             "lexicon start states must name states of the call's lexicon tables"
         self.line_lex = np.concatenate([self.line_lex, lx])
+        br = d.get("boost_roots")
+        br = np.full(m, -1, np.int64) if br is None else np.asarray(br, np.int64)
+        assert br.shape == (m,) and int(br.min()) >= -1 and int(br.max()) < self.n_boost_states, \
+            "boost roots must name states of the call's boost tables"
+        self.line_root = np.concatenate([self.line_root, br])
+        if self.n_boost_states:
+            self.plain_tok_mat = np.concatenate([self.plain_tok_mat, np.zeros((m, self.cap), np.int32)])
+            self.plain_p_mat = np.concatenate([self.plain_p_mat, np.zeros((m, self.cap), np.float32)])
         self.queue.extend(range(base, base + m))
 
     def tiles_of(self, first_id, last_id):
@@ -274,16 +295,21 @@ class DeviceLoop:
         self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
         if self.on_done is not None:
             more = (self.alt_tok_mat[p_idx, :L_].copy(), self.alt_p_mat[p_idx, :L_].copy()) if self.alternatives else ()
+            if self.n_boost_states:
+                more = (self.plain_tok_mat[p_idx, :L_].copy(), self.plain_p_mat[p_idx, :L_].copy())
             if self.forced:
                 more = (self.greedy_tok_mat[p_idx, :L_].copy(), self.greedy_p_mat[p_idx, :L_].copy(), self.logp_mat[p_idx, :L_].copy())
             self.on_done(p_idx, self.predicted_tokens[p_idx], self.scores[p_idx],
                          self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)], *more)
 
-    def _put(self, p, pos, t, s_, b_, at=None, ap=None, fo=None):
-        """Token t / score s_ / box b_ (/ alternatives at, ap / forced outputs fo = (greedy token, its probability, log-probability))
-        of lines p at positions pos (arrays over the lines of one step)."""
+    def _put(self, p, pos, t, s_, b_, at=None, ap=None, fo=None, bo=None):
+        """Token t / score s_ / box b_ (/ alternatives at, ap / forced outputs fo = (greedy token, its probability, log-probability) /
+        boost outputs bo = (plain token, the emitted token's plain probability)) of lines p at positions pos (arrays over the lines of
+        one step)."""
         self.tok_mat[p, pos] = t
         self.sc_mat[p, pos] = s_
+        if bo is not None:
+            self.plain_tok_mat[p, pos], self.plain_p_mat[p, pos] = bo
         if at is not None:
             self.alt_tok_mat[p, pos] = at
             self.alt_p_mat[p, pos] = ap
@@ -313,6 +339,7 @@ class DeviceLoop:
             return self._absorb_beam(k, bb, self.model.wait_beam(k, ring))
         at, ap = self.model.wait_alternatives(k, ring) if self.alternatives else (None, None)
         fo = self.model.wait_forced(k, ring) if self.forced else None
+        bo = self.model.wait_boost(k, ring) if self.n_boost_states else None
         slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
         changed = False
         for step in range(k):
@@ -324,6 +351,8 @@ class DeviceLoop:
             t = tok[step, s_idx]
             if fo is not None:
                 self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], fo=tuple(a[step, s_idx] for a in fo))
+            elif bo is not None:
+                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], bo=tuple(a[step, s_idx] for a in bo))
             elif at is None:
                 self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
             else:
@@ -413,6 +442,8 @@ class DeviceLoop:
             self.model.set_slot_patterns(slots, self.line_state[take].tolist())   # behind the mask ids: a start state names its own row
         if self.n_lex_states:
             self.model.set_slot_lexicon(slots, self.line_lex[take].tolist())      # likewise: the slot's own row becomes its mask id
+        if self.n_boost_states:
+            self.model.set_slot_boost(slots, self.line_root[take].tolist(), self.boost_beta)      # behind the mask ids: a root names the slot's own row
         if self.forced:
             self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
         self._prefill(take, grids, prompt_ids, slots)
@@ -424,7 +455,8 @@ class DeviceLoop:
             at, ap = self.model.read_alternatives(1)
             more = (at[0, sl_], ap[0, sl_])
         fo = tuple(a[0, sl_] for a in self.model.read_forced(1)) if self.forced else None
-        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more, fo=fo)
+        bo = tuple(a[0, sl_] for a in self.model.read_boost(1)) if self.n_boost_states else None
+        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more, fo=fo, bo=bo)
         go_on = (first != self.eos) & (first != self.nop)
         if self.forced:
             go_on &= self.max_tok[ids_] > 1                         # a one-id list is complete with the prefill's token
@@ -463,6 +495,10 @@ class DeviceLoop:
         assert pattern_tables is None or not (self.beam or self.forced), "patterns exclude beam search and forced decoding"
         lexicon_tables = None if prep is None else prep.get("lexicon_tables")
         assert lexicon_tables is None or not (self.beam or self.forced), "lexicons exclude beam search and forced decoding"
+        boost_tables = None if prep is None else prep.get("boost_tables")
+        assert boost_tables is None or not (self.beam or self.forced or self.alternatives or pattern_tables is not None or
+                                            lexicon_tables is not None), \
+            "boosting excludes alternatives, beam search, forced decoding, patterns and lexicons"
 
         def masks_on():
             m.set_token_masks(table)                   # once per call: identical masks were merged by the caller
@@ -475,6 +511,11 @@ class DeviceLoop:
         def lexicon_on():
             m.set_lexicon(lexicon_tables)              # behind the mask table too: every slot gets a row of its own behind its rows
             self.n_lex_states = int(lexicon_tables.n_states)
+
+        def boost_on():
+            m.set_boost(boost_tables)                  # behind the mask table, which holds the word-unit row
+            self.n_boost_states, self.boost_beta = int(boost_tables.n_states), float(prep["boost_weight"])
+            self.plain_tok_mat, self.plain_p_mat = np.zeros((0, self.cap), np.int32), np.zeros((0, self.cap), np.float32)
         # (requested, switch on, switch off): switched on in this order, off in reverse on the way out, also after an exception, so the
         # next call starts on the greedy, unmasked kernels without candidates. What was not requested never touches its entry points.
         modes = [(self.beam, lambda: m.set_beam(self.beam, self.nop), lambda: m.set_beam(None)),
@@ -482,7 +523,8 @@ class DeviceLoop:
                  (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False)),
                  (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None)),
                  (pattern_tables is not None, patterns_on, lambda: m.set_patterns(None)),
-                 (lexicon_tables is not None, lexicon_on, lambda: m.set_lexicon(None))]
+                 (lexicon_tables is not None, lexicon_on, lambda: m.set_lexicon(None)),
+                 (boost_tables is not None, boost_on, lambda: m.set_boost(None))]
         with ExitStack() as undo:
             for wanted, on, off in modes:
                 if wanted:

@@ -97,10 +97,12 @@ class HipRecModel:
         self._alt = _StepBufs("alternatives", [(i32, A), (f32, A)], max_slots)               # the other sets: made on first switch-on
         self._forced = _StepBufs("forced", [(i32, ()), (f32, ()), (f32, ())], max_slots)
         self._beam = _StepBufs("beam", [(i32, ()), (i32, ()), (i32, ()), (f32, ()), (f32, ())], max_slots)
+        self._boost = _StepBufs("boost", [(i32, ()), (f32, ())], max_slots)
         self.mx_weights = None
         self.n_token_masks = 0
         self.n_pattern_states = 0
         self.n_lexicon_states = 0
+        self.n_boost_states = 0
         self.alternatives = False
         self.forced = False
         self.beam = 0
@@ -150,14 +152,14 @@ class HipRecModel:
         words = (self.vocab + 31) // 32
         if masks is None or len(masks) == 0:
             L.check(self.lib.surya_rec_set_token_masks(self.handle, None, C.c_int(0), self._stream), "surya_rec_set_token_masks")
-            self.n_token_masks = self.n_pattern_states = self.n_lexicon_states = 0      # (a new or dropped table switches patterns and the lexicon off)
+            self.n_token_masks = self.n_pattern_states = self.n_lexicon_states = self.n_boost_states = 0      # (a new or dropped table switches patterns, the lexicon and boosting off)
             return
         m = np.ascontiguousarray(np.asarray(masks, np.uint32))
         if m.ndim != 2 or m.shape[1] != words:
             raise ValueError(f"token masks must be [n, {words}] uint32 for a vocabulary of {self.vocab}, got {m.shape}")
         L.check(self.lib.surya_rec_set_token_masks(self.handle, L.np_ptr(m, C.c_uint32), C.c_int(m.shape[0]), self._stream),
                 "surya_rec_set_token_masks")
-        self.n_token_masks, self.n_pattern_states, self.n_lexicon_states = int(m.shape[0]), 0, 0
+        self.n_token_masks, self.n_pattern_states, self.n_lexicon_states, self.n_boost_states = int(m.shape[0]), 0, 0, 0
 
     def set_slot_masks(self, slots, mask_ids):
         """Mask id (row of the table, -1 = unconstrained) of the slots about to be prefilled; a slot keeps it until it is set again."""
@@ -235,6 +237,51 @@ class HipRecModel:
         buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
         L.check(self.lib.surya_rec_copy_lexicon_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_lexicon_states")
         return buf.cpu().numpy()
+
+    def set_boost(self, tables):
+        """The call's boost automaton (surya_rec_set_boost; recognition/boost.py::BoostTables, or anything with its edge_off / edge_tok /
+        edge_next arrays, `out_state` and `word_row`, the row of the uploaded token-mask table that holds the word-unit set), uploaded
+        behind the token-mask table. None switches the feature off. New tables set every slot back to "not boosted"; set_slot_boost
+        names root and beta of the slots about to be prefilled."""
+        if tables is None:
+            L.check(self.lib.surya_rec_set_boost(self.handle, None, None, None, C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), self._stream),
+                    "surya_rec_set_boost")
+            self.n_boost_states = 0
+            return
+        eo = np.ascontiguousarray(np.asarray(tables.edge_off, np.int32))
+        et = np.ascontiguousarray(np.asarray(tables.edge_tok, np.int32))
+        en = np.ascontiguousarray(np.asarray(tables.edge_next, np.int32))
+        if eo.ndim != 1 or len(eo) < 2 or et.ndim != 1 or en.shape != et.shape:
+            raise ValueError(f"boost tables must be edge_off [n_states + 1], edge_tok / edge_next [n_edges], got {eo.shape}, {et.shape}, {en.shape}")
+        L.check(self.lib.surya_rec_set_boost(self.handle, L.np_ptr(eo), L.np_ptr(et), L.np_ptr(en), C.c_int(len(eo) - 1), C.c_int(len(et)),
+                                             C.c_int(int(tables.out_state)), C.c_int(int(tables.word_row)), self._stream), "surya_rec_set_boost")
+        self.n_boost_states = int(len(eo) - 1)
+        self._boost.ensure()
+
+    def set_slot_boost(self, slots, roots, betas):
+        """Root state (-1 = not boosted: the slot keeps its mask id) and beta (logit units, finite, >= 0; a scalar or one per slot) of the
+        slots about to be prefilled, after set_slot_masks. The slot's state and row then follow its tokens on the device."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int32))
+        r = np.ascontiguousarray(np.asarray(roots, np.int32))
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(betas, np.float32), s.shape))
+        assert s.shape == r.shape and s.ndim == 1
+        L.check(self.lib.surya_rec_set_slot_boost(self.handle, L.np_ptr(s), L.np_ptr(r), L.np_ptr(b, C.c_float), C.c_int(len(s)), self._stream),
+                "surya_rec_set_slot_boost")
+
+    def copy_boost_states(self) -> np.ndarray:
+        """Sync; the boost state of every slot, int32 [max_slots] (-1 = not boosted). A test hook, like slot_states."""
+        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
+        L.check(self.lib.surya_rec_copy_boost_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_boost_states")
+        return buf.cpu().numpy()
+
+    def read_boost(self, n_steps: int = 1):
+        """Sync; (plain_tokens [n_steps, slots] int32, plain_probs [n_steps, slots] float32) of the steps read_outputs returns: the token
+        the model would have emitted without the boost, and the emitted token's probability without the boost."""
+        return self._boost.read(self, n_steps)
+
+    def wait_boost(self, n_steps: int, ring: int):
+        """The boost outputs of the decode_async call on `ring`, parallel to wait_outputs."""
+        return self._boost.wait(self, n_steps, ring)
 
     def set_alternatives(self, on: bool):
         """Report the SA_MAX_ALTERNATIVES most likely (allowed) tokens of every step beside the token itself (surya_rec_set_alternatives).

@@ -126,28 +126,28 @@ def _as_lexicon(x):
     return None
 
 
-def per_image_lexicons(arg, n_images) -> list:
-    """A `lexicon` argument as one entry per image: None, a LexiconKey, or a list with one None / LexiconKey per line. The argument is a
+def per_image_lexicons(arg, n_images, name="lexicon") -> list:
+    """A `lexicon` (or, under its `name`, `boost_words`) argument as one entry per image: None, a LexiconKey, or a list with one None / LexiconKey per line. The argument is a
     list of str (one lexicon for every line), or a list with one entry per image: None, a list of str, or a list per line of None /
     list of str."""
     if arg is None:
         return [None] * n_images
     if isinstance(arg, str) or not isinstance(arg, (list, tuple)):
-        raise TypeError(f"lexicon must be a list of str or a list with one entry per image, got {type(arg).__name__}")
+        raise TypeError(f"{name} must be a list of str or a list with one entry per image, got {type(arg).__name__}")
     if len(arg) == 0:
-        raise ValueError("lexicon is an empty list: a lexicon needs at least one entry")
+        raise ValueError(f"{name} is an empty list: a {name} needs at least one entry")
     whole = _as_lexicon(arg)
     if whole is not None:
         return [whole] * n_images
     if len(arg) != n_images:
-        raise ValueError(f"lexicon has {len(arg)} entries for {n_images} images")
+        raise ValueError(f"{name} has {len(arg)} entries for {n_images} images")
     out = []
     for i, e in enumerate(arg):
         if e is None:
             out.append(None)
             continue
         if isinstance(e, str) or not isinstance(e, (list, tuple)):
-            raise TypeError("an entry of lexicon is None, a list of str, or a list of None / list of str per line")
+            raise TypeError(f"an entry of {name} is None, a list of str, or a list of None / list of str per line")
         key = _as_lexicon(e)
         if key is not None:
             out.append(key)
@@ -157,8 +157,8 @@ def per_image_lexicons(arg, n_images) -> list:
             k = None if x is None else _as_lexicon(x)
             if x is not None and k is None:
                 if isinstance(x, (list, tuple)) and len(x) == 0:
-                    raise ValueError(f"image {i}: a lexicon is an empty list: it needs at least one entry")
-                raise TypeError("an entry of lexicon is None, a list of str, or a list of None / list of str per line")
+                    raise ValueError(f"image {i}: a {name} is an empty list: it needs at least one entry")
+                raise TypeError(f"an entry of {name} is None, a list of str, or a list of None / list of str per line")
             lines.append(k)
         out.append(lines)
     return out
@@ -173,9 +173,13 @@ class LineConstraints:
     pattern has mask id -1: its start state names its row. With lexicons: `lexicons` is the call's LexiconTables
     (recognition/lexicon.py), compiled once, and `per_image_lex[i]` the lexicon start state of image i's lines in the same two forms
     (-1 = no lexicon). A line takes a lexicon, a pattern, or an allowlist / blocklist, never two. A lexicon needs a mask table on the
-    device, so a call whose only constraints are lexicons gets one row that allows everything and that no line names."""
+    device, so a call whose only constraints are lexicons gets one row that allows everything and that no line names. With boosted
+    decoding: `boost` is the call's BoostTables (recognition/boost.py), compiled once for the call's distinct lists, whose word-unit
+    set is one more row of `table` (boost.word_row; so the table is never empty), and `per_image_root[i]` the root state of image i's
+    lines in the same two forms (-1 = not boosted). A boosted line takes no allowlist / blocklist; other lines of the call may."""
 
-    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None, pattern=None, lexicon=None):
+    def __init__(self, tokenizer, allowlist, blocklist, n_images, line_counts, vocab_size=None, limit=None, pattern=None, lexicon=None,
+                 boost_words=None):
         from .tokenizer import MaskTable
         self.table = MaskTable(tokenizer, vocab_size, limit)
         allow, block = per_image_lists(allowlist, "allowlist", n_images), per_image_lists(blocklist, "blocklist", n_images)
@@ -213,6 +217,37 @@ class LineConstraints:
         lex = per_image_lexicons(lexicon, n_images)
         if any(x is not None for x in lex):
             self._add_lexicons(tokenizer, lex, per_image_pat, line_counts, vocab_size)
+        self.boost, self.per_image_root = None, None
+        bw = per_image_lexicons(boost_words, n_images, "boost_words")
+        if any(x is not None for x in bw):
+            self._add_boost(tokenizer, bw, line_counts, vocab_size)
+
+    def _add_boost(self, tokenizer, bw, line_counts, vocab_size):
+        if self.patterns is not None or self.lexicons is not None:
+            raise ValueError("boost_words is not available with pattern or lexicon")
+        for i, (x, ids) in enumerate(zip(bw, self.per_image)):
+            if x is None:
+                continue
+            if not isinstance(x, list) and not isinstance(ids, list):
+                if ids != -1:
+                    raise ValueError(f"image {i}: a boosted line takes no allowlist / blocklist")
+                continue
+            if line_counts is None:
+                raise ValueError("per-line boost_words need bboxes or polygons: with det_predictor the lines are not known yet")
+            n = line_counts[i]
+            x, ids = (v if isinstance(v, list) else [v] * n for v in (x, ids))
+            if len(x) != n:
+                raise ValueError(f"image {i} has {n} lines but its boost_words entry has {len(x)}")
+            for j, (k, y) in enumerate(zip(x, ids)):
+                if k is not None and y != -1:
+                    raise ValueError(f"image {i}, line {j}: a boosted line takes no allowlist / blocklist")
+        distinct = list(dict.fromkeys(k for x in bw for k in (x if isinstance(x, list) else [x]) if k is not None))
+        from .boost import compile_boost
+        self.boost = compile_boost(tokenizer, distinct, vocab_size)
+        self.boost.word_row = self.table.add_row(self.boost.word_mask, "allowlists / blocklists (boost_words take one row)")
+        root = {k: r for k, r in zip(distinct, self.boost.roots)}
+        root[None] = -1
+        self.per_image_root = [[root[k] for k in x] if isinstance(x, list) else root[x] for x in bw]
 
     def _add_lexicons(self, tokenizer, lex, per_image_pat, line_counts, vocab_size):
         for i, (lx, ids, p) in enumerate(zip(lex, self.per_image, per_image_pat)):
@@ -260,6 +295,10 @@ class LineConstraints:
     def line_lexicon_starts(self, slice_map) -> list:
         """One lexicon start state per line (-1 = no lexicon), like line_ids; a call with lexicons only."""
         return self.line_ids(slice_map, self.per_image_lex)
+
+    def line_boost_roots(self, slice_map) -> list:
+        """One boost root state per line (-1 = not boosted), like line_ids; a call with boost_words only."""
+        return self.line_ids(slice_map, self.per_image_root)
 
 
 class AssemblyHandover(ThreadPoolExecutor):
@@ -479,6 +518,8 @@ class RecognitionPredictor(BasePredictor):
             prep.update(pattern_tables=flat["pattern_tables"], start_states=flat["start_states"])
         if flat.get("lexicon_tables") is not None:            # ... and with lexicons theirs
             prep.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=flat["lexicon_starts"])
+        if flat.get("boost_tables") is not None:              # ... and with boost_words the automaton, beta and one root per line
+            prep.update(boost_tables=flat["boost_tables"], boost_weight=flat["boost_weight"], boost_roots=flat["boost_roots"])
         if flat.get("forced_ids") is not None:                # align(): one forced id list per line
             prep["forced_ids"] = flat["forced_ids"]
         return prep
@@ -506,6 +547,8 @@ class RecognitionPredictor(BasePredictor):
         self.last_packed = (PackedLines(loop.tok_mat, loop.line_len), PackedLines(loop.sc_mat, loop.line_len))
         if "forced" in more:                                  # ... an aligned call's greedy ids, their probabilities, the log-probabilities
             self.last_forced = tuple(PackedLines(a, loop.line_len) for a in (loop.greedy_tok_mat, loop.greedy_p_mat, loop.logp_mat))
+        if first.get("boost_tables") is not None:             # ... a boosted call's plain readings [n, cap]
+            self.last_boost = (PackedLines(loop.plain_tok_mat, loop.line_len), PackedLines(loop.plain_p_mat, loop.line_len))
         if "alternatives" in more:                            # ... and the alternatives [n, cap, 4] likewise
             self.last_alternatives = (PackedLines(loop.alt_tok_mat, loop.line_len), PackedLines(loop.alt_p_mat, loop.line_len))
         return loop.predicted_tokens, torch.from_numpy(loop.batch_bboxes), loop.scores
@@ -544,8 +587,11 @@ class RecognitionPredictor(BasePredictor):
             local.update(pattern_tables=flat["pattern_tables"], start_states=[flat["start_states"][i] for i in mine])
         if flat.get("lexicon_tables") is not None:
             local.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=[flat["lexicon_starts"][i] for i in mine])
+        if flat.get("boost_tables") is not None:
+            local.update(boost_tables=flat["boost_tables"], boost_weight=flat["boost_weight"], boost_roots=[flat["boost_roots"][i] for i in mine])
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
-        alts = None
+        alts = plain = None
+        boosted = flat.get("boost_tables") is not None
         if mine:
             self.last_packed = None                          # only what generate() sets DURING this call counts (a stand-in prediction_loop
             toks, boxes, scores = self.prediction_loop(local, recognition_batch_size, math_mode)      # must not gather an earlier call's arrays)
@@ -554,11 +600,21 @@ class RecognitionPredictor(BasePredictor):
                 toks, scores = packed
             self.last_packed = None                          # (and the [n, cap] matrices are not pinned on the predictor between calls)
             alts, self.last_alternatives = getattr(self, "last_alternatives", None), None
+            plain, self.last_boost = getattr(self, "last_boost", None), None
             boxes = boxes.numpy()
             if boxes.shape[1] < max_tokens:
                 boxes = np.pad(boxes, ((0, 0), (0, max_tokens - boxes.shape[1]), (0, 0)))
         else:
             toks, scores, boxes = [], [], np.zeros((0, max_tokens, 6), np.float32)
+        if boosted:                                          # the plain readings ride in the alternatives' places of the same collective:
+            w1 = lambda pl: sdist.PackedLines(pl.data[:, :, None], pl.lens)      # one "alternative" per token (boost_words exclude top_k)
+            if plain is None:
+                plain = (sdist.PackedLines(np.zeros((0, max_tokens), np.int32), np.zeros(0, np.int64)),
+                         sdist.PackedLines(np.zeros((0, max_tokens), np.float32), np.zeros(0, np.int64)))
+            toks, scores, boxes, a_tok, a_p = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group,
+                                                                        alts=(w1(plain[0]), w1(plain[1])))
+            self.last_boost = (sdist.PackedLines(a_tok.data[:, :, 0], a_tok.lens), sdist.PackedLines(a_p.data[:, :, 0], a_p.lens))
+            return toks, torch.from_numpy(boxes), scores
         if self._top_k is not None:                          # the two alternative arrays ride in the same collective
             if alts is None:
                 alts = (sdist.PackedLines(np.zeros((0, max_tokens, 4), np.int32), np.zeros(0, np.int64)),
@@ -634,6 +690,17 @@ class RecognitionPredictor(BasePredictor):
         proper prefix of an entry; None without a lexicon. `top_k` works with it. ValueError, before any device work, with `beam_width`,
         in `align`, for an empty list, an empty entry and an entry the model's vocabulary cannot write.
 
+        `self.boost_words` (an attribute like `lexicon`, in the same three forms; None = off) PREFERS the entries of a word list -- drug
+        names, surnames, part numbers -- without forbidding anything else: wherever the tokens so far could be the beginning of an
+        entry that began at a word boundary, the entry's next character gets `self.boost_weight` (logit units, a finite float >= 0,
+        required, no default) added to its logit. Entries are verbatim and may hold spaces and punctuation. The line still reads every
+        word that is not listed. A boost that was spent on a match that then died is not taken back, so use a moderate weight.
+        `TextLine.boost_matches` lists the entries (indices in the line's own list) that were read in full, in order of completion;
+        `TextChar.plain` is the character the model would have emitted without the boost, `TextChar.plain_confidence` the emitted
+        character's probability without it; confidences are softmax values of the boosted distribution. All three are None on lines
+        that are not boosted. Other lines of the call may carry allowlists; a boosted line takes none. ValueError, before any device
+        work, with `top_k`, `beam_width`, `pattern` or `lexicon`, without `boost_weight`, and in `align`.
+
         `self.beam_width` (an attribute like `top_k`; None = greedy, else 2..4): beam search on the device. Every TextLine carries
         `hypotheses`, its up to beam_width best readings as LineHypothesis(text, confidence, log_prob, finished, chars) -- finished
         readings by log_prob descending, then the ones the token budget or the repeat rule cut -- each assembled like a line
@@ -655,6 +722,16 @@ class RecognitionPredictor(BasePredictor):
         lexicon = self.lexicon
         if lexicon is not None and beam is not None:
             raise ValueError("lexicon is not available with beam_width: a beam would have to inherit its parent's automaton state and row")
+        boost_words, boost_weight = self.boost_words, self.boost_weight
+        if boost_words is not None:
+            for name, v in (("top_k", top_k), ("beam_width", beam), ("pattern", pattern), ("lexicon", lexicon)):
+                if v is not None:
+                    raise ValueError(f"boost_words is not available with {name}: the boosted head runs the masked and the plain greedy "
+                                     f"lm_head epilogues and owns the slot's mask row")
+            if boost_weight is None:
+                raise ValueError("boost_words needs boost_weight, the boost in logit units (a finite float >= 0); it has no default")
+            if isinstance(boost_weight, bool) or not isinstance(boost_weight, (int, float)) or not 0 <= boost_weight < float("inf"):
+                raise ValueError(f"boost_weight must be a finite float >= 0, got {boost_weight!r}")
         # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
         # page-sharded path and by stand-ins and read it from here)
         saved_k, self._top_k = self._top_k, top_k
@@ -662,7 +739,7 @@ class RecognitionPredictor(BasePredictor):
         try:
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                                        pattern, lexicon)
+                                        pattern, lexicon, boost_words, boost_weight)
         finally:
             self._top_k, self._beam = saved_k, saved_b
             if top_k is not None:
@@ -706,6 +783,8 @@ class RecognitionPredictor(BasePredictor):
             raise ValueError("pattern does not apply to align(): forced decoding reads no allowed set (set pattern = None)")
         if self.lexicon is not None:
             raise ValueError("lexicon does not apply to align(): forced decoding reads no allowed set (set lexicon = None)")
+        if self.boost_words is not None:
+            raise ValueError("boost_words do not apply to align(): the text is given, there is nothing to prefer (set boost_words = None)")
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         if self.shard_lines or self.shard_pages or self.process_group is not None:
@@ -773,12 +852,15 @@ class RecognitionPredictor(BasePredictor):
     _beam = None                      # the running call's validated beam_width (see __call__)
     pattern = None                    # regex per call / image / line (see __call__), None = off: set on an instance, e.g. pred.pattern = r"\d+"
     lexicon = None                    # word list per call / image / line (see __call__), None = off: pred.lexicon = ["Alabama", "Alaska", ...]
+    boost_words = None                # word list per call / image / line to PREFER (see __call__), None = off: pred.boost_words = ["Paracetamol", ...]
+    boost_weight = None               # ... and the boost in logit units, a finite float >= 0: required with boost_words, no default
+    last_boost = None
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
 
     def _call_gc_paused(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                        pattern=None, lexicon=None):
+                        pattern=None, lexicon=None, boost_words=None, boost_weight=None):
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
             # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
@@ -787,12 +869,14 @@ class RecognitionPredictor(BasePredictor):
                 lists["pattern"] = pattern
             if lexicon is not None:
                 lists["lexicon"] = lexicon
+            if boost_words is not None:
+                lists.update(boost_words=boost_words, boost_weight=boost_weight)
             return self._call(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                               bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
 
-    def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None, lexicon=None):
-        """The call's LineConstraints, or None for a call without lists, patterns or lexicons (or whose entries are all None)."""
-        if allowlist is None and blocklist is None and pattern is None and lexicon is None:
+    def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None, lexicon=None, boost_words=None):
+        """The call's LineConstraints, or None for a call without lists, patterns, lexicons or boost_words (or whose entries are all None)."""
+        if allowlist is None and blocklist is None and pattern is None and lexicon is None and boost_words is None:
             return None
         given = polygons if polygons is not None else bboxes
         if given is not None and len(given) != len(images):
@@ -801,12 +885,12 @@ class RecognitionPredictor(BasePredictor):
         from .. import _lib as L
         cons = LineConstraints(self.processor.ocr_tokenizer, allowlist, blocklist, len(images), counts,
                                vocab_size=getattr(self.model, "vocab", None), limit=L.SA_MAX_TOKEN_MASKS, pattern=pattern,
-                               lexicon=lexicon)
+                               lexicon=lexicon, boost_words=boost_words)
         return cons if cons else None
 
     def _call(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images, bboxes,
               polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None,
-              pattern=None, lexicon=None) -> List[OCRResult]:
+              pattern=None, lexicon=None, boost_words=None, boost_weight=None) -> List[OCRResult]:
         if getattr(self, "_poisoned", None):
             raise RuntimeError(self._poisoned)
         allowed = self.tasks.keys()
@@ -821,7 +905,9 @@ class RecognitionPredictor(BasePredictor):
         if highres_images is not None:
             assert len(images) == len(highres_images), "You need to pass in one highres image for each image"
         highres_images = convert_if_not_rgb(highres_images) if highres_images is not None else [None] * len(images)
-        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons, pattern, lexicon)
+        cons = self._constraints(allowlist, blocklist, images, bboxes, polygons, pattern, lexicon, boost_words)
+        if cons is not None and cons.boost is not None:
+            cons.boost_weight = float(boost_weight)
 
         if bboxes is None and polygons is None:
             assert det_predictor is not None, (
@@ -834,6 +920,8 @@ class RecognitionPredictor(BasePredictor):
                         lists["pattern"] = pattern
                     if cons is not None and cons.lexicons is not None:
                         lists["lexicon"] = lexicon
+                    if cons is not None and cons.boost is not None:
+                        lists.update(boost_words=boost_words, boost_weight=boost_weight)
                     return self._call_page_sharded(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
                                                    highres_images, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
             if self._can_stream(det_predictor):
@@ -861,6 +949,9 @@ class RecognitionPredictor(BasePredictor):
             if cons.lexicons is not None:
                 flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, cons.line_lexicon_starts(flat["slice_map"])
                 sorted_keys += ("lexicon_starts",)
+            if cons.boost is not None:
+                flat.update(boost_tables=cons.boost, boost_weight=cons.boost_weight, boost_roots=cons.line_boost_roots(flat["slice_map"]))
+                sorted_keys += ("boost_roots",)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
@@ -874,6 +965,8 @@ class RecognitionPredictor(BasePredictor):
                 bb = batch_bboxes.numpy()
                 chunks = [range(a, min(a + 256, len(order))) for a in range(0, len(order), 256)]
                 la = self.last_alternatives if self._top_k is not None else None
+                if flat.get("boost_tables") is not None:      # the plain readings travel like the alternatives
+                    la, self.last_boost = getattr(self, "last_boost", None), None
                 alt_of = (lambda k: ()) if la is None else (lambda k: ((la[0].row(k), la[1].row(k)),))
                 text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) + alt_of(k) for k in ks])) for ks in chunks)
             else:
@@ -904,7 +997,7 @@ class RecognitionPredictor(BasePredictor):
 
     def _call_page_sharded(self, images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                            sort_lines, math_mode, return_words, drop_repeated_text, allowlist=None, blocklist=None, pattern=None,
-                           lexicon=None) -> list:
+                           lexicon=None, boost_words=None, boost_weight=None) -> list:
         from .. import dist as sdist
         group = self.process_group
         rank, world = sdist.world_info(group)
@@ -928,6 +1021,11 @@ class RecognitionPredictor(BasePredictor):
             per = per_image_lexicons(lexicon, n)
             lists["lexicon"] = [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list)
                                 else list(per[i]) for i in mine]
+        if boost_words is not None:                           # ... and the boost lists, likewise; beta is the call's
+            per = per_image_lexicons(boost_words, n, "boost_words")
+            lists["boost_words"] = [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list)
+                                    else list(per[i]) for i in mine]
+            lists["boost_weight"] = boost_weight
         try:
             hr = [highres_images[i] for i in mine]
             local = self._call([images[i] for i in mine], [task_names[i] for i in mine], det_predictor, detection_batch_size,
@@ -995,6 +1093,9 @@ class RecognitionPredictor(BasePredictor):
         with_lexicons = cons is not None and cons.lexicons is not None
         if with_lexicons:
             flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, []
+        with_boost = cons is not None and cons.boost is not None
+        if with_boost:
+            flat.update(boost_tables=cons.boost, boost_weight=cons.boost_weight, boost_roots=[])
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
@@ -1010,6 +1111,7 @@ class RecognitionPredictor(BasePredictor):
                     if stop.is_set():
                         break
                     pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all, lex_all = [], [], [], [], [], [], [], []
+                    roots_all = []
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
@@ -1023,6 +1125,8 @@ class RecognitionPredictor(BasePredictor):
                                 states_all.extend([cons.per_image_state[page]] * len(polygons))
                             if with_lexicons:
                                 lex_all.extend([cons.per_image_lex[page]] * len(polygons))
+                            if with_boost:
+                                roots_all.extend([cons.per_image_root[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -1043,12 +1147,15 @@ class RecognitionPredictor(BasePredictor):
                         flat["start_states"].extend(states_all[i] for i in order)
                     if with_lexicons:
                         flat["lexicon_starts"].extend(lex_all[i] for i in order)
+                    if with_boost:
+                        flat["boost_roots"].extend(roots_all[i] for i in order)
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
                            "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts},
                            "mask_ids": [masks_all[i] for i in order] if cons is not None else None,
                            "start_states": [states_all[i] for i in order] if with_patterns else None,
-                           "lexicon_starts": [lex_all[i] for i in order] if with_lexicons else None})
+                           "lexicon_starts": [lex_all[i] for i in order] if with_lexicons else None,
+                           "boost_roots": [roots_all[i] for i in order] if with_boost else None})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -1080,6 +1187,8 @@ class RecognitionPredictor(BasePredictor):
                             first["pattern_tables"] = cons.patterns
                         if with_lexicons:
                             first["lexicon_tables"] = cons.lexicons
+                        if with_boost:
+                            first.update(boost_tables=cons.boost, boost_weight=cons.boost_weight)
                     self.generate(first, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...

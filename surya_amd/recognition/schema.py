@@ -55,12 +55,19 @@ class TextChar(BaseChar):
     # `greedy` (RecognitionPredictor.align): the model's own reading at the token the character takes its confidence from -- text,
     # probability, token id; it equals the character where the model agrees with the aligned text. None, and left out like
     # `alternatives`, everywhere else.
+    # `plain` / `plain_confidence` (RecognitionPredictor.boost_words): the character the model would have emitted here without the boost,
+    # given the same prefix, and the emitted character's probability without the boost, both at the token the character takes its
+    # confidence from (the rule of `greedy`). None, and left out likewise, on every line that was not boosted.
     if _EXCLUDE_IF:
         alternatives: Optional[List[CharAlternative]] = Field(default=None, exclude_if=lambda v: v is None)
         greedy: Optional[CharAlternative] = Field(default=None, exclude_if=lambda v: v is None)
+        plain: Optional[str] = Field(default=None, exclude_if=lambda v: v is None)
+        plain_confidence: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         alternatives: Optional[List[CharAlternative]] = None
         greedy: Optional[CharAlternative] = None
+        plain: Optional[str] = None
+        plain_confidence: Optional[float] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_alternatives(self, handler):
@@ -69,6 +76,10 @@ class TextChar(BaseChar):
                 d.pop("alternatives", None)
             if self.greedy is None:
                 d.pop("greedy", None)
+            if self.plain is None:
+                d.pop("plain", None)
+            if self.plain_confidence is None:
+                d.pop("plain_confidence", None)
             return d
 
 
@@ -103,16 +114,20 @@ class TextLine(BaseChar):
     # `lexicon_index` (RecognitionPredictor.lexicon): the index, in the line's own word list, of the entry the line read -- >= 0 iff the
     # line ended (EOS or pad) on a whole entry; -1 for a line cut by the token budget, the repeat rule or the no-output token (its text is
     # then a proper prefix of an entry, or empty). None, and left out likewise, for a line without a lexicon.
+    # `boost_matches` (RecognitionPredictor.boost_words): the indices, in the line's own list, of the entries some live match completed
+    # while the line was read, in order of completion, each once; [] if none. None, and left out likewise, for a line that was not boosted.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
         hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
         pattern_matched: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
         lexicon_index: Optional[int] = Field(default=None, exclude_if=lambda v: v is None)
+        boost_matches: Optional[List[int]] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
         hypotheses: Optional[List[LineHypothesis]] = None
         pattern_matched: Optional[bool] = None
         lexicon_index: Optional[int] = None
+        boost_matches: Optional[List[int]] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
@@ -125,6 +140,8 @@ class TextLine(BaseChar):
                 d.pop("pattern_matched", None)
             if self.lexicon_index is None:
                 d.pop("lexicon_index", None)
+            if self.boost_matches is None:
+                d.pop("boost_matches", None)
             return d
 
 

@@ -5,7 +5,7 @@ For every tuning configuration (surya_set_tuning, csrc/common.h sa::Tuning) this
 read, and reports wall us/step (HIP events around the whole run) plus whether the greedy tokens equal the first
 configuration's (tile / split-K changes re-order fp32 sums, so bf16 argmax near-ties may flip; reported, not asserted).
 
-    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced|patterns|lexicon] [--fp8] [--slots N]
+    python tools/microbench/decode_sweep.py [--steps 32] [--configs all|base|fp8|mxbigm|masks|alts|forced|patterns|lexicon|boost] [--fp8] [--slots N]
 
 `fp8`: bf16 decode vs the MXFP8 decode path (HipRecModel.set_decode_fp8, csrc/gemm_mx.h) on the same lines.
 `--fp8`: every arm runs with set_decode_fp8(True) unless it says fp8=0 itself.
@@ -35,6 +35,13 @@ arms alternating in one process: unmasked / masks only / the date pattern / a le
 three identical unmasked arms, whose spread is the noise band. lex=1 is 2000 random five-digit codes (a line is complete after 6 tokens
 and keeps its state and row from then on), lex=2 is 300 entries with 300 different first characters and 40 digits each: a root with 300
 children, and a transition at every step of the run. `lexicononly` / `lexiconwide`: the lex=1 / lex=2 arm alone (for a kernel trace).
+
+`boost`: boosted decoding (HipRecModel.set_boost: a second, unmasked lm_head launch, boost_head_kernel in place of the greedy head and
+boost_step_kernel behind it), arms alternating in one process: unmasked / masks only / boost on every slot, twice, then unmasked once
+more -- three identical unmasked arms, whose spread is the noise band. bst=1 is 2000 random lower-case words of 5 to 9 letters at beta =
+8 (on random weights most slots sit in the state without edges and rewrite nothing); bst=2 is 300 two-unit entries with 300 different
+first characters and a full stop at beta = 1e4: every slot alternates between the root's 300-bit set and a one-bit set, a row rewrite at
+every step. `boostonly` / `boostwide`: the bst=1 / bst=2 arm alone (for a kernel trace).
 
 The tile-shape / dual-stream / lm_head-ring / skinny-GEMM variants swept in round 2 lost and were removed from the library; their
 results are in profiles/r02_decode_sweeps.md.
@@ -118,6 +125,11 @@ def main():
         variants = arms + arms + [dict()]
     elif args.configs in ("lexicononly", "lexiconwide"):     # one arm, a lexicon on every slot (for a kernel trace)
         variants = [dict(lex=1 if args.configs == "lexicononly" else 2)]
+    elif args.configs == "boost":        # boosted decoding against unmasked / masks only, alternating
+        arms = [dict(), dict(masks=1), dict(bst=1), dict(bst=2)]
+        variants = arms + arms + [dict()]
+    elif args.configs in ("boostonly", "boostwide"):         # one arm, boosting on every slot (for a kernel trace)
+        variants = [dict(bst=1 if args.configs == "boostonly" else 2)]
     elif args.configs == "alts":         # alternatives: off against on, alternating
         variants = [dict(), dict(alts=1), dict(), dict(alts=1), dict()]
     elif args.configs == "altsonly":
@@ -142,8 +154,12 @@ def main():
 
     pat_start = [None]
     lex_start = [None]
+    bst_start = [None]                               # (root, beta)
 
     def run(n_steps):
+        if bst_start[0] is not None:                 # every run starts every slot at its root again
+            m.set_slot_masks(slots, [-1] * n)
+            m.set_slot_boost(slots, [bst_start[0][0]] * n, bst_start[0][1])
         if lex_start[0] is not None:                 # every run starts every slot's lexicon again
             m.set_slot_masks(slots, [-1] * n)
             m.set_slot_lexicon(slots, [lex_start[0]] * n)
@@ -170,6 +186,8 @@ def main():
                 m.wait_alternatives(*call)               # what the device loop reads beside the tokens
             if m.forced:
                 m.wait_forced(*call)
+            if m.n_boost_states:
+                m.wait_boost(*call)
             toks.append(t[: call[0], :n].copy())
         e1.record()
         torch.cuda.synchronize()
@@ -216,7 +234,25 @@ def main():
         m.set_lexicon(lt)
         lex_start[0] = lt.starts[0]
 
+    def set_boost(kind):                         # 0 = off (the mask table goes too), 1 = 2000 words at beta 8, 2 = a root with 300 children at 1e4
+        bst_start[0] = None
+        if not kind:
+            return m.set_token_masks(None)
+        import random
+        from surya_amd.recognition.boost import compile_boost
+        from surya_amd.recognition.loader import RecognitionModelLoader
+        tk = RecognitionModelLoader({"config": cfg, "state_dict": {}}).processor().ocr_tokenizer
+        r = random.Random(2)
+        entries = (["".join(r.choice("abcdefghijklmnopqrstuvwxyz") for _ in range(r.randint(5, 9))) for _ in range(2000)] if kind == 1 else
+                   [chr(0x100 + k) + "." for k in range(300)])
+        bt = compile_boost(tk, [entries], cfg.decoder.vocab_size)
+        bt.word_row = 0
+        m.set_token_masks(bt.word_mask[None])        # (boosting needs a mask table: the word-unit row)
+        m.set_boost(bt)
+        bst_start[0] = (bt.roots[0], 8.0 if kind == 1 else 1e4)
+
     lex_cfg = args.configs in ("lexicon", "lexicononly", "lexiconwide")
+    bst_cfg = args.configs in ("boost", "boostonly", "boostwide")
     ref = {}
     print(f"# REC-FULL bf16, {n} active slots, {args.steps} decode steps per run, us/step (event) | us/step (host wall) | tokens == first arm of the same arithmetic")
     for v in variants:
@@ -233,13 +269,18 @@ def main():
         lex = v.pop("lex", 0)
         if lex_cfg:
             set_lexicon(lex)                         # (off: the mask table and patterns go too; the arm's own constraint follows)
+        bst = v.pop("bst", 0)
+        if bst_cfg:
+            set_boost(bst)                           # (likewise)
+            if masks:
+                set_masks(masks)
         if pat:
             set_patterns(pat)
         elif args.configs in ("patterns", "patternonly"):
             set_patterns(0)
             if masks:
                 set_masks(masks)
-        if masks or args.configs in ("masks", "maskonly"):
+        if (masks and not bst_cfg) or args.configs in ("masks", "maskonly"):
             set_masks(masks)
         setk(**{**base, **v})
         v = {**v, "fp8": int(m.decode_fp8)}
@@ -249,6 +290,8 @@ def main():
                 v["pat"] = pat
             if lex_cfg:
                 v["lex"] = lex
+        if bst_cfg:
+            v.update(masks=masks, bst=bst)
         if args.configs in ("alts", "altsonly"):
             v["alts"] = alts
         if args.configs in ("forced", "forcedonly"):
@@ -256,12 +299,12 @@ def main():
         run(8)                                   # warm-up (attribute set, graph capture on 2nd sight)
         run(8)
         best = min((run(args.steps) for _ in range(3)), key=lambda r: r[0])
-        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0), v.get("pat", 0), v.get("lex", 0)), best[2])).all(axis=0).mean())
+        same = float((best[2] == ref.setdefault((v["fp8"], v.get("masks", 0), v.get("forced", 0), v.get("pat", 0), v.get("lex", 0), v.get("bst", 0)), best[2])).all(axis=0).mean())
         print(f"{str(v):90s} {best[0]:8.1f} {best[1]:8.1f}   lines identical {same:.3f}", flush=True)
     setk(**base)
     m.set_decode_fp8(False)
-    if args.configs in ("masks", "maskonly", "patterns", "patternonly") or lex_cfg:
-        m.set_token_masks(None)                      # (which switches patterns and the lexicon off as well)
+    if args.configs in ("masks", "maskonly", "patterns", "patternonly") or lex_cfg or bst_cfg:
+        m.set_token_masks(None)                      # (which switches patterns, the lexicon and boosting off as well)
     if args.configs in ("alts", "altsonly"):
         m.set_alternatives(False)
     if args.configs in ("forced", "forcedonly"):
