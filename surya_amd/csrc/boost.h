@@ -6,12 +6,12 @@
 //     lm_head, masked greedy epilogue   -> record A of every row, over S      (gemm.h / gemm_mx.h, unchanged)
 //     lm_head, unmasked greedy epilogue -> record B, over every column        (a second partial buffer)
 //     boost_head_kernel                 -> reduces both, boost_core.h decides: token, score, plain reading, box, fused next embedding
-//     boost_step_kernel                 -> the slot's next state and row
+//     automaton_step_kernel<true>       -> the slot's next state and row   (lexicon.h: the lexicon's step kernel with the fallback)
 // A slot that is not boosted (state -1) carries beta = +inf: record A alone, the bits of greedy_head2_kernel on it.
 //
-// The launch code below is the only place that launches the three kernels: the engine (rec_engine.h) and the op hooks
-// (surya_op_rec_boost_step / surya_op_rec_boost_head) both go through it. The kernels read the tables unchecked: the engine validates them
-// on the host (RecModel::set_boost), a caller of the op hooks answers for its own. Plain vector stores and vector atomics only.
+// The launch code below is the only place that launches the head and the boost's start and step: the engine (rec_engine.h) and the op
+// hooks (surya_op_rec_boost_step / surya_op_rec_boost_head) both go through it. The kernels read the tables unchecked: the engine
+// validates them on the host (automaton_core.h), a caller of the op hooks answers for its own. Plain vector stores and vector atomics only.
 #pragma once
 #include "kernels.h"
 #include "lexicon.h"
@@ -19,69 +19,12 @@
 
 namespace sa {
 
-#define SA_BOOST_STEP_THREADS 64        // one wave, as lexicon_step_kernel
+#define SA_BOOST_STEP_THREADS SA_LEXICON_STEP_THREADS      // the same kernel template, one wave
 
-struct BoostArgs {
+struct BoostArgs : TotalOps {           // slot_root, slot_beta, out_state, word_row (lexicon.h)
     LexiconArgs lx;                     // the CSR tables, the mask table and slot_state = the slots' boost states (state_flags: all 0;
                                         // eos / pad / nop are never preferred)
-    int* slot_root = nullptr;           // [slots]: the root state of the slot's list, -1 = not boosted
-    float* slot_beta = nullptr;         // [slots]: the boost in logit units, +inf = not boosted
-    int out_state = 0;                  // the shared state without edges
-    int word_row = 0;                   // row of the mask table that holds the word-unit set
 };
-
-// Workgroup i: slot slots[i] starts at roots[i] with boost betas[i]. Root -1 (or roots == nullptr) = not boosted: state and root -1, beta
-// +inf, the slot's mask id and row are left alone. Else the whole row is zeroed (a previous occupant's bits may be anywhere), the root's
-// set is written and the slot's mask id names the row.
-static __global__ __launch_bounds__(SA_LEXICON_START_THREADS) void boost_start_kernel(BoostArgs b, const int* __restrict__ slots,
-                                                                                const int* __restrict__ roots, const float* __restrict__ betas) {
-    const LexiconArgs& a = b.lx;
-    const int slot = slots[blockIdx.x], st = roots ? roots[blockIdx.x] : -1;
-    if (threadIdx.x == 0) {
-        a.slot_state[slot] = st;
-        b.slot_root[slot] = st;
-        b.slot_beta[slot] = st < 0 ? INFINITY : betas[blockIdx.x];
-    }
-    if (st < 0) return;                                       // (workgroup-uniform)
-    uint32_t* row = a.table + (long)(a.row_base + slot) * a.words;
-    for (int w = threadIdx.x; w < a.words; w += SA_LEXICON_START_THREADS) row[w] = 0u;
-    __syncthreads();                                          // the zeros are in place before any bit is set
-    lexicon_apply<true>(a, row, st);
-    if (threadIdx.x == 0) a.slot_mask[slot] = a.row_base + slot;
-}
-
-// Workgroup r: row r of the step, slot row_slot[r], whose head just wrote out_token[slot]. A slot that is not boosted, a row that ended
-// (eos / pad) and an id outside the vocabulary keep state and row. Else the next state is the edge's target, or the fallback: the shared
-// out_state for a word unit, the slot's root for a boundary. A state that stays (word after word outside every entry) rewrites nothing;
-// else: clear the old set's words, barrier -- the old and the new set commonly share words --, set the new set's bits, store the state.
-// Sets may be empty.
-static __global__ __launch_bounds__(SA_BOOST_STEP_THREADS) void boost_step_kernel(BoostArgs b, const int* __restrict__ row_slot,
-                                                                             const int* __restrict__ out_token) {
-    const LexiconArgs a = b.lx;                               // (a copy: a reference into the by-value argument costs the lambdas scratch)
-    const int slot = row_slot[blockIdx.x], st = a.slot_state[slot];
-    if (st < 0) return;                                       // (every exit before the barrier is workgroup-uniform)
-    const int t = out_token[slot];
-    if (t == a.eos_id || t == a.pad_id || (unsigned)t >= (unsigned)a.vocab) return;
-    const int e1 = a.edge_off[st + 1];
-    int lo = a.edge_off[st], hi = e1;                         // binary search, every lane the same one
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a.edge_tok[mid] < t) lo = mid + 1; else hi = mid;
-    }
-    int ns;
-    if (lo < e1 && a.edge_tok[lo] == t) {
-        ns = a.edge_next[lo];
-    } else {
-        const uint32_t w = a.table[(long)b.word_row * a.words + (t >> 5)];
-        ns = (w >> (t & 31)) & 1u ? b.out_state : b.slot_root[slot];
-    }
-    if (ns == st) return;
-    uint32_t* row = a.table + (long)(a.row_base + slot) * a.words;
-    lexicon_apply<false>(a, row, st);
-    __syncthreads();
-    lexicon_apply<true>(a, row, ns);
-    if (threadIdx.x == 0) a.slot_state[slot] = ns;
-}
 
 // The boosted head: greedy_head2_kernel (kernels.h) on two records per row. `h` carries what that kernel takes (its forced / pattern /
 // alternatives members stay empty), h.part record A's per-tile partials, part_b record B's, same tiling. Both rows of partials (<= 4 per
@@ -202,15 +145,12 @@ __global__ __launch_bounds__(SA_HEAD_THREADS) void boost_head_kernel(BoostHeadAr
         embed_norm_row<T, NT>(a.table + (long)tok_next * H, a.x + (long)r * H, a.wnorm, a.y + (long)r * H, H, a.eps, red, a.y8, a.sy, a.srows, r);
 }
 
+// automaton_start_kernel<true> / automaton_step_kernel<true> (lexicon.h) on the boost's operands.
 inline int launch_boost_start(const BoostArgs& b, const int* slots, const int* roots, const float* betas, int n, hipStream_t s) {
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL(boost_start_kernel, dim3(n), dim3(SA_LEXICON_START_THREADS), 0, s, b, slots, roots, betas);
-    return (int)hipGetLastError();
+    return launch_automaton_start<true>(b.lx, b, slots, roots, betas, n, s);
 }
 inline int launch_boost_step(const BoostArgs& b, const int* row_slot, const int* out_token, int rows, hipStream_t s) {
-    if (rows <= 0) return 0;
-    hipLaunchKernelGGL(boost_step_kernel, dim3(rows), dim3(SA_BOOST_STEP_THREADS), 0, s, b, row_slot, out_token);
-    return (int)hipGetLastError();
+    return launch_automaton_step<true>(b.lx, b, row_slot, out_token, rows, s);
 }
 // Where greedy_head_kernel<T, true> would have to run instead of the partials head (launch_head, kernels.h): SA_ERR_STATE, fused or not.
 template <typename T>

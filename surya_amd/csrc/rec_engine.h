@@ -19,6 +19,7 @@
 #include "decode_attn_kv8.h"
 #include "attn_mfma.h"
 #include "beam.h"
+#include "automaton_core.h"
 #include "lexicon.h"
 #include "boost.h"
 
@@ -91,6 +92,69 @@ struct DevBlock {   // a zeroed device block and (host_bytes > 0) a pinned host 
         if (host) (void)hipHostFree(host);
         if (dev) (void)hipFree(dev);
         dev = host = nullptr;
+    }
+};
+
+// A sparse automaton's tables (CSR: edge_off / edge_tok / edge_next, and a flag byte per state) in handle-owned memory sized by need,
+// with their pinned staging copy: what lexicon-guided and boosted decoding each keep one of ("Sparse automata").
+struct CsrDevice {
+    DevBlock arena;                                      // device tables and the staging copy, same layout, [cap_states] / [cap_edges]
+    int *edge_off = nullptr, *edge_tok = nullptr, *edge_next = nullptr;      // into arena.dev
+    uint8_t* flags = nullptr;
+    int cap_states = 0, cap_edges = 0;
+    hipEvent_t ev = nullptr;                             // the staging copy is on the device
+    bool pending = false;
+    // Room for n_states / n_edges: powers of two from 1024, so a call's tables mostly fit the last call's. *moved = the tables are in a
+    // new (zeroed) block and the old one is gone: captured steps hold stale addresses, and the feature is off until the next upload.
+    // A failure changes nothing. Moving waits for the device: nothing in flight reads the old tables or their staging copy.
+    int grow(int n_states, int n_edges, bool* moved) {
+        *moved = false;
+        if (n_states <= cap_states && n_edges <= cap_edges) return SA_OK;
+        int cs = std::max(cap_states, 1024), ce = std::max(cap_edges, 1024);
+        while (cs < n_states) cs *= 2;
+        while (ce < n_edges) ce *= 2;
+        Carve cv;
+        const size_t o = cv.take(((size_t)cs + 1) * sizeof(int)), t = cv.take((size_t)ce * sizeof(int)), n = cv.take((size_t)ce * sizeof(int)),
+                     f = cv.take((size_t)cs);
+        DevBlock nb;
+        int rc = nb.alloc(cv.off, cv.off);
+        if (!rc && !ev) rc = (int)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (!rc) rc = (int)hipDeviceSynchronize();
+        if (rc) { nb.release(); return rc; }
+        arena.release();
+        arena = nb;
+        pending = false;
+        edge_off = reinterpret_cast<int*>(nb.dev + o);
+        edge_tok = reinterpret_cast<int*>(nb.dev + t);
+        edge_next = reinterpret_cast<int*>(nb.dev + n);
+        flags = reinterpret_cast<uint8_t*>(nb.dev + f);
+        cap_states = cs; cap_edges = ce;
+        *moved = true;
+        return SA_OK;
+    }
+    // Host tables -> staging copy -> device, in stream order, once the previous upload has left the staging copy. f == nullptr copies
+    // no flags: they stay the zeros of the allocation.
+    int upload(const int32_t* off, const int32_t* tok, const int32_t* next, const uint8_t* f, int n_states, int n_edges, hipStream_t s) {
+        if (pending) { (void)hipEventSynchronize(ev); pending = false; }
+        auto put = [&](void* dev, const void* src, size_t bytes) {
+            char* h = arena.host + (static_cast<char*>(dev) - arena.dev);
+            memcpy(h, src, bytes);
+            return hipMemcpyAsync(dev, h, bytes, hipMemcpyHostToDevice, s);
+        };
+        SA_HIP(put(edge_off, off, ((size_t)n_states + 1) * sizeof(int)));
+        if (n_edges) {
+            SA_HIP(put(edge_tok, tok, (size_t)n_edges * sizeof(int)));
+            SA_HIP(put(edge_next, next, (size_t)n_edges * sizeof(int)));
+        }
+        if (f) SA_HIP(put(flags, f, (size_t)n_states));
+        SA_HIP(hipEventRecord(ev, s));
+        pending = true;
+        return SA_OK;
+    }
+    void release() {
+        arena.release();
+        if (ev) (void)hipEventDestroy(ev);
+        ev = nullptr;
     }
 };
 
@@ -386,39 +450,25 @@ struct RecModel : RecBase {
     int* slot_state = nullptr;                           // [max_slots], -1 = no pattern
     Stager st_pat;
     int pat_states = 0, pat_classes = 0;
-    // Lexicon-guided decoding (surya_rec_set_lexicon; lexicon.h): a sparse automaton in handle-owned memory sized by need -- growing it,
-    // like switching the feature on or off, drops captured steps; new contents of the same capacity keep them -- and a state per slot,
-    // allocated on the first call at an address that never changes. Slot s owns row SA_MAX_TOKEN_MASKS + s of the mask table; those
+    // Lexicon-guided decoding (surya_rec_set_lexicon; lexicon.h): the tables and a state per slot, allocated on the first call at an
+    // address that never changes. Switching on or off drops captured steps. Slot s owns row SA_MAX_TOKEN_MASKS + s of the mask table; those
     // max_slots rows exist only on a handle that has seen a lexicon (mask_dyn_rows: the first set_lexicon moves the mask arena into a
     // larger block, at the one moment at which every captured step is dropped anyway; from then on its addresses never move again).
     // lex_states == 0: the handle launches exactly what a handle without this entry launches.
-    DevBlock lex_arena;                                  // device tables + their pinned staging copy, [lex_cap_states] / [lex_cap_edges]
-    int *lex_edge_off = nullptr, *lex_edge_tok = nullptr, *lex_edge_next = nullptr;
-    uint8_t* lex_flags = nullptr;
-    size_t lex_o_tok = 0, lex_o_next = 0, lex_o_flags = 0;   // offsets in both blocks (edge_off is at 0)
-    int lex_cap_states = 0, lex_cap_edges = 0;
-    hipEvent_t lex_ev = nullptr;                         // the staging copy is on the device
-    bool lex_pending = false;
+    CsrDevice lex;
     int* slot_lex_state = nullptr;                       // [max_slots], -1 = no lexicon
     Stager st_lex;                                       // slots and start states of set_slot_lexicon
     bool mask_dyn_rows = false;
     int lex_states = 0, lex_nop = -1;
-    LexiconArgs lex_args() const {
-        return LexiconArgs{lex_edge_off, lex_edge_tok, lex_edge_next, lex_flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS, slot_lex_state,
-                           slot_mask, c.vocab, c.eos_token_id, c.pad_token_id, lex_nop};
+    LexiconArgs csr_args(const CsrDevice& t, int* slot_st, int nop) const {
+        return LexiconArgs{t.edge_off, t.edge_tok, t.edge_next, t.flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS, slot_st, slot_mask,
+                           c.vocab, c.eos_token_id, c.pad_token_id, nop};
     }
-    // Boosted decoding (surya_rec_set_boost; boost.h): a sparse automaton like the lexicon's, in handle-owned memory sized by need -- growing
-    // it, like switching the feature on or off, drops captured steps; new contents of the same capacity keep them. State, root and beta
-    // per slot, the second lm_head partial buffer (record B) and the STEPS_BOOST outputs with their pinned mirror are allocated on the
-    // first call at addresses that never change. A boosted slot owns the mask-table row a lexicon slot would (mask_dyn_rows above).
-    // bst_states == 0: the handle launches exactly what a handle without this entry launches.
-    DevBlock bst_arena;                                  // device tables (+ an all-zero state_flags array) and their pinned staging copy
-    int *bst_edge_off = nullptr, *bst_edge_tok = nullptr, *bst_edge_next = nullptr;
-    uint8_t* bst_flags = nullptr;
-    size_t bst_o_tok = 0, bst_o_next = 0;
-    int bst_cap_states = 0, bst_cap_edges = 0;
-    hipEvent_t bst_ev = nullptr;
-    bool bst_pending = false;
+    LexiconArgs lex_args() const { return csr_args(lex, slot_lex_state, lex_nop); }
+    // Boosted decoding (surya_rec_set_boost; boost.h): the tables; state, root and beta per slot, the second lm_head partial buffer
+    // (record B) and the STEPS_BOOST outputs with their pinned mirror, allocated on the first call at addresses that never change. A
+    // boosted slot owns the mask-table row a lexicon slot would. bst_states == 0: the handle launches what one without this entry does.
+    CsrDevice bst;                                       // (state_flags: the zeros of the allocation, never uploaded)
     DevBlock bst_slots;                                  // per-slot state / root / beta, record B's partials, the outputs and their mirror
     int *slot_bst_state = nullptr, *slot_bst_root = nullptr; float* slot_bst_beta = nullptr;     // [max_slots]: -1, -1, +inf = not boosted
     float4* amax_b = nullptr;                            // as amax
@@ -426,9 +476,23 @@ struct RecModel : RecBase {
     Stager st_bst;                                       // slots, roots and betas of set_slot_boost
     int bst_states = 0, bst_out = 0, bst_word_row = 0;
     BoostArgs bst_args() const {
-        return BoostArgs{LexiconArgs{bst_edge_off, bst_edge_tok, bst_edge_next, bst_flags, mask_table, mask_words(), SA_MAX_TOKEN_MASKS,
-                                     slot_bst_state, slot_mask, c.vocab, c.eos_token_id, c.pad_token_id, -1},
-                         slot_bst_root, slot_bst_beta, bst_out, bst_word_row};
+        return BoostArgs{TotalOps{slot_bst_root, slot_bst_beta, bst_out, bst_word_row}, csr_args(bst, slot_bst_state, -1)};
+    }
+    // The slot list of a set_slot_* call: 1 <= n <= max_slots entries, every slot in range and named once (which value would win is a
+    // race in the scatter), and also(i), the call's own check of entry i, holds. SA_OK or SA_ERR_ARG.
+    template <typename F>
+    int check_slots(const int32_t* slots, int n, F&& also) const {
+        std::vector<char> seen(c.max_slots, 0);
+        for (int i = 0; i < n; ++i) {
+            if (slots[i] < 0 || slots[i] >= c.max_slots || seen[slots[i]] || !also(i)) return SA_ERR_ARG;
+            seen[slots[i]] = 1;
+        }
+        return SA_OK;
+    }
+    int copy_states(int32_t* dst, const int* states, hipStream_t s) const {      // the three copy_*_states
+        if (!states) return SA_ERR_STATE;
+        SA_HIP(hipMemcpyAsync(dst, states, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
+        return SA_OK;
     }
     bool topk() const { return alts || beam > 0; }       // the lm_head collects candidates and topk_combine_kernel runs
     // Which step-output sets the kernels write right now: decode_async mirrors these, read_steps / wait_steps refuse the others.
@@ -563,11 +627,8 @@ struct RecModel : RecBase {
         for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena}) b->release();
         if (mask_arena) (void)hipFree(mask_arena);
         if (pat_arena) (void)hipFree(pat_arena);
-        lex_arena.release();
-        bst_arena.release(); bst_slots.release();
-        if (bst_ev) (void)hipEventDestroy(bst_ev);
+        lex.release(); bst.release(); bst_slots.release();
         if (slot_lex_state) (void)hipFree(slot_lex_state);
-        if (lex_ev) (void)hipEventDestroy(lex_ev);
         st_mask.destroy(); st_forced.destroy(); st_pat.destroy(); st_lex.destroy(); st_bst.destroy();
         for (auto& kv : graphs) (void)hipGraphExecDestroy(kv.second);
         if (gstream) (void)hipStreamDestroy(gstream);
@@ -868,12 +929,7 @@ struct RecModel : RecBase {
         if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
         if (n > c.max_slots) return SA_ERR_ARG;
         if (n_token_masks == 0) return SA_ERR_STATE;
-        std::vector<char> seen(c.max_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            if (slots[i] < 0 || slots[i] >= c.max_slots || ids[i] < -1 || ids[i] >= n_token_masks) return SA_ERR_ARG;
-            if (seen[slots[i]]) return SA_ERR_ARG;          // a slot named twice: which id would win is a race in the scatter
-            seen[slots[i]] = 1;
-        }
+        if (check_slots(slots, n, [&](int i) { return ids[i] >= -1 && ids[i] < n_token_masks; })) return SA_ERR_ARG;
         st_mask.begin();
         const int* ds = st_mask.put(slots, n);
         const int* di = st_mask.put(ids, n);
@@ -958,12 +1014,7 @@ struct RecModel : RecBase {
         if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
         if (n > c.max_slots) return SA_ERR_ARG;
         if (pat_states == 0) return SA_ERR_STATE;
-        std::vector<char> seen(c.max_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            if (slots[i] < 0 || slots[i] >= c.max_slots || states[i] < -1 || states[i] >= pat_states) return SA_ERR_ARG;
-            if (seen[slots[i]]) return SA_ERR_ARG;
-            seen[slots[i]] = 1;
-        }
+        if (check_slots(slots, n, [&](int i) { return states[i] >= -1 && states[i] < pat_states; })) return SA_ERR_ARG;
         st_pat.begin();
         const int* ds = st_pat.put(slots, n);
         const int* dt = st_pat.put(states, n);
@@ -973,11 +1024,7 @@ struct RecModel : RecBase {
         hipLaunchKernelGGL(set_slot_patterns_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, ds, dt, pat_state_mask, slot_state, slot_mask, n);
         return (int)hipGetLastError();
     }
-    int copy_slot_states(int32_t* dst, hipStream_t s) override {
-        if (!slot_state) return SA_ERR_STATE;
-        SA_HIP(hipMemcpyAsync(dst, slot_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
-        return SA_OK;
-    }
+    int copy_slot_states(int32_t* dst, hipStream_t s) override { return copy_states(dst, slot_state, s); }
 
     // The automaton of lexicon-guided decoding (lexicon.h), from host arrays. Everything is checked before anything is enqueued or
     // allocated: the kernels read the tables unchecked. New tables set every slot's state back to -1.
@@ -987,69 +1034,21 @@ struct RecModel : RecBase {
         if (n_states == 0) return lexicon_off(s);
         if (!edge_off || !flags || (n_edges > 0 && (!edge_tok || !edge_next))) return SA_ERR_ARG;
         if (n_token_masks == 0 || excluded(M_LEXICON)) return SA_ERR_STATE;
-        if (edge_off[0] != 0 || edge_off[n_states] != n_edges) return SA_ERR_ARG;
-        const bool ends = (c.eos_token_id >= 0 && c.eos_token_id < c.vocab) || (c.pad_token_id >= 0 && c.pad_token_id < c.vocab);
-        for (int st = 0; st < n_states; ++st) {
-            const int a = edge_off[st], b = edge_off[st + 1];
-            if (a < 0 || b < a || b > n_edges || (flags[st] & ~3)) return SA_ERR_ARG;
-            if ((flags[st] & 2) && (nop < 0 || nop >= c.vocab)) return SA_ERR_ARG;
-            if (b == a && !((flags[st] & 1) && ends) && !(flags[st] & 2)) return SA_ERR_ARG;      // a state without an allowed id
-            for (int e = a; e < b; ++e) {
-                if (edge_tok[e] < 0 || edge_tok[e] >= c.vocab || edge_next[e] < 0 || edge_next[e] >= n_states) return SA_ERR_ARG;
-                if (e > a && edge_tok[e] <= edge_tok[e - 1]) return SA_ERR_ARG;
-            }
-        }
+        if (csr_check(edge_off, edge_tok, edge_next, n_states, n_edges, c.vocab) ||
+            lexicon_check(edge_off, flags, n_states, c.vocab, c.eos_token_id, c.pad_token_id, nop))
+            return SA_ERR_ARG;
         int rc;
         if (!slot_lex_state) {                              // first tables: the per-slot state and its staging, or nothing
             int* mem = nullptr;
             Stager st;
-            hipEvent_t ev = nullptr;
             SA_HIP(hipMalloc((void**)&mem, (size_t)c.max_slots * sizeof(int)));
             rc = st.init((size_t)c.max_slots * 2 * sizeof(int) + 4096);
-            if (!rc) rc = (int)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
             if (!rc) rc = (int)hipMemset(mem, 0xff, (size_t)c.max_slots * sizeof(int));      // every slot -1, whatever fails below
-            if (rc) { if (ev) (void)hipEventDestroy(ev); st.destroy(); (void)hipFree(mem); return rc; }
-            st_lex = st; lex_ev = ev; slot_lex_state = mem;
+            if (rc) { st.destroy(); (void)hipFree(mem); return rc; }
+            st_lex = st; slot_lex_state = mem;
         }
         if (!mask_dyn_rows && (rc = grow_mask_arena(s))) return rc;
-        if (n_states > lex_cap_states || n_edges > lex_cap_edges) {      // grow: powers of two, so a call's tables mostly fit the last call's
-            int cs = std::max(lex_cap_states, 1024), ce = std::max(lex_cap_edges, 1024);
-            while (cs < n_states) cs *= 2;
-            while (ce < n_edges) ce *= 2;
-            Carve cv;
-            (void)cv.take(((size_t)cs + 1) * sizeof(int));
-            const size_t o_tok = cv.take((size_t)ce * sizeof(int)), o_next = cv.take((size_t)ce * sizeof(int)), o_flags = cv.take((size_t)cs);
-            DevBlock nb;
-            if ((rc = nb.alloc(cv.off, cv.off))) return rc;
-            SA_HIP(hipDeviceSynchronize());                 // nothing in flight reads the old tables or their staging copy
-            drop_graphs();                                  // captured steps hold the old addresses
-            lex_arena.release();
-            lex_arena = nb;
-            lex_pending = false;
-            lex_o_tok = o_tok; lex_o_next = o_next; lex_o_flags = o_flags;
-            lex_edge_off = reinterpret_cast<int*>(nb.dev);
-            lex_edge_tok = reinterpret_cast<int*>(nb.dev + o_tok);
-            lex_edge_next = reinterpret_cast<int*>(nb.dev + o_next);
-            lex_flags = reinterpret_cast<uint8_t*>(nb.dev + o_flags);
-            lex_cap_states = cs; lex_cap_edges = ce;
-            if (lex_states > 0) lex_states = 0;             // (the old tables are gone: off until the new ones are on their way)
-        }
-        if (lex_pending) { (void)hipEventSynchronize(lex_ev); lex_pending = false; }
-        char* hb = lex_arena.host;
-        memcpy(hb, edge_off, ((size_t)n_states + 1) * sizeof(int));
-        if (n_edges) {
-            memcpy(hb + lex_o_tok, edge_tok, (size_t)n_edges * sizeof(int));
-            memcpy(hb + lex_o_next, edge_next, (size_t)n_edges * sizeof(int));
-        }
-        memcpy(hb + lex_o_flags, flags, (size_t)n_states);
-        SA_HIP(hipMemcpyAsync(lex_edge_off, hb, ((size_t)n_states + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        if (n_edges) {
-            SA_HIP(hipMemcpyAsync(lex_edge_tok, hb + lex_o_tok, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
-            SA_HIP(hipMemcpyAsync(lex_edge_next, hb + lex_o_next, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
-        }
-        SA_HIP(hipMemcpyAsync(lex_flags, hb + lex_o_flags, (size_t)n_states, hipMemcpyHostToDevice, s));
-        SA_HIP(hipEventRecord(lex_ev, s));
-        lex_pending = true;
+        if ((rc = place_tables(lex, lex_states, edge_off, edge_tok, edge_next, flags, n_states, n_edges, s))) return rc;
         SA_HIP(hipMemsetAsync(slot_lex_state, 0xff, (size_t)c.max_slots * sizeof(int), s));
         if (lex_states == 0 || nop != lex_nop) drop_graphs();      // on <-> off, and the by-value no-output id of the step launch
         lex_states = n_states;
@@ -1079,6 +1078,16 @@ struct RecModel : RecBase {
         mask_dyn_rows = true;
         return SA_OK;
     }
+    // Room for a feature's tables, then the tables (set_lexicon, set_boost). A block that moved drops captured steps, which hold the
+    // old addresses, and switches the feature off (states_on = 0) until the new tables are on their way.
+    int place_tables(CsrDevice& t, int& states_on, const int32_t* edge_off, const int32_t* edge_tok, const int32_t* edge_next,
+                     const uint8_t* flags, int n_states, int n_edges, hipStream_t s) {
+        bool moved = false;
+        const int rc = t.grow(n_states, n_edges, &moved);
+        if (rc) return rc;
+        if (moved) { drop_graphs(); states_on = 0; }
+        return t.upload(edge_off, edge_tok, edge_next, flags, n_states, n_edges, s);
+    }
     int lexicon_off(hipStream_t s) {
         if (lex_states == 0) return SA_OK;
         drop_graphs();
@@ -1091,12 +1100,7 @@ struct RecModel : RecBase {
         if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
         if (n > c.max_slots) return SA_ERR_ARG;
         if (lex_states == 0) return SA_ERR_STATE;
-        std::vector<char> seen(c.max_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            if (slots[i] < 0 || slots[i] >= c.max_slots || states[i] < -1 || states[i] >= lex_states) return SA_ERR_ARG;
-            if (seen[slots[i]]) return SA_ERR_ARG;
-            seen[slots[i]] = 1;
-        }
+        if (check_slots(slots, n, [&](int i) { return states[i] >= -1 && states[i] < lex_states; })) return SA_ERR_ARG;
         st_lex.begin();
         const int* ds = st_lex.put(slots, n);
         const int* dt = st_lex.put(states, n);
@@ -1105,11 +1109,7 @@ struct RecModel : RecBase {
         if (rc) return rc;
         return launch_lexicon_start(lex_args(), ds, dt, n, s);
     }
-    int copy_lexicon_states(int32_t* dst, hipStream_t s) override {
-        if (!slot_lex_state) return SA_ERR_STATE;
-        SA_HIP(hipMemcpyAsync(dst, slot_lex_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
-        return SA_OK;
-    }
+    int copy_lexicon_states(int32_t* dst, hipStream_t s) override { return copy_states(dst, slot_lex_state, s); }
 
     // The automaton of boosted decoding (boost.h), from host arrays. Everything is checked before anything is enqueued or allocated: the
     // kernels read the tables unchecked. New tables set every slot back to "not boosted".
@@ -1120,17 +1120,9 @@ struct RecModel : RecBase {
         if (!edge_off || (n_edges > 0 && (!edge_tok || !edge_next))) return SA_ERR_ARG;
         if (n_token_masks == 0 || excluded(M_BOOST)) return SA_ERR_STATE;
         if (!head2_ok() || cdiv(c.vocab, 64) > 4 * SA_HEAD_THREADS) return SA_ERR_STATE;      // the fallback head would have to run
-        if (out_state < 0 || out_state >= n_states || word_row < 0 || word_row >= n_token_masks) return SA_ERR_ARG;
-        if (edge_off[0] != 0 || edge_off[n_states] != n_edges || edge_off[out_state + 1] != edge_off[out_state]) return SA_ERR_ARG;
-        for (int st = 0; st < n_states; ++st) {
-            const int a = edge_off[st], b = edge_off[st + 1];
-            if (a < 0 || b < a || b > n_edges) return SA_ERR_ARG;
-            for (int e = a; e < b; ++e) {
-                const int t = edge_tok[e];
-                if (t < 0 || t >= c.vocab || t == c.eos_token_id || t == c.pad_token_id || edge_next[e] < 0 || edge_next[e] >= n_states) return SA_ERR_ARG;
-                if (e > a && t <= edge_tok[e - 1]) return SA_ERR_ARG;
-            }
-        }
+        if (csr_check(edge_off, edge_tok, edge_next, n_states, n_edges, c.vocab) ||
+            boost_check(edge_off, edge_tok, n_states, n_edges, out_state, word_row, n_token_masks, c.eos_token_id, c.pad_token_id))
+            return SA_ERR_ARG;
         int rc;
         if (!bst_slots.dev) {                               // first tables: the per-slot arrays, record B's partials, the outputs -- or nothing
             const size_t S = c.max_slots, out_b = (size_t)SA_MAX_STEPS * S * 4;
@@ -1139,15 +1131,13 @@ struct RecModel : RecBase {
                          o_amax = cv.take(S * (size_t)cdiv(c.vocab, 32) * sizeof(float4)), o_ptok = cv.take(out_b), o_pprob = cv.take(out_b);
             DevBlock b;
             Stager st;
-            hipEvent_t ev = nullptr;
             std::vector<float> inf(S, INFINITY);
             rc = b.alloc(cv.off, 2 * out_b);
             if (!rc) rc = st.init(S * 3 * sizeof(int) + 4096);
-            if (!rc) rc = (int)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
             if (!rc) rc = (int)hipMemset(b.dev + o_state, 0xff, o_beta - o_state);                    // state and root -1
             if (!rc) rc = (int)hipMemcpy(b.dev + o_beta, inf.data(), S * 4, hipMemcpyHostToDevice);      // beta +inf
-            if (rc) { if (ev) (void)hipEventDestroy(ev); st.destroy(); b.release(); return rc; }
-            bst_slots = b; st_bst = st; bst_ev = ev;
+            if (rc) { st.destroy(); b.release(); return rc; }
+            bst_slots = b; st_bst = st;
             slot_bst_state = reinterpret_cast<int*>(b.dev + o_state);
             slot_bst_root = reinterpret_cast<int*>(b.dev + o_root);
             slot_bst_beta = reinterpret_cast<float*>(b.dev + o_beta);
@@ -1159,40 +1149,7 @@ struct RecModel : RecBase {
             o.host = b.host;
         }
         if (!mask_dyn_rows && (rc = grow_mask_arena(s))) return rc;
-        if (n_states > bst_cap_states || n_edges > bst_cap_edges) {      // grow: powers of two, so a call's tables mostly fit the last call's
-            int cs = std::max(bst_cap_states, 1024), ce = std::max(bst_cap_edges, 1024);
-            while (cs < n_states) cs *= 2;
-            while (ce < n_edges) ce *= 2;
-            Carve cv;
-            (void)cv.take(((size_t)cs + 1) * sizeof(int));
-            const size_t o_tok = cv.take((size_t)ce * sizeof(int)), o_next = cv.take((size_t)ce * sizeof(int)), o_flags = cv.take((size_t)cs);
-            DevBlock nb;
-            if ((rc = nb.alloc(cv.off, o_flags))) return rc;      // (the flags stay the zeros of the allocation: no staging copy)
-            SA_HIP(hipDeviceSynchronize());                 // nothing in flight reads the old tables or their staging copy
-            drop_graphs();                                  // captured steps hold the old addresses
-            bst_arena.release();
-            bst_arena = nb;
-            bst_pending = false;
-            bst_o_tok = o_tok; bst_o_next = o_next;
-            bst_edge_off = reinterpret_cast<int*>(nb.dev);
-            bst_edge_tok = reinterpret_cast<int*>(nb.dev + o_tok);
-            bst_edge_next = reinterpret_cast<int*>(nb.dev + o_next);
-            bst_flags = reinterpret_cast<uint8_t*>(nb.dev + o_flags);
-            bst_cap_states = cs; bst_cap_edges = ce;
-            bst_states = 0;                                 // (the old tables are gone: off until the new ones are on their way)
-        }
-        if (bst_pending) { (void)hipEventSynchronize(bst_ev); bst_pending = false; }
-        char* hb = bst_arena.host;
-        memcpy(hb, edge_off, ((size_t)n_states + 1) * sizeof(int));
-        SA_HIP(hipMemcpyAsync(bst_edge_off, hb, ((size_t)n_states + 1) * sizeof(int), hipMemcpyHostToDevice, s));
-        if (n_edges) {
-            memcpy(hb + bst_o_tok, edge_tok, (size_t)n_edges * sizeof(int));
-            memcpy(hb + bst_o_next, edge_next, (size_t)n_edges * sizeof(int));
-            SA_HIP(hipMemcpyAsync(bst_edge_tok, hb + bst_o_tok, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
-            SA_HIP(hipMemcpyAsync(bst_edge_next, hb + bst_o_next, (size_t)n_edges * sizeof(int), hipMemcpyHostToDevice, s));
-        }
-        SA_HIP(hipEventRecord(bst_ev, s));
-        bst_pending = true;
+        if ((rc = place_tables(bst, bst_states, edge_off, edge_tok, edge_next, nullptr, n_states, n_edges, s))) return rc;
         if ((rc = reset_boost_slots(s))) return rc;
         if (bst_states == 0 || out_state != bst_out || word_row != bst_word_row) drop_graphs();      // on <-> off, and the by-value ids of the step launch
         bst_states = n_states;
@@ -1217,13 +1174,10 @@ struct RecModel : RecBase {
         if (n <= 0) return n < 0 ? SA_ERR_ARG : SA_OK;
         if (n > c.max_slots) return SA_ERR_ARG;
         if (bst_states == 0) return SA_ERR_STATE;
-        std::vector<char> seen(c.max_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            if (slots[i] < 0 || slots[i] >= c.max_slots || roots[i] < -1 || roots[i] >= bst_states) return SA_ERR_ARG;
-            if (roots[i] >= 0 && !(betas[i] >= 0.f && betas[i] < INFINITY)) return SA_ERR_ARG;      // finite, >= 0 (NaN fails both)
-            if (seen[slots[i]]) return SA_ERR_ARG;
-            seen[slots[i]] = 1;
-        }
+        if (check_slots(slots, n, [&](int i) {              // a boosted slot's beta: finite, >= 0 (NaN fails both)
+                return roots[i] >= -1 && roots[i] < bst_states && (roots[i] < 0 || (betas[i] >= 0.f && betas[i] < INFINITY));
+            }))
+            return SA_ERR_ARG;
         st_bst.begin();
         const int* ds = st_bst.put(slots, n);
         const int* dr = st_bst.put(roots, n);
@@ -1233,11 +1187,7 @@ struct RecModel : RecBase {
         if (rc) return rc;
         return launch_boost_start(bst_args(), ds, dr, db, n, s);
     }
-    int copy_boost_states(int32_t* dst, hipStream_t s) override {
-        if (!slot_bst_state) return SA_ERR_STATE;
-        SA_HIP(hipMemcpyAsync(dst, slot_bst_state, (size_t)c.max_slots * sizeof(int), hipMemcpyDeviceToDevice, s));
-        return SA_OK;
-    }
+    int copy_boost_states(int32_t* dst, hipStream_t s) override { return copy_states(dst, slot_bst_state, s); }
 
     // Alternatives on / off. Memory on the first switch-on, or nothing (a failure leaves the handle as it was); switching drops captured
     // steps, which hold the other lm_head kernel and the head's null / non-null (max, total) pointer.
@@ -1374,14 +1324,14 @@ struct RecModel : RecBase {
         if (!forcing) return SA_ERR_STATE;
         if (n == 0) return SA_OK;
         if (offsets[0] < 0) return SA_ERR_ARG;
-        std::vector<char> seen(c.max_slots, 0);
-        for (int i = 0; i < n; ++i) {
-            const int len = offsets[i + 1] - offsets[i];
-            if (slots[i] < 0 || slots[i] >= c.max_slots || seen[slots[i]] || len < 0 || len > SA_MAX_FORCED_TOKENS) return SA_ERR_ARG;
-            seen[slots[i]] = 1;
-            for (int j = offsets[i]; j < offsets[i + 1]; ++j)
-                if (tokens[j] < 0 || tokens[j] >= c.vocab) return SA_ERR_ARG;
-        }
+        if (check_slots(slots, n, [&](int i) {
+                const int len = offsets[i + 1] - offsets[i];
+                if (len < 0 || len > SA_MAX_FORCED_TOKENS) return false;
+                for (int j = offsets[i]; j < offsets[i + 1]; ++j)
+                    if (tokens[j] < 0 || tokens[j] >= c.vocab) return false;
+                return true;
+            }))
+            return SA_ERR_ARG;
         st_forced.begin();
         const int* ds = st_forced.put(slots, n);
         const int* dof = st_forced.put(offsets, (size_t)n + 1);

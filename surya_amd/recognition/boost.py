@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
-from .lexicon import SA_MAX_LEXICON_EDGES, SA_MAX_LEXICON_STATES, entry_units
+from .lexicon import SA_MAX_LEXICON_EDGES, SA_MAX_LEXICON_STATES, CsrTables, entry_units
 
 
 @lru_cache(maxsize=4)
@@ -45,39 +45,25 @@ def word_unit_bits(special_token_offset: int, vocab: int) -> np.ndarray:
     return bits
 
 
-class BoostTables:
+class BoostTables(CsrTables):
     """The joint CSR automaton of a call's lists and its host restatement (what csrc/boost.h does on the device). roots[i] = root state of
     lists[i]; out_state = the shared state without edges; word_bits = the word-unit set (word_mask: the same as a mask-table row;
     word_row: that row's id in the call's table, set by whoever adds it); edge_done[e] = the entries of the root's list (indices, ascending)
     that a match completes by taking edge e."""
 
     def __init__(self, edge_off, edge_tok, edge_next, roots, out_state, word_bits, edge_done, vocab, eos, pad):
-        self.edge_off, self.edge_tok, self.edge_next = edge_off, edge_tok, edge_next
+        super().__init__(edge_off, edge_tok, edge_next, vocab, eos, pad)
         self.roots, self.out_state, self.word_bits, self.edge_done = list(roots), int(out_state), word_bits, edge_done
-        self.vocab, self.eos, self.pad = int(vocab), eos, pad
-        self.n_states, self.n_edges = len(edge_off) - 1, len(edge_tok)
         self.word_row: Optional[int] = None
 
     @property
     def word_mask(self) -> np.ndarray:
-        bits = np.zeros((self.vocab + 31) // 32 * 32, bool)
-        bits[:self.vocab] = self.word_bits
-        return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
-
-    def edges(self, state: int):
-        a, b = int(self.edge_off[state]), int(self.edge_off[state + 1])
-        return self.edge_tok[a:b], self.edge_next[a:b]
-
-    def _edge(self, state: int, token: int) -> int:
-        """Index of the edge of `state` for `token`, or -1."""
-        a, b = int(self.edge_off[state]), int(self.edge_off[state + 1])
-        k = a + int(np.searchsorted(self.edge_tok[a:b], token))
-        return k if k < b and int(self.edge_tok[k]) == token else -1
+        return self._row(np.flatnonzero(self.word_bits))
 
     def advance(self, state: int, token: int, root: int) -> int:
-        """What boost_step_kernel does behind `token` for a slot whose list has root state `root`: not boosted (-1), a row that ended (eos /
+        """What the step kernel does behind `token` for a slot whose list has root state `root`: not boosted (-1), a row that ended (eos /
         pad) and an id outside the vocabulary keep the state; else the edge's target, or OUT for a word unit, or the root."""
-        if state < 0 or token == self.eos or token == self.pad or not 0 <= token < self.vocab:
+        if self._stays(state, token):
             return state
         e = self._edge(state, token)
         if e >= 0:
@@ -90,9 +76,7 @@ class BoostTables:
 
     def row(self, state: int) -> np.ndarray:
         """preferred(state) as a mask-table row, uint32 [cdiv(vocab, 32)]."""
-        bits = np.zeros((self.vocab + 31) // 32 * 32, bool)
-        bits[sorted(self.preferred(state))] = True
-        return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+        return self._row(self.preferred(state))
 
     def matches(self, root: int, tokens: Sequence[int]) -> List[int]:
         """The entries (indices in the root's own list) that some live match completed while the line's `tokens` went by, in order of
@@ -100,7 +84,7 @@ class BoostTables:
         st, out, seen = root, [], set()
         for t in tokens:
             t = int(t)
-            if st >= 0 and t != self.eos and t != self.pad and 0 <= t < self.vocab:
+            if not self._stays(st, t):
                 e = self._edge(st, t)
                 for i in (self.edge_done.get(e, ()) if e >= 0 else ()):
                     if i not in seen:

@@ -39,29 +39,53 @@ def entry_units(entry: str) -> List[int]:
     return np.frombuffer(b, "<u2").tolist()
 
 
-class LexiconTables:
-    """The joint CSR automaton of a call's lexicons and its host restatement (what csrc/lexicon.h does on the device).
-    starts[i] = start state of lexicons[i]; entries[i] maps an entry's token tuple to its first index in lexicons[i]."""
+class CsrTables:
+    """A sparse automaton in CSR form over a vocabulary with its eos and pad ids: what the lexicon's and the boost's tables
+    (recognition/boost.py) share, and the host restatement of what both do with it on the device (csrc/lexicon.h)."""
 
-    def __init__(self, edge_off, edge_tok, edge_next, state_flags, starts, entries, vocab, eos, pad, nop):
-        self.edge_off, self.edge_tok, self.edge_next, self.state_flags = edge_off, edge_tok, edge_next, state_flags
-        self.starts, self.entries = list(starts), entries
-        self.vocab, self.eos, self.pad, self.nop = int(vocab), eos, pad, nop
-        self.n_states, self.n_edges = len(state_flags), len(edge_tok)
+    def __init__(self, edge_off, edge_tok, edge_next, vocab, eos, pad):
+        self.edge_off, self.edge_tok, self.edge_next = edge_off, edge_tok, edge_next
+        self.vocab, self.eos, self.pad = int(vocab), eos, pad
+        self.n_states, self.n_edges = len(edge_off) - 1, len(edge_tok)
 
     def edges(self, state: int):
         a, b = int(self.edge_off[state]), int(self.edge_off[state + 1])
         return self.edge_tok[a:b], self.edge_next[a:b]
 
+    def _edge(self, state: int, token: int) -> int:
+        """Index of the edge of `state` for `token`, or -1."""
+        a, b = int(self.edge_off[state]), int(self.edge_off[state + 1])
+        k = a + int(np.searchsorted(self.edge_tok[a:b], token))
+        return k if k < b and int(self.edge_tok[k]) == token else -1
+
+    def _stays(self, state: int, token: int) -> bool:
+        """The step kernel touches nothing: no automaton (-1), a row that ended (eos / pad), an id outside the vocabulary."""
+        return state < 0 or token == self.eos or token == self.pad or not 0 <= token < self.vocab
+
+    def _row(self, ids) -> np.ndarray:
+        """The ids as a mask-table row, uint32 [cdiv(vocab, 32)]."""
+        bits = np.zeros((self.vocab + 31) // 32 * 32, bool)
+        bits[np.fromiter(ids, np.int64)] = True
+        return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+
+
+class LexiconTables(CsrTables):
+    """The joint CSR automaton of a call's lexicons and its host restatement (what csrc/lexicon.h does on the device).
+    starts[i] = start state of lexicons[i]; entries[i] maps an entry's token tuple to its first index in lexicons[i]."""
+
+    def __init__(self, edge_off, edge_tok, edge_next, state_flags, starts, entries, vocab, eos, pad, nop):
+        super().__init__(edge_off, edge_tok, edge_next, vocab, eos, pad)
+        self.state_flags, self.nop = state_flags, nop
+        self.starts, self.entries = list(starts), entries
+
     def advance(self, state: int, token: int) -> int:
-        """What lexicon_step_kernel does behind `token`: no lexicon (-1), a row that ended (eos / pad), an id outside the vocabulary and
+        """What the step kernel does behind `token`: no lexicon (-1), a row that ended (eos / pad), an id outside the vocabulary and
         an id the state has no edge for (the mask never lets the device emit one; the no-output token at a start state is the one id
         that gets there) keep the state."""
-        if state < 0 or token == self.eos or token == self.pad or not 0 <= token < self.vocab:
+        if self._stays(state, token):
             return state
-        toks, nxt = self.edges(state)
-        k = int(np.searchsorted(toks, token))
-        return int(nxt[k]) if k < len(toks) and int(toks[k]) == token else state
+        e = self._edge(state, token)
+        return int(self.edge_next[e]) if e >= 0 else state
 
     def allowed(self, state: int) -> set:
         """The ids a slot in `state` may emit: its children, EOS and pad where it is terminal, the no-output token at a start state."""
@@ -78,9 +102,7 @@ class LexiconTables:
 
     def row(self, state: int) -> np.ndarray:
         """allowed(state) as a mask-table row, uint32 [cdiv(vocab, 32)]."""
-        bits = np.zeros((self.vocab + 31) // 32 * 32, bool)
-        bits[sorted(self.allowed(state))] = True
-        return np.packbits(bits.reshape(-1, 32), axis=1, bitorder="little").view("<u4").reshape(-1).astype(np.uint32)
+        return self._row(self.allowed(state))
 
     def entry_of(self, lexicon: int, tokens: Sequence[int]) -> int:
         """A finished line of lexicons[lexicon]: the index of the entry read, the first one for a duplicate, iff the line ended (EOS or

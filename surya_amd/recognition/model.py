@@ -161,13 +161,28 @@ class HipRecModel:
                 "surya_rec_set_token_masks")
         self.n_token_masks, self.n_pattern_states, self.n_lexicon_states, self.n_boost_states = int(m.shape[0]), 0, 0, 0
 
+    def _set_slots(self, name, slots, values):
+        """surya_rec_<name>(slots, values): one int32 per slot about to be prefilled."""
+        s = np.ascontiguousarray(np.asarray(slots, np.int32))
+        v = np.ascontiguousarray(np.asarray(values, np.int32))
+        assert s.shape == v.shape and s.ndim == 1
+        L.check(getattr(self.lib, "surya_rec_" + name)(self.handle, L.np_ptr(s), L.np_ptr(v), C.c_int(len(s)), self._stream), "surya_rec_" + name)
+
+    def _read_states(self, name) -> np.ndarray:
+        """Sync; surya_rec_<name>: one int32 per slot."""
+        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
+        L.check(getattr(self.lib, "surya_rec_" + name)(self.handle, L.ptr(buf), self._stream), "surya_rec_" + name)
+        return buf.cpu().numpy()
+
+    @staticmethod
+    def _csr_arrays(tables):
+        """edge_off / edge_tok / edge_next of a sparse automaton as contiguous int32 arrays, and whether their shapes fit each other."""
+        eo, et, en = (np.ascontiguousarray(np.asarray(a, np.int32)) for a in (tables.edge_off, tables.edge_tok, tables.edge_next))
+        return eo, et, en, eo.ndim == 1 and et.ndim == 1 and en.shape == et.shape
+
     def set_slot_masks(self, slots, mask_ids):
         """Mask id (row of the table, -1 = unconstrained) of the slots about to be prefilled; a slot keeps it until it is set again."""
-        s = np.ascontiguousarray(np.asarray(slots, np.int32))
-        m = np.ascontiguousarray(np.asarray(mask_ids, np.int32))
-        assert s.shape == m.shape and s.ndim == 1
-        L.check(self.lib.surya_rec_set_slot_masks(self.handle, L.np_ptr(s), L.np_ptr(m), C.c_int(len(s)), self._stream),
-                "surya_rec_set_slot_masks")
+        self._set_slots("set_slot_masks", slots, mask_ids)
 
     def set_patterns(self, tables):
         """The call's pattern automaton (surya_rec_set_patterns; recognition/pattern.py::PatternTables, or anything with its tok_class /
@@ -190,17 +205,11 @@ class HipRecModel:
     def set_slot_patterns(self, slots, start_states):
         """Start state (-1 = no pattern: the slot keeps its mask id) of the slots about to be prefilled, after set_slot_masks; a state
         >= 0 also sets the slot's mask id to the state's row. A slot's state then follows its tokens on the device."""
-        s = np.ascontiguousarray(np.asarray(slots, np.int32))
-        t = np.ascontiguousarray(np.asarray(start_states, np.int32))
-        assert s.shape == t.shape and s.ndim == 1
-        L.check(self.lib.surya_rec_set_slot_patterns(self.handle, L.np_ptr(s), L.np_ptr(t), C.c_int(len(s)), self._stream),
-                "surya_rec_set_slot_patterns")
+        self._set_slots("set_slot_patterns", slots, start_states)
 
     def slot_states(self) -> np.ndarray:
         """Sync; the automaton state of every slot, int32 [max_slots] (-1 = no pattern). A test hook, like last_logits."""
-        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
-        L.check(self.lib.surya_rec_copy_slot_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_slot_states")
-        return buf.cpu().numpy()
+        return self._read_states("copy_slot_states")
 
     def set_lexicon(self, tables):
         """The call's lexicon automaton (surya_rec_set_lexicon; recognition/lexicon.py::LexiconTables, or anything with its edge_off /
@@ -212,11 +221,9 @@ class HipRecModel:
                     "surya_rec_set_lexicon")
             self.n_lexicon_states = 0
             return
-        eo = np.ascontiguousarray(np.asarray(tables.edge_off, np.int32))
-        et = np.ascontiguousarray(np.asarray(tables.edge_tok, np.int32))
-        en = np.ascontiguousarray(np.asarray(tables.edge_next, np.int32))
+        eo, et, en, ok = self._csr_arrays(tables)
         fl = np.ascontiguousarray(np.asarray(tables.state_flags, np.uint8))
-        if eo.ndim != 1 or fl.shape != (len(eo) - 1,) or et.ndim != 1 or en.shape != et.shape:
+        if not ok or fl.shape != (len(eo) - 1,):
             raise ValueError(f"lexicon tables must be edge_off [n_states + 1], edge_tok / edge_next [n_edges], state_flags [n_states], got "
                              f"{eo.shape}, {et.shape}, {en.shape}, {fl.shape}")
         L.check(self.lib.surya_rec_set_lexicon(self.handle, L.np_ptr(eo), L.np_ptr(et), L.np_ptr(en), L.np_ptr(fl, C.c_uint8), C.c_int(len(fl)),
@@ -226,17 +233,11 @@ class HipRecModel:
     def set_slot_lexicon(self, slots, start_states):
         """Start state (-1 = no lexicon: the slot keeps its mask id) of the slots about to be prefilled, after set_slot_masks; a state
         >= 0 makes the slot's own row its mask id. The slot's state and row then follow its tokens on the device."""
-        s = np.ascontiguousarray(np.asarray(slots, np.int32))
-        t = np.ascontiguousarray(np.asarray(start_states, np.int32))
-        assert s.shape == t.shape and s.ndim == 1
-        L.check(self.lib.surya_rec_set_slot_lexicon(self.handle, L.np_ptr(s), L.np_ptr(t), C.c_int(len(s)), self._stream),
-                "surya_rec_set_slot_lexicon")
+        self._set_slots("set_slot_lexicon", slots, start_states)
 
     def copy_lexicon_states(self) -> np.ndarray:
         """Sync; the lexicon state of every slot, int32 [max_slots] (-1 = no lexicon). A test hook, like slot_states."""
-        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
-        L.check(self.lib.surya_rec_copy_lexicon_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_lexicon_states")
-        return buf.cpu().numpy()
+        return self._read_states("copy_lexicon_states")
 
     def set_boost(self, tables):
         """The call's boost automaton (surya_rec_set_boost; recognition/boost.py::BoostTables, or anything with its edge_off / edge_tok /
@@ -248,10 +249,8 @@ class HipRecModel:
                     "surya_rec_set_boost")
             self.n_boost_states = 0
             return
-        eo = np.ascontiguousarray(np.asarray(tables.edge_off, np.int32))
-        et = np.ascontiguousarray(np.asarray(tables.edge_tok, np.int32))
-        en = np.ascontiguousarray(np.asarray(tables.edge_next, np.int32))
-        if eo.ndim != 1 or len(eo) < 2 or et.ndim != 1 or en.shape != et.shape:
+        eo, et, en, ok = self._csr_arrays(tables)
+        if not ok or len(eo) < 2:
             raise ValueError(f"boost tables must be edge_off [n_states + 1], edge_tok / edge_next [n_edges], got {eo.shape}, {et.shape}, {en.shape}")
         L.check(self.lib.surya_rec_set_boost(self.handle, L.np_ptr(eo), L.np_ptr(et), L.np_ptr(en), C.c_int(len(eo) - 1), C.c_int(len(et)),
                                              C.c_int(int(tables.out_state)), C.c_int(int(tables.word_row)), self._stream), "surya_rec_set_boost")
@@ -270,9 +269,7 @@ class HipRecModel:
 
     def copy_boost_states(self) -> np.ndarray:
         """Sync; the boost state of every slot, int32 [max_slots] (-1 = not boosted). A test hook, like slot_states."""
-        buf = torch.empty(self.max_slots, dtype=torch.int32, device=self.device)
-        L.check(self.lib.surya_rec_copy_boost_states(self.handle, L.ptr(buf), self._stream), "surya_rec_copy_boost_states")
-        return buf.cpu().numpy()
+        return self._read_states("copy_boost_states")
 
     def read_boost(self, n_steps: int = 1):
         """Sync; (plain_tokens [n_steps, slots] int32, plain_probs [n_steps, slots] float32) of the steps read_outputs returns: the token

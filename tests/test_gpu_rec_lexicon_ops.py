@@ -4,7 +4,8 @@ the launch code RecModel uses -- on caller-owned buffers, against the host resta
 1 / 64 / 320 rows; rows of 32 words (vocabulary 1024) and 2560 words (81 920). The automaton is made by hand and holds what can go
 wrong: a state with 300 children (more than the workgroup has lanes), a state whose 26 children share two words (lost bits without the
 atomic), transitions whose old and new sets share a word (the barrier between clearing and setting), a terminal leaf, a child at the
-vocabulary's last id in the row's last word. Rows that ended (eos, pad), rows with state -1, a row whose token is the head's "no column"
+vocabulary's last id in the row's last word, a state with an edge to itself (the step kernel returns early there: state and row stay, as
+the host restatement says). Rows that ended (eos, pad), rows with state -1, a row whose token is the head's "no column"
 index and the no-output token at the start state must touch nothing. The start runs onto a table filled with 0xff.
 
 Exact: a touched slot's row equals the new state's set bit for bit, every other word zero; untouched slots' rows, states and mask ids, and
@@ -21,7 +22,7 @@ from surya_amd.recognition.lexicon import LexiconTables
 pytestmark = pytest.mark.gpu
 EOS, PAD, NOP = 256, 257, 264
 ROW_BASE, MASK_SENT, FREE_STATE = 5, 77, 3          # static rows in front; slot_mask before the start; the state of slots no row names
-ROOT, A, B, CC, LEAF = 0, 1, 2, 3, 4
+ROOT, A, B, CC, LEAF, LOOP = 0, 1, 2, 3, 4, 5
 NO_COLUMN = 0x7fffffff
 
 
@@ -31,15 +32,16 @@ def _automaton(V) -> LexiconTables:
              A: [(400 + k, B if k % 3 else LEAF) for k in range(26)],                # 26 children in words 12 and 13
              B: [(410, LEAF), (last, CC)],                                           # shares word 12 with A; the last id of the last word
              CC: [(last, LEAF)],                                                     # shares the last word with B
-             LEAF: []}
-    flags = {ROOT: 2, A: 0, B: 1, CC: 0, LEAF: 1}
+             LEAF: [],
+             LOOP: [(500, LOOP), (501, LEAF)]}                                       # an edge to itself
+    flags = {ROOT: 2, A: 0, B: 1, CC: 0, LEAF: 1, LOOP: 0}
     off, tok, nxt = [0], [], []
-    for s in range(5):
+    for s in range(6):
         for t, n in edges[s]:
             tok.append(t); nxt.append(n)
         off.append(len(tok))
     return LexiconTables(np.asarray(off, np.int32), np.asarray(tok, np.int32), np.asarray(nxt, np.int32),
-                         np.asarray([flags[s] for s in range(5)], np.uint8), [ROOT], [{}], V, EOS, PAD, NOP)
+                         np.asarray([flags[s] for s in range(6)], np.uint8), [ROOT], [{}], V, EOS, PAD, NOP)
 
 
 def _case(lt, rows):
@@ -50,7 +52,8 @@ def _case(lt, rows):
     state0, token = np.full(S, FREE_STATE, np.int32), np.full(S, -9, np.int32)
     last = lt.vocab - 1
     kinds = [(ROOT, lambda r: 300 + (r * 7) % 300), (A, lambda r: 400 + r % 26), (B, lambda r: last), (B, lambda r: EOS), (-1, lambda r: 410),
-             (A, lambda r: NO_COLUMN), (B, lambda r: 410), (CC, lambda r: PAD), (ROOT, lambda r: NOP), (CC, lambda r: last)]
+             (A, lambda r: NO_COLUMN), (B, lambda r: 410), (CC, lambda r: PAD), (ROOT, lambda r: NOP), (CC, lambda r: last),
+             (LOOP, lambda r: 500), (LOOP, lambda r: 501)]               # the edge to itself, and the way out of that state
     for r in range(rows):
         st, t = kinds[r % len(kinds)]
         state0[slots[r]], token[slots[r]] = st, t(r)
@@ -127,6 +130,7 @@ def test_the_hand_made_automaton_holds_the_cases():
     assert lt.accepts(LEAF) and len(lt.edges(LEAF)[0]) == 0
     assert max(lt.allowed(B)) == 81919 and 81919 >> 5 == 2559
     assert lt.advance(ROOT, NOP) == ROOT and NOP in lt.allowed(ROOT)
+    assert lt.advance(LOOP, 500) == LOOP and lt.advance(LOOP, 501) == LEAF
 
 
 L_STEP_LANES = 64       # SA_LEXICON_STEP_THREADS (csrc/lexicon.h)
