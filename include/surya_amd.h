@@ -955,6 +955,32 @@ int surya_ocrerr_destroy(surya_ocrerr* h);
  * Enqueue only (the host arrays are staged before the call returns). */
 int surya_ocrerr_forward(surya_ocrerr* h, const int32_t* ids, const int32_t* text_len, int n_texts, float* logits, int32_t* labels,
                          void* stream);
+/* The classifier's kernels by themselves (tests/test_gpu_ocr_ops.py), each through the launcher the engine uses (csrc/ocr_error_kernels.h).
+ * dtype = SA_DTYPE_F32 / BF16 / F16 (the storage type of every `void*` operand). Device pointers are the caller's; a NULL pointer or a
+ * size <= 0 returns SA_ERR_ARG, a size the kernel's vector accesses cannot take (C % 4, head_dim % 8, K not in whole 128-byte chunks)
+ * SA_ERR_SHAPE, before anything is launched. Enqueue only, except cls_attn.
+ *   embed_ln:    y[r] = LayerNorm(T(word[clamp(ids[r], 0, vocab - 1)] + pos[tok_pos[r]])) over C channels (tok_pos is NOT clamped).
+ *   layernorm:   y[r] = LayerNorm(x[r]), fp32 two-pass statistics, eps inside the square root.
+ *   gather_rows: out[i] = x[rows_idx[i]], rows of C elements.
+ *   cls_attn:    cls_attn_kernel<T, head_dim>: out[t] [dim] = attention of ONE query, row host_starts[t] of the packed qkv rows [.][3 dim]
+ *                (q | k | v, head h at columns h * head_dim), over the host_lens[t] rows from there; the LDS is sized for max_len. The two
+ *                HOST arrays are copied by the call, which returns after the kernel ran. bf16 and fp16 only (fp32: SA_ERR_UNSUPPORTED);
+ *                head_dim in {32, 64, 80, 128}, max_len <= 4096 and the LDS within 64 KB, else SA_ERR_UNSUPPORTED; dim != heads *
+ *                head_dim, a start < 0 or a length outside 1 .. max_len: SA_ERR_SHAPE.
+ *   cls_head:    logits[t][j] = T(pre[t] . w[j] + b[j]) as fp32, labels[t] = the first argmax (a NaN never wins; all NaN: 0).
+ *   gemm:        OcrErrModel's GEMM: C [M][N] = epi(X W^T + bias), X rows ldx elements apart, W [N][K], bias [N], R [M][N]; epi 0 bias,
+ *                1 residual (T(T(X W^T + bias) + R), R required), 2 erf GELU, 5 ReLU, others SA_ERR_UNSUPPORTED. pinned = 1: the 64 x 64
+ *                tile of the [CLS]-row GEMMs whatever M; 0: launch_gemm's choice. */
+int surya_op_ocrerr_embed_ln(int dtype, const int32_t* ids, const int32_t* tok_pos, const void* word, const void* pos, const void* w, const void* b,
+                             void* y, int rows, int C, int vocab, float eps, void* stream);
+int surya_op_ocrerr_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, int rows, int C, float eps, void* stream);
+int surya_op_ocrerr_gather_rows(int dtype, const void* x, const int32_t* rows_idx, void* out, int n, int C, void* stream);
+int surya_op_ocrerr_cls_attn(int dtype, int head_dim, const void* qkv, const int32_t* host_starts, const int32_t* host_lens, int n, void* out,
+                             int dim, int heads, int max_len, float scale, void* stream);
+int surya_op_ocrerr_cls_head(int dtype, const void* pre, const void* w, const void* b, float* logits, int32_t* labels, int n, int dim,
+                             int num_labels, void* stream);
+int surya_op_ocrerr_gemm(int dtype, int epi, int pinned, const void* X, long ldx, const void* W, const void* bias, void* C, const void* R, int M,
+                         int N, int K, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Measurement support (bench.py `roofline`): when enabled every GEMM launch is bracketed by hipEvents on its own

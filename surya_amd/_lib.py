@@ -187,6 +187,18 @@ def _bind_lay_ops(lib):
     for name, args in rec.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, C.c_int
+    # the OCR-error classifier's kernels alone (csrc/ocr_error_kernels.h): `dtype` first; cls_attn's starts / lengths are host arrays
+    ocr = {
+        "surya_op_ocrerr_embed_ln": [i, p, p, p, p, p, p, p, i, i, i, f, p],
+        "surya_op_ocrerr_layernorm": [i, p, p, p, p, i, i, f, p],
+        "surya_op_ocrerr_gather_rows": [i, p, p, p, i, i, p],
+        "surya_op_ocrerr_cls_attn": [i, i, p, ip, ip, i, p, i, i, i, f, p],
+        "surya_op_ocrerr_cls_head": [i, p, p, p, p, p, i, i, i, p],
+        "surya_op_ocrerr_gemm": [i, i, i, p, l, p, p, p, p, i, i, i, p],
+    }
+    for name, args in ocr.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, C.c_int
 
 
 def check(rc: int, what: str):

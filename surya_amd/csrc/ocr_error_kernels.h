@@ -199,5 +199,66 @@ __global__ __launch_bounds__(64) void cls_head_kernel(const T* __restrict__ pre,
     if (lane == 0) labels[t] = arg;
 }
 
+// ---- launchers: the one launch of each kernel, shared by OcrErrModel and the surya_op_ocrerr_* hooks (ocr_error_model.hip)
+template <typename T>
+static inline int launch_embed_ln(const int* ids, const int* tok_pos, const T* word, const T* pos, const T* w, const T* b, T* y, int rows, int C,
+                                  int vocab, float eps, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    hipLaunchKernelGGL(embed_ln_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, ids, tok_pos, word, pos, w, b, y, rows, C, vocab, eps);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static inline int launch_layernorm(const T* x, const T* w, const T* b, T* y, int rows, int C, float eps, hipStream_t s) {
+    if (rows <= 0) return SA_OK;
+    hipLaunchKernelGGL(layernorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, x, w, b, y, rows, C, eps);
+    return (int)hipGetLastError();
+}
+
+template <typename T>
+static inline int launch_gather_rows(const T* x, const int* rows_idx, T* out, int n, int C, hipStream_t s) {
+    if (n <= 0) return SA_OK;
+    hipLaunchKernelGGL(gather_rows_kernel<T>, dim3(n), dim3(64), 0, s, x, rows_idx, out, n, C);
+    return (int)hipGetLastError();
+}
+
+// LDS of cls_attn_kernel for texts of up to max_len tokens: q [dim] + P [heads][NC * 64] + chunk factors [heads][NC] floats
+static inline size_t cls_attn_lds_bytes(int dim, int heads, int max_len) {
+    const long ncmax = (max_len + 63) / 64;
+    return (size_t)(dim + (long)heads * ncmax * 64 + (long)heads * ncmax) * sizeof(float);
+}
+
+// starts / lens: device [n]; every len in 1 .. max_len (the caller checks them on the host). 16-bit storage only; head_dim D in
+// {32, 64, 80, 128}, max_len <= 4096 (the kernel keeps a chunk's running max in lane `chunk`) and the LDS within 64 KB, else SA_ERR_UNSUPPORTED.
+template <typename T>
+static inline int launch_cls_attn(int D, const T* qkv, const int* starts, const int* lens, int n, T* out, int dim, int heads, int max_len,
+                                  float scale, hipStream_t s) {
+    if constexpr (sizeof(T) == 2) {
+        if (n <= 0) return SA_OK;
+        if (max_len < 1 || max_len > 4096) return SA_ERR_UNSUPPORTED;
+        const size_t lds = cls_attn_lds_bytes(dim, heads, max_len);
+        if (lds > 64 * 1024) return SA_ERR_UNSUPPORTED;
+#define SA_OCR_CLS(DD) hipLaunchKernelGGL((cls_attn_kernel<T, DD>), dim3(n), dim3(256), lds, s, qkv, starts, lens, out, dim, heads, scale)
+        switch (D) {
+            case 32: SA_OCR_CLS(32); break;
+            case 64: SA_OCR_CLS(64); break;
+            case 80: SA_OCR_CLS(80); break;
+            case 128: SA_OCR_CLS(128); break;
+            default: return SA_ERR_UNSUPPORTED;
+        }
+#undef SA_OCR_CLS
+        return (int)hipGetLastError();
+    } else {
+        return SA_ERR_UNSUPPORTED;
+    }
+}
+
+template <typename T>
+static inline int launch_cls_head(const T* pre, const T* w, const T* b, float* logits, int* labels, int n, int dim, int num_labels, hipStream_t s) {
+    if (n <= 0) return SA_OK;
+    hipLaunchKernelGGL(cls_head_kernel<T>, dim3(n), dim3(64), 0, s, pre, w, b, logits, labels, dim, num_labels);
+    return (int)hipGetLastError();
+}
+
 }  // namespace ocr
 }  // namespace sa

@@ -40,6 +40,16 @@ struct OcrErrBase {
 
 static size_t oalign(size_t v) { return (v + 255) & ~(size_t)255; }
 
+// Every GEMM of the classifier, shared by OcrErrModel and surya_op_ocrerr_gemm: C = epilogue(X W^T + bias), X rows ldx elements apart, W [N][K],
+// C and R [M][N]. pinned = the [CLS]-row GEMMs: the 64 x 64 tile whatever the text count.
+template <typename T, int EPI>
+static int ocr_gemm(const T* X, long ldx, const T* Wt, const T* bias, T* C, const T* R, int M, int N, int K, bool pinned, hipStream_t s) {
+    GemmArgs<T, T> a{X, ldx, Wt, (long)K, C, (long)N, bias, R, (long)N, M, N, K};
+    if (M <= 0) return SA_OK;
+    if (pinned) return launch_gemm_cfg<T, T, 64, 64, 2, 2, EPI>(a, s);     // [CLS]-row GEMMs: one path whatever the text count
+    return launch_gemm<T, T, EPI>(a, s);
+}
+
 template <typename T>
 struct OcrErrModel : OcrErrBase {
     surya_ocrerr_config c;
@@ -86,8 +96,7 @@ struct OcrErrModel : OcrErrBase {
             SA_HIP(hipMalloc((void**)&sl.dev, stage_cap));
             SA_HIP(hipEventCreateWithFlags(&sl.ev, hipEventDisableTiming));
         }
-        const int ncmax = (c.max_pos + 63) / 64;
-        cls_lds = (size_t)(c.dim + (long)c.heads * ncmax * 64 + (long)c.heads * ncmax) * sizeof(float);
+        cls_lds = ocr::cls_attn_lds_bytes(c.dim, c.heads, c.max_pos);
         if (sizeof(T) == 2 && cls_lds > 64 * 1024) return SA_ERR_UNSUPPORTED;
         return SA_OK;
     }
@@ -103,34 +112,17 @@ struct OcrErrModel : OcrErrBase {
 
     template <int EPI>
     int gemm(const T* X, long ldx, const T* Wt, const T* bias, T* C, const T* R, int M, int N, int K, bool pinned, hipStream_t s) {
-        GemmArgs<T, T> a{X, ldx, Wt, (long)K, C, (long)N, bias, R, (long)N, M, N, K};
-        if (M <= 0) return SA_OK;
-        if (pinned) return launch_gemm_cfg<T, T, 64, 64, 2, 2, EPI>(a, s);     // [CLS]-row GEMMs: one path whatever the text count
-        return launch_gemm<T, T, EPI>(a, s);
+        return ocr_gemm<T, EPI>(X, ldx, Wt, bias, C, R, M, N, K, pinned, s);
     }
     int layernorm(const T* in, const T* wt, const T* b, T* out, int rows, hipStream_t s) {
-        if (rows <= 0) return SA_OK;
-        hipLaunchKernelGGL(ocr::layernorm_kernel<T>, dim3(cdiv(rows, 4)), dim3(256), 0, s, in, wt, b, out, rows, c.dim, c.ln_eps);
-        return (int)hipGetLastError();
+        return ocr::launch_layernorm<T>(in, wt, b, out, rows, c.dim, c.ln_eps, s);
     }
     int attention(const T* q, T* o, const AttnSegs& sg, int n_tiles, long o_row, hipStream_t s) {
         const long ld = 3L * c.dim;
         return launch_attn<T>(D, q, q + c.dim, q + 2 * c.dim, o, sg, n_tiles, c.heads, ld, D, ld, D, o_row, D, 1, 0, attn_scale, s);
     }
     int cls_attention(const int* starts, const int* lens, int n, hipStream_t s) {
-        if constexpr (sizeof(T) == 2) {
-#define SA_OCR_CLS(DD) hipLaunchKernelGGL((ocr::cls_attn_kernel<T, DD>), dim3(n), dim3(256), cls_lds, s, qkv, starts, lens, catt, c.dim, c.heads, attn_scale)
-            switch (D) {
-                case 32: SA_OCR_CLS(32); break;
-                case 64: SA_OCR_CLS(64); break;
-                case 80: SA_OCR_CLS(80); break;
-                case 128: SA_OCR_CLS(128); break;
-                default: return SA_ERR_UNSUPPORTED;
-            }
-#undef SA_OCR_CLS
-            return (int)hipGetLastError();
-        }
-        return SA_ERR_STATE;
+        return ocr::launch_cls_attn<T>(D, qkv, starts, lens, n, catt, c.dim, c.heads, c.max_pos, attn_scale, s);
     }
 
     int forward(const int32_t* ids, const int32_t* text_len, int n, float* logits, int32_t* labels, hipStream_t s) override {
@@ -197,9 +189,8 @@ struct OcrErrModel : OcrErrBase {
         first.o_off = reinterpret_cast<const long*>(sl.dev + o_co);
 
         // ---- embeddings
-        hipLaunchKernelGGL(ocr::embed_ln_kernel<T>, dim3(cdiv(Tn, 4)), dim3(256), 0, s, ids, d_pos, gw(SA_OW_WORD), gw(SA_OW_POS),
-                           gw(SA_OW_EMB_LN_W), gw(SA_OW_EMB_LN_B), x, Tn, c.dim, c.vocab, c.ln_eps);
-        int rc = (int)hipGetLastError();
+        int rc = ocr::launch_embed_ln<T>(ids, d_pos, gw(SA_OW_WORD), gw(SA_OW_POS), gw(SA_OW_EMB_LN_W), gw(SA_OW_EMB_LN_B), x, Tn, c.dim, c.vocab,
+                                         c.ln_eps, s);
         if (rc) return rc;
         const int dim = c.dim, hid = c.hidden;
         const bool cls_only = tuning().ocrerr_cls_only != 0;
@@ -225,8 +216,7 @@ struct OcrErrModel : OcrErrBase {
             } else {
                 if ((rc = cls_attention(d_start, d_len, n, s))) return rc;
             }
-            hipLaunchKernelGGL(ocr::gather_rows_kernel<T>, dim3(n), dim3(64), 0, s, x, d_start, cx, n, dim);
-            if ((rc = (int)hipGetLastError())) return rc;
+            if ((rc = ocr::launch_gather_rows<T>(x, d_start, cx, n, dim, s))) return rc;
             if ((rc = gemm<EPI_RESIDUAL>(catt, att_ld, lw(l, SA_OL_OUT_W), lw(l, SA_OL_OUT_B), ctmp, cx, n, dim, dim, true, s))) return rc;
             if ((rc = layernorm(ctmp, lw(l, SA_OL_SA_LN_W), lw(l, SA_OL_SA_LN_B), ch1, n, s))) return rc;
             if ((rc = gemm<EPI_GELU>(ch1, dim, lw(l, SA_OL_LIN1_W), lw(l, SA_OL_LIN1_B), cffn, nullptr, n, hid, dim, true, s))) return rc;
@@ -234,14 +224,11 @@ struct OcrErrModel : OcrErrBase {
             if ((rc = layernorm(ctmp, lw(l, SA_OL_OUT_LN_W), lw(l, SA_OL_OUT_LN_B), cx, n, s))) return rc;
         }
         if (!cls_only || c.layers == 0) {
-            hipLaunchKernelGGL(ocr::gather_rows_kernel<T>, dim3(n), dim3(64), 0, s, x, d_start, cx, n, dim);
-            if ((rc = (int)hipGetLastError())) return rc;
+            if ((rc = ocr::launch_gather_rows<T>(x, d_start, cx, n, dim, s))) return rc;
         }
         // ---- head: pre_classifier + ReLU (GEMM at M = n), classifier + argmax
         if ((rc = gemm<EPI_RELU>(cx, dim, gw(SA_OW_PRE_W), gw(SA_OW_PRE_B), cpre, nullptr, n, dim, dim, true, s))) return rc;
-        hipLaunchKernelGGL(ocr::cls_head_kernel<T>, dim3(n), dim3(64), 0, s, cpre, gw(SA_OW_CLS_W), gw(SA_OW_CLS_B), logits, labels, dim,
-                           c.num_labels);
-        return (int)hipGetLastError();
+        return ocr::launch_cls_head<T>(cpre, gw(SA_OW_CLS_W), gw(SA_OW_CLS_B), logits, labels, n, dim, c.num_labels, s);
     }
 };
 
@@ -255,6 +242,38 @@ int op_attn_f16(int D, const void* q, const void* k, const void* v, void* o, con
                 long k_row, long k_head, long o_row, long o_head, int group, int causal, float scale, hipStream_t s) {
     return launch_attn<fp16_t>(D, (const fp16_t*)q, (const fp16_t*)k, (const fp16_t*)v, (fp16_t*)o, sg, n_tiles, heads, q_row, q_head, k_row, k_head,
                                o_row, o_head, group, causal, scale, s);
+}
+
+// the bodies of surya_op_ocrerr_cls_attn / surya_op_ocrerr_gemm (below) per storage type
+template <typename T>
+static int op_cls_attn(int head_dim, const void* qkv, const int32_t* host_starts, const int32_t* host_lens, int n, void* out, int dim, int heads,
+                       int max_len, float scale, hipStream_t s) {
+    int* d = nullptr;                                     // starts [n] | lens [n]
+    std::vector<int> h(2 * (size_t)n);
+    std::copy(host_starts, host_starts + n, h.begin());
+    std::copy(host_lens, host_lens + n, h.begin() + n);
+    SA_HIP(hipMalloc((void**)&d, h.size() * sizeof(int)));
+    int rc = (int)hipMemcpyAsync(d, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice, s);
+    if (!rc) rc = ocr::launch_cls_attn<T>(head_dim, (const T*)qkv, d, d + n, n, (T*)out, dim, heads, max_len, scale, s);
+    const int rs = (int)hipStreamSynchronize(s);          // the tables above are freed on return
+    (void)hipFree(d);
+    return rc ? rc : rs;
+}
+
+template <typename T>
+static int op_ocr_gemm(int epi, int pinned, const void* X, long ldx, const void* W, const void* bias, void* C, const void* R, int M, int N, int K,
+                       hipStream_t s) {
+    constexpr int V = 16 / (int)sizeof(T);                // elements per 16-byte chunk: rows of X, W, C and R are read and written in them
+    if (K % Ty<T>::KE || N % 4 || N % V || ldx % V || ldx < K) return SA_ERR_SHAPE;
+    const T *x = (const T*)X, *w = (const T*)W, *bb = (const T*)bias, *r = (const T*)R;
+    T* c = (T*)C;
+    switch (epi) {
+        case EPI_BIAS: return ocr_gemm<T, EPI_BIAS>(x, ldx, w, bb, c, nullptr, M, N, K, pinned != 0, s);
+        case EPI_RESIDUAL: return r ? ocr_gemm<T, EPI_RESIDUAL>(x, ldx, w, bb, c, r, M, N, K, pinned != 0, s) : (int)SA_ERR_ARG;
+        case EPI_GELU: return ocr_gemm<T, EPI_GELU>(x, ldx, w, bb, c, nullptr, M, N, K, pinned != 0, s);
+        case EPI_RELU: return ocr_gemm<T, EPI_RELU>(x, ldx, w, bb, c, nullptr, M, N, K, pinned != 0, s);
+        default: return SA_ERR_UNSUPPORTED;
+    }
 }
 
 }  // namespace sa
@@ -307,5 +326,62 @@ int surya_ocrerr_forward(surya_ocrerr* h, const int32_t* ids, const int32_t* tex
     if (!h || !h->impl || (n_texts > 0 && (!ids || !text_len || !logits || !labels)) || n_texts < 0) return SA_ERR_ARG;
     return h->impl->forward(ids, text_len, n_texts, logits, labels, (hipStream_t)stream);
 }
+
+// ---- the classifier's kernels alone (tests): the launchers of ocr_error_kernels.h and ocr_gemm, as OcrErrModel calls them
+#define SA_OCR_BY_DTYPE(CALL)                                                \
+    switch (dtype) {                                                         \
+        case SA_DTYPE_F32: { typedef float T; return CALL; }                 \
+        case SA_DTYPE_BF16: { typedef bf16_t T; return CALL; }               \
+        case SA_DTYPE_F16: { typedef fp16_t T; return CALL; }                \
+        default: return SA_ERR_UNSUPPORTED;                                  \
+    }
+
+int surya_op_ocrerr_embed_ln(int dtype, const int32_t* ids, const int32_t* tok_pos, const void* word, const void* pos, const void* w, const void* b,
+                             void* y, int rows, int C, int vocab, float eps, void* stream) {
+    if (!ids || !tok_pos || !word || !pos || !w || !b || !y || rows <= 0 || C <= 0 || vocab <= 0) return SA_ERR_ARG;
+    if (C % 4) return SA_ERR_SHAPE;
+    SA_OCR_BY_DTYPE(ocr::launch_embed_ln<T>(ids, tok_pos, (const T*)word, (const T*)pos, (const T*)w, (const T*)b, (T*)y, rows, C, vocab, eps,
+                                            (hipStream_t)stream))
+}
+
+int surya_op_ocrerr_layernorm(int dtype, const void* x, const void* w, const void* b, void* y, int rows, int C, float eps, void* stream) {
+    if (!x || !w || !b || !y || rows <= 0 || C <= 0) return SA_ERR_ARG;
+    if (C % 4) return SA_ERR_SHAPE;
+    SA_OCR_BY_DTYPE(ocr::launch_layernorm<T>((const T*)x, (const T*)w, (const T*)b, (T*)y, rows, C, eps, (hipStream_t)stream))
+}
+
+int surya_op_ocrerr_gather_rows(int dtype, const void* x, const int32_t* rows_idx, void* out, int n, int C, void* stream) {
+    if (!x || !rows_idx || !out || n <= 0 || C <= 0) return SA_ERR_ARG;
+    if (C % 4) return SA_ERR_SHAPE;
+    SA_OCR_BY_DTYPE(ocr::launch_gather_rows<T>((const T*)x, rows_idx, (T*)out, n, C, (hipStream_t)stream))
+}
+
+int surya_op_ocrerr_cls_attn(int dtype, int head_dim, const void* qkv, const int32_t* host_starts, const int32_t* host_lens, int n, void* out,
+                             int dim, int heads, int max_len, float scale, void* stream) {
+    if (!qkv || !host_starts || !host_lens || !out || n <= 0 || dim <= 0 || heads <= 0 || head_dim <= 0 || max_len <= 0) return SA_ERR_ARG;
+    if (dtype == SA_DTYPE_F32) return SA_ERR_UNSUPPORTED;                       // cls_attn_kernel has 16-bit storage only
+    if (dtype != SA_DTYPE_BF16 && dtype != SA_DTYPE_F16) return SA_ERR_UNSUPPORTED;
+    if (head_dim % 8 || dim != heads * head_dim) return SA_ERR_SHAPE;
+    if (head_dim != 32 && head_dim != 64 && head_dim != 80 && head_dim != 128) return SA_ERR_UNSUPPORTED;
+    if (max_len > 4096 || ocr::cls_attn_lds_bytes(dim, heads, max_len) > 64 * 1024) return SA_ERR_UNSUPPORTED;
+    for (int i = 0; i < n; ++i)
+        if (host_starts[i] < 0 || host_lens[i] < 1 || host_lens[i] > max_len) return SA_ERR_SHAPE;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SA_DTYPE_BF16) return op_cls_attn<bf16_t>(head_dim, qkv, host_starts, host_lens, n, out, dim, heads, max_len, scale, s);
+    return op_cls_attn<fp16_t>(head_dim, qkv, host_starts, host_lens, n, out, dim, heads, max_len, scale, s);
+}
+
+int surya_op_ocrerr_cls_head(int dtype, const void* pre, const void* w, const void* b, float* logits, int32_t* labels, int n, int dim,
+                             int num_labels, void* stream) {
+    if (!pre || !w || !b || !logits || !labels || n <= 0 || dim <= 0 || num_labels <= 0) return SA_ERR_ARG;
+    SA_OCR_BY_DTYPE(ocr::launch_cls_head<T>((const T*)pre, (const T*)w, (const T*)b, logits, labels, n, dim, num_labels, (hipStream_t)stream))
+}
+
+int surya_op_ocrerr_gemm(int dtype, int epi, int pinned, const void* X, long ldx, const void* W, const void* bias, void* C, const void* R, int M,
+                         int N, int K, void* stream) {
+    if (!X || !W || !bias || !C || M <= 0 || N <= 0 || K <= 0 || ldx <= 0) return SA_ERR_ARG;
+    SA_OCR_BY_DTYPE(op_ocr_gemm<T>(epi, pinned, X, ldx, W, bias, C, R, M, N, K, (hipStream_t)stream))
+}
+#undef SA_OCR_BY_DTYPE
 
 }  // extern "C"
