@@ -452,6 +452,25 @@ int surya_op_kv8_quant_rows(int head_dim, const void* kcache, const void* vcache
 int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
                              float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
                              int heads, int kv_heads, int max_kv_len, float scale, void* stream);
+/* The same two launches with the MXFP8 copy of the output that the fp8 o-projection reads (tests): the hooks only fill out8 / sout / srows of
+ * DecodeAttnArgs / DecodeAttnKv8Args. out8[rows][heads * head_dim] = e4m3 codes of the rows of `out` AS STORED (rounded to bf16 first), one E8M0
+ * scale byte per 32 columns at sout[col / 128][srows][4] (K-tile-major, csrc/gemm_mx.h; oracle/mx_oracle.py::quantize is the definition);
+ * srows >= rows, scale bytes of rows >= `rows` are not written; heads * head_dim a multiple of 128, else SA_ERR_ARG. Only the bf16 flash
+ * kernels (decode_attn_flash2_kernel in both buffer forms, decode_attn_flash_kernel) and the KV8 kernel have the copy: dtype fp32
+ * (decode_attn_mfma_kernel) and fp16 return SA_ERR_UNSUPPORTED and launch nothing.
+ * What a launch may read. surya_op_decode_attn (all three kernels, every dtype): of the caches only rows < row_len[r] of the row's own slot
+ * and kv heads can influence the result; row_len[r] = 0 is allowed (LayoutModel::decode_step at position 0 launches it) and then no cache row can
+ * (decode_attn_flash_kernel and decode_attn_mfma_kernel still load row 0 through their clamp: its K copies are masked, its V copies zeroed). Cache rows
+ * that were never appended, other slots and slabs >= n_slabs may hold anything, NaN included.
+ * surya_op_decode_attn_kv8: K rows and k scales likewise; but the kernel fetches V^T (token-minor inside a 128-token tile) and the v scales by
+ * whole 16-key blocks and multiplies what lies past the context by P = 0, so the V^T columns and v scales of tokens row_len[r] + 1 ..
+ * (row_len[r] | 31) must be FINITE (RecModel zero-fills the arrays at creation and appends only finite rows). */
+int surya_op_decode_attn_mx(int dtype, int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* kcache,
+                            void* vcache, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows, int heads,
+                            int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows);
+int surya_op_decode_attn_kv8_mx(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
+                                float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
+                                int heads, int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows);
 
 /* bf16 split-K projection of the decode step (launch_gemm_splitk): raw fp32 partial sums to part[*splitk][M][N] (capacity 8 slabs), no
  * epilogue; M <= 256 as the decoder runs it. */

@@ -199,6 +199,11 @@ def _bind_lay_ops(lib):
     for name, args in ocr.items():
         fn = getattr(lib, name)
         fn.argtypes, fn.restype = args, C.c_int
+    # decode attention with the MXFP8 copy of its output (csrc/rec_model.hip): surya_op_decode_attn / _kv8 + (out8, sout, srows)
+    lib.surya_op_decode_attn_mx.argtypes = [i, i, p, i, p, p, p, p, p, p, p, i, i, i, i, f, p, p, p, i]
+    lib.surya_op_decode_attn_mx.restype = C.c_int
+    lib.surya_op_decode_attn_kv8_mx.argtypes = [i, p, i, p, p, p, p, p, p, p, p, p, i, i, i, i, f, p, p, p, i]
+    lib.surya_op_decode_attn_kv8_mx.restype = C.c_int
 
 
 def check(rc: int, what: str):

@@ -134,6 +134,10 @@ __global__ __launch_bounds__(256) void decode_attn_mfma_kernel(const float* __re
         Ty<T>::st(vnew_dst + i, val);
         if (new_tile == 0) Ty<T>::st(reinterpret_cast<T*>(Vs + new_row * ROWB) + i, val);
     }
+    // empty cache (block-uniform): the clamp above filled every row from cache row 0, which was never appended. Rows 1 .. 7 of V are
+    // multiplied by P = 0 in the 8-key trip of P . V: they must be finite whatever that row held
+    if (len == 0)
+        for (int i = tid; i < 7 * CPRk; i += 256) *reinterpret_cast<u32x4*>(Vs + ROWB + i * 16) = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
     SA_DA_STAMP(4)
 
@@ -369,6 +373,10 @@ __global__ __launch_bounds__(256) void decode_attn_flash_kernel(const float* __r
         Ty<T>::st(vnew_dst + i, val);
         if (new_tile == 0) Ty<T>::st(reinterpret_cast<T*>(Vs + new_row * ROWB) + i, val);
     }
+    // empty cache (block-uniform): rows 1 .. 15 of the first MFMA step are copies of cache row 0, which was never appended; they meet
+    // P = 0 in O^T += V^T P^T and must be finite whatever that row held (the LDS-DMA has landed: vmcnt(0) and the barrier above)
+    if (len == 0)
+        for (int i = tid; i < 15 * CPR; i += 256) *reinterpret_cast<u32x4*>(Vs + ROWB + i * 16) = u32x4{0u, 0u, 0u, 0u};
     __syncthreads();
     SA_DA_STAMP(4)
 
@@ -566,8 +574,8 @@ __global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
 
-    // Rows of tile `base` that a 16-key MFMA step can touch get finite data (cached rows, clamped duplicates past len) -- EXCEPT row
-    // `len` itself: the lanes that would fill it are masked off (LDS-DMA honours EXEC), so the new token's K / V rows, which this
+    // Rows of tile `base` that a 16-key MFMA step can touch get finite data (cached rows, clamped duplicates of row len - 1 past len; with
+    // an empty cache zeros, below) -- EXCEPT row `len` itself: the lanes that would fill it are masked off (LDS-DMA honours EXEC), so the new token's K / V rows, which this
     // workgroup writes with ordinary LDS stores, never race with a late-landing duplicate and need no barrier of their own.
     auto issue_tile = [&](int base, int buf) {
         const int rows = min(KT, (total - base + 15) & ~15);
@@ -577,7 +585,7 @@ __global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __
         for (int g = wave; g < ngroups; g += 4) {
             const int r = g * RPI + lane / CPR, pc = lane % CPR;
             const long j = min(base + r, max(len - 1, 0));
-            if (base + r != len) {
+            if (len > 0 && base + r != len) {                // empty cache: nothing to fetch (row 0 was never appended), see below
                 __builtin_amdgcn_global_load_lds((gptr_t)(kb + j * ROWB + ((pc ^ (r & XM)) << 4)), (lptr_t)(Kd + g * 1024), 16, 0, 0);
                 __builtin_amdgcn_global_load_lds((gptr_t)(vb + j * ROWB + (pc << 4)), (lptr_t)(Vd + g * 1024), 16, 0, 0);
             }
@@ -673,6 +681,10 @@ __global__ __launch_bounds__(256) void decode_attn_flash2_kernel(const float* __
         lds_put4(qT + hh * ROWB, hh & XM, i0 + half, yhi, scale);
     }
     if (new_tile == 0) put_new_rows(0);
+    // empty cache (block-uniform): no row was fetched. K rows 1 .. 15 of the first MFMA step may hold anything (their scores are replaced
+    // by -inf), the V rows meet P = 0 in O^T += V^T P^T and must be finite: zero them
+    if (len == 0)
+        for (int i = tid; i < 15 * CPR; i += 256) *reinterpret_cast<u32x4*>(Vs + ROWB + i * 16) = u32x4{0u, 0u, 0u, 0u};
     SA_DA_STAMP(3)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // the LDS-DMA rows of tile 0 (not tracked by the compiler)
     __syncthreads();

@@ -490,9 +490,10 @@ int surya_op_attn(int dtype, int head_dim, const void* q, const void* k, const v
     return SA_OK;
 }
 
-int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* kcache,
-                         void* vcache, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows, int heads,
-                         int kv_heads, int max_kv_len, float scale, void* stream) {
+// surya_op_decode_attn and surya_op_decode_attn_mx: the second one also fills the three MXFP8 fields of the args (out8 != NULL)
+static int op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* kcache,
+                          void* vcache, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows, int heads,
+                          int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows) {
     if (!qkv_part || !qkv_bias || !out || !kcache || !vcache || !active_slots || !row_len || !rope_cs) return SA_ERR_ARG;
     if (rows <= 0 || n_slabs < 1 || n_slabs > 8 || kv_heads <= 0 || heads % kv_heads) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
@@ -501,19 +502,37 @@ int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_s
     if (dtype == SA_DTYPE_BF16) {
         sa::DecodeAttnArgs<bf16_t> a{qkv_part, n_slabs, (const bf16_t*)qkv_bias, (bf16_t*)out, (bf16_t*)kcache, (bf16_t*)vcache, active_slots, row_len,
                                      cs, rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        a.out8 = out8; a.sout = sout; a.srows = srows;
         return sa::launch_decode_attn<bf16_t>(a, s);
     }
     if (dtype == SA_DTYPE_F32) {
         sa::DecodeAttnArgs<float> a{qkv_part, n_slabs, (const float*)qkv_bias, (float*)out, (float*)kcache, (float*)vcache, active_slots, row_len, cs,
                                     rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        a.out8 = out8; a.sout = sout; a.srows = srows;          // no copy in fp32: the launcher refuses
         return sa::launch_decode_attn<float>(a, s);
     }
     if (dtype == SA_DTYPE_F16) {              // d = 64 / 32 built in layout_model.hip, d = 128 (the recogniser's) in rec_model_f16.hip
         sa::DecodeAttnArgs<sa::fp16_t> a{qkv_part, n_slabs, (const sa::fp16_t*)qkv_bias, (sa::fp16_t*)out, (sa::fp16_t*)kcache, (sa::fp16_t*)vcache,
                                          active_slots, row_len, cs, rows, heads, kv_heads, head_dim, max_kv_len, scale};
+        a.out8 = out8; a.sout = sout; a.srows = srows;          // nor in fp16
         return sa::launch_decode_attn<sa::fp16_t>(a, s);
     }
     return SA_ERR_UNSUPPORTED;
+}
+
+int surya_op_decode_attn(int dtype, int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* kcache,
+                         void* vcache, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows, int heads,
+                         int kv_heads, int max_kv_len, float scale, void* stream) {
+    return op_decode_attn(dtype, head_dim, qkv_part, n_slabs, qkv_bias, out, kcache, vcache, active_slots, row_len, rope_cs, rows, heads, kv_heads,
+                          max_kv_len, scale, stream, nullptr, nullptr, 0);
+}
+
+int surya_op_decode_attn_mx(int dtype, int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* kcache,
+                            void* vcache, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows, int heads,
+                            int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows) {
+    if (!out8 || !sout || srows < rows || (heads * head_dim) % 128) return SA_ERR_ARG;
+    return op_decode_attn(dtype, head_dim, qkv_part, n_slabs, qkv_bias, out, kcache, vcache, active_slots, row_len, rope_cs, rows, heads, kv_heads,
+                          max_kv_len, scale, stream, out8, sout, srows);
 }
 
 int surya_op_kv8_quant_rows(int head_dim, const void* kcache, const void* vcache, const int32_t* tok_slot, const int32_t* tok_pos, int n_tokens,
@@ -524,15 +543,31 @@ int surya_op_kv8_quant_rows(int head_dim, const void* kcache, const void* vcache
                                      vscale, kv_heads, max_kv_len, s);
 }
 
-int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
-                             float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
-                             int heads, int kv_heads, int max_kv_len, float scale, void* stream) {
+static int op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
+                              float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
+                              int heads, int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows) {
     if (!qkv_part || !qkv_bias || !out || !k8 || !v8t || !kscale || !vscale || !active_slots || !row_len || !rope_cs) return SA_ERR_ARG;
     if (rows <= 0 || n_slabs < 1 || n_slabs > 8 || kv_heads <= 0 || heads % kv_heads) return SA_ERR_ARG;
     hipStream_t s = (hipStream_t)stream;
     sa::DecodeAttnKv8Args a{qkv_part, n_slabs, (const bf16_t*)qkv_bias, (bf16_t*)out, (uint8_t*)k8, (uint8_t*)v8t, kscale, vscale, active_slots, row_len,
                             reinterpret_cast<const float2*>(rope_cs), rows, heads, kv_heads, head_dim, max_kv_len, scale};
+    a.out8 = out8; a.sout = sout; a.srows = srows;
     return sa::launch_decode_attn_kv8(a, s);
+}
+
+int surya_op_decode_attn_kv8(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
+                             float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
+                             int heads, int kv_heads, int max_kv_len, float scale, void* stream) {
+    return op_decode_attn_kv8(head_dim, qkv_part, n_slabs, qkv_bias, out, k8, v8t, kscale, vscale, active_slots, row_len, rope_cs, rows, heads, kv_heads,
+                              max_kv_len, scale, stream, nullptr, nullptr, 0);
+}
+
+int surya_op_decode_attn_kv8_mx(int head_dim, const float* qkv_part, int n_slabs, const void* qkv_bias, void* out, void* k8, void* v8t,
+                                float* kscale, float* vscale, const int32_t* active_slots, const int32_t* row_len, const float* rope_cs, int rows,
+                                int heads, int kv_heads, int max_kv_len, float scale, void* stream, uint8_t* out8, uint8_t* sout, int srows) {
+    if (!out8 || !sout || srows < rows || (heads * head_dim) % 128) return SA_ERR_ARG;
+    return op_decode_attn_kv8(head_dim, qkv_part, n_slabs, qkv_bias, out, k8, v8t, kscale, vscale, active_slots, row_len, rope_cs, rows, heads, kv_heads,
+                              max_kv_len, scale, stream, out8, sout, srows);
 }
 
 __global__ __launch_bounds__(256) void mx_quantize_rows_kernel(const float* __restrict__ x, int K, uint8_t* __restrict__ q,
