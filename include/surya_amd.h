@@ -174,6 +174,22 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
                          int patch_size, int merge_size, float pad_value, const float* mean, const float* std, int any_poly,
                          int max_stage1_width, int pixel_stride, void* stream);
 
+/* Rectification of rotated line quadrilaterals (RecognitionPredictor.rectify): n quads of the pages -> upright uint8 crops, each the
+ * rule of warp_quad (surya_amd/common/imageops.py): output pixel (u, v) samples its page at the image of (u + 0.5, v + 0.5) under
+ * the line's homography, minus 0.5 per axis, with 4 x 4 cubic taps (a = -0.75) around floor() of that point, replicate border,
+ * float64 sums in tap order (horizontal pass first), rint, clamp to 0..255; uint8-equal to the host function. A crop is written
+ * like a page (HWC, `pixel_stride` bytes per pixel, X = 0 with 4), so surya_rec_preprocess reads it through a descriptor whose
+ * page is the crop: page_off = its offset, page_w / page_h = cw / ch = its size, x0 = y0 = 0, has_poly = 0.
+ * pages, out: device; `out` may lie in the pages' allocation, in a disjoint range. descs: HOST array of n descriptors
+ *   { int64 page_off; int32 page_w, page_h; int32 out_w, out_h; int64 out_off (bytes into out);
+ *     double h[9] (row-major, h[8] = 1: crop corners (0,0), (out_w,0), (out_w,out_h), (0,out_h) -> the quad's p0..p3, grid-line
+ *     coordinates: pixel i covers [i, i + 1)) }                                                          -- 104 bytes, C layout;
+ * they are copied into the launches' kernel arguments, so the array may be reused as soon as the call returns. max_w, max_h: the
+ * largest out_w / out_h of the call (grid sizing). SA_ERR_ARG, with nothing launched, when pixel_stride is not 3 or 4, a size is
+ * non-positive or exceeds max_w / max_h, or (pixel_stride 4) a page_off or out_off is not a multiple of 4; n == 0 launches nothing.
+ * What a descriptor addresses is not checked against the buffers: the caller keeps offsets and sizes inside them. Enqueue only. */
+int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream);
+
 /* Test hooks (tolerance tests of intermediate tensors):
  *   encode_only: run the vision encoder + 2-D position embedding, write [P/merge^2, dec_hidden] features in
  *                ORIGINAL token order (= get_image_embeddings, common/surya/__init__.py:130-195) to `out`

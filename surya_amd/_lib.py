@@ -174,6 +174,8 @@ def _bind_lay_ops(lib):
     lib.surya_rec_wait_boost.argtypes, lib.surya_rec_wait_boost.restype = [p, i, i, ip, fp], C.c_int
     lib.surya_op_rec_boost_step.argtypes, lib.surya_op_rec_boost_step.restype = [C.POINTER(RecLexiconArgsC), p, i, i, p, p, i, p], C.c_int
     lib.surya_op_rec_boost_head.argtypes, lib.surya_op_rec_boost_head.restype = [i, C.POINTER(RecBoostHeadArgsC), p], C.c_int
+    # rectification of rotated line quads in front of surya_rec_preprocess (csrc/rec_rectify.h); `descs` is a host array
+    lib.surya_rec_rectify.argtypes, lib.surya_rec_rectify.restype = [p, p, i, p, i, i, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

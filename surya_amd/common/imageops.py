@@ -11,6 +11,8 @@ They are NOT pinned against cv2 (absent); the parity boundary of the model path 
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 
 
@@ -96,6 +98,112 @@ def fill_poly_mask(h: int, w: int, pts) -> np.ndarray:
             if xb >= xa:
                 mask[y, max(xa, 0): min(xb, w - 1) + 1] = 1
     return mask
+
+
+# ------------------------------------------------------------------------------------------ quadrilateral rectification
+# A rotated text line is a quadrilateral p0..p3, clockwise in image coordinates, whose vertex order is the reading direction: p0 -> p1
+# is the top edge, read left to right. Vertex coordinates are grid-line coordinates (pixel i covers [i, i + 1)), the convention under
+# which slice_and_pad_poly cuts [min, max). The rule is stated here once; csrc/rec_rectify.h restates warp_quad per pixel.
+def quad_size(quad):
+    """(W, H) of the upright crop of a quad: the longer of each pair of opposite edges, rounded half up, at least 1."""
+    p = [(float(x), float(y)) for x, y in quad]             # (plain float64 arithmetic: this runs several times per line of a call)
+    n = lambda a, b: math.sqrt((p[a][0] - p[b][0]) ** 2 + (p[a][1] - p[b][1]) ** 2)
+    return max(1, int(max(n(1, 0), n(2, 3)) + 0.5)), max(1, int(max(n(3, 0), n(2, 1)) + 0.5))
+
+
+def quad_ok(quad) -> bool:
+    """Four vertices, strictly convex and clockwise in image coordinates (every cross product of consecutive edges > 0): what can be
+    rectified. Three points, a bow-tie, zero area and a counter-clockwise quad cannot."""
+    try:
+        if len(quad) != 4 or any(len(v) != 2 for v in quad):
+            return False
+        p = [(float(v[0]), float(v[1])) for v in quad]
+    except (TypeError, ValueError):
+        return False
+    if not all(math.isfinite(c) for v in p for c in v):
+        return False
+    for i in range(4):
+        a, b, c = p[i], p[(i + 1) % 4], p[(i + 2) % 4]
+        if not (b[0] - a[0]) * (c[1] - b[1]) - (b[1] - a[1]) * (c[0] - b[0]) > 0:
+            return False
+    return True
+
+
+def rectify_threshold(value):
+    """A `rectify` setting as a threshold in degrees: None is off, True is 0, a non-negative finite number is itself. ValueError else."""
+    if value is None:
+        return None
+    if value is True:
+        return 0.0
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0 <= value < float("inf"):
+        raise ValueError(f"rectify must be None, True or a non-negative number of degrees, got {value!r}")
+    return float(value)
+
+
+def should_rectify(coords, threshold) -> bool:
+    """THE decision whether a line's slice is warped from its polygon (`coords`, as the slices are cut from: page pixels) instead of
+    being cut as the polygon's bounding rectangle: rectification is on (`threshold`, degrees, not None), the polygon is a rectifiable
+    quad (quad_ok), it is not an axis-aligned rectangle in canonical order (that crop is today's, bit for bit), and its top edge
+    p0 -> p1 is tilted by at least the threshold. No orientation is guessed: the vertex order is the reading direction."""
+    if threshold is None or coords is None or len(coords) != 4 or not quad_ok(coords):
+        return False
+    (x0, y0), (x1, y1), (x2, y2), (x3, y3) = ((float(c[0]), float(c[1])) for c in coords)
+    if y0 == y1 and x1 == x2 and y2 == y3 and x3 == x0 and x0 < x1 and y1 < y2:     # canonical order: p0 is the top-left corner
+        return False
+    return abs(math.degrees(math.atan2(y1 - y0, x1 - x0))) >= threshold
+
+
+def quad_homography(quad, W: int, H: int) -> np.ndarray:
+    """float64 [9], row-major with h[8] = 1: the projective map that takes the rectangle corners (0,0), (W,0), (W,H), (0,H) to p0..p3."""
+    return quad_homographies([quad], [W], [H])[0]
+
+
+def quad_homographies(quads, Ws, Hs) -> np.ndarray:
+    """quad_homography of n quads at once, float64 [n, 9]: the n 8 x 8 systems are built as arrays and solved by one stacked
+    numpy.linalg.solve (the same LAPACK solve per system, so a row does not depend on its neighbours)."""
+    p = np.asarray(quads, np.float64).reshape(-1, 4, 2)
+    n = len(p)
+    W, H = np.asarray(Ws, np.float64).reshape(n), np.asarray(Hs, np.float64).reshape(n)
+    zero = np.zeros(n)
+    u, v = np.stack([zero, W, W, zero], 1), np.stack([zero, zero, H, H], 1)          # [n, 4]: the rectangle corners
+    x, y = p[..., 0], p[..., 1]
+    A = np.zeros((n, 4, 2, 8), np.float64)
+    A[:, :, 0, 0], A[:, :, 0, 1], A[:, :, 0, 2], A[:, :, 0, 6], A[:, :, 0, 7] = u, v, 1.0, -u * x, -v * x
+    A[:, :, 1, 3], A[:, :, 1, 4], A[:, :, 1, 5], A[:, :, 1, 6], A[:, :, 1, 7] = u, v, 1.0, -u * y, -v * y
+    h = np.linalg.solve(A.reshape(n, 8, 8), p.reshape(n, 8, 1))[..., 0]
+    return np.concatenate([h, np.ones((n, 1))], axis=1)
+
+
+def warp_quad(page_u8: np.ndarray, h9, W: int, H: int) -> np.ndarray:
+    """uint8 [H, W, C] (C = the page's pixel stride, 3 or 4): output pixel (u, v) samples the page at the image of (u + 0.5, v + 0.5)
+    under h9, minus 0.5 on both axes (half-pixel centres, as every resampler here); 4 x 4 cubic taps (a = -0.75) around floor() of that
+    point, tap indices clamped to the page (replicate border); float64 products summed in tap order, the horizontal pass per tap row
+    first, then the vertical taps; rint (half to even), clamp to 0..255. With stride 4 the X byte is written as 0."""
+    h = np.asarray(h9, np.float64).reshape(9)
+    ph, pw, C = page_u8.shape
+    U = (np.arange(W, dtype=np.float64) + 0.5)[None, :]
+    V = (np.arange(H, dtype=np.float64) + 0.5)[:, None]
+    w = h[6] * U + h[7] * V + h[8]
+    sx = (h[0] * U + h[1] * V + h[2]) / w - 0.5
+    sy = (h[3] * U + h[4] * V + h[5]) / w - 0.5
+    fx, fy = np.floor(sx), np.floor(sy)
+    wx, wy = _cubic_weights(sx - fx), _cubic_weights(sy - fy)                  # [H, W, 4]
+    # (the base is clamped before it becomes an integer: far outside the page every tap is the border pixel anyway)
+    bx = np.clip(fx, -4.0, pw + 4.0).astype(np.int64)
+    by = np.clip(fy, -4.0, ph + 4.0).astype(np.int64)
+    xi = [np.clip(bx - 1 + k, 0, pw - 1) for k in range(4)]
+    yi = [np.clip(by - 1 + k, 0, ph - 1) for k in range(4)]
+    acc = None
+    for j in range(4):
+        hrow = None
+        for k in range(4):
+            prod = page_u8[yi[j], xi[k], :3].astype(np.float64) * wx[..., k, None]
+            hrow = prod if hrow is None else hrow + prod
+        prod = hrow * wy[..., j, None]
+        acc = prod if acc is None else acc + prod
+    out = np.zeros((H, W, C), np.uint8)
+    out[..., :3] = np.clip(np.rint(acc), 0.0, 255.0).astype(np.uint8)
+    return out
 
 
 def page_pixels(image) -> np.ndarray:

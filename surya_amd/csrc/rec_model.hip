@@ -13,6 +13,7 @@
 #include "rec_engine.h"
 #include "rec_ops.h"
 #include "rec_prep.h"
+#include "rec_rectify.h"
 
 namespace sa {
 
@@ -634,6 +635,11 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
     p.max_mid_w = max_stage1_width;
     p.pix = pixel_stride;
     return sa::prep::prep_run(p, any_poly, max_stage1_width > 0, (hipStream_t)stream);
+}
+
+int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream) {
+    return sa::prep::rectify_run(pages, reinterpret_cast<const sa::prep::RectifyDesc*>(descs), n, out, pixel_stride, max_w, max_h,
+                                 (hipStream_t)stream);
 }
 
 int surya_set_tuning(const char* key, int value) {

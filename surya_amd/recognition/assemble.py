@@ -8,6 +8,7 @@ from typing import List, Optional
 import numpy as np
 
 from ..common.geometry import PolygonBox, coerce_polygon
+from ..common.imageops import quad_homography, quad_size
 from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags, prediction_to_polygon_batch, unwrap_math,
                           words_from_chars)
 from .processor import NOMATH_TOKEN
@@ -32,7 +33,7 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
 
 
 _LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched",
-                "lexicon_index", "boost_matches")
+                "lexicon_index", "boost_matches", "rectified")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -44,7 +45,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
                          "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None,
-                         "lexicon_index": None, "boost_matches": None})
+                         "lexicon_index": None, "boost_matches": None, "rectified": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -148,6 +149,36 @@ def set_boost_fields(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
         line.boost_matches = [int(i) for i in flat["boost_tables"].matches(root, tokens)]
         line.__pydantic_fields_set__.add("boost_matches")
     return line
+
+
+def line_quad(flat, orig):
+    """The quad line `orig` was warped from (a call with `rectify` set keeps flat["quads"] by original position), else None."""
+    quads = flat.get("quads")
+    return None if quads is None else quads[orig]
+
+
+def set_rectified(flat, orig, line: TextLine) -> TextLine:
+    """line.rectified in a call with `rectify` set: whether this line was warped. Every other call leaves None."""
+    if flat.get("quads") is not None:
+        line.rectified = flat["quads"][orig] is not None
+        line.__pydantic_fields_set__.add("rectified")
+    return line
+
+
+def quad_to_page(P, quad, res_scale):
+    """Corners P [..., 2] (float64, in place) of a rectified line's characters, in rectified-crop coordinates, onto the page: clamped
+    into [0, W] x [0, H], mapped through the line's homography in float64, then the high-res rescale with int() truncation of the
+    ordinary path (chars_of). This replaces its shift and clamp-into-bbox: the characters of a tilted line are tilted quads. (The
+    mapped coordinates are rounded to 1e-6 px in front of the truncation, so that the round-off of the solve never moves a corner
+    that sits on an integer down a pixel.)"""
+    W, H = quad_size(quad)
+    h = quad_homography(quad, W, H)
+    u, v = np.clip(P[..., 0], 0.0, float(W)), np.clip(P[..., 1], 0.0, float(H))
+    w = h[6] * u + h[7] * v + h[8]
+    x, y = (h[0] * u + h[1] * v + h[2]) / w, (h[3] * u + h[4] * v + h[5]) / w
+    P[..., 0] = np.trunc(np.round(x, 6) * (1.0 / res_scale[0]))
+    P[..., 1] = np.trunc(np.round(y, 6) * (1.0 / res_scale[1]))
+    return P
 
 
 def assemble_beam_batch(proc, flat, items, drop_repeated_text, return_words, bbox_size) -> List[TextLine]:
@@ -261,18 +292,22 @@ def line_runs(proc, ids: list, far: list):
     return texts, src, csrc, valid
 
 
-def chars_of(line, res_scale, line_bbox) -> List[TextChar]:
+def chars_of(line, res_scale, line_bbox, quad=None) -> List[TextChar]:
     """TextChars of one line with the reference's per-char geometry (:905-909: rescale by the high-res factor with int()
     truncation, shift to the line's corner, clamp into the line's bbox) applied to all of the line's polygons at once;
-    objects are built without re-validating fields that were just computed (pydantic model_construct)."""
+    objects are built without re-validating fields that were just computed (pydantic model_construct). A rectified line
+    (`quad`) takes quad_to_page instead of the shift and clamp."""
     texts, conf, valid, P = line
     if not texts:
         return []
     P = P.copy()
-    P[..., 0] = np.trunc(P[..., 0] * (1.0 / res_scale[0])) + line_bbox[0]
-    P[..., 1] = np.trunc(P[..., 1] * (1.0 / res_scale[1])) + line_bbox[1]
-    np.clip(P[..., 0], line_bbox[0], line_bbox[2], out=P[..., 0])
-    np.clip(P[..., 1], line_bbox[1], line_bbox[3], out=P[..., 1])
+    if quad is not None:
+        quad_to_page(P, quad, res_scale)
+    else:
+        P[..., 0] = np.trunc(P[..., 0] * (1.0 / res_scale[0])) + line_bbox[0]
+        P[..., 1] = np.trunc(P[..., 1] * (1.0 / res_scale[1])) + line_bbox[1]
+        np.clip(P[..., 0], line_bbox[0], line_bbox[2], out=P[..., 0])
+        np.clip(P[..., 1], line_bbox[1], line_bbox[3], out=P[..., 1])
     polys = P.tolist()
     conf = [0.0 if c != c else c for c in conf.tolist()]               # BaseChar: NaN -> 0, stored as a float
     return [_text_char(pg, c, t, v) for pg, c, t, v in zip(polys, conf, texts, valid.tolist())]
@@ -282,6 +317,10 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
+    if flat.get("quads") is not None and not flat.get("_quads_set"):      # a call with `rectify`: the line, then whether it was warped
+        line = assemble_line(proc, {**flat, "_quads_set": True}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
+                             bbox_size, alts=alts)
+        return set_rectified(flat, orig, line)
     if flat.get("boost_tables") is not None:          # a boosted call: alts = (plain ids [T], the emitted tokens' plain probabilities [T])
         inner, its = boost_items(flat, [(sorted_pos, orig, tokens, sc, bbox_rows, alts)])
         line = assemble_line(proc, inner, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words, bbox_size,
@@ -314,7 +353,7 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     # mean of the characters' confidences as the TextChar objects hold them (NaN -> 0, schema.py), reference :899-903
     confidence = float(np.mean(np.where(np.isnan(chars[1]), 0.0, chars[1])))
     box = PolygonBox(polygon=polygon)
-    chars = chars_of(chars, res_scale, box.bbox)
+    chars = chars_of(chars, res_scale, box.bbox, line_quad(flat, orig))
     if alts is not None and csrc[0] is not None:
         attach_alternatives(chars, csrc[0], alts, flat.get("top_k") or 1, AltDecoder(proc))
     chars = fix_unbalanced_tags(chars, proc.ocr_tokenizer.special_tokens)
@@ -330,6 +369,9 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
+    if flat.get("quads") is not None and not flat.get("_quads_set"):
+        out = assemble_batch(proc, {**flat, "_quads_set": True}, items, drop_repeated_text, return_words, bbox_size)
+        return [set_rectified(flat, it[1], line) for it, line in zip(items, out)]
     if flat.get("boost_tables") is not None:
         inner, its = boost_items(flat, items)
         out = assemble_batch(proc, inner, its, drop_repeated_text, return_words, bbox_size)
@@ -384,7 +426,7 @@ def _assemble_batch_forced(proc, flat, items, forced_of, drop_repeated_text, ret
     P = prediction_to_polygon_batch(R, [flat["slices"][items[i][0]].shape for i, _ in work], bbox_size,
                                     bbox_size // 2).astype(np.float64)                       # [W, t_max, 4, 2]
     far = (np.abs(P[:, 1:] - P[:, :-1]).reshape(W, t_max - 1, 8).max(axis=2) > 0.1).tolist() if t_max > 1 else [[]] * W
-    keep, all_w, all_src, all_conf, all_valid, counts, geo = [], [], [], [], [], [], []
+    keep, all_w, all_src, all_conf, all_valid, counts, geo, quad_of = [], [], [], [], [], [], [], []
     for w, (i, n) in enumerate(work):
         sp, orig, tokens, sc, rows = items[i][:5]
         texts, src, csrc, valid = line_runs(proc, tokens[:n], far[w])
@@ -396,6 +438,7 @@ def _assemble_batch_forced(proc, flat, items, forced_of, drop_repeated_text, ret
         bbox = [min(xs), min(ys), max(xs), max(ys)]
         rs = flat["res_scales"][orig]
         keep.append((i, texts, valid, polygon, bbox, csrc))
+        quad_of.append(line_quad(flat, orig))
         all_w.extend([w] * len(src)); all_src.extend(src); all_valid.extend(valid)
         all_conf.extend([0.0 if sc[j] != sc[j] else sc[j] for j in csrc])          # TextChar's NaN -> 0 rule
         counts.append(len(src))
@@ -406,8 +449,15 @@ def _assemble_batch_forced(proc, flat, items, forced_of, drop_repeated_text, ret
     v_all = np.asarray(all_valid, bool)
     PP[~v_all] = _BLANK_POLY
     g = np.repeat(np.asarray(geo, np.float64), counts, axis=0)[:, :, None]                    # [C, 6, 1]
+    if any(q is not None for q in quad_of):                   # rectified lines: their corners in crop coordinates, mapped below
+        crop = PP.copy()
     PP[..., 0] = np.minimum(np.maximum(np.trunc(PP[..., 0] * g[:, 0]) + g[:, 2], g[:, 2]), g[:, 4])
     PP[..., 1] = np.minimum(np.maximum(np.trunc(PP[..., 1] * g[:, 1]) + g[:, 3], g[:, 3]), g[:, 5])
+    a = 0
+    for (i, *_), c, q in zip(keep, counts, quad_of):
+        if q is not None:
+            PP[a:a + c] = quad_to_page(crop[a:a + c], q, flat["res_scales"][items[i][1]])
+        a += c
     polys = PP.tolist()
     conf_arr = np.asarray(all_conf, np.float64)
     special = proc.ocr_tokenizer.special_tokens

@@ -26,13 +26,13 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ..common.imageops import fill_poly_mask
+from ..common.imageops import fill_poly_mask, quad_homography, quad_size, rectify_threshold, should_rectify, warp_quad
 from ..common.predictor import BasePredictor, gc_paused
 from ..settings import settings
 from . import assemble
 from .loader import RecognitionModelLoader, rec_config_from_reference_json  # noqa: F401  (re-exported)
 from .loop import FEED_END, DeviceLoop
-from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref
+from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref, quad_ref
 from .postprocess import sort_text_lines
 from .schema import OCRResult, TaskNames, TextLine
 
@@ -76,9 +76,32 @@ def slice_polys_from_image(image: np.ndarray, polys) -> List[np.ndarray]:
     return [slice_and_pad_poly(image, p) for p in polys]
 
 
+def slice_polys(polys, threshold, page=None, pg: int = -1, arr=None):
+    """The slices of one page's polygons (in the pixels of the image they are cut from) and, with rectification on (`threshold` not
+    None), per polygon the quad it is warped from or None -- the ONE place where should_rectify is asked, for every call path. Device
+    path (`page`: the page's uint8 pixels, registered as page `pg`): LineRefs; host path (`arr`: the image processor's array of the
+    same page): arrays, a rectified one being warp_quad's pixels as float32."""
+    quads = None if threshold is None else [tuple((float(c[0]), float(c[1])) for c in pl) if should_rectify(pl, threshold) else None
+                                            for pl in polys]
+    slices = []
+    for i, pl in enumerate(polys):
+        q = None if quads is None else quads[i]
+        if arr is None:
+            h, w = page.shape[:2]
+            slices.append(quad_ref(pg, w, h, pl) if q is not None else poly_ref(pg, w, h, pl))
+        elif q is not None:
+            w, h = quad_size(q)
+            slices.append(warp_quad(page, quad_homography(q, w, h), w, h)[..., :3].astype(np.float32))
+        else:
+            slices.append(slice_and_pad_poly(arr, pl))
+    return slices, quads
+
+
 def new_flat() -> dict:
     """The lines of one call, flattened over its pages. By line id (sorted / admission order): slices, task_names, input_text;
-    by ORIGINAL position (page order): polygons, res_scales; slice_map holds the line count per page. The device path adds "pages"."""
+    by ORIGINAL position (page order): polygons, res_scales; slice_map holds the line count per page. The device path adds "pages";
+    a call with `rectify` set adds "quads", by original position: the quad a line was warped from (in the pixels its slice came
+    from), None for a line that took the ordinary path."""
     return {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
 
 
@@ -397,13 +420,20 @@ class RecognitionPredictor(BasePredictor):
     def detect_and_slice_bboxes(self, images, task_names, det_predictor, detection_batch_size=None, highres_images=None):
         det_predictions = det_predictor(images, batch_size=detection_batch_size)
         flat = new_flat()
+        thr = rectify_threshold(self.rectify)
+        if thr is not None:
+            flat["quads"] = []
         for det_pred, image, highres, task in zip(det_predictions, images, highres_images, task_names):
             polygons, src, polys_px, scale = page_lines(det_pred, image, highres)
             if self.device_preprocess:
                 pg = self._page(flat, src)
-                slices = [poly_ref(pg, src.size[0], src.size[1], poly) for poly in polys_px]
-            else:
+                slices, quads = slice_polys(polys_px, thr, flat["pages"][pg], pg)
+            elif thr is None:
                 slices = slice_polys_from_image(self.processor.image_processor(src), polys_px)
+            else:
+                slices, quads = slice_polys(polys_px, thr, page_pixels(src), arr=self.processor.image_processor(src))
+            if thr is not None:
+                flat["quads"].extend(quads)
             flat["slice_map"].append(len(slices))
             flat["slices"].extend(slices)
             flat["polygons"].extend(polygons)
@@ -418,17 +448,26 @@ class RecognitionPredictor(BasePredictor):
         # ONE decision for the whole call (prepare_lines dispatches on the type of the first slice): the device path takes 4-point
         # polygons only, so a single polygon with another vertex count anywhere sends every image of the call down the host path
         dev = self.device_preprocess and (polygons is None or all(len(pl) == 4 for page in polygons for pl in page))
+        thr = rectify_threshold(self.rectify)
+        if thr is not None:
+            flat["quads"] = []
         for idx, image in enumerate(images):
             arr = None if dev else self.processor.image_processor(image)
             pg = self._page(flat, image) if dev else -1
             if polygons is not None:
                 polys = polygons[idx]
-                slices = ([poly_ref(pg, image.size[0], image.size[1], pl) for pl in polys] if dev
-                          else slice_polys_from_image(arr, polys))
+                if thr is None:
+                    slices = ([poly_ref(pg, image.size[0], image.size[1], pl) for pl in polys] if dev
+                              else slice_polys_from_image(arr, polys))
+                else:
+                    slices, quads = slice_polys(polys, thr, flat["pages"][pg], pg) if dev else slice_polys(polys, thr, page_pixels(image), arr=arr)
+                    flat["quads"].extend(quads)
             else:
                 slices = ([bbox_ref(pg, image.size[0], image.size[1], b) for b in bboxes[idx]] if dev
                           else slice_bboxes_from_image(arr, bboxes[idx]))
                 polys = [[[b[0], b[1]], [b[2], b[1]], [b[2], b[3]], [b[0], b[3]]] for b in bboxes[idx]]
+                if thr is not None:                           # `bboxes=` lines are never rectified
+                    flat["quads"].extend([None] * len(slices))
             flat["slice_map"].append(len(slices))
             flat["slices"].extend(slices)
             flat["polygons"].extend(polys)
@@ -701,6 +740,16 @@ class RecognitionPredictor(BasePredictor):
         that are not boosted. Other lines of the call may carry allowlists; a boosted line takes none. ValueError, before any device
         work, with `top_k`, `beam_width`, `pattern` or `lexicon`, without `boost_weight`, and in `align`.
 
+        `self.rectify` (an attribute like `top_k`; None = off, True = every tilted line, or a non-negative threshold in degrees): a line
+        that came with a 4-point polygon (`polygons=` or `det_predictor=`, never `bboxes=`) which is strictly convex and clockwise, is not
+        an axis-aligned rectangle in canonical order and whose top edge p0 -> p1 is tilted by at least the threshold is warped to an
+        upright crop (common/imageops.py: warp_quad) instead of being cut as its bounding rectangle; every other line takes today's path
+        with today's bits. The vertex order is the reading direction: a caller who knows a line is vertical or upside down says so with
+        the order of its vertices; nothing is guessed. Characters of a warped line are tilted quads on the page, `TextLine.polygon` stays
+        the polygon that came in, `TextLine.rectified` says whether the line was warped (None while `rectify` is None). It works with every
+        decoding option, dtype and KV mode, and in `align`: nothing behind the image tiles changes. ValueError, before any device work,
+        for any other value.
+
         `self.beam_width` (an attribute like `top_k`; None = greedy, else 2..4): beam search on the device. Every TextLine carries
         `hypotheses`, its up to beam_width best readings as LineHypothesis(text, confidence, log_prob, finished, chars) -- finished
         readings by log_prob descending, then the ones the token budget or the repeat rule cut -- each assembled like a line
@@ -716,6 +765,7 @@ class RecognitionPredictor(BasePredictor):
         if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= 4):
             raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
         beam = self._check_beam_width(top_k)
+        rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
         pattern = self.pattern
         if pattern is not None and beam is not None:
             raise ValueError("pattern is not available with beam_width: a beam would have to inherit its parent's automaton state")
@@ -779,6 +829,7 @@ class RecognitionPredictor(BasePredictor):
         a count mismatch, a line longer than its task's token budget or than SA_MAX_FORCED_TOKENS, or an id outside the model's
         vocabulary. Not with `shard_lines` or a process group: multi-rank alignment is not supported. Allow-lists and `top_k`
         do not apply to an aligned call, and a set `pattern` raises ValueError: the text is given, there is nothing to constrain."""
+        rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
         if self.pattern is not None:
             raise ValueError("pattern does not apply to align(): forced decoding reads no allowed set (set pattern = None)")
         if self.lexicon is not None:
@@ -854,6 +905,7 @@ class RecognitionPredictor(BasePredictor):
     lexicon = None                    # word list per call / image / line (see __call__), None = off: pred.lexicon = ["Alabama", "Alaska", ...]
     boost_words = None                # word list per call / image / line to PREFER (see __call__), None = off: pred.boost_words = ["Paracetamol", ...]
     boost_weight = None               # ... and the boost in logit units, a finite float >= 0: required with boost_words, no default
+    rectify = None                    # warp tilted 4-point polygons upright (see __call__): None = off, True, or a threshold in degrees: pred.rectify = 2.0
     last_boost = None
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
@@ -1096,6 +1148,9 @@ class RecognitionPredictor(BasePredictor):
         with_boost = cons is not None and cons.boost is not None
         if with_boost:
             flat.update(boost_tables=cons.boost, boost_weight=cons.boost_weight, boost_roots=[])
+        thr = rectify_threshold(self.rectify)
+        if thr is not None:
+            flat["quads"] = []
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
@@ -1111,11 +1166,16 @@ class RecognitionPredictor(BasePredictor):
                     if stop.is_set():
                         break
                     pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all, lex_all = [], [], [], [], [], [], [], []
-                    roots_all = []
+                    roots_all, quads_all = [], []
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
-                        refs.extend(poly_ref(len(pages) - 1, src.size[0], src.size[1], poly) for poly in polys_px)
+                        if thr is None:
+                            refs.extend(poly_ref(len(pages) - 1, src.size[0], src.size[1], poly) for poly in polys_px)
+                        else:
+                            page_refs, quads = slice_polys(polys_px, thr, pages[-1], len(pages) - 1)
+                            refs.extend(page_refs)
+                            quads_all.extend(quads)
                         polys_all.extend(polygons)
                         scales_all.extend([scale] * len(polygons))
                         tasks_all.extend([task_names[page]] * len(polygons))
@@ -1140,6 +1200,8 @@ class RecognitionPredictor(BasePredictor):
                     # everything the assembly thread reads about these lines is in place BEFORE the chunk can be admitted
                     flat["polygons"].extend(polys_all)
                     flat["res_scales"].extend(scales_all)
+                    if thr is not None:
+                        flat["quads"].extend(quads_all)
                     flat["slices"].extend(refs[i] for i in order)
                     flat["task_names"].extend(tasks_all[i] for i in order)
                     flat["input_text"].extend([None] * len(order))

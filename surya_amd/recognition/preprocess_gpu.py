@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..common.imageops import page_pixels, parallel_copy  # noqa: F401  (page_pixels is re-exported: the predictor and tests import it from here)
+from ..common.imageops import page_pixels, parallel_copy, quad_homographies, quad_size  # noqa: F401  (page_pixels is re-exported: the predictor and tests import it from here)
 
 # must match sa::prep::LineDesc (csrc/rec_prep.h); align=True reproduces the C layout (8-byte longs after the int block)
 LINE_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("x0", np.int32), ("y0", np.int32),
@@ -23,6 +23,10 @@ LINE_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", n
                       ("mid_h", np.int32), ("out_w", np.int32), ("out_h", np.int32), ("mask_off", np.int64), ("mid_off", np.int64),
                       ("tile_row", np.int64)], align=True)
 assert LINE_DESC.itemsize == 112, LINE_DESC.itemsize
+# must match sa::prep::RectifyDesc (csrc/rec_rectify.h): one per rectified line, a HOST array (surya_rec_rectify copies it into kernel arguments)
+RECTIFY_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("out_w", np.int32), ("out_h", np.int32),
+                         ("out_off", np.int64), ("h", np.float64, (9,))], align=True)
+assert RECTIFY_DESC.itemsize == 104, RECTIFY_DESC.itemsize
 
 
 @dataclass
@@ -36,9 +40,15 @@ class LineRef:
     x1: int
     y1: int
     poly: Optional[Tuple[Tuple[int, int], ...]] = None      # absolute page coordinates, 4 vertices
+    # a line that is RECTIFIED (RecognitionPredictor.rectify): four (x, y) floats in page coordinates, clockwise, p0 -> p1 the top edge in
+    # reading direction. Its pixels are warp_quad's (common/imageops.py) of the quad, its shape quad_size's; `poly` is then not read.
+    quad: Optional[Tuple[Tuple[float, float], ...]] = None
 
     @property
     def shape(self):
+        if self.quad is not None:
+            w, h = quad_size(self.quad)
+            return (h, w, 3)
         return (max(self.y1 - self.y0, 0), max(self.x1 - self.x0, 0), 3)
 
     @property
@@ -64,6 +74,13 @@ def poly_ref(page: int, page_w: int, page_h: int, coords) -> LineRef:
     x0, y0 = min(p[0] for p in pts), min(p[1] for p in pts)
     x1, y1 = max(p[0] for p in pts), max(p[1] for p in pts)
     return LineRef(page, max(x0, 0), max(y0, 0), min(x1, page_w), min(y1, page_h), pts)
+
+
+def quad_ref(page: int, page_w: int, page_h: int, coords) -> LineRef:
+    """poly_ref of a line that is rectified: the same reference with the quad the pixels are warped from."""
+    ln = poly_ref(page, page_w, page_h, coords)
+    ln.quad = tuple((float(c[0]), float(c[1])) for c in coords)
+    return ln
 
 
 def fit_sizes(h: int, w: int, max_size, min_size=(168, 168), factor: int = 28):
@@ -92,7 +109,9 @@ class DevicePreprocessor:
 
     def __call__(self, pages: Sequence[np.ndarray], lines: Sequence[LineRef], max_sizes: Sequence[Tuple[int, int]]):
         """pages: uint8 [H, W, 3] (RGB) or [H, W, 4] (RGBX) arrays; lines: LineRefs into them; max_sizes: the task's img_size per line.
-        Returns (tiles cuda fp32 [sum P, 3 ps^2], tile_offs int64 [n + 1], grids [(gh, gw)])."""
+        Returns (tiles cuda fp32 [sum P, 3 ps^2], tile_offs int64 [n + 1], grids [(gh, gw)]).
+        Lines with a `quad` are rectified first (surya_rec_rectify, once per call): their upright crops are written into an arena behind the
+        pages and each then is an ordinary line whose page is its crop. A call without a quad allocates and launches what it always did."""
         n = len(lines)
         f = self.ps * self.merge
         offs, total = [], 0
@@ -103,19 +122,32 @@ class DevicePreprocessor:
             assert pg.dtype == np.uint8 and pg.ndim == 3 and pg.shape[2] == pix
             offs.append(total)
             total += pg.size
+        # rectified lines: their upright crops are written behind the pages, each at a 4-byte-aligned offset, as pages of their own
+        n_rect = sum(1 for ln in lines if ln.quad is not None)
+        rdesc = np.zeros(n_rect, RECTIFY_DESC)
+        arena, r, max_rw, max_rh = (total + 3) & ~3, 0, 0, 0
         desc = np.zeros(n, LINE_DESC)
         tile_offs = np.zeros(n + 1, np.int64)
         grids, mask_bytes, mid_floats, max_mid_w = [], 0, 0, 0
         for i, (ln, mx) in enumerate(zip(lines, max_sizes)):
             ph, pw = pages[ln.page].shape[:2]
             h, w = ln.y1 - ln.y0, ln.x1 - ln.x0
+            if ln.quad is not None:
+                w, h = quad_size(ln.quad)
             if h <= 0 or w <= 0:
                 raise ValueError("empty line crop on the device pre-processing path (caller substitutes a blank page)")
             (mh, mw), (oh, ow) = fit_sizes(h, w, mx, factor=f)
             d = desc[i]
-            d["page_off"], d["page_w"], d["page_h"] = offs[ln.page], pw, ph
-            d["x0"], d["y0"], d["cw"], d["ch"] = ln.x0, ln.y0, w, h
-            if ln.poly is not None and len(ln.poly) >= 3:
+            if ln.quad is not None:                    # the line's page is its rectified crop
+                rd = rdesc[r]
+                rd["page_off"], rd["page_w"], rd["page_h"], rd["out_w"], rd["out_h"], rd["out_off"] = offs[ln.page], pw, ph, w, h, arena
+                d["page_off"], d["page_w"], d["page_h"], d["cw"], d["ch"] = arena, w, h, w, h
+                arena += (w * h * pix + 3) & ~3
+                r, max_rw, max_rh = r + 1, max(max_rw, w), max(max_rh, h)
+            else:
+                d["page_off"], d["page_w"], d["page_h"] = offs[ln.page], pw, ph
+                d["x0"], d["y0"], d["cw"], d["ch"] = ln.x0, ln.y0, w, h
+            if ln.quad is None and ln.poly is not None and len(ln.poly) >= 3:
                 if len(ln.poly) != 4:
                     raise ValueError("device pre-processing handles 4-point polygons")
                 d["has_poly"] = 1
@@ -131,18 +163,27 @@ class DevicePreprocessor:
             gh, gw = oh // self.ps, ow // self.ps
             grids.append((gh, gw))
             tile_offs[i + 1] = tile_offs[i] + gh * gw
+        if n_rect:                                     # all homographies of the call in one stacked solve
+            rdesc["h"] = quad_homographies([ln.quad for ln in lines if ln.quad is not None], rdesc["out_w"], rdesc["out_h"])
         torch.cuda.set_device(self.device)
         # pinned staging straight from torch's caching host allocator (a pageable buffer + .pin_memory() would allocate, fault in and
         # copy the pages' ~3 MB each a second time)
         host = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         parallel_copy([hv[o: o + pg.size].reshape(pg.shape) for pg, o in zip(pages, offs)], list(pages))   # 3-8 MB each: side by side
-        d_pages = host.to(self.device, non_blocking=True)
+        if n_rect:
+            d_pages = torch.empty(arena, dtype=torch.uint8, device=self.device)
+            d_pages[:host.numel()].copy_(host, non_blocking=True)
+        else:
+            d_pages = host.to(self.device, non_blocking=True)
         d_desc = torch.from_numpy(desc.view(np.uint8).reshape(-1)).to(self.device)
         d_mask = torch.empty(max(mask_bytes, 1), dtype=torch.uint8, device=self.device)
         d_mid = torch.empty(max(mid_floats, 1), dtype=torch.float32, device=self.device)
         tiles = torch.empty((int(tile_offs[-1]), 3 * self.ps * self.ps), dtype=torch.float32, device=self.device)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        if n_rect:
+            L.check(self.lib.surya_rec_rectify(L.ptr(d_pages), rdesc.ctypes.data_as(C.c_void_p), C.c_int(n_rect), L.ptr(d_pages), C.c_int(pix),
+                                               C.c_int(max_rw), C.c_int(max_rh), stream), "surya_rec_rectify")
         L.check(self.lib.surya_rec_preprocess(L.ptr(d_pages), L.ptr(d_desc), C.c_int(n), L.ptr(d_mask), L.ptr(d_mid), L.ptr(tiles),
                                               C.c_int(self.ps), C.c_int(self.merge), C.c_float(self.pad), self.mean, self.std,
                                               C.c_int(int(mask_bytes > 0)), C.c_int(max_mid_w), C.c_int(pix), stream),

@@ -116,18 +116,22 @@ class TextLine(BaseChar):
     # then a proper prefix of an entry, or empty). None, and left out likewise, for a line without a lexicon.
     # `boost_matches` (RecognitionPredictor.boost_words): the indices, in the line's own list, of the entries some live match completed
     # while the line was read, in order of completion, each once; [] if none. None, and left out likewise, for a line that was not boosted.
+    # `rectified` (RecognitionPredictor.rectify): whether the line's pixels were warped upright from its quadrilateral; its characters'
+    # polygons are then tilted quads on the page. None, and left out likewise, while `rectify` is None.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
         hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
         pattern_matched: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
         lexicon_index: Optional[int] = Field(default=None, exclude_if=lambda v: v is None)
         boost_matches: Optional[List[int]] = Field(default=None, exclude_if=lambda v: v is None)
+        rectified: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
         hypotheses: Optional[List[LineHypothesis]] = None
         pattern_matched: Optional[bool] = None
         lexicon_index: Optional[int] = None
         boost_matches: Optional[List[int]] = None
+        rectified: Optional[bool] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
@@ -142,6 +146,8 @@ class TextLine(BaseChar):
                 d.pop("lexicon_index", None)
             if self.boost_matches is None:
                 d.pop("boost_matches", None)
+            if self.rectified is None:
+                d.pop("rectified", None)
             return d
 
 
