@@ -122,6 +122,24 @@ int surya_rec_plan_encoder(const surya_rec_config* cfg, const int32_t* grid_hw, 
 int surya_rec_prefill(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids,
                       const int32_t* seq_offsets, const int32_t* slot_ids, int n_seqs, void* stream);
 
+/* surya_rec_prefill with one prompt shared by several slots: sequence i is encoded and prefilled ONCE, into its lead slot
+ * fan_slots[fan_offsets[i]], and afterwards occupies every slot of fan_slots[fan_offsets[i] .. fan_offsets[i + 1]) -- any slots, in any
+ * order, at least one per sequence. Every fan slot gets the sequence's length, a head row of its own (so with forced decoding on, its own
+ * forced column, cursor and step outputs; with forcing off the fan slots run identical greedy streams) and, behind the decoder layers,
+ * a copy of the lead's prompt rows of every layer, kv head, K and V (csrc/kv_fanout.h). Outputs(step 0) hold token / score / bbox for
+ * every fan slot. The other arguments, tiles == NULL included, are surya_rec_prefill's, and the lead slots take that call's code path.
+ *   fan_offsets  host [n_seqs+1], fan_offsets[0] == 0, strictly increasing
+ *   fan_slots    host [fan_offsets[n_seqs]], distinct, < max_slots, at most max_slots in all
+ * Checked before anything is enqueued or changed: SA_ERR_ARG for offsets that do not start at 0 or do not increase (an empty fan), a slot
+ * out of range or named twice, more than max_slots fan slots; SA_ERR_STATE while beam search (which owns whole groups and forks on its
+ * own) or the FP8 KV cache is on. Enqueue only. */
+int surya_rec_prefill_shared(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids,
+                             const int32_t* seq_offsets, const int32_t* fan_offsets, const int32_t* fan_slots, int n_seqs, void* stream);
+/* Test hook, like surya_rec_copy_last_logits: rows [0, rows) of every layer's and kv head's run of `slot` in the KV cache, to the device
+ * buffers k_out / v_out [dec_layers][dec_kv_heads][rows][dec_head_dim] of the handle's dtype. SA_ERR_ARG for a slot out of range or rows
+ * outside 1..max_kv_len. Enqueue only. */
+int surya_rec_copy_kv_rows(surya_rec* h, int slot, int rows, void* k_out, void* v_out, void* stream);
+
 /* Look-ahead encoding (no counterpart in the reference, which encodes inside the prefill call, common/surya/__init__.py:
  * 130-195): run the vision encoder for the images of the NEXT prompts on the library's own low-priority stream (after
  * the work already queued on `stream`, which produced `tiles`), concurrently with decode steps on `stream`. The merged
@@ -611,6 +629,14 @@ int surya_op_rec_beam_select(const int32_t* lead_slots, int stride, int n_groups
                              int32_t* kv_len, int32_t* prompt_len, int32_t* fork_base, int32_t* fork_len, int max_kv_len, void* stream);
 int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* fork_src, const int32_t* base, const int32_t* len, int rows,
                          int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream);
+/* The prompt fan-out of surya_rec_prefill_shared alone (csrc/kv_fanout.h), through the launcher the engine uses; device pointers. Caches as
+ * for kv_fork. For every sequence n < n_seqs, rows [0, fan_len[n]) of every layer, kv head, K and V are copied from slot fan_src[n] to the
+ * slots fan_dst[fan_off[n] .. fan_off[n + 1]); fan_dst holds n_dst entries. fan_len is clamped to [0, max_kv_len]; a destination out of
+ * range or equal to its source is skipped. A source must not be a destination, nor a slot a destination twice, in one call. Shape rules
+ * and errors as for kv_fork. */
+int surya_op_rec_kv_fanout(int dtype, void* kcache, void* vcache, const int32_t* fan_src, const int32_t* fan_off, const int32_t* fan_dst,
+                           const int32_t* fan_len, int n_seqs, int n_dst, int layers, int slots, int kv_heads, int max_kv_len, int head_dim,
+                           void* stream);
 /* The two kernels of lexicon-guided decoding (csrc/lexicon.h) on caller-owned DEVICE buffers, through the launch code the engine uses. The
  * tables are read unchecked, as the engine's are after its validation. `table` is a whole mask table of rows of `words` uint32; slot s
  * owns row row_base + s. eos / pad / nop ids outside [0, vocab) have no bit.

@@ -155,6 +155,10 @@ def _bind_lay_ops(lib):
     lib.surya_op_rec_beam_select.argtypes = [p, i, i, i, i, p, p, p, p, i, i, i, i, p, p, p, p, p, p, p, p, p, p, p, i, p]
     lib.surya_op_rec_beam_select.restype = C.c_int
     lib.surya_op_rec_kv_fork.argtypes, lib.surya_op_rec_kv_fork.restype = [i, p, p, p, p, p, i, i, i, i, i, i, p], C.c_int
+    # one prefill shared by many slots (rank candidate texts) and its fan-out kernel by itself
+    lib.surya_rec_prefill_shared.argtypes, lib.surya_rec_prefill_shared.restype = [p, p, ip, i, ip, ip, ip, ip, i, p], C.c_int
+    lib.surya_rec_copy_kv_rows.argtypes, lib.surya_rec_copy_kv_rows.restype = [p, i, i, p, p, p], C.c_int
+    lib.surya_op_rec_kv_fanout.argtypes, lib.surya_op_rec_kv_fanout.restype = [i, p, p, p, p, p, p, i, i, i, i, i, i, i, p], C.c_int
     # pattern-guided decoding (a slot's mask id follows an automaton over its tokens; recognition/pattern.py compiles the tables)
     lib.surya_rec_set_patterns.argtypes = [p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), i, i, p]
     lib.surya_rec_set_patterns.restype = C.c_int

@@ -17,6 +17,7 @@
 #include "kernels.h"
 #include "decode_attn.h"
 #include "decode_attn_kv8.h"
+#include "kv_fanout.h"
 #include "attn_mfma.h"
 #include "beam.h"
 #include "automaton_core.h"
@@ -291,6 +292,7 @@ enum StepSet { STEPS_BASE = 0, STEPS_ALTS, STEPS_BEAM, STEPS_FORCED, STEPS_BOOST
 struct RecBase {
     virtual ~RecBase() {}
     virtual int prefill(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int prefill_shared(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_active(const int32_t*, int, hipStream_t) = 0;
     virtual int encode_ahead(const float*, const int32_t*, int, hipStream_t) = 0;
     virtual int decode(int, hipStream_t) = 0;
@@ -299,6 +301,7 @@ struct RecBase {
     virtual int wait_steps(StepSet, int n_steps, int ring, std::initializer_list<void*> dst) = 0;
     virtual int encode_only(const float*, const int32_t*, int, void*, hipStream_t) = 0;
     virtual int copy_last_logits(float*, int, int*, hipStream_t) = 0;
+    virtual int copy_kv_rows(int, int, void*, void*, hipStream_t) = 0;
     virtual int set_next_tokens(const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int set_mx_weights(const void* const*, int) = 0;
     virtual int set_kv_fp8(int) = 0;
@@ -1529,6 +1532,28 @@ struct RecModel : RecBase {
 
     int prefill(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
                 const int32_t* slot_ids, int n_seqs, hipStream_t s) override {
+        return prefill_fan(tiles, grid_hw, n_images, input_ids, seq_offsets, slot_ids, n_seqs, nullptr, nullptr, s);
+    }
+
+    // surya_rec_prefill_shared: sequence i is prefilled once, into its lead slot fan_slots[fan_offsets[i]], and then occupies every slot of
+    // fan_slots[fan_offsets[i] .. fan_offsets[i + 1]). Everything about the fans is checked here, before anything is enqueued or changed.
+    int prefill_shared(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
+                       const int32_t* fan_offsets, const int32_t* fan_slots, int n_seqs, hipStream_t s) override {
+        if (n_seqs <= 0) return SA_OK;
+        if (n_seqs > c.max_slots) return SA_ERR_ARG;
+        if (beam > 0 || kv8) return SA_ERR_STATE;           // beam search owns whole groups and forks on its own; the fan-out copies no fp8 rows
+        if (fan_offsets[0] != 0) return SA_ERR_ARG;
+        for (int i = 0; i < n_seqs; ++i)
+            if (fan_offsets[i + 1] <= fan_offsets[i] || fan_offsets[i + 1] > c.max_slots) return SA_ERR_ARG;      // at least the lead; max_slots in all
+        if (check_slots(fan_slots, fan_offsets[n_seqs], [](int) { return true; })) return SA_ERR_ARG;
+        std::vector<int32_t> leads(n_seqs);
+        for (int i = 0; i < n_seqs; ++i) leads[i] = fan_slots[fan_offsets[i]];
+        return prefill_fan(tiles, grid_hw, n_images, input_ids, seq_offsets, leads.data(), n_seqs, fan_offsets, fan_slots, s);
+    }
+
+    // The body of both prefills. fan_offsets == nullptr: surya_rec_prefill, one slot per sequence.
+    int prefill_fan(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
+                    const int32_t* slot_ids, int n_seqs, const int32_t* fan_offsets, const int32_t* fan_slots, hipStream_t s) {
         if (n_seqs <= 0) return SA_OK;
         if (n_seqs > c.max_slots) return SA_ERR_ARG;
         const int Ttot = seq_offsets[n_seqs];
@@ -1541,8 +1566,6 @@ struct RecModel : RecBase {
             if (L <= 0 || L >= c.max_kv_len || slot_ids[i] < 0 || slot_ids[i] >= c.max_slots) return SA_ERR_ARG;
             if (beam > 0 && (slot_ids[i] % beam || slot_ids[i] + beam > c.max_slots)) return SA_ERR_ARG;      // lead slots of whole groups only
             lens[i] = L; last_row[i] = a + L - 1;
-            if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
-            for (int b = 0; b < std::max(beam, 1); ++b) h_len[slot_ids[i] + b] = L;
             for (int t = 0; t < L; ++t) {
                 const int id = input_ids[a + t];
                 if (id < 0 || id >= c.vocab) return SA_ERR_ARG;
@@ -1561,6 +1584,21 @@ struct RecModel : RecBase {
         long ntok = 0;
         for (int i = 0; i < n_images; ++i) ntok += (long)grid_hw[2 * i] * grid_hw[2 * i + 1] / (c.merge * c.merge);
         if ((long)img_pos.size() != ntok) return SA_ERR_SHAPE;   // reference only warns (common/surya/__init__.py:216-221)
+        if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
+        // The fans as the launches below take them: per fan slot its length and the prompt's last row (slot state, head pass), and per
+        // sequence the slots behind the lead (kv_fanout_kernel).
+        std::vector<int> f_lens, f_last, f_off, f_dst;
+        for (int i = 0; i < n_seqs; ++i) {
+            for (int b = 0; b < std::max(beam, 1); ++b) h_len[slot_ids[i] + b] = lens[i];
+            if (!fan_offsets) continue;
+            f_off.push_back((int)f_dst.size());
+            for (int j = fan_offsets[i]; j < fan_offsets[i + 1]; ++j) {
+                h_len[fan_slots[j]] = lens[i];
+                f_lens.push_back(lens[i]); f_last.push_back(last_row[i]);
+                if (j > fan_offsets[i]) f_dst.push_back(fan_slots[j]);
+            }
+        }
+        if (fan_offsets) f_off.push_back((int)f_dst.size());
         int rc;
         // small plan first (its own stager: the encoder re-stages per chunk)
         st_small.begin();
@@ -1597,11 +1635,28 @@ struct RecModel : RecBase {
         const int* d_tok_pos = st.put(tok_pos);
         AttnSegs d_sg = stage_segs(st, sg);
         if (!d_sg.o_off) return SA_ERR_NOMEM;
+        if (!fan_offsets) {
+            if ((rc = st.flush(s))) return rc;
+            hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, s, d_slots, d_lens, kv_len, n_seqs);
+            if ((rc = decoder_layers_prefill(Ttot, d_tok_slot, d_tok_pos, &d_sg, (int)sg.tile_seg.size(), s))) return rc;
+            if ((rc = heads(n_seqs, d_last, d_slots, 0, 0, false, s)) || beam == 0) return rc;
+            return beam_step(d_slots, 1, n_seqs, 0, 1, s);   // the B best first tokens, and the prompt's rows to the group's other slots
+        }
+        // shared prefill: every fan slot gets the length and a head row of its own; the cache rows follow behind the layers
+        const int F = fan_offsets[n_seqs], n_dst = (int)f_dst.size();
+        const int* d_fslots = st.put(fan_slots, F);
+        const int* d_flens = st.put(f_lens);
+        const int* d_flast = st.put(f_last);
+        const int* d_foff = st.put(f_off);
+        if (f_dst.empty()) f_dst.push_back(-1);                 // (a call of single-slot fans: one entry nobody reads, n_dst stays 0)
+        const int* d_fdst = st.put(f_dst);
+        if (!d_fslots || !d_flens || !d_flast || !d_foff || !d_fdst) return SA_ERR_NOMEM;
         if ((rc = st.flush(s))) return rc;
-        hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, s, d_slots, d_lens, kv_len, n_seqs);
+        hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(F, 256)), dim3(256), 0, s, d_fslots, d_flens, kv_len, F);
         if ((rc = decoder_layers_prefill(Ttot, d_tok_slot, d_tok_pos, &d_sg, (int)sg.tile_seg.size(), s))) return rc;
-        if ((rc = heads(n_seqs, d_last, d_slots, 0, 0, false, s)) || beam == 0) return rc;
-        return beam_step(d_slots, 1, n_seqs, 0, 1, s);       // the B best first tokens, and the prompt's rows to the group's other slots
+        if ((rc = launch_kv_fanout<T>(kcache, vcache, d_slots, d_foff, d_fdst, d_lens, n_seqs, n_dst, c.dec_layers, c.max_slots, c.dec_kv_heads,
+                                      c.max_kv_len, c.dec_head_dim, s))) return rc;
+        return heads(F, d_flast, d_fslots, 0, 0, false, s);
     }
 
     int set_active(const int32_t* slots, int n, hipStream_t s) override {
@@ -1716,6 +1771,20 @@ struct RecModel : RecBase {
         SA_HIP(hipGraphLaunch(it->second, gstream));
         SA_HIP(hipEventRecord(gev_out, gstream));
         SA_HIP(hipStreamWaitEvent(s, gev_out, 0));
+        return SA_OK;
+    }
+
+    // Test hook: rows [0, rows) of every (layer, kv head) run of `slot`, K and V, to device buffers [layers][kv_heads][rows][head_dim] of the
+    // model's dtype.
+    int copy_kv_rows(int slot, int rows, void* kdst, void* vdst, hipStream_t s) override {
+        if (slot < 0 || slot >= c.max_slots || rows <= 0 || rows > c.max_kv_len || !kdst || !vdst) return SA_ERR_ARG;
+        const size_t run = (size_t)c.max_kv_len * c.dec_head_dim, bytes = (size_t)rows * c.dec_head_dim * sizeof(T);
+        for (int l = 0; l < c.dec_layers; ++l)
+            for (int h = 0; h < c.dec_kv_heads; ++h) {
+                const size_t src = (((size_t)l * c.max_slots + slot) * c.dec_kv_heads + h) * run, dst = ((size_t)l * c.dec_kv_heads + h) * bytes;
+                SA_HIP(hipMemcpyAsync((char*)kdst + dst, kcache + src, bytes, hipMemcpyDeviceToDevice, s));
+                SA_HIP(hipMemcpyAsync((char*)vdst + dst, vcache + src, bytes, hipMemcpyDeviceToDevice, s));
+            }
         return SA_OK;
     }
 

@@ -185,6 +185,15 @@ int surya_rec_prefill(surya_rec* h, const float* tiles, const int32_t* grid_hw, 
     if (!h || !input_ids || !seq_offsets || !slot_ids || (n_images > 0 && !grid_hw)) return SA_ERR_ARG;   // tiles == NULL: look-ahead mode
     return h->impl->prefill(tiles, grid_hw, n_images, input_ids, seq_offsets, slot_ids, n_seqs, (hipStream_t)stream);
 }
+int surya_rec_prefill_shared(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids,
+                             const int32_t* seq_offsets, const int32_t* fan_offsets, const int32_t* fan_slots, int n_seqs, void* stream) {
+    if (!h || !input_ids || !seq_offsets || !fan_offsets || !fan_slots || (n_images > 0 && !grid_hw)) return SA_ERR_ARG;
+    return h->impl->prefill_shared(tiles, grid_hw, n_images, input_ids, seq_offsets, fan_offsets, fan_slots, n_seqs, (hipStream_t)stream);
+}
+int surya_rec_copy_kv_rows(surya_rec* h, int slot, int rows, void* k_out, void* v_out, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->copy_kv_rows(slot, rows, k_out, v_out, (hipStream_t)stream);
+}
 int surya_rec_encode_ahead(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, void* stream) {
     if (!h || n_images < 0 || (n_images > 0 && (!tiles || !grid_hw))) return SA_ERR_ARG;      // n_images == 0: discard (see the header)
     return h->impl->encode_ahead(tiles, grid_hw, n_images, (hipStream_t)stream);
@@ -783,6 +792,12 @@ int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* f
                          int layers, int slots, int kv_heads, int max_kv_len, int head_dim, void* stream) {
     const sa::RecKvForkOp a{kcache, vcache, fork_src, base, len, rows, layers, slots, kv_heads, max_kv_len, head_dim};
     return rec_dispatch(dtype, sa::REC_OP_KV_FORK, &a, stream);
+}
+int surya_op_rec_kv_fanout(int dtype, void* kcache, void* vcache, const int32_t* fan_src, const int32_t* fan_off, const int32_t* fan_dst,
+                           const int32_t* fan_len, int n_seqs, int n_dst, int layers, int slots, int kv_heads, int max_kv_len, int head_dim,
+                           void* stream) {
+    const sa::RecKvFanoutOp a{kcache, vcache, fan_src, fan_off, fan_dst, fan_len, n_seqs, n_dst, layers, slots, kv_heads, max_kv_len, head_dim};
+    return rec_dispatch(dtype, sa::REC_OP_KV_FANOUT, &a, stream);
 }
 static int lexicon_op_args(const surya_rec_lexicon_args* g, sa::LexiconArgs& a) {
     if (!g || !g->edge_off || !g->edge_tok || !g->edge_next || !g->state_flags || !g->table || !g->slot_state || !g->slot_mask || g->words <= 0 ||

@@ -4,6 +4,7 @@
 #pragma once
 #include "kernels.h"
 #include "beam.h"
+#include "kv_fanout.h"
 #include "boost.h"
 
 namespace sa {
@@ -18,7 +19,9 @@ struct RecEmbedOp {
     int rows, H; float eps; uint8_t *y8, *sy; int srows;
 };
 struct RecKvForkOp { void *kc, *vc; const int *fork_src, *base, *len; int rows, layers, slots, nkv, Tmax, D; };
-enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK, REC_OP_BOOST_HEAD };
+struct RecKvFanoutOp { void *kc, *vc; const int *fan_src, *fan_off, *fan_dst, *fan_len; int n_seqs, n_dst, layers, slots, nkv, Tmax, D; };
+enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK, REC_OP_BOOST_HEAD,
+       REC_OP_KV_FANOUT };
 
 template <typename T> constexpr bool rec_mx_ok() { return std::is_same<T, bf16_t>::value; }     // the MXFP8 copies exist beside bf16 only
 
@@ -134,6 +137,11 @@ int rec_op(const RecKvForkOp& a, hipStream_t s) {
 }
 
 template <typename T>
+int rec_op(const RecKvFanoutOp& a, hipStream_t s) {
+    return launch_kv_fanout<T>((T*)a.kc, (T*)a.vc, a.fan_src, a.fan_off, a.fan_dst, a.fan_len, a.n_seqs, a.n_dst, a.layers, a.slots, a.nkv, a.Tmax, a.D, s);
+}
+
+template <typename T>
 int rec_op_any(int op, const void* a, hipStream_t s) {
     switch (op) {
         case REC_OP_RMS_ROWS: return rec_op<T>(*static_cast<const RecRmsRowsOp*>(a), s);
@@ -145,6 +153,7 @@ int rec_op_any(int op, const void* a, hipStream_t s) {
         case REC_OP_HEAD: return rec_op<T>(*static_cast<const surya_rec_head_args*>(a), s);
         case REC_OP_KV_FORK: return rec_op<T>(*static_cast<const RecKvForkOp*>(a), s);
         case REC_OP_BOOST_HEAD: return rec_op<T>(*static_cast<const surya_rec_boost_head_args*>(a), s);
+        case REC_OP_KV_FANOUT: return rec_op<T>(*static_cast<const RecKvFanoutOp*>(a), s);
     }
     return SA_ERR_ARG;
 }

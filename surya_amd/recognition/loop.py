@@ -77,6 +77,16 @@ class DeviceLoop:
     run and off on the way out, also after an exception. Not requested: the arrays do not exist and the model's four entry points
     (set_forced / set_forced_tokens / read_forced / wait_forced) are never called -- a model without them works.
 
+    Candidate fans (`fan=True`, with `forced=True` only): "forced_ids" holds per prompt a non-empty LIST of non-empty id lists, the
+    line's candidates. A line takes as many slots as it has candidates and is prefilled ONCE (the model's prefill_shared: the first of its
+    slots is the lead, the prompt's cache rows are copied to the others), each slot forced to one candidate. Lines are admitted from the
+    head of the queue while their candidates fit the empty slots and their prompt tokens, counted once per line, fit max_prefill; a line
+    that does not fit waits for slots to drain and nothing behind it overtakes it (the look-ahead encoder queue stays in order). From
+    the prefill on a line's candidates are independent: each has its own budget, its list's length, finishes on its own and frees its
+    slot on its own. The loop's per-line arrays then hold one row per CANDIDATE (row cand_base[line] + j), and predicted_tokens / scores
+    stay empty. `on_done(line, results)` fires when the line's last candidate finished: per candidate, in the order given, the tuple
+    (greedy ids, their probabilities, forced log-probabilities). Without `fan` prefill_shared is never called.
+
     Beam search (`beam=B`, 2..4; not together with alternatives or forced decoding): the model keeps the B best readings of a line in
     a group of B consecutive slots, so `slots // B` lines are in flight and everything above that says "slot" means a group. A line is
     prefilled once, into its group's lead slot g * B (its mask id goes to all B slots); the model selects, places and forks on the
@@ -89,7 +99,7 @@ class DeviceLoop:
     out, also after an exception. beam=None: set_beam / read_beam / wait_beam are never called -- a model without them works."""
 
     def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None,
-                 alternatives=False, forced=False, beam=None):
+                 alternatives=False, forced=False, beam=None, fan=False):
         self.beam = int(beam) if beam else 0
         if self.beam:
             assert 2 <= self.beam <= SA_MAX_BEAMS and slots >= self.beam, "beam width must be 2..4 and fit the slots"
@@ -120,7 +130,11 @@ class DeviceLoop:
         self.alt_p_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.float32) if self.alternatives else None
         self.forced = bool(forced)
         assert not (self.forced and self.alternatives), "forced decoding and alternatives exclude each other"
-        self.forced_ids = []                                   # per line: its forced id list (forced only)
+        self.forced_ids = []                                   # per line: its forced id list (forced only); with `fan` per candidate row
+        self.fan = bool(fan)
+        assert not self.fan or self.forced, "candidate fans need forced decoding"
+        self.cand_base, self.n_cand, self.cand_left = [], [], []      # fan, per line: its first row, its candidates, those still running
+        self.row_line = []                                     # fan, per candidate row: its line
         self.greedy_tok_mat = np.zeros((0, self.cap), np.int32) if self.forced else None
         self.greedy_p_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
         self.logp_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
@@ -165,7 +179,21 @@ class DeviceLoop:
             return
         assert [p.id for p in new] == list(range(base, base + m)), "fed prompts must continue the admitted ids"
         mt = np.asarray([d["max_tokens"][p.id] for p in new], np.int64)
-        if self.forced:
+        rows = m                                               # rows of the token matrices the lines take: one each, or one per candidate
+        if self.fan:
+            cands = [[[int(t) for t in ids] for ids in line] for line in d["forced_ids"]]
+            assert len(cands) == m, "forced_ids: one list of candidates per prompt"
+            assert all(0 < len(line) <= self.slots and all(line) for line in cands), \
+                "a line needs 1..slots candidates, each a non-empty id list"
+            assert all(len(ids) <= b for line, b in zip(cands, mt.tolist()) for ids in line), "a candidate exceeds its line's token budget"
+            fi = [ids for line in cands for ids in line]
+            rows = len(fi)
+            for k, line in enumerate(cands):
+                self.cand_base.append(len(self.row_line))
+                self.row_line.extend([base + k] * len(line))
+                self.n_cand.append(len(line)); self.cand_left.append(len(line))
+            mt = np.asarray([len(ids) for ids in fi], np.int64)
+        elif self.forced:
             fi = [[int(t) for t in ids] for ids in d["forced_ids"]]
             assert len(fi) == m, "forced_ids: one id list per prompt"
             mt = np.asarray([len(ids) or b for ids, b in zip(fi, mt.tolist())], np.int64)      # the budget is the list's length
@@ -176,18 +204,18 @@ class DeviceLoop:
         self.scores.extend([] for _ in range(m))
         self.chunk_tiles.append(d["tiles"]); self.chunk_offs.append(d["tile_offs"]); self.chunk_base.append(base)
         self.line_chunk = np.concatenate([self.line_chunk, np.full(m, len(self.chunk_base) - 1, np.int64)])
-        self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((m, self.overall_max_tokens, 6), np.float32)])
-        self.tok_mat = np.concatenate([self.tok_mat, np.zeros((m, self.cap), np.int64)])
-        self.sc_mat = np.concatenate([self.sc_mat, np.zeros((m, self.cap), np.float32)])
+        self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((rows, self.overall_max_tokens, 6), np.float32)])
+        self.tok_mat = np.concatenate([self.tok_mat, np.zeros((rows, self.cap), np.int64)])
+        self.sc_mat = np.concatenate([self.sc_mat, np.zeros((rows, self.cap), np.float32)])
         if self.alternatives:
             self.alt_tok_mat = np.concatenate([self.alt_tok_mat, np.full((m, self.cap, SA_MAX_ALTERNATIVES), -1, np.int32)])
             self.alt_p_mat = np.concatenate([self.alt_p_mat, np.zeros((m, self.cap, SA_MAX_ALTERNATIVES), np.float32)])
         if self.forced:
             self.forced_ids.extend(fi)
-            self.greedy_tok_mat = np.concatenate([self.greedy_tok_mat, np.zeros((m, self.cap), np.int32)])
-            self.greedy_p_mat = np.concatenate([self.greedy_p_mat, np.zeros((m, self.cap), np.float32)])
-            self.logp_mat = np.concatenate([self.logp_mat, np.zeros((m, self.cap), np.float32)])
-        self.line_len = np.concatenate([self.line_len, np.zeros(m, np.int64)])
+            self.greedy_tok_mat = np.concatenate([self.greedy_tok_mat, np.zeros((rows, self.cap), np.int32)])
+            self.greedy_p_mat = np.concatenate([self.greedy_p_mat, np.zeros((rows, self.cap), np.float32)])
+            self.logp_mat = np.concatenate([self.logp_mat, np.zeros((rows, self.cap), np.float32)])
+        self.line_len = np.concatenate([self.line_len, np.zeros(rows, np.int64)])
         self.max_tok = np.concatenate([self.max_tok, mt])
         mk = d.get("mask_ids")
         mk = np.full(m, -1, np.int64) if mk is None else np.asarray(mk, np.int64)
@@ -289,7 +317,21 @@ class DeviceLoop:
                 stop[ci] = True
         return stop
 
+    def _finish_fan(self, row):
+        """Candidate row `row` is final; its line is once all its candidates are."""
+        line = self.row_line[row]
+        self.cand_left[line] -= 1
+        if self.cand_left[line] or self.on_done is None:
+            return
+        res = []
+        for r in range(self.cand_base[line], self.cand_base[line] + self.n_cand[line]):
+            n = int(self.line_len[r])
+            res.append((self.greedy_tok_mat[r, :n].copy(), self.greedy_p_mat[r, :n].copy(), self.logp_mat[r, :n].copy()))
+        self.on_done(line, res)
+
     def _finish(self, p_idx):
+        if self.fan:
+            return self._finish_fan(p_idx)
         L_ = int(self.line_len[p_idx])
         self.predicted_tokens[p_idx] = self.tok_mat[p_idx, :L_].tolist()
         self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
@@ -409,18 +451,60 @@ class DeviceLoop:
         self.ahead.extend(cand)
 
     def _prefill(self, take, grids, prompt_ids, slots):
-        """The model's prefill of lines `take` into `slots`: from the look-ahead queue, whose head they are, or with their own tiles."""
+        """The model's prefill of lines `take` into `slots` (fan: one slot list per line, prefill_shared): from the look-ahead queue, whose
+        head they are, or with their own tiles."""
+        prefill = self.model.prefill_shared if self.fan else self.model.prefill
         if self.look_ahead:
             for i in take:
                 assert self.ahead.popleft() == i
-            self.model.prefill(None, grids, prompt_ids, slots)
+            prefill(None, grids, prompt_ids, slots)
             if not self.ahead and self.queue:
                 self.encode_ahead()                    # the next lines' encoder pass runs beside the decode steps that follow
         else:
-            self.model.prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, slots)      # queue order == id order
+            prefill(self.tiles_of(take[0], take[-1]), grids, prompt_ids, slots)      # queue order == id order
+
+    def _prefill_fan(self):
+        """prefill_batch with candidate fans: lines from the head of the queue while their candidates fit the empty slots (ascending) and
+        their prompts, once each, max_prefill. The caller made sure that the head line fits."""
+        queue, ahead, look_ahead, line_chunk = self.queue, self.ahead, self.look_ahead, self.line_chunk
+        empty = np.flatnonzero(self.slot_line < 0).tolist()
+        if look_ahead and not ahead:
+            self.encode_ahead()
+        take, fans, ntok, used = [], [], 0, 0
+        while queue and (not look_ahead or len(take) < len(ahead)):
+            i = queue[0]
+            L_, k = len(self.prompt_ids[i]), self.n_cand[i]
+            if used + k > len(empty) or (take and (ntok + L_ > self.max_prefill or line_chunk[i] != line_chunk[take[0]])):
+                break
+            take.append(queue.popleft())
+            fans.append(empty[used: used + k])
+            ntok += L_
+            used += k
+        assert take, "the head line's candidates must fit the empty slots"
+        rows = np.asarray([self.cand_base[i] + j for i in take for j in range(self.n_cand[i])], np.int64)
+        sl_ = np.asarray([s for f in fans for s in f], np.int64)
+        self.model.set_forced_tokens(sl_.tolist(), [self.forced_ids[r] for r in rows.tolist()])
+        self._prefill(take, [self.grids[i] for i in take], [self.prompt_ids[i] for i in take], fans)
+        tok, sc, bb = self.model.read_outputs(1)
+        first = tok[0, sl_]
+        fo = tuple(a[0, sl_] for a in self.model.read_forced(1))
+        self._put(rows, np.zeros(len(rows), np.int64), first, sc[0, sl_], bb[0, sl_], fo=fo)
+        go_on = (first != self.eos) & (first != self.nop) & (self.max_tok[rows] > 1)
+        for r, s, go in zip(rows.tolist(), sl_.tolist(), go_on.tolist()):
+            if go:
+                self.slot_line[s] = r                               # (in fan mode THE slot table names candidate rows)
+            else:
+                self._finish(r)
+        self._flush_active()
+
+    def _fits(self) -> bool:
+        """Whether the head of the queue can be prefilled now: always without fans (one empty slot does), else all its candidates fit."""
+        return not self.fan or self.n_cand[self.queue[0]] <= self.num_empty
 
     def prefill_batch(self):
         """Fill the empty slots (ascending) from the head of the queue; a line whose first token already stops never takes its slot."""
+        if self.fan:
+            return self._prefill_fan()
         queue, ahead, look_ahead, line_chunk = self.queue, self.ahead, self.look_ahead, self.line_chunk
         empty = np.flatnonzero(self.slot_line < 0).tolist()
         if look_ahead and not ahead:
@@ -547,7 +631,7 @@ class DeviceLoop:
                 if self.feed_done:
                     break
                 continue
-            if self.queue and (self.num_empty / self.slots) > self.min_prefill_ratio:
+            if self.queue and (self.num_empty / self.slots) > self.min_prefill_ratio and self._fits():
                 if self.inflight:
                     self.absorb(self.inflight)
                     self.inflight = None

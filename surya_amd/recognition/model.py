@@ -400,6 +400,28 @@ class HipRecModel:
                                            L.np_ptr(offs), L.np_ptr(slots), C.c_int(len(slots)), self._stream),
                 "surya_rec_prefill")
 
+    def prefill_shared(self, tiles: torch.Tensor, grid_hw, input_ids: Sequence[Sequence[int]], fan_slots: Sequence[Sequence[int]]):
+        """`prefill` with one prompt shared by several slots (surya_rec_prefill_shared): fan_slots[i] holds the slots of sequence i, any
+        distinct ones, at least one. The sequence is encoded and prefilled once, into fan_slots[i][0]; every slot of the list then holds
+        its prompt rows, its length and a first token of its own (with forced decoding on: its own forced id). Not with beam search or
+        the fp8 KV cache."""
+        torch.cuda.set_device(self.device)
+        grid = np.ascontiguousarray(np.asarray(grid_hw, np.int32).reshape(-1, 2))
+        if len(fan_slots) != len(input_ids):
+            raise ValueError("prefill_shared: one slot list per sequence")
+        offs = np.zeros(len(input_ids) + 1, np.int32)
+        offs[1:] = np.cumsum([len(s) for s in input_ids])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32) for s in input_ids]))
+        foffs = np.zeros(len(fan_slots) + 1, np.int32)
+        foffs[1:] = np.cumsum([len(f) for f in fan_slots])
+        slots = np.ascontiguousarray([s for f in fan_slots for s in f], np.int32) if foffs[-1] else np.zeros(1, np.int32)
+        if tiles is not None:
+            assert tiles.is_cuda and tiles.dtype == torch.float32 and tiles.is_contiguous()
+            assert tiles.shape[0] == int((grid[:, 0] * grid[:, 1]).sum()) and tiles.shape[1] == self.cfg.encoder.patch_dim
+        L.check(self.lib.surya_rec_prefill_shared(self.handle, L.ptr(tiles), L.np_ptr(grid), C.c_int(len(grid)), L.np_ptr(flat), L.np_ptr(offs),
+                                                  L.np_ptr(foffs), L.np_ptr(slots), C.c_int(len(fan_slots)), self._stream),
+                "surya_rec_prefill_shared")
+
     def encode_ahead(self, tiles: torch.Tensor, grid_hw):
         """Encode the images of the next prompts on the library's low-priority stream (overlaps with decode steps); the
         following prefill(None, ...) calls consume the embeddings in this order."""
@@ -446,6 +468,16 @@ class HipRecModel:
         L.check(self.lib.surya_rec_encode_only(self.handle, L.ptr(tiles), L.np_ptr(grid), C.c_int(len(grid)), L.ptr(out),
                                                self._stream), "surya_rec_encode_only")
         return out
+
+    def kv_rows(self, slot: int, rows: int):
+        """Sync; (K, V) [layers, kv_heads, rows, head_dim] of the first `rows` cache rows of `slot`, in the model's dtype. A test hook, like
+        last_logits."""
+        d = self.cfg.decoder
+        shape = (d.num_hidden_layers, d.num_key_value_heads, rows, d.head_dim)
+        k, v = torch.empty(shape, dtype=self.dtype, device=self.device), torch.empty(shape, dtype=self.dtype, device=self.device)
+        L.check(self.lib.surya_rec_copy_kv_rows(self.handle, C.c_int(slot), C.c_int(rows), L.ptr(k), L.ptr(v), self._stream), "surya_rec_copy_kv_rows")
+        torch.cuda.synchronize(self.device)
+        return k, v
 
     def last_logits(self) -> torch.Tensor:
         """fp32 logits of the last prefill / decode step, recomputed; with token masks set these are still the UNMASKED logits."""

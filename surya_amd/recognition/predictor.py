@@ -34,7 +34,7 @@ from .loader import RecognitionModelLoader, rec_config_from_reference_json  # no
 from .loop import FEED_END, DeviceLoop
 from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref, quad_ref
 from .postprocess import sort_text_lines
-from .schema import OCRResult, TaskNames, TextLine
+from .schema import LineRanking, OCRResult, RankedCandidate, RankResult, TaskNames, TextLine
 
 
 # ------------------------------------------------------------------------------------------------ input slicing
@@ -561,6 +561,8 @@ class RecognitionPredictor(BasePredictor):
             prep.update(boost_tables=flat["boost_tables"], boost_weight=flat["boost_weight"], boost_roots=flat["boost_roots"])
         if flat.get("forced_ids") is not None:                # align(): one forced id list per line
             prep["forced_ids"] = flat["forced_ids"]
+            if flat.get("fan"):                               # rank(): a LIST of id lists per line, one slot each behind one prefill
+                prep["fan"] = True
         return prep
 
     def generate(self, prep: dict | None, recognition_batch_size: int | None = None, on_done=None, on_flush=None, feed=None) -> tuple:
@@ -573,7 +575,7 @@ class RecognitionPredictor(BasePredictor):
         proc = self.processor
         more = {"alternatives": True} if self._top_k is not None else {}      # (only then: a stand-in loop keeps its signature)
         if first.get("forced_ids") is not None:
-            more = {"forced": True}
+            more = {"forced": True, "fan": True} if first.get("fan") else {"forced": True}      # rank(): a list of candidates per line
         elif self._beam is not None:
             more = {"beam": self._beam}
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
@@ -816,6 +818,46 @@ class RecognitionPredictor(BasePredictor):
         """The ids `align` forces for one line: the tokenizer's ids of the text for the line's task, then eos."""
         return [int(t) for t in self.processor.ocr_tokenizer(text, task)["input_ids"][0]] + [int(self.processor.eos_token_id)]
 
+    def _forced_call_checks(self, what, arg, arg_lists, images, per_line, task_names, bboxes, polygons):
+        """What `align` and `rank` refuse before any device work; -> (the bbox / polygon lists, the task names)."""
+        rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
+        if self.pattern is not None:
+            raise ValueError(f"pattern does not apply to {what}(): forced decoding reads no allowed set (set pattern = None)")
+        if self.lexicon is not None:
+            raise ValueError(f"lexicon does not apply to {what}(): forced decoding reads no allowed set (set lexicon = None)")
+        if self.boost_words is not None:
+            raise ValueError(f"boost_words do not apply to {what}(): the text is given, there is nothing to prefer (set boost_words = None)")
+        if getattr(self, "_poisoned", None):
+            raise RuntimeError(self._poisoned)
+        if self.shard_lines or self.shard_pages or self.process_group is not None:
+            raise NotImplementedError(f"{what}() runs on one rank: unset shard_lines / shard_pages / process_group")
+        given = polygons if polygons is not None else bboxes
+        if given is None:
+            raise ValueError(f"{what}() needs bboxes or polygons: the lines the {arg} belong to")
+        if task_names is None:
+            task_names = [TaskNames.ocr_with_boxes] * len(images)
+        if not (len(images) == len(per_line) == len(given) == len(task_names)):
+            raise ValueError(f"{what}(): {len(images)} images, {len(per_line)} {arg_lists}, {len(given)} bbox / polygon lists, {len(task_names)} task names")
+        for t in task_names:
+            if t not in self.tasks:
+                raise ValueError(f"task {t!r} is not supported. Supported tasks are {list(self.tasks)}")
+        return given, task_names
+
+    def _forced_line_ids(self, where, text, task) -> List[int]:
+        """`forced_ids` of one text of a line of `task`, checked against the budget, SA_MAX_FORCED_TOKENS and the vocabulary."""
+        from .. import _lib as L
+        if not isinstance(text, str):
+            raise ValueError(f"{where}: the text must be a str, got {type(text).__name__}")
+        ids = self.forced_ids(text, task)
+        budget, vocab = self.line_budget(task), getattr(self.model, "vocab", None)
+        if len(ids) > budget:
+            raise ValueError(f"{where}: {len(ids)} tokens (eos included) exceed the token budget {budget} of task {task}")
+        if len(ids) > L.SA_MAX_FORCED_TOKENS:
+            raise ValueError(f"{where}: {len(ids)} tokens exceed SA_MAX_FORCED_TOKENS = {L.SA_MAX_FORCED_TOKENS}")
+        if vocab is not None and max(ids) >= vocab:
+            raise ValueError(f"{where}: token id {max(ids)} is outside the model's vocabulary of {vocab}")
+        return ids
+
     def align(self, images: List[Image.Image], texts: List[List[str]], task_names: List[str] | None = None,
               bboxes: List[List[List[int]]] | None = None, polygons: List[List[List[List[int]]]] | None = None,
               recognition_batch_size: int | None = None, math_mode: bool = True, return_words: bool = False) -> List[OCRResult]:
@@ -829,45 +871,13 @@ class RecognitionPredictor(BasePredictor):
         a count mismatch, a line longer than its task's token budget or than SA_MAX_FORCED_TOKENS, or an id outside the model's
         vocabulary. Not with `shard_lines` or a process group: multi-rank alignment is not supported. Allow-lists and `top_k`
         do not apply to an aligned call, and a set `pattern` raises ValueError: the text is given, there is nothing to constrain."""
-        rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
-        if self.pattern is not None:
-            raise ValueError("pattern does not apply to align(): forced decoding reads no allowed set (set pattern = None)")
-        if self.lexicon is not None:
-            raise ValueError("lexicon does not apply to align(): forced decoding reads no allowed set (set lexicon = None)")
-        if self.boost_words is not None:
-            raise ValueError("boost_words do not apply to align(): the text is given, there is nothing to prefer (set boost_words = None)")
-        if getattr(self, "_poisoned", None):
-            raise RuntimeError(self._poisoned)
-        if self.shard_lines or self.shard_pages or self.process_group is not None:
-            raise NotImplementedError("align() runs on one rank: unset shard_lines / shard_pages / process_group")
-        from .. import _lib as L
-        given = polygons if polygons is not None else bboxes
-        if given is None:
-            raise ValueError("align() needs bboxes or polygons: the lines the texts belong to")
-        if task_names is None:
-            task_names = [TaskNames.ocr_with_boxes] * len(images)
-        if not (len(images) == len(texts) == len(given) == len(task_names)):
-            raise ValueError(f"align(): {len(images)} images, {len(texts)} text lists, {len(given)} bbox / polygon lists, {len(task_names)} task names")
-        for t in task_names:
-            if t not in self.tasks:
-                raise ValueError(f"task {t!r} is not supported. Supported tasks are {list(self.tasks)}")
-        vocab = getattr(self.model, "vocab", None)
+        given, task_names = self._forced_call_checks("align", "texts", "text lists", images, texts, task_names, bboxes, polygons)
         forced = []
         for i, (tx, gv, task) in enumerate(zip(texts, given, task_names)):
             if len(tx) != len(gv):
                 raise ValueError(f"image {i} has {len(gv)} lines but {len(tx)} texts")
-            budget = self.line_budget(task)
             for j, text in enumerate(tx):
-                if not isinstance(text, str):
-                    raise ValueError(f"image {i}, line {j}: the text must be a str, got {type(text).__name__}")
-                ids = self.forced_ids(text, task)
-                if len(ids) > budget:
-                    raise ValueError(f"image {i}, line {j}: {len(ids)} tokens (eos included) exceed the token budget {budget} of task {task}")
-                if len(ids) > L.SA_MAX_FORCED_TOKENS:
-                    raise ValueError(f"image {i}, line {j}: {len(ids)} tokens exceed SA_MAX_FORCED_TOKENS = {L.SA_MAX_FORCED_TOKENS}")
-                if vocab is not None and max(ids) >= vocab:
-                    raise ValueError(f"image {i}, line {j}: token id {max(ids)} is outside the model's vocabulary of {vocab}")
-                forced.append(ids)
+                forced.append(self._forced_line_ids(f"image {i}, line {j}", text, task))
         saved_k, self._top_k = self._top_k, None              # (an aligned call reports `greedy`, not alternatives)
         saved_b, self._beam = self._beam, None                # (and one reading, the given one, whatever beam_width says)
         try:
@@ -894,6 +904,86 @@ class RecognitionPredictor(BasePredictor):
             stamps["prepare_ms"] = (t1 - t0) * 1e3
             text_lines = hand.finish(stamps, t1)
         results = self._page_results(images, flat["slice_map"], text_lines, False)
+        stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
+        return results
+
+    def rank(self, images: List[Image.Image], candidates: List[List[List[str]]], task_names: List[str] | None = None,
+             bboxes: List[List[List[int]]] | None = None, polygons: List[List[List[List[int]]]] | None = None,
+             recognition_batch_size: int | None = None, math_mode: bool = True) -> List[RankResult]:
+        """Rank candidate texts: candidates[i][j] is the non-empty list of texts the caller holds for image i's j-th bbox / polygon (one
+        of the two is required). Every line is encoded and prefilled ONCE and takes one KV slot per distinct candidate, each forced to
+        its candidate's `forced_ids` as in `align`; equal id lists within a line are scored once and reported at every index that named
+        them. The result holds, per line, RankedCandidate(index, text, log_prob, n_tokens, probability, greedy_match) sorted by
+        log_prob descending, then index ascending, and `best`, the caller's index of the first: log_prob is `align`'s
+        TextLine.log_prob for the same line and text, probability its softmax over the line's distinct candidates. No characters,
+        polygons or words are assembled. ValueError, naming image and line, as in `align`, and for an empty candidate list or a line
+        with more distinct candidates than the slots in use (min(recognition_batch_size, the model's slots): one line is not split over
+        several prefills); a set `pattern` / `lexicon` / `boost_words` raises ValueError too. Not with `shard_lines` or a process group.
+        `rectify` applies; `top_k` and `beam_width` do not."""
+        given, task_names = self._forced_call_checks("rank", "candidates", "candidate lists", images, candidates, task_names, bboxes, polygons)
+        slots = recognition_batch_size if recognition_batch_size is not None else self.get_batch_size()
+        slots = min(slots, self.model.max_slots)
+        lines = []                                            # per line: (its texts, its distinct id lists, text index -> distinct index)
+        for i, (cs, gv, task) in enumerate(zip(candidates, given, task_names)):
+            if len(cs) != len(gv):
+                raise ValueError(f"image {i} has {len(gv)} lines but {len(cs)} candidate lists")
+            for j, texts in enumerate(cs):
+                if isinstance(texts, str) or len(texts) == 0:
+                    raise ValueError(f"image {i}, line {j}: the candidates must be a non-empty list of str")
+                distinct, where, index = [], {}, []
+                for k, text in enumerate(texts):
+                    ids = self._forced_line_ids(f"image {i}, line {j}, candidate {k}", text, task)
+                    if tuple(ids) not in where:
+                        where[tuple(ids)] = len(distinct)
+                        distinct.append(ids)
+                    index.append(where[tuple(ids)])
+                if len(distinct) > slots:
+                    raise ValueError(f"image {i}, line {j}: {len(distinct)} distinct candidates exceed the {slots} slots in use "
+                                     f"(recognition_batch_size / the model's slots)")
+                lines.append((list(texts), distinct, index))
+        saved_k, self._top_k = self._top_k, None              # (parked for the call, as in align)
+        saved_b, self._beam = self._beam, None
+        try:
+            with gc_paused():
+                return self._rank(convert_if_not_rgb(images), lines, task_names, bboxes, polygons, recognition_batch_size, math_mode)
+        finally:
+            self._top_k, self._beam = saved_k, saved_b
+
+    def _rank(self, images, lines, task_names, bboxes, polygons, recognition_batch_size, math_mode) -> List[RankResult]:
+        t_call = time.perf_counter()
+        stamps = self.last_timing = {}
+        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
+        n = len(flat["slices"])
+        assert n == len(lines)
+        scored = {}                                           # sorted position -> per distinct candidate (greedy ids, probabilities, log-probabilities)
+        if n:
+            flat["forced_ids"], flat["fan"] = [ln[1] for ln in lines], True      # by line id like the slices: sorted with them below
+            order = sorted(range(n), key=lambda i: -flat["slices"][i].shape[1])
+            for key in ("slices", "input_text", "task_names", "forced_ids"):
+                flat[key] = [flat[key][i] for i in order]
+            t0 = time.perf_counter()
+            prep = self.prepare_lines(flat, math_mode)
+            t1 = time.perf_counter()
+            self.generate(prep, recognition_batch_size, on_done=scored.__setitem__)
+            stamps.update(prepare_ms=(t1 - t0) * 1e3, device_loop_ms=(time.perf_counter() - t1) * 1e3)
+            assert len(scored) == n
+        rankings = [None] * n
+        for k in range(n):
+            o = order[k]
+            texts, distinct, index = lines[o]
+            lp = np.asarray([np.sum(np.asarray(r[2], np.float64)) for r in scored[k]], np.float64)     # set_log_prob's sum
+            e = np.exp(lp - lp.max())
+            prob = e / e.sum()
+            match = [len(r[0]) == len(ids) and bool(np.array_equal(np.asarray(r[0], np.int64), np.asarray(ids, np.int64)))
+                     for r, ids in zip(scored[k], distinct)]
+            cands = [RankedCandidate(index=c, text=texts[c], log_prob=float(lp[d]), n_tokens=len(distinct[d]), probability=float(prob[d]),
+                                     greedy_match=match[d]) for c, d in enumerate(index)]
+            cands.sort(key=lambda r: (-r.log_prob, r.index))
+            rankings[o] = LineRanking(polygon=flat["polygons"][o], candidates=cands, best=cands[0].index)
+        results, start = [], 0
+        for image, count in zip(images, flat["slice_map"]):
+            results.append(RankResult(lines=rankings[start:start + count], image_bbox=[0, 0, image.size[0], image.size[1]]))
+            start += count
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results
 

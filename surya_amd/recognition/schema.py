@@ -151,6 +151,31 @@ class TextLine(BaseChar):
             return d
 
 
+class RankedCandidate(BaseModel):
+    """One candidate text of a line out of RecognitionPredictor.rank: `index` is its position in the caller's list, `log_prob` the float64
+    sum of log p(token | image, preceding tokens) over its `n_tokens` tokens, eos included (TextLine.log_prob's definition: comparable
+    with `align` and with beam hypotheses), `probability` the softmax of log_prob over the line's DISTINCT candidates, and `greedy_match`
+    whether the model's own reading under the candidate's prefix equals the candidate at every token."""
+    index: int
+    text: str
+    log_prob: float
+    n_tokens: int
+    probability: float
+    greedy_match: bool
+
+
+class LineRanking(PolygonBox):
+    """A line's candidates by log_prob descending, then index ascending; `best` is the caller's index of the first. polygon / bbox as a
+    TextLine has them; no characters or words are assembled."""
+    candidates: List[RankedCandidate]
+    best: int
+
+
+class RankResult(BaseModel):
+    lines: List[LineRanking]
+    image_bbox: List[float]
+
+
 class OCRResult(BaseModel):
     text_lines: List[TextLine]
     image_bbox: List[float]
