@@ -8,6 +8,7 @@ from contextlib import ExitStack
 import numpy as np
 
 from ..settings import settings
+from . import options
 from .postprocess import detect_repeat_token
 
 FEED_END = object()          # what a `generate(feed=...)` callable returns once no further lines will come
@@ -32,50 +33,38 @@ class DeviceLoop:
     Scheduling decisions never change a line's stream (slot / batch-composition invariance), so the result per line is the
     one the closed list gives.
 
-    Constrained output: the dict handed to `run` may carry "token_masks" (uint32 [n, words], the call's distinct allowed-id sets,
-    uploaded once before the first prefill) and every admitted dict "mask_ids" (one row id per prompt, -1 = unconstrained). A line's
-    id stays with the line: it is set on whatever slot the line is prefilled into, so a slot that is reused takes its new line's id.
-    Without "token_masks" the model's mask entry points are never called.
+    Per-line options (recognition/options.py: LINE_OPTIONS -- masks, patterns, lexicon, boost -- with every key and model method named
+    below): the dict handed to `run` may carry an option's table under its `table_key` (uploaded once with `set_table`, in table order,
+    before the first prefill) and every admitted dict one integer per prompt under its `line_key`, naming a row / state of the table,
+    -1 = off for the line (the key may be absent or None: all -1). A line's integer stays with the line: `set_slot` puts it on whatever
+    slot the line is prefilled into, in table order, so a reused slot takes its new line's values; from then on the model moves the
+    slot's state itself, token by token, on the device. Options are switched off in reverse order on the way out, also after an
+    exception. An option whose table is absent (or empty) is off: it keeps no array, its model entry points are never called -- a model
+    without them works -- and an integer other than -1 under its key fails `admit`. What the options differ in:
+      masks     the table is uint32 [n, words], the call's distinct allowed-id sets; every other option's table sits behind it.
+      patterns  PatternTables, whose states' allowed sets are rows of the mask table. Not with beam search or forced decoding.
+      lexicon   LexiconTables; needs a mask table of at least one row; the model rewrites the slot's own mask row. A line follows a
+                pattern or a lexicon, not both. Not with beam search or forced decoding.
+      boost     BoostTables, whose word_row names the mask row of the word-unit set, with the call's beta ("boost_weight"), handed to
+                `set_slot` behind the roots. Switches the boost output set on (below). Not with alternatives, beam search, forced
+                decoding, patterns or lexicons.
 
-    Patterns: the dict handed to `run` may also carry "pattern_tables" (recognition/pattern.py::PatternTables, whose states' allowed
-    sets are rows of "token_masks"; uploaded once, behind the mask table) and every admitted dict "start_states" (one automaton state
-    per prompt, -1 = no pattern). A line's start state is set, beside its mask id, on whatever slot the line is prefilled into; from
-    then on the model moves the slot's state and mask id itself, token by token, on the device. Patterns are switched off on the way
-    out, before the mask table, also after an exception. Without "pattern_tables" set_patterns / set_slot_patterns are never called
-    -- a model without them works. Not with beam search or forced decoding.
-
-    Lexicons: the dict handed to `run` may also carry "lexicon_tables" (recognition/lexicon.py::LexiconTables; uploaded once, behind the
-    mask table, which must have at least one row) and every admitted dict "lexicon_starts" (one automaton state per prompt, -1 = no
-    lexicon). A line's start state is set on whatever slot the line is prefilled into, behind its mask id (and its pattern state: a
-    line follows at most one of the two); from then on the model rewrites the slot's own mask row itself, token by token, on the
-    device. The lexicon is switched off on the way out, before patterns and the mask table, also after an exception. Without
-    "lexicon_tables" set_lexicon / set_slot_lexicon are never called -- a model without them works. Not with beam search or forced
-    decoding.
-
-    Boosted decoding: the dict handed to `run` may also carry "boost_tables" (recognition/boost.py::BoostTables, whose word_row names
-    the row of "token_masks" that holds the word-unit set; uploaded once, behind the mask table) with "boost_weight" (beta, one per call)
-    and every admitted dict "boost_roots" (one root state per prompt, -1 = not boosted). A line's root and beta are set on whatever slot
-    the line is prefilled into, behind its mask id; from then on the model moves the slot's state and preferred set itself. The model
-    reports per step the token it would have emitted without the boost and the emitted token's probability without it; the loop keeps
-    them per line (plain_tok_mat / plain_p_mat [lines, cap]) and hands a finished line's rows to `on_done` as two more arguments.
-    Boosting is switched off on the way out, before the mask table, also after an exception. Without "boost_tables" set_boost /
-    set_slot_boost / read_boost / wait_boost are never called -- a model without them works. Not with alternatives, beam search,
-    forced decoding, patterns or lexicons.
-
-    Alternatives (`alternatives=True`): the model reports the SA_MAX_ALTERNATIVES most likely tokens of every step; the loop keeps
-    them per line beside tokens and scores (alt_tok_mat / alt_p_mat [lines, cap, 4], id -1 = no such entry) and hands a finished
-    line's rows to `on_done` as two more arguments. The feature is switched on for the run and off on the way out, also after an
-    exception. Not requested: the arrays do not exist, on_done keeps its four arguments and the model's three entry points
-    (set_alternatives / read_alternatives / wait_alternatives) are never called -- a model without them works.
+    Extra per-step outputs (options.py: EXTRA_SETS; at most one per loop): the model reports more per step than token, score and box;
+    the loop keeps it per line in the set's matrices [lines, cap, *tail] -- readable as attributes of the loop, None while their set is
+    off -- and hands a finished line's rows to `on_done` as further arguments. A set that is off has no arrays, and the model's `read` /
+    `wait` calls for it are never made.
+      alternatives  (`alternatives=True`) alt_tok_mat / alt_p_mat [lines, cap, 4]: the SA_MAX_ALTERNATIVES most likely tokens of every
+                    step, id -1 = no such entry. set_alternatives switches the mode on for the run and off on the way out.
+      forced        (`forced=True`) greedy_tok_mat / greedy_p_mat / logp_mat [lines, cap]: the model's own argmax, that argmax's
+                    probability and the emitted token's log-probability. set_forced switches the mode likewise.
+      boost         (with the boost option) plain_tok_mat / plain_p_mat [lines, cap]: the token the model would have emitted without
+                    the boost and the emitted token's probability without it.
 
     Forced decoding (`forced=True`, not together with alternatives or token masks): every admitted dict carries "forced_ids", one id
-    list per prompt; the loop sets a line's list on whatever slot the line is prefilled into (beside set_slot_masks), the line's token
-    budget is the length of its list (an empty list: the line free-runs on the budget it came with), and the repeat rule is skipped --
-    a ground-truth line of forty dashes must not stop early. The model emits the forced ids and reports beside them its own argmax,
-    that argmax's probability and the emitted token's log-probability; the loop keeps them per line (greedy_tok_mat / greedy_p_mat /
-    logp_mat [lines, cap]) and hands a finished line's rows to `on_done` as three more arguments. The feature is switched on for the
-    run and off on the way out, also after an exception. Not requested: the arrays do not exist and the model's four entry points
-    (set_forced / set_forced_tokens / read_forced / wait_forced) are never called -- a model without them works.
+    list per prompt; the loop sets a line's list on whatever slot the line is prefilled into (set_forced_tokens, behind the options'
+    slot setters), the line's token budget is the length of its list (an empty list: the line free-runs on the budget it came with),
+    and the repeat rule is skipped -- a ground-truth line of forty dashes must not stop early. The model emits the forced ids. Not
+    requested: set_forced / set_forced_tokens are never called -- a model without them works.
 
     Candidate fans (`fan=True`, with `forced=True` only): "forced_ids" holds per prompt a non-empty LIST of non-empty id lists, the
     line's candidates. A line takes as many slots as it has candidates and is prefilled ONCE (the model's prefill_shared: the first of its
@@ -125,19 +114,16 @@ class DeviceLoop:
         self.sc_mat = np.zeros((0, self.cap), np.float32)
         self.line_len, self.max_tok = np.zeros(0, np.int64), np.zeros(0, np.int64)      # tokens so far / token budget per line
         self.slot_line = np.full(slots, -1, np.int64)
-        self.alternatives = bool(alternatives)
-        self.alt_tok_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.int32) if self.alternatives else None
-        self.alt_p_mat = np.zeros((0, self.cap, SA_MAX_ALTERNATIVES), np.float32) if self.alternatives else None
-        self.forced = bool(forced)
+        self.alternatives, self.forced = bool(alternatives), bool(forced)
         assert not (self.forced and self.alternatives), "forced decoding and alternatives exclude each other"
+        self.extra, self.extra_mats = None, ()                 # the one extra output set of this run (options.EXTRA_SETS) and its matrices
+        if self.alternatives or self.forced:
+            self._use_extra(options.ALTERNATIVES if self.alternatives else options.FORCED)
         self.forced_ids = []                                   # per line: its forced id list (forced only); with `fan` per candidate row
         self.fan = bool(fan)
         assert not self.fan or self.forced, "candidate fans need forced decoding"
         self.cand_base, self.n_cand, self.cand_left = [], [], []      # fan, per line: its first row, its candidates, those still running
         self.row_line = []                                     # fan, per candidate row: its line
-        self.greedy_tok_mat = np.zeros((0, self.cap), np.int32) if self.forced else None
-        self.greedy_p_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
-        self.logp_mat = np.zeros((0, self.cap), np.float32) if self.forced else None
         if self.beam:
             # per group: the beams' token / probability / box histories [groups, beam, cap(, 6)], re-indexed by `parents` every step; their
             # lengths, cumulative scores, finished flags and whether the slot holds a beam at all
@@ -146,15 +132,9 @@ class DeviceLoop:
             self.b_box = np.zeros((slots, B, cap, 6), np.float32)
             self.b_len, self.b_score = np.zeros((slots, B), np.int64), np.full((slots, B), -np.inf, np.float32)
             self.b_fin, self.b_alive = np.ones((slots, B), bool), np.zeros((slots, B), bool)
-        self.line_mask = np.zeros(0, np.int64)                 # id -> row of the call's token-mask table, -1 = unconstrained
-        self.n_masks = 0                                       # rows of the table uploaded for this loop (0: masks are off)
-        self.line_state = np.zeros(0, np.int64)                # id -> start state of the line's pattern, -1 = none
-        self.n_states = 0                                      # states of the automaton uploaded for this loop (0: patterns are off)
-        self.line_lex = np.zeros(0, np.int64)                  # id -> start state of the line's lexicon, -1 = none
-        self.n_lex_states = 0                                  # states of the lexicon automaton uploaded for this loop (0: off)
-        self.line_root = np.zeros(0, np.int64)                 # id -> root state of the line's boost list, -1 = not boosted
-        self.n_boost_states, self.boost_beta = 0, 0.0          # states of the boost automaton uploaded for this loop (0: off), the call's beta
-        self.plain_tok_mat = self.plain_p_mat = None           # [lines, cap] while boosting is on
+        # the per-line options that are ON in this loop (options.LINE_OPTIONS, in table order; `run` fills it): option -> [rows / states
+        # of its uploaded table, id -> the line's integer (-1 = off for the line), the call values its slot setter takes]
+        self.line_opts = {}
         # Look-ahead encoding (RECOGNITION_ENCODE_AHEAD, default on): the vision encoder of the next up-to-batch-size queued
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
@@ -170,6 +150,17 @@ class DeviceLoop:
     @property
     def num_empty(self) -> int:
         return self.slots - self.num_active
+
+    def _use_extra(self, xs):
+        assert self.extra is None and not self.grids, "one extra output set per loop, chosen before the first line"
+        self.extra, self.extra_mats = xs, options.empty_rows(xs, 0, (self.cap,))
+
+    def __getattr__(self, name):
+        # (reached for names the instance does not have:) alt_tok_mat ... plain_p_mat, the matrix while its set is on, else None
+        xs, i = options.EXTRA_ATTRS.get(name) or (None, 0)
+        if xs is None:
+            raise AttributeError(name)
+        return self.extra_mats[i] if self.__dict__.get("extra") is xs else None
 
     def admit(self, d):
         """Append the lines of one prepare_lines dict (ids continue the admitted ones)."""
@@ -207,39 +198,20 @@ class DeviceLoop:
         self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((rows, self.overall_max_tokens, 6), np.float32)])
         self.tok_mat = np.concatenate([self.tok_mat, np.zeros((rows, self.cap), np.int64)])
         self.sc_mat = np.concatenate([self.sc_mat, np.zeros((rows, self.cap), np.float32)])
-        if self.alternatives:
-            self.alt_tok_mat = np.concatenate([self.alt_tok_mat, np.full((m, self.cap, SA_MAX_ALTERNATIVES), -1, np.int32)])
-            self.alt_p_mat = np.concatenate([self.alt_p_mat, np.zeros((m, self.cap, SA_MAX_ALTERNATIVES), np.float32)])
+        if self.extra is not None:                             # (rows == m but for fans, which are forced)
+            self.extra_mats = tuple(np.concatenate(pair) for pair in zip(self.extra_mats, options.empty_rows(self.extra, rows, (self.cap,))))
         if self.forced:
             self.forced_ids.extend(fi)
-            self.greedy_tok_mat = np.concatenate([self.greedy_tok_mat, np.zeros((rows, self.cap), np.int32)])
-            self.greedy_p_mat = np.concatenate([self.greedy_p_mat, np.zeros((rows, self.cap), np.float32)])
-            self.logp_mat = np.concatenate([self.logp_mat, np.zeros((rows, self.cap), np.float32)])
         self.line_len = np.concatenate([self.line_len, np.zeros(rows, np.int64)])
         self.max_tok = np.concatenate([self.max_tok, mt])
-        mk = d.get("mask_ids")
-        mk = np.full(m, -1, np.int64) if mk is None else np.asarray(mk, np.int64)
-        assert mk.shape == (m,) and int(mk.min()) >= -1 and int(mk.max()) < self.n_masks, \
-            "mask ids must name rows of the call's token-mask table"
-        self.line_mask = np.concatenate([self.line_mask, mk])
-        st = d.get("start_states")
-        st = np.full(m, -1, np.int64) if st is None else np.asarray(st, np.int64)
-        assert st.shape == (m,) and int(st.min()) >= -1 and int(st.max()) < self.n_states, \
-            "start states must name states of the call's pattern tables"
-        self.line_state = np.concatenate([self.line_state, st])
-        lx = d.get("lexicon_starts")
-        lx = np.full(m, -1, np.int64) if lx is None else np.asarray(lx, np.int64)
-        assert lx.shape == (m,) and int(lx.min()) >= -1 and int(lx.max()) < self.n_lex_states, \
-            "lexicon start states must name states of the call's lexicon tables"
-        self.line_lex = np.concatenate([self.line_lex, lx])
-        br = d.get("boost_roots")
-        br = np.full(m, -1, np.int64) if br is None else np.asarray(br, np.int64)
-        assert br.shape == (m,) and int(br.min()) >= -1 and int(br.max()) < self.n_boost_states, \
-            "boost roots must name states of the call's boost tables"
-        self.line_root = np.concatenate([self.line_root, br])
-        if self.n_boost_states:
-            self.plain_tok_mat = np.concatenate([self.plain_tok_mat, np.zeros((m, self.cap), np.int32)])
-            self.plain_p_mat = np.concatenate([self.plain_p_mat, np.zeros((m, self.cap), np.float32)])
+        for o in options.LINE_OPTIONS:
+            vals, on = d.get(o.line_key), self.line_opts.get(o)
+            if vals is None and on is None:
+                continue                                       # off and not named: nothing to check, nothing to keep
+            vals = np.full(m, -1, np.int64) if vals is None else np.asarray(vals, np.int64)
+            assert vals.shape == (m,) and int(vals.min()) >= -1 and int(vals.max()) < (on[0] if on else 0), o.admit_msg
+            if on:
+                on[1] = np.concatenate([on[1], vals])
         self.queue.extend(range(base, base + m))
 
     def tiles_of(self, first_id, last_id):
@@ -326,7 +298,7 @@ class DeviceLoop:
         res = []
         for r in range(self.cand_base[line], self.cand_base[line] + self.n_cand[line]):
             n = int(self.line_len[r])
-            res.append((self.greedy_tok_mat[r, :n].copy(), self.greedy_p_mat[r, :n].copy(), self.logp_mat[r, :n].copy()))
+            res.append(tuple(a[r, :n].copy() for a in self.extra_mats))
         self.on_done(line, res)
 
     def _finish(self, p_idx):
@@ -336,33 +308,26 @@ class DeviceLoop:
         self.predicted_tokens[p_idx] = self.tok_mat[p_idx, :L_].tolist()
         self.scores[p_idx] = self.sc_mat[p_idx, :L_].tolist()
         if self.on_done is not None:
-            more = (self.alt_tok_mat[p_idx, :L_].copy(), self.alt_p_mat[p_idx, :L_].copy()) if self.alternatives else ()
-            if self.n_boost_states:
-                more = (self.plain_tok_mat[p_idx, :L_].copy(), self.plain_p_mat[p_idx, :L_].copy())
-            if self.forced:
-                more = (self.greedy_tok_mat[p_idx, :L_].copy(), self.greedy_p_mat[p_idx, :L_].copy(), self.logp_mat[p_idx, :L_].copy())
             self.on_done(p_idx, self.predicted_tokens[p_idx], self.scores[p_idx],
-                         self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)], *more)
+                         self.batch_bboxes[p_idx, :max(min(L_, self.overall_max_tokens), 1)], *(a[p_idx, :L_].copy() for a in self.extra_mats))
 
-    def _put(self, p, pos, t, s_, b_, at=None, ap=None, fo=None, bo=None):
-        """Token t / score s_ / box b_ (/ alternatives at, ap / forced outputs fo = (greedy token, its probability, log-probability) /
-        boost outputs bo = (plain token, the emitted token's plain probability)) of lines p at positions pos (arrays over the lines of
-        one step)."""
+    def _put(self, p, pos, t, s_, b_, more=()):
+        """Token t / score s_ / box b_ (/ `more`: the extra set's values, one array per matrix) of lines p at positions pos (arrays over
+        the lines of one step)."""
         self.tok_mat[p, pos] = t
         self.sc_mat[p, pos] = s_
-        if bo is not None:
-            self.plain_tok_mat[p, pos], self.plain_p_mat[p, pos] = bo
-        if at is not None:
-            self.alt_tok_mat[p, pos] = at
-            self.alt_p_mat[p, pos] = ap
-        if fo is not None:
-            self.greedy_tok_mat[p, pos], self.greedy_p_mat[p, pos], self.logp_mat[p, pos] = fo
+        for a, v in zip(self.extra_mats, more):
+            a[p, pos] = v
         m = pos < self.overall_max_tokens
         if m.all():
             self.batch_bboxes[p, pos] = b_
         elif m.any():
             self.batch_bboxes[p[m], pos[m]] = b_[m]
         self.line_len[p] = pos + 1
+
+    def _read_extra(self, sl_) -> list:
+        """The extra set's values of the prefill's token (it has alternatives / a greedy reading / a plain reading too) for slots sl_."""
+        return [a[0, sl_] for a in getattr(self.model, self.extra.read)(1)] if self.extra is not None else ()
 
     def _flush_active(self):
         """Tell the model which slots still decode (ascending) and let the caller collect the lines that just finished."""
@@ -379,9 +344,7 @@ class DeviceLoop:
         tok, sc, bb = self.model.wait_outputs(k, ring)
         if self.beam:
             return self._absorb_beam(k, bb, self.model.wait_beam(k, ring))
-        at, ap = self.model.wait_alternatives(k, ring) if self.alternatives else (None, None)
-        fo = self.model.wait_forced(k, ring) if self.forced else None
-        bo = self.model.wait_boost(k, ring) if self.n_boost_states else None
+        ex = getattr(self.model, self.extra.wait)(k, ring) if self.extra is not None else ()
         slot_line, line_len, max_tok, tok_mat, eos, pad = self.slot_line, self.line_len, self.max_tok, self.tok_mat, self.eos, self.pad
         changed = False
         for step in range(k):
@@ -391,14 +354,7 @@ class DeviceLoop:
             p = slot_line[s_idx]
             pos = line_len[p]
             t = tok[step, s_idx]
-            if fo is not None:
-                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], fo=tuple(a[step, s_idx] for a in fo))
-            elif bo is not None:
-                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], bo=tuple(a[step, s_idx] for a in bo))
-            elif at is None:
-                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx])
-            else:
-                self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], at[step, s_idx], ap[step, s_idx])
+            self._put(p, pos, t, sc[step, s_idx], bb[step, s_idx], [a[step, s_idx] for a in ex] if ex else ())
             new_len = pos + 1
             stop = (t == eos) | (t == pad) | (new_len >= max_tok[p])
             # repeat rule: <= 5 distinct ids in the last 40 and the last u ids equal to the u before; the distinct count is
@@ -487,8 +443,7 @@ class DeviceLoop:
         self._prefill(take, [self.grids[i] for i in take], [self.prompt_ids[i] for i in take], fans)
         tok, sc, bb = self.model.read_outputs(1)
         first = tok[0, sl_]
-        fo = tuple(a[0, sl_] for a in self.model.read_forced(1))
-        self._put(rows, np.zeros(len(rows), np.int64), first, sc[0, sl_], bb[0, sl_], fo=fo)
+        self._put(rows, np.zeros(len(rows), np.int64), first, sc[0, sl_], bb[0, sl_], self._read_extra(sl_))
         go_on = (first != self.eos) & (first != self.nop) & (self.max_tok[rows] > 1)
         for r, s, go in zip(rows.tolist(), sl_.tolist(), go_on.tolist()):
             if go:
@@ -520,27 +475,15 @@ class DeviceLoop:
         grids, prompt_ids = [self.grids[i] for i in take], [self.prompt_ids[i] for i in take]
         if self.beam:
             return self._prefill_beam(take, slots, grids, prompt_ids)
-        if self.n_masks:
-            self.model.set_slot_masks(slots, self.line_mask[take].tolist())       # the first token is constrained too
-        if self.n_states:
-            self.model.set_slot_patterns(slots, self.line_state[take].tolist())   # behind the mask ids: a start state names its own row
-        if self.n_lex_states:
-            self.model.set_slot_lexicon(slots, self.line_lex[take].tolist())      # likewise: the slot's own row becomes its mask id
-        if self.n_boost_states:
-            self.model.set_slot_boost(slots, self.line_root[take].tolist(), self.boost_beta)      # behind the mask ids: a root names the slot's own row
+        for o, (_, vals, args) in self.line_opts.items():       # in table order, behind the mask ids; the first token is constrained too
+            getattr(self.model, o.set_slot)(slots, vals[take].tolist(), *args)
         if self.forced:
             self.model.set_forced_tokens(slots, [self.forced_ids[i] for i in take])      # the first token is forced too
         self._prefill(take, grids, prompt_ids, slots)
         tok, sc, bb = self.model.read_outputs(1)
         ids_, sl_ = np.asarray(take, np.int64), np.asarray(slots, np.int64)
         first = tok[0, sl_]
-        more = ()
-        if self.alternatives:                                       # the first token has alternatives too
-            at, ap = self.model.read_alternatives(1)
-            more = (at[0, sl_], ap[0, sl_])
-        fo = tuple(a[0, sl_] for a in self.model.read_forced(1)) if self.forced else None
-        bo = tuple(a[0, sl_] for a in self.model.read_boost(1)) if self.n_boost_states else None
-        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], *more, fo=fo, bo=bo)
+        self._put(ids_, np.zeros(len(take), np.int64), first, sc[0, sl_], bb[0, sl_], self._read_extra(sl_))
         go_on = (first != self.eos) & (first != self.nop)
         if self.forced:
             go_on &= self.max_tok[ids_] > 1                         # a one-id list is complete with the prefill's token
@@ -557,8 +500,8 @@ class DeviceLoop:
         B = self.beam
         g = np.asarray(groups, np.int64)
         sl = g[:, None] * B + self.lane[None, :]
-        if self.n_masks:
-            self.model.set_slot_masks(sl.reshape(-1).tolist(), np.repeat(self.line_mask[take], B).tolist())
+        if options.MASKS in self.line_opts:                     # (masks only: patterns, lexicons and boosting exclude beam search)
+            getattr(self.model, options.MASKS.set_slot)(sl.reshape(-1).tolist(), np.repeat(self.line_opts[options.MASKS][1][take], B).tolist())
         self._prefill(take, grids, prompt_ids, (g * B).tolist())
         _, _, bb = self.model.read_outputs(1)
         bt, bpar, _, bprob, blogp = self.model.read_beam(1)
@@ -574,41 +517,23 @@ class DeviceLoop:
     def run(self, prep=None):
         """Admit `prep` (if any) and loop until the queue, the slots and the feed are exhausted."""
         m = self.model
-        table = None if prep is None else prep.get("token_masks")
-        pattern_tables = None if prep is None else prep.get("pattern_tables")
-        assert pattern_tables is None or not (self.beam or self.forced), "patterns exclude beam search and forced decoding"
-        lexicon_tables = None if prep is None else prep.get("lexicon_tables")
-        assert lexicon_tables is None or not (self.beam or self.forced), "lexicons exclude beam search and forced decoding"
-        boost_tables = None if prep is None else prep.get("boost_tables")
-        assert boost_tables is None or not (self.beam or self.forced or self.alternatives or pattern_tables is not None or
-                                            lexicon_tables is not None), \
-            "boosting excludes alternatives, beam search, forced decoding, patterns and lexicons"
+        # the options whose table came with `prep` and names at least one row / state
+        on = [(o, prep[o.table_key]) for o in options.requested(prep or {}) if o.count(prep[o.table_key]) > 0]
+        running = {k for k in ("beam", "forced", "alternatives") if getattr(self, k)} | {o.name for o, _ in on}
+        for o, _ in on:
+            assert running.isdisjoint(o.excludes), o.excludes_msg
 
-        def masks_on():
-            m.set_token_masks(table)                   # once per call: identical masks were merged by the caller
-            self.n_masks = len(table)
-
-        def patterns_on():
-            m.set_patterns(pattern_tables)             # behind the mask table: the states name its rows
-            self.n_states = int(pattern_tables.n_states)
-
-        def lexicon_on():
-            m.set_lexicon(lexicon_tables)              # behind the mask table too: every slot gets a row of its own behind its rows
-            self.n_lex_states = int(lexicon_tables.n_states)
-
-        def boost_on():
-            m.set_boost(boost_tables)                  # behind the mask table, which holds the word-unit row
-            self.n_boost_states, self.boost_beta = int(boost_tables.n_states), float(prep["boost_weight"])
-            self.plain_tok_mat, self.plain_p_mat = np.zeros((0, self.cap), np.int32), np.zeros((0, self.cap), np.float32)
+        def option_on(o, table):
+            getattr(m, o.set_table)(table)                 # once per call, behind the tables before it
+            self.line_opts[o] = [o.count(table), np.zeros(0, np.int64), tuple(float(prep[k]) for k in o.call_keys)]
+            if o.extra is not None:
+                self._use_extra(o.extra)
         # (requested, switch on, switch off): switched on in this order, off in reverse on the way out, also after an exception, so the
         # next call starts on the greedy, unmasked kernels without candidates. What was not requested never touches its entry points.
         modes = [(self.beam, lambda: m.set_beam(self.beam, self.nop), lambda: m.set_beam(None)),
                  (self.forced, lambda: m.set_forced(True), lambda: m.set_forced(False)),      # (at most one of the first three: __init__)
-                 (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False)),
-                 (table is not None and len(table) > 0, masks_on, lambda: m.set_token_masks(None)),
-                 (pattern_tables is not None, patterns_on, lambda: m.set_patterns(None)),
-                 (lexicon_tables is not None, lexicon_on, lambda: m.set_lexicon(None)),
-                 (boost_tables is not None, boost_on, lambda: m.set_boost(None))]
+                 (self.alternatives, lambda: m.set_alternatives(True), lambda: m.set_alternatives(False))]
+        modes += [(True, lambda o=o, t=t: option_on(o, t), lambda o=o: getattr(m, o.set_table)(None)) for o, t in on]
         with ExitStack() as undo:
             for wanted, on, off in modes:
                 if wanted:

@@ -19,6 +19,7 @@ import os
 import time
 import zlib
 from concurrent.futures import ThreadPoolExecutor
+from contextlib import contextmanager
 from dataclasses import dataclass
 from typing import List, Optional
 
@@ -29,7 +30,7 @@ from PIL import Image
 from ..common.imageops import fill_poly_mask, quad_homography, quad_size, rectify_threshold, should_rectify, warp_quad
 from ..common.predictor import BasePredictor, gc_paused
 from ..settings import settings
-from . import assemble
+from . import assemble, options
 from .loader import RecognitionModelLoader, rec_config_from_reference_json  # noqa: F401  (re-exported)
 from .loop import FEED_END, DeviceLoop
 from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref, quad_ref
@@ -187,6 +188,27 @@ def per_image_lexicons(arg, n_images, name="lexicon") -> list:
     return out
 
 
+def given_lists(allowlist=None, blocklist=None, pattern=None, lexicon=None, boost_words=None, boost_weight=None) -> dict:
+    """The list arguments of a call that were given, as keywords: `_call` is reached positionally by the page-sharded path and by
+    stand-ins, so the lists go by keyword and only when given (allowlist and blocklist together; boost_weight with boost_words)."""
+    lists = {} if allowlist is None and blocklist is None else {"allowlist": allowlist, "blocklist": blocklist}
+    lists.update((k, v) for k, v in (("pattern", pattern), ("lexicon", lexicon), ("boost_words", boost_words)) if v is not None)
+    if boost_words is not None:
+        lists["boost_weight"] = boost_weight
+    return lists
+
+
+def list_for_pages(name, arg, n_images, pages) -> list:
+    """List argument `name` of a call over n_images, for the images `pages` only, back in argument form (one entry per image; a
+    lexicon as a list, not a key)."""
+    if name in ("allowlist", "blocklist", "pattern"):
+        per = per_image_lists(arg, name, n_images)
+        return [per[i] for i in pages]
+    per = per_image_lexicons(arg, n_images, name)
+    return [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list) else list(per[i])
+            for i in pages]
+
+
 class LineConstraints:
     """The allowlist / blocklist / pattern arguments of one call, resolved: `table` holds the call's distinct token masks (MaskTable:
     identical sets are merged), `per_image[i]` the mask id of every line of image i (an int) or one id per line (a list). `lines_known`
@@ -311,16 +333,14 @@ class LineConstraints:
             out.extend(ids if isinstance(ids, list) else [ids] * n)
         return out
 
+    # line_ids for the other options' integers (-1 = no pattern / no lexicon / not boosted); a call with that option only
     def line_states(self, slice_map) -> list:
-        """One start state per line (-1 = no pattern), like line_ids; a call with patterns only."""
         return self.line_ids(slice_map, self.per_image_state)
 
     def line_lexicon_starts(self, slice_map) -> list:
-        """One lexicon start state per line (-1 = no lexicon), like line_ids; a call with lexicons only."""
         return self.line_ids(slice_map, self.per_image_lex)
 
     def line_boost_roots(self, slice_map) -> list:
-        """One boost root state per line (-1 = not boosted), like line_ids; a call with boost_words only."""
         return self.line_ids(slice_map, self.per_image_root)
 
 
@@ -550,15 +570,7 @@ class RecognitionPredictor(BasePredictor):
         else:
             tiles, tile_offs, grids, prompt_ids = self.preprocess_prompts(prompts)
         prep = {"prompts": prompts, "max_tokens": max_tokens, "tiles": tiles, "tile_offs": tile_offs, "grids": grids,
-                "prompt_ids": prompt_ids}
-        if flat.get("token_masks") is not None:               # constrained output: the call's mask table and one row id per line
-            prep.update(token_masks=flat["token_masks"], mask_ids=flat["mask_ids"])
-        if flat.get("pattern_tables") is not None:            # ... and with patterns the call's automaton and one start state per line
-            prep.update(pattern_tables=flat["pattern_tables"], start_states=flat["start_states"])
-        if flat.get("lexicon_tables") is not None:            # ... and with lexicons theirs
-            prep.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=flat["lexicon_starts"])
-        if flat.get("boost_tables") is not None:              # ... and with boost_words the automaton, beta and one root per line
-            prep.update(boost_tables=flat["boost_tables"], boost_weight=flat["boost_weight"], boost_roots=flat["boost_roots"])
+                "prompt_ids": prompt_ids, **options.take(flat)}      # ... and every per-line option of the call: its table, one integer per line
         if flat.get("forced_ids") is not None:                # align(): one forced id list per line
             prep["forced_ids"] = flat["forced_ids"]
             if flat.get("fan"):                               # rank(): a LIST of id lists per line, one slot each behind one prefill
@@ -573,11 +585,13 @@ class RecognitionPredictor(BasePredictor):
         first = prep if prep is not None else {}
         overall_max_tokens = int(first.get("overall_max_tokens") or max(first["max_tokens"].values()))
         proc = self.processor
-        more = {"alternatives": True} if self._top_k is not None else {}      # (only then: a stand-in loop keeps its signature)
+        # (keywords only for what is on: a stand-in loop keeps its signature.) `extra`: the one extra output set of the run, if any
+        more, extra = ({"alternatives": True}, options.ALTERNATIVES) if self._top_k is not None else ({}, None)
         if first.get("forced_ids") is not None:
-            more = {"forced": True, "fan": True} if first.get("fan") else {"forced": True}      # rank(): a list of candidates per line
+            more, extra = ({"forced": True, "fan": True} if first.get("fan") else {"forced": True}), options.FORCED      # rank(): a list of candidates per line
         elif self._beam is not None:
-            more = {"beam": self._beam}
+            more, extra = {"beam": self._beam}, None
+        extra = options.option_extra(first) or extra
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
                           min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
                           on_done=on_done, on_flush=on_flush, feed=feed, **more)
@@ -586,12 +600,8 @@ class RecognitionPredictor(BasePredictor):
         # without walking the per-line lists again
         from ..dist import PackedLines
         self.last_packed = (PackedLines(loop.tok_mat, loop.line_len), PackedLines(loop.sc_mat, loop.line_len))
-        if "forced" in more:                                  # ... an aligned call's greedy ids, their probabilities, the log-probabilities
-            self.last_forced = tuple(PackedLines(a, loop.line_len) for a in (loop.greedy_tok_mat, loop.greedy_p_mat, loop.logp_mat))
-        if first.get("boost_tables") is not None:             # ... a boosted call's plain readings [n, cap]
-            self.last_boost = (PackedLines(loop.plain_tok_mat, loop.line_len), PackedLines(loop.plain_p_mat, loop.line_len))
-        if "alternatives" in more:                            # ... and the alternatives [n, cap, 4] likewise
-            self.last_alternatives = (PackedLines(loop.alt_tok_mat, loop.line_len), PackedLines(loop.alt_p_mat, loop.line_len))
+        if extra is not None:                                 # ... and the extra set's matrices likewise: last_forced / last_boost / last_alternatives
+            setattr(self, extra.last, tuple(PackedLines(getattr(loop, f.attr), loop.line_len) for f in extra.fields))
         return loop.predicted_tokens, torch.from_numpy(loop.batch_bboxes), loop.scores
 
     def prediction_loop(self, flat: dict, recognition_batch_size: int | None = None, math_mode: bool = True) -> tuple:
@@ -622,17 +632,11 @@ class RecognitionPredictor(BasePredictor):
         local = {k: [flat[k][i] for i in mine] for k in ("slices", "input_text", "task_names")}
         if "pages" in flat:
             local["pages"] = flat["pages"]
-        if flat.get("token_masks") is not None:               # every rank holds the whole table; the ids travel with the lines
-            local.update(token_masks=flat["token_masks"], mask_ids=[flat["mask_ids"][i] for i in mine])
-        if flat.get("pattern_tables") is not None:            # ... and so do the start states
-            local.update(pattern_tables=flat["pattern_tables"], start_states=[flat["start_states"][i] for i in mine])
-        if flat.get("lexicon_tables") is not None:
-            local.update(lexicon_tables=flat["lexicon_tables"], lexicon_starts=[flat["lexicon_starts"][i] for i in mine])
-        if flat.get("boost_tables") is not None:
-            local.update(boost_tables=flat["boost_tables"], boost_weight=flat["boost_weight"], boost_roots=[flat["boost_roots"][i] for i in mine])
+        local.update(options.take(flat, mine))                # every rank holds the whole tables; the lines' integers travel with the lines
         max_tokens = max(self.line_budget(t) for t in flat["task_names"])
-        alts = plain = None
-        boosted = flat.get("boost_tables") is not None
+        # the extra output set that rides in the same collective: a boosted call's plain readings, else the alternatives of top_k
+        extra = options.option_extra(flat) or (options.ALTERNATIVES if self._top_k is not None else None)
+        more = None
         if mine:
             self.last_packed = None                          # only what generate() sets DURING this call counts (a stand-in prediction_loop
             toks, boxes, scores = self.prediction_loop(local, recognition_batch_size, math_mode)      # must not gather an earlier call's arrays)
@@ -640,31 +644,26 @@ class RecognitionPredictor(BasePredictor):
             if packed is not None and len(packed[0]) == len(toks):      # generate()'s dense arrays: no per-token Python in the pack
                 toks, scores = packed
             self.last_packed = None                          # (and the [n, cap] matrices are not pinned on the predictor between calls)
-            alts, self.last_alternatives = getattr(self, "last_alternatives", None), None
-            plain, self.last_boost = getattr(self, "last_boost", None), None
+            if extra is not None:
+                more = getattr(self, extra.last, None)
+                setattr(self, extra.last, None)
             boxes = boxes.numpy()
             if boxes.shape[1] < max_tokens:
                 boxes = np.pad(boxes, ((0, 0), (0, max_tokens - boxes.shape[1]), (0, 0)))
         else:
             toks, scores, boxes = [], [], np.zeros((0, max_tokens, 6), np.float32)
-        if boosted:                                          # the plain readings ride in the alternatives' places of the same collective:
-            w1 = lambda pl: sdist.PackedLines(pl.data[:, :, None], pl.lens)      # one "alternative" per token (boost_words exclude top_k)
-            if plain is None:
-                plain = (sdist.PackedLines(np.zeros((0, max_tokens), np.int32), np.zeros(0, np.int64)),
-                         sdist.PackedLines(np.zeros((0, max_tokens), np.float32), np.zeros(0, np.int64)))
-            toks, scores, boxes, a_tok, a_p = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group,
-                                                                        alts=(w1(plain[0]), w1(plain[1])))
-            self.last_boost = (sdist.PackedLines(a_tok.data[:, :, 0], a_tok.lens), sdist.PackedLines(a_p.data[:, :, 0], a_p.lens))
+        if extra is None:
+            toks, scores, boxes = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group)
             return toks, torch.from_numpy(boxes), scores
-        if self._top_k is not None:                          # the two alternative arrays ride in the same collective
-            if alts is None:
-                alts = (sdist.PackedLines(np.zeros((0, max_tokens, 4), np.int32), np.zeros(0, np.int64)),
-                        sdist.PackedLines(np.zeros((0, max_tokens, 4), np.float32), np.zeros(0, np.int64)))
-            toks, scores, boxes, a_tok, a_p = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group,
-                                                                        alts=alts)
-            self.last_alternatives = (a_tok, a_p)
-            return toks, torch.from_numpy(boxes), scores
-        toks, scores, boxes = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group)
+        # the set's two arrays ride in the collective's [n, T, A] places: the alternatives as they are, the plain readings as one
+        # "alternative" per token (boost_words exclude top_k)
+        if more is None:
+            more = tuple(sdist.PackedLines(a, np.zeros(0, np.int64)) for a in options.empty_rows(extra, 0, (max_tokens,)))
+        scalar = not extra.fields[0].tail
+        if scalar:
+            more = tuple(sdist.PackedLines(pl.data[:, :, None], pl.lens) for pl in more)
+        toks, scores, boxes, *more = sdist.gather_line_outputs(toks, scores, boxes, mine, n, max_tokens, device=dev, group=group, alts=tuple(more))
+        setattr(self, extra.last, tuple(sdist.PackedLines(pl.data[:, :, 0], pl.lens) if scalar else pl for pl in more))
         return toks, torch.from_numpy(boxes), scores
 
     # ------------------------------------------------------------------------------------- output assembly
@@ -784,16 +783,22 @@ class RecognitionPredictor(BasePredictor):
                 raise ValueError("boost_words needs boost_weight, the boost in logit units (a finite float >= 0); it has no default")
             if isinstance(boost_weight, bool) or not isinstance(boost_weight, (int, float)) or not 0 <= boost_weight < float("inf"):
                 raise ValueError(f"boost_weight must be a finite float >= 0, got {boost_weight!r}")
-        # (the validated value, for the length of the call: `_call`, `generate` and the loops are reached positionally by the
-        # page-sharded path and by stand-ins and read it from here)
-        saved_k, self._top_k = self._top_k, top_k
-        saved_b, self._beam = self._beam, beam
-        try:
+        with self._modes(top_k, beam):
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
                                         pattern, lexicon, boost_words, boost_weight)
+
+    @contextmanager
+    def _modes(self, top_k=None, beam=None):
+        """The validated top_k and beam_width for the length of a call: `_call`, `generate` and the loops are reached positionally by the
+        page-sharded path and by stand-ins and read them from here. align() and rank() park both: they report `greedy`, not
+        alternatives, and one reading, the given one, whatever beam_width says."""
+        saved = self._top_k, self._beam
+        self._top_k, self._beam = top_k, beam
+        try:
+            yield
         finally:
-            self._top_k, self._beam = saved_k, saved_b
+            self._top_k, self._beam = saved
             if top_k is not None:
                 self.last_alternatives = None
 
@@ -878,13 +883,8 @@ class RecognitionPredictor(BasePredictor):
                 raise ValueError(f"image {i} has {len(gv)} lines but {len(tx)} texts")
             for j, text in enumerate(tx):
                 forced.append(self._forced_line_ids(f"image {i}, line {j}", text, task))
-        saved_k, self._top_k = self._top_k, None              # (an aligned call reports `greedy`, not alternatives)
-        saved_b, self._beam = self._beam, None                # (and one reading, the given one, whatever beam_width says)
-        try:
-            with gc_paused():
-                return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
-        finally:
-            self._top_k, self._beam = saved_k, saved_b
+        with self._modes(), gc_paused():
+            return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
 
     def _align(self, images, forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words) -> List[OCRResult]:
         t_call = time.perf_counter()
@@ -941,13 +941,8 @@ class RecognitionPredictor(BasePredictor):
                     raise ValueError(f"image {i}, line {j}: {len(distinct)} distinct candidates exceed the {slots} slots in use "
                                      f"(recognition_batch_size / the model's slots)")
                 lines.append((list(texts), distinct, index))
-        saved_k, self._top_k = self._top_k, None              # (parked for the call, as in align)
-        saved_b, self._beam = self._beam, None
-        try:
-            with gc_paused():
-                return self._rank(convert_if_not_rgb(images), lines, task_names, bboxes, polygons, recognition_batch_size, math_mode)
-        finally:
-            self._top_k, self._beam = saved_k, saved_b
+        with self._modes(), gc_paused():
+            return self._rank(convert_if_not_rgb(images), lines, task_names, bboxes, polygons, recognition_batch_size, math_mode)
 
     def _rank(self, images, lines, task_names, bboxes, polygons, recognition_batch_size, math_mode) -> List[RankResult]:
         t_call = time.perf_counter()
@@ -1005,16 +1000,9 @@ class RecognitionPredictor(BasePredictor):
                         pattern=None, lexicon=None, boost_words=None, boost_weight=None):
         # the whole call runs with the cyclic GC paused (gc_paused): slicing, scheduling and assembly allocate ~10^6 acyclic objects
         with gc_paused():
-            # (the lists go by keyword and only when given: `_call` is reached positionally by the page-sharded path and by stand-ins)
-            lists = {} if allowlist is None and blocklist is None else {"allowlist": allowlist, "blocklist": blocklist}
-            if pattern is not None:
-                lists["pattern"] = pattern
-            if lexicon is not None:
-                lists["lexicon"] = lexicon
-            if boost_words is not None:
-                lists.update(boost_words=boost_words, boost_weight=boost_weight)
             return self._call(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                              bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
+                              bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text,
+                              **given_lists(allowlist, blocklist, pattern, lexicon, boost_words, boost_weight))
 
     def _constraints(self, allowlist, blocklist, images, bboxes, polygons, pattern=None, lexicon=None, boost_words=None):
         """The call's LineConstraints, or None for a call without lists, patterns, lexicons or boost_words (or whose entries are all None)."""
@@ -1057,13 +1045,8 @@ class RecognitionPredictor(BasePredictor):
             if self.shard_pages:
                 from .. import dist as sdist
                 if sdist.collectives_on(self.process_group):
-                    lists = {} if cons is None else {"allowlist": allowlist, "blocklist": blocklist}
-                    if cons is not None and cons.patterns is not None:
-                        lists["pattern"] = pattern
-                    if cons is not None and cons.lexicons is not None:
-                        lists["lexicon"] = lexicon
-                    if cons is not None and cons.boost is not None:
-                        lists.update(boost_words=boost_words, boost_weight=boost_weight)
+                    # (lists whose entries are all None -- no `cons` -- are no lists)
+                    lists = {} if cons is None else given_lists(allowlist, blocklist, pattern, lexicon, boost_words, boost_weight)
                     return self._call_page_sharded(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
                                                    highres_images, sort_lines, math_mode, return_words, drop_repeated_text, **lists)
             if self._can_stream(det_predictor):
@@ -1082,18 +1065,8 @@ class RecognitionPredictor(BasePredictor):
         if self._top_k is not None:
             flat["top_k"] = self._top_k
         sorted_keys = ("slices", "input_text", "task_names")
-        if cons is not None:                                  # by line id like the slices: sorted with them below
-            flat["token_masks"], flat["mask_ids"] = cons.table.array(), cons.line_ids(flat["slice_map"])
-            sorted_keys += ("mask_ids",)
-            if cons.patterns is not None:
-                flat["pattern_tables"], flat["start_states"] = cons.patterns, cons.line_states(flat["slice_map"])
-                sorted_keys += ("start_states",)
-            if cons.lexicons is not None:
-                flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, cons.line_lexicon_starts(flat["slice_map"])
-                sorted_keys += ("lexicon_starts",)
-            if cons.boost is not None:
-                flat.update(boost_tables=cons.boost, boost_weight=cons.boost_weight, boost_roots=cons.line_boost_roots(flat["slice_map"]))
-                sorted_keys += ("boost_roots",)
+        if cons is not None:                                  # the options' integers are by line id like the slices: sorted with them below
+            sorted_keys += options.attach(flat, cons)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
@@ -1107,8 +1080,10 @@ class RecognitionPredictor(BasePredictor):
                 bb = batch_bboxes.numpy()
                 chunks = [range(a, min(a + 256, len(order))) for a in range(0, len(order), 256)]
                 la = self.last_alternatives if self._top_k is not None else None
-                if flat.get("boost_tables") is not None:      # the plain readings travel like the alternatives
-                    la, self.last_boost = getattr(self, "last_boost", None), None
+                if options.option_extra(flat) is not None:    # an option's own extra set (the plain readings) travels like the alternatives
+                    last = options.option_extra(flat).last
+                    la = getattr(self, last, None)
+                    setattr(self, last, None)
                 alt_of = (lambda k: ()) if la is None else (lambda k: ((la[0].row(k), la[1].row(k)),))
                 text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) + alt_of(k) for k in ks])) for ks in chunks)
             else:
@@ -1153,21 +1128,10 @@ class RecognitionPredictor(BasePredictor):
         self.shard_pages = self.shard_lines = False
         if hasattr(det_predictor, "shard_pages"):
             det_predictor.shard_pages = False
-        lists = {}                                            # a call without lists reaches the rank's own call exactly as it always did
-        if allowlist is not None or blocklist is not None:
-            lists = {"allowlist": [per_image_lists(allowlist, "allowlist", n)[i] for i in mine],
-                     "blocklist": [per_image_lists(blocklist, "blocklist", n)[i] for i in mine]}
-        if pattern is not None:                               # a rank compiles the patterns of its own pages
-            lists["pattern"] = [per_image_lists(pattern, "pattern", n)[i] for i in mine]
-        if lexicon is not None:                               # ... and the lexicons (back in argument form: lists, not keys)
-            per = per_image_lexicons(lexicon, n)
-            lists["lexicon"] = [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list)
-                                else list(per[i]) for i in mine]
-        if boost_words is not None:                           # ... and the boost lists, likewise; beta is the call's
-            per = per_image_lexicons(boost_words, n, "boost_words")
-            lists["boost_words"] = [None if per[i] is None else [None if k is None else list(k) for k in per[i]] if isinstance(per[i], list)
-                                    else list(per[i]) for i in mine]
-            lists["boost_weight"] = boost_weight
+        # a rank compiles the lists of its own pages (beta is the call's); a call without lists reaches the rank's own call exactly as
+        # it always did
+        lists = {k: v if k == "boost_weight" else list_for_pages(k, v, n, mine)
+                 for k, v in given_lists(allowlist, blocklist, pattern, lexicon, boost_words, boost_weight).items()}
         try:
             hr = [highres_images[i] for i in mine]
             local = self._call([images[i] for i in mine], [task_names[i] for i in mine], det_predictor, detection_batch_size,
@@ -1229,15 +1193,8 @@ class RecognitionPredictor(BasePredictor):
         flat = new_flat()
         if self._top_k is not None:
             flat["top_k"] = self._top_k
-        with_patterns = cons is not None and cons.patterns is not None
-        if with_patterns:                                     # assembly replays a line's automaton from its start state
-            flat["pattern_tables"], flat["start_states"] = cons.patterns, []
-        with_lexicons = cons is not None and cons.lexicons is not None
-        if with_lexicons:
-            flat["lexicon_tables"], flat["lexicon_starts"] = cons.lexicons, []
-        with_boost = cons is not None and cons.boost is not None
-        if with_boost:
-            flat.update(boost_tables=cons.boost, boost_weight=cons.boost_weight, boost_roots=[])
+        if cons is not None:                                  # the options' tables and, no page being there yet, an empty list per option:
+            options.attach(flat, cons)                        # assembly replays a line's automaton from the line's integer
         thr = rectify_threshold(self.rectify)
         if thr is not None:
             flat["quads"] = []
@@ -1255,8 +1212,8 @@ class RecognitionPredictor(BasePredictor):
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
-                    pages, refs, polys_all, scales_all, tasks_all, masks_all, states_all, lex_all = [], [], [], [], [], [], [], []
-                    roots_all, quads_all = [], []
+                    pages, refs, polys_all, scales_all, tasks_all, quads_all = [], [], [], [], [], []
+                    first_page = page
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
@@ -1269,14 +1226,6 @@ class RecognitionPredictor(BasePredictor):
                         polys_all.extend(polygons)
                         scales_all.extend([scale] * len(polygons))
                         tasks_all.extend([task_names[page]] * len(polygons))
-                        if cons is not None:                  # (per-call and per-image lists only: one id per page)
-                            masks_all.extend([cons.per_image[page]] * len(polygons))
-                            if with_patterns:
-                                states_all.extend([cons.per_image_state[page]] * len(polygons))
-                            if with_lexicons:
-                                lex_all.extend([cons.per_image_lex[page]] * len(polygons))
-                            if with_boost:
-                                roots_all.extend([cons.per_image_root[page]] * len(polygons))
                         flat["slice_map"].append(len(polygons))
                         page += 1
                     if not refs:
@@ -1287,6 +1236,9 @@ class RecognitionPredictor(BasePredictor):
                     prompts = [RecognitionPrompt(id=base_id + k, task_name=tasks_all[i], text=None, image=refs[i], math_mode=math_mode)
                                for k, i in enumerate(order)]
                     tiles, tile_offs, grids, prompt_ids = self.preprocess_prompts_device(prompts, pages)
+                    # the options' integers of the chunk's lines (per-call and per-image lists only: one per page), by line id
+                    lines = {} if cons is None else {k: [v[i] for i in order] for k, v in
+                                                     options.line_part(cons, flat["slice_map"][first_page:], range(first_page, page)).items()}
                     # everything the assembly thread reads about these lines is in place BEFORE the chunk can be admitted
                     flat["polygons"].extend(polys_all)
                     flat["res_scales"].extend(scales_all)
@@ -1295,19 +1247,11 @@ class RecognitionPredictor(BasePredictor):
                     flat["slices"].extend(refs[i] for i in order)
                     flat["task_names"].extend(tasks_all[i] for i in order)
                     flat["input_text"].extend([None] * len(order))
-                    if with_patterns:
-                        flat["start_states"].extend(states_all[i] for i in order)
-                    if with_lexicons:
-                        flat["lexicon_starts"].extend(lex_all[i] for i in order)
-                    if with_boost:
-                        flat["boost_roots"].extend(roots_all[i] for i in order)
+                    for k, v in lines.items():
+                        flat[k].extend(v)
                     orig_of.extend(base_orig + i for i in order)
                     q.put({"prompts": prompts, "tiles": tiles, "tile_offs": tile_offs, "grids": grids, "prompt_ids": prompt_ids,
-                           "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts},
-                           "mask_ids": [masks_all[i] for i in order] if cons is not None else None,
-                           "start_states": [states_all[i] for i in order] if with_patterns else None,
-                           "lexicon_starts": [lex_all[i] for i in order] if with_lexicons else None,
-                           "boost_roots": [roots_all[i] for i in order] if with_boost else None})
+                           "max_tokens": {p.id: self.line_budget(p.task_name) for p in prompts}, **lines})
                 det_wall[0] = (time.perf_counter() - t_p) * 1e3
                 q.put(FEED_END)
             except BaseException as e:                        # surfaces in the calling thread
@@ -1334,13 +1278,7 @@ class RecognitionPredictor(BasePredictor):
                 try:
                     first = {"prompts": [], "max_tokens": {}, "overall_max_tokens": overall_max_tokens}
                     if cons is not None:
-                        first["token_masks"] = cons.table.array()      # the whole call's table up front: chunks carry row ids only
-                        if with_patterns:
-                            first["pattern_tables"] = cons.patterns
-                        if with_lexicons:
-                            first["lexicon_tables"] = cons.lexicons
-                        if with_boost:
-                            first.update(boost_tables=cons.boost, boost_weight=cons.boost_weight)
+                        first.update(options.call_part(cons))          # the whole call's tables up front: chunks carry the lines' integers only
                     self.generate(first, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush, feed=feed)
                 except BaseException:
                     stop.set()                         # the producer ends after the batch it is working on ...
