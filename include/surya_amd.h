@@ -140,6 +140,44 @@ int surya_rec_prefill_shared(surya_rec* h, const float* tiles, const int32_t* gr
  * outside 1..max_kv_len. Enqueue only. */
 int surya_rec_copy_kv_rows(surya_rec* h, int slot, int rows, void* k_out, void* v_out, void* stream);
 
+/* The prompt store: prompts that outlive their slots (csrc/kv_store.h). A kept prompt ("entry") is a range [first, first + len) of store
+ * rows that holds the prompt's K and V rows of every layer and kv head -- [K | V][layer][kv_head][rows][head_dim] of the handle's dtype --
+ * and, in a side array indexed by `first`, the pre-norm hidden row the prefill's head pass reads for the first token. The caller hands out
+ * row ranges, as it hands out slots; the handle keeps a table of live entries (first -> len) and checks every call against it. A handle
+ * that never reserves rows allocates nothing. Only the prompt is kept: rows appended by decode steps are not.
+ *
+ * surya_rec_reserve_prompts: the store holds at least `rows` rows afterwards (never shrinks; rows <= the current capacity changes
+ * nothing). Growing allocates a new block, copies the old rows over in stream order and frees the old block once they are there (it waits
+ * for the device). No captured decode step holds an address of the store, so none is dropped. SA_ERR_ARG for rows < 0; an allocation
+ * failure leaves the store as it was. */
+int surya_rec_reserve_prompts(surya_rec* h, int rows, void* stream);
+/* surya_rec_prefill that also keeps prompts: behind the decoder layers, sequence i with keep_first[i] >= 0 has its rows [0, len_i) and its
+ * last hidden row copied to the store at row keep_first[i] (in this call, because the hidden rows do not survive the next launch that
+ * uses the workspace), and [keep_first[i], keep_first[i] + len_i) becomes a live entry. The slots take surya_rec_prefill's code path and
+ * emit their first token as ever; the other arguments are that call's.
+ *   keep_first   host [n_seqs], first store row of sequence i, or -1 to keep nothing of it
+ * Checked before anything is enqueued or changed: SA_ERR_ARG for a value below -1, a range that reaches past the reserved rows or
+ * overlaps a live entry or another range of this call; SA_ERR_STATE while the FP8 KV cache is on. Enqueue only. */
+int surya_rec_prefill_keep(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids,
+                           const int32_t* seq_offsets, const int32_t* slot_ids, int n_seqs, const int32_t* keep_first, void* stream);
+/* Land kept prompts in slots: entry first[i] is read once and written to every slot of fan_slots[fan_offsets[i] .. fan_offsets[i + 1]).
+ * Every fan slot gets the entry's length as kv_len and a head row of its own, computed from the stored hidden row by the kernels that end
+ * a prefill: outputs(step 0) and the slots' next tokens are what surya_rec_prefill of the same prompt would have left, under whatever the
+ * surya_rec_set_slot_* calls before it set on the slots (masks, pattern / lexicon / boost states, forced columns). With beam search on
+ * every fan is one lead slot of a whole group and the first selection follows, as in surya_rec_prefill.
+ *   first        host [n], live entries (an entry may be named more than once)
+ *   fan_offsets  host [n+1], fan_offsets[0] == 0, strictly increasing
+ *   fan_slots    host [fan_offsets[n]], distinct, < max_slots, at most max_slots in all
+ * Checked before anything is enqueued or changed: SA_ERR_ARG for an unknown entry and for what surya_rec_prefill_shared refuses in its
+ * fans (with beam search on also a fan of more than one slot, or a slot that does not lead a whole group); SA_ERR_STATE while the FP8 KV
+ * cache is on (the store holds bf16 / fp16 / fp32 rows only). MXFP8 decode weights are fine: no prefill kernel reads them. Enqueue only. */
+int surya_rec_restore(surya_rec* h, const int32_t* first, const int32_t* fan_offsets, const int32_t* fan_slots, int n, void* stream);
+/* Forget entries: host bookkeeping only, their rows may be handed out again. SA_ERR_ARG (and nothing forgotten) if one of them is not a
+ * live entry or is named twice. */
+int surya_rec_drop_prompts(surya_rec* h, const int32_t* first, int n);
+/* Test hooks: the store's capacity in rows and the number of live entries. */
+int surya_rec_prompt_store_info(surya_rec* h, int32_t* cap_rows, int32_t* live_entries);
+
 /* Look-ahead encoding (no counterpart in the reference, which encodes inside the prefill call, common/surya/__init__.py:
  * 130-195): run the vision encoder for the images of the NEXT prompts on the library's own low-priority stream (after
  * the work already queued on `stream`, which produced `tiles`), concurrently with decode steps on `stream`. The merged
@@ -637,6 +675,21 @@ int surya_op_rec_kv_fork(int dtype, void* kcache, void* vcache, const int32_t* f
 int surya_op_rec_kv_fanout(int dtype, void* kcache, void* vcache, const int32_t* fan_src, const int32_t* fan_off, const int32_t* fan_dst,
                            const int32_t* fan_len, int n_seqs, int n_dst, int layers, int slots, int kv_heads, int max_kv_len, int head_dim,
                            void* stream);
+/* The two kernels of the prompt store alone (csrc/kv_store.h), through the launcher the engine uses; device pointers. Caches as for
+ * kv_fork; store_k / store_v are [layers][kv_heads][cap_rows][head_dim] of `dtype`. Entry n is the store rows [first[n], first[n] + len[n]);
+ * len is clamped to [0, max_kv_len] and to cap_rows - first[n], and an entry whose first row is outside [0, cap_rows) is skipped.
+ *   kv_keep:     rows [0, len[n]) of every layer, kv head, K and V of slot slot[n] go to entry n; a slot out of range is skipped. With x
+ *                given (else x, last_row, hid NULL), row last_row[n] of x [x_rows][hidden] also goes to row first[n] of hid
+ *                [cap_rows][hidden]; a last_row outside [0, x_rows) copies none. Entries of one call must not overlap.
+ *   kv_restore:  entry n goes to rows [0, len[n]) of the slots fan_dst[fan_off[n] .. fan_off[n + 1]); fan_dst holds n_dst entries. A
+ *                destination out of range is skipped. A slot must not be a destination twice in one call.
+ * Shape rules and errors as for kv_fork; hidden * sizeof(dtype) must be a multiple of 16 as well. */
+int surya_op_rec_kv_keep(int dtype, const void* kcache, const void* vcache, void* store_k, void* store_v, const int32_t* slot,
+                         const int32_t* first, const int32_t* len, int n, int layers, int slots, int kv_heads, int max_kv_len, int head_dim,
+                         int cap_rows, const void* x, const int32_t* last_row, void* hid, int hidden, int x_rows, void* stream);
+int surya_op_rec_kv_restore(int dtype, void* kcache, void* vcache, const void* store_k, const void* store_v, const int32_t* first,
+                            const int32_t* len, const int32_t* fan_off, const int32_t* fan_dst, int n, int n_dst, int layers, int slots,
+                            int kv_heads, int max_kv_len, int head_dim, int cap_rows, void* stream);
 /* The two kernels of lexicon-guided decoding (csrc/lexicon.h) on caller-owned DEVICE buffers, through the launch code the engine uses. The
  * tables are read unchecked, as the engine's are after its validation. `table` is a whole mask table of rows of `words` uint32; slot s
  * owns row row_base + s. eos / pad / nop ids outside [0, vocab) have no bit.

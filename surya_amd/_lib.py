@@ -159,6 +159,14 @@ def _bind_lay_ops(lib):
     lib.surya_rec_prefill_shared.argtypes, lib.surya_rec_prefill_shared.restype = [p, p, ip, i, ip, ip, ip, ip, i, p], C.c_int
     lib.surya_rec_copy_kv_rows.argtypes, lib.surya_rec_copy_kv_rows.restype = [p, i, i, p, p, p], C.c_int
     lib.surya_op_rec_kv_fanout.argtypes, lib.surya_op_rec_kv_fanout.restype = [i, p, p, p, p, p, p, i, i, i, i, i, i, i, p], C.c_int
+    # the prompt store (prompts kept across calls: encode once, read / rank / align as often as asked) and its two kernels by themselves
+    lib.surya_rec_reserve_prompts.argtypes, lib.surya_rec_reserve_prompts.restype = [p, i, p], C.c_int
+    lib.surya_rec_prefill_keep.argtypes, lib.surya_rec_prefill_keep.restype = [p, p, ip, i, ip, ip, ip, i, ip, p], C.c_int
+    lib.surya_rec_restore.argtypes, lib.surya_rec_restore.restype = [p, ip, ip, ip, i, p], C.c_int
+    lib.surya_rec_drop_prompts.argtypes, lib.surya_rec_drop_prompts.restype = [p, ip, i], C.c_int
+    lib.surya_rec_prompt_store_info.argtypes, lib.surya_rec_prompt_store_info.restype = [p, ip, ip], C.c_int
+    lib.surya_op_rec_kv_keep.argtypes, lib.surya_op_rec_kv_keep.restype = [i, p, p, p, p, p, p, p, i, i, i, i, i, i, i, p, p, p, i, i, p], C.c_int
+    lib.surya_op_rec_kv_restore.argtypes, lib.surya_op_rec_kv_restore.restype = [i, p, p, p, p, p, p, p, p, i, i, i, i, i, i, i, i, p], C.c_int
     # pattern-guided decoding (a slot's mask id follows an automaton over its tokens; recognition/pattern.py compiles the tables)
     lib.surya_rec_set_patterns.argtypes = [p, C.POINTER(C.c_uint8), C.POINTER(C.c_uint16), C.POINTER(C.c_uint8), i, i, p]
     lib.surya_rec_set_patterns.restype = C.c_int

@@ -18,6 +18,7 @@
 #include "decode_attn.h"
 #include "decode_attn_kv8.h"
 #include "kv_fanout.h"
+#include "kv_store.h"
 #include "attn_mfma.h"
 #include "beam.h"
 #include "automaton_core.h"
@@ -293,6 +294,11 @@ struct RecBase {
     virtual ~RecBase() {}
     virtual int prefill(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
     virtual int prefill_shared(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int reserve_prompts(int, hipStream_t) = 0;
+    virtual int prefill_keep(const float*, const int32_t*, int, const int32_t*, const int32_t*, const int32_t*, int, const int32_t*, hipStream_t) = 0;
+    virtual int restore(const int32_t*, const int32_t*, const int32_t*, int, hipStream_t) = 0;
+    virtual int drop_prompts(const int32_t*, int) = 0;
+    virtual int prompt_store_info(int32_t*, int32_t*) = 0;
     virtual int set_active(const int32_t*, int, hipStream_t) = 0;
     virtual int encode_ahead(const float*, const int32_t*, int, hipStream_t) = 0;
     virtual int decode(int, hipStream_t) = 0;
@@ -627,7 +633,7 @@ struct RecModel : RecBase {
         return SA_OK;
     }
     ~RecModel() override {
-        for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena}) b->release();
+        for (DevBlock* b : {&mx_arena, &kv8_arena, &alt_arena, &beam_arena, &forced_arena, &store}) b->release();
         if (mask_arena) (void)hipFree(mask_arena);
         if (pat_arena) (void)hipFree(pat_arena);
         lex.release(); bst.release(); bst_slots.release();
@@ -1456,12 +1462,14 @@ struct RecModel : RecBase {
 
     // fuse_next: the rows are the active list of a decode call and another step follows -- the head also writes that step's
     // embedding, first RMSNorm and row_len (decode_eager skips the embed launch).
-    int heads(int rows, const int* d_last_row, const int* d_row_slot, int step, int len_inc, bool normed, hipStream_t s, bool fuse_next = false) {
+    // xrows: the pre-norm rows d_last_row indexes, where they are not the prefill's (restore: the store's hidden rows).
+    int heads(int rows, const int* d_last_row, const int* d_row_slot, int step, int len_inc, bool normed, hipStream_t s, bool fuse_next = false,
+              const T* xrows = nullptr) {
         const int Hd = c.dec_hidden;
         int rc;
         T* last = dlast;
         float4* am = amax;
-        if (!normed && (rc = rmsnorm(dx, Hd, W(SA_RW_DEC_NORM), last, Hd, d_last_row, rows, Hd, c.dec_eps, s))) return rc;
+        if (!normed && (rc = rmsnorm(xrows ? xrows : dx, Hd, W(SA_RW_DEC_NORM), last, Hd, d_last_row, rows, Hd, c.dec_eps, s))) return rc;
         // lm_head with the greedy reduction in its epilogue: logits stay in LDS, the head combines per-tile partials.
         // Which greedy epilogue the mode asks for -- forced | candidates (masked or not) | masked | plain -- and what it reads, once for
         // both weight formats: `launch(a, tag)` runs `a` with epilogue EPIS[tag] of its format.
@@ -1551,9 +1559,117 @@ struct RecModel : RecBase {
         return prefill_fan(tiles, grid_hw, n_images, input_ids, seq_offsets, leads.data(), n_seqs, fan_offsets, fan_slots, s);
     }
 
-    // The body of both prefills. fan_offsets == nullptr: surya_rec_prefill, one slot per sequence.
+    // ---------------------------------------------------------------------------------------- prompt store
+    // Prompts that outlive their slots (surya_rec_prefill_keep / surya_rec_restore; kv_store.h): [K | V][layer][kv_head][store_cap][D] and
+    // the hidden rows [store_cap][dec_hidden], in one lazily allocated block. store_live is the host's table of entries, first -> len.
+    // Decode steps never read the store, so no captured step holds one of its addresses and growing it drops none.
+    DevBlock store;
+    T *store_k = nullptr, *store_v = nullptr, *store_h = nullptr;
+    int store_cap = 0;
+    std::map<int, int> store_live;
+    static bool store_free(const std::map<int, int>& live, int first, int len) {      // [first, first + len) touches no entry of `live`
+        auto it = live.lower_bound(first);
+        if (it != live.end() && it->first < first + len) return false;
+        if (it == live.begin()) return true;
+        --it;                                               // the entry below: it must end at or before `first`
+        return it->first + it->second <= first;
+    }
+    int reserve_prompts(int rows, hipStream_t s) override {
+        if (rows < 0) return SA_ERR_ARG;
+        if (rows <= store_cap) return SA_OK;
+        const size_t runs = (size_t)c.dec_layers * c.dec_kv_heads, row_b = (size_t)c.dec_head_dim * sizeof(T), hid_b = (size_t)c.dec_hidden * sizeof(T);
+        Carve cv;
+        const size_t o_k = cv.take(runs * rows * row_b), o_v = cv.take(runs * rows * row_b), o_h = cv.take((size_t)rows * hid_b);
+        DevBlock nb;
+        int rc = nb.alloc(cv.off, 0);
+        if (rc) return rc;
+        if (store_cap > 0) {      // every run's old rows to the front of its new run, in stream order; then nothing in flight reads the old block
+            const size_t old_run = (size_t)store_cap * row_b, new_run = (size_t)rows * row_b;
+            rc = (int)hipMemcpy2DAsync(nb.dev + o_k, new_run, store_k, old_run, old_run, runs, hipMemcpyDeviceToDevice, s);
+            if (!rc) rc = (int)hipMemcpy2DAsync(nb.dev + o_v, new_run, store_v, old_run, old_run, runs, hipMemcpyDeviceToDevice, s);
+            if (!rc) rc = (int)hipMemcpyAsync(nb.dev + o_h, store_h, (size_t)store_cap * hid_b, hipMemcpyDeviceToDevice, s);
+        }
+        if (!rc) rc = (int)hipDeviceSynchronize();
+        if (rc) { nb.release(); return rc; }
+        store.release();
+        store = nb;
+        store_k = reinterpret_cast<T*>(nb.dev + o_k); store_v = reinterpret_cast<T*>(nb.dev + o_v); store_h = reinterpret_cast<T*>(nb.dev + o_h);
+        store_cap = rows;
+        return SA_OK;
+    }
+    // surya_rec_prefill_keep: the ranges are checked here, before anything is enqueued; the table changes once the launches are out.
+    int prefill_keep(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
+                     const int32_t* slot_ids, int n_seqs, const int32_t* keep_first, hipStream_t s) override {
+        if (n_seqs <= 0) return SA_OK;
+        if (n_seqs > c.max_slots) return SA_ERR_ARG;
+        if (kv8) return SA_ERR_STATE;                       // the store holds bf16 / fp16 / fp32 rows only
+        std::map<int, int> live = store_live;
+        for (int i = 0; i < n_seqs; ++i) {
+            const int f = keep_first[i], L = seq_offsets[i + 1] - seq_offsets[i];
+            if (f == -1) continue;
+            if (f < 0 || L <= 0 || L > store_cap || f > store_cap - L || !store_free(live, f, L)) return SA_ERR_ARG;
+            live[f] = L;
+        }
+        if (live.size() == store_live.size()) keep_first = nullptr;      // nothing named: surya_rec_prefill
+        const int rc = prefill_fan(tiles, grid_hw, n_images, input_ids, seq_offsets, slot_ids, n_seqs, nullptr, nullptr, s, keep_first);
+        if (!rc) store_live.swap(live);
+        return rc;
+    }
+    // surya_rec_restore: everything about the entries and the fans is checked here, before anything is enqueued or changed.
+    int restore(const int32_t* first, const int32_t* fan_offsets, const int32_t* fan_slots, int n, hipStream_t s) override {
+        if (n <= 0) return SA_OK;
+        if (n > c.max_slots) return SA_ERR_ARG;
+        if (kv8) return SA_ERR_STATE;
+        if (fan_offsets[0] != 0) return SA_ERR_ARG;
+        for (int i = 0; i < n; ++i) {
+            if (fan_offsets[i + 1] <= fan_offsets[i] || fan_offsets[i + 1] > c.max_slots) return SA_ERR_ARG;
+            if (beam > 0 && fan_offsets[i + 1] - fan_offsets[i] != 1) return SA_ERR_ARG;           // beam search owns whole groups and forks on its own
+            if (!store_live.count(first[i])) return SA_ERR_ARG;
+        }
+        const int F = fan_offsets[n];
+        if (check_slots(fan_slots, F, [&](int j) { return beam == 0 || (fan_slots[j] % beam == 0 && fan_slots[j] + beam <= c.max_slots); }))
+            return SA_ERR_ARG;
+        if (h_len.size() < (size_t)c.max_slots) h_len.resize(c.max_slots, 0);
+        std::vector<int> lens(n), f_lens, f_first;
+        for (int i = 0; i < n; ++i) {
+            lens[i] = store_live[first[i]];
+            for (int j = fan_offsets[i]; j < fan_offsets[i + 1]; ++j) {
+                for (int b = 0; b < std::max(beam, 1); ++b) h_len[fan_slots[j] + b] = lens[i];
+                f_lens.push_back(lens[i]); f_first.push_back(first[i]);
+            }
+        }
+        int rc;
+        st.begin();
+        const int* d_first = st.put(first, n);
+        const int* d_lens = st.put(lens);
+        const int* d_foff = st.put(fan_offsets, n + 1);
+        const int* d_fslots = st.put(fan_slots, F);
+        const int* d_flens = st.put(f_lens);
+        const int* d_ffirst = st.put(f_first);
+        if (!d_first || !d_lens || !d_foff || !d_fslots || !d_flens || !d_ffirst) return SA_ERR_NOMEM;
+        if ((rc = st.flush(s))) return rc;
+        hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(F, 256)), dim3(256), 0, s, d_fslots, d_flens, kv_len, F);
+        if ((rc = launch_kv_restore<T>(kcache, vcache, store_k, store_v, d_first, d_lens, d_foff, d_fslots, n, F, c.dec_layers, c.max_slots,
+                                       c.dec_kv_heads, c.max_kv_len, c.dec_head_dim, store_cap, s))) return rc;
+        if ((rc = heads(F, d_ffirst, d_fslots, 0, 0, false, s, false, store_h)) || beam == 0) return rc;
+        return beam_step(d_fslots, 1, n, 0, 1, s);          // the B best first tokens, and the prompt's rows to the group's other slots
+    }
+    int drop_prompts(const int32_t* first, int n) override {
+        std::set<int> named;
+        for (int i = 0; i < n; ++i)
+            if (!store_live.count(first[i]) || !named.insert(first[i]).second) return SA_ERR_ARG;
+        for (int f : named) store_live.erase(f);
+        return SA_OK;
+    }
+    int prompt_store_info(int32_t* cap_rows, int32_t* live_entries) override {
+        *cap_rows = store_cap; *live_entries = (int32_t)store_live.size();
+        return SA_OK;
+    }
+
+    // The body of both prefills. fan_offsets == nullptr: surya_rec_prefill, one slot per sequence; with keep_first, surya_rec_prefill_keep.
     int prefill_fan(const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids, const int32_t* seq_offsets,
-                    const int32_t* slot_ids, int n_seqs, const int32_t* fan_offsets, const int32_t* fan_slots, hipStream_t s) {
+                    const int32_t* slot_ids, int n_seqs, const int32_t* fan_offsets, const int32_t* fan_slots, hipStream_t s,
+                    const int32_t* keep_first = nullptr) {
         if (n_seqs <= 0) return SA_OK;
         if (n_seqs > c.max_slots) return SA_ERR_ARG;
         const int Ttot = seq_offsets[n_seqs];
@@ -1605,7 +1721,8 @@ struct RecModel : RecBase {
         const int* d_slots = st_small.put(slot_ids, n_seqs);
         const int* d_lens = st_small.put(lens);
         const int* d_last = st_small.put(last_row);
-        if (!d_last) return SA_ERR_NOMEM;
+        const int* d_keep = keep_first ? st_small.put(keep_first, n_seqs) : nullptr;
+        if (!d_last || (keep_first && !d_keep)) return SA_ERR_NOMEM;
         if ((rc = st_small.flush(s))) return rc;
         // token embeddings for non-image positions
         {
@@ -1639,6 +1756,10 @@ struct RecModel : RecBase {
             if ((rc = st.flush(s))) return rc;
             hipLaunchKernelGGL(set_slot_state_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, s, d_slots, d_lens, kv_len, n_seqs);
             if ((rc = decoder_layers_prefill(Ttot, d_tok_slot, d_tok_pos, &d_sg, (int)sg.tile_seg.size(), s))) return rc;
+            // kept prompts: their cache rows and the hidden row the head pass is about to read, while dx still holds it (kv_keep_kernel)
+            if (keep_first && (rc = launch_kv_keep<T>(kcache, vcache, store_k, store_v, d_slots, d_keep, d_lens, n_seqs, c.dec_layers, c.max_slots,
+                                                      c.dec_kv_heads, c.max_kv_len, c.dec_head_dim, store_cap, dx, d_last, store_h, c.dec_hidden,
+                                                      Ttot, s))) return rc;
             if ((rc = heads(n_seqs, d_last, d_slots, 0, 0, false, s)) || beam == 0) return rc;
             return beam_step(d_slots, 1, n_seqs, 0, 1, s);   // the B best first tokens, and the prompt's rows to the group's other slots
         }

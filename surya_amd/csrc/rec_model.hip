@@ -194,6 +194,27 @@ int surya_rec_copy_kv_rows(surya_rec* h, int slot, int rows, void* k_out, void* 
     if (!h) return SA_ERR_ARG;
     return h->impl->copy_kv_rows(slot, rows, k_out, v_out, (hipStream_t)stream);
 }
+int surya_rec_reserve_prompts(surya_rec* h, int rows, void* stream) {
+    if (!h) return SA_ERR_ARG;
+    return h->impl->reserve_prompts(rows, (hipStream_t)stream);
+}
+int surya_rec_prefill_keep(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, const int32_t* input_ids,
+                           const int32_t* seq_offsets, const int32_t* slot_ids, int n_seqs, const int32_t* keep_first, void* stream) {
+    if (!h || !input_ids || !seq_offsets || !slot_ids || !keep_first || (n_images > 0 && !grid_hw)) return SA_ERR_ARG;
+    return h->impl->prefill_keep(tiles, grid_hw, n_images, input_ids, seq_offsets, slot_ids, n_seqs, keep_first, (hipStream_t)stream);
+}
+int surya_rec_restore(surya_rec* h, const int32_t* first, const int32_t* fan_offsets, const int32_t* fan_slots, int n, void* stream) {
+    if (!h || (n > 0 && (!first || !fan_offsets || !fan_slots))) return SA_ERR_ARG;
+    return h->impl->restore(first, fan_offsets, fan_slots, n, (hipStream_t)stream);
+}
+int surya_rec_drop_prompts(surya_rec* h, const int32_t* first, int n) {
+    if (!h || n < 0 || (n > 0 && !first)) return SA_ERR_ARG;
+    return h->impl->drop_prompts(first, n);
+}
+int surya_rec_prompt_store_info(surya_rec* h, int32_t* cap_rows, int32_t* live_entries) {
+    if (!h || !cap_rows || !live_entries) return SA_ERR_ARG;
+    return h->impl->prompt_store_info(cap_rows, live_entries);
+}
 int surya_rec_encode_ahead(surya_rec* h, const float* tiles, const int32_t* grid_hw, int n_images, void* stream) {
     if (!h || n_images < 0 || (n_images > 0 && (!tiles || !grid_hw))) return SA_ERR_ARG;      // n_images == 0: discard (see the header)
     return h->impl->encode_ahead(tiles, grid_hw, n_images, (hipStream_t)stream);
@@ -798,6 +819,20 @@ int surya_op_rec_kv_fanout(int dtype, void* kcache, void* vcache, const int32_t*
                            void* stream) {
     const sa::RecKvFanoutOp a{kcache, vcache, fan_src, fan_off, fan_dst, fan_len, n_seqs, n_dst, layers, slots, kv_heads, max_kv_len, head_dim};
     return rec_dispatch(dtype, sa::REC_OP_KV_FANOUT, &a, stream);
+}
+int surya_op_rec_kv_keep(int dtype, const void* kcache, const void* vcache, void* store_k, void* store_v, const int32_t* slot,
+                         const int32_t* first, const int32_t* len, int n, int layers, int slots, int kv_heads, int max_kv_len, int head_dim,
+                         int cap_rows, const void* x, const int32_t* last_row, void* hid, int hidden, int x_rows, void* stream) {
+    const sa::RecKvKeepOp a{kcache, vcache, store_k, store_v, slot, first, len, n, layers, slots, kv_heads, max_kv_len, head_dim, cap_rows,
+                            x, last_row, hid, hidden, x_rows};
+    return rec_dispatch(dtype, sa::REC_OP_KV_KEEP, &a, stream);
+}
+int surya_op_rec_kv_restore(int dtype, void* kcache, void* vcache, const void* store_k, const void* store_v, const int32_t* first,
+                            const int32_t* len, const int32_t* fan_off, const int32_t* fan_dst, int n, int n_dst, int layers, int slots,
+                            int kv_heads, int max_kv_len, int head_dim, int cap_rows, void* stream) {
+    const sa::RecKvRestoreOp a{kcache, vcache, store_k, store_v, first, len, fan_off, fan_dst, n, n_dst, layers, slots, kv_heads, max_kv_len,
+                               head_dim, cap_rows};
+    return rec_dispatch(dtype, sa::REC_OP_KV_RESTORE, &a, stream);
 }
 static int lexicon_op_args(const surya_rec_lexicon_args* g, sa::LexiconArgs& a) {
     if (!g || !g->edge_off || !g->edge_tok || !g->edge_next || !g->state_flags || !g->table || !g->slot_state || !g->slot_mask || g->words <= 0 ||

@@ -5,6 +5,7 @@
 #include "kernels.h"
 #include "beam.h"
 #include "kv_fanout.h"
+#include "kv_store.h"
 #include "boost.h"
 
 namespace sa {
@@ -20,8 +21,13 @@ struct RecEmbedOp {
 };
 struct RecKvForkOp { void *kc, *vc; const int *fork_src, *base, *len; int rows, layers, slots, nkv, Tmax, D; };
 struct RecKvFanoutOp { void *kc, *vc; const int *fan_src, *fan_off, *fan_dst, *fan_len; int n_seqs, n_dst, layers, slots, nkv, Tmax, D; };
+struct RecKvKeepOp {
+    const void *kc, *vc; void *sk, *sv; const int *slot, *first, *len; int n, layers, slots, nkv, Tmax, D, cap; const void* x; const int* last_row;
+    void* hid; int H, x_rows;
+};
+struct RecKvRestoreOp { void *kc, *vc; const void *sk, *sv; const int *first, *len, *fan_off, *fan_dst; int n, n_dst, layers, slots, nkv, Tmax, D, cap; };
 enum { REC_OP_RMS_ROWS = 0, REC_OP_ROWS, REC_OP_ROPE_TABLE, REC_OP_ROPE_KV, REC_OP_REDUCE, REC_OP_EMBED, REC_OP_HEAD, REC_OP_KV_FORK, REC_OP_BOOST_HEAD,
-       REC_OP_KV_FANOUT };
+       REC_OP_KV_FANOUT, REC_OP_KV_KEEP, REC_OP_KV_RESTORE };
 
 template <typename T> constexpr bool rec_mx_ok() { return std::is_same<T, bf16_t>::value; }     // the MXFP8 copies exist beside bf16 only
 
@@ -142,6 +148,18 @@ int rec_op(const RecKvFanoutOp& a, hipStream_t s) {
 }
 
 template <typename T>
+int rec_op(const RecKvKeepOp& a, hipStream_t s) {
+    return launch_kv_keep<T>((const T*)a.kc, (const T*)a.vc, (T*)a.sk, (T*)a.sv, a.slot, a.first, a.len, a.n, a.layers, a.slots, a.nkv, a.Tmax, a.D, a.cap,
+                             (const T*)a.x, a.last_row, (T*)a.hid, a.H, a.x_rows, s);
+}
+
+template <typename T>
+int rec_op(const RecKvRestoreOp& a, hipStream_t s) {
+    return launch_kv_restore<T>((T*)a.kc, (T*)a.vc, (const T*)a.sk, (const T*)a.sv, a.first, a.len, a.fan_off, a.fan_dst, a.n, a.n_dst, a.layers, a.slots,
+                                a.nkv, a.Tmax, a.D, a.cap, s);
+}
+
+template <typename T>
 int rec_op_any(int op, const void* a, hipStream_t s) {
     switch (op) {
         case REC_OP_RMS_ROWS: return rec_op<T>(*static_cast<const RecRmsRowsOp*>(a), s);
@@ -154,6 +172,8 @@ int rec_op_any(int op, const void* a, hipStream_t s) {
         case REC_OP_KV_FORK: return rec_op<T>(*static_cast<const RecKvForkOp*>(a), s);
         case REC_OP_BOOST_HEAD: return rec_op<T>(*static_cast<const surya_rec_boost_head_args*>(a), s);
         case REC_OP_KV_FANOUT: return rec_op<T>(*static_cast<const RecKvFanoutOp*>(a), s);
+        case REC_OP_KV_KEEP: return rec_op<T>(*static_cast<const RecKvKeepOp*>(a), s);
+        case REC_OP_KV_RESTORE: return rec_op<T>(*static_cast<const RecKvRestoreOp*>(a), s);
     }
     return SA_ERR_ARG;
 }

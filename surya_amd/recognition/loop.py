@@ -85,10 +85,25 @@ class DeviceLoop:
     beams are finished, when its token budget is reached (also right after the prefill), or when the repeat rule fires on the
     best-scored live beam. `on_done(line, hypotheses)` gets a list of BeamHypothesis, finished ones by log_prob descending, then the
     unfinished ones; empty beams (fewer candidates than slots) are dropped. The mode is switched on for the run and off on the way
-    out, also after an exception. beam=None: set_beam / read_beam / wait_beam are never called -- a model without them works."""
+    out, also after an exception. beam=None: set_beam / read_beam / wait_beam are never called -- a model without them works.
+
+    The prompt store (`store="keep"` or `store="restore"`; None: prefill_keep / restore are never called -- a model without them works):
+    every admitted dict carries "store_first", one first store row per prompt. A loop run handles either fresh lines or restored lines,
+    never both.
+      keep     the lines are fresh (tiles, look-ahead encoder and prefill batching as ever), prefilled with the model's prefill_keep,
+               which leaves every prompt in the store at its row, and a line stops after the prefill's token: the loop only encodes.
+               Not with candidate fans.
+      restore  the lines carry no tiles ("tiles" / "tile_offs" may be None): prefill_batch's counterpart calls the model's
+               restore(first rows, one slot list per line) for as many lines as there are free slots / groups / candidate fans, behind
+               the same set_slot_* and set_forced_tokens calls, and reads the prefill's outputs as ever. There is no encoder, no
+               look-ahead queue, no max_prefill chunking and no `min_prefill_ratio` wait: a landing is a copy, so any free slot is
+               refilled at once. A store row may be admitted once per run (a line restored twice in one call would be two lines)."""
 
     def __init__(self, model, eos, pad, nop, slots, overall_max_tokens, min_prefill_ratio, on_done=None, on_flush=None, feed=None,
-                 alternatives=False, forced=False, beam=None, fan=False):
+                 alternatives=False, forced=False, beam=None, store=None, fan=False):
+        assert store in (None, "keep", "restore"), "store is None, 'keep' or 'restore'"
+        assert not (store == "keep" and (fan or beam)), "prompts are kept by plain greedy prefills, not by candidate fans or beam groups"
+        self.store, self.store_first = store, []               # per line: the first store row of its prompt
         self.beam = int(beam) if beam else 0
         if self.beam:
             assert 2 <= self.beam <= SA_MAX_BEAMS and slots >= self.beam, "beam width must be 2..4 and fit the slots"
@@ -139,6 +154,8 @@ class DeviceLoop:
         # lines runs on the model's second stream while the current lines decode; prefill then only scatters the finished
         # embeddings and runs the decoder over the prompts. Scheduling decisions (which lines, which slots, when) are unchanged.
         self.look_ahead, self.ahead = settings.RECOGNITION_ENCODE_AHEAD, deque()      # ahead: the encoded ids, in id order
+        if store == "restore":
+            self.look_ahead, self.max_prefill = False, float("inf")      # nothing to encode, nothing to chunk
         self.ahead_cap = max(model.c.max_prefill_tokens, model.c.max_slots)
         self.merge2 = model.cfg.encoder.spatial_merge_size ** 2
         self.inflight, self.ring = None, 0                     # the decode call whose outputs were not read yet: (steps, ring half)
@@ -189,12 +206,18 @@ class DeviceLoop:
             assert len(fi) == m, "forced_ids: one id list per prompt"
             mt = np.asarray([len(ids) or b for ids, b in zip(fi, mt.tolist())], np.int64)      # the budget is the list's length
         assert int(mt.max()) <= self.overall_max_tokens, "a fed line's token budget exceeds the call's overall_max_tokens"
+        if self.store:
+            first = [int(f) for f in d["store_first"]]
+            assert len(first) == m and all(f >= 0 for f in first), "store_first: one store row per prompt"
+            assert len(set(first)) == m and set(first).isdisjoint(self.store_first), "a store row is admitted once per run"
+            self.store_first.extend(first)
         self.grids.extend(d["grids"])
         self.prompt_ids.extend(d["prompt_ids"])
         self.predicted_tokens.extend([] for _ in range(m))
         self.scores.extend([] for _ in range(m))
-        self.chunk_tiles.append(d["tiles"]); self.chunk_offs.append(d["tile_offs"]); self.chunk_base.append(base)
-        self.line_chunk = np.concatenate([self.line_chunk, np.full(m, len(self.chunk_base) - 1, np.int64)])
+        self.chunk_tiles.append(d.get("tiles")); self.chunk_offs.append(d.get("tile_offs")); self.chunk_base.append(base)
+        # (restored lines have no tile tensor whose boundary a prefill could not cross: they all count as one chunk)
+        self.line_chunk = np.concatenate([self.line_chunk, np.full(m, 0 if self.store == "restore" else len(self.chunk_base) - 1, np.int64)])
         self.batch_bboxes = np.concatenate([self.batch_bboxes, np.zeros((rows, self.overall_max_tokens, 6), np.float32)])
         self.tok_mat = np.concatenate([self.tok_mat, np.zeros((rows, self.cap), np.int64)])
         self.sc_mat = np.concatenate([self.sc_mat, np.zeros((rows, self.cap), np.float32)])
@@ -409,7 +432,12 @@ class DeviceLoop:
     def _prefill(self, take, grids, prompt_ids, slots):
         """The model's prefill of lines `take` into `slots` (fan: one slot list per line, prefill_shared): from the look-ahead queue, whose
         head they are, or with their own tiles."""
+        if self.store == "restore":                    # no tiles, no encoder: the prompts come out of the store
+            return self.model.restore([self.store_first[i] for i in take], slots if self.fan else [[s] for s in slots])
         prefill = self.model.prefill_shared if self.fan else self.model.prefill
+        if self.store == "keep":
+            first = [self.store_first[i] for i in take]
+            prefill = lambda tiles, grids_, ids_, slots_: self.model.prefill_keep(tiles, grids_, ids_, slots_, first)
         if self.look_ahead:
             for i in take:
                 assert self.ahead.popleft() == i
@@ -487,6 +515,8 @@ class DeviceLoop:
         go_on = (first != self.eos) & (first != self.nop)
         if self.forced:
             go_on &= self.max_tok[ids_] > 1                         # a one-id list is complete with the prefill's token
+        if self.store == "keep":
+            go_on[:] = False                                        # the prompt is in the store: that was all
         for p_id, s, go in zip(take, slots, go_on.tolist()):
             if go:                                                  # prefill stop rule (reference :559-563)
                 self.slot_line[s] = p_id
@@ -556,7 +586,8 @@ class DeviceLoop:
                 if self.feed_done:
                     break
                 continue
-            if self.queue and (self.num_empty / self.slots) > self.min_prefill_ratio and self._fits():
+            if self.queue and self._fits() and ((self.num_empty / self.slots) > self.min_prefill_ratio or
+                                                (self.store == "restore" and self.num_empty > 0)):
                 if self.inflight:
                     self.absorb(self.inflight)
                     self.inflight = None

@@ -422,6 +422,55 @@ class HipRecModel:
                                                   L.np_ptr(foffs), L.np_ptr(slots), C.c_int(len(fan_slots)), self._stream),
                 "surya_rec_prefill_shared")
 
+    # ---- the prompt store (surya_rec_reserve_prompts ...): prompts kept on the device across calls; EncodedLines (encoded.py) hands out its rows
+    def reserve_prompts(self, rows: int):
+        """The store holds at least `rows` rows afterwards; growing keeps the live entries' bytes."""
+        torch.cuda.set_device(self.device)
+        L.check(self.lib.surya_rec_reserve_prompts(self.handle, C.c_int(int(rows)), self._stream), "surya_rec_reserve_prompts")
+
+    def prefill_keep(self, tiles: torch.Tensor, grid_hw, input_ids: Sequence[Sequence[int]], slot_ids: Sequence[int], keep_first: Sequence[int]):
+        """`prefill` that also keeps prompts (surya_rec_prefill_keep): sequence i with keep_first[i] >= 0 leaves its prompt rows and its last
+        hidden row in the store at rows [keep_first[i], keep_first[i] + len(input_ids[i])). Not with the fp8 KV cache."""
+        torch.cuda.set_device(self.device)
+        grid = np.ascontiguousarray(np.asarray(grid_hw, np.int32).reshape(-1, 2))
+        offs = np.zeros(len(input_ids) + 1, np.int32)
+        offs[1:] = np.cumsum([len(s) for s in input_ids])
+        flat = np.ascontiguousarray(np.concatenate([np.asarray(s, np.int32) for s in input_ids]))
+        slots = np.ascontiguousarray(np.asarray(slot_ids, np.int32))
+        keep = np.ascontiguousarray(np.asarray(keep_first, np.int32))
+        if keep.shape != slots.shape:
+            raise ValueError("prefill_keep: one store row (or -1) per sequence")
+        if tiles is not None:
+            assert tiles.is_cuda and tiles.dtype == torch.float32 and tiles.is_contiguous()
+            assert tiles.shape[0] == int((grid[:, 0] * grid[:, 1]).sum()) and tiles.shape[1] == self.cfg.encoder.patch_dim
+        L.check(self.lib.surya_rec_prefill_keep(self.handle, L.ptr(tiles), L.np_ptr(grid), C.c_int(len(grid)), L.np_ptr(flat), L.np_ptr(offs),
+                                                L.np_ptr(slots), C.c_int(len(slots)), L.np_ptr(keep), self._stream), "surya_rec_prefill_keep")
+
+    def restore(self, first: Sequence[int], fan_slots: Sequence[Sequence[int]]):
+        """Land kept prompts in slots (surya_rec_restore): entry first[i] goes to every slot of fan_slots[i], each of which then holds the
+        prompt's rows, its length and a first token of its own, as after `prefill` / `prefill_shared`. With beam search on every list is
+        one lead slot. Not with the fp8 KV cache."""
+        torch.cuda.set_device(self.device)
+        if len(fan_slots) != len(first):
+            raise ValueError("restore: one slot list per entry")
+        f = np.ascontiguousarray(np.asarray(first, np.int32))
+        foffs = np.zeros(len(fan_slots) + 1, np.int32)
+        foffs[1:] = np.cumsum([len(x) for x in fan_slots])
+        slots = np.ascontiguousarray([s for x in fan_slots for s in x], np.int32) if foffs[-1] else np.zeros(1, np.int32)
+        L.check(self.lib.surya_rec_restore(self.handle, L.np_ptr(f), L.np_ptr(foffs), L.np_ptr(slots), C.c_int(len(f)), self._stream),
+                "surya_rec_restore")
+
+    def drop_prompts(self, first: Sequence[int]):
+        """Forget entries (host bookkeeping only)."""
+        f = np.ascontiguousarray(np.asarray(first, np.int32))
+        L.check(self.lib.surya_rec_drop_prompts(self.handle, L.np_ptr(f), C.c_int(len(f))), "surya_rec_drop_prompts")
+
+    def prompt_store_info(self):
+        """(capacity in rows, live entries) of the store. A test hook."""
+        cap, live = C.c_int32(0), C.c_int32(0)
+        L.check(self.lib.surya_rec_prompt_store_info(self.handle, C.byref(cap), C.byref(live)), "surya_rec_prompt_store_info")
+        return int(cap.value), int(live.value)
+
     def encode_ahead(self, tiles: torch.Tensor, grid_hw):
         """Encode the images of the next prompts on the library's low-priority stream (overlaps with decode steps); the
         following prefill(None, ...) calls consume the embeddings in this order."""

@@ -592,6 +592,8 @@ class RecognitionPredictor(BasePredictor):
         elif self._beam is not None:
             more, extra = {"beam": self._beam}, None
         extra = options.option_extra(first) or extra
+        if first.get("store_mode") is not None:               # encode() / EncodedLines: the lines leave their prompts in the store, or come out of it
+            more = dict(more, store=first["store_mode"])
         loop = DeviceLoop(self.model, proc.eos_token_id, proc.pad_token_id, proc.no_output_token,
                           min(recognition_batch_size, self.model.max_slots), overall_max_tokens, self.min_prefill_ratio,
                           on_done=on_done, on_flush=on_flush, feed=feed, **more)
@@ -762,6 +764,15 @@ class RecognitionPredictor(BasePredictor):
         together with `top_k` (the alternatives arrays serve the beams), or on a model running MXFP8 decode weights or the fp8 KV cache;
         NotImplementedError with `shard_lines`, `shard_pages` or a process group. With `det_predictor` a beam call detects all pages
         before it recognises (no streamed detection). `align` is unaffected."""
+        top_k, beam, pattern, lexicon, boost_words, boost_weight = self._checked_modes()
+        with self._modes(top_k, beam):
+            return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
+                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
+                                        pattern, lexicon, boost_words, boost_weight)
+
+    def _checked_modes(self) -> tuple:
+        """The attributes a reading call runs under -- (top_k, beam_width, pattern, lexicon, boost_words, boost_weight) -- validated as
+        `__call__` documents, before any device work."""
         top_k = self.top_k
         if top_k is not None and (isinstance(top_k, bool) or not isinstance(top_k, int) or not 2 <= top_k <= 4):
             raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
@@ -783,10 +794,7 @@ class RecognitionPredictor(BasePredictor):
                 raise ValueError("boost_words needs boost_weight, the boost in logit units (a finite float >= 0); it has no default")
             if isinstance(boost_weight, bool) or not isinstance(boost_weight, (int, float)) or not 0 <= boost_weight < float("inf"):
                 raise ValueError(f"boost_weight must be a finite float >= 0, got {boost_weight!r}")
-        with self._modes(top_k, beam):
-            return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                                        pattern, lexicon, boost_words, boost_weight)
+        return top_k, beam, pattern, lexicon, boost_words, boost_weight
 
     @contextmanager
     def _modes(self, top_k=None, beam=None):
@@ -877,28 +885,38 @@ class RecognitionPredictor(BasePredictor):
         vocabulary. Not with `shard_lines` or a process group: multi-rank alignment is not supported. Allow-lists and `top_k`
         do not apply to an aligned call, and a set `pattern` raises ValueError: the text is given, there is nothing to constrain."""
         given, task_names = self._forced_call_checks("align", "texts", "text lists", images, texts, task_names, bboxes, polygons)
+        forced = self._align_forced(texts, given, task_names)
+        with self._modes(), gc_paused():
+            return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
+
+    def _align_forced(self, texts, given, task_names) -> list:
+        """The forced id list of every line of an `align` call, in page order; `given` holds one entry per line and image."""
         forced = []
         for i, (tx, gv, task) in enumerate(zip(texts, given, task_names)):
             if len(tx) != len(gv):
                 raise ValueError(f"image {i} has {len(gv)} lines but {len(tx)} texts")
             for j, text in enumerate(tx):
                 forced.append(self._forced_line_ids(f"image {i}, line {j}", text, task))
-        with self._modes(), gc_paused():
-            return self._align(convert_if_not_rgb(images), forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words)
+        return forced
 
     def _align(self, images, forced, task_names, bboxes, polygons, recognition_batch_size, math_mode, return_words) -> List[OCRResult]:
+        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
+        return self._align_flat(images, flat, forced, recognition_batch_size, return_words, lambda f: self.prepare_lines(f, math_mode))
+
+    def _align_flat(self, images, flat, forced, recognition_batch_size, return_words, prepare) -> List[OCRResult]:
+        """`align` from the sliced lines on. `images`: anything with `.size` per page; `prepare(flat)`: the loop's dict of the lines
+        (prepare_lines, or EncodedLines' dict of restored lines, which sorts flat["enc_ids"] with the slices)."""
         t_call = time.perf_counter()
         stamps = self.last_timing = {}
-        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
         if len(flat["slices"]) == 0:
             return []
         flat["forced"], flat["forced_ids"] = True, forced     # by line id like the slices: sorted with them below
         order = sorted(range(len(flat["slices"])), key=lambda i: -flat["slices"][i].shape[1])
-        for key in ("slices", "input_text", "task_names", "forced_ids"):
+        for key in ("slices", "input_text", "task_names", "forced_ids") + (("enc_ids",) if "enc_ids" in flat else ()):
             flat[key] = [flat[key][i] for i in order]
         with AssemblyHandover(self, flat, order, False, return_words) as hand:
             t0 = time.perf_counter()
-            prep = self.prepare_lines(flat, math_mode)
+            prep = prepare(flat)
             t1 = time.perf_counter()
             self.generate(prep, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush)
             stamps["prepare_ms"] = (t1 - t0) * 1e3
@@ -921,6 +939,12 @@ class RecognitionPredictor(BasePredictor):
         several prefills); a set `pattern` / `lexicon` / `boost_words` raises ValueError too. Not with `shard_lines` or a process group.
         `rectify` applies; `top_k` and `beam_width` do not."""
         given, task_names = self._forced_call_checks("rank", "candidates", "candidate lists", images, candidates, task_names, bboxes, polygons)
+        lines = self._rank_candidates(candidates, given, task_names, recognition_batch_size)
+        with self._modes(), gc_paused():
+            return self._rank(convert_if_not_rgb(images), lines, task_names, bboxes, polygons, recognition_batch_size, math_mode)
+
+    def _rank_candidates(self, candidates, given, task_names, recognition_batch_size) -> list:
+        """Per line of a `rank` call, in page order: (its texts, its distinct id lists, text index -> distinct index)."""
         slots = recognition_batch_size if recognition_batch_size is not None else self.get_batch_size()
         slots = min(slots, self.model.max_slots)
         lines = []                                            # per line: (its texts, its distinct id lists, text index -> distinct index)
@@ -941,23 +965,26 @@ class RecognitionPredictor(BasePredictor):
                     raise ValueError(f"image {i}, line {j}: {len(distinct)} distinct candidates exceed the {slots} slots in use "
                                      f"(recognition_batch_size / the model's slots)")
                 lines.append((list(texts), distinct, index))
-        with self._modes(), gc_paused():
-            return self._rank(convert_if_not_rgb(images), lines, task_names, bboxes, polygons, recognition_batch_size, math_mode)
+        return lines
 
     def _rank(self, images, lines, task_names, bboxes, polygons, recognition_batch_size, math_mode) -> List[RankResult]:
+        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
+        return self._rank_flat(images, flat, lines, recognition_batch_size, lambda f: self.prepare_lines(f, math_mode))
+
+    def _rank_flat(self, images, flat, lines, recognition_batch_size, prepare) -> List[RankResult]:
+        """`rank` from the sliced lines on; `images` and `prepare` as in `_align_flat`."""
         t_call = time.perf_counter()
         stamps = self.last_timing = {}
-        flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=None, task_names=task_names)
         n = len(flat["slices"])
         assert n == len(lines)
         scored = {}                                           # sorted position -> per distinct candidate (greedy ids, probabilities, log-probabilities)
         if n:
             flat["forced_ids"], flat["fan"] = [ln[1] for ln in lines], True      # by line id like the slices: sorted with them below
             order = sorted(range(n), key=lambda i: -flat["slices"][i].shape[1])
-            for key in ("slices", "input_text", "task_names", "forced_ids"):
+            for key in ("slices", "input_text", "task_names", "forced_ids") + (("enc_ids",) if "enc_ids" in flat else ()):
                 flat[key] = [flat[key][i] for i in order]
             t0 = time.perf_counter()
-            prep = self.prepare_lines(flat, math_mode)
+            prep = prepare(flat)
             t1 = time.perf_counter()
             self.generate(prep, recognition_batch_size, on_done=scored.__setitem__)
             stamps.update(prepare_ms=(t1 - t0) * 1e3, device_loop_ms=(time.perf_counter() - t1) * 1e3)
@@ -981,6 +1008,21 @@ class RecognitionPredictor(BasePredictor):
             start += count
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results
+
+    def encode(self, images: List[Image.Image], task_names: List[str] | None = None, bboxes: List[List[List[int]]] | None = None,
+               polygons: List[List[List[List[int]]]] | None = None, input_text: List[List[str | None]] | None = None,
+               highres_images: List[Image.Image] | None = None, math_mode: bool = True, recognition_batch_size: int | None = None,
+               det_predictor=None):
+        """Encode lines once and keep them on the device: the lines are sliced (honouring `self.rectify`), resized, patchified, run through
+        the vision encoder and prefilled as in `__call__`, and every prompt's KV rows stay in the model's prompt store. The result, an
+        EncodedLines (recognition/encoded.py), reads (`enc.read`), ranks (`enc.rank`) and aligns (`enc.align`) those lines as often as
+        asked, all of them or a subset (`lines=`), with the results of `__call__` / `rank` / `align` on the same inputs bit for bit, and
+        without the encoder and the prefill. It holds device memory (about the prompt's rows per line) until `release()`, the end of its
+        `with` block, or its collection. `highres_images` is accepted and unused, as in `__call__` with bboxes or polygons. ValueError, before
+        any device work, with `det_predictor` (run the detector and pass `polygons=`) and on a model running the fp8 KV cache;
+        NotImplementedError with `shard_lines`, `shard_pages` or a process group."""
+        from .encoded import EncodedLines
+        return EncodedLines.encode(self, images, task_names, bboxes, polygons, input_text, math_mode, recognition_batch_size, det_predictor)
 
     top_k: int | None = None          # alternatives per character (2..4), None = off: RecognitionPredictor.top_k = 3, or on an instance
     _top_k = None                     # the running call's validated top_k (see __call__)
@@ -1059,12 +1101,19 @@ class RecognitionPredictor(BasePredictor):
             if polygons is not None:
                 assert len(images) == len(polygons), "You need to pass in one list of polygons for each image"
             flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=input_text, task_names=task_names)
+        return self._read_flat(images, flat, cons, recognition_batch_size, sort_lines, return_words, drop_repeated_text, stamps, t_call,
+                               lambda f: self.prepare_lines(f, math_mode), math_mode)
+
+    def _read_flat(self, images, flat, cons, recognition_batch_size, sort_lines, return_words, drop_repeated_text, stamps, t_call, prepare,
+                   math_mode=True) -> List[OCRResult]:
+        """`_call` from the sliced lines on; `images` and `prepare` as in `_align_flat` (`math_mode` reaches the line-sharded loop only,
+        which prepares its own share)."""
         if len(flat["slices"]) == 0:
             return []
         stamps["slice_ms"] = (time.perf_counter() - t_call) * 1e3
         if self._top_k is not None:
             flat["top_k"] = self._top_k
-        sorted_keys = ("slices", "input_text", "task_names")
+        sorted_keys = ("slices", "input_text", "task_names") + (("enc_ids",) if "enc_ids" in flat else ())
         if cons is not None:                                  # the options' integers are by line id like the slices: sorted with them below
             sorted_keys += options.attach(flat, cons)
 
@@ -1088,7 +1137,7 @@ class RecognitionPredictor(BasePredictor):
                 text_lines = hand.place((ks, hand.assemble([(k, predicted_tokens[k], scores[k], bb[k]) + alt_of(k) for k in ks])) for ks in chunks)
             else:
                 t0 = time.perf_counter()
-                prep = self.prepare_lines(flat, math_mode)
+                prep = prepare(flat)
                 t1 = time.perf_counter()
                 self.generate(prep, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush)
                 stamps["prepare_ms"] = (t1 - t0) * 1e3
