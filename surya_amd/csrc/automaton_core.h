@@ -1,5 +1,5 @@
-// The host-side checks of a sparse automaton in CSR form (edge_off / edge_tok / edge_next), shared by RecModel::set_lexicon and
-// RecModel::set_boost (rec_engine.h) and a plain-C++ build used by the CPU tests (tests/native/automaton_host.cpp). The kernels of
+// The host-side checks of a sparse automaton in CSR form (edge_off / edge_tok / edge_next), shared by RecBase::set_lexicon and
+// RecBase::set_boost (rec_state.h) and a plain-C++ build used by the CPU tests (tests/native/automaton_host.cpp). The kernels of
 // lexicon.h and boost.h read the tables unchecked: these functions are what keeps a bad table from a stray read on the device. No HIP
 // here. Every function returns SA_OK or SA_ERR_ARG and reads nothing outside the ranges it has already checked; the callers have
 // checked the counts (>= 0, n_states >= 1) and the pointers.

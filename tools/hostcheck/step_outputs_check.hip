@@ -1,15 +1,19 @@
-// Host-only check of the arena and mirror arithmetic of csrc/rec_engine.h (Carve, StepOutputs): no GPU, no HIP call. Meant to run under
-// the host sanitizers, which see every byte StepOutputs::wait copies out of a mirror that is exactly host_bytes() long:
+// Host-only check of csrc/rec_state.h: the arena and mirror arithmetic (Carve, StepOutputs) and the engine's pure host checks (the mode
+// exclusion table, slot lists, fans, the prompt store's ranges): no GPU, no HIP call. Meant to run under the host sanitizers, which see
+// every byte StepOutputs::wait copies out of a mirror that is exactly host_bytes() long:
 //
 //   hipcc --offload-arch=gfx950 -std=c++17 -O1 -g -Iinclude -Xarch_host -fsanitize=address,undefined \
 //         tools/hostcheck/step_outputs_check.hip -o /tmp/step_outputs_check && /tmp/step_outputs_check
 //
-// The expected offsets are written out by hand below, per set and field.
+// The expected offsets and verdicts are written out by hand below.
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <memory>
+#include <utility>
 #include <vector>
 
-#include "../../surya_amd/csrc/rec_engine.h"
+#include "../../surya_amd/csrc/rec_state.h"
 
 using sa::Carve;
 using sa::StepOutputs;
@@ -100,6 +104,96 @@ static void check_carve() {
     CHECK(c2.off == part_bytes + bt_bytes + 2 * out_b);
 }
 
+// The exclusion table: row m, column p = "m may not be switched on while p is on", in the order of sa::Mode (masks, alternatives, forced,
+// beam, fp8 KV, MXFP8, patterns, lexicon, boost). The 14 pairs of modes_excluded written out in both directions: 28 ones.
+static void check_exclusions() {
+    static const char* expect[sa::MODES] = {"001000000", "001000001", "110100111", "001011111", "000100000",
+                                            "000100000", "001100001", "001100001", "011100110"};
+    int ones = 0;
+    for (int m = 0; m < sa::MODES; ++m) {
+        const bool none[sa::MODES] = {};
+        CHECK(!sa::modes_excluded(m, none));
+        for (int p = 0; p < sa::MODES; ++p) {
+            bool on[sa::MODES] = {};
+            on[p] = true;
+            CHECK(sa::modes_excluded(m, on) == (expect[m][p] == '1'));
+            CHECK(expect[m][p] == expect[p][m]);
+            ones += expect[m][p] == '1';
+        }
+    }
+    CHECK(ones == 28);
+    bool all[sa::MODES];
+    for (bool& b : all) b = true;
+    for (int m = 0; m < sa::MODES; ++m) CHECK(sa::modes_excluded(m, all));      // every mode has a partner
+}
+
+static void check_store_free() {
+    std::map<int, int> live;
+    CHECK(sa::store_free(live, 0, 1) && sa::store_free(live, 7, 100));         // an empty table
+    live[10] = 5;                                                            // rows 10..14
+    CHECK(sa::store_free(live, 5, 5));                                       // touches it from below
+    CHECK(sa::store_free(live, 15, 3));                                      // ... from above
+    CHECK(!sa::store_free(live, 6, 5));                                      // one row too far: row 10
+    CHECK(!sa::store_free(live, 14, 3));                                     // starts on its last row
+    CHECK(!sa::store_free(live, 11, 2) && !sa::store_free(live, 10, 5));      // inside it, and the entry itself
+    CHECK(!sa::store_free(live, 8, 10));                                     // around it
+    live[20] = 5;                                                            // rows 20..24
+    CHECK(sa::store_free(live, 15, 5));                                      // touches both neighbours
+    CHECK(!sa::store_free(live, 15, 6) && !sa::store_free(live, 14, 6));
+    CHECK(sa::store_free(live, 0, 10) && sa::store_free(live, 25, 1));
+}
+
+static void check_slot_lists() {
+    auto yes = [](int) { return true; };
+    const int32_t ok[] = {0, 3}, high[] = {0, 4}, low[] = {-1}, twice[] = {1, 2, 1}, three[] = {0, 1, 2};
+    CHECK(sa::check_slots(ok, 2, 4, yes) == SA_OK);
+    CHECK(sa::check_slots(ok, 0, 4, yes) == SA_OK);
+    CHECK(sa::check_slots(high, 2, 4, yes) == SA_ERR_ARG && sa::check_slots(high, 2, 5, yes) == SA_OK);      // out of range
+    CHECK(sa::check_slots(low, 1, 4, yes) == SA_ERR_ARG);
+    CHECK(sa::check_slots(twice, 3, 4, yes) == SA_ERR_ARG && sa::check_slots(twice, 2, 4, yes) == SA_OK);    // a repeated slot
+    CHECK(sa::check_slots(three, 3, 4, [](int i) { return i != 2; }) == SA_ERR_ARG);                          // the predicate fails on the last entry
+    CHECK(sa::check_slots(three, 2, 4, [](int i) { return i != 2; }) == SA_OK);
+}
+
+static void check_fan_lists() {
+    auto yes = [](int, int) { return true; };
+    const int32_t off[] = {0, 2, 3}, slots[] = {0, 1, 3};
+    std::vector<std::pair<int, int>> seen;
+    CHECK(sa::check_fans(off, slots, 2, 4, [&](int i, int j) { seen.emplace_back(i, j); return true; }) == SA_OK);
+    CHECK((seen == std::vector<std::pair<int, int>>{{0, 0}, {0, 1}, {1, 2}}));                               // (fan, entry) as the predicate gets them
+    CHECK(sa::check_fans(off, slots, 2, 4, [](int i, int) { return i == 0; }) == SA_ERR_ARG);
+    const int32_t off1[] = {1, 2}, s1[] = {0, 1};
+    CHECK(sa::check_fans(off1, s1, 1, 4, yes) == SA_ERR_ARG);                                                 // a non-zero first offset
+    const int32_t empty[] = {0, 0, 1}, back[] = {0, 2, 1};
+    CHECK(sa::check_fans(empty, slots, 2, 4, yes) == SA_ERR_ARG && sa::check_fans(back, slots, 2, 4, yes) == SA_ERR_ARG);      // an empty fan
+    const int32_t many[] = {0, 3, 5}, s5[] = {0, 1, 2, 3, 0};
+    CHECK(sa::check_fans(many, s5, 2, 4, yes) == SA_ERR_ARG);                                                 // five slots on a handle of four
+    const int32_t full[] = {0, 3, 4}, rep[] = {0, 1, 2, 1};
+    CHECK(sa::check_fans(full, s5, 2, 4, yes) == SA_OK && sa::check_fans(full, rep, 2, 4, yes) == SA_ERR_ARG);      // exactly max_slots; a slot in two fans
+}
+
+static void check_keep_ranges() {
+    const int32_t seq[] = {0, 3, 8};                                         // two prompts of 3 and 5 rows
+    const std::map<int, int> base = {{4, 4}};                                // rows 4..7 of a store of 16
+    auto run = [&](int32_t a, int32_t b, int cap, std::map<int, int>* out) {
+        const int32_t keep[] = {a, b};
+        std::map<int, int> live = base;
+        const int rc = sa::check_keep(live, keep, seq, 2, cap);
+        if (out) *out = live;
+        return rc;
+    };
+    std::map<int, int> live;
+    CHECK(run(-1, -1, 16, &live) == SA_OK && live == base);
+    CHECK(run(0, 8, 16, &live) == SA_OK && (live == std::map<int, int>{{0, 3}, {4, 4}, {8, 5}}));
+    CHECK(run(1, 11, 16, &live) == SA_OK && live.size() == 3);               // touches the entry from below; ends on the store's last row
+    CHECK(run(2, -1, 16, nullptr) == SA_ERR_ARG);                            // rows 2..4 reach into the entry
+    CHECK(run(0, 12, 16, nullptr) == SA_ERR_ARG);                            // rows 12..16 of 16
+    CHECK(run(8, 10, 16, nullptr) == SA_ERR_ARG);                            // the call's own two ranges overlap
+    CHECK(run(-2, -1, 16, nullptr) == SA_ERR_ARG);
+    CHECK(run(-1, 0, 4, nullptr) == SA_ERR_ARG);                             // five rows into a store of four
+    CHECK(run(0, -1, 0, nullptr) == SA_ERR_ARG);                             // no store at all
+}
+
 int main() {
     for (size_t S : {1, 3, 24, 256, 1024}) check_offsets(S);
     for (size_t S : {1, 5, 24}) {
@@ -109,6 +203,13 @@ int main() {
         check_wait(S, {4, 4, 4, 4, 4});
     }
     check_carve();
+    check_exclusions();
+    check_store_free();
+    check_slot_lists();
+    check_fan_lists();
+    check_keep_ranges();
     std::printf(failures ? "step_outputs_check: %d FAILED\n" : "step_outputs_check: ok\n", failures);
     return failures ? 1 : 0;
 }
+
+
