@@ -246,6 +246,29 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
  * What a descriptor addresses is not checked against the buffers: the caller keeps offsets and sizes inside them. Enqueue only. */
 int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream);
 
+/* Contrast adjustment of line crops (RecognitionPredictor.reread, LineRef.adjust): n crops of the pages -> their adjusted, padded
+ * copies, each Pillow's ImageOps.autocontrast(crop, cutoff, preserve_tone=True, mask), byte for byte: 256 bins of the luma
+ * (19595 R + 38470 G + 7471 B + 32768) >> 16 over the crop (has_poly: over the pixels of the 4-point polygon's mask, rasterised as
+ * surya_rec_preprocess rasterises it), cutoff percent of the counts removed from the low end, then from the high end of what is
+ * left, lo / hi the first / last bin left, lut[i] = clamp(int(i * (255.0 / (hi - lo)) + (-lo * scale))) in float64 (the identity when
+ * hi <= lo), applied to the three channels of every pixel, the pixels outside the polygon being 255 before the LUT. A crop is
+ * written like a page (HWC, `pixel_stride` bytes per pixel, X = 0 with 4), so surya_rec_preprocess reads it through a descriptor
+ * whose page is the crop: page_off = its offset, page_w / page_h = cw / ch = its size, x0 = y0 = 0, has_poly = 0. The source may be
+ * a crop surya_rec_rectify wrote earlier on the same stream.
+ * pages, out, mask_arena, work, lo_hi: device; `out` may lie in the pages' allocation. descs: HOST array of n descriptors
+ *   { int64 src_off (byte offset of the source page in `pages`); int32 src_w, src_h, x0, y0, w, h (the crop inside it), cutoff (0..49),
+ *     has_poly; float poly[8] (relative to the crop origin); int64 out_off (byte offset of the copy in `out`), mask_off (byte offset
+ *     of the line's w * h mask bytes in mask_arena, read with has_poly only) }                                 -- 88 bytes, C layout;
+ * they are copied into the launches' kernel arguments, so the array may be reused as soon as the call returns. work: n * 1280 bytes,
+ * 4-byte aligned (the histograms, then the LUTs); lo_hi: int32 [n][2], the bounds of every line. SA_ERR_ARG, with nothing launched
+ * or written, when pixel_stride is not 3 or 4; a size is non-positive, a crop leaves its source or holds more than 2^28 pixels; a
+ * cutoff is outside 0..49; has_poly is neither 0 nor 1, or 1 without a mask_arena; an offset is negative or (pixel_stride 4) not a
+ * multiple of 4; two output ranges overlap, an output range overlaps the source page of any descriptor, or two mask ranges overlap;
+ * work or lo_hi is null. n == 0 launches nothing. What a descriptor addresses is not checked against the buffers' ends: the caller
+ * keeps offsets and sizes inside them. Enqueue only. */
+int surya_rec_adjust_contrast(const uint8_t* pages, const void* descs, int n, uint8_t* out, uint8_t* mask_arena, void* work, int32_t* lo_hi,
+                              int pixel_stride, void* stream);
+
 /* Test hooks (tolerance tests of intermediate tensors):
  *   encode_only: run the vision encoder + 2-D position embedding, write [P/merge^2, dec_hidden] features in
  *                ORIGINAL token order (= get_image_embeddings, common/surya/__init__.py:130-195) to `out`

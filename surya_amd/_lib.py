@@ -188,6 +188,8 @@ def _bind_lay_ops(lib):
     lib.surya_op_rec_boost_head.argtypes, lib.surya_op_rec_boost_head.restype = [i, C.POINTER(RecBoostHeadArgsC), p], C.c_int
     # rectification of rotated line quads in front of surya_rec_preprocess (csrc/rec_rectify.h); `descs` is a host array
     lib.surya_rec_rectify.argtypes, lib.surya_rec_rectify.restype = [p, p, i, p, i, i, i, p], C.c_int
+    # contrast adjustment of line crops in front of surya_rec_preprocess (csrc/rec_adjust.h); `descs` is a host array
+    lib.surya_rec_adjust_contrast.argtypes, lib.surya_rec_adjust_contrast.restype = [p, p, i, p, p, p, p, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
     rec = {
         "surya_op_rec_rmsnorm_rows": [i, p, l, p, p, l, p, i, i, f, p],

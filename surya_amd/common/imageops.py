@@ -251,3 +251,52 @@ def parallel_copy(dsts, srcs, min_bytes: int = 4 << 20) -> None:
 
     list(copy_pool().map(one, range(len(srcs))))
 
+
+
+# --------------------------------------------------------------------------------------------------- contrast adjustment
+# Pillow's ImageOps.autocontrast(crop, cutoff, preserve_tone=True, mask) restated in numpy, byte for byte (tests/test_reread_cpu.py
+# holds it to Pillow's own function); csrc/adjust_core.h + rec_adjust.h restate it once more for the device.
+def autocontrast_bounds(hist, cutoff: int):
+    """(lo, hi) of a 256-bin histogram: `cutoff` percent of the counts removed from the low end, then from the high end of what is
+    left, then the first and the last bin that still holds something (255, 0 for an empty histogram)."""
+    h = [int(v) for v in hist]
+    n = sum(h)
+    for rng in (range(256), range(255, -1, -1)):
+        cut = n * int(cutoff) // 100
+        for i in rng:
+            if cut <= 0:
+                break
+            take = min(cut, h[i])
+            h[i] -= take
+            cut -= take
+    lo = next((i for i in range(256) if h[i]), 255)
+    hi = next((i for i in range(255, -1, -1) if h[i]), 0)
+    return lo, hi
+
+
+def autocontrast_lut(lo: int, hi: int) -> np.ndarray:
+    """The 256-entry uint8 table for bounds (lo, hi): the identity when hi <= lo, else int(i * scale + offset) clamped to 0..255 with
+    scale = 255.0 / (hi - lo), offset = -lo * scale in float64 (for (0, 25) lut[25] is 254, as in Pillow)."""
+    if hi <= lo:
+        return np.arange(256, dtype=np.uint8)
+    scale = 255.0 / (hi - lo)
+    offset = -lo * scale
+    return np.clip((np.arange(256, dtype=np.float64) * scale + offset).astype(np.int64), 0, 255).astype(np.uint8)
+
+
+def autocontrast_crop(crop_u8: np.ndarray, mask, cutoff: int, with_bounds: bool = False):
+    """The contrast-adjusted copy of a padded uint8 crop [h, w, 3]: the histogram of the luma (Pillow's convert("L")) over the pixels
+    `mask` keeps ([h, w], non-zero = counted; None = all), autocontrast_bounds, autocontrast_lut, the table applied to every channel
+    of every pixel, the pad included. `cutoff` is an integer percent in 0..49."""
+    if isinstance(cutoff, bool) or not isinstance(cutoff, (int, np.integer)) or not 0 <= cutoff <= 49:
+        raise ValueError(f"cutoff must be an integer percent in 0..49, got {cutoff!r}")
+    crop_u8 = np.asarray(crop_u8)
+    if crop_u8.dtype != np.uint8 or crop_u8.ndim != 3 or crop_u8.shape[2] != 3:
+        raise ValueError("autocontrast_crop takes a uint8 [h, w, 3] crop")
+    c = crop_u8.astype(np.int64)
+    luma = (19595 * c[..., 0] + 38470 * c[..., 1] + 7471 * c[..., 2] + 32768) >> 16
+    if mask is not None:
+        luma = luma[np.asarray(mask) != 0]
+    lo, hi = autocontrast_bounds(np.bincount(luma.reshape(-1), minlength=256), int(cutoff))
+    out = autocontrast_lut(lo, hi)[crop_u8]
+    return (out, (lo, hi)) if with_bounds else out

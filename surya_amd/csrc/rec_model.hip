@@ -14,6 +14,7 @@
 #include "rec_ops.h"
 #include "rec_prep.h"
 #include "rec_rectify.h"
+#include "rec_adjust.h"
 
 namespace sa {
 
@@ -670,6 +671,12 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
 int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream) {
     return sa::prep::rectify_run(pages, reinterpret_cast<const sa::prep::RectifyDesc*>(descs), n, out, pixel_stride, max_w, max_h,
                                  (hipStream_t)stream);
+}
+
+int surya_rec_adjust_contrast(const uint8_t* pages, const void* descs, int n, uint8_t* out, uint8_t* mask_arena, void* work, int32_t* lo_hi,
+                              int pixel_stride, void* stream) {
+    return sa::prep::adjust_run(pages, reinterpret_cast<const sa::adjust::AdjustDesc*>(descs), n, out, mask_arena, work, lo_hi, pixel_stride,
+                                (hipStream_t)stream);
 }
 
 int surya_set_tuning(const char* key, int value) {

@@ -51,50 +51,66 @@ struct PrepArgs {
 // fill_poly_mask of surya_amd/common/imageops.py (= cv2.fillPoly's boundary-inclusive convention as restated there):
 // interior by the even-odd rule at pixel centres per scanline (ceil / floor of the edge intersections), then the boundary by a
 // dense rasterisation of every edge (rint of max(|dx|, |dy|) + 1 equal steps).
-__global__ __launch_bounds__(256) void prep_mask_rows_kernel(PrepArgs p) {
+// (the two passes as device functions of (polygon, crop size, mask), so that the contrast adjustment, rec_adjust.h, rasterises its
+// polygon lines with the same code: `t0`, `nt` are the calling thread's index and the thread count over the line)
+__device__ __forceinline__ void poly_mask_rows(const float (&poly)[8], int cw, int ch, unsigned char* m, int t0, int nt) {
 #pragma clang fp contract(off)
-    const LineDesc& L = p.lines[blockIdx.y];
-    if (!L.has_poly) return;
-    unsigned char* m = p.mask + L.mask_off;
-    for (int y = blockIdx.x * blockDim.x + threadIdx.x; y < L.ch; y += gridDim.x * blockDim.x) {
+    for (int y = t0; y < ch; y += nt) {
         double xs[4];
         int n = 0;
         for (int i = 0; i < 4; ++i) {
-            const double x0 = L.poly[2 * i], y0 = L.poly[2 * i + 1], x1 = L.poly[2 * ((i + 1) & 3)], y1 = L.poly[2 * ((i + 1) & 3) + 1];
+            const double x0 = poly[2 * i], y0 = poly[2 * i + 1], x1 = poly[2 * ((i + 1) & 3)], y1 = poly[2 * ((i + 1) & 3) + 1];
             if (y0 == y1) continue;
             const double lo = y0 < y1 ? y0 : y1, hi = y0 < y1 ? y1 : y0;
             if (lo <= (double)y && (double)y < hi) xs[n++] = x0 + ((double)y - y0) * (x1 - x0) / (y1 - y0);
         }
         for (int i = 1; i < n; ++i)                      // insertion sort of <= 4 intersections
             for (int j = i; j > 0 && xs[j] < xs[j - 1]; --j) { const double t = xs[j]; xs[j] = xs[j - 1]; xs[j - 1] = t; }
-        unsigned char* row = m + (long)y * L.cw;
-        for (int x = 0; x < L.cw; ++x) row[x] = 0;
+        unsigned char* row = m + (long)y * cw;
+        for (int x = 0; x < cw; ++x) row[x] = 0;
         for (int i = 0; i + 1 < n; i += 2) {
             int xa = (int)ceil(xs[i]), xb = (int)floor(xs[i + 1]);
             if (xb < xa) continue;
             xa = xa < 0 ? 0 : xa;
-            xb = xb > L.cw - 1 ? L.cw - 1 : xb;
+            xb = xb > cw - 1 ? cw - 1 : xb;
             for (int x = xa; x <= xb; ++x) row[x] = 1;
         }
     }
 }
 
-__global__ __launch_bounds__(256) void prep_mask_edges_kernel(PrepArgs p) {
+__device__ __forceinline__ void poly_mask_edges(const float (&poly)[8], int cw, int ch, unsigned char* m, int t0, int nt) {
 #pragma clang fp contract(off)
-    const LineDesc& L = p.lines[blockIdx.y];
-    if (!L.has_poly) return;
-    unsigned char* m = p.mask + L.mask_off;
     for (int e = 0; e < 4; ++e) {
-        const double x0 = L.poly[2 * e], y0 = L.poly[2 * e + 1], x1 = L.poly[2 * ((e + 1) & 3)], y1 = L.poly[2 * ((e + 1) & 3) + 1];
+        const double x0 = poly[2 * e], y0 = poly[2 * e + 1], x1 = poly[2 * ((e + 1) & 3)], y1 = poly[2 * ((e + 1) & 3) + 1];
         const double ax = fabs(x1 - x0), ay = fabs(y1 - y0);
         const int steps = (int)(ax > ay ? ax : ay) + 1;                   // np.linspace(a, b, steps + 1)
         const double sx = (x1 - x0) / (double)steps, sy = (y1 - y0) / (double)steps;
-        for (int k = blockIdx.x * blockDim.x + threadIdx.x; k <= steps; k += gridDim.x * blockDim.x) {
+        for (int k = t0; k <= steps; k += nt) {
             const double fx = k == steps ? x1 : x0 + (double)k * sx, fy = k == steps ? y1 : y0 + (double)k * sy;
             const long xi = (long)rint(fx), yi = (long)rint(fy);
-            if (xi >= 0 && xi < L.cw && yi >= 0 && yi < L.ch) m[yi * L.cw + xi] = 1;
+            if (xi >= 0 && xi < cw && yi >= 0 && yi < ch) m[yi * cw + xi] = 1;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void prep_mask_rows_kernel(PrepArgs p) {
+    const LineDesc& L = p.lines[blockIdx.y];
+    if (!L.has_poly) return;
+    poly_mask_rows(L.poly, L.cw, L.ch, p.mask + L.mask_off, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+__global__ __launch_bounds__(256) void prep_mask_edges_kernel(PrepArgs p) {
+    const LineDesc& L = p.lines[blockIdx.y];
+    if (!L.has_poly) return;
+    poly_mask_edges(L.poly, L.cw, L.ch, p.mask + L.mask_off, blockIdx.x * blockDim.x + threadIdx.x, gridDim.x * blockDim.x);
+}
+
+// the two passes of a polygon mask, in order, for `n_lines` descriptors: every polygon mask of the library is launched here
+constexpr int MASK_GRID_X = 2;
+template <typename Args>
+static inline void launch_poly_masks(void (*rows)(Args), void (*edges)(Args), const Args& a, int n_lines, hipStream_t s) {
+    hipLaunchKernelGGL(rows, dim3(MASK_GRID_X, n_lines), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(edges, dim3(MASK_GRID_X, n_lines), dim3(256), 0, s, a);
 }
 
 // ------------------------------------------------------------------------------------------------------------ resampling
@@ -230,8 +246,7 @@ static inline int prep_run(const PrepArgs& p, int any_poly, int any_stage1, hipS
     if (!p.pages || !p.lines || !p.tiles) return SA_ERR_ARG;
     if (any_poly) {
         if (!p.mask) return SA_ERR_ARG;
-        hipLaunchKernelGGL(prep_mask_rows_kernel, dim3(2, p.n_lines), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(prep_mask_edges_kernel, dim3(2, p.n_lines), dim3(256), 0, s, p);
+        launch_poly_masks(prep_mask_rows_kernel, prep_mask_edges_kernel, p, p.n_lines, s);
     }
     if (any_stage1) {
         if (!p.mid) return SA_ERR_ARG;

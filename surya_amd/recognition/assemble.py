@@ -33,7 +33,7 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
 
 
 _LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched",
-                "lexicon_index", "boost_matches", "rectified")
+                "lexicon_index", "boost_matches", "rectified", "variant", "readings")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -45,7 +45,7 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
                          "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None,
-                         "lexicon_index": None, "boost_matches": None, "rectified": None})
+                         "lexicon_index": None, "boost_matches": None, "rectified": None, "variant": None, "readings": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)

@@ -110,6 +110,8 @@ def _refuse(pred, what, det_predictor=None):
     """What every entry point refuses before any device work."""
     if getattr(pred, "_poisoned", None):
         raise RuntimeError(pred._poisoned)
+    if getattr(pred, "reread", None) is not None:
+        raise ValueError(f"reread does not apply to {what}(): a stored prompt holds no pixels to adjust or turn (set reread = None)")
     if det_predictor is not None:
         raise ValueError(f"{what}() takes no det_predictor: run the detector first and pass its polygons (polygons=)")
     if pred.shard_lines or pred.shard_pages or pred.process_group is not None:

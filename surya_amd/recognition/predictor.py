@@ -30,11 +30,12 @@ from PIL import Image
 from ..common.imageops import fill_poly_mask, quad_homography, quad_size, rectify_threshold, should_rectify, warp_quad
 from ..common.predictor import BasePredictor, gc_paused
 from ..settings import settings
-from . import assemble, options
+from . import assemble, options, reread as rereading
 from .loader import RecognitionModelLoader, rec_config_from_reference_json  # noqa: F401  (re-exported)
 from .loop import FEED_END, DeviceLoop
 from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref, quad_ref
 from .postprocess import sort_text_lines
+from .reread import Reread  # noqa: F401  (re-exported: pred.reread = Reread(...))
 from .schema import LineRanking, OCRResult, RankedCandidate, RankResult, TaskNames, TextLine
 
 
@@ -763,9 +764,28 @@ class RecognitionPredictor(BasePredictor):
         `blocklist` work with it (the readings are made of allowed characters). ValueError before any device work for another value,
         together with `top_k` (the alternatives arrays serve the beams), or on a model running MXFP8 decode weights or the fp8 KV cache;
         NotImplementedError with `shard_lines`, `shard_pages` or a process group. With `det_predictor` a beam call detects all pages
-        before it recognises (no streamed detection). `align` is unaffected."""
+        before it recognises (no streamed detection). `align` is unaffected.
+
+        `self.reread` (an attribute like `rectify`; None = off, else a recognition.reread.Reread: `pred.reread = Reread(below=0.6,
+        contrast=2, rotations=(180,))`): after the call's lines are read and assembled as always, every DOUBTFUL line -- a non-empty text
+        with `confidence < below`, or a pattern / lexicon that was not met -- is read once more per variant, all of them in one more run
+        of the loop under the line's own task, input text and per-line options and the call's `top_k` / `beam_width` / `math_mode`:
+        "contrast" is the line's own crop (padded, or rectified if the first pass rectified it) after Pillow's
+        ImageOps.autocontrast(cutoff=contrast, preserve_tone=True) over the polygon's pixels; "rot90" / "rot180" / "rot270" are the
+        line's quad -- the rectangle for a `bboxes=` line -- with its vertex list rolled by 1 / 2 / 3, read through the rectify path whatever
+        `rectify` says (a polygon that is no rectifiable quad gets none). Candidates are the first reading, then the variants in that
+        order; the winner meets its constraint (where the line has one), has a non-empty text, then the highest confidence, the earlier
+        one on a tie, and its whole TextLine takes the line's place (`polygon` stays the one that came in; a turned winner's characters
+        are tilted quads on the page). `TextLine.variant` names the winner, `TextLine.readings` lists every candidate of a line that was
+        re-read as LineReading(variant, text, confidence); both are None while `reread` is None. `last_timing` gains `reread_ms` and
+        `reread_lines`. TypeError / ValueError for a bad value, NotImplementedError with `shard_lines`, `shard_pages` or a process group,
+        before any device work; ValueError naming `reread` in `align`, `rank`, `encode` and the methods of EncodedLines: a stored prompt
+        holds no pixels to adjust or turn."""
         top_k, beam, pattern, lexicon, boost_words, boost_weight = self._checked_modes()
-        with self._modes(top_k, beam):
+        setting = rereading.checked(self.reread)
+        if setting is not None and (self.shard_lines or self.shard_pages or self.process_group is not None):
+            raise NotImplementedError("a call with reread runs on one rank: unset shard_lines / shard_pages / process_group")
+        with self._modes(top_k, beam, setting):
             return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
                                         bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
                                         pattern, lexicon, boost_words, boost_weight)
@@ -797,16 +817,16 @@ class RecognitionPredictor(BasePredictor):
         return top_k, beam, pattern, lexicon, boost_words, boost_weight
 
     @contextmanager
-    def _modes(self, top_k=None, beam=None):
+    def _modes(self, top_k=None, beam=None, reread=None):
         """The validated top_k and beam_width for the length of a call: `_call`, `generate` and the loops are reached positionally by the
         page-sharded path and by stand-ins and read them from here. align() and rank() park both: they report `greedy`, not
         alternatives, and one reading, the given one, whatever beam_width says."""
-        saved = self._top_k, self._beam
-        self._top_k, self._beam = top_k, beam
+        saved = self._top_k, self._beam, self._reread
+        self._top_k, self._beam, self._reread = top_k, beam, reread
         try:
             yield
         finally:
-            self._top_k, self._beam = saved
+            self._top_k, self._beam, self._reread = saved
             if top_k is not None:
                 self.last_alternatives = None
 
@@ -834,6 +854,8 @@ class RecognitionPredictor(BasePredictor):
     def _forced_call_checks(self, what, arg, arg_lists, images, per_line, task_names, bboxes, polygons):
         """What `align` and `rank` refuse before any device work; -> (the bbox / polygon lists, the task names)."""
         rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
+        if self.reread is not None:
+            raise ValueError(f"reread does not apply to {what}(): the text is given, there is no reading to doubt (set reread = None)")
         if self.pattern is not None:
             raise ValueError(f"pattern does not apply to {what}(): forced decoding reads no allowed set (set pattern = None)")
         if self.lexicon is not None:
@@ -1033,6 +1055,8 @@ class RecognitionPredictor(BasePredictor):
     boost_words = None                # word list per call / image / line to PREFER (see __call__), None = off: pred.boost_words = ["Paracetamol", ...]
     boost_weight = None               # ... and the boost in logit units, a finite float >= 0: required with boost_words, no default
     rectify = None                    # warp tilted 4-point polygons upright (see __call__): None = off, True, or a threshold in degrees: pred.rectify = 2.0
+    reread = None                     # re-read doubtful lines as other pictures (see __call__): None = off, or Reread(below=0.6, contrast=2, rotations=(180,))
+    _reread = None                    # the running call's validated Reread (see __call__)
     last_boost = None
     last_alternatives = None
     last_forced = None                # align(): (greedy ids, greedy probabilities, forced log-probabilities) per line id, like last_packed
@@ -1095,12 +1119,16 @@ class RecognitionPredictor(BasePredictor):
                 return self._call_streamed(images, task_names, det_predictor, detection_batch_size, recognition_batch_size,
                                            highres_images, sort_lines, math_mode, return_words, drop_repeated_text, stamps, t_call, cons=cons)
             flat = self.detect_and_slice_bboxes(images, task_names, det_predictor, detection_batch_size, highres_images)
+            if self._reread is not None:                      # the second pass cuts from the images the first pass cut from
+                flat["reread_from"] = ([hr if hr is not None else im for im, hr in zip(images, highres_images)], "poly")
         else:
             if bboxes is not None:
                 assert len(images) == len(bboxes), "You need to pass in one list of bboxes for each image"
             if polygons is not None:
                 assert len(images) == len(polygons), "You need to pass in one list of polygons for each image"
             flat = self.slice_bboxes(images, bboxes=bboxes, polygons=polygons, input_text=input_text, task_names=task_names)
+            if self._reread is not None:
+                flat["reread_from"] = (images, "poly" if polygons is not None else "bbox")
         return self._read_flat(images, flat, cons, recognition_batch_size, sort_lines, return_words, drop_repeated_text, stamps, t_call,
                                lambda f: self.prepare_lines(f, math_mode), math_mode)
 
@@ -1116,6 +1144,8 @@ class RecognitionPredictor(BasePredictor):
         sorted_keys = ("slices", "input_text", "task_names") + (("enc_ids",) if "enc_ids" in flat else ())
         if cons is not None:                                  # the options' integers are by line id like the slices: sorted with them below
             sorted_keys += options.attach(flat, cons)
+        else:                                                 # (a second pass brings its lines' integers with it: reread.second_pass)
+            sorted_keys += tuple(o.line_key for o in options.requested(flat) if o.line_key in flat)
 
         # widest first: the length bucketing that keeps prefill batches homogeneous (reference :847-854); `order[k]` is the original
         # position of sorted line k, so a finished line can be assembled against its own polygon / scale
@@ -1142,6 +1172,9 @@ class RecognitionPredictor(BasePredictor):
                 self.generate(prep, recognition_batch_size, on_done=hand.on_done, on_flush=hand.on_flush)
                 stamps["prepare_ms"] = (t1 - t0) * 1e3
                 text_lines = hand.finish(stamps, t1)
+        if self._reread is not None and flat.get("reread_from") is not None:
+            text_lines = rereading.second_pass(self, self._reread, flat, order, text_lines, *flat["reread_from"], recognition_batch_size,
+                                               return_words, drop_repeated_text, math_mode, stamps)
         results = self._page_results(images, flat["slice_map"], text_lines, sort_lines)
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results
@@ -1343,6 +1376,10 @@ class RecognitionPredictor(BasePredictor):
         if not text_lines:
             return []
         assert len(flat["slice_map"]) == len(images)
+        if self._reread is not None:
+            sources = [hr if hr is not None else im for im, hr in zip(images, highres_images)]
+            text_lines = rereading.second_pass(self, self._reread, flat, orig_of, text_lines, sources, "poly", recognition_batch_size,
+                                               return_words, drop_repeated_text, math_mode, stamps)
         results = self._page_results(images, flat["slice_map"], text_lines, sort_lines)
         stamps["total_ms"] = (time.perf_counter() - t_call) * 1e3
         return results

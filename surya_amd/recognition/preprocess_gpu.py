@@ -27,6 +27,12 @@ assert LINE_DESC.itemsize == 112, LINE_DESC.itemsize
 RECTIFY_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("out_w", np.int32), ("out_h", np.int32),
                          ("out_off", np.int64), ("h", np.float64, (9,))], align=True)
 assert RECTIFY_DESC.itemsize == 104, RECTIFY_DESC.itemsize
+# must match sa::adjust::AdjustDesc (csrc/adjust_core.h): one per contrast-adjusted line, a HOST array like RECTIFY_DESC
+ADJUST_DESC = np.dtype([("src_off", np.int64), ("src_w", np.int32), ("src_h", np.int32), ("x0", np.int32), ("y0", np.int32), ("w", np.int32),
+                        ("h", np.int32), ("cutoff", np.int32), ("has_poly", np.int32), ("poly", np.float32, (8,)), ("out_off", np.int64),
+                        ("mask_off", np.int64)], align=True)
+assert ADJUST_DESC.itemsize == 88, ADJUST_DESC.itemsize
+ADJUST_WORK_BYTES = 1280                                   # per line of a surya_rec_adjust_contrast call: 256 counters, then the LUT
 
 
 @dataclass
@@ -43,6 +49,9 @@ class LineRef:
     # a line that is RECTIFIED (RecognitionPredictor.rectify): four (x, y) floats in page coordinates, clockwise, p0 -> p1 the top edge in
     # reading direction. Its pixels are warp_quad's (common/imageops.py) of the quad, its shape quad_size's; `poly` is then not read.
     quad: Optional[Tuple[Tuple[float, float], ...]] = None
+    # a line read from its CONTRAST-ADJUSTED crop (RecognitionPredictor.reread): the cutoff, an integer percent in 0..49. Its pixels are
+    # autocontrast_crop's (common/imageops.py) of the padded crop it would have been read from -- the rectified one for a line with a `quad`.
+    adjust: Optional[int] = None
 
     @property
     def shape(self):
@@ -111,7 +120,10 @@ class DevicePreprocessor:
         """pages: uint8 [H, W, 3] (RGB) or [H, W, 4] (RGBX) arrays; lines: LineRefs into them; max_sizes: the task's img_size per line.
         Returns (tiles cuda fp32 [sum P, 3 ps^2], tile_offs int64 [n + 1], grids [(gh, gw)]).
         Lines with a `quad` are rectified first (surya_rec_rectify, once per call): their upright crops are written into an arena behind the
-        pages and each then is an ordinary line whose page is its crop. A call without a quad allocates and launches what it always did."""
+        pages and each then is an ordinary line whose page is its crop. Lines with `adjust` set get their contrast-adjusted, padded crops
+        behind those (surya_rec_adjust_contrast, once per call, after the rectification) and are read from them likewise; the call's
+        (lo, hi) bounds stay in `last_adjust_bounds` (device int32 [n_adjusted, 2], in line order). A call without a quad and without an
+        adjusted line allocates and launches what it always did."""
         n = len(lines)
         f = self.ps * self.merge
         offs, total = [], 0
@@ -126,6 +138,8 @@ class DevicePreprocessor:
         n_rect = sum(1 for ln in lines if ln.quad is not None)
         rdesc = np.zeros(n_rect, RECTIFY_DESC)
         arena, r, max_rw, max_rh = (total + 3) & ~3, 0, 0, 0
+        adj = [i for i, ln in enumerate(lines) if ln.adjust is not None]
+        adesc, amask_bytes = np.zeros(len(adj), ADJUST_DESC), 0
         desc = np.zeros(n, LINE_DESC)
         tile_offs = np.zeros(n + 1, np.int64)
         grids, mask_bytes, mid_floats, max_mid_w = [], 0, 0, 0
@@ -152,8 +166,9 @@ class DevicePreprocessor:
                     raise ValueError("device pre-processing handles 4-point polygons")
                 d["has_poly"] = 1
                 d["poly"] = np.asarray([(x - ln.x0, y - ln.y0) for x, y in ln.poly], np.float32).reshape(-1)
-                d["mask_off"] = mask_bytes
-                mask_bytes += h * w
+                if ln.adjust is None:
+                    d["mask_off"] = mask_bytes
+                    mask_bytes += h * w
             d["mid_w"], d["mid_h"], d["out_w"], d["out_h"] = mw, mh, ow, oh
             if (mh, mw) != (h, w):
                 d["mid_off"] = mid_floats
@@ -163,6 +178,18 @@ class DevicePreprocessor:
             gh, gw = oh // self.ps, ow // self.ps
             grids.append((gh, gw))
             tile_offs[i + 1] = tile_offs[i] + gh * gw
+        # adjusted lines, behind every rectified crop: what the line would have been read from is the source, the line's page its adjusted copy
+        for k, i in enumerate(adj):
+            d, ad = desc[i], adesc[k]
+            w, h = int(d["cw"]), int(d["ch"])
+            ad["src_off"], ad["src_w"], ad["src_h"], ad["x0"], ad["y0"] = d["page_off"], d["page_w"], d["page_h"], d["x0"], d["y0"]
+            ad["w"], ad["h"], ad["cutoff"], ad["out_off"] = w, h, lines[i].adjust, arena
+            if d["has_poly"]:                          # the pad is in the adjusted pixels: the mask moves to the adjustment
+                ad["has_poly"], ad["poly"], ad["mask_off"] = 1, d["poly"], amask_bytes
+                amask_bytes += h * w
+                d["has_poly"], d["poly"] = 0, 0
+            d["page_off"], d["page_w"], d["page_h"], d["x0"], d["y0"] = arena, w, h, 0, 0
+            arena += (w * h * pix + 3) & ~3
         if n_rect:                                     # all homographies of the call in one stacked solve
             rdesc["h"] = quad_homographies([ln.quad for ln in lines if ln.quad is not None], rdesc["out_w"], rdesc["out_h"])
         torch.cuda.set_device(self.device)
@@ -171,7 +198,7 @@ class DevicePreprocessor:
         host = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         parallel_copy([hv[o: o + pg.size].reshape(pg.shape) for pg, o in zip(pages, offs)], list(pages))   # 3-8 MB each: side by side
-        if n_rect:
+        if n_rect or adj:
             d_pages = torch.empty(arena, dtype=torch.uint8, device=self.device)
             d_pages[:host.numel()].copy_(host, non_blocking=True)
         else:
@@ -184,9 +211,16 @@ class DevicePreprocessor:
         if n_rect:
             L.check(self.lib.surya_rec_rectify(L.ptr(d_pages), rdesc.ctypes.data_as(C.c_void_p), C.c_int(n_rect), L.ptr(d_pages), C.c_int(pix),
                                                C.c_int(max_rw), C.c_int(max_rh), stream), "surya_rec_rectify")
+        if adj:
+            d_amask = torch.empty(max(amask_bytes, 1), dtype=torch.uint8, device=self.device)
+            d_work = torch.empty(len(adj) * ADJUST_WORK_BYTES, dtype=torch.uint8, device=self.device)
+            self.last_adjust_bounds = torch.empty((len(adj), 2), dtype=torch.int32, device=self.device)
+            L.check(self.lib.surya_rec_adjust_contrast(L.ptr(d_pages), adesc.ctypes.data_as(C.c_void_p), C.c_int(len(adj)), L.ptr(d_pages),
+                                                       L.ptr(d_amask), L.ptr(d_work), L.ptr(self.last_adjust_bounds), C.c_int(pix), stream),
+                    "surya_rec_adjust_contrast")
         L.check(self.lib.surya_rec_preprocess(L.ptr(d_pages), L.ptr(d_desc), C.c_int(n), L.ptr(d_mask), L.ptr(d_mid), L.ptr(tiles),
                                               C.c_int(self.ps), C.c_int(self.merge), C.c_float(self.pad), self.mean, self.std,
                                               C.c_int(int(mask_bytes > 0)), C.c_int(max_mid_w), C.c_int(pix), stream),
                 "surya_rec_preprocess")
-        self._keep = (d_pages, d_desc, d_mask, d_mid, host)          # alive until the stream has consumed them
+        self._keep = (d_pages, d_desc, d_mask, d_mid, host) + ((d_amask, d_work) if adj else ())      # alive until the stream has consumed them
         return tiles, tile_offs, grids

@@ -100,6 +100,14 @@ class LineHypothesis(BaseModel):
     words: List[TextWord] | None = None
 
 
+class LineReading(BaseModel):
+    """One candidate reading of a line that was re-read (RecognitionPredictor.reread): the picture it was read from -- "original",
+    "contrast", "rot90", "rot180" or "rot270" -- with its text and line confidence."""
+    variant: str
+    text: str
+    confidence: Optional[float] = 0
+
+
 class TextLine(BaseChar):
     chars: List[TextChar]
     original_text_good: bool = False
@@ -118,6 +126,9 @@ class TextLine(BaseChar):
     # while the line was read, in order of completion, each once; [] if none. None, and left out likewise, for a line that was not boosted.
     # `rectified` (RecognitionPredictor.rectify): whether the line's pixels were warped upright from its quadrilateral; its characters'
     # polygons are then tilted quads on the page. None, and left out likewise, while `rectify` is None.
+    # `variant` (RecognitionPredictor.reread): the picture the line's reading comes from, "original" | "contrast" | "rot90" | "rot180" |
+    # "rot270"; `readings`: every candidate of a line that was re-read, the first reading first, then the variants in that order; None
+    # for a line that was read once. Both None, and left out likewise, while `reread` is None.
     if _EXCLUDE_IF:
         log_prob: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
         hypotheses: Optional[List[LineHypothesis]] = Field(default=None, exclude_if=lambda v: v is None)
@@ -125,6 +136,8 @@ class TextLine(BaseChar):
         lexicon_index: Optional[int] = Field(default=None, exclude_if=lambda v: v is None)
         boost_matches: Optional[List[int]] = Field(default=None, exclude_if=lambda v: v is None)
         rectified: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
+        variant: Optional[str] = Field(default=None, exclude_if=lambda v: v is None)
+        readings: Optional[List[LineReading]] = Field(default=None, exclude_if=lambda v: v is None)
     else:
         log_prob: Optional[float] = None
         hypotheses: Optional[List[LineHypothesis]] = None
@@ -132,6 +145,8 @@ class TextLine(BaseChar):
         lexicon_index: Optional[int] = None
         boost_matches: Optional[List[int]] = None
         rectified: Optional[bool] = None
+        variant: Optional[str] = None
+        readings: Optional[List[LineReading]] = None
 
         @model_serializer(mode="wrap")
         def _without_absent_log_prob(self, handler):
@@ -148,6 +163,10 @@ class TextLine(BaseChar):
                 d.pop("boost_matches", None)
             if self.rectified is None:
                 d.pop("rectified", None)
+            if self.variant is None:
+                d.pop("variant", None)
+            if self.readings is None:
+                d.pop("readings", None)
             return d
 
 
