@@ -505,7 +505,11 @@ int surya_rec_wait_boost(surya_rec* h, int n_steps, int ring, int32_t* plain_tok
 /* ------------------------------------------------------------------------------------------------------------
  * Op-level entry points (unit tests of the kernels through the same library; row-major, compute dtype).
  * ---------------------------------------------------------------------------------------------------------- */
-/* C[M,N] = X[M,K] W[N,K]^T + bias, epilogue: 0 none/bias, 1 +residual R, 2 gelu, 3 swiglu (W rows interleaved,
+/* Operands of every GEMM entry point below (surya_op_gemm, _rope, _splitk_*, surya_op_rec_gemm_f16) and of every GEMM an engine launches:
+ * K > 0 and a multiple of one 128-byte K-tile (64 16-bit / 32 fp32 elements); X, W, C, R and the split-K slabs start on 16-byte boundaries and
+ * ldx, ldw, ldc, ldr are multiples of 16 bytes of their element type (rows move in 16-byte chunks); bias starts on a boundary of 4 of its
+ * elements. Anything else is refused with SA_ERR_SHAPE before any launch.
+ * C[M,N] = X[M,K] W[N,K]^T + bias, epilogue: 0 none/bias, 1 +residual R, 2 gelu, 3 swiglu (W rows interleaved,
  * C is [M,N/2]), 4 hardswish, 5 relu, 8 geglu = gelu_tanh(gate) * up with gate, up and the gelu each rounded to the compute dtype
  * (the ADETR decoder's MLP, W rows interleaved like swiglu, C is [M,N/2]; fp32 and bf16 only, no bias, no R, out_f32 == 0; fp16: surya_op_gemm_geglu_f16 below).
  * Codes 6 and 7 are epilogues of the recogniser that take further operands and are not reachable here: SA_ERR_ARG.
@@ -514,6 +518,12 @@ int surya_rec_wait_boost(surya_rec* h, int n_steps, int ring, int32_t* plain_tok
  * SA_ERR_UNSUPPORTED. */
 int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc,
                   const void* bias, const void* R, long ldr, int M, int N, int K, void* stream);
+/* The vision qkv projection with the rotary embedding in its epilogue (launch_gemm<T, T, EPI_ROPE>, filled as the recognition encoder fills
+ * it): C[M,N] = T(X W^T + bias), then columns n < rope_cols rotated in pairs (2j, 2j + 1) of each rope_D-wide head by
+ * rope[m][(n % rope_D) / 2] = (cos, sin) (fp32 [M][rope_D / 2][2]; the weight rows are pair-interleaved), fp32 math, rounded to T once more.
+ * Columns >= rope_cols are the plain projection. rope_D % 4 == 0, rope_cols a multiple of rope_D, rope 16-byte aligned. dtype fp32 / bf16 / fp16. */
+int surya_op_gemm_rope(int dtype, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const float* rope,
+                       int rope_cols, int rope_D, int M, int N, int K, void* stream);
 int surya_op_rmsnorm(int dtype, const void* x, long ldx, const void* w, void* y, long ldy, int rows, int C, float eps,
                      void* stream);
 /* Attention kernels by themselves (tests against fp32 PyTorch SDPA; synchronous -- the call returns after the kernel ran).

@@ -128,6 +128,7 @@ def _bind_lay_ops(lib):
             f16 = getattr(lib, name + "_f16")
             f16.argtypes, f16.restype = args[1:], C.c_int
     lib.surya_op_gemm_geglu_f16.argtypes, lib.surya_op_gemm_geglu_f16.restype = [p, l, p, l, p, l, i, i, i, p], C.c_int
+    lib.surya_op_gemm_rope.argtypes, lib.surya_op_gemm_rope.restype = [i, p, l, p, l, p, l, p, p, i, i, i, i, i, p], C.c_int
     # the fp16 recogniser's GEMMs (csrc/rec_model_f16.hip)
     lib.surya_op_rec_gemm_f16.argtypes, lib.surya_op_rec_gemm_f16.restype = [i, i, p, l, p, l, p, l, p, p, l, i, i, i, p, ip, p], C.c_int
     lib.surya_op_gemm_splitk_f16.argtypes, lib.surya_op_gemm_splitk_f16.restype = [p, l, p, l, p, i, i, i, ip, p], C.c_int

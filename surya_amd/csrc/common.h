@@ -307,7 +307,7 @@ struct Tuning {
     int split_target = 256;  // decode split-K projections: aim at this many workgroups
     int split_min_kt = 4;    // at least this many 128-byte K-tiles per slice
     int split_max = 8;       // slice cap (the reduce kernels keep <= 8 slabs in flight)
-    int bigtile = 3;         // 256x256 tiles for large bf16 GEMMs: 3 = the 8-phase schedule (round 5; even K-tile counts, else the 2-stage loop), 1 = 2-stage loop, 2 = 2-stage on 4 waves, 0 = 128x128 only
+    int bigtile = 3;         // 256x256 tiles for large bf16 GEMMs: 3 = the 8-phase schedule (round 5; even K-tile counts, else the 2-stage loop), 1 = 2-stage loop, 2 = 2-stage on 4 waves (even K-tile counts, else as 1), 0 = 128x128 only
     int bigtile_any = 0;     // 1: every M > 256 bf16 GEMM takes the 256x256 tile whatever its round count (tests / race screens of the tile on small shapes)
     int big_m_split = -1;    // decode projections above 256 rows (round 6): split-K tile -- -1 = by workgroup count (128x128 once it fills half the chip, else 128x64 within one round; 4-stage ring),
                              // 0 = the 64x64 tile of the <= 256-row regime, 2 = 128x128, 3 = 128x64 (slice count unchanged: same bits in every arm)

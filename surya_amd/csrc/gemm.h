@@ -1926,12 +1926,31 @@ static inline int launch_gemm_persist(const GemmArgs<TI, TO>& a, hipStream_t s) 
 #include "gemm_ring.h"
 namespace sa {
 
+// What the kernels' accesses need of the operands (stated once above surya_op_gemm in include/surya_amd.h): computed correctly or refused
+// here, before any launch. K > 0: the K loops request K-tile 0 unconditionally (the 2-stage loop's first SA_ISSUE(0, 0)). X and W rows are
+// fetched in 16-byte chunks (global_load_lds_dwordx4 / uint4 loads): bases and row strides are multiples of 16 bytes. C, R and the split-K
+// slabs are accessed as u32x4: likewise. The bias is read four columns at a time (float4 / uint2; the persistent loop reads two): 4 elements.
+static inline bool gemm_misaligned(const void* p, size_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+template <typename TI, typename TO>
+static inline bool gemm_operands_ok(const GemmArgs<TI, TO>& a, bool with_r) {
+    constexpr long CI = 16 / (long)sizeof(TI), CO = 16 / (long)sizeof(TO);
+    if (a.K <= 0 || a.ldx % CI != 0 || a.ldw % CI != 0 || a.ldc % CO != 0) return false;
+    if (gemm_misaligned(a.X, 16) || gemm_misaligned(a.W, 16) || gemm_misaligned(a.C, 16) || gemm_misaligned(a.part, 16)) return false;
+    if (gemm_misaligned(a.bias, 4 * sizeof(TI))) return false;
+    if (with_r && (a.ldr % CO != 0 || gemm_misaligned(a.R, 16))) return false;
+    return true;
+}
+
 // Tile choice. M <= 256 is the decode regime: one workgroup spans all rows (weights stream from HBM once), BN picked so
 // the grid has >= ~128 workgroups where N allows. Larger M uses 128x128 tiles, with 64x64 for problems too small to
 // fill the chip.
 template <typename TI, typename TO, int EPI>
 static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return SA_OK;
+    if (!gemm_operands_ok(a, EPI == EPI_RESIDUAL)) return SA_ERR_SHAPE;
+    if constexpr (EPI == EPI_ROPE) {      // the table is read as float4 = two (cos, sin) pairs: rope[m * (D / 2) + (n % D) / 2] at n % 4 == 0
+        if (!a.rope || gemm_misaligned(a.rope, 16) || a.rope_D <= 0 || a.rope_D % 4 != 0 || a.rope_cols < 4 || a.rope_cols % 4 != 0) return SA_ERR_SHAPE;
+    }
     {   // rows are stored in 16-byte chunks: output width (N, or N/2 after SwiGLU) must be a multiple of 16 bytes of TO
         const int n_out = (EPI == EPI_SWIGLU || EPI == EPI_GEGLU) ? a.N / 2 : a.N;
         if (a.K % Ty<TI>::KE != 0 || a.N % 4 != 0 || n_out % (16 / (int)sizeof(TO)) != 0 || a.ldc % (16 / (int)sizeof(TO)) != 0)
@@ -2044,7 +2063,10 @@ static inline int launch_gemm(const GemmArgs<TI, TO>& a, hipStream_t s) {
             // stage does not fit (3 x 64 KB > 160 KB of LDS). Same K order and MFMA: bit-identical outputs.
             // A/B: tools/microbench/bigtile_ab.py 1 2.
             if constexpr (sizeof(TI) == 2 && !epi_is_argmax(EPI)) {
-                if (bigtile == 2) return launch_gemm_cfg<TI, TO, 256, 256, 2, 2, EPI, false, 2>(a, s);
+                // Even K-tile counts only: with 256 accumulator registers per lane the tile is one of the kernel's LEAN ones, whose 2-stage
+                // loop has no odd tail (`if constexpr (!LEAN) if (nk & 1) ...`) -- at K = 64 or 192 the last K-tile was never multiplied
+                // (tests/test_gpu_gemm_ops.py, t256w4 at 1 and 3 K-tiles: every element wrong). Odd counts take the 8-wave tile below.
+                if (bigtile == 2 && (a.K / Ty<TI>::KE) % 2 == 0) return launch_gemm_cfg<TI, TO, 256, 256, 2, 2, EPI, false, 2>(a, s);
                 // bigtile = 3: the 8-phase schedule (half-tile ring, counted vmcnt, two wave groups one barrier apart); even K-tile counts
                 if (bigtile == 3 && (a.K / Ty<TI>::KE) % 2 == 0) return launch_gemm_cfg<TI, TO, 256, 256, 4, 2, EPI, false, 8>(a, s);
             }
@@ -2078,6 +2100,7 @@ template <typename TI>
 static inline int launch_gemm_splitk(GemmArgs<TI, TI>& a, hipStream_t s) {
     if (a.M <= 0 || a.N <= 0) return SA_OK;
     if (a.K % Ty<TI>::KE != 0 || a.N % 4 != 0 || !a.part) return SA_ERR_SHAPE;
+    if (!gemm_operands_ok(a, false)) return SA_ERR_SHAPE;
     const int nk = a.K / Ty<TI>::KE;
     // 64x64 tiles with a 4-stage direct-to-LDS ring and ~256 workgroups. 128x64 / 128x128 split-K tiles (fewer L2->CU requests per
     // MAC, more slices) were measured in r02 and lose by 70-180 us per decode step (profiles/r02_decode_sweeps.md).

@@ -75,6 +75,8 @@ int rec_f16_create(const surya_rec_config& cfg, const void* const* weights, int 
 int rec_f16_ring_error(bool reset);
 int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N, int K, const TokenMask* tm, float4* amax, float2* alt, int* bn_used,
                    hipStream_t s, const ForcedCols* fc = nullptr);
+int op_gemm_rope_f16(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const float* rope, int rope_cols,
+                     int rope_D, int M, int N, int K, hipStream_t s);
 // det_model.hip: the fp16 GEMMs of surya_op_gemm
 int op_gemm_f16(int epi, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const void* R, long ldr,
                 int M, int N, int K, hipStream_t s);
@@ -100,6 +102,14 @@ static int op_gemm_t(int epi, const void* X, long ldx, const void* W, long ldw, 
     return SA_ERR_ARG;
 }
 
+// surya_op_gemm_rope: the vision qkv projection by itself, GemmArgs filled as RecModel<T>::encode fills them (rec_engine.h)
+template <typename T>
+static int op_gemm_rope_t(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const float* rope, int rope_cols,
+                          int rope_D, int M, int N, int K, hipStream_t s) {
+    GemmArgs<T, T> a{(const T*)X, ldx, (const T*)W, ldw, (T*)C, ldc, (const T*)bias, nullptr, 0, M, N, K};
+    a.rope = reinterpret_cast<const float2*>(rope); a.rope_cols = rope_cols; a.rope_D = rope_D;
+    return launch_gemm<T, T, EPI_ROPE>(a, s);
+}
 
 // surya_op_lm_head_partials: the lm_head launch of RecModel<T>::heads for the 16-bit / fp32 operand types built here
 template <typename T>
@@ -464,6 +474,17 @@ int surya_op_gemm(int dtype, int out_f32, int epi, const void* X, long ldx, cons
         if (epi == EPI_GELU) return R ? SA_ERR_UNSUPPORTED : sa::op_gemm_f16_gelu(X, ldx, W, ldw, C, ldc, bias, M, N, K, s);
         return sa::op_gemm_f16(epi, X, ldx, W, ldw, C, ldc, bias, R, ldr, M, N, K, s);
     }
+    return SA_ERR_UNSUPPORTED;
+}
+
+int surya_op_gemm_rope(int dtype, const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const float* rope,
+                       int rope_cols, int rope_D, int M, int N, int K, void* stream) {
+    if (!X || !W || !C || !rope) return SA_ERR_ARG;
+    if (rope_D <= 0 || rope_cols <= 0 || rope_cols > N || rope_cols % rope_D != 0) return SA_ERR_ARG;
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == SA_DTYPE_F32) return op_gemm_rope_t<float>(X, ldx, W, ldw, C, ldc, bias, rope, rope_cols, rope_D, M, N, K, s);
+    if (dtype == SA_DTYPE_BF16) return op_gemm_rope_t<bf16_t>(X, ldx, W, ldw, C, ldc, bias, rope, rope_cols, rope_D, M, N, K, s);
+    if (dtype == SA_DTYPE_F16) return sa::op_gemm_rope_f16(X, ldx, W, ldw, C, ldc, bias, rope, rope_cols, rope_D, M, N, K, s);
     return SA_ERR_UNSUPPORTED;
 }
 

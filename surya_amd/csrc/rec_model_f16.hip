@@ -59,6 +59,14 @@ int op_lm_head_f16(const void* X, const void* W, const void* bias, int M, int N,
     return rc;
 }
 
+// the fp16 arm of surya_op_gemm_rope (rec_model.hip): the vision qkv projection as RecModel<fp16_t>::encode launches it
+int op_gemm_rope_f16(const void* X, long ldx, const void* W, long ldw, void* C, long ldc, const void* bias, const float* rope, int rope_cols,
+                     int rope_D, int M, int N, int K, hipStream_t s) {
+    GemmArgs<fp16_t, fp16_t> a{(const fp16_t*)X, ldx, (const fp16_t*)W, ldw, (fp16_t*)C, ldc, (const fp16_t*)bias, nullptr, 0, M, N, K};
+    a.rope = reinterpret_cast<const float2*>(rope); a.rope_cols = rope_cols; a.rope_D = rope_D;
+    return launch_gemm<fp16_t, fp16_t, EPI_ROPE>(a, s);
+}
+
 // the fp16 arm of the surya_op_rec_* entries (rec_model.hip): the launchers of kernels.h on the fp16 instances
 int op_rec_f16(int op, const void* args, hipStream_t s) { return rec_op_any<fp16_t>(op, args, s); }
 

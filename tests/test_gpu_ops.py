@@ -1,4 +1,5 @@
-"""GPU: op-level kernels through the C ABI vs a plain PyTorch fp32 reference of the same op."""
+"""GPU: op-level kernels through the C ABI vs a plain PyTorch fp32 reference of the same op.
+(The GEMM's tiles, stagings and schedules one by one, per element against float64: tests/test_gpu_gemm_ops.py.)"""
 import ctypes as C
 
 import pytest

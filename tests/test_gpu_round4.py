@@ -8,6 +8,7 @@ surya_set_tuning inside one process), and the hipGraph cache against mode change
   * split-K reduce with slab loads sized by the slice count vs the 8-slab kernel: bit-identical by construction.
   * toggling the fp8 KV cache / MXFP8 weights / any knob while graph replay is on must not replay a graph
     captured under the other mode.
+(The 8-phase tile and the persistent loop against an independent float64 reference, per element: tests/test_gpu_gemm_ops.py.)
 """
 import ctypes as C
 
