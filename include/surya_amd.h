@@ -957,6 +957,20 @@ int surya_reduce_u8(const uint8_t* src, int src_w, int src_h, int src_pix, uint8
 size_t surya_det_boxes_workspace_bytes(int batch, int height, int width, int max_boxes);
 int surya_det_boxes(const float* heat, long page_stride, int batch, int height, int width, float text_threshold, float low_text,
                     int max_boxes, float* boxes, float* conf, int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+/* Test and diagnostic surface: where surya_det_boxes keeps its intermediates in the caller's workspace, so that a test can read
+ * every stage of one call (tests/test_gpu_det_post_stages.py). Host code only; no effect on any launch. offsets receives
+ * SA_DET_BOXES_LAYOUT_WORDS values in this fixed order: the byte offsets of
+ *   st (PageState [batch]), hist (uint32 [batch][2048]), psum (double [batch][1024]), pcnt (uint32 [batch][1024]),
+ *   label, area, minx, maxx, miny, maxy, maxv (int32 / float bits [batch][height * width] each),
+ *   blk (int32 [batch][n_blk][2]), comp (CompStats [batch][max_boxes]), rowoff (int32 [batch][max_boxes]),
+ *   rmin, rmax (int32 [batch][row_cap] each), big (scratch of the tall-component launch),
+ * then big_stride (bytes of one scratch slice; 0 when the page height needs none), total (= surya_det_boxes_workspace_bytes),
+ * sizeof(PageState) and sizeof(CompStats) (csrc/det_post.h, csrc/det_post_core.h) for a caller that mirrors the two structs.
+ * n_blk: scan blocks of 4096 pixels per page; row_cap: entries of a page's rmin / rmax (either may be NULL).
+ * SA_ERR_ARG for a non-positive size, offsets == NULL or n_offsets < SA_DET_BOXES_LAYOUT_WORDS. */
+#define SA_DET_BOXES_LAYOUT_WORDS 21
+int surya_det_boxes_workspace_layout(int batch, int height, int width, int max_boxes, size_t* offsets, int n_offsets, int* n_blk,
+                                     int* row_cap);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Layout model family: Donut-Swin window-attention encoder + ADETR decoder with cross- and self-attention.

@@ -99,6 +99,9 @@ def lib() -> C.CDLL:
         _lib.surya_amd_version.restype = C.c_char_p
         _lib.surya_rec_workspace_bytes.restype = C.c_size_t
         _lib.surya_det_boxes_workspace_bytes.restype = C.c_size_t
+        _lib.surya_det_boxes_workspace_layout.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t), C.c_int,
+                                                          C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _lib.surya_det_boxes_workspace_layout.restype = C.c_int
         _bind_lay_ops(_lib)
     return _lib
 

@@ -621,6 +621,19 @@ size_t surya_det_boxes_workspace_bytes(int batch, int height, int width, int max
     return sa::post::post_layout(batch, height, width, max_boxes).total;
 }
 
+int surya_det_boxes_workspace_layout(int batch, int height, int width, int max_boxes, size_t* offsets, int n_offsets, int* n_blk,
+                                     int* row_cap) {
+    if (batch <= 0 || height <= 0 || width <= 0 || max_boxes <= 0 || !offsets || n_offsets < SA_DET_BOXES_LAYOUT_WORDS) return SA_ERR_ARG;
+    const sa::post::PostLayout L = sa::post::post_layout(batch, height, width, max_boxes);
+    const size_t o[SA_DET_BOXES_LAYOUT_WORDS] = {L.st, L.hist, L.psum, L.pcnt, L.label, L.area, L.minx, L.maxx, L.miny, L.maxy, L.maxv,
+                                                 L.blk, L.comp, L.rowoff, L.rmin, L.rmax, L.big, L.big_stride, L.total,
+                                                 sizeof(sa::post::PageState), sizeof(sa::post::CompStats)};
+    for (int i = 0; i < SA_DET_BOXES_LAYOUT_WORDS; ++i) offsets[i] = o[i];
+    if (n_blk) *n_blk = L.n_blk;
+    if (row_cap) *row_cap = L.row_cap;
+    return SA_OK;
+}
+
 int surya_det_boxes(const float* heat, long page_stride, int batch, int height, int width, float text_threshold, float low_text,
                     int max_boxes, float* boxes, float* conf, int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
     return sa::post::post_run(heat, page_stride, batch, height, width, text_threshold, low_text, max_boxes, boxes, conf, count,
