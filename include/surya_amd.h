@@ -972,6 +972,39 @@ int surya_det_boxes(const float* heat, long page_stride, int batch, int height, 
 int surya_det_boxes_workspace_layout(int batch, int height, int width, int max_boxes, size_t* offsets, int n_offsets, int* n_blk,
                                      int* row_cap);
 
+/* Tiled detection (DetectionPredictor.tiling; the grid and the ownership rule: surya_amd/detection/tiling.py): the two copies around
+ * the forward of a batch of tiles. Both read a DEVICE table of n descriptors, so one launch serves every tile of a model batch
+ * whatever pages they belong to. Enqueue only.
+ *
+ * surya_det_cut_tiles_u8: descriptor i copies the tile_size x tile_size window at (x0, y0) of its page into tile `tile` of
+ * dst, device uint8 [n_tiles][tile_size][tile_size][dst_pix] -- the batch surya_det_forward_u8 reads, written in place. White (255)
+ * outside the page (the origin may be negative), the fourth byte 0 when dst_pix is 4. descs: device array of
+ *   { uint64 src (device address of the page, uint8 [h][w][pix]); int32 w, h, pix (3 = RGB, 4 = RGBX, fourth byte ignored);
+ *     int32 x0, y0; int32 tile }                                                                        -- 32 bytes, C layout.
+ * SA_ERR_ARG, with nothing launched, when descs or dst is null, n < 0, n > 65535, n_tiles or tile_size is non-positive or dst_pix
+ * is not 3 or 4; n == 0 launches nothing. The table lives on the device, so what IT says is checked there: a descriptor with a
+ * null page, a non-positive size, a pix that is not 3 or 4 or a tile outside [0, n_tiles) writes nothing. Two descriptors of one
+ * launch must not name the same tile. A lane writes 16 bytes (four RGBX pixels) when tile_size % 4 == 0 and dst is 16-byte aligned
+ * (RGB: 12 bytes, dst 4-byte aligned), reading them as one 16-byte / three 4-byte loads where the source address allows it.
+ *
+ * surya_det_stitch_tiles: descriptor i copies the rectangle its tile OWNS, [ty0, ty0 + th) x [tx0, tx0 + tw) of the first `planes`
+ * planes of tile `tile` of heat, device fp32 [n_tiles][labels][tile_size][tile_size] (surya_det_forward_u8's output), to rows
+ * dy0.., columns dx0.. of the page map, and writes pad_cols zeros behind the rectangle's last column on each of those rows: the
+ * page map is fp32 [planes][rows][pitch] with pitch = the map width rounded up to 4 (surya_det_boxes wants width % 4 == 0), and
+ * the descriptors of a page's last tile column carry its pad columns -- zeroing them belongs to THIS entry point, the map needs no
+ * memset. Every map pixel has one owner, so a page stitched by several launches (its tiles span several forwards) equals the page
+ * stitched by one, in any order; cells no descriptor owns are left as they are. descs: device array of
+ *   { uint64 dst (device address of plane 0 of the page map); int64 pitch (floats per row); int64 plane_stride (floats between
+ *     planes); int32 tile; int32 tx0, ty0, tw, th; int32 dx0, dy0; int32 planes (1 .. labels); int32 pad_cols (0 .. 3);
+ *     int32 reserved }                                                                                  -- 64 bytes, C layout.
+ * SA_ERR_ARG, with nothing launched, when heat or descs is null, n < 0, n > 65535 or n_tiles, labels or tile_size is
+ * non-positive; n == 0 launches nothing. Checked on the device: a descriptor with a null map, a non-positive pitch, a tile outside
+ * [0, n_tiles), a rectangle that is empty or leaves the tile, a negative origin, planes outside 1 .. labels or pad_cols outside
+ * 0 .. 3 writes nothing. What a descriptor addresses in the page or the map is not checked against their ends: the caller keeps
+ * them inside. Rectangles of one launch must not overlap in a map. */
+int surya_det_cut_tiles_u8(const void* descs, int n, uint8_t* dst, int n_tiles, int tile_size, int dst_pix, void* stream);
+int surya_det_stitch_tiles(const float* heat, int n_tiles, int labels, int tile_size, const void* descs, int n, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Layout model family: Donut-Swin window-attention encoder + ADETR decoder with cross- and self-attention.
  * Replaces DonutSwinLayoutModel.forward (surya/layout/model/encoder.py:36-80, surya/common/donut/encoder.py) and

@@ -226,6 +226,15 @@ def _bind_lay_ops(lib):
     lib.surya_op_decode_attn_kv8_mx.restype = C.c_int
 
 
+def bind_det_tile(lib):
+    """Tiled detection (csrc/det_tile.h): the cut in front of a forward of tiles and the stitch behind it; `descs` is a DEVICE table.
+    Bound by HipDetTiler, not at load: an A/B build from before these entries (SURYA_AMD_LIB) still serves every other path."""
+    i, p = C.c_int, C.c_void_p
+    lib.surya_det_cut_tiles_u8.argtypes, lib.surya_det_cut_tiles_u8.restype = [p, i, p, i, i, i, p], C.c_int
+    lib.surya_det_stitch_tiles.argtypes, lib.surya_det_stitch_tiles.restype = [p, i, i, i, p, i, p], C.c_int
+    return lib
+
+
 def check(rc: int, what: str):
     if rc != 0:
         raise SuryaAmdError(f"{what} failed: {_ERR.get(rc, 'hipError ' + str(rc))} ({rc})")

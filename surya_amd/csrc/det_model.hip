@@ -14,6 +14,7 @@
 #include "det_head.h"
 #include "det_post.h"
 #include "resample.h"
+#include "det_tile.h"
 
 namespace sa {
 
@@ -678,6 +679,14 @@ int surya_reduce_u8(const uint8_t* src, int src_w, int src_h, int src_pix, uint8
     if (!src || !dst || src_w <= 0 || src_h <= 0 || fx < 1 || fy < 1 || fx > 255 || fy > 255 || (fx == 1 && fy == 1)) return SA_ERR_ARG;
     if ((src_pix != 3 && src_pix != 4) || (dst_pix != 3 && dst_pix != 4) || (dst_pix == 4 && (uintptr_t)dst % 4 != 0)) return SA_ERR_ARG;
     return sa::rs::reduce_run(src, src_w, src_h, src_pix, dst, dst_pix, fx, fy, (hipStream_t)stream);
+}
+
+int surya_det_cut_tiles_u8(const void* descs, int n, uint8_t* dst, int n_tiles, int tile_size, int dst_pix, void* stream) {
+    return sa::tile::cut_tiles_run(descs, n, dst, n_tiles, tile_size, dst_pix, (hipStream_t)stream);
+}
+
+int surya_det_stitch_tiles(const float* heat, int n_tiles, int labels, int tile_size, const void* descs, int n, void* stream) {
+    return sa::tile::stitch_tiles_run(heat, n_tiles, labels, tile_size, descs, n, (hipStream_t)stream);
 }
 
 }  // extern "C"

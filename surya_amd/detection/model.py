@@ -304,3 +304,44 @@ class DeviceResampler:
                                                    C.c_int(out.shape[2]), L.ptr(bx), L.ptr(kx), C.c_int(ksx), L.ptr(by), L.ptr(ky),
                                                    C.c_int(ksy), L.ptr(tmp), stream), "surya_resample_lanczos_u8")
         return out
+
+
+# must match sa::tile::CutDesc / StitchDesc (csrc/det_tile.h, include/surya_amd.h): DEVICE tables, one entry per tile
+CUT_DESC = np.dtype([("src", "<u8"), ("w", "<i4"), ("h", "<i4"), ("pix", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("tile", "<i4")])
+STITCH_DESC = np.dtype([("dst", "<u8"), ("pitch", "<i8"), ("plane_stride", "<i8"), ("tile", "<i4"), ("tx0", "<i4"), ("ty0", "<i4"),
+                        ("tw", "<i4"), ("th", "<i4"), ("dx0", "<i4"), ("dy0", "<i4"), ("planes", "<i4"), ("pad_cols", "<i4"),
+                        ("reserved", "<i4")])
+assert CUT_DESC.itemsize == 32 and STITCH_DESC.itemsize == 64
+
+
+class HipDetTiler:
+    """The two copies of tiled detection (surya_det_cut_tiles_u8, surya_det_stitch_tiles; csrc/det_tile.h): windows of uint8 pages ->
+    the tile batch `forward_u8` reads, and the rectangle every tile owns of its heat planes -> the page map. Descriptor tables are
+    device memory (a uint8 tensor holding CUT_DESC / STITCH_DESC records); the predictor uploads them with the pages."""
+
+    def __init__(self, device="cuda:0"):
+        if not torch.cuda.is_available():
+            raise L.SuryaAmdError("HipDetTiler needs a GPU (MI355X); there is no CPU fallback")
+        self.lib = L.bind_det_tile(L.lib())
+        self.device = torch.device(device)
+
+    def table(self, descs: np.ndarray) -> torch.Tensor:
+        """A host descriptor array as a device table (op-level callers; the predictor packs its tables into the batch's staging buffer)."""
+        assert descs.dtype in (CUT_DESC, STITCH_DESC)
+        return torch.from_numpy(np.ascontiguousarray(descs).view(np.uint8).copy()).to(self.device)
+
+    def cut(self, table: torch.Tensor, n: int, dst: torch.Tensor):
+        """table: device uint8, n CUT_DESC records; dst: cuda uint8 [tiles, P, P, 3 | 4], written in place."""
+        assert table.is_cuda and table.dtype == torch.uint8 and table.numel() >= n * CUT_DESC.itemsize and table.data_ptr() % 8 == 0
+        assert dst.is_cuda and dst.dtype == torch.uint8 and dst.is_contiguous() and dst.dim() == 4 and dst.shape[1] == dst.shape[2]
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.surya_det_cut_tiles_u8(L.ptr(table), n, L.ptr(dst), dst.shape[0], dst.shape[1], dst.shape[3], stream),
+                "surya_det_cut_tiles_u8")
+
+    def stitch(self, heat: torch.Tensor, table: torch.Tensor, n: int):
+        """heat: cuda fp32 [tiles, labels, P, P]; table: device uint8, n STITCH_DESC records naming the page maps."""
+        assert table.is_cuda and table.dtype == torch.uint8 and table.numel() >= n * STITCH_DESC.itemsize and table.data_ptr() % 8 == 0
+        assert heat.is_cuda and heat.dtype == torch.float32 and heat.is_contiguous() and heat.dim() == 4 and heat.shape[2] == heat.shape[3]
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.surya_det_stitch_tiles(L.ptr(heat), heat.shape[0], heat.shape[1], heat.shape[2], L.ptr(table), n, stream),
+                "surya_det_stitch_tiles")

@@ -19,9 +19,10 @@ from ..common.imageops import copy_pool, page_pixels, parallel_copy
 from ..common.predictor import BasePredictor, ModelLoader, gc_paused
 from ..config import DetConfig, det_config
 from ..settings import settings
-from .heatmap import TextDetectionResult, parallel_get_boxes, result_from_device_boxes
+from .heatmap import TextDetectionResult, detect_boxes, parallel_get_boxes, result_from_device_boxes
 from ..common.pil_resample import plan_chain as plan_resize
-from .model import DeviceResampler, HipDetModel, HipDetPost
+from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetModel, HipDetPost, HipDetTiler
+from .tiling import DetTiling, check_tiling, page_plan  # noqa: F401  (DetTiling: what `DetectionPredictor.tiling` takes)
 
 
 class SegformerImageProcessor:
@@ -130,6 +131,23 @@ class DetectionModelLoader(ModelLoader):
         return p
 
 
+def _one_batch_ahead(launched, finish, eager_first=False):
+    """One batch in flight ahead of the one being read: `launched` prepares (PIL convert / resize, pinned staging) and launches batch
+    i + 1 while the GPU still works on batch i, whose boxes `finish` only then waits for. eager_first: the FIRST batch is handed over
+    as soon as its boxes exist instead of after the second batch has been prepared and launched."""
+    prev = None
+    for job in launched:
+        if prev is not None:
+            yield finish(prev)
+        prev = job
+        if eager_first:
+            eager_first = False
+            yield finish(prev)
+            prev = None
+    if prev is not None:
+        yield finish(prev)
+
+
 class DetectionPredictor(BasePredictor):
     model_loader_cls = DetectionModelLoader
     batch_size = settings.DETECTOR_BATCH_SIZE
@@ -164,7 +182,19 @@ class DetectionPredictor(BasePredictor):
     # the host, or already there. With device_resize, "host" counts only images more than 100 times as tall as wide.
     last_resize_paths = {"device": 0, "host": 0, "ready": 0}
 
+    # Tiled detection (detection/tiling.py states the rules): None = every page, or strip of a tall page, is squeezed onto the processor's
+    # square as the reference does; a DetTiling = the page at `scale` times its own resolution is cut into processor-sized tiles on the
+    # device, the tiles' heat maps are stitched into ONE page map there (every pixel from the tile that saw it farthest from a cut), and
+    # the thresholds, the labelling and the boxes are those of that whole map: a line across a tile border stays one box.
+    tiling = None
+    # per page of the last tiled call: {"size": (mw, mh) of the scaled page and its map, "grid": (columns, rows), "tiles": their product}
+    last_tiling: list = []
+
     def _detect(self, images: List[Image.Image], batch_size=None, include_maps=False) -> List[TextDetectionResult]:
+        if self.tiling is not None:
+            check_tiling(self.tiling, self.processor.size["height"])
+            if not self.device_postprocess:
+                return self._detect_tiled_host(images, batch_size, include_maps)
         if self.device_postprocess:
             return self._detect_device(images, batch_size, include_maps)
         gen = self.batch_detection(images, batch_size=batch_size)
@@ -196,9 +226,14 @@ class DetectionPredictor(BasePredictor):
         """eager_first: hand the FIRST batch over as soon as its boxes exist instead of after the second batch has been prepared and
         launched -- a consumer that starts other device work from it (the streamed recognise call) gets going one host preparation
         (~10 ms per 16 pages) earlier, at the price of that much overlap inside the detector."""
+        if self.tiling is not None:
+            check_tiling(self.tiling, self.processor.size["height"])
         if getattr(self, "_post", None) is None:
             self._post = HipDetPost(self.model.device)
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
+        if self.tiling is not None:
+            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first)
+            return
 
         def finish(job):
             """Results of one launched batch (waits for ITS event only)."""
@@ -222,46 +257,174 @@ class DetectionPredictor(BasePredictor):
                 out.append(result_from_device_boxes(bx, cf, list(psize), sizes[pg], hi, ai))
             return out
 
-        # One batch in flight ahead of the one being read: the generator prepares (PIL convert / resize, pinned staging) and
-        # launches batch i + 1 while the GPU still works on batch i, whose boxes are only then waited for.
-        prev = None
-        for heat, split_index, split_heights, sizes in self.batch_heatmaps(images, batch_size):
-            ph, pw = heat.shape[2], heat.shape[3]
-            n_pages = split_index[-1] + 1
-            tiles_of = [[i for i, k in enumerate(split_index) if k == page] for page in range(n_pages)]
-            whole = [page for page in range(n_pages) if len(tiles_of[page]) == 1]
-            jobs = []
-            if whole:
-                sel = heat if len(whole) == heat.shape[0] else heat[[tiles_of[pg][0] for pg in whole]].contiguous()
-                jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole)))
-            # tall pages: strips re-assembled on the device (:134-151); pages of equal height share ONE post-processing call (a call per
-            # page was 17 launches + a D2H each: 16 letter pages spent 40 of their 77 ms there, tools/hostbench/det_letter_profile.py)
-            by_height = {}
-            for pg in range(n_pages):
-                if len(tiles_of[pg]) > 1:
-                    by_height.setdefault(sum(split_heights[t] for t in tiles_of[pg]), []).append(pg)
-            for hf, pgs in by_height.items():
-                full = torch.empty((len(pgs), hf, pw), dtype=heat.dtype, device=heat.device)
-                for i, pg in enumerate(pgs):
-                    r0 = 0
-                    for t in tiles_of[pg]:
-                        full[i, r0: r0 + split_heights[t]] = heat[t, 0, : split_heights[t]]
-                        r0 += split_heights[t]
-                jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs)))
-            job = (jobs, n_pages, tiles_of, split_heights, sizes, heat, pw)
-            if prev is not None:
-                yield finish(prev)
-            prev = job
-            if eager_first:
-                eager_first = False
-                yield finish(prev)
-                prev = None
-        if prev is not None:
-            yield finish(prev)
+        def launched():
+            for heat, split_index, split_heights, sizes in self.batch_heatmaps(images, batch_size):
+                ph, pw = heat.shape[2], heat.shape[3]
+                n_pages = split_index[-1] + 1
+                tiles_of = [[i for i, k in enumerate(split_index) if k == page] for page in range(n_pages)]
+                whole = [page for page in range(n_pages) if len(tiles_of[page]) == 1]
+                jobs = []
+                if whole:
+                    sel = heat if len(whole) == heat.shape[0] else heat[[tiles_of[pg][0] for pg in whole]].contiguous()
+                    jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole)))
+                # tall pages: strips re-assembled on the device (:134-151); pages of equal height share ONE post-processing call (a call per
+                # page was 17 launches + a D2H each: 16 letter pages spent 40 of their 77 ms there, tools/hostbench/det_letter_profile.py)
+                by_height = {}
+                for pg in range(n_pages):
+                    if len(tiles_of[pg]) > 1:
+                        by_height.setdefault(sum(split_heights[t] for t in tiles_of[pg]), []).append(pg)
+                for hf, pgs in by_height.items():
+                    full = torch.empty((len(pgs), hf, pw), dtype=heat.dtype, device=heat.device)
+                    for i, pg in enumerate(pgs):
+                        r0 = 0
+                        for t in tiles_of[pg]:
+                            full[i, r0: r0 + split_heights[t]] = heat[t, 0, : split_heights[t]]
+                            r0 += split_heights[t]
+                    jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs)))
+                yield (jobs, n_pages, tiles_of, split_heights, sizes, heat, pw)
 
-    def resize_image(self, img: Image.Image) -> np.ndarray:
-        """The reference's double LANCZOS resize to the processor size (surya/detection/__init__.py:50-57), uint8 HWC."""
-        new_size = (self.processor.size["width"], self.processor.size["height"])
+        yield from _one_batch_ahead(launched(), finish, eager_first)
+
+    # ------------------------------------------------------------------------------------------------------------ tiled detection
+    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first):
+        """_iter_detect_device under `tiling`: the same one-batch-ahead hand-over, a page's boxes from its stitched map."""
+        tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
+
+        def finish(job):
+            groups, sizes, pendings = job
+            out = [None] * len(sizes)
+            for (ks, maps, (mw, mh)), pending in zip(groups, pendings):
+                host = maps.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
+                for i, (k, (bx, cf)) in enumerate(zip(ks, self._post.collect(pending))):
+                    out[k] = result_from_device_boxes(bx, cf, [mw, mh], sizes[k], *self._map_images(host, i, mw, mh))
+            return out
+
+        def launched():
+            for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
+                # pages of equal map size share ONE post-processing call, as tall pages of equal height do
+                yield groups, sizes, [self._post.launch(maps, tt, lt) for _, maps, _ in groups]
+
+        yield from _one_batch_ahead(launched(), finish, eager_first)
+
+    def _detect_tiled_host(self, images, batch_size, include_maps):
+        """The checker arm under `tiling` (DETECTOR_POSTPROCESS_HOST): the stitched maps D2H, heatmap.py on them."""
+        tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
+        out = []
+        for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
+            res = [None] * len(sizes)
+            for ks, maps, (mw, mh) in groups:
+                host = maps.cpu().numpy()
+                for i, k in enumerate(ks):
+                    boxes, confs = detect_boxes(host[i, 0], tt, lt)
+                    res[k] = result_from_device_boxes(boxes, confs, [mw, mh], sizes[k], *self._map_images(host if include_maps else None, i, mw, mh))
+            out.extend(res)
+        return out
+
+    @staticmethod
+    def _map_images(host, i, mw, mh):
+        """include_maps under `tiling`: the stitched valid region (mh x mw) of both planes, as the reference's images."""
+        if host is None:
+            return None, None
+        return tuple(Image.fromarray((host[i, pl, :mh, :mw] * 255).astype(np.uint8)) for pl in (0, 1))
+
+    def _tiled_batches(self, images, batch_size, planes):
+        """Upload -> [scale] -> per forward: cut, model, stitch (detection/tiling.py). Yields per batch of pages (groups, page sizes), groups =
+        [(pages of the batch, their maps cuda fp32 [n, planes, mh, round_up(mw, 4)], (mw, mh))]: pages of equal map size lie in one tensor.
+        Everything is enqueued and nothing waited for."""
+        assert all(isinstance(im, Image.Image) for im in images)
+        P = self.processor.size["height"]
+        assert self.processor.size["width"] == P
+        tiling = check_tiling(self.tiling, P)
+        if batch_size is None:
+            batch_size = self.get_batch_size()
+        mb = self.model.max_batch
+        batch_size = min(batch_size, mb)
+        plans = [page_plan(im.size[0], im.size[1], P, tiling) for im in images]
+        self.last_tiling = [{"size": pl.map_size, "grid": pl.grid, "tiles": pl.n_tiles} for pl in plans]
+        batches, cur, cur_n = [], [], 0
+        for i, pl in enumerate(plans):                             # greedy packing by tile count, as strips are packed
+            if cur_n + pl.n_tiles > batch_size:
+                if cur:
+                    batches.append(cur)
+                cur, cur_n = [], 0
+            cur.append(i)
+            cur_n += pl.n_tiles
+        if cur:
+            batches.append(cur)
+        paths = self.last_resize_paths = {"device": 0, "host": 0, "ready": 0}
+        if getattr(self, "_tiler", None) is None:
+            self._tiler = HipDetTiler(self.model.device)
+        dev = self.model.device
+        for idxs in batches:
+            pages = [images[j] if images[j].mode == "RGB" else images[j].convert("RGB") for j in idxs]
+            bplans = [plans[j] for j in idxs]
+            # how a page becomes its scaled page S: [] = it is S, a list of steps = on the device, None = Pillow on the host
+            chains = [[] if pl.map_size == pl.size else (plan_resize(pl.size[0], pl.size[1], pl.map_size) if self.device_resize else None)
+                      for pl in bplans]
+            for ch in chains:
+                paths["device" if ch else "ready" if ch is not None else "host"] += 1
+
+            def pixels(k):
+                return self.resize_image(pages[k], bplans[k].map_size) if chains[k] is None else page_pixels(pages[k])
+            px = list(copy_pool().map(pixels, range(len(pages)))) if len(pages) > 1 else [pixels(0)]
+            # ONE pinned staging buffer and ONE H2D copy per batch: the pages whole, then the two descriptor tables
+            n_tiles = sum(pl.n_tiles for pl in bplans)
+            sizes_b = [int(a.nbytes) for a in px]
+            offs = np.concatenate([[0], np.cumsum([(b + 255) & ~255 for b in sizes_b])]).astype(np.int64)
+            cut_off = int(offs[-1])
+            stitch_off = cut_off + n_tiles * CUT_DESC.itemsize
+            stage = torch.empty(stitch_off + n_tiles * STITCH_DESC.itemsize, dtype=torch.uint8, pin_memory=True)
+            sv = stage.numpy()
+            parallel_copy([sv[int(o): int(o) + b].reshape(a.shape) for a, o, b in zip(px, offs[:-1], sizes_b)], px)
+            dev_stage = torch.empty(stage.numel(), dtype=torch.uint8, device=dev)
+            scaled = [torch.empty((pl.map_size[1], pl.map_size[0], 4), dtype=torch.uint8, device=dev) if ch else None
+                      for pl, ch in zip(bplans, chains)]
+            by_size = {}
+            for k, pl in enumerate(bplans):
+                by_size.setdefault(pl.map_size, []).append(k)
+            groups, map_of = [], {}
+            for (mw, mh), ks in by_size.items():
+                maps = torch.empty((len(ks), planes, mh, (mw + 3) & ~3), dtype=torch.float32, device=dev)
+                groups.append((ks, maps, (mw, mh)))
+                for i, k in enumerate(ks):
+                    map_of[k] = maps[i].data_ptr()
+            # the tiles of the batch in page order, row-major inside a page; a tile's index is its place in ITS forward
+            cut, st = np.zeros(n_tiles, CUT_DESC), np.zeros(n_tiles, STITCH_DESC)
+            t = 0
+            for k, pl in enumerate(bplans):
+                mw, mh = pl.map_size
+                src = ((scaled[k].data_ptr(), mw, mh, 4) if scaled[k] is not None
+                       else (dev_stage.data_ptr() + int(offs[k]), px[k].shape[1], px[k].shape[0], px[k].shape[2]))
+                for x0, y0, (ox0, ox1), (oy0, oy1) in pl.tiles():
+                    cut[t] = (*src, x0, y0, t % mb)
+                    st[t] = (map_of[k], pl.pitch, mh * pl.pitch, t % mb, ox0 - x0, oy0 - y0, ox1 - ox0, oy1 - oy0, ox0, oy0, planes,
+                             pl.pitch - mw if ox1 == mw else 0, 0)
+                    t += 1
+            sv[cut_off: stitch_off] = cut.view(np.uint8)
+            sv[stitch_off:] = st.view(np.uint8)
+            dev_stage.copy_(stage, non_blocking=True)
+            for k, ch in enumerate(chains):
+                if ch:
+                    if getattr(self, "_resampler", None) is None:
+                        self._resampler = DeviceResampler(dev)
+                    img = dev_stage[int(offs[k]): int(offs[k]) + sizes_b[k]].view(px[k].shape)
+                    for i, step in enumerate(ch):              # [thumbnail's box reduction,] thumbnail's size, then the scaled size
+                        if step[0] == "reduce":
+                            img = self._resampler.reduce(img, step[1], step[2])
+                        else:
+                            img = self._resampler.resize(img, step[1], out=scaled[k] if i == len(ch) - 1 else None, box=step[2])
+            for s in range(0, n_tiles, mb):                        # a page with more tiles than the batch: chunks of max_batch, stitched as they come
+                n = min(mb, n_tiles - s)
+                tiles = torch.empty((n, P, P, 4), dtype=torch.uint8, device=dev)
+                self._tiler.cut(dev_stage[cut_off + s * CUT_DESC.itemsize:], n, tiles)
+                heat = self.model.forward_u8(tiles, self.processor.image_mean, self.processor.image_std)
+                self._tiler.stitch(heat, dev_stage[stitch_off + s * STITCH_DESC.itemsize:], n)
+            yield groups, [images[j].size for j in idxs]
+
+    def resize_image(self, img: Image.Image, size=None) -> np.ndarray:
+        """The reference's double LANCZOS resize to the processor size (surya/detection/__init__.py:50-57), or to `size` (a tiled page's
+        scaled size), uint8 HWC."""
+        new_size = size or (self.processor.size["width"], self.processor.size["height"])
         if img.size != new_size:
             img = img.copy()                                          # thumbnail() works in place; the page may be the caller's
             img.thumbnail(new_size, Image.Resampling.LANCZOS)
