@@ -1005,6 +1005,25 @@ int surya_det_boxes_workspace_layout(int batch, int height, int width, int max_b
 int surya_det_cut_tiles_u8(const void* descs, int n, uint8_t* dst, int n_tiles, int tile_size, int dst_pix, void* stream);
 int surya_det_stitch_tiles(const float* heat, int n_tiles, int labels, int tile_size, const void* descs, int n, void* stream);
 
+/* Page skew from the heat map (DetectionPredictor.skew; the rule: surya_amd/detection/skew.py, the arithmetic: csrc/det_skew_core.h):
+ * the projection profile of every page's text pixels under every candidate angle, scored by the sum of squared differences of
+ * neighbouring bins. Integers only, so the scores equal the numpy statement bit for bit. Enqueue only.
+ * heat is addressed as surya_det_boxes addresses it: page b starts at heat + b * page_stride (floats), is [height][width], width % 4
+ * == 0; pixel (x, y) is text iff heat > threshold (strict). cs: device int32 [batch][n_angles][2] = (c, s) = (rint(cos * 65536),
+ * rint(sin * 65536)) of the candidate's angle IN THE MAP, every page its own table; a text pixel falls into bin
+ * r = (y * c - x * s + (width - 1) * max(s, 0)) >> 16 of height + width bins (int32 arithmetic: c > 0, |s| <= c and sizes <= 8192 keep
+ * it below 2^31). scores: device uint64 [batch][n_angles] = sum over r of (P[r + 1] - P[r])^2; n_text: device int32 [batch] = the
+ * page's text pixels (it is the compaction's counter: zeroed and counted by the call). A page without text scores 0 everywhere.
+ * workspace: device, caller-owned, >= surya_det_skew_workspace_bytes(...) (a word per map pixel: the lists of text pixels).
+ * SA_ERR_ARG, with nothing launched, for a null pointer (heat, cs, scores, n_text, workspace), a negative batch, a non-positive
+ * height or width, n_angles outside 1 .. 1024, a negative or NaN threshold or a workspace that is too small; SA_ERR_SHAPE for a height
+ * or width above 8192, width % 4 != 0, page_stride % 4 != 0 or a heat pointer that is not 16-byte aligned; batch == 0 launches
+ * nothing. The coefficient table lives on the device and is read unchecked: the kernel does not count a bin outside
+ * [0, height + width), so a table that breaks the bounds above gives wrong scores and touches no memory it should not. */
+size_t surya_det_skew_workspace_bytes(int batch, int height, int width);
+int surya_det_skew(const float* heat, long page_stride, int batch, int height, int width, float threshold, const int32_t* cs, int n_angles,
+                   uint64_t* scores, int32_t* n_text, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Layout model family: Donut-Swin window-attention encoder + ADETR decoder with cross- and self-attention.
  * Replaces DonutSwinLayoutModel.forward (surya/layout/model/encoder.py:36-80, surya/common/donut/encoder.py) and

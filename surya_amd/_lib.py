@@ -235,6 +235,14 @@ def bind_det_tile(lib):
     return lib
 
 
+def bind_det_skew(lib):
+    """Page skew from the heat map (csrc/det_skew.h); `cs` is a DEVICE table. Bound by HipDetSkew, not at load, as bind_det_tile is."""
+    i, l, f, p = C.c_int, C.c_long, C.c_float, C.c_void_p
+    lib.surya_det_skew_workspace_bytes.argtypes, lib.surya_det_skew_workspace_bytes.restype = [i, i, i], C.c_size_t
+    lib.surya_det_skew.argtypes, lib.surya_det_skew.restype = [p, l, i, i, i, f, p, i, p, p, p, C.c_size_t, p], C.c_int
+    return lib
+
+
 def check(rc: int, what: str):
     if rc != 0:
         raise SuryaAmdError(f"{what} failed: {_ERR.get(rc, 'hipError ' + str(rc))} ({rc})")

@@ -15,6 +15,7 @@
 #include "det_post.h"
 #include "resample.h"
 #include "det_tile.h"
+#include "det_skew.h"
 
 namespace sa {
 
@@ -639,6 +640,17 @@ int surya_det_boxes(const float* heat, long page_stride, int batch, int height, 
                     int max_boxes, float* boxes, float* conf, int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
     return sa::post::post_run(heat, page_stride, batch, height, width, text_threshold, low_text, max_boxes, boxes, conf, count,
                               workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+size_t surya_det_skew_workspace_bytes(int batch, int height, int width) {
+    if (batch <= 0 || height <= 0 || width <= 0) return 0;
+    return sa::skew::skew_workspace_bytes(batch, height, width);
+}
+
+int surya_det_skew(const float* heat, long page_stride, int batch, int height, int width, float threshold, const int32_t* cs, int n_angles,
+                   uint64_t* scores, int32_t* n_text, void* workspace, size_t workspace_bytes, void* stream) {
+    return sa::skew::skew_run(heat, page_stride, batch, height, width, threshold, cs, n_angles, scores, n_text, workspace, workspace_bytes,
+                              (hipStream_t)stream);
 }
 
 int surya_det_forward(surya_det* h, const float* pixel_values, int batch, float* heatmaps, float* lowres, void* stream) {

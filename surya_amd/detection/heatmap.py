@@ -13,7 +13,9 @@ from typing import List, Optional
 
 import numpy as np
 from PIL import Image
-from pydantic import BaseModel
+import inspect
+
+from pydantic import BaseModel, Field, model_serializer
 from scipy import ndimage
 
 from ..common.geometry import PolygonBox
@@ -25,12 +27,34 @@ class ColumnLine(PolygonBox):
     horizontal: bool
 
 
+_EXCLUDE_IF = "exclude_if" in inspect.signature(Field).parameters          # pydantic >= 2.12: the exclusion runs inside pydantic-core
+
+
 class TextDetectionResult(BaseModel):       # surya/detection/schema.py:12-17
     bboxes: List[PolygonBox]
     vertical_lines: List[ColumnLine]
     heatmap: Optional[object]
     affinity_map: Optional[object]
     image_bbox: List[float]
+    # `skew` (DetectionPredictor.skew): the angle in degrees of the page's text baselines, image coordinates with y down (positive = the
+    # lines run down to the right), estimated from the heat map the boxes come from (detection/skew.py); `skew_confidence` = 1 - median
+    # score / best score. Both None while `skew` is None on the predictor, or when the page has no estimate, and then left out of the
+    # serialised form, which stays the reference's (the pattern of recognition/schema.py).
+    if _EXCLUDE_IF:
+        skew: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
+        skew_confidence: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
+    else:
+        skew: Optional[float] = None
+        skew_confidence: Optional[float] = None
+
+        @model_serializer(mode="wrap")
+        def _without_absent_skew(self, handler):
+            d = handler(self)
+            if self.skew is None:
+                d.pop("skew", None)
+            if self.skew_confidence is None:
+                d.pop("skew_confidence", None)
+            return d
 
 
 def get_dynamic_thresholds(linemap, text_threshold, low_text, typical_top10_avg=0.7):

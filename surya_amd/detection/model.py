@@ -243,6 +243,63 @@ class HipDetPost:
         return self.collect(self.launch(heat, text_threshold, low_text))
 
 
+class HipDetSkew:
+    """Heat map -> projection-profile scores of every candidate angle on the device (surya_det_skew, csrc/det_skew.h): the estimator
+    behind DetectionPredictor.skew (detection/skew.py states the rule and chooses the angle from the scores). Owns the workspace; `launch`
+    enqueues behind whatever is on the stream (the predictor: behind surya_det_boxes of the same maps), `collect` waits for ITS event."""
+
+    def __init__(self, device="cuda:0"):
+        if not torch.cuda.is_available():
+            raise L.SuryaAmdError("HipDetSkew needs a GPU (MI355X); there is no CPU fallback")
+        self.lib = L.bind_det_skew(L.lib())
+        self.device = torch.device(device)
+        self._ws = None
+
+    def _workspace(self, B, H, W):
+        need = int(self.lib.surya_det_skew_workspace_bytes(B, H, W))
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._ws, need
+
+    def launch(self, heat: torch.Tensor, tables: np.ndarray, threshold: float):
+        """heat: as HipDetPost.launch takes it ([B, H, W], or [B, labels, H, W] whose plane 0 is the text map); tables: int32
+        [B, n_angles, 2] = (c, s), every page its own (skew.coeff_table). Returns a handle for `collect`; nothing here waits."""
+        assert heat.is_cuda and heat.dtype == torch.float32 and heat.is_contiguous()
+        if heat.dim() == 4:
+            B, Lb, H, W = heat.shape
+            stride = Lb * H * W
+        else:
+            B, H, W = heat.shape
+            stride = H * W
+        tables = np.ascontiguousarray(tables, np.int32)
+        assert tables.ndim == 3 and tables.shape[0] == B and tables.shape[2] == 2
+        n = tables.shape[1]
+        torch.cuda.set_device(self.device)
+        ws, need = self._workspace(B, H, W)
+        hcs = torch.empty(tables.shape, dtype=torch.int32, pin_memory=True)
+        hcs.numpy()[...] = tables
+        cs = hcs.to(self.device, non_blocking=True)
+        scores = torch.empty((B, n), dtype=torch.int64, device=self.device)              # uint64 on the device; torch moves the bits
+        n_text = torch.empty((B,), dtype=torch.int32, device=self.device)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        L.check(self.lib.surya_det_skew(L.ptr(heat), stride, B, H, W, float(threshold), L.ptr(cs), n, L.ptr(scores), L.ptr(n_text), L.ptr(ws),
+                                        need, stream), "surya_det_skew")
+        hs = torch.empty(scores.shape, dtype=torch.int64, pin_memory=True).copy_(scores, non_blocking=True)
+        hn = torch.empty(n_text.shape, dtype=torch.int32, pin_memory=True).copy_(n_text, non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return (ev, hs, hn, heat, hcs, cs)              # `heat`, the tables and their staging ride along: they must outlive the kernels
+
+    def collect(self, pending):
+        """(scores uint64 [B, n_angles], n_text int32 [B]) of a launched batch."""
+        ev, hs, hn = pending[:3]
+        ev.synchronize()
+        return hs.numpy().view(np.uint64).copy(), hn.numpy().copy()
+
+    def __call__(self, heat: torch.Tensor, tables: np.ndarray, threshold: float):
+        return self.collect(self.launch(heat, tables, threshold))
+
+
 class DeviceResampler:
     """Pillow LANCZOS resizes (surya_resample_lanczos_u8) and integer box reductions (surya_reduce_u8) of uint8 pages on the
     device (csrc/resample.h). Coefficient tables are built once per (source length, target length, source span) by

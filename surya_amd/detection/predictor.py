@@ -21,7 +21,9 @@ from ..config import DetConfig, det_config
 from ..settings import settings
 from .heatmap import TextDetectionResult, detect_boxes, parallel_get_boxes, result_from_device_boxes
 from ..common.pil_resample import plan_chain as plan_resize
-from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetModel, HipDetPost, HipDetTiler
+from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetModel, HipDetPost, HipDetSkew, HipDetTiler
+from . import skew as skew_rule
+from .skew import SkewEstimate, straighten  # noqa: F401  (SkewEstimate: what `DetectionPredictor.skew` takes)
 from .tiling import DetTiling, check_tiling, page_plan  # noqa: F401  (DetTiling: what `DetectionPredictor.tiling` takes)
 
 
@@ -190,24 +192,78 @@ class DetectionPredictor(BasePredictor):
     # per page of the last tiled call: {"size": (mw, mh) of the scaled page and its map, "grid": (columns, rows), "tiles": their product}
     last_tiling: list = []
 
+    # Page skew (detection/skew.py states the rule): None = nothing is estimated and nothing is launched; a SkewEstimate = every result
+    # carries `skew` (degrees, the page's text baselines, positive = down to the right) and `skew_confidence`, estimated from the SAME
+    # page map its boxes come from -- the whole tile, the device-side reassembly of a tall page's strips, or the stitched map under
+    # `tiling` -- by surya_det_skew, enqueued behind that map's surya_det_boxes. No additional forward pass.
+    skew = None
+    # per page of the last call with `skew` set: {"angle", "confidence", "n_text" (text pixels of the map), "map_size" (w, h)}
+    last_skew: list = []
+
+    def _check_skew(self, images):
+        """The refusals of `skew` before any device work; returns the estimate's (candidate angles, mask threshold), or None when off."""
+        if self.skew is None:
+            return None
+        est = skew_rule.check_skew(self.skew)
+        P = self.processor.size["height"]
+        pw = self.processor.size["width"]
+        geo = []
+        for im in images:
+            w, h = im.size
+            if self.tiling is not None:
+                geo.append(((w, h), page_plan(w, h, P, self.tiling).map_size))
+            else:
+                geo.append(((w, h), (pw, h if get_total_splits((w, h), P) > 1 else P)))
+        skew_rule.check_skew(est, geo)
+        self.last_skew = []
+        return skew_rule.candidate_angles(est), float(settings.DETECTOR_BLANK_THRESHOLD if est.threshold is None else est.threshold)
+
+    def _skew_launch(self, sk, maps, page_sizes, map_size):
+        """surya_det_skew on the maps a surya_det_boxes launch just took: every page its own table from the one candidate list."""
+        if getattr(self, "_skew_op", None) is None:
+            self._skew_op = HipDetSkew(self.model.device)
+        tables = np.stack([skew_rule.coeff_table(sk[0], ps, map_size) for ps in page_sizes])
+        return self._skew_op.launch(maps, tables, sk[1])
+
+    def _skew_set(self, sk, result, scores, n_text, map_size):
+        """The choice (host, float64) from one page's scores, onto its result and into last_skew."""
+        angle, conf = skew_rule.choose(scores, int(n_text), sk[0], self.skew.step, self.skew.min_pixels)
+        result.skew, result.skew_confidence = angle, conf
+        return {"angle": angle, "confidence": conf, "n_text": int(n_text), "map_size": (int(map_size[0]), int(map_size[1]))}
+
+    def _skew_host(self, sk, result, heat, page_size, map_size):
+        """The checker arm (DETECTOR_POSTPROCESS_HOST): the numpy reference on the downloaded map."""
+        scores, n_text = skew_rule.skew_scores(heat, sk[1], skew_rule.coeff_table(sk[0], page_size, map_size))
+        return self._skew_set(sk, result, scores, n_text, map_size)
+
     def _detect(self, images: List[Image.Image], batch_size=None, include_maps=False) -> List[TextDetectionResult]:
         if self.tiling is not None:
             check_tiling(self.tiling, self.processor.size["height"])
-            if not self.device_postprocess:
-                return self._detect_tiled_host(images, batch_size, include_maps)
+        sk = self._check_skew(images)
+        if self.tiling is not None and not self.device_postprocess:
+            return self._detect_tiled_host(images, batch_size, include_maps, sk)
         if self.device_postprocess:
             return self._detect_device(images, batch_size, include_maps)
         gen = self.batch_detection(images, batch_size=batch_size)
         futures = []
         workers = max(1, min(settings.DETECTOR_POSTPROCESSING_CPU_WORKERS, len(images)))
+
+        def one(p, s):
+            r = parallel_get_boxes(p, s, include_maps)
+            return r if sk is None else (r, self._skew_host(sk, r, p[0], s, (p[0].shape[1], p[0].shape[0])))
+
         if len(images) >= settings.DETECTOR_MIN_PARALLEL_THRESH:
             with ThreadPoolExecutor(max_workers=workers) as ex:
                 for preds, sizes in gen:
-                    futures.extend(ex.submit(parallel_get_boxes, p, s, include_maps) for p, s in zip(preds, sizes))
-            return [f.result() for f in futures]
-        out = []
-        for preds, sizes in gen:
-            out.extend(parallel_get_boxes(p, s, include_maps) for p, s in zip(preds, sizes))
+                    futures.extend(ex.submit(one, p, s) for p, s in zip(preds, sizes))
+            out = [f.result() for f in futures]
+        else:
+            out = []
+            for preds, sizes in gen:
+                out.extend(one(p, s) for p, s in zip(preds, sizes))
+        if sk is not None:
+            self.last_skew = [info for _, info in out]
+            out = [r for r, _ in out]
         return out
 
     def _detect_device(self, images, batch_size=None, include_maps=False) -> List[TextDetectionResult]:
@@ -228,21 +284,25 @@ class DetectionPredictor(BasePredictor):
         (~10 ms per 16 pages) earlier, at the price of that much overlap inside the detector."""
         if self.tiling is not None:
             check_tiling(self.tiling, self.processor.size["height"])
+        sk = self._check_skew(images)
         if getattr(self, "_post", None) is None:
             self._post = HipDetPost(self.model.device)
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
         if self.tiling is not None:
-            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first)
+            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first, sk)
             return
 
         def finish(job):
             """Results of one launched batch (waits for ITS event only)."""
             out: List[TextDetectionResult] = []
             jobs, n_pages, tiles_of, split_heights, sizes, heat, pw = job
-            res = {}
-            for pages_, pending, psizes in jobs:
+            res, skews = {}, {}
+            for pages_, pending, psizes, spending in jobs:
                 for pg, (bx, cf), psize in zip(pages_, self._post.collect(pending), psizes):
                     res[pg] = (bx, cf, psize)
+                if spending is not None:
+                    for pg, sc, nt in zip(pages_, *self._skew_op.collect(spending)):
+                        skews[pg] = (sc, nt)
             maps = heat.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
             for pg in range(n_pages):
                 bx, cf, psize = res[pg]
@@ -255,6 +315,8 @@ class DetectionPredictor(BasePredictor):
                     am = np.vstack([maps[t, 1, :r] for t, r in zip(tiles_of[pg], rows)])
                     hi, ai = Image.fromarray((hm * 255).astype(np.uint8)), Image.fromarray((am * 255).astype(np.uint8))
                 out.append(result_from_device_boxes(bx, cf, list(psize), sizes[pg], hi, ai))
+                if sk is not None:
+                    self.last_skew.append(self._skew_set(sk, out[-1], *skews[pg], psize))
             return out
 
         def launched():
@@ -266,7 +328,8 @@ class DetectionPredictor(BasePredictor):
                 jobs = []
                 if whole:
                     sel = heat if len(whole) == heat.shape[0] else heat[[tiles_of[pg][0] for pg in whole]].contiguous()
-                    jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole)))
+                    jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole),
+                                 None if sk is None else self._skew_launch(sk, sel, [sizes[pg] for pg in whole], (pw, ph))))
                 # tall pages: strips re-assembled on the device (:134-151); pages of equal height share ONE post-processing call (a call per
                 # page was 17 launches + a D2H each: 16 letter pages spent 40 of their 77 ms there, tools/hostbench/det_letter_profile.py)
                 by_height = {}
@@ -280,43 +343,56 @@ class DetectionPredictor(BasePredictor):
                         for t in tiles_of[pg]:
                             full[i, r0: r0 + split_heights[t]] = heat[t, 0, : split_heights[t]]
                             r0 += split_heights[t]
-                    jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs)))
+                    jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs),
+                                 None if sk is None else self._skew_launch(sk, full, [sizes[pg] for pg in pgs], (pw, hf))))
                 yield (jobs, n_pages, tiles_of, split_heights, sizes, heat, pw)
 
         yield from _one_batch_ahead(launched(), finish, eager_first)
 
     # ------------------------------------------------------------------------------------------------------------ tiled detection
-    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first):
+    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first, sk=None):
         """_iter_detect_device under `tiling`: the same one-batch-ahead hand-over, a page's boxes from its stitched map."""
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
 
         def finish(job):
-            groups, sizes, pendings = job
+            groups, sizes, pendings, spendings = job
             out = [None] * len(sizes)
-            for (ks, maps, (mw, mh)), pending in zip(groups, pendings):
+            infos = [None] * len(sizes)
+            for (ks, maps, (mw, mh)), pending, spending in zip(groups, pendings, spendings):
                 host = maps.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
                 for i, (k, (bx, cf)) in enumerate(zip(ks, self._post.collect(pending))):
                     out[k] = result_from_device_boxes(bx, cf, [mw, mh], sizes[k], *self._map_images(host, i, mw, mh))
+                if spending is not None:
+                    for k, sc, nt in zip(ks, *self._skew_op.collect(spending)):
+                        infos[k] = self._skew_set(sk, out[k], sc, nt, (mw, mh))
+            if sk is not None:
+                self.last_skew.extend(infos)
             return out
 
         def launched():
             for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
                 # pages of equal map size share ONE post-processing call, as tall pages of equal height do
-                yield groups, sizes, [self._post.launch(maps, tt, lt) for _, maps, _ in groups]
+                pendings = [self._post.launch(maps, tt, lt) for _, maps, _ in groups]
+                yield groups, sizes, pendings, [None if sk is None else self._skew_launch(sk, maps, [sizes[k] for k in ks], ms)
+                                                for ks, maps, ms in groups]
 
         yield from _one_batch_ahead(launched(), finish, eager_first)
 
-    def _detect_tiled_host(self, images, batch_size, include_maps):
+    def _detect_tiled_host(self, images, batch_size, include_maps, sk=None):
         """The checker arm under `tiling` (DETECTOR_POSTPROCESS_HOST): the stitched maps D2H, heatmap.py on them."""
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
         out = []
         for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
-            res = [None] * len(sizes)
+            res, infos = [None] * len(sizes), [None] * len(sizes)
             for ks, maps, (mw, mh) in groups:
                 host = maps.cpu().numpy()
                 for i, k in enumerate(ks):
                     boxes, confs = detect_boxes(host[i, 0], tt, lt)
                     res[k] = result_from_device_boxes(boxes, confs, [mw, mh], sizes[k], *self._map_images(host if include_maps else None, i, mw, mh))
+                    if sk is not None:
+                        infos[k] = self._skew_host(sk, res[k], host[i, 0], sizes[k], (mw, mh))
+            if sk is not None:
+                self.last_skew.extend(infos)
             out.extend(res)
         return out
 
