@@ -246,6 +246,24 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
  * What a descriptor addresses is not checked against the buffers: the caller keeps offsets and sizes inside them. Enqueue only. */
 int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream);
 
+/* Unrolling of bent text lines along their centre lines (RecognitionPredictor.unroll): n bands of the pages -> upright uint8 crops,
+ * each the rule of warp_columns (surya_amd/common/imageops.py): output column u has a centre C(u) = (Cx, Cy) on the centre line and a
+ * unit normal N(u) = (Nx, Ny), made by curve_table on the host (arc-length parametrised, float64); output pixel (u, v) samples its page
+ * at C(u) + (v + 0.5 - out_h / 2) N(u) - 0.5 per axis and from there on as surya_rec_rectify does: 4 x 4 cubic taps (a = -0.75) around
+ * floor() of that point, replicate border, float64 sums in tap order (horizontal pass first), rint, clamp to 0..255; uint8-equal to
+ * the host function. A crop is written like a page (HWC, `pixel_stride` bytes per pixel, X = 0 with 4), so surya_rec_preprocess reads it
+ * as it reads a rectified crop. pages, out, tables: device; `out` may lie in the pages' allocation, in a disjoint range; tables: doubles,
+ * 16-byte aligned. descs: HOST array of n descriptors
+ *   { int64 page_off; int32 page_w, page_h; int32 out_w, out_h; int64 out_off (bytes into out);
+ *     int64 table_off (doubles into tables, even: the crop's [out_w][4] = Cx, Cy, Nx, Ny per column) }    -- 40 bytes, C layout;
+ * they are copied into the launches' kernel arguments, so the array may be reused as soon as the call returns. max_w, max_h: the
+ * largest out_w / out_h of the call (grid sizing). SA_ERR_ARG, with nothing launched, when pixel_stride is not 3 or 4, n is negative, a
+ * pointer (pages, descs, tables, out) is null, tables is not 16-byte aligned, a size is non-positive or exceeds max_w / max_h, an offset
+ * is negative, a table_off is odd, or (pixel_stride 4) a page_off or out_off is not a multiple of 4; n == 0 launches nothing. What a
+ * descriptor addresses is not checked against the buffers: the caller keeps offsets and sizes inside them. Enqueue only. */
+int surya_rec_unroll(const uint8_t* pages, const void* descs, int n, const double* tables, uint8_t* out, int pixel_stride, int max_w,
+                     int max_h, void* stream);
+
 /* Contrast adjustment of line crops (RecognitionPredictor.reread, LineRef.adjust): n crops of the pages -> their adjusted, padded
  * copies, each Pillow's ImageOps.autocontrast(crop, cutoff, preserve_tone=True, mask), byte for byte: 256 bins of the luma
  * (19595 R + 38470 G + 7471 B + 32768) >> 16 over the crop (has_poly: over the pixels of the 4-point polygon's mask, rasterised as
@@ -1023,6 +1041,27 @@ int surya_det_stitch_tiles(const float* heat, int n_tiles, int labels, int tile_
 size_t surya_det_skew_workspace_bytes(int batch, int height, int width);
 int surya_det_skew(const float* heat, long page_stride, int batch, int height, int width, float threshold, const int32_t* cs, int n_angles,
                    uint64_t* scores, int32_t* n_text, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Centre-line profiles of the kept text components (DetectionPredictor.centerlines; the rule: surya_amd/detection/centerline.py, the
+ * arithmetic: csrc/det_centerline_core.h). Enqueued BEHIND a surya_det_boxes call of the same (batch, height, width, max_boxes) on the
+ * same stream: boxes_workspace is that call's workspace, read through its layout (st, label, area and comp of
+ * surya_det_boxes_workspace_layout; after the call `area` holds a kept root's compact index and -1 for a dropped one) and never written.
+ * Integers only, so the outputs equal the numpy statement bit for bit. Enqueue only.
+ * For kept component c of page b, inclusive bounding box x0..x1, y0..y1: axis = 0 (bins along x, perpendicular coordinate p = y) when
+ * x1 - x0 >= y1 - y0, else 1 (bins along y, p = x); a pixel of the component at coordinate a along the axis falls into bin
+ * k = ((a - origin) * knots) / extent by integer division (origin = x0 or y0, extent = the box length along the axis, <= 8192).
+ * cnt: device uint32 [batch][max_boxes][knots] = pixels of the bin; sum: device uint64, same shape = the sum of p; lo / hi: device int32,
+ * same shape = min / max of p; an empty bin holds 0, 0, 0x7fffffff, -1. axis: device int32 [batch][max_boxes]. The call initialises all
+ * five arrays itself. Components beyond the page's count, and every component of a page whose count is -1 (more than max_boxes
+ * components), have empty bins and axis = -1.
+ * SA_ERR_ARG, with nothing launched, for a null pointer (boxes_workspace, cnt, sum, lo, hi, axis), a negative batch, a non-positive
+ * height, width or max_boxes, knots outside 2 .. 64, batch > 65535, max_boxes > 2^25, or a workspace that is smaller than
+ * surya_det_boxes_workspace_bytes(batch, height, width, max_boxes) or not 16-byte aligned; SA_ERR_SHAPE for width % 4 != 0 (as
+ * surya_det_boxes) or a height or width above 8192; batch == 0 launches nothing. The workspace is read unchecked but guarded: a label
+ * outside the page, a compact index outside the page's count and a pixel outside its component's box are skipped, so a workspace that no
+ * surya_det_boxes call filled gives meaningless bins and touches no memory it should not. */
+int surya_det_centerlines(int batch, int height, int width, int max_boxes, int knots, const void* boxes_workspace, size_t workspace_bytes,
+                          uint32_t* cnt, uint64_t* sum, int32_t* lo, int32_t* hi, int32_t* axis, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Layout model family: Donut-Swin window-attention encoder + ADETR decoder with cross- and self-attention.

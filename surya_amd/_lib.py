@@ -192,6 +192,8 @@ def _bind_lay_ops(lib):
     lib.surya_op_rec_boost_head.argtypes, lib.surya_op_rec_boost_head.restype = [i, C.POINTER(RecBoostHeadArgsC), p], C.c_int
     # rectification of rotated line quads in front of surya_rec_preprocess (csrc/rec_rectify.h); `descs` is a host array
     lib.surya_rec_rectify.argtypes, lib.surya_rec_rectify.restype = [p, p, i, p, i, i, i, p], C.c_int
+    # unrolling of bent lines along their centre lines, likewise (csrc/rec_unroll.h); `descs` is a host array, `tables` a device one
+    lib.surya_rec_unroll.argtypes, lib.surya_rec_unroll.restype = [p, p, i, p, p, i, i, i, p], C.c_int
     # contrast adjustment of line crops in front of surya_rec_preprocess (csrc/rec_adjust.h); `descs` is a host array
     lib.surya_rec_adjust_contrast.argtypes, lib.surya_rec_adjust_contrast.restype = [p, p, i, p, p, p, p, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first
@@ -240,6 +242,14 @@ def bind_det_skew(lib):
     i, l, f, p = C.c_int, C.c_long, C.c_float, C.c_void_p
     lib.surya_det_skew_workspace_bytes.argtypes, lib.surya_det_skew_workspace_bytes.restype = [i, i, i], C.c_size_t
     lib.surya_det_skew.argtypes, lib.surya_det_skew.restype = [p, l, i, i, i, f, p, i, p, p, p, C.c_size_t, p], C.c_int
+    return lib
+
+
+def bind_det_centerlines(lib):
+    """Centre-line profiles of the kept components (csrc/det_centerline.h), behind surya_det_boxes on its workspace. Bound by
+    HipDetCenterlines, not at load, as bind_det_skew is."""
+    i, p = C.c_int, C.c_void_p
+    lib.surya_det_centerlines.argtypes, lib.surya_det_centerlines.restype = [i, i, i, i, i, p, C.c_size_t, p, p, p, p, p, p], C.c_int
     return lib
 
 

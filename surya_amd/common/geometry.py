@@ -6,11 +6,15 @@ callers that post-process results see identical numbers.
 from __future__ import annotations
 
 import copy
+import inspect
+import math
 import numbers
 from typing import List, Optional
 
 import numpy as np
-from pydantic import BaseModel, computed_field, field_validator
+from pydantic import BaseModel, Field, computed_field, field_validator, model_serializer
+
+_EXCLUDE_IF = "exclude_if" in inspect.signature(Field).parameters          # pydantic >= 2.12: the exclusion runs inside pydantic-core
 
 
 def coerce_polygon(value) -> List[List[float]]:
@@ -145,3 +149,50 @@ class PolygonBox(BaseModel):
 
     def __hash__(self):
         return hash(tuple(self.bbox))
+
+
+class TextBox(PolygonBox):
+    """The PolygonBox of a detected text line in a call with `DetectionPredictor.centerlines` set (every other call builds plain
+    PolygonBoxes, as it always did). `centerline` / `thickness` (detection/centerline.py states the rule): the centre line of a line that
+    is BENT, as points (x, y) ordered along the reading direction, and the height of the band around it that holds the line, both in the
+    coordinates of `polygon`. None for a line that is not bent, and then left out of the serialised form, which stays the reference's (the
+    pattern of recognition/schema.py)."""
+    if _EXCLUDE_IF:
+        centerline: Optional[List[List[float]]] = Field(default=None, exclude_if=lambda v: v is None)
+        thickness: Optional[float] = Field(default=None, exclude_if=lambda v: v is None)
+    else:
+        centerline: Optional[List[List[float]]] = None
+        thickness: Optional[float] = None
+
+        @model_serializer(mode="wrap")
+        def _without_absent_centerline(self, handler):
+            d = handler(self)
+            if self.centerline is None:
+                d.pop("centerline", None)
+            if self.thickness is None:
+                d.pop("thickness", None)
+            return d
+
+    def rescale(self, processor_size, image_size):
+        """The corners as PolygonBox.rescale takes them. The centre line goes with the same two factors but keeps its fractions (a knot is
+        a mean, not a pixel corner). The band's height is measured AFTER scaling: the unit normal at every vertex (across its two
+        neighbours) is scaled like a point, so unequal x / y factors are handled; the median of the lengths counts."""
+        super().rescale(processor_size, image_size)
+        if self.centerline is None:
+            return
+        sx = image_size[0] / processor_size[0]
+        sy = image_size[1] / processor_size[1]
+        pts = [[float(p[0]), float(p[1])] for p in self.centerline]
+        if self.thickness is not None and len(pts) >= 2:
+            scales = []
+            for i in range(len(pts)):
+                a, b = pts[max(i - 1, 0)], pts[min(i + 1, len(pts) - 1)]
+                tx, ty = b[0] - a[0], b[1] - a[1]
+                n = math.hypot(tx, ty)
+                if n > 0.0:
+                    scales.append(math.hypot(-ty / n * sx, tx / n * sy))
+            if scales:
+                self.thickness = float(self.thickness) * float(np.median(scales))
+        self.centerline = [[p[0] * sx, p[1] * sy] for p in pts]
+    # (fit_to_bounds leaves a centre line as it is: clamping could fold two of its points into one, and a curve may leave the page -- the
+    # warp that reads it replicates the page's border)

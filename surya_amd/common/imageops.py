@@ -186,6 +186,13 @@ def warp_quad(page_u8: np.ndarray, h9, W: int, H: int) -> np.ndarray:
     w = h[6] * U + h[7] * V + h[8]
     sx = (h[0] * U + h[1] * V + h[2]) / w - 0.5
     sy = (h[3] * U + h[4] * V + h[5]) / w - 0.5
+    return _sample_cubic(page_u8, sx, sy, W, H)
+
+
+def _sample_cubic(page_u8: np.ndarray, sx: np.ndarray, sy: np.ndarray, W: int, H: int) -> np.ndarray:
+    """The sampling half of warp_quad and warp_columns: sx, sy float64 [H, W] = where every output pixel reads the page (pixel-index
+    coordinates); taps, sums, rounding as warp_quad says."""
+    ph, pw, C = page_u8.shape
     fx, fy = np.floor(sx), np.floor(sy)
     wx, wy = _cubic_weights(sx - fx), _cubic_weights(sy - fy)                  # [H, W, 4]
     # (the base is clamped before it becomes an integer: far outside the page every tap is the border pixel anyway)
@@ -204,6 +211,118 @@ def warp_quad(page_u8: np.ndarray, h9, W: int, H: int) -> np.ndarray:
     out = np.zeros((H, W, C), np.uint8)
     out[..., :3] = np.clip(np.rint(acc), 0.0, 255.0).astype(np.uint8)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ unrolling along a curve
+# A BENT text line is a centre line -- points (x, y) in grid-line coordinates of the page, ordered along the reading direction -- and a
+# thickness: the height of the band around the centre line that holds the line. Unrolling samples the band column by column along the
+# arc length into an upright crop. The rule is stated here once; csrc/rec_unroll.h restates warp_columns per pixel.
+def curve_ok(points, thickness) -> bool:
+    """At least two points of two finite numbers each, no segment of zero length, a finite positive thickness: what can be unrolled."""
+    try:
+        if len(points) < 2 or any(len(v) != 2 for v in points):
+            return False
+        p = [(float(v[0]), float(v[1])) for v in points]
+        t = float(thickness)
+    except (TypeError, ValueError):
+        return False
+    if isinstance(thickness, (bool, str, bytes)) or not all(math.isfinite(c) for v in p for c in v) or not (math.isfinite(t) and t > 0.0):
+        return False
+    return all(a != b for a, b in zip(p[:-1], p[1:]))
+
+
+class Curve(tuple):
+    """(points, thickness) of a line that is read from its unrolled crop: points a tuple of (x, y) floats in the pixels its slice is cut
+    from, thickness a float. A tuple of its own type, so that the places that hold "the quad a line was warped from" can hold it too."""
+    __slots__ = ()
+
+    def __new__(cls, points, thickness):
+        return super().__new__(cls, (tuple((float(p[0]), float(p[1])) for p in points), float(thickness)))
+
+    points = property(lambda self: self[0])
+    thickness = property(lambda self: self[1])
+
+    def scaled(self, sx: float, sy: float) -> "Curve":
+        """The curve in an image sx x sy times as large: points by the two factors, the thickness by the median length of the scaled
+        unit normals at the vertices (TextBox.rescale's rule)."""
+        if sx == 1 and sy == 1:
+            return self
+        pts = self[0]
+        ks = []
+        for i in range(len(pts)):
+            a, b = pts[max(i - 1, 0)], pts[min(i + 1, len(pts) - 1)]
+            tx, ty = b[0] - a[0], b[1] - a[1]
+            n = math.hypot(tx, ty)
+            if n > 0.0:
+                ks.append(math.hypot(-ty / n * sx, tx / n * sy))
+        return Curve([(x * sx, y * sy) for x, y in pts], self[1] * (float(np.median(ks)) if ks else 1.0))
+
+
+def _curve_frame(points):
+    """(P [m, 2], segment lengths [m - 1], cumulative arc length [m], unit tangents [m - 1, 2], vertex normals [m, 2]). A segment's normal
+    is (-ty, tx): it points DOWN for text read left to right. A vertex normal is the normalised sum of the adjacent segments' normals."""
+    P = np.asarray(points, np.float64).reshape(-1, 2)
+    seg = np.diff(P, axis=0)
+    ln = np.hypot(seg[:, 0], seg[:, 1])
+    cum = np.concatenate([[0.0], np.cumsum(ln)])
+    tang = seg / ln[:, None]
+    nseg = np.stack([-tang[:, 1], tang[:, 0]], 1)
+    vn = np.concatenate([nseg[:1], nseg[:-1] + nseg[1:], nseg[-1:]])
+    nv = np.hypot(vn[:, 0], vn[:, 1])
+    vn = np.where(nv[:, None] > 0.0, vn / np.where(nv > 0.0, nv, 1.0)[:, None], np.concatenate([nseg[:1], nseg[1:], nseg[-1:]]))    # (a hairpin: the next segment's)
+    return P, ln, cum, tang, vn
+
+
+def _curve_at(frame, s):
+    """Centre C [n, 2] and unit normal N [n, 2] at arc lengths s [n]: C linear on its segment (the end segments continue beyond the ends),
+    N interpolated between the vertex normals (held beyond the ends) and renormalised."""
+    P, ln, cum, tang, vn = frame
+    s = np.asarray(s, np.float64).reshape(-1)
+    i = np.clip(np.searchsorted(cum, s, side="right") - 1, 0, len(ln) - 1)
+    d = s - cum[i]
+    C = P[i] + d[:, None] * tang[i]
+    f = np.clip(d / ln[i], 0.0, 1.0)
+    N = vn[i] * (1.0 - f)[:, None] + vn[i + 1] * f[:, None]
+    nn = np.hypot(N[:, 0], N[:, 1])
+    N = np.where(nn[:, None] > 0.0, N / np.where(nn > 0.0, nn, 1.0)[:, None], vn[i])
+    return C, N
+
+
+def curve_size(points, thickness):
+    """(out_w, out_h, L) of the unrolled crop: the arc length and the thickness, rounded half up, at least 1."""
+    _, ln, _, _, _ = _curve_frame(points)
+    L = float(ln.sum())
+    return max(1, int(L + 0.5)), max(1, int(float(thickness) + 0.5)), L
+
+
+def curve_table(points, thickness):
+    """(table float64 [out_w][4] = (Cx, Cy, Nx, Ny) per output column, out_w, out_h): column u sits at arc length
+    s = (u + 0.5) * L / out_w."""
+    out_w, out_h, L = curve_size(points, thickness)
+    C, N = _curve_at(_curve_frame(points), (np.arange(out_w, dtype=np.float64) + 0.5) * L / out_w)
+    return np.ascontiguousarray(np.concatenate([C, N], 1)), out_w, out_h
+
+
+def warp_columns(page_u8: np.ndarray, table, out_h: int) -> np.ndarray:
+    """uint8 [out_h, out_w, C]: output pixel (u, v) samples the page at C(u) + (v + 0.5 - out_h / 2) * N(u) - 0.5 per axis; from there
+    warp_quad's words exactly (4 x 4 Keys taps around floor, base clamped, tap indices clamped to the page, float64 products summed in
+    tap order, the horizontal pass first, rint, clamp; the fourth byte 0 with stride 4)."""
+    t = np.asarray(table, np.float64).reshape(-1, 4)
+    d = ((np.arange(out_h, dtype=np.float64) + 0.5) - out_h / 2)[:, None]
+    sx = t[None, :, 0] + d * t[None, :, 2] - 0.5
+    sy = t[None, :, 1] + d * t[None, :, 3] - 0.5
+    return _sample_cubic(page_u8, sx, sy, len(t), out_h)
+
+
+def curve_to_page(P, points, thickness) -> np.ndarray:
+    """Points P [..., 2] (float64) of the unrolled crop, in its grid-line coordinates, onto the page: (u, v) -> C(s) + (v - out_h / 2) N(s)
+    at the continuous arc length s = u * L / out_w -- the map warp_columns samples through, so a crop pixel's centre lands where its
+    value was read."""
+    out_w, out_h, L = curve_size(points, thickness)
+    P = np.asarray(P, np.float64)
+    flat = P.reshape(-1, 2)
+    C, N = _curve_at(_curve_frame(points), flat[:, 0] * L / out_w)
+    return (C + (flat[:, 1] - out_h / 2)[:, None] * N).reshape(P.shape)
 
 
 def page_pixels(image) -> np.ndarray:

@@ -16,6 +16,7 @@
 #include "resample.h"
 #include "det_tile.h"
 #include "det_skew.h"
+#include "det_centerline.h"
 
 namespace sa {
 
@@ -651,6 +652,12 @@ int surya_det_skew(const float* heat, long page_stride, int batch, int height, i
                    uint64_t* scores, int32_t* n_text, void* workspace, size_t workspace_bytes, void* stream) {
     return sa::skew::skew_run(heat, page_stride, batch, height, width, threshold, cs, n_angles, scores, n_text, workspace, workspace_bytes,
                               (hipStream_t)stream);
+}
+
+int surya_det_centerlines(int batch, int height, int width, int max_boxes, int knots, const void* boxes_workspace, size_t workspace_bytes,
+                          uint32_t* cnt, uint64_t* sum, int32_t* lo, int32_t* hi, int32_t* axis, void* stream) {
+    return sa::centerline::centerlines_run(batch, height, width, max_boxes, knots, boxes_workspace, workspace_bytes, cnt, sum, lo, hi, axis,
+                                           (hipStream_t)stream);
 }
 
 int surya_det_forward(surya_det* h, const float* pixel_values, int batch, float* heatmaps, float* lowres, void* stream) {

@@ -14,6 +14,7 @@
 #include "rec_ops.h"
 #include "rec_prep.h"
 #include "rec_rectify.h"
+#include "rec_unroll.h"
 #include "rec_adjust.h"
 
 namespace sa {
@@ -692,6 +693,12 @@ int surya_rec_preprocess(const uint8_t* pages, const void* lines, int n_lines, u
 int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* out, int pixel_stride, int max_w, int max_h, void* stream) {
     return sa::prep::rectify_run(pages, reinterpret_cast<const sa::prep::RectifyDesc*>(descs), n, out, pixel_stride, max_w, max_h,
                                  (hipStream_t)stream);
+}
+
+int surya_rec_unroll(const uint8_t* pages, const void* descs, int n, const double* tables, uint8_t* out, int pixel_stride, int max_w,
+                     int max_h, void* stream) {
+    return sa::prep::unroll_run(pages, reinterpret_cast<const sa::prep::UnrollDesc*>(descs), n, tables, out, pixel_stride, max_w, max_h,
+                                (hipStream_t)stream);
 }
 
 int surya_rec_adjust_contrast(const uint8_t* pages, const void* descs, int n, uint8_t* out, uint8_t* mask_arena, void* work, int32_t* lo_hi,

@@ -43,36 +43,29 @@ __device__ __forceinline__ long tap_base(double f, int len) {
     return (long)(f < lo ? lo : (f > hi ? hi : f));
 }
 
-__global__ __launch_bounds__(256) void rectify_kernel(RectifyArgs a) {
+// The tap body of rectify_kernel and unroll_kernel (rec_unroll.h): the page is read at (sx, sy), pixel-index coordinates, and the
+// rounded pixel written to dst. ONE function, so the two kernels cannot drift apart in a product or a sum.
+__device__ __forceinline__ void warp_sample(const unsigned char* page, int page_w, int page_h, int pix, double sx, double sy,
+                                            unsigned char* dst) {
 #pragma clang fp contract(off)
-    const RectifyDesc& D = a.d[blockIdx.z];
-    if ((int)blockIdx.x * RECTIFY_TILE >= D.out_w || (int)blockIdx.y * RECTIFY_TILE >= D.out_h) return;    // workgroup-uniform
-    const int u = blockIdx.x * RECTIFY_TILE + (threadIdx.x & (RECTIFY_TILE - 1));
-    const int v = blockIdx.y * RECTIFY_TILE + (threadIdx.x / RECTIFY_TILE);
-    if (u >= D.out_w || v >= D.out_h) return;
-    const double U = (double)u + 0.5, V = (double)v + 0.5;
-    const double w = D.h[6] * U + D.h[7] * V + D.h[8];
-    const double sx = (D.h[0] * U + D.h[1] * V + D.h[2]) / w - 0.5;
-    const double sy = (D.h[3] * U + D.h[4] * V + D.h[5]) / w - 0.5;
     const double fx = floor(sx), fy = floor(sy);
     double wx[4], wy[4];
     cubic_w(sx - fx, wx);
     cubic_w(sy - fy, wy);
-    const long bx = tap_base(fx, D.page_w), by = tap_base(fy, D.page_h);
+    const long bx = tap_base(fx, page_w), by = tap_base(fy, page_h);
     int xi[4], yi[4];
     for (int k = 0; k < 4; ++k) {
         const long x = bx - 1 + k, y = by - 1 + k;
-        xi[k] = (int)(x < 0 ? 0 : (x > D.page_w - 1 ? D.page_w - 1 : x));     // replicate border
-        yi[k] = (int)(y < 0 ? 0 : (y > D.page_h - 1 ? D.page_h - 1 : y));
+        xi[k] = (int)(x < 0 ? 0 : (x > page_w - 1 ? page_w - 1 : x));         // replicate border
+        yi[k] = (int)(y < 0 ? 0 : (y > page_h - 1 ? page_h - 1 : y));
     }
-    const unsigned char* page = a.pages + D.page_off;
     double acc[3];
     for (int j = 0; j < 4; ++j) {
-        const unsigned char* row = page + (long)yi[j] * D.page_w * a.pix;
+        const unsigned char* row = page + (long)yi[j] * page_w * pix;
         double h[3];
         for (int k = 0; k < 4; ++k) {
             double p[3];
-            if (a.pix == 4) {                                 // page_off and the pixel offset are multiples of 4
+            if (pix == 4) {                                   // page_off and the pixel offset are multiples of 4
                 const uint32_t q = *reinterpret_cast<const uint32_t*>(row + (long)xi[k] * 4);
                 p[0] = (double)(q & 0xff); p[1] = (double)((q >> 8) & 0xff); p[2] = (double)((q >> 16) & 0xff);
             } else {
@@ -88,12 +81,25 @@ __global__ __launch_bounds__(256) void rectify_kernel(RectifyArgs a) {
         const double r = rint(acc[c]);
         b[c] = (uint32_t)(int)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));
     }
-    unsigned char* dst = a.out + D.out_off + ((long)v * D.out_w + u) * a.pix;
-    if (a.pix == 4) {
+    if (pix == 4) {
         *reinterpret_cast<uint32_t*>(dst) = b[0] | (b[1] << 8) | (b[2] << 16);
     } else {
         dst[0] = (unsigned char)b[0]; dst[1] = (unsigned char)b[1]; dst[2] = (unsigned char)b[2];
     }
+}
+
+__global__ __launch_bounds__(256) void rectify_kernel(RectifyArgs a) {
+#pragma clang fp contract(off)
+    const RectifyDesc& D = a.d[blockIdx.z];
+    if ((int)blockIdx.x * RECTIFY_TILE >= D.out_w || (int)blockIdx.y * RECTIFY_TILE >= D.out_h) return;    // workgroup-uniform
+    const int u = blockIdx.x * RECTIFY_TILE + (threadIdx.x & (RECTIFY_TILE - 1));
+    const int v = blockIdx.y * RECTIFY_TILE + (threadIdx.x / RECTIFY_TILE);
+    if (u >= D.out_w || v >= D.out_h) return;
+    const double U = (double)u + 0.5, V = (double)v + 0.5;
+    const double w = D.h[6] * U + D.h[7] * V + D.h[8];
+    const double sx = (D.h[0] * U + D.h[1] * V + D.h[2]) / w - 0.5;
+    const double sy = (D.h[3] * U + D.h[4] * V + D.h[5]) / w - 0.5;
+    warp_sample(a.pages + D.page_off, D.page_w, D.page_h, a.pix, sx, sy, a.out + D.out_off + ((long)v * D.out_w + u) * a.pix);
 }
 
 // descs: HOST array of n descriptors, validated here (what the device then reads, it reads unchecked); nothing is launched unless

@@ -15,10 +15,10 @@ import numpy as np
 from PIL import Image
 import inspect
 
-from pydantic import BaseModel, Field, model_serializer
+from pydantic import BaseModel, Field, SerializeAsAny, model_serializer
 from scipy import ndimage
 
-from ..common.geometry import PolygonBox
+from ..common.geometry import PolygonBox, TextBox
 from ..settings import settings
 
 
@@ -31,7 +31,8 @@ _EXCLUDE_IF = "exclude_if" in inspect.signature(Field).parameters          # pyd
 
 
 class TextDetectionResult(BaseModel):       # surya/detection/schema.py:12-17
-    bboxes: List[PolygonBox]
+    # (serialised as what they are: a call with DetectionPredictor.centerlines set puts TextBoxes here, whose centre lines are dumped)
+    bboxes: List[SerializeAsAny[PolygonBox]]
     vertical_lines: List[ColumnLine]
     heatmap: Optional[object]
     affinity_map: Optional[object]
@@ -216,11 +217,16 @@ def get_and_clean_boxes(textmap, processor_size, image_size, text_threshold=None
 
 
 def result_from_device_boxes(boxes: np.ndarray, confs: np.ndarray, processor_size, orig_sizes, heat_img=None,
-                             aff_img=None) -> TextDetectionResult:
+                             aff_img=None, attach=None) -> TextDetectionResult:
     """The host remainder of parallel_get_boxes (surya/detection/heatmap.py:160-184) when detect_boxes ran on the device
     (surya_det_boxes): PolygonBox construction, rescale / fit_to_bounds / clean_boxes (get_and_clean_boxes :127-136) and the
-    y-expansion, on a few hundred 4-point boxes."""
-    bboxes = [PolygonBox(polygon=b, confidence=float(c)) for b, c in zip(boxes, confs)]
+    y-expansion, on a few hundred 4-point boxes. attach: called with the boxes while they are still in map coordinates and in the
+    detector's order (DetectionPredictor.centerlines gives the bent ones their centre lines there)."""
+    if attach is None:
+        bboxes = [PolygonBox(polygon=b, confidence=float(c)) for b, c in zip(boxes, confs)]
+    else:
+        bboxes = [TextBox(polygon=b, confidence=float(c)) for b, c in zip(boxes, confs)]
+        attach(bboxes)
     for b in bboxes:
         b.rescale(processor_size, orig_sizes)
         b.fit_to_bounds([0, 0, orig_sizes[0], orig_sizes[1]])

@@ -300,6 +300,85 @@ class HipDetSkew:
         return self.collect(self.launch(heat, tables, threshold))
 
 
+class HipDetCenterlines:
+    """Centre-line profiles of the kept components on the device (surya_det_centerlines, csrc/det_centerline.h): the estimator behind
+    DetectionPredictor.centerlines (detection/centerline.py states the rule and makes the curves from the integers). `launch` enqueues
+    behind the surya_det_boxes call whose workspace it reads -- the HipDetPost's last launch -- and owns the output buffers; `collect` waits
+    for ITS event. Of the [max_boxes] rows of every output only the first HEAD travel to the host with the launch (a page rarely has more
+    lines); a page with more components fetches its rows when it is collected."""
+    HEAD = 512
+
+    def __init__(self, device="cuda:0"):
+        if not torch.cuda.is_available():
+            raise L.SuryaAmdError("HipDetCenterlines needs a GPU (MI355X); there is no CPU fallback")
+        self.lib = L.bind_det_centerlines(L.lib())
+        self.device = torch.device(device)
+        self._layouts = {}
+
+    def _comp_offset(self, B, H, W, max_boxes):
+        key = (B, H, W, max_boxes)
+        if key not in self._layouts:
+            off = (C.c_size_t * 21)()                                # SA_DET_BOXES_LAYOUT_WORDS
+            L.check(self.lib.surya_det_boxes_workspace_layout(B, H, W, max_boxes, off, 21, None, None), "surya_det_boxes_workspace_layout")
+            assert int(off[20]) == 24, "CompStats is six words (csrc/det_post_core.h)"
+            self._layouts[key] = int(off[12])                        # comp
+        return self._layouts[key]
+
+    def launch(self, post: HipDetPost, heat: torch.Tensor, knots: int):
+        """post: the HipDetPost that has just launched on `heat` (same stream). Returns a handle for `collect`; nothing here waits."""
+        B, H, W = heat.shape[0], heat.shape[-2], heat.shape[-1]
+        mb = post.max_boxes
+        torch.cuda.set_device(self.device)
+        ws = post._ws
+        need = int(self.lib.surya_det_boxes_workspace_bytes(C.c_int(B), C.c_int(H), C.c_int(W), C.c_int(mb)))
+        assert ws is not None and ws.numel() >= need, "HipDetCenterlines.launch follows HipDetPost.launch of the same maps"
+        dev = self.device
+        cnt = torch.empty((B, mb, knots), dtype=torch.int32, device=dev)                 # uint32 / uint64 on the device; torch moves the bits
+        sm = torch.empty((B, mb, knots), dtype=torch.int64, device=dev)
+        lo = torch.empty((B, mb, knots), dtype=torch.int32, device=dev)
+        hi = torch.empty((B, mb, knots), dtype=torch.int32, device=dev)
+        axis = torch.empty((B, mb), dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L.check(self.lib.surya_det_centerlines(B, H, W, mb, int(knots), L.ptr(ws), need, L.ptr(cnt), L.ptr(sm), L.ptr(lo), L.ptr(hi), L.ptr(axis),
+                                               stream), "surya_det_centerlines")
+        off = self._comp_offset(B, H, W, mb)
+        comp = ws[off: off + B * mb * 24].view(torch.int32).view(B, mb, 6)[:, :, :4].contiguous()      # (x0, x1, y0, y1); the next call rewrites ws
+        full = (cnt, sm, lo, hi, axis, comp)
+        head = min(mb, self.HEAD)
+        host = tuple(torch.empty((B, head, *t.shape[2:]), dtype=t.dtype, pin_memory=True).copy_(t[:, :head], non_blocking=True) for t in full)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(dev))
+        return (ev, host, full, heat, post, int(knots))
+
+    def collect(self, pending, counts, thresholds=None):
+        """Per page the profile of its first counts[b] components, as detection/centerline.py `profile_page` returns it. counts: the boxes
+        HipDetPost.collect returned for the same pages. A page that overflowed the post-processing's max_boxes was run again there with more
+        room; its profile is taken again likewise (thresholds: the (text, low) pair of that launch)."""
+        ev, host, full, heat, post, knots = pending
+        ev.synchronize()
+        head = host[0].shape[1]
+        out = []
+        over = [b for b, n in enumerate(counts) if n > post.max_boxes]
+        for b, n in enumerate(counts):
+            if b in over:
+                out.append(None)
+                continue
+            src = [t[b, :n].numpy() for t in host] if n <= head else [t[b, :n].cpu().numpy() for t in full]
+            cnt, sm, lo, hi, axis, box = (np.ascontiguousarray(a) for a in src)
+            out.append({"cnt": cnt.view(np.uint32).copy(), "sum": sm.view(np.uint64).copy(), "lo": lo.copy(), "hi": hi.copy(), "axis": axis.copy(),
+                        "box": box.copy()})
+        if over:
+            assert thresholds is not None, "a page overflowed max_boxes: collect needs the thresholds to run it again"
+            big = HipDetPost(self.device, max_boxes=post.max_boxes * 16)
+            sel = heat[over].contiguous()
+            p = big.launch(sel, *thresholds)
+            c = self.launch(big, sel, knots)
+            redo = self.collect(c, [len(bx) for bx, _ in big.collect(p)])
+            for b, r in zip(over, redo):
+                out[b] = r
+        return out
+
+
 class DeviceResampler:
     """Pillow LANCZOS resizes (surya_resample_lanczos_u8) and integer box reductions (surya_reduce_u8) of uint8 pages on the
     device (csrc/resample.h). Coefficient tables are built once per (source length, target length, source span) by

@@ -21,8 +21,10 @@ from ..config import DetConfig, det_config
 from ..settings import settings
 from .heatmap import TextDetectionResult, detect_boxes, parallel_get_boxes, result_from_device_boxes
 from ..common.pil_resample import plan_chain as plan_resize
-from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetModel, HipDetPost, HipDetSkew, HipDetTiler
+from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetCenterlines, HipDetModel, HipDetPost, HipDetSkew, HipDetTiler
+from . import centerline as centerline_rule
 from . import skew as skew_rule
+from .centerline import Centerlines  # noqa: F401  (what `DetectionPredictor.centerlines` takes)
 from .skew import SkewEstimate, straighten  # noqa: F401  (SkewEstimate: what `DetectionPredictor.skew` takes)
 from .tiling import DetTiling, check_tiling, page_plan  # noqa: F401  (DetTiling: what `DetectionPredictor.tiling` takes)
 
@@ -200,6 +202,47 @@ class DetectionPredictor(BasePredictor):
     # per page of the last call with `skew` set: {"angle", "confidence", "n_text" (text pixels of the map), "map_size" (w, h)}
     last_skew: list = []
 
+    # Centre lines of bent text lines (detection/centerline.py states the rule): None = nothing is estimated and nothing is launched; a
+    # Centerlines = every box whose component is bent carries `centerline` (points along the line, page pixels) and `thickness` (the height of
+    # the band around it), from the labelling of the SAME page map its box comes from: surya_det_centerlines, enqueued behind that map's
+    # surya_det_boxes, reads the labels that call left in its workspace. No additional forward pass, no second labelling.
+    centerlines = None
+    # per page of the last call with `centerlines` set: {"n_boxes" (kept components of the map), "n_curved" (those that got a centre line)}
+    last_centerlines: list = []
+
+    def _check_centerlines(self):
+        """The refusals of `centerlines` before any device work; returns the checked Centerlines, or None when off."""
+        if self.centerlines is None:
+            return None
+        cli = centerline_rule.check_centerlines(self.centerlines)
+        self.last_centerlines = []
+        return cli
+
+    def _cl_launch(self, cli, maps):
+        """surya_det_centerlines behind the surya_det_boxes launch that just took `maps`."""
+        if cli is None:
+            return None
+        if getattr(self, "_cl_op", None) is None:
+            self._cl_op = HipDetCenterlines(self.model.device)
+        return self._cl_op.launch(self._post, maps, cli.knots)
+
+    def _cl_collect(self, cpending, got):
+        """The profiles of one launch, per page (None when off). got: what HipDetPost.collect returned for the same launch."""
+        if cpending is None:
+            return [None] * len(got)
+        return self._cl_op.collect(cpending, [len(bx) for bx, _ in got], (settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD))
+
+    @staticmethod
+    def _cl_result(cli, prof, bx, cf, psize, size, hi=None, ai=None):
+        """result_from_device_boxes with the centre lines of one page's profile attached; returns (result, its last_centerlines entry)."""
+        if cli is None:
+            return result_from_device_boxes(bx, cf, psize, size, hi, ai), None
+        info = {}
+
+        def attach(bboxes):
+            info["n_boxes"], info["n_curved"] = len(bboxes), centerline_rule.attach(bboxes, prof, cli)
+        return result_from_device_boxes(bx, cf, psize, size, hi, ai, attach=attach), info
+
     def _check_skew(self, images):
         """The refusals of `skew` before any device work; returns the estimate's (candidate angles, mask threshold), or None when off."""
         if self.skew is None:
@@ -240,8 +283,9 @@ class DetectionPredictor(BasePredictor):
         if self.tiling is not None:
             check_tiling(self.tiling, self.processor.size["height"])
         sk = self._check_skew(images)
+        cli = self._check_centerlines()
         if self.tiling is not None and not self.device_postprocess:
-            return self._detect_tiled_host(images, batch_size, include_maps, sk)
+            return self._detect_tiled_host(images, batch_size, include_maps, sk, cli)
         if self.device_postprocess:
             return self._detect_device(images, batch_size, include_maps)
         gen = self.batch_detection(images, batch_size=batch_size)
@@ -249,8 +293,16 @@ class DetectionPredictor(BasePredictor):
         workers = max(1, min(settings.DETECTOR_POSTPROCESSING_CPU_WORKERS, len(images)))
 
         def one(p, s):
-            r = parallel_get_boxes(p, s, include_maps)
-            return r if sk is None else (r, self._skew_host(sk, r, p[0], s, (p[0].shape[1], p[0].shape[0])))
+            info = None
+            if cli is None:
+                r = parallel_get_boxes(p, s, include_maps)
+            else:                                          # the same steps (heatmap.py), with the profile of the same map in between
+                heat = p[0] if p[0].dtype == np.float32 else p[0].astype(np.float32)
+                tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
+                imgs = [Image.fromarray((m * 255).astype(np.uint8)) for m in p[:2]] if include_maps else [None, None]
+                r, info = self._cl_result(cli, centerline_rule.profile_page(heat, tt, lt, cli.knots), *detect_boxes(heat, tt, lt),
+                                          [heat.shape[1], heat.shape[0]], s, *imgs)
+            return r, (None if sk is None else self._skew_host(sk, r, p[0], s, (p[0].shape[1], p[0].shape[0]))), info
 
         if len(images) >= settings.DETECTOR_MIN_PARALLEL_THRESH:
             with ThreadPoolExecutor(max_workers=workers) as ex:
@@ -262,9 +314,10 @@ class DetectionPredictor(BasePredictor):
             for preds, sizes in gen:
                 out.extend(one(p, s) for p, s in zip(preds, sizes))
         if sk is not None:
-            self.last_skew = [info for _, info in out]
-            out = [r for r, _ in out]
-        return out
+            self.last_skew = [info for _, info, _ in out]
+        if cli is not None:
+            self.last_centerlines = [info for _, _, info in out]
+        return [r for r, _, _ in out]
 
     def _detect_device(self, images, batch_size=None, include_maps=False) -> List[TextDetectionResult]:
         return [r for batch in self._iter_detect_device(images, batch_size, include_maps) for r in batch]
@@ -285,11 +338,12 @@ class DetectionPredictor(BasePredictor):
         if self.tiling is not None:
             check_tiling(self.tiling, self.processor.size["height"])
         sk = self._check_skew(images)
+        cli = self._check_centerlines()
         if getattr(self, "_post", None) is None:
             self._post = HipDetPost(self.model.device)
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
         if self.tiling is not None:
-            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first, sk)
+            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first, sk, cli)
             return
 
         def finish(job):
@@ -297,15 +351,16 @@ class DetectionPredictor(BasePredictor):
             out: List[TextDetectionResult] = []
             jobs, n_pages, tiles_of, split_heights, sizes, heat, pw = job
             res, skews = {}, {}
-            for pages_, pending, psizes, spending in jobs:
-                for pg, (bx, cf), psize in zip(pages_, self._post.collect(pending), psizes):
-                    res[pg] = (bx, cf, psize)
+            for pages_, pending, psizes, spending, cpending in jobs:
+                got = self._post.collect(pending)
+                for pg, (bx, cf), psize, prof in zip(pages_, got, psizes, self._cl_collect(cpending, got)):
+                    res[pg] = (bx, cf, psize, prof)
                 if spending is not None:
                     for pg, sc, nt in zip(pages_, *self._skew_op.collect(spending)):
                         skews[pg] = (sc, nt)
             maps = heat.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
             for pg in range(n_pages):
-                bx, cf, psize = res[pg]
+                bx, cf, psize, prof = res[pg]
                 hi = ai = None
                 if include_maps:
                     # the reference keeps a page's FIRST tile whole -- an unsplit page shorter than the processor height still gets
@@ -314,7 +369,10 @@ class DetectionPredictor(BasePredictor):
                     hm = np.vstack([maps[t, 0, :r] for t, r in zip(tiles_of[pg], rows)])
                     am = np.vstack([maps[t, 1, :r] for t, r in zip(tiles_of[pg], rows)])
                     hi, ai = Image.fromarray((hm * 255).astype(np.uint8)), Image.fromarray((am * 255).astype(np.uint8))
-                out.append(result_from_device_boxes(bx, cf, list(psize), sizes[pg], hi, ai))
+                r, info = self._cl_result(cli, prof, bx, cf, list(psize), sizes[pg], hi, ai)
+                out.append(r)
+                if cli is not None:
+                    self.last_centerlines.append(info)
                 if sk is not None:
                     self.last_skew.append(self._skew_set(sk, out[-1], *skews[pg], psize))
             return out
@@ -329,7 +387,8 @@ class DetectionPredictor(BasePredictor):
                 if whole:
                     sel = heat if len(whole) == heat.shape[0] else heat[[tiles_of[pg][0] for pg in whole]].contiguous()
                     jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole),
-                                 None if sk is None else self._skew_launch(sk, sel, [sizes[pg] for pg in whole], (pw, ph))))
+                                 None if sk is None else self._skew_launch(sk, sel, [sizes[pg] for pg in whole], (pw, ph)),
+                                 self._cl_launch(cli, sel)))
                 # tall pages: strips re-assembled on the device (:134-151); pages of equal height share ONE post-processing call (a call per
                 # page was 17 launches + a D2H each: 16 letter pages spent 40 of their 77 ms there, tools/hostbench/det_letter_profile.py)
                 by_height = {}
@@ -344,55 +403,68 @@ class DetectionPredictor(BasePredictor):
                             full[i, r0: r0 + split_heights[t]] = heat[t, 0, : split_heights[t]]
                             r0 += split_heights[t]
                     jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs),
-                                 None if sk is None else self._skew_launch(sk, full, [sizes[pg] for pg in pgs], (pw, hf))))
+                                 None if sk is None else self._skew_launch(sk, full, [sizes[pg] for pg in pgs], (pw, hf)),
+                                 self._cl_launch(cli, full)))
                 yield (jobs, n_pages, tiles_of, split_heights, sizes, heat, pw)
 
         yield from _one_batch_ahead(launched(), finish, eager_first)
 
     # ------------------------------------------------------------------------------------------------------------ tiled detection
-    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first, sk=None):
+    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first, sk=None, cli=None):
         """_iter_detect_device under `tiling`: the same one-batch-ahead hand-over, a page's boxes from its stitched map."""
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
 
         def finish(job):
-            groups, sizes, pendings, spendings = job
+            groups, sizes, pendings, spendings, cpendings = job
             out = [None] * len(sizes)
             infos = [None] * len(sizes)
-            for (ks, maps, (mw, mh)), pending, spending in zip(groups, pendings, spendings):
+            cinfos = [None] * len(sizes)
+            for (ks, maps, (mw, mh)), pending, spending, cpending in zip(groups, pendings, spendings, cpendings):
                 host = maps.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
-                for i, (k, (bx, cf)) in enumerate(zip(ks, self._post.collect(pending))):
-                    out[k] = result_from_device_boxes(bx, cf, [mw, mh], sizes[k], *self._map_images(host, i, mw, mh))
+                got = self._post.collect(pending)
+                for i, (k, (bx, cf), prof) in enumerate(zip(ks, got, self._cl_collect(cpending, got))):
+                    out[k], cinfos[k] = self._cl_result(cli, prof, bx, cf, [mw, mh], sizes[k], *self._map_images(host, i, mw, mh))
                 if spending is not None:
                     for k, sc, nt in zip(ks, *self._skew_op.collect(spending)):
                         infos[k] = self._skew_set(sk, out[k], sc, nt, (mw, mh))
             if sk is not None:
                 self.last_skew.extend(infos)
+            if cli is not None:
+                self.last_centerlines.extend(cinfos)
             return out
 
         def launched():
             for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
-                # pages of equal map size share ONE post-processing call, as tall pages of equal height do
-                pendings = [self._post.launch(maps, tt, lt) for _, maps, _ in groups]
-                yield groups, sizes, pendings, [None if sk is None else self._skew_launch(sk, maps, [sizes[k] for k in ks], ms)
-                                                for ks, maps, ms in groups]
+                # pages of equal map size share ONE post-processing call, as tall pages of equal height do; what reads a call's workspace
+                # (the centre lines) goes right behind it, before the next call rewrites it
+                pendings, spendings, cpendings = [], [], []
+                for ks, maps, ms in groups:
+                    pendings.append(self._post.launch(maps, tt, lt))
+                    cpendings.append(self._cl_launch(cli, maps))
+                    spendings.append(None if sk is None else self._skew_launch(sk, maps, [sizes[k] for k in ks], ms))
+                yield groups, sizes, pendings, spendings, cpendings
 
         yield from _one_batch_ahead(launched(), finish, eager_first)
 
-    def _detect_tiled_host(self, images, batch_size, include_maps, sk=None):
+    def _detect_tiled_host(self, images, batch_size, include_maps, sk=None, cli=None):
         """The checker arm under `tiling` (DETECTOR_POSTPROCESS_HOST): the stitched maps D2H, heatmap.py on them."""
         tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
         out = []
         for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
-            res, infos = [None] * len(sizes), [None] * len(sizes)
+            res, infos, cinfos = [None] * len(sizes), [None] * len(sizes), [None] * len(sizes)
             for ks, maps, (mw, mh) in groups:
                 host = maps.cpu().numpy()
                 for i, k in enumerate(ks):
                     boxes, confs = detect_boxes(host[i, 0], tt, lt)
-                    res[k] = result_from_device_boxes(boxes, confs, [mw, mh], sizes[k], *self._map_images(host if include_maps else None, i, mw, mh))
+                    prof = None if cli is None else centerline_rule.profile_page(host[i, 0], tt, lt, cli.knots)
+                    res[k], cinfos[k] = self._cl_result(cli, prof, boxes, confs, [mw, mh], sizes[k],
+                                                        *self._map_images(host if include_maps else None, i, mw, mh))
                     if sk is not None:
                         infos[k] = self._skew_host(sk, res[k], host[i, 0], sizes[k], (mw, mh))
             if sk is not None:
                 self.last_skew.extend(infos)
+            if cli is not None:
+                self.last_centerlines.extend(cinfos)
             out.extend(res)
         return out
 

@@ -8,7 +8,7 @@ from typing import List, Optional
 import numpy as np
 
 from ..common.geometry import PolygonBox, coerce_polygon
-from ..common.imageops import quad_homography, quad_size
+from ..common.imageops import Curve, curve_size, curve_to_page, quad_homography, quad_size
 from .postprocess import (clean_math_tags, detect_repeat_token, fix_unbalanced_tags, prediction_to_polygon_batch, unwrap_math,
                           words_from_chars)
 from .processor import NOMATH_TOKEN
@@ -33,7 +33,7 @@ def _text_char(polygon, confidence, text, bbox_valid) -> TextChar:
 
 
 _LINE_FIELDS = ("polygon", "confidence", "text", "chars", "original_text_good", "words", "log_prob", "hypotheses", "pattern_matched",
-                "lexicon_index", "boost_matches", "rectified", "variant", "readings")
+                "lexicon_index", "boost_matches", "rectified", "variant", "readings", "unrolled")
 assert frozenset(_LINE_FIELDS) == frozenset(TextLine.model_fields), "TextLine fields changed: update _text_line"
 _new_line = TextLine.__new__
 _BLANK_POLY = np.array([[0, 0], [0, 1], [1, 1], [1, 0]], np.float64)
@@ -45,7 +45,8 @@ def _text_line(polygon, confidence, text, chars, words) -> TextLine:
     m = _new_line(TextLine)
     _set(m, "__dict__", {"polygon": polygon, "confidence": confidence, "text": text, "chars": chars,
                          "original_text_good": False, "words": words, "log_prob": None, "hypotheses": None, "pattern_matched": None,
-                         "lexicon_index": None, "boost_matches": None, "rectified": None, "variant": None, "readings": None})
+                         "lexicon_index": None, "boost_matches": None, "rectified": None, "variant": None, "readings": None,
+                         "unrolled": None})
     _set(m, "__pydantic_fields_set__", {"polygon", "confidence", "text", "chars", "words"})     # as TextLine(text=, polygon=, ...)
     _set(m, "__pydantic_extra__", None)
     _set(m, "__pydantic_private__", None)
@@ -153,6 +154,9 @@ def set_boost_fields(flat, sorted_pos, tokens, line: TextLine) -> TextLine:
 
 def line_quad(flat, orig):
     """The quad line `orig` was warped from (a call with `rectify` set keeps flat["quads"] by original position), else None."""
+    curves = flat.get("curves")
+    if curves is not None and curves[orig] is not None:       # (a call with `unroll` set keeps flat["curves"] likewise: a Curve)
+        return curves[orig]
     quads = flat.get("quads")
     return None if quads is None else quads[orig]
 
@@ -162,6 +166,9 @@ def set_rectified(flat, orig, line: TextLine) -> TextLine:
     if flat.get("quads") is not None:
         line.rectified = flat["quads"][orig] is not None
         line.__pydantic_fields_set__.add("rectified")
+    if flat.get("curves") is not None:                        # likewise in a call with `unroll` set: whether the line was unrolled
+        line.unrolled = flat["curves"][orig] is not None
+        line.__pydantic_fields_set__.add("unrolled")
     return line
 
 
@@ -170,7 +177,15 @@ def quad_to_page(P, quad, res_scale):
     into [0, W] x [0, H], mapped through the line's homography in float64, then the high-res rescale with int() truncation of the
     ordinary path (chars_of). This replaces its shift and clamp-into-bbox: the characters of a tilted line are tilted quads. (The
     mapped coordinates are rounded to 1e-6 px in front of the truncation, so that the round-off of the solve never moves a corner
-    that sits on an integer down a pixel.)"""
+    that sits on an integer down a pixel.) An UNROLLED line (`quad` is a Curve) goes through curve_to_page the same way: its
+    characters come back as tilted quads that follow the bend."""
+    if isinstance(quad, Curve):
+        W, H, _ = curve_size(*quad)
+        uv = np.stack([np.clip(P[..., 0], 0.0, float(W)), np.clip(P[..., 1], 0.0, float(H))], -1)
+        xy = curve_to_page(uv, *quad)
+        P[..., 0] = np.trunc(np.round(xy[..., 0], 6) * (1.0 / res_scale[0]))
+        P[..., 1] = np.trunc(np.round(xy[..., 1], 6) * (1.0 / res_scale[1]))
+        return P
     W, H = quad_size(quad)
     h = quad_homography(quad, W, H)
     u, v = np.clip(P[..., 0], 0.0, float(W)), np.clip(P[..., 1], 0.0, float(H))
@@ -317,7 +332,7 @@ def assemble_line(proc, flat, sorted_pos, orig, tokens, sc, bbox_rows, drop_repe
     """One line's TextLine from its finished token stream (reference :609-771 + :886-925). alts = (ids [T, 4], probabilities [T, 4])
     of the line's tokens with flat["top_k"] set: every character of the stream gets `alternatives` (characters that
     fix_unbalanced_tags inserts keep None)."""
-    if flat.get("quads") is not None and not flat.get("_quads_set"):      # a call with `rectify`: the line, then whether it was warped
+    if (flat.get("quads") is not None or flat.get("curves") is not None) and not flat.get("_quads_set"):      # a call with `rectify` / `unroll`: the line, then whether it was warped
         line = assemble_line(proc, {**flat, "_quads_set": True}, sorted_pos, orig, tokens, sc, bbox_rows, drop_repeated_text, return_words,
                              bbox_size, alts=alts)
         return set_rectified(flat, orig, line)
@@ -369,7 +384,7 @@ def assemble_batch(proc, flat, items, drop_repeated_text, return_words, bbox_siz
     polygons, close-box filter, per-char rescale / shift / clamp -- is done ONCE for the whole batch instead of ~25 small
     array calls per line, and TextLine is built from values that are already in validated form. Python walks only the token
     runs (`line_runs`) and creates the character objects. ~430 -> 80-90 us per 45-character line (tools/hostbench/assemble_cost.py)."""
-    if flat.get("quads") is not None and not flat.get("_quads_set"):
+    if (flat.get("quads") is not None or flat.get("curves") is not None) and not flat.get("_quads_set"):
         out = assemble_batch(proc, {**flat, "_quads_set": True}, items, drop_repeated_text, return_words, bbox_size)
         return [set_rectified(flat, it[1], line) for it, line in zip(items, out)]
     if flat.get("boost_tables") is not None:

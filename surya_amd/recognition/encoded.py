@@ -137,6 +137,7 @@ class EncodedLines:
         self._slices, self._tasks, self._texts = list(flat["slices"]), list(flat["task_names"]), list(flat["input_text"])
         self._polygons, self._scales = list(flat["polygons"]), list(flat["res_scales"])
         self._quads = list(flat["quads"]) if flat.get("quads") is not None else None
+        self._curves = list(flat["curves"]) if flat.get("curves") is not None else None
         self._first, self._prompt_ids, self._grids = list(first), list(prompt_ids), list(grids)
         self._base = [0]
         for n in self.line_counts:
@@ -248,6 +249,8 @@ class EncodedLines:
             flat[key] = [src[g] for g in ids]
         if self._quads is not None:
             flat["quads"] = [self._quads[g] for g in ids]
+        if self._curves is not None:
+            flat["curves"] = [self._curves[g] for g in ids]
         flat["enc_ids"] = ids
         return flat
 

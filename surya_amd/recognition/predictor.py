@@ -27,13 +27,14 @@ import numpy as np
 import torch
 from PIL import Image
 
-from ..common.imageops import fill_poly_mask, quad_homography, quad_size, rectify_threshold, should_rectify, warp_quad
+from ..common.imageops import (Curve, curve_ok, curve_table, fill_poly_mask, quad_homography, quad_size, rectify_threshold, should_rectify,
+                               warp_columns, warp_quad)
 from ..common.predictor import BasePredictor, gc_paused
 from ..settings import settings
 from . import assemble, options, reread as rereading
 from .loader import RecognitionModelLoader, rec_config_from_reference_json  # noqa: F401  (re-exported)
 from .loop import FEED_END, DeviceLoop
-from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, page_pixels, poly_ref, quad_ref
+from .preprocess_gpu import DevicePreprocessor, LineRef, bbox_ref, curve_ref, page_pixels, poly_ref, quad_ref
 from .postprocess import sort_text_lines
 from .reread import Reread  # noqa: F401  (re-exported: pred.reread = Reread(...))
 from .schema import LineRanking, OCRResult, RankedCandidate, RankResult, TaskNames, TextLine
@@ -78,17 +79,26 @@ def slice_polys_from_image(image: np.ndarray, polys) -> List[np.ndarray]:
     return [slice_and_pad_poly(image, p) for p in polys]
 
 
-def slice_polys(polys, threshold, page=None, pg: int = -1, arr=None):
+def slice_polys(polys, threshold, page=None, pg: int = -1, arr=None, curves=None):
     """The slices of one page's polygons (in the pixels of the image they are cut from) and, with rectification on (`threshold` not
     None), per polygon the quad it is warped from or None -- the ONE place where should_rectify is asked, for every call path. Device
     path (`page`: the page's uint8 pixels, registered as page `pg`): LineRefs; host path (`arr`: the image processor's array of the
-    same page): arrays, a rectified one being warp_quad's pixels as float32."""
-    quads = None if threshold is None else [tuple((float(c[0]), float(c[1])) for c in pl) if should_rectify(pl, threshold) else None
-                                            for pl in polys]
+    same page): arrays, a rectified one being warp_quad's pixels as float32. curves (a call with `unroll` set): per polygon None or the
+    Curve the line is unrolled along, in the same pixels; such a line is read from warp_columns' crop and is not asked about rectification."""
+    bent = [None] * len(polys) if curves is None else curves
+    quads = None if threshold is None else [tuple((float(c[0]), float(c[1])) for c in pl) if bent[i] is None and should_rectify(pl, threshold)
+                                            else None for i, pl in enumerate(polys)]
     slices = []
     for i, pl in enumerate(polys):
         q = None if quads is None else quads[i]
-        if arr is None:
+        if bent[i] is not None:
+            if arr is None:
+                h, w = page.shape[:2]
+                slices.append(curve_ref(pg, w, h, pl, bent[i]))
+            else:
+                table, _, out_h = curve_table(*bent[i])
+                slices.append(warp_columns(page, table, out_h)[..., :3].astype(np.float32))
+        elif arr is None:
             h, w = page.shape[:2]
             slices.append(quad_ref(pg, w, h, pl) if q is not None else poly_ref(pg, w, h, pl))
         elif q is not None:
@@ -99,11 +109,35 @@ def slice_polys(polys, threshold, page=None, pg: int = -1, arr=None):
     return slices, quads
 
 
+def checked_curve(where: str, given):
+    """One entry of `RecognitionPredictor.centerlines` (None, or (points, thickness)) as a Curve; ValueError naming the line for what curve_ok refuses."""
+    if given is None:
+        return None
+    try:
+        points, thickness = given
+    except (TypeError, ValueError):
+        raise ValueError(f"{where}: a centre line is None or (points, thickness), got {given!r}") from None
+    if not curve_ok(points, thickness):
+        raise ValueError(f"{where}: the centre line cannot be unrolled (at least two finite points, no zero-length segment, a positive "
+                         f"thickness), got {given!r}")
+    return Curve(points, thickness)
+
+
+def detected_curves(det_pred, scale):
+    """The Curves of one detected page's boxes (DetectionPredictor.centerlines), in the pixels the crops are cut from; None per straight line."""
+    out = []
+    for k, b in enumerate(det_pred.bboxes):
+        pts, th = getattr(b, "centerline", None), getattr(b, "thickness", None)
+        out.append(None if pts is None or th is None else checked_curve(f"detected line {k}", (pts, th)).scaled(scale[0], scale[1]))
+    return out
+
+
 def new_flat() -> dict:
     """The lines of one call, flattened over its pages. By line id (sorted / admission order): slices, task_names, input_text;
     by ORIGINAL position (page order): polygons, res_scales; slice_map holds the line count per page. The device path adds "pages";
     a call with `rectify` set adds "quads", by original position: the quad a line was warped from (in the pixels its slice came
-    from), None for a line that took the ordinary path."""
+    from), None for a line that took the ordinary path; a call with `unroll` set adds "curves" likewise: the Curve a line was unrolled
+    along."""
     return {"slices": [], "slice_map": [], "polygons": [], "task_names": [], "input_text": [], "res_scales": []}
 
 
@@ -444,17 +478,23 @@ class RecognitionPredictor(BasePredictor):
         thr = rectify_threshold(self.rectify)
         if thr is not None:
             flat["quads"] = []
+        unroll = self._unroll_on()
+        if unroll:
+            flat["curves"] = []
         for det_pred, image, highres, task in zip(det_predictions, images, highres_images, task_names):
             polygons, src, polys_px, scale = page_lines(det_pred, image, highres)
+            curves = detected_curves(det_pred, scale) if unroll else None
             if self.device_preprocess:
                 pg = self._page(flat, src)
-                slices, quads = slice_polys(polys_px, thr, flat["pages"][pg], pg)
-            elif thr is None:
+                slices, quads = slice_polys(polys_px, thr, flat["pages"][pg], pg, curves=curves)
+            elif thr is None and not unroll:
                 slices = slice_polys_from_image(self.processor.image_processor(src), polys_px)
             else:
-                slices, quads = slice_polys(polys_px, thr, page_pixels(src), arr=self.processor.image_processor(src))
+                slices, quads = slice_polys(polys_px, thr, page_pixels(src), arr=self.processor.image_processor(src), curves=curves)
             if thr is not None:
                 flat["quads"].extend(quads)
+            if unroll:
+                flat["curves"].extend(curves)
             flat["slice_map"].append(len(slices))
             flat["slices"].extend(slices)
             flat["polygons"].extend(polygons)
@@ -472,12 +512,25 @@ class RecognitionPredictor(BasePredictor):
         thr = rectify_threshold(self.rectify)
         if thr is not None:
             flat["quads"] = []
+        unroll, given = self._unroll_on(), self._curves_given
+        if unroll:
+            flat["curves"] = []
         for idx, image in enumerate(images):
             arr = None if dev else self.processor.image_processor(image)
             pg = self._page(flat, image) if dev else -1
+            curves = None
+            if unroll:                                        # (validated by __call__, before any device work)
+                n_lines = len(polygons[idx] if polygons is not None else bboxes[idx])
+                curves = [None] * n_lines if given is None or polygons is None else list(given[idx])
+                flat["curves"].extend(curves)
             if polygons is not None:
                 polys = polygons[idx]
-                if thr is None:
+                if curves is not None and any(c is not None for c in curves):
+                    slices, quads = (slice_polys(polys, thr, flat["pages"][pg], pg, curves=curves) if dev
+                                     else slice_polys(polys, thr, page_pixels(image), arr=arr, curves=curves))
+                    if thr is not None:
+                        flat["quads"].extend(quads)
+                elif thr is None:
                     slices = ([poly_ref(pg, image.size[0], image.size[1], pl) for pl in polys] if dev
                               else slice_polys_from_image(arr, polys))
                 else:
@@ -780,15 +833,33 @@ class RecognitionPredictor(BasePredictor):
         re-read as LineReading(variant, text, confidence); both are None while `reread` is None. `last_timing` gains `reread_ms` and
         `reread_lines`. TypeError / ValueError for a bad value, NotImplementedError with `shard_lines`, `shard_pages` or a process group,
         before any device work; ValueError naming `reread` in `align`, `rank`, `encode` and the methods of EncodedLines: a stored prompt
-        holds no pixels to adjust or turn."""
+        holds no pixels to adjust or turn.
+
+        `self.unroll` (an attribute like `rectify`; None = off, or True): a line that carries a CENTRE LINE is read from its unrolled crop
+        (common/imageops.py: curve_table, warp_columns -- the band of `thickness` around the centre line, sampled column by column along
+        the arc length) instead of its bounding rectangle or its rectified quad; every other line is handled as always. The centre line
+        comes with the detection (`det_predictor=` whose `centerlines` is set: TextBox.centerline / .thickness) or with
+        `self.centerlines` (an attribute like `pattern`, for the same reason: the call's signature ends with the two lists), a list
+        parallel to `polygons=` -- one list per image, one entry per polygon: None or (points, thickness) in page pixels, points ordered in
+        reading direction. Characters of an unrolled line are tilted quads that follow the bend, `TextLine.polygon` stays the polygon that came
+        in, `TextLine.unrolled` says whether the line was unrolled (None while `unroll` is None). It works with every decoding option,
+        dtype and KV mode: nothing behind the image tiles changes. A turned `reread` variant of an unrolled line reads the line's quad as
+        always. ValueError, before any device work, for another value of `unroll`, for `centerlines` without `polygons=` or of another
+        shape, and, naming the line, for a centre line with fewer than two points, a non-finite value, a zero-length segment or a
+        non-positive thickness."""
         top_k, beam, pattern, lexicon, boost_words, boost_weight = self._checked_modes()
         setting = rereading.checked(self.reread)
         if setting is not None and (self.shard_lines or self.shard_pages or self.process_group is not None):
             raise NotImplementedError("a call with reread runs on one rank: unset shard_lines / shard_pages / process_group")
+        given = self._checked_centerlines(self.centerlines, images, polygons)
         with self._modes(top_k, beam, setting):
-            return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
-                                        bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist, blocklist,
-                                        pattern, lexicon, boost_words, boost_weight)
+            self._curves_given = given
+            try:
+                return self._call_gc_paused(images, task_names, det_predictor, detection_batch_size, recognition_batch_size, highres_images,
+                                            bboxes, polygons, input_text, sort_lines, math_mode, return_words, drop_repeated_text, allowlist,
+                                            blocklist, pattern, lexicon, boost_words, boost_weight)
+            finally:
+                self._curves_given = None
 
     def _checked_modes(self) -> tuple:
         """The attributes a reading call runs under -- (top_k, beam_width, pattern, lexicon, boost_words, boost_weight) -- validated as
@@ -798,6 +869,7 @@ class RecognitionPredictor(BasePredictor):
             raise ValueError(f"top_k must be None or an integer in 2..4, got {top_k!r}")
         beam = self._check_beam_width(top_k)
         rectify_threshold(self.rectify)                       # ValueError for a bad value, before any device work
+        self._unroll_on()
         pattern = self.pattern
         if pattern is not None and beam is not None:
             raise ValueError("pattern is not available with beam_width: a beam would have to inherit its parent's automaton state")
@@ -829,6 +901,22 @@ class RecognitionPredictor(BasePredictor):
             self._top_k, self._beam, self._reread = saved
             if top_k is not None:
                 self.last_alternatives = None
+
+    def _unroll_on(self) -> bool:
+        """`self.unroll` validated (None or True); ValueError for anything else, before any device work."""
+        if self.unroll is not None and self.unroll is not True:
+            raise ValueError(f"unroll must be None or True, got {self.unroll!r}")
+        return self.unroll is True
+
+    def _checked_centerlines(self, centerlines, images, polygons):
+        """`self.centerlines` for a call as per-image lists of None / Curve; ValueError naming the line, before any device work."""
+        if centerlines is None:
+            return None
+        if polygons is None:
+            raise ValueError("centerlines goes with polygons=: one entry (None, or (points, thickness)) per polygon")
+        if len(centerlines) != len(images) or any(len(c) != len(pl) for c, pl in zip(centerlines, polygons)):
+            raise ValueError("centerlines needs one list per image with one entry per polygon of that image")
+        return [[checked_curve(f"image {i}, line {k}", c) for k, c in enumerate(page)] for i, page in enumerate(centerlines)]
 
     def _check_beam_width(self, top_k):
         """`self.beam_width` validated for a call (None: off), before any device work."""
@@ -1055,6 +1143,9 @@ class RecognitionPredictor(BasePredictor):
     boost_words = None                # word list per call / image / line to PREFER (see __call__), None = off: pred.boost_words = ["Paracetamol", ...]
     boost_weight = None               # ... and the boost in logit units, a finite float >= 0: required with boost_words, no default
     rectify = None                    # warp tilted 4-point polygons upright (see __call__): None = off, True, or a threshold in degrees: pred.rectify = 2.0
+    unroll = None                     # read bent lines from crops unrolled along their centre lines (see __call__): None = off, or True
+    centerlines = None                # centre lines given with `polygons=` (see __call__): per image a list with None or (points, thickness) per polygon
+    _curves_given = None              # the running call's validated `centerlines` (see __call__): per image, per line None or a Curve
     reread = None                     # re-read doubtful lines as other pictures (see __call__): None = off, or Reread(below=0.6, contrast=2, rotations=(180,))
     _reread = None                    # the running call's validated Reread (see __call__)
     last_boost = None
@@ -1280,6 +1371,9 @@ class RecognitionPredictor(BasePredictor):
         thr = rectify_threshold(self.rectify)
         if thr is not None:
             flat["quads"] = []
+        unroll = self._unroll_on()
+        if unroll:
+            flat["curves"] = []
         orig_of: List[int] = []                               # line id -> original position
         q: "queue.Queue" = queue.Queue()
         overall_max_tokens = max([self.line_budget(t) for t in task_names] or [1])
@@ -1294,17 +1388,21 @@ class RecognitionPredictor(BasePredictor):
                 for dets in det_predictor.iter_detect(images, batch_size=detection_batch_size):
                     if stop.is_set():
                         break
-                    pages, refs, polys_all, scales_all, tasks_all, quads_all = [], [], [], [], [], []
+                    pages, refs, polys_all, scales_all, tasks_all, quads_all, curves_all = [], [], [], [], [], [], []
                     first_page = page
                     for det_pred in dets:
                         polygons, src, polys_px, scale = page_lines(det_pred, images[page], highres_images[page])
                         pages.append(page_pixels(src))
-                        if thr is None:
+                        if thr is None and not unroll:
                             refs.extend(poly_ref(len(pages) - 1, src.size[0], src.size[1], poly) for poly in polys_px)
                         else:
-                            page_refs, quads = slice_polys(polys_px, thr, pages[-1], len(pages) - 1)
+                            curves = detected_curves(det_pred, scale) if unroll else None
+                            page_refs, quads = slice_polys(polys_px, thr, pages[-1], len(pages) - 1, curves=curves)
                             refs.extend(page_refs)
-                            quads_all.extend(quads)
+                            if thr is not None:
+                                quads_all.extend(quads)
+                            if unroll:
+                                curves_all.extend(curves)
                         polys_all.extend(polygons)
                         scales_all.extend([scale] * len(polygons))
                         tasks_all.extend([task_names[page]] * len(polygons))
@@ -1326,6 +1424,8 @@ class RecognitionPredictor(BasePredictor):
                     flat["res_scales"].extend(scales_all)
                     if thr is not None:
                         flat["quads"].extend(quads_all)
+                    if unroll:
+                        flat["curves"].extend(curves_all)
                     flat["slices"].extend(refs[i] for i in order)
                     flat["task_names"].extend(tasks_all[i] for i in order)
                     flat["input_text"].extend([None] * len(order))

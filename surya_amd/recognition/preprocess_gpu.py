@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from .. import _lib as L
-from ..common.imageops import page_pixels, parallel_copy, quad_homographies, quad_size  # noqa: F401  (page_pixels is re-exported: the predictor and tests import it from here)
+from ..common.imageops import curve_size, curve_table, page_pixels, parallel_copy, quad_homographies, quad_size  # noqa: F401  (page_pixels is re-exported: the predictor and tests import it from here)
 
 # must match sa::prep::LineDesc (csrc/rec_prep.h); align=True reproduces the C layout (8-byte longs after the int block)
 LINE_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("x0", np.int32), ("y0", np.int32),
@@ -27,6 +27,10 @@ assert LINE_DESC.itemsize == 112, LINE_DESC.itemsize
 RECTIFY_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("out_w", np.int32), ("out_h", np.int32),
                          ("out_off", np.int64), ("h", np.float64, (9,))], align=True)
 assert RECTIFY_DESC.itemsize == 104, RECTIFY_DESC.itemsize
+# must match sa::prep::UnrollDesc (csrc/rec_unroll.h): one per unrolled line, a HOST array like RECTIFY_DESC; table_off counts doubles
+UNROLL_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("out_w", np.int32), ("out_h", np.int32),
+                        ("out_off", np.int64), ("table_off", np.int64)], align=True)
+assert UNROLL_DESC.itemsize == 40, UNROLL_DESC.itemsize
 # must match sa::adjust::AdjustDesc (csrc/adjust_core.h): one per contrast-adjusted line, a HOST array like RECTIFY_DESC
 ADJUST_DESC = np.dtype([("src_off", np.int64), ("src_w", np.int32), ("src_h", np.int32), ("x0", np.int32), ("y0", np.int32), ("w", np.int32),
                         ("h", np.int32), ("cutoff", np.int32), ("has_poly", np.int32), ("poly", np.float32, (8,)), ("out_off", np.int64),
@@ -52,9 +56,15 @@ class LineRef:
     # a line read from its CONTRAST-ADJUSTED crop (RecognitionPredictor.reread): the cutoff, an integer percent in 0..49. Its pixels are
     # autocontrast_crop's (common/imageops.py) of the padded crop it would have been read from -- the rectified one for a line with a `quad`.
     adjust: Optional[int] = None
+    # a line that is UNROLLED along its centre line (RecognitionPredictor.unroll): an imageops.Curve in page coordinates. Its pixels are
+    # warp_columns' (common/imageops.py) of the curve's table, its shape curve_size's; `poly` and `quad` are then not read.
+    curve: Optional[tuple] = None
 
     @property
     def shape(self):
+        if self.curve is not None:
+            w, h, _ = curve_size(*self.curve)
+            return (h, w, 3)
         if self.quad is not None:
             w, h = quad_size(self.quad)
             return (h, w, 3)
@@ -92,6 +102,13 @@ def quad_ref(page: int, page_w: int, page_h: int, coords) -> LineRef:
     return ln
 
 
+def curve_ref(page: int, page_w: int, page_h: int, coords, curve) -> LineRef:
+    """poly_ref of a line that is unrolled: the same reference with the curve the pixels are unrolled along."""
+    ln = poly_ref(page, page_w, page_h, coords)
+    ln.curve = curve
+    return ln
+
+
 def fit_sizes(h: int, w: int, max_size, min_size=(168, 168), factor: int = 28):
     """(mid_h, mid_w) after scale_to_fit and (out_h, out_w) after the round-up to multiples of `factor`."""
     cur, mx, mn = w * h, max_size[0] * max_size[1], min_size[0] * min_size[1]
@@ -123,7 +140,9 @@ class DevicePreprocessor:
         pages and each then is an ordinary line whose page is its crop. Lines with `adjust` set get their contrast-adjusted, padded crops
         behind those (surya_rec_adjust_contrast, once per call, after the rectification) and are read from them likewise; the call's
         (lo, hi) bounds stay in `last_adjust_bounds` (device int32 [n_adjusted, 2], in line order). A call without a quad and without an
-        adjusted line allocates and launches what it always did."""
+        adjusted line allocates and launches what it always did. Lines with a `curve` are unrolled likewise (surya_rec_unroll, once per call,
+        from the tables of all of them in one device array): the arena holds the rectified crops, then the unrolled ones, then the adjusted
+        copies."""
         n = len(lines)
         f = self.ps * self.merge
         offs, total = [], 0
@@ -135,7 +154,8 @@ class DevicePreprocessor:
             offs.append(total)
             total += pg.size
         # rectified lines: their upright crops are written behind the pages, each at a 4-byte-aligned offset, as pages of their own
-        n_rect = sum(1 for ln in lines if ln.quad is not None)
+        n_rect = sum(1 for ln in lines if ln.quad is not None and ln.curve is None)
+        unr = [i for i, ln in enumerate(lines) if ln.curve is not None]
         rdesc = np.zeros(n_rect, RECTIFY_DESC)
         arena, r, max_rw, max_rh = (total + 3) & ~3, 0, 0, 0
         adj = [i for i, ln in enumerate(lines) if ln.adjust is not None]
@@ -146,13 +166,17 @@ class DevicePreprocessor:
         for i, (ln, mx) in enumerate(zip(lines, max_sizes)):
             ph, pw = pages[ln.page].shape[:2]
             h, w = ln.y1 - ln.y0, ln.x1 - ln.x0
-            if ln.quad is not None:
+            if ln.curve is not None:
+                w, h, _ = curve_size(*ln.curve)
+            elif ln.quad is not None:
                 w, h = quad_size(ln.quad)
             if h <= 0 or w <= 0:
                 raise ValueError("empty line crop on the device pre-processing path (caller substitutes a blank page)")
             (mh, mw), (oh, ow) = fit_sizes(h, w, mx, factor=f)
             d = desc[i]
-            if ln.quad is not None:                    # the line's page is its rectified crop
+            if ln.curve is not None:                   # the line's page is its unrolled crop, placed behind the rectified ones below
+                d["page_w"], d["page_h"], d["cw"], d["ch"] = w, h, w, h
+            elif ln.quad is not None:                  # the line's page is its rectified crop
                 rd = rdesc[r]
                 rd["page_off"], rd["page_w"], rd["page_h"], rd["out_w"], rd["out_h"], rd["out_off"] = offs[ln.page], pw, ph, w, h, arena
                 d["page_off"], d["page_w"], d["page_h"], d["cw"], d["ch"] = arena, w, h, w, h
@@ -161,7 +185,7 @@ class DevicePreprocessor:
             else:
                 d["page_off"], d["page_w"], d["page_h"] = offs[ln.page], pw, ph
                 d["x0"], d["y0"], d["cw"], d["ch"] = ln.x0, ln.y0, w, h
-            if ln.quad is None and ln.poly is not None and len(ln.poly) >= 3:
+            if ln.quad is None and ln.curve is None and ln.poly is not None and len(ln.poly) >= 3:
                 if len(ln.poly) != 4:
                     raise ValueError("device pre-processing handles 4-point polygons")
                 d["has_poly"] = 1
@@ -178,7 +202,19 @@ class DevicePreprocessor:
             gh, gw = oh // self.ps, ow // self.ps
             grids.append((gh, gw))
             tile_offs[i + 1] = tile_offs[i] + gh * gw
-        # adjusted lines, behind every rectified crop: what the line would have been read from is the source, the line's page its adjusted copy
+        # unrolled lines, behind every rectified crop: one table per line, all of them in one array of doubles
+        udesc, tables, t_at, max_uw, max_uh = np.zeros(len(unr), UNROLL_DESC), [], 0, 0, 0
+        for k, i in enumerate(unr):
+            d, ud, ln = desc[i], udesc[k], lines[i]
+            ph, pw = pages[ln.page].shape[:2]
+            table, w, h = curve_table(*ln.curve)
+            ud["page_off"], ud["page_w"], ud["page_h"], ud["out_w"], ud["out_h"], ud["out_off"], ud["table_off"] = offs[ln.page], pw, ph, w, h, arena, t_at
+            d["page_off"] = arena
+            arena += (w * h * pix + 3) & ~3
+            tables.append(table.reshape(-1))
+            t_at += table.size
+            max_uw, max_uh = max(max_uw, w), max(max_uh, h)
+        # adjusted lines, behind every rectified and every unrolled crop: what the line would have been read from is the source, the line's page its adjusted copy
         for k, i in enumerate(adj):
             d, ad = desc[i], adesc[k]
             w, h = int(d["cw"]), int(d["ch"])
@@ -191,14 +227,14 @@ class DevicePreprocessor:
             d["page_off"], d["page_w"], d["page_h"], d["x0"], d["y0"] = arena, w, h, 0, 0
             arena += (w * h * pix + 3) & ~3
         if n_rect:                                     # all homographies of the call in one stacked solve
-            rdesc["h"] = quad_homographies([ln.quad for ln in lines if ln.quad is not None], rdesc["out_w"], rdesc["out_h"])
+            rdesc["h"] = quad_homographies([ln.quad for ln in lines if ln.quad is not None and ln.curve is None], rdesc["out_w"], rdesc["out_h"])
         torch.cuda.set_device(self.device)
         # pinned staging straight from torch's caching host allocator (a pageable buffer + .pin_memory() would allocate, fault in and
         # copy the pages' ~3 MB each a second time)
         host = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
         hv = host.numpy()
         parallel_copy([hv[o: o + pg.size].reshape(pg.shape) for pg, o in zip(pages, offs)], list(pages))   # 3-8 MB each: side by side
-        if n_rect or adj:
+        if n_rect or adj or unr:
             d_pages = torch.empty(arena, dtype=torch.uint8, device=self.device)
             d_pages[:host.numel()].copy_(host, non_blocking=True)
         else:
@@ -211,6 +247,11 @@ class DevicePreprocessor:
         if n_rect:
             L.check(self.lib.surya_rec_rectify(L.ptr(d_pages), rdesc.ctypes.data_as(C.c_void_p), C.c_int(n_rect), L.ptr(d_pages), C.c_int(pix),
                                                C.c_int(max_rw), C.c_int(max_rh), stream), "surya_rec_rectify")
+        d_tables = None
+        if unr:
+            d_tables = torch.from_numpy(np.concatenate(tables)).to(self.device)
+            L.check(self.lib.surya_rec_unroll(L.ptr(d_pages), udesc.ctypes.data_as(C.c_void_p), C.c_int(len(unr)), L.ptr(d_tables), L.ptr(d_pages),
+                                              C.c_int(pix), C.c_int(max_uw), C.c_int(max_uh), stream), "surya_rec_unroll")
         if adj:
             d_amask = torch.empty(max(amask_bytes, 1), dtype=torch.uint8, device=self.device)
             d_work = torch.empty(len(adj) * ADJUST_WORK_BYTES, dtype=torch.uint8, device=self.device)
@@ -222,5 +263,5 @@ class DevicePreprocessor:
                                               C.c_int(self.ps), C.c_int(self.merge), C.c_float(self.pad), self.mean, self.std,
                                               C.c_int(int(mask_bytes > 0)), C.c_int(max_mid_w), C.c_int(pix), stream),
                 "surya_rec_preprocess")
-        self._keep = (d_pages, d_desc, d_mask, d_mid, host) + ((d_amask, d_work) if adj else ())      # alive until the stream has consumed them
+        self._keep = (d_pages, d_desc, d_mask, d_mid, host, d_tables) + ((d_amask, d_work) if adj else ())      # alive until the stream has consumed them
         return tiles, tile_offs, grids

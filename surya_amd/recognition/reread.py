@@ -184,15 +184,16 @@ def second_pass(pred, setting: Reread, flat, orig_of, text_lines, sources, kind,
         return text_lines
     from .preprocess_gpu import LineRef, quad_ref
     device = isinstance(flat["slices"][0], LineRef)           # the call's one decision (prepare_lines dispatches on the first slice)
-    first_quads = flat.get("quads")
+    first_quads, first_curves = flat.get("quads"), flat.get("curves")
     pages, page_idx, host_pages = [], {}, {}
-    slices, ids, owner, names, quads2 = [], [], [], [], []
+    slices, ids, owner, names, quads2, curves2 = [], [], [], [], [], []
     for o in picked:
         k, pg = id_of[o], page_of[o]
         src = sources[pg]
         poly_px = source_polygon(flat["polygons"][o], flat["res_scales"][o])
         fq = None if first_quads is None else first_quads[o]
-        clipped = None
+        fc = None if first_curves is None else first_curves[o]       # an unrolled line: its contrast variant is its unrolled crop's, its
+        clipped = None                                               # turned variants read the line's quad as always
         if kind == "bbox":
             pl = flat["polygons"][o]
             clipped = clip_bbox([pl[0][0], pl[0][1], pl[2][0], pl[2][1]], src.size[0], src.size[1])
@@ -206,7 +207,7 @@ def second_pass(pred, setting: Reread, flat, orig_of, text_lines, sources, kind,
                 else:
                     sl = quad_ref(page_idx[pg], src.size[0], src.size[1], arg)
             elif what == "adjust":
-                sl = host_contrast(flat["slices"][k], kind, poly_px, fq, arg)
+                sl = host_contrast(flat["slices"][k], kind, poly_px, fq if fc is None else fc, arg)
             else:
                 if pg not in host_pages:
                     host_pages[pg] = page_pixels(src)
@@ -217,6 +218,7 @@ def second_pass(pred, setting: Reread, flat, orig_of, text_lines, sources, kind,
             owner.append(o)
             names.append(name)
             quads2.append(arg if what == "quad" else fq)
+            curves2.append(fc if what == "adjust" else None)
     if not slices:
         return text_lines
     from .predictor import new_flat
@@ -229,6 +231,8 @@ def second_pass(pred, setting: Reread, flat, orig_of, text_lines, sources, kind,
     any_quad = any(q is not None for q in quads2)
     if any_quad or first_quads is not None:
         flat2["quads"] = quads2
+    if first_curves is not None:
+        flat2["curves"] = curves2
     span = max(s.size[0] for s in sources), max(s.size[1] for s in sources)
     sub = {}
     results = pred._read_flat([_Page(span)], flat2, None, recognition_batch_size, False, return_words, drop_repeated_text, sub,

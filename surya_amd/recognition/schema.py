@@ -126,6 +126,8 @@ class TextLine(BaseChar):
     # while the line was read, in order of completion, each once; [] if none. None, and left out likewise, for a line that was not boosted.
     # `rectified` (RecognitionPredictor.rectify): whether the line's pixels were warped upright from its quadrilateral; its characters'
     # polygons are then tilted quads on the page. None, and left out likewise, while `rectify` is None.
+    # `unrolled` (RecognitionPredictor.unroll): whether the line's pixels were unrolled along its centre line; its characters' polygons
+    # are then tilted quads that follow the bend. None, and left out likewise, while `unroll` is None.
     # `variant` (RecognitionPredictor.reread): the picture the line's reading comes from, "original" | "contrast" | "rot90" | "rot180" |
     # "rot270"; `readings`: every candidate of a line that was re-read, the first reading first, then the variants in that order; None
     # for a line that was read once. Both None, and left out likewise, while `reread` is None.
@@ -136,6 +138,7 @@ class TextLine(BaseChar):
         lexicon_index: Optional[int] = Field(default=None, exclude_if=lambda v: v is None)
         boost_matches: Optional[List[int]] = Field(default=None, exclude_if=lambda v: v is None)
         rectified: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
+        unrolled: Optional[bool] = Field(default=None, exclude_if=lambda v: v is None)
         variant: Optional[str] = Field(default=None, exclude_if=lambda v: v is None)
         readings: Optional[List[LineReading]] = Field(default=None, exclude_if=lambda v: v is None)
     else:
@@ -145,6 +148,7 @@ class TextLine(BaseChar):
         lexicon_index: Optional[int] = None
         boost_matches: Optional[List[int]] = None
         rectified: Optional[bool] = None
+        unrolled: Optional[bool] = None
         variant: Optional[str] = None
         readings: Optional[List[LineReading]] = None
 
@@ -163,6 +167,8 @@ class TextLine(BaseChar):
                 d.pop("boost_matches", None)
             if self.rectified is None:
                 d.pop("rectified", None)
+            if self.unrolled is None:
+                d.pop("unrolled", None)
             if self.variant is None:
                 d.pop("variant", None)
             if self.readings is None:
