@@ -1,14 +1,15 @@
 """DetectionPredictor: drop-in for surya.detection.DetectionPredictor on MI355X.
 
 Same call signature / result schema (surya/detection/__init__.py:22-48, detection/schema.py:12-17). The model forward,
-sigmoid and x4 upsample run in libsurya_amd.so (HipDetModel); tall-page splitting, PIL resizing and heat-map -> box
-post-processing stay on the host as in the reference. No CPU fallback for the model.
+sigmoid and x4 upsample run in libsurya_amd.so (HipDetModel). This file holds the sources of page maps (`batch_heatmaps`, `_tiled_batches`,
+and `batch_detection`, the reference layout of the checker arm); what turns a page map into a result is detection/pagepost.py. No CPU
+fallback for the model.
 """
 from __future__ import annotations
 
 import math
 import os
-from concurrent.futures import ThreadPoolExecutor
+from itertools import accumulate
 from typing import Generator, List, Tuple
 
 import numpy as np
@@ -19,11 +20,10 @@ from ..common.imageops import copy_pool, page_pixels, parallel_copy
 from ..common.predictor import BasePredictor, ModelLoader, gc_paused
 from ..config import DetConfig, det_config
 from ..settings import settings
-from .heatmap import TextDetectionResult, detect_boxes, parallel_get_boxes, result_from_device_boxes
+from .heatmap import TextDetectionResult
 from ..common.pil_resample import plan_chain as plan_resize
-from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetCenterlines, HipDetModel, HipDetPost, HipDetSkew, HipDetTiler
-from . import centerline as centerline_rule
-from . import skew as skew_rule
+from .model import CUT_DESC, STITCH_DESC, DeviceResampler, HipDetModel, HipDetTiler
+from .pagepost import PageGroup, PagePost, stitched_map_images, strip_groups, strip_map_images
 from .centerline import Centerlines  # noqa: F401  (what `DetectionPredictor.centerlines` takes)
 from .skew import SkewEstimate, straighten  # noqa: F401  (SkewEstimate: what `DetectionPredictor.skew` takes)
 from .tiling import DetTiling, check_tiling, page_plan  # noqa: F401  (DetTiling: what `DetectionPredictor.tiling` takes)
@@ -135,6 +135,39 @@ class DetectionModelLoader(ModelLoader):
         return p
 
 
+def pack_greedy(counts, batch_size):
+    """The reference's greedy packing by tile count (surya/detection/__init__.py:77-90): page indices per batch, in order; a new batch
+    starts when the next page would overflow it, none is empty, and a page with more tiles than the batch goes alone."""
+    batches, filled = [], 0
+    for i, n in enumerate(counts):
+        if not batches or filled + n > batch_size:
+            batches.append([])
+            filled = 0
+        batches[-1].append(i)
+        filled += n
+    return batches
+
+
+def stage_pixels(px, tail=0):
+    """ONE pinned staging buffer for the pixel arrays of a batch, hence ONE H2D copy (a pinned allocation + copy + transfer per page cost
+    ~4.7 ms of host time each: 210 pages/s on letter pages): every array at a 256-byte aligned offset, `tail` more bytes behind them for
+    what else travels with the batch. Returns (buffer, offsets; the last one is where the tail starts)."""
+    offs = [0, *accumulate((int(a.nbytes) + 255) & ~255 for a in px)]
+    stage = torch.empty(offs[-1] + tail, dtype=torch.uint8, pin_memory=True)
+    sv = stage.numpy()
+    parallel_copy([sv[o: o + a.nbytes].reshape(a.shape) for a, o in zip(px, offs)], px)
+    return stage, offs
+
+
+def run_chain(resampler, src, steps, out):
+    """The steps of common/pil_resample.plan_chain on the device: [thumbnail's box reduction,] thumbnail's size, then the final size into `out`."""
+    for i, st in enumerate(steps):
+        if st[0] == "reduce":
+            src = resampler.reduce(src, st[1], st[2])
+        else:
+            src = resampler.resize(src, st[1], out=out if i == len(steps) - 1 else None, box=st[2])
+
+
 def _one_batch_ahead(launched, finish, eager_first=False):
     """One batch in flight ahead of the one being read: `launched` prepares (PIL convert / resize, pinned staging) and launches batch
     i + 1 while the GPU still works on batch i, whose boxes `finish` only then waits for. eager_first: the FIRST batch is handed over
@@ -210,114 +243,23 @@ class DetectionPredictor(BasePredictor):
     # per page of the last call with `centerlines` set: {"n_boxes" (kept components of the map), "n_curved" (those that got a centre line)}
     last_centerlines: list = []
 
-    def _check_centerlines(self):
-        """The refusals of `centerlines` before any device work; returns the checked Centerlines, or None when off."""
-        if self.centerlines is None:
-            return None
-        cli = centerline_rule.check_centerlines(self.centerlines)
-        self.last_centerlines = []
-        return cli
+    def _op(self, name, cls):
+        """The device op kept under `name`, created at its first use: a call that never needs it allocates nothing for it."""
+        op = getattr(self, name, None)
+        if op is None:
+            op = cls(self.model.device)
+            setattr(self, name, op)
+        return op
 
-    def _cl_launch(self, cli, maps):
-        """surya_det_centerlines behind the surya_det_boxes launch that just took `maps`."""
-        if cli is None:
-            return None
-        if getattr(self, "_cl_op", None) is None:
-            self._cl_op = HipDetCenterlines(self.model.device)
-        return self._cl_op.launch(self._post, maps, cli.knots)
-
-    def _cl_collect(self, cpending, got):
-        """The profiles of one launch, per page (None when off). got: what HipDetPost.collect returned for the same launch."""
-        if cpending is None:
-            return [None] * len(got)
-        return self._cl_op.collect(cpending, [len(bx) for bx, _ in got], (settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD))
-
-    @staticmethod
-    def _cl_result(cli, prof, bx, cf, psize, size, hi=None, ai=None):
-        """result_from_device_boxes with the centre lines of one page's profile attached; returns (result, its last_centerlines entry)."""
-        if cli is None:
-            return result_from_device_boxes(bx, cf, psize, size, hi, ai), None
-        info = {}
-
-        def attach(bboxes):
-            info["n_boxes"], info["n_curved"] = len(bboxes), centerline_rule.attach(bboxes, prof, cli)
-        return result_from_device_boxes(bx, cf, psize, size, hi, ai, attach=attach), info
-
-    def _check_skew(self, images):
-        """The refusals of `skew` before any device work; returns the estimate's (candidate angles, mask threshold), or None when off."""
-        if self.skew is None:
-            return None
-        est = skew_rule.check_skew(self.skew)
-        P = self.processor.size["height"]
-        pw = self.processor.size["width"]
-        geo = []
-        for im in images:
-            w, h = im.size
-            if self.tiling is not None:
-                geo.append(((w, h), page_plan(w, h, P, self.tiling).map_size))
-            else:
-                geo.append(((w, h), (pw, h if get_total_splits((w, h), P) > 1 else P)))
-        skew_rule.check_skew(est, geo)
-        self.last_skew = []
-        return skew_rule.candidate_angles(est), float(settings.DETECTOR_BLANK_THRESHOLD if est.threshold is None else est.threshold)
-
-    def _skew_launch(self, sk, maps, page_sizes, map_size):
-        """surya_det_skew on the maps a surya_det_boxes launch just took: every page its own table from the one candidate list."""
-        if getattr(self, "_skew_op", None) is None:
-            self._skew_op = HipDetSkew(self.model.device)
-        tables = np.stack([skew_rule.coeff_table(sk[0], ps, map_size) for ps in page_sizes])
-        return self._skew_op.launch(maps, tables, sk[1])
-
-    def _skew_set(self, sk, result, scores, n_text, map_size):
-        """The choice (host, float64) from one page's scores, onto its result and into last_skew."""
-        angle, conf = skew_rule.choose(scores, int(n_text), sk[0], self.skew.step, self.skew.min_pixels)
-        result.skew, result.skew_confidence = angle, conf
-        return {"angle": angle, "confidence": conf, "n_text": int(n_text), "map_size": (int(map_size[0]), int(map_size[1]))}
-
-    def _skew_host(self, sk, result, heat, page_size, map_size):
-        """The checker arm (DETECTOR_POSTPROCESS_HOST): the numpy reference on the downloaded map."""
-        scores, n_text = skew_rule.skew_scores(heat, sk[1], skew_rule.coeff_table(sk[0], page_size, map_size))
-        return self._skew_set(sk, result, scores, n_text, map_size)
+    def _map_geometry(self, images):
+        """(page size, size of the map its boxes come from) of every page: stitched under `tiling`, else the processor's square or a tall page's strips."""
+        P, pw = self.processor.size["height"], self.processor.size["width"]
+        if self.tiling is not None:
+            return [(im.size, page_plan(im.size[0], im.size[1], P, self.tiling).map_size) for im in images]
+        return [(im.size, (pw, im.size[1] if get_total_splits(im.size, P) > 1 else P)) for im in images]
 
     def _detect(self, images: List[Image.Image], batch_size=None, include_maps=False) -> List[TextDetectionResult]:
-        if self.tiling is not None:
-            check_tiling(self.tiling, self.processor.size["height"])
-        sk = self._check_skew(images)
-        cli = self._check_centerlines()
-        if self.tiling is not None and not self.device_postprocess:
-            return self._detect_tiled_host(images, batch_size, include_maps, sk, cli)
-        if self.device_postprocess:
-            return self._detect_device(images, batch_size, include_maps)
-        gen = self.batch_detection(images, batch_size=batch_size)
-        futures = []
-        workers = max(1, min(settings.DETECTOR_POSTPROCESSING_CPU_WORKERS, len(images)))
-
-        def one(p, s):
-            info = None
-            if cli is None:
-                r = parallel_get_boxes(p, s, include_maps)
-            else:                                          # the same steps (heatmap.py), with the profile of the same map in between
-                heat = p[0] if p[0].dtype == np.float32 else p[0].astype(np.float32)
-                tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
-                imgs = [Image.fromarray((m * 255).astype(np.uint8)) for m in p[:2]] if include_maps else [None, None]
-                r, info = self._cl_result(cli, centerline_rule.profile_page(heat, tt, lt, cli.knots), *detect_boxes(heat, tt, lt),
-                                          [heat.shape[1], heat.shape[0]], s, *imgs)
-            return r, (None if sk is None else self._skew_host(sk, r, p[0], s, (p[0].shape[1], p[0].shape[0]))), info
-
-        if len(images) >= settings.DETECTOR_MIN_PARALLEL_THRESH:
-            with ThreadPoolExecutor(max_workers=workers) as ex:
-                for preds, sizes in gen:
-                    futures.extend(ex.submit(one, p, s) for p, s in zip(preds, sizes))
-            out = [f.result() for f in futures]
-        else:
-            out = []
-            for preds, sizes in gen:
-                out.extend(one(p, s) for p, s in zip(preds, sizes))
-        if sk is not None:
-            self.last_skew = [info for _, info, _ in out]
-        if cli is not None:
-            self.last_centerlines = [info for _, _, info in out]
-        return [r for r, _, _ in out]
+        return (self._detect_device if self.device_postprocess else self._detect_host)(images, batch_size, include_maps)
 
     def _detect_device(self, images, batch_size=None, include_maps=False) -> List[TextDetectionResult]:
         return [r for batch in self._iter_detect_device(images, batch_size, include_maps) for r in batch]
@@ -335,146 +277,41 @@ class DetectionPredictor(BasePredictor):
         """eager_first: hand the FIRST batch over as soon as its boxes exist instead of after the second batch has been prepared and
         launched -- a consumer that starts other device work from it (the streamed recognise call) gets going one host preparation
         (~10 ms per 16 pages) earlier, at the price of that much overlap inside the detector."""
-        if self.tiling is not None:
-            check_tiling(self.tiling, self.processor.size["height"])
-        sk = self._check_skew(images)
-        cli = self._check_centerlines()
-        if getattr(self, "_post", None) is None:
-            self._post = HipDetPost(self.model.device)
-        tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
-        if self.tiling is not None:
-            yield from self._iter_detect_tiled(images, batch_size, include_maps, eager_first, sk, cli)
-            return
-
-        def finish(job):
-            """Results of one launched batch (waits for ITS event only)."""
-            out: List[TextDetectionResult] = []
-            jobs, n_pages, tiles_of, split_heights, sizes, heat, pw = job
-            res, skews = {}, {}
-            for pages_, pending, psizes, spending, cpending in jobs:
-                got = self._post.collect(pending)
-                for pg, (bx, cf), psize, prof in zip(pages_, got, psizes, self._cl_collect(cpending, got)):
-                    res[pg] = (bx, cf, psize, prof)
-                if spending is not None:
-                    for pg, sc, nt in zip(pages_, *self._skew_op.collect(spending)):
-                        skews[pg] = (sc, nt)
-            maps = heat.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
-            for pg in range(n_pages):
-                bx, cf, psize, prof = res[pg]
-                hi = ai = None
-                if include_maps:
-                    # the reference keeps a page's FIRST tile whole -- an unsplit page shorter than the processor height still gets
-                    # its full map -- and trims only the later strips of a split page to their valid rows (detection/__init__.py:134-151)
-                    rows = [maps.shape[2] if k == 0 else split_heights[t] for k, t in enumerate(tiles_of[pg])]
-                    hm = np.vstack([maps[t, 0, :r] for t, r in zip(tiles_of[pg], rows)])
-                    am = np.vstack([maps[t, 1, :r] for t, r in zip(tiles_of[pg], rows)])
-                    hi, ai = Image.fromarray((hm * 255).astype(np.uint8)), Image.fromarray((am * 255).astype(np.uint8))
-                r, info = self._cl_result(cli, prof, bx, cf, list(psize), sizes[pg], hi, ai)
-                out.append(r)
-                if cli is not None:
-                    self.last_centerlines.append(info)
-                if sk is not None:
-                    self.last_skew.append(self._skew_set(sk, out[-1], *skews[pg], psize))
-            return out
+        post = PagePost(self, images)                      # every refusal of the call, before any device work
 
         def launched():
-            for heat, split_index, split_heights, sizes in self.batch_heatmaps(images, batch_size):
-                ph, pw = heat.shape[2], heat.shape[3]
-                n_pages = split_index[-1] + 1
-                tiles_of = [[i for i, k in enumerate(split_index) if k == page] for page in range(n_pages)]
-                whole = [page for page in range(n_pages) if len(tiles_of[page]) == 1]
-                jobs = []
-                if whole:
-                    sel = heat if len(whole) == heat.shape[0] else heat[[tiles_of[pg][0] for pg in whole]].contiguous()
-                    jobs.append((whole, self._post.launch(sel, tt, lt), [(pw, ph)] * len(whole),
-                                 None if sk is None else self._skew_launch(sk, sel, [sizes[pg] for pg in whole], (pw, ph)),
-                                 self._cl_launch(cli, sel)))
-                # tall pages: strips re-assembled on the device (:134-151); pages of equal height share ONE post-processing call (a call per
-                # page was 17 launches + a D2H each: 16 letter pages spent 40 of their 77 ms there, tools/hostbench/det_letter_profile.py)
-                by_height = {}
-                for pg in range(n_pages):
-                    if len(tiles_of[pg]) > 1:
-                        by_height.setdefault(sum(split_heights[t] for t in tiles_of[pg]), []).append(pg)
-                for hf, pgs in by_height.items():
-                    full = torch.empty((len(pgs), hf, pw), dtype=heat.dtype, device=heat.device)
-                    for i, pg in enumerate(pgs):
-                        r0 = 0
-                        for t in tiles_of[pg]:
-                            full[i, r0: r0 + split_heights[t]] = heat[t, 0, : split_heights[t]]
-                            r0 += split_heights[t]
-                    jobs.append((pgs, self._post.launch(full, tt, lt), [(pw, hf)] * len(pgs),
-                                 None if sk is None else self._skew_launch(sk, full, [sizes[pg] for pg in pgs], (pw, hf)),
-                                 self._cl_launch(cli, full)))
-                yield (jobs, n_pages, tiles_of, split_heights, sizes, heat, pw)
+            if self.tiling is not None:
+                for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
+                    yield post.launch(groups, sizes, stitched_map_images(groups) if include_maps else None)
+            else:
+                for heat, split_index, split_heights, sizes in self.batch_heatmaps(images, batch_size):
+                    yield post.launch(strip_groups(heat, split_index, split_heights), sizes,
+                                      strip_map_images(heat, split_index, split_heights) if include_maps else None)
 
-        yield from _one_batch_ahead(launched(), finish, eager_first)
+        yield from _one_batch_ahead(launched(), post.finish, eager_first)
 
-    # ------------------------------------------------------------------------------------------------------------ tiled detection
-    def _iter_detect_tiled(self, images, batch_size, include_maps, eager_first, sk=None, cli=None):
-        """_iter_detect_device under `tiling`: the same one-batch-ahead hand-over, a page's boxes from its stitched map."""
-        tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
+    def _detect_host(self, images, batch_size=None, include_maps=False) -> List[TextDetectionResult]:
+        """The checker arm (DETECTOR_POSTPROCESS_HOST): the page maps D2H, heatmap.py and the numpy references of the extras on them. Without
+        `tiling` the maps come from `batch_detection`, the reference-layout path that shares nothing with `batch_heatmaps`."""
+        post = PagePost(self, images)                      # every refusal of the call, before any device work
 
-        def finish(job):
-            groups, sizes, pendings, spendings, cpendings = job
-            out = [None] * len(sizes)
-            infos = [None] * len(sizes)
-            cinfos = [None] * len(sizes)
-            for (ks, maps, (mw, mh)), pending, spending, cpending in zip(groups, pendings, spendings, cpendings):
-                host = maps.cpu().numpy() if include_maps else None      # callers that want the maps pay for their D2H
-                got = self._post.collect(pending)
-                for i, (k, (bx, cf), prof) in enumerate(zip(ks, got, self._cl_collect(cpending, got))):
-                    out[k], cinfos[k] = self._cl_result(cli, prof, bx, cf, [mw, mh], sizes[k], *self._map_images(host, i, mw, mh))
-                if spending is not None:
-                    for k, sc, nt in zip(ks, *self._skew_op.collect(spending)):
-                        infos[k] = self._skew_set(sk, out[k], sc, nt, (mw, mh))
-            if sk is not None:
-                self.last_skew.extend(infos)
-            if cli is not None:
-                self.last_centerlines.extend(cinfos)
-            return out
-
-        def launched():
+        def pages():
+            if self.tiling is None:
+                for preds, sizes in self.batch_detection(images, batch_size=batch_size):
+                    for p, size in zip(preds, sizes):
+                        yield p[0], p[1] if include_maps else None, (p[0].shape[1], p[0].shape[0]), size
+                return
             for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
-                # pages of equal map size share ONE post-processing call, as tall pages of equal height do; what reads a call's workspace
-                # (the centre lines) goes right behind it, before the next call rewrites it
-                pendings, spendings, cpendings = [], [], []
-                for ks, maps, ms in groups:
-                    pendings.append(self._post.launch(maps, tt, lt))
-                    cpendings.append(self._cl_launch(cli, maps))
-                    spendings.append(None if sk is None else self._skew_launch(sk, maps, [sizes[k] for k in ks], ms))
-                yield groups, sizes, pendings, spendings, cpendings
+                batch = [None] * len(sizes)
+                for ks, maps, map_size in groups:
+                    host = maps.cpu().numpy()
+                    for i, k in enumerate(ks):
+                        batch[k] = (host[i, 0], host[i, 1] if include_maps else None, map_size, sizes[k])
+                yield from batch
 
-        yield from _one_batch_ahead(launched(), finish, eager_first)
+        return post.host(pages(), len(images))
 
-    def _detect_tiled_host(self, images, batch_size, include_maps, sk=None, cli=None):
-        """The checker arm under `tiling` (DETECTOR_POSTPROCESS_HOST): the stitched maps D2H, heatmap.py on them."""
-        tt, lt = settings.DETECTOR_TEXT_THRESHOLD, settings.DETECTOR_BLANK_THRESHOLD
-        out = []
-        for groups, sizes in self._tiled_batches(images, batch_size, 2 if include_maps else 1):
-            res, infos, cinfos = [None] * len(sizes), [None] * len(sizes), [None] * len(sizes)
-            for ks, maps, (mw, mh) in groups:
-                host = maps.cpu().numpy()
-                for i, k in enumerate(ks):
-                    boxes, confs = detect_boxes(host[i, 0], tt, lt)
-                    prof = None if cli is None else centerline_rule.profile_page(host[i, 0], tt, lt, cli.knots)
-                    res[k], cinfos[k] = self._cl_result(cli, prof, boxes, confs, [mw, mh], sizes[k],
-                                                        *self._map_images(host if include_maps else None, i, mw, mh))
-                    if sk is not None:
-                        infos[k] = self._skew_host(sk, res[k], host[i, 0], sizes[k], (mw, mh))
-            if sk is not None:
-                self.last_skew.extend(infos)
-            if cli is not None:
-                self.last_centerlines.extend(cinfos)
-            out.extend(res)
-        return out
-
-    @staticmethod
-    def _map_images(host, i, mw, mh):
-        """include_maps under `tiling`: the stitched valid region (mh x mw) of both planes, as the reference's images."""
-        if host is None:
-            return None, None
-        return tuple(Image.fromarray((host[i, pl, :mh, :mw] * 255).astype(np.uint8)) for pl in (0, 1))
-
+    # ------------------------------------------------------------------------------------------------------------ the sources of page maps
     def _tiled_batches(self, images, batch_size, planes):
         """Upload -> [scale] -> per forward: cut, model, stitch (detection/tiling.py). Yields per batch of pages (groups, page sizes), groups =
         [(pages of the batch, their maps cuda fp32 [n, planes, mh, round_up(mw, 4)], (mw, mh))]: pages of equal map size lie in one tensor.
@@ -483,27 +320,14 @@ class DetectionPredictor(BasePredictor):
         P = self.processor.size["height"]
         assert self.processor.size["width"] == P
         tiling = check_tiling(self.tiling, P)
-        if batch_size is None:
-            batch_size = self.get_batch_size()
         mb = self.model.max_batch
-        batch_size = min(batch_size, mb)
+        batch_size = min(self.get_batch_size() if batch_size is None else batch_size, mb)
         plans = [page_plan(im.size[0], im.size[1], P, tiling) for im in images]
         self.last_tiling = [{"size": pl.map_size, "grid": pl.grid, "tiles": pl.n_tiles} for pl in plans]
-        batches, cur, cur_n = [], [], 0
-        for i, pl in enumerate(plans):                             # greedy packing by tile count, as strips are packed
-            if cur_n + pl.n_tiles > batch_size:
-                if cur:
-                    batches.append(cur)
-                cur, cur_n = [], 0
-            cur.append(i)
-            cur_n += pl.n_tiles
-        if cur:
-            batches.append(cur)
         paths = self.last_resize_paths = {"device": 0, "host": 0, "ready": 0}
-        if getattr(self, "_tiler", None) is None:
-            self._tiler = HipDetTiler(self.model.device)
+        tiler = self._op("_tiler", HipDetTiler)
         dev = self.model.device
-        for idxs in batches:
+        for idxs in pack_greedy([pl.n_tiles for pl in plans], batch_size):      # by tile count, as strips are packed
             pages = [images[j] if images[j].mode == "RGB" else images[j].convert("RGB") for j in idxs]
             bplans = [plans[j] for j in idxs]
             # how a page becomes its scaled page S: [] = it is S, a list of steps = on the device, None = Pillow on the host
@@ -517,13 +341,10 @@ class DetectionPredictor(BasePredictor):
             px = list(copy_pool().map(pixels, range(len(pages)))) if len(pages) > 1 else [pixels(0)]
             # ONE pinned staging buffer and ONE H2D copy per batch: the pages whole, then the two descriptor tables
             n_tiles = sum(pl.n_tiles for pl in bplans)
-            sizes_b = [int(a.nbytes) for a in px]
-            offs = np.concatenate([[0], np.cumsum([(b + 255) & ~255 for b in sizes_b])]).astype(np.int64)
-            cut_off = int(offs[-1])
+            stage, offs = stage_pixels(px, n_tiles * (CUT_DESC.itemsize + STITCH_DESC.itemsize))
+            cut_off = offs[-1]
             stitch_off = cut_off + n_tiles * CUT_DESC.itemsize
-            stage = torch.empty(stitch_off + n_tiles * STITCH_DESC.itemsize, dtype=torch.uint8, pin_memory=True)
             sv = stage.numpy()
-            parallel_copy([sv[int(o): int(o) + b].reshape(a.shape) for a, o, b in zip(px, offs[:-1], sizes_b)], px)
             dev_stage = torch.empty(stage.numel(), dtype=torch.uint8, device=dev)
             scaled = [torch.empty((pl.map_size[1], pl.map_size[0], 4), dtype=torch.uint8, device=dev) if ch else None
                       for pl, ch in zip(bplans, chains)]
@@ -533,7 +354,7 @@ class DetectionPredictor(BasePredictor):
             groups, map_of = [], {}
             for (mw, mh), ks in by_size.items():
                 maps = torch.empty((len(ks), planes, mh, (mw + 3) & ~3), dtype=torch.float32, device=dev)
-                groups.append((ks, maps, (mw, mh)))
+                groups.append(PageGroup(ks, maps, (mw, mh)))
                 for i, k in enumerate(ks):
                     map_of[k] = maps[i].data_ptr()
             # the tiles of the batch in page order, row-major inside a page; a tile's index is its place in ITS forward
@@ -542,7 +363,7 @@ class DetectionPredictor(BasePredictor):
             for k, pl in enumerate(bplans):
                 mw, mh = pl.map_size
                 src = ((scaled[k].data_ptr(), mw, mh, 4) if scaled[k] is not None
-                       else (dev_stage.data_ptr() + int(offs[k]), px[k].shape[1], px[k].shape[0], px[k].shape[2]))
+                       else (dev_stage.data_ptr() + offs[k], px[k].shape[1], px[k].shape[0], px[k].shape[2]))
                 for x0, y0, (ox0, ox1), (oy0, oy1) in pl.tiles():
                     cut[t] = (*src, x0, y0, t % mb)
                     st[t] = (map_of[k], pl.pitch, mh * pl.pitch, t % mb, ox0 - x0, oy0 - y0, ox1 - ox0, oy1 - oy0, ox0, oy0, planes,
@@ -553,20 +374,13 @@ class DetectionPredictor(BasePredictor):
             dev_stage.copy_(stage, non_blocking=True)
             for k, ch in enumerate(chains):
                 if ch:
-                    if getattr(self, "_resampler", None) is None:
-                        self._resampler = DeviceResampler(dev)
-                    img = dev_stage[int(offs[k]): int(offs[k]) + sizes_b[k]].view(px[k].shape)
-                    for i, step in enumerate(ch):              # [thumbnail's box reduction,] thumbnail's size, then the scaled size
-                        if step[0] == "reduce":
-                            img = self._resampler.reduce(img, step[1], step[2])
-                        else:
-                            img = self._resampler.resize(img, step[1], out=scaled[k] if i == len(ch) - 1 else None, box=step[2])
+                    run_chain(self._op("_resampler", DeviceResampler), dev_stage[offs[k]: offs[k] + px[k].nbytes].view(px[k].shape), ch, scaled[k])
             for s in range(0, n_tiles, mb):                        # a page with more tiles than the batch: chunks of max_batch, stitched as they come
                 n = min(mb, n_tiles - s)
                 tiles = torch.empty((n, P, P, 4), dtype=torch.uint8, device=dev)
-                self._tiler.cut(dev_stage[cut_off + s * CUT_DESC.itemsize:], n, tiles)
+                tiler.cut(dev_stage[cut_off + s * CUT_DESC.itemsize:], n, tiles)
                 heat = self.model.forward_u8(tiles, self.processor.image_mean, self.processor.image_std)
-                self._tiler.stitch(heat, dev_stage[stitch_off + s * STITCH_DESC.itemsize:], n)
+                tiler.stitch(heat, dev_stage[stitch_off + s * STITCH_DESC.itemsize:], n)
             yield groups, [images[j].size for j in idxs]
 
     def resize_image(self, img: Image.Image, size=None) -> np.ndarray:
@@ -590,24 +404,11 @@ class DetectionPredictor(BasePredictor):
         """Split -> prepare_image -> model, like batch_detection (surya/detection/__init__.py:64-132), but the heat maps stay
         on the device: yields (heat cuda fp32 [tiles, labels, H, W], page index of each tile, valid rows of each tile, sizes)."""
         assert all(isinstance(im, Image.Image) for im in images)
-        if batch_size is None:
-            batch_size = self.get_batch_size()
-        batch_size = min(batch_size, self.model.max_batch)
+        batch_size = min(self.get_batch_size() if batch_size is None else batch_size, self.model.max_batch)
         ph = self.processor.size["height"]
         orig_sizes = [im.size for im in images]
-        splits = [get_total_splits(s, ph) for s in orig_sizes]
-        batches, cur, cur_n = [], [], 0
-        for i in range(len(images)):                               # greedy packing by tile count (:77-90)
-            if cur_n + splits[i] > batch_size:
-                if cur:
-                    batches.append(cur)
-                cur, cur_n = [], 0
-            cur.append(i)
-            cur_n += splits[i]
-        if cur:
-            batches.append(cur)
         paths = self.last_resize_paths = {"device": 0, "host": 0, "ready": 0}
-        for idxs in batches:
+        for idxs in pack_greedy([get_total_splits(s, ph) for s in orig_sizes], batch_size):
             # the device path only READS the pages (zero-copy pixel views, resize on the device): no defensive copies of pages that
             # already are RGB (convert() and split_image() each copied 4 MB per 1024^2 page under the GIL; the Pillow resize of
             # the host path, which works in place, copies for itself in resize_image)
@@ -626,13 +427,12 @@ class DetectionPredictor(BasePredictor):
             # or DETECTOR_RESIZE_HOST=1 asks for the host path; rescale + normalise happen in the model's first kernel
             pw = self.processor.size["width"]
             plans = [None if not self.device_resize else plan_resize(p_.size[0], p_.size[1], (pw, ph)) for p_ in parts]
-            pool = copy_pool()
             # pixels of every part: Pillow's own memory where it can export it (page_pixels), the Pillow double resize for the parts the
             # device path does not take; both release the GIL in their C loops, so the parts of a batch are prepared side by side
-            if len(parts) > 1:
-                px = list(pool.map(lambda k: self.resize_image(parts[k]) if plans[k] is None else page_pixels(parts[k]), range(len(parts))))
-            else:
-                px = [self.resize_image(parts[k]) if plans[k] is None else page_pixels(parts[k]) for k in range(len(parts))]
+
+            def pixels(k):
+                return self.resize_image(parts[k]) if plans[k] is None else page_pixels(parts[k])
+            px = list(copy_pool().map(pixels, range(len(parts)))) if len(parts) > 1 else [pixels(0)]
             # RGBX views of PIL's own memory where it can export them (page_pixels), else repacked RGB; one stride per batch
             ready = [k for k, pl in enumerate(plans) if pl is None or not pl]          # already at the processor size
             for k, pl in enumerate(plans):
@@ -644,53 +444,23 @@ class DetectionPredictor(BasePredictor):
             dev_batch = host.to(self.model.device, non_blocking=True)
             todo = [k for k, pl in enumerate(plans) if pl]
             if todo:
-                # the parts that need the double LANCZOS resize: ONE pinned staging buffer and ONE H2D copy for the batch (a pinned
-                # allocation + copy + transfer per page cost ~4.7 ms of host time each: 210 pages/s on letter pages), then the resize
-                # passes part by part on the device
-                if getattr(self, "_resampler", None) is None:
-                    self._resampler = DeviceResampler(self.model.device)
-                sizes_b = [int(px[k].nbytes) for k in todo]
-                offs_b = np.concatenate([[0], np.cumsum([(b + 255) & ~255 for b in sizes_b])]).astype(np.int64)
-                stage = torch.empty(int(offs_b[-1]), dtype=torch.uint8, pin_memory=True)
-                sv = stage.numpy()
-                parallel_copy([sv[int(o): int(o) + b].reshape(px[k].shape) for k, o, b in zip(todo, offs_b[:-1], sizes_b)],
-                              [px[k] for k in todo])
+                # the parts that need the double LANCZOS resize: staged together, then the resize passes part by part on the device
+                stage, offs = stage_pixels([px[k] for k in todo])
                 dev_stage = stage.to(self.model.device, non_blocking=True)
-                for k, o, b in zip(todo, offs_b[:-1], sizes_b):
-                    cur = dev_stage[int(o): int(o) + b].view(px[k].shape)
-                    pl = plans[k]
-                    for i, st in enumerate(pl):                # [thumbnail's box reduction,] thumbnail's size, then the processor size
-                        if st[0] == "reduce":
-                            cur = self._resampler.reduce(cur, st[1], st[2])
-                        else:
-                            cur = self._resampler.resize(cur, st[1], out=dev_batch[k] if i == len(pl) - 1 else None, box=st[2])
-            heat_parts = []
-            for s in range(0, len(parts), self.model.max_batch):            # a single page may exceed max_batch tiles
-                heat_parts.append(self.model.forward_u8(dev_batch[s: s + self.model.max_batch], self.processor.image_mean,
-                                                        self.processor.image_std))
+                for k, o in zip(todo, offs):
+                    run_chain(self._op("_resampler", DeviceResampler), dev_stage[o: o + px[k].nbytes].view(px[k].shape), plans[k], dev_batch[k])
+            heat_parts = [self.model.forward_u8(dev_batch[s: s + self.model.max_batch], self.processor.image_mean, self.processor.image_std)
+                          for s in range(0, len(parts), self.model.max_batch)]      # a single page may exceed max_batch tiles
             heat = heat_parts[0] if len(heat_parts) == 1 else torch.cat(heat_parts, 0)
             yield heat, split_index, [min(h, ph) for h in split_heights], [orig_sizes[j] for j in idxs]
 
     def batch_detection(self, images: List, batch_size=None) -> Generator[Tuple[List[List[np.ndarray]], List[Tuple[int, int]]], None, None]:
         assert all(isinstance(im, Image.Image) for im in images)
-        if batch_size is None:
-            batch_size = self.get_batch_size()
-        batch_size = min(batch_size, self.model.max_batch)
+        batch_size = min(self.get_batch_size() if batch_size is None else batch_size, self.model.max_batch)
         nlab = self.model.cfg.num_labels
         ph = self.processor.size["height"]
         orig_sizes = [im.size for im in images]
-        splits = [get_total_splits(s, ph) for s in orig_sizes]
-        batches, cur, cur_n = [], [], 0
-        for i in range(len(images)):                               # greedy packing by tile count (:77-90)
-            if cur_n + splits[i] > batch_size:
-                if cur:
-                    batches.append(cur)
-                cur, cur_n = [], 0
-            cur.append(i)
-            cur_n += splits[i]
-        if cur:
-            batches.append(cur)
-        for idxs in batches:
+        for idxs in pack_greedy([get_total_splits(s, ph) for s in orig_sizes], batch_size):
             batch_images = [images[j].convert("RGB") for j in idxs]
             split_index, split_heights, parts = [], [], []
             for k, im in enumerate(batch_images):

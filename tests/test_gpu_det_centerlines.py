@@ -190,6 +190,38 @@ def test_together_with_skew(planted, pages):
     assert all(i["n_curved"] >= 2 for i in dev_info)
 
 
+@pytest.mark.parametrize("tiled", [False, True])
+def test_every_option_in_one_call_device_equals_host_checker(planted, pages, tiled):
+    """`skew`, `centerlines` and include_maps in one call, without and with `tiling`: four small pages of two sizes around a tall one, two
+    tiles to a batch, so that a batch holds two groups under `tiling` and the tall page runs alone in several forwards."""
+    from surya_amd.detection.predictor import DetTiling
+    from test_gpu_det_tiling import _same
+    sizes = [(256, 256), (200, 180), (300, 1500), (200, 180), (256, 256)]
+    ims = [pages[k] for k in sizes]
+    planted.skew, planted.centerlines = sk.SkewEstimate(), cl.Centerlines()
+    planted.tiling = DetTiling(scale=1.0, overlap=32) if tiled else None
+    try:
+        dev = planted(ims, batch_size=2, include_maps=True)
+        dev_info, dev_skew = list(planted.last_centerlines), list(planted.last_skew)
+        planted.device_postprocess = False
+        host = planted(ims, batch_size=2, include_maps=True)
+        host_info, host_skew = list(planted.last_centerlines), list(planted.last_skew)
+    finally:
+        planted.device_postprocess = True
+        planted.tiling = planted.skew = planted.centerlines = None
+    assert len(dev) == len(host) == len(dev_info) == len(dev_skew) == 5
+    _same(dev, host, atol=1e-6)
+    assert dev_skew == host_skew and dev_info == host_info
+    assert [i["map_size"] for i in dev_skew] == (sizes if tiled else [(P, P), (P, P), (P, 1500), (P, P), (P, P)])
+    for d, h, s, size in zip(dev, host, dev_skew, sizes):
+        assert (d.skew, d.skew_confidence) == (h.skew, h.skew_confidence) == (s["angle"], s["confidence"]) and d.skew is not None
+        assert [b.centerline for b in d.bboxes] == [b.centerline for b in h.bboxes]
+        assert [b.thickness for b in d.bboxes] == [b.thickness for b in h.bboxes]
+        for a, b in ((d.heatmap, h.heatmap), (d.affinity_map, h.affinity_map)):
+            assert a.size == b.size == (size if tiled else (P, 1500 if size[1] > P else P)) and np.array_equal(np.asarray(a), np.asarray(b))
+    assert sum(len(r.bboxes) for r in dev) >= 1 and all(i["n_curved"] >= 2 for i in dev_info)
+
+
 def test_iter_detect_and_the_streamed_call_carry_the_same_centre_lines(planted, pages):
     from test_gpu_predictors import make_rec_predictor
     ims = [pages[k] for k in SMALL + [(300, 1500)]]
