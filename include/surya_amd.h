@@ -264,6 +264,28 @@ int surya_rec_rectify(const uint8_t* pages, const void* descs, int n, uint8_t* o
 int surya_rec_unroll(const uint8_t* pages, const void* descs, int n, const double* tables, uint8_t* out, int pixel_stride, int max_w,
                      int max_h, void* stream);
 
+/* Flattening of curled pages through a warp mesh (surya_amd.detection.dewarp): n pages -> uint8 outputs of the pages' own sizes, each the
+ * rule of warp_mesh (surya_amd/common/imageops.py): the mesh of a w x h page with cell size `cell` is float64 [gh + 1][gw + 1][2],
+ * gw = ceil(w / cell), gh = ceil(h / cell), entry (j, i) the displacement (dx, dy) at output point (i * cell, j * cell), grid-line
+ * coordinates; output pixel (u, v) lies in cell (u / cell, v / cell), takes the bilinear form of the cell's four nodes at
+ * ((u + 0.5 - i * cell) / cell, (v + 0.5 - j * cell) / cell) -- top and bottom edge along x first, then along y, float64, no contraction --
+ * and samples its page at (u + 0.5 + dx) - 0.5, (v + 0.5 + dy) - 0.5 and from there on as surya_rec_rectify does: 4 x 4 cubic taps
+ * (a = -0.75) around floor() of that point, replicate border, float64 sums in tap order (horizontal pass first), rint, clamp to 0..255;
+ * uint8-equal to the host function. An output is written like a page (HWC, `pixel_stride` bytes per pixel, X = 0 with 4). pages, out,
+ * meshes: device; `out` may lie in the pages' allocation, in a disjoint range; meshes: doubles, 16-byte aligned. descs: HOST array of n
+ * descriptors
+ *   { int64 page_off; int32 w, h; int32 cell, reserved (0); int64 out_off (bytes into out);
+ *     int64 mesh_off (doubles into meshes, even: the page's [gh + 1][gw + 1][2]) }                        -- 40 bytes, C layout;
+ * they are copied into the launches' kernel arguments, so the array may be reused as soon as the call returns. max_w, max_h: the
+ * largest w / h of the call (grid sizing). SA_ERR_ARG, with nothing launched, when pixel_stride is not 3 or 4, n is negative, a pointer
+ * (pages, descs, meshes, out) is null, meshes is not 16-byte aligned, a size is non-positive or exceeds max_w / max_h, cell is not a
+ * multiple of 16 in 16 .. 1024, reserved is not 0, an offset is negative, a mesh_off is odd, (pixel_stride 4) pages, out, a page_off or
+ * an out_off is not a multiple of 4, or max_h needs more than 65535 tiles; n == 0 launches nothing. The VALUES of a mesh are not checked
+ * (check_mesh does that on the host): whatever they are, every read stays inside the page. What a descriptor addresses is not checked
+ * against the buffers: the caller keeps offsets and sizes inside them. Enqueue only. */
+int surya_warp_mesh(const uint8_t* pages, const void* descs, int n, const double* meshes, uint8_t* out, int pixel_stride, int max_w,
+                    int max_h, void* stream);
+
 /* Contrast adjustment of line crops (RecognitionPredictor.reread, LineRef.adjust): n crops of the pages -> their adjusted, padded
  * copies, each Pillow's ImageOps.autocontrast(crop, cutoff, preserve_tone=True, mask), byte for byte: 256 bins of the luma
  * (19595 R + 38470 G + 7471 B + 32768) >> 16 over the crop (has_poly: over the pixels of the 4-point polygon's mask, rasterised as

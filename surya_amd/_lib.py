@@ -194,6 +194,8 @@ def _bind_lay_ops(lib):
     lib.surya_rec_rectify.argtypes, lib.surya_rec_rectify.restype = [p, p, i, p, i, i, i, p], C.c_int
     # unrolling of bent lines along their centre lines, likewise (csrc/rec_unroll.h); `descs` is a host array, `tables` a device one
     lib.surya_rec_unroll.argtypes, lib.surya_rec_unroll.restype = [p, p, i, p, p, i, i, i, p], C.c_int
+    # flattening of whole pages through a warp mesh (csrc/page_warp.h; detection/dewarp.py); `descs` is a host array, `meshes` a device one
+    lib.surya_warp_mesh.argtypes, lib.surya_warp_mesh.restype = [p, p, i, p, p, i, i, i, p], C.c_int
     # contrast adjustment of line crops in front of surya_rec_preprocess (csrc/rec_adjust.h); `descs` is a host array
     lib.surya_rec_adjust_contrast.argtypes, lib.surya_rec_adjust_contrast.restype = [p, p, i, p, p, p, p, i, p], C.c_int
     # the recogniser's non-GEMM kernels alone (csrc/rec_ops.h): one entry per op, `dtype` first

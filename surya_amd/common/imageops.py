@@ -325,6 +325,104 @@ def curve_to_page(P, points, thickness) -> np.ndarray:
     return (C + (flat[:, 1] - out_h / 2)[:, None] * N).reshape(P.shape)
 
 
+# ------------------------------------------------------------------------------------------------ flattening through a mesh
+# A CURLED page is flattened through a warp mesh: a coarse grid of displacements over the OUTPUT, cell x cell pixels per cell. For a page
+# of W x H pixels gw = ceil(W / cell), gh = ceil(H / cell); the mesh is float64 [gh + 1, gw + 1, 2], entry (j, i) the displacement (dx, dy)
+# at output point (i * cell, j * cell), grid-line coordinates. An output point reads the page at itself plus the displacement, bilinear
+# inside a cell. The rule is stated here once; csrc/page_warp_core.h + page_warp.h restate warp_mesh per pixel (detection/dewarp.py fits
+# a mesh from text-line centre lines).
+MESH_MIN_CELL, MESH_MAX_CELL = 16, 1024          # csrc/page_warp_core.h: a multiple of 16, so that a 16 x 16 output tile lies in one cell
+
+
+def mesh_shape(size, cell: int):
+    """(gh + 1, gw + 1, 2) of the mesh of a page of size (W, H)."""
+    return -(-int(size[1]) // cell) + 1, -(-int(size[0]) // cell) + 1, 2
+
+
+def check_mesh(mesh, cell, size) -> np.ndarray:
+    """The refusals of a mesh for a page of size (W, H), by ValueError: `cell` not a multiple of 16 in 16 .. 1024; not a float64 array of
+    mesh_shape; non-finite entries; a mesh that FOLDS -- i * cell + dx not strictly increasing along i, or j * cell + dy not strictly
+    increasing along j (which is also what makes mesh_from_page converge: a displacement varies by less than a cell per cell)."""
+    if isinstance(cell, bool) or not isinstance(cell, (int, np.integer)) or not MESH_MIN_CELL <= cell <= MESH_MAX_CELL or cell % 16:
+        raise ValueError(f"mesh cell must be a multiple of 16 in {MESH_MIN_CELL} .. {MESH_MAX_CELL}, got {cell!r}")
+    if len(size) != 2 or min(int(size[0]), int(size[1])) <= 0:
+        raise ValueError(f"mesh: the page size is (W, H) with both positive, got {size!r}")
+    want = mesh_shape(size, int(cell))
+    if not isinstance(mesh, np.ndarray) or mesh.dtype != np.float64 or mesh.shape != want:
+        raise ValueError(f"mesh: a page of {int(size[0])} x {int(size[1])} at cell {cell} takes a float64 array of shape {want}, got "
+                         f"{getattr(mesh, 'dtype', type(mesh).__name__)} {getattr(mesh, 'shape', '')}")
+    if not np.isfinite(mesh).all():
+        raise ValueError("mesh: non-finite entries")
+    gx = np.arange(want[1], dtype=np.float64)[None, :] * cell + mesh[..., 0]
+    gy = np.arange(want[0], dtype=np.float64)[:, None] * cell + mesh[..., 1]
+    if not (np.diff(gx, axis=1) > 0).all() or not (np.diff(gy, axis=0) > 0).all():
+        raise ValueError("mesh: it folds (i * cell + dx must increase strictly along i, j * cell + dy along j)")
+    return mesh
+
+
+def _mesh_bilinear(m: np.ndarray, i, j, fx, fy) -> np.ndarray:
+    """THE bilinear form, per component: top = m[j, i] (1 - fx) + m[j, i + 1] fx, bot one row down, d = top (1 - fy) + bot fy."""
+    gx, gy = (1.0 - fx)[..., None], (1.0 - fy)[..., None]
+    fx, fy = fx[..., None], fy[..., None]
+    top = m[j, i] * gx + m[j, i + 1] * fx
+    bot = m[j + 1, i] * gx + m[j + 1, i + 1] * fx
+    return top * gy + bot * fy
+
+
+def warp_mesh(page_u8: np.ndarray, mesh, cell: int) -> np.ndarray:
+    """uint8 [H, W, C], the page's own size: output pixel (u, v) has X = u + 0.5, Y = v + 0.5, cell i = u // cell, j = v // cell,
+    fx = (X - i * cell) / cell, fy likewise, displacement d = _mesh_bilinear, and samples the page at sx = (X + dx) - 0.5,
+    sy = (Y + dy) - 0.5 (float64, in this order); from there warp_quad's words exactly (_sample_cubic). The VALUES of the mesh are not
+    judged here (check_mesh does that): far outside the page every tap is the border pixel."""
+    m = np.asarray(mesh, np.float64)
+    H, W, _ = page_u8.shape
+    assert m.shape == mesh_shape((W, H), cell), (m.shape, (W, H), cell)
+    u, v = np.arange(W, dtype=np.int64)[None, :], np.arange(H, dtype=np.int64)[:, None]
+    X, Y = u.astype(np.float64) + 0.5, v.astype(np.float64) + 0.5
+    i, j = u // cell, v // cell
+    fx = np.broadcast_to((X - (i * cell).astype(np.float64)) / float(cell), (H, W))
+    fy = np.broadcast_to((Y - (j * cell).astype(np.float64)) / float(cell), (H, W))
+    d = _mesh_bilinear(m, np.broadcast_to(i, (H, W)), np.broadcast_to(j, (H, W)), fx, fy)
+    sx = (X + d[..., 0]) - 0.5
+    sy = (Y + d[..., 1]) - 0.5
+    return _sample_cubic(page_u8, sx, sy, W, H)
+
+
+def _mesh_disp(points: np.ndarray, m: np.ndarray, cell: int) -> np.ndarray:
+    """The displacement at continuous output points [n, 2]: the cell index is floor(x / cell) clamped to the mesh, the fractions are not
+    clamped, so points outside the page extrapolate its edge cells."""
+    gh, gw = m.shape[0] - 1, m.shape[1] - 1
+    i = np.clip(np.floor(points[:, 0] / cell), 0, gw - 1).astype(np.int64)
+    j = np.clip(np.floor(points[:, 1] / cell), 0, gh - 1).astype(np.int64)
+    fx = (points[:, 0] - (i * cell).astype(np.float64)) / float(cell)
+    fy = (points[:, 1] - (j * cell).astype(np.float64)) / float(cell)
+    return _mesh_bilinear(m, i, j, fx, fy)
+
+
+def mesh_to_page(points, mesh, cell: int) -> np.ndarray:
+    """Points [..., 2] (x, y) of the flattened output, grid-line coordinates -> the page, float64: p + d(p), the map warp_mesh samples
+    through (an output pixel's centre lands where its value was read)."""
+    P = np.asarray(points, np.float64)
+    flat = P.reshape(-1, 2)
+    return (flat + _mesh_disp(flat, np.asarray(mesh, np.float64), cell)).reshape(P.shape)
+
+
+def mesh_from_page(points, mesh, cell: int) -> np.ndarray:
+    """The inverse of mesh_to_page by fixed-point iteration q <- p - d(q) from q = p, until the largest step is below 1e-9, for at most
+    50 rounds (a mesh that passes check_mesh contracts)."""
+    P = np.asarray(points, np.float64)
+    flat = P.reshape(-1, 2)
+    m = np.asarray(mesh, np.float64)
+    q = flat.copy()
+    for _ in range(50):
+        nq = flat - _mesh_disp(q, m, cell)
+        step = float(np.abs(nq - q).max()) if len(q) else 0.0
+        q = nq
+        if step < 1e-9:
+            break
+    return q.reshape(P.shape)
+
+
 def page_pixels(image) -> np.ndarray:
     """uint8 [H, W, 3 or 4] pixels of a PIL RGB page. Pillow stores RGB as 4 bytes per pixel; np.asarray(image) repacks that to
     3 (~2-3 ms per 1024^2 page under the GIL: 128 pages cost more host time than their detection forward pass). When Pillow can

@@ -15,6 +15,7 @@
 #include "rec_prep.h"
 #include "rec_rectify.h"
 #include "rec_unroll.h"
+#include "page_warp.h"
 #include "rec_adjust.h"
 
 namespace sa {
@@ -699,6 +700,12 @@ int surya_rec_unroll(const uint8_t* pages, const void* descs, int n, const doubl
                      int max_h, void* stream) {
     return sa::prep::unroll_run(pages, reinterpret_cast<const sa::prep::UnrollDesc*>(descs), n, tables, out, pixel_stride, max_w, max_h,
                                 (hipStream_t)stream);
+}
+
+int surya_warp_mesh(const uint8_t* pages, const void* descs, int n, const double* meshes, uint8_t* out, int pixel_stride, int max_w,
+                    int max_h, void* stream) {
+    return sa::prep::warp_mesh_run(pages, reinterpret_cast<const sa::pagewarp::MeshDesc*>(descs), n, meshes, out, pixel_stride, max_w, max_h,
+                                   (hipStream_t)stream);
 }
 
 int surya_rec_adjust_contrast(const uint8_t* pages, const void* descs, int n, uint8_t* out, uint8_t* mask_arena, void* work, int32_t* lo_hi,

@@ -31,6 +31,10 @@ assert RECTIFY_DESC.itemsize == 104, RECTIFY_DESC.itemsize
 UNROLL_DESC = np.dtype([("page_off", np.int64), ("page_w", np.int32), ("page_h", np.int32), ("out_w", np.int32), ("out_h", np.int32),
                         ("out_off", np.int64), ("table_off", np.int64)], align=True)
 assert UNROLL_DESC.itemsize == 40, UNROLL_DESC.itemsize
+# must match sa::pagewarp::MeshDesc (csrc/page_warp_core.h): one per flattened page, a HOST array like RECTIFY_DESC; mesh_off counts doubles
+MESH_DESC = np.dtype([("page_off", np.int64), ("w", np.int32), ("h", np.int32), ("cell", np.int32), ("reserved", np.int32),
+                      ("out_off", np.int64), ("mesh_off", np.int64)], align=True)
+assert MESH_DESC.itemsize == 40, MESH_DESC.itemsize
 # must match sa::adjust::AdjustDesc (csrc/adjust_core.h): one per contrast-adjusted line, a HOST array like RECTIFY_DESC
 ADJUST_DESC = np.dtype([("src_off", np.int64), ("src_w", np.int32), ("src_h", np.int32), ("x0", np.int32), ("y0", np.int32), ("w", np.int32),
                         ("h", np.int32), ("cutoff", np.int32), ("has_poly", np.int32), ("poly", np.float32, (8,)), ("out_off", np.int64),
